@@ -17,9 +17,22 @@ FLOP accounting: fw = 4*B*H*N^2*d, bw = 10*B*H*N^2*d; sof
     python bench.py --config c4 [--gpus N ...]     BASELINE.json configs[4]: FA-2 forward, bf16, B=128 H=16 N=4096 d=128, the
                                                    batch*head axis cut over the ranks (strong scaling), with the RCCL gather
 
-Extra objects on the JSON line:
+A plain run sets up, settles the clock, runs the W warm-up steps, times EXACTLY K steps and prints the line; `value`,
+`ms_per_step` and `pct_mfma_roofline` come from those K steps.  Everything else it can measure is behind --full.
+
+    --dump-outputs DIR   after the timed steps, what the last step computed, as float32 .npy files: o.npy, L.npy, dq.npy,
+                         dk.npy, dv.npy (rank 0).  At most 32 MiB in all: when the outputs are larger, the same fixed sample of
+                         (batch*head, query) rows of each (numpy default_rng(0), sorted); inputs are seeded, so two builds can be
+                         compared output for output.
+
+With --full, more objects on the JSON line (--no-* switch single ones off):
   roofline     -- dominant kernel (longest average launch): algorithmic FLOPs per launch / HIP-event duration,
                   against the dense bf16 MFMA peak (2.5 PFLOP/s, MI355X_MICROARCH.md).
+  kernels_ms   -- every kernel's launch duration, from an untimed pass of K steps with a HIP event at every kernel boundary;
+                  the timed block then carries the two events around the dominant kernel.
+  ms_per_step_blocks -- five more timed blocks of K steps after the first (`value` stays the first block's), and their median.
+  sustained_mfma_peak -- a bare bf16 MFMA loop on this device, >= 0.3 s.
+  gather_ms    -- --gpus N > 1: the RCCL all-gather of O, and the forward with the gather overlapped.
   cpu_baseline -- the oracle's NumPy fp32 vanilla attention fw+bw (oracle/attention_ref.py), timed on this host on a
                   bounded sample of heads of the same workload (rank 0, --gpus 1 only).
   vs_vanilla   -- the reference's own comparison (README.md:7, kernel_tests/test_flashattn_time.py) on this GPU: materialised-S
@@ -69,7 +82,41 @@ def parse():
                          "guarded default to its fp32-scaling kernels)")
     ap.add_argument("--phased", action="store_true",
                     help="profiling A/B only: run the phased (round-1 v5) kernels instead of the MFMA-slot ones")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-kernel breakdown and roofline, five more timed blocks, the sustained MFMA peak, the RCCL "
+                         "gather (--gpus N > 1), the CPU baseline and the vs_vanilla / variants / ablation tables")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; a fixed row sample when large)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.config != "metric":
+        ap.error("--dump-outputs: the metric config only")
+    return args
+
+
+DUMP_BYTES = 32 << 20   # --dump-outputs budget: o, L, dq, dk, dv together
+
+
+def dump_outputs(out_dir, BH, N, d, named):
+    """named: (name, fp32 device tensor of BH*N rows) pairs.  Writes DIR/<name>.npy; all rows when they fit DUMP_BYTES, else the
+    same seeded sample of rows from each, so two runs with the same arguments write the same elements."""
+    import numpy as np
+    import torch
+    rows = BH * N
+    row_bytes = sum(4 * (t.numel() // rows) for _, t in named)
+    keep = min(rows, DUMP_BYTES // row_bytes)
+    idx = None
+    if keep < rows:
+        sel = np.sort(np.random.default_rng(0).choice(rows, size=keep, replace=False))
+        idx = torch.from_numpy(sel).to(named[0][1].device)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in named:
+        flat = t.reshape(rows, -1)
+        if idx is not None:
+            flat = flat.index_select(0, idx)
+        a = flat.float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a.reshape(-1) if t.dim() == 2 else a)
 
 
 def with_scale_mode(opts, mode):
@@ -400,7 +447,7 @@ def main():
     # order, is asked of the library (fa_mi355x_plan runs its dispatch code with the launches skipped): kernel names as rocprofv3
     # shows them (fa::<name><...>).
     STAGES, K_FWD, K_DQ, K_DKDV = stage_plan(device_ops, BH, N, d, causal, args.dtype, OPTS, fwd, bwd, GUARDED)
-    breakdown = not args.no_kernel_breakdown
+    breakdown = args.full and not args.no_kernel_breakdown
 
     def step(ev=None, only=-1):
         # ev: one HIP event per kernel boundary (len(STAGES) + 1 of them); only >= 0: record just the two around stage `only`
@@ -427,7 +474,7 @@ def main():
         settle_ms = (time.perf_counter() - ts) * 1e3
         if settle_ms >= SETTLE_MS:
             break
-    # Every kernel's launch duration, by HIP events between the launches, over --steps untimed steps of the settled load: the
+    # --full: every kernel's launch duration, by HIP events between the launches, over --steps untimed steps of the settled load: the
     # `kernels_ms` key, and which kernel is the dominant one.  An event between two kernels costs the step about 3 us, so the timed
     # region below keeps only the two events around the dominant kernel (roofline.avg_launch_ms is measured THERE, live).
     new_events = lambda: [[torch.cuda.Event(enable_timing=True) for _ in range(len(STAGES) + 1)] for _ in range(args.steps)]
@@ -458,8 +505,10 @@ def main():
         return el
 
     elapsed = timed_block(events if breakdown else None)   # the contractual block: EXACTLY --steps steps, barrier + synchronize on both sides
-    # ... and five more blocks of the same length, so that the line carries its own spread (`value` stays the first block's)
-    more_blocks = [timed_block(None) for _ in range(5)]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, BH, N, d, (("o", out), ("L", L), ("dq", grads[0]), ("dk", grads[1]), ("dv", grads[2])))
+    # --full: five more blocks of the same length, so that the line carries its own spread (`value` stays the first block's)
+    more_blocks = [timed_block(None) for _ in range(5)] if args.full else []
 
     cf = 0.5 if causal else 1.0
     flops_fw = 4.0 * BH * N * N * d * cf
@@ -512,7 +561,7 @@ def main():
 
     # what this device sustains on a bare bf16 MFMA loop with random operands (power-limited clock), measured live
     sustained = None
-    if rank == 0 and args.dtype == "bf16" and not args.no_sustained_peak:
+    if rank == 0 and args.full and args.dtype == "bf16" and not args.no_sustained_peak:
         import ctypes
         from flash_attention_minitorch_amd import _lib
         tf, ghz = ctypes.c_double(0.0), ctypes.c_double(0.0)
@@ -526,7 +575,7 @@ def main():
     # The one all-gather of O the north star describes: reported beside the metric, never inside it.  Every rank takes the same
     # path (no rank-local try/except: a rank that skipped a collective would leave the others in it).
     gather_ms = fw_with_gather_ms = None
-    if world > 1:
+    if world > 1 and args.full:
         from flash_attention_minitorch_amd import sharded
         sharded.all_gather_bh(out, BH * world)
         barrier()
@@ -545,7 +594,7 @@ def main():
         fw_with_gather_ms = (time.perf_counter() - t1) / 3 * 1e3
 
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         import numpy as np
         import oracle
         from threadpoolctl import threadpool_limits
@@ -575,7 +624,7 @@ def main():
                                           "sample": f"1 head, 1 BLAS thread, {ct1:.1f} s"}}
 
     extras = {}
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and args.full and not args.no_extras:
         extras = run_extras(torch, device_ops, q, k, v, do, causal, B, H)
 
     if rank == 0:
@@ -592,6 +641,7 @@ def main():
             "vs_baseline": None,
             "dtype": args.dtype,
             "data": "synthetic",
+            "full": args.full,
             "config": {"workload": f"FlashAttention-2 fw+bw, B={B} H={H} N={N} d={d}, {args.dtype} in / fp32 out, "
                                    f"{'causal' if causal else 'non-causal'}, per GPU",
                        "B": B, "H": H, "N": N, "d": d, "causal": causal,
