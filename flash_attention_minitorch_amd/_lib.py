@@ -18,10 +18,7 @@ KERNEL_DIR = os.environ.get(
     "FA_MI355X_KERNEL_DIR", os.path.join(os.path.dirname(os.path.abspath(__file__)), "cuda_kernels")
 )
 
-# FA_MI355X_DIAG=1 (tools/ only) loads the diagnostic build instead: stamp / ablation kernels and fa_mi355x_set_tuning live there,
-# never in the product library the tests, the shims and bench.py use.
-DIAG = bool(os.environ.get("FA_MI355X_DIAG"))
-CORE_NAME = "libflash_attn_mi355x_diag.so" if DIAG else "libflash_attn_mi355x.so"
+CORE_NAME = "libflash_attn_mi355x.so"
 VARIANT_LIBS = (
     "flash_attn_fw.so",
     "flash_attn_bw.so",
@@ -129,11 +126,6 @@ def core() -> ctypes.CDLL:
     h.fa_mi355x_bwd_guarded.restype = _i
     h.fa_mi355x_plan.argtypes = [_i] * 7 + [_ip, _i, ctypes.c_char_p, ctypes.c_size_t]
     h.fa_mi355x_plan.restype = _i
-    if DIAG:
-        h.fa_mi355x_set_tuning.argtypes = [_i, _i]
-        h.fa_mi355x_set_tuning.restype = _i
-        h.fa_mi355x_debug_phase_cycles.argtypes = [_vp, _i]
-        h.fa_mi355x_debug_phase_cycles.restype = _i
     h.fa_mi355x_measure_mfma_peak.argtypes = [ctypes.c_double, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _vp]
     h.fa_mi355x_measure_mfma_peak.restype = _i
     h.fa_mi355x_probe.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]

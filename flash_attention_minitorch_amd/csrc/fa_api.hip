@@ -85,60 +85,30 @@ inline bool d_supported(int d) { return d == 32 || d == 64 || d == 128; }
 inline int d_padded(int d) { return d <= 32 ? 32 : (d <= 64 ? 64 : 128); }
 
 // Per-call kernel selection (fa_mi355x_fwd_ex / fa_mi355x_bwd_ex; every other entry point runs the defaults): [0] dK/dV geometry,
-// [1] forward kernel, [2] dQ kernel, [3] 1 = s_setprio 1 for waves 4-7 of the slot kernels, [4] 2 = one-pass backward, [5] (FA_DIAG
-// builds only) timing ablations of the one-pass backward, [6] 1 = causal d = 64 forward / dK/dV as main build + follow-up launch (A/B).  The product library accepts only values whose kernels give correct
-// results; stamp builds, A/B staging variants and ablations exist in the FA_DIAG build alone (libflash_attn_mi355x_diag.so, tools/).
+// [1] forward kernel, [2] dQ kernel, [3] reserved, [4] preprocess / fp32 one-pass backward, [5] 1 = one head per workgroup in the
+// tiled slot builds, [6] reserved, [7] causal block order.  Only values whose kernels give correct results are accepted (parse_opts).
 // [8] where tau*log2(e) is applied (see run_scaled): 0 = by the call's scale guard when it has one, else fp32 scaling; 1 = the caller
 // vouches for the operand range (inputs of the north star's U(-1, 1) magnitude): the kernels that fold it into a bf16 operand run
-// without a guard; 2 = fp32 scaling whatever the guard says; 3 = (fa_mi355x_plan only) plan a guarded call.  [9] unused.
+// without a guard; 2 = fp32 scaling whatever the guard says; 3 = (fa_mi355x_plan only) plan a guarded call.  [9] 1 = bf16 output.
 constexpr int NTUN = 10;
 struct Tun { int v[NTUN]; };
-#ifdef FA_DIAG
-// fa_mi355x_set_tuning(): process-wide defaults of the diagnostic build (its tools time and stamp the folded-scale kernels: [8] = 1)
-int g_tuning[NTUN] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 0};
-#endif
-inline Tun default_tun() {
-  Tun t = {{0, 0, 0, 0, 0, 0, 0, 0, 0, 0}};
-#ifdef FA_DIAG
-  for (int i = 0; i < NTUN; ++i) t.v[i] = g_tuning[i];
-#endif
-  return t;
-}
+inline Tun default_tun() { return Tun{{0, 0, 0, 0, 0, 0, 0, 0, 0, 0}}; }
 int parse_opts(const int* opts, int nopts, Tun& t) {
   t = default_tun();
   if (nopts < 0 || nopts > NTUN || (nopts > 0 && !opts)) return set_err(FA_ERR_BAD_ARG, "bad options array");
   for (int i = 0; i < nopts; ++i) t.v[i] = opts[i];
-#ifndef FA_DIAG
-  // (round 3 library diet: the values that lost their A/B and had no test -- opts[0] = 1 / 2, opts[1] = 6, opts[2] = 1 / 4, opts[3] = 1,
-  // opts[4] = 2 (the one-pass backward), opts[6] = 1 -- exist in the diagnostic build only, together with their kernels)
+  // (the values that lost their A/B were retired with their kernels: DESIGN.md section 3, "Retired experiments")
   static const int allowed[NTUN][7] = {{0, 3, 4, 5, -1}, {0, 2, 3, 4, -1}, {0, 2, 3, -1}, {0, -1}, {0, 1, 4, 5, -1}, {0, 1, -1}, {0, -1}, {0, 1, 2, -1},
                                        {0, 1, 2, 3, -1}, {0, 1, -1}};
   for (int i = 0; i < NTUN; ++i) {
     bool ok = false;
     for (int j = 0; allowed[i][j] >= 0; ++j) ok |= allowed[i][j] == t.v[i];
-    if (!ok) return set_err(FA_ERR_BAD_ARG, "option value not available in the product library (diagnostic builds only)");
+    if (!ok) return set_err(FA_ERR_BAD_ARG, "option value not supported (retired diagnostic values included)");
   }
-#endif
   return FA_OK;
 }
 
-// ---- workspace of the one-pass backward (bwd_fused_kernel; diagnostic build only since round 3) --------------------------
-// [ -L/tau | -delta | -L*log2e : 3 * rows floats ] (pad to 256 B) [ control: 256 B, word 0 = error ][ flags: FUSED_FLAG_BYTES ]
-// [ zero page 2 KiB | dummy page 2 KiB ][ running dQ tiles: ngroups * N * 64 floats ]
-inline size_t align256z(size_t x) { return (x + 255) & ~(size_t)255; }
-constexpr int WS_VECS = 3;   // row-constant vectors at the head of the backward workspace: -L/tau, -delta, -L*log2(e)
-#ifdef FA_DIAG
-constexpr size_t FUSED_CTL_BYTES = fa::FUSED_FLAG0, FUSED_FLAG_BYTES = fa::FUSED_FLAG_BYTES;
-constexpr int FUSED_MAX_CUS = 512;   // sizing bound only (flags: 4 * CUs words; slabs: CUs * 64 KiB)
-inline bool fused_shape(int N, int d) { return d == 64 && N >= 256 && N % 256 == 0 && N / 256 <= FUSED_MAX_CUS; }
-inline size_t fused_extra_bytes(int batch, int N, int d) {
-  if (!fused_shape(N, d)) return 0;
-  const size_t groups = (size_t)std::min(batch, std::max(1, FUSED_MAX_CUS / (N / 256)));
-  return FUSED_CTL_BYTES + FUSED_FLAG_BYTES + fa::FUSED_PAGES + groups * (size_t)N * 64 * sizeof(float);
-}
-#else
-inline size_t fused_extra_bytes(int, int, int) { return 0; }   // the product library runs the two-kernel backward only
-#endif
+constexpr int WS_VECS = 3;   // row-constant vectors of the backward workspace: -L/tau, -delta, -L*log2(e)
 int device_cus_raw();
 // Compute units the launch-size rules assume: the current device's, or 256 (an MI355X) when there is none -- fa_mi355x_plan without a
 // GPU must name the kernels a real launch would select (three rules used max(cus, 1) and two `cus > 0 ? cus : 256`).
@@ -159,32 +129,6 @@ int device_cus_raw() {   // compute units of the current device (cached per devi
   }
   return cus[dev];
 }
-
-// ---- the chained one-pass backward (bwd_chain_kernel: bf16, d = 64, non-causal, N a multiple of 256; DIAGNOSTIC BUILD ONLY: it
-// measured slower than the two-kernel backward, profiles/r04_chain_backward.txt, and keeps 36 B of scratch per lane) ---------------
-// A workgroup takes C = nkb / nchains consecutive key blocks of one (batch*head); nchains = the smallest divisor of nkb = N / 256
-// that fills the chip (batch * nchains >= CUs), all of them if none does.  nchains == 1: dq carries the running sums, no atomics,
-// no workspace beyond the 4-KiB header; otherwise a private slab of N * 64 floats per workgroup and fp32 atomics from each chain's
-// last key block into a zero-filled dq.
-inline bool chain_shape(int N, int d) { return d == 64 && N >= 256 && N % 256 == 0; }
-inline int chain_count(int batch, int N, int cus) {
-  const int nkb = N / 256;
-  if (cus <= 0) cus = 256;
-  for (int n = 1; n <= nkb; ++n)
-    if (nkb % n == 0 && (long)batch * n >= cus) return n;
-  return nkb;
-}
-#ifdef FA_DIAG
-inline size_t chain_extra_bytes(int batch, int N, int d, int cus) {
-  if (!chain_shape(N, d)) return 0;
-  const int nchains = chain_count(batch, N, cus), nkb = N / 256;
-  size_t b = fa::CHAIN_HDR;
-  if (nchains < nkb) b += (size_t)batch * nchains * (size_t)N * 256u;   // running sums of chains of more than one key block
-  return b;
-}
-#else
-inline size_t chain_extra_bytes(int, int, int, int) { return 0; }
-#endif
 
 // Causal slot builds: heads per XCD dispatched together, longest block first (fa::map_block_ranked): a chunk of two rounds of the chip
 int rank_chunk(int wgs_per_cu, int nb) {
@@ -270,42 +214,23 @@ int fwd_launch(const void* q, const void* k, const void* v, float* out, float* l
     const bool cslot = causal && N % 256 == 0 && (tun.v[1] == 3 || (tun.v[1] == 0 && batch * nqb >= 256));
     if (variant == FA_VARIANT_FA2 && tun.v[1] != 2 && (!causal || tun.v[1] == 3 || cslot) && !lay.kmask && !lay.drop_thr && N >= 64) {
       const bool whole = !causal && N % (8192 / D) == 0;   // no sub-tile needs a mask
-#ifdef FA_DIAG
-      if (whole && tun.v[1] == 94) {   // timing ablation: no per-stage barrier (WRONG results)
-        FA_LAUNCH_FOLD((fa::fwd_slot_kernel<T, D, false, 2, 64, (D == 64 ? 4 : 2)>), dim3(batch * nqb), dim3(512), 0, st, (const T*)q,
-                           (const T*)k, (const T*)v, out, l, N, nqb, batch, lay, causal, tau);
-        FA_HIP_TRY(hipGetLastError());
-        return FA_OK;
-      }
-      if (whole && tun.v[1] == 93) {   // phase stamps (never timed)
-        FA_LAUNCH_FOLD((fa::fwd_slot_kernel<T, D, false, 1, 64, (D == 64 ? 4 : 2)>), dim3(batch * nqb), dim3(512), 0, st, (const T*)q,
-                           (const T*)k, (const T*)v, out, l, N, nqb, batch, lay, causal, tau);
-        FA_HIP_TRY(hipGetLastError());
-        return FA_OK;
-      }
-#endif
       if (cslot) {   // (d = 64: four waves per SIMD, two workgroups per CU; d = 128: two waves per SIMD, one workgroup)
         const bool ranked = causal_ranked(tun, batch * nqb, D == 64 ? 2 : 1);
         lay.rank_chunk = rank_chunk(D == 64 ? 2 : 1, nqb);
-        FA_LAUNCH_FOLD((fa::fwd_slot_kernel<T, D, false, 0, 64, (D == 64 ? 4 : 2), true>),
+        FA_LAUNCH_FOLD((fa::fwd_slot_kernel<T, D, false, 64, (D == 64 ? 4 : 2), true>),
                            dim3(ranked ? batch * nqb : batch * ((nqb + 1) / 2)),
                            dim3(512), 0, st, (const T*)q, (const T*)k, (const T*)v, out, l, N, nqb, batch, lay, ranked ? 2 : 1, tau);
         FA_HIP_TRY(hipGetLastError());
         return FA_OK;
       }
-#ifdef FA_DIAG
-      constexpr bool diag_stk = true;    // option 1 = 6: the 128-key-stage build of the d = 64 kernel (A/B)
-#else
-      constexpr bool diag_stk = false;
-#endif
-      if (whole && (tun.v[1] != 6 || !diag_stk) && D == 64) {   // d = 64 default: 64-key stages (64 KiB of rings), two workgroups per CU = four
-        // waves per SIMD at 122 VGPRs: 0.268 vs 0.282 ms for the 128-key-stage build at two waves per SIMD (tuning key 1 = 6)
-        FA_LAUNCH_FOLD_P((fa::fwd_slot_kernel<T, 64, false, 0, 64, 4>), dim3(batch * nqb), dim3(512), 0, st, (const T*)q,
+      if (whole && D == 64) {   // d = 64 default: 64-key stages (64 KiB of rings), two workgroups per CU = four waves per SIMD at
+        // 122 VGPRs: 0.268 vs 0.282 ms for the 128-key-stage build at two waves per SIMD
+        FA_LAUNCH_FOLD_P((fa::fwd_slot_kernel<T, 64, false, 64, 4>), dim3(batch * nqb), dim3(512), 0, st, (const T*)q,
                            (const T*)k, (const T*)v, out, l, N, nqb, batch, lay, causal, tau);
         FA_HIP_TRY(hipGetLastError());
         return FA_OK;
       }
-      if constexpr (D == 128 || diag_stk) {
+      if constexpr (D == 128) {
         if (whole) {
           FA_LAUNCH_FOLD_P((fa::fwd_slot_kernel<T, D, false>), dim3(batch * nqb), dim3(512), 0, st, (const T*)q,
                              (const T*)k, (const T*)v, out, l, N, nqb, batch, lay, causal, tau);
@@ -325,7 +250,7 @@ int fwd_launch(const void* q, const void* k, const void* v, float* out, float* l
     }
   }
   return fwd_launch_cfg<T, D, (sizeof(T) == 2 ? 64 : 32), 1>(q, k, v, out, l, m, batch, N, lay, causal, variant, tau,
-                                                             st, -1, (D == 64 && tun.v[6] == 0) ? 1 : 0,
+                                                             st, -1, D == 64 ? 1 : 0,
                                                              tun.v[7] == 2 || (tun.v[7] == 0 && sizeof(T) == 2 && D == 32));   // (d = 32: ranked measured 10 % faster)
 }
 
@@ -439,20 +364,20 @@ int dq_launch(const void* q, const void* k, const void* v, const void* dout, con
   return FA_OK;
 }
 
-template <typename T, int D, int DIAG = 0>
+template <typename T, int D>
 int dq_slot_launch(const void* q, const void* k, const void* v, const void* dout, const float* nlc, const float* delta,
-                   float* dq, int batch, int N, fa::Layout lay, int causal, float tau, hipStream_t st, const Tun& tun = default_tun(),
-                   const fa::DqPrep* prep = nullptr) {
+                   float* dq, int batch, int N, fa::Layout lay, int causal, float tau, hipStream_t st, const Tun& tun,
+                   const fa::DqPrep* prep) {
   // prep != nullptr: the launch also does the preprocess for its rows and writes the workspace (see dq_fuses_prep)
   const int nqb = (N + 255) / 256;
   lay.rank_chunk = rank_chunk(1, nqb);
   const bool paired = !causal_ranked(tun, batch * nqb, 1);
-  if (DIAG == 0 && causal && N % 256 == 0) {   // causal build: unmasked sweep + the diagonal block per wave; one block per workgroup,
+  if (causal && N % 256 == 0) {   // causal build: unmasked sweep + the diagonal block per wave; one block per workgroup,
     // longest first across all heads (paired: blocks p and nqb-1-p in one workgroup)
     const dim3 grid(paired ? batch * ((nqb + 1) / 2) : batch * nqb);
-    FA_LAUNCH_SEL((fa::bwd_dq_slot_kernel<T, D, 0, false, true>), grid, dim3(512), 0, st, (const T*)q, (const T*)k,
+    FA_LAUNCH_SEL((fa::bwd_dq_slot_kernel<T, D, false, true>), grid, dim3(512), 0, st, (const T*)q, (const T*)k,
               (const T*)v, (const T*)dout, nlc, delta, dq, N, nqb, batch, lay, paired ? 1 : 2, tau, prep ? *prep : fa::DqPrep{});
-  } else if (DIAG == 0 && !causal && N % 128 == 0) {   // no sub-tile needs a mask: the build without masked period variants
+  } else if (!causal && N % 128 == 0) {   // no sub-tile needs a mask: the build without masked period variants
     // Query block qb of several consecutive heads per workgroup (the tiled build: no set-up, no wait for the first stage, no store
     // drain between them) while the grid still covers every CU (the rule of the tiled dK/dV launch); option 5 = 1: one head
     int tiles = 1;
@@ -463,14 +388,14 @@ int dq_slot_launch(const void* q, const void* k, const void* v, const void* dout
     }
     if (tiles > 1) {
       lay.tiles = tiles;
-      FA_LAUNCH_SEL((fa::bwd_dq_slot_kernel<T, D, 0, false, false, true>), dim3((batch / tiles) * nqb), dim3(512), 0, st, (const T*)q,
+      FA_LAUNCH_SEL((fa::bwd_dq_slot_kernel<T, D, false, false, true>), dim3((batch / tiles) * nqb), dim3(512), 0, st, (const T*)q,
                 (const T*)k, (const T*)v, (const T*)dout, nlc, delta, dq, N, nqb, batch, lay, causal, tau, prep ? *prep : fa::DqPrep{});
     } else {
-      FA_LAUNCH_SEL((fa::bwd_dq_slot_kernel<T, D, 0, false>), dim3(batch * nqb), dim3(512), 0, st, (const T*)q, (const T*)k,
+      FA_LAUNCH_SEL((fa::bwd_dq_slot_kernel<T, D, false>), dim3(batch * nqb), dim3(512), 0, st, (const T*)q, (const T*)k,
                 (const T*)v, (const T*)dout, nlc, delta, dq, N, nqb, batch, lay, causal, tau, prep ? *prep : fa::DqPrep{});
     }
   } else {
-    FA_LAUNCH((fa::bwd_dq_slot_kernel<T, D, DIAG>), dim3(batch * nqb), dim3(512), 0, st, (const T*)q, (const T*)k,
+    FA_LAUNCH((fa::bwd_dq_slot_kernel<T, D>), dim3(batch * nqb), dim3(512), 0, st, (const T*)q, (const T*)k,
                        (const T*)v, (const T*)dout, nlc, delta, dq, N, nqb, batch, lay, causal, tau, fa::DqPrep{});
   }
   FA_HIP_TRY(hipGetLastError());
@@ -479,8 +404,8 @@ int dq_slot_launch(const void* q, const void* k, const void* v, const void* dout
 
 // Does a backward call that asks for the preprocess AND dQ fold the preprocess into its dQ launch (dQ is then launched BEFORE dK/dV,
 // which reads the workspace the dQ launch wrote)?  Yes whenever dq_stage sends the call to a plain main build: not under a key mask
-// or dropout, not bf16 with N < 64 (split-operand builds), not the bf16 d = 64 slot build with masked periods (no registers), not a
-// diagnostic build; option 4 = 1 keeps the separate preprocess kernel (A/B), 2 is the one-pass backward.
+// or dropout, not bf16 with N < 64 (split-operand builds), not the bf16 d = 64 slot build with masked periods (no registers); option
+// 4 = 1 keeps the separate preprocess kernel (A/B).
 // fp32, d = 64, N >= 256, no key mask / dropout, dQ and dK/dV asked for together: the one-pass backward
 // (fa_bwd_onepass_f32.h: five products instead of the two-kernel path's seven, dQ by fp32 atomics) when its launch fills the chip:
 // one 8-wave workgroup per CU and 256-key block, so batch * ceil(N / 256) workgroups run in ceil(that / CUs) rounds; below one
@@ -519,9 +444,9 @@ bool dq_fuses_prep(int batch, int N, const fa::Layout& lay, int causal, int stag
   constexpr bool BF = sizeof(T) == 2;
   if (onepass_f32<T, D>(batch, N, lay, causal, stages, tun)) return false;
   const int need = FA_BWD_STAGE_PREP | FA_BWD_STAGE_DQ;
-  if ((stages & need) != need || tun.v[4] != 0 || lay.kmask || lay.drop_thr || (BF && N < 64) || tun.v[2] > 4) return false;
+  if ((stages & need) != need || tun.v[4] != 0 || lay.kmask || lay.drop_thr || (BF && N < 64)) return false;
   if constexpr (BF && D == 64) {
-    const bool phased = tun.v[2] == 1 || tun.v[2] == 2 || (causal && tun.v[2] != 3 && !(N % 256 == 0 && batch * (N / 256) >= 128));
+    const bool phased = tun.v[2] == 2 || (causal && tun.v[2] != 3 && !(N % 256 == 0 && batch * (N / 256) >= 128));
     if (!phased) return causal ? N % 256 == 0 : N % 128 == 0;   // the slot kernel: its unmasked / causal builds only
   }
   return true;
@@ -534,13 +459,7 @@ int dq_stage(const void* q, const void* k, const void* v, const void* dout, cons
              int N, fa::Layout lay, int causal, float tau, hipStream_t st, const Tun& tun, const fa::DqPrep* prep) {
   int rc;
   if constexpr (sizeof(T) == 2 && D == 128) {
-#ifdef FA_DIAG
-    if (tun.v[2] == 1)   // 64-key tiles (A/B)
-      rc = dq_launch<T, D, 64>(q, k, v, dout, nlc, delta, dq, batch, N, lay, causal, tau, st, -1, 0, prep,
-                          tun.v[7] == 2 || (tun.v[7] == 0 && sizeof(T) == 2 && D == 32));
-    else
-#endif
-    if (tun.v[2] == 4 || causal || lay.kmask || lay.drop_thr || N < 64)   // 4 waves x 32 queries, two workgroups per CU
+    if (causal || lay.kmask || lay.drop_thr || N < 64)   // 4 waves x 32 queries, two workgroups per CU
       rc = dq_launch<T, D, 32>(q, k, v, dout, nlc, delta, dq, batch, N, lay, causal, tau, st, -1, 0, prep,
                           tun.v[7] == 2 || (tun.v[7] == 0 && sizeof(T) == 2 && D == 32));
     else {   // non-causal default: 8 waves x 32 queries, one workgroup per CU (each staged K / V tile feeds twice the waves)
@@ -551,12 +470,6 @@ int dq_stage(const void* q, const void* k, const void* v, const void* dout, cons
       rc = FA_OK;
     }
   } else if constexpr (sizeof(T) == 2 && D == 64) {   // d = 64: slot-interleaved three-deep pipeline (default)
-#ifdef FA_DIAG
-    if (tun.v[2] == 1)   // phased kernel on 64-key tiles (A/B)
-      rc = dq_launch<T, D, 64>(q, k, v, dout, nlc, delta, dq, batch, N, lay, causal, tau, st, -1, 0, prep,
-                          tun.v[7] == 2 || (tun.v[7] == 0 && sizeof(T) == 2 && D == 32));
-    else
-#endif
     if (tun.v[2] == 2 || lay.kmask || lay.drop_thr || N < 64 ||
              (causal && tun.v[2] != 3 && !(N % 256 == 0 && batch * (N / 256) >= 128)))
       // key mask and dropout live in the phased kernel, which is also 1 % faster than the slot build WITH masked periods under
@@ -564,12 +477,6 @@ int dq_stage(const void* q, const void* k, const void* v, const void* dout, cons
       // build (unmasked sweep + diagonal block per wave, paired query blocks): 0.199 vs 0.223 ms at the metric shape
       rc = dq_launch<T, D, 32>(q, k, v, dout, nlc, delta, dq, batch, N, lay, causal, tau, st, -1, 0, prep,
                           tun.v[7] == 2 || (tun.v[7] == 0 && sizeof(T) == 2 && D == 32));
-#ifdef FA_DIAG
-    else if (tun.v[2] == 94)   // timing ablation: no per-stage barrier (WRONG results; upper bound for a flag-based hand-off)
-      rc = dq_slot_launch<T, D, 2>(q, k, v, dout, nlc, delta, dq, batch, N, lay, causal, tau, st);
-    else if (tun.v[2] == 93)   // phase stamps (never timed)
-      rc = dq_slot_launch<T, D, 1>(q, k, v, dout, nlc, delta, dq, batch, N, lay, causal, tau, st);
-#endif
     else {
       rc = dq_slot_launch<T, D>(q, k, v, dout, nlc, delta, dq, batch, N, lay, causal, tau, st, tun, prep);
       // the masked slot build forced onto a causal launch: rows 0..63 (few keys) are redone by the phased kernel's split-operand
@@ -577,13 +484,7 @@ int dq_stage(const void* q, const void* k, const void* v, const void* dout, cons
       if (!rc && causal && N % 256 != 0) rc = dq_launch<T, D, 32>(q, k, v, dout, nlc, delta, dq, batch, N, lay, causal, tau, st, 0);
     }
   } else if constexpr (sizeof(T) == 2) {   // d = 32: 32-key tiles run 3 waves/SIMD, measured 2 % faster
-#ifdef FA_DIAG
-    if (tun.v[2] == 1)
-      rc = dq_launch<T, D, 64>(q, k, v, dout, nlc, delta, dq, batch, N, lay, causal, tau, st, -1, 0, prep,
-                          tun.v[7] == 2 || (tun.v[7] == 0 && sizeof(T) == 2 && D == 32));
-    else
-#endif
-      rc = dq_launch<T, D, 32>(q, k, v, dout, nlc, delta, dq, batch, N, lay, causal, tau, st, -1, 0, prep,
+    rc = dq_launch<T, D, 32>(q, k, v, dout, nlc, delta, dq, batch, N, lay, causal, tau, st, -1, 0, prep,
                           tun.v[7] == 2 || (tun.v[7] == 0 && sizeof(T) == 2 && D == 32));
   } else {
     rc = dq_launch<T, D, 32>(q, k, v, dout, nlc, delta, dq, batch, N, lay, causal, tau, st, -1, 0, prep,
@@ -638,120 +539,14 @@ int bwd_launch(const void* q, const void* k, const void* v, const float* out, co
       return FA_OK;
     }
   }
-#ifdef FA_DIAG
-  if constexpr (sizeof(T) == 2 && D == 64) {
-    // DIAGNOSTIC BUILD ONLY since round 3 (it lost its A/B at every measured size once the two-kernel path dropped its per-score
-    // scale instruction, and it is the one kernel with scratch and a persistent-grid spin protocol): tools/check_fused.py.
-    // One pass for dQ, dK, dV (five products instead of seven): non-causal, N a multiple of 256, all members of a head's
-    // hand-off chain resident (N / 256 workgroups of one per CU).  Opt-in (option 4 = 2): measured 3-8 % SLOWER than the two-kernel
-    // backward up to N = 8192 and 3 % faster at N = 16384 (profiles/README.md, round 2), so the default stays two kernels.
-    const int both = FA_BWD_STAGE_DKDV | FA_BWD_STAGE_DQ;
-    const int cus = device_cus();
-    if ((stages & both) == both && tun.v[4] == 2 && !causal && !lay.kmask &&
-        !lay.drop_thr && fused_shape(N, D) && N / 256 <= cus && cus <= FUSED_MAX_CUS) {
-      const int nkb = N / 256;
-      const int xcdmap = (cus == 256 && nkb <= 32 && 32 % nkb == 0) ? 1 : 0;
-      const int avail = xcdmap ? 8 * (32 / nkb) : cus / nkb;
-      const int ngroups = std::min(avail, batch);
-      const int grid = xcdmap ? 256 : ngroups * nkb;
-      char* fz = (char*)ws + align256z((size_t)WS_VECS * rows * sizeof(float));
-      unsigned* hand = (unsigned*)fz;
-      FA_HIP_TRY(hipMemsetAsync(fz, 0, FUSED_CTL_BYTES + FUSED_FLAG_BYTES + fa::FUSED_PAGES / 2, st));   // error word, flags, zero page: every call
-#define FA_FUSED_LAUNCH(ABL)                                                                                              \
-  FA_LAUNCH((fa::bwd_fused_kernel<T, 64, ABL>), dim3(grid), dim3(512), 0, st, (const T*)q, (const T*)k, (const T*)v, \
-                     (const T*)dout, nlc, delta, dq, dk, dv, hand, N, nkb, batch, ngroups, xcdmap, lay, tau)
-      switch (tun.v[5]) {   // timing ablations (wrong results) and phase stamps: see bwd_fused_kernel
-        case 1: FA_FUSED_LAUNCH(1); break;
-        case 2: FA_FUSED_LAUNCH(2); break;
-        case 3: FA_FUSED_LAUNCH(3); break;
-        case 7: FA_FUSED_LAUNCH(7); break;
-        case 8: FA_FUSED_LAUNCH(8); break;
-        case 32: FA_FUSED_LAUNCH(32); break;
-        case 33: FA_FUSED_LAUNCH(33); break;
-        case 64: FA_FUSED_LAUNCH(64); break;
-        case 128: FA_FUSED_LAUNCH(128); break;
-        case 256: FA_FUSED_LAUNCH(256); break;
-        case 192: FA_FUSED_LAUNCH(192); break;
-        case 320: FA_FUSED_LAUNCH(320); break;
-        case 384: FA_FUSED_LAUNCH(384); break;
-        default: FA_FUSED_LAUNCH(0); break;
-      }
-#undef FA_FUSED_LAUNCH
-      FA_HIP_TRY(hipGetLastError());
-      return FA_OK;
-    }
-  }
-#endif   // FA_DIAG: one-pass backward
-#ifdef FA_DIAG
-  if constexpr (sizeof(T) == 2 && D == 64) {
-    // Option 4 = 3: the chained one-pass backward (five products instead of seven; fa_bwd_chain.h).
-    const int both = FA_BWD_STAGE_DKDV | FA_BWD_STAGE_DQ;
-    if ((stages & both) == both && tun.v[4] == 3 && chain_shape(N, D) && !causal && !lay.kmask && !lay.drop_thr) {
-      const int nkb = N / 256, nchains = chain_count(batch, N, device_cus());
-      float* slab = (float*)((char*)ws + align256z((size_t)WS_VECS * rows * sizeof(float)));
-      const dim3 grid((unsigned)(batch * nchains));
-#define FA_CHAIN_LAUNCH(ATOMIC, ABL)                                                                                         \
-  FA_LAUNCH_FOLD((fa::bwd_chain_kernel<T, 64, ATOMIC, ABL>), grid, dim3(512), 0, st, (const T*)q, (const T*)k, (const T*)v,       \
-            (const T*)dout, nl2, delta, dq, dk, dv, slab, N, nkb, batch, nchains, lay, tau)
-      if (nchains > 1) {
-        // every chain's last key block ADDS tau * (its sum) to dq (the reference's caller zeroes q_grad for its atomicAdd as well:
-        // minitorch/cuda_kernel_ops.py:609-611); [B][N][H][d] or [BH][N][d]: the tensor is one contiguous range either way
-        FA_HIP_TRY(hipMemsetAsync(dq, 0, (size_t)rows * D * sizeof(float), st));
-        switch (tun.v[5]) {   // timing ablations (WRONG results): see bwd_chain_kernel
-          case 1: FA_CHAIN_LAUNCH(true, 1); break;
-          case 2: FA_CHAIN_LAUNCH(true, 2); break;
-          case 3: FA_CHAIN_LAUNCH(true, 3); break;
-          case 64: FA_CHAIN_LAUNCH(true, 64); break;
-          case 128: FA_CHAIN_LAUNCH(true, 128); break;
-          case 256: FA_CHAIN_LAUNCH(true, 256); break;
-          case 512: FA_CHAIN_LAUNCH(true, 512); break;
-          case 1024: FA_CHAIN_LAUNCH(true, 1024); break;
-          case 1536: FA_CHAIN_LAUNCH(true, 1536); break;
-          case 2048: FA_CHAIN_LAUNCH(true, 2048); break;
-          case 2304: FA_CHAIN_LAUNCH(true, 2304); break;
-          case 4352: FA_CHAIN_LAUNCH(true, 4352); break;
-          case 8448: FA_CHAIN_LAUNCH(true, 8448); break;
-          default: FA_CHAIN_LAUNCH(true, 0); break;
-        }
-      } else {
-        FA_CHAIN_LAUNCH(false, 0);
-      }
-#undef FA_CHAIN_LAUNCH
-      FA_HIP_TRY(hipGetLastError());
-      return FA_OK;
-    }
-  }
-#endif   // FA_DIAG: chained one-pass backward
   if (stages & FA_BWD_STAGE_DKDV) {
     int rc;
     if constexpr (sizeof(T) == 2 && D <= 64) {
       // measured at B=8,H=8,N=4096,d=64 (ms, one device, profiles/README.md): 8 waves x 32 keys, 128-query stages,
       // software-pipelined sub-slices 0.505; not pipelined 0.514; 64-query stages 0.519; 256-query 0.525;
       // 4 waves x 32 keys (two workgroups per CU) 0.521; 4 waves x 64 keys (one wave per SIMD) 0.559
-#ifdef FA_DIAG
-      if (tun.v[0] == 1)   // the geometries that lost their A/B (not pipelined; 4 waves x 64 keys)
-        rc = dkdv_launch<T, D, 32, 8, 128, 1>(q, k, v, dout, nlc, delta, dk, dv, batch, N, lay, causal, tau, st);
-      else if (tun.v[0] == 2)
-        rc = dkdv_launch<T, D, 64, 4, 32, 1>(q, k, v, dout, nlc, delta, dk, dv, batch, N, lay, causal, tau, st);
-      else
-#endif
       if (tun.v[0] == 4 || D != 64)   // compiler-interleaved software pipeline (the d = 32 default)
         rc = dkdv_launch<T, D, 32, 8, 128, 0>(q, k, v, dout, nlc, delta, dk, dv, batch, N, lay, causal, tau, st);
-#ifdef FA_DIAG
-      else if (tun.v[0] == 13 && D == 64)   // slot path on register staging instead of LDS-DMA (A/B)
-        rc = dkdv_launch<T, D, 32, 8, 128, 13>(q, k, v, dout, nlc, delta, dk, dv, batch, N, lay, causal, tau, st);
-      else if (tun.v[0] == 93)   // slot-interleaved path with phase stamps (never timed)
-        rc = dkdv_launch<T, D, 32, 8, 128, 93>(q, k, v, dout, nlc, delta, dk, dv, batch, N, lay, causal, tau, st);
-      else if (tun.v[0] == 9)   // phased path with phase stamps (never timed)
-        rc = dkdv_launch<T, D, 32, 8, 128, 9>(q, k, v, dout, nlc, delta, dk, dv, batch, N, lay, causal, tau, st);
-      else if (D == 64 && !causal && tun.v[0] == 193 && !lay.drop_thr) {   // continuous slot pipeline with phase stamps
-        const int nkb = (N + 255) / 256;
-        FA_LAUNCH_SEL((fa::bwd_dkdv_slot_kernel<T, 64, 1>), dim3(batch * nkb), dim3(512), 0, st, (const T*)q,
-                           (const T*)k, (const T*)v, (const T*)dout, nl2, delta, dk, dv, N, nkb, batch, lay, tau);
-        FA_HIP_TRY(hipGetLastError());
-        rc = FA_OK;
-      }
-#endif
       else if (D == 64 && !causal && tun.v[0] == 0 && !lay.drop_thr && !lay.kmask && N >= 64) {
         // d = 64, non-causal default: the continuous slot pipeline (no drain at stage boundaries, three-slot LDS-DMA ring);
         // rows thinned by a key mask or N < 64 go to the kernel below, whose per-sub-slice path splits P and dS
@@ -766,10 +561,10 @@ int bwd_launch(const void* q, const void* k, const void* v, const float* out, co
         }
         if (tiles > 1) {
           lay.tiles = tiles;
-          FA_LAUNCH_SEL((fa::bwd_dkdv_slot_kernel<T, 64, 0, false, true>), dim3((batch / tiles) * nkb), dim3(512), 0, st,
+          FA_LAUNCH_SEL((fa::bwd_dkdv_slot_kernel<T, 64, false, true>), dim3((batch / tiles) * nkb), dim3(512), 0, st,
                              (const T*)q, (const T*)k, (const T*)v, (const T*)dout, nl2, delta, dk, dv, N, nkb, batch, lay, tau);
         } else {
-          FA_LAUNCH_SEL((fa::bwd_dkdv_slot_kernel<T, 64, 0>), dim3(batch * nkb), dim3(512), 0, st, (const T*)q,
+          FA_LAUNCH_SEL((fa::bwd_dkdv_slot_kernel<T, 64>), dim3(batch * nkb), dim3(512), 0, st, (const T*)q,
                              (const T*)k, (const T*)v, (const T*)dout, nl2, delta, dk, dv, N, nkb, batch, lay, tau);
         }
         FA_HIP_TRY(hipGetLastError());
@@ -778,68 +573,28 @@ int bwd_launch(const void* q, const void* k, const void* v, const float* out, co
                  (tun.v[0] == 5 || (tun.v[0] == 0 && batch * (N / 256) >= 128))) {   // (tuning key 0 = 5 forces it)
         // d = 64, causal, N a multiple of 256: the causal build of the continuous pipeline (sweep of the stages below the
         // diagonal block, the block per wave, workgroups longest first); tuning key 0 = 3: the phased kernel below
+        // (key blocks p and nkb-1-p of several consecutive heads per workgroup, a causal tiled build, gave bitwise the same results
+        // 4-8 % slower: profiles/r04_causal_tiled_dkdv.txt)
         const int nkb = N / 256;
-        // Round 4, DIAGNOSTIC BUILD ONLY (option 5 = 2; tools/check_causal_tiled.py): key blocks p and nkb-1-p of several consecutive
-        // heads per workgroup (the causal tiled build: uniform work, the ring carried from unit to unit).  Bitwise the ranked build and
-        // 4-8 % SLOWER (0.262 vs 0.251 ms at the metric shape, profiles/r04_causal_tiled_dkdv.txt), with 40 B of scratch: not kept.
-        int tiles = 0;
-#ifdef FA_DIAG
-        if (nkb % 2 == 0 && tun.v[5] == 2) {
-          const int cus = device_cus();
-          for (int t = 1; t <= 16; ++t)
-            if (batch % t == 0 && (batch / t) % 8 == 0 && (long)(batch / t) * (nkb / 2) >= cus) tiles = t;
-        }
-        if (tiles > 0) {
-          lay.tiles = tiles;
-          FA_LAUNCH_SEL((fa::bwd_dkdv_slot_kernel<T, 64, 0, true, true>), dim3((batch / tiles) * (nkb / 2)), dim3(512), 0, st,
-                        (const T*)q, (const T*)k, (const T*)v, (const T*)dout, nl2, delta, dk, dv, N, nkb, batch, lay, tau);
-        }
-#endif
-        if (tiles == 0) {
-          lay.rank_chunk = rank_chunk(1, nkb);
-          FA_LAUNCH_SEL((fa::bwd_dkdv_slot_kernel<T, 64, 0, true>), dim3(batch * nkb), dim3(512), 0, st, (const T*)q,
-                             (const T*)k, (const T*)v, (const T*)dout, nl2, delta, dk, dv, N, nkb, batch, lay, tau);
-        }
+        lay.rank_chunk = rank_chunk(1, nkb);
+        FA_LAUNCH_SEL((fa::bwd_dkdv_slot_kernel<T, 64, true>), dim3(batch * nkb), dim3(512), 0, st, (const T*)q,
+                           (const T*)k, (const T*)v, (const T*)dout, nl2, delta, dk, dv, N, nkb, batch, lay, tau);
         FA_HIP_TRY(hipGetLastError());
         rc = FA_OK;
       } else if constexpr (D == 64) {   // d = 64, causal (or tuning 3): slot-interleaved fast path for unmasked stages, per-sub-slice path on the diagonal
         // (a build with the masked paths compiled out, for non-causal launches, measured the same: 0.4983 vs 0.4992 ms)
-        rc = dkdv_launch<T, D, 32, 8, 128, 3>(q, k, v, dout, nlc, delta, dk, dv, batch, N, lay, causal, tau, st, tun.v[6] == 0 ? 1 : 0);
+        rc = dkdv_launch<T, D, 32, 8, 128, 3>(q, k, v, dout, nlc, delta, dk, dv, batch, N, lay, causal, tau, st, 1);
       } else {
         rc = set_err(FA_ERR_BAD_ARG, "internal: no dK/dV kernel selected");   // (d = 32 never gets here: the branch above takes it)
       }
     } else if constexpr (sizeof(T) == 2) {
-#ifdef FA_DIAG
-      if (tun.v[0] == 1)
-        rc = dkdv_launch<T, D, 32, 4, 32>(q, k, v, dout, nlc, delta, dk, dv, batch, N, lay, causal, tau, st);
-      else if (tun.v[0] == 2)
-        rc = dkdv_launch<T, D, 32, 4, 128>(q, k, v, dout, nlc, delta, dk, dv, batch, N, lay, causal, tau, st);
-      else
-#endif
-#ifdef FA_DIAG
-      if (tun.v[0] == 5)   // two 128-key workgroups per CU (4 waves each) (A/B: 3.92 vs 3.65 ms)
-        rc = dkdv_launch<T, D, 32, 4, 64>(q, k, v, dout, nlc, delta, dk, dv, batch, N, lay, causal, tau, st);
-      else
-#endif
-        // d = 128 default (dropout / key mask / N < 64: dkdv_launch runs the 4-wave split-operand build, which has the registers for it): 8 waves x 32 keys, one 256-key workgroup per CU (half the Q / dO staging per MFMA): 3.64 vs 3.92 ms
-        rc = dkdv_launch<T, D, 32, 8, 64>(q, k, v, dout, nlc, delta, dk, dv, batch, N, lay, causal, tau, st, 0, tun.v[7] != 1);
+      // d = 128 default (dropout / key mask / N < 64: dkdv_launch runs the 4-wave split-operand build, which has the registers for it): 8 waves x 32 keys, one 256-key workgroup per CU (half the Q / dO staging per MFMA): 3.64 vs 3.92 ms
+      rc = dkdv_launch<T, D, 32, 8, 64>(q, k, v, dout, nlc, delta, dk, dv, batch, N, lay, causal, tau, st, 0, tun.v[7] != 1);
     } else if constexpr (D == 64) {
       // fp32, d = 64 (configs[1], [2]): the allocation lands on 256 VGPRs + 2 AGPRs = one wave per SIMD; asking for two
-      // (launch bound) keeps it under 256 (tuning key 0 = 1: the unconstrained build)
+      // (launch bound) keeps it under 256
       if (lay.drop_thr)
         rc = dkdv_launch<T, D, 32, 4, 32, 0, true>(q, k, v, dout, nlc, delta, dk, dv, batch, N, lay, causal, tau, st);
-#ifdef FA_DIAG
-      else if (tun.v[0] == 1)   // the unconstrained register allocation (A/B)
-        rc = dkdv_launch<T, D, 32, 4, 32>(q, k, v, dout, nlc, delta, dk, dv, batch, N, lay, causal, tau, st);
-      else if (tun.v[0] == 5) {   // one 8-wave workgroup per CU instead of two of 4 waves (A/B: 2 % slower)
-        const int nkb = (N + 255) / 256;
-        FA_LAUNCH((fa::bwd_dkdv_kernel<T, D, 32, 8, 32, 0, false, 2>), dim3(batch * nkb), dim3(512), 0, st,
-                           (const T*)q, (const T*)k, (const T*)v, (const T*)dout, nlc, delta, dk, dv, N, nkb, batch, lay,
-                           causal, tau);
-        FA_HIP_TRY(hipGetLastError());
-        rc = FA_OK;
-      }
-#endif
       else {
         const int nkb = (N + 127) / 128;
         // causal: longest block first across a chunk of heads instead of head by head: 0.57 vs 0.80 ms at the reference's timing-harness
@@ -1204,22 +959,6 @@ extern "C" {
 const char* fa_mi355x_last_error(void) { return g_err; }
 const char* fa_mi355x_version(void) { return "flash_attn_mi355x 0.2 gfx950"; }
 
-#ifdef FA_DIAG
-int fa_mi355x_debug_phase_cycles(unsigned long long* host_out, int n) {
-  g_err[0] = 0;
-  if (!host_out || n <= 0 || n > 8 * 8192) return set_err(FA_ERR_BAD_ARG, "bad debug buffer");
-  FA_HIP_TRY(hipDeviceSynchronize());
-  FA_HIP_TRY(hipMemcpyFromSymbol(host_out, HIP_SYMBOL(fa::g_phase_cycles), (size_t)n * sizeof(unsigned long long)));
-  return FA_OK;
-}
-
-int fa_mi355x_set_tuning(int key, int value) {
-  if (key < 0 || key >= NTUN) return set_err(FA_ERR_BAD_ARG, "unknown tuning key");
-  g_tuning[key] = value;
-  return FA_OK;
-}
-#endif
-
 int fa_mi355x_measure_mfma_peak(double min_ms, double* tflops, double* clock_ghz, void* stream) {
   g_err[0] = 0;
   if (!tflops || !clock_ghz || !(min_ms > 0)) return set_err(FA_ERR_BAD_ARG, "bad argument");
@@ -1560,31 +1299,19 @@ int fa_mi355x_bwd_guarded(const void* q, const void* k, const void* v, const flo
                       causal ? 1 : 0, variant, dtype, stages, (hipStream_t)stream, tun, softmax_scale, (const float*)guard);
 }
 
-size_t fa_mi355x_bwd_workspace_bytes(int batch, int N, int d) {
+size_t fa_mi355x_bwd_workspace_bytes(int batch, int N, int /*d*/) {
   if (batch <= 0 || N <= 0) return 0;
-  const size_t rowc = (size_t)WS_VECS * batch * N * sizeof(float);
-  const size_t extra = fused_extra_bytes(batch, N, d);
-  return extra ? align256z(rowc) + extra : rowc;
+  return (size_t)WS_VECS * batch * N * sizeof(float);
 }
 
-size_t fa_mi355x_bwd_workspace_bytes_ex(int batch, int N, int d, const int* opts, int nopts) {
-  const size_t plain = fa_mi355x_bwd_workspace_bytes(batch, N, d);
-  if (!plain || !opts || nopts < 5 || opts[4] != 3) return plain;
-  const size_t rowc = (size_t)WS_VECS * batch * N * sizeof(float);
-  const size_t extra = chain_extra_bytes(batch, N, d, device_cus());
-  return std::max(plain, extra ? align256z(rowc) + extra : rowc);
+size_t fa_mi355x_bwd_workspace_bytes_ex(int batch, int N, int d, const int* /*opts*/, int /*nopts*/) {
+  return fa_mi355x_bwd_workspace_bytes(batch, N, d);
 }
 
-int fa_mi355x_bwd_status(const void* workspace, int batch, int N, int d, int* status) {
+int fa_mi355x_bwd_status(const void* workspace, int batch, int N, int /*d*/, int* status) {
   g_err[0] = 0;
   if (!workspace || !status || batch <= 0 || N <= 0) return set_err(FA_ERR_BAD_ARG, "bad argument");
   *status = 0;
-  if (!fused_extra_bytes(batch, N, d)) return FA_OK;
-  unsigned word = 0;
-  FA_HIP_TRY(hipMemcpy(&word, (const char*)workspace + align256z((size_t)WS_VECS * batch * N * sizeof(float)), sizeof(word),
-                       hipMemcpyDeviceToHost));
-  *status = (int)word;
-  if (word) return set_err(FA_ERR_HIP, "one-pass backward: a hand-off wait timed out (a chain member was not running)");
   return FA_OK;
 }
 

@@ -123,7 +123,7 @@ bwd_dkdv_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
   // Stage copies of Q and dO.  bf16, d >= 64: LDS-DMA, 1 KiB pieces (half an 8-row group at d = 128), the image's chunk swizzle
   // applied to each lane's source address; wave w moves pieces w, w + NW, ... (same swizzle parity, one lane offset) -- no
   // staging registers, no ds_write pass.  Otherwise (fp32's padded image, d = 32): registers, written after the MFMA phase.
-  constexpr bool DMA = sizeof(T) == 2 && D >= 64 && MODE != 9 && MODE != 13;   // MODE 13: slot path on register staging (A/B)
+  constexpr bool DMA = sizeof(T) == 2 && D >= 64;
   constexpr int PPG = D >= 128 ? 2 : 1;                          // pieces per 8-row group
   constexpr int NP = QS * D * (int)sizeof(T) / 1024, NPW = DMA ? NP / NW : 0;
   static_assert(!DMA || (NP % NW == 0 && NW % 4 == 0), "every wave moves whole pieces of one swizzle parity");
@@ -177,13 +177,6 @@ bwd_dkdv_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
   }
   __syncthreads();
 
-  constexpr bool DIAG = MODE == 9 || MODE == 93;
-  unsigned long long ph[6] = {0, 0, 0, 0, 0, 0};
-  unsigned long long k_t0 = 0, k_r0 = 0;
-  if constexpr (DIAG) {
-    k_t0 = stamp();
-    k_r0 = __builtin_amdgcn_s_memrealtime();
-  }
   // Stages whose query rows may see fewer than 64 admissible keys (the first rows under the causal mask, N < 64, a key mask or
   // dropout thinning the row) take the per-sub-slice path, where P and dS enter the dV / dK products as two bf16 fragments each
   // (Atom::pack_lo): on such rows their 2^-9 rounding is not averaged out (bf16 only; wave-uniform).
@@ -193,10 +186,7 @@ bwd_dkdv_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
   auto slice = [&](auto par, int qi) {
     constexpr int PAR = decltype(par)::value;
     const bool more = qi + 1 < nqi;
-    unsigned long long t0 = 0, t1 = 0, t2 = 0, t3 = 0;
-    if constexpr (DIAG) t0 = stamp();
     if (more) stage_load(qi + 1, (PAR ^ 1) * BUF);
-    if constexpr (DIAG) { t1 = stamp(); ph[0] += t1 - t0; }
     lds_char* buf = smem + PAR * BUF;
     lds_char* tq = buf;
     lds_char* tdo = buf + TB;
@@ -208,7 +198,7 @@ bwd_dkdv_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
     //   slots 0-7   S', dP' of sub-slice i+1 (row constants enter as accumulator inputs)   | exp of sub-slice i
     //   slots 8-15  dV^T += dO^T P, dK^T += Q^T dS of sub-slice i                           | mul / pack of sub-slice i
     // LDS fragments are requested four slots before the MFMA that consumes them.
-    constexpr bool SLOT = !HD && (MODE == 3 || MODE == 93 || MODE == 13) && NSUB == 4 && D == 64 && KT == 1 && sizeof(T) == 2;
+    constexpr bool SLOT = !HD && MODE == 3 && NSUB == 4 && D == 64 && KT == 1 && sizeof(T) == 2;
     if constexpr (SLOT) {
       const bool fast3 = !careful_stage(qi) && (kw0 < N) && (!causal || qi * QS >= kw0 + KPW - 1);   // wave-uniform
       if (fast3) {
@@ -328,15 +318,11 @@ bwd_dkdv_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
         ld_c(cD, 4 * QS, 0);
         rdo[0] = A::template row_frag<D>(tdo, ra, 0, 0);
         SB();
-        if constexpr (DIAG) t1 = stamp();
         period(ic<0>{}, ic<-1>{}, sA, dpA, sB, dpB);
-        if constexpr (DIAG) { t2 = stamp(); ph[1] += t2 - t1; }
         period(ic<1>{}, ic<0>{}, sB, dpB, sA, dpA);
         period(ic<2>{}, ic<1>{}, sA, dpA, sB, dpB);
         period(ic<3>{}, ic<2>{}, sB, dpB, sA, dpA);
-        if constexpr (DIAG) { t3 = stamp(); ph[2] += t3 - t2; }
         period(ic<-1>{}, ic<3>{}, sA, dpA, sB, dpB);
-        if constexpr (DIAG) { t0 = stamp(); ph[3] += t0 - t3; }
       }
     }
     // ---- software-pipelined fast path (stage fully unmasked): S, dP of sub-slice i+1 are issued before the
@@ -428,7 +414,6 @@ bwd_dkdv_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
       if (active) {
         // register i of lane half h is query qi0 + acc_row(i, h): its nlc / -delta come from LDS (broadcast reads);
         // -delta enters the dP tile as the accumulator input of its first MFMA
-        if constexpr (DIAG) t1 = stamp();
         f32x16 nl16, nd16;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
@@ -458,7 +443,6 @@ bwd_dkdv_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
           }
         }
         const bool need_mask = causal && (kw0 + KPW - 1 > qi0);  // wave-uniform
-        if constexpr (DIAG) { t2 = stamp(); ph[1] += t2 - t1; }
 #pragma unroll
         for (int kt = 0; kt < KT; ++kt)
 #pragma unroll
@@ -490,19 +474,6 @@ bwd_dkdv_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
             pf[kt][s2] = A::pack(s[kt], s2);
             dsf[kt][s2] = A::pack(dp[kt], s2);
           }
-        if constexpr (DIAG) {
-#pragma unroll
-          for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-              for (int j = 0; j < 4; ++j) {   // pin the VALU phase in front of the stamp
-                asm volatile("" ::"v"(__builtin_bit_cast(u32x4, pf[kt][s2])[j]));
-                asm volatile("" ::"v"(__builtin_bit_cast(u32x4, dsf[kt][s2])[j]));
-              }
-          t3 = stamp();
-          ph[2] += t3 - t2;
-        }
         if (!(CARE && (thin || (A::SPLITS && (causal ? qi0 < 64 : N < 64))))) {
 #pragma unroll
           for (int dt = 0; dt < DT; ++dt)
@@ -542,14 +513,10 @@ bwd_dkdv_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
               }
             }
         }
-        if constexpr (DIAG) { t0 = stamp(); ph[3] += t0 - t3; }
       }
     }
-    if constexpr (DIAG) t0 = stamp();
     if (more) stage_store(smem + (PAR ^ 1) * BUF);
-    if constexpr (DIAG) { t1 = stamp(); ph[4] += t1 - t0; }
     __syncthreads();
-    if constexpr (DIAG) { t2 = stamp(); ph[5] += t2 - t1; }
   };
   int qi = qi_begin;
   for (; qi + 1 < nqi; qi += 2) {
@@ -558,15 +525,6 @@ bwd_dkdv_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
   }
   if (qi < nqi) slice(ic<0>{}, qi);
 
-  if constexpr (DIAG) {
-    const int slot = blockIdx.x * NW + w;
-    const unsigned long long k_t1 = stamp(), k_r1 = __builtin_amdgcn_s_memrealtime();
-    if (slot < 8192 && lane == 0) {
-      for (int j = 0; j < 6; ++j) g_phase_cycles[slot * 8 + j] = ph[j];
-      g_phase_cycles[slot * 8 + 6] = k_t1 - k_t0;   // wave lifetime in shader cycles
-      g_phase_cycles[slot * 8 + 7] = k_r1 - k_r0;   // the same in 100 MHz ticks
-    }
-  }
 #pragma unroll
   for (int kt = 0; kt < KT; ++kt) {
     const int key = kw0 + 32 * kt + r;
@@ -614,14 +572,14 @@ bwd_dkdv_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
 // a head's Q / dO stream is still shared through the XCD's L2; consecutive key blocks of ONE head per workgroup lost that sharing
 // and measured 9 % slower at B = 32): the last stage iteration of a head requests stage 0 of the next head into the next ring slot,
 // the next head's K / V fragments are requested before the dK / dV stores of the finished one are issued, and nothing waits for
-// those stores.  In-kernel stamps (tools/phase_cycles.py 393) put the un-overlapped head and tail of a
+// those stores.  In-kernel stamps (round 3) put the un-overlapped head and tail of a
 // one-block workgroup at 8 % of its life (1.6 k cycles of set-up, 5.5 k waiting for fragments and stage 0, 7 k until the stores
 // have drained, of 200 k): with one workgroup per CU nothing else runs there meanwhile.
 // Scaling: tau*log2(e) is folded into the K fragments once per key block (re-rounded to bf16) and the row constant arrives in log2
 // units (nl2 = -L*log2(e), the workspace's third vector), so S' = Q (cK)^T + nl2 leaves the MFMA chain as the exp2 argument: ONE
 // instruction per score.  The sub-slices of queries 0..63 in the causal build's diagonal block (fewer than 64 admissible keys) take
 // the unscaled K and the fp32 fma instead.  The launcher never sends a key mask here.
-template <typename T, int D, int DIAG = 0, bool CDIAG = false, bool TILED = false>
+template <typename T, int D, bool CDIAG = false, bool TILED = false>
 __global__ void __launch_bounds__(512)
 bwd_dkdv_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, const T* __restrict__ dout,
                      const float* __restrict__ nl2, const float* __restrict__ ndelta, float* __restrict__ dk,
@@ -639,25 +597,12 @@ bwd_dkdv_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* 
 
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  static_assert(!CDIAG || DIAG == 0, "causal build: no stamps");
-  unsigned long long k_t00 = 0;
-  if constexpr (DIAG) k_t00 = stamp();   // first instruction of the wave
-  static_assert(!TILED || DIAG == 0, "tiled builds: no stamps");
-  // CT (round 4): the causal tiled build.  A workgroup takes key blocks p (heavy: it sweeps the most query stages) and nkb-1-p (light)
-  // of lay.tiles consecutive heads, one UNIT after the other, without leaving the ring: every workgroup does the same work (a pair
-  // sweeps nkb-1 blocks' worth of stages plus two diagonal blocks), so no ranking is needed; the first stage of the next unit is
-  // requested while the diagonal block of the current one is worked off, its K / V fragments before the dK / dV stores are issued.
-  constexpr bool CT = CDIAG && TILED;
+  static_assert(!(CDIAG && TILED), "tiled builds: non-causal");
   const int tiles = TILED ? max(lay.tiles, 1) : 1;   // heads per workgroup (the launcher sizes the grid with BH / tiles head groups)
   int bh, kb;   // (causal build: key block 0 sweeps the most query stages: the heaviest blocks of all heads are dispatched first)
-  int pair = 0;
-  if (CT) {
-    map_block(blockIdx.x, BH / tiles, nkb / 2, bh, pair);   // (the launcher sends even nkb only)
-    kb = pair;
-  } else if (CDIAG) map_block_ranked(blockIdx.x, BH, nkb, max(lay.rank_chunk, 1), bh, kb);
+  if (CDIAG) map_block_ranked(blockIdx.x, BH, nkb, max(lay.rank_chunk, 1), bh, kb);
   else map_block(blockIdx.x, BH / tiles, nkb, bh, kb);
   bh *= tiles;
-  const int nunits = CT ? 2 * tiles : 1;
   size_t base = head_base(lay, bh);
   const int ld = lay.ld;
   const uint32_t mat_bytes = ((uint32_t)(N - 1) * ld + D) * (uint32_t)sizeof(T);
@@ -671,17 +616,12 @@ bwd_dkdv_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* 
   raw_rsrc_t nlraw = make_raw_rsrc(nlv + (size_t)bh * N, (uint32_t)N * 4u);
   raw_rsrc_t ndraw = make_raw_rsrc(ndelta + (size_t)bh * N, (uint32_t)N * 4u);
   const float c = tau * LOG2E;
-  int kw0 = kb * BK + w * KPW;
-  const bool active = CT || kw0 < N;   // wave-uniform: a wave whose keys all lie past N only moves data and joins the barriers
-                                       // (tiled builds: N is a multiple of 256, every wave of every block is active)
+  const int kw0 = kb * BK + w * KPW;
+  const bool active = kw0 < N;   // wave-uniform: a wave whose keys all lie past N only moves data and joins the barriers
+                                 // (tiled builds: N is a multiple of 256, every wave of every block is active)
   frag kf[KC], vf[KC];
   auto load_kv = [&](int k0) {
-    int rr = r, hh = h;
-    if constexpr (CDIAG && TILED) {   // (lane constants re-derived where the unit loop needs them instead of carried through its sweep)
-      const int l2 = lane_fresh();
-      rr = l2 & 31;
-      hh = l2 >> 5;
-    }
+    const int rr = r, hh = h;   // (copies, and the lambda `block` below: the form whose register assignment hipcc gave the measured builds)
 #pragma unroll
     for (int kc = 0; kc < KC; ++kc) {
       const int off = ((k0 + rr) * ld + 16 * kc + 8 * hh) * (int)sizeof(T);   // rows >= N read as zero
@@ -695,7 +635,7 @@ bwd_dkdv_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* 
 #pragma unroll
     for (int kc = 0; kc < KC; ++kc) kf[kc] = A::scale(kf[kc], c);
   };
-  int key = kw0 + r;
+  const int key = kw0 + r;
   f32x16 acc_dk[2], acc_dv[2];
 #pragma unroll
   for (int dt = 0; dt < 2; ++dt) {
@@ -726,34 +666,18 @@ bwd_dkdv_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* 
   };
   int roff = 0;   // tiled build: ring position of the current block's stage 0
   auto slot_of = [&](int st) { return ((st + roff) % 3) * BUF; };
-  unsigned long long ph[6] = {0, 0, 0, 0, 0, 0}, k_t0 = 0, k_r0 = 0, t0 = 0, t1 = 0;
-  if constexpr (DIAG) {
-    k_t0 = stamp();
-    k_r0 = __builtin_amdgcn_s_memrealtime();
-  }
-  // MODE: which scaling's copy of the sweep the loop holds: 0 = folded, 1 = fp32, 2 = both behind a branch (every build but the causal
-  // tiled one, whose unit loop carries its state around the sweep: with both copies inside it hipcc spilled 187 registers, so that
-  // build takes the branch outside and holds two copies of the whole loop)
-  auto units = [&](auto mode_c) {
-  constexpr int MODE = decltype(mode_c)::value;
-  for (int u = 0;; ++u) {   // units of the causal tiled build (every other build: one pass)
-  int nbh = bh, nkbk = kb, nst0 = 0, nroff = 0;   // (causal tiled build: the unit after this one)
-  bool nsweep = false;
+  auto block = [&]() {   // the workgroup's key block(s): the sweep, then (causal build) the diagonal block
   const int st0 = CDIAG ? 2 * (kb + 1) : 0;   // first stage of the sweep (causal build: the stage below the diagonal block)
   if (!CDIAG || st0 < nst) {
-  if (!(CT && u > 0)) {   // (later units: requested during the previous unit's diagonal block, published by the barrier behind it)
-    stage_dma(st0, slot_of(st0));
-    dma_wait_all();
-  }
-  if constexpr (DIAG) { ph[4] = k_t0 - k_t00; ph[5] = stamp() - k_t0; }   // set-up + fragment-load issue; wait for fragments + stage 0
+  stage_dma(st0, slot_of(st0));
+  dma_wait_all();
   // The K / V fragments are tracked loads whose first use sits behind `if (active)`: without an unconditional use HERE (where
   // everything has landed anyway) hipcc re-emits their s_waitcnt vmcnt(7..0) inside the stage loop, where they wait out the
   // LDS-DMA of the next stage that the loop has just issued.
 #pragma unroll
   for (int kc = 0; kc < KC; ++kc) asm volatile("" ::"v"(kf[kc]), "v"(vf[kc]));
   scale_k();
-  if (!(CT && u > 0)) __syncthreads();
-  if constexpr (DIAG) { t0 = stamp(); ph[0] += t0 - k_t0; }
+  __syncthreads();
 
   // (two copies of the sweep, one per scaling: the fp32 multiply of the exact one exists in its own instruction stream only)
   auto sweep = [&](auto ex_c) {
@@ -873,8 +797,7 @@ bwd_dkdv_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* 
   };
   auto T1 = ic<1>{};
   auto T0 = ic<0>{};
-  const int heads_here = CDIAG ? 1 : tiles;   // (the causal tiled build loops over its units outside the sweep)
-  for (int t = 0; t < heads_here; ++t) {
+  for (int t = 0; t < tiles; ++t) {
   if (TILED && t) {   // the fragments of this head were requested before the previous head's stores (see below)
 #pragma unroll
     for (int kc = 0; kc < KC; ++kc) asm volatile("" ::"v"(kf[kc]), "v"(vf[kc]));
@@ -897,7 +820,7 @@ bwd_dkdv_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* 
     const int nr0 = ra.b[0] + nb, nr1 = ra.b[1] + nb, nh16 = 16 * h + nb;
     if (st + 1 < nst) stage_dma(st + 1, nb);
     else if (CDIAG) stage_dma(2 * kb, nb);   // the first stage of the diagonal block follows the sweep in the ring
-    else if (TILED && t + 1 < heads_here) {   // the next head's sweep: its stage 0 follows in the ring
+    else if (TILED && t + 1 < tiles) {   // the next head's sweep: its stage 0 follows in the ring
       const size_t nbase = head_base(lay, bh + 1);
       qraw = make_raw_rsrc(q + nbase, mat_bytes);
       doraw = make_raw_rsrc(dout + nbase, mat_bytes);
@@ -909,11 +832,8 @@ bwd_dkdv_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* 
       period(T1, T1, ic<1>{}, ic<0>{}, ic<2>{}, cr0, cr1, ct0, ct1, cr0, cr1, ch16, sB, dpB, sA, dpA);
       period(T1, T1, ic<2>{}, ic<1>{}, ic<3>{}, cr0, cr1, ct0, ct1, cr0, cr1, ch16, sA, dpA, sB, dpB);
     }
-    if constexpr (DIAG) { t1 = stamp(); ph[1] += t1 - t0; }
     dma_wait_all();   // this wave's pieces of the next stage have landed
-    if constexpr (DIAG) { t0 = stamp(); ph[2] += t0 - t1; }
     __syncthreads();
-    if constexpr (DIAG) { t1 = stamp(); ph[3] += t1 - t0; t0 = t1; }
     if (CDIAG && st + 1 == nst) stage_dma(2 * kb + 1, slot_of(nst + 1));   // second diagonal stage: the slot of stage nst-2 is free now
     if (active) {
       // sub-slice 0 of the next stage is requested from here on (after the last stage: stale data, results unused)
@@ -923,11 +843,11 @@ bwd_dkdv_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* 
     cr0 = nr0; cr1 = nr1; ch16 = nh16;
     ct0 = ta.b[0] + nb; ct1 = ta.b[1] + nb;
   }
-  if constexpr (TILED && !CDIAG) {   // hand over to the next head: its fragments are requested before this head's stores are issued
+  if constexpr (TILED) {   // hand over to the next head: its fragments are requested before this head's stores are issued
     // (requesting them a stage ahead into spare registers, so that the pipeline never refills, spilled: 256 VGPRs + 128 B)
     float* dkrow = dk + base + (size_t)key * ld;
     float* dvrow = dv + base + (size_t)key * ld;
-    if (t + 1 < heads_here) {
+    if (t + 1 < tiles) {
       ++bh;
       base = head_base(lay, bh);
       krs = make_rsrc(k + base, mat_bytes);
@@ -952,13 +872,9 @@ bwd_dkdv_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* 
   }
   }   // heads of this workgroup
   };
-  if constexpr (MODE == 2) {
-    if (exact) sweep(ic<1>{});
-    else sweep(ic<0>{});
-  } else {
-    sweep(ic<MODE>{});
-  }
-  if constexpr (TILED && !CDIAG) return;
+  if (exact) sweep(ic<1>{});
+  else sweep(ic<0>{});
+  if constexpr (TILED) return;
   }
   if constexpr (CDIAG) {
     // The diagonal block: queries kb * 256 .. + 255 = stages 2 * kb, 2 * kb + 1, in the ring slots of stages nst, nst + 1.
@@ -969,26 +885,6 @@ bwd_dkdv_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* 
     }
     dma_wait_all();
     __syncthreads();
-    // Causal tiled build: the next unit (the pair's light block, then the next head's heavy one).  The slot of the sweep's last stage
-    // is free from here on (every wave is past the sweep): the next unit's first stage goes there while this block is worked off.
-    if constexpr (CT) {
-      if (u + 1 < nunits) {
-        if (u & 1) { nbh = bh + 1; nkbk = pair; }
-        else nkbk = nkb - 1 - pair;
-        nst0 = 2 * (nkbk + 1);
-        nsweep = nst0 < nst;
-        const size_t nbase = head_base(lay, nbh);
-        qraw = make_raw_rsrc(q + nbase, mat_bytes);      // (the diagonal block below reads LDS only)
-        doraw = make_raw_rsrc(dout + nbase, mat_bytes);
-        nlraw = make_raw_rsrc(nlv + (size_t)nbh * N, (uint32_t)N * 4u);
-        ndraw = make_raw_rsrc(ndelta + (size_t)nbh * N, (uint32_t)N * 4u);
-        if (nsweep) {
-          const int free_slot = (nst + 2 + roff) % 3;                // = the slot of stage nst - 1
-          nroff = ((free_slot - nst0) % 3 + 3) % 3;                  // slot_of(nst0) under the next unit's ring position
-          stage_dma(nst0, free_slot * BUF);
-        }
-      }
-    }
     for (int j = w; j < 8; ++j) {
       lds_char* tq = smem + slot_of(nst + (j >> 2));
       lds_char* tdo = tq + TB;
@@ -1084,51 +980,9 @@ bwd_dkdv_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* 
       }
     }
   }
-  if constexpr (CT) {
-    if (u + 1 < nunits) {
-      dma_wait_all();     // this wave's pieces of the next unit's first stage have landed
-      __syncthreads();    // every wave is done with the diagonal block's stages; the prefetched stage is published
-      const int l2 = lane_fresh();
-      const int h2 = l2 >> 5;
-      float* dkrow = dk + base + (size_t)(kw0 + (l2 & 31)) * ld;
-      float* dvrow = dv + base + (size_t)(kw0 + (l2 & 31)) * ld;
-      bh = nbh;
-      kb = nkbk;
-      base = head_base(lay, bh);
-      krs = make_rsrc(k + base, mat_bytes);
-      vrs = make_rsrc(v + base, mat_bytes);
-      kw0 = kb * BK + w * KPW;
-      load_kv(kw0);       // requested before the finished unit's stores are issued
-      if (nsweep) roff = nroff;
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          f32x4 a = {acc_dk[dt][4 * g] * tau, acc_dk[dt][4 * g + 1] * tau, acc_dk[dt][4 * g + 2] * tau, acc_dk[dt][4 * g + 3] * tau};
-          f32x4 b = {acc_dv[dt][4 * g], acc_dv[dt][4 * g + 1], acc_dv[dt][4 * g + 2], acc_dv[dt][4 * g + 3]};
-          *reinterpret_cast<f32x4*>(dkrow + 32 * dt + 8 * g + 4 * h2) = a;
-          *reinterpret_cast<f32x4*>(dvrow + 32 * dt + 8 * g + 4 * h2) = b;
-        }
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt) {
-        acc_dk[dt] = zero16();
-        acc_dv[dt] = zero16();
-      }
-      continue;
-    }
-  }
-  break;
-  }   // units
   };
-  if constexpr (CT) {
-    if (exact) units(ic<1>{});
-    else units(ic<0>{});
-  } else {
-    units(ic<2>{});
-  }
-  if constexpr (TILED && !CDIAG) return;
-  if constexpr (DIAG) ph[1] += stamp() - t0;
-  if constexpr (CT) key = kw0 + (lane_fresh() & 31);
+  block();
+  if constexpr (TILED) return;
   if (key < N) {
     float* dkrow = dk + base + (size_t)key * ld;
     float* dvrow = dv + base + (size_t)key * ld;
@@ -1141,16 +995,6 @@ bwd_dkdv_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* 
         *reinterpret_cast<f32x4*>(dkrow + 32 * dt + 8 * g + 4 * h) = a;
         *reinterpret_cast<f32x4*>(dvrow + 32 * dt + 8 * g + 4 * h) = b;
       }
-  }
-  if constexpr (DIAG) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the stores have left: upper bound of the epilogue
-    const unsigned long long k_t2 = stamp(), k_r1 = __builtin_amdgcn_s_memrealtime();
-    const int slot = blockIdx.x * 8 + w;
-    if (slot < 8192 && lane == 0) {
-      for (int j = 0; j < 6; ++j) g_phase_cycles[slot * 8 + j] = ph[j];
-      g_phase_cycles[slot * 8 + 6] = k_t2 - k_t00;   // wave lifetime, first instruction to stores drained
-      g_phase_cycles[slot * 8 + 7] = k_r1 - k_r0;
-    }
   }
 }
 

@@ -293,7 +293,7 @@ bwd_dq_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restr
 // iteration of a head requests key stage 0 of the NEXT head into the next ring slot (the ring simply goes on: stage j of the next head
 // is ring stage nstage + j), so the next head starts at its prologue period with no DMA wait and no barrier, and its Q / dO / O loads
 // run while the dQ stores of the finished one drain.
-template <typename T, int D, int DIAG = 0, bool MASKS = true, bool CDIAG = false, bool TILED = false>
+template <typename T, int D, bool MASKS = true, bool CDIAG = false, bool TILED = false>
 __global__ void __launch_bounds__(512)
 bwd_dq_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, const T* __restrict__ dout,
                    const float* __restrict__ nlc, const float* __restrict__ ndelta, float* __restrict__ dq, int N, int nqb,
@@ -310,8 +310,8 @@ bwd_dq_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __
 
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  static_assert(!CDIAG || (!MASKS && DIAG == 0), "causal build: unmasked sweep + diagonal block");
-  static_assert(!TILED || (!MASKS && !CDIAG && DIAG == 0), "tiled build: non-causal, unmasked, no stamps");
+  static_assert(!CDIAG || !MASKS, "causal build: unmasked sweep + diagonal block");
+  static_assert(!TILED || (!MASKS && !CDIAG), "tiled build: non-causal, unmasked");
   const int tiles = TILED ? max(lay.tiles, 1) : 1;   // heads per workgroup (the launcher sizes the grid with BH / tiles head groups)
   const bool ranked = CDIAG && causal == 2;   // A/B: one block per workgroup, heaviest blocks of all heads first
   const int nblk = (CDIAG && !ranked) ? (nqb + 1) / 2 : nqb;
@@ -399,11 +399,6 @@ bwd_dq_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __
       dma16(vraw, smem_addr + slot_base + VOFF + 1024 * g, dma_voff, soff);
     }
   };
-  unsigned long long ph[6] = {0, 0, 0, 0, 0, 0}, k_t0 = 0, k_r0 = 0, t0 = 0, t1 = 0;
-  if constexpr (DIAG == 1) {
-    k_t0 = stamp();
-    k_r0 = __builtin_amdgcn_s_memrealtime();
-  }
   if constexpr (MASKS) {   // see fwd_slot_kernel: stage rows past N must read as zeros
 #pragma unroll 4
     for (int off = tid * 16; off < 6 * TB; off += 512 * 16) *FA_LDS(u32x4, smem + off) = u32x4{0u, 0u, 0u, 0u};
@@ -420,7 +415,6 @@ bwd_dq_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __
     dma_wait_all();   // this wave's pieces have landed
     __syncthreads();
   }
-  if constexpr (DIAG == 1) { t0 = stamp(); ph[0] += t0 - k_t0; }
 
   if (lay.young_prio && w >= 4) __builtin_amdgcn_s_setprio(1);   // the later-dispatched half loses VALU arbitration otherwise
   // (the mask-free builds carry two copies of the sweep, one per scaling: the fp32 multiply exists in the exact one's stream only)
@@ -583,11 +577,8 @@ bwd_dq_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __
       period(T1, T1, T1, T0, ic<2>{}, ic<0>{}, ic<3>{}, cr0, cr1, ct0, ct1, cr0, cr1, kb + 32, sA, dpA, sB, dpB, dsA0, dsA1, dsB0, dsB1);
     }
     // the next stage goes to LDS and is published before the second half of period 4st+2 asks for its rows
-    if constexpr (DIAG == 1) { t1 = stamp(); ph[1] += t1 - t0; }
     dma_wait_all();   // this wave's pieces of the next stage have landed
-    if constexpr (DIAG == 1) { t0 = stamp(); ph[2] += t0 - t1; }
-    if constexpr (DIAG != 2) __syncthreads();   // DIAG 2: timing ablation without the per-stage barrier (results are wrong)
-    if constexpr (DIAG == 1) { t1 = stamp(); ph[3] += t1 - t0; t0 = t1; }
+    __syncthreads();
     // period 4st+2: produce sub 3, consume sub 2, dQ of sub 1; rows two ahead = sub 0 of the next stage
     if constexpr (MASKS) {
       if (need(2)) period(T1, T1, T1, T1, ic<3>{}, ic<1>{}, ic<0>{}, cr0, cr1, ct0, ct1, nr0, nr1, kb + 64, sB, dpB, sA, dpA, dsB0, dsB1, dsA0, dsA1);
@@ -675,16 +666,6 @@ bwd_dq_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __
     }
   }
 
-  if constexpr (DIAG == 1) {
-    const unsigned long long k_t1 = stamp(), k_r1 = __builtin_amdgcn_s_memrealtime();
-    ph[1] += k_t1 - t0;
-    const int slot = blockIdx.x * 8 + w;
-    if (slot < 8192 && lane == 0) {
-      for (int j = 0; j < 6; ++j) g_phase_cycles[slot * 8 + j] = ph[j];
-      g_phase_cycles[slot * 8 + 6] = k_t1 - k_t0;
-      g_phase_cycles[slot * 8 + 7] = k_r1 - k_r0;
-    }
-  }
   // (the output address is formed HERE from opaque copies: computed before the loop, hipcc keeps it in three registers the
   // masked build does not have and spills them around the loop)
   int qr = qrow, hh = h;

@@ -2,7 +2,7 @@
 // dQ, dK and dV -- the five products of the reference's single-pass FA-2 backward (src/flash_attn2_bw.cu:94-247: S, dP, dV, dK, dQ),
 // dQ summed over the key blocks with fp32 atomics as the reference does (:228).  Part of the kernel set described in fa_kernels.h.
 //
-// Why it pays HERE and not for bf16 (fa_bwd_chain.h, profiles/r04_chain_backward.txt): the exact-fp32 MFMA (v_mfma_f32_32x32x2_f32 /
+// Why it pays HERE and not for bf16 (the retired bf16 one-pass backward, profiles/r04_chain_backward.txt): the exact-fp32 MFMA (v_mfma_f32_32x32x2_f32 /
 // 16x16x4_f32) runs at 1/16 of the bf16 rate, so the kernel is MFMA-bound by a wide margin and the two-kernel backward's seven
 // products for five cost their full 40 %; the same dQ adds (N/256 per element) that exceed the chip's ~1.3 TB/s atomic rate beside
 // bf16 MFMAs need a third of it beside fp32 ones (0.45 TB/s at any N: bytes and time both grow with N^2), spread evenly over the

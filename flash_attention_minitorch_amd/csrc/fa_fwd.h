@@ -385,7 +385,7 @@ FA_DEV void fwd_redo_rows(rsrc_t qrs, rsrc_t krs, rsrc_t vrs, int qrow, int q0, 
 // block, the classic way (true maximum, reference moved), masking the last one: at most two plain sub-tiles per wave instead of up
 // to eight (round 3).  Rows 0..63 (fewer than 64 admissible keys) split P into two bf16 fragments there (Atom::pack_lo), which is
 // what the phased CARE build does for them.
-template <typename T, int D, bool MASKS = true, int DIAG = 0, int STK = 8192 / D, int MINW = 2, bool CDIAG = false>
+template <typename T, int D, bool MASKS = true, int STK = 8192 / D, int MINW = 2, bool CDIAG = false>
 __global__ void __launch_bounds__(512, MINW)
 fwd_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, float* __restrict__ o,
                 float* __restrict__ aux_l, int N, int nqb, int BH, Layout lay, int causal, float tau) {
@@ -486,11 +486,6 @@ fwd_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
     }
   };
   auto slot_of = [&](int st) { return (st % R) * TB; };
-  unsigned long long ph[6] = {0, 0, 0, 0, 0, 0}, k_t0 = 0, k_r0 = 0, t0 = 0, t1 = 0;
-  if constexpr (DIAG == 1) {
-    k_t0 = stamp();
-    k_r0 = __builtin_amdgcn_s_memrealtime();
-  }
   if constexpr (MASKS) {   // ragged launches read stage rows past N: make sure they are zeros whatever an out-of-range
     // LDS-DMA lane does (0 * stale NaN bits would poison P.V); 96 / 128 KiB once per workgroup
 #pragma unroll 4
@@ -523,7 +518,6 @@ fwd_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
   }
   dma_wait_all();
   __syncthreads();
-  if constexpr (DIAG == 1) { t0 = stamp(); ph[0] += t0 - k_t0; }
 
   if (lay.young_prio && w >= 4) __builtin_amdgcn_s_setprio(1);   // the later-dispatched half loses VALU arbitration otherwise
   f32x16 sA, sB;
@@ -693,11 +687,8 @@ fwd_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
       } else {
         period(T1, T1, T1, T0, ic<2>{}, ic<0>{}, ic<3>{}, ic<1>{}, cr0, cr1, ct0, ct1, cr0, cr1, cr0, cr1, kb + 32, sA, sB, pA0, pA1, pB0, pB1);
       }
-      if constexpr (DIAG == 1) { t1 = stamp(); ph[1] += t1 - t0; }
       dma_wait_all();   // this wave's pieces of the next stage have landed
-      if constexpr (DIAG == 1) { t0 = stamp(); ph[2] += t0 - t1; }
       __syncthreads();
-      if constexpr (DIAG == 1) { t1 = stamp(); ph[3] += t1 - t0; t0 = t1; }
       // period 4st+2: produce sub 3, softmax of sub 2, P.V of sub 1; rows two ahead = sub 0 of the next stage
       if constexpr (MASKS) {
         if (need(2)) period(T1, T1, T1, T1, ic<3>{}, ic<1>{}, ic<0>{}, ic<2>{}, cr0, cr1, ct0, ct1, nr0, nr1, cr0, cr1, kb + 64, sB, sA, pB0, pB1, pA0, pA1);
@@ -715,11 +706,8 @@ fwd_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
     } else {
       // two sub-tiles per stage: stage st+1 (requested one stage ago) is published here, then stage st+2 is requested
       if (st > 0) {   // (stage 1 was waited for and published in the prologue)
-        if constexpr (DIAG == 1) { t1 = stamp(); ph[1] += t1 - t0; }
         dma_wait_all();
-        if constexpr (DIAG == 1) { t0 = stamp(); ph[2] += t0 - t1; }
-        if constexpr (DIAG != 2) __syncthreads();   // DIAG 2: timing ablation without the per-stage barrier (results are wrong)
-        if constexpr (DIAG == 1) { t1 = stamp(); ph[3] += t1 - t0; t0 = t1; }
+        __syncthreads();
       }
       if (CDIAG ? st + 2 < nstage + 4 : st + 2 < nstage) stage_dma((st + 2) * ST, slot_of(st + 2));   // (causal build: the diagonal block's four stages follow)
       // period 2st+0: produce sub 1, softmax of sub 0, P.V of sub 1 of the previous stage; rows two ahead: next stage, sub 0
@@ -836,7 +824,6 @@ fwd_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
     for (int j = 2 * (w >> 1); j <= w; ++j) diag_tile(j, nst_w == 0 && j == 0);
   }
 
-  if constexpr (DIAG == 1) { t1 = stamp(); ph[1] += t1 - t0; t0 = t1; }
   float l_tot = xhalf_sum(l_run);
   if constexpr (PRE) {   // a row sum outside [2^-96, 2^96] (or NaN): exp2(S') over- or underflowed somewhere in the wave's rows
     if (__any(!(l_tot >= 0x1p-96f && l_tot <= 0x1p96f))) {
@@ -875,17 +862,6 @@ fwd_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
       }
     if (hh == 0)
       aux_l[(size_t)bh * N + qr] = PRE ? (m_ref + __builtin_amdgcn_logf(l_tot)) * 0.6931471805599453f : m_ref * tau + __logf(l_tot);
-  }
-  if constexpr (DIAG == 1) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned long long k_t1 = stamp(), k_r1 = __builtin_amdgcn_s_memrealtime();
-    ph[4] += k_t1 - t0;   // epilogue: O / L stores
-    const int slot = blockIdx.x * 8 + w;
-    if (slot < 8192 && lane == 0) {
-      for (int j = 0; j < 6; ++j) g_phase_cycles[slot * 8 + j] = ph[j];
-      g_phase_cycles[slot * 8 + 6] = k_t1 - k_t0;
-      g_phase_cycles[slot * 8 + 7] = k_r1 - k_r0;
-    }
   }
   }   // pass
 }

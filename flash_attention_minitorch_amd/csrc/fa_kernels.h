@@ -27,7 +27,7 @@
 // a per-lane register computed once plus an instruction immediate, and every global tile load is a buffer load
 // whose tile offset is a scalar operand (out-of-range rows read as zero) -- no address VALU inside the loops.
 //
-// Files: fa_atoms.h (MFMA / LDS / LDS-DMA primitives), fa_common.h (constants, phase stamps, small helpers), fa_fwd.h (forward),
+// Files: fa_atoms.h (MFMA / LDS / LDS-DMA primitives), fa_common.h (constants, small helpers), fa_fwd.h (forward),
 // fa_bwd_dkdv.h (preprocess, dK / dV), fa_bwd_dq.h (dQ), fa_aux.h (sustained-peak loop, layout probes).
 #pragma once
 #include "fa_common.h"
@@ -36,8 +36,4 @@
 #include "fa_bwd_dkdv.h"
 #include "fa_bwd_dq.h"
 #include "fa_bwd_onepass_f32.h"
-#ifdef FA_DIAG
-#include "fa_bwd_fused.h"   // the one-pass backward: diagnostic build only (tools/check_fused.py)
-#include "fa_bwd_chain.h"   // its round-4 form (chained key blocks, fp32 atomics from the last one): tools/check_chain.py
-#endif
 #include "fa_aux.h"

@@ -90,8 +90,6 @@ def scale_guard(q, k, out=None):
 
 def _wants_guard(q, opts):
     """Could a folded-scale kernel run for these operands (bf16, d = 64 / 128, option 8 left at 0)?"""
-    if _lib.DIAG:
-        return False   # (tools/ on the diagnostic library: its process-wide default is the folded scale, option 8 = 1)
     return q.dtype == torch.bfloat16 and q.shape[-1] in (64, 128) and _scale_mode(opts) == 0
 
 
@@ -108,13 +106,6 @@ def _auto_guard(q, k, opts, guard):
     if not isinstance(guard, str):
         return guard
     return scale_guard(q, k) if _wants_guard(q, opts) else None
-
-
-OPTS_ONE_PASS_BWD = (0, 0, 0, 0, 2)   # DIAGNOSTIC LIBRARY ONLY (tools/check_fused.py): dQ inside the key-stationary kernel, ordered hand-off
-# DIAGNOSTIC LIBRARY ONLY (tools/check_chain.py): the chained one-pass backward (bf16, d = 64, non-causal, N % 256 == 0): five products
-# instead of seven, the running dQ tiles carried through memory along a workgroup's key blocks, fp32 atomics only from each chain's last
-# block (none when B*H >= CUs).  Measured 2-5 % slower than the two-kernel default from N = 2048 up (profiles/r04_chain_backward.txt).
-OPTS_CHAINED_BWD = (0, 0, 0, 0, 3)
 
 
 _NATIVE_D = (32, 64, 128)
@@ -199,15 +190,15 @@ def _workspace(bh, n, d, device, opts=None):
 
 
 def bwd_workspace(q, opts=None):
-    """Scratch for the backward of (.., N, d) tensors, sized by the library (fa_mi355x_bwd_workspace_bytes_ex: the chained
-    one-pass backward, OPTS_CHAINED_BWD, needs slabs for its running dQ tiles on top of the row constants)."""
+    """Scratch for the backward of (.., N, d) tensors, sized by the library (fa_mi355x_bwd_workspace_bytes_ex: the three
+    row-constant vectors)."""
     n, d = q.shape[-2], q.shape[-1]
     return _workspace(q.numel() // (n * d), n, _padded_d(d), q.device, opts)
 
 
 def bwd_status(workspace, q):
-    """Synchronous check of the one-pass backward's error word after a backward call that used ``workspace``; raises if a
-    hand-off wait timed out (fa_mi355x_bwd_status)."""
+    """Status of a backward call that used ``workspace`` (fa_mi355x_bwd_status): 0, as no kernel of the library waits for another
+    workgroup; kept for callers of the published ABI."""
     n, d = q.shape[-2], q.shape[-1]
     st = ctypes.c_int(0)
     _lib.check(_lib.core().fa_mi355x_bwd_status(_ptr(workspace), q.numel() // (n * d), n, d, ctypes.byref(st)))

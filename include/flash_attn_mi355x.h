@@ -89,19 +89,14 @@ int fa_mi355x_fwd(const void* q, const void* k, const void* v, float* out, float
                   int batch, int N, int d, int causal, int variant, int dtype, void* stream);
 
 /* Bytes of scratch fa_mi355x_bwd needs: 3 * batch * N floats (-L/tau, -rowsum(dO*O), -L*log2(e)).  Every backward entry point
- * below expects a workspace of at least this size.  (The diagnostic library adds the hand-off region of its round-2 one-pass
- * backward for d = 64, N a multiple of 256; the product library has no kernel that needs more.) */
+ * below expects a workspace of at least this size; no kernel of the library needs more. */
 size_t fa_mi355x_bwd_workspace_bytes(int batch, int N, int d);
 
-/* The same for a backward call with per-call options (fa_mi355x_bwd_ex).  Product library: fa_mi355x_bwd_workspace_bytes.  Diagnostic
- * library: opts[4] = 3 (the chained one-pass backward) adds a 4-KiB header and, when a chain is more than one key block (nchains <
- * N / 256), one slab of N * 64 floats per workgroup: batch * nchains * N * 256 bytes with nchains = the smallest divisor of N / 256
- * that gives batch * nchains >= CUs (256 MiB at batch 64, N 4096 on 256 CUs). */
+/* The same for a backward call with per-call options (fa_mi355x_bwd_ex): fa_mi355x_bwd_workspace_bytes, whatever the options. */
 size_t fa_mi355x_bwd_workspace_bytes_ex(int batch, int N, int d, const int* opts, int nopts);
 
-/* Product library: a no-op that sets *status = 0 (no kernel of it waits for another workgroup, and backward calls may run
- * concurrently on different streams).  Diagnostic library: the error word of the round-2 one-pass backward (a persistent grid with a
- * bounded-spin hand-off, opts[4] = 2) in a workspace the last backward call used; FA_ERR_HIP and a message when a wait timed out. */
+/* Sets *status = 0 and makes no HIP call: no kernel of the library waits for another workgroup, and backward calls may run
+ * concurrently on different streams.  Kept for callers that check a backward's workspace after the call. */
 int fa_mi355x_bwd_status(const void* workspace, int batch, int N, int d, int* status);
 
 /* Backward on device pointers.  out: float (the forward's output); out_grad: dtype elements;
@@ -133,7 +128,7 @@ int fa_mi355x_bwd_stages(const void* q, const void* k, const void* v, const floa
  *            of the keys each, partial (O, l, m) combined through LDS: the default of launches that would leave most of the chip idle,
  *            up to 128 workgroups of the phased kernel, 256 under the causal mask), 2 = never
  *   opts[2]  dQ kernel: 2 = phased with 32-key tiles (fp32 scaling), 3 = slot kernel also under the causal mask
- *   opts[3]  (diagnostic library only)
+ *   opts[3]  reserved, must be 0
  *   opts[4]  1 = keep the separate preprocess kernel (default: the dQ launch preprocesses its own rows, writes the workspace and runs
  *            BEFORE the dK/dV launch; same results up to summation order of delta);
  *            4 / 5 = fp32, d = 64: two kernels always / the ONE-PASS backward whatever the launch size.  By default an fp32, d = 64
@@ -150,7 +145,7 @@ int fa_mi355x_bwd_stages(const void* q, const void* k, const void* v, const floa
  *   opts[5]  1 = the non-causal d = 64 dK/dV kernel takes one head per workgroup (default: key block kb of several consecutive heads
  *            per workgroup when the launch still covers every CU), and so does the non-causal d = 64 dQ kernel (default: query block
  *            qb of several consecutive heads, same condition); bitwise the same results
- *   opts[6]  (diagnostic library only)
+ *   opts[6]  reserved, must be 0
  *   opts[7]  block order of causal launches: 1 = query blocks p and nqb-1-p paired in one workgroup (slot and phased forward / dQ
  *            kernels) and head-by-head order for the unpaired dK/dV launches (fp32 d = 64, bf16 d = 128); 2 = one block per
  *            workgroup dispatched longest first across a chunk of heads, everywhere; 0 = per kernel what measured faster (slot
@@ -164,10 +159,8 @@ int fa_mi355x_bwd_stages(const void* q, const void* k, const void* v, const floa
  *            relative: |error| <= 2e-3 |o|, i.e. above the 1e-3 parity bound once |o| > 0.5; fp32 stays the default and the parity
  *            path).  For consumers that take a bf16 activation, e.g. the sharded gather of BASELINE configs[4] at half the bytes.  The
  *            backward needs the fp32 `out` of a default forward.
- * Values that lost their A/B (opts[0] = 1 / 2, opts[1] = 6, opts[2] = 1 / 4, opts[3] = 1, opts[4] = 2 / 3 = the one-pass
- * backwards, opts[6] = 1) exist in the diagnostic library only; the product library answers them with FA_ERR_BAD_ARG.
- * Every value selects kernels with the same results within the stated tolerances; stamp / ablation builds are not in this
- * library (FA_ERR_BAD_ARG).  `stages` as fa_mi355x_bwd_stages. */
+ * Any other value is answered with FA_ERR_BAD_ARG before any HIP call.  Every accepted value selects kernels with the same results
+ * within the stated tolerances.  `stages` as fa_mi355x_bwd_stages. */
 int fa_mi355x_fwd_ex(const void* q, const void* k, const void* v, float* out, float* l, float* m, int batch, int N, int d,
                      int causal, int variant, int dtype, const int* opts, int nopts, void* stream);
 int fa_mi355x_bwd_ex(const void* q, const void* k, const void* v, const float* out, const void* out_grad, float* q_grad,
@@ -283,17 +276,6 @@ const char* fa_mi355x_last_error(void);
 
 /* Library version, e.g. "flash_attn_mi355x 0.1 gfx950". */
 const char* fa_mi355x_version(void);
-
-/* ---- diagnostic build only (libflash_attn_mi355x_diag.so, compiled with -DFA_DIAG; used by tools/, never by the product
- * path or the tests) ----
- * fa_mi355x_set_tuning: process-wide defaults for the option slots of fa_mi355x_*_ex, plus the values the product library
- * rejects: stamp builds (opts[0] = 9 / 93 / 193, opts[1] = 93, opts[2] = 93), the register-staging A/B build (opts[0] = 13), the
- * barrier-less dQ timing ablation (opts[2] = 94, WRONG results) and opts[5] = timing ablations / stamps of the one-pass backward.
- * fa_mi355x_debug_phase_cycles: copies the first n per-wave phase counters (8 per wave slot) a stamp build wrote. */
-#ifdef FA_DIAG
-int fa_mi355x_set_tuning(int key, int value);
-int fa_mi355x_debug_phase_cycles(unsigned long long* host_out, int n);
-#endif
 
 /* Measurement aid: runs a bare v_mfma_f32_32x32x16_bf16 loop on pseudo-random operands on every CU (two waves per SIMD) for
  * at least min_ms and reports what the device SUSTAINS under power: dense bf16 TFLOP/s and the in-kernel clock (GHz).  bench.py

@@ -21,15 +21,10 @@ def built():
     return _lib
 
 
-def _declared_symbols(diag=False):
-    """Entry points the header declares; those inside ``#ifdef FA_DIAG`` belong to the diagnostic build only."""
+def _declared_symbols():
+    """Entry points the header declares."""
     text = open(os.path.join(ROOT, "include", "flash_attn_mi355x.h")).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    diag_blocks = re.findall(r"#ifdef FA_DIAG(.*?)#endif", text, flags=re.S)
-    if diag:
-        text = "\n".join(diag_blocks)
-    else:
-        text = re.sub(r"#ifdef FA_DIAG.*?#endif", "", text, flags=re.S)
     return sorted(set(re.findall(r"\b((?:launch_flash_attn|fa_mi355x)_\w+)\s*\(", text)))
 
 
@@ -97,34 +92,22 @@ def _device_kernels(path):
 
 
 def test_product_library_has_no_diagnostic_code_and_no_scratch(built):
-    """stamp builds, the barrier-less ablation and fa_mi355x_set_tuning live in the FA_DIAG build only, and no
-    kernel of the product library uses scratch memory (round 3: no exception left; the one-pass backward, which kept 8 B per lane,
-    moved to the diagnostic build)."""
+    """no stamp build, timing ablation or tuning entry point in the library, and no kernel of it uses scratch
+    memory (round 3: no exception left; the one-pass backward, which kept 8 B per lane, was retired)."""
     path = built.lib_path("libflash_attn_mi355x.so")
     syms = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True).stdout
-    for s in _declared_symbols(diag=True):
+    for s in ("fa_mi355x_set_tuning", "fa_mi355x_debug_phase_cycles", "g_phase_cycles"):
         assert s not in syms, s
-    assert "g_phase_cycles" not in syms
     kernels = _device_kernels(path)
     assert len(kernels) > 40
     for name, scratch, vgpr in kernels:
         assert vgpr <= 512
         assert scratch == 0, (name, scratch)
-    # template arguments that only diagnostic instantiations carry: DIAG = 1 / 2 of the slot kernels, MODE 9 / 13 / 93 of dK/dV, ABL != 0
+    # the retired stamp / register-staging builds of dK/dV (MODE 9 / 13 / 93) and the bf16 one-pass backwards
     names = " ".join(k[0] for k in kernels)
     assert not re.search(r"bwd_dkdv_kernelI\S*Li(9|13|93)ELb", names)
-    assert "bwd_dkdv_slot_kernelIDF16bLi64ELi1E" not in names and "bwd_dq_slot_kernelIDF16bLi64ELi1E" not in names
-    assert "bwd_dq_slot_kernelIDF16bLi64ELi2E" not in names
-    assert "bwd_fused_kernel" not in names   # the one-pass backward: diagnostic build only since round 3
+    assert "bwd_fused_kernel" not in names and "bwd_chain_kernel" not in names
     assert len(kernels) < 98, len(kernels)   # round 3 library diet (133 before, 88 then; round 4: + two scale-guard kernels, + four builds of the fp32 one-pass backward)
-
-
-def test_diagnostic_library_exports_the_diag_entry_points(built):
-    path = built.lib_path("libflash_attn_mi355x_diag.so")
-    assert os.path.exists(path)
-    syms = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True).stdout
-    for s in _declared_symbols(diag=True) + ["fa_mi355x_fwd_ex", "fa_mi355x_bwd_ex"]:
-        assert s in syms, s
 
 
 def test_library_contains_gfx950_code_object(built):
@@ -143,8 +126,7 @@ def test_argument_validation_without_gpu(built):
     assert core.fa_mi355x_bwd_workspace_bytes(64, 4100, 64) == 3 * 64 * 4100 * 4      # not a one-pass shape
     assert core.fa_mi355x_bwd_workspace_bytes(64, 4096, 64) == 3 * 64 * 4096 * 4
     assert core.fa_mi355x_bwd_workspace_bytes(0, 4096, 64) == 0
-    # with options: the product library has no kernel that needs more (the chained one-pass backward, opts[4] = 3, whose slabs this
-    # entry point sizes, lives in the diagnostic library)
+    # with options: no kernel of the library needs more, whatever the options say (opts[4] = 3 once sized a retired kernel's slabs)
     core.fa_mi355x_bwd_workspace_bytes_ex.restype = ctypes.c_size_t
     chain = (ctypes.c_int * 5)(0, 0, 0, 0, 3)
     assert core.fa_mi355x_bwd_workspace_bytes_ex(64, 4096, 64, chain, 5) == 3 * 64 * 4096 * 4
@@ -165,7 +147,7 @@ def test_argument_validation_without_gpu(built):
     assert fw(one, one, one, one, one, one, 1, 1, 16, 48, 0, 0.0, 0, 2, 1, None, 0, null, 0, null) == 2      # head dim
     mode9 = (ctypes.c_int * 10)(0, 0, 0, 0, 0, 0, 0, 0, 4, 0)
     assert fw(one, one, one, one, one, one, 1, 1, 16, 64, 0, 0.0, 0, 2, 1, mode9, 10, null, 0, null) == 1    # option 8 = 4 does not exist
-    # per-call options: diagnostic values are rejected by the product library before any HIP call
+    # per-call options: values outside the table (e.g. the retired stamp build 93) are rejected before any HIP call
     bad = (ctypes.c_int * 3)(93, 0, 0)
     assert core.fa_mi355x_fwd_ex(one, one, one, one, one, one, 1, 16, 64, 0, 2, 0, bad, 3, null) == 1
     assert b"diagnostic" in core.fa_mi355x_last_error()

@@ -579,8 +579,8 @@ def test_default_dispatch_around_launch_size_thresholds(dev, BH, N, causal):
 @pytest.mark.parametrize("opts", [(3,), (4,), (5,), (0, 2), (0, 3), (0, 0, 2), (0, 0, 3), (0, 0, 0, 0, 1), (0, 0, 0, 0, 0, 1),
                                   (0, 0, 0, 0, 0, 0, 0, 1), (0, 0, 0, 0, 0, 0, 0, 2)])
 def test_every_accepted_option_value_against_the_oracle(dev, opts, causal):
-    """Every per-call option value the product library accepts (include/flash_attn_mi355x.h; the values that lost their A/B moved
-    to the diagnostic library in round 3), one at a time, bf16 d = 64 at a size where the launch-size rules would otherwise pick for
+    """Every per-call option value the library accepts (include/flash_attn_mi355x.h; the values that lost their A/B were retired
+    with their kernels), one at a time, bf16 d = 64 at a size where the launch-size rules would otherwise pick for
     themselves: forward + backward against the fp64 oracle at the ordinary bound."""
     import torch
     BH, N, d = 16, 768, 64
@@ -763,36 +763,6 @@ def test_causal_forward_slot_kernel_d128(dev, N):
     assert maxabs(to_np(o_s), ro) < TOLBF and maxabs(to_np(l_s), rL) < TOLBF
     assert maxabs(to_np(o_p), ro) < TOLBF and maxabs(to_np(l_p), rL) < TOLBF
     assert maxabs(to_np(o_s), to_np(o_p)) < 1.5 * TOLBF
-
-
-def test_one_pass_backward_in_the_diagnostic_library():
-    """The one-pass backward (csrc/fa_bwd_fused.h: dQ formed in the key-stationary kernel and summed across the key-block workgroups
-    of a head by an ordered hand-off; the reference's single pass, src/flash_attn2_bw.cu:94-247) left the product library in round 3
-    (it lost its A/B at every size and was the one kernel with scratch and a spin protocol) and lives in the diagnostic build.
-    tools/check_fused.py, run as a CHILD process (this process never loads the diagnostic library), checks it against the fp64
-    oracle (1e-3), against the two-kernel backward, bitwise repeatability and the hand-off status word at six shapes incl. B=8, H=8,
-    N=4096."""
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "tools", "check_fused.py")], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "ALL OK" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
-
-
-def test_chained_one_pass_backward_in_the_diagnostic_library():
-    """Round 4: the five-product backward of the reference (src/flash_attn2_bw.cu:94-247: S, dP, dV, dK, dQ in ONE
-    key-stationary pass, dQ summed over key blocks with atomicAdd at :228) as csrc/fa_bwd_chain.h builds it: a workgroup takes
-    consecutive key blocks of a head and carries its running dQ tiles through memory; fp32 atomics only from the last block of each
-    chain, none when a workgroup covers a whole head.  It measured slower than the two-kernel backward (profiles/r04_chain_backward.txt)
-    and keeps 36 B of scratch, so it lives in the diagnostic build.  tools/check_chain.py, run as a CHILD process, checks it at eight
-    shapes (1-4 chains per head, 1-16 blocks per chain, B=8 H=8 N=4096 among them) against the fp64 oracle (1e-3), the two-kernel
-    backward (2e-3) and itself (run to run: 1e-5; the atomics' arrival order moves dq in the last bits only)."""
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, FA_MI355X_DIAG="1")
-    r = subprocess.run([sys.executable, os.path.join(root, "tools", "check_chain.py")], capture_output=True, text=True, timeout=600, env=env)
-    assert r.returncode == 0 and "ALL OK" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
 
 
 @pytest.mark.parametrize("dtype,d", [("f32", 64), ("bf16", 128), ("bf16", 32)])
