@@ -68,8 +68,6 @@ void plan_add(const char* expr) {   // "(fa::fwd_slot_kernel<T, 64, false>)" -> 
     t_fold = true;                                                          \
     FA_LAUNCH(kern, grid, block, shmem, st, __VA_ARGS__);                   \
   } while (0)
-// ... of a backward MFMA-slot kernel that carries BOTH scalings and picks one per launch (Layout::scale_sel): no twin needed
-#define FA_LAUNCH_SEL(kern, grid, block, shmem, st, ...) FA_LAUNCH(kern, grid, block, shmem, st, __VA_ARGS__)
 // ... and can fill the call's scale guard inside its own launch (the non-causal builds of the slot forward: guard_produce)
 #define FA_LAUNCH_FOLD_P(kern, grid, block, shmem, st, ...)                 \
   do {                                                                      \
@@ -109,9 +107,47 @@ int parse_opts(const int* opts, int nopts, Tun& t) {
 }
 
 constexpr int WS_VECS = 3;   // row-constant vectors of the backward workspace: -L/tau, -delta, -L*log2(e)
+
+// One device call.  An entry point fills in its arguments, validate() checks them and completes the call (batch, tun, lay), and
+// fwd_dispatch / bwd_dispatch run it; the host-pointer launchers fill in the completed fields themselves.
+struct Call {
+  // forward: q, k, v -> out, l, m; backward: q, k, v, out, dout, l, m (read only) -> dq, dk, dv, with the workspace ws
+  const void *q = nullptr, *k = nullptr, *v = nullptr, *dout = nullptr;
+  float *out = nullptr, *l = nullptr, *m = nullptr, *dq = nullptr, *dk = nullptr, *dv = nullptr, *ws = nullptr;
+  bool bwd = false;
+  int B = 0, H = 1;            // B batch elements of H heads (by_heads); otherwise B is the number of (batch*head) matrices
+  bool by_heads = false;       // the B, H, layout form of the *_layout / _scaled / _masked / _dropout / _guarded entry points
+  int layout = FA_LAYOUT_BHND;
+  int N = 0, d = 0;
+  bool padded = false;         // fa_mi355x_*_padded: rows of dp elements; otherwise dp = d
+  int dp = 0;
+  int causal = 0, variant = 0, dtype = 0;
+  int stages = 0;              // backward stage mask
+  const int* opts = nullptr;
+  int nopts = 0;
+  const float* kmask = nullptr;   // additive key mask, one row per mask_heads (batch*head) matrices
+  int mask_heads = 1;
+  float drop_rate = 0.f, drop_scale = 1.f;
+  unsigned drop_seed = 0;
+  float scale = 0.f;           // softmax scale, 0 = sqrt(1/d)
+  bool scale_required = false;   // fa_mi355x_*_scaled: 0 is not accepted
+  const float* guard = nullptr;
+  int produce = 0;             // forward: fill the guard instead of reading it
+  hipStream_t st = nullptr;
+  // completed by validate() (tau by fwd_dispatch / bwd_dispatch)
+  int batch = 0;               // (batch*head) matrices
+  Tun tun = default_tun();
+  fa::Layout lay{};
+  float tau = 0.f;
+  // the workspace's row-constant vectors
+  float* nlc() const { return ws; }                           // -L / tau        (raw score units)
+  float* delta() const { return ws + (long)batch * N; }       // -rowsum(dO * O)
+  float* nl2() const { return ws + 2 * (long)batch * N; }     // -L * log2(e)    (the slot dK/dV kernel: its K fragments carry tau*log2(e))
+};
+
 int device_cus_raw();
 // Compute units the launch-size rules assume: the current device's, or 256 (an MI355X) when there is none -- fa_mi355x_plan without a
-// GPU must name the kernels a real launch would select (three rules used max(cus, 1) and two `cus > 0 ? cus : 256`).
+// GPU must name the kernels a real launch would select.  Never 0.
 int device_cus() {
   const int n = device_cus_raw();
   return n > 0 ? n : 256;
@@ -132,8 +168,7 @@ int device_cus_raw() {   // compute units of the current device (cached per devi
 
 // Causal slot builds: heads per XCD dispatched together, longest block first (fa::map_block_ranked): a chunk of two rounds of the chip
 int rank_chunk(int wgs_per_cu, int nb) {
-  const int cus = device_cus();
-  return std::max(1, (cus > 0 ? cus : 256) * wgs_per_cu / (4 * nb));
+  return std::max(1, device_cus() * wgs_per_cu / (4 * nb));
 }
 
 // Causal slot builds of the forward / dQ kernels: one block per workgroup in ranked order (measured 1-20 % faster than paired blocks
@@ -141,18 +176,30 @@ int rank_chunk(int wgs_per_cu, int nb) {
 // in one workgroup.  Option 7: 0 = by launch size, 1 = paired, 2 = ranked.
 bool causal_ranked(const Tun& tun, int blocks, int wgs_per_cu) {
   if (tun.v[7]) return tun.v[7] == 2;
-  const int cus = device_cus();
-  return blocks < 8 * (cus > 0 ? cus : 256) * wgs_per_cu;
+  return blocks < 8 * device_cus() * wgs_per_cu;
+}
+
+// The tiled slot builds of dK/dV and dQ: block kb (qb) of several consecutive heads per workgroup (no set-up, no wait for the K / V
+// fragments or the first stage, no store drain between them) while the grid of nb blocks per head still covers every CU; option
+// 5 = 1: one head per workgroup
+int head_tiles(const Call& c, int nb) {
+  int tiles = 1;
+  if (c.N % 256 == 0 && c.tun.v[5] == 0) {
+    const int cus = device_cus();
+    for (int t = 2; t <= 16; ++t)
+      if (c.batch % t == 0 && (c.batch / t) % 8 == 0 && (long)(c.batch / t) * nb >= cus) tiles = t;
+  }
+  return tiles;
 }
 
 // Phased forward.  bf16 rows with fewer than 64 admissible keys need the split-operand build (CARE): whole launches under a key
 // mask, dropout or N < 64; behind a causal launch, query block 0 alone is redone by it (one small workgroup per batch*head).
-template <typename T, int D, int BN, int WPE>
-int fwd_launch_cfg(const void* q, const void* k, const void* v, float* out, float* l, float* m, int batch, int N,
-                   fa::Layout lay, int causal, int variant, float tau, hipStream_t st, int only_qb = -1, int care_main = 0,
-                   int ranked = 0) {
+template <typename T, int D, int BN>
+int fwd_launch_cfg(const Call& c, int only_qb = -1, int care_main = 0, int ranked = 0) {
   constexpr bool BF = sizeof(T) == 2;
+  const int batch = c.batch, N = c.N, causal = c.causal;
   const int nqb = (N + 127) / 128;
+  fa::Layout lay = c.lay;
   // causal: query blocks p and nqb-1-p share a workgroup, or (ranked) one block per workgroup, longest first across a chunk of heads
   lay.rank_chunk = (ranked && causal && only_qb < 0) ? rank_chunk(2, nqb) : 0;
   // the fp32-scaling twin of a guarded non-causal call: four query blocks per workgroup while the launch still covers the chip twice
@@ -165,8 +212,8 @@ int fwd_launch_cfg(const void* q, const void* k, const void* v, float* out, floa
   fa::Layout lay1 = lay;   // (the follow-up launch of one block per head below is not ranked)
   lay1.rank_chunk = 0;
 #define FA_FWD_LAUNCH(FEAT, CARE, BLOCKS, ONLY)                                                                          \
-  FA_LAUNCH((fa::fwd_kernel<T, D, BN, WPE, FEAT, CARE>), dim3(batch * (BLOCKS)), dim3(256), 0, st, (const T*)q, \
-                     (const T*)k, (const T*)v, out, l, m, N, nqb, batch, lay, causal, variant, tau, ONLY)
+  FA_LAUNCH((fa::fwd_kernel<T, D, BN, 1, FEAT, CARE>), dim3(batch * (BLOCKS)), dim3(256), 0, c.st, (const T*)c.q,    \
+            (const T*)c.k, (const T*)c.v, c.out, c.l, c.m, N, nqb, batch, lay, causal, c.variant, c.tau, ONLY)
   if (lay.drop_thr) {   // dropout on P (and the key mask, staged as zeros when absent)
     FA_FWD_LAUNCH(2, BF, nblk, only_qb);
   } else if (lay.kmask) {   // additive key mask: staged per tile, enters S^T as the accumulator input
@@ -177,8 +224,8 @@ int fwd_launch_cfg(const void* q, const void* k, const void* v, float* out, floa
   } else {
     FA_FWD_LAUNCH(0, false, nblk, only_qb);
     if (BF && causal) {   // rows 0..63 see fewer than 64 keys: query block 0 again, split operands
-      FA_LAUNCH((fa::fwd_kernel<T, D, BN, WPE, 0, BF>), dim3(batch), dim3(256), 0, st, (const T*)q, (const T*)k, (const T*)v,
-                         out, l, m, N, nqb, batch, lay1, causal, variant, tau, 0);
+      FA_LAUNCH((fa::fwd_kernel<T, D, BN, 1, 0, BF>), dim3(batch), dim3(256), 0, c.st, (const T*)c.q, (const T*)c.k, (const T*)c.v,
+                c.out, c.l, c.m, N, nqb, batch, lay1, causal, c.variant, c.tau, 0);
     }
   }
 #undef FA_FWD_LAUNCH
@@ -187,18 +234,19 @@ int fwd_launch_cfg(const void* q, const void* k, const void* v, float* out, floa
 }
 
 template <typename T, int D>
-int fwd_launch(const void* q, const void* k, const void* v, float* out, float* l, float* m, int batch, int N,
-               fa::Layout lay, int causal, int variant, float tau, hipStream_t st, const Tun& tun) {
+int fwd_launch(const Call& c) {
+  const int batch = c.batch, N = c.N, causal = c.causal;
+  const Tun& tun = c.tun;
   if constexpr (sizeof(T) == 4 && D == 64) {
     // fp32, d = 64, launches that leave most of the chip idle under fwd_kernel's geometry (a wave = 32 queries x all keys, 128-query
     // workgroups, two per CU): the split-key forward (fa_fwd_splitk_f32.h: a workgroup = one 32-query block, its four waves a quarter
     // of the keys each).  Option 1: 4 = always, 2 = never.
-    const long wgs = (long)batch * ((N + 127) / 128), cus = device_cus() > 0 ? device_cus() : 256;
-    if (!lay.kmask && !lay.drop_thr && !lay.out_bf16 && N >= 128 && (tun.v[1] == 4 ||
+    const long wgs = (long)batch * ((N + 127) / 128), cus = device_cus();
+    if (!c.lay.kmask && !c.lay.drop_thr && !c.lay.out_bf16 && N >= 128 && (tun.v[1] == 4 ||
          (tun.v[1] == 0 && wgs <= (causal ? FWD_SPLITK_MAX_WGS_PER_CU_CAUSAL : FWD_SPLITK_MAX_WGS_PER_CU) * cus))) {
       const int nqb = (N + 31) / 32;
-      FA_LAUNCH((fa::fwd_splitk_f32_kernel<D>), dim3((unsigned)(batch * nqb)), dim3(256), 0, st, (const float*)q, (const float*)k,
-                (const float*)v, out, l, m, N, nqb, batch, lay, causal, variant, tau);
+      FA_LAUNCH((fa::fwd_splitk_f32_kernel<D>), dim3((unsigned)(batch * nqb)), dim3(256), 0, c.st, (const float*)c.q, (const float*)c.k,
+                (const float*)c.v, c.out, c.l, c.m, N, nqb, batch, c.lay, causal, c.variant, c.tau);
       FA_HIP_TRY(hipGetLastError());
       return FA_OK;
     }
@@ -212,46 +260,47 @@ int fwd_launch(const void* q, const void* k, const void* v, float* out, float* l
     // nqb-1-p paired): 0.155 vs 0.192 ms for the phased kernel at the metric shape; it needs about one 8-wave workgroup per CU to pay.
     const int nqb = (N + 255) / 256;
     const bool cslot = causal && N % 256 == 0 && (tun.v[1] == 3 || (tun.v[1] == 0 && batch * nqb >= 256));
-    if (variant == FA_VARIANT_FA2 && tun.v[1] != 2 && (!causal || tun.v[1] == 3 || cslot) && !lay.kmask && !lay.drop_thr && N >= 64) {
+    if (c.variant == FA_VARIANT_FA2 && tun.v[1] != 2 && (!causal || tun.v[1] == 3 || cslot) && !c.lay.kmask && !c.lay.drop_thr &&
+        N >= 64) {
       const bool whole = !causal && N % (8192 / D) == 0;   // no sub-tile needs a mask
       if (cslot) {   // (d = 64: four waves per SIMD, two workgroups per CU; d = 128: two waves per SIMD, one workgroup)
         const bool ranked = causal_ranked(tun, batch * nqb, D == 64 ? 2 : 1);
+        fa::Layout lay = c.lay;
         lay.rank_chunk = rank_chunk(D == 64 ? 2 : 1, nqb);
         FA_LAUNCH_FOLD((fa::fwd_slot_kernel<T, D, false, 64, (D == 64 ? 4 : 2), true>),
-                           dim3(ranked ? batch * nqb : batch * ((nqb + 1) / 2)),
-                           dim3(512), 0, st, (const T*)q, (const T*)k, (const T*)v, out, l, N, nqb, batch, lay, ranked ? 2 : 1, tau);
+                       dim3(ranked ? batch * nqb : batch * ((nqb + 1) / 2)), dim3(512), 0, c.st, (const T*)c.q, (const T*)c.k,
+                       (const T*)c.v, c.out, c.l, N, nqb, batch, lay, ranked ? 2 : 1, c.tau);
         FA_HIP_TRY(hipGetLastError());
         return FA_OK;
       }
       if (whole && D == 64) {   // d = 64 default: 64-key stages (64 KiB of rings), two workgroups per CU = four waves per SIMD at
         // 122 VGPRs: 0.268 vs 0.282 ms for the 128-key-stage build at two waves per SIMD
-        FA_LAUNCH_FOLD_P((fa::fwd_slot_kernel<T, 64, false, 64, 4>), dim3(batch * nqb), dim3(512), 0, st, (const T*)q,
-                           (const T*)k, (const T*)v, out, l, N, nqb, batch, lay, causal, tau);
+        FA_LAUNCH_FOLD_P((fa::fwd_slot_kernel<T, 64, false, 64, 4>), dim3(batch * nqb), dim3(512), 0, c.st, (const T*)c.q,
+                         (const T*)c.k, (const T*)c.v, c.out, c.l, N, nqb, batch, c.lay, causal, c.tau);
         FA_HIP_TRY(hipGetLastError());
         return FA_OK;
       }
       if constexpr (D == 128) {
         if (whole) {
-          FA_LAUNCH_FOLD_P((fa::fwd_slot_kernel<T, D, false>), dim3(batch * nqb), dim3(512), 0, st, (const T*)q,
-                             (const T*)k, (const T*)v, out, l, N, nqb, batch, lay, causal, tau);
+          FA_LAUNCH_FOLD_P((fa::fwd_slot_kernel<T, D, false>), dim3(batch * nqb), dim3(512), 0, c.st, (const T*)c.q,
+                           (const T*)c.k, (const T*)c.v, c.out, c.l, N, nqb, batch, c.lay, causal, c.tau);
           FA_HIP_TRY(hipGetLastError());
           return FA_OK;
         }
       }
       if constexpr (D == 64) {   // ragged N / forced causal: the variant with masked periods (d = 128 takes the phased kernel)
-        FA_LAUNCH((fa::fwd_slot_kernel<T, D, true>), dim3(batch * nqb), dim3(512), 0, st, (const T*)q,
-                           (const T*)k, (const T*)v, out, l, N, nqb, batch, lay, causal, tau);
+        FA_LAUNCH((fa::fwd_slot_kernel<T, D, true>), dim3(batch * nqb), dim3(512), 0, c.st, (const T*)c.q,
+                  (const T*)c.k, (const T*)c.v, c.out, c.l, N, nqb, batch, c.lay, causal, c.tau);
         FA_HIP_TRY(hipGetLastError());
         // under the causal mask rows 0..63 see fewer than 64 keys: the slot kernel has no split-operand path, so the phased
         // kernel redoes query block 0 (one small workgroup per batch*head) behind it
-        if (causal) return fwd_launch_cfg<T, D, 64, 1>(q, k, v, out, l, m, batch, N, lay, causal, variant, tau, st, 0);
+        if (causal) return fwd_launch_cfg<T, D, 64>(c, 0);
         return FA_OK;
       }
     }
   }
-  return fwd_launch_cfg<T, D, (sizeof(T) == 2 ? 64 : 32), 1>(q, k, v, out, l, m, batch, N, lay, causal, variant, tau,
-                                                             st, -1, D == 64 ? 1 : 0,
-                                                             tun.v[7] == 2 || (tun.v[7] == 0 && sizeof(T) == 2 && D == 32));   // (d = 32: ranked measured 10 % faster)
+  return fwd_launch_cfg<T, D, (sizeof(T) == 2 ? 64 : 32)>(c, -1, D == 64 ? 1 : 0,
+                                                          tun.v[7] == 2 || (tun.v[7] == 0 && sizeof(T) == 2 && D == 32));   // (d = 32: ranked measured 10 % faster)
 }
 
 // bf16 launches whose rows may see fewer than 64 admissible keys everywhere (key mask, dropout, N < 64) run the split-operand
@@ -261,15 +310,15 @@ int fwd_launch(const void* q, const void* k, const void* v, float* out, float* l
 // DROP_ONLY: the instantiation serves dropout calls alone (fp32 d = 64: the plain launches have a build of their own), so the plain
 // kernels of this geometry are not compiled into the library.
 template <typename T, int D, int KPW, int NW, int QS, int MODE = 0, bool DROP_ONLY = false>
-int dkdv_launch(const void* q, const void* k, const void* v, const void* dout, const float* nlc, const float* delta,
-                float* dk, float* dv, int batch, int N, fa::Layout lay, int causal, float tau, hipStream_t st, int care_main = 0,
-                int rank_causal = 1) {
+int dkdv_launch(const Call& c, int care_main = 0, int rank_causal = 1) {
   constexpr bool BF = sizeof(T) == 2;
+  const int batch = c.batch, N = c.N, causal = c.causal;
   const int nkb = (N + NW * KPW - 1) / (NW * KPW);
   const int nkb4 = (N + 127) / 128;
+  fa::Layout lay = c.lay;
 #define FA_CARE_LAUNCH(HD, GRID, THIN)                                                                                        \
-  FA_LAUNCH((fa::bwd_dkdv_kernel<T, D, 32, 4, 64, 1, HD, 1, BF>), dim3(GRID), dim3(256), 0, st, (const T*)q, (const T*)k, \
-                     (const T*)v, (const T*)dout, nlc, delta, dk, dv, N, nkb4, batch, lay, causal, tau, THIN)
+  FA_LAUNCH((fa::bwd_dkdv_kernel<T, D, 32, 4, 64, 1, HD, 1, BF>), dim3(GRID), dim3(256), 0, c.st, (const T*)c.q, (const T*)c.k, \
+            (const T*)c.v, (const T*)c.dout, c.nlc(), c.delta(), c.dk, c.dv, N, nkb4, batch, lay, causal, c.tau, THIN)
   if (lay.drop_thr) {   // dropout: the plain per-sub-slice path regenerates the mask from (bh, query, key)
     // (these whole-launch builds take one key block per workgroup: under the causal mask longest first across a chunk of heads)
     if constexpr (BF) {
@@ -277,9 +326,9 @@ int dkdv_launch(const void* q, const void* k, const void* v, const void* dout, c
       FA_CARE_LAUNCH(true, batch * nkb4, 0);
     } else {
       if (causal && rank_causal) lay.rank_chunk = rank_chunk(2, nkb);
-      FA_LAUNCH((fa::bwd_dkdv_kernel<T, D, KPW, NW, QS, 1, true>), dim3(batch * nkb), dim3(NW * 64), 0, st,
-                         (const T*)q, (const T*)k, (const T*)v, (const T*)dout, nlc, delta, dk, dv, N, nkb, batch, lay,
-                         causal, tau, 0);
+      FA_LAUNCH((fa::bwd_dkdv_kernel<T, D, KPW, NW, QS, 1, true>), dim3(batch * nkb), dim3(NW * 64), 0, c.st,
+                (const T*)c.q, (const T*)c.k, (const T*)c.v, (const T*)c.dout, c.nlc(), c.delta(), c.dk, c.dv, N, nkb, batch, lay,
+                causal, c.tau, 0);
     }
     FA_HIP_TRY(hipGetLastError());
     return FA_OK;
@@ -295,8 +344,8 @@ int dkdv_launch(const void* q, const void* k, const void* v, const void* dout, c
   if constexpr (BF && MODE == 3) {
     if (causal && care_main) {   // d = 64 default: the split-operand path inside the main (paired) kernel: 2 % faster than main + corner launch
       FA_LAUNCH((fa::bwd_dkdv_kernel<T, D, KPW, NW, QS, MODE, false, 1, true, true>), dim3(batch * ((nkb + 1) / 2)),
-                         dim3(NW * 64), 0, st, (const T*)q, (const T*)k, (const T*)v, (const T*)dout, nlc, delta, dk, dv, N, nkb, batch,
-                         lay, causal, tau, 0);
+                dim3(NW * 64), 0, c.st, (const T*)c.q, (const T*)c.k, (const T*)c.v, (const T*)c.dout, c.nlc(), c.delta(), c.dk, c.dv,
+                N, nkb, batch, lay, causal, c.tau, 0);
       FA_HIP_TRY(hipGetLastError());
       return FA_OK;
     }
@@ -312,15 +361,15 @@ int dkdv_launch(const void* q, const void* k, const void* v, const void* dout, c
   if ((causal || MODE == 3) && CAN_PAIR) {
     if constexpr (CAN_PAIR)
       FA_LAUNCH((fa::bwd_dkdv_kernel<T, D, KPW, NW, QS, MODE, false, 1, false, true>), dim3(batch * ((nkb + 1) / 2)),
-                         dim3(NW * 64), 0, st, (const T*)q, (const T*)k, (const T*)v, (const T*)dout, nlc, delta, dk, dv, N, nkb, batch,
-                         lay, causal, tau, thin);
+                dim3(NW * 64), 0, c.st, (const T*)c.q, (const T*)c.k, (const T*)c.v, (const T*)c.dout, c.nlc(), c.delta(), c.dk, c.dv,
+                N, nkb, batch, lay, causal, c.tau, thin);
   } else {
     // unpaired causal launch (the 8-wave d = 128 geometry): longest block first across a chunk of heads instead of head by head:
     // 2.05 vs 2.21 ms at configs[3]'s shape, 0.157 vs 0.207 at B = 8, N = 2048 (option 7 = 1: head by head)
     if (causal && rank_causal) lay.rank_chunk = rank_chunk(NW == 8 ? 1 : 2, nkb);
     if constexpr (MODE != 3 || !CAN_PAIR)
-      FA_LAUNCH((fa::bwd_dkdv_kernel<T, D, KPW, NW, QS, MODE>), dim3(batch * nkb), dim3(NW * 64), 0, st, (const T*)q,
-                         (const T*)k, (const T*)v, (const T*)dout, nlc, delta, dk, dv, N, nkb, batch, lay, causal, tau, thin);
+      FA_LAUNCH((fa::bwd_dkdv_kernel<T, D, KPW, NW, QS, MODE>), dim3(batch * nkb), dim3(NW * 64), 0, c.st, (const T*)c.q,
+                (const T*)c.k, (const T*)c.v, (const T*)c.dout, c.nlc(), c.delta(), c.dk, c.dv, N, nkb, batch, lay, causal, c.tau, thin);
   }
   if constexpr (BF) {
     if (thin) FA_CARE_LAUNCH(false, batch, 2);
@@ -332,20 +381,21 @@ int dkdv_launch(const void* q, const void* k, const void* v, const void* dout, c
 }
 
 template <typename T, int D, int BN>
-int dq_launch(const void* q, const void* k, const void* v, const void* dout, const float* nlc, const float* delta,
-              float* dq, int batch, int N, fa::Layout lay, int causal, float tau, hipStream_t st, int only_qb = -1, int care_main = 0,
-              const fa::DqPrep* prep = nullptr, int ranked = 0) {
+int dq_launch(const Call& c, int only_qb = -1, int care_main = 0, const fa::DqPrep* prep = nullptr, int ranked = 0) {
   // prep != nullptr (only when dq_fuses_prep said so: the plain main build runs): the launch also preprocesses its rows
   constexpr bool BF = sizeof(T) == 2;   // CARE policy as fwd_launch_cfg's
+  const int batch = c.batch, N = c.N, causal = c.causal;
   const int nqb = (N + 127) / 128;
+  fa::Layout lay = c.lay;
   // causal: query blocks p and nqb-1-p share a workgroup, or (ranked) one block per workgroup, longest first across a chunk of heads
   lay.rank_chunk = (ranked && causal && only_qb < 0) ? rank_chunk(2, nqb) : 0;
   const int nblk = only_qb >= 0 ? 1 : ((causal && !lay.rank_chunk) ? (nqb + 1) / 2 : nqb);
   fa::Layout lay1 = lay;   // (the follow-up launch of one block per head below is not ranked)
   lay1.rank_chunk = 0;
 #define FA_DQ_LAUNCH(FEAT, CARE, BLOCKS, ONLY)                                                                              \
-  FA_LAUNCH((fa::bwd_dq_kernel<T, D, BN, FEAT, 4, CARE>), dim3(batch * (BLOCKS)), dim3(256), 0, st, (const T*)q,   \
-                     (const T*)k, (const T*)v, (const T*)dout, nlc, delta, dq, N, nqb, batch, lay, causal, tau, ONLY, fa::DqPrep{})
+  FA_LAUNCH((fa::bwd_dq_kernel<T, D, BN, FEAT, 4, CARE>), dim3(batch * (BLOCKS)), dim3(256), 0, c.st, (const T*)c.q,   \
+            (const T*)c.k, (const T*)c.v, (const T*)c.dout, c.nlc(), c.delta(), c.dq, N, nqb, batch, lay, causal, c.tau, ONLY,   \
+            fa::DqPrep{})
   if (lay.drop_thr) {
     FA_DQ_LAUNCH(2, BF, nblk, only_qb);
   } else if (lay.kmask) {
@@ -353,50 +403,46 @@ int dq_launch(const void* q, const void* k, const void* v, const void* dout, con
   } else if (BF && (N < 64 || only_qb >= 0 || (causal && care_main))) {
     FA_DQ_LAUNCH(0, BF, nblk, only_qb);
   } else {
-    FA_LAUNCH((fa::bwd_dq_kernel<T, D, BN, 0, 4, false>), dim3(batch * nblk), dim3(256), 0, st, (const T*)q, (const T*)k, (const T*)v,
-              (const T*)dout, nlc, delta, dq, N, nqb, batch, lay, causal, tau, only_qb, prep ? *prep : fa::DqPrep{});
+    FA_LAUNCH((fa::bwd_dq_kernel<T, D, BN, 0, 4, false>), dim3(batch * nblk), dim3(256), 0, c.st, (const T*)c.q, (const T*)c.k,
+              (const T*)c.v, (const T*)c.dout, c.nlc(), c.delta(), c.dq, N, nqb, batch, lay, causal, c.tau, only_qb,
+              prep ? *prep : fa::DqPrep{});
     if (BF && causal)   // rows 0..63 again with split operands
-      FA_LAUNCH((fa::bwd_dq_kernel<T, D, BN, 0, 4, BF>), dim3(batch), dim3(256), 0, st, (const T*)q, (const T*)k, (const T*)v,
-                         (const T*)dout, nlc, delta, dq, N, nqb, batch, lay1, causal, tau, 0, fa::DqPrep{});
+      FA_LAUNCH((fa::bwd_dq_kernel<T, D, BN, 0, 4, BF>), dim3(batch), dim3(256), 0, c.st, (const T*)c.q, (const T*)c.k, (const T*)c.v,
+                (const T*)c.dout, c.nlc(), c.delta(), c.dq, N, nqb, batch, lay1, causal, c.tau, 0, fa::DqPrep{});
   }
 #undef FA_DQ_LAUNCH
   FA_HIP_TRY(hipGetLastError());
   return FA_OK;
 }
 
+// The MFMA-slot dQ kernel.  Its mask-free builds carry both scalings and pick one per launch (Layout::scale_sel): no twin launch.
 template <typename T, int D>
-int dq_slot_launch(const void* q, const void* k, const void* v, const void* dout, const float* nlc, const float* delta,
-                   float* dq, int batch, int N, fa::Layout lay, int causal, float tau, hipStream_t st, const Tun& tun,
-                   const fa::DqPrep* prep) {
+int dq_slot_launch(const Call& c, const fa::DqPrep* prep) {
   // prep != nullptr: the launch also does the preprocess for its rows and writes the workspace (see dq_fuses_prep)
+  const int batch = c.batch, N = c.N, causal = c.causal;
+  const fa::DqPrep pa = prep ? *prep : fa::DqPrep{};
   const int nqb = (N + 255) / 256;
+  fa::Layout lay = c.lay;
   lay.rank_chunk = rank_chunk(1, nqb);
-  const bool paired = !causal_ranked(tun, batch * nqb, 1);
+  const bool paired = !causal_ranked(c.tun, batch * nqb, 1);
   if (causal && N % 256 == 0) {   // causal build: unmasked sweep + the diagonal block per wave; one block per workgroup,
     // longest first across all heads (paired: blocks p and nqb-1-p in one workgroup)
     const dim3 grid(paired ? batch * ((nqb + 1) / 2) : batch * nqb);
-    FA_LAUNCH_SEL((fa::bwd_dq_slot_kernel<T, D, false, true>), grid, dim3(512), 0, st, (const T*)q, (const T*)k,
-              (const T*)v, (const T*)dout, nlc, delta, dq, N, nqb, batch, lay, paired ? 1 : 2, tau, prep ? *prep : fa::DqPrep{});
+    FA_LAUNCH((fa::bwd_dq_slot_kernel<T, D, false, true>), grid, dim3(512), 0, c.st, (const T*)c.q, (const T*)c.k,
+              (const T*)c.v, (const T*)c.dout, c.nlc(), c.delta(), c.dq, N, nqb, batch, lay, paired ? 1 : 2, c.tau, pa);
   } else if (!causal && N % 128 == 0) {   // no sub-tile needs a mask: the build without masked period variants
-    // Query block qb of several consecutive heads per workgroup (the tiled build: no set-up, no wait for the first stage, no store
-    // drain between them) while the grid still covers every CU (the rule of the tiled dK/dV launch); option 5 = 1: one head
-    int tiles = 1;
-    if (N % 256 == 0 && tun.v[5] == 0) {
-      const int cus = std::max(device_cus(), 1);
-      for (int t = 2; t <= 16; ++t)
-        if (batch % t == 0 && (batch / t) % 8 == 0 && (long)(batch / t) * nqb >= cus) tiles = t;
-    }
-    if (tiles > 1) {
+    // (query block qb of several consecutive heads per workgroup: head_tiles, the rule of the tiled dK/dV launch)
+    if (const int tiles = head_tiles(c, nqb); tiles > 1) {
       lay.tiles = tiles;
-      FA_LAUNCH_SEL((fa::bwd_dq_slot_kernel<T, D, false, false, true>), dim3((batch / tiles) * nqb), dim3(512), 0, st, (const T*)q,
-                (const T*)k, (const T*)v, (const T*)dout, nlc, delta, dq, N, nqb, batch, lay, causal, tau, prep ? *prep : fa::DqPrep{});
+      FA_LAUNCH((fa::bwd_dq_slot_kernel<T, D, false, false, true>), dim3((batch / tiles) * nqb), dim3(512), 0, c.st, (const T*)c.q,
+                (const T*)c.k, (const T*)c.v, (const T*)c.dout, c.nlc(), c.delta(), c.dq, N, nqb, batch, lay, causal, c.tau, pa);
     } else {
-      FA_LAUNCH_SEL((fa::bwd_dq_slot_kernel<T, D, false>), dim3(batch * nqb), dim3(512), 0, st, (const T*)q, (const T*)k,
-                (const T*)v, (const T*)dout, nlc, delta, dq, N, nqb, batch, lay, causal, tau, prep ? *prep : fa::DqPrep{});
+      FA_LAUNCH((fa::bwd_dq_slot_kernel<T, D, false>), dim3(batch * nqb), dim3(512), 0, c.st, (const T*)c.q, (const T*)c.k,
+                (const T*)c.v, (const T*)c.dout, c.nlc(), c.delta(), c.dq, N, nqb, batch, lay, causal, c.tau, pa);
     }
   } else {
-    FA_LAUNCH((fa::bwd_dq_slot_kernel<T, D>), dim3(batch * nqb), dim3(512), 0, st, (const T*)q, (const T*)k,
-                       (const T*)v, (const T*)dout, nlc, delta, dq, N, nqb, batch, lay, causal, tau, fa::DqPrep{});
+    FA_LAUNCH((fa::bwd_dq_slot_kernel<T, D>), dim3(batch * nqb), dim3(512), 0, c.st, (const T*)c.q, (const T*)c.k,
+              (const T*)c.v, (const T*)c.dout, c.nlc(), c.delta(), c.dq, N, nqb, batch, lay, causal, c.tau, fa::DqPrep{});
   }
   FA_HIP_TRY(hipGetLastError());
   return FA_OK;
@@ -415,21 +461,23 @@ int dq_slot_launch(const void* q, const void* k, const void* v, const void* dout
 // Returns the number of parts, 0 = two kernels.  Option 4: 4 = two kernels always (dq bitwise repeatable from run to run), 5 = one
 // pass whatever the launch size.
 template <typename T, int D>
-int onepass_f32(int batch, int N, const fa::Layout& lay, int causal, int stages, const Tun& tun) {   // 0: two kernels; else the split
+int onepass_f32(const Call& c) {   // 0: two kernels; else the split
+  const int N = c.N;
+  const Tun& tun = c.tun;
   const int both = FA_BWD_STAGE_DKDV | FA_BWD_STAGE_DQ;
-  if (!(sizeof(T) == 4 && D == 64 && (stages & both) == both && (tun.v[4] == 0 || tun.v[4] == 5) && !lay.kmask && !lay.drop_thr &&
-        N >= 256))
+  if (!(sizeof(T) == 4 && D == 64 && (c.stages & both) == both && (tun.v[4] == 0 || tun.v[4] == 5) && !c.lay.kmask &&
+        !c.lay.drop_thr && N >= 256))
     return 0;
   // FA_MI355X_DETERMINISTIC=1: never by default (the reference ABI has no options argument: a caller who needs a bitwise repeatable dq there)
   static const bool deterministic = [] { const char* e = getenv("FA_MI355X_DETERMINISTIC"); return e && e[0] == '1'; }();
   if (deterministic && tun.v[4] != 5) return 0;
   // Launches below one workgroup per CU: the query sweep of every key block is cut into 2, 4 or 8 parts (one workgroup each, dK / dV
   // summed by atomics as well) while a part keeps at least 4 stages of 32 queries
-  const long cus = device_cus() > 0 ? device_cus() : 256, wgs1 = (long)batch * ((N + 255) / 256), nqi = (N + 31) / 32;
+  const long cus = device_cus(), wgs1 = (long)c.batch * ((N + 255) / 256), nqi = (N + 31) / 32;
   // (causal: key block 0 sweeps N / 256 times the stages of the last one, so one round is bound by its longest workgroup -- 0.65 ms
   // against 0.36 of balanced work at B = 4, H = 8, N = 2048: first look for a cut that gives the longest-first dispatch two rounds)
   // (from four key blocks per head on: at N = 256 / 512 the cut costs more than the imbalance, 0.146 vs 0.087 and 0.181 vs 0.164 ms)
-  for (int pass = (causal && N >= 1024) ? 0 : 1; pass < 2; ++pass)
+  for (int pass = (c.causal && N >= 1024) ? 0 : 1; pass < 2; ++pass)
     for (int split = 1; split <= 8; split *= 2) {
       if (split > 1 && nqi / split < 4) break;
       const long wgs = wgs1 * split, rounds = (wgs + cus - 1) / cus;
@@ -439,15 +487,22 @@ int onepass_f32(int batch, int N, const fa::Layout& lay, int causal, int stages,
   return tun.v[4] == 5 ? 1 : 0;
 }
 
+// bf16, d = 64: does the dQ stage take the phased kernel instead of the slot build (key mask, dropout and N < 64 aside)?  The phased
+// kernel is 1 % faster than the slot build WITH masked periods under the causal mask (option 2 = 3 forces the slot kernel).  Causal
+// launches with N a multiple of 256 take the causal slot build (unmasked sweep + diagonal block per wave, paired query blocks): 0.199
+// vs 0.223 ms at the metric shape
+bool dq64_phased(const Call& c) {
+  return c.tun.v[2] == 2 || (c.causal && c.tun.v[2] != 3 && !(c.N % 256 == 0 && c.batch * (c.N / 256) >= 128));
+}
+
 template <typename T, int D>
-bool dq_fuses_prep(int batch, int N, const fa::Layout& lay, int causal, int stages, const Tun& tun) {
+bool dq_fuses_prep(const Call& c) {
   constexpr bool BF = sizeof(T) == 2;
-  if (onepass_f32<T, D>(batch, N, lay, causal, stages, tun)) return false;
+  if (onepass_f32<T, D>(c)) return false;
   const int need = FA_BWD_STAGE_PREP | FA_BWD_STAGE_DQ;
-  if ((stages & need) != need || tun.v[4] != 0 || lay.kmask || lay.drop_thr || (BF && N < 64)) return false;
+  if ((c.stages & need) != need || c.tun.v[4] != 0 || c.lay.kmask || c.lay.drop_thr || (BF && c.N < 64)) return false;
   if constexpr (BF && D == 64) {
-    const bool phased = tun.v[2] == 2 || (causal && tun.v[2] != 3 && !(N % 256 == 0 && batch * (N / 256) >= 128));
-    if (!phased) return causal ? N % 256 == 0 : N % 128 == 0;   // the slot kernel: its unmasked / causal builds only
+    if (!dq64_phased(c)) return c.causal ? c.N % 256 == 0 : c.N % 128 == 0;   // the slot kernel: its unmasked / causal builds only
   }
   return true;
 }
@@ -455,253 +510,170 @@ bool dq_fuses_prep(int batch, int N, const fa::Layout& lay, int causal, int stag
 // The dQ stage of a backward call: kernel selection by dtype / head dim / launch shape / options.  prep != nullptr: the launch also does
 // the preprocess for its rows (dq_fuses_prep decided that a plain main build runs).
 template <typename T, int D>
-int dq_stage(const void* q, const void* k, const void* v, const void* dout, const float* nlc, const float* delta, float* dq, int batch,
-             int N, fa::Layout lay, int causal, float tau, hipStream_t st, const Tun& tun, const fa::DqPrep* prep) {
-  int rc;
+int dq_stage(const Call& c, const fa::DqPrep* prep) {
+  // every launch the branches below do not take runs the phased kernel with 32-key tiles (bf16 d = 32: they run 3 waves/SIMD,
+  // measured 2 % faster), causal query blocks ranked by default at bf16 d = 32 (option 7)
+  const int ranked = c.tun.v[7] == 2 || (c.tun.v[7] == 0 && sizeof(T) == 2 && D == 32);
+  const bool few_keys = c.lay.kmask || c.lay.drop_thr || c.N < 64;   // (key mask and dropout live in the phased kernel)
   if constexpr (sizeof(T) == 2 && D == 128) {
-    if (causal || lay.kmask || lay.drop_thr || N < 64)   // 4 waves x 32 queries, two workgroups per CU
-      rc = dq_launch<T, D, 32>(q, k, v, dout, nlc, delta, dq, batch, N, lay, causal, tau, st, -1, 0, prep,
-                          tun.v[7] == 2 || (tun.v[7] == 0 && sizeof(T) == 2 && D == 32));
-    else {   // non-causal default: 8 waves x 32 queries, one workgroup per CU (each staged K / V tile feeds twice the waves)
-      const int nqb = (N + 255) / 256;
-      FA_LAUNCH((fa::bwd_dq_kernel<T, D, 32, 0, 8>), dim3(batch * nqb), dim3(512), 0, st, (const T*)q, (const T*)k,
-                (const T*)v, (const T*)dout, nlc, delta, dq, N, nqb, batch, lay, causal, tau, -1, prep ? *prep : fa::DqPrep{});
+    if (!c.causal && !few_keys) {   // non-causal default: 8 waves x 32 queries, one workgroup per CU (each staged K / V tile feeds
+      // twice the waves); otherwise 4 waves x 32 queries, two workgroups per CU
+      const int nqb = (c.N + 255) / 256;
+      FA_LAUNCH((fa::bwd_dq_kernel<T, D, 32, 0, 8>), dim3(c.batch * nqb), dim3(512), 0, c.st, (const T*)c.q, (const T*)c.k,
+                (const T*)c.v, (const T*)c.dout, c.nlc(), c.delta(), c.dq, c.N, nqb, c.batch, c.lay, c.causal, c.tau, -1,
+                prep ? *prep : fa::DqPrep{});
       FA_HIP_TRY(hipGetLastError());
-      rc = FA_OK;
+      return FA_OK;
     }
   } else if constexpr (sizeof(T) == 2 && D == 64) {   // d = 64: slot-interleaved three-deep pipeline (default)
-    if (tun.v[2] == 2 || lay.kmask || lay.drop_thr || N < 64 ||
-             (causal && tun.v[2] != 3 && !(N % 256 == 0 && batch * (N / 256) >= 128)))
-      // key mask and dropout live in the phased kernel, which is also 1 % faster than the slot build WITH masked periods under
-      // the causal mask (tuning key 2 = 3 forces the slot kernel).  Causal launches with N a multiple of 256 take the causal slot
-      // build (unmasked sweep + diagonal block per wave, paired query blocks): 0.199 vs 0.223 ms at the metric shape
-      rc = dq_launch<T, D, 32>(q, k, v, dout, nlc, delta, dq, batch, N, lay, causal, tau, st, -1, 0, prep,
-                          tun.v[7] == 2 || (tun.v[7] == 0 && sizeof(T) == 2 && D == 32));
-    else {
-      rc = dq_slot_launch<T, D>(q, k, v, dout, nlc, delta, dq, batch, N, lay, causal, tau, st, tun, prep);
+    if (!few_keys && !dq64_phased(c)) {
+      const int rc = dq_slot_launch<T, D>(c, prep);
       // the masked slot build forced onto a causal launch: rows 0..63 (few keys) are redone by the phased kernel's split-operand
       // path (query block 0); the causal slot build (N a multiple of 256) splits them itself
-      if (!rc && causal && N % 256 != 0) rc = dq_launch<T, D, 32>(q, k, v, dout, nlc, delta, dq, batch, N, lay, causal, tau, st, 0);
+      if (!rc && c.causal && c.N % 256 != 0) return dq_launch<T, D, 32>(c, 0);
+      return rc;
     }
-  } else if constexpr (sizeof(T) == 2) {   // d = 32: 32-key tiles run 3 waves/SIMD, measured 2 % faster
-    rc = dq_launch<T, D, 32>(q, k, v, dout, nlc, delta, dq, batch, N, lay, causal, tau, st, -1, 0, prep,
-                          tun.v[7] == 2 || (tun.v[7] == 0 && sizeof(T) == 2 && D == 32));
-  } else {
-    rc = dq_launch<T, D, 32>(q, k, v, dout, nlc, delta, dq, batch, N, lay, causal, tau, st, -1, 0, prep,
-                          tun.v[7] == 2 || (tun.v[7] == 0 && sizeof(T) == 2 && D == 32));
   }
-  return rc;
+  return dq_launch<T, D, 32>(c, -1, 0, prep, ranked);
+}
+
+// The dK/dV stage of a backward call: kernel selection by dtype / head dim / launch shape / options.
+template <typename T, int D>
+int dkdv_stage(const Call& c) {
+  const int batch = c.batch, N = c.N, causal = c.causal;
+  const Tun& tun = c.tun;
+  if constexpr (sizeof(T) == 2 && D == 64) {
+    // The continuous slot pipeline (no drain at stage boundaries, three-slot LDS-DMA ring) carries both scalings and picks one per
+    // launch (Layout::scale_sel): no twin launch.  Option 0 = 4: the compiler-interleaved phased kernel below.
+    fa::Layout lay = c.lay;
+    if (!causal && tun.v[0] == 0 && !lay.drop_thr && !lay.kmask && N >= 64) {
+      // d = 64, non-causal default: the continuous slot pipeline; rows thinned by a key mask or N < 64 go to the kernel below, whose
+      // per-sub-slice path splits P and dS.  Key block kb of several consecutive heads per workgroup: head_tiles
+      const int nkb = (N + 255) / 256;
+      if (const int tiles = head_tiles(c, nkb); tiles > 1) {
+        lay.tiles = tiles;
+        FA_LAUNCH((fa::bwd_dkdv_slot_kernel<T, 64, false, true>), dim3((batch / tiles) * nkb), dim3(512), 0, c.st,
+                  (const T*)c.q, (const T*)c.k, (const T*)c.v, (const T*)c.dout, c.nl2(), c.delta(), c.dk, c.dv, N, nkb, batch, lay, c.tau);
+      } else {
+        FA_LAUNCH((fa::bwd_dkdv_slot_kernel<T, 64>), dim3(batch * nkb), dim3(512), 0, c.st, (const T*)c.q,
+                  (const T*)c.k, (const T*)c.v, (const T*)c.dout, c.nl2(), c.delta(), c.dk, c.dv, N, nkb, batch, lay, c.tau);
+      }
+      FA_HIP_TRY(hipGetLastError());
+      return FA_OK;
+    }
+    if (causal && !lay.drop_thr && !lay.kmask && N % 256 == 0 &&
+        (tun.v[0] == 5 || (tun.v[0] == 0 && batch * (N / 256) >= 128))) {   // (tuning key 0 = 5 forces it)
+      // d = 64, causal, N a multiple of 256: the causal build of the continuous pipeline (sweep of the stages below the
+      // diagonal block, the block per wave, workgroups longest first); tuning key 0 = 3: the phased kernel below
+      // (key blocks p and nkb-1-p of several consecutive heads per workgroup, a causal tiled build, gave bitwise the same results
+      // 4-8 % slower: profiles/r04_causal_tiled_dkdv.txt)
+      const int nkb = N / 256;
+      lay.rank_chunk = rank_chunk(1, nkb);
+      FA_LAUNCH((fa::bwd_dkdv_slot_kernel<T, 64, true>), dim3(batch * nkb), dim3(512), 0, c.st, (const T*)c.q,
+                (const T*)c.k, (const T*)c.v, (const T*)c.dout, c.nl2(), c.delta(), c.dk, c.dv, N, nkb, batch, lay, c.tau);
+      FA_HIP_TRY(hipGetLastError());
+      return FA_OK;
+    }
+    // d = 64, causal (or tuning 3): slot-interleaved fast path for unmasked stages, per-sub-slice path on the diagonal
+    // (a build with the masked paths compiled out, for non-causal launches, measured the same: 0.4983 vs 0.4992 ms)
+    if (tun.v[0] != 4) return dkdv_launch<T, D, 32, 8, 128, 3>(c, 1);
+  }
+  if constexpr (sizeof(T) == 2 && D <= 64) {
+    // measured at B=8,H=8,N=4096,d=64 (ms, one device, profiles/README.md): 8 waves x 32 keys, 128-query stages,
+    // software-pipelined sub-slices 0.505; not pipelined 0.514; 64-query stages 0.519; 256-query 0.525;
+    // 4 waves x 32 keys (two workgroups per CU) 0.521; 4 waves x 64 keys (one wave per SIMD) 0.559
+    return dkdv_launch<T, D, 32, 8, 128, 0>(c);   // compiler-interleaved software pipeline (the d = 32 default; d = 64: option 0 = 4)
+  } else if constexpr (sizeof(T) == 2) {
+    // d = 128 default (dropout / key mask / N < 64: dkdv_launch runs the 4-wave split-operand build, which has the registers for it): 8 waves x 32 keys, one 256-key workgroup per CU (half the Q / dO staging per MFMA): 3.64 vs 3.92 ms
+    return dkdv_launch<T, D, 32, 8, 64>(c, 0, tun.v[7] != 1);
+  } else if constexpr (D == 64) {
+    // fp32, d = 64 (configs[1], [2]): the allocation lands on 256 VGPRs + 2 AGPRs = one wave per SIMD; asking for two
+    // (launch bound) keeps it under 256
+    if (c.lay.drop_thr) return dkdv_launch<T, D, 32, 4, 32, 0, true>(c);
+    const int nkb = (N + 127) / 128;
+    fa::Layout lay = c.lay;
+    // causal: longest block first across a chunk of heads instead of head by head: 0.57 vs 0.80 ms at the reference's timing-harness
+    // shape (B = 8, H = 8, N = 2048, fp32), bitwise the same (option 7 = 1: head by head)
+    if (causal && tun.v[7] != 1) lay.rank_chunk = rank_chunk(2, nkb);
+    FA_LAUNCH((fa::bwd_dkdv_kernel<T, D, 32, 4, 32, 0, false, 2>), dim3(batch * nkb), dim3(256), 0, c.st,
+              (const T*)c.q, (const T*)c.k, (const T*)c.v, (const T*)c.dout, c.nlc(), c.delta(), c.dk, c.dv, N, nkb, batch, lay,
+              causal, c.tau);
+    FA_HIP_TRY(hipGetLastError());
+    return FA_OK;
+  } else {
+    return dkdv_launch<T, D, 32, 4, 32>(c);
+  }
 }
 
 template <typename T, int D>
-int bwd_launch(const void* q, const void* k, const void* v, const float* out, const void* dout, float* dq, float* dk,
-               float* dv, const float* l, const float* m, float* ws, int batch, int N, fa::Layout lay, int causal,
-               int variant, float tau, int stages, hipStream_t st, const Tun& tun) {
-  const long rows = (long)batch * N;
-  float* nlc = ws;              // -L / tau        (raw score units)
-  float* delta = ws + rows;     // -rowsum(dO * O)
-  float* nl2 = ws + 2 * rows;   // -L * log2(e)    (the slot dK/dV kernel: its K fragments carry tau*log2(e))
+int bwd_launch(const Call& c) {
+  const long rows = (long)c.batch * c.N;
   constexpr int RPB = 256 / (D / 8);
-  const bool fuse_prep = dq_fuses_prep<T, D>(batch, N, lay, causal, stages, tun);
-  if ((stages & FA_BWD_STAGE_PREP) && !fuse_prep) {
-    FA_LAUNCH((fa::bwd_prep_kernel<T, D>), dim3((unsigned)((rows + RPB - 1) / RPB)), dim3(256), 0, st, out,
-                       (const T*)dout, l, m, nlc, delta, nl2, rows, N, lay, variant, 1.0f / tau);
+  const bool fuse_prep = dq_fuses_prep<T, D>(c);
+  if ((c.stages & FA_BWD_STAGE_PREP) && !fuse_prep) {
+    FA_LAUNCH((fa::bwd_prep_kernel<T, D>), dim3((unsigned)((rows + RPB - 1) / RPB)), dim3(256), 0, c.st, c.out,
+              (const T*)c.dout, c.l, c.m, c.nlc(), c.delta(), c.nl2(), rows, c.N, c.lay, c.variant, 1.0f / c.tau);
     FA_HIP_TRY(hipGetLastError());
   }
   if (fuse_prep) {   // dQ first: it preprocesses its own rows and leaves -L/tau, -delta in the workspace for the dK/dV kernel
-    const fa::DqPrep pa{out, l, m, nlc, delta, nl2, variant, 1.0f / tau};
-    const int rc = dq_stage<T, D>(q, k, v, dout, nlc, delta, dq, batch, N, lay, causal, tau, st, tun, &pa);
-    if (rc) return rc;
+    const fa::DqPrep pa{c.out, c.l, c.m, c.nlc(), c.delta(), c.nl2(), c.variant, 1.0f / c.tau};
+    if (const int rc = dq_stage<T, D>(c, &pa)) return rc;
   }
   if constexpr (sizeof(T) == 4 && D == 64) {
-    if (const int nsplit = onepass_f32<T, D>(batch, N, lay, causal, stages, tun)) {
+    if (const int nsplit = onepass_f32<T, D>(c)) {
       // the workgroups ADD into dq (the reference's caller zeroes q_grad for its atomicAdd as well: minitorch/cuda_kernel_ops.py:609-611);
       // [B][N][H][d] or [BH][N][d]: the tensor is one contiguous range either way
       if (!t_probe && !t_plan) {
-        FA_HIP_TRY(hipMemsetAsync(dq, 0, (size_t)rows * D * sizeof(float), st));
+        FA_HIP_TRY(hipMemsetAsync(c.dq, 0, (size_t)rows * D * sizeof(float), c.st));
         if (nsplit > 1) {   // the parts of a key block's sweep ADD their dK, dV
-          FA_HIP_TRY(hipMemsetAsync(dk, 0, (size_t)rows * D * sizeof(float), st));
-          FA_HIP_TRY(hipMemsetAsync(dv, 0, (size_t)rows * D * sizeof(float), st));
+          FA_HIP_TRY(hipMemsetAsync(c.dk, 0, (size_t)rows * D * sizeof(float), c.st));
+          FA_HIP_TRY(hipMemsetAsync(c.dv, 0, (size_t)rows * D * sizeof(float), c.st));
         }
       }
-      const int nkb = (N + 255) / 256;
-      if (causal) lay.rank_chunk = rank_chunk(1, nkb);   // key block 0 (the longest sweep) of a chunk of heads first
+      const int nkb = (c.N + 255) / 256;
+      fa::Layout lay = c.lay;
+      if (c.causal) lay.rank_chunk = rank_chunk(1, nkb);   // key block 0 (the longest sweep) of a chunk of heads first
 #define FA_ONEPASS(C, R)                                                                                                             \
-  FA_LAUNCH((fa::bwd_onepass_f32_kernel<D, C, R>), dim3((unsigned)(batch * nkb * nsplit)), dim3(512), 0, st, (const float*)q, (const float*)k, \
-            (const float*)v, (const float*)dout, nlc, delta, dq, dk, dv, N, nkb, batch, lay, tau, nsplit)
-      if (N % 256 == 0) {
-        if (causal) FA_ONEPASS(true, false); else FA_ONEPASS(false, false);
+  FA_LAUNCH((fa::bwd_onepass_f32_kernel<D, C, R>), dim3((unsigned)(c.batch * nkb * nsplit)), dim3(512), 0, c.st, (const float*)c.q,   \
+            (const float*)c.k, (const float*)c.v, (const float*)c.dout, c.nlc(), c.delta(), c.dq, c.dk, c.dv, c.N, nkb, c.batch, lay,   \
+            c.tau, nsplit)
+      if (c.N % 256 == 0) {
+        if (c.causal) FA_ONEPASS(true, false); else FA_ONEPASS(false, false);
       } else {
-        if (causal) FA_ONEPASS(true, true); else FA_ONEPASS(false, true);
+        if (c.causal) FA_ONEPASS(true, true); else FA_ONEPASS(false, true);
       }
 #undef FA_ONEPASS
       FA_HIP_TRY(hipGetLastError());
       return FA_OK;
     }
   }
-  if (stages & FA_BWD_STAGE_DKDV) {
-    int rc;
-    if constexpr (sizeof(T) == 2 && D <= 64) {
-      // measured at B=8,H=8,N=4096,d=64 (ms, one device, profiles/README.md): 8 waves x 32 keys, 128-query stages,
-      // software-pipelined sub-slices 0.505; not pipelined 0.514; 64-query stages 0.519; 256-query 0.525;
-      // 4 waves x 32 keys (two workgroups per CU) 0.521; 4 waves x 64 keys (one wave per SIMD) 0.559
-      if (tun.v[0] == 4 || D != 64)   // compiler-interleaved software pipeline (the d = 32 default)
-        rc = dkdv_launch<T, D, 32, 8, 128, 0>(q, k, v, dout, nlc, delta, dk, dv, batch, N, lay, causal, tau, st);
-      else if (D == 64 && !causal && tun.v[0] == 0 && !lay.drop_thr && !lay.kmask && N >= 64) {
-        // d = 64, non-causal default: the continuous slot pipeline (no drain at stage boundaries, three-slot LDS-DMA ring);
-        // rows thinned by a key mask or N < 64 go to the kernel below, whose per-sub-slice path splits P and dS
-        const int nkb = (N + 255) / 256;
-        // Key block kb of several consecutive heads per workgroup (the tiled build: no set-up, no wait for K / V fragments and
-        // stage 0, no store drain between them) while the grid still covers every CU; option 5 = 1: one head per workgroup
-        int tiles = 1;
-        if (N % 256 == 0 && tun.v[5] == 0) {
-          const int cus = std::max(device_cus(), 1);
-          for (int t = 2; t <= 16; ++t)
-            if (batch % t == 0 && (batch / t) % 8 == 0 && (long)(batch / t) * nkb >= cus) tiles = t;
-        }
-        if (tiles > 1) {
-          lay.tiles = tiles;
-          FA_LAUNCH_SEL((fa::bwd_dkdv_slot_kernel<T, 64, false, true>), dim3((batch / tiles) * nkb), dim3(512), 0, st,
-                             (const T*)q, (const T*)k, (const T*)v, (const T*)dout, nl2, delta, dk, dv, N, nkb, batch, lay, tau);
-        } else {
-          FA_LAUNCH_SEL((fa::bwd_dkdv_slot_kernel<T, 64>), dim3(batch * nkb), dim3(512), 0, st, (const T*)q,
-                             (const T*)k, (const T*)v, (const T*)dout, nl2, delta, dk, dv, N, nkb, batch, lay, tau);
-        }
-        FA_HIP_TRY(hipGetLastError());
-        rc = FA_OK;
-      } else if (D == 64 && causal && !lay.drop_thr && !lay.kmask && N % 256 == 0 &&
-                 (tun.v[0] == 5 || (tun.v[0] == 0 && batch * (N / 256) >= 128))) {   // (tuning key 0 = 5 forces it)
-        // d = 64, causal, N a multiple of 256: the causal build of the continuous pipeline (sweep of the stages below the
-        // diagonal block, the block per wave, workgroups longest first); tuning key 0 = 3: the phased kernel below
-        // (key blocks p and nkb-1-p of several consecutive heads per workgroup, a causal tiled build, gave bitwise the same results
-        // 4-8 % slower: profiles/r04_causal_tiled_dkdv.txt)
-        const int nkb = N / 256;
-        lay.rank_chunk = rank_chunk(1, nkb);
-        FA_LAUNCH_SEL((fa::bwd_dkdv_slot_kernel<T, 64, true>), dim3(batch * nkb), dim3(512), 0, st, (const T*)q,
-                           (const T*)k, (const T*)v, (const T*)dout, nl2, delta, dk, dv, N, nkb, batch, lay, tau);
-        FA_HIP_TRY(hipGetLastError());
-        rc = FA_OK;
-      } else if constexpr (D == 64) {   // d = 64, causal (or tuning 3): slot-interleaved fast path for unmasked stages, per-sub-slice path on the diagonal
-        // (a build with the masked paths compiled out, for non-causal launches, measured the same: 0.4983 vs 0.4992 ms)
-        rc = dkdv_launch<T, D, 32, 8, 128, 3>(q, k, v, dout, nlc, delta, dk, dv, batch, N, lay, causal, tau, st, 1);
-      } else {
-        rc = set_err(FA_ERR_BAD_ARG, "internal: no dK/dV kernel selected");   // (d = 32 never gets here: the branch above takes it)
-      }
-    } else if constexpr (sizeof(T) == 2) {
-      // d = 128 default (dropout / key mask / N < 64: dkdv_launch runs the 4-wave split-operand build, which has the registers for it): 8 waves x 32 keys, one 256-key workgroup per CU (half the Q / dO staging per MFMA): 3.64 vs 3.92 ms
-      rc = dkdv_launch<T, D, 32, 8, 64>(q, k, v, dout, nlc, delta, dk, dv, batch, N, lay, causal, tau, st, 0, tun.v[7] != 1);
-    } else if constexpr (D == 64) {
-      // fp32, d = 64 (configs[1], [2]): the allocation lands on 256 VGPRs + 2 AGPRs = one wave per SIMD; asking for two
-      // (launch bound) keeps it under 256
-      if (lay.drop_thr)
-        rc = dkdv_launch<T, D, 32, 4, 32, 0, true>(q, k, v, dout, nlc, delta, dk, dv, batch, N, lay, causal, tau, st);
-      else {
-        const int nkb = (N + 127) / 128;
-        // causal: longest block first across a chunk of heads instead of head by head: 0.57 vs 0.80 ms at the reference's timing-harness
-        // shape (B = 8, H = 8, N = 2048, fp32), bitwise the same (option 7 = 1: head by head)
-        if (causal && tun.v[7] != 1) lay.rank_chunk = rank_chunk(2, nkb);
-        FA_LAUNCH((fa::bwd_dkdv_kernel<T, D, 32, 4, 32, 0, false, 2>), dim3(batch * nkb), dim3(256), 0, st,
-                           (const T*)q, (const T*)k, (const T*)v, (const T*)dout, nlc, delta, dk, dv, N, nkb, batch, lay,
-                           causal, tau);
-        FA_HIP_TRY(hipGetLastError());
-        rc = FA_OK;
-      }
-    } else {
-      rc = dkdv_launch<T, D, 32, 4, 32>(q, k, v, dout, nlc, delta, dk, dv, batch, N, lay, causal, tau, st);
-    }
-    if (rc) return rc;
-  }
-  if ((stages & FA_BWD_STAGE_DQ) && !fuse_prep) {
-    const int rc = dq_stage<T, D>(q, k, v, dout, nlc, delta, dq, batch, N, lay, causal, tau, st, tun, nullptr);
-    if (rc) return rc;
-  }
+  if (c.stages & FA_BWD_STAGE_DKDV)
+    if (const int rc = dkdv_stage<T, D>(c)) return rc;
+  if ((c.stages & FA_BWD_STAGE_DQ) && !fuse_prep)
+    if (const int rc = dq_stage<T, D>(c, nullptr)) return rc;
   return FA_OK;
 }
 
-#define FA_DISPATCH(FN, ...)                                                              \
+#define FA_DISPATCH(FN)                                                                   \
   do {                                                                                    \
-    if (dtype == FA_DTYPE_BF16) {                                                         \
-      if (dp == 32) return FN<fa::bf16_t, 32>(__VA_ARGS__);                               \
-      if (dp == 64) return FN<fa::bf16_t, 64>(__VA_ARGS__);                               \
-      return FN<fa::bf16_t, 128>(__VA_ARGS__);                                            \
+    if (c.dtype == FA_DTYPE_BF16) {                                                       \
+      if (c.dp == 32) return FN<fa::bf16_t, 32>(c);                                       \
+      if (c.dp == 64) return FN<fa::bf16_t, 64>(c);                                       \
+      return FN<fa::bf16_t, 128>(c);                                                      \
     } else {                                                                              \
-      if (dp == 32) return FN<float, 32>(__VA_ARGS__);                                    \
-      if (dp == 64) return FN<float, 64>(__VA_ARGS__);                                    \
-      return FN<float, 128>(__VA_ARGS__);                                                 \
+      if (c.dp == 32) return FN<float, 32>(c);                                            \
+      if (c.dp == 64) return FN<float, 64>(c);                                            \
+      return FN<float, 128>(c);                                                           \
     }                                                                                     \
   } while (0)
+int fwd_dispatch_one(const Call& c) { FA_DISPATCH(fwd_launch); }
+int bwd_dispatch_one(const Call& c) { FA_DISPATCH(bwd_launch); }
+#undef FA_DISPATCH
 
 // tau uses the caller's d even when the rows are zero-padded to dp columns (zero columns of Q/K add
 // nothing to the scores; zero columns of V produce zero output columns that are dropped).
 fa::Layout bhnd(int N, int dp) { return fa::Layout{1, dp, (long)N * dp, 0, nullptr, 1, 0u, 1.0f, 0u, 0}; }
 fa::Layout bnhd(int H, int N, int dp) { return fa::Layout{H, H * dp, (long)N * H * dp, (long)dp, nullptr, 1, 0u, 1.0f, 0u, 0}; }
-
-// ---- where tau*log2(e) is applied (round 4) -------------------------------------------------------------------------------------
-// The MFMA-slot kernels fold c = tau*log2(e) into one bf16 operand (one more 2^-9 relative rounding of q or k, worth 8-10 % of the
-// step); everything else scales each score in fp32, as the reference does (src/flash_attn2_fw.cu:152-167).  The fold is invisible at
-// the north star's U(-1, 1) inputs and grows with the square of the input magnitude (x2: 1.4e-3 on O against 0.7e-3; x6: 3.6e-2
-// against 3.6e-3, profiles/r03_prescale_accuracy.txt), so it needs evidence about the operands:
-//   * a call WITH a scale guard (fa_mi355x_scale_guard: one pass over q and k on the device, no host synchronisation) launches the
-//     selected kernels AND their fp32-scaling twins; every workgroup evaluates the guard on entry and the launch on the wrong side of
-//     the budget returns at once (fa_common.h: guard_skip).  Estimate: 2^-9 / sqrt(3) * c * max_rows |q| * max_rows |k| against
-//     GUARD_BUDGET (log2 units): U(-1, 1) gives 5.7e-3 at d = 64 and 7e-3 at d = 128, inputs 1.3x larger go to fp32 scaling.
-//   * a call WITHOUT one scales in fp32 (the phased forward; the backward's slot kernels carry both scalings in one launch and
-//     take their fp32 copy of the sweep: no twin launches in the backward at all), unless
-//     option 8 = 1 (the caller vouches for the range), the selection folds nothing anyway (fp32, d = 32, key mask, dropout, ragged N:
-//     probed with a dry run of the dispatch code), or c is 1 (softmax_scale = ln 2: the operand multiply is exact).
-constexpr float GUARD_BUDGET = 1e-2f;
-inline Tun exact_tun(Tun t) {   // the forward that scales every score in fp32 (the phased kernel), whatever else the caller selected
-  t.v[1] = 2;
-  return t;
-}
-// produce (forward calls only, option 8 = 0): the call FILLS `guard` instead of reading it, so that the backward of the same (q, k)
-// can take it: a forward that folds produces it inside its own launch (fa_common.h: guard_produce: no separate pass over q and k;
-// the launch runs with the folded scale and its fp32-scaling twin, behind it, redoes the call if the finished guard says so);
-// a forward whose selection folds nothing runs the separate pass (guard_pass), because the backward of the same call may fold.
-template <class F, class Z, class G>
-int run_scaled(F&& run, const Tun& tun, fa::Layout lay, float tau, const float* guard, int produce, Z&& zero_guard, G&& guard_pass) {
-  const float c = tau * fa::LOG2E;
-  const int mode = tun.v[8];
-  lay.scale_sel = 0;
-  if (mode == 1 || fabsf(c - 1.0f) < 1e-6f) return run(tun, lay);
-  if (mode == 3 && t_plan) guard = reinterpret_cast<const float*>(16);   // fa_mi355x_plan: both launches of a guarded call
-  // the backward's MFMA-slot kernels hold both scalings in one launch: fp32 scaling without a guard, the guard's choice with one
-  lay.scale_sel = (mode == 2 || !guard) ? 1 : 2;
-  if (lay.scale_sel == 2) {
-    lay.guard = guard;
-    lay.guard_coef = c * (0.001953125f * 0.57735027f) / GUARD_BUDGET;
-    lay.guard_want = 3;   // (no launch of this run is skipped)
-  }
-  if (!plan_mode() || t_plan) {   // does the selection fold at all?  (dry run: no launch, no HIP call, nothing recorded)
-    std::vector<std::string>* keep = t_plan;
-    t_plan = nullptr;
-    t_probe = true;
-    t_fold = t_fold_produces = false;
-    const int rc = run(tun, lay);
-    t_probe = false;
-    t_plan = keep;
-    if (rc) return rc;
-    if (!t_fold) {
-      if (produce && guard && mode == 0)
-        if (const int rc2 = guard_pass()) return rc2;
-      return run(tun, lay);
-    }
-  }
-  if (mode == 2 || !guard) return run(exact_tun(tun), lay);
-  lay.guard = guard;
-  lay.guard_coef = c * (0.001953125f * 0.57735027f) / GUARD_BUDGET;
-  if (produce && t_fold_produces) {
-    if (const int rc = zero_guard()) return rc;
-    lay.guard_want = 2;
-  } else {
-    if (produce)   // (a folding forward that cannot fill the guard itself: the causal slot build)
-      if (const int rc = guard_pass()) return rc;
-    lay.guard_want = 0;
-  }
-  if (const int rc = run(tun, lay)) return rc;
-  lay.guard_want = 1;
-  return run(exact_tun(tun), lay);
-}
 
 int launch_scale_guard(const void* q, const void* k, long rows, int row_elems, int dtype, void* guard, hipStream_t st) {
   // only bf16 rows of 64 / 128 elements ever reach a kernel that folds the scale into an operand: everything else gets an all-zero
@@ -723,51 +695,161 @@ int launch_scale_guard(const void* q, const void* k, long rows, int row_elems, i
   return FA_OK;
 }
 
-int fwd_dispatch_one(const void* q, const void* k, const void* v, float* out, float* l, float* m, int batch, int N, int dp,
-                     fa::Layout lay, int causal, int variant, int dtype, hipStream_t st, const Tun& tun, float tau) {
-  FA_DISPATCH(fwd_launch, q, k, v, out, l, m, batch, N, lay, causal, variant, tau, st, tun);
-}
-int bwd_dispatch_one(const void* q, const void* k, const void* v, const float* out, const void* dout, float* dq, float* dk,
-                     float* dv, const float* l, const float* m, float* ws, int batch, int N, int dp, fa::Layout lay, int causal,
-                     int variant, int dtype, int stages, hipStream_t st, const Tun& tun, float tau) {
-  FA_DISPATCH(bwd_launch, q, k, v, out, dout, dq, dk, dv, l, m, ws, batch, N, lay, causal, variant, tau, stages, st, tun);
-}
-
-int fwd_dispatch(const void* q, const void* k, const void* v, float* out, float* l, float* m, int batch, int N, int d,
-                 int dp, fa::Layout lay, int causal, int variant, int dtype, hipStream_t st, const Tun& tun = default_tun(),
-                 float scale = 0.f, const float* guard = nullptr, int produce = 0) {
-  const float tau = scale > 0.f ? scale : sqrtf(1.0f / (float)d);   // (scale: fa_mi355x_*_scaled; the reference has sqrt(1/d) only)
-  lay.young_prio = tun.v[3];
-  lay.out_bf16 = tun.v[9] == 1 ? 1 : 0;
-  return run_scaled([&](const Tun& t, const fa::Layout& L) {
-    return fwd_dispatch_one(q, k, v, out, l, m, batch, N, dp, L, causal, variant, dtype, st, t, tau);
-  }, tun, lay, tau, guard, produce,
-  [&]() -> int {
-    if (t_plan) { t_plan->emplace_back("memset"); return FA_OK; }
-    FA_HIP_TRY(hipMemsetAsync(const_cast<float*>(guard), 0, (size_t)2 * fa::GUARD_SLOTS * sizeof(float), st));
-    return FA_OK;
-  },
-  [&]() -> int { return launch_scale_guard(q, k, (long)batch * N, dp, dtype, const_cast<float*>(guard), st); });
-}
-
-int bwd_dispatch(const void* q, const void* k, const void* v, const float* out, const void* dout, float* dq, float* dk,
-                 float* dv, const float* l, const float* m, float* ws, int batch, int N, int d, int dp, fa::Layout lay,
-                 int causal, int variant, int dtype, int stages, hipStream_t st, const Tun& tun = default_tun(), float scale = 0.f,
-                 const float* guard = nullptr) {
-  const float tau = scale > 0.f ? scale : sqrtf(1.0f / (float)d);
-  lay.young_prio = tun.v[3];
-  return run_scaled([&](const Tun& t, const fa::Layout& L) {
-    return bwd_dispatch_one(q, k, v, out, dout, dq, dk, dv, l, m, ws, batch, N, dp, L, causal, variant, dtype, stages, st, t, tau);
-  }, tun, lay, tau, guard, 0, []() -> int { return FA_OK; }, []() -> int { return FA_OK; });
-}
-
-int check_common(int batch, int N, int d, int variant, int dtype) {
-  if (batch <= 0 || N <= 0 || d <= 0) return set_err(FA_ERR_BAD_ARG, "batch, N and d must be positive");
-  if (variant != FA_VARIANT_FA1 && variant != FA_VARIANT_FA2) return set_err(FA_ERR_BAD_ARG, "unknown variant");
-  if (dtype != FA_DTYPE_F32 && dtype != FA_DTYPE_BF16) return set_err(FA_ERR_BAD_ARG, "unknown dtype");
-  if ((long)N * 128 * 4 >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "N too large: one (batch*head) matrix must stay under 2 GiB");
+// produce: a folding forward fills the call's guard inside its own launch, into the zeroed buffer ...
+int zero_guard(const Call& c) {
+  if (t_plan) { t_plan->emplace_back("memset"); return FA_OK; }
+  FA_HIP_TRY(hipMemsetAsync(const_cast<float*>(c.guard), 0, (size_t)2 * fa::GUARD_SLOTS * sizeof(float), c.st));
   return FA_OK;
 }
+// ... any other forward by the separate pass over q and k
+int guard_pass(const Call& c) {
+  return launch_scale_guard(c.q, c.k, (long)c.batch * c.N, c.dp, c.dtype, const_cast<float*>(c.guard), c.st);
+}
+
+// ---- where tau*log2(e) is applied (round 4) -------------------------------------------------------------------------------------
+// The MFMA-slot kernels fold c = tau*log2(e) into one bf16 operand (one more 2^-9 relative rounding of q or k, worth 8-10 % of the
+// step); everything else scales each score in fp32, as the reference does (src/flash_attn2_fw.cu:152-167).  The fold is invisible at
+// the north star's U(-1, 1) inputs and grows with the square of the input magnitude (x2: 1.4e-3 on O against 0.7e-3; x6: 3.6e-2
+// against 3.6e-3, profiles/r03_prescale_accuracy.txt), so it needs evidence about the operands:
+//   * a call WITH a scale guard (fa_mi355x_scale_guard: one pass over q and k on the device, no host synchronisation) launches the
+//     selected kernels AND their fp32-scaling twins; every workgroup evaluates the guard on entry and the launch on the wrong side of
+//     the budget returns at once (fa_common.h: guard_skip).  Estimate: 2^-9 / sqrt(3) * c * max_rows |q| * max_rows |k| against
+//     GUARD_BUDGET (log2 units): U(-1, 1) gives 5.7e-3 at d = 64 and 7e-3 at d = 128, inputs 1.3x larger go to fp32 scaling.
+//   * a call WITHOUT one scales in fp32 (the phased forward; the backward's slot kernels carry both scalings in one launch and
+//     take their fp32 copy of the sweep: no twin launches in the backward at all), unless
+//     option 8 = 1 (the caller vouches for the range), the selection folds nothing anyway (fp32, d = 32, key mask, dropout, ragged N:
+//     probed with a dry run of the dispatch code), or c is 1 (softmax_scale = ln 2: the operand multiply is exact).
+constexpr float GUARD_BUDGET = 1e-2f;
+inline Call exact(Call call) {   // the forward that scales every score in fp32 (the phased kernel), whatever else the caller selected
+  call.tun.v[1] = 2;
+  return call;
+}
+// produce (forward calls only, option 8 = 0): the call FILLS `guard` instead of reading it, so that the backward of the same (q, k)
+// can take it: a forward that folds produces it inside its own launch (fa_common.h: guard_produce: no separate pass over q and k;
+// the launch runs with the folded scale and its fp32-scaling twin, behind it, redoes the call if the finished guard says so);
+// a forward whose selection folds nothing runs the separate pass (guard_pass), because the backward of the same call may fold.
+int run_scaled(Call call, int (*run)(const Call&)) {
+  const float c = call.tau * fa::LOG2E;
+  const int mode = call.tun.v[8], produce = call.produce;
+  const float* guard = call.guard;
+  fa::Layout& lay = call.lay;
+  lay.scale_sel = 0;
+  if (mode == 1 || fabsf(c - 1.0f) < 1e-6f) return run(call);
+  if (mode == 3 && t_plan) guard = reinterpret_cast<const float*>(16);   // fa_mi355x_plan: both launches of a guarded call
+  // the backward's MFMA-slot kernels hold both scalings in one launch: fp32 scaling without a guard, the guard's choice with one
+  lay.scale_sel = (mode == 2 || !guard) ? 1 : 2;
+  if (lay.scale_sel == 2) {
+    lay.guard = guard;
+    lay.guard_coef = c * (0.001953125f * 0.57735027f) / GUARD_BUDGET;
+    lay.guard_want = 3;   // (no launch of this run is skipped)
+  }
+  if (!plan_mode() || t_plan) {   // does the selection fold at all?  (dry run: no launch, no HIP call, nothing recorded)
+    std::vector<std::string>* keep = t_plan;
+    t_plan = nullptr;
+    t_probe = true;
+    t_fold = t_fold_produces = false;
+    const int rc = run(call);
+    t_probe = false;
+    t_plan = keep;
+    if (rc) return rc;
+    if (!t_fold) {
+      if (produce && guard && mode == 0)
+        if (const int rc2 = guard_pass(call)) return rc2;
+      return run(call);
+    }
+  }
+  if (mode == 2 || !guard) return run(exact(call));
+  lay.guard = guard;
+  lay.guard_coef = c * (0.001953125f * 0.57735027f) / GUARD_BUDGET;
+  if (produce && t_fold_produces) {
+    if (const int rc = zero_guard(call)) return rc;
+    lay.guard_want = 2;
+  } else {
+    if (produce)   // (a folding forward that cannot fill the guard itself: the causal slot build)
+      if (const int rc = guard_pass(call)) return rc;
+    lay.guard_want = 0;
+  }
+  if (const int rc = run(call)) return rc;
+  lay.guard_want = 1;
+  return run(exact(call));
+}
+
+int fwd_dispatch(Call c) {
+  c.tau = c.scale > 0.f ? c.scale : sqrtf(1.0f / (float)c.d);   // (scale: fa_mi355x_*_scaled / _guarded; the reference has sqrt(1/d) only)
+  c.lay.out_bf16 = c.tun.v[9] == 1 ? 1 : 0;
+  return run_scaled(c, fwd_dispatch_one);
+}
+
+int bwd_dispatch(Call c) {
+  c.tau = c.scale > 0.f ? c.scale : sqrtf(1.0f / (float)c.d);
+  return run_scaled(c, bwd_dispatch_one);
+}
+
+// The checks of every device entry point, in one order: the first that fails decides the return code and fa_mi355x_last_error().
+// The rules that differ between entry points are the call's fields (bwd, by_heads, padded, scale_required; arguments an entry point
+// does not take keep defaults that pass).  Completes the call: batch, dp, tun, lay.
+int validate(Call& c) {
+  g_err[0] = 0;
+  if (int rc = parse_opts(c.opts, c.nopts, c.tun)) return rc;
+  if (c.bwd && (c.stages <= 0 || c.stages > FA_BWD_STAGE_ALL)) return set_err(FA_ERR_BAD_ARG, "bad stages mask");
+  if (c.by_heads && (c.B <= 0 || c.H <= 0)) return set_err(FA_ERR_BAD_ARG, "B and H must be positive");
+  c.batch = c.B * c.H;
+  if (c.batch <= 0 || c.N <= 0 || c.d <= 0) return set_err(FA_ERR_BAD_ARG, "batch, N and d must be positive");
+  if (c.variant != FA_VARIANT_FA1 && c.variant != FA_VARIANT_FA2) return set_err(FA_ERR_BAD_ARG, "unknown variant");
+  if (c.dtype != FA_DTYPE_F32 && c.dtype != FA_DTYPE_BF16) return set_err(FA_ERR_BAD_ARG, "unknown dtype");
+  if ((long)c.N * 128 * 4 >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "N too large: one (batch*head) matrix must stay under 2 GiB");
+  if (!c.q || !c.k || !c.v || !c.out || !c.l || (c.variant == FA_VARIANT_FA1 && !c.m) ||
+      (c.bwd && (!c.dout || !c.dq || !c.dk || !c.dv || !c.ws)))
+    return set_err(FA_ERR_BAD_ARG, "null pointer argument");
+  if (c.produce && !c.guard) return set_err(FA_ERR_BAD_ARG, "produce_guard needs a guard buffer");
+  if (!c.padded) c.dp = c.d;
+  if (c.padded && (!d_supported(c.dp) || c.d > c.dp))
+    return set_err(FA_ERR_UNSUPPORTED_D, "padded row length dp must be 32, 64 or 128 and >= d");
+  if (!d_supported(c.dp)) return set_err(FA_ERR_UNSUPPORTED_D, "device path supports d in {32, 64, 128}");
+  if (c.by_heads && c.layout != FA_LAYOUT_BHND && c.layout != FA_LAYOUT_BNHD) return set_err(FA_ERR_BAD_ARG, "unknown layout");
+  if (c.scale_required && (!(c.scale > 0.f) || !std::isfinite(c.scale)))
+    return set_err(FA_ERR_BAD_ARG, "softmax_scale must be positive and finite");
+  if (c.scale != 0.f && (!(c.scale > 0.f) || !std::isfinite(c.scale)))
+    return set_err(FA_ERR_BAD_ARG, "softmax_scale must be positive and finite (0: sqrt(1/d))");
+  if (c.by_heads && (long)c.N * c.H * c.d * 4 >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "one batch element must stay under 2 GiB");
+  if (!(c.drop_rate >= 0.0f && c.drop_rate < 1.0f)) return set_err(FA_ERR_BAD_ARG, "dropout rate must be in [0, 1)");
+  c.lay = c.layout == FA_LAYOUT_BNHD ? bnhd(c.H, c.N, c.dp) : bhnd(c.N, c.dp);
+  c.lay.kmask = c.kmask;
+  c.lay.mask_heads = c.mask_heads;
+  c.lay.drop_thr = (uint32_t)((double)c.drop_rate * 16777216.0);   // floor(rate * 2^24); 0 disables dropout
+  c.lay.drop_scale = c.drop_scale;
+  c.lay.drop_seed = c.drop_seed;
+  return FA_OK;
+}
+
+int validate_and_dispatch(Call c) {
+  if (int rc = validate(c)) return rc;
+  return c.bwd ? bwd_dispatch(c) : fwd_dispatch(c);
+}
+
+Call fwd_call(const void* q, const void* k, const void* v, float* out, float* l, float* m, int B, int N, int d, int causal,
+              int variant, int dtype, void* stream) {
+  Call c;
+  c.q = q; c.k = k; c.v = v; c.out = out; c.l = l; c.m = m;
+  c.B = B; c.N = N; c.d = d; c.causal = causal ? 1 : 0; c.variant = variant; c.dtype = dtype; c.st = (hipStream_t)stream;
+  return c;
+}
+Call bwd_call(const void* q, const void* k, const void* v, const float* out, const void* dout, float* dq, float* dk, float* dv,
+              const float* l, const float* m, void* ws, int B, int N, int d, int causal, int variant, int dtype, int stages,
+              void* stream) {
+  Call c = fwd_call(q, k, v, const_cast<float*>(out), const_cast<float*>(l), const_cast<float*>(m), B, N, d, causal, variant, dtype,
+                    stream);
+  c.bwd = true;
+  c.dout = dout; c.dq = dq; c.dk = dk; c.dv = dv; c.ws = (float*)ws; c.stages = stages;
+  return c;
+}
+Call heads(Call c, int H, int layout) {   // the B, H, layout form (fwd_call / bwd_call took B)
+  c.by_heads = true;
+  c.H = H;
+  c.layout = layout;
+  return c;
+}
+
 
 // ---- host-pointer path ------------------------------------------------------------------------
 // A grow-only device arena replaces the reference's per-call cudaMalloc/cudaFree of 6 (fw) or 10 (bw)
@@ -946,6 +1028,14 @@ struct HostTimer {
     fprintf(stderr, "[fa_mi355x host %s] pin %.2f ms, pipeline %.2f ms, unpin %.2f ms\n", what, ms(t0, t1), ms(t1, t2), ms(t2, t3));
   }
 };
+// The call of one chunk of a host-pointer launcher (fp32 rows of dp elements in the arena, default options; the launcher has checked
+// its arguments itself): the pointers are filled in per chunk
+Call host_call(int batch, int N, int d, int dp, bool causal, int variant, hipStream_t st) {
+  Call c;
+  c.batch = batch; c.N = N; c.d = d; c.dp = dp; c.causal = causal ? 1 : 0; c.variant = variant; c.dtype = FA_DTYPE_F32; c.st = st;
+  c.lay = bhnd(N, dp);
+  return c;
+}
 inline int host_chunks(int batch, size_t bytes_per_bh) {
   // ~32 MiB of input per chunk and tensor, at most 8 chunks: enough to hide the tails, few enough to keep the launches cheap
   const size_t want = (bytes_per_bh * (size_t)batch + (32u << 20) - 1) / (32u << 20);
@@ -1008,20 +1098,17 @@ int fa_mi355x_measure_mfma_peak(double min_ms, double* tflops, double* clock_ghz
 
 int fa_mi355x_plan(int batch, int N, int d, int causal, int variant, int dtype, int stages, const int* opts, int nopts, char* out,
                    size_t n) {
-  g_err[0] = 0;
-  Tun tun;
-  if (int rc = parse_opts(opts, nopts, tun)) return rc;
-  if (stages < 0 || stages > FA_BWD_STAGE_ALL) return set_err(FA_ERR_BAD_ARG, "bad stages mask");
-  if (int rc = check_common(batch, N, d, variant, dtype)) return rc;
-  if (!d_supported(d)) return set_err(FA_ERR_UNSUPPORTED_D, "device path supports d in {32, 64, 128}");
+  // the dispatch functions only pass their pointers on to the (skipped) launches: any non-null values do
+  float* one = reinterpret_cast<float*>(16);
+  Call c = bwd_call(one, one, one, one, one, one, one, one, one, one, one, batch, N, d, causal, variant, dtype, stages, nullptr);
+  c.bwd = stages != 0;   // stages = 0: the forward
+  c.opts = opts;
+  c.nopts = nopts;
+  if (int rc = validate(c)) return rc;
   if (!out || n == 0) return set_err(FA_ERR_BAD_ARG, "null output buffer");
   std::vector<std::string> names;
   t_plan = &names;
-  // the dispatch functions only pass their pointers on to the (skipped) launches: any non-null values do
-  float* one = reinterpret_cast<float*>(16);
-  const int rc = stages == 0 ? fwd_dispatch(one, one, one, one, one, one, batch, N, d, d, bhnd(N, d), causal ? 1 : 0, variant, dtype, nullptr, tun)
-                             : bwd_dispatch(one, one, one, one, one, one, one, one, one, one, one, batch, N, d, d, bhnd(N, d), causal ? 1 : 0,
-                                            variant, dtype, stages, nullptr, tun);
+  const int rc = c.bwd ? bwd_dispatch(c) : fwd_dispatch(c);
   t_plan = nullptr;
   if (rc) return rc;
   std::string joined;
@@ -1033,213 +1120,118 @@ int fa_mi355x_plan(int batch, int N, int d, int causal, int variant, int dtype, 
 
 int fa_mi355x_fwd(const void* q, const void* k, const void* v, float* out, float* l, float* m, int batch, int N,
                   int d, int causal, int variant, int dtype, void* stream) {
-  g_err[0] = 0;
-  if (int rc = check_common(batch, N, d, variant, dtype)) return rc;
-  if (!q || !k || !v || !out || !l || (variant == FA_VARIANT_FA1 && !m))
-    return set_err(FA_ERR_BAD_ARG, "null pointer argument");
-  if (!d_supported(d)) return set_err(FA_ERR_UNSUPPORTED_D, "device path supports d in {32, 64, 128}");
-  return fwd_dispatch(q, k, v, out, l, m, batch, N, d, d, bhnd(N, d), causal ? 1 : 0, variant, dtype,
-                      (hipStream_t)stream);
+  return validate_and_dispatch(fwd_call(q, k, v, out, l, m, batch, N, d, causal, variant, dtype, stream));
 }
 
 int fa_mi355x_fwd_ex(const void* q, const void* k, const void* v, float* out, float* l, float* m, int batch, int N, int d,
                      int causal, int variant, int dtype, const int* opts, int nopts, void* stream) {
-  g_err[0] = 0;
-  Tun tun;
-  if (int rc = parse_opts(opts, nopts, tun)) return rc;
-  if (int rc = check_common(batch, N, d, variant, dtype)) return rc;
-  if (!q || !k || !v || !out || !l || (variant == FA_VARIANT_FA1 && !m))
-    return set_err(FA_ERR_BAD_ARG, "null pointer argument");
-  if (!d_supported(d)) return set_err(FA_ERR_UNSUPPORTED_D, "device path supports d in {32, 64, 128}");
-  return fwd_dispatch(q, k, v, out, l, m, batch, N, d, d, bhnd(N, d), causal ? 1 : 0, variant, dtype, (hipStream_t)stream, tun);
+  Call c = fwd_call(q, k, v, out, l, m, batch, N, d, causal, variant, dtype, stream);
+  c.opts = opts;
+  c.nopts = nopts;
+  return validate_and_dispatch(c);
 }
 
 int fa_mi355x_bwd_ex(const void* q, const void* k, const void* v, const float* out, const void* out_grad, float* q_grad,
                      float* k_grad, float* v_grad, const float* l, const float* m, void* workspace, int batch, int N, int d,
                      int causal, int variant, int dtype, int stages, const int* opts, int nopts, void* stream) {
-  g_err[0] = 0;
-  Tun tun;
-  if (int rc = parse_opts(opts, nopts, tun)) return rc;
-  if (stages <= 0 || stages > FA_BWD_STAGE_ALL) return set_err(FA_ERR_BAD_ARG, "bad stages mask");
-  if (int rc = check_common(batch, N, d, variant, dtype)) return rc;
-  if (!q || !k || !v || !out || !out_grad || !q_grad || !k_grad || !v_grad || !l || !workspace ||
-      (variant == FA_VARIANT_FA1 && !m))
-    return set_err(FA_ERR_BAD_ARG, "null pointer argument");
-  if (!d_supported(d)) return set_err(FA_ERR_UNSUPPORTED_D, "device path supports d in {32, 64, 128}");
-  return bwd_dispatch(q, k, v, out, out_grad, q_grad, k_grad, v_grad, l, m, (float*)workspace, batch, N, d, d, bhnd(N, d),
-                      causal ? 1 : 0, variant, dtype, stages, (hipStream_t)stream, tun);
+  Call c = bwd_call(q, k, v, out, out_grad, q_grad, k_grad, v_grad, l, m, workspace, batch, N, d, causal, variant, dtype, stages, stream);
+  c.opts = opts;
+  c.nopts = nopts;
+  return validate_and_dispatch(c);
 }
 
 int fa_mi355x_fwd_scaled(const void* q, const void* k, const void* v, float* out, float* l, float* m, int B, int H, int N, int d,
                          int layout, float softmax_scale, int causal, int variant, int dtype, void* stream) {
-  g_err[0] = 0;
-  if (B <= 0 || H <= 0) return set_err(FA_ERR_BAD_ARG, "B and H must be positive");
-  if (int rc = check_common(B * H, N, d, variant, dtype)) return rc;
-  if (!q || !k || !v || !out || !l || (variant == FA_VARIANT_FA1 && !m)) return set_err(FA_ERR_BAD_ARG, "null pointer argument");
-  if (!d_supported(d)) return set_err(FA_ERR_UNSUPPORTED_D, "device path supports d in {32, 64, 128}");
-  if (layout != FA_LAYOUT_BHND && layout != FA_LAYOUT_BNHD) return set_err(FA_ERR_BAD_ARG, "unknown layout");
-  if (!(softmax_scale > 0.f) || !std::isfinite(softmax_scale)) return set_err(FA_ERR_BAD_ARG, "softmax_scale must be positive and finite");
-  if ((long)N * H * d * 4 >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "one batch element must stay under 2 GiB");
-  const fa::Layout lay = layout == FA_LAYOUT_BNHD ? bnhd(H, N, d) : bhnd(N, d);
-  return fwd_dispatch(q, k, v, out, l, m, B * H, N, d, d, lay, causal ? 1 : 0, variant, dtype, (hipStream_t)stream, default_tun(),
-                      softmax_scale);
+  Call c = heads(fwd_call(q, k, v, out, l, m, B, N, d, causal, variant, dtype, stream), H, layout);
+  c.scale = softmax_scale;
+  c.scale_required = true;
+  return validate_and_dispatch(c);
 }
 
 int fa_mi355x_bwd_scaled(const void* q, const void* k, const void* v, const float* out, const void* out_grad, float* q_grad,
                          float* k_grad, float* v_grad, const float* l, const float* m, void* workspace, int B, int H, int N, int d,
                          int layout, float softmax_scale, int causal, int variant, int dtype, void* stream) {
-  g_err[0] = 0;
-  if (B <= 0 || H <= 0) return set_err(FA_ERR_BAD_ARG, "B and H must be positive");
-  if (int rc = check_common(B * H, N, d, variant, dtype)) return rc;
-  if (!q || !k || !v || !out || !out_grad || !q_grad || !k_grad || !v_grad || !l || !workspace ||
-      (variant == FA_VARIANT_FA1 && !m))
-    return set_err(FA_ERR_BAD_ARG, "null pointer argument");
-  if (!d_supported(d)) return set_err(FA_ERR_UNSUPPORTED_D, "device path supports d in {32, 64, 128}");
-  if (layout != FA_LAYOUT_BHND && layout != FA_LAYOUT_BNHD) return set_err(FA_ERR_BAD_ARG, "unknown layout");
-  if (!(softmax_scale > 0.f) || !std::isfinite(softmax_scale)) return set_err(FA_ERR_BAD_ARG, "softmax_scale must be positive and finite");
-  if ((long)N * H * d * 4 >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "one batch element must stay under 2 GiB");
-  const fa::Layout lay = layout == FA_LAYOUT_BNHD ? bnhd(H, N, d) : bhnd(N, d);
-  return bwd_dispatch(q, k, v, out, out_grad, q_grad, k_grad, v_grad, l, m, (float*)workspace, B * H, N, d, d, lay,
-                      causal ? 1 : 0, variant, dtype, FA_BWD_STAGE_ALL, (hipStream_t)stream, default_tun(), softmax_scale);
+  Call c = heads(bwd_call(q, k, v, out, out_grad, q_grad, k_grad, v_grad, l, m, workspace, B, N, d, causal, variant, dtype,
+                          FA_BWD_STAGE_ALL, stream), H, layout);
+  c.scale = softmax_scale;
+  c.scale_required = true;
+  return validate_and_dispatch(c);
 }
 
 int fa_mi355x_fwd_padded(const void* q, const void* k, const void* v, float* out, float* l, float* m, int batch, int N, int d,
                          int dp, int causal, int variant, int dtype, void* stream) {
-  g_err[0] = 0;
-  if (int rc = check_common(batch, N, d, variant, dtype)) return rc;
-  if (!q || !k || !v || !out || !l || (variant == FA_VARIANT_FA1 && !m)) return set_err(FA_ERR_BAD_ARG, "null pointer argument");
-  if (!d_supported(dp) || d > dp) return set_err(FA_ERR_UNSUPPORTED_D, "padded row length dp must be 32, 64 or 128 and >= d");
-  return fwd_dispatch(q, k, v, out, l, m, batch, N, d, dp, bhnd(N, dp), causal ? 1 : 0, variant, dtype, (hipStream_t)stream);
+  Call c = fwd_call(q, k, v, out, l, m, batch, N, d, causal, variant, dtype, stream);
+  c.padded = true;
+  c.dp = dp;
+  return validate_and_dispatch(c);
 }
 
 int fa_mi355x_bwd_padded(const void* q, const void* k, const void* v, const float* out, const void* out_grad, float* q_grad,
                          float* k_grad, float* v_grad, const float* l, const float* m, void* workspace, int batch, int N, int d,
                          int dp, int causal, int variant, int dtype, void* stream) {
-  g_err[0] = 0;
-  if (int rc = check_common(batch, N, d, variant, dtype)) return rc;
-  if (!q || !k || !v || !out || !out_grad || !q_grad || !k_grad || !v_grad || !l || !workspace ||
-      (variant == FA_VARIANT_FA1 && !m))
-    return set_err(FA_ERR_BAD_ARG, "null pointer argument");
-  if (!d_supported(dp) || d > dp) return set_err(FA_ERR_UNSUPPORTED_D, "padded row length dp must be 32, 64 or 128 and >= d");
-  return bwd_dispatch(q, k, v, out, out_grad, q_grad, k_grad, v_grad, l, m, (float*)workspace, batch, N, d, dp, bhnd(N, dp),
-                      causal ? 1 : 0, variant, dtype, FA_BWD_STAGE_ALL, (hipStream_t)stream);
+  Call c = bwd_call(q, k, v, out, out_grad, q_grad, k_grad, v_grad, l, m, workspace, batch, N, d, causal, variant, dtype,
+                    FA_BWD_STAGE_ALL, stream);
+  c.padded = true;
+  c.dp = dp;
+  return validate_and_dispatch(c);
 }
 
 int fa_mi355x_fwd_layout(const void* q, const void* k, const void* v, float* out, float* l, float* m, int B, int H,
                          int N, int d, int layout, int causal, int variant, int dtype, void* stream) {
-  g_err[0] = 0;
-  if (B <= 0 || H <= 0) return set_err(FA_ERR_BAD_ARG, "B and H must be positive");
-  if (int rc = check_common(B * H, N, d, variant, dtype)) return rc;
-  if (!q || !k || !v || !out || !l || (variant == FA_VARIANT_FA1 && !m))
-    return set_err(FA_ERR_BAD_ARG, "null pointer argument");
-  if (!d_supported(d)) return set_err(FA_ERR_UNSUPPORTED_D, "device path supports d in {32, 64, 128}");
-  if (layout != FA_LAYOUT_BHND && layout != FA_LAYOUT_BNHD) return set_err(FA_ERR_BAD_ARG, "unknown layout");
-  if ((long)N * H * d * 4 >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "one batch element must stay under 2 GiB");
-  const fa::Layout lay = layout == FA_LAYOUT_BNHD ? bnhd(H, N, d) : bhnd(N, d);
-  return fwd_dispatch(q, k, v, out, l, m, B * H, N, d, d, lay, causal ? 1 : 0, variant, dtype, (hipStream_t)stream);
+  return validate_and_dispatch(heads(fwd_call(q, k, v, out, l, m, B, N, d, causal, variant, dtype, stream), H, layout));
 }
 
 int fa_mi355x_bwd_layout(const void* q, const void* k, const void* v, const float* out, const void* out_grad,
                          float* q_grad, float* k_grad, float* v_grad, const float* l, const float* m, void* workspace,
                          int B, int H, int N, int d, int layout, int causal, int variant, int dtype, void* stream) {
-  g_err[0] = 0;
-  if (B <= 0 || H <= 0) return set_err(FA_ERR_BAD_ARG, "B and H must be positive");
-  if (int rc = check_common(B * H, N, d, variant, dtype)) return rc;
-  if (!q || !k || !v || !out || !out_grad || !q_grad || !k_grad || !v_grad || !l || !workspace ||
-      (variant == FA_VARIANT_FA1 && !m))
-    return set_err(FA_ERR_BAD_ARG, "null pointer argument");
-  if (!d_supported(d)) return set_err(FA_ERR_UNSUPPORTED_D, "device path supports d in {32, 64, 128}");
-  if (layout != FA_LAYOUT_BHND && layout != FA_LAYOUT_BNHD) return set_err(FA_ERR_BAD_ARG, "unknown layout");
-  if ((long)N * H * d * 4 >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "one batch element must stay under 2 GiB");
-  const fa::Layout lay = layout == FA_LAYOUT_BNHD ? bnhd(H, N, d) : bhnd(N, d);
-  return bwd_dispatch(q, k, v, out, out_grad, q_grad, k_grad, v_grad, l, m, (float*)workspace, B * H, N, d, d, lay,
-                      causal ? 1 : 0, variant, dtype, FA_BWD_STAGE_ALL, (hipStream_t)stream);
+  return validate_and_dispatch(heads(bwd_call(q, k, v, out, out_grad, q_grad, k_grad, v_grad, l, m, workspace, B, N, d, causal,
+                                              variant, dtype, FA_BWD_STAGE_ALL, stream), H, layout));
 }
 
 int fa_mi355x_fwd_masked(const void* q, const void* k, const void* v, float* out, float* l, float* m,
                          const float* key_mask, int B, int H, int N, int d, int layout, int causal, int variant,
                          int dtype, void* stream) {
-  g_err[0] = 0;
-  if (B <= 0 || H <= 0) return set_err(FA_ERR_BAD_ARG, "B and H must be positive");
-  if (int rc = check_common(B * H, N, d, variant, dtype)) return rc;
-  if (!q || !k || !v || !out || !l || (variant == FA_VARIANT_FA1 && !m))
-    return set_err(FA_ERR_BAD_ARG, "null pointer argument");
-  if (!d_supported(d)) return set_err(FA_ERR_UNSUPPORTED_D, "device path supports d in {32, 64, 128}");
-  if (layout != FA_LAYOUT_BHND && layout != FA_LAYOUT_BNHD) return set_err(FA_ERR_BAD_ARG, "unknown layout");
-  if ((long)N * H * d * 4 >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "one batch element must stay under 2 GiB");
-  fa::Layout lay = layout == FA_LAYOUT_BNHD ? bnhd(H, N, d) : bhnd(N, d);
-  lay.kmask = key_mask;   // NULL: same as fa_mi355x_fwd_layout
-  lay.mask_heads = H;
-  return fwd_dispatch(q, k, v, out, l, m, B * H, N, d, d, lay, causal ? 1 : 0, variant, dtype, (hipStream_t)stream);
+  Call c = heads(fwd_call(q, k, v, out, l, m, B, N, d, causal, variant, dtype, stream), H, layout);
+  c.kmask = key_mask;   // NULL: same as fa_mi355x_fwd_layout
+  c.mask_heads = H;
+  return validate_and_dispatch(c);
 }
 
 int fa_mi355x_bwd_masked(const void* q, const void* k, const void* v, const float* out, const void* out_grad,
                          float* q_grad, float* k_grad, float* v_grad, const float* l, const float* m,
                          const float* key_mask, void* workspace, int B, int H, int N, int d, int layout, int causal,
                          int variant, int dtype, void* stream) {
-  g_err[0] = 0;
-  if (B <= 0 || H <= 0) return set_err(FA_ERR_BAD_ARG, "B and H must be positive");
-  if (int rc = check_common(B * H, N, d, variant, dtype)) return rc;
-  if (!q || !k || !v || !out || !out_grad || !q_grad || !k_grad || !v_grad || !l || !workspace ||
-      (variant == FA_VARIANT_FA1 && !m))
-    return set_err(FA_ERR_BAD_ARG, "null pointer argument");
-  if (!d_supported(d)) return set_err(FA_ERR_UNSUPPORTED_D, "device path supports d in {32, 64, 128}");
-  if (layout != FA_LAYOUT_BHND && layout != FA_LAYOUT_BNHD) return set_err(FA_ERR_BAD_ARG, "unknown layout");
-  if ((long)N * H * d * 4 >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "one batch element must stay under 2 GiB");
-  fa::Layout lay = layout == FA_LAYOUT_BNHD ? bnhd(H, N, d) : bhnd(N, d);
-  lay.kmask = key_mask;
-  lay.mask_heads = H;
-  return bwd_dispatch(q, k, v, out, out_grad, q_grad, k_grad, v_grad, l, m, (float*)workspace, B * H, N, d, d, lay,
-                      causal ? 1 : 0, variant, dtype, FA_BWD_STAGE_ALL, (hipStream_t)stream);
+  Call c = heads(bwd_call(q, k, v, out, out_grad, q_grad, k_grad, v_grad, l, m, workspace, B, N, d, causal, variant, dtype,
+                          FA_BWD_STAGE_ALL, stream), H, layout);
+  c.kmask = key_mask;
+  c.mask_heads = H;
+  return validate_and_dispatch(c);
 }
-
-namespace {
-int set_dropout(fa::Layout& lay, float rate, float scale, unsigned seed) {
-  if (!(rate >= 0.0f && rate < 1.0f)) return set_err(FA_ERR_BAD_ARG, "dropout rate must be in [0, 1)");
-  lay.drop_thr = (uint32_t)((double)rate * 16777216.0);   // floor(rate * 2^24); 0 disables dropout
-  lay.drop_scale = scale;
-  lay.drop_seed = seed;
-  return FA_OK;
-}
-}  // namespace
 
 int fa_mi355x_fwd_dropout(const void* q, const void* k, const void* v, float* out, float* l, float* m,
                           const float* key_mask, float rate, float scale, unsigned seed, int B, int H, int N, int d,
                           int layout, int causal, int variant, int dtype, void* stream) {
-  g_err[0] = 0;
-  if (B <= 0 || H <= 0) return set_err(FA_ERR_BAD_ARG, "B and H must be positive");
-  if (int rc = check_common(B * H, N, d, variant, dtype)) return rc;
-  if (!q || !k || !v || !out || !l || (variant == FA_VARIANT_FA1 && !m))
-    return set_err(FA_ERR_BAD_ARG, "null pointer argument");
-  if (!d_supported(d)) return set_err(FA_ERR_UNSUPPORTED_D, "device path supports d in {32, 64, 128}");
-  if (layout != FA_LAYOUT_BHND && layout != FA_LAYOUT_BNHD) return set_err(FA_ERR_BAD_ARG, "unknown layout");
-  if ((long)N * H * d * 4 >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "one batch element must stay under 2 GiB");
-  fa::Layout lay = layout == FA_LAYOUT_BNHD ? bnhd(H, N, d) : bhnd(N, d);
-  lay.kmask = key_mask;
-  lay.mask_heads = H;
-  if (int rc = set_dropout(lay, rate, scale, seed)) return rc;
-  return fwd_dispatch(q, k, v, out, l, m, B * H, N, d, d, lay, causal ? 1 : 0, variant, dtype, (hipStream_t)stream);
+  Call c = heads(fwd_call(q, k, v, out, l, m, B, N, d, causal, variant, dtype, stream), H, layout);
+  c.kmask = key_mask;
+  c.mask_heads = H;
+  c.drop_rate = rate;
+  c.drop_scale = scale;
+  c.drop_seed = seed;
+  return validate_and_dispatch(c);
 }
 
 int fa_mi355x_bwd_dropout(const void* q, const void* k, const void* v, const float* out, const void* out_grad,
                           float* q_grad, float* k_grad, float* v_grad, const float* l, const float* m,
                           const float* key_mask, float rate, float scale, unsigned seed, void* workspace, int B, int H,
                           int N, int d, int layout, int causal, int variant, int dtype, void* stream) {
-  g_err[0] = 0;
-  if (B <= 0 || H <= 0) return set_err(FA_ERR_BAD_ARG, "B and H must be positive");
-  if (int rc = check_common(B * H, N, d, variant, dtype)) return rc;
-  if (!q || !k || !v || !out || !out_grad || !q_grad || !k_grad || !v_grad || !l || !workspace ||
-      (variant == FA_VARIANT_FA1 && !m))
-    return set_err(FA_ERR_BAD_ARG, "null pointer argument");
-  if (!d_supported(d)) return set_err(FA_ERR_UNSUPPORTED_D, "device path supports d in {32, 64, 128}");
-  if (layout != FA_LAYOUT_BHND && layout != FA_LAYOUT_BNHD) return set_err(FA_ERR_BAD_ARG, "unknown layout");
-  if ((long)N * H * d * 4 >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "one batch element must stay under 2 GiB");
-  fa::Layout lay = layout == FA_LAYOUT_BNHD ? bnhd(H, N, d) : bhnd(N, d);
-  lay.kmask = key_mask;
-  lay.mask_heads = H;
-  if (int rc = set_dropout(lay, rate, scale, seed)) return rc;
-  return bwd_dispatch(q, k, v, out, out_grad, q_grad, k_grad, v_grad, l, m, (float*)workspace, B * H, N, d, d, lay,
-                      causal ? 1 : 0, variant, dtype, FA_BWD_STAGE_ALL, (hipStream_t)stream);
+  Call c = heads(bwd_call(q, k, v, out, out_grad, q_grad, k_grad, v_grad, l, m, workspace, B, N, d, causal, variant, dtype,
+                          FA_BWD_STAGE_ALL, stream), H, layout);
+  c.kmask = key_mask;
+  c.mask_heads = H;
+  c.drop_rate = rate;
+  c.drop_scale = scale;
+  c.drop_seed = seed;
+  return validate_and_dispatch(c);
 }
 
 void fa_mi355x_host_pin_stats(unsigned long long* pinned_ranges, unsigned long long* pageable_ranges) {
@@ -1259,44 +1251,26 @@ int fa_mi355x_scale_guard(const void* q, const void* k, long rows, int row_elems
 int fa_mi355x_fwd_guarded(const void* q, const void* k, const void* v, float* out, float* l, float* m, int B, int H, int N, int d,
                           int layout, float softmax_scale, int causal, int variant, int dtype, const int* opts, int nopts,
                           void* guard, int produce_guard, void* stream) {
-  g_err[0] = 0;
-  Tun tun;
-  if (int rc = parse_opts(opts, nopts, tun)) return rc;
-  if (B <= 0 || H <= 0) return set_err(FA_ERR_BAD_ARG, "B and H must be positive");
-  if (int rc = check_common(B * H, N, d, variant, dtype)) return rc;
-  if (!q || !k || !v || !out || !l || (variant == FA_VARIANT_FA1 && !m)) return set_err(FA_ERR_BAD_ARG, "null pointer argument");
-  if (produce_guard && !guard) return set_err(FA_ERR_BAD_ARG, "produce_guard needs a guard buffer");
-  if (!d_supported(d)) return set_err(FA_ERR_UNSUPPORTED_D, "device path supports d in {32, 64, 128}");
-  if (layout != FA_LAYOUT_BHND && layout != FA_LAYOUT_BNHD) return set_err(FA_ERR_BAD_ARG, "unknown layout");
-  if (softmax_scale != 0.f && (!(softmax_scale > 0.f) || !std::isfinite(softmax_scale)))
-    return set_err(FA_ERR_BAD_ARG, "softmax_scale must be positive and finite (0: sqrt(1/d))");
-  if ((long)N * H * d * 4 >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "one batch element must stay under 2 GiB");
-  const fa::Layout lay = layout == FA_LAYOUT_BNHD ? bnhd(H, N, d) : bhnd(N, d);
-  return fwd_dispatch(q, k, v, out, l, m, B * H, N, d, d, lay, causal ? 1 : 0, variant, dtype, (hipStream_t)stream, tun,
-                      softmax_scale, (const float*)guard, produce_guard ? 1 : 0);
+  Call c = heads(fwd_call(q, k, v, out, l, m, B, N, d, causal, variant, dtype, stream), H, layout);
+  c.scale = softmax_scale;
+  c.opts = opts;
+  c.nopts = nopts;
+  c.guard = (const float*)guard;
+  c.produce = produce_guard ? 1 : 0;
+  return validate_and_dispatch(c);
 }
 
 int fa_mi355x_bwd_guarded(const void* q, const void* k, const void* v, const float* out, const void* out_grad, float* q_grad,
                           float* k_grad, float* v_grad, const float* l, const float* m, void* workspace, int B, int H, int N, int d,
                           int layout, float softmax_scale, int causal, int variant, int dtype, int stages, const int* opts,
                           int nopts, const void* guard, void* stream) {
-  g_err[0] = 0;
-  Tun tun;
-  if (int rc = parse_opts(opts, nopts, tun)) return rc;
-  if (stages <= 0 || stages > FA_BWD_STAGE_ALL) return set_err(FA_ERR_BAD_ARG, "bad stages mask");
-  if (B <= 0 || H <= 0) return set_err(FA_ERR_BAD_ARG, "B and H must be positive");
-  if (int rc = check_common(B * H, N, d, variant, dtype)) return rc;
-  if (!q || !k || !v || !out || !out_grad || !q_grad || !k_grad || !v_grad || !l || !workspace ||
-      (variant == FA_VARIANT_FA1 && !m))
-    return set_err(FA_ERR_BAD_ARG, "null pointer argument");
-  if (!d_supported(d)) return set_err(FA_ERR_UNSUPPORTED_D, "device path supports d in {32, 64, 128}");
-  if (layout != FA_LAYOUT_BHND && layout != FA_LAYOUT_BNHD) return set_err(FA_ERR_BAD_ARG, "unknown layout");
-  if (softmax_scale != 0.f && (!(softmax_scale > 0.f) || !std::isfinite(softmax_scale)))
-    return set_err(FA_ERR_BAD_ARG, "softmax_scale must be positive and finite (0: sqrt(1/d))");
-  if ((long)N * H * d * 4 >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "one batch element must stay under 2 GiB");
-  const fa::Layout lay = layout == FA_LAYOUT_BNHD ? bnhd(H, N, d) : bhnd(N, d);
-  return bwd_dispatch(q, k, v, out, out_grad, q_grad, k_grad, v_grad, l, m, (float*)workspace, B * H, N, d, d, lay,
-                      causal ? 1 : 0, variant, dtype, stages, (hipStream_t)stream, tun, softmax_scale, (const float*)guard);
+  Call c = heads(bwd_call(q, k, v, out, out_grad, q_grad, k_grad, v_grad, l, m, workspace, B, N, d, causal, variant, dtype, stages,
+                          stream), H, layout);
+  c.scale = softmax_scale;
+  c.opts = opts;
+  c.nopts = nopts;
+  c.guard = (const float*)guard;
+  return validate_and_dispatch(c);
 }
 
 size_t fa_mi355x_bwd_workspace_bytes(int batch, int N, int /*d*/) {
@@ -1322,19 +1296,14 @@ int fa_mi355x_bwd(const void* q, const void* k, const void* v, const float* out,
                               variant, dtype, FA_BWD_STAGE_ALL, stream);
 }
 
+
 int fa_mi355x_bwd_stages(const void* q, const void* k, const void* v, const float* out, const void* out_grad,
                          float* q_grad, float* k_grad, float* v_grad, const float* l, const float* m, void* workspace,
                          int batch, int N, int d, int causal, int variant, int dtype, int stages, void* stream) {
-  g_err[0] = 0;
-  if (stages <= 0 || stages > FA_BWD_STAGE_ALL) return set_err(FA_ERR_BAD_ARG, "bad stages mask");
-  if (int rc = check_common(batch, N, d, variant, dtype)) return rc;
-  if (!q || !k || !v || !out || !out_grad || !q_grad || !k_grad || !v_grad || !l || !workspace ||
-      (variant == FA_VARIANT_FA1 && !m))
-    return set_err(FA_ERR_BAD_ARG, "null pointer argument");
-  if (!d_supported(d)) return set_err(FA_ERR_UNSUPPORTED_D, "device path supports d in {32, 64, 128}");
-  return bwd_dispatch(q, k, v, out, out_grad, q_grad, k_grad, v_grad, l, m, (float*)workspace, batch, N, d, d,
-                      bhnd(N, d), causal ? 1 : 0, variant, dtype, stages, (hipStream_t)stream);
+  return validate_and_dispatch(bwd_call(q, k, v, out, out_grad, q_grad, k_grad, v_grad, l, m, workspace, batch, N, d, causal,
+                                        variant, dtype, stages, stream));
 }
+
 
 void fa_mi355x_launch_fw_host(int variant, float* q, float* k, float* v, float* out, float* l, float* m, int batch,
                               int N, int d, bool causal_mask, void* stream) {
@@ -1374,9 +1343,9 @@ void fa_mi355x_launch_fw_host(int variant, float* q, float* k, float* v, float* 
     h2d_rows(dv_ + r0 * dp, v + r0 * d, nr, d, dp, g_pipe.up);
     FA_HOST_TRY(hipEventRecord(g_pipe.event(2 * c), g_pipe.up));
     FA_HOST_TRY(hipStreamWaitEvent(st, g_pipe.event(2 * c), 0));
-    if (fwd_dispatch(dq_ + r0 * dp, dk_ + r0 * dp, dv_ + r0 * dp, do_ + r0 * dp, dl_ + r0, dm_ + r0, nb, N, d, dp, bhnd(N, dp),
-                     causal_mask ? 1 : 0, variant, FA_DTYPE_F32, st))
-      die(g_err, hipSuccess);
+    Call call = host_call(nb, N, d, dp, causal_mask, variant, st);
+    call.q = dq_ + r0 * dp; call.k = dk_ + r0 * dp; call.v = dv_ + r0 * dp; call.out = do_ + r0 * dp; call.l = dl_ + r0; call.m = dm_ + r0;
+    if (fwd_dispatch(call)) die(g_err, hipSuccess);
     FA_HOST_TRY(hipEventRecord(g_pipe.event(2 * c + 1), st));
     FA_HOST_TRY(hipStreamWaitEvent(g_pipe.down, g_pipe.event(2 * c + 1), 0));
     d2h_rows(out + r0 * d, do_ + r0 * dp, nr, d, dp, g_pipe.down);
@@ -1443,10 +1412,11 @@ void fa_mi355x_launch_bw_host(int variant, float* q, float* k, float* v, float* 
     FA_HOST_TRY(hipEventRecord(g_pipe.event(2 * c), g_pipe.up));
     FA_HOST_TRY(hipStreamWaitEvent(st, g_pipe.event(2 * c), 0));
     // the chunk's row-constant vectors sit at ws + WS_VECS * r0 (the kernels take ws, ws + rows, ws + 2 * rows of THEIR launch)
-    if (bwd_dispatch(bq + r0 * dp, bk + r0 * dp, bv + r0 * dp, bo + r0 * dp, bdo + r0 * dp, bdq + r0 * dp, bdk + r0 * dp,
-                     bdv + r0 * dp, bl + r0, bm + r0, ws + WS_VECS * r0, nb, N, d, dp, bhnd(N, dp), causal_mask ? 1 : 0, variant,
-                     FA_DTYPE_F32, FA_BWD_STAGE_ALL, st))
-      die(g_err, hipSuccess);
+    Call call = host_call(nb, N, d, dp, causal_mask, variant, st);
+    call.q = bq + r0 * dp; call.k = bk + r0 * dp; call.v = bv + r0 * dp; call.out = bo + r0 * dp; call.dout = bdo + r0 * dp;
+    call.dq = bdq + r0 * dp; call.dk = bdk + r0 * dp; call.dv = bdv + r0 * dp; call.l = bl + r0; call.m = bm + r0; call.ws = ws + WS_VECS * r0;
+    call.stages = FA_BWD_STAGE_ALL;
+    if (bwd_dispatch(call)) die(g_err, hipSuccess);
     FA_HOST_TRY(hipEventRecord(g_pipe.event(2 * c + 1), st));
     FA_HOST_TRY(hipStreamWaitEvent(g_pipe.down, g_pipe.event(2 * c + 1), 0));
     d2h_rows(q_grad + r0 * d, bdq + r0 * dp, nr, d, dp, g_pipe.down);

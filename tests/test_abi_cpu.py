@@ -223,3 +223,168 @@ def test_deterministic_switch_keeps_the_two_kernel_fp32_backward(built):
         out[val] = r.stdout.strip()
     assert out["0"] == "['bwd_prep_kernel', 'bwd_onepass_f32_kernel'] ['bwd_prep_kernel', 'bwd_onepass_f32_kernel']", out["0"]
     assert out["1"] == "['bwd_dq_kernel', 'bwd_dkdv_kernel'] ['bwd_prep_kernel', 'bwd_onepass_f32_kernel']", out["1"]
+
+
+# ---- validation of the device entry points, pinned argument by argument ------------------------------------------------------------
+# Every call below is rejected before any HIP call (fake non-null pointers are never dereferenced).  No valid call is made here: on a
+# GPU machine it would launch kernels on those pointers.
+_P6 = ["q", "k", "v", "out", "l", "m"]
+_P11 = ["q", "k", "v", "out", "dout", "dq", "dk", "dv", "l", "m", "ws"]
+_P10 = _P11[:-1]
+_ENTRY_ARGS = {
+    "fwd": _P6 + ["batch", "N", "d", "causal", "variant", "dtype", "stream"],
+    "fwd_ex": _P6 + ["batch", "N", "d", "causal", "variant", "dtype", "opts", "nopts", "stream"],
+    "fwd_scaled": _P6 + ["B", "H", "N", "d", "layout", "scale", "causal", "variant", "dtype", "stream"],
+    "fwd_padded": _P6 + ["batch", "N", "d", "dp", "causal", "variant", "dtype", "stream"],
+    "fwd_layout": _P6 + ["B", "H", "N", "d", "layout", "causal", "variant", "dtype", "stream"],
+    "fwd_masked": _P6 + ["mask", "B", "H", "N", "d", "layout", "causal", "variant", "dtype", "stream"],
+    "fwd_dropout": _P6 + ["mask", "rate", "dscale", "seed", "B", "H", "N", "d", "layout", "causal", "variant", "dtype", "stream"],
+    "fwd_guarded": _P6 + ["B", "H", "N", "d", "layout", "scale", "causal", "variant", "dtype", "opts", "nopts", "guard", "produce",
+                          "stream"],
+    "bwd": _P11 + ["batch", "N", "d", "causal", "variant", "dtype", "stream"],
+    "bwd_stages": _P11 + ["batch", "N", "d", "causal", "variant", "dtype", "stages", "stream"],
+    "bwd_ex": _P11 + ["batch", "N", "d", "causal", "variant", "dtype", "stages", "opts", "nopts", "stream"],
+    "bwd_scaled": _P11 + ["B", "H", "N", "d", "layout", "scale", "causal", "variant", "dtype", "stream"],
+    "bwd_padded": _P11 + ["batch", "N", "d", "dp", "causal", "variant", "dtype", "stream"],
+    "bwd_layout": _P11 + ["B", "H", "N", "d", "layout", "causal", "variant", "dtype", "stream"],
+    "bwd_masked": _P10 + ["mask", "ws", "B", "H", "N", "d", "layout", "causal", "variant", "dtype", "stream"],
+    "bwd_dropout": _P10 + ["mask", "rate", "dscale", "seed", "ws", "B", "H", "N", "d", "layout", "causal", "variant", "dtype",
+                           "stream"],
+    "bwd_guarded": _P11 + ["B", "H", "N", "d", "layout", "scale", "causal", "variant", "dtype", "stages", "opts", "nopts", "guard",
+                           "stream"],
+    "plan": ["batch", "N", "d", "causal", "variant", "dtype", "stages", "opts", "nopts", "pout", "pn"],
+}
+_VALID = dict(batch=1, B=1, H=2, N=16, d=64, dp=64, layout=0, scale=0.125, causal=0, variant=2, dtype=1, stages=7, opts=None,
+              nopts=0, mask=None, rate=0.0, dscale=1.0, seed=0, produce=0, pn=1024)
+_FLOAT_ARGS = ("scale", "rate", "dscale")
+_D_MSG = "device path supports d in {32, 64, 128}"
+_PADDED_MSG = "padded row length dp must be 32, 64 or 128 and >= d"
+_NULL = (1, "null pointer argument")
+_BATCH = (1, "batch, N and d must be positive")
+_BH = (1, "B and H must be positive")
+_OPTS = (1, "option value not supported")
+_STAGES = (1, "bad stages mask")
+_LAYOUT = (1, "unknown layout")
+_GIB = (1, "one batch element must stay under 2 GiB")
+_SCALE = (1, "softmax_scale must be positive and finite")
+
+
+def _single_bad_cases(entry):
+    """(overrides, rc, message substring) for each single bad argument the entry point takes."""
+    args = _ENTRY_ARGS[entry]
+    padded = "dp" in args
+    cases = []
+    for p in args:
+        if p in _P11 and not (entry == "fwd_guarded" and p == "guard"):
+            cases.append(({p: None, "variant": 1} if p == "m" else {p: None}, *_NULL))
+    if "opts" in args:
+        cases += [({"opts": (93, 0, 0), "nopts": 3}, *_OPTS), ({"opts": (0,) * 8 + (4, 0), "nopts": 10}, *_OPTS),
+                  ({"opts": None, "nopts": 9}, 1, "bad options array"), ({"opts": (0,) * 11, "nopts": 11}, 1, "bad options array"),
+                  ({"opts": (0,), "nopts": -1}, 1, "bad options array")]
+    if "stages" in args:
+        cases += [({"stages": 8}, *_STAGES), ({"stages": -1}, *_STAGES)]
+        if entry != "plan":
+            cases.append(({"stages": 0}, *_STAGES))
+    if "B" in args:
+        cases += [({"B": 0}, *_BH), ({"H": 0}, *_BH), ({"B": -3}, *_BH), ({"layout": 5}, *_LAYOUT), ({"layout": -1}, *_LAYOUT),
+                  ({"H": 64, "N": 65536, "d": 128}, *_GIB)]
+    else:
+        cases.append(({"batch": 0}, *_BATCH))
+    cases += [({"N": 0}, *_BATCH), ({"N": 1 << 22}, 1, "N too large"), ({"d": 0}, *_BATCH), ({"d": -64}, *_BATCH),
+              ({"variant": 7}, 1, "unknown variant"), ({"variant": 0}, 1, "unknown variant"), ({"dtype": 9}, 1, "unknown dtype")]
+    if padded:
+        cases += [({"dp": 48}, 2, _PADDED_MSG), ({"d": 128, "dp": 64}, 2, _PADDED_MSG), ({"d": 48, "dp": 48}, 2, _PADDED_MSG),
+                  ({"dp": 0}, 2, _PADDED_MSG)]
+    else:
+        cases += [({"d": 48}, 2, _D_MSG), ({"d": 256}, 2, _D_MSG), ({"d": 34}, 2, _D_MSG)]
+    if entry in ("fwd_scaled", "bwd_scaled"):
+        cases += [({"scale": 0.0}, *_SCALE), ({"scale": -1.0}, *_SCALE), ({"scale": float("nan")}, *_SCALE),
+                  ({"scale": float("inf")}, *_SCALE)]
+    if entry in ("fwd_guarded", "bwd_guarded"):
+        cases += [({"scale": -1.0}, 1, "(0: sqrt(1/d))"), ({"scale": float("nan")}, 1, "(0: sqrt(1/d))"),
+                  ({"scale": float("inf")}, 1, "(0: sqrt(1/d))")]
+    if entry == "fwd_guarded":
+        cases.append(({"produce": 1, "guard": None}, 1, "produce_guard needs a guard buffer"))
+    if "rate" in args:
+        cases += [({"rate": 1.0}, 1, "dropout rate must be in [0, 1)"), ({"rate": -0.25}, 1, "dropout rate must be in [0, 1)"),
+                  ({"rate": float("nan")}, 1, "dropout rate must be in [0, 1)")]
+    if entry == "plan":
+        cases += [({"pout": None}, 1, "null output buffer"), ({"pn": 0}, 1, "null output buffer"),
+                  ({"pn": 4}, 1, "plan buffer too small")]
+    return cases
+
+
+def _multi_bad_cases(entry):
+    """Several bad arguments at once: the first failing check of the entry point's order decides."""
+    args = _ENTRY_ARGS[entry]
+    ptr = "v"
+    cases = [({"variant": 7, ptr: None}, 1, "unknown variant"), ({"dtype": 9, "d": 48}, 1, "unknown dtype"),
+             ({ptr: None, "d": 48}, *_NULL)] if entry != "plan" else [({"variant": 7, "d": 48}, 1, "unknown variant")]
+    if "opts" in args:
+        cases += [({"opts": (93,), "nopts": 1, "N": 0}, *_OPTS)]
+        cases += [({"opts": (93,), "nopts": 1, "stages": 0 if entry != "plan" else -1}, *_OPTS)] if "stages" in args else []
+    if "stages" in args:
+        cases += [({"stages": 9, "N": 0}, *_STAGES)]
+        if "B" in args:
+            cases += [({"stages": 9, "B": 0}, *_STAGES)]
+    if "B" in args:
+        cases += [({"B": 0, "N": 0}, *_BH), ({"H": 0, ptr: None}, *_BH), ({"layout": 5, "d": 48}, 2, _D_MSG),
+                  ({"layout": 5, "H": 64, "N": 65536, "d": 128}, *_LAYOUT), ({ptr: None, "layout": 5}, *_NULL)]
+    if "scale" in args:
+        cases += [({"scale": -1.0, "layout": 5}, *_LAYOUT), ({"scale": -1.0, "H": 64, "N": 65536, "d": 128}, *_SCALE)]
+    if "rate" in args:
+        cases += [({"rate": 2.0, "H": 64, "N": 65536, "d": 128}, *_GIB), ({"rate": 2.0, "layout": 5}, *_LAYOUT),
+                  ({"rate": 2.0, ptr: None}, *_NULL)]
+    if entry == "fwd_guarded":
+        cases += [({"produce": 1, "guard": None, "d": 48}, 1, "produce_guard"), ({"produce": 1, "guard": None, ptr: None}, *_NULL),
+                  ({"produce": 1, "guard": None, "layout": 5}, 1, "produce_guard")]
+    if "dp" in args:
+        cases += [({"dp": 48, ptr: None}, *_NULL), ({"dp": 48, "N": 0}, *_BATCH)]
+    if entry == "plan":
+        cases += [({"pout": None, "d": 48}, 2, _D_MSG), ({"pout": None, "stages": 8}, *_STAGES)]
+    return cases
+
+
+def _call_entry(lib, entry, overrides):
+    """Calls fa_mi355x_<entry> with the valid defaults, fake non-null pointers and the overrides; returns (rc, last error)."""
+    args = dict(_VALID, **overrides)
+    keep = []
+    vals = []
+    for name in _ENTRY_ARGS[entry]:
+        if name == "stream":
+            vals.append(ctypes.c_void_p(0))
+        elif name in _P11 or name == "guard":
+            vals.append(ctypes.c_void_p(16) if args.get(name, 16) is not None else ctypes.c_void_p(0))
+        elif name == "mask":
+            vals.append(ctypes.c_void_p(0) if args["mask"] is None else ctypes.c_void_p(16))
+        elif name == "opts":
+            arr = None if args["opts"] is None else (ctypes.c_int * max(1, len(args["opts"])))(*args["opts"])
+            keep.append(arr)
+            vals.append(arr)
+        elif name == "pout":
+            buf = ctypes.create_string_buffer(1024) if args.get("pout", 1) is not None else None
+            keep.append(buf)
+            vals.append(buf)
+        elif name == "pn":
+            vals.append(ctypes.c_size_t(args["pn"]))
+        elif name in _FLOAT_ARGS:
+            vals.append(ctypes.c_float(args[name]))
+        elif name == "seed":
+            vals.append(ctypes.c_uint(args[name]))
+        else:
+            vals.append(ctypes.c_int(args[name]))
+    rc = getattr(lib, "fa_mi355x_" + entry)(*vals)   # (the values carry their own ctypes types)
+    return rc, lib.fa_mi355x_last_error().decode()
+
+
+@pytest.mark.parametrize("entry", sorted(_ENTRY_ARGS))
+def test_entry_point_validation_table(built, entry):
+    """Each device entry point answers every single bad argument, and combinations of them, with the return code and message of the
+    first failing check in its order: options, stages, B/H, batch / N / d / variant / dtype / N size, null pointers, produce_guard
+    without a guard, d (or dp), layout, softmax scale, one batch element under 2 GiB, dropout rate (fa_mi355x_plan: its output
+    buffer last)."""
+    lib = ctypes.CDLL(built.lib_path(built.CORE_NAME))   # a handle of its own: core()'s argtypes stay as they are
+    lib.fa_mi355x_last_error.restype = ctypes.c_char_p
+    for overrides, rc, msg in _single_bad_cases(entry) + _multi_bad_cases(entry):
+        got_rc, got_msg = _call_entry(lib, entry, overrides)
+        assert (got_rc, msg in got_msg) == (rc, True), (entry, overrides, got_rc, got_msg)
