@@ -2,7 +2,7 @@
 # Builds the MI355X (gfx950) FlashAttention libraries with hipcc.  Name kept from the reference
 # (compile_cuda.sh / Makefile:28-50 there built the CUDA .so files with nvcc); the output directory
 # holds the same six library names the reference's cuda_kernel_ops.py:30-35 opens, plus the core
-# library they forward to.
+# library they forward to and the KV-cache decode library.
 #   OUT_DIR=minitorch/cuda_kernels ./compile_cuda.sh     # drop-in location inside a minitorch checkout
 set -euo pipefail
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
@@ -20,6 +20,15 @@ if stale "$CORE"; then
   "$HIPCC" "${FLAGS[@]}" "$SRC/fa_api.hip" -o "$CORE"
 else
   echo "[compile_cuda.sh] $CORE is up to date"
+fi
+
+# KV-cache decode (include/flash_attn_mi355x_decode.h): its own library, so the training library's code object stays as it is
+DECODE="$OUT_DIR/libflash_attn_mi355x_decode.so"
+if [ ! -f "$DECODE" ] || [ -n "$(find "$SRC" "$HERE/include" -newer "$DECODE" \( -name '*.h' -o -name '*.hip' \) -print -quit)" ]; then
+  echo "[compile_cuda.sh] hipcc --offload-arch=$ARCH  fa_decode.hip -> $DECODE"
+  "$HIPCC" "${FLAGS[@]}" "$SRC/fa_decode.hip" -o "$DECODE"
+else
+  echo "[compile_cuda.sh] $DECODE is up to date"
 fi
 
 shim() {  # name variant FW|BW

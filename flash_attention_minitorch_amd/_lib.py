@@ -155,3 +155,29 @@ def check(status: int) -> None:
     if status != FA_OK:
         msg = core().fa_mi355x_last_error().decode()
         raise FlashAttnLibraryError(f"flash_attn_mi355x error {status}: {msg}")
+
+
+DECODE_NAME = "libflash_attn_mi355x_decode.so"
+
+
+def decode() -> ctypes.CDLL:
+    """libflash_attn_mi355x_decode.so (include/flash_attn_mi355x_decode.h) with argtypes set."""
+    h = load(DECODE_NAME)
+    if getattr(h, "_fa_typed", False):
+        return h
+    h.fa_mi355x_decode_workspace_bytes.argtypes = [_i] * 5
+    h.fa_mi355x_decode_workspace_bytes.restype = ctypes.c_size_t
+    h.fa_mi355x_decode_splits.argtypes = [_i] * 6
+    h.fa_mi355x_decode_splits.restype = _i
+    h.fa_mi355x_fwd_decode.argtypes = [_vp] * 7 + [_i] * 6 + [ctypes.c_float, _i, _i, _vp]
+    h.fa_mi355x_fwd_decode.restype = _i
+    h.fa_mi355x_decode_last_error.argtypes = []
+    h.fa_mi355x_decode_last_error.restype = ctypes.c_char_p
+    h._fa_typed = True
+    return h
+
+
+def decode_check(status: int) -> None:
+    if status != FA_OK:
+        msg = decode().fa_mi355x_decode_last_error().decode()
+        raise FlashAttnLibraryError(f"flash_attn_mi355x_decode error {status}: {msg}")

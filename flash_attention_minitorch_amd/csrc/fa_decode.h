@@ -1,0 +1,272 @@
+// KV-cache decode attention for MI355X (gfx950): Nq = 1..128 new queries against a cache of up to Ncap keys per (batch, head), with
+// per-batch valid lengths on the device.  Declared in include/flash_attn_mi355x_decode.h, dispatched by fa_decode.hip; the training
+// kernels (fa_kernels.h) are not part of this unit.
+//
+// Split kernel: a workgroup = one (batch*head, key chunk, 32-query block).  Its four waves stage 128-key super tiles of K and V through
+// LDS together (register staging: the next super tile's loads are in flight under this one's products) and each wave takes 32 keys of
+// the super tile: S^T = K Q^T with the QUERY on the lane, the online softmax of fwd_splitk_f32_kernel, O^T += V^T P^T from registers.
+// At the end the four partial (O, m, l) meet in LDS and wave 0 combines them in wave order.  The result is either final (one split:
+// out and lse written directly) or one fp32 partial (unnormalised O, m, l) per row in the workspace.
+// Combine kernel: one workgroup per (batch*head, row) reduces the partials of its row in a fixed order (no atomics: bitwise
+// repeatable).
+//
+// Bounds: every K / V / Q load goes through a buffer resource of its (batch, head) sized to the valid rows (len_b clamped to [0, Ncap]
+// for the cache, Nq for q), with the row offset in the per-lane voffset, so rows at or past len_b read as zero in hardware: whatever
+// they hold (NaN included) reaches neither a score nor the P.V product, and no load goes past row Ncap - 1.
+#pragma once
+#include "fa_common.h"
+
+namespace fa {
+
+constexpr int DEC_ROWS = 128;   // keys per super tile: 32 per wave
+
+struct DecodeArgs {
+  const void* q;
+  const void* k;
+  const void* v;
+  float* out;          // final output (nsplit == 1) in q's layout
+  float* lse;          // [BH][Nq], may be null
+  float* part_o;       // [BH][nsplit][Nq][D] unnormalised partial O (nsplit > 1)
+  float* part_ml;      // [BH][nsplit][Nq][2] partial (m, l), m in raw score units
+  const int* seqlens;  // [B] or null (= Ncap)
+  int H, Nq, Ncap, nsplit, chunk, nqb, items;
+  int q_ld, kv_ld;     // elements between consecutive rows of one head (D or H*D)
+  long q_bstride, q_hstride, kv_bstride, kv_hstride;
+  int causal;
+  float tau;
+};
+
+FA_DEV int clamp_len(const DecodeArgs& a, int b) {
+  const int len = a.seqlens ? a.seqlens[b] : a.Ncap;
+  return min(max(len, 0), a.Ncap);
+}
+
+// Row n of the loader's matrix at byte voffset n*ldb: TileStager's (row, chunk) map and LDS image, with the tile's row offset added to
+// the voffset instead of the scalar offset, so that the resource's range check covers it.
+template <typename S> FA_DEV void load_rows(S& st, rsrc_t rs, int row0) {
+#pragma unroll
+  for (int i = 0; i < S::PER; ++i) {
+    u32x4 v = {0u, 0u, 0u, 0u};
+    if (S::NCH % 256 == 0 || st.live)
+      v = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, st.voff + (row0 + i * S::RSTEP) * st.ldb, 0, 0));
+    st.regs[i] = v;
+  }
+}
+
+template <typename T, int D>
+__global__ void __launch_bounds__(256) decode_split_kernel(DecodeArgs a) {
+  using A = Atom<T>;
+  typedef typename A::frag frag;
+  constexpr int KC = D / 16, DT = D / 32;
+  constexpr int TB = A::template tile_bytes<D>(DEC_ROWS);
+  constexpr int PW = (16 * DT + 2) * 64 * 4;   // one wave's partial: [lane][16*DT accumulator registers, m, l]
+  static_assert(3 * PW <= 2 * TB, "the partials of waves 1-3 must fit the tile images");
+  __shared__ __attribute__((aligned(16))) char smem_raw[2 * TB];
+  lds_char* tk = (lds_char*)smem_raw;
+  lds_char* tv = tk + TB;
+
+  // workgroup -> (item = bh * nsplit + split, query block): the query blocks of one item are 8 workgroup ids apart, so they share an
+  // XCD's L2 under round-robin dispatch and the chunk is fetched from HBM once (speed only)
+  const int id = blockIdx.x, slot = id >> 3;
+  const int qb = slot % a.nqb, item = (slot / a.nqb) * 8 + (id & 7);
+  if (item >= a.items) return;
+  const int bh = item / a.nsplit, split = item - bh * a.nsplit;
+  const int b = bh / a.H, hd = bh - b * a.H;
+  const int len = __builtin_amdgcn_readfirstlane(clamp_len(a, b));
+  const int c0 = split * a.chunk, c1 = min(c0 + a.chunk, len);
+
+  const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int q0 = qb * 32, qrow = q0 + r;
+  const float c = a.tau * LOG2E;
+
+  f32x16 acc_o[DT];
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt) acc_o[dt] = zero16();
+  float m_run = -INFINITY, l_run = 0.f;
+
+  if (c0 < c1) {   // (a chunk wholly past len_b loads nothing and leaves the empty partial m = -inf, l = 0)
+    const T* qh = reinterpret_cast<const T*>(a.q) + (size_t)b * a.q_bstride + (size_t)hd * a.q_hstride;
+    const size_t kvoff = (size_t)b * a.kv_bstride + (size_t)hd * a.kv_hstride;
+    const uint32_t esz = sizeof(T);
+    const rsrc_t qrs = make_rsrc(qh, ((uint32_t)(a.Nq - 1) * a.q_ld + D) * esz);
+    const uint32_t kv_bytes = ((uint32_t)(len - 1) * a.kv_ld + D) * esz;
+    const rsrc_t krs = make_rsrc(reinterpret_cast<const T*>(a.k) + kvoff, kv_bytes);
+    const rsrc_t vrs = make_rsrc(reinterpret_cast<const T*>(a.v) + kvoff, kv_bytes);
+
+    frag qf[KC];
+#pragma unroll
+    for (int kc = 0; kc < KC; ++kc) qf[kc] = load_frag_buf<T>(qrs, (qrow * a.q_ld + 16 * kc + 8 * h) * (int)esz);
+
+    const LaneAddr ra = A::template row_addr<D>(lane);
+    const LaneAddr ta = A::template tr_addr<D>(lane);
+    TileStager<T, D, DEC_ROWS, 256> sk, sv;
+    sk.init(tid, a.kv_ld);
+    sv.init(tid, a.kv_ld);
+    // causal: query i sits at position len - Nq + i and sees keys j <= len - Nq + i (bottom-right aligned)
+    const int qpos0 = len - a.Nq + q0;
+    load_rows(sk, krs, c0);
+    load_rows(sv, vrs, c0);
+    for (int t0 = c0; t0 < c1; t0 += DEC_ROWS) {
+      __syncthreads();   // (the previous super tile's reads are done)
+      sk.store(tk);
+      sv.store(tv);
+      if (t0 + DEC_ROWS < c1) {
+        load_rows(sk, krs, t0 + DEC_ROWS);
+        load_rows(sv, vrs, t0 + DEC_ROWS);
+      }
+      __syncthreads();
+      const int kbase = t0 + 32 * w;
+      if (kbase >= c1 || (a.causal && kbase > qpos0 + 31)) continue;   // wave-uniform: no admissible key in the wave's 32
+      f32x16 s = zero16();
+#pragma unroll
+      for (int kc = 0; kc < KC; ++kc) A::mma(s, A::template row_frag<D>(tk, ra, 32 * w, kc), qf[kc]);
+      if (kbase + 32 > c1 || (a.causal && kbase + 31 > qpos0)) {   // wave-uniform
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const int key = kbase + acc_row(i, h);
+          if (key >= c1 || (a.causal && key > qpos0 + r)) s[i] = -INFINITY;
+        }
+      }
+      float mx = s[0];
+#pragma unroll
+      for (int i = 1; i < 16; ++i) mx = fmaxf(mx, s[i]);
+      const float m_new = fmaxf(m_run, xhalf_max(mx));
+      const float nm = (m_new == -INFINITY) ? 0.f : -m_new * c;   // (every key so far masked: any finite reference, P = 0)
+      const float alpha = __builtin_amdgcn_exp2f(__builtin_fmaf(m_run, c, nm));
+      float rs = 0.f;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        s[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[i], c, nm));
+        rs += s[i];
+      }
+      if (__any(alpha != 1.0f)) {
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+          for (int i = 0; i < 16; ++i) acc_o[dt][i] *= alpha;
+      }
+      l_run = l_run * alpha + rs;
+      m_run = m_new;
+      // bf16: P goes in at 16 significant bits (pack + pack_lo): a row with few admissible keys holds P of order 1, whose 2^-9
+      // rounding would not average out (the decode step's first tokens, causal rows near position 0)
+#pragma unroll
+      for (int s2 = 0; s2 < 2; ++s2) {
+        const frag p_hi = A::pack(s, s2);
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt) {
+          const frag vt = A::template tr_frag<D>(tv, ta, 32 * w + 16 * s2, dt);
+          A::mma(acc_o[dt], vt, p_hi);
+          if constexpr (A::SPLITS) A::mma(acc_o[dt], vt, A::pack_lo(s, s2, p_hi));
+        }
+      }
+    }
+  }
+  const float l_w = xhalf_sum(l_run);
+
+  // the partials of waves 1-3 meet in LDS (over the tile images), wave 0 adds them in wave order
+  __syncthreads();
+  if (w != 0) {
+    lds_char* mine = tk + (w - 1) * PW + lane * (16 * DT + 2) * 4;
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) *FA_LDS(float, mine + (16 * dt + i) * 4) = acc_o[dt][i];
+    *FA_LDS(float, mine + 16 * DT * 4) = m_run;
+    *FA_LDS(float, mine + (16 * DT + 1) * 4) = l_w;
+  }
+  __syncthreads();
+  if (w != 0) return;
+  float m_all = m_run;
+#pragma unroll
+  for (int u = 0; u < 3; ++u) m_all = fmaxf(m_all, *FA_LDS(float, tk + u * PW + (lane * (16 * DT + 2) + 16 * DT) * 4));
+  float wgt = (m_run == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f((m_run - m_all) * c);
+  float l_tot = l_w * wgt;
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc_o[dt][i] *= wgt;
+#pragma unroll
+  for (int u = 0; u < 3; ++u) {
+    lds_char* pu = tk + u * PW + lane * (16 * DT + 2) * 4;
+    const float mu = *FA_LDS(float, pu + 16 * DT * 4);
+    wgt = (mu == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f((mu - m_all) * c);
+    l_tot += *FA_LDS(float, pu + (16 * DT + 1) * 4) * wgt;
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) acc_o[dt][i] += *FA_LDS(float, pu + (16 * dt + i) * 4) * wgt;
+  }
+  if (qrow >= a.Nq) return;
+  const size_t ri = (size_t)bh * a.Nq + qrow;
+  if (a.nsplit == 1) {   // final: out = O / l, lse = m * tau + ln l; a row without an admissible key: out = 0, lse = -inf
+    const float inv = (l_tot > 0.f) ? 1.0f / l_tot : 0.f;
+    float* orow = a.out + (size_t)b * a.q_bstride + (size_t)hd * a.q_hstride + (size_t)qrow * a.q_ld;
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        f32x4 val = {acc_o[dt][4 * g] * inv, acc_o[dt][4 * g + 1] * inv, acc_o[dt][4 * g + 2] * inv, acc_o[dt][4 * g + 3] * inv};
+        *reinterpret_cast<f32x4*>(orow + 32 * dt + 8 * g + 4 * h) = val;
+      }
+    if (h == 0 && a.lse) a.lse[ri] = (l_tot > 0.f) ? m_all * a.tau + __logf(l_tot) : -INFINITY;
+  } else {
+    const size_t pr = ((size_t)bh * a.nsplit + split) * a.Nq + qrow;
+    float* prow = a.part_o + pr * D;
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        f32x4 val = {acc_o[dt][4 * g], acc_o[dt][4 * g + 1], acc_o[dt][4 * g + 2], acc_o[dt][4 * g + 3]};
+        *reinterpret_cast<f32x4*>(prow + 32 * dt + 8 * g + 4 * h) = val;
+      }
+    if (h == 0) *reinterpret_cast<f32x2*>(a.part_ml + 2 * pr) = f32x2{m_all, l_tot};
+  }
+}
+
+// out[row] = sum_s O_s 2^(c (m_s - M)) / sum_s l_s 2^(c (m_s - M)), M = max_s m_s.  A workgroup = one (bh, row): thread (g, j) takes
+// columns 4g .. 4g+3 of the splits j, j + S, j + 2S, ... and the S partial sums of a column group are added in the order j = 0 .. S-1
+// (a fixed order: bitwise repeatable).
+template <int D>
+__global__ void __launch_bounds__(256) decode_combine_kernel(DecodeArgs a) {
+  constexpr int G = D / 4, S = 256 / G;
+  __shared__ f32x4 red_o[256];
+  __shared__ float red_m[256], red_l[256];
+  const int tid = threadIdx.x, g = tid % G, j = tid / G;
+  const int row = blockIdx.x % a.Nq, bh = blockIdx.x / a.Nq;
+  const int b = bh / a.H, hd = bh - b * a.H;
+  const float c = a.tau * LOG2E;
+  const size_t p0 = (size_t)bh * a.nsplit * a.Nq + row;   // partial row of split s: p0 + s * Nq
+  float m = -INFINITY;
+  for (int s = j; s < a.nsplit; s += S) m = fmaxf(m, a.part_ml[2 * (p0 + (size_t)s * a.Nq)]);
+  red_m[tid] = m;
+  __syncthreads();
+  float m_all = -INFINITY;
+  for (int u = 0; u < S; ++u) m_all = fmaxf(m_all, red_m[u * G + g]);
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  float l = 0.f;
+  if (m_all != -INFINITY) {
+    for (int s = j; s < a.nsplit; s += S) {
+      const size_t p = p0 + (size_t)s * a.Nq;
+      const f32x2 ml = *reinterpret_cast<const f32x2*>(a.part_ml + 2 * p);
+      if (ml[0] == -INFINITY) continue;
+      const float wgt = __builtin_amdgcn_exp2f((ml[0] - m_all) * c);
+      l += ml[1] * wgt;
+      acc += *reinterpret_cast<const f32x4*>(a.part_o + p * D + 4 * g) * wgt;
+    }
+  }
+  red_o[tid] = acc;
+  red_l[tid] = l;
+  __syncthreads();
+  if (j != 0) return;
+  for (int u = 1; u < S; ++u) {
+    acc += red_o[u * G + g];
+    l += red_l[u * G + g];
+  }
+  const float inv = (l > 0.f) ? 1.0f / l : 0.f;
+  float* orow = a.out + (size_t)b * a.q_bstride + (size_t)hd * a.q_hstride + (size_t)row * a.q_ld;
+  *reinterpret_cast<f32x4*>(orow + 4 * g) = acc * inv;
+  if (g == 0 && a.lse) a.lse[(size_t)bh * a.Nq + row] = (l > 0.f) ? m_all * a.tau + __logf(l) : -INFINITY;
+}
+
+}  // namespace fa

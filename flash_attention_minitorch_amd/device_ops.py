@@ -391,3 +391,84 @@ def flash_attn_causal(q, k, v, causal=True):  # Tensor.flash_attn_causal, minito
 
 def flash_attn2(q, k, v, causal=False):       # Tensor.flash_attn2, minitorch/tensor.py:428-429
     return _FlashAttnFn.apply(q, k, v, bool(causal), _lib.FA_VARIANT_FA2)
+
+
+_DECODE_LAYOUTS = {"bnhd": _lib.FA_LAYOUT_BNHD, "bhnd": _lib.FA_LAYOUT_BHND}
+
+
+def _decode_dims(q, k_cache, layout):
+    """(B, H, Nq, Ncap, dq, dp) of a decode call: q (B, Nq, H, dq) / cache (B, Ncap, H, dp) for "bnhd", (B, H, Nq, dq) / (B, H, Ncap, dp)
+    for "bhnd"."""
+    if q.dim() != 4 or k_cache.dim() != 4:
+        raise ValueError("decode expects 4-d q and caches")
+    if layout == "bnhd":
+        (B, Nq, H, dq), (Bc, Ncap, Hc, dp) = q.shape, k_cache.shape
+    else:
+        (B, H, Nq, dq), (Bc, Hc, Ncap, dp) = q.shape, k_cache.shape
+    if (B, H) != (Bc, Hc):
+        raise ValueError(f"q and the cache disagree on (B, H): {(B, H)} vs {(Bc, Hc)}")
+    return B, H, Nq, Ncap, dq, dp
+
+
+def decode_workspace(q, k_cache, layout="bnhd"):
+    """Scratch for flash_attn_decode with these tensors (fa_mi355x_decode_workspace_bytes; one partial O, m, l per query row and key
+    chunk), or None when the call runs as one split and needs none.  A pure function of the shapes: allocate once, reuse every step."""
+    B, H, Nq, Ncap, _, dp = _decode_dims(q, k_cache, layout)
+    nbytes = _lib.decode().fa_mi355x_decode_workspace_bytes(B, H, Nq, Ncap, dp)
+    return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=q.device) if nbytes else None
+
+
+def flash_attn_decode(q, k_cache, v_cache, cache_seqlens=None, causal=True, softmax_scale=None, layout="bnhd", out=None, lse=None,
+                      workspace=None):
+    """Attention of Nq <= 128 new queries against a KV cache (fa_mi355x_fwd_decode, include/flash_attn_mi355x_decode.h).
+    ``layout`` "bnhd": q (B, Nq, H, d), caches (B, Ncap, H, dp); "bhnd": q (B, H, Nq, d), caches (B, H, Ncap, dp).  dp in {32, 64, 128};
+    a q with fewer columns (d < dp) is zero-padded to the cache's row length (the cache itself holds zero columns d .. dp-1) and the
+    default scale is then 1/sqrt(d).  ``cache_seqlens``: int32 (B,) on q's device, the valid cache rows per batch element counting the
+    new tokens (None: all Ncap); clamped to [0, Ncap] on the device, no host synchronisation.  ``causal``: the queries are the last Nq
+    positions.  Returns (out fp32 in q's shape, lse fp32 (B, H, Nq)): rows with no admissible key give out = 0, lse = -inf."""
+    if layout not in _DECODE_LAYOUTS:
+        raise ValueError(f"layout must be one of {sorted(_DECODE_LAYOUTS)}")
+    if q.dtype not in _DTYPES:
+        raise TypeError(f"unsupported dtype {q.dtype}: use float32 or bfloat16")
+    if k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
+        raise TypeError("q, k_cache and v_cache must share one dtype")
+    if k_cache.shape != v_cache.shape:
+        raise ValueError("k_cache and v_cache must have one shape")
+    B, H, Nq, Ncap, d, dp = _decode_dims(q, k_cache, layout)
+    if d > dp:
+        raise ValueError(f"q's head dim {d} exceeds the cache's row length {dp}")
+    if cache_seqlens is not None and (cache_seqlens.dtype != torch.int32 or tuple(cache_seqlens.shape) != (B,)
+                                      or cache_seqlens.device != q.device or not cache_seqlens.is_contiguous()):
+        raise ValueError("cache_seqlens must be a contiguous int32 tensor of shape (B,) on q's device")
+    for t in (q, k_cache, v_cache):
+        if not t.is_cuda:
+            raise _lib.FlashAttnLibraryError("flash_attn_decode needs GPU tensors; there is no CPU fallback")
+        if t.device != q.device:
+            raise ValueError("q, k_cache and v_cache must live on one device")
+        if not t.is_contiguous():
+            raise ValueError("q, k_cache and v_cache must be contiguous")
+    if softmax_scale is None:
+        softmax_scale = 0.0 if d == dp else d ** -0.5
+    qp = _pad_cols(q, dp) if d < dp else q
+    if out is not None and (out.shape != q.shape or out.dtype != torch.float32 or not out.is_contiguous()):
+        raise ValueError("out must be a contiguous float32 tensor of q's shape")
+    outp = out if out is not None and d == dp else torch.empty(qp.shape, dtype=torch.float32, device=q.device)
+    if lse is None:
+        lse = torch.empty((B, H, Nq), dtype=torch.float32, device=q.device)
+    elif tuple(lse.shape) != (B, H, Nq) or lse.dtype != torch.float32 or not lse.is_contiguous():
+        raise ValueError("lse must be a contiguous float32 tensor of shape (B, H, Nq)")
+    lib = _lib.decode()
+    if workspace is None:
+        workspace = decode_workspace(qp, k_cache, layout)
+    elif workspace.numel() * workspace.element_size() < lib.fa_mi355x_decode_workspace_bytes(B, H, Nq, Ncap, dp):
+        raise ValueError("workspace too small: size it with decode_workspace()")
+    _lib.decode_check(lib.fa_mi355x_fwd_decode(_ptr(qp), _ptr(k_cache), _ptr(v_cache), _ptr(outp), _ptr(lse), _ptr(cache_seqlens),
+                                               _ptr(workspace), B, H, Nq, Ncap, dp, _DECODE_LAYOUTS[layout], float(softmax_scale),
+                                               int(bool(causal)), _DTYPES[q.dtype], _stream_ptr()))
+    if d < dp:
+        if out is None:
+            out = outp[..., :d].contiguous()
+        else:
+            out.copy_(outp[..., :d])
+        return out, lse
+    return outp, lse

@@ -105,3 +105,94 @@ def attention_stack(x, layers, n_head: int, causal: bool = True, fused_layout: b
     for (wq, wk, wv, wo) in layers:
         x = x + multi_head_attention(x, wq, wk, wv, wo, n_head, causal, fused_layout, fold_scale)
     return x
+
+
+# ---- incremental generation: the inference half of the chain above ----------------------------------------------------------------
+# The reference's generate() (project/run_machine_translation.py:276-292) re-runs the whole model over the full prefix for every new
+# token and keeps the last row.  With a KV cache, the prompt runs once through the fused causal forward (attention_stack_prefill), and
+# every further step projects only its new tokens, appends their k and v at each batch element's own length and attends to the cache
+# with the decode kernels (attention_stack_step): one pass over the cached K and V per layer instead of causal attention over N tokens.
+
+MAX_STEP_TOKENS = 128   # fa_mi355x_fwd_decode's largest Nq; longer inputs are prefill
+
+
+class KVCache:
+    """Per-layer k and v caches of a causal attention stack: ``k[l]``, ``v[l]`` are (B, capacity, n_head, dp) in the projection's own
+    [B][N][H][d] layout (no permute), dp = head_dim rounded up to 32, 64 or 128 with zero columns past head_dim.  ``lengths``: device
+    int32 (B,), the valid rows per batch element (read by the decode kernels, never by the host)."""
+
+    def __init__(self, n_layers, B, capacity, n_head, head_dim, dtype, device):
+        self.head_dim, self.dp = head_dim, device_ops._padded_d(head_dim)
+        self.capacity, self.n_head = capacity, n_head
+        shape = (B, capacity, n_head, self.dp)
+        self.k = [torch.zeros(shape, dtype=dtype, device=device) for _ in range(n_layers)]
+        self.v = [torch.zeros(shape, dtype=dtype, device=device) for _ in range(n_layers)]
+        self.lengths = torch.zeros(B, dtype=torch.int32, device=device)
+        self.length_bound = 0   # host-side upper bound of every length: capacity checks without a device synchronisation
+        self._workspaces = {}
+
+    def workspace(self, q):
+        key = tuple(q.shape)
+        if key not in self._workspaces:
+            self._workspaces[key] = device_ops.decode_workspace(q, self.k[0], "bnhd")
+        return self._workspaces[key]
+
+    def _pad(self, t):
+        return t if self.dp == self.head_dim else device_ops._pad_cols(t, self.dp)
+
+
+def _project(x, wq, wk, wv, n_head):
+    B, N, E = x.shape
+    x2 = x.reshape(B * N, E)
+    return tuple((x2 @ w).view(B, N, n_head, E // n_head) for w in (wq, wk, wv))
+
+
+def attention_stack_prefill(x, layers, n_head: int, cache: KVCache):
+    """attention_stack(x, layers, n_head, causal=True) over a prompt x (B, P, E) that also (re)fills ``cache`` with every layer's k and
+    v of the P tokens (lengths = P).  Returns the stack's output (B, P, E)."""
+    B, P, E = x.shape
+    if P > cache.capacity:
+        raise ValueError(f"prompt of {P} tokens exceeds the cache capacity {cache.capacity}")
+    d = E // n_head
+    for li, (wq, wk, wv, wo) in enumerate(layers):
+        q, k, v = _project(x, wq, wk, wv, n_head)
+        kp, vp = cache._pad(k), cache._pad(v)
+        cache.k[li][:, :P] = kp
+        cache.v[li][:, :P] = vp
+        if cache.dp == d:
+            o, _, _ = device_ops.flash_attn_fwd_bnhd(q, k, v, True, _lib.FA_VARIANT_FA2)
+        else:   # zero columns add nothing to the scores; the scale keeps the caller's d
+            o, _, _ = device_ops.flash_attn_fwd_bnhd(cache._pad(q), kp, vp, True, _lib.FA_VARIANT_FA2, softmax_scale=d ** -0.5)
+            o = o[..., :d]
+        x = x + (o.reshape(B * P, E).to(x.dtype) @ wo).view(B, P, E)
+    cache.lengths.fill_(P)
+    cache.length_bound = P
+    return x
+
+
+def attention_stack_step(x_new, layers, n_head: int, cache: KVCache):
+    """One generation step of the stack: x_new (B, T, E), T <= 128 new tokens that follow each batch element's cached prefix.  Every
+    layer projects them, appends k and v at rows lengths[b] .. lengths[b] + T - 1 (device indexing: no host synchronisation), and
+    attends causally to the cache with the decode kernels; lengths grow by T.  Returns the stack's output for the new tokens (B, T, E),
+    the last T rows of attention_stack over the whole sequence."""
+    B, T, E = x_new.shape
+    if T > MAX_STEP_TOKENS:
+        raise ValueError(f"a step takes at most {MAX_STEP_TOKENS} tokens; use attention_stack_prefill for longer inputs")
+    if cache.length_bound + T > cache.capacity:
+        raise ValueError(f"cache capacity {cache.capacity} exceeded")
+    dev = x_new.device
+    # rows b * capacity + lengths[b] + t of the (B * capacity, H, dp) view of a layer's cache: the new tokens' k and v
+    rows = (cache.lengths.long() + torch.arange(B, device=dev) * cache.capacity)[:, None] + torch.arange(T, device=dev)
+    rows = rows.reshape(B * T)
+    new_len = cache.lengths + T
+    x = x_new
+    for li, (wq, wk, wv, wo) in enumerate(layers):
+        q, k, v = _project(x, wq, wk, wv, n_head)
+        for dst, t in ((cache.k[li], k), (cache.v[li], v)):
+            dst.view(B * cache.capacity, n_head, cache.dp).index_copy_(0, rows, cache._pad(t).reshape(B * T, n_head, cache.dp))
+        o, _ = device_ops.flash_attn_decode(q, cache.k[li], cache.v[li], new_len, causal=True, layout="bnhd",
+                                            workspace=cache.workspace(q))
+        x = x + (o.reshape(B * T, E).to(x.dtype) @ wo).view(B, T, E)
+    cache.lengths.copy_(new_len)
+    cache.length_bound += T
+    return x

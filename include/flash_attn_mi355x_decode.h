@@ -1,0 +1,65 @@
+/*
+ * flash_attn_mi355x_decode.h -- C ABI of the MI355X (gfx950) KV-cache decode attention library, libflash_attn_mi355x_decode.so.
+ *
+ * The decode step of token-by-token generation: a few new queries against a cache that already holds the earlier keys and values.
+ * The reference model's generate() re-runs the whole model over the full prefix for every new token and keeps the last row
+ * (project/run_machine_translation.py:276-292 there); with a cache, a step costs one pass over the cached K and V instead.
+ *
+ *   out[b,h,i,:] = softmax_j(scale * q[b,h,i,:] . k[b,h,j,:]) . v[b,h,j,:],   j < len_b
+ *
+ * A library of its own: the training library (flash_attn_mi355x.h) keeps its code object, and inference users can ship only this.
+ * Same status codes (FA_OK, FA_ERR_*), dtypes (FA_DTYPE_*) and layouts (FA_LAYOUT_*) as the training library.
+ */
+#ifndef FLASH_ATTN_MI355X_DECODE_H
+#define FLASH_ATTN_MI355X_DECODE_H
+
+#include <stddef.h>
+
+#include "flash_attn_mi355x.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* Largest number of new queries per call; more is prefill (fa_mi355x_fwd_layout / fa_mi355x_fwd_scaled). */
+#define FA_DECODE_MAX_NQ 128
+
+/* Bytes of device workspace fa_mi355x_fwd_decode needs for these sizes: 0 when the call runs as one split, else
+ * B*H*nsplit*Nq*(d + 2) floats (one partial O, m, l per query row and split).  A pure function of its arguments (no device query);
+ * 0 for non-positive sizes. */
+size_t fa_mi355x_decode_workspace_bytes(int B, int H, int Nq, int Ncap, int d);
+
+/* The number of key chunks (splits) a call with these sizes uses: 1 = one launch that writes out and lse directly; more = a split
+ * launch into the workspace and a combine launch.  The policy assumes a 256-CU chip (as fa_mi355x_plan does), so the split count,
+ * the workspace size and the results do not depend on the GPU that runs the call.  0 for non-positive sizes. */
+int fa_mi355x_decode_splits(int B, int H, int Nq, int Ncap, int d, int dtype);
+
+/* Decode attention on device pointers, asynchronous on `stream`, no allocation, no host synchronisation (capturable in a graph).
+ *   q        dtype elements, [B][H][Nq][d] (FA_LAYOUT_BHND) or [B][Nq][H][d] (FA_LAYOUT_BNHD), 1 <= Nq <= FA_DECODE_MAX_NQ
+ *   k_cache, v_cache   dtype elements, [B][H][Ncap][d] or [B][Ncap][H][d] (the same layout family as q)
+ *   out      float, q's shape and layout
+ *   lse      float [B][H][Nq]: natural-log logsumexp of the scaled scores (the FA-2 l of the training library); may be NULL
+ *   cache_seqlens  device int [B]: len_b, the valid cache rows of batch element b, counting the Nq new tokens (the caller writes
+ *            their k / v into the cache first); clamped to [0, Ncap] in the kernel.  NULL: every len_b = Ncap.  Cache rows at or past
+ *            len_b contribute nothing whatever they hold, and no cache row past Ncap - 1 is read.
+ *   workspace  device memory of fa_mi355x_decode_workspace_bytes(B, H, Nq, Ncap, d) bytes (may be NULL when that is 0)
+ *   d        32, 64 or 128 (FA_ERR_UNSUPPORTED_D otherwise).  Other head sizes run through a cache padded with zero columns to
+ *            the next of them, with q padded likewise and softmax_scale = 1/sqrt(d).
+ *   softmax_scale  0: 1/sqrt(d); otherwise positive and finite.  Applied in fp32 to every score (no folded operand, no guard).
+ *   causal   queries are the LAST Nq positions: query i sits at len_b - Nq + i and sees keys j <= len_b - Nq + i.  Otherwise a
+ *            query sees all len_b keys.
+ *   dtype    FA_DTYPE_F32 or FA_DTYPE_BF16 (q and the cache alike); out and lse are fp32.
+ * A row with no admissible key (len_b = 0, or a causal row at a position below 0) returns out = 0 and lse = -inf, as
+ * fa_mi355x_fwd_masked does.  No atomics: the split boundaries and the combine order depend only on the arguments, so repeated
+ * calls are bitwise identical.  Every bad argument is answered with FA_ERR_BAD_ARG / FA_ERR_UNSUPPORTED_D before any HIP call. */
+int fa_mi355x_fwd_decode(const void* q, const void* k_cache, const void* v_cache, float* out, float* lse, const int* cache_seqlens,
+                         void* workspace, int B, int H, int Nq, int Ncap, int d, int layout, float softmax_scale, int causal,
+                         int dtype, void* stream);
+
+/* Message of the last FA_ERR_* of this library on this thread ("" if none). */
+const char* fa_mi355x_decode_last_error(void);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* FLASH_ATTN_MI355X_DECODE_H */

@@ -1,0 +1,126 @@
+"""KV-cache decode (fa_mi355x_fwd_decode) on the MI355X: one JSON line per shape.
+
+Per shape: microseconds per decode call (device events around `--reps` calls after `--warmup`), the K+V bytes one call must read
+(B * H * len * d * 2 * element size), GB/s and the share of the 6.3 TB/s measured copy rate and of the 8 TB/s spec.  The calls rotate
+over enough distinct caches that the bytes touched exceed 512 MB, so the 256 MB Infinity Cache does not serve repeated calls.
+Beside it, on the same data:
+  (a) what a user does without decode: the existing causal forward on [B][N][H][d] (device_ops.flash_attn_fwd_bnhd, the library's
+      default guarded call) over all len tokens, of which the caller keeps the last Nq rows;
+  (b) torch.nn.functional.scaled_dot_product_attention on the cache slice ([B][H][len][d]); no mask (for Nq = 1 the same function).
+Then the in-model number: one attention_stack_step of a 4-layer stack against re-running attention_stack over the whole prefix.
+
+    python tools/bench_decode.py [--reps 50] [--warmup 5] [--only decode] > decode.txt
+"""
+import argparse
+import json
+import math
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from flash_attention_minitorch_amd import _lib, device_ops, modules_transformer as mt  # noqa: E402
+
+COPY_TBS, SPEC_TBS = 6.3, 8.0
+ROTATE_BYTES = 512 << 20
+
+# (dtype, B, H, Nq, len, d)
+SHAPES = [
+    ("bf16", 1, 8, 1, 4096, 128), ("bf16", 1, 8, 1, 16384, 128), ("bf16", 1, 8, 1, 65536, 128), ("bf16", 32, 32, 1, 4096, 128),
+    ("f32", 8, 8, 1, 4096, 64),
+    ("f32", 8, 8, 1, 1024, 32), ("bf16", 8, 8, 1, 1024, 32),
+    ("bf16", 8, 8, 4, 4096, 128), ("bf16", 8, 8, 64, 4096, 128),
+]
+DT = {"bf16": torch.bfloat16, "f32": torch.float32}
+
+
+def timed_us(fn, reps, warmup):
+    for i in range(warmup):
+        fn(i)
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for i in range(reps):
+        fn(i)
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) * 1e3 / reps
+
+
+def bench_shape(dtype, B, H, Nq, n, d, reps, warmup, only):
+    dt = DT[dtype]
+    esz = torch.tensor([], dtype=dt).element_size()
+    kv_bytes = B * H * n * d * 2 * esz
+    ncache = max(1, math.ceil(ROTATE_BYTES / kv_bytes) + 1) if kv_bytes < ROTATE_BYTES else 1
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    u = lambda *s: (torch.rand(*s, device="cuda", generator=gen) * 2 - 1).to(dt)
+    caches = [(u(B, n, H, d), u(B, n, H, d)) for _ in range(ncache)]
+    q = u(B, Nq, H, d)
+    lens = torch.full((B,), n, dtype=torch.int32, device="cuda")
+    out = torch.empty(q.shape, dtype=torch.float32, device="cuda")
+    lse = torch.empty((B, H, Nq), dtype=torch.float32, device="cuda")
+    ws = device_ops.decode_workspace(q, caches[0][0])
+    splits = _lib.decode().fa_mi355x_decode_splits(B, H, Nq, n, d, 1 if dtype == "bf16" else 0)
+
+    def dec(i):
+        k, v = caches[i % ncache]
+        device_ops.flash_attn_decode(q, k, v, lens, causal=True, out=out, lse=lse, workspace=ws)
+
+    us = timed_us(dec, reps, warmup)
+    rec = {"shape": f"B={B} H={H} Nq={Nq} len={n} d={d} {dtype}", "dtype": dtype, "B": B, "H": H, "Nq": Nq, "len": n, "d": d,
+           "splits": splits, "caches_rotated": ncache, "decode_us": round(us, 2), "kv_bytes": kv_bytes,
+           "GB_s": round(kv_bytes / us / 1e3, 1), "of_copy_6.3TBs": round(kv_bytes / us / 1e6 / COPY_TBS, 3),
+           "of_spec_8TBs": round(kv_bytes / us / 1e6 / SPEC_TBS, 3)}
+    if only != "decode":
+        k, v = caches[0]
+        qfull = u(B, n, H, d)
+        qfull[:, n - Nq:] = q
+
+        def prefill(i):
+            device_ops.flash_attn_fwd_bnhd(qfull, k, v, True, _lib.FA_VARIANT_FA2)
+
+        r = max(3, reps // 10)
+        rec["a_full_causal_fwd_us"] = round(timed_us(prefill, r, 2), 2)
+        qs, ks, vs = (t.transpose(1, 2).contiguous() for t in (q, k, v))
+        sdpa = lambda i: torch.nn.functional.scaled_dot_product_attention(qs, ks, vs)
+        rec["b_torch_sdpa_us"] = round(timed_us(sdpa, r, 2), 2)
+        rec["speedup_vs_a"] = round(rec["a_full_causal_fwd_us"] / us, 2)
+        rec["speedup_vs_b"] = round(rec["b_torch_sdpa_us"] / us, 2)
+    del caches
+    torch.cuda.empty_cache()
+    return rec
+
+
+def bench_stack(dtype, B, E, H, prefix, reps, warmup, layers_n=4):
+    dt = DT[dtype]
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    u = lambda *s: (torch.rand(*s, device="cuda", generator=gen) * 2 - 1)
+    layers = [tuple((u(E, E) / math.sqrt(E)).to(dt) for _ in range(4)) for _ in range(layers_n)]
+    x = u(B, prefix + 1, E).to(dt)
+    cache = mt.KVCache(layers_n, B, prefix + warmup + reps + 8, H, E // H, dt, "cuda")
+    mt.attention_stack_prefill(x[:, :prefix].contiguous(), layers, H, cache)
+    xs = x[:, prefix:].contiguous()
+    step = timed_us(lambda i: mt.attention_stack_step(xs, layers, H, cache), reps, warmup)
+    full = timed_us(lambda i: mt.attention_stack(x, layers, H, causal=True), max(3, reps // 5), 2)
+    return {"stack": f"{layers_n}-layer B={B} E={E} H={H} prefix={prefix} {dtype}", "step_us": round(step, 1),
+            "full_prefix_us": round(full, 1), "speedup": round(full / step, 2)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--only", choices=["all", "decode"], default="all", help="decode: the decode timings alone (for a trace run)")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_decode.py needs a GPU")
+    for s in SHAPES:
+        print(json.dumps(bench_shape(*s, args.reps, args.warmup, args.only)), flush=True)
+    if args.only == "all":
+        for dtype, B, E, H, prefix in (("bf16", 8, 256, 8, 1024), ("f32", 8, 256, 8, 1024), ("bf16", 1, 1024, 8, 8192)):
+            print(json.dumps(bench_stack(dtype, B, E, H, prefix, args.reps, args.warmup)), flush=True)
+
+
+if __name__ == "__main__":
+    main()
