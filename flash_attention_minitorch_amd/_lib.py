@@ -66,72 +66,76 @@ def load(name: str) -> ctypes.CDLL:
     return h
 
 
-_vp, _i, _fp = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_float)
+_vp, _i, _u, _f, _d, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint, ctypes.c_float, ctypes.c_double, ctypes.c_size_t
+_ip, _dp, _s = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double), ctypes.c_char_p
+
+# symbol -> (restype, argtypes) of every entry point of include/flash_attn_mi355x.h but the host-pointer launchers
+# (tests/test_lib_cpu.py holds this table against the header)
+CORE_ABI = {
+    "fa_mi355x_host_pin_stats": (None, [ctypes.POINTER(ctypes.c_ulonglong)] * 2),
+    "fa_mi355x_fwd": (_i, [_vp] * 6 + [_i] * 6 + [_vp]),
+    "fa_mi355x_bwd_workspace_bytes": (_sz, [_i] * 3),
+    "fa_mi355x_bwd_workspace_bytes_ex": (_sz, [_i] * 3 + [_ip, _i]),
+    "fa_mi355x_bwd_status": (_i, [_vp] + [_i] * 3 + [_ip]),
+    "fa_mi355x_bwd": (_i, [_vp] * 11 + [_i] * 6 + [_vp]),
+    "fa_mi355x_bwd_stages": (_i, [_vp] * 11 + [_i] * 7 + [_vp]),
+    "fa_mi355x_fwd_ex": (_i, [_vp] * 6 + [_i] * 6 + [_ip, _i, _vp]),
+    "fa_mi355x_bwd_ex": (_i, [_vp] * 11 + [_i] * 7 + [_ip, _i, _vp]),
+    "fa_mi355x_guard_bytes": (_sz, []),
+    "fa_mi355x_scale_guard": (_i, [_vp, _vp, ctypes.c_long, _i, _i, _vp, _vp]),
+    "fa_mi355x_fwd_guarded": (_i, [_vp] * 6 + [_i] * 5 + [_f] + [_i] * 3 + [_ip, _i, _vp, _i, _vp]),
+    "fa_mi355x_bwd_guarded": (_i, [_vp] * 11 + [_i] * 5 + [_f] + [_i] * 4 + [_ip, _i, _vp, _vp]),
+    "fa_mi355x_fwd_scaled": (_i, [_vp] * 6 + [_i] * 5 + [_f] + [_i] * 3 + [_vp]),
+    "fa_mi355x_bwd_scaled": (_i, [_vp] * 11 + [_i] * 5 + [_f] + [_i] * 3 + [_vp]),
+    "fa_mi355x_fwd_padded": (_i, [_vp] * 6 + [_i] * 7 + [_vp]),
+    "fa_mi355x_bwd_padded": (_i, [_vp] * 11 + [_i] * 7 + [_vp]),
+    "fa_mi355x_plan": (_i, [_i] * 7 + [_ip, _i, _s, _sz]),
+    "fa_mi355x_fwd_layout": (_i, [_vp] * 6 + [_i] * 8 + [_vp]),
+    "fa_mi355x_bwd_layout": (_i, [_vp] * 11 + [_i] * 8 + [_vp]),
+    "fa_mi355x_fwd_masked": (_i, [_vp] * 7 + [_i] * 8 + [_vp]),
+    "fa_mi355x_bwd_masked": (_i, [_vp] * 12 + [_i] * 8 + [_vp]),
+    "fa_mi355x_fwd_dropout": (_i, [_vp] * 7 + [_f, _f, _u] + [_i] * 8 + [_vp]),
+    "fa_mi355x_bwd_dropout": (_i, [_vp] * 11 + [_f, _f, _u] + [_vp] + [_i] * 8 + [_vp]),
+    "fa_mi355x_last_error": (_s, []),
+    "fa_mi355x_version": (_s, []),
+    "fa_mi355x_measure_mfma_peak": (_i, [_d, _dp, _dp, _vp]),
+    "fa_mi355x_probe": (_i, [_vp] * 6 + [_i, _i, _vp]),
+}
+
+# the same for include/flash_attn_mi355x_decode.h
+DECODE_ABI = {
+    "fa_mi355x_decode_workspace_bytes": (_sz, [_i] * 5),
+    "fa_mi355x_decode_splits": (_i, [_i] * 6),
+    "fa_mi355x_fwd_decode": (_i, [_vp] * 7 + [_i] * 6 + [_f, _i, _i, _vp]),
+    "fa_mi355x_decode_last_error": (_s, []),
+}
+
+
+def _typed(name: str, abi: dict) -> ctypes.CDLL:
+    """The library with restype / argtypes of every symbol in ``abi`` set (once, on first load)."""
+    h = load(name)
+    if not getattr(h, "_fa_typed", False):
+        for sym, (res, args) in abi.items():
+            fn = getattr(h, sym)
+            fn.restype, fn.argtypes = res, args
+        h._fa_typed = True
+    return h
 
 
 def core() -> ctypes.CDLL:
     """libflash_attn_mi355x.so with argtypes set for the device-pointer entry points."""
-    h = load(CORE_NAME)
-    if getattr(h, "_fa_typed", False):
-        return h
-    h.fa_mi355x_fwd.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]
-    h.fa_mi355x_fwd.restype = _i
-    h.fa_mi355x_bwd.argtypes = [_vp] * 11 + [_i] * 6 + [_vp]
-    h.fa_mi355x_bwd.restype = _i
-    h.fa_mi355x_bwd_stages.argtypes = [_vp] * 11 + [_i] * 7 + [_vp]
-    h.fa_mi355x_bwd_stages.restype = _i
-    h.fa_mi355x_fwd_layout.argtypes = [_vp] * 6 + [_i] * 8 + [_vp]
-    h.fa_mi355x_fwd_layout.restype = _i
-    h.fa_mi355x_bwd_layout.argtypes = [_vp] * 11 + [_i] * 8 + [_vp]
-    h.fa_mi355x_bwd_layout.restype = _i
-    h.fa_mi355x_fwd_masked.argtypes = [_vp] * 7 + [_i] * 8 + [_vp]
-    h.fa_mi355x_fwd_masked.restype = _i
-    h.fa_mi355x_bwd_masked.argtypes = [_vp] * 12 + [_i] * 8 + [_vp]
-    h.fa_mi355x_bwd_masked.restype = _i
-    _f, _u = ctypes.c_float, ctypes.c_uint
-    h.fa_mi355x_fwd_dropout.argtypes = [_vp] * 7 + [_f, _f, _u] + [_i] * 8 + [_vp]
-    h.fa_mi355x_fwd_dropout.restype = _i
-    h.fa_mi355x_bwd_dropout.argtypes = [_vp] * 11 + [_f, _f, _u] + [_vp] + [_i] * 8 + [_vp]
-    h.fa_mi355x_bwd_dropout.restype = _i
-    h.fa_mi355x_bwd_workspace_bytes.argtypes = [_i, _i, _i]
-    h.fa_mi355x_bwd_workspace_bytes.restype = ctypes.c_size_t
-    h.fa_mi355x_bwd_workspace_bytes_ex.argtypes = [_i, _i, _i, ctypes.POINTER(ctypes.c_int), _i]
-    h.fa_mi355x_bwd_workspace_bytes_ex.restype = ctypes.c_size_t
-    h.fa_mi355x_last_error.argtypes = []
-    h.fa_mi355x_last_error.restype = ctypes.c_char_p
-    h.fa_mi355x_version.argtypes = []
-    h.fa_mi355x_version.restype = ctypes.c_char_p
-    _ip = ctypes.POINTER(ctypes.c_int)
-    h.fa_mi355x_fwd_ex.argtypes = [_vp] * 6 + [_i] * 6 + [_ip, _i, _vp]
-    h.fa_mi355x_fwd_ex.restype = _i
-    h.fa_mi355x_bwd_ex.argtypes = [_vp] * 11 + [_i] * 7 + [_ip, _i, _vp]
-    h.fa_mi355x_bwd_ex.restype = _i
-    h.fa_mi355x_bwd_status.argtypes = [_vp, _i, _i, _i, _ip]
-    h.fa_mi355x_bwd_status.restype = _i
-    h.fa_mi355x_fwd_scaled.argtypes = [_vp] * 6 + [_i] * 5 + [ctypes.c_float] + [_i] * 3 + [_vp]
-    h.fa_mi355x_fwd_scaled.restype = _i
-    h.fa_mi355x_bwd_scaled.argtypes = [_vp] * 11 + [_i] * 5 + [ctypes.c_float] + [_i] * 3 + [_vp]
-    h.fa_mi355x_bwd_scaled.restype = _i
-    h.fa_mi355x_fwd_padded.argtypes = [_vp] * 6 + [_i] * 7 + [_vp]
-    h.fa_mi355x_fwd_padded.restype = _i
-    h.fa_mi355x_bwd_padded.argtypes = [_vp] * 11 + [_i] * 7 + [_vp]
-    h.fa_mi355x_bwd_padded.restype = _i
-    h.fa_mi355x_guard_bytes.argtypes = []
-    h.fa_mi355x_guard_bytes.restype = ctypes.c_size_t
-    h.fa_mi355x_scale_guard.argtypes = [_vp, _vp, ctypes.c_long, _i, _i, _vp, _vp]
-    h.fa_mi355x_scale_guard.restype = _i
-    h.fa_mi355x_fwd_guarded.argtypes = [_vp] * 6 + [_i] * 5 + [ctypes.c_float] + [_i] * 3 + [_ip, _i, _vp, _i, _vp]
-    h.fa_mi355x_fwd_guarded.restype = _i
-    h.fa_mi355x_bwd_guarded.argtypes = [_vp] * 11 + [_i] * 5 + [ctypes.c_float] + [_i] * 4 + [_ip, _i, _vp, _vp]
-    h.fa_mi355x_bwd_guarded.restype = _i
-    h.fa_mi355x_plan.argtypes = [_i] * 7 + [_ip, _i, ctypes.c_char_p, ctypes.c_size_t]
-    h.fa_mi355x_plan.restype = _i
-    h.fa_mi355x_measure_mfma_peak.argtypes = [ctypes.c_double, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _vp]
-    h.fa_mi355x_measure_mfma_peak.restype = _i
-    h.fa_mi355x_probe.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]
-    h.fa_mi355x_probe.restype = _i
-    h._fa_typed = True
-    return h
+    return _typed(CORE_NAME, CORE_ABI)
+
+
+_guard_elems = None
+
+
+def guard_elems() -> int:
+    """float32 elements of a scale guard (fa_mi355x_guard_bytes() / 4, a constant of the build: read once)."""
+    global _guard_elems
+    if _guard_elems is None:
+        _guard_elems = core().fa_mi355x_guard_bytes() // 4
+    return _guard_elems
 
 
 def opts_array(opts):
@@ -151,10 +155,14 @@ def plan(batch, n, d, causal, variant, dtype, stages, opts=None):
     return [x for x in buf.value.decode().split(";") if x]
 
 
+def _raise(status: int, lib: ctypes.CDLL, last_error: str, what: str) -> None:
+    """The library's error: ``status`` and the message of its ``last_error`` symbol."""
+    raise FlashAttnLibraryError(f"{what} error {status}: {getattr(lib, last_error)().decode()}")
+
+
 def check(status: int) -> None:
     if status != FA_OK:
-        msg = core().fa_mi355x_last_error().decode()
-        raise FlashAttnLibraryError(f"flash_attn_mi355x error {status}: {msg}")
+        _raise(status, core(), "fa_mi355x_last_error", "flash_attn_mi355x")
 
 
 DECODE_NAME = "libflash_attn_mi355x_decode.so"
@@ -162,22 +170,9 @@ DECODE_NAME = "libflash_attn_mi355x_decode.so"
 
 def decode() -> ctypes.CDLL:
     """libflash_attn_mi355x_decode.so (include/flash_attn_mi355x_decode.h) with argtypes set."""
-    h = load(DECODE_NAME)
-    if getattr(h, "_fa_typed", False):
-        return h
-    h.fa_mi355x_decode_workspace_bytes.argtypes = [_i] * 5
-    h.fa_mi355x_decode_workspace_bytes.restype = ctypes.c_size_t
-    h.fa_mi355x_decode_splits.argtypes = [_i] * 6
-    h.fa_mi355x_decode_splits.restype = _i
-    h.fa_mi355x_fwd_decode.argtypes = [_vp] * 7 + [_i] * 6 + [ctypes.c_float, _i, _i, _vp]
-    h.fa_mi355x_fwd_decode.restype = _i
-    h.fa_mi355x_decode_last_error.argtypes = []
-    h.fa_mi355x_decode_last_error.restype = ctypes.c_char_p
-    h._fa_typed = True
-    return h
+    return _typed(DECODE_NAME, DECODE_ABI)
 
 
 def decode_check(status: int) -> None:
     if status != FA_OK:
-        msg = decode().fa_mi355x_decode_last_error().decode()
-        raise FlashAttnLibraryError(f"flash_attn_mi355x_decode error {status}: {msg}")
+        _raise(status, decode(), "fa_mi355x_decode_last_error", "flash_attn_mi355x_decode")

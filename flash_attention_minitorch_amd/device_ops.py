@@ -6,6 +6,9 @@ torch is plumbing only: device memory, streams.  All arithmetic runs in the HIP 
 
 Tensors are (B, H, N, d) or (BH, N, d), contiguous, float32 or bfloat16; outputs (O, dQ, dK, dV) are
 float32 (a bf16 store alone would exceed the 1e-3 max-abs bound).
+
+Every training entry point is one call of ``_fwd`` or ``_bwd``: the checks in one fixed order, the allocation of what the caller did not
+supply, and exactly one C call.
 """
 from __future__ import annotations
 
@@ -16,32 +19,28 @@ import torch
 from . import _lib
 
 _DTYPES = {torch.float32: _lib.FA_DTYPE_F32, torch.bfloat16: _lib.FA_DTYPE_BF16}
+_BHND, _BNHD = _lib.FA_LAYOUT_BHND, _lib.FA_LAYOUT_BNHD
+_FA1 = _lib.FA_VARIANT_FA1
 
 
-def _check_inputs(*ts):
-    t0 = ts[0]
-    if not t0.is_cuda:
-        raise _lib.FlashAttnLibraryError("device_ops needs GPU tensors; there is no CPU fallback")
-    if t0.dtype not in _DTYPES:
-        raise TypeError(f"unsupported dtype {t0.dtype}: use float32 or bfloat16")
-    for t in ts:
-        if t.shape != t0.shape or t.dtype != t0.dtype or t.device != t0.device:
-            raise ValueError("q, k, v (and out_grad) must share shape, dtype and device")
-        if not t.is_contiguous():
-            raise ValueError("tensors must be contiguous [.., N, d]")
-    if t0.dim() not in (3, 4):
-        raise ValueError("expected (B, H, N, d) or (BH, N, d)")
-    n, d = t0.shape[-2], t0.shape[-1]
-    bh = t0.numel() // (n * d)
-    return bh, n, d
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+def _ptr(t):   # (a plain int or None: ctypes converts either for a c_void_p parameter)
+    return t.data_ptr() if t is not None else None
 
 
 def _stream_ptr():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _dtype_code(t):
+    code = _DTYPES.get(t.dtype)
+    if code is None:
+        raise TypeError(f"unsupported dtype {t.dtype}: use float32 or bfloat16")
+    return code
+
+
+def _require_gpu(t, who):
+    if not t.is_cuda:
+        raise _lib.FlashAttnLibraryError(f"{who} needs GPU tensors; there is no CPU fallback")
 
 
 # per-call kernel options of fa_mi355x_fwd_ex / _bwd_ex / *_guarded (include/flash_attn_mi355x.h); all give the same results
@@ -81,10 +80,12 @@ def scale_guard(q, k, out=None):
         raise ValueError("q and k must be contiguous GPU tensors of one dtype and row length")
     if out is None:
         out = torch.empty(_lib.core().fa_mi355x_guard_bytes() // 4, dtype=torch.float32, device=q.device)
+    else:
+        _check_buffer(out, q.get_device(), "guard", _lib.guard_elems())
     d = q.shape[-1]
     if q.numel() != k.numel():
         raise ValueError("q and k must have the same number of rows")
-    _lib.check(_lib.core().fa_mi355x_scale_guard(_ptr(q), _ptr(k), q.numel() // d, d, _DTYPES[q.dtype], _ptr(out), _stream_ptr()))
+    _lib.check(_lib.core().fa_mi355x_scale_guard(_ptr(q), _ptr(k), q.numel() // d, d, _dtype_code(q), _ptr(out), _stream_ptr()))
     return out
 
 
@@ -101,83 +102,33 @@ def new_guard(q, opts=None):
     return torch.empty(_lib.core().fa_mi355x_guard_bytes() // 4, dtype=torch.float32, device=q.device)
 
 
-def _auto_guard(q, k, opts, guard):
-    """guard = "auto" on a call that only READS a guard (the backward on its own): the separate pass over q and k."""
-    if not isinstance(guard, str):
-        return guard
-    return scale_guard(q, k) if _wants_guard(q, opts) else None
-
-
 _NATIVE_D = (32, 64, 128)
 
 
-def _padded_d(d):
+def padded_head_dim(d):
+    """The row length {32, 64, 128} that a head dim d <= 128 runs at (zero columns d .. dp-1)."""
     if d > 128:
         raise ValueError("head dimension d > 128 is not supported (the reference kernels assert d <= 128, src/flash_attn_fw.cu:43)")
     return 32 if d <= 32 else (64 if d <= 64 else 128)
 
 
-def _pad_cols(t, dp):
-    """(.., N, d) -> contiguous (.., N, dp) with zero columns d .. dp-1 (what fa_mi355x_*_padded expects)."""
+def pad_head_dim(t, dp):
+    """(.., N, d) -> contiguous (.., N, dp) with zero columns d .. dp-1 (what fa_mi355x_*_padded and a padded KV cache expect)."""
     return torch.nn.functional.pad(t, (0, dp - t.shape[-1]))
+
+
+def _unpad(tp, d, dst):
+    """Columns 0 .. d-1 of a padded result: a new contiguous tensor, or copied into the caller's ``dst``."""
+    if dst is None:
+        return tp[..., :d].contiguous()
+    dst.copy_(tp[..., :d])
+    return dst
 
 
 def _with_opt(opts, index, value):
     o = list(opts or ()) + [0] * (index + 1)
     o[index] = value
     return tuple(o[:max(index + 1, len(opts or ()))])
-
-
-def flash_attn_fwd(q, k, v, causal=False, variant=_lib.FA_VARIANT_FA2, out=None, l=None, m=None, opts=None, guard="auto",
-                   out_dtype=torch.float32, produce_guard=False):
-    """Forward.  Returns (out fp32, l, m): FA-1 -> l = sum exp(s - rowmax), m = rowmax;
-    FA-2 -> l = logsumexp, m = None.  ``opts``: per-call kernel options (see OPTS_*).  ``guard``: "auto" = the call guards itself (a
-    forward with the folded scale forms the row norms of q and k inside its own launch and its fp32-scaling twin redoes the call if
-    they are beyond the budget); a tensor with ``produce_guard`` = the same, and the tensor (new_guard) is FILLED for the backward of
-    this (q, k); a tensor without = a guard computed before (scale_guard); None = none (fp32 scaling).
-    ``out_dtype`` = torch.bfloat16: the kernels store O as bf16 (one rounding of the fp32 result; option 9; native d only) -- for
-    consumers that take a bf16 activation (sharded.py's gather at half the bytes); the backward needs the fp32 O.
-    Any head dim d <= 128: d outside {32, 64, 128} is zero-padded to the next of them on the device (tau keeps the caller's d; the
-    reference operator takes any d up to its assert, minitorch/cuda_kernel_ops.py:527-581 / src/flash_attn_fw.cu:43)."""
-    bh, n, d = _check_inputs(q, k, v)
-    lead = q.shape[:-2]
-    if d not in _NATIVE_D:
-        if out_dtype != torch.float32 or opts is not None:
-            raise ValueError("per-call options and a bf16 output need a native head dim (32, 64, 128): other d run zero-padded through "
-                             "fa_mi355x_fwd_padded, which takes neither")
-        dp = _padded_d(d)
-        qp, kp, vp = (_pad_cols(t, dp) for t in (q, k, v))
-        outp = torch.empty(lead + (n, dp), dtype=torch.float32, device=q.device)
-        if l is None:
-            l = torch.empty(lead + (n,), dtype=torch.float32, device=q.device)
-        if variant == _lib.FA_VARIANT_FA1 and m is None:
-            m = torch.empty(lead + (n,), dtype=torch.float32, device=q.device)
-        _lib.check(_lib.core().fa_mi355x_fwd_padded(_ptr(qp), _ptr(kp), _ptr(vp), _ptr(outp), _ptr(l), _ptr(m), bh, n, d, dp,
-                                                    int(bool(causal)), variant, _DTYPES[q.dtype], _stream_ptr()))
-        if out is None:
-            out = outp[..., :d].contiguous()
-        else:
-            out.copy_(outp[..., :d])
-        return out, l, m
-    if out_dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError("out_dtype must be float32 or bfloat16")
-    if out is None:
-        out = torch.empty(q.shape, dtype=out_dtype, device=q.device)
-    elif out.dtype != out_dtype or out.shape != q.shape or not out.is_contiguous():
-        raise ValueError("out must be a contiguous tensor of q's shape and of out_dtype")
-    if out_dtype == torch.bfloat16:
-        opts = _with_opt(opts, 9, 1)
-    if l is None:
-        l = torch.empty(lead + (n,), dtype=torch.float32, device=q.device)
-    if variant == _lib.FA_VARIANT_FA1 and m is None:
-        m = torch.empty(lead + (n,), dtype=torch.float32, device=q.device)
-    arr, cnt = _lib.opts_array(opts)
-    if isinstance(guard, str):
-        guard, produce_guard = new_guard(q, opts), True
-    _lib.check(_lib.core().fa_mi355x_fwd_guarded(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(l), _ptr(m), bh, 1, n, d,
-                                                 _lib.FA_LAYOUT_BHND, 0.0, int(bool(causal)), variant, _DTYPES[q.dtype], arr, cnt,
-                                                 _ptr(guard), int(bool(produce_guard and guard is not None)), _stream_ptr()))
-    return out, l, m
 
 
 def _workspace_bytes(bh, n, d, opts=None):
@@ -193,7 +144,7 @@ def bwd_workspace(q, opts=None):
     """Scratch for the backward of (.., N, d) tensors, sized by the library (fa_mi355x_bwd_workspace_bytes_ex: the three
     row-constant vectors)."""
     n, d = q.shape[-2], q.shape[-1]
-    return _workspace(q.numel() // (n * d), n, _padded_d(d), q.device, opts)
+    return _workspace(q.numel() // (n * d), n, padded_head_dim(d), q.device, opts)
 
 
 def bwd_status(workspace, q):
@@ -206,6 +157,175 @@ def bwd_status(workspace, q):
 
 
 STAGE_PREP, STAGE_DKDV, STAGE_DQ, STAGE_ALL = 1, 2, 4, 7
+_F32 = torch.float32
+_MASK_RANK = "a key mask needs (B, H, N, d) tensors: it is shared by the heads of a batch element"
+_RANK4 = "expected (B, H, N, d)"
+
+
+def _check_buffer(t, dev, name, numel):
+    """A caller's float32 buffer that a kernel reads or writes as ``numel`` contiguous elements, on device index ``dev``."""
+    if t.dtype is not _F32 or not t.is_contiguous() or t.get_device() != dev or t.numel() < numel:
+        raise ValueError(f"{name} must be a contiguous float32 tensor on q's device with at least {numel} elements")
+
+
+def _check_inputs(layout, ts, o, key_mask, rank4):
+    """The checks every call starts with, in the order the entry points have always run them: the tensors (GPU, dtype, shared shape /
+    dtype / device, contiguity, rank), the key mask, the forward's O.  ``rank4``: the message for a BHND call that needs 4-d tensors
+    (key mask, dropout), else None; _MASK_RANK also requires the key mask.  Returns (B, H, N, d, dtype code) as the C entry point
+    takes them: B*H and 1 for a call without mask or dropout."""
+    q = ts[0]
+    dev = q.get_device()
+    if layout == _BNHD:
+        if q.dim() != 4:
+            raise ValueError("expected (B, N, H, d)")
+        for t in ts:
+            if not t.is_cuda or t.shape != q.shape or t.dtype != q.dtype or t.get_device() != dev or not t.is_contiguous():
+                raise ValueError("q, k, v must be contiguous GPU tensors of one shape and dtype")
+        B, N, H, d = q.shape
+        dtype = _dtype_code(q)
+    else:
+        _require_gpu(q, "device_ops")
+        dtype = _dtype_code(q)
+        for t in ts:
+            if t.shape != q.shape or t.dtype != q.dtype or t.get_device() != dev:
+                raise ValueError("q, k, v (and out_grad) must share shape, dtype and device")
+            if not t.is_contiguous():
+                raise ValueError("tensors must be contiguous [.., N, d]")
+        if q.dim() not in (3, 4):
+            raise ValueError("expected (B, H, N, d) or (BH, N, d)")
+        N, d = q.shape[-2], q.shape[-1]
+        B, H = q.numel() // (N * d), 1
+        if rank4 is not None:
+            if q.dim() != 4:
+                raise ValueError(rank4)
+            B, H = q.shape[0], q.shape[1]
+    if (key_mask is not None or rank4 is _MASK_RANK) and (key_mask is None or not key_mask.is_cuda or key_mask.dtype is not _F32
+                                                          or tuple(key_mask.shape) != (B, N) or not key_mask.is_contiguous()):
+        raise ValueError("key_mask must be a contiguous float32 GPU tensor of shape (B, N)")
+    if o is not None and (o.dtype is not _F32 or o.shape != q.shape or not o.is_contiguous() or o.get_device() != dev):
+        raise ValueError("out must be the forward's contiguous float32 output")
+    return B, H, N, d, dtype
+
+
+def _check_caller(dev, rows, l, m, guard):
+    if l is not None:
+        _check_buffer(l, dev, "l", rows)
+    if m is not None:
+        _check_buffer(m, dev, "m", rows)
+    if isinstance(guard, torch.Tensor):
+        _check_buffer(guard, dev, "guard", _lib.guard_elems())
+
+
+def _dropout(rate, scale, seed):
+    return float(rate), float(scale), int(seed) & 0xFFFFFFFF
+
+
+def _fwd(layout, q, k, v, causal, variant, scale=None, opts=None, out_dtype=_F32, key_mask=None, dropout=None, guard="auto",
+         produce=False, out=None, l=None, m=None, rank4=None):
+    """Every forward: check the call, allocate what the caller did not supply, make one C call.  Returns (out, l, m)."""
+    B, H, N, d, dtype = _check_inputs(layout, (q, k, v), None, key_mask, rank4)
+    padded = layout == _BHND and rank4 is None and d not in _NATIVE_D
+    if padded:
+        if out_dtype is not _F32 or opts is not None:
+            raise ValueError("per-call options and a bf16 output need a native head dim (32, 64, 128): other d run zero-padded through "
+                             "fa_mi355x_fwd_padded, which takes neither")
+        dp = padded_head_dim(d)
+    else:
+        if out_dtype is not _F32 and out_dtype is not torch.bfloat16:
+            raise TypeError("out_dtype must be float32 or bfloat16")
+        if out is not None and (out.dtype != out_dtype or out.shape != q.shape or not out.is_contiguous()
+                                or out.get_device() != q.get_device()):
+            raise ValueError("out must be a contiguous tensor of q's shape and of out_dtype")
+    _check_caller(q.get_device(), B * H * N, l, m, guard)
+    lib, dev, causal = _lib.core(), q.device, int(bool(causal))
+    stats = (B, H, N) if layout == _BNHD else q.shape[:-2] + (N,)
+    if l is None:
+        l = torch.empty(stats, dtype=_F32, device=dev)
+    if m is None and variant == _FA1:
+        m = torch.empty(stats, dtype=_F32, device=dev)
+    if padded:
+        qp, kp, vp = (pad_head_dim(t, dp) for t in (q, k, v))
+        outp = torch.empty(qp.shape, dtype=_F32, device=dev)
+        _lib.check(lib.fa_mi355x_fwd_padded(_ptr(qp), _ptr(kp), _ptr(vp), _ptr(outp), _ptr(l), _ptr(m), B, N, d, dp, causal, variant,
+                                            dtype, _stream_ptr()))
+        return _unpad(outp, d, out), l, m
+    if out is None:
+        out = torch.empty(q.shape, dtype=out_dtype, device=dev)
+    ptrs = (_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(l), _ptr(m))
+    if dropout is not None:
+        st = lib.fa_mi355x_fwd_dropout(*ptrs, _ptr(key_mask), *dropout, B, H, N, d, layout, causal, variant, dtype, _stream_ptr())
+    elif key_mask is not None:
+        st = lib.fa_mi355x_fwd_masked(*ptrs, _ptr(key_mask), B, H, N, d, layout, causal, variant, dtype, _stream_ptr())
+    else:
+        if out_dtype is torch.bfloat16:
+            opts = _with_opt(opts, 9, 1)
+        arr, cnt = _lib.opts_array(opts)
+        if isinstance(guard, str):
+            guard, produce = new_guard(q, opts), True
+        st = lib.fa_mi355x_fwd_guarded(*ptrs, B, H, N, d, layout, float(scale or 0.0), causal, variant, dtype, arr, cnt, _ptr(guard),
+                                       int(bool(produce and guard is not None)), _stream_ptr())
+    _lib.check(st)
+    return out, l, m
+
+
+def _bwd(layout, q, k, v, o, do, l, m, causal, variant, scale=None, opts=None, key_mask=None, dropout=None, guard="auto",
+         grads=None, workspace=None, stages=STAGE_ALL, rank4=None):
+    """Every backward: check the call, allocate what the caller did not supply, make one C call.  Returns (dq, dk, dv)."""
+    B, H, N, d, dtype = _check_inputs(layout, (q, k, v, do), o, key_mask, rank4)
+    padded = layout == _BHND and rank4 is None and d not in _NATIVE_D
+    if padded:
+        if opts is not None or stages != STAGE_ALL or workspace is not None:
+            raise ValueError("per-call options, a stage mask and a caller's workspace need a native head dim (32, 64, 128): other d run "
+                             "zero-padded through fa_mi355x_bwd_padded, which takes none of them")
+        dp = padded_head_dim(d)
+    elif workspace is not None:
+        if workspace.numel() * workspace.element_size() < _workspace_bytes(B * H, N, d, opts):
+            raise ValueError("workspace too small for these options: size it with bwd_workspace(q, opts)")
+        if not workspace.is_contiguous() or workspace.get_device() != q.get_device():
+            raise ValueError("workspace must be a contiguous tensor on q's device")
+    _check_caller(q.get_device(), B * H * N, l, m, guard)
+    if grads is not None and not padded:
+        for g in grads:
+            _check_buffer(g, q.get_device(), "each of grads", q.numel())
+    lib, dev, causal = _lib.core(), q.device, int(bool(causal))
+    if padded:
+        ins = [pad_head_dim(t, dp) for t in (q, k, v, o, do)]
+        ws = _workspace(B, N, dp, dev)
+        gp = [torch.empty(ins[0].shape, dtype=_F32, device=dev) for _ in range(3)]
+        _lib.check(lib.fa_mi355x_bwd_padded(*map(_ptr, ins + gp), _ptr(l), _ptr(m), _ptr(ws), B, N, d, dp, causal, variant, dtype,
+                                            _stream_ptr()))
+        return tuple(_unpad(g, d, dst) for g, dst in zip(gp, grads or (None,) * 3))
+    if workspace is None:   # (a BNHD call has always sized it without the options: the size does not depend on them)
+        workspace = _workspace(B * H, N, d, dev, opts if layout == _BHND else None)
+    dq, dk, dv = grads or (torch.empty(q.shape, dtype=_F32, device=dev) for _ in range(3))
+    ptrs = (_ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(do), _ptr(dq), _ptr(dk), _ptr(dv), _ptr(l), _ptr(m))
+    if dropout is not None:
+        st = lib.fa_mi355x_bwd_dropout(*ptrs, _ptr(key_mask), *dropout, _ptr(workspace), B, H, N, d, layout, causal, variant, dtype,
+                                       _stream_ptr())
+    elif key_mask is not None:
+        st = lib.fa_mi355x_bwd_masked(*ptrs, _ptr(key_mask), _ptr(workspace), B, H, N, d, layout, causal, variant, dtype, _stream_ptr())
+    else:
+        if isinstance(guard, str):   # "auto" on a call that only reads a guard: the separate pass over q and k
+            guard = scale_guard(q, k) if _wants_guard(q, opts) else None
+        arr, cnt = _lib.opts_array(opts)
+        st = lib.fa_mi355x_bwd_guarded(*ptrs, _ptr(workspace), B, H, N, d, layout, float(scale or 0.0), causal, variant, dtype,
+                                       int(stages), arr, cnt, _ptr(guard), _stream_ptr())
+    _lib.check(st)
+    return dq, dk, dv
+
+
+def flash_attn_fwd(q, k, v, causal=False, variant=_lib.FA_VARIANT_FA2, out=None, l=None, m=None, opts=None, guard="auto",
+                   out_dtype=torch.float32, produce_guard=False):
+    """Forward.  Returns (out fp32, l, m): FA-1 -> l = sum exp(s - rowmax), m = rowmax;
+    FA-2 -> l = logsumexp, m = None.  ``opts``: per-call kernel options (see OPTS_*).  ``guard``: "auto" = the call guards itself (a
+    forward with the folded scale forms the row norms of q and k inside its own launch and its fp32-scaling twin redoes the call if
+    they are beyond the budget); a tensor with ``produce_guard`` = the same, and the tensor (new_guard) is FILLED for the backward of
+    this (q, k); a tensor without = a guard computed before (scale_guard); None = none (fp32 scaling).
+    ``out_dtype`` = torch.bfloat16: the kernels store O as bf16 (one rounding of the fp32 result; option 9; native d only) -- for
+    consumers that take a bf16 activation (sharded.py's gather at half the bytes); the backward needs the fp32 O.
+    Any head dim d <= 128: d outside {32, 64, 128} is zero-padded to the next of them on the device (tau keeps the caller's d; the
+    reference operator takes any d up to its assert, minitorch/cuda_kernel_ops.py:527-581 / src/flash_attn_fw.cu:43)."""
+    return _fwd(_BHND, q, k, v, causal, variant, None, opts, out_dtype, None, None, guard, produce_guard, out, l, m)
 
 
 def flash_attn_bwd(q, k, v, out, out_grad, l, m=None, causal=False, variant=_lib.FA_VARIANT_FA2,
@@ -213,39 +333,7 @@ def flash_attn_bwd(q, k, v, out, out_grad, l, m=None, causal=False, variant=_lib
     """Backward.  out: the forward's fp32 output.  Returns (dq, dk, dv) fp32.
     ``stages`` restricts the call to some of its kernels (profiling only); ``opts``: per-call kernel options (see OPTS_*);
     ``guard`` as flash_attn_fwd (pass the forward's guard tensor to save the second pass over q and k)."""
-    bh, n, d = _check_inputs(q, k, v, out_grad)
-    if out.dtype != torch.float32 or out.shape != q.shape or not out.is_contiguous():
-        raise ValueError("out must be the forward's contiguous float32 output")
-    if d not in _NATIVE_D:   # any d <= 128: zero-padded columns, see flash_attn_fwd
-        if opts is not None or stages != STAGE_ALL or workspace is not None:
-            raise ValueError("per-call options, a stage mask and a caller's workspace need a native head dim (32, 64, 128): other d run "
-                             "zero-padded through fa_mi355x_bwd_padded, which takes none of them")
-        dp = _padded_d(d)
-        qp, kp, vp, op, dop = (_pad_cols(t, dp) for t in (q, k, v, out, out_grad))
-        ws = _workspace(bh, n, dp, q.device)
-        gp = tuple(torch.empty(qp.shape, dtype=torch.float32, device=q.device) for _ in range(3))
-        _lib.check(_lib.core().fa_mi355x_bwd_padded(_ptr(qp), _ptr(kp), _ptr(vp), _ptr(op), _ptr(dop), _ptr(gp[0]), _ptr(gp[1]),
-                                                    _ptr(gp[2]), _ptr(l), _ptr(m), _ptr(ws), bh, n, d, dp, int(bool(causal)),
-                                                    variant, _DTYPES[q.dtype], _stream_ptr()))
-        if grads is None:
-            return tuple(g[..., :d].contiguous() for g in gp)
-        for dst, g in zip(grads, gp):
-            dst.copy_(g[..., :d])
-        return tuple(grads)
-    if workspace is None:
-        workspace = bwd_workspace(q, opts)
-    elif workspace.numel() * workspace.element_size() < _workspace_bytes(bh, n, d, opts):
-        raise ValueError("workspace too small for these options: size it with bwd_workspace(q, opts)")
-    if grads is None:
-        grads = tuple(torch.empty(q.shape, dtype=torch.float32, device=q.device) for _ in range(3))
-    dq, dk, dv = grads
-    arr, cnt = _lib.opts_array(opts)
-    guard = _auto_guard(q, k, opts, guard)
-    _lib.check(_lib.core().fa_mi355x_bwd_guarded(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(out_grad), _ptr(dq),
-                                                 _ptr(dk), _ptr(dv), _ptr(l), _ptr(m), _ptr(workspace), bh, 1, n, d,
-                                                 _lib.FA_LAYOUT_BHND, 0.0, int(bool(causal)), variant, _DTYPES[q.dtype], int(stages),
-                                                 arr, cnt, _ptr(guard), _stream_ptr()))
-    return dq, dk, dv
+    return _bwd(_BHND, q, k, v, out, out_grad, l, m, causal, variant, None, opts, None, None, guard, grads, workspace, stages)
 
 
 def flash_attn_fwd_bnhd(q, k, v, causal=False, variant=_lib.FA_VARIANT_FA2, softmax_scale=None, guard="auto", opts=None,
@@ -254,131 +342,65 @@ def flash_attn_fwd_bnhd(q, k, v, causal=False, variant=_lib.FA_VARIANT_FA2, soft
     permute(0,2,1,3).contiguous() (minitorch/modules_transfomer.py:67-89): no head-split copies.
     Returns (out (B, N, H, d) fp32, l (B, H, N), m (B, H, N) or None).
     ``softmax_scale``: P = softmax(softmax_scale * q.k) instead of the reference's sqrt(1/d) (fa_mi355x_fwd_scaled): for callers that
-    fold the scale into their query projection (modules_transformer.multi_head_attention(fold_scale=True))."""
-    if q.dim() != 4:
-        raise ValueError("expected (B, N, H, d)")
-    for t in (q, k, v):
-        if not t.is_cuda or t.shape != q.shape or t.dtype != q.dtype or not t.is_contiguous():
-            raise ValueError("q, k, v must be contiguous GPU tensors of one shape and dtype")
-    B, N, H, d = q.shape
-    out = torch.empty(q.shape, dtype=torch.float32, device=q.device)
-    l = torch.empty((B, H, N), dtype=torch.float32, device=q.device)
-    m = torch.empty((B, H, N), dtype=torch.float32, device=q.device) if variant == _lib.FA_VARIANT_FA1 else None
-    arr, cnt = _lib.opts_array(opts)
-    if isinstance(guard, str):   # (with softmax_scale = ln 2 the library ignores it: the folded factor is 1)
-        guard, produce_guard = new_guard(q, opts), True
-    _lib.check(_lib.core().fa_mi355x_fwd_guarded(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(l), _ptr(m), B, H, N, d,
-                                                 _lib.FA_LAYOUT_BNHD, float(softmax_scale or 0.0), int(bool(causal)), variant,
-                                                 _DTYPES[q.dtype], arr, cnt, _ptr(guard), int(bool(produce_guard and guard is not None)),
-                                                 _stream_ptr()))
-    return out, l, m
+    fold the scale into their query projection (modules_transformer.multi_head_attention(fold_scale=True)).  With guard = "auto" the
+    call guards itself even then (with softmax_scale = ln 2 the library ignores it: the folded factor is 1)."""
+    return _fwd(_BNHD, q, k, v, causal, variant, softmax_scale, opts, guard=guard, produce=produce_guard)
 
 
 def flash_attn_bwd_bnhd(q, k, v, out, out_grad, l, m=None, causal=False, variant=_lib.FA_VARIANT_FA2, softmax_scale=None,
                         guard="auto", opts=None):
     """Backward on (B, N, H, d) tensors; returns (dq, dk, dv) in the same layout, fp32 (``softmax_scale`` as the forward's)."""
-    B, N, H, d = q.shape
-    ws = _workspace(B * H, N, d, q.device)
-    dq, dk, dv = (torch.empty(q.shape, dtype=torch.float32, device=q.device) for _ in range(3))
-    arr, cnt = _lib.opts_array(opts)
-    guard = _auto_guard(q, k, opts, guard)
-    _lib.check(_lib.core().fa_mi355x_bwd_guarded(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(out_grad), _ptr(dq), _ptr(dk),
-                                                 _ptr(dv), _ptr(l), _ptr(m), _ptr(ws), B, H, N, d, _lib.FA_LAYOUT_BNHD,
-                                                 float(softmax_scale or 0.0), int(bool(causal)), variant, _DTYPES[q.dtype],
-                                                 STAGE_ALL, arr, cnt, _ptr(guard), _stream_ptr()))
-    return dq, dk, dv
-
-
-def _check_mask(key_mask, q):
-    if q.dim() != 4:
-        raise ValueError("a key mask needs (B, H, N, d) tensors: it is shared by the heads of a batch element")
-    B, H, N, d = q.shape
-    if (not key_mask.is_cuda or key_mask.dtype != torch.float32 or tuple(key_mask.shape) != (B, N)
-            or not key_mask.is_contiguous()):
-        raise ValueError("key_mask must be a contiguous float32 GPU tensor of shape (B, N)")
-    return B, H, N, d
+    return _bwd(_BNHD, q, k, v, out, out_grad, l, m, causal, variant, softmax_scale, opts, guard=guard)
 
 
 def flash_attn_fwd_masked(q, k, v, key_mask, causal=False, variant=_lib.FA_VARIANT_FA2):
     """Forward with an additive key mask: P = softmax_k(tau * q.k + key_mask[b, k]), the
     [batch, to_len] mask of the reference's fused softmax (src/softmax_kernel.cu:27-34; 0 keeps a key, -inf drops it).
     q, k, v: (B, H, N, d); key_mask: (B, N) float32.  Returns (out, l, m) as flash_attn_fwd."""
-    _check_inputs(q, k, v)
-    B, H, N, d = _check_mask(key_mask, q)
-    out = torch.empty(q.shape, dtype=torch.float32, device=q.device)
-    l = torch.empty((B, H, N), dtype=torch.float32, device=q.device)
-    m = torch.empty((B, H, N), dtype=torch.float32, device=q.device) if variant == _lib.FA_VARIANT_FA1 else None
-    _lib.check(_lib.core().fa_mi355x_fwd_masked(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(l), _ptr(m), _ptr(key_mask),
-                                                B, H, N, d, _lib.FA_LAYOUT_BHND, int(bool(causal)), variant,
-                                                _DTYPES[q.dtype], _stream_ptr()))
-    return out, l, m
+    return _fwd(_BHND, q, k, v, causal, variant, key_mask=key_mask, rank4=_MASK_RANK)
 
 
 def flash_attn_bwd_masked(q, k, v, out, out_grad, l, m, key_mask, causal=False, variant=_lib.FA_VARIANT_FA2):
     """Backward of flash_attn_fwd_masked; returns (dq, dk, dv) fp32 (no gradient flows into the mask)."""
-    _check_inputs(q, k, v, out_grad)
-    B, H, N, d = _check_mask(key_mask, q)
-    ws = _workspace(B * H, N, d, q.device)
-    dq, dk, dv = (torch.empty(q.shape, dtype=torch.float32, device=q.device) for _ in range(3))
-    _lib.check(_lib.core().fa_mi355x_bwd_masked(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(out_grad), _ptr(dq), _ptr(dk),
-                                                _ptr(dv), _ptr(l), _ptr(m), _ptr(key_mask), _ptr(ws), B, H, N, d,
-                                                _lib.FA_LAYOUT_BHND, int(bool(causal)), variant, _DTYPES[q.dtype],
-                                                _stream_ptr()))
-    return dq, dk, dv
+    return _bwd(_BHND, q, k, v, out, out_grad, l, m, causal, variant, key_mask=key_mask, rank4=_MASK_RANK)
 
 
 def flash_attn_fwd_dropout(q, k, v, rate, seed, scale=1.0, key_mask=None, causal=False, variant=_lib.FA_VARIANT_FA2):
     """Forward with dropout on the attention probabilities (and an optional key mask): out = scale * (M o P) v with the
     stateless mask of include/flash_attn_mi355x.h (kept iff rate < r, minitorch/nn.py:168-186; scale = 1 is minitorch's
     convention).  q, k, v: (B, H, N, d).  Returns (out, l, m); l / m are the statistics before dropout."""
-    _check_inputs(q, k, v)
-    if q.dim() != 4:
-        raise ValueError("expected (B, H, N, d)")
-    B, H, N, d = _check_mask(key_mask, q) if key_mask is not None else q.shape
-    out = torch.empty(q.shape, dtype=torch.float32, device=q.device)
-    l = torch.empty((B, H, N), dtype=torch.float32, device=q.device)
-    m = torch.empty((B, H, N), dtype=torch.float32, device=q.device) if variant == _lib.FA_VARIANT_FA1 else None
-    _lib.check(_lib.core().fa_mi355x_fwd_dropout(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(l), _ptr(m), _ptr(key_mask),
-                                                 float(rate), float(scale), int(seed) & 0xFFFFFFFF, B, H, N, d,
-                                                 _lib.FA_LAYOUT_BHND, int(bool(causal)), variant, _DTYPES[q.dtype],
-                                                 _stream_ptr()))
-    return out, l, m
+    return _fwd(_BHND, q, k, v, causal, variant, key_mask=key_mask, dropout=_dropout(rate, scale, seed), rank4=_RANK4)
 
 
 def flash_attn_bwd_dropout(q, k, v, out, out_grad, l, m, rate, seed, scale=1.0, key_mask=None, causal=False,
                            variant=_lib.FA_VARIANT_FA2):
     """Backward of flash_attn_fwd_dropout (same rate, seed, scale, mask); returns (dq, dk, dv) fp32."""
-    _check_inputs(q, k, v, out_grad)
-    B, H, N, d = _check_mask(key_mask, q) if key_mask is not None else q.shape
-    ws = _workspace(B * H, N, d, q.device)
-    dq, dk, dv = (torch.empty(q.shape, dtype=torch.float32, device=q.device) for _ in range(3))
-    _lib.check(_lib.core().fa_mi355x_bwd_dropout(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(out_grad), _ptr(dq), _ptr(dk),
-                                                 _ptr(dv), _ptr(l), _ptr(m), _ptr(key_mask), float(rate), float(scale),
-                                                 int(seed) & 0xFFFFFFFF, _ptr(ws), B, H, N, d, _lib.FA_LAYOUT_BHND,
-                                                 int(bool(causal)), variant, _DTYPES[q.dtype], _stream_ptr()))
-    return dq, dk, dv
+    return _bwd(_BHND, q, k, v, out, out_grad, l, m, causal, variant, key_mask=key_mask, dropout=_dropout(rate, scale, seed),
+                rank4=_RANK4 if key_mask is None else _MASK_RANK)
 
 
 class _FlashAttnFn(torch.autograd.Function):
     """Autograd contract of the reference's Flash_Attn / Flash_Attn2 / Flash_Attn_Causal
     (minitorch/tensor_functions.py:462-497): forward returns o and saves (q, k, v, o, l, m, causal);
-    backward hands them to the SAME variant's backward.  Gradients are cast to the input dtype."""
+    backward hands them to the SAME variant's backward.  Gradients are cast to the input dtype.  ``layout``: BHND, or BNHD for
+    modules_transformer's head-split-free path; ``softmax_scale`` as flash_attn_fwd_bnhd."""
 
     @staticmethod
-    def forward(ctx, q, k, v, causal, variant):
-        guard = new_guard(q) if q.shape[-1] in _NATIVE_D else None   # filled by the forward's own launch, read by the backward
-        o, l, m = flash_attn_fwd(q, k, v, causal, variant, guard=guard, produce_guard=True)
-        none = torch.empty(0, device=q.device)
-        ctx.save_for_backward(q, k, v, o, l, m if m is not None else none, guard if guard is not None else none)
-        ctx.causal, ctx.variant = causal, variant
+    def forward(ctx, q, k, v, causal, variant, layout=_BHND, softmax_scale=None):
+        # the forward fills the scale guard inside its own launch and the backward of the same (q, k) reads it; there is none when
+        # the caller gives the scale (the kernels' folded factor is then exactly 1), and new_guard gives none where d is not native
+        guard = new_guard(q) if softmax_scale is None else None
+        o, l, m = _fwd(layout, q, k, v, causal, variant, softmax_scale, guard=guard, produce=True)
+        ctx.save_for_backward(q, k, v, o, l, m, guard)   # m is None but for FA-1
+        ctx.causal, ctx.variant, ctx.layout, ctx.softmax_scale = causal, variant, layout, softmax_scale
         return o
 
     @staticmethod
     def backward(ctx, out_grad):
         q, k, v, o, l, m, guard = ctx.saved_tensors
-        dq, dk, dv = flash_attn_bwd(q, k, v, o, out_grad.to(q.dtype).contiguous(), l,
-                                    m if m.numel() else None, ctx.causal, ctx.variant, guard=guard if guard.numel() else None)
-        return dq.to(q.dtype), dk.to(q.dtype), dv.to(q.dtype), None, None
+        dq, dk, dv = _bwd(ctx.layout, q, k, v, o, out_grad.to(q.dtype).contiguous(), l, m, ctx.causal, ctx.variant, ctx.softmax_scale,
+                          guard=guard)
+        return dq.to(q.dtype), dk.to(q.dtype), dv.to(q.dtype), None, None, None, None
 
 
 def flash_attn(q, k, v, causal=False):        # Tensor.flash_attn, minitorch/tensor.py:422-423
@@ -428,8 +450,7 @@ def flash_attn_decode(q, k_cache, v_cache, cache_seqlens=None, causal=True, soft
     positions.  Returns (out fp32 in q's shape, lse fp32 (B, H, Nq)): rows with no admissible key give out = 0, lse = -inf."""
     if layout not in _DECODE_LAYOUTS:
         raise ValueError(f"layout must be one of {sorted(_DECODE_LAYOUTS)}")
-    if q.dtype not in _DTYPES:
-        raise TypeError(f"unsupported dtype {q.dtype}: use float32 or bfloat16")
+    dtype = _dtype_code(q)
     if k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
         raise TypeError("q, k_cache and v_cache must share one dtype")
     if k_cache.shape != v_cache.shape:
@@ -441,15 +462,14 @@ def flash_attn_decode(q, k_cache, v_cache, cache_seqlens=None, causal=True, soft
                                       or cache_seqlens.device != q.device or not cache_seqlens.is_contiguous()):
         raise ValueError("cache_seqlens must be a contiguous int32 tensor of shape (B,) on q's device")
     for t in (q, k_cache, v_cache):
-        if not t.is_cuda:
-            raise _lib.FlashAttnLibraryError("flash_attn_decode needs GPU tensors; there is no CPU fallback")
+        _require_gpu(t, "flash_attn_decode")
         if t.device != q.device:
             raise ValueError("q, k_cache and v_cache must live on one device")
         if not t.is_contiguous():
             raise ValueError("q, k_cache and v_cache must be contiguous")
     if softmax_scale is None:
         softmax_scale = 0.0 if d == dp else d ** -0.5
-    qp = _pad_cols(q, dp) if d < dp else q
+    qp = pad_head_dim(q, dp) if d < dp else q
     if out is not None and (out.shape != q.shape or out.dtype != torch.float32 or not out.is_contiguous()):
         raise ValueError("out must be a contiguous float32 tensor of q's shape")
     outp = out if out is not None and d == dp else torch.empty(qp.shape, dtype=torch.float32, device=q.device)
@@ -464,11 +484,5 @@ def flash_attn_decode(q, k_cache, v_cache, cache_seqlens=None, causal=True, soft
         raise ValueError("workspace too small: size it with decode_workspace()")
     _lib.decode_check(lib.fa_mi355x_fwd_decode(_ptr(qp), _ptr(k_cache), _ptr(v_cache), _ptr(outp), _ptr(lse), _ptr(cache_seqlens),
                                                _ptr(workspace), B, H, Nq, Ncap, dp, _DECODE_LAYOUTS[layout], float(softmax_scale),
-                                               int(bool(causal)), _DTYPES[q.dtype], _stream_ptr()))
-    if d < dp:
-        if out is None:
-            out = outp[..., :d].contiguous()
-        else:
-            out.copy_(outp[..., :d])
-        return out, lse
-    return outp, lse
+                                               int(bool(causal)), dtype, _stream_ptr()))
+    return (_unpad(outp, d, out) if d < dp else outp), lse

@@ -21,47 +21,9 @@ import torch
 from . import _lib, device_ops
 
 
-class _FlashAttnBNHD(torch.autograd.Function):
-    """flash_attn2 (``q.flash_attn2(kT, v, self.causal)``, modules_transfomer.py:119-120; autograd contract
-    minitorch/tensor_functions.py:462-497) on (B, N, H, d) tensors."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, causal, softmax_scale=None):
-        # the forward fills the scale guard inside its own launch, the backward reads it (none needed when the caller folded the
-        # scale: the kernels' factor is then exactly 1)
-        guard = None if softmax_scale is not None else device_ops.new_guard(q)
-        o, l, _ = device_ops.flash_attn_fwd_bnhd(q, k, v, causal, _lib.FA_VARIANT_FA2, softmax_scale, guard=guard, produce_guard=True)
-        none = torch.empty(0, device=q.device)
-        ctx.save_for_backward(q, k, v, o, l, guard if guard is not None else none)
-        ctx.causal, ctx.softmax_scale = causal, softmax_scale
-        return o
-
-    @staticmethod
-    def backward(ctx, out_grad):
-        q, k, v, o, l, guard = ctx.saved_tensors
-        dq, dk, dv = device_ops.flash_attn_bwd_bnhd(q, k, v, o, out_grad.to(q.dtype).contiguous(), l, None, ctx.causal,
-                                                    _lib.FA_VARIANT_FA2, ctx.softmax_scale, guard=guard if guard.numel() else None)
-        return dq.to(q.dtype), dk.to(q.dtype), dv.to(q.dtype), None, None
-
-
-class _FlashAttnBHND(torch.autograd.Function):
-    """The same operator on (B, H, N, d): what the reference's module calls after its permute + contiguous copies."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, causal):
-        guard = device_ops.new_guard(q)
-        o, l, _ = device_ops.flash_attn_fwd(q, k, v, causal, _lib.FA_VARIANT_FA2, guard=guard, produce_guard=True)
-        none = torch.empty(0, device=q.device)
-        ctx.save_for_backward(q, k, v, o, l, guard if guard is not None else none)
-        ctx.causal = causal
-        return o
-
-    @staticmethod
-    def backward(ctx, out_grad):
-        q, k, v, o, l, guard = ctx.saved_tensors
-        dq, dk, dv = device_ops.flash_attn_bwd(q, k, v, o, out_grad.to(q.dtype).contiguous(), l, None, ctx.causal,
-                                               _lib.FA_VARIANT_FA2, guard=guard if guard.numel() else None)
-        return dq.to(q.dtype), dk.to(q.dtype), dv.to(q.dtype), None
+def _attention(q, k, v, causal, layout, softmax_scale=None):
+    """flash_attn2 with autograd (``q.flash_attn2(kT, v, self.causal)``, modules_transfomer.py:119-120)."""
+    return device_ops._FlashAttnFn.apply(q, k, v, causal, _lib.FA_VARIANT_FA2, layout, softmax_scale)
 
 
 LOG2E = 1.4426950408889634
@@ -76,25 +38,13 @@ def multi_head_attention(x, wq, wk, wv, wo, n_head: int, causal: bool = True, fu
     with softmax_scale = ln 2 -- the same function of x, but the bf16 MFMA-slot kernels' folded scale is then exactly 1: no extra
     operand rounding whatever the magnitude of the activations (DESIGN.md section 3 "Scaling")."""
     B, N, E = x.shape
-    d = E // n_head
-    x2 = x.reshape(B * N, E)
-    if fused_layout and fold_scale:
-        q = (x2 @ (wq * (LOG2E / d ** 0.5))).view(B, N, n_head, d)
-        k = (x2 @ wk).view(B, N, n_head, d)
-        v = (x2 @ wv).view(B, N, n_head, d)
-        o = _FlashAttnBNHD.apply(q, k, v, causal, LN2)
-        merged = o.reshape(B * N, E)
-    elif fused_layout:
-        q = (x2 @ wq).view(B, N, n_head, d)
-        k = (x2 @ wk).view(B, N, n_head, d)
-        v = (x2 @ wv).view(B, N, n_head, d)
-        o = _FlashAttnBNHD.apply(q, k, v, causal)                     # (B, N, H, d) fp32: already merged
+    if fused_layout:
+        q, k, v = _project(x, wq * (LOG2E / (E // n_head) ** 0.5) if fold_scale else wq, wk, wv, n_head)
+        o = _attention(q, k, v, causal, _lib.FA_LAYOUT_BNHD, LN2 if fold_scale else None)   # (B, N, H, d) fp32: already merged
         merged = o.reshape(B * N, E)
     else:
-        q = (x2 @ wq).view(B, N, n_head, d).permute(0, 2, 1, 3).contiguous()
-        k = (x2 @ wk).view(B, N, n_head, d).permute(0, 2, 1, 3).contiguous()
-        v = (x2 @ wv).view(B, N, n_head, d).permute(0, 2, 1, 3).contiguous()
-        o = _FlashAttnBHND.apply(q, k, v, causal)                     # (B, H, N, d)
+        q, k, v = (t.permute(0, 2, 1, 3).contiguous() for t in _project(x, wq, wk, wv, n_head))
+        o = _attention(q, k, v, causal, _lib.FA_LAYOUT_BHND)                                  # (B, H, N, d)
         merged = o.permute(0, 2, 1, 3).contiguous().view(B * N, E)
     return (merged.to(x.dtype) @ wo).view(B, N, E)
 
@@ -122,7 +72,7 @@ class KVCache:
     int32 (B,), the valid rows per batch element (read by the decode kernels, never by the host)."""
 
     def __init__(self, n_layers, B, capacity, n_head, head_dim, dtype, device):
-        self.head_dim, self.dp = head_dim, device_ops._padded_d(head_dim)
+        self.head_dim, self.dp = head_dim, device_ops.padded_head_dim(head_dim)
         self.capacity, self.n_head = capacity, n_head
         shape = (B, capacity, n_head, self.dp)
         self.k = [torch.zeros(shape, dtype=dtype, device=device) for _ in range(n_layers)]
@@ -138,7 +88,7 @@ class KVCache:
         return self._workspaces[key]
 
     def _pad(self, t):
-        return t if self.dp == self.head_dim else device_ops._pad_cols(t, self.dp)
+        return t if self.dp == self.head_dim else device_ops.pad_head_dim(t, self.dp)
 
 
 def _project(x, wq, wk, wv, n_head):
