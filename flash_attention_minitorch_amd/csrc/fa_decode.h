@@ -1,18 +1,26 @@
-// KV-cache decode attention for MI355X (gfx950): Nq = 1..128 new queries against a cache of up to Ncap keys per (batch, head), with
+// KV-cache decode attention for MI355X (gfx950): Nq = 1..128 new queries against a cache of up to Ncap keys per (batch, kv head), with
 // per-batch valid lengths on the device.  Declared in include/flash_attn_mi355x_decode.h, dispatched by fa_decode.hip; the training
 // kernels (fa_kernels.h) are not part of this unit.
 //
-// Split kernel: a workgroup = one (batch*head, key chunk, 32-query block).  Its four waves stage 128-key super tiles of K and V through
+// Grouped-query heads: the cache holds Hkv heads and q holds H = G * Hkv; query head h reads kv head h / G.  The G * Nq (query, head)
+// pairs of one kv head are the ROWS of that head, row rho = i * G + g for query i and head hkv * G + g, so the G heads of a group fill
+// the 32-row MFMA tile that a single query leaves empty and share one pass over the kv head's K and V.  Query-major order keeps the
+// causal positions of a block compact (row rho sits at len - Nq + rho / G), and in [B][Nq][H][d] a block's rows are contiguous.
+// G = 1 is the ungrouped call: rho = i.
+//
+// Split kernel: a workgroup = one (batch*kv head, key chunk, 32-row block).  Its four waves stage 128-key super tiles of K and V through
 // LDS together (register staging: the next super tile's loads are in flight under this one's products) and each wave takes 32 keys of
-// the super tile: S^T = K Q^T with the QUERY on the lane, the online softmax of fwd_splitk_f32_kernel, O^T += V^T P^T from registers.
+// the super tile: S^T = K Q^T with the ROW on the lane, the online softmax of fwd_splitk_f32_kernel, O^T += V^T P^T from registers.
 // At the end the four partial (O, m, l) meet in LDS and wave 0 combines them in wave order.  The result is either final (one split:
 // out and lse written directly) or one fp32 partial (unnormalised O, m, l) per row in the workspace.
-// Combine kernel: one workgroup per (batch*head, row) reduces the partials of its row in a fixed order (no atomics: bitwise
+// Output, lse and the partials are indexed by QUERY head and query row, whatever G.
+// Combine kernel: one workgroup per (batch*head, query row) reduces the partials of its row in a fixed order (no atomics: bitwise
 // repeatable).
 //
-// Bounds: every K / V / Q load goes through a buffer resource of its (batch, head) sized to the valid rows (len_b clamped to [0, Ncap]
-// for the cache, Nq for q), with the row offset in the per-lane voffset, so rows at or past len_b read as zero in hardware: whatever
-// they hold (NaN included) reaches neither a score nor the P.V product, and no load goes past row Ncap - 1.
+// Bounds: every K / V load goes through a buffer resource of its (batch, kv head) sized to the valid rows (len_b clamped to
+// [0, Ncap]), with the row offset in the per-lane voffset, so rows at or past len_b read as zero in hardware: whatever they hold (NaN
+// included) reaches neither a score nor the P.V product, and no load goes past row Ncap - 1.  Q goes through a resource of its batch
+// element with (head, query) in the voffset; rows rho >= G * Nq get the resource's size as their offset, read as zero and store nothing.
 #pragma once
 #include "fa_common.h"
 
@@ -29,8 +37,9 @@ struct DecodeArgs {
   float* part_o;       // [BH][nsplit][Nq][D] unnormalised partial O (nsplit > 1)
   float* part_ml;      // [BH][nsplit][Nq][2] partial (m, l), m in raw score units
   const int* seqlens;  // [B] or null (= Ncap)
-  int H, Nq, Ncap, nsplit, chunk, nqb, items;
-  int q_ld, kv_ld;     // elements between consecutive rows of one head (D or H*D)
+  int H, Hkv, G, Nq, Ncap, nsplit, chunk, nqb, items;   // H = G * Hkv query heads; nqb row blocks per kv head; items = B * Hkv * nsplit
+  float inv_G;         // 1.0f / G (row_query)
+  int q_ld, kv_ld;     // elements between consecutive rows of one head (D or H*D for q, D or Hkv*D for the cache)
   long q_bstride, q_hstride, kv_bstride, kv_hstride;
   int causal;
   float tau;
@@ -39,6 +48,15 @@ struct DecodeArgs {
 FA_DEV int clamp_len(const DecodeArgs& a, int b) {
   const int len = a.seqlens ? a.seqlens[b] : a.Ncap;
   return min(max(len, 0), a.Ncap);
+}
+
+// rho / G for a row index 0 <= rho < 2^25 without the integer division's long dependent chain in front of the workgroup's first
+// loads: the float quotient is off by at most one, which the remainder corrects.  (G = 1: exact at once.)
+FA_DEV int row_query(const DecodeArgs& a, int rho) {
+  int qi = (int)(((float)rho + 0.5f) * a.inv_G);
+  const int rem = rho - qi * a.G;
+  qi += (rem >= a.G) - (rem < 0);
+  return qi;
 }
 
 // Row n of the loader's matrix at byte voffset n*ldb: TileStager's (row, chunk) map and LDS image, with the tile's row offset added to
@@ -53,7 +71,9 @@ template <typename S> FA_DEV void load_rows(S& st, rsrc_t rs, int row0) {
   }
 }
 
-template <typename T, int D>
+// GROUPED = false is the G = 1 build: rho = i with no row arithmetic in front of the workgroup's first loads (a workgroup lives for a
+// few super tiles, so its prologue is not free: DESIGN.md "Decode").
+template <typename T, int D, bool GROUPED>
 __global__ void __launch_bounds__(256) decode_split_kernel(DecodeArgs a) {
   using A = Atom<T>;
   typedef typename A::frag frag;
@@ -65,19 +85,22 @@ __global__ void __launch_bounds__(256) decode_split_kernel(DecodeArgs a) {
   lds_char* tk = (lds_char*)smem_raw;
   lds_char* tv = tk + TB;
 
-  // workgroup -> (item = bh * nsplit + split, query block): the query blocks of one item are 8 workgroup ids apart, so they share an
-  // XCD's L2 under round-robin dispatch and the chunk is fetched from HBM once (speed only)
+  // workgroup -> (item = (b * Hkv + kv head) * nsplit + split, row block): the row blocks of one item are 8 workgroup ids apart, so
+  // they share an XCD's L2 under round-robin dispatch and the chunk is fetched from HBM once (speed only)
   const int id = blockIdx.x, slot = id >> 3;
   const int qb = slot % a.nqb, item = (slot / a.nqb) * 8 + (id & 7);
   if (item >= a.items) return;
   const int bh = item / a.nsplit, split = item - bh * a.nsplit;
-  const int b = bh / a.H, hd = bh - b * a.H;
+  const int b = bh / a.Hkv, hkv = bh - b * a.Hkv;
   const int len = __builtin_amdgcn_readfirstlane(clamp_len(a, b));
   const int c0 = split * a.chunk, c1 = min(c0 + a.chunk, len);
 
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int q0 = qb * 32, qrow = q0 + r;
+  // the lane's row rho = qi * G + g: query qi of head hd = hkv * G + g
+  const int G = GROUPED ? a.G : 1;
+  const int q0 = qb * 32, rho = q0 + r, qi = GROUPED ? row_query(a, rho) : rho, hd = hkv * G + (rho - qi * G);
+  const bool live = rho < G * a.Nq;
   const float c = a.tau * LOG2E;
 
   f32x16 acc_o[DT];
@@ -86,25 +109,28 @@ __global__ void __launch_bounds__(256) decode_split_kernel(DecodeArgs a) {
   float m_run = -INFINITY, l_run = 0.f;
 
   if (c0 < c1) {   // (a chunk wholly past len_b loads nothing and leaves the empty partial m = -inf, l = 0)
-    const T* qh = reinterpret_cast<const T*>(a.q) + (size_t)b * a.q_bstride + (size_t)hd * a.q_hstride;
-    const size_t kvoff = (size_t)b * a.kv_bstride + (size_t)hd * a.kv_hstride;
+    const size_t kvoff = (size_t)b * a.kv_bstride + (size_t)hkv * a.kv_hstride;
     const uint32_t esz = sizeof(T);
-    const rsrc_t qrs = make_rsrc(qh, ((uint32_t)(a.Nq - 1) * a.q_ld + D) * esz);
+    const uint32_t q_bytes = (uint32_t)a.q_bstride * esz;
+    const rsrc_t qrs = make_rsrc(reinterpret_cast<const T*>(a.q) + (size_t)b * a.q_bstride, q_bytes);
     const uint32_t kv_bytes = ((uint32_t)(len - 1) * a.kv_ld + D) * esz;
     const rsrc_t krs = make_rsrc(reinterpret_cast<const T*>(a.k) + kvoff, kv_bytes);
     const rsrc_t vrs = make_rsrc(reinterpret_cast<const T*>(a.v) + kvoff, kv_bytes);
 
     frag qf[KC];
+    const int qoff = live ? (hd * (int)a.q_hstride + qi * a.q_ld + 8 * h) * (int)esz : (int)q_bytes;
 #pragma unroll
-    for (int kc = 0; kc < KC; ++kc) qf[kc] = load_frag_buf<T>(qrs, (qrow * a.q_ld + 16 * kc + 8 * h) * (int)esz);
+    for (int kc = 0; kc < KC; ++kc) qf[kc] = load_frag_buf<T>(qrs, qoff + 16 * kc * (int)esz);
 
     const LaneAddr ra = A::template row_addr<D>(lane);
     const LaneAddr ta = A::template tr_addr<D>(lane);
     TileStager<T, D, DEC_ROWS, 256> sk, sv;
     sk.init(tid, a.kv_ld);
     sv.init(tid, a.kv_ld);
-    // causal: query i sits at position len - Nq + i and sees keys j <= len - Nq + i (bottom-right aligned)
-    const int qpos0 = len - a.Nq + q0;
+    // causal: query i sits at position len - Nq + i and sees keys j <= len - Nq + i (bottom-right aligned); the block's rows span
+    // the positions pos_lo .. pos_hi (wave-uniform; pos_hi may count rows past G * Nq, which only keeps a tile that masks to nothing)
+    const int qpos = len - a.Nq + qi;
+    const int pos_lo = len - a.Nq + (GROUPED ? row_query(a, q0) : q0), pos_hi = len - a.Nq + (GROUPED ? row_query(a, q0 + 31) : q0 + 31);
     load_rows(sk, krs, c0);
     load_rows(sv, vrs, c0);
     for (int t0 = c0; t0 < c1; t0 += DEC_ROWS) {
@@ -117,15 +143,15 @@ __global__ void __launch_bounds__(256) decode_split_kernel(DecodeArgs a) {
       }
       __syncthreads();
       const int kbase = t0 + 32 * w;
-      if (kbase >= c1 || (a.causal && kbase > qpos0 + 31)) continue;   // wave-uniform: no admissible key in the wave's 32
+      if (kbase >= c1 || (a.causal && kbase > pos_hi)) continue;   // wave-uniform: no admissible key in the wave's 32
       f32x16 s = zero16();
 #pragma unroll
       for (int kc = 0; kc < KC; ++kc) A::mma(s, A::template row_frag<D>(tk, ra, 32 * w, kc), qf[kc]);
-      if (kbase + 32 > c1 || (a.causal && kbase + 31 > qpos0)) {   // wave-uniform
+      if (kbase + 32 > c1 || (a.causal && kbase + 31 > pos_lo)) {   // wave-uniform
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
           const int key = kbase + acc_row(i, h);
-          if (key >= c1 || (a.causal && key > qpos0 + r)) s[i] = -INFINITY;
+          if (key >= c1 || (a.causal && key > qpos)) s[i] = -INFINITY;
         }
       }
       float mx = s[0];
@@ -197,11 +223,11 @@ __global__ void __launch_bounds__(256) decode_split_kernel(DecodeArgs a) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) acc_o[dt][i] += *FA_LDS(float, pu + (16 * dt + i) * 4) * wgt;
   }
-  if (qrow >= a.Nq) return;
-  const size_t ri = (size_t)bh * a.Nq + qrow;
+  if (!live) return;
+  const size_t bhq = (size_t)b * a.H + hd;
   if (a.nsplit == 1) {   // final: out = O / l, lse = m * tau + ln l; a row without an admissible key: out = 0, lse = -inf
     const float inv = (l_tot > 0.f) ? 1.0f / l_tot : 0.f;
-    float* orow = a.out + (size_t)b * a.q_bstride + (size_t)hd * a.q_hstride + (size_t)qrow * a.q_ld;
+    float* orow = a.out + (size_t)b * a.q_bstride + (size_t)hd * a.q_hstride + (size_t)qi * a.q_ld;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
@@ -209,9 +235,9 @@ __global__ void __launch_bounds__(256) decode_split_kernel(DecodeArgs a) {
         f32x4 val = {acc_o[dt][4 * g] * inv, acc_o[dt][4 * g + 1] * inv, acc_o[dt][4 * g + 2] * inv, acc_o[dt][4 * g + 3] * inv};
         *reinterpret_cast<f32x4*>(orow + 32 * dt + 8 * g + 4 * h) = val;
       }
-    if (h == 0 && a.lse) a.lse[ri] = (l_tot > 0.f) ? m_all * a.tau + __logf(l_tot) : -INFINITY;
+    if (h == 0 && a.lse) a.lse[bhq * a.Nq + qi] = (l_tot > 0.f) ? m_all * a.tau + __logf(l_tot) : -INFINITY;
   } else {
-    const size_t pr = ((size_t)bh * a.nsplit + split) * a.Nq + qrow;
+    const size_t pr = (bhq * a.nsplit + split) * a.Nq + qi;
     float* prow = a.part_o + pr * D;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt)

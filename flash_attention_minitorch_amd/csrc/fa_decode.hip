@@ -20,33 +20,42 @@ int set_err(int code, const char* what, hipError_t e = hipSuccess) {
   return code;
 }
 
-// Split policy (DESIGN.md "Decode"): enough (batch*head, chunk, query block) workgroups to cover a 256-CU chip four times, chunks a
-// multiple of 256 keys (two super tiles) and at least 256 keys.  Launches that already have 1024 workgroups without splitting run as
-// one split.  The chip size is assumed, not queried, so the split count is a function of the arguments alone.
+// Split policy (DESIGN.md "Decode"): enough (batch*kv head, chunk, row block) workgroups to cover a 256-CU chip four times, chunks a
+// multiple of 256 keys (two super tiles) and at least 256 keys.  A kv head has G*Nq rows (G = H / Hkv query heads per kv head), 32 to
+// a block.  Launches that already have 1024 workgroups without splitting run as one split.  The chip size is assumed, not queried,
+// so the split count is a function of the arguments alone.
 constexpr int DEC_CUS = 256, DEC_WAVES = 4, DEC_MIN_CHUNK = 256;
 
-bool sizes_ok(int B, int H, int Nq, int Ncap, int d) { return B > 0 && H > 0 && Nq > 0 && Ncap > 0 && d > 0; }
+// (positive sizes and H a multiple of Hkv: what the two size queries need to answer at all)
+bool sizes_ok(int B, int H, int Hkv, int Nq, int Ncap, int d) {
+  return B > 0 && H > 0 && Hkv > 0 && Nq > 0 && Ncap > 0 && d > 0 && H % Hkv == 0;
+}
 
-int chunk_keys(int B, int H, int Nq, int Ncap) {
-  const long groups = (long)B * H * ((Nq + 31) / 32);
+int row_blocks(int H, int Hkv, int Nq) { return (int)(((long)(H / Hkv) * Nq + 31) / 32); }
+
+int chunk_keys(int B, int H, int Hkv, int Nq, int Ncap) {
+  const long groups = (long)B * Hkv * row_blocks(H, Hkv, Nq);
   const long want = std::max(1L, (DEC_CUS * DEC_WAVES + groups - 1) / groups);
   const long per = (Ncap + want - 1) / want;
   return (int)std::max((long)DEC_MIN_CHUNK, (per + DEC_MIN_CHUNK - 1) / DEC_MIN_CHUNK * DEC_MIN_CHUNK);
 }
 
-int splits(int B, int H, int Nq, int Ncap) {
-  const int ch = chunk_keys(B, H, Nq, Ncap);
+int splits(int B, int H, int Hkv, int Nq, int Ncap) {
+  const int ch = chunk_keys(B, H, Hkv, Nq, Ncap);
   return (int)(((long)Ncap + ch - 1) / ch);
 }
 
-size_t workspace_bytes(int B, int H, int Nq, int Ncap, int d) {
-  const int ns = splits(B, H, Nq, Ncap);
+size_t workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int d) {
+  const int ns = splits(B, H, Hkv, Nq, Ncap);
   return ns == 1 ? 0 : (size_t)B * H * ns * Nq * (size_t)(d + 2) * sizeof(float);
 }
 
 template <typename T, int D> int launch(fa::DecodeArgs a, int BH, hipStream_t st) {
   const int grid = ((a.items + 7) / 8) * 8 * a.nqb;
-  hipLaunchKernelGGL((fa::decode_split_kernel<T, D>), dim3(grid), dim3(256), 0, st, a);
+  if (a.G > 1)
+    hipLaunchKernelGGL((fa::decode_split_kernel<T, D, true>), dim3(grid), dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL((fa::decode_split_kernel<T, D, false>), dim3(grid), dim3(256), 0, st, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return set_err(FA_ERR_HIP, "decode_split_kernel launch", e);
   if (a.nsplit > 1) {
@@ -69,22 +78,27 @@ template <typename T> int launch_d(const fa::DecodeArgs& a, int BH, int d, hipSt
 
 extern "C" {
 
-size_t fa_mi355x_decode_workspace_bytes(int B, int H, int Nq, int Ncap, int d) {
-  if (!sizes_ok(B, H, Nq, Ncap, d)) return 0;
-  return workspace_bytes(B, H, Nq, Ncap, d);
+size_t fa_mi355x_decode_workspace_bytes_gqa(int B, int H, int Hkv, int Nq, int Ncap, int d) {
+  if (!sizes_ok(B, H, Hkv, Nq, Ncap, d)) return 0;
+  return workspace_bytes(B, H, Hkv, Nq, Ncap, d);
 }
 
-int fa_mi355x_decode_splits(int B, int H, int Nq, int Ncap, int d, int dtype) {
+int fa_mi355x_decode_splits_gqa(int B, int H, int Hkv, int Nq, int Ncap, int d, int dtype) {
   (void)dtype;
-  if (!sizes_ok(B, H, Nq, Ncap, d)) return 0;
-  return splits(B, H, Nq, Ncap);
+  if (!sizes_ok(B, H, Hkv, Nq, Ncap, d)) return 0;
+  return splits(B, H, Hkv, Nq, Ncap);
 }
 
-int fa_mi355x_fwd_decode(const void* q, const void* k_cache, const void* v_cache, float* out, float* lse, const int* cache_seqlens,
-                         void* workspace, int B, int H, int Nq, int Ncap, int d, int layout, float softmax_scale, int causal,
-                         int dtype, void* stream) {
+int fa_mi355x_fwd_decode_gqa(const void* q, const void* k_cache, const void* v_cache, float* out, float* lse, const int* cache_seqlens,
+                             void* workspace, int B, int H, int Hkv, int Nq, int Ncap, int d, int layout, float softmax_scale,
+                             int causal, int dtype, void* stream) {
   g_err[0] = 0;
-  if (!sizes_ok(B, H, Nq, Ncap, d)) return set_err(FA_ERR_BAD_ARG, "B, H, Nq, Ncap and d must be positive");
+  if (B <= 0 || H <= 0 || Nq <= 0 || Ncap <= 0 || d <= 0) return set_err(FA_ERR_BAD_ARG, "B, H, Nq, Ncap and d must be positive");
+  if (Hkv <= 0) return set_err(FA_ERR_BAD_ARG, "Hkv must be positive");
+  if (H % Hkv != 0) {
+    snprintf(g_err, sizeof(g_err), "H = %d query heads must be a multiple of Hkv = %d cache heads", H, Hkv);
+    return FA_ERR_BAD_ARG;
+  }
   if (Nq > FA_DECODE_MAX_NQ)
     return set_err(FA_ERR_BAD_ARG, "Nq > 128 is prefill: use fa_mi355x_fwd_layout or fa_mi355x_fwd_scaled (the forward entry points)");
   if (dtype != FA_DTYPE_F32 && dtype != FA_DTYPE_BF16) return set_err(FA_ERR_BAD_ARG, "unknown dtype");
@@ -95,9 +109,11 @@ int fa_mi355x_fwd_decode(const void* q, const void* k_cache, const void* v_cache
   if (softmax_scale != 0.f && (!(softmax_scale > 0.f) || !std::isfinite(softmax_scale)))
     return set_err(FA_ERR_BAD_ARG, "softmax_scale must be positive and finite (0: 1/sqrt(d))");
   const long esz = dtype == FA_DTYPE_BF16 ? 2 : 4;
-  // (a buffer load's row offset is a 32-bit byte count: one batch element, plus a super tile of rows past its end, stays under 2 GiB)
-  if (((long)Ncap + fa::DEC_ROWS) * H * d * esz >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "one batch element of the cache must stay under 2 GiB");
-  const int ns = splits(B, H, Nq, Ncap);
+  // (a buffer load's row offset is a 32-bit byte count: one batch element, plus a super tile of rows past its end, stays under 2 GiB;
+  // q's (head, query) offset within its batch element likewise)
+  if (((long)Ncap + fa::DEC_ROWS) * Hkv * d * esz >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "one batch element of the cache must stay under 2 GiB");
+  if ((long)Nq * H * d * esz >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "one batch element of q must stay under 2 GiB");
+  const int ns = splits(B, H, Hkv, Nq, Ncap);
   if (ns > 1 && !workspace) return set_err(FA_ERR_BAD_ARG, "null workspace: this call needs fa_mi355x_decode_workspace_bytes() bytes");
 
   fa::DecodeArgs a;
@@ -110,23 +126,42 @@ int fa_mi355x_fwd_decode(const void* q, const void* k_cache, const void* v_cache
   a.part_ml = ns > 1 ? a.part_o + (size_t)B * H * ns * Nq * d : nullptr;
   a.seqlens = cache_seqlens;
   a.H = H;
+  a.Hkv = Hkv;
+  a.G = H / Hkv;
+  a.inv_G = 1.0f / (float)a.G;
   a.Nq = Nq;
   a.Ncap = Ncap;
   a.nsplit = ns;
-  a.chunk = chunk_keys(B, H, Nq, Ncap);
-  a.nqb = (Nq + 31) / 32;
-  a.items = B * H * ns;
+  a.chunk = chunk_keys(B, H, Hkv, Nq, Ncap);
+  a.nqb = row_blocks(H, Hkv, Nq);
+  a.items = B * Hkv * ns;
   const bool bnhd = layout == FA_LAYOUT_BNHD;
   a.q_ld = bnhd ? H * d : d;
-  a.kv_ld = a.q_ld;
+  a.kv_ld = bnhd ? Hkv * d : d;
   a.q_bstride = (long)Nq * H * d;
-  a.kv_bstride = (long)Ncap * H * d;
+  a.kv_bstride = (long)Ncap * Hkv * d;
   a.q_hstride = bnhd ? d : (long)Nq * d;
   a.kv_hstride = bnhd ? d : (long)Ncap * d;
   a.causal = causal ? 1 : 0;
   a.tau = softmax_scale > 0.f ? softmax_scale : sqrtf(1.0f / (float)d);
   hipStream_t st = static_cast<hipStream_t>(stream);
   return dtype == FA_DTYPE_BF16 ? launch_d<fa::bf16_t>(a, B * H, d, st) : launch_d<float>(a, B * H, d, st);
+}
+
+// The ungrouped entry points: Hkv = H.
+size_t fa_mi355x_decode_workspace_bytes(int B, int H, int Nq, int Ncap, int d) {
+  return fa_mi355x_decode_workspace_bytes_gqa(B, H, H, Nq, Ncap, d);
+}
+
+int fa_mi355x_decode_splits(int B, int H, int Nq, int Ncap, int d, int dtype) {
+  return fa_mi355x_decode_splits_gqa(B, H, H, Nq, Ncap, d, dtype);
+}
+
+int fa_mi355x_fwd_decode(const void* q, const void* k_cache, const void* v_cache, float* out, float* lse, const int* cache_seqlens,
+                         void* workspace, int B, int H, int Nq, int Ncap, int d, int layout, float softmax_scale, int causal,
+                         int dtype, void* stream) {
+  return fa_mi355x_fwd_decode_gqa(q, k_cache, v_cache, out, lse, cache_seqlens, workspace, B, H, H, Nq, Ncap, d, layout, softmax_scale,
+                                  causal, dtype, stream);
 }
 
 const char* fa_mi355x_decode_last_error(void) { return g_err; }

@@ -419,31 +419,40 @@ _DECODE_LAYOUTS = {"bnhd": _lib.FA_LAYOUT_BNHD, "bhnd": _lib.FA_LAYOUT_BHND}
 
 
 def _decode_dims(q, k_cache, layout):
-    """(B, H, Nq, Ncap, dq, dp) of a decode call: q (B, Nq, H, dq) / cache (B, Ncap, H, dp) for "bnhd", (B, H, Nq, dq) / (B, H, Ncap, dp)
-    for "bhnd"."""
+    """(B, H, Hkv, Nq, Ncap, dq, dp) of a decode call: q (B, Nq, H, dq) / cache (B, Ncap, Hkv, dp) for "bnhd", (B, H, Nq, dq) /
+    (B, Hkv, Ncap, dp) for "bhnd"; H a multiple of Hkv (grouped-query heads: query head h reads cache head h // (H // Hkv))."""
     if q.dim() != 4 or k_cache.dim() != 4:
         raise ValueError("decode expects 4-d q and caches")
     if layout == "bnhd":
-        (B, Nq, H, dq), (Bc, Ncap, Hc, dp) = q.shape, k_cache.shape
+        (B, Nq, H, dq), (Bc, Ncap, Hkv, dp) = q.shape, k_cache.shape
     else:
-        (B, H, Nq, dq), (Bc, Hc, Ncap, dp) = q.shape, k_cache.shape
-    if (B, H) != (Bc, Hc):
-        raise ValueError(f"q and the cache disagree on (B, H): {(B, H)} vs {(Bc, Hc)}")
-    return B, H, Nq, Ncap, dq, dp
+        (B, H, Nq, dq), (Bc, Hkv, Ncap, dp) = q.shape, k_cache.shape
+    if B != Bc or Hkv <= 0 or H % Hkv:
+        raise ValueError(f"q and the cache disagree on (B, H): {(B, H)} vs {(Bc, Hkv)} (the cache's heads must divide q's)")
+    return B, H, Hkv, Nq, Ncap, dq, dp
+
+
+def _decode_workspace_bytes(B, H, Hkv, Nq, Ncap, dp):
+    lib = _lib.decode()
+    if Hkv == H:
+        return lib.fa_mi355x_decode_workspace_bytes(B, H, Nq, Ncap, dp)
+    return lib.fa_mi355x_decode_workspace_bytes_gqa(B, H, Hkv, Nq, Ncap, dp)
 
 
 def decode_workspace(q, k_cache, layout="bnhd"):
     """Scratch for flash_attn_decode with these tensors (fa_mi355x_decode_workspace_bytes; one partial O, m, l per query row and key
     chunk), or None when the call runs as one split and needs none.  A pure function of the shapes: allocate once, reuse every step."""
-    B, H, Nq, Ncap, _, dp = _decode_dims(q, k_cache, layout)
-    nbytes = _lib.decode().fa_mi355x_decode_workspace_bytes(B, H, Nq, Ncap, dp)
+    B, H, Hkv, Nq, Ncap, _, dp = _decode_dims(q, k_cache, layout)
+    nbytes = _decode_workspace_bytes(B, H, Hkv, Nq, Ncap, dp)
     return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=q.device) if nbytes else None
 
 
 def flash_attn_decode(q, k_cache, v_cache, cache_seqlens=None, causal=True, softmax_scale=None, layout="bnhd", out=None, lse=None,
                       workspace=None):
-    """Attention of Nq <= 128 new queries against a KV cache (fa_mi355x_fwd_decode, include/flash_attn_mi355x_decode.h).
-    ``layout`` "bnhd": q (B, Nq, H, d), caches (B, Ncap, H, dp); "bhnd": q (B, H, Nq, d), caches (B, H, Ncap, dp).  dp in {32, 64, 128};
+    """Attention of Nq <= 128 new queries against a KV cache (fa_mi355x_fwd_decode / _gqa, include/flash_attn_mi355x_decode.h).
+    ``layout`` "bnhd": q (B, Nq, H, d), caches (B, Ncap, Hkv, dp); "bhnd": q (B, H, Nq, d), caches (B, Hkv, Ncap, dp).  Hkv is the
+    cache's own head count and must divide H: Hkv < H is a grouped-query (Hkv = 1: multi-query) cache, query head h reads cache head
+    h // (H // Hkv), and the group's heads share one pass over it (no expansion of the cache).  dp in {32, 64, 128};
     a q with fewer columns (d < dp) is zero-padded to the cache's row length (the cache itself holds zero columns d .. dp-1) and the
     default scale is then 1/sqrt(d).  ``cache_seqlens``: int32 (B,) on q's device, the valid cache rows per batch element counting the
     new tokens (None: all Ncap); clamped to [0, Ncap] on the device, no host synchronisation.  ``causal``: the queries are the last Nq
@@ -455,7 +464,7 @@ def flash_attn_decode(q, k_cache, v_cache, cache_seqlens=None, causal=True, soft
         raise TypeError("q, k_cache and v_cache must share one dtype")
     if k_cache.shape != v_cache.shape:
         raise ValueError("k_cache and v_cache must have one shape")
-    B, H, Nq, Ncap, d, dp = _decode_dims(q, k_cache, layout)
+    B, H, Hkv, Nq, Ncap, d, dp = _decode_dims(q, k_cache, layout)
     if d > dp:
         raise ValueError(f"q's head dim {d} exceeds the cache's row length {dp}")
     if cache_seqlens is not None and (cache_seqlens.dtype != torch.int32 or tuple(cache_seqlens.shape) != (B,)
@@ -480,9 +489,10 @@ def flash_attn_decode(q, k_cache, v_cache, cache_seqlens=None, causal=True, soft
     lib = _lib.decode()
     if workspace is None:
         workspace = decode_workspace(qp, k_cache, layout)
-    elif workspace.numel() * workspace.element_size() < lib.fa_mi355x_decode_workspace_bytes(B, H, Nq, Ncap, dp):
+    elif workspace.numel() * workspace.element_size() < _decode_workspace_bytes(B, H, Hkv, Nq, Ncap, dp):
         raise ValueError("workspace too small: size it with decode_workspace()")
-    _lib.decode_check(lib.fa_mi355x_fwd_decode(_ptr(qp), _ptr(k_cache), _ptr(v_cache), _ptr(outp), _ptr(lse), _ptr(cache_seqlens),
-                                               _ptr(workspace), B, H, Nq, Ncap, dp, _DECODE_LAYOUTS[layout], float(softmax_scale),
-                                               int(bool(causal)), dtype, _stream_ptr()))
+    # (Hkv == H goes through the ungrouped entry points, which are the Hkv = H case of the _gqa ones inside the library)
+    fwd, heads = (lib.fa_mi355x_fwd_decode, (H,)) if Hkv == H else (lib.fa_mi355x_fwd_decode_gqa, (H, Hkv))
+    _lib.decode_check(fwd(_ptr(qp), _ptr(k_cache), _ptr(v_cache), _ptr(outp), _ptr(lse), _ptr(cache_seqlens), _ptr(workspace), B, *heads,
+                          Nq, Ncap, dp, _DECODE_LAYOUTS[layout], float(softmax_scale), int(bool(causal)), dtype, _stream_ptr()))
     return (_unpad(outp, d, out) if d < dp else outp), lse

@@ -30,20 +30,33 @@ LOG2E = 1.4426950408889634
 LN2 = 0.6931471805599453
 
 
+def _expand_kv(t, n_head):
+    """(B, N, Hkv, d) -> (B, N, n_head, d): every kv head repeated for the G = n_head // Hkv query heads that read it (one copy; under
+    autograd its backward sums the group's gradients).  The tensor itself when Hkv == n_head."""
+    B, N, Hkv, d = t.shape
+    if Hkv == n_head:
+        return t
+    return t[:, :, :, None, :].expand(B, N, Hkv, n_head // Hkv, d).reshape(B, N, n_head, d)
+
+
 def multi_head_attention(x, wq, wk, wv, wo, n_head: int, causal: bool = True, fused_layout: bool = True, fold_scale: bool = False):
-    """MultiHeadAttention.forward (modules_transfomer.py:141-157).  x: (B, N, E); wq, wk, wv, wo: (E, E) (bias-free, as the
-    reference's ``Linear(..., bias=False)`` projections, :40-52).  ``fused_layout=False`` reproduces the reference's four
-    permute + contiguous copies (for comparison); both give the same values.
+    """MultiHeadAttention.forward (modules_transfomer.py:141-157).  x: (B, N, E); wq, wo: (E, E); wk, wv: (E, E), or (E, Hkv * d) for
+    grouped-query heads (Hkv divides n_head, d = E // n_head; query head h reads kv head h // (n_head // Hkv)): k and v are then
+    expanded to n_head heads in front of the operator -- the function the generation path below is tested against, not a fused GQA
+    training path.  Bias-free, as the reference's ``Linear(..., bias=False)`` projections (:40-52).  ``fused_layout=False``
+    reproduces the reference's four permute + contiguous copies (for comparison); both give the same values.
     ``fold_scale`` (with ``fused_layout``): log2(e)/sqrt(d) is folded into the query projection's weights and the operator is called
     with softmax_scale = ln 2 -- the same function of x, but the bf16 MFMA-slot kernels' folded scale is then exactly 1: no extra
     operand rounding whatever the magnitude of the activations (DESIGN.md section 3 "Scaling")."""
     B, N, E = x.shape
     if fused_layout:
         q, k, v = _project(x, wq * (LOG2E / (E // n_head) ** 0.5) if fold_scale else wq, wk, wv, n_head)
+        k, v = _expand_kv(k, n_head), _expand_kv(v, n_head)
         o = _attention(q, k, v, causal, _lib.FA_LAYOUT_BNHD, LN2 if fold_scale else None)   # (B, N, H, d) fp32: already merged
         merged = o.reshape(B * N, E)
     else:
-        q, k, v = (t.permute(0, 2, 1, 3).contiguous() for t in _project(x, wq, wk, wv, n_head))
+        q, k, v = _project(x, wq, wk, wv, n_head)
+        q, k, v = (t.permute(0, 2, 1, 3).contiguous() for t in (q, _expand_kv(k, n_head), _expand_kv(v, n_head)))
         o = _attention(q, k, v, causal, _lib.FA_LAYOUT_BHND)                                  # (B, H, N, d)
         merged = o.permute(0, 2, 1, 3).contiguous().view(B * N, E)
     return (merged.to(x.dtype) @ wo).view(B, N, E)
@@ -67,14 +80,18 @@ MAX_STEP_TOKENS = 128   # fa_mi355x_fwd_decode's largest Nq; longer inputs are p
 
 
 class KVCache:
-    """Per-layer k and v caches of a causal attention stack: ``k[l]``, ``v[l]`` are (B, capacity, n_head, dp) in the projection's own
-    [B][N][H][d] layout (no permute), dp = head_dim rounded up to 32, 64 or 128 with zero columns past head_dim.  ``lengths``: device
-    int32 (B,), the valid rows per batch element (read by the decode kernels, never by the host)."""
+    """Per-layer k and v caches of a causal attention stack: ``k[l]``, ``v[l]`` are (B, capacity, n_kv_head, dp) in the projection's
+    own [B][N][H][d] layout (no permute), dp = head_dim rounded up to 32, 64 or 128 with zero columns past head_dim.  ``n_kv_head``
+    (default n_head) is the number of key/value heads of a grouped-query stack: it must divide n_head, and the cache holds only those.
+    ``lengths``: device int32 (B,), the valid rows per batch element (read by the decode kernels, never by the host)."""
 
-    def __init__(self, n_layers, B, capacity, n_head, head_dim, dtype, device):
+    def __init__(self, n_layers, B, capacity, n_head, head_dim, dtype, device, n_kv_head=None):
         self.head_dim, self.dp = head_dim, device_ops.padded_head_dim(head_dim)
         self.capacity, self.n_head = capacity, n_head
-        shape = (B, capacity, n_head, self.dp)
+        self.n_kv_head = n_head if n_kv_head is None else n_kv_head
+        if self.n_kv_head <= 0 or n_head % self.n_kv_head:
+            raise ValueError(f"n_kv_head = {n_kv_head} must divide n_head = {n_head}")
+        shape = (B, capacity, self.n_kv_head, self.dp)
         self.k = [torch.zeros(shape, dtype=dtype, device=device) for _ in range(n_layers)]
         self.v = [torch.zeros(shape, dtype=dtype, device=device) for _ in range(n_layers)]
         self.lengths = torch.zeros(B, dtype=torch.int32, device=device)
@@ -92,27 +109,40 @@ class KVCache:
 
 
 def _project(x, wq, wk, wv, n_head):
+    """q (B, N, n_head, d), k and v (B, N, Hkv, d) with d = E // n_head and Hkv read from wk's and wv's (E, Hkv * d) shape."""
     B, N, E = x.shape
     x2 = x.reshape(B * N, E)
-    return tuple((x2 @ w).view(B, N, n_head, E // n_head) for w in (wq, wk, wv))
+    d = E // n_head
+    if wk.shape != wv.shape or wk.shape[1] % d or n_head % max(wk.shape[1] // d, 1):
+        raise ValueError(f"wk and wv must both be (E, Hkv * {d}) with Hkv a divisor of n_head = {n_head}")
+    return tuple((x2 @ w).view(B, N, w.shape[1] // d, d) for w in (wq, wk, wv))
+
+
+def _check_kv_heads(k, cache):
+    if k.shape[2] != cache.n_kv_head:
+        raise ValueError(f"the layers project {k.shape[2]} kv heads, the cache holds {cache.n_kv_head}")
 
 
 def attention_stack_prefill(x, layers, n_head: int, cache: KVCache):
     """attention_stack(x, layers, n_head, causal=True) over a prompt x (B, P, E) that also (re)fills ``cache`` with every layer's k and
-    v of the P tokens (lengths = P).  Returns the stack's output (B, P, E)."""
+    v of the P tokens (lengths = P).  A grouped-query stack (wk, wv of shape (E, Hkv * d)) stores its Hkv heads; for the prompt's own
+    attention k and v are expanded to n_head heads (one copy each per layer) in front of the fused causal forward.  Returns the
+    stack's output (B, P, E)."""
     B, P, E = x.shape
     if P > cache.capacity:
         raise ValueError(f"prompt of {P} tokens exceeds the cache capacity {cache.capacity}")
     d = E // n_head
     for li, (wq, wk, wv, wo) in enumerate(layers):
         q, k, v = _project(x, wq, wk, wv, n_head)
+        _check_kv_heads(k, cache)
         kp, vp = cache._pad(k), cache._pad(v)
         cache.k[li][:, :P] = kp
         cache.v[li][:, :P] = vp
+        ke, ve = _expand_kv(kp, n_head), _expand_kv(vp, n_head)
         if cache.dp == d:
-            o, _, _ = device_ops.flash_attn_fwd_bnhd(q, k, v, True, _lib.FA_VARIANT_FA2)
+            o, _, _ = device_ops.flash_attn_fwd_bnhd(q, ke, ve, True, _lib.FA_VARIANT_FA2)
         else:   # zero columns add nothing to the scores; the scale keeps the caller's d
-            o, _, _ = device_ops.flash_attn_fwd_bnhd(cache._pad(q), kp, vp, True, _lib.FA_VARIANT_FA2, softmax_scale=d ** -0.5)
+            o, _, _ = device_ops.flash_attn_fwd_bnhd(cache._pad(q), ke, ve, True, _lib.FA_VARIANT_FA2, softmax_scale=d ** -0.5)
             o = o[..., :d]
         x = x + (o.reshape(B * P, E).to(x.dtype) @ wo).view(B, P, E)
     cache.lengths.fill_(P)
@@ -123,7 +153,8 @@ def attention_stack_prefill(x, layers, n_head: int, cache: KVCache):
 def attention_stack_step(x_new, layers, n_head: int, cache: KVCache):
     """One generation step of the stack: x_new (B, T, E), T <= 128 new tokens that follow each batch element's cached prefix.  Every
     layer projects them, appends k and v at rows lengths[b] .. lengths[b] + T - 1 (device indexing: no host synchronisation), and
-    attends causally to the cache with the decode kernels; lengths grow by T.  Returns the stack's output for the new tokens (B, T, E),
+    attends causally to the cache with the decode kernels (a grouped-query stack appends its Hkv heads and its n_head query heads
+    read them in place); lengths grow by T.  Returns the stack's output for the new tokens (B, T, E),
     the last T rows of attention_stack over the whole sequence."""
     B, T, E = x_new.shape
     if T > MAX_STEP_TOKENS:
@@ -131,15 +162,17 @@ def attention_stack_step(x_new, layers, n_head: int, cache: KVCache):
     if cache.length_bound + T > cache.capacity:
         raise ValueError(f"cache capacity {cache.capacity} exceeded")
     dev = x_new.device
-    # rows b * capacity + lengths[b] + t of the (B * capacity, H, dp) view of a layer's cache: the new tokens' k and v
+    # rows b * capacity + lengths[b] + t of the (B * capacity, Hkv, dp) view of a layer's cache: the new tokens' k and v
     rows = (cache.lengths.long() + torch.arange(B, device=dev) * cache.capacity)[:, None] + torch.arange(T, device=dev)
     rows = rows.reshape(B * T)
     new_len = cache.lengths + T
     x = x_new
     for li, (wq, wk, wv, wo) in enumerate(layers):
         q, k, v = _project(x, wq, wk, wv, n_head)
+        _check_kv_heads(k, cache)
+        hkv = cache.n_kv_head
         for dst, t in ((cache.k[li], k), (cache.v[li], v)):
-            dst.view(B * cache.capacity, n_head, cache.dp).index_copy_(0, rows, cache._pad(t).reshape(B * T, n_head, cache.dp))
+            dst.view(B * cache.capacity, hkv, cache.dp).index_copy_(0, rows, cache._pad(t).reshape(B * T, hkv, cache.dp))
         o, _ = device_ops.flash_attn_decode(q, cache.k[li], cache.v[li], new_len, causal=True, layout="bnhd",
                                             workspace=cache.workspace(q))
         x = x + (o.reshape(B * T, E).to(x.dtype) @ wo).view(B, T, E)

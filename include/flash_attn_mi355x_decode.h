@@ -56,6 +56,27 @@ int fa_mi355x_fwd_decode(const void* q, const void* k_cache, const void* v_cache
                          void* workspace, int B, int H, int Nq, int Ncap, int d, int layout, float softmax_scale, int causal,
                          int dtype, void* stream);
 
+/* Grouped-query (GQA) and multi-query (MQA) caches: q and out have H heads, the caches Hkv heads, H a multiple of Hkv, and query
+ * head h reads kv head h / G with G = H / Hkv (Hkv = 1: multi-query).
+ *
+ *   out[b,h,i,:] = softmax_j(scale * q[b,h,i,:] . k[b,h/G,j,:]) . v[b,h/G,j,:],   j < len_b
+ *
+ * The G heads of a group share one pass over their kv head's K and V: the G*Nq (query, head) pairs of a kv head are the rows of
+ * the kernel's 32-row tiles (row i*G + g: query i, head hkv*G + g), so a call reads B*Hkv*len*d elements of K and of V whatever G.
+ * The three functions below are the general form of the three above, with Hkv directly after H; the ones above are their Hkv = H
+ * case (the same code: identical splits, workspace and bits).  Everything said there holds here, with these differences:
+ *   k_cache, v_cache   [B][Hkv][Ncap][d] (FA_LAYOUT_BHND) or [B][Ncap][Hkv][d] (FA_LAYOUT_BNHD)
+ *   q, out, lse        H heads, as above: lse is [B][H][Nq]
+ *   workspace          fa_mi355x_decode_workspace_bytes_gqa(B, H, Hkv, Nq, Ncap, d) bytes: B*H*nsplit*Nq*(d + 2) floats or 0 (the
+ *                      partials are per QUERY head); the split policy counts B*Hkv*ceil(G*Nq/32) row blocks
+ *   Hkv <= 0, or H not a multiple of Hkv: FA_ERR_BAD_ARG (the size queries return 0).  The 2 GiB bound per batch element applies to
+ *   the cache with its Hkv heads, and to q. */
+size_t fa_mi355x_decode_workspace_bytes_gqa(int B, int H, int Hkv, int Nq, int Ncap, int d);
+int fa_mi355x_decode_splits_gqa(int B, int H, int Hkv, int Nq, int Ncap, int d, int dtype);
+int fa_mi355x_fwd_decode_gqa(const void* q, const void* k_cache, const void* v_cache, float* out, float* lse, const int* cache_seqlens,
+                             void* workspace, int B, int H, int Hkv, int Nq, int Ncap, int d, int layout, float softmax_scale,
+                             int causal, int dtype, void* stream);
+
 /* Message of the last FA_ERR_* of this library on this thread ("" if none). */
 const char* fa_mi355x_decode_last_error(void);
 
