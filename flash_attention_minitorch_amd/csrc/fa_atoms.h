@@ -244,6 +244,63 @@ FA_DEV void dma4(raw_rsrc_t rs, uint32_t lds_dst, int voff, int soff) {
 }
 FA_DEV void dma_wait_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
+// ---------------------------------------------------------------------------------------------
+// Stages of the LDS-DMA kernels: ROWS x D bf16 elements of a tensor (K, V, Q, dO) go global -> LDS in 1 KiB pieces, one
+// wave-instruction each, and are read back as row fragments and transposed fragments of 32-row sub-tiles.  Everything here is a
+// pure function of its arguments: the kernels keep what they computed (lane offset, slot addresses) in their own registers and
+// decide themselves when to issue, when to wait (dma_wait_all) and where the barrier that publishes a stage sits.
+// A piece is the image of one 8-row group (d = 64) or of half of one (d = 128: chunks 0-7 / 8-15 of its rows); wave w of NW moves
+// pieces w, w + NW, ...  LDS-DMA writes lane-linearly, so the image's chunk swizzle is applied to each lane's SOURCE address: the
+// 16 bytes that lane l of piece p fetches (FA_DMA_VOFF past row 8 * (p / PPG)) are the chunk that Atom::off places at byte
+// 1024 * p + 16 * l of the image -- dma_matches_image checks every lane of every piece, and every kernel asserts it on its own
+// geometry.  A wave's pieces share their group parity, hence ONE lane offset per wave.
+// ---------------------------------------------------------------------------------------------
+// Declares `name`: the byte offset of this lane's 16 bytes from the first element of its piece's 8-row group (ld: elements between
+// rows, esz: bytes per element).  A macro, not a function: the kernels need the expression in their own body (a helper is optimised
+// before it is inlined, without lane = tid & 63, and comes out as different code), and the check must read the very same text.
+#define FA_DMA_VOFF(name, PPG, lane, w, ld, esz)                              \
+  const int dma_row7 = ((lane) >> 2) & 7;                                     \
+  const int dma_gpar = ((PPG) == 1) ? ((w) & 1) : (((w) >> 1) & 1);           \
+  const int dma_half = ((PPG) == 1) ? 0 : ((w) & 1);                          \
+  const int name = dma_row7 * (ld) * (esz) +                                  \
+                   16 * (4 * (2 * dma_half + ((lane) >> 5)) + (((lane) & 3) ^ ((2 * dma_gpar + (dma_row7 >> 2)) & 3)))
+
+template <int D, int ROWS, int NW = 8>
+struct StageRing {
+  using A = Atom<bf16_t>;
+  typedef A::frag frag;
+  static constexpr int PPG = D / 64;                              // pieces per 8-row group
+  static constexpr int NPW = A::tile_bytes<D>(ROWS) / 1024 / NW;  // pieces per wave and tensor
+  static constexpr int SUBB = (D / 32) * 512 * 4;                 // bytes of one 32-row sub-tile inside a stage image
+  static_assert((D == 64 || D == 128) && A::tile_bytes<D>(ROWS) % (1024 * NW) == 0 && NW % 4 == 0,
+                "every wave moves whole pieces of one swizzle parity");
+  static constexpr bool dma_matches_image() {
+    constexpr int LDB = 1 << 16;   // a row stride wider than any row splits a source offset into (row, chunk)
+    for (int w = 0; w < NW; ++w)
+      for (int i = 0; i < NPW; ++i)
+        for (int lane = 0; lane < 64; ++lane) {
+          FA_DMA_VOFF(so, PPG, lane, w, LDB / A::ESZ, A::ESZ);
+          const int piece = w + NW * i, row = 8 * (piece / PPG) + so / LDB, ch = so % LDB / 16;
+          if (so % 16 != 0 || ch >= D / 8 || A::off<D>(row, ch) != 1024 * piece + 16 * lane) return false;
+        }
+    return true;
+  }
+  // Readers on a per-stage address register + immediate: b0 / b1 = the lane's row_addr / tr_addr phases + the stage's slot,
+  // toff = the tensor's offset.  row: k-chunk kc of the lane's row of sub-tile sub; tr: rows 16 * s2 .. + 15 of sub-tile sub at
+  // columns 32 * dt .. + 31, transposed (Atom::row_frag / tr_frag with every index a compile-time constant).
+  static FA_DEV frag row(lds_char* smem, int b0, int b1, int sub, int kc, int toff = 0) {
+    return *FA_LDS(frag, smem + ((kc & 1) ? b1 : b0) + toff + SUBB * sub + 512 * (kc >> 1));
+  }
+  static FA_DEV frag tr(lds_char* smem, int b0, int b1, int sub, int s2, int dt, int toff = 0) {
+    const int kk = toff + SUBB * sub + (D / 32) * 512 * (2 * s2) + 512 * dt;
+    bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(FA_LDS(bf16x4, smem + b0 + kk));
+    bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(FA_LDS(bf16x4, smem + b1 + kk + (D / 32) * 512));
+    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+  }
+};
+// byte offset of stage st's slot in a ring of R slots SLOTB bytes apart (roff: where stage 0 stands in the ring)
+template <int R, int SLOTB> FA_DEV constexpr int ring_slot(int st, int roff = 0) { return ((st + roff) % R) * SLOTB; }
+
 // Register-staged global -> LDS tile copy of ROWS x D elements by NT threads, split into an early issue (load)
 // and a late LDS write (store) so the HBM/L2 latency hides under the MFMA phase in between.
 template <typename T, int D, int ROWS, int NT> struct TileStager {

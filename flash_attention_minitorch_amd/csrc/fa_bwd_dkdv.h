@@ -125,8 +125,6 @@ bwd_dkdv_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
   // staging registers, no ds_write pass.  Otherwise (fp32's padded image, d = 32): registers, written after the MFMA phase.
   constexpr bool DMA = sizeof(T) == 2 && D >= 64;
   constexpr int PPG = D >= 128 ? 2 : 1;                          // pieces per 8-row group
-  constexpr int NP = QS * D * (int)sizeof(T) / 1024, NPW = DMA ? NP / NW : 0;
-  static_assert(!DMA || (NP % NW == 0 && NW % 4 == 0), "every wave moves whole pieces of one swizzle parity");
   TileStager<T, D, QS, NT> sq, sdo;
   if constexpr (!DMA) {
     sq.init(tid, ld);
@@ -134,16 +132,14 @@ bwd_dkdv_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
   }
   const raw_rsrc_t qraw = make_raw_rsrc(q + base, mat_bytes), doraw = make_raw_rsrc(dout + base, mat_bytes);
   const uint32_t smem_addr = (uint32_t)(uintptr_t)smem;
-  const int dma_row7 = (lane >> 2) & 7;
-  const int dma_gpar = (PPG == 1) ? (w & 1) : ((w >> 1) & 1);
-  const int dma_half = (PPG == 1) ? 0 : (w & 1);
-  const int dma_voff = dma_row7 * ld * (int)sizeof(T) +
-                       16 * (4 * (2 * dma_half + (lane >> 5)) + ((lane & 3) ^ ((2 * dma_gpar + (dma_row7 >> 2)) & 3)));
+  FA_DMA_VOFF(dma_voff, PPG, lane, w, ld, (int)sizeof(T));
   float st_nl = 0.f, st_de = 0.f;
   auto stage_load = [&](int qi, int dst /* LDS byte offset of the stage buffer */) {
     if constexpr (DMA) {
+      using RG = StageRing<D, QS, NW>;   // (fa_atoms.h)
+      static_assert(RG::PPG == PPG && RG::dma_matches_image(), "LDS-DMA source swizzle vs Atom::off");
 #pragma unroll
-      for (int i = 0; i < NPW; ++i) {
+      for (int i = 0; i < RG::NPW; ++i) {
         const int piece = w + NW * i, g = piece / PPG;
         const int soff = (qi * QS + 8 * g) * ld * (int)sizeof(T);
         dma16(qraw, smem_addr + dst + 1024 * piece, dma_voff, soff);
@@ -591,7 +587,8 @@ bwd_dkdv_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* 
   constexpr int KC = 4, QS = 128, NW = 8, KPW = 32, BK = NW * KPW;
   constexpr int TB = A::template tile_bytes<D>(QS);   // 16 KiB
   constexpr int BUF = 2 * TB + 8 * QS;                // Q tile, dO tile, QS x (-L/tau), QS x (-delta)
-  constexpr int SUBB = (D / 32) * 512 * 4;            // bytes of one 32-row sub-slice inside a tile image
+  using RG = StageRing<D, QS>;                        // DMA pieces and readers of a stage (fa_atoms.h)
+  static_assert(RG::dma_matches_image(), "LDS-DMA source swizzle vs Atom::off");
   __shared__ __attribute__((aligned(16))) char smem_raw[3 * BUF];
   lds_char* smem = (lds_char*)smem_raw;
 
@@ -648,8 +645,7 @@ bwd_dkdv_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* 
   const int nst = (N + QS - 1) / QS;
   const uint32_t smem_addr = (uint32_t)(uintptr_t)smem;
   // LDS-DMA: wave w moves pieces w and w + 8 (1 KiB = one 8-row group) of the Q and of the dO tile, waves 0-3 the row constants
-  const int dma_row7 = (lane >> 2) & 7;
-  const int dma_voff = dma_row7 * ld * (int)sizeof(T) + 16 * (4 * (lane >> 5) + ((lane & 3) ^ ((2 * (w & 1) + (dma_row7 >> 2)) & 3)));
+  FA_DMA_VOFF(dma_voff, RG::PPG, lane, w, ld, (int)sizeof(T));
   auto stage_dma = [&](int st, int dst) {
 #pragma unroll
     for (int g2 = 0; g2 < 2; ++g2) {
@@ -665,7 +661,7 @@ bwd_dkdv_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* 
     }
   };
   int roff = 0;   // tiled build: ring position of the current block's stage 0
-  auto slot_of = [&](int st) { return ((st + roff) % 3) * BUF; };
+  auto slot_of = [&](int st) { return ring_slot<3, BUF>(st, roff); };
   auto block = [&]() {   // the workgroup's key block(s): the sweep, then (causal build) the diagonal block
   const int st0 = CDIAG ? 2 * (kb + 1) : 0;   // first stage of the sweep (causal build: the stage below the diagonal block)
   if (!CDIAG || st0 < nst) {
@@ -686,16 +682,6 @@ bwd_dkdv_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* 
   f32x16 sA, dpA, sB, dpB, cS, cD;
   frag pf0, pf1, df0, df1, rq[4], rdo[4], tf[4];
   auto SB = [&]() { __builtin_amdgcn_sched_barrier(0); };
-  // LDS readers: per-stage address registers (row / transposed, two swizzle phases each) + immediates
-  auto rowf = [&](int b0, int b1, int tile_off, int sub, int kc) -> frag {
-    return *FA_LDS(frag, smem + ((kc & 1) ? b1 : b0) + tile_off + SUBB * sub + 512 * (kc >> 1));
-  };
-  auto trf = [&](int b0, int b1, int tile_off, int sub, int s2, int dt) -> frag {
-    const int kk = tile_off + SUBB * sub + (D / 32) * 512 * (2 * s2) + 512 * dt;
-    bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(FA_LDS(bf16x4, smem + b0 + kk));
-    bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(FA_LDS(bf16x4, smem + b1 + kk + (D / 32) * 512));
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  };
   auto ld_c = [&](f32x16& x, int hb /* stage base + 16 * h */, int off, int sub) {
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -718,7 +704,7 @@ bwd_dkdv_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* 
         if (kq == 0) A::mma_c(ns, rq[0], kf[0], cS);
         else A::mma(ns, rq[kq], kf[kq]);
         SB();
-        if (kq < 3) rdo[kq + 1] = rowf(nr0, nr1, TB, SN, kq + 1);
+        if (kq < 3) rdo[kq + 1] = RG::row(smem, nr0, nr1, SN, kq + 1, TB);
       }
       if constexpr (HC) { me(cs, 2 * kq); me(cs, 2 * kq + 1); }
       SB();
@@ -728,7 +714,7 @@ bwd_dkdv_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* 
     if constexpr (HC) {
       pf0 = A::pack(cs, 0);
       cdp[0] = cs[0] * cdp[0];
-      tf[0] = trf(ct0, ct1, TB, SC, 0, 0);
+      tf[0] = RG::tr(smem, ct0, ct1, SC, 0, 0, TB);
     }
     SB();
 #pragma unroll
@@ -736,7 +722,7 @@ bwd_dkdv_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* 
       if constexpr (HN) { A::mma(ndp, rdo[kq], vf[kq]); SB(); }
       if constexpr (HC) {
         me(cs, 6 + 2 * kq); me(cs, 7 + 2 * kq);
-        tf[kq] = trf(ct0, ct1, TB, SC, kq >> 1, kq & 1);
+        tf[kq] = RG::tr(smem, ct0, ct1, SC, kq >> 1, kq & 1, TB);
       }
       SB();
     }
@@ -744,25 +730,25 @@ bwd_dkdv_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* 
       A::mma(acc_dv[0], tf[0], pf0);   // slot 8
       SB();
       me(cs, 14); me(cs, 15);
-      tf[0] = trf(ct0, ct1, 0, SC, 0, 0);
+      tf[0] = RG::tr(smem, ct0, ct1, SC, 0, 0, 0);
       SB();
       A::mma(acc_dv[1], tf[1], pf0);   // slot 9
       SB();
       pf1 = A::pack(cs, 1);
       cdp[1] = cs[1] * cdp[1];
-      tf[1] = trf(ct0, ct1, 0, SC, 0, 1);
+      tf[1] = RG::tr(smem, ct0, ct1, SC, 0, 1, 0);
       SB();
       A::mma(acc_dv[0], tf[2], pf1);   // slot 10
       SB();
 #pragma unroll
       for (int i = 2; i < 8; ++i) cdp[i] = cs[i] * cdp[i];
-      tf[2] = trf(ct0, ct1, 0, SC, 1, 0);
+      tf[2] = RG::tr(smem, ct0, ct1, SC, 1, 0, 0);
       SB();
       A::mma(acc_dv[1], tf[3], pf1);   // slot 11
       SB();
       df0 = A::pack(cdp, 0);
       cdp[8] = cs[8] * cdp[8];
-      tf[3] = trf(ct0, ct1, 0, SC, 1, 1);
+      tf[3] = RG::tr(smem, ct0, ct1, SC, 1, 1, 0);
       SB();
       A::mma(acc_dk[0], tf[0], df0);   // slot 12
       SB();
@@ -770,8 +756,8 @@ bwd_dkdv_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* 
       for (int i = 9; i < 15; ++i) cdp[i] = cs[i] * cdp[i];
     }
     if constexpr (HN) {
-      rq[0] = rowf(pr0, pr1, 0, SP, 0);
-      rq[1] = rowf(pr0, pr1, 0, SP, 1);
+      rq[0] = RG::row(smem, pr0, pr1, SP, 0, 0);
+      rq[1] = RG::row(smem, pr0, pr1, SP, 1, 0);
     }
     SB();
     if constexpr (HC) {   // slot 13
@@ -781,8 +767,8 @@ bwd_dkdv_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* 
       df1 = A::pack(cdp, 1);
     }
     if constexpr (HN) {
-      rq[2] = rowf(pr0, pr1, 0, SP, 2);
-      rq[3] = rowf(pr0, pr1, 0, SP, 3);
+      rq[2] = RG::row(smem, pr0, pr1, SP, 2, 0);
+      rq[3] = RG::row(smem, pr0, pr1, SP, 3, 0);
     }
     SB();
     if constexpr (HC) { A::mma(acc_dk[0], tf[2], df1); SB(); }   // slot 14
@@ -791,7 +777,7 @@ bwd_dkdv_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* 
     if constexpr (HC) { A::mma(acc_dk[1], tf[3], df1); SB(); }   // slot 15
     if constexpr (HN) {
       ld_c(cD, ph16, 4 * QS, SP);
-      rdo[0] = rowf(pr0, pr1, TB, SP, 0);
+      rdo[0] = RG::row(smem, pr0, pr1, SP, 0, TB);
     }
     SB();
   };
@@ -808,10 +794,10 @@ bwd_dkdv_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* 
   if (active) {
     // operands of sub-slice 0, then its S', dP' alone (the pipeline fills)
 #pragma unroll
-    for (int kc = 0; kc < 4; ++kc) rq[kc] = rowf(cr0, cr1, 0, 0, kc);
+    for (int kc = 0; kc < 4; ++kc) rq[kc] = RG::row(smem, cr0, cr1, 0, kc, 0);
     ld_c(cS, ch16, 0, 0);
     ld_c(cD, ch16, 4 * QS, 0);
-    rdo[0] = rowf(cr0, cr1, TB, 0, 0);
+    rdo[0] = RG::row(smem, cr0, cr1, 0, 0, TB);
     SB();
     period(T1, T0, ic<0>{}, ic<0>{}, ic<1>{}, cr0, cr1, ct0, ct1, cr0, cr1, ch16, sA, dpA, sB, dpB);
   }

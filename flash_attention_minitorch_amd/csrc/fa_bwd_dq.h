@@ -305,6 +305,8 @@ bwd_dq_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __
   constexpr int KC = D / 16, ST = 128;
   constexpr int TB = A::template tile_bytes<D>(ST);   // 16 KiB
   constexpr int VOFF = 3 * TB;                        // V slot = K slot + 48 KiB
+  using RG = StageRing<D, ST>;                        // DMA pieces and readers of a stage (fa_atoms.h)
+  static_assert(RG::dma_matches_image(), "LDS-DMA source swizzle vs Atom::off");
   __shared__ __attribute__((aligned(16))) char smem_raw[6 * TB];
   lds_char* smem = (lds_char*)smem_raw;
 
@@ -384,12 +386,9 @@ bwd_dq_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __
   const int kmax = CDIAG ? qb * 256 : (causal ? min(N, qb * 256 + 256) : N);
   const int nstage = (kmax + ST - 1) / ST;
   // Stage loads go global -> LDS directly (buffer_load ... lds, 1 KiB = 8 rows per wave-instruction, no staging
-  // registers): LDS-DMA writes lane-linearly, so the image's chunk swizzle is applied to each lane's SOURCE address.
-  // Wave w moves the 8-row groups w and w + 8 of K and of V (same parity, hence one lane offset).
+  // registers): wave w moves the 8-row groups w and w + 8 of K and of V (same parity, hence one lane offset).
   const uint32_t smem_addr = (uint32_t)(uintptr_t)smem;
-  const int dma_row7 = (lane >> 2) & 7;
-  const int dma_voff = dma_row7 * ld * (int)sizeof(T) +
-                       16 * (4 * (lane >> 5) + ((lane & 3) ^ ((2 * (w & 1) + (dma_row7 >> 2)) & 3)));
+  FA_DMA_VOFF(dma_voff, RG::PPG, lane, w, ld, (int)sizeof(T));
   auto stage_dma = [&](int row0, int slot_base) {
 #pragma unroll
     for (int g2 = 0; g2 < 2; ++g2) {
@@ -426,15 +425,6 @@ bwd_dq_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __
   frag rk[4], rv[4], tf[4];
   auto SB = [&]() { __builtin_amdgcn_sched_barrier(0); };
   // LDS readers on a per-stage address register + immediate
-  auto krow = [&](int b0, int b1, int sub, int kc) -> frag {
-    return *FA_LDS(frag, smem + ((kc & 1) ? b1 : b0) + (D / 32) * 512 * (4 * sub) + 512 * (kc >> 1));
-  };
-  auto ktr = [&](int b0, int b1, int sub, int s2, int dt) -> frag {
-    const int kk = (D / 32) * 512 * (4 * sub + 2 * s2) + 512 * dt;
-    bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(FA_LDS(bf16x4, smem + b0 + kk));
-    bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(FA_LDS(bf16x4, smem + b1 + kk + (D / 32) * 512));
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  };
   // One period.  SUBN: sub-tile (0..3) whose S^T / dP^T are produced [row addresses rn*: its stage]; SUBP: the
   // sub-tile whose dQ product is issued [transposed addresses tp*: its stage]; SUB2: the sub-tile two ahead, whose K
   // rows are requested in slots 8-11 [row addresses r2*].  kcur: first key of the sub-tile in the exp / mul stream.
@@ -455,9 +445,6 @@ bwd_dq_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __
       cs[i] = pv;
     };
     auto md = [&](int i) { cdp[i] = NDACC ? cs[i] * cdp[i] : cs[i] * (cdp[i] + ndq); };
-    auto vrow = [&](int kq) -> frag {
-      return *FA_LDS(frag, smem + ((kq & 1) ? rn1 : rn0) + VOFF + (D / 32) * 512 * (4 * SUBN) + 512 * (kq >> 1));
-    };
     // LDS fragments are requested LEAD slots before the MFMA that consumes them: 4 in the build without masked periods
     // (186 VGPRs), 2 where the masked variants' joins leave no registers for more
     constexpr int LEAD = MASKS ? 2 : 4;
@@ -467,8 +454,8 @@ bwd_dq_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __
         if (kq == 0) A::mma_c(ns, rk[0], qf[0], PRE ? nl16 : zero16());
         else A::mma(ns, rk[kq], qf[kq]);
         SB();   // the MFMA opens its slot; the fillers follow in its shadow
-        if constexpr (LEAD == 4) rv[kq] = vrow(kq);
-        else if (kq >= 2) rv[kq - 2] = vrow(kq - 2);
+        if constexpr (LEAD == 4) rv[kq] = RG::row(smem, rn0, rn1, SUBN, kq, VOFF);
+        else if (kq >= 2) rv[kq - 2] = RG::row(smem, rn0, rn1, SUBN, kq - 2, VOFF);
       }
       if constexpr (HC) { fe(2 * kq); fe(2 * kq + 1); }
       SB();
@@ -480,7 +467,7 @@ bwd_dq_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __
         else A::mma(ndp, rv[kq], dof[kq]);
         SB();
         if constexpr (LEAD == 2) {
-          if (kq < 2) rv[kq + 2] = vrow(kq + 2);
+          if (kq < 2) rv[kq + 2] = RG::row(smem, rn0, rn1, SUBN, kq + 2, VOFF);
         }
       }
       if constexpr (HC) {
@@ -494,8 +481,8 @@ bwd_dq_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __
         }
       }
       if constexpr (HP) {
-        if constexpr (LEAD == 4) tf[kq] = ktr(tp0, tp1, SUBP, kq >> 1, kq & 1);
-        else if (kq >= 2) tf[kq - 2] = ktr(tp0, tp1, SUBP, 0, kq & 1);
+        if constexpr (LEAD == 4) tf[kq] = RG::tr(smem, tp0, tp1, SUBP, kq >> 1, kq & 1);
+        else if (kq >= 2) tf[kq - 2] = RG::tr(smem, tp0, tp1, SUBP, 0, kq & 1);
       }
       SB();
     }
@@ -505,7 +492,7 @@ bwd_dq_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __
         A::mma(acc[kq & 1], tf[kq], (kq < 2) ? dp0 : dp1);
         SB();
         if constexpr (LEAD == 2) {
-          if (kq < 2) tf[2 + kq] = ktr(tp0, tp1, SUBP, 1, kq);
+          if (kq < 2) tf[2 + kq] = RG::tr(smem, tp0, tp1, SUBP, 1, kq);
         }
       }
       if constexpr (HC) {
@@ -520,10 +507,10 @@ bwd_dq_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __
       }
       if constexpr (HN) {
         if constexpr (LEAD == 4) {
-          rk[kq] = krow(r20, r21, SUB2, kq);
+          rk[kq] = RG::row(smem, r20, r21, SUB2, kq);
         } else if (kq >= 2) {
-          rk[2 * (kq - 2)] = krow(r20, r21, SUB2, 2 * (kq - 2));
-          rk[2 * (kq - 2) + 1] = krow(r20, r21, SUB2, 2 * (kq - 2) + 1);
+          rk[2 * (kq - 2)] = RG::row(smem, r20, r21, SUB2, 2 * (kq - 2));
+          rk[2 * (kq - 2) + 1] = RG::row(smem, r20, r21, SUB2, 2 * (kq - 2) + 1);
         }
       }
       SB();
@@ -532,8 +519,7 @@ bwd_dq_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __
   auto T1 = ic<1>{};
   auto T0 = ic<0>{};
   // per-stage address registers: K slot of stage s is s % 3
-  auto slot_of = [&](int st) { return ((st + roff) % 3) * TB; };
-  const int b0_ = slot_of(0);
+  const int b0_ = ring_slot<3, TB>(0, roff);
   int cr0 = ra.b[0] + b0_, cr1 = ra.b[1] + b0_;     // rows of the current stage (slot 0; tiled build: where the ring stands)
   int ct0 = ta.b[0] + b0_, ct1 = ta.b[1] + b0_;     // transposed reads of the current stage
   int pt0 = ct0, pt1 = ct1;                         // ... of the previous stage (stage 0: any finite data, dS = 0)
@@ -543,14 +529,14 @@ bwd_dq_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __
   // which never touches those rows, is finite)
   if (CDIAG && nst_w == 0) return;
 #pragma unroll
-  for (int kc = 0; kc < 4; ++kc) rk[kc] = krow(cr0, cr1, 0, kc);
+  for (int kc = 0; kc < 4; ++kc) rk[kc] = RG::row(smem, cr0, cr1, 0, kc);
   dsB0 = A::zero();
   dsB1 = A::zero();
   SB();
   period(T1, T0, T0, T0, ic<0>{}, ic<0>{}, ic<1>{}, cr0, cr1, ct0, ct1, cr0, cr1, 0, sA, dpA, sB, dpB, dsB0, dsB1, dsA0, dsA1);
   for (int st = 0; st < nst_w; ++st) {
     const bool more = st + 1 < nstage;
-    const int nb = slot_of(st + 1);
+    const int nb = ring_slot<3, TB>(st + 1, roff);
     const int nr0 = ra.b[0] + nb, nr1 = ra.b[1] + nb;   // rows of the next stage
     if (CDIAG || more) stage_dma((st + 1) * ST, nb);   // (causal build: the two stages of the diagonal block follow the sweep)
     else if (TILED && pass + 1 < npass) {   // the next head's sweep: its key stage 0 follows in the ring
@@ -606,11 +592,10 @@ bwd_dq_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __
   } else {
     sweep(ic<0>{});
   }
-  auto slot_of = [&](int st) { return ((st + roff) % 3) * TB; };   // (as inside the sweep)
   if constexpr (TILED) roff = (roff + nstage) % 3;
   if constexpr (CDIAG) {   // the stage hand-off this wave has no periods for (same DMA share, wait and barrier as in the loop)
     for (int st = nst_w; st < nst_all; ++st) {
-      stage_dma((st + 1) * ST, slot_of(st + 1));
+      stage_dma((st + 1) * ST, ring_slot<3, TB>(st + 1, roff));
       dma_wait_all();
       __syncthreads();
     }

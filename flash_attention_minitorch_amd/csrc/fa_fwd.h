@@ -398,9 +398,9 @@ fwd_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
   constexpr int NSUBT = ST / 32;                      // sub-tiles per stage: 4 (d = 64) or 2 (d = 128)
   constexpr int R = NSUBT == 2 ? 4 : 3;               // ring slots
   constexpr int TB = A::template tile_bytes<D>(ST);   // 16 KiB (8 KiB with 64-key stages at d = 64)
-  constexpr int PCS = TB / 8192;                      // 1 KiB DMA pieces per wave and tensor
   constexpr int VOFF = R * TB;
-  constexpr int SUBB = (D / 32) * 512 * 4;            // bytes of one 32-key sub-tile inside a stage image
+  using RG = StageRing<D, ST>;                        // DMA pieces and readers of a stage (fa_atoms.h)
+  static_assert(RG::dma_matches_image(), "LDS-DMA source swizzle vs Atom::off");
   static_assert((TB == 16384 || TB == 8192) && 2 * DT == KC && (NSUBT == 2 || NSUBT == 4), "stage geometry");
   static_assert(!CDIAG || (!MASKS && NSUBT == 2 && R * ST == 256), "causal build: the ring holds one 256-key diagonal block");
   // PRE (every build without masked periods): tau*log2(e) is folded into the Q fragments once per block (re-rounded to bf16), so
@@ -469,23 +469,16 @@ fwd_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
   const int nstage = (kmax + ST - 1) / ST;
   const uint32_t smem_addr = (uint32_t)(uintptr_t)smem;
   // LDS-DMA pieces of 1 KiB: d = 64: one 8-row group (piece = w, w + 8); d = 128: half of one (piece = 2 * group + half).
-  // The image's chunk swizzle is applied to each lane's SOURCE address; a wave's pieces share its parity, hence one offset.
-  constexpr int PPG = D / 64;   // pieces per 8-row group
-  const int dma_row7 = (lane >> 2) & 7;
-  const int dma_gpar = (PPG == 1) ? (w & 1) : ((w >> 1) & 1);
-  const int dma_half = (PPG == 1) ? 0 : (w & 1);
-  const int dma_voff = dma_row7 * ld * (int)sizeof(T) +
-                       16 * (4 * (2 * dma_half + (lane >> 5)) + ((lane & 3) ^ ((2 * dma_gpar + (dma_row7 >> 2)) & 3)));
+  FA_DMA_VOFF(dma_voff, RG::PPG, lane, w, ld, (int)sizeof(T));
   auto stage_dma = [&](int row0, int slot_base) {
 #pragma unroll
-    for (int g2 = 0; g2 < PCS; ++g2) {
-      const int piece = w + 8 * g2, g = piece / PPG;
+    for (int g2 = 0; g2 < RG::NPW; ++g2) {
+      const int piece = w + 8 * g2, g = piece / RG::PPG;
       const int soff = (row0 + 8 * g) * ld * (int)sizeof(T);
       dma16(kraw, smem_addr + slot_base + 1024 * piece, dma_voff, soff);
       dma16(vraw, smem_addr + slot_base + VOFF + 1024 * piece, dma_voff, soff);
     }
   };
-  auto slot_of = [&](int st) { return (st % R) * TB; };
   if constexpr (MASKS) {   // ragged launches read stage rows past N: make sure they are zeros whatever an out-of-range
     // LDS-DMA lane does (0 * stale NaN bits would poison P.V); 96 / 128 KiB once per workgroup
 #pragma unroll 4
@@ -499,7 +492,7 @@ fwd_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
   const int nst_all = CDIAG ? nstage + 3 : nstage;        // stage hand-offs every wave takes part in
   {
   stage_dma(0, 0);
-  if (NSUBT == 2 && (CDIAG || nstage > 1)) stage_dma(ST, slot_of(1));
+  if (NSUBT == 2 && (CDIAG || nstage > 1)) stage_dma(ST, ring_slot<R, TB>(1));
   if (produce) {   // the guard's row norms, while the first stages are in flight (scratch: the tail of the ring, written by stage R - 1 first)
     float qs = 0.f, ks = 0.f;
 #pragma unroll
@@ -524,15 +517,6 @@ fwd_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
   u32x4 pA0, pA1, pB0, pB1;   // packed P^T (bf16 pairs): chunks s2 = 0, 1 of the two sub-tiles in flight
   frag rk[4], tf[4];          // rings: K rows of the S^T chain, transposed V of the P.V chain (requested two slots ahead)
   auto SB = [&]() { __builtin_amdgcn_sched_barrier(0); };
-  auto krow = [&](int b0, int b1, int sub, int kc) -> frag {
-    return *FA_LDS(frag, smem + ((kc & 1) ? b1 : b0) + SUBB * sub + 512 * (kc >> 1));
-  };
-  auto vtr = [&](int b0, int b1, int sub, int s2, int dt) -> frag {
-    const int kk = VOFF + SUBB * sub + (D / 32) * 512 * (2 * s2) + 512 * dt;
-    bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(FA_LDS(bf16x4, smem + b0 + kk));
-    bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(FA_LDS(bf16x4, smem + b1 + kk + (D / 32) * 512));
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  };
   auto cvt2 = [&](float a, float b) -> uint32_t {
     f32x2 pr = {a, b};
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(pr, bf16x2));
@@ -593,11 +577,11 @@ fwd_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
         if (kq == 0) A::mma_c(ns, rk[0], qf[0], zero16());
         else A::mma(ns, rk[kq & 3], qf[kq]);
         SB();   // the MFMA opens its slot; the fillers follow in its shadow
-        if (kq + 2 < KC) rk[(kq + 2) & 3] = krow(rn0, rn1, SUBN, kq + 2);
+        if (kq + 2 < KC) rk[(kq + 2) & 3] = RG::row(smem, rn0, rn1, SUBN, kq + 2);
       }
       valu(kq);
       if constexpr (HP) {
-        if (kq >= KC - 2) tf[kq - (KC - 2)] = vtr(tp0, tp1, SUBP, 0, kq - (KC - 2));
+        if (kq >= KC - 2) tf[kq - (KC - 2)] = RG::tr(smem, tp0, tp1, SUBP, 0, kq - (KC - 2), VOFF);
       }
       SB();
     }
@@ -606,11 +590,11 @@ fwd_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
       if constexpr (HP) {
         A::mma(acc_o[t % DT], tf[t & 3], __builtin_bit_cast(frag, (t < DT) ? pp0 : pp1));
         SB();
-        if (t + 2 < KC) tf[(t + 2) & 3] = vtr(tp0, tp1, SUBP, (t + 2) / DT, (t + 2) % DT);
+        if (t + 2 < KC) tf[(t + 2) & 3] = RG::tr(smem, tp0, tp1, SUBP, (t + 2) / DT, (t + 2) % DT, VOFF);
       }
       valu(KC + t);
       if constexpr (HN) {
-        if (t >= KC - 2) rk[t - (KC - 2)] = krow(r20, r21, SUB2, t - (KC - 2));
+        if (t >= KC - 2) rk[t - (KC - 2)] = RG::row(smem, r20, r21, SUB2, t - (KC - 2));
       }
       SB();
     }
@@ -620,7 +604,7 @@ fwd_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
       if (__any(!(rs < MAX_DEFER_SUM))) {   // rare: some row outgrew its reference -> redo this sub-tile the classic way
 #pragma unroll
         for (int kc = 0; kc < KC; ++kc) {
-          const frag kk = krow(rc0, rc1, SUBC, kc);
+          const frag kk = RG::row(smem, rc0, rc1, SUBC, kc);
           if (kc == 0) A::mma_c(cs, kk, qf[0], zero16());
           else A::mma(cs, kk, qf[kc]);
         }
@@ -654,8 +638,8 @@ fwd_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
   int ct0 = ta.b[0], ct1 = ta.b[1];   // transposed-read addresses of the current stage
   int pt0 = ct0, pt1 = ct1;           // ... of the previous stage (stage 0: any finite data, P = 0)
   // prologue: S^T of sub-tile 0, whose row maximum becomes the reference
-  rk[0] = krow(cr0, cr1, 0, 0);
-  rk[1] = krow(cr0, cr1, 0, 1);
+  rk[0] = RG::row(smem, cr0, cr1, 0, 0);
+  rk[1] = RG::row(smem, cr0, cr1, 0, 1);
   pB0 = pB1 = pA0 = pA1 = u32x4{0u, 0u, 0u, 0u};
   SB();
   period(T1, T0, T0, T0, ic<0>{}, ic<0>{}, ic<1>{}, ic<0>{}, cr0, cr1, ct0, ct1, cr0, cr1, cr0, cr1, 0, sA, sB, pB0, pB1, pA0, pA1);
@@ -666,7 +650,7 @@ fwd_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
     nmc = -m_ref * c;
   }
   for (int st = 0; st < nst_w; ++st) {
-    const int nb = slot_of(st + 1);
+    const int nb = ring_slot<R, TB>(st + 1);
     const int nr0 = ra.b[0] + nb, nr1 = ra.b[1] + nb;
     const int kb = st * ST;
     // a sub-tile needs the mask when it crosses N or (causal) this wave's first query; wave-uniform
@@ -709,7 +693,7 @@ fwd_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
         dma_wait_all();
         __syncthreads();
       }
-      if (CDIAG ? st + 2 < nstage + 4 : st + 2 < nstage) stage_dma((st + 2) * ST, slot_of(st + 2));   // (causal build: the diagonal block's four stages follow)
+      if (CDIAG ? st + 2 < nstage + 4 : st + 2 < nstage) stage_dma((st + 2) * ST, ring_slot<R, TB>(st + 2));   // (causal build: the diagonal block's four stages follow)
       // period 2st+0: produce sub 1, softmax of sub 0, P.V of sub 1 of the previous stage; rows two ahead: next stage, sub 0
       if constexpr (MASKS) {
         if (need(0)) period(T1, T1, T1, T1, ic<1>{}, ic<1>{}, ic<0>{}, ic<0>{}, cr0, cr1, pt0, pt1, nr0, nr1, cr0, cr1, kb, sB, sA, pB0, pB1, pA0, pA1);
@@ -746,7 +730,7 @@ fwd_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
         dma_wait_all();
         __syncthreads();
       }
-      if (st + 2 < nstage + 4) stage_dma((st + 2) * ST, slot_of(st + 2));
+      if (st + 2 < nstage + 4) stage_dma((st + 2) * ST, ring_slot<R, TB>(st + 2));
     }
   }
   }
