@@ -22,8 +22,6 @@ namespace {
 
 thread_local char g_err[512] = "";
 
-bool plan_mode();   // a fa_mi355x_plan() call is recording on this thread (see FA_LAUNCH)
-
 int set_err(int code, const char* what, hipError_t e = hipSuccess) {
   if (e != hipSuccess)
     snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
@@ -34,45 +32,8 @@ int set_err(int code, const char* what, hipError_t e = hipSuccess) {
 
 #define FA_HIP_TRY(expr)                                             \
   do {                                                               \
-    if (!plan_mode()) {   /* fa_mi355x_plan: no HIP call at all */   \
-      hipError_t e_ = (expr);                                        \
-      if (e_ != hipSuccess) return set_err(FA_ERR_HIP, #expr, e_);   \
-    }                                                                \
-  } while (0)
-
-// Every kernel launch of the dispatch code below goes through FA_LAUNCH.  fa_mi355x_plan() runs the SAME dispatch functions with a
-// recorder installed: the launch is then skipped and the kernel's name appended to the plan, so what bench.py labels and what the
-// library launches cannot drift apart (one source of truth for the kernel selection).
-thread_local std::vector<std::string>* t_plan = nullptr;
-// A second dry-run mode, for run_scaled below: the dispatch code runs with every launch and HIP call skipped and nothing recorded but
-// t_fold: did the selection reach a kernel that carries tau*log2(e) in a bf16 operand (FA_LAUNCH_FOLD sites)?
-thread_local bool t_probe = false, t_fold = false, t_fold_produces = false;   // (..._produces: the folding launch can fill the guard itself)
-bool plan_mode() { return t_plan != nullptr || t_probe; }
-void plan_add(const char* expr) {   // "(fa::fwd_slot_kernel<T, 64, false>)" -> "fwd_slot_kernel"
-  const char* b = expr;
-  while (*b == '(' || *b == ' ') ++b;
-  if (strncmp(b, "fa::", 4) == 0) b += 4;
-  const char* e = b;
-  while (*e && *e != '<' && *e != ')' && *e != ' ') ++e;
-  t_plan->emplace_back(b, e);
-}
-#define FA_LAUNCH(kern, grid, block, shmem, st, ...)                        \
-  do {                                                                      \
-    if (t_probe) break;                                                     \
-    if (t_plan) plan_add(#kern);                                            \
-    else hipLaunchKernelGGL(kern, grid, block, shmem, st, __VA_ARGS__);     \
-  } while (0)
-// ... of a kernel whose lane-stationary bf16 operand carries tau*log2(e) (the MFMA-slot builds without masked periods)
-#define FA_LAUNCH_FOLD(kern, grid, block, shmem, st, ...)                   \
-  do {                                                                      \
-    t_fold = true;                                                          \
-    FA_LAUNCH(kern, grid, block, shmem, st, __VA_ARGS__);                   \
-  } while (0)
-// ... and can fill the call's scale guard inside its own launch (the non-causal builds of the slot forward: guard_produce)
-#define FA_LAUNCH_FOLD_P(kern, grid, block, shmem, st, ...)                 \
-  do {                                                                      \
-    t_fold_produces = true;                                                 \
-    FA_LAUNCH_FOLD(kern, grid, block, shmem, st, __VA_ARGS__);              \
+    hipError_t e_ = (expr);                                          \
+    if (e_ != hipSuccess) return set_err(FA_ERR_HIP, #expr, e_);     \
   } while (0)
 
 // fwd_kernel workgroups per CU up to which the fp32 split-key forward takes the launch (measured, profiles/r04_fwd_splitk_f32.txt: 64 / 128
@@ -85,7 +46,7 @@ inline int d_padded(int d) { return d <= 32 ? 32 : (d <= 64 ? 64 : 128); }
 // Per-call kernel selection (fa_mi355x_fwd_ex / fa_mi355x_bwd_ex; every other entry point runs the defaults): [0] dK/dV geometry,
 // [1] forward kernel, [2] dQ kernel, [3] reserved, [4] preprocess / fp32 one-pass backward, [5] 1 = one head per workgroup in the
 // tiled slot builds, [6] reserved, [7] causal block order.  Only values whose kernels give correct results are accepted (parse_opts).
-// [8] where tau*log2(e) is applied (see run_scaled): 0 = by the call's scale guard when it has one, else fp32 scaling; 1 = the caller
+// [8] where tau*log2(e) is applied (see select_call): 0 = by the call's scale guard when it has one, else fp32 scaling; 1 = the caller
 // vouches for the operand range (inputs of the north star's U(-1, 1) magnitude): the kernels that fold it into a bf16 operand run
 // without a guard; 2 = fp32 scaling whatever the guard says; 3 = (fa_mi355x_plan only) plan a guarded call.  [9] 1 = bf16 output.
 constexpr int NTUN = 10;
@@ -192,66 +153,134 @@ int head_tiles(const Call& c, int nb) {
   return tiles;
 }
 
-// Phased forward.  bf16 rows with fewer than 64 admissible keys need the split-operand build (CARE): whole launches under a key
-// mask, dropout or N < 64; behind a causal launch, query block 0 alone is redone by it (one small workgroup per batch*head).
-template <typename T, int D, int BN>
-int fwd_launch_cfg(const Call& c, int only_qb = -1, int care_main = 0, int ranked = 0) {
-  constexpr bool BF = sizeof(T) == 2;
-  const int batch = c.batch, N = c.N, causal = c.causal;
-  const int nqb = (N + 127) / 128;
-  fa::Layout lay = c.lay;
-  // causal: query blocks p and nqb-1-p share a workgroup, or (ranked) one block per workgroup, longest first across a chunk of heads
-  lay.rank_chunk = (ranked && causal && only_qb < 0) ? rank_chunk(2, nqb) : 0;
-  // the fp32-scaling twin of a guarded non-causal call: four query blocks per workgroup while the launch still covers the chip twice
-  // (its workgroups almost always return at their guard check: 4.7 -> about 1.5 us at the metric shape)
-  lay.twin_blocks = 1;
-  if (lay.guard && lay.guard_want == 1 && !causal && only_qb < 0)
-    for (int t = 4; t > 1; t >>= 1)
-      if (nqb % t == 0 && (long)batch * (nqb / t) >= 2L * device_cus()) { lay.twin_blocks = t; break; }
-  const int nblk = only_qb >= 0 ? 1 : ((causal && !lay.rank_chunk) ? (nqb + 1) / 2 : nqb / lay.twin_blocks);
-  fa::Layout lay1 = lay;   // (the follow-up launch of one block per head below is not ranked)
-  lay1.rank_chunk = 0;
-#define FA_FWD_LAUNCH(FEAT, CARE, BLOCKS, ONLY)                                                                          \
-  FA_LAUNCH((fa::fwd_kernel<T, D, BN, 1, FEAT, CARE>), dim3(batch * (BLOCKS)), dim3(256), 0, c.st, (const T*)c.q,    \
-            (const T*)c.k, (const T*)c.v, c.out, c.l, c.m, N, nqb, batch, lay, causal, c.variant, c.tau, ONLY)
-  if (lay.drop_thr) {   // dropout on P (and the key mask, staged as zeros when absent)
-    FA_FWD_LAUNCH(2, BF, nblk, only_qb);
-  } else if (lay.kmask) {   // additive key mask: staged per tile, enters S^T as the accumulator input
-    FA_FWD_LAUNCH(1, BF, nblk, only_qb);
-  } else if (BF && (N < 64 || only_qb >= 0 || (causal && care_main))) {   // care_main (d = 64): ONE launch of the split-operand build,
-    // measured 1 % faster than the main build + the block-0 follow-up launch (7.8 us); the dQ kernel is the other way round (+7 %)
-    FA_FWD_LAUNCH(0, BF, nblk, only_qb);
-  } else {
-    FA_FWD_LAUNCH(0, false, nblk, only_qb);
-    if (BF && causal) {   // rows 0..63 see fewer than 64 keys: query block 0 again, split operands
-      FA_LAUNCH((fa::fwd_kernel<T, D, BN, 1, 0, BF>), dim3(batch), dim3(256), 0, c.st, (const T*)c.q, (const T*)c.k, (const T*)c.v,
-                c.out, c.l, c.m, N, nqb, batch, lay1, causal, c.variant, c.tau, 0);
-    }
+// only bf16 rows of 64 / 128 elements ever reach a kernel that folds the scale into an operand: everything else gets an all-zero
+// guard ("within the budget"; those calls run fp32-scaling kernels whatever it says)
+inline bool guard_rows_fold(int dtype, int row_elems) { return dtype == FA_DTYPE_BF16 && (row_elems == 64 || row_elems == 128); }
+int launch_scale_guard(const void* q, const void* k, long rows, int row_elems, int dtype, void* guard, hipStream_t st) {
+  if (!guard_rows_fold(dtype, row_elems)) {
+    FA_HIP_TRY(hipMemsetAsync(guard, 0, (size_t)2 * fa::GUARD_SLOTS * sizeof(float), st));
+    return FA_OK;
   }
-#undef FA_FWD_LAUNCH
+  const dim3 grid(fa::GUARD_SLOTS, 2);
+  if (row_elems == 64)
+    hipLaunchKernelGGL((fa::scale_guard_kernel<64>), grid, dim3(256), 0, st, (const fa::bf16_t*)q, (const fa::bf16_t*)k, rows, (float*)guard);
+  else
+    hipLaunchKernelGGL((fa::scale_guard_kernel<128>), grid, dim3(256), 0, st, (const fa::bf16_t*)q, (const fa::bf16_t*)k, rows, (float*)guard);
   FA_HIP_TRY(hipGetLastError());
   return FA_OK;
 }
 
+// ---- kernel selection: a value ---------------------------------------------------------------------------------------------------
+// What a call runs is computed ONCE, by pure code, as a Selection: an ordered list of steps.  select_call() builds it from the validated
+// Call (no HIP call but the cached device_cus(), no thread-local or global mutable state), execute() walks it and launches, and
+// fa_mi355x_plan() walks the same value and reads the names: what bench.py labels and what the library launches cannot drift apart.
+// Every build this file instantiates, and the few steps that are no kernel of ours, with the name fa_mi355x_plan lists them under
+// (nullptr: not listed).  The four phased forward / dQ builds keep the order drop, mask, care, main (select_phased).
+#define FA_KERNS(X)                                                                                                                  \
+  X(FWD_SPLITK, "fwd_splitk_f32_kernel")                                                                                             \
+  X(FWD_SLOT_CAUSAL, "fwd_slot_kernel") X(FWD_SLOT_WHOLE, "fwd_slot_kernel") X(FWD_SLOT_MASKED, "fwd_slot_kernel")                   \
+  X(FWD_DROP, "fwd_kernel") X(FWD_MASK, "fwd_kernel") X(FWD_CARE, "fwd_kernel") X(FWD_MAIN, "fwd_kernel")                            \
+  X(BWD_PREP, "bwd_prep_kernel")                                                                                                     \
+  X(DQ_DROP, "bwd_dq_kernel") X(DQ_MASK, "bwd_dq_kernel") X(DQ_CARE, "bwd_dq_kernel") X(DQ_MAIN, "bwd_dq_kernel")                    \
+  X(DQ_WAVE8, "bwd_dq_kernel")                                                                                                       \
+  X(DQ_SLOT_CAUSAL, "bwd_dq_slot_kernel") X(DQ_SLOT_TILED, "bwd_dq_slot_kernel") X(DQ_SLOT_WHOLE, "bwd_dq_slot_kernel")              \
+  X(DQ_SLOT_MASKED, "bwd_dq_slot_kernel")                                                                                            \
+  X(DKDV_SLOT_TILED, "bwd_dkdv_slot_kernel") X(DKDV_SLOT, "bwd_dkdv_slot_kernel") X(DKDV_SLOT_CAUSAL, "bwd_dkdv_slot_kernel")        \
+  X(DKDV_CARE_DROP, "bwd_dkdv_kernel") X(DKDV_CARE, "bwd_dkdv_kernel") X(DKDV_DROP_F32, "bwd_dkdv_kernel")                           \
+  X(DKDV_CARE_MAIN, "bwd_dkdv_kernel") X(DKDV_PAIRED, "bwd_dkdv_kernel") X(DKDV_PAIRED_M3, "bwd_dkdv_kernel")                        \
+  X(DKDV_PLAIN, "bwd_dkdv_kernel") X(DKDV_F32_64, "bwd_dkdv_kernel")                                                                 \
+  X(ONEPASS, "bwd_onepass_f32_kernel")                                                                                               \
+  X(GUARD_PASS, "scale_guard_kernel")   /* the separate pass over q and k ... */                                                     \
+  X(GUARD_PASS_ZERO, nullptr)           /* ... of rows no kernel folds: launch_scale_guard only zeroes the guard */                  \
+  X(GUARD_ZERO, "memset")               /* the guard memset in front of a forward that fills it */                                   \
+  X(ZERO_GRADS, nullptr)                /* the one-pass backward's memsets of dq (and dk, dv when the sweep is cut) */
+#define X(id, name) id,
+enum Kern : int { FA_KERNS(X) };
+#undef X
+#define X(id, name) name,
+constexpr const char* KERN_NAME[] = {FA_KERNS(X)};
+#undef X
+
+struct Step {
+  Kern kern;
+  unsigned grid, block;
+  int nb;    // query / key blocks per head, as the kernel is told
+  int arg;   // the build's mode argument: only_qb (phased forward / dQ), thin_mode (phased dK/dV), the block order of a causal slot
+             // build, `causal` of the other slot builds, the split of ONEPASS / ZERO_GRADS
+  int rank_chunk = 0, tiles = 0, twin_blocks = 0, guard_want = 0;   // the fa::Layout fields that belong to this launch alone
+  bool prep = false;    // a dQ launch that also preprocesses its rows (fa::DqPrep)
+  bool check = true;    // hipGetLastError() behind this launch (false: behind its follow-up launch)
+};
+struct Selection {
+  Step steps[8] = {};   // (the most: memsets, preprocess, two launches each of dQ and dK/dV)
+  int n = 0;
+  bool folds = false;            // a kernel carries tau*log2(e) in a bf16 operand (the MFMA-slot forward without masked periods) ...
+  bool produces_guard = false;   // ... and can fill the call's scale guard inside its own launch (its non-causal builds: guard_produce)
+  bool fuses_prep = false;       // the dQ launch preprocesses its own rows: no preprocess kernel, stage order dQ -> dK/dV
+  int onepass = 0;               // parts of the fp32 one-pass backward's query sweep, 0 = two kernels
+  Step& add(Kern kern, int grid, int block, int nb = 0, int arg = 0) {
+    return steps[n++] = Step{kern, (unsigned)grid, (unsigned)block, nb, arg};
+  }
+  void append(const Selection& o, int guard_want = 0) {
+    for (int i = 0; i < o.n; ++i) (steps[n++] = o.steps[i]).guard_want = guard_want;
+    folds |= o.folds;
+    produces_guard |= o.produces_guard;
+    fuses_prep |= o.fuses_prep;
+    onepass |= o.onepass;
+  }
+};
+
+// The phased forward (base = FWD_DROP) and dQ (DQ_DROP) kernels, 128-query blocks.  bf16 rows with fewer than 64 admissible keys need
+// the split-operand build (CARE): whole launches under a key mask, dropout or N < 64; behind a causal launch, query block 0 alone is
+// redone by it (one small workgroup per batch*head).  care_main: ONE launch of the split-operand build instead (forward, d = 64:
+// measured 1 % faster than the main build + the block-0 follow-up launch (7.8 us); the dQ kernel is the other way round (+7 %)).
+// only_qb >= 0: that query block alone, split operands (the follow-up of a masked slot build).  prep: see select_dq.
+void select_phased(Selection& s, const Call& c, bool bf, Kern base, int only_qb, int care_main, int ranked, bool prep) {
+  const int batch = c.batch, N = c.N, causal = c.causal, nqb = (N + 127) / 128;
+  const bool fwd = base == FWD_DROP;
+  // causal: query blocks p and nqb-1-p share a workgroup, or (ranked) one block per workgroup, longest first across a chunk of heads
+  const int chunk = (ranked && causal && only_qb < 0) ? rank_chunk(2, nqb) : 0;
+  // the fp32-scaling twin of a guarded non-causal call: four query blocks per workgroup while the launch still covers the chip twice
+  // (its workgroups almost always return at their guard check: 4.7 -> about 1.5 us at the metric shape)
+  int twin = 1;
+  if (fwd && c.lay.guard && c.lay.guard_want == 1 && !causal && only_qb < 0)
+    for (int t = 4; t > 1; t >>= 1)
+      if (nqb % t == 0 && (long)batch * (nqb / t) >= 2L * device_cus()) { twin = t; break; }
+  const int nblk = only_qb >= 0 ? 1 : ((causal && !chunk) ? (nqb + 1) / 2 : nqb / twin);
+  const int build = c.lay.drop_thr ? 0      // dropout on P (and the key mask, staged as zeros when absent)
+                    : c.lay.kmask  ? 1      // additive key mask: staged per tile, enters S^T as the accumulator input
+                    : (bf && (N < 64 || only_qb >= 0 || (causal && care_main))) ? 2 : 3;
+  Step& m = s.add(Kern(base + build), batch * nblk, 256, nqb, only_qb);
+  m.rank_chunk = chunk;
+  m.twin_blocks = fwd ? twin : 0;
+  if (build != 3) return;
+  m.prep = prep;
+  if (bf && causal) {   // rows 0..63 see fewer than 64 keys: query block 0 again, split operands (not ranked)
+    m.check = false;
+    s.add(Kern(base + 2), batch, 256, nqb, 0).twin_blocks = m.twin_blocks;
+  }
+}
+
 template <typename T, int D>
-int fwd_launch(const Call& c) {
+Selection select_fwd(const Call& c) {
+  constexpr bool BF = sizeof(T) == 2;
   const int batch = c.batch, N = c.N, causal = c.causal;
   const Tun& tun = c.tun;
-  if constexpr (sizeof(T) == 4 && D == 64) {
+  const bool plain = !c.lay.kmask && !c.lay.drop_thr;
+  Selection s;
+  if (!BF && D == 64) {
     // fp32, d = 64, launches that leave most of the chip idle under fwd_kernel's geometry (a wave = 32 queries x all keys, 128-query
     // workgroups, two per CU): the split-key forward (fa_fwd_splitk_f32.h: a workgroup = one 32-query block, its four waves a quarter
     // of the keys each).  Option 1: 4 = always, 2 = never.
     const long wgs = (long)batch * ((N + 127) / 128), cus = device_cus();
-    if (!c.lay.kmask && !c.lay.drop_thr && !c.lay.out_bf16 && N >= 128 && (tun.v[1] == 4 ||
+    if (plain && !c.lay.out_bf16 && N >= 128 && (tun.v[1] == 4 ||
          (tun.v[1] == 0 && wgs <= (causal ? FWD_SPLITK_MAX_WGS_PER_CU_CAUSAL : FWD_SPLITK_MAX_WGS_PER_CU) * cus))) {
       const int nqb = (N + 31) / 32;
-      FA_LAUNCH((fa::fwd_splitk_f32_kernel<D>), dim3((unsigned)(batch * nqb)), dim3(256), 0, c.st, (const float*)c.q, (const float*)c.k,
-                (const float*)c.v, c.out, c.l, c.m, N, nqb, batch, c.lay, causal, c.variant, c.tau);
-      FA_HIP_TRY(hipGetLastError());
-      return FA_OK;
+      s.add(FWD_SPLITK, batch * nqb, 256, nqb);
+      return s;
     }
   }
-  if constexpr (sizeof(T) == 2 && (D == 64 || D == 128)) {
+  if (BF && (D == 64 || D == 128)) {
     // FA-2 side output, bf16, d = 64 / 128, non-causal: slot-interleaved three-deep pipeline.  Under the causal mask the slot build
     // WITH masked period variants is 3.6 % slower than the phased kernel (128-query workgroups, per-wave tile skipping), which keeps
     // the causal launches the build below does not take; tuning key 1: 2 = always phased, 3 = always slot.
@@ -260,198 +289,79 @@ int fwd_launch(const Call& c) {
     // nqb-1-p paired): 0.155 vs 0.192 ms for the phased kernel at the metric shape; it needs about one 8-wave workgroup per CU to pay.
     const int nqb = (N + 255) / 256;
     const bool cslot = causal && N % 256 == 0 && (tun.v[1] == 3 || (tun.v[1] == 0 && batch * nqb >= 256));
-    if (c.variant == FA_VARIANT_FA2 && tun.v[1] != 2 && (!causal || tun.v[1] == 3 || cslot) && !c.lay.kmask && !c.lay.drop_thr &&
-        N >= 64) {
-      const bool whole = !causal && N % (8192 / D) == 0;   // no sub-tile needs a mask
+    if (c.variant == FA_VARIANT_FA2 && tun.v[1] != 2 && (!causal || tun.v[1] == 3 || cslot) && plain && N >= 64) {
       if (cslot) {   // (d = 64: four waves per SIMD, two workgroups per CU; d = 128: two waves per SIMD, one workgroup)
         const bool ranked = causal_ranked(tun, batch * nqb, D == 64 ? 2 : 1);
-        fa::Layout lay = c.lay;
-        lay.rank_chunk = rank_chunk(D == 64 ? 2 : 1, nqb);
-        FA_LAUNCH_FOLD((fa::fwd_slot_kernel<T, D, false, 64, (D == 64 ? 4 : 2), true>),
-                       dim3(ranked ? batch * nqb : batch * ((nqb + 1) / 2)), dim3(512), 0, c.st, (const T*)c.q, (const T*)c.k,
-                       (const T*)c.v, c.out, c.l, N, nqb, batch, lay, ranked ? 2 : 1, c.tau);
-        FA_HIP_TRY(hipGetLastError());
-        return FA_OK;
+        s.add(FWD_SLOT_CAUSAL, ranked ? batch * nqb : batch * ((nqb + 1) / 2), 512, nqb, ranked ? 2 : 1).rank_chunk =
+            rank_chunk(D == 64 ? 2 : 1, nqb);
+        s.folds = true;
+        return s;
       }
-      if (whole && D == 64) {   // d = 64 default: 64-key stages (64 KiB of rings), two workgroups per CU = four waves per SIMD at
-        // 122 VGPRs: 0.268 vs 0.282 ms for the 128-key-stage build at two waves per SIMD
-        FA_LAUNCH_FOLD_P((fa::fwd_slot_kernel<T, 64, false, 64, 4>), dim3(batch * nqb), dim3(512), 0, c.st, (const T*)c.q,
-                         (const T*)c.k, (const T*)c.v, c.out, c.l, N, nqb, batch, c.lay, causal, c.tau);
-        FA_HIP_TRY(hipGetLastError());
-        return FA_OK;
+      if (!causal && N % (8192 / D) == 0) {   // no sub-tile needs a mask.  d = 64 default: 64-key stages (64 KiB of rings), two
+        // workgroups per CU = four waves per SIMD at 122 VGPRs: 0.268 vs 0.282 ms for the 128-key-stage build at two waves per SIMD
+        s.add(FWD_SLOT_WHOLE, batch * nqb, 512, nqb, causal);
+        s.folds = s.produces_guard = true;
+        return s;
       }
-      if constexpr (D == 128) {
-        if (whole) {
-          FA_LAUNCH_FOLD_P((fa::fwd_slot_kernel<T, D, false>), dim3(batch * nqb), dim3(512), 0, c.st, (const T*)c.q,
-                           (const T*)c.k, (const T*)c.v, c.out, c.l, N, nqb, batch, c.lay, causal, c.tau);
-          FA_HIP_TRY(hipGetLastError());
-          return FA_OK;
-        }
-      }
-      if constexpr (D == 64) {   // ragged N / forced causal: the variant with masked periods (d = 128 takes the phased kernel)
-        FA_LAUNCH((fa::fwd_slot_kernel<T, D, true>), dim3(batch * nqb), dim3(512), 0, c.st, (const T*)c.q,
-                  (const T*)c.k, (const T*)c.v, c.out, c.l, N, nqb, batch, c.lay, causal, c.tau);
-        FA_HIP_TRY(hipGetLastError());
+      if (D == 64) {   // ragged N / forced causal: the variant with masked periods (d = 128 takes the phased kernel)
+        s.add(FWD_SLOT_MASKED, batch * nqb, 512, nqb, causal);
         // under the causal mask rows 0..63 see fewer than 64 keys: the slot kernel has no split-operand path, so the phased
         // kernel redoes query block 0 (one small workgroup per batch*head) behind it
-        if (causal) return fwd_launch_cfg<T, D, 64>(c, 0);
-        return FA_OK;
+        if (causal) select_phased(s, c, BF, FWD_DROP, 0, 0, 0, false);
+        return s;
       }
     }
   }
-  return fwd_launch_cfg<T, D, (sizeof(T) == 2 ? 64 : 32)>(c, -1, D == 64 ? 1 : 0,
-                                                          tun.v[7] == 2 || (tun.v[7] == 0 && sizeof(T) == 2 && D == 32));   // (d = 32: ranked measured 10 % faster)
+  select_phased(s, c, BF, FWD_DROP, -1, D == 64 ? 1 : 0, tun.v[7] == 2 || (tun.v[7] == 0 && BF && D == 32), false);   // (d = 32: ranked measured 10 % faster)
+  return s;
 }
 
-// bf16 launches whose rows may see fewer than 64 admissible keys everywhere (key mask, dropout, N < 64) run the split-operand
-// build (CARE) in a 4-wave geometry that has the registers for it.  A causal launch runs the requested geometry with the
-// sub-slices of queries 0..63 SKIPPED (thin_mode 1) and then one CARE workgroup per batch*head that handles exactly those and
+// The phased dK/dV kernel in the geometry of <T, D>: 8 waves x 32 keys (bf16) or 4 (fp32) per workgroup; mode3 (bf16, d = 64): the
+// slot-interleaved build.  bf16 launches whose rows may see fewer than 64 admissible keys everywhere (key mask, dropout, N < 64) run
+// the split-operand build (CARE) in a 4-wave geometry that has the registers for it.  A causal launch runs the requested geometry with
+// the sub-slices of queries 0..63 SKIPPED (thin_mode 1) and then one CARE workgroup per batch*head that handles exactly those and
 // adds its dK, dV (thin_mode 2): the main kernel keeps its registers and its speed.
-// DROP_ONLY: the instantiation serves dropout calls alone (fp32 d = 64: the plain launches have a build of their own), so the plain
-// kernels of this geometry are not compiled into the library.
-template <typename T, int D, int KPW, int NW, int QS, int MODE = 0, bool DROP_ONLY = false>
-int dkdv_launch(const Call& c, int care_main = 0, int rank_causal = 1) {
+// (fp32, d = 64 comes here for dropout calls alone: its plain launches have a build of their own, see execute.)
+template <typename T, int D>
+void select_dkdv_phased(Selection& s, const Call& c, bool mode3 = false, int care_main = 0, int rank_causal = 1) {
   constexpr bool BF = sizeof(T) == 2;
+  constexpr int NW = BF ? 8 : 4;
   const int batch = c.batch, N = c.N, causal = c.causal;
-  const int nkb = (N + NW * KPW - 1) / (NW * KPW);
-  const int nkb4 = (N + 127) / 128;
-  fa::Layout lay = c.lay;
-#define FA_CARE_LAUNCH(HD, GRID, THIN)                                                                                        \
-  FA_LAUNCH((fa::bwd_dkdv_kernel<T, D, 32, 4, 64, 1, HD, 1, BF>), dim3(GRID), dim3(256), 0, c.st, (const T*)c.q, (const T*)c.k, \
-            (const T*)c.v, (const T*)c.dout, c.nlc(), c.delta(), c.dk, c.dv, N, nkb4, batch, lay, causal, c.tau, THIN)
-  if (lay.drop_thr) {   // dropout: the plain per-sub-slice path regenerates the mask from (bh, query, key)
+  const int nkb = (N + NW * 32 - 1) / (NW * 32), nkb4 = (N + 127) / 128;
+  const bool rank = causal && rank_causal;
+  if (c.lay.drop_thr) {   // dropout: the plain per-sub-slice path regenerates the mask from (bh, query, key)
     // (these whole-launch builds take one key block per workgroup: under the causal mask longest first across a chunk of heads)
-    if constexpr (BF) {
-      if (causal && rank_causal) lay.rank_chunk = rank_chunk(2, nkb4);
-      FA_CARE_LAUNCH(true, batch * nkb4, 0);
-    } else {
-      if (causal && rank_causal) lay.rank_chunk = rank_chunk(2, nkb);
-      FA_LAUNCH((fa::bwd_dkdv_kernel<T, D, KPW, NW, QS, 1, true>), dim3(batch * nkb), dim3(NW * 64), 0, c.st,
-                (const T*)c.q, (const T*)c.k, (const T*)c.v, (const T*)c.dout, c.nlc(), c.delta(), c.dk, c.dv, N, nkb, batch, lay,
-                causal, c.tau, 0);
-    }
-    FA_HIP_TRY(hipGetLastError());
-    return FA_OK;
+    if (BF) s.add(DKDV_CARE_DROP, batch * nkb4, 256, nkb4).rank_chunk = rank ? rank_chunk(2, nkb4) : 0;
+    else s.add(DKDV_DROP_F32, batch * nkb, NW * 64, nkb).rank_chunk = rank ? rank_chunk(2, nkb) : 0;
+    return;
   }
-  if constexpr (BF) {
-    if (lay.kmask || N < 64) {
-      if (causal && rank_causal) lay.rank_chunk = rank_chunk(2, nkb4);
-      FA_CARE_LAUNCH(false, batch * nkb4, 0);
-      FA_HIP_TRY(hipGetLastError());
-      return FA_OK;
-    }
+  if (BF && (c.lay.kmask || N < 64)) {
+    s.add(DKDV_CARE, batch * nkb4, 256, nkb4).rank_chunk = rank ? rank_chunk(2, nkb4) : 0;
+    return;
   }
-  if constexpr (BF && MODE == 3) {
-    if (causal && care_main) {   // d = 64 default: the split-operand path inside the main (paired) kernel: 2 % faster than main + corner launch
-      FA_LAUNCH((fa::bwd_dkdv_kernel<T, D, KPW, NW, QS, MODE, false, 1, true, true>), dim3(batch * ((nkb + 1) / 2)),
-                dim3(NW * 64), 0, c.st, (const T*)c.q, (const T*)c.k, (const T*)c.v, (const T*)c.dout, c.nlc(), c.delta(), c.dk, c.dv,
-                N, nkb, batch, lay, causal, c.tau, 0);
-      FA_HIP_TRY(hipGetLastError());
-      return FA_OK;
-    }
+  if (mode3 && causal && care_main) {   // d = 64 default: the split-operand path inside the main (paired) kernel: 2 % faster than main + corner launch
+    s.add(DKDV_CARE_MAIN, batch * ((nkb + 1) / 2), NW * 64, nkb);
+    return;
   }
-  if constexpr (DROP_ONLY) {
-    return set_err(FA_ERR_BAD_ARG, "internal: dropout-only dK/dV launch without dropout");
-  } else {
   const int thin = (BF && causal) ? 1 : 0;
   // causal: key blocks p and nkb-1-p share a workgroup (uniform work, no tail: -13 % at the metric shape).  Not for the 8-wave
   // d = 128 geometry, whose register allocation has no room for the pass loop (it would spill).
-  constexpr bool CAN_PAIR = !(BF && D == 128 && NW == 8);
-  // (MODE 3 always runs its paired build: hipcc's allocation of the unpaired MODE 3 instance spills, the paired one does not)
-  if ((causal || MODE == 3) && CAN_PAIR) {
-    if constexpr (CAN_PAIR)
-      FA_LAUNCH((fa::bwd_dkdv_kernel<T, D, KPW, NW, QS, MODE, false, 1, false, true>), dim3(batch * ((nkb + 1) / 2)),
-                dim3(NW * 64), 0, c.st, (const T*)c.q, (const T*)c.k, (const T*)c.v, (const T*)c.dout, c.nlc(), c.delta(), c.dk, c.dv,
-                N, nkb, batch, lay, causal, c.tau, thin);
+  // (mode3 always runs its paired build: hipcc's allocation of the unpaired instance spills, the paired one does not)
+  Step* m;
+  if ((causal || mode3) && !(BF && D == 128)) {
+    m = &s.add(mode3 ? DKDV_PAIRED_M3 : DKDV_PAIRED, batch * ((nkb + 1) / 2), NW * 64, nkb, thin);
   } else {
     // unpaired causal launch (the 8-wave d = 128 geometry): longest block first across a chunk of heads instead of head by head:
     // 2.05 vs 2.21 ms at configs[3]'s shape, 0.157 vs 0.207 at B = 8, N = 2048 (option 7 = 1: head by head)
-    if (causal && rank_causal) lay.rank_chunk = rank_chunk(NW == 8 ? 1 : 2, nkb);
-    if constexpr (MODE != 3 || !CAN_PAIR)
-      FA_LAUNCH((fa::bwd_dkdv_kernel<T, D, KPW, NW, QS, MODE>), dim3(batch * nkb), dim3(NW * 64), 0, c.st, (const T*)c.q,
-                (const T*)c.k, (const T*)c.v, (const T*)c.dout, c.nlc(), c.delta(), c.dk, c.dv, N, nkb, batch, lay, causal, c.tau, thin);
+    m = &s.add(DKDV_PLAIN, batch * nkb, NW * 64, nkb, thin);
+    m->rank_chunk = rank ? rank_chunk(NW == 8 ? 1 : 2, nkb) : 0;
   }
-  if constexpr (BF) {
-    if (thin) FA_CARE_LAUNCH(false, batch, 2);
+  if (thin) {
+    m->check = false;
+    s.add(DKDV_CARE, batch, 256, nkb4, 2).rank_chunk = m->rank_chunk;
   }
-  FA_HIP_TRY(hipGetLastError());
-  return FA_OK;
-  }   // !DROP_ONLY
-#undef FA_CARE_LAUNCH
 }
 
-template <typename T, int D, int BN>
-int dq_launch(const Call& c, int only_qb = -1, int care_main = 0, const fa::DqPrep* prep = nullptr, int ranked = 0) {
-  // prep != nullptr (only when dq_fuses_prep said so: the plain main build runs): the launch also preprocesses its rows
-  constexpr bool BF = sizeof(T) == 2;   // CARE policy as fwd_launch_cfg's
-  const int batch = c.batch, N = c.N, causal = c.causal;
-  const int nqb = (N + 127) / 128;
-  fa::Layout lay = c.lay;
-  // causal: query blocks p and nqb-1-p share a workgroup, or (ranked) one block per workgroup, longest first across a chunk of heads
-  lay.rank_chunk = (ranked && causal && only_qb < 0) ? rank_chunk(2, nqb) : 0;
-  const int nblk = only_qb >= 0 ? 1 : ((causal && !lay.rank_chunk) ? (nqb + 1) / 2 : nqb);
-  fa::Layout lay1 = lay;   // (the follow-up launch of one block per head below is not ranked)
-  lay1.rank_chunk = 0;
-#define FA_DQ_LAUNCH(FEAT, CARE, BLOCKS, ONLY)                                                                              \
-  FA_LAUNCH((fa::bwd_dq_kernel<T, D, BN, FEAT, 4, CARE>), dim3(batch * (BLOCKS)), dim3(256), 0, c.st, (const T*)c.q,   \
-            (const T*)c.k, (const T*)c.v, (const T*)c.dout, c.nlc(), c.delta(), c.dq, N, nqb, batch, lay, causal, c.tau, ONLY,   \
-            fa::DqPrep{})
-  if (lay.drop_thr) {
-    FA_DQ_LAUNCH(2, BF, nblk, only_qb);
-  } else if (lay.kmask) {
-    FA_DQ_LAUNCH(1, BF, nblk, only_qb);
-  } else if (BF && (N < 64 || only_qb >= 0 || (causal && care_main))) {
-    FA_DQ_LAUNCH(0, BF, nblk, only_qb);
-  } else {
-    FA_LAUNCH((fa::bwd_dq_kernel<T, D, BN, 0, 4, false>), dim3(batch * nblk), dim3(256), 0, c.st, (const T*)c.q, (const T*)c.k,
-              (const T*)c.v, (const T*)c.dout, c.nlc(), c.delta(), c.dq, N, nqb, batch, lay, causal, c.tau, only_qb,
-              prep ? *prep : fa::DqPrep{});
-    if (BF && causal)   // rows 0..63 again with split operands
-      FA_LAUNCH((fa::bwd_dq_kernel<T, D, BN, 0, 4, BF>), dim3(batch), dim3(256), 0, c.st, (const T*)c.q, (const T*)c.k, (const T*)c.v,
-                (const T*)c.dout, c.nlc(), c.delta(), c.dq, N, nqb, batch, lay1, causal, c.tau, 0, fa::DqPrep{});
-  }
-#undef FA_DQ_LAUNCH
-  FA_HIP_TRY(hipGetLastError());
-  return FA_OK;
-}
-
-// The MFMA-slot dQ kernel.  Its mask-free builds carry both scalings and pick one per launch (Layout::scale_sel): no twin launch.
-template <typename T, int D>
-int dq_slot_launch(const Call& c, const fa::DqPrep* prep) {
-  // prep != nullptr: the launch also does the preprocess for its rows and writes the workspace (see dq_fuses_prep)
-  const int batch = c.batch, N = c.N, causal = c.causal;
-  const fa::DqPrep pa = prep ? *prep : fa::DqPrep{};
-  const int nqb = (N + 255) / 256;
-  fa::Layout lay = c.lay;
-  lay.rank_chunk = rank_chunk(1, nqb);
-  const bool paired = !causal_ranked(c.tun, batch * nqb, 1);
-  if (causal && N % 256 == 0) {   // causal build: unmasked sweep + the diagonal block per wave; one block per workgroup,
-    // longest first across all heads (paired: blocks p and nqb-1-p in one workgroup)
-    const dim3 grid(paired ? batch * ((nqb + 1) / 2) : batch * nqb);
-    FA_LAUNCH((fa::bwd_dq_slot_kernel<T, D, false, true>), grid, dim3(512), 0, c.st, (const T*)c.q, (const T*)c.k,
-              (const T*)c.v, (const T*)c.dout, c.nlc(), c.delta(), c.dq, N, nqb, batch, lay, paired ? 1 : 2, c.tau, pa);
-  } else if (!causal && N % 128 == 0) {   // no sub-tile needs a mask: the build without masked period variants
-    // (query block qb of several consecutive heads per workgroup: head_tiles, the rule of the tiled dK/dV launch)
-    if (const int tiles = head_tiles(c, nqb); tiles > 1) {
-      lay.tiles = tiles;
-      FA_LAUNCH((fa::bwd_dq_slot_kernel<T, D, false, false, true>), dim3((batch / tiles) * nqb), dim3(512), 0, c.st, (const T*)c.q,
-                (const T*)c.k, (const T*)c.v, (const T*)c.dout, c.nlc(), c.delta(), c.dq, N, nqb, batch, lay, causal, c.tau, pa);
-    } else {
-      FA_LAUNCH((fa::bwd_dq_slot_kernel<T, D, false>), dim3(batch * nqb), dim3(512), 0, c.st, (const T*)c.q, (const T*)c.k,
-                (const T*)c.v, (const T*)c.dout, c.nlc(), c.delta(), c.dq, N, nqb, batch, lay, causal, c.tau, pa);
-    }
-  } else {
-    FA_LAUNCH((fa::bwd_dq_slot_kernel<T, D>), dim3(batch * nqb), dim3(512), 0, c.st, (const T*)c.q, (const T*)c.k,
-              (const T*)c.v, (const T*)c.dout, c.nlc(), c.delta(), c.dq, N, nqb, batch, lay, causal, c.tau, fa::DqPrep{});
-  }
-  FA_HIP_TRY(hipGetLastError());
-  return FA_OK;
-}
-
-// Does a backward call that asks for the preprocess AND dQ fold the preprocess into its dQ launch (dQ is then launched BEFORE dK/dV,
-// which reads the workspace the dQ launch wrote)?  Yes whenever dq_stage sends the call to a plain main build: not under a key mask
-// or dropout, not bf16 with N < 64 (split-operand builds), not the bf16 d = 64 slot build with masked periods (no registers); option
-// 4 = 1 keeps the separate preprocess kernel (A/B).
 // fp32, d = 64, N >= 256, no key mask / dropout, dQ and dK/dV asked for together: the one-pass backward
 // (fa_bwd_onepass_f32.h: five products instead of the two-kernel path's seven, dQ by fp32 atomics) when its launch fills the chip:
 // one 8-wave workgroup per CU and 256-key block, so batch * ceil(N / 256) workgroups run in ceil(that / CUs) rounds; below one
@@ -495,216 +405,289 @@ bool dq64_phased(const Call& c) {
   return c.tun.v[2] == 2 || (c.causal && c.tun.v[2] != 3 && !(c.N % 256 == 0 && c.batch * (c.N / 256) >= 128));
 }
 
+// The dQ stage of a backward call: kernel selection by dtype / head dim / launch shape / options.
+// prep: the call asks for the preprocess AND dQ (and option 4 = 0: 1 keeps the separate preprocess kernel, A/B).  The launch then
+// preprocesses its own rows whenever the stage lands on a plain main build: not under a key mask or dropout, not bf16 with N < 64
+// (split-operand builds), not the bf16 d = 64 slot build with masked periods (no registers).  What was chosen is what is reported:
+// fuses_prep, and dQ is then launched BEFORE dK/dV, which reads the workspace the dQ launch wrote.
 template <typename T, int D>
-bool dq_fuses_prep(const Call& c) {
+Selection select_dq(const Call& c, bool prep) {
   constexpr bool BF = sizeof(T) == 2;
-  if (onepass_f32<T, D>(c)) return false;
-  const int need = FA_BWD_STAGE_PREP | FA_BWD_STAGE_DQ;
-  if ((c.stages & need) != need || c.tun.v[4] != 0 || c.lay.kmask || c.lay.drop_thr || (BF && c.N < 64)) return false;
-  if constexpr (BF && D == 64) {
-    if (!dq64_phased(c)) return c.causal ? c.N % 256 == 0 : c.N % 128 == 0;   // the slot kernel: its unmasked / causal builds only
-  }
-  return true;
-}
-
-// The dQ stage of a backward call: kernel selection by dtype / head dim / launch shape / options.  prep != nullptr: the launch also does
-// the preprocess for its rows (dq_fuses_prep decided that a plain main build runs).
-template <typename T, int D>
-int dq_stage(const Call& c, const fa::DqPrep* prep) {
-  // every launch the branches below do not take runs the phased kernel with 32-key tiles (bf16 d = 32: they run 3 waves/SIMD,
-  // measured 2 % faster), causal query blocks ranked by default at bf16 d = 32 (option 7)
-  const int ranked = c.tun.v[7] == 2 || (c.tun.v[7] == 0 && sizeof(T) == 2 && D == 32);
-  const bool few_keys = c.lay.kmask || c.lay.drop_thr || c.N < 64;   // (key mask and dropout live in the phased kernel)
-  if constexpr (sizeof(T) == 2 && D == 128) {
-    if (!c.causal && !few_keys) {   // non-causal default: 8 waves x 32 queries, one workgroup per CU (each staged K / V tile feeds
-      // twice the waves); otherwise 4 waves x 32 queries, two workgroups per CU
-      const int nqb = (c.N + 255) / 256;
-      FA_LAUNCH((fa::bwd_dq_kernel<T, D, 32, 0, 8>), dim3(c.batch * nqb), dim3(512), 0, c.st, (const T*)c.q, (const T*)c.k,
-                (const T*)c.v, (const T*)c.dout, c.nlc(), c.delta(), c.dq, c.N, nqb, c.batch, c.lay, c.causal, c.tau, -1,
-                prep ? *prep : fa::DqPrep{});
-      FA_HIP_TRY(hipGetLastError());
-      return FA_OK;
+  const int batch = c.batch, N = c.N, causal = c.causal;
+  Selection s;
+  const bool few_keys = c.lay.kmask || c.lay.drop_thr || N < 64;   // (key mask and dropout live in the phased kernel)
+  if (BF && D == 128 && !causal && !few_keys) {   // non-causal default: 8 waves x 32 queries, one workgroup per CU (each staged K / V
+    // tile feeds twice the waves); otherwise 4 waves x 32 queries, two workgroups per CU
+    const int nqb = (N + 255) / 256;
+    s.add(DQ_WAVE8, batch * nqb, 512, nqb, -1).prep = prep;
+  } else if (BF && D == 64 && !few_keys && !dq64_phased(c)) {   // d = 64: slot-interleaved three-deep pipeline (default).  Its mask-free
+    // builds carry both scalings and pick one per launch (Layout::scale_sel): no twin launch.
+    const int nqb = (N + 255) / 256;
+    Step* m;
+    if (causal && N % 256 == 0) {   // causal build: unmasked sweep + the diagonal block per wave; one block per workgroup,
+      // longest first across all heads (paired: blocks p and nqb-1-p in one workgroup)
+      const bool paired = !causal_ranked(c.tun, batch * nqb, 1);
+      m = &s.add(DQ_SLOT_CAUSAL, paired ? batch * ((nqb + 1) / 2) : batch * nqb, 512, nqb, paired ? 1 : 2);
+    } else if (!causal && N % 128 == 0) {   // no sub-tile needs a mask: the build without masked period variants
+      // (query block qb of several consecutive heads per workgroup: head_tiles, the rule of the tiled dK/dV launch)
+      const int tiles = head_tiles(c, nqb);
+      m = tiles > 1 ? &s.add(DQ_SLOT_TILED, (batch / tiles) * nqb, 512, nqb, causal) : &s.add(DQ_SLOT_WHOLE, batch * nqb, 512, nqb, causal);
+      m->tiles = tiles > 1 ? tiles : 0;
+    } else {
+      m = &s.add(DQ_SLOT_MASKED, batch * nqb, 512, nqb, causal);
+      prep = false;
     }
-  } else if constexpr (sizeof(T) == 2 && D == 64) {   // d = 64: slot-interleaved three-deep pipeline (default)
-    if (!few_keys && !dq64_phased(c)) {
-      const int rc = dq_slot_launch<T, D>(c, prep);
-      // the masked slot build forced onto a causal launch: rows 0..63 (few keys) are redone by the phased kernel's split-operand
-      // path (query block 0); the causal slot build (N a multiple of 256) splits them itself
-      if (!rc && c.causal && c.N % 256 != 0) return dq_launch<T, D, 32>(c, 0);
-      return rc;
-    }
+    m->prep = prep;
+    m->rank_chunk = rank_chunk(1, nqb);
+    // the masked slot build forced onto a causal launch: rows 0..63 (few keys) are redone by the phased kernel's split-operand
+    // path (query block 0); the causal slot build (N a multiple of 256) splits them itself
+    if (m->kern == DQ_SLOT_MASKED && causal) select_phased(s, c, BF, DQ_DROP, 0, 0, 0, false);
+  } else {
+    // every launch the branches above do not take runs the phased kernel with 32-key tiles (bf16 d = 32: they run 3 waves/SIMD,
+    // measured 2 % faster), causal query blocks ranked by default at bf16 d = 32 (option 7)
+    select_phased(s, c, BF, DQ_DROP, -1, 0, c.tun.v[7] == 2 || (c.tun.v[7] == 0 && BF && D == 32), prep);
   }
-  return dq_launch<T, D, 32>(c, -1, 0, prep, ranked);
+  s.fuses_prep = s.steps[0].prep;   // (only a stage's first launch ever takes it)
+  return s;
 }
 
 // The dK/dV stage of a backward call: kernel selection by dtype / head dim / launch shape / options.
 template <typename T, int D>
-int dkdv_stage(const Call& c) {
+Selection select_dkdv(const Call& c) {
+  constexpr bool BF = sizeof(T) == 2;
   const int batch = c.batch, N = c.N, causal = c.causal;
   const Tun& tun = c.tun;
-  if constexpr (sizeof(T) == 2 && D == 64) {
+  Selection s;
+  if (BF && D == 64) {
     // The continuous slot pipeline (no drain at stage boundaries, three-slot LDS-DMA ring) carries both scalings and picks one per
     // launch (Layout::scale_sel): no twin launch.  Option 0 = 4: the compiler-interleaved phased kernel below.
-    fa::Layout lay = c.lay;
-    if (!causal && tun.v[0] == 0 && !lay.drop_thr && !lay.kmask && N >= 64) {
+    const bool plain = !c.lay.drop_thr && !c.lay.kmask;
+    if (!causal && tun.v[0] == 0 && plain && N >= 64) {
       // d = 64, non-causal default: the continuous slot pipeline; rows thinned by a key mask or N < 64 go to the kernel below, whose
       // per-sub-slice path splits P and dS.  Key block kb of several consecutive heads per workgroup: head_tiles
-      const int nkb = (N + 255) / 256;
-      if (const int tiles = head_tiles(c, nkb); tiles > 1) {
-        lay.tiles = tiles;
-        FA_LAUNCH((fa::bwd_dkdv_slot_kernel<T, 64, false, true>), dim3((batch / tiles) * nkb), dim3(512), 0, c.st,
-                  (const T*)c.q, (const T*)c.k, (const T*)c.v, (const T*)c.dout, c.nl2(), c.delta(), c.dk, c.dv, N, nkb, batch, lay, c.tau);
-      } else {
-        FA_LAUNCH((fa::bwd_dkdv_slot_kernel<T, 64>), dim3(batch * nkb), dim3(512), 0, c.st, (const T*)c.q,
-                  (const T*)c.k, (const T*)c.v, (const T*)c.dout, c.nl2(), c.delta(), c.dk, c.dv, N, nkb, batch, lay, c.tau);
-      }
-      FA_HIP_TRY(hipGetLastError());
-      return FA_OK;
+      const int nkb = (N + 255) / 256, tiles = head_tiles(c, nkb);
+      if (tiles > 1) s.add(DKDV_SLOT_TILED, (batch / tiles) * nkb, 512, nkb).tiles = tiles;
+      else s.add(DKDV_SLOT, batch * nkb, 512, nkb);
+      return s;
     }
-    if (causal && !lay.drop_thr && !lay.kmask && N % 256 == 0 &&
-        (tun.v[0] == 5 || (tun.v[0] == 0 && batch * (N / 256) >= 128))) {   // (tuning key 0 = 5 forces it)
+    if (causal && plain && N % 256 == 0 && (tun.v[0] == 5 || (tun.v[0] == 0 && batch * (N / 256) >= 128))) {   // (tuning key 0 = 5 forces it)
       // d = 64, causal, N a multiple of 256: the causal build of the continuous pipeline (sweep of the stages below the
       // diagonal block, the block per wave, workgroups longest first); tuning key 0 = 3: the phased kernel below
       // (key blocks p and nkb-1-p of several consecutive heads per workgroup, a causal tiled build, gave bitwise the same results
       // 4-8 % slower: profiles/r04_causal_tiled_dkdv.txt)
       const int nkb = N / 256;
-      lay.rank_chunk = rank_chunk(1, nkb);
-      FA_LAUNCH((fa::bwd_dkdv_slot_kernel<T, 64, true>), dim3(batch * nkb), dim3(512), 0, c.st, (const T*)c.q,
-                (const T*)c.k, (const T*)c.v, (const T*)c.dout, c.nl2(), c.delta(), c.dk, c.dv, N, nkb, batch, lay, c.tau);
-      FA_HIP_TRY(hipGetLastError());
-      return FA_OK;
+      s.add(DKDV_SLOT_CAUSAL, batch * nkb, 512, nkb).rank_chunk = rank_chunk(1, nkb);
+      return s;
     }
     // d = 64, causal (or tuning 3): slot-interleaved fast path for unmasked stages, per-sub-slice path on the diagonal
     // (a build with the masked paths compiled out, for non-causal launches, measured the same: 0.4983 vs 0.4992 ms)
-    if (tun.v[0] != 4) return dkdv_launch<T, D, 32, 8, 128, 3>(c, 1);
+    if (tun.v[0] != 4) {
+      select_dkdv_phased<T, D>(s, c, true, 1);
+      return s;
+    }
   }
-  if constexpr (sizeof(T) == 2 && D <= 64) {
+  if (BF && D <= 64) {
     // measured at B=8,H=8,N=4096,d=64 (ms, one device, profiles/README.md): 8 waves x 32 keys, 128-query stages,
     // software-pipelined sub-slices 0.505; not pipelined 0.514; 64-query stages 0.519; 256-query 0.525;
     // 4 waves x 32 keys (two workgroups per CU) 0.521; 4 waves x 64 keys (one wave per SIMD) 0.559
-    return dkdv_launch<T, D, 32, 8, 128, 0>(c);   // compiler-interleaved software pipeline (the d = 32 default; d = 64: option 0 = 4)
-  } else if constexpr (sizeof(T) == 2) {
-    // d = 128 default (dropout / key mask / N < 64: dkdv_launch runs the 4-wave split-operand build, which has the registers for it): 8 waves x 32 keys, one 256-key workgroup per CU (half the Q / dO staging per MFMA): 3.64 vs 3.92 ms
-    return dkdv_launch<T, D, 32, 8, 64>(c, 0, tun.v[7] != 1);
-  } else if constexpr (D == 64) {
+    select_dkdv_phased<T, D>(s, c);   // compiler-interleaved software pipeline (the d = 32 default; d = 64: option 0 = 4)
+  } else if (BF) {
+    // d = 128 default (dropout / key mask / N < 64: the 4-wave split-operand build, which has the registers for it): 8 waves x 32 keys,
+    // one 256-key workgroup per CU (half the Q / dO staging per MFMA): 3.64 vs 3.92 ms
+    select_dkdv_phased<T, D>(s, c, false, 0, tun.v[7] != 1);
+  } else if (D == 64 && !c.lay.drop_thr) {
     // fp32, d = 64 (configs[1], [2]): the allocation lands on 256 VGPRs + 2 AGPRs = one wave per SIMD; asking for two
     // (launch bound) keeps it under 256
-    if (c.lay.drop_thr) return dkdv_launch<T, D, 32, 4, 32, 0, true>(c);
     const int nkb = (N + 127) / 128;
-    fa::Layout lay = c.lay;
     // causal: longest block first across a chunk of heads instead of head by head: 0.57 vs 0.80 ms at the reference's timing-harness
     // shape (B = 8, H = 8, N = 2048, fp32), bitwise the same (option 7 = 1: head by head)
-    if (causal && tun.v[7] != 1) lay.rank_chunk = rank_chunk(2, nkb);
-    FA_LAUNCH((fa::bwd_dkdv_kernel<T, D, 32, 4, 32, 0, false, 2>), dim3(batch * nkb), dim3(256), 0, c.st,
-              (const T*)c.q, (const T*)c.k, (const T*)c.v, (const T*)c.dout, c.nlc(), c.delta(), c.dk, c.dv, N, nkb, batch, lay,
-              causal, c.tau);
-    FA_HIP_TRY(hipGetLastError());
-    return FA_OK;
+    s.add(DKDV_F32_64, batch * nkb, 256, nkb).rank_chunk = (causal && tun.v[7] != 1) ? rank_chunk(2, nkb) : 0;
   } else {
-    return dkdv_launch<T, D, 32, 4, 32>(c);
+    select_dkdv_phased<T, D>(s, c);
   }
+  return s;
 }
 
 template <typename T, int D>
-int bwd_launch(const Call& c) {
+Selection select_bwd(const Call& c) {
   const long rows = (long)c.batch * c.N;
   constexpr int RPB = 256 / (D / 8);
-  const bool fuse_prep = dq_fuses_prep<T, D>(c);
-  if ((c.stages & FA_BWD_STAGE_PREP) && !fuse_prep) {
-    FA_LAUNCH((fa::bwd_prep_kernel<T, D>), dim3((unsigned)((rows + RPB - 1) / RPB)), dim3(256), 0, c.st, c.out,
-              (const T*)c.dout, c.l, c.m, c.nlc(), c.delta(), c.nl2(), rows, c.N, c.lay, c.variant, 1.0f / c.tau);
-    FA_HIP_TRY(hipGetLastError());
+  const int need = FA_BWD_STAGE_PREP | FA_BWD_STAGE_DQ;
+  Selection s, dq;
+  s.onepass = onepass_f32<T, D>(c);
+  if ((c.stages & FA_BWD_STAGE_DQ) && !s.onepass) dq = select_dq<T, D>(c, (c.stages & need) == need && c.tun.v[4] == 0);
+  s.fuses_prep = dq.fuses_prep;
+  if ((c.stages & FA_BWD_STAGE_PREP) && !s.fuses_prep) s.add(BWD_PREP, (int)((rows + RPB - 1) / RPB), 256);
+  if (s.fuses_prep) s.append(dq);   // dQ first: it preprocesses its own rows and leaves -L/tau, -delta in the workspace for the dK/dV kernel
+  if (s.onepass) {
+    // the workgroups ADD into dq (the reference's caller zeroes q_grad for its atomicAdd as well: minitorch/cuda_kernel_ops.py:609-611);
+    // the parts of a key block's sweep ADD their dK, dV
+    s.add(ZERO_GRADS, 0, 0, 0, s.onepass);
+    const int nkb = (c.N + 255) / 256;
+    s.add(ONEPASS, c.batch * nkb * s.onepass, 512, nkb, s.onepass).rank_chunk =
+        c.causal ? rank_chunk(1, nkb) : 0;   // key block 0 (the longest sweep) of a chunk of heads first
+    return s;
   }
-  if (fuse_prep) {   // dQ first: it preprocesses its own rows and leaves -L/tau, -delta in the workspace for the dK/dV kernel
-    const fa::DqPrep pa{c.out, c.l, c.m, c.nlc(), c.delta(), c.nl2(), c.variant, 1.0f / c.tau};
-    if (const int rc = dq_stage<T, D>(c, &pa)) return rc;
-  }
-  if constexpr (sizeof(T) == 4 && D == 64) {
-    if (const int nsplit = onepass_f32<T, D>(c)) {
-      // the workgroups ADD into dq (the reference's caller zeroes q_grad for its atomicAdd as well: minitorch/cuda_kernel_ops.py:609-611);
-      // [B][N][H][d] or [BH][N][d]: the tensor is one contiguous range either way
-      if (!t_probe && !t_plan) {
+  if (c.stages & FA_BWD_STAGE_DKDV) s.append(select_dkdv<T, D>(c));
+  if (!s.fuses_prep) s.append(dq);
+  return s;
+}
+
+// The one executor: walks a selection and launches.  Which builds exist for <T, D> is decided here, by the if constexpr around each
+// typed launch (fp32 d = 64 has no plain phased dK/dV build: its dropout calls alone come to that geometry).
+template <typename T, int D>
+int execute(const Call& c, const Selection& sel) {
+  constexpr bool BF = sizeof(T) == 2;
+  constexpr int BN = BF ? 64 : 32, NW = BF ? 8 : 4, QS = BF ? (D == 128 ? 64 : 128) : 32;   // forward key tile; phased dK/dV geometry
+  const int batch = c.batch, N = c.N, causal = c.causal;
+  const long rows = (long)batch * N;
+#define FA_GO(kern, ...) hipLaunchKernelGGL(kern, dim3(s.grid), dim3(s.block), 0, c.st, __VA_ARGS__)
+#define FA_QKV (const T*)c.q, (const T*)c.k, (const T*)c.v
+#define FA_FWD(FEAT, CARE) \
+  FA_GO((fa::fwd_kernel<T, D, BN, 1, FEAT, CARE>), FA_QKV, c.out, c.l, c.m, N, s.nb, batch, lay, causal, c.variant, c.tau, s.arg)
+#define FA_FWD_SLOT(...) FA_GO((fa::fwd_slot_kernel<__VA_ARGS__>), FA_QKV, c.out, c.l, N, s.nb, batch, lay, s.arg, c.tau)
+#define FA_DQ(FEAT, NWQ, ...)                                                                                                    \
+  FA_GO((fa::bwd_dq_kernel<T, D, 32, FEAT, NWQ, ##__VA_ARGS__>), FA_QKV, (const T*)c.dout, c.nlc(), c.delta(), c.dq, N, s.nb, batch, lay, \
+        causal, c.tau, s.arg, pa)
+#define FA_DQ_SLOT(...)                                                                                                            \
+  FA_GO((fa::bwd_dq_slot_kernel<T, D, ##__VA_ARGS__>), FA_QKV, (const T*)c.dout, c.nlc(), c.delta(), c.dq, N, s.nb, batch, lay, s.arg, \
+        c.tau, pa)
+#define FA_DKDV_SLOT(...)                                                                                                         \
+  FA_GO((fa::bwd_dkdv_slot_kernel<T, 64, ##__VA_ARGS__>), FA_QKV, (const T*)c.dout, c.nl2(), c.delta(), c.dk, c.dv, N, s.nb, batch, lay, \
+        c.tau)
+#define FA_DKDV(...)                                                                                                               \
+  FA_GO((fa::bwd_dkdv_kernel<T, D, 32, __VA_ARGS__>), FA_QKV, (const T*)c.dout, c.nlc(), c.delta(), c.dk, c.dv, N, s.nb, batch, lay, \
+        causal, c.tau, s.arg)
+#define FA_ONEPASS(C, R)                                                                                                         \
+  FA_GO((fa::bwd_onepass_f32_kernel<D, C, R>), FA_QKV, (const T*)c.dout, c.nlc(), c.delta(), c.dq, c.dk, c.dv, N, s.nb, batch, lay, \
+        c.tau, s.arg)
+  for (int i = 0; i < sel.n; ++i) {
+    const Step& s = sel.steps[i];
+    fa::Layout lay = c.lay;
+    lay.rank_chunk = s.rank_chunk;
+    lay.tiles = s.tiles;
+    lay.twin_blocks = s.twin_blocks;
+    lay.guard_want = s.guard_want;
+    const fa::DqPrep pa = s.prep ? fa::DqPrep{c.out, c.l, c.m, c.nlc(), c.delta(), c.nl2(), c.variant, 1.0f / c.tau} : fa::DqPrep{};
+    switch (s.kern) {
+      case FWD_SPLITK:
+        if constexpr (!BF && D == 64)
+          FA_GO((fa::fwd_splitk_f32_kernel<D>), FA_QKV, c.out, c.l, c.m, N, s.nb, batch, lay, causal, c.variant, c.tau);
+        break;
+      case FWD_SLOT_CAUSAL:
+        if constexpr (BF && D >= 64) FA_FWD_SLOT(T, D, false, 64, (D == 64 ? 4 : 2), true);
+        break;
+      case FWD_SLOT_WHOLE:
+        if constexpr (BF && D == 64) FA_FWD_SLOT(T, 64, false, 64, 4);
+        else if constexpr (BF && D == 128) FA_FWD_SLOT(T, D, false);
+        break;
+      case FWD_SLOT_MASKED:
+        if constexpr (BF && D == 64) FA_FWD_SLOT(T, D, true);
+        break;
+      case FWD_DROP: FA_FWD(2, BF); break;
+      case FWD_MASK: FA_FWD(1, BF); break;
+      case FWD_CARE: FA_FWD(0, BF); break;
+      case FWD_MAIN: FA_FWD(0, false); break;
+      case BWD_PREP:
+        FA_GO((fa::bwd_prep_kernel<T, D>), c.out, (const T*)c.dout, c.l, c.m, c.nlc(), c.delta(), c.nl2(), rows, N, lay, c.variant,
+              1.0f / c.tau);
+        break;
+      case DQ_DROP: FA_DQ(2, 4, BF); break;
+      case DQ_MASK: FA_DQ(1, 4, BF); break;
+      case DQ_CARE: FA_DQ(0, 4, BF); break;
+      case DQ_MAIN: FA_DQ(0, 4, false); break;
+      case DQ_WAVE8:
+        if constexpr (BF && D == 128) FA_DQ(0, 8);
+        break;
+      case DQ_SLOT_CAUSAL:
+        if constexpr (BF && D == 64) FA_DQ_SLOT(false, true);
+        break;
+      case DQ_SLOT_TILED:
+        if constexpr (BF && D == 64) FA_DQ_SLOT(false, false, true);
+        break;
+      case DQ_SLOT_WHOLE:
+        if constexpr (BF && D == 64) FA_DQ_SLOT(false);
+        break;
+      case DQ_SLOT_MASKED:
+        if constexpr (BF && D == 64) FA_DQ_SLOT();
+        break;
+      case DKDV_SLOT_TILED:
+        if constexpr (BF && D == 64) FA_DKDV_SLOT(false, true);
+        break;
+      case DKDV_SLOT:
+        if constexpr (BF && D == 64) FA_DKDV_SLOT();
+        break;
+      case DKDV_SLOT_CAUSAL:
+        if constexpr (BF && D == 64) FA_DKDV_SLOT(true);
+        break;
+      case DKDV_CARE_DROP:
+        if constexpr (BF) FA_DKDV(4, 64, 1, true, 1, BF);
+        break;
+      case DKDV_CARE:
+        if constexpr (BF) FA_DKDV(4, 64, 1, false, 1, BF);
+        break;
+      case DKDV_DROP_F32:
+        if constexpr (!BF) FA_DKDV(NW, QS, 1, true);
+        break;
+      case DKDV_CARE_MAIN:
+        if constexpr (BF && D == 64) FA_DKDV(NW, QS, 3, false, 1, true, true);
+        break;
+      case DKDV_PAIRED:
+        if constexpr (!(BF && D == 128) && !(!BF && D == 64)) FA_DKDV(NW, QS, 0, false, 1, false, true);
+        break;
+      case DKDV_PAIRED_M3:
+        if constexpr (BF && D == 64) FA_DKDV(NW, QS, 3, false, 1, false, true);
+        break;
+      case DKDV_PLAIN:
+        if constexpr (!(!BF && D == 64)) FA_DKDV(NW, QS, 0);
+        break;
+      case DKDV_F32_64:
+        if constexpr (!BF && D == 64)
+          FA_GO((fa::bwd_dkdv_kernel<T, D, 32, 4, 32, 0, false, 2>), FA_QKV, (const T*)c.dout, c.nlc(), c.delta(), c.dk, c.dv, N, s.nb,
+                batch, lay, causal, c.tau);
+        break;
+      case ONEPASS:
+        if constexpr (!BF && D == 64) {
+          if (N % 256 == 0) {
+            if (causal) FA_ONEPASS(true, false); else FA_ONEPASS(false, false);
+          } else {
+            if (causal) FA_ONEPASS(true, true); else FA_ONEPASS(false, true);
+          }
+        }
+        break;
+      case GUARD_PASS:
+      case GUARD_PASS_ZERO:
+        if (const int rc = launch_scale_guard(c.q, c.k, rows, c.dp, c.dtype, const_cast<float*>(c.guard), c.st)) return rc;
+        continue;
+      case GUARD_ZERO:
+        FA_HIP_TRY(hipMemsetAsync(const_cast<float*>(c.guard), 0, (size_t)2 * fa::GUARD_SLOTS * sizeof(float), c.st));
+        continue;
+      case ZERO_GRADS:   // [B][N][H][d] or [BH][N][d]: the tensor is one contiguous range either way
         FA_HIP_TRY(hipMemsetAsync(c.dq, 0, (size_t)rows * D * sizeof(float), c.st));
-        if (nsplit > 1) {   // the parts of a key block's sweep ADD their dK, dV
+        if (s.arg > 1) {
           FA_HIP_TRY(hipMemsetAsync(c.dk, 0, (size_t)rows * D * sizeof(float), c.st));
           FA_HIP_TRY(hipMemsetAsync(c.dv, 0, (size_t)rows * D * sizeof(float), c.st));
         }
-      }
-      const int nkb = (c.N + 255) / 256;
-      fa::Layout lay = c.lay;
-      if (c.causal) lay.rank_chunk = rank_chunk(1, nkb);   // key block 0 (the longest sweep) of a chunk of heads first
-#define FA_ONEPASS(C, R)                                                                                                             \
-  FA_LAUNCH((fa::bwd_onepass_f32_kernel<D, C, R>), dim3((unsigned)(c.batch * nkb * nsplit)), dim3(512), 0, c.st, (const float*)c.q,   \
-            (const float*)c.k, (const float*)c.v, (const float*)c.dout, c.nlc(), c.delta(), c.dq, c.dk, c.dv, c.N, nkb, c.batch, lay,   \
-            c.tau, nsplit)
-      if (c.N % 256 == 0) {
-        if (c.causal) FA_ONEPASS(true, false); else FA_ONEPASS(false, false);
-      } else {
-        if (c.causal) FA_ONEPASS(true, true); else FA_ONEPASS(false, true);
-      }
-#undef FA_ONEPASS
-      FA_HIP_TRY(hipGetLastError());
-      return FA_OK;
+        continue;
     }
+    if (s.check) FA_HIP_TRY(hipGetLastError());
   }
-  if (c.stages & FA_BWD_STAGE_DKDV)
-    if (const int rc = dkdv_stage<T, D>(c)) return rc;
-  if ((c.stages & FA_BWD_STAGE_DQ) && !fuse_prep)
-    if (const int rc = dq_stage<T, D>(c, nullptr)) return rc;
+#undef FA_GO
+#undef FA_QKV
+#undef FA_FWD
+#undef FA_FWD_SLOT
+#undef FA_DQ
+#undef FA_DQ_SLOT
+#undef FA_DKDV_SLOT
+#undef FA_DKDV
+#undef FA_ONEPASS
   return FA_OK;
 }
-
-#define FA_DISPATCH(FN)                                                                   \
-  do {                                                                                    \
-    if (c.dtype == FA_DTYPE_BF16) {                                                       \
-      if (c.dp == 32) return FN<fa::bf16_t, 32>(c);                                       \
-      if (c.dp == 64) return FN<fa::bf16_t, 64>(c);                                       \
-      return FN<fa::bf16_t, 128>(c);                                                      \
-    } else {                                                                              \
-      if (c.dp == 32) return FN<float, 32>(c);                                            \
-      if (c.dp == 64) return FN<float, 64>(c);                                            \
-      return FN<float, 128>(c);                                                           \
-    }                                                                                     \
-  } while (0)
-int fwd_dispatch_one(const Call& c) { FA_DISPATCH(fwd_launch); }
-int bwd_dispatch_one(const Call& c) { FA_DISPATCH(bwd_launch); }
-#undef FA_DISPATCH
 
 // tau uses the caller's d even when the rows are zero-padded to dp columns (zero columns of Q/K add
 // nothing to the scores; zero columns of V produce zero output columns that are dropped).
 fa::Layout bhnd(int N, int dp) { return fa::Layout{1, dp, (long)N * dp, 0, nullptr, 1, 0u, 1.0f, 0u, 0}; }
 fa::Layout bnhd(int H, int N, int dp) { return fa::Layout{H, H * dp, (long)N * H * dp, (long)dp, nullptr, 1, 0u, 1.0f, 0u, 0}; }
-
-int launch_scale_guard(const void* q, const void* k, long rows, int row_elems, int dtype, void* guard, hipStream_t st) {
-  // only bf16 rows of 64 / 128 elements ever reach a kernel that folds the scale into an operand: everything else gets an all-zero
-  // guard ("within the budget"; those calls run fp32-scaling kernels whatever it says)
-  if (dtype != FA_DTYPE_BF16 || (row_elems != 64 && row_elems != 128)) {
-    FA_HIP_TRY(hipMemsetAsync(guard, 0, (size_t)2 * fa::GUARD_SLOTS * sizeof(float), st));
-    return FA_OK;
-  }
-  if (plan_mode()) {
-    if (t_plan) t_plan->emplace_back("scale_guard_kernel");
-    return FA_OK;
-  }
-  const dim3 grid(fa::GUARD_SLOTS, 2);
-  if (row_elems == 64)
-    hipLaunchKernelGGL((fa::scale_guard_kernel<64>), grid, dim3(256), 0, st, (const fa::bf16_t*)q, (const fa::bf16_t*)k, rows, (float*)guard);
-  else
-    hipLaunchKernelGGL((fa::scale_guard_kernel<128>), grid, dim3(256), 0, st, (const fa::bf16_t*)q, (const fa::bf16_t*)k, rows, (float*)guard);
-  FA_HIP_TRY(hipGetLastError());
-  return FA_OK;
-}
-
-// produce: a folding forward fills the call's guard inside its own launch, into the zeroed buffer ...
-int zero_guard(const Call& c) {
-  if (t_plan) { t_plan->emplace_back("memset"); return FA_OK; }
-  FA_HIP_TRY(hipMemsetAsync(const_cast<float*>(c.guard), 0, (size_t)2 * fa::GUARD_SLOTS * sizeof(float), c.st));
-  return FA_OK;
-}
-// ... any other forward by the separate pass over q and k
-int guard_pass(const Call& c) {
-  return launch_scale_guard(c.q, c.k, (long)c.batch * c.N, c.dp, c.dtype, const_cast<float*>(c.guard), c.st);
-}
 
 // ---- where tau*log2(e) is applied (round 4) -------------------------------------------------------------------------------------
 // The MFMA-slot kernels fold c = tau*log2(e) into one bf16 operand (one more 2^-9 relative rounding of q or k, worth 8-10 % of the
@@ -718,72 +701,81 @@ int guard_pass(const Call& c) {
 //   * a call WITHOUT one scales in fp32 (the phased forward; the backward's slot kernels carry both scalings in one launch and
 //     take their fp32 copy of the sweep: no twin launches in the backward at all), unless
 //     option 8 = 1 (the caller vouches for the range), the selection folds nothing anyway (fp32, d = 32, key mask, dropout, ragged N:
-//     probed with a dry run of the dispatch code), or c is 1 (softmax_scale = ln 2: the operand multiply is exact).
+//     Selection::folds), or c is 1 (softmax_scale = ln 2: the operand multiply is exact).
 constexpr float GUARD_BUDGET = 1e-2f;
 inline Call exact(Call call) {   // the forward that scales every score in fp32 (the phased kernel), whatever else the caller selected
   call.tun.v[1] = 2;
   return call;
 }
+template <typename T, int D>
+Selection select_one(const Call& c) { return c.bwd ? select_bwd<T, D>(c) : select_fwd<T, D>(c); }
+
+// Everything one call runs, in order; completes call.lay (scale_sel, guard, guard_coef; guard_want belongs to the steps).
 // produce (forward calls only, option 8 = 0): the call FILLS `guard` instead of reading it, so that the backward of the same (q, k)
 // can take it: a forward that folds produces it inside its own launch (fa_common.h: guard_produce: no separate pass over q and k;
 // the launch runs with the folded scale and its fp32-scaling twin, behind it, redoes the call if the finished guard says so);
-// a forward whose selection folds nothing runs the separate pass (guard_pass), because the backward of the same call may fold.
-int run_scaled(Call call, int (*run)(const Call&)) {
+// a forward whose selection folds nothing runs the separate pass, because the backward of the same call may fold.
+// planning: fa_mi355x_plan is asking (option 8 = 3 then plans a guarded call; a real call has its guard or none).
+template <typename T, int D>
+Selection select_call(Call& call, bool planning) {
   const float c = call.tau * fa::LOG2E;
   const int mode = call.tun.v[8], produce = call.produce;
   const float* guard = call.guard;
   fa::Layout& lay = call.lay;
   lay.scale_sel = 0;
-  if (mode == 1 || fabsf(c - 1.0f) < 1e-6f) return run(call);
-  if (mode == 3 && t_plan) guard = reinterpret_cast<const float*>(16);   // fa_mi355x_plan: both launches of a guarded call
+  const Selection sel = select_one<T, D>(call);
+  if (mode == 1 || fabsf(c - 1.0f) < 1e-6f) return sel;
+  if (mode == 3 && planning) guard = reinterpret_cast<const float*>(16);   // both launches of a guarded call
   // the backward's MFMA-slot kernels hold both scalings in one launch: fp32 scaling without a guard, the guard's choice with one
   lay.scale_sel = (mode == 2 || !guard) ? 1 : 2;
   if (lay.scale_sel == 2) {
     lay.guard = guard;
     lay.guard_coef = c * (0.001953125f * 0.57735027f) / GUARD_BUDGET;
-    lay.guard_want = 3;   // (no launch of this run is skipped)
   }
-  if (!plan_mode() || t_plan) {   // does the selection fold at all?  (dry run: no launch, no HIP call, nothing recorded)
-    std::vector<std::string>* keep = t_plan;
-    t_plan = nullptr;
-    t_probe = true;
-    t_fold = t_fold_produces = false;
-    const int rc = run(call);
-    t_probe = false;
-    t_plan = keep;
-    if (rc) return rc;
-    if (!t_fold) {
-      if (produce && guard && mode == 0)
-        if (const int rc2 = guard_pass(call)) return rc2;
-      return run(call);
-    }
+  // ... any forward that cannot fill the guard itself by the separate pass over q and k
+  const Kern pass = guard_rows_fold(call.dtype, call.dp) ? GUARD_PASS : GUARD_PASS_ZERO;
+  Selection out;
+  if (!sel.folds) {
+    if (produce && guard && mode == 0) out.add(pass, 0, 0);
+    out.append(sel, lay.scale_sel == 2 ? 3 : 0);   // (guard_want 3: no launch of this run is skipped)
+    return out;
   }
-  if (mode == 2 || !guard) return run(exact(call));
-  lay.guard = guard;
-  lay.guard_coef = c * (0.001953125f * 0.57735027f) / GUARD_BUDGET;
-  if (produce && t_fold_produces) {
-    if (const int rc = zero_guard(call)) return rc;
-    lay.guard_want = 2;
-  } else {
-    if (produce)   // (a folding forward that cannot fill the guard itself: the causal slot build)
-      if (const int rc = guard_pass(call)) return rc;
-    lay.guard_want = 0;
-  }
-  if (const int rc = run(call)) return rc;
-  lay.guard_want = 1;
-  return run(exact(call));
+  if (mode == 2 || !guard) return select_one<T, D>(exact(call));
+  if (produce && sel.produces_guard) out.add(GUARD_ZERO, 0, 0);   // the folding forward fills the zeroed buffer
+  else if (produce) out.add(pass, 0, 0);                         // (a folding forward that cannot: the causal slot build)
+  out.append(sel, (produce && sel.produces_guard) ? 2 : 0);
+  lay.guard_want = 1;   // (the twin's launch shape depends on it: select_phased)
+  out.append(select_one<T, D>(exact(call)), 1);
+  return out;
 }
 
-int fwd_dispatch(Call c) {
+#define FA_DISPATCH(FN, ...)                                                              \
+  do {                                                                                    \
+    if (c.dtype == FA_DTYPE_BF16) {                                                       \
+      if (c.dp == 32) return FN<fa::bf16_t, 32>(__VA_ARGS__);                             \
+      if (c.dp == 64) return FN<fa::bf16_t, 64>(__VA_ARGS__);                             \
+      return FN<fa::bf16_t, 128>(__VA_ARGS__);                                            \
+    } else {                                                                              \
+      if (c.dp == 32) return FN<float, 32>(__VA_ARGS__);                                  \
+      if (c.dp == 64) return FN<float, 64>(__VA_ARGS__);                                  \
+      return FN<float, 128>(__VA_ARGS__);                                                 \
+    }                                                                                     \
+  } while (0)
+Selection select_any(Call& c, bool planning) {
   c.tau = c.scale > 0.f ? c.scale : sqrtf(1.0f / (float)c.d);   // (scale: fa_mi355x_*_scaled / _guarded; the reference has sqrt(1/d) only)
-  c.lay.out_bf16 = c.tun.v[9] == 1 ? 1 : 0;
-  return run_scaled(c, fwd_dispatch_one);
+  if (!c.bwd) c.lay.out_bf16 = c.tun.v[9] == 1 ? 1 : 0;
+  FA_DISPATCH(select_call, c, planning);
 }
+int execute_any(const Call& c, const Selection& sel) { FA_DISPATCH(execute, c, sel); }
+#undef FA_DISPATCH
 
-int bwd_dispatch(Call c) {
-  c.tau = c.scale > 0.f ? c.scale : sqrtf(1.0f / (float)c.d);
-  return run_scaled(c, bwd_dispatch_one);
+int dispatch(Call c, bool bwd) {
+  c.bwd = bwd;
+  const Selection sel = select_any(c, false);
+  return execute_any(c, sel);
 }
+int fwd_dispatch(const Call& c) { return dispatch(c, false); }
+int bwd_dispatch(const Call& c) { return dispatch(c, true); }
 
 // The checks of every device entry point, in one order: the first that fails decides the return code and fa_mi355x_last_error().
 // The rules that differ between entry points are the call's fields (bwd, by_heads, padded, scale_required; arguments an entry point
@@ -1098,7 +1090,7 @@ int fa_mi355x_measure_mfma_peak(double min_ms, double* tflops, double* clock_ghz
 
 int fa_mi355x_plan(int batch, int N, int d, int causal, int variant, int dtype, int stages, const int* opts, int nopts, char* out,
                    size_t n) {
-  // the dispatch functions only pass their pointers on to the (skipped) launches: any non-null values do
+  // the selectors only pass the call's pointers on to the steps, which are not executed here: any non-null values do
   float* one = reinterpret_cast<float*>(16);
   Call c = bwd_call(one, one, one, one, one, one, one, one, one, one, one, batch, N, d, causal, variant, dtype, stages, nullptr);
   c.bwd = stages != 0;   // stages = 0: the forward
@@ -1106,13 +1098,10 @@ int fa_mi355x_plan(int batch, int N, int d, int causal, int variant, int dtype, 
   c.nopts = nopts;
   if (int rc = validate(c)) return rc;
   if (!out || n == 0) return set_err(FA_ERR_BAD_ARG, "null output buffer");
-  std::vector<std::string> names;
-  t_plan = &names;
-  const int rc = c.bwd ? bwd_dispatch(c) : fwd_dispatch(c);
-  t_plan = nullptr;
-  if (rc) return rc;
+  const Selection sel = select_any(c, true);   // built exactly as a real call builds it
   std::string joined;
-  for (size_t i = 0; i < names.size(); ++i) joined += (i ? ";" : "") + names[i];
+  for (int i = 0; i < sel.n; ++i)
+    if (const char* name = KERN_NAME[sel.steps[i].kern]) joined += (joined.empty() ? "" : ";") + std::string(name);
   if (joined.size() + 1 > n) return set_err(FA_ERR_BAD_ARG, "plan buffer too small");
   memcpy(out, joined.c_str(), joined.size() + 1);
   return FA_OK;

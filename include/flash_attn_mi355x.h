@@ -220,8 +220,8 @@ int fa_mi355x_bwd_padded(const void* q, const void* k, const void* v, const floa
                          float* k_grad, float* v_grad, const float* l, const float* m, void* workspace, int batch, int N, int d,
                          int dp, int causal, int variant, int dtype, void* stream);
 
-/* Which kernels would a call launch, in order?  Runs the library's own dispatch code with the launches skipped (no HIP call, works
- * without a GPU except for launch-size rules that read the CU count: 256 is assumed then) and writes the kernel names, separated by
+/* Which kernels would a call launch, in order?  Builds the selection exactly as a real call builds it and does not execute it (no HIP
+ * call, works without a GPU except for launch-size rules that read the CU count: 256 is assumed then); writes the kernel names, separated by
  * ';', to out[0..n-1] (NUL terminated), e.g. "bwd_dq_slot_kernel;bwd_dkdv_slot_kernel".  stages = 0: the forward (fa_mi355x_fwd_ex);
  * otherwise the backward stage mask of fa_mi355x_bwd_ex.  A backward plan without "bwd_prep_kernel" means the dQ launch does the
  * preprocess (and therefore runs first).  bench.py labels its per-kernel timings and its roofline from this. */

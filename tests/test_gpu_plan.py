@@ -1,4 +1,4 @@
-"""The kernel plan (fa_mi355x_plan) is the library's own dispatch code with the launches skipped; bench.py labels its per-kernel
+"""The kernel plan (fa_mi355x_plan) is the selection a real call computes and executes, read instead of executed; bench.py labels its per-kernel
 timings and its roofline from it (bench.stage_plan).  Checked here on the GPU box (the launch-size rules read the CU count): the plan
 of the three shapes the bench line reports, and that bench.py's stage list is built from exactly those names."""
 import os
