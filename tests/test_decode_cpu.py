@@ -1,6 +1,7 @@
 """CPU-side checks of the KV-cache decode library (include/flash_attn_mi355x_decode.h): exported symbols, the gfx950 code object
-without scratch, argument validation before any HIP call, the split policy, the Python entry point's checks, and this file's fp64
-decode reference (used by tests/test_gpu_decode.py) against the dense oracle."""
+without scratch, argument validation before any HIP call, the split policy (with the split counts that the shapes of
+tests/test_gpu_decode_edges.py rely on), the Python entry point's checks, and this file's fp64 decode reference (used by
+tests/test_gpu_decode.py) against the dense oracle."""
 import ctypes
 import os
 import re
@@ -135,6 +136,34 @@ def test_split_policy_is_pure_and_sizes_the_workspace(built):
     assert lib.fa_mi355x_decode_splits(32, 32, 1, 4096, 128, 1) == 1
     assert lib.fa_mi355x_decode_splits(0, 2, 1, 65536, 128, 1) == 0
     assert lib.fa_mi355x_decode_workspace_bytes(1, 2, 0, 65536, 128) == 0
+
+
+def test_split_counts_that_the_gpu_edge_cases_rely_on(built):
+    """tests/test_gpu_decode_edges.py picks its shapes for the path the policy sends them down; the same counts, checked wherever
+    the library builds.  (B, H, Hkv, Nq, Ncap, d) -> splits."""
+    lib = built.decode()
+    want = [((3, 2, 2, 33, 256, 64), 1),            # a cache of one chunk
+            ((128, 8, 8, 1, 700, 64), 1),           # 1024 workgroups without splitting: one chunk of six super tiles
+            ((128, 8, 8, 3, 700, 128), 1),
+            ((128, 32, 8, 1, 700, 64), 1),          # the same, four heads per kv head
+            ((16, 8, 8, 1, 8192, 128), 8),          # chunks of 1024 keys
+            ((16, 8, 8, 5, 8192, 64), 8),
+            ((40, 2, 2, 1, 1300, 64), 6),           # chunks of 256 keys, one and two row blocks
+            ((40, 2, 2, 33, 1300, 64), 6),
+            ((1, 8, 8, 1, 1048447, 128), 128),      # the largest batch element the 2 GiB check admits: chunks of 8192 keys
+            ((2, 71, 1, 1, 520, 64), 3),            # one query's 71 heads: three row blocks
+            ((6, 71, 1, 11, 520, 128), 3),
+            ((6, 28, 4, 128, 520, 64), 2),          # 28 row blocks per kv head: 672 workgroups per split, chunks of 512
+            ((1, 4096, 1, 128, 64, 32), 1)]
+    for (B, H, Hkv, Nq, Ncap, d), ns in want:
+        for dt in (0, 1):
+            assert lib.fa_mi355x_decode_splits_gqa(B, H, Hkv, Nq, Ncap, d, dt) == ns, (B, H, Hkv, Nq, Ncap, d)
+            if H == Hkv:
+                assert lib.fa_mi355x_decode_splits(B, H, Nq, Ncap, d, dt) == ns, (B, H, Nq, Ncap, d)
+        assert lib.fa_mi355x_decode_workspace_bytes_gqa(B, H, Hkv, Nq, Ncap, d) == (0 if ns == 1 else B * H * ns * Nq * (d + 2) * 4)
+    # one row more and the 2 GiB check refuses the cache before any HIP call
+    assert _call(lib, B=1, H=8, Nq=1, Ncap=1048447 + 1, d=128, ws=_ONE) == 1
+    assert "2 GiB" in lib.fa_mi355x_decode_last_error().decode()
 
 
 def test_flash_attn_decode_python_checks(built):

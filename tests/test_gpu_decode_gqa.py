@@ -17,11 +17,15 @@ from test_gpu_decode import LENS, TOL, _check, _from_dev, _tdt, _to_dev, _torch
 pytestmark = pytest.mark.gpu
 
 
-def _inputs(rng, dtype, B, H, Hkv, Nq, Ncap, d, lens):
-    """fp32 numpy q (B, H, Nq, d), k, v (B, Hkv, Ncap, d) (bf16-rounded for bf16), rows at or past lens[b] of k / v set to NaN."""
-    q, k, v = (rand_u(rng, s) for s in ((B, H, Nq, d), (B, Hkv, Ncap, d), (B, Hkv, Ncap, d)))
+def _inputs(rng, dtype, B, H, Hkv, Nq, Ncap, d, lens, coarse=False):
+    """fp32 numpy q (B, H, Nq, d), k, v (B, Hkv, Ncap, d) (bf16-rounded for bf16), rows at or past lens[b] of k / v set to NaN.
+    ``coarse``, for caches of 10^8 elements: k and v are drawn from the multiples of 2^-7 in (-1, 1) in one int8 pass (exact in bf16;
+    a third of the time of the float passes and the rounding)."""
+    q, k, v = (rand_u(rng, s) if i == 0 or not coarse else
+               np.multiply(rng.integers(-127, 128, s, dtype=np.int8), np.float32(2.0 ** -7), dtype=np.float32)
+               for i, s in enumerate(((B, H, Nq, d), (B, Hkv, Ncap, d), (B, Hkv, Ncap, d))))
     if dtype == "bf16":
-        q, k, v = (oracle.bf16_round(t) for t in (q, k, v))
+        q, k, v = (oracle.bf16_round(t) if i == 0 or not coarse else t for i, t in enumerate((q, k, v)))
     for b, n in enumerate(lens):
         n = min(max(n, 0), Ncap)
         k[b, :, n:] = np.nan
@@ -94,14 +98,19 @@ def test_single_query_of_grouped_heads_over_a_long_cache(dtype, d):
         _check_grouped(q, k, v, lens, causal, dtype, out, lse)
 
 
-def _raw(sym, heads, tq, tk, tv, lens, ws, B, Nq, Ncap, d, layout, causal, dtype):
-    """A direct call of one of the two C entry points on the same tensors; returns fresh (out, lse)."""
+def _raw(sym, heads, tq, tk, tv, lens, ws, B, Nq, Ncap, d, layout, causal, dtype, out=None, lse=None, null_lse=False):
+    """A direct call of one of the two C entry points on the same tensors; returns (out, lse): fresh NaN-filled ones unless the caller
+    supplies them; ``null_lse`` passes lse = NULL and returns (out, None)."""
     torch = _torch()
     from flash_attention_minitorch_amd import _lib
     lib = _lib.decode()
-    out = torch.full(tq.shape, float("nan"), dtype=torch.float32, device="cuda")
+    if out is None:
+        out = torch.full(tq.shape, float("nan"), dtype=torch.float32, device="cuda")
     H = heads[0]
-    lse = torch.full((B, H, Nq), float("nan"), dtype=torch.float32, device="cuda")
+    if null_lse:
+        lse = None
+    elif lse is None:
+        lse = torch.full((B, H, Nq), float("nan"), dtype=torch.float32, device="cuda")
     p = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)
     _lib.decode_check(getattr(lib, sym)(p(tq), p(tk), p(tv), p(out), p(lse), p(lens), p(ws), B, *heads, Nq, Ncap, d,
                                         _lib.FA_LAYOUT_BNHD if layout == "bnhd" else _lib.FA_LAYOUT_BHND, 0.0, int(causal),
