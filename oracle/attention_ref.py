@@ -176,16 +176,18 @@ def masked_attention_bw(q, k, v, do, key_mask, causal: bool = False, dtype=np.fl
     return tau * np.matmul(ds, k), tau * np.matmul(np.swapaxes(ds, -1, -2), q), dv
 
 
-def dropout_keep_mask(BH: int, N: int, rate: float, seed: int) -> np.ndarray:
+def dropout_keep_mask(BH: int, N: int, rate: float, seed: int, heads=None) -> np.ndarray:
     """The HIP path's stateless dropout mask (csrc/fa_atoms.h drop_base / drop_keep) restated in NumPy uint32
     arithmetic: keep[bh, q, k] = (hash32(seed + bh*0xC2B2AE3D + q*0x9E3779B1 + k*0x85EBCA77) >> 8) >= floor(rate * 2^24),
     i.e. "rate < r" with r a 24-bit uniform, minitorch's keep rule (minitorch/nn.py:168-186: `drop = rate < r`).
     The reference applies no dropout on its flash path and draws its masks from NumPy's global RNG elsewhere, so
     there is nothing bit-level to pin: what IS the reference's is the rule and that the mask multiplies the
-    probabilities (kernel_tests/test_flashattn_fw.py:66,71)."""
+    probabilities (kernel_tests/test_flashattn_fw.py:66,71).
+    ``heads``: a list of batch*head indices b*H + h (default: all BH); the result then holds those rows only, in that order."""
     thr = np.uint32(int(float(np.float32(rate)) * 16777216.0))
+    rows = np.arange(BH, dtype=np.uint32) if heads is None else np.asarray(list(heads), dtype=np.uint32)
     with np.errstate(over="ignore"):
-        bh = np.arange(BH, dtype=np.uint32)[:, None, None] * np.uint32(0xC2B2AE3D)
+        bh = rows[:, None, None] * np.uint32(0xC2B2AE3D)
         qq = np.arange(N, dtype=np.uint32)[None, :, None] * np.uint32(0x9E3779B1)
         kk = np.arange(N, dtype=np.uint32)[None, None, :] * np.uint32(0x85EBCA77)
         a = (np.uint32(seed & 0xFFFFFFFF) + bh + qq + kk).astype(np.uint32)

@@ -231,3 +231,33 @@ def test_dropout_oracle_identities():
     assert oracle.dropout_keep_mask(2, 16, 0.0, 3).all()
     # decorrelated across heads and seeds
     assert abs((big[0] == big[1]).mean() - (0.75 ** 2 + 0.25 ** 2)) < 0.02
+
+
+def test_left_padding_mask_equals_dense_oracle_over_the_kept_keys():
+    """The expectation the GPU left-padding tests rest on: with keys [0, pad) at -inf (non-causal), masked_attention_fw / _bw
+    equal the pinned dense oracle run over keys pad .. N-1 alone, the padded keys get exactly zero dK / dV, and no row is dead."""
+    rng = np.random.default_rng(13)
+    B, H, N, d, pad = 2, 3, 50, 16, 19
+    q, k, v, do = (rng.uniform(-1, 1, (B, H, N, d)) for _ in range(4))
+    mask = np.zeros((B, 1, N))
+    mask[:, :, :pad] = -np.inf
+    o, L = oracle.masked_attention_fw(q, k, v, mask, False)
+    dq, dk, dv = oracle.masked_attention_bw(q, k, v, do, mask, False)
+    oc, Lc, _, _ = oracle.dense_attention_fw(q, k[:, :, pad:], v[:, :, pad:], False)
+    assert np.all(np.isfinite(L))
+    assert _maxabs(o, oc) < 1e-12 and _maxabs(L, Lc) < 1e-12
+    dqc, dkc, dvc = oracle.dense_attention_bw(q, k[:, :, pad:], v[:, :, pad:], do, False)   # (N queries, N - pad keys)
+    assert _maxabs(dq, dqc) < 1e-12 and _maxabs(dk[:, :, pad:], dkc) < 1e-12 and _maxabs(dv[:, :, pad:], dvc) < 1e-12
+    assert np.all(dk[:, :, :pad] == 0) and np.all(dv[:, :, :pad] == 0)
+
+
+def test_dropout_keep_mask_of_selected_heads_is_the_rows_of_the_full_mask():
+    """dropout_keep_mask(heads=[...]) builds the N x N masks of those batch*head indices alone, in the order given."""
+    BH, N, rate, seed = 96, 40, 0.2, 0xC0FFEE
+    full = oracle.dropout_keep_mask(BH, N, rate, seed)
+    heads = [0, 7, 8, 11, 12, 84, 95, 3, 3]
+    part = oracle.dropout_keep_mask(BH, N, rate, seed, heads=heads)
+    assert part.shape == (len(heads), N, N) and part.dtype == full.dtype
+    assert np.array_equal(part, full[heads])
+    assert np.array_equal(oracle.dropout_keep_mask(BH, N, rate, seed, heads=range(BH)), full)
+    assert not np.array_equal(full[0], full[1])   # (the rows do differ: the selection is not vacuous)
