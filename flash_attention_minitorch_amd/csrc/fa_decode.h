@@ -17,6 +17,9 @@
 // Combine kernel: one workgroup per (batch*head, query row) reduces the partials of its row in a fixed order (no atomics: bitwise
 // repeatable).
 //
+// Append kernel (decode_append_kernel, at the end of this file): writes the Nq new tokens' k and v into the caches in front of the
+// two kernels above, at the rows where the split kernel's causal mask places the queries.
+//
 // Bounds: every K / V load goes through a buffer resource of its (batch, kv head) sized to the valid rows (len_b clamped to
 // [0, Ncap]), with the row offset in the per-lane voffset, so rows at or past len_b read as zero in hardware: whatever they hold (NaN
 // included) reaches neither a score nor the P.V product, and no load goes past row Ncap - 1.  Q goes through a resource of its batch
@@ -45,10 +48,12 @@ struct DecodeArgs {
   float tau;
 };
 
-FA_DEV int clamp_len(const DecodeArgs& a, int b) {
-  const int len = a.seqlens ? a.seqlens[b] : a.Ncap;
-  return min(max(len, 0), a.Ncap);
+FA_DEV int clamp_len(const int* seqlens, int Ncap, int b) {
+  const int len = seqlens ? seqlens[b] : Ncap;
+  return min(max(len, 0), Ncap);
 }
+
+FA_DEV int clamp_len(const DecodeArgs& a, int b) { return clamp_len(a.seqlens, a.Ncap, b); }
 
 // rho / G for a row index 0 <= rho < 2^25 without the integer division's long dependent chain in front of the workgroup's first
 // loads: the float quotient is off by at most one, which the remainder corrects.  (G = 1: exact at once.)
@@ -293,6 +298,55 @@ __global__ void __launch_bounds__(256) decode_combine_kernel(DecodeArgs a) {
   float* orow = a.out + (size_t)b * a.q_bstride + (size_t)hd * a.q_hstride + (size_t)row * a.q_ld;
   *reinterpret_cast<f32x4*>(orow + 4 * g) = acc * inv;
   if (g == 0 && a.lse) a.lse[(size_t)bh * a.Nq + row] = (l > 0.f) ? m_all * a.tau + __logf(l) : -INFINITY;
+}
+
+// ---- append: the new tokens' k and v into the caches ------------------------------------------------------------------------------
+// k_new / v_new hold rows of d_new <= D elements, [B][Nq][Hkv] (bnhd) or [B][Hkv][Nq] of them, contiguous.  With L_b = len_b clamped
+// to [0, Ncap] (the length COUNTS the new tokens, as the split kernel reads it), token i goes to cache row L_b - Nq + i: the position
+// the causal mask gives query i, so a key always lands on its own query's position.  Rows below 0 (len_b < Nq) are not written; no
+// row reaches Ncap.  Columns d_new .. D-1 of a written row are set to zero: the caller neither pads nor keeps stale columns clean.
+struct AppendArgs {
+  const void* k_new;
+  const void* v_new;
+  void* k;
+  void* v;
+  const int* seqlens;   // [B] or null (= Ncap)
+  long lanes;           // B * Nq * Hkv * (D / E)
+  int Hkv, Nq, Ncap, d_new, bnhd;
+  int ch_shift;         // log2(D / E): lanes per row
+  int kv_ld;            // elements between consecutive rows of one head of the cache (D or Hkv*D)
+  long kv_bstride, kv_hstride;
+};
+
+// A lane = E consecutive elements of one new row, of K and of V: E = 16 bytes' worth (one vector load and store each; the host picks
+// it when d_new * sizeof(T) is a multiple of 16 and all four pointers are 16-byte aligned) or E = 1.  Consecutive lanes walk the
+// source in memory order.  The elements are copied as bits; the cache's row length D (a power of two) is a run-time argument.
+template <typename T, int E>
+__global__ void __launch_bounds__(256) decode_append_kernel(AppendArgs a) {
+  typedef typename std::conditional<sizeof(T) == 2, uint16_t, uint32_t>::type U;
+  typedef __attribute__((ext_vector_type(E))) U vec;
+  static_assert(E == 1 || E * sizeof(T) == 16, "a lane moves one element or 16 bytes");
+  const long lane = (long)blockIdx.x * 256 + threadIdx.x;
+  if (lane >= a.lanes) return;
+  const long row = lane >> a.ch_shift;           // source row (b, i, hkv) or (b, hkv, i)
+  const int col = (int)(lane - (row << a.ch_shift)) * E;
+  const int inner = a.bnhd ? a.Hkv : a.Nq;
+  const long outer = row / inner;
+  const int in = (int)(row - outer * inner);
+  const int mid = a.bnhd ? a.Nq : a.Hkv;
+  const int b = (int)(outer / mid), md = (int)(outer - (long)b * mid);
+  const int i = a.bnhd ? md : in, hkv = a.bnhd ? in : md;
+  const int pos = clamp_len(a.seqlens, a.Ncap, b) - a.Nq + i;
+  if (pos < 0) return;
+  const size_t src = (size_t)row * a.d_new + col;
+  const size_t dst = (size_t)b * a.kv_bstride + (size_t)hkv * a.kv_hstride + (size_t)pos * a.kv_ld + col;
+  vec kk = {}, vv = {};
+  if (col < a.d_new) {   // (E > 1: d_new is a multiple of E, so the whole lane is inside the row)
+    kk = *reinterpret_cast<const vec*>(reinterpret_cast<const U*>(a.k_new) + src);
+    vv = *reinterpret_cast<const vec*>(reinterpret_cast<const U*>(a.v_new) + src);
+  }
+  *reinterpret_cast<vec*>(reinterpret_cast<U*>(a.k) + dst) = kk;
+  *reinterpret_cast<vec*>(reinterpret_cast<U*>(a.v) + dst) = vv;
 }
 
 }  // namespace fa

@@ -1,7 +1,8 @@
 // C ABI of the MI355X KV-cache decode library (declared in include/flash_attn_mi355x_decode.h): argument checks, the split policy
-// and the launches of the two kernels of fa_decode.h.
+// and the launches of the kernels of fa_decode.h.
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <stdint.h>
 #include <algorithm>
 #include <stdio.h>
 
@@ -74,24 +75,9 @@ template <typename T> int launch_d(const fa::DecodeArgs& a, int BH, int d, hipSt
   }
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t fa_mi355x_decode_workspace_bytes_gqa(int B, int H, int Hkv, int Nq, int Ncap, int d) {
-  if (!sizes_ok(B, H, Hkv, Nq, Ncap, d)) return 0;
-  return workspace_bytes(B, H, Hkv, Nq, Ncap, d);
-}
-
-int fa_mi355x_decode_splits_gqa(int B, int H, int Hkv, int Nq, int Ncap, int d, int dtype) {
-  (void)dtype;
-  if (!sizes_ok(B, H, Hkv, Nq, Ncap, d)) return 0;
-  return splits(B, H, Hkv, Nq, Ncap);
-}
-
-int fa_mi355x_fwd_decode_gqa(const void* q, const void* k_cache, const void* v_cache, float* out, float* lse, const int* cache_seqlens,
-                             void* workspace, int B, int H, int Hkv, int Nq, int Ncap, int d, int layout, float softmax_scale,
-                             int causal, int dtype, void* stream) {
+// The argument checks of fa_mi355x_fwd_decode_gqa: FA_OK, or the error with its message set.
+int check_decode(const void* q, const void* k_cache, const void* v_cache, const float* out, const void* workspace, int B, int H, int Hkv,
+                 int Nq, int Ncap, int d, int layout, float softmax_scale, int dtype) {
   g_err[0] = 0;
   if (B <= 0 || H <= 0 || Nq <= 0 || Ncap <= 0 || d <= 0) return set_err(FA_ERR_BAD_ARG, "B, H, Nq, Ncap and d must be positive");
   if (Hkv <= 0) return set_err(FA_ERR_BAD_ARG, "Hkv must be positive");
@@ -115,7 +101,13 @@ int fa_mi355x_fwd_decode_gqa(const void* q, const void* k_cache, const void* v_c
   if ((long)Nq * H * d * esz >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "one batch element of q must stay under 2 GiB");
   const int ns = splits(B, H, Hkv, Nq, Ncap);
   if (ns > 1 && !workspace) return set_err(FA_ERR_BAD_ARG, "null workspace: this call needs fa_mi355x_decode_workspace_bytes() bytes");
+  return FA_OK;
+}
 
+// The split (and combine) launches of a checked call.
+int run_decode(const void* q, const void* k_cache, const void* v_cache, float* out, float* lse, const int* cache_seqlens, void* workspace,
+               int B, int H, int Hkv, int Nq, int Ncap, int d, int layout, float softmax_scale, int causal, int dtype, void* stream) {
+  const int ns = splits(B, H, Hkv, Nq, Ncap);
   fa::DecodeArgs a;
   a.q = q;
   a.k = k_cache;
@@ -146,6 +138,106 @@ int fa_mi355x_fwd_decode_gqa(const void* q, const void* k_cache, const void* v_c
   a.tau = softmax_scale > 0.f ? softmax_scale : sqrtf(1.0f / (float)d);
   hipStream_t st = static_cast<hipStream_t>(stream);
   return dtype == FA_DTYPE_BF16 ? launch_d<fa::bf16_t>(a, B * H, d, st) : launch_d<float>(a, B * H, d, st);
+}
+
+// The argument checks of the append: FA_OK, or the error with its message set.
+int check_append(const void* k_new, const void* v_new, const void* k_cache, const void* v_cache, int B, int Hkv, int Nq, int Ncap,
+                 int d_new, int d, int layout, int dtype) {
+  g_err[0] = 0;
+  if (B <= 0 || Hkv <= 0 || Nq <= 0 || Ncap <= 0 || d <= 0) return set_err(FA_ERR_BAD_ARG, "B, Hkv, Nq, Ncap and d must be positive");
+  if (Nq > FA_DECODE_MAX_NQ) return set_err(FA_ERR_BAD_ARG, "Nq > 128 new tokens per call: fill the cache of a prompt directly");
+  if (dtype != FA_DTYPE_F32 && dtype != FA_DTYPE_BF16) return set_err(FA_ERR_BAD_ARG, "unknown dtype");
+  if (layout != FA_LAYOUT_BHND && layout != FA_LAYOUT_BNHD) return set_err(FA_ERR_BAD_ARG, "unknown layout");
+  if (!k_new || !v_new || !k_cache || !v_cache) return set_err(FA_ERR_BAD_ARG, "null pointer argument (k_new, v_new and the caches)");
+  if (d != 32 && d != 64 && d != 128) return set_err(FA_ERR_UNSUPPORTED_D, "decode supports cache rows of d in {32, 64, 128}");
+  if (d_new < 1 || d_new > d) {
+    snprintf(g_err, sizeof(g_err), "d_new = %d must be in 1 .. d = %d", d_new, d);
+    return FA_ERR_BAD_ARG;
+  }
+  // (one lane per element at the most, 256 lanes to a workgroup, the workgroup count an int)
+  if ((long)B * Nq * Hkv * d / 256 >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "too many new elements for one append launch");
+  return FA_OK;
+}
+
+template <typename T, int E> int launch_append(fa::AppendArgs a, int d, hipStream_t st) {
+  a.ch_shift = __builtin_ctz(d / E);
+  a.lanes <<= a.ch_shift;   // (rows on entry)
+  hipLaunchKernelGGL((fa::decode_append_kernel<T, E>), dim3((unsigned)((a.lanes + 255) / 256)), dim3(256), 0, st, a);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? FA_OK : set_err(FA_ERR_HIP, "decode_append_kernel launch", e);
+}
+
+template <typename T> int launch_append_e(const fa::AppendArgs& a, int d, bool vec, hipStream_t st) {
+  return vec ? launch_append<T, 16 / sizeof(T)>(a, d, st) : launch_append<T, 1>(a, d, st);
+}
+
+// The append launch of a checked call.
+int run_append(const void* k_new, const void* v_new, void* k_cache, void* v_cache, const int* cache_seqlens, int B, int Hkv, int Nq,
+               int Ncap, int d_new, int d, int layout, int dtype, void* stream) {
+  fa::AppendArgs a;
+  a.k_new = k_new;
+  a.v_new = v_new;
+  a.k = k_cache;
+  a.v = v_cache;
+  a.seqlens = cache_seqlens;
+  a.lanes = (long)B * Nq * Hkv;
+  a.Hkv = Hkv;
+  a.Nq = Nq;
+  a.Ncap = Ncap;
+  a.d_new = d_new;
+  a.bnhd = layout == FA_LAYOUT_BNHD;
+  a.kv_ld = a.bnhd ? Hkv * d : d;
+  a.kv_bstride = (long)Ncap * Hkv * d;
+  a.kv_hstride = a.bnhd ? d : (long)Ncap * d;
+  const size_t esz = dtype == FA_DTYPE_BF16 ? 2 : 4;
+  // 16-byte lanes where every row of the source starts on 16 bytes, as every row of the cache does once its base is
+  const bool vec = (d_new * esz) % 16 == 0 &&
+                   (((uintptr_t)k_new | (uintptr_t)v_new | (uintptr_t)k_cache | (uintptr_t)v_cache) & 15) == 0;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  return dtype == FA_DTYPE_BF16 ? launch_append_e<fa::bf16_t>(a, d, vec, st) : launch_append_e<float>(a, d, vec, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t fa_mi355x_decode_workspace_bytes_gqa(int B, int H, int Hkv, int Nq, int Ncap, int d) {
+  if (!sizes_ok(B, H, Hkv, Nq, Ncap, d)) return 0;
+  return workspace_bytes(B, H, Hkv, Nq, Ncap, d);
+}
+
+int fa_mi355x_decode_splits_gqa(int B, int H, int Hkv, int Nq, int Ncap, int d, int dtype) {
+  (void)dtype;
+  if (!sizes_ok(B, H, Hkv, Nq, Ncap, d)) return 0;
+  return splits(B, H, Hkv, Nq, Ncap);
+}
+
+int fa_mi355x_fwd_decode_gqa(const void* q, const void* k_cache, const void* v_cache, float* out, float* lse, const int* cache_seqlens,
+                             void* workspace, int B, int H, int Hkv, int Nq, int Ncap, int d, int layout, float softmax_scale,
+                             int causal, int dtype, void* stream) {
+  const int rc = check_decode(q, k_cache, v_cache, out, workspace, B, H, Hkv, Nq, Ncap, d, layout, softmax_scale, dtype);
+  if (rc != FA_OK) return rc;
+  return run_decode(q, k_cache, v_cache, out, lse, cache_seqlens, workspace, B, H, Hkv, Nq, Ncap, d, layout, softmax_scale, causal, dtype,
+                    stream);
+}
+
+int fa_mi355x_decode_append(const void* k_new, const void* v_new, void* k_cache, void* v_cache, const int* cache_seqlens, int B, int Hkv,
+                            int Nq, int Ncap, int d_new, int d, int layout, int dtype, void* stream) {
+  const int rc = check_append(k_new, v_new, k_cache, v_cache, B, Hkv, Nq, Ncap, d_new, d, layout, dtype);
+  if (rc != FA_OK) return rc;
+  return run_append(k_new, v_new, k_cache, v_cache, cache_seqlens, B, Hkv, Nq, Ncap, d_new, d, layout, dtype, stream);
+}
+
+int fa_mi355x_fwd_decode_append(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
+                                const int* cache_seqlens, void* workspace, int B, int H, int Hkv, int Nq, int Ncap, int d_new, int d,
+                                int layout, float softmax_scale, int causal, int dtype, void* stream) {
+  int rc = check_decode(q, k_cache, v_cache, out, workspace, B, H, Hkv, Nq, Ncap, d, layout, softmax_scale, dtype);
+  if (rc == FA_OK) rc = check_append(k_new, v_new, k_cache, v_cache, B, Hkv, Nq, Ncap, d_new, d, layout, dtype);
+  if (rc != FA_OK) return rc;
+  rc = run_append(k_new, v_new, k_cache, v_cache, cache_seqlens, B, Hkv, Nq, Ncap, d_new, d, layout, dtype, stream);
+  if (rc != FA_OK) return rc;
+  return run_decode(q, k_cache, v_cache, out, lse, cache_seqlens, workspace, B, H, Hkv, Nq, Ncap, d, layout, softmax_scale, causal, dtype,
+                    stream);
 }
 
 // The ungrouped entry points: Hkv = H.

@@ -447,8 +447,65 @@ def decode_workspace(q, k_cache, layout="bnhd"):
     return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=q.device) if nbytes else None
 
 
+def _check_seqlens(cache_seqlens, B, device):
+    if cache_seqlens is not None and (cache_seqlens.dtype != torch.int32 or tuple(cache_seqlens.shape) != (B,)
+                                      or cache_seqlens.device != device or not cache_seqlens.is_contiguous()):
+        raise ValueError("cache_seqlens must be a contiguous int32 tensor of shape (B,) on q's device")
+
+
+def _check_new(k_new, v_new, k_cache, layout, Nq=None):
+    """(Nq, d_new) of the new tokens' k_new / v_new, (B, Nq, Hkv, d_new) for "bnhd" or (B, Hkv, Nq, d_new) for "bhnd", checked
+    against the cache they are appended to (and against the caller's Nq, when given)."""
+    if k_new.dim() != 4 or k_new.shape != v_new.shape:
+        raise ValueError("k_new and v_new must be 4-d tensors of one shape")
+    if k_new.dtype != k_cache.dtype or v_new.dtype != k_cache.dtype:
+        raise TypeError("k_new and v_new must have the cache's dtype")
+    if layout == "bnhd":
+        (B, n, Hkv, d_new), (Bc, _, Hc, dp) = k_new.shape, k_cache.shape
+    else:
+        (B, Hkv, n, d_new), (Bc, Hc, _, dp) = k_new.shape, k_cache.shape
+    if (B, Hkv) != (Bc, Hc):
+        raise ValueError(f"k_new and the cache disagree on (B, Hkv): {(B, Hkv)} vs {(Bc, Hc)}")
+    if Nq is not None and n != Nq:
+        raise ValueError(f"k_new holds {n} new tokens, q {Nq}")
+    if not 1 <= d_new <= dp:
+        raise ValueError(f"k_new's head dim {d_new} must be in 1 .. {dp}, the cache's row length")
+    for t in (k_new, v_new):
+        if t.device != k_cache.device:
+            raise ValueError("k_new and v_new must live on the cache's device")
+        if not t.is_contiguous():
+            raise ValueError("k_new and v_new must be contiguous")
+    return n, d_new
+
+
+def decode_append(k_new, v_new, k_cache, v_cache, cache_seqlens=None, layout="bnhd"):
+    """Write the Nq <= 128 new tokens' k and v into the caches on the device (fa_mi355x_decode_append): k_new, v_new (B, Nq, Hkv,
+    d_new) for "bnhd" or (B, Hkv, Nq, d_new) for "bhnd", 1 <= d_new <= dp, into caches (B, Ncap, Hkv, dp) / (B, Hkv, Ncap, dp).
+    ``cache_seqlens`` COUNTS the new tokens, as flash_attn_decode reads it: token i goes to row clamp(len_b, 0, Ncap) - Nq + i when
+    that is >= 0 (None: the last Nq rows), with zeros in columns d_new .. dp-1; every other row keeps its contents.  k_new and v_new
+    must not alias the caches.  In place, no host synchronisation."""
+    if layout not in _DECODE_LAYOUTS:
+        raise ValueError(f"layout must be one of {sorted(_DECODE_LAYOUTS)}")
+    if k_cache.dim() != 4 or k_cache.shape != v_cache.shape:
+        raise ValueError("k_cache and v_cache must be 4-d tensors of one shape")
+    if v_cache.dtype != k_cache.dtype:
+        raise TypeError("k_cache and v_cache must share one dtype")
+    dtype = _dtype_code(k_cache)
+    Nq, d_new = _check_new(k_new, v_new, k_cache, layout)
+    B, dp = k_cache.shape[0], k_cache.shape[3]
+    Ncap, Hkv = (k_cache.shape[1], k_cache.shape[2]) if layout == "bnhd" else (k_cache.shape[2], k_cache.shape[1])
+    _check_seqlens(cache_seqlens, B, k_cache.device)
+    for t in (k_cache, v_cache):
+        if t.device != k_cache.device or not t.is_contiguous():
+            raise ValueError("k_cache and v_cache must be contiguous and live on one device")
+        _require_gpu(t, "decode_append")
+    _lib.decode_check(_lib.decode().fa_mi355x_decode_append(
+        _ptr(k_new), _ptr(v_new), _ptr(k_cache), _ptr(v_cache), _ptr(cache_seqlens), B, Hkv, Nq, Ncap, d_new, dp,
+        _DECODE_LAYOUTS[layout], dtype, _stream_ptr()))
+
+
 def flash_attn_decode(q, k_cache, v_cache, cache_seqlens=None, causal=True, softmax_scale=None, layout="bnhd", out=None, lse=None,
-                      workspace=None):
+                      workspace=None, k_new=None, v_new=None):
     """Attention of Nq <= 128 new queries against a KV cache (fa_mi355x_fwd_decode / _gqa, include/flash_attn_mi355x_decode.h).
     ``layout`` "bnhd": q (B, Nq, H, d), caches (B, Ncap, Hkv, dp); "bhnd": q (B, H, Nq, d), caches (B, Hkv, Ncap, dp).  Hkv is the
     cache's own head count and must divide H: Hkv < H is a grouped-query (Hkv = 1: multi-query) cache, query head h reads cache head
@@ -456,7 +513,11 @@ def flash_attn_decode(q, k_cache, v_cache, cache_seqlens=None, causal=True, soft
     a q with fewer columns (d < dp) is zero-padded to the cache's row length (the cache itself holds zero columns d .. dp-1) and the
     default scale is then 1/sqrt(d).  ``cache_seqlens``: int32 (B,) on q's device, the valid cache rows per batch element counting the
     new tokens (None: all Ncap); clamped to [0, Ncap] on the device, no host synchronisation.  ``causal``: the queries are the last Nq
-    positions.  Returns (out fp32 in q's shape, lse fp32 (B, H, Nq)): rows with no admissible key give out = 0, lse = -inf."""
+    positions.  ``k_new``, ``v_new`` (both or neither; shapes and placement as decode_append): the new tokens' k and v, written into
+    the caches on the device in front of the attention (fa_mi355x_fwd_decode_append: decode_append, then this call, one library call).
+    Returns (out fp32 in q's shape, lse fp32 (B, H, Nq)): rows with no admissible key give out = 0, lse = -inf."""
+    if (k_new is None) != (v_new is None):
+        raise ValueError("k_new and v_new go together: give both (fused append) or neither")
     if layout not in _DECODE_LAYOUTS:
         raise ValueError(f"layout must be one of {sorted(_DECODE_LAYOUTS)}")
     dtype = _dtype_code(q)
@@ -467,9 +528,9 @@ def flash_attn_decode(q, k_cache, v_cache, cache_seqlens=None, causal=True, soft
     B, H, Hkv, Nq, Ncap, d, dp = _decode_dims(q, k_cache, layout)
     if d > dp:
         raise ValueError(f"q's head dim {d} exceeds the cache's row length {dp}")
-    if cache_seqlens is not None and (cache_seqlens.dtype != torch.int32 or tuple(cache_seqlens.shape) != (B,)
-                                      or cache_seqlens.device != q.device or not cache_seqlens.is_contiguous()):
-        raise ValueError("cache_seqlens must be a contiguous int32 tensor of shape (B,) on q's device")
+    _check_seqlens(cache_seqlens, B, q.device)
+    if k_new is not None:
+        _, d_new = _check_new(k_new, v_new, k_cache, layout, Nq)
     for t in (q, k_cache, v_cache):
         _require_gpu(t, "flash_attn_decode")
         if t.device != q.device:
@@ -491,8 +552,14 @@ def flash_attn_decode(q, k_cache, v_cache, cache_seqlens=None, causal=True, soft
         workspace = decode_workspace(qp, k_cache, layout)
     elif workspace.numel() * workspace.element_size() < _decode_workspace_bytes(B, H, Hkv, Nq, Ncap, dp):
         raise ValueError("workspace too small: size it with decode_workspace()")
-    # (Hkv == H goes through the ungrouped entry points, which are the Hkv = H case of the _gqa ones inside the library)
-    fwd, heads = (lib.fa_mi355x_fwd_decode, (H,)) if Hkv == H else (lib.fa_mi355x_fwd_decode_gqa, (H, Hkv))
-    _lib.decode_check(fwd(_ptr(qp), _ptr(k_cache), _ptr(v_cache), _ptr(outp), _ptr(lse), _ptr(cache_seqlens), _ptr(workspace), B, *heads,
-                          Nq, Ncap, dp, _DECODE_LAYOUTS[layout], float(softmax_scale), int(bool(causal)), dtype, _stream_ptr()))
+    tail = (_DECODE_LAYOUTS[layout], float(softmax_scale), int(bool(causal)), dtype, _stream_ptr())
+    if k_new is not None:
+        status = lib.fa_mi355x_fwd_decode_append(_ptr(qp), _ptr(k_new), _ptr(v_new), _ptr(k_cache), _ptr(v_cache), _ptr(outp), _ptr(lse),
+                                                 _ptr(cache_seqlens), _ptr(workspace), B, H, Hkv, Nq, Ncap, d_new, dp, *tail)
+    else:
+        # (Hkv == H goes through the ungrouped entry points, which are the Hkv = H case of the _gqa ones inside the library)
+        fwd, heads = (lib.fa_mi355x_fwd_decode, (H,)) if Hkv == H else (lib.fa_mi355x_fwd_decode_gqa, (H, Hkv))
+        status = fwd(_ptr(qp), _ptr(k_cache), _ptr(v_cache), _ptr(outp), _ptr(lse), _ptr(cache_seqlens), _ptr(workspace), B, *heads,
+                     Nq, Ncap, dp, *tail)
+    _lib.decode_check(status)
     return (_unpad(outp, d, out) if d < dp else outp), lse

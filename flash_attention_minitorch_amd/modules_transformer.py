@@ -150,32 +150,96 @@ def attention_stack_prefill(x, layers, n_head: int, cache: KVCache):
     return x
 
 
-def attention_stack_step(x_new, layers, n_head: int, cache: KVCache):
-    """One generation step of the stack: x_new (B, T, E), T <= 128 new tokens that follow each batch element's cached prefix.  Every
-    layer projects them, appends k and v at rows lengths[b] .. lengths[b] + T - 1 (device indexing: no host synchronisation), and
-    attends causally to the cache with the decode kernels (a grouped-query stack appends its Hkv heads and its n_head query heads
-    read them in place); lengths grow by T.  Returns the stack's output for the new tokens (B, T, E),
-    the last T rows of attention_stack over the whole sequence."""
+def _step(x_new, layers, n_head: int, cache: KVCache, fused: bool):
     B, T, E = x_new.shape
     if T > MAX_STEP_TOKENS:
         raise ValueError(f"a step takes at most {MAX_STEP_TOKENS} tokens; use attention_stack_prefill for longer inputs")
     if cache.length_bound + T > cache.capacity:
         raise ValueError(f"cache capacity {cache.capacity} exceeded")
     dev = x_new.device
-    # rows b * capacity + lengths[b] + t of the (B * capacity, Hkv, dp) view of a layer's cache: the new tokens' k and v
-    rows = (cache.lengths.long() + torch.arange(B, device=dev) * cache.capacity)[:, None] + torch.arange(T, device=dev)
-    rows = rows.reshape(B * T)
+    if not fused:
+        # rows b * capacity + lengths[b] + t of the (B * capacity, Hkv, dp) view of a layer's cache: the new tokens' k and v
+        rows = (cache.lengths.long() + torch.arange(B, device=dev) * cache.capacity)[:, None] + torch.arange(T, device=dev)
+        rows = rows.reshape(B * T)
     new_len = cache.lengths + T
     x = x_new
     for li, (wq, wk, wv, wo) in enumerate(layers):
         q, k, v = _project(x, wq, wk, wv, n_head)
         _check_kv_heads(k, cache)
-        hkv = cache.n_kv_head
-        for dst, t in ((cache.k[li], k), (cache.v[li], v)):
-            dst.view(B * cache.capacity, hkv, cache.dp).index_copy_(0, rows, cache._pad(t).reshape(B * T, hkv, cache.dp))
+        new = {}
+        if fused:   # the library writes k and v at rows new_len[b] - T .. new_len[b] - 1 (zero columns past head_dim), then attends
+            new = dict(k_new=k, v_new=v)
+        else:
+            hkv = cache.n_kv_head
+            for dst, t in ((cache.k[li], k), (cache.v[li], v)):
+                dst.view(B * cache.capacity, hkv, cache.dp).index_copy_(0, rows, cache._pad(t).reshape(B * T, hkv, cache.dp))
         o, _ = device_ops.flash_attn_decode(q, cache.k[li], cache.v[li], new_len, causal=True, layout="bnhd",
-                                            workspace=cache.workspace(q))
+                                            workspace=cache.workspace(q), **new)
         x = x + (o.reshape(B * T, E).to(x.dtype) @ wo).view(B, T, E)
     cache.lengths.copy_(new_len)
     cache.length_bound += T
     return x
+
+
+def attention_stack_step(x_new, layers, n_head: int, cache: KVCache):
+    """One generation step of the stack: x_new (B, T, E), T <= 128 new tokens that follow each batch element's cached prefix.  Every
+    layer projects them, appends k and v at rows lengths[b] .. lengths[b] + T - 1 (device indexing: no host synchronisation), and
+    attends causally to the cache with the decode kernels (a grouped-query stack appends its Hkv heads and its n_head query heads
+    read them in place); lengths grow by T.  Returns the stack's output for the new tokens (B, T, E),
+    the last T rows of attention_stack over the whole sequence."""
+    return _step(x_new, layers, n_head, cache, fused=False)
+
+
+def attention_stack_step_fused(x_new, layers, n_head: int, cache: KVCache):
+    """attention_stack_step with the append inside the library: every layer hands q, k and v to one fused call
+    (flash_attn_decode(..., k_new=, v_new=)), which writes k and v into the cache and then attends.  No row indices, padded copies
+    or index_copy_ on the caller's side; the same results and the same cache contents, bit for bit."""
+    return _step(x_new, layers, n_head, cache, fused=True)
+
+
+class GraphedStep:
+    """attention_stack_step_fused for T new tokens per call, captured once in a device graph and replayed per call: a step is a fixed launch
+    sequence (projections, the library's append + decode, the output projection), and everything it reads that changes from step to
+    step -- ``cache.lengths`` and the caches -- is updated by that sequence itself, so every replay advances the cache by T tokens.
+    Owns a static (B, T, E) input and output; ``step`` returns the static output, which the next call overwrites.  The host-side
+    capacity check and ``cache.length_bound`` stay outside the graph."""
+
+    def __init__(self, layers, n_head: int, cache: KVCache, T: int = 1):
+        if not 1 <= T <= MAX_STEP_TOKENS:
+            raise ValueError(f"a step takes 1 .. {MAX_STEP_TOKENS} tokens")
+        self.layers, self.n_head, self.cache, self.T = layers, n_head, cache, T
+        self.graph = self.x = self.y = None
+
+    def _capture(self, x_new):
+        cache = self.cache
+        self.x = torch.empty_like(x_new)
+        # one eager step on a side stream first (workspaces and library handles exist before the capture); it runs on a throw-away
+        # input and its effects are undone: lengths restored, and the rows it wrote are the rows the first replay writes again
+        lengths, bound = cache.lengths.clone(), cache.length_bound
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            self.x.zero_()
+            attention_stack_step_fused(self.x, self.layers, self.n_head, cache)
+            cache.lengths.copy_(lengths)
+        torch.cuda.current_stream().wait_stream(side)
+        cache.length_bound = bound
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self.y = attention_stack_step_fused(self.x, self.layers, self.n_head, cache)
+        cache.length_bound = bound   # (capturing runs nothing on the device; step() counts the replays)
+
+    def step(self, x_new):
+        B, T, E = x_new.shape
+        if T != self.T:
+            raise ValueError(f"this graph steps {self.T} tokens at a time, got {T}")
+        if self.cache.length_bound + T > self.cache.capacity:
+            raise ValueError(f"cache capacity {self.cache.capacity} exceeded")
+        if self.graph is None:
+            self._capture(x_new)
+        elif x_new.shape != self.x.shape or x_new.dtype != self.x.dtype:
+            raise ValueError("x_new must keep the shape and dtype of the captured step")
+        self.x.copy_(x_new)
+        self.graph.replay()
+        self.cache.length_bound += T
+        return self.y

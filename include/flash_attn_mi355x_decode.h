@@ -77,6 +77,30 @@ int fa_mi355x_fwd_decode_gqa(const void* q, const void* k_cache, const void* v_c
                              void* workspace, int B, int H, int Hkv, int Nq, int Ncap, int d, int layout, float softmax_scale,
                              int causal, int dtype, void* stream);
 
+/* Append the Nq new tokens' k and v to the caches, on the device: one launch writes both, asynchronous on `stream`, no allocation, no
+ * host synchronisation (capturable in a graph).  The call that makes "the caller writes their k / v into the cache first" above.
+ *   k_new, v_new   dtype elements, [B][Nq][Hkv][d_new] (FA_LAYOUT_BNHD) or [B][Hkv][Nq][d_new] (FA_LAYOUT_BHND), 1 <= d_new <= d;
+ *            they must not alias the caches (not checked)
+ *   k_cache, v_cache   as fa_mi355x_fwd_decode_gqa: rows of d in {32, 64, 128} (FA_ERR_UNSUPPORTED_D otherwise)
+ *   cache_seqlens  as above, with the same meaning: len_b COUNTS the Nq new tokens.  With L_b = len_b clamped to [0, Ncap] on the
+ *            device, new token i goes to row L_b - Nq + i, the position the causal mask gives query i, so a token's key always lands
+ *            on its own position.  A row below 0 (len_b < Nq) is not written; no row reaches Ncap.  NULL: every L_b = Ncap, the new
+ *            tokens go to the last Nq rows.
+ * Columns d_new .. d-1 of a written row are set to zero (the caller neither pads nor keeps stale columns clean); every other row of
+ * the caches is left untouched.  Stores are 16 bytes per lane when d_new * sizeof(element) is a multiple of 16 and all four pointers
+ * are 16-byte aligned, element by element otherwise.  Null k_new, v_new or caches, d_new outside 1 .. d, Nq > FA_DECODE_MAX_NQ,
+ * non-positive sizes, an unknown layout or dtype: FA_ERR_BAD_ARG before any HIP call. */
+int fa_mi355x_decode_append(const void* k_new, const void* v_new, void* k_cache, void* v_cache, const int* cache_seqlens, int B, int Hkv,
+                            int Nq, int Ncap, int d_new, int d, int layout, int dtype, void* stream);
+
+/* fa_mi355x_decode_append followed, on the same stream, by exactly what fa_mi355x_fwd_decode_gqa does with the same arguments: by
+ * definition the result is what fa_mi355x_fwd_decode_gqa returns on the caches after the append (same splits, same workspace size
+ * from fa_mi355x_decode_workspace_bytes_gqa, same bits).  q has d columns (padded by the caller when d_new < d, as above).  Every
+ * argument either of the two rejects is rejected here, before any HIP call and before the caches are touched. */
+int fa_mi355x_fwd_decode_append(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
+                                const int* cache_seqlens, void* workspace, int B, int H, int Hkv, int Nq, int Ncap, int d_new, int d,
+                                int layout, float softmax_scale, int causal, int dtype, void* stream);
+
 /* Message of the last FA_ERR_* of this library on this thread ("" if none). */
 const char* fa_mi355x_decode_last_error(void);
 

@@ -10,10 +10,11 @@ Beside it, on the same data:
 A grouped shape (Hkv < H: G = H / Hkv query heads share a cache head) is also timed against the two calls that bracket it:
   (x) the same q on the cache expanded to H heads (repeat_interleave: all a user can do without grouped decode; G x the bytes);
   (y) an ungrouped call with H = Hkv heads: the same K / V stream with 1/G of the queries (the floor the bytes set).
-Then the in-model numbers: one attention_stack_step of a 4-layer stack against re-running attention_stack over the whole prefix, and
-the step of a 32-head stack with 8 kv heads against the same stack with 32.
+Then the in-model numbers: one attention_stack_step of a 4-layer stack, the same step with the append inside the library
+(attention_stack_step_fused), eager and captured in a graph (GraphedStep), against re-running attention_stack over the whole prefix, and the step of a 32-head stack with 8 kv heads against the same stack with 32; and the
+append launch alone (decode_append: the new token's k and v into the caches, the launch the step's fused call starts with).
 
-    python tools/bench_decode.py [--reps 50] [--warmup 5] [--only decode|grouped] > decode.txt
+    python tools/bench_decode.py [--reps 50] [--warmup 5] [--only decode|grouped|model] > decode.txt
 """
 import argparse
 import json
@@ -127,7 +128,19 @@ def bench_shape(dtype, B, H, Nq, n, d, Hkv=None, reps=50, warmup=5, only="all"):
     return rec
 
 
-def bench_stack(dtype, B, E, H, prefix, reps, warmup, layers_n=4, Hkv=None, full=True):
+def bench_append(dtype, B, Hkv, Nq, Ncap, d, reps, warmup):
+    """us per decode_append call: Nq new tokens of B * Hkv heads into caches of Ncap rows, at lengths that differ per batch element."""
+    dt = DT[dtype]
+    gen = torch.Generator(device="cuda").manual_seed(2)
+    u = lambda *s: (torch.rand(*s, device="cuda", generator=gen) * 2 - 1).to(dt)
+    kc, vc, kn, vn = u(B, Ncap, Hkv, d), u(B, Ncap, Hkv, d), u(B, Nq, Hkv, d), u(B, Nq, Hkv, d)
+    lens = (torch.arange(B, dtype=torch.int32, device="cuda") * 97) % (Ncap - Nq) + Nq
+    us = timed_us(lambda i: device_ops.decode_append(kn, vn, kc, vc, lens), reps, warmup)
+    return {"append": f"B={B} Hkv={Hkv} Nq={Nq} Ncap={Ncap} d={d} {dtype}", "append_us": round(us, 2),
+            "bytes_written": 2 * kn.numel() * kn.element_size()}
+
+
+def bench_stack(dtype, B, E, H, prefix, reps, warmup, layers_n=4, Hkv=None, full=True, graphed=False):
     dt = DT[dtype]
     Hkv = Hkv or H
     gen = torch.Generator(device="cuda").manual_seed(1)
@@ -135,14 +148,22 @@ def bench_stack(dtype, B, E, H, prefix, reps, warmup, layers_n=4, Hkv=None, full
     kv_cols = Hkv * (E // H)
     layers = [tuple((u(E, c) / math.sqrt(E)).to(dt) for c in (E, kv_cols, kv_cols, E)) for _ in range(layers_n)]
     x = u(B, prefix + 1, E).to(dt)
-    cache = mt.KVCache(layers_n, B, prefix + warmup + reps + 8, H, E // H, dt, "cuda", n_kv_head=Hkv)
+    cache = mt.KVCache(layers_n, B, prefix + (3 if graphed else 1) * (warmup + reps) + 8, H, E // H, dt, "cuda", n_kv_head=Hkv)
     mt.attention_stack_prefill(x[:, :prefix].contiguous(), layers, H, cache)
     xs = x[:, prefix:].contiguous()
     step = timed_us(lambda i: mt.attention_stack_step(xs, layers, H, cache), reps, warmup)
     rec = {"stack": f"{layers_n}-layer B={B} E={E} H={H} Hkv={Hkv} prefix={prefix} {dtype}", "step_us": round(step, 1)}
+    if graphed:   # the fused step, eager and replayed from a graph, on the same cache (each goes on from where the last one stopped)
+        fus = timed_us(lambda i: mt.attention_stack_step_fused(xs, layers, H, cache), reps, warmup)
+        g = mt.GraphedStep(layers, H, cache, 1)
+        gus = timed_us(lambda i: g.step(xs), reps, warmup)
+        rec.update(fused_step_us=round(fus, 1), graphed_step_us=round(gus, 1), fused_vs_step=round(step / fus, 2),
+                   graphed_vs_fused=round(fus / gus, 2))
     if full:
         full_us = timed_us(lambda i: mt.attention_stack(x, layers, H, causal=True), max(3, reps // 5), 2)
         rec.update(full_prefix_us=round(full_us, 1), speedup=round(full_us / step, 2))
+        if graphed:
+            rec.update(fused_speedup=round(full_us / fus, 2), graphed_speedup=round(full_us / gus, 2))
     del cache
     torch.cuda.empty_cache()
     return rec
@@ -152,21 +173,24 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--only", choices=["all", "decode", "ungrouped", "grouped"], default="all",
+    ap.add_argument("--only", choices=["all", "decode", "ungrouped", "grouped", "model"], default="all",
                     help="decode: the decode timings alone, without the comparisons (a) and (b) (for a trace run); ungrouped: the nine "
-                         "Hkv = H shapes alone (build-against-build comparisons); grouped: the Hkv < H shapes and the grouped stack")
+                         "Hkv = H shapes alone (build-against-build comparisons); grouped: the Hkv < H shapes and the grouped stack; "
+                         "model: the model steps (plain, fused and graphed) and the append launch alone")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_decode.py needs a GPU")
     only = "decode" if args.only in ("ungrouped", "grouped") else args.only
-    for s in (SHAPES if args.only != "grouped" else []) + (GROUPED_SHAPES if args.only != "ungrouped" else []):
+    shapes = [] if args.only == "model" else (SHAPES if args.only != "grouped" else []) + (GROUPED_SHAPES if args.only != "ungrouped" else [])
+    for s in shapes:
         print(json.dumps(bench_shape(*s, reps=args.reps, warmup=args.warmup, only=only)), flush=True)
-    if args.only in ("all", "grouped"):
+    if args.only in ("all", "grouped", "model"):
         for hkv in (8, 32):
-            print(json.dumps(bench_stack("bf16", 8, 4096, 32, 8192, args.reps, args.warmup, Hkv=hkv, full=False)), flush=True)
-    if args.only == "all":
+            print(json.dumps(bench_stack("bf16", 8, 4096, 32, 8192, args.reps, args.warmup, Hkv=hkv, full=False, graphed=True)), flush=True)
+    if args.only in ("all", "model"):
         for dtype, B, E, H, prefix in (("bf16", 8, 256, 8, 1024), ("f32", 8, 256, 8, 1024), ("bf16", 1, 1024, 8, 8192)):
-            print(json.dumps(bench_stack(dtype, B, E, H, prefix, args.reps, args.warmup)), flush=True)
+            print(json.dumps(bench_stack(dtype, B, E, H, prefix, args.reps, args.warmup, graphed=True)), flush=True)
+        print(json.dumps(bench_append("bf16", 32, 8, 1, 4096, 128, args.reps, args.warmup)), flush=True)
 
 
 if __name__ == "__main__":
