@@ -85,6 +85,11 @@ CORE_ABI = {
     "fa_mi355x_scale_guard": (_i, [_vp, _vp, ctypes.c_long, _i, _i, _vp, _vp]),
     "fa_mi355x_fwd_guarded": (_i, [_vp] * 6 + [_i] * 5 + [_f] + [_i] * 3 + [_ip, _i, _vp, _i, _vp]),
     "fa_mi355x_bwd_guarded": (_i, [_vp] * 11 + [_i] * 5 + [_f] + [_i] * 4 + [_ip, _i, _vp, _vp]),
+    "fa_mi355x_bwd_workspace_bytes_gqa": (_sz, [_i] * 5),
+    "fa_mi355x_scale_guard_gqa": (_i, [_vp, _vp, ctypes.c_long, ctypes.c_long, _i, _i, _vp, _vp]),
+    "fa_mi355x_fwd_gqa": (_i, [_vp] * 6 + [_i] * 6 + [_f] + [_i] * 3 + [_ip, _i, _vp, _i, _vp]),
+    "fa_mi355x_bwd_gqa": (_i, [_vp] * 11 + [_i] * 6 + [_f] + [_i] * 4 + [_ip, _i, _vp, _vp]),
+    "fa_mi355x_plan_gqa": (_i, [_i] * 9 + [_ip, _i, _s, _sz]),
     "fa_mi355x_fwd_scaled": (_i, [_vp] * 6 + [_i] * 5 + [_f] + [_i] * 3 + [_vp]),
     "fa_mi355x_bwd_scaled": (_i, [_vp] * 11 + [_i] * 5 + [_f] + [_i] * 3 + [_vp]),
     "fa_mi355x_fwd_padded": (_i, [_vp] * 6 + [_i] * 7 + [_vp]),
@@ -151,13 +156,22 @@ def opts_array(opts):
     return arr, len(opts)
 
 
+def _plan(entry, dims, causal, variant, dtype, stages, opts):
+    arr, cnt = opts_array(opts)
+    buf = ctypes.create_string_buffer(1024)
+    check(entry(*(int(x) for x in dims), int(bool(causal)), int(variant), int(dtype), int(stages), arr, cnt, buf, 1024))
+    return [x for x in buf.value.decode().split(";") if x]
+
+
 def plan(batch, n, d, causal, variant, dtype, stages, opts=None):
     """Kernel names, in launch order, of the call with these arguments (fa_mi355x_plan: the library's own dispatch code with the
     launches skipped).  stages = 0: the forward; otherwise the backward stage mask."""
-    arr, cnt = opts_array(opts)
-    buf = ctypes.create_string_buffer(1024)
-    check(core().fa_mi355x_plan(int(batch), int(n), int(d), int(bool(causal)), int(variant), int(dtype), int(stages), arr, cnt, buf, 1024))
-    return [x for x in buf.value.decode().split(";") if x]
+    return _plan(core().fa_mi355x_plan, (batch, n, d), causal, variant, dtype, stages, opts)
+
+
+def plan_gqa(B, H, Hkv, n, d, causal, variant, dtype, stages, opts=None):
+    """``plan`` for a grouped-query call (fa_mi355x_plan_gqa): B * H query heads reading Hkv key/value heads per batch element."""
+    return _plan(core().fa_mi355x_plan_gqa, (B, H, Hkv, n, d), causal, variant, dtype, stages, opts)
 
 
 def _raise(status: int, lib: ctypes.CDLL, last_error: str, what: str) -> None:

@@ -94,6 +94,11 @@ struct Call {
   bool scale_required = false;   // fa_mi355x_*_scaled: 0 is not accepted
   const float* guard = nullptr;
   int produce = 0;             // forward: fill the guard instead of reading it
+  // grouped-query heads (fa_mi355x_*_gqa): k, v (and the caller's dk, dv) have Hkv heads, query head h reads kv head h / (H / Hkv).
+  // validate() then points dk, dv at the workspace's two q-shaped scratch tensors and keeps the caller's pointers in gdk, gdv.
+  bool gqa = false;
+  int Hkv = 0;
+  float *gdk = nullptr, *gdv = nullptr;
   hipStream_t st = nullptr;
   // completed by validate() (tau by fwd_dispatch / bwd_dispatch)
   int batch = 0;               // (batch*head) matrices
@@ -143,9 +148,11 @@ bool causal_ranked(const Tun& tun, int blocks, int wgs_per_cu) {
 // The tiled slot builds of dK/dV and dQ: block kb (qb) of several consecutive heads per workgroup (no set-up, no wait for the K / V
 // fragments or the first stage, no store drain between them) while the grid of nb blocks per head still covers every CU; option
 // 5 = 1: one head per workgroup
+// (grouped-query heads: one head per workgroup.  The tiled builds keep K and V where q lives: their hand-over from head to head has no
+// SGPRs left for a second base and stride, fa_bwd_dq.h)
 int head_tiles(const Call& c, int nb) {
   int tiles = 1;
-  if (c.N % 256 == 0 && c.tun.v[5] == 0) {
+  if (c.N % 256 == 0 && c.tun.v[5] == 0 && c.lay.G == 1) {
     const int cus = device_cus();
     for (int t = 2; t <= 16; ++t)
       if (c.batch % t == 0 && (c.batch / t) % 8 == 0 && (long)(c.batch / t) * nb >= cus) tiles = t;
@@ -156,16 +163,16 @@ int head_tiles(const Call& c, int nb) {
 // only bf16 rows of 64 / 128 elements ever reach a kernel that folds the scale into an operand: everything else gets an all-zero
 // guard ("within the budget"; those calls run fp32-scaling kernels whatever it says)
 inline bool guard_rows_fold(int dtype, int row_elems) { return dtype == FA_DTYPE_BF16 && (row_elems == 64 || row_elems == 128); }
-int launch_scale_guard(const void* q, const void* k, long rows, int row_elems, int dtype, void* guard, hipStream_t st) {
+int launch_scale_guard(const void* q, const void* k, long rows, long krows, int row_elems, int dtype, void* guard, hipStream_t st) {
   if (!guard_rows_fold(dtype, row_elems)) {
     FA_HIP_TRY(hipMemsetAsync(guard, 0, (size_t)2 * fa::GUARD_SLOTS * sizeof(float), st));
     return FA_OK;
   }
   const dim3 grid(fa::GUARD_SLOTS, 2);
   if (row_elems == 64)
-    hipLaunchKernelGGL((fa::scale_guard_kernel<64>), grid, dim3(256), 0, st, (const fa::bf16_t*)q, (const fa::bf16_t*)k, rows, (float*)guard);
+    hipLaunchKernelGGL((fa::scale_guard_kernel<64>), grid, dim3(256), 0, st, (const fa::bf16_t*)q, (const fa::bf16_t*)k, rows, krows, (float*)guard);
   else
-    hipLaunchKernelGGL((fa::scale_guard_kernel<128>), grid, dim3(256), 0, st, (const fa::bf16_t*)q, (const fa::bf16_t*)k, rows, (float*)guard);
+    hipLaunchKernelGGL((fa::scale_guard_kernel<128>), grid, dim3(256), 0, st, (const fa::bf16_t*)q, (const fa::bf16_t*)k, rows, krows, (float*)guard);
   FA_HIP_TRY(hipGetLastError());
   return FA_OK;
 }
@@ -190,6 +197,7 @@ int launch_scale_guard(const void* q, const void* k, long rows, int row_elems, i
   X(DKDV_CARE_MAIN, "bwd_dkdv_kernel") X(DKDV_PAIRED, "bwd_dkdv_kernel") X(DKDV_PAIRED_M3, "bwd_dkdv_kernel")                        \
   X(DKDV_PLAIN, "bwd_dkdv_kernel") X(DKDV_F32_64, "bwd_dkdv_kernel")                                                                 \
   X(ONEPASS, "bwd_onepass_f32_kernel")                                                                                               \
+  X(GROUP_SUM, "group_sum_kernel")      /* grouped-query heads: the group's per-head dK, dV summed into the caller's Hkv heads */    \
   X(GUARD_PASS, "scale_guard_kernel")   /* the separate pass over q and k ... */                                                     \
   X(GUARD_PASS_ZERO, nullptr)           /* ... of rows no kernel folds: launch_scale_guard only zeroes the guard */                  \
   X(GUARD_ZERO, "memset")               /* the guard memset in front of a forward that fills it */                                   \
@@ -212,7 +220,7 @@ struct Step {
   bool check = true;    // hipGetLastError() behind this launch (false: behind its follow-up launch)
 };
 struct Selection {
-  Step steps[8] = {};   // (the most: memsets, preprocess, two launches each of dQ and dK/dV)
+  Step steps[8] = {};   // (the most: memsets, preprocess, two launches each of dQ and dK/dV, the group sum)
   int n = 0;
   bool folds = false;            // a kernel carries tau*log2(e) in a bf16 operand (the MFMA-slot forward without masked periods) ...
   bool produces_guard = false;   // ... and can fill the call's scale guard inside its own launch (its non-causal builds: guard_produce)
@@ -515,7 +523,12 @@ Selection select_bwd(const Call& c) {
   const int need = FA_BWD_STAGE_PREP | FA_BWD_STAGE_DQ;
   Selection s, dq;
   s.onepass = onepass_f32<T, D>(c);
-  if ((c.stages & FA_BWD_STAGE_DQ) && !s.onepass) dq = select_dq<T, D>(c, (c.stages & need) == need && c.tun.v[4] == 0);
+  // grouped-query heads: the one-pass kernel's cut sweep ADDS dK, dV into zeroed outputs with atomics; a grouped call that would take it
+  // runs exactly what option 4 = 4 selects instead (two kernels, separate preprocess), whose per-head stores the ordered group sum adds
+  const bool two_kernels = s.onepass && c.lay.G > 1;
+  if (two_kernels) s.onepass = 0;
+  if ((c.stages & FA_BWD_STAGE_DQ) && !s.onepass)
+    dq = select_dq<T, D>(c, (c.stages & need) == need && c.tun.v[4] == 0 && !two_kernels);
   s.fuses_prep = dq.fuses_prep;
   if ((c.stages & FA_BWD_STAGE_PREP) && !s.fuses_prep) s.add(BWD_PREP, (int)((rows + RPB - 1) / RPB), 256);
   if (s.fuses_prep) s.append(dq);   // dQ first: it preprocesses its own rows and leaves -L/tau, -delta in the workspace for the dK/dV kernel
@@ -528,7 +541,12 @@ Selection select_bwd(const Call& c) {
         c.causal ? rank_chunk(1, nkb) : 0;   // key block 0 (the longest sweep) of a chunk of heads first
     return s;
   }
-  if (c.stages & FA_BWD_STAGE_DKDV) s.append(select_dkdv<T, D>(c));
+  if (c.stages & FA_BWD_STAGE_DKDV) {
+    s.append(select_dkdv<T, D>(c));
+    // grouped-query heads: the launches above stored dK, dV per QUERY head into the workspace's scratch; one ordered sum per group
+    // (fa_aux.h: group_sum_kernel) writes the caller's Hkv heads, one thread per 16-byte chunk of them
+    if (c.lay.G > 1) s.add(GROUP_SUM, (int)((rows / c.lay.G * (D / 4) + 255) / 256), 256);
+  }
   if (!s.fuses_prep) s.append(dq);
   return s;
 }
@@ -655,9 +673,13 @@ int execute(const Call& c, const Selection& sel) {
           }
         }
         break;
+      case GROUP_SUM:   // inner: 16-byte chunks between the heads of a group ([B][N][H][d]: d / 4; [B][H][N][d]: N * d / 4)
+        FA_GO(fa::group_sum_kernel, c.dk, c.dv, c.gdk, c.gdv, rows / lay.G * (D / 4),
+              c.layout == FA_LAYOUT_BNHD ? (long)(D / 4) : (long)N * (D / 4), lay.G);
+        break;
       case GUARD_PASS:
       case GUARD_PASS_ZERO:
-        if (const int rc = launch_scale_guard(c.q, c.k, rows, c.dp, c.dtype, const_cast<float*>(c.guard), c.st)) return rc;
+        if (const int rc = launch_scale_guard(c.q, c.k, rows, rows / lay.G, c.dp, c.dtype, const_cast<float*>(c.guard), c.st)) return rc;
         continue;
       case GUARD_ZERO:
         FA_HIP_TRY(hipMemsetAsync(const_cast<float*>(c.guard), 0, (size_t)2 * fa::GUARD_SLOTS * sizeof(float), c.st));
@@ -686,8 +708,16 @@ int execute(const Call& c, const Selection& sel) {
 
 // tau uses the caller's d even when the rows are zero-padded to dp columns (zero columns of Q/K add
 // nothing to the scores; zero columns of V produce zero output columns that are dropped).
-fa::Layout bhnd(int N, int dp) { return fa::Layout{1, dp, (long)N * dp, 0, nullptr, 1, 0u, 1.0f, 0u, 0}; }
-fa::Layout bnhd(int H, int N, int dp) { return fa::Layout{H, H * dp, (long)N * H * dp, (long)dp, nullptr, 1, 0u, 1.0f, 0u, 0}; }
+// (K and V of an ungrouped call live where q does: group size 1, the same strides)
+fa::Layout ungrouped(fa::Layout l) {
+  l.G = 1;
+  l.kvH = l.H;
+  l.ldk = l.ld;
+  return l;
+}
+fa::Layout bhnd(int N, int dp) { return ungrouped(fa::Layout{1, dp, (long)N * dp, 0, nullptr, 1, 0u, 1.0f, 0u, 0}); }
+fa::Layout bnhd(int H, int N, int dp) { return ungrouped(fa::Layout{H, H * dp, (long)N * H * dp, (long)dp, nullptr, 1, 0u, 1.0f, 0u, 0}); }
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // ---- where tau*log2(e) is applied (round 4) -------------------------------------------------------------------------------------
 // The MFMA-slot kernels fold c = tau*log2(e) into one bf16 operand (one more 2^-9 relative rounding of q or k, worth 8-10 % of the
@@ -785,6 +815,7 @@ int validate(Call& c) {
   if (int rc = parse_opts(c.opts, c.nopts, c.tun)) return rc;
   if (c.bwd && (c.stages <= 0 || c.stages > FA_BWD_STAGE_ALL)) return set_err(FA_ERR_BAD_ARG, "bad stages mask");
   if (c.by_heads && (c.B <= 0 || c.H <= 0)) return set_err(FA_ERR_BAD_ARG, "B and H must be positive");
+  if (c.gqa && (c.Hkv <= 0 || c.H % c.Hkv != 0)) return set_err(FA_ERR_BAD_ARG, "Hkv must be positive and divide H");
   c.batch = c.B * c.H;
   if (c.batch <= 0 || c.N <= 0 || c.d <= 0) return set_err(FA_ERR_BAD_ARG, "batch, N and d must be positive");
   if (c.variant != FA_VARIANT_FA1 && c.variant != FA_VARIANT_FA2) return set_err(FA_ERR_BAD_ARG, "unknown variant");
@@ -811,6 +842,23 @@ int validate(Call& c) {
   c.lay.drop_thr = (uint32_t)((double)c.drop_rate * 16777216.0);   // floor(rate * 2^24); 0 disables dropout
   c.lay.drop_scale = c.drop_scale;
   c.lay.drop_seed = c.drop_seed;
+  if (c.gqa && c.Hkv < c.H) {   // (Hkv == H is by definition the ungrouped call: no scratch, no group sum)
+    // K / V with their own row stride (fa::Layout; their matrices are no larger than q's: the size bounds above cover them)
+    c.lay.G = c.H / c.Hkv;
+    const bool rows_by_head = c.layout == FA_LAYOUT_BNHD;
+    c.lay.kvH = rows_by_head ? c.Hkv : 1;
+    c.lay.ldk = rows_by_head ? c.Hkv * c.dp : c.dp;
+    if (c.bwd) {   // the dK/dV kernels store per query head into the scratch behind the row constants (fa_mi355x_bwd_workspace_bytes_gqa)
+      // (the group sum reads it in 16-byte pieces)
+      if ((uintptr_t)c.ws % 256 != 0) return set_err(FA_ERR_BAD_ARG, "the workspace of a grouped backward must be 256-byte aligned");
+      const size_t elems = (size_t)c.batch * c.N * c.dp;
+      float* scratch = reinterpret_cast<float*>(reinterpret_cast<char*>(c.ws) + align256((size_t)WS_VECS * c.batch * c.N * sizeof(float)));
+      c.gdk = c.dk;
+      c.gdv = c.dv;
+      c.dk = scratch;
+      c.dv = scratch + elems;
+    }
+  }
   return FA_OK;
 }
 
@@ -884,8 +932,6 @@ hipError_t pool_reserve(size_t bytes) {
     hipError_t e_ = (expr);                      \
     if (e_ != hipSuccess) die(#expr, e_);        \
   } while (0)
-
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // host [rows][d] -> device [rows][dp] (zero padded columns)
 void h2d_rows(float* dst, const float* src, size_t rows, int d, int dp, hipStream_t st) {
@@ -1034,6 +1080,34 @@ inline int host_chunks(int batch, size_t bytes_per_bh) {
   return (int)std::max<size_t>(1, std::min<size_t>({want, (size_t)8, (size_t)batch}));
 }
 
+
+// the selectors only pass the call's pointers on to the steps, which are not executed here: any non-null values do
+Call plan_call(int B, int N, int d, int causal, int variant, int dtype, int stages, const int* opts, int nopts) {
+  float* one = reinterpret_cast<float*>(256);   // (aligned as validate() asks of a grouped backward's workspace)
+  Call c = bwd_call(one, one, one, one, one, one, one, one, one, one, one, B, N, d, causal, variant, dtype, stages, nullptr);
+  c.bwd = stages != 0;   // stages = 0: the forward
+  c.opts = opts;
+  c.nopts = nopts;
+  return c;
+}
+int plan(Call c, char* out, size_t n) {
+  if (int rc = validate(c)) return rc;
+  if (!out || n == 0) return set_err(FA_ERR_BAD_ARG, "null output buffer");
+  const Selection sel = select_any(c, true);   // built exactly as a real call builds it
+  std::string joined;
+  for (int i = 0; i < sel.n; ++i)
+    if (const char* name = KERN_NAME[sel.steps[i].kern]) joined += (joined.empty() ? "" : ";") + std::string(name);
+  if (joined.size() + 1 > n) return set_err(FA_ERR_BAD_ARG, "plan buffer too small");
+  memcpy(out, joined.c_str(), joined.size() + 1);
+  return FA_OK;
+}
+Call grouped(Call c, int H, int Hkv, int layout) {   // the B, H, Hkv, layout form of fa_mi355x_*_gqa
+  c = heads(c, H, layout);
+  c.gqa = true;
+  c.Hkv = Hkv;
+  return c;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1088,23 +1162,15 @@ int fa_mi355x_measure_mfma_peak(double min_ms, double* tflops, double* clock_ghz
   return FA_OK;
 }
 
+
 int fa_mi355x_plan(int batch, int N, int d, int causal, int variant, int dtype, int stages, const int* opts, int nopts, char* out,
                    size_t n) {
-  // the selectors only pass the call's pointers on to the steps, which are not executed here: any non-null values do
-  float* one = reinterpret_cast<float*>(16);
-  Call c = bwd_call(one, one, one, one, one, one, one, one, one, one, one, batch, N, d, causal, variant, dtype, stages, nullptr);
-  c.bwd = stages != 0;   // stages = 0: the forward
-  c.opts = opts;
-  c.nopts = nopts;
-  if (int rc = validate(c)) return rc;
-  if (!out || n == 0) return set_err(FA_ERR_BAD_ARG, "null output buffer");
-  const Selection sel = select_any(c, true);   // built exactly as a real call builds it
-  std::string joined;
-  for (int i = 0; i < sel.n; ++i)
-    if (const char* name = KERN_NAME[sel.steps[i].kern]) joined += (joined.empty() ? "" : ";") + std::string(name);
-  if (joined.size() + 1 > n) return set_err(FA_ERR_BAD_ARG, "plan buffer too small");
-  memcpy(out, joined.c_str(), joined.size() + 1);
-  return FA_OK;
+  return plan(plan_call(batch, N, d, causal, variant, dtype, stages, opts, nopts), out, n);
+}
+
+int fa_mi355x_plan_gqa(int B, int H, int Hkv, int N, int d, int causal, int variant, int dtype, int stages, const int* opts,
+                       int nopts, char* out, size_t n) {
+  return plan(grouped(plan_call(B, N, d, causal, variant, dtype, stages, opts, nopts), H, Hkv, FA_LAYOUT_BHND), out, n);
 }
 
 int fa_mi355x_fwd(const void* q, const void* k, const void* v, float* out, float* l, float* m, int batch, int N,
@@ -1234,7 +1300,15 @@ int fa_mi355x_scale_guard(const void* q, const void* k, long rows, int row_elems
   g_err[0] = 0;
   if (!q || !k || !guard || rows <= 0) return set_err(FA_ERR_BAD_ARG, "bad argument");
   if (dtype != FA_DTYPE_F32 && dtype != FA_DTYPE_BF16) return set_err(FA_ERR_BAD_ARG, "unknown dtype");
-  return launch_scale_guard(q, k, rows, row_elems, dtype, guard, (hipStream_t)stream);
+  return launch_scale_guard(q, k, rows, rows, row_elems, dtype, guard, (hipStream_t)stream);
+}
+
+int fa_mi355x_scale_guard_gqa(const void* q, const void* k, long q_rows, long k_rows, int row_elems, int dtype, void* guard,
+                              void* stream) {
+  g_err[0] = 0;
+  if (!q || !k || !guard || q_rows <= 0 || k_rows <= 0) return set_err(FA_ERR_BAD_ARG, "bad argument");
+  if (dtype != FA_DTYPE_F32 && dtype != FA_DTYPE_BF16) return set_err(FA_ERR_BAD_ARG, "unknown dtype");
+  return launch_scale_guard(q, k, q_rows, k_rows, row_elems, dtype, guard, (hipStream_t)stream);
 }
 
 int fa_mi355x_fwd_guarded(const void* q, const void* k, const void* v, float* out, float* l, float* m, int B, int H, int N, int d,
@@ -1260,6 +1334,38 @@ int fa_mi355x_bwd_guarded(const void* q, const void* k, const void* v, const flo
   c.nopts = nopts;
   c.guard = (const float*)guard;
   return validate_and_dispatch(c);
+}
+
+int fa_mi355x_fwd_gqa(const void* q, const void* k, const void* v, float* out, float* l, float* m, int B, int H, int Hkv, int N, int d,
+                      int layout, float softmax_scale, int causal, int variant, int dtype, const int* opts, int nopts, void* guard,
+                      int produce_guard, void* stream) {
+  Call c = grouped(fwd_call(q, k, v, out, l, m, B, N, d, causal, variant, dtype, stream), H, Hkv, layout);
+  c.scale = softmax_scale;
+  c.opts = opts;
+  c.nopts = nopts;
+  c.guard = (const float*)guard;
+  c.produce = produce_guard ? 1 : 0;
+  return validate_and_dispatch(c);
+}
+
+int fa_mi355x_bwd_gqa(const void* q, const void* k, const void* v, const float* out, const void* out_grad, float* q_grad,
+                      float* k_grad, float* v_grad, const float* l, const float* m, void* workspace, int B, int H, int Hkv, int N,
+                      int d, int layout, float softmax_scale, int causal, int variant, int dtype, int stages, const int* opts,
+                      int nopts, const void* guard, void* stream) {
+  Call c = grouped(bwd_call(q, k, v, out, out_grad, q_grad, k_grad, v_grad, l, m, workspace, B, N, d, causal, variant, dtype, stages,
+                            stream), H, Hkv, layout);
+  c.scale = softmax_scale;
+  c.opts = opts;
+  c.nopts = nopts;
+  c.guard = (const float*)guard;
+  return validate_and_dispatch(c);
+}
+
+size_t fa_mi355x_bwd_workspace_bytes_gqa(int B, int H, int Hkv, int N, int d) {
+  if (B <= 0 || H <= 0 || Hkv <= 0 || H % Hkv != 0 || N <= 0 || d <= 0) return 0;
+  const size_t vecs = fa_mi355x_bwd_workspace_bytes(B * H, N, d);
+  if (Hkv == H) return vecs;
+  return align256(vecs) + (size_t)2 * B * H * N * d * sizeof(float);   // + the per-query-head dK and dV of the group sum
 }
 
 size_t fa_mi355x_bwd_workspace_bytes(int batch, int N, int /*d*/) {

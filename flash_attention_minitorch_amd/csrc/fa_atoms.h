@@ -384,6 +384,15 @@ struct Layout {
   // scale guard (fa_common.h: scale_exact).  The forward keeps the pair-of-launches form (its fp32-scaling twin is another kernel).
   int scale_sel;
   int twin_blocks;       // phased forward launched as the fp32-scaling twin of a guarded call: consecutive query blocks per workgroup
+  // Grouped-query heads (H = G * Hkv; query head h reads kv head h / G): where K and V live.  (batch*head) bh reads kv matrix
+  // bh / G, whose element (n, :) is at kv_base(bh) + n * ldk.  kvH: kv matrices per batch element that share rows (their heads lie
+  // side by side in a row).  [B][Hkv][N][d]: kvH = 1, ldk = d; [B][N][Hkv][d]: kvH = Hkv, ldk = Hkv*d.  K/V's batch stride is N * ldk
+  // and their head stride d in both (kv_base forms them: three scalars here instead of five, the tiled slot builds carry them from
+  // head to head).  An ungrouped call has G = 1, kvH = H, ldk = ld: kv_base == head_base.  Everything indexed by the QUERY head (q,
+  // o, dO, the gradients the kernels store, row constants, dropout hash, key-mask row) keeps head_base and ld.
+  int G;
+  int kvH;
+  int ldk;
 };
 
 // Counter-based dropout bit of attention position (batch*head bh, query q, key k): a 32-bit finaliser (two
@@ -404,6 +413,13 @@ FA_DEV bool drop_keep(uint32_t base_bh_q, int k, uint32_t thr) {
 }
 FA_DEV size_t head_base(const Layout& L, int bh) {
   return (size_t)(bh / L.H) * (size_t)L.bstride + (size_t)(bh % L.H) * (size_t)L.hstride;
+}
+
+template <int D>   // D: elements of a row (the kernel's head dim)
+FA_DEV size_t kv_base(const Layout& L, int bh, int N) {
+  if (L.G == 1) return head_base(L, bh);   // (ungrouped: the value the kernel has already formed, no second pair of divisions)
+  const int kvh = bh / L.G;
+  return (size_t)(kvh / L.kvH) * ((size_t)N * (size_t)L.ldk) + (size_t)((kvh % L.kvH) * D);
 }
 
 // Workgroup id -> (batch*head, block) with every block of one (batch*head) on the same XCD

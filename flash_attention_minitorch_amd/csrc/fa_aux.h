@@ -42,15 +42,16 @@ __global__ void __launch_bounds__(512) mfma_peak_kernel(float* __restrict__ sink
 // ---------------------------------------------------------------------------------------------
 // Scale guard (fa_common.h: guard_skip): the largest squared row norm of q (blockIdx.y = 0) and of k (1), as GUARD_SLOTS partial
 // maxima each.  A row is D contiguous bf16 elements in both layouts ([BH][N][d] and [B][N][H][d]), so the kernel sees `rows` rows of
-// D elements whatever the layout (zero-padded columns add nothing).  HBM-bound: one pass over both tensors, 16 bytes per lane.
+// D elements whatever the layout (zero-padded columns add nothing); k has `krows` of them (grouped-query heads: B*N*Hkv).
+// HBM-bound: one pass over both tensors, 16 bytes per lane.
 // ---------------------------------------------------------------------------------------------
 template <int D>
 __global__ void __launch_bounds__(256) scale_guard_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, long rows,
-                                                          float* __restrict__ guard) {
+                                                          long krows, float* __restrict__ guard) {
   constexpr int LPR = D / 8;   // lanes per row, 8 elements each
   static_assert(256 % LPR == 0 && 64 % LPR == 0, "a row's lanes sit in one wave");
   const bf16_t* p = blockIdx.y ? k : q;
-  const long total = rows * LPR, stride = (long)gridDim.x * 256;
+  const long total = (blockIdx.y ? krows : rows) * LPR, stride = (long)gridDim.x * 256;
   float mx = 0.f;
   constexpr int U = 8;   // 16-byte loads in flight per lane: 16 MiB across the chip (4 gave 8 MiB = 4.6 TB/s at HBM latency)
   for (long c0 = (long)blockIdx.x * 256 + threadIdx.x; c0 < total; c0 += U * stride) {
@@ -76,6 +77,39 @@ __global__ void __launch_bounds__(256) scale_guard_kernel(const bf16_t* __restri
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = mx;
   __syncthreads();
   if (threadIdx.x == 0) guard[blockIdx.y * GUARD_SLOTS + blockIdx.x] = fmaxf(fmaxf(part[0], part[1]), fmaxf(part[2], part[3]));
+}
+
+// ---------------------------------------------------------------------------------------------
+// Grouped-query heads, backward: the dK/dV kernels of a grouped call store one dK and one dV per QUERY head into two q-shaped fp32
+// scratch tensors (sk, sv); this kernel adds the G heads of every group, g ascending, into the caller's Hkv-head dk and dv:
+//   dk[b, hkv] = sk[b, hkv*G + 0] + sk[b, hkv*G + 1] + ... + sk[b, hkv*G + G-1]     (and dv from sv, in the same launch)
+// No atomics: the order of every sum depends on the arguments alone.  Both layouts in one index map, in 16-byte units: output chunk o
+// reads scratch chunks (o / inner) * G * inner + g * inner + o % inner, with inner = d/4 under [B][N][H][d] (a group's G rows lie side
+// by side: G*d contiguous floats) and N*d/4 under [B][H][N][d] (G whole matrices apart).  HBM-bound: reads 2*B*H*N*d floats, writes
+// 2*B*Hkv*N*d, one output chunk of dk and of dv per thread, the group's loads issued four deep.
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) group_sum_kernel(const float* __restrict__ sk, const float* __restrict__ sv, float* __restrict__ dk,
+                                                        float* __restrict__ dv, long total, long inner, int G) {
+  const long o = (long)blockIdx.x * 256 + threadIdx.x;
+  if (o >= total) return;
+  long src;
+  if (total * G < (1L << 32)) {   // (kernel arguments: a scalar branch) 32-bit division where every index fits
+    const uint32_t o32 = (uint32_t)o, in32 = (uint32_t)inner, outer = o32 / in32;
+    src = (long)(outer * ((uint32_t)G * in32) + (o32 - outer * in32));
+  } else {
+    const long outer = o / inner;
+    src = outer * G * inner + (o - outer * inner);
+  }
+  const f32x4* pk = reinterpret_cast<const f32x4*>(sk) + src;
+  const f32x4* pv = reinterpret_cast<const f32x4*>(sv) + src;
+  f32x4 ak = pk[0], av = pv[0];
+#pragma unroll 4
+  for (int g = 1; g < G; ++g) {
+    ak += pk[g * inner];
+    av += pv[g * inner];
+  }
+  reinterpret_cast<f32x4*>(dk)[o] = ak;
+  reinterpret_cast<f32x4*>(dv)[o] = av;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -84,8 +84,11 @@ bwd_dkdv_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
   const uint32_t mat_bytes = ((uint32_t)(N - 1) * ld + D) * (uint32_t)sizeof(T);
   const rsrc_t qrs = make_rsrc(q + base, mat_bytes);
   const rsrc_t dors = make_rsrc(dout + base, mat_bytes);
-  const rsrc_t krs = make_rsrc(k + base, mat_bytes);
-  const rsrc_t vrs = make_rsrc(v + base, mat_bytes);
+  const size_t kvb = kv_base<D>(lay, bh, N);   // K / V: the group's kv head, its own row stride (Layout: grouped-query heads)
+  const int ldk = lay.ldk;
+  const uint32_t kv_bytes = ((uint32_t)(N - 1) * ldk + D) * (uint32_t)sizeof(T);
+  const rsrc_t krs = make_rsrc(k + kvb, kv_bytes);
+  const rsrc_t vrs = make_rsrc(v + kvb, kv_bytes);
   const float* nlg = nlc + (size_t)bh * N;
   const float* deg = ndelta + (size_t)bh * N;
   const float c = tau * LOG2E;
@@ -95,7 +98,7 @@ bwd_dkdv_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
   for (int kt = 0; kt < KT; ++kt)
 #pragma unroll
     for (int kc = 0; kc < KC; ++kc) {
-      const int off = ((kw0 + 32 * kt + r) * ld + 16 * kc + 8 * h) * (int)sizeof(T);  // rows >= N read as zero
+      const int off = ((kw0 + 32 * kt + r) * ldk + 16 * kc + 8 * h) * (int)sizeof(T);  // rows >= N read as zero
       kf[kt][kc] = load_frag_buf<T>(krs, off);
       vf[kt][kc] = load_frag_buf<T>(vrs, off);
     }
@@ -603,8 +606,16 @@ bwd_dkdv_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* 
   size_t base = head_base(lay, bh);
   const int ld = lay.ld;
   const uint32_t mat_bytes = ((uint32_t)(N - 1) * ld + D) * (uint32_t)sizeof(T);
-  rsrc_t krs = make_rsrc(k + base, mat_bytes);
-  rsrc_t vrs = make_rsrc(v + base, mat_bytes);
+  // K / V: the group's kv head, its own row stride (Layout: grouped-query heads).  Not the tiled build (see bwd_dq_slot_kernel):
+  // grouped calls take the one-head-per-workgroup build, so there K and V live where q does.
+  const int ldk = TILED ? ld : lay.ldk;
+  const uint32_t kv_bytes = TILED ? mat_bytes : ((uint32_t)(N - 1) * ldk + D) * (uint32_t)sizeof(T);
+  rsrc_t krs, vrs;
+  {
+    const size_t kvb = TILED ? base : kv_base<D>(lay, bh, N);
+    krs = make_rsrc(k + kvb, kv_bytes);
+    vrs = make_rsrc(v + kvb, kv_bytes);
+  }
   raw_rsrc_t qraw = make_raw_rsrc(q + base, mat_bytes), doraw = make_raw_rsrc(dout + base, mat_bytes);
   // Both scalings in one launch (Layout::scale_sel): exact = the K fragments stay unscaled, the row constant is -L/tau (raw score
   // units: the workspace's FIRST vector, two vectors in front of nl2) and every score is multiplied in fp32, P = exp2(c * S').
@@ -621,7 +632,7 @@ bwd_dkdv_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* 
     const int rr = r, hh = h;   // (copies, and the lambda `block` below: the form whose register assignment hipcc gave the measured builds)
 #pragma unroll
     for (int kc = 0; kc < KC; ++kc) {
-      const int off = ((k0 + rr) * ld + 16 * kc + 8 * hh) * (int)sizeof(T);   // rows >= N read as zero
+      const int off = ((k0 + rr) * ldk + 16 * kc + 8 * hh) * (int)sizeof(T);   // rows >= N read as zero
       kf[kc] = load_frag_buf<T>(krs, off);
       vf[kc] = load_frag_buf<T>(vrs, off);
     }
@@ -836,7 +847,7 @@ bwd_dkdv_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* 
     if (t + 1 < tiles) {
       ++bh;
       base = head_base(lay, bh);
-      krs = make_rsrc(k + base, mat_bytes);
+      krs = make_rsrc(k + base, mat_bytes);   // (tiled build: ungrouped calls only, see above)
       vrs = make_rsrc(v + base, mat_bytes);
       load_kv(kw0);
       roff = (roff + nst) % 3;
@@ -892,7 +903,7 @@ bwd_dkdv_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* 
       if (exactk) {   // the unscaled K and the fp32 fma (the rounding of cK is the same for every query and these rows average nothing out)
         frag ku[KC];
 #pragma unroll
-        for (int kc = 0; kc < KC; ++kc) ku[kc] = load_frag_buf<T>(krs, ((kw0 + r) * ld + 16 * kc + 8 * h) * (int)sizeof(T));
+        for (int kc = 0; kc < KC; ++kc) ku[kc] = load_frag_buf<T>(krs, ((kw0 + r) * ldk + 16 * kc + 8 * h) * (int)sizeof(T));
 #pragma unroll
         for (int kc = 0; kc < KC; ++kc) {
           const frag aq = A::template row_frag<D>(tq, ra, 32 * sub, kc);

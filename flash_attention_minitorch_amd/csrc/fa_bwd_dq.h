@@ -90,9 +90,12 @@ bwd_dq_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restr
   const uint32_t mat_bytes = ((uint32_t)(N - 1) * ld + D) * (uint32_t)sizeof(T);
   rsrc_t qrs = make_rsrc(q + base, mat_bytes);
   rsrc_t dors = make_rsrc(dout + base, mat_bytes);
-  raw_rsrc_t kraw = make_raw_rsrc(k + base, mat_bytes), vraw = make_raw_rsrc(v + base, mat_bytes);
-  const rsrc_t krs = make_rsrc(k + base, mat_bytes);
-  const rsrc_t vrs = make_rsrc(v + base, mat_bytes);
+  const size_t kvb = kv_base<D>(lay, bh, N);   // K / V: the group's kv head, its own row stride (Layout: grouped-query heads)
+  const int ldk = lay.ldk;
+  const uint32_t kv_bytes = ((uint32_t)(N - 1) * ldk + D) * (uint32_t)sizeof(T);
+  raw_rsrc_t kraw = make_raw_rsrc(k + kvb, kv_bytes), vraw = make_raw_rsrc(v + kvb, kv_bytes);
+  const rsrc_t krs = make_rsrc(k + kvb, kv_bytes);
+  const rsrc_t vrs = make_rsrc(v + kvb, kv_bytes);
   const float c = tau * LOG2E;
 
   frag qf[KC], dof[KC];
@@ -123,8 +126,8 @@ bwd_dq_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restr
   const int kmax = causal ? min(N, qb * (32 * NWQ) + 32 * NWQ) : N;
   const int nt = (kmax + BN - 1) / BN;
   TileStager<T, D, BN, 64 * NWQ> sk, sv;
-  sk.init(tid, ld);
-  sv.init(tid, ld);
+  sk.init(tid, ldk);
+  sv.init(tid, ldk);
   sk.load(krs, 0);
   sv.load(vrs, 0);
   sk.store(smem);
@@ -326,7 +329,17 @@ bwd_dq_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __
   const uint32_t mat_bytes = ((uint32_t)(N - 1) * ld + D) * (uint32_t)sizeof(T);
   rsrc_t qrs = make_rsrc(q + base, mat_bytes);
   rsrc_t dors = make_rsrc(dout + base, mat_bytes);
-  raw_rsrc_t kraw = make_raw_rsrc(k + base, mat_bytes), vraw = make_raw_rsrc(v + base, mat_bytes);
+  // K / V: the group's kv head, its own row stride (Layout: grouped-query heads).  Not the tiled build: it carries every such scalar
+  // from head to head next to a pipeline that already keeps SGPRs in VGPR lanes (the K/V fields cost the ungrouped metric 3 TFLOP/s of 919
+  // there, profiles/gqa_ungrouped_ab.txt); grouped calls take the one-head-per-workgroup build (fa_api.hip: head_tiles), so here K and V live where q does.
+  const int ldk = TILED ? ld : lay.ldk;
+  const uint32_t kv_bytes = TILED ? mat_bytes : ((uint32_t)(N - 1) * ldk + D) * (uint32_t)sizeof(T);
+  raw_rsrc_t kraw, vraw;
+  {
+    const size_t kvb = TILED ? base : kv_base<D>(lay, bh, N);
+    kraw = make_raw_rsrc(k + kvb, kv_bytes);
+    vraw = make_raw_rsrc(v + kvb, kv_bytes);
+  }
   const float c = tau * LOG2E;
   const int npass = TILED ? tiles : ((CDIAG && !ranked && pblk != nqb - 1 - pblk) ? 2 : 1);
   int roff = 0;   // tiled build: ring position of the current block's stage 0
@@ -388,12 +401,12 @@ bwd_dq_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __
   // Stage loads go global -> LDS directly (buffer_load ... lds, 1 KiB = 8 rows per wave-instruction, no staging
   // registers): wave w moves the 8-row groups w and w + 8 of K and of V (same parity, hence one lane offset).
   const uint32_t smem_addr = (uint32_t)(uintptr_t)smem;
-  FA_DMA_VOFF(dma_voff, RG::PPG, lane, w, ld, (int)sizeof(T));
+  FA_DMA_VOFF(dma_voff, RG::PPG, lane, w, ldk, (int)sizeof(T));
   auto stage_dma = [&](int row0, int slot_base) {
 #pragma unroll
     for (int g2 = 0; g2 < 2; ++g2) {
       const int g = w + 8 * g2;
-      const int soff = (row0 + 8 * g) * ld * (int)sizeof(T);
+      const int soff = (row0 + 8 * g) * ldk * (int)sizeof(T);
       dma16(kraw, smem_addr + slot_base + 1024 * g, dma_voff, soff);
       dma16(vraw, smem_addr + slot_base + VOFF + 1024 * g, dma_voff, soff);
     }
@@ -540,7 +553,7 @@ bwd_dq_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __
     const int nr0 = ra.b[0] + nb, nr1 = ra.b[1] + nb;   // rows of the next stage
     if (CDIAG || more) stage_dma((st + 1) * ST, nb);   // (causal build: the two stages of the diagonal block follow the sweep)
     else if (TILED && pass + 1 < npass) {   // the next head's sweep: its key stage 0 follows in the ring
-      const size_t nbase = head_base(lay, bh + 1);
+      const size_t nbase = head_base(lay, bh + 1);   // (tiled build: ungrouped calls only, see above)
       kraw = make_raw_rsrc(k + nbase, mat_bytes);
       vraw = make_raw_rsrc(v + nbase, mat_bytes);
       stage_dma(0, nb);

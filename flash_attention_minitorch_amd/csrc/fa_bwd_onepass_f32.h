@@ -62,7 +62,10 @@ bwd_onepass_f32_kernel(const float* __restrict__ q, const float* __restrict__ k,
   const int ld = lay.ld;
   const uint32_t mat_bytes = ((uint32_t)(N - 1) * ld + D) * 4u;
   const rsrc_t qrs = make_rsrc(q + base, mat_bytes), dors = make_rsrc(dout + base, mat_bytes);
-  const rsrc_t krs = make_rsrc(k + base, mat_bytes), vrs = make_rsrc(v + base, mat_bytes);
+  const size_t kvb = kv_base<D>(lay, bh, N);   // K / V: the group's kv head, its own row stride (Layout: grouped-query heads; the gradients it
+  const int ldk = lay.ldk;               // stores and adds stay with the query head, so a grouped call never selects this kernel)
+  const uint32_t kv_bytes = ((uint32_t)(N - 1) * ldk + D) * 4u;
+  const rsrc_t krs = make_rsrc(k + kvb, kv_bytes), vrs = make_rsrc(v + kvb, kv_bytes);
   const rsrc_t dqrs = make_rsrc(dq + base, mat_bytes);
   const float* nlg = nlc + (size_t)bh * N;
   const float* deg = ndelta + (size_t)bh * N;
@@ -71,10 +74,10 @@ bwd_onepass_f32_kernel(const float* __restrict__ q, const float* __restrict__ k,
 
   frag vf[KC];   // (the wave's K fragments are re-read from the key image every stage: 32 registers for 8 LDS reads)
 #pragma unroll
-  for (int kc = 0; kc < KC; ++kc) vf[kc] = load_frag_buf<float>(vrs, ((kw0 + r) * ld + 16 * kc + 8 * h) * 4);
+  for (int kc = 0; kc < KC; ++kc) vf[kc] = load_frag_buf<float>(vrs, ((kw0 + r) * ldk + 16 * kc + 8 * h) * 4);
   {   // the block's key rows as an LDS image (the B operand of dQ = dS K by column reads)
     TileStager<float, D, OP32_BK, 512> sk;
-    sk.init(tid, ld);
+    sk.init(tid, ldk);
     sk.load(krs, kb0);
     if (RAGGED && kb0 + OP32_BK > N) {   // ragged N: key rows past N as exact zeros (dS is zero there; 0 * whatever lies behind the tensor must be too)
 #pragma unroll

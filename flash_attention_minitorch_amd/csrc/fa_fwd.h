@@ -61,8 +61,11 @@ fwd_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict
   const int ld = lay.ld;   // elements between consecutive rows
   const uint32_t mat_bytes = ((uint32_t)(N - 1) * ld + D) * (uint32_t)sizeof(T);
   const rsrc_t qrs = make_rsrc(q + base, mat_bytes);
-  const rsrc_t krs = make_rsrc(k + base, mat_bytes);
-  const rsrc_t vrs = make_rsrc(v + base, mat_bytes);
+  const size_t kvb = kv_base<D>(lay, bh, N);   // K / V: the group's kv head, its own row stride (Layout: grouped-query heads)
+  const int ldk = lay.ldk;
+  const uint32_t kv_bytes = ((uint32_t)(N - 1) * ldk + D) * (uint32_t)sizeof(T);
+  const rsrc_t krs = make_rsrc(k + kvb, kv_bytes);
+  const rsrc_t vrs = make_rsrc(v + kvb, kv_bytes);
   const float c = tau * LOG2E;
 
   frag qf[KC];
@@ -80,8 +83,8 @@ fwd_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict
   const int kmax = causal ? min(N, qb * 128 + 128) : N;
   const int nt = (kmax + BN - 1) / BN;
   TileStager<T, D, BN, 256> sk, sv;
-  sk.init(tid, ld);
-  sv.init(tid, ld);
+  sk.init(tid, ldk);
+  sv.init(tid, ldk);
   sk.load(krs, 0);
   sv.load(vrs, 0);
   sk.store(smem);
@@ -283,7 +286,7 @@ fwd_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict
 // phased kernel is correct for.  On return acc_o / l_run are relative to m_ref, the row maximum in log2 units (tau*log2e * q.k).
 // ---------------------------------------------------------------------------------------------
 template <int D>
-FA_DEV void fwd_redo_rows(rsrc_t qrs, rsrc_t krs, rsrc_t vrs, int qrow, int q0, int ld, int N, bool causal, float c, int r, int h,
+FA_DEV void fwd_redo_rows(rsrc_t qrs, rsrc_t krs, rsrc_t vrs, int qrow, int q0, int ld, int ldk, int N, bool causal, float c, int r, int h,
                           f32x16 (&acc_o)[D / 32], float& m_ref, float& l_run) {
   using A = Atom<bf16_t>;
   typedef A::frag frag;
@@ -303,7 +306,7 @@ FA_DEV void fwd_redo_rows(rsrc_t qrs, rsrc_t krs, rsrc_t vrs, int qrow, int q0, 
     f32x16 s;
 #pragma unroll
     for (int kc = 0; kc < KC; ++kc) {
-      const frag kk = load_frag_buf<bf16_t>(krs, ((k0 + r) * ld + 16 * kc + 8 * h) * 2);   // rows >= N read as zero
+      const frag kk = load_frag_buf<bf16_t>(krs, ((k0 + r) * ldk + 16 * kc + 8 * h) * 2);   // rows >= N read as zero
       if (kc == 0) A::mma_c(s, kk, qf[0], zero16());
       else A::mma(s, kk, qf[kc]);
     }
@@ -348,7 +351,7 @@ FA_DEV void fwd_redo_rows(rsrc_t qrs, rsrc_t krs, rsrc_t vrs, int qrow, int q0, 
         u16x8 raw;
 #pragma unroll
         for (int j = 0; j < 8; ++j)   // element j: V[k0 + 16*s2 + 8*(j>>2) + 4*h + (j&3)][32*dt + r]  (Atom::tr_frag's map)
-          raw[j] = __builtin_amdgcn_raw_buffer_load_b16(vrs, ((k0 + 16 * s2 + 8 * (j >> 2) + 4 * h + (j & 3)) * ld + 32 * dt + r) * 2, 0, 0);
+          raw[j] = __builtin_amdgcn_raw_buffer_load_b16(vrs, ((k0 + 16 * s2 + 8 * (j >> 2) + 4 * h + (j & 3)) * ldk + 32 * dt + r) * 2, 0, 0);
         const frag vt = __builtin_bit_cast(frag, raw);
         A::mma(acc_o[dt], vt, s2 ? pf1 : pf0);
         A::mma(acc_o[dt], vt, s2 ? pl1 : pl0);
@@ -426,7 +429,10 @@ fwd_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
   const int ld = lay.ld;
   const uint32_t mat_bytes = ((uint32_t)(N - 1) * ld + D) * (uint32_t)sizeof(T);
   const rsrc_t qrs = make_rsrc(q + base, mat_bytes);
-  const raw_rsrc_t kraw = make_raw_rsrc(k + base, mat_bytes), vraw = make_raw_rsrc(v + base, mat_bytes);
+  const size_t kvb = kv_base<D>(lay, bh, N);   // K / V: the group's kv head, its own row stride (Layout: grouped-query heads)
+  const int ldk = lay.ldk;
+  const uint32_t kv_bytes = ((uint32_t)(N - 1) * ldk + D) * (uint32_t)sizeof(T);
+  const raw_rsrc_t kraw = make_raw_rsrc(k + kvb, kv_bytes), vraw = make_raw_rsrc(v + kvb, kv_bytes);
   const float c = tau * LOG2E;
   const int npass = (CDIAG && !ranked && pblk != nqb - 1 - pblk) ? 2 : 1;
   for (int pass = 0; pass < npass; ++pass) {
@@ -450,9 +456,9 @@ fwd_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
   const bool produce = PRE && !CDIAG && lay.guard_want == 2 && lay.guard != nullptr;
   frag kg[KC];   // (the key rows of the query rows' indices: requested here, summed behind the first stages' LDS-DMA, see below)
   if (produce) {
-    const rsrc_t krs = make_rsrc(k + base, mat_bytes);
+    const rsrc_t krs = make_rsrc(k + kvb, kv_bytes);
 #pragma unroll
-    for (int kc = 0; kc < KC; ++kc) kg[kc] = load_frag_buf<T>(krs, (qrow * ld + 16 * kc + 8 * h) * (int)sizeof(T));
+    for (int kc = 0; kc < KC; ++kc) kg[kc] = load_frag_buf<T>(krs, (qrow * ldk + 16 * kc + 8 * h) * (int)sizeof(T));
   }
 #pragma unroll
   for (int kc = 0; kc < KC; ++kc) qf[kc] = load_frag_buf<T>(qrs, (qrow * ld + 16 * kc + 8 * h) * (int)sizeof(T));
@@ -469,12 +475,12 @@ fwd_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
   const int nstage = (kmax + ST - 1) / ST;
   const uint32_t smem_addr = (uint32_t)(uintptr_t)smem;
   // LDS-DMA pieces of 1 KiB: d = 64: one 8-row group (piece = w, w + 8); d = 128: half of one (piece = 2 * group + half).
-  FA_DMA_VOFF(dma_voff, RG::PPG, lane, w, ld, (int)sizeof(T));
+  FA_DMA_VOFF(dma_voff, RG::PPG, lane, w, ldk, (int)sizeof(T));
   auto stage_dma = [&](int row0, int slot_base) {
 #pragma unroll
     for (int g2 = 0; g2 < RG::NPW; ++g2) {
       const int piece = w + 8 * g2, g = piece / RG::PPG;
-      const int soff = (row0 + 8 * g) * ld * (int)sizeof(T);
+      const int soff = (row0 + 8 * g) * ldk * (int)sizeof(T);
       dma16(kraw, smem_addr + slot_base + 1024 * piece, dma_voff, soff);
       dma16(vraw, smem_addr + slot_base + VOFF + 1024 * piece, dma_voff, soff);
     }
@@ -811,14 +817,13 @@ fwd_slot_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
   float l_tot = xhalf_sum(l_run);
   if constexpr (PRE) {   // a row sum outside [2^-96, 2^96] (or NaN): exp2(S') over- or underflowed somewhere in the wave's rows
     if (__any(!(l_tot >= 0x1p-96f && l_tot <= 0x1p96f))) {
-      const uint32_t kv_bytes = ((uint32_t)(N - 1) * ld + D) * (uint32_t)sizeof(T);
       if constexpr (CDIAG) {
         const int l2 = lane_fresh();
         r = l2 & 31;
         h = l2 >> 5;
         qrow = q0 + r;
       }
-      fwd_redo_rows<D>(qrs, make_rsrc(k + base, kv_bytes), make_rsrc(v + base, kv_bytes), qrow, q0, ld, N, CDIAG, c, r, h, acc_o,
+      fwd_redo_rows<D>(qrs, make_rsrc(k + kvb, kv_bytes), make_rsrc(v + kvb, kv_bytes), qrow, q0, ld, ldk, N, CDIAG, c, r, h, acc_o,
                        m_ref, l_run);
       l_tot = xhalf_sum(l_run);
     }

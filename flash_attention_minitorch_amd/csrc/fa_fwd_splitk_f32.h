@@ -34,7 +34,10 @@ fwd_splitk_f32_kernel(const float* __restrict__ q, const float* __restrict__ k, 
   const size_t base = head_base(lay, bh);
   const int ld = lay.ld;
   const uint32_t mat_bytes = ((uint32_t)(N - 1) * ld + D) * 4u;
-  const rsrc_t qrs = make_rsrc(q + base, mat_bytes), krs = make_rsrc(k + base, mat_bytes), vrs = make_rsrc(v + base, mat_bytes);
+  const size_t kvb = kv_base<D>(lay, bh, N);   // K / V: the group's kv head, its own row stride (Layout: grouped-query heads)
+  const int ldk = lay.ldk;
+  const uint32_t kv_bytes = ((uint32_t)(N - 1) * ldk + D) * 4u;
+  const rsrc_t qrs = make_rsrc(q + base, mat_bytes), krs = make_rsrc(k + kvb, kv_bytes), vrs = make_rsrc(v + kvb, kv_bytes);
   const float c = tau * LOG2E;
 
   frag qf[KC];
@@ -52,8 +55,8 @@ fwd_splitk_f32_kernel(const float* __restrict__ q, const float* __restrict__ k, 
   const int kmax = causal ? min(N, q0 + 32) : N;
   const int nt = (kmax + BN - 1) / BN;
   TileStager<float, D, BN, 64> sk, sv;   // one wave moves its own tiles
-  sk.init(lane, ld);
-  sv.init(lane, ld);
+  sk.init(lane, ldk);
+  sv.init(lane, ldk);
   int t = w;
   if (t < nt) {
     sk.load(krs, t * BN);

@@ -5,7 +5,8 @@ This is SURVEY.md row f2 (replace the reference's per-call malloc / H2D / D2H,
 torch is plumbing only: device memory, streams.  All arithmetic runs in the HIP kernels.
 
 Tensors are (B, H, N, d) or (BH, N, d), contiguous, float32 or bfloat16; outputs (O, dQ, dK, dV) are
-float32 (a bf16 store alone would exceed the 1e-3 max-abs bound).
+float32 (a bf16 store alone would exceed the 1e-3 max-abs bound).  Grouped-query heads (k and v with fewer
+heads than q, read in place): flash_attn_fwd_gqa / flash_attn_bwd_gqa / flash_attn_gqa.
 
 Every training entry point is one call of ``_fwd`` or ``_bwd``: the checks in one fixed order, the allocation of what the caller did not
 supply, and exactly one C call.
@@ -416,6 +417,139 @@ def flash_attn2(q, k, v, causal=False):       # Tensor.flash_attn2, minitorch/te
 
 
 _DECODE_LAYOUTS = {"bnhd": _lib.FA_LAYOUT_BNHD, "bhnd": _lib.FA_LAYOUT_BHND}
+
+
+# ---- grouped-query heads (GQA / MQA): fa_mi355x_fwd_gqa / _bwd_gqa ----------------------------------------------------------------
+# q has H heads, k and v have Hkv (read from k's shape; H a multiple of it): query head h reads kv head h // (H // Hkv), in place --
+# no expanded copy of k or v, forward or backward.  ``layout`` "bnhd": q (B, N, H, d), k and v (B, N, Hkv, d); "bhnd": (B, H, N, d) and
+# (B, Hkv, N, d).  dk and dv come back in k's shape.
+
+def _check_gqa(layout, q, k, v, o=None, do=None):
+    """The checks of a grouped call, in one order.  Returns (B, H, Hkv, N, d, dtype code) as the C entry points take them."""
+    if layout not in _DECODE_LAYOUTS:
+        raise ValueError(f"layout must be one of {sorted(_DECODE_LAYOUTS)}")
+    _require_gpu(q, "device_ops")
+    dtype = _dtype_code(q)
+    if q.dim() != 4 or k.dim() != 4:
+        raise ValueError("expected 4-d tensors: q (B, N, H, d) and k, v (B, N, Hkv, d) for \"bnhd\", (B, H, N, d) and (B, Hkv, N, d) for \"bhnd\"")
+    dev = q.get_device()
+    if v.shape != k.shape:
+        raise ValueError("k and v must have one shape")
+    for t in (k, v):
+        if not t.is_cuda or t.dtype != q.dtype or t.get_device() != dev:
+            raise ValueError("q, k, v must be GPU tensors of one dtype on one device")
+    if layout == "bnhd":
+        (B, N, H, d), (Bk, Nk, Hkv, dk) = q.shape, k.shape
+    else:
+        (B, H, N, d), (Bk, Hkv, Nk, dk) = q.shape, k.shape
+    if (B, N, d) != (Bk, Nk, dk):
+        raise ValueError(f"q and k disagree on (B, N, d): {(B, N, d)} vs {(Bk, Nk, dk)}")
+    if Hkv <= 0 or H % Hkv:
+        raise ValueError(f"q's {H} heads must be a multiple of k's {Hkv}")
+    if d not in _NATIVE_D:
+        raise ValueError("grouped-query heads need a native head dim (32, 64, 128): pad q, k and v (pad_head_dim) and pass softmax_scale")
+    if do is not None and (do.shape != q.shape or do.dtype != q.dtype or do.get_device() != dev):
+        raise ValueError("out_grad must share q's shape, dtype and device")
+    for t in (q, k, v) + ((do,) if do is not None else ()):
+        if not t.is_contiguous():
+            raise ValueError("tensors must be contiguous")
+    if o is not None and (o.dtype is not _F32 or o.shape != q.shape or not o.is_contiguous() or o.get_device() != dev):
+        raise ValueError("out must be the forward's contiguous float32 output")
+    return B, H, Hkv, N, d, dtype
+
+
+def _scale_guard_gqa(q, k):
+    """scale_guard for tensors with different head counts (fa_mi355x_scale_guard_gqa: q has B*N*H rows of d elements, k B*N*Hkv)."""
+    out = torch.empty(_lib.guard_elems(), dtype=_F32, device=q.device)
+    d = q.shape[-1]
+    _lib.check(_lib.core().fa_mi355x_scale_guard_gqa(_ptr(q), _ptr(k), q.numel() // d, k.numel() // d, d, _dtype_code(q), _ptr(out),
+                                                     _stream_ptr()))
+    return out
+
+
+def bwd_workspace_gqa(q, k, layout="bnhd"):
+    """Scratch for flash_attn_bwd_gqa with these tensors (fa_mi355x_bwd_workspace_bytes_gqa): the three row-constant vectors and, when
+    k has fewer heads than q, two float32 tensors of q's shape (the dK and dV of every query head, which the group sum then adds)."""
+    B, H, Hkv, N, d, _ = _check_gqa(layout, q, k, k)
+    nbytes = _lib.core().fa_mi355x_bwd_workspace_bytes_gqa(B, H, Hkv, N, d)
+    return torch.empty((nbytes + 3) // 4, dtype=_F32, device=q.device)
+
+
+def flash_attn_fwd_gqa(q, k, v, causal=False, variant=_lib.FA_VARIANT_FA2, softmax_scale=None, layout="bnhd", guard="auto", opts=None,
+                       produce_guard=False, out=None):
+    """Forward with grouped-query heads.  Returns (out fp32 in q's shape, l (B, H, N), m (B, H, N) or None); ``guard``, ``opts``,
+    ``produce_guard`` and ``softmax_scale`` as flash_attn_fwd / flash_attn_fwd_bnhd.  k with q's head count is the ungrouped call."""
+    B, H, Hkv, N, d, dtype = _check_gqa(layout, q, k, v)
+    if out is not None and (out.dtype is not _F32 or out.shape != q.shape or not out.is_contiguous() or out.get_device() != q.get_device()):
+        raise ValueError("out must be a contiguous float32 tensor of q's shape")
+    _check_caller(q.get_device(), B * H * N, None, None, guard)
+    dev, causal = q.device, int(bool(causal))
+    l = torch.empty((B, H, N), dtype=_F32, device=dev)
+    m = torch.empty((B, H, N), dtype=_F32, device=dev) if variant == _FA1 else None
+    if out is None:
+        out = torch.empty(q.shape, dtype=_F32, device=dev)
+    arr, cnt = _lib.opts_array(opts)
+    if isinstance(guard, str):
+        guard, produce_guard = new_guard(q, opts), True
+    _lib.check(_lib.core().fa_mi355x_fwd_gqa(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(l), _ptr(m), B, H, Hkv, N, d,
+                                             _DECODE_LAYOUTS[layout], float(softmax_scale or 0.0), causal, variant, dtype, arr, cnt,
+                                             _ptr(guard), int(bool(produce_guard and guard is not None)), _stream_ptr()))
+    return out, l, m
+
+
+def flash_attn_bwd_gqa(q, k, v, out, out_grad, l, m=None, causal=False, variant=_lib.FA_VARIANT_FA2, softmax_scale=None, layout="bnhd",
+                       guard="auto", opts=None, workspace=None, grads=None):
+    """Backward with grouped-query heads.  Returns (dq in q's shape, dk, dv in k's shape), fp32.  The dK/dV kernels store one dK and
+    one dV per query head into the workspace; one more launch adds every group's heads in ascending order (no atomics: the same bits
+    on every run).  ``workspace``: bwd_workspace_gqa(q, k, layout); ``grads``: (dq, dk, dv) buffers to write into."""
+    B, H, Hkv, N, d, dtype = _check_gqa(layout, q, k, v, out, out_grad)
+    lib, dev = _lib.core(), q.device
+    if workspace is not None:
+        if workspace.numel() * workspace.element_size() < lib.fa_mi355x_bwd_workspace_bytes_gqa(B, H, Hkv, N, d):
+            raise ValueError("workspace too small: size it with bwd_workspace_gqa(q, k, layout)")
+        if not workspace.is_contiguous() or workspace.get_device() != q.get_device() or workspace.data_ptr() % 256:
+            raise ValueError("workspace must be a contiguous, 256-byte aligned tensor on q's device")
+    _check_caller(q.get_device(), B * H * N, l, m, guard)
+    if grads is not None:
+        for g, like in zip(grads, (q, k, v)):
+            _check_buffer(g, q.get_device(), "each of grads", like.numel())
+    if workspace is None:
+        workspace = bwd_workspace_gqa(q, k, layout)
+    dq, dk, dv = grads or (torch.empty(t.shape, dtype=_F32, device=dev) for t in (q, k, v))
+    if isinstance(guard, str):   # "auto" on a call that only reads a guard: the separate pass over q and k
+        guard = _scale_guard_gqa(q, k) if _wants_guard(q, opts) else None
+    arr, cnt = _lib.opts_array(opts)
+    _lib.check(lib.fa_mi355x_bwd_gqa(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(out_grad), _ptr(dq), _ptr(dk), _ptr(dv), _ptr(l), _ptr(m),
+                                     _ptr(workspace), B, H, Hkv, N, d, _DECODE_LAYOUTS[layout], float(softmax_scale or 0.0),
+                                     int(bool(causal)), variant, dtype, STAGE_ALL, arr, cnt, _ptr(guard), _stream_ptr()))
+    return dq, dk, dv
+
+
+class _FlashAttnGqaFn(torch.autograd.Function):
+    """flash_attn2 with grouped-query heads under autograd: the forward saves q, the UNEXPANDED k and v, o, l and the scale guard it
+    filled; the backward returns k.grad and v.grad in k's shape.  Gradients are cast to the input dtype."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, causal, softmax_scale, layout):
+        _check_gqa(layout, q, k, v)
+        guard = new_guard(q) if softmax_scale is None else None   # (as _FlashAttnFn: a caller's scale makes the folded factor 1)
+        o, l, _ = flash_attn_fwd_gqa(q, k, v, causal, _lib.FA_VARIANT_FA2, softmax_scale, layout, guard, produce_guard=True)
+        ctx.save_for_backward(q, k, v, o, l, guard)
+        ctx.causal, ctx.softmax_scale, ctx.layout = causal, softmax_scale, layout
+        return o
+
+    @staticmethod
+    def backward(ctx, out_grad):
+        q, k, v, o, l, guard = ctx.saved_tensors
+        dq, dk, dv = flash_attn_bwd_gqa(q, k, v, o, out_grad.to(q.dtype).contiguous(), l, None, ctx.causal, _lib.FA_VARIANT_FA2,
+                                        ctx.softmax_scale, ctx.layout, guard)
+        return dq.to(q.dtype), dk.to(q.dtype), dv.to(q.dtype), None, None, None
+
+
+def flash_attn_gqa(q, k, v, causal=False, softmax_scale=None, layout="bnhd"):
+    """Attention with grouped-query heads under autograd (FA-2): out fp32 in q's shape; q.grad in q's shape and dtype, k.grad and
+    v.grad in k's."""
+    return _FlashAttnGqaFn.apply(q, k, v, bool(causal), softmax_scale, layout)
 
 
 def _decode_dims(q, k_cache, layout):

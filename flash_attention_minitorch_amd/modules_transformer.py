@@ -41,18 +41,21 @@ def _expand_kv(t, n_head):
 
 def multi_head_attention(x, wq, wk, wv, wo, n_head: int, causal: bool = True, fused_layout: bool = True, fold_scale: bool = False):
     """MultiHeadAttention.forward (modules_transfomer.py:141-157).  x: (B, N, E); wq, wo: (E, E); wk, wv: (E, E), or (E, Hkv * d) for
-    grouped-query heads (Hkv divides n_head, d = E // n_head; query head h reads kv head h // (n_head // Hkv)): k and v are then
-    expanded to n_head heads in front of the operator -- the function the generation path below is tested against, not a fused GQA
-    training path.  Bias-free, as the reference's ``Linear(..., bias=False)`` projections (:40-52).  ``fused_layout=False``
-    reproduces the reference's four permute + contiguous copies (for comparison); both give the same values.
+    grouped-query heads (Hkv divides n_head, d = E // n_head; query head h reads kv head h // (n_head // Hkv)).  With ``fused_layout``
+    the kernels read the Hkv heads of k and v in place, forward and backward (device_ops.flash_attn_gqa: no expanded copy, and the
+    group's dK / dV are added by the library's ordered group sum); ``fused_layout=False`` expands k and v to n_head heads in front of
+    the operator and reproduces the reference's four permute + contiguous copies (for comparison); both give the same values.
+    Bias-free, as the reference's ``Linear(..., bias=False)`` projections (:40-52).
     ``fold_scale`` (with ``fused_layout``): log2(e)/sqrt(d) is folded into the query projection's weights and the operator is called
     with softmax_scale = ln 2 -- the same function of x, but the bf16 MFMA-slot kernels' folded scale is then exactly 1: no extra
     operand rounding whatever the magnitude of the activations (DESIGN.md section 3 "Scaling")."""
     B, N, E = x.shape
     if fused_layout:
         q, k, v = _project(x, wq * (LOG2E / (E // n_head) ** 0.5) if fold_scale else wq, wk, wv, n_head)
-        k, v = _expand_kv(k, n_head), _expand_kv(v, n_head)
-        o = _attention(q, k, v, causal, _lib.FA_LAYOUT_BNHD, LN2 if fold_scale else None)   # (B, N, H, d) fp32: already merged
+        if k.shape[2] == n_head:
+            o = _attention(q, k, v, causal, _lib.FA_LAYOUT_BNHD, LN2 if fold_scale else None)   # (B, N, H, d) fp32: already merged
+        else:   # grouped-query heads: k and v stay (B, N, Hkv, d)
+            o = device_ops.flash_attn_gqa(q, k, v, causal, LN2 if fold_scale else None, "bnhd")
         merged = o.reshape(B * N, E)
     else:
         q, k, v = _project(x, wq, wk, wv, n_head)
@@ -125,9 +128,9 @@ def _check_kv_heads(k, cache):
 
 def attention_stack_prefill(x, layers, n_head: int, cache: KVCache):
     """attention_stack(x, layers, n_head, causal=True) over a prompt x (B, P, E) that also (re)fills ``cache`` with every layer's k and
-    v of the P tokens (lengths = P).  A grouped-query stack (wk, wv of shape (E, Hkv * d)) stores its Hkv heads; for the prompt's own
-    attention k and v are expanded to n_head heads (one copy each per layer) in front of the fused causal forward.  Returns the
-    stack's output (B, P, E)."""
+    v of the P tokens (lengths = P).  A grouped-query stack (wk, wv of shape (E, Hkv * d)) stores its Hkv heads, and the prompt's own
+    attention reads those cache-shaped k and v in place (device_ops.flash_attn_fwd_gqa: no expanded copy).  Returns the stack's
+    output (B, P, E)."""
     B, P, E = x.shape
     if P > cache.capacity:
         raise ValueError(f"prompt of {P} tokens exceeds the cache capacity {cache.capacity}")
@@ -138,11 +141,12 @@ def attention_stack_prefill(x, layers, n_head: int, cache: KVCache):
         kp, vp = cache._pad(k), cache._pad(v)
         cache.k[li][:, :P] = kp
         cache.v[li][:, :P] = vp
-        ke, ve = _expand_kv(kp, n_head), _expand_kv(vp, n_head)
+        # (a grouped-query stack: the kernels read the Hkv heads in place)
+        fwd = device_ops.flash_attn_fwd_bnhd if cache.n_kv_head == n_head else device_ops.flash_attn_fwd_gqa
         if cache.dp == d:
-            o, _, _ = device_ops.flash_attn_fwd_bnhd(q, ke, ve, True, _lib.FA_VARIANT_FA2)
+            o, _, _ = fwd(q, kp, vp, True, _lib.FA_VARIANT_FA2)
         else:   # zero columns add nothing to the scores; the scale keeps the caller's d
-            o, _, _ = device_ops.flash_attn_fwd_bnhd(cache._pad(q), ke, ve, True, _lib.FA_VARIANT_FA2, softmax_scale=d ** -0.5)
+            o, _, _ = fwd(cache._pad(q), kp, vp, True, _lib.FA_VARIANT_FA2, softmax_scale=d ** -0.5)
             o = o[..., :d]
         x = x + (o.reshape(B * P, E).to(x.dtype) @ wo).view(B, P, E)
     cache.lengths.fill_(P)

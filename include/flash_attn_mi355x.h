@@ -198,6 +198,39 @@ int fa_mi355x_bwd_guarded(const void* q, const void* k, const void* v, const flo
                           int layout, float softmax_scale, int causal, int variant, int dtype, int stages, const int* opts,
                           int nopts, const void* guard, void* stream);
 
+/* ---- Grouped-query heads (GQA / MQA) ----
+ * H = G * Hkv query heads share Hkv key/value heads: query head h reads kv head h / G (Hkv = 1: multi-query), the convention of
+ * include/flash_attn_mi355x_decode.h.  The kernels read K and V from their Hkv heads in place (no expanded copy):
+ *   q, out, out_grad, q_grad   [B][H][N][d]   (FA_LAYOUT_BHND)  or  [B][N][H][d]    (FA_LAYOUT_BNHD)
+ *   k, v, k_grad, v_grad       [B][Hkv][N][d]                   or  [B][N][Hkv][d]
+ *   l, m                       [B][H][N]
+ * Everything else as fa_mi355x_*_guarded (softmax_scale = 0: sqrt(1/d); opts, guard, produce_guard, stages); d in {32, 64, 128}.
+ * Hkv <= 0 or H not a multiple of Hkv: FA_ERR_BAD_ARG.  Hkv == H IS the _guarded call: the same kernels, the same bits, no scratch.
+ * Backward, Hkv < H: the dK/dV kernels store one dK and one dV per QUERY head into two fp32 scratch tensors of q's shape inside
+ * the workspace, and one more launch (group_sum_kernel) adds the G heads of every group in ascending order into k_grad / v_grad:
+ * no atomics, the same bits on every run.  The fp32 d = 64 one-pass backward (which adds dK, dV with atomics) is not selected for a
+ * grouped call: it runs what opts[4] = 4 selects; nor are the several-heads-per-workgroup builds of the d = 64 slot kernels: it runs
+ * what opts[5] = 1 selects.  Otherwise a grouped call selects what the ungrouped call of the same B*H, N, d, dtype, causal flag and
+ * options selects.  No key mask / dropout form.
+ *   fa_mi355x_bwd_workspace_bytes_gqa   the three row-constant vectors of fa_mi355x_bwd_workspace_bytes(B*H, N, d) and, when
+ *                                       Hkv < H, 2 * B*H*N*d floats of scratch behind them, starting on a 256-byte boundary
+ *                                       (the workspace itself must be 256-byte aligned: FA_ERR_BAD_ARG otherwise).  0 for a bad shape.
+ *   fa_mi355x_scale_guard_gqa           fa_mi355x_scale_guard with separate row counts: q has B*N*H rows, k has B*N*Hkv.
+ *   fa_mi355x_plan_gqa                  fa_mi355x_plan(B*H, ...) for a grouped call: the same text, plus "group_sum_kernel" behind
+ *                                       the dK/dV stage when Hkv < H and `stages` asks for that stage. */
+size_t fa_mi355x_bwd_workspace_bytes_gqa(int B, int H, int Hkv, int N, int d);
+int fa_mi355x_scale_guard_gqa(const void* q, const void* k, long q_rows, long k_rows, int row_elems, int dtype, void* guard,
+                              void* stream);
+int fa_mi355x_fwd_gqa(const void* q, const void* k, const void* v, float* out, float* l, float* m, int B, int H, int Hkv, int N, int d,
+                      int layout, float softmax_scale, int causal, int variant, int dtype, const int* opts, int nopts, void* guard,
+                      int produce_guard, void* stream);
+int fa_mi355x_bwd_gqa(const void* q, const void* k, const void* v, const float* out, const void* out_grad, float* q_grad,
+                      float* k_grad, float* v_grad, const float* l, const float* m, void* workspace, int B, int H, int Hkv, int N,
+                      int d, int layout, float softmax_scale, int causal, int variant, int dtype, int stages, const int* opts,
+                      int nopts, const void* guard, void* stream);
+int fa_mi355x_plan_gqa(int B, int H, int Hkv, int N, int d, int causal, int variant, int dtype, int stages, const int* opts,
+                       int nopts, char* out, size_t n);
+
 /* The same two operations with the caller's softmax scale instead of sqrt(1/d): P = softmax_k(softmax_scale * q.k).  The reference's
  * operator has no such argument (tau = sqrt(1/d) is fixed, src/flash_attn_fw.cu:37); it is here for callers that fold the scale into
  * their query projection, the usual arrangement in fused-attention stacks: with q' = (log2(e)/sqrt(d)) * q formed in fp32 BEFORE the
