@@ -117,6 +117,11 @@ DECODE_ABI = {
     "fa_mi355x_fwd_decode_gqa": (_i, [_vp] * 7 + [_i] * 7 + [_f, _i, _i, _vp]),
     "fa_mi355x_decode_append": (_i, [_vp] * 5 + [_i] * 8 + [_vp]),
     "fa_mi355x_fwd_decode_append": (_i, [_vp] * 9 + [_i] * 8 + [_f, _i, _i, _vp]),
+    "fa_mi355x_extend_splits": (_i, [_i] * 7),
+    "fa_mi355x_extend_workspace_bytes": (_sz, [_i] * 6),
+    "fa_mi355x_fwd_extend": (_i, [_vp] * 7 + [_i] * 7 + [_f, _i, _i, _vp]),
+    "fa_mi355x_extend_append": (_i, [_vp] * 5 + [_i] * 8 + [_vp]),
+    "fa_mi355x_fwd_extend_append": (_i, [_vp] * 9 + [_i] * 8 + [_f, _i, _i, _vp]),
     "fa_mi355x_decode_last_error": (_s, []),
 }
 

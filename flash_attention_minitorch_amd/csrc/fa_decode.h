@@ -17,8 +17,10 @@
 // Combine kernel: one workgroup per (batch*head, query row) reduces the partials of its row in a fixed order (no atomics: bitwise
 // repeatable).
 //
+// Extend kernel (extend_split_kernel, behind the split kernel): the same call for ANY Nq (a long input after a cached prefix, chunked
+// prefill), a workgroup = one (batch*kv head, key chunk, 128-row block) whose waves each own 32 rows and share the staged tiles.
 // Append kernel (decode_append_kernel, at the end of this file): writes the Nq new tokens' k and v into the caches in front of the
-// two kernels above, at the rows where the split kernel's causal mask places the queries.
+// kernels above, at the rows where the split kernel's causal mask places the queries.
 //
 // Bounds: every K / V load goes through a buffer resource of its (batch, kv head) sized to the valid rows (len_b clamped to
 // [0, Ncap]), with the row offset in the per-lane voffset, so rows at or past len_b read as zero in hardware: whatever they hold (NaN
@@ -252,6 +254,163 @@ __global__ void __launch_bounds__(256) decode_split_kernel(DecodeArgs a) {
         *reinterpret_cast<f32x4*>(prow + 32 * dt + 8 * g + 4 * h) = val;
       }
     if (h == 0) *reinterpret_cast<f32x2*>(a.part_ml + 2 * pr) = f32x2{m_all, l_tot};
+  }
+}
+
+// ---- extend: any number of new queries against the cache ---------------------------------------------------------------------------
+// The split kernel's semantics for any Nq >= 1 with the roles of its waves swapped: a workgroup = one (batch*kv head, key chunk,
+// 128-ROW block), wave w owns rows 128 * qb + 32 * w .. + 31 (its own Q fragments, acc_o, m_run, l_run), the four waves stage the
+// 128-key super tiles together as above, and every wave walks all four 32-key sub-tiles of a staged tile for its own rows.  A staged
+// tile serves 128 rows instead of 32 and there is no cross-wave merge: each wave writes its 32 rows, final (one split) or as a
+// partial in the layout decode_combine_kernel reads.  DecodeArgs as above with nqb = ceil(G * Nq / 128).
+// Causal: the workgroup's key loop ends at the block's highest position + 1 (workgroup-uniform: every wave reaches every barrier, and
+// no tile is loaded that no row of the block can see); inside it a wave skips the sub-tiles wholly above its own pos_hi and masks
+// only those that straddle pos_lo .. pos_hi.  A wave whose rows are all >= G * Nq stages, meets the barriers and stores nothing.
+constexpr int EXT_BLOCK = 128;   // rows per workgroup: 32 per wave
+
+template <typename T, int D>
+__global__ void __launch_bounds__(256) extend_split_kernel(DecodeArgs a) {
+  using A = Atom<T>;
+  typedef typename A::frag frag;
+  constexpr int KC = D / 16, DT = D / 32;
+  constexpr int TB = A::template tile_bytes<D>(DEC_ROWS);
+  __shared__ __attribute__((aligned(16))) char smem_raw[2 * TB];
+  lds_char* tk = (lds_char*)smem_raw;
+  lds_char* tv = tk + TB;
+
+  // workgroup -> (item, row block) as in decode_split_kernel: the row blocks of one item share an XCD's L2
+  const int id = blockIdx.x, slot = id >> 3;
+  const int qb = slot % a.nqb, item = (slot / a.nqb) * 8 + (id & 7);
+  if (item >= a.items) return;
+  const int bh = item / a.nsplit, split = item - bh * a.nsplit;
+  const int b = bh / a.Hkv, hkv = bh - b * a.Hkv;
+  const int len = __builtin_amdgcn_readfirstlane(clamp_len(a, b));
+  const int c0 = split * a.chunk, c1 = min(c0 + a.chunk, len);
+
+  const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int rows = a.G * a.Nq;
+  const int q0 = qb * EXT_BLOCK + 32 * w, rho = q0 + r, qi = row_query(a, rho), hd = hkv * a.G + (rho - qi * a.G);
+  const bool live = rho < rows;
+  const bool wave_live = q0 < rows;   // (wave-uniform)
+  const float c = a.tau * LOG2E;
+  // causal: the last key any row of the block sees is the position of its last row (of its last REAL row: rows >= G * Nq see nothing)
+  const int blk_hi = len - a.Nq + row_query(a, min(qb * EXT_BLOCK + EXT_BLOCK, rows) - 1);
+  const int cend = a.causal ? min(c1, blk_hi + 1) : c1;
+
+  f32x16 acc_o[DT];
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt) acc_o[dt] = zero16();
+  float m_run = -INFINITY, l_run = 0.f;
+
+  if (c0 < cend) {   // (a chunk past len_b, or past every position of the block, loads nothing and leaves m = -inf, l = 0)
+    const size_t kvoff = (size_t)b * a.kv_bstride + (size_t)hkv * a.kv_hstride;
+    const uint32_t esz = sizeof(T);
+    const uint32_t q_bytes = (uint32_t)a.q_bstride * esz;
+    const rsrc_t qrs = make_rsrc(reinterpret_cast<const T*>(a.q) + (size_t)b * a.q_bstride, q_bytes);
+    const uint32_t kv_bytes = ((uint32_t)(len - 1) * a.kv_ld + D) * esz;
+    const rsrc_t krs = make_rsrc(reinterpret_cast<const T*>(a.k) + kvoff, kv_bytes);
+    const rsrc_t vrs = make_rsrc(reinterpret_cast<const T*>(a.v) + kvoff, kv_bytes);
+
+    frag qf[KC];
+    const int qoff = live ? (hd * (int)a.q_hstride + qi * a.q_ld + 8 * h) * (int)esz : (int)q_bytes;
+#pragma unroll
+    for (int kc = 0; kc < KC; ++kc) qf[kc] = load_frag_buf<T>(qrs, qoff + 16 * kc * (int)esz);
+
+    const LaneAddr ra = A::template row_addr<D>(lane);
+    const LaneAddr ta = A::template tr_addr<D>(lane);
+    TileStager<T, D, DEC_ROWS, 256> sk, sv;
+    sk.init(tid, a.kv_ld);
+    sv.init(tid, a.kv_ld);
+    // the wave's rows span the positions pos_lo .. pos_hi (wave-uniform; rows past G * Nq may push pos_hi up, which only keeps a
+    // sub-tile that masks to nothing for the real rows' lanes)
+    const int qpos = len - a.Nq + qi;
+    const int pos_lo = len - a.Nq + row_query(a, q0), pos_hi = len - a.Nq + row_query(a, q0 + 31);
+    load_rows(sk, krs, c0);
+    load_rows(sv, vrs, c0);
+    for (int t0 = c0; t0 < cend; t0 += DEC_ROWS) {
+      __syncthreads();   // (the previous super tile's reads are done)
+      sk.store(tk);
+      sv.store(tv);
+      if (t0 + DEC_ROWS < cend) {
+        load_rows(sk, krs, t0 + DEC_ROWS);
+        load_rows(sv, vrs, t0 + DEC_ROWS);
+      }
+      __syncthreads();
+      if (!wave_live) continue;
+#pragma unroll
+      for (int st = 0; st < DEC_ROWS / 32; ++st) {
+        const int kbase = t0 + 32 * st;
+        if (kbase >= cend || (a.causal && kbase > pos_hi)) break;   // wave-uniform: no admissible key here or further on
+        f32x16 s = zero16();
+#pragma unroll
+        for (int kc = 0; kc < KC; ++kc) A::mma(s, A::template row_frag<D>(tk, ra, 32 * st, kc), qf[kc]);
+        if (kbase + 32 > c1 || (a.causal && kbase + 31 > pos_lo)) {   // wave-uniform
+#pragma unroll
+          for (int i = 0; i < 16; ++i) {
+            const int key = kbase + acc_row(i, h);
+            if (key >= c1 || (a.causal && key > qpos)) s[i] = -INFINITY;
+          }
+        }
+        float mx = s[0];
+#pragma unroll
+        for (int i = 1; i < 16; ++i) mx = fmaxf(mx, s[i]);
+        const float m_new = fmaxf(m_run, xhalf_max(mx));
+        const float nm = (m_new == -INFINITY) ? 0.f : -m_new * c;   // (every key so far masked: any finite reference, P = 0)
+        const float alpha = __builtin_amdgcn_exp2f(__builtin_fmaf(m_run, c, nm));
+        float rs = 0.f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          s[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[i], c, nm));
+          rs += s[i];
+        }
+        if (__any(alpha != 1.0f)) {
+#pragma unroll
+          for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc_o[dt][i] *= alpha;
+        }
+        l_run = l_run * alpha + rs;
+        m_run = m_new;
+        // bf16: P at 16 significant bits (pack + pack_lo), as in decode_split_kernel
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) {
+          const frag p_hi = A::pack(s, s2);
+#pragma unroll
+          for (int dt = 0; dt < DT; ++dt) {
+            const frag vt = A::template tr_frag<D>(tv, ta, 32 * st + 16 * s2, dt);
+            A::mma(acc_o[dt], vt, p_hi);
+            if constexpr (A::SPLITS) A::mma(acc_o[dt], vt, A::pack_lo(s, s2, p_hi));
+          }
+        }
+      }
+    }
+  }
+  const float l_tot = xhalf_sum(l_run);
+  if (!live) return;   // (no barrier follows)
+  const size_t bhq = (size_t)b * a.H + hd;
+  if (a.nsplit == 1) {   // final: out = O / l, lse = m * tau + ln l; a row without an admissible key: out = 0, lse = -inf
+    const float inv = (l_tot > 0.f) ? 1.0f / l_tot : 0.f;
+    float* orow = a.out + (size_t)b * a.q_bstride + (size_t)hd * a.q_hstride + (size_t)qi * a.q_ld;
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        f32x4 val = {acc_o[dt][4 * g] * inv, acc_o[dt][4 * g + 1] * inv, acc_o[dt][4 * g + 2] * inv, acc_o[dt][4 * g + 3] * inv};
+        *reinterpret_cast<f32x4*>(orow + 32 * dt + 8 * g + 4 * h) = val;
+      }
+    if (h == 0 && a.lse) a.lse[bhq * a.Nq + qi] = (l_tot > 0.f) ? m_run * a.tau + __logf(l_tot) : -INFINITY;
+  } else {
+    const size_t pr = (bhq * a.nsplit + split) * a.Nq + qi;
+    float* prow = a.part_o + pr * D;
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        f32x4 val = {acc_o[dt][4 * g], acc_o[dt][4 * g + 1], acc_o[dt][4 * g + 2], acc_o[dt][4 * g + 3]};
+        *reinterpret_cast<f32x4*>(prow + 32 * dt + 8 * g + 4 * h) = val;
+      }
+    if (h == 0) *reinterpret_cast<f32x2*>(a.part_ml + 2 * pr) = f32x2{m_run, l_tot};
   }
 }
 

@@ -1,5 +1,5 @@
-// C ABI of the MI355X KV-cache decode library (declared in include/flash_attn_mi355x_decode.h): argument checks, the split policy
-// and the launches of the kernels of fa_decode.h.
+// C ABI of the MI355X KV-cache decode library (declared in include/flash_attn_mi355x_decode.h): argument checks, the split policies
+// (decode: 32-row blocks, at most 128 queries; extend: 128-row blocks, any number) and the launches of the kernels of fa_decode.h.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -51,6 +51,52 @@ size_t workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int d) {
   return ns == 1 ? 0 : (size_t)B * H * ns * Nq * (size_t)(d + 2) * sizeof(float);
 }
 
+// Extend policy: the same with 128-row blocks (a workgroup of extend_split_kernel owns 128 rows): groups = B * Hkv * ceil(G*Nq / 128),
+// and TWO workgroups per CU as the target: a workgroup here lives for a long key loop, so a second round of workgroups buys nothing,
+// while every split costs a partial per row and the combine launch over B*H*Nq rows (measured: profiles/extend_bench.txt).
+constexpr int EXT_WAVES = 2;
+int ext_row_blocks(int H, int Hkv, int Nq) { return (int)(((long)(H / Hkv) * Nq + fa::EXT_BLOCK - 1) / fa::EXT_BLOCK); }
+
+int ext_chunk_keys(int B, int H, int Hkv, int Nq, int Ncap) {
+  const long groups = (long)B * Hkv * ext_row_blocks(H, Hkv, Nq);
+  const long want = std::max(1L, (DEC_CUS * EXT_WAVES + groups - 1) / groups);
+  const long per = (Ncap + want - 1) / want;
+  return (int)std::max((long)DEC_MIN_CHUNK, (per + DEC_MIN_CHUNK - 1) / DEC_MIN_CHUNK * DEC_MIN_CHUNK);
+}
+
+int ext_splits(int B, int H, int Hkv, int Nq, int Ncap) {
+  const int ch = ext_chunk_keys(B, H, Hkv, Nq, Ncap);
+  return (int)(((long)Ncap + ch - 1) / ch);
+}
+
+size_t ext_workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int d) {
+  const int ns = ext_splits(B, H, Hkv, Nq, Ncap);
+  return ns == 1 ? 0 : (size_t)B * H * ns * Nq * (size_t)(d + 2) * sizeof(float);
+}
+
+// workgroups of the split launch: the items rounded up to 8, times the row blocks (the kernels' workgroup -> (item, row block) map)
+long split_grid(long items, int nqb) { return (items + 7) / 8 * 8 * nqb; }
+
+template <typename T, int D> int launch_extend(fa::DecodeArgs a, int BH, hipStream_t st) {
+  hipLaunchKernelGGL((fa::extend_split_kernel<T, D>), dim3((unsigned)split_grid(a.items, a.nqb)), dim3(256), 0, st, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return set_err(FA_ERR_HIP, "extend_split_kernel launch", e);
+  if (a.nsplit > 1) {
+    hipLaunchKernelGGL((fa::decode_combine_kernel<D>), dim3((unsigned)((long)BH * a.Nq)), dim3(256), 0, st, a);
+    e = hipGetLastError();
+    if (e != hipSuccess) return set_err(FA_ERR_HIP, "decode_combine_kernel launch", e);
+  }
+  return FA_OK;
+}
+
+template <typename T> int launch_extend_d(const fa::DecodeArgs& a, int BH, int d, hipStream_t st) {
+  switch (d) {
+    case 32: return launch_extend<T, 32>(a, BH, st);
+    case 64: return launch_extend<T, 64>(a, BH, st);
+    default: return launch_extend<T, 128>(a, BH, st);
+  }
+}
+
 template <typename T, int D> int launch(fa::DecodeArgs a, int BH, hipStream_t st) {
   const int grid = ((a.items + 7) / 8) * 8 * a.nqb;
   if (a.G > 1)
@@ -75,9 +121,9 @@ template <typename T> int launch_d(const fa::DecodeArgs& a, int BH, int d, hipSt
   }
 }
 
-// The argument checks of fa_mi355x_fwd_decode_gqa: FA_OK, or the error with its message set.
+// The argument checks of fa_mi355x_fwd_decode_gqa, or (extend) of fa_mi355x_fwd_extend: FA_OK, or the error with its message set.
 int check_decode(const void* q, const void* k_cache, const void* v_cache, const float* out, const void* workspace, int B, int H, int Hkv,
-                 int Nq, int Ncap, int d, int layout, float softmax_scale, int dtype) {
+                 int Nq, int Ncap, int d, int layout, float softmax_scale, int dtype, bool extend = false) {
   g_err[0] = 0;
   if (B <= 0 || H <= 0 || Nq <= 0 || Ncap <= 0 || d <= 0) return set_err(FA_ERR_BAD_ARG, "B, H, Nq, Ncap and d must be positive");
   if (Hkv <= 0) return set_err(FA_ERR_BAD_ARG, "Hkv must be positive");
@@ -85,7 +131,7 @@ int check_decode(const void* q, const void* k_cache, const void* v_cache, const 
     snprintf(g_err, sizeof(g_err), "H = %d query heads must be a multiple of Hkv = %d cache heads", H, Hkv);
     return FA_ERR_BAD_ARG;
   }
-  if (Nq > FA_DECODE_MAX_NQ)
+  if (!extend && Nq > FA_DECODE_MAX_NQ)
     return set_err(FA_ERR_BAD_ARG, "Nq > 128 is prefill: use fa_mi355x_fwd_layout or fa_mi355x_fwd_scaled (the forward entry points)");
   if (dtype != FA_DTYPE_F32 && dtype != FA_DTYPE_BF16) return set_err(FA_ERR_BAD_ARG, "unknown dtype");
   if (layout != FA_LAYOUT_BHND && layout != FA_LAYOUT_BNHD) return set_err(FA_ERR_BAD_ARG, "unknown layout");
@@ -94,20 +140,32 @@ int check_decode(const void* q, const void* k_cache, const void* v_cache, const 
     return set_err(FA_ERR_UNSUPPORTED_D, "decode supports d in {32, 64, 128}: pad the cache with zero columns for other d <= 128");
   if (softmax_scale != 0.f && (!(softmax_scale > 0.f) || !std::isfinite(softmax_scale)))
     return set_err(FA_ERR_BAD_ARG, "softmax_scale must be positive and finite (0: 1/sqrt(d))");
+  // (row_query is exact for rows below 2^25)
+  if (extend && (long)(H / Hkv) * Nq >= (1L << 25)) return set_err(FA_ERR_BAD_ARG, "G * Nq rows per kv head must stay under 2^25");
   const long esz = dtype == FA_DTYPE_BF16 ? 2 : 4;
   // (a buffer load's row offset is a 32-bit byte count: one batch element, plus a super tile of rows past its end, stays under 2 GiB;
   // q's (head, query) offset within its batch element likewise)
   if (((long)Ncap + fa::DEC_ROWS) * Hkv * d * esz >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "one batch element of the cache must stay under 2 GiB");
   if ((long)Nq * H * d * esz >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "one batch element of q must stay under 2 GiB");
+  if (extend) {
+    // (the workgroup counts of the split and the combine launch are unsigned ints, the items an int)
+    const int ens = ext_splits(B, H, Hkv, Nq, Ncap);
+    if (split_grid((long)B * Hkv * ens, ext_row_blocks(H, Hkv, Nq)) >= (1L << 32) || (long)B * Hkv * ens >= (1L << 31) ||
+        (long)B * H * Nq >= (1L << 32))
+      return set_err(FA_ERR_BAD_ARG, "too many workgroups for one launch: B * Hkv * splits * row blocks and B * H * Nq must fit an unsigned int");
+    if (ens > 1 && !workspace) return set_err(FA_ERR_BAD_ARG, "null workspace: this call needs fa_mi355x_extend_workspace_bytes() bytes");
+    return FA_OK;
+  }
   const int ns = splits(B, H, Hkv, Nq, Ncap);
   if (ns > 1 && !workspace) return set_err(FA_ERR_BAD_ARG, "null workspace: this call needs fa_mi355x_decode_workspace_bytes() bytes");
   return FA_OK;
 }
 
-// The split (and combine) launches of a checked call.
+// The split (and combine) launches of a checked call: the decode kernels, or (extend) the extend kernels under their own policy.
 int run_decode(const void* q, const void* k_cache, const void* v_cache, float* out, float* lse, const int* cache_seqlens, void* workspace,
-               int B, int H, int Hkv, int Nq, int Ncap, int d, int layout, float softmax_scale, int causal, int dtype, void* stream) {
-  const int ns = splits(B, H, Hkv, Nq, Ncap);
+               int B, int H, int Hkv, int Nq, int Ncap, int d, int layout, float softmax_scale, int causal, int dtype, void* stream,
+               bool extend = false) {
+  const int ns = extend ? ext_splits(B, H, Hkv, Nq, Ncap) : splits(B, H, Hkv, Nq, Ncap);
   fa::DecodeArgs a;
   a.q = q;
   a.k = k_cache;
@@ -124,8 +182,8 @@ int run_decode(const void* q, const void* k_cache, const void* v_cache, float* o
   a.Nq = Nq;
   a.Ncap = Ncap;
   a.nsplit = ns;
-  a.chunk = chunk_keys(B, H, Hkv, Nq, Ncap);
-  a.nqb = row_blocks(H, Hkv, Nq);
+  a.chunk = extend ? ext_chunk_keys(B, H, Hkv, Nq, Ncap) : chunk_keys(B, H, Hkv, Nq, Ncap);
+  a.nqb = extend ? ext_row_blocks(H, Hkv, Nq) : row_blocks(H, Hkv, Nq);
   a.items = B * Hkv * ns;
   const bool bnhd = layout == FA_LAYOUT_BNHD;
   a.q_ld = bnhd ? H * d : d;
@@ -137,15 +195,16 @@ int run_decode(const void* q, const void* k_cache, const void* v_cache, float* o
   a.causal = causal ? 1 : 0;
   a.tau = softmax_scale > 0.f ? softmax_scale : sqrtf(1.0f / (float)d);
   hipStream_t st = static_cast<hipStream_t>(stream);
+  if (extend) return dtype == FA_DTYPE_BF16 ? launch_extend_d<fa::bf16_t>(a, B * H, d, st) : launch_extend_d<float>(a, B * H, d, st);
   return dtype == FA_DTYPE_BF16 ? launch_d<fa::bf16_t>(a, B * H, d, st) : launch_d<float>(a, B * H, d, st);
 }
 
 // The argument checks of the append: FA_OK, or the error with its message set.
 int check_append(const void* k_new, const void* v_new, const void* k_cache, const void* v_cache, int B, int Hkv, int Nq, int Ncap,
-                 int d_new, int d, int layout, int dtype) {
+                 int d_new, int d, int layout, int dtype, bool extend = false) {
   g_err[0] = 0;
   if (B <= 0 || Hkv <= 0 || Nq <= 0 || Ncap <= 0 || d <= 0) return set_err(FA_ERR_BAD_ARG, "B, Hkv, Nq, Ncap and d must be positive");
-  if (Nq > FA_DECODE_MAX_NQ) return set_err(FA_ERR_BAD_ARG, "Nq > 128 new tokens per call: fill the cache of a prompt directly");
+  if (!extend && Nq > FA_DECODE_MAX_NQ) return set_err(FA_ERR_BAD_ARG, "Nq > 128 new tokens per call: fill the cache of a prompt directly");
   if (dtype != FA_DTYPE_F32 && dtype != FA_DTYPE_BF16) return set_err(FA_ERR_BAD_ARG, "unknown dtype");
   if (layout != FA_LAYOUT_BHND && layout != FA_LAYOUT_BNHD) return set_err(FA_ERR_BAD_ARG, "unknown layout");
   if (!k_new || !v_new || !k_cache || !v_cache) return set_err(FA_ERR_BAD_ARG, "null pointer argument (k_new, v_new and the caches)");
@@ -238,6 +297,46 @@ int fa_mi355x_fwd_decode_append(const void* q, const void* k_new, const void* v_
   if (rc != FA_OK) return rc;
   return run_decode(q, k_cache, v_cache, out, lse, cache_seqlens, workspace, B, H, Hkv, Nq, Ncap, d, layout, softmax_scale, causal, dtype,
                     stream);
+}
+
+// The extend entry points: any Nq, the extend kernels and their policy; the append is the decode library's own.
+size_t fa_mi355x_extend_workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int d) {
+  if (!sizes_ok(B, H, Hkv, Nq, Ncap, d)) return 0;
+  return ext_workspace_bytes(B, H, Hkv, Nq, Ncap, d);
+}
+
+int fa_mi355x_extend_splits(int B, int H, int Hkv, int Nq, int Ncap, int d, int dtype) {
+  (void)dtype;
+  if (!sizes_ok(B, H, Hkv, Nq, Ncap, d)) return 0;
+  return ext_splits(B, H, Hkv, Nq, Ncap);
+}
+
+int fa_mi355x_fwd_extend(const void* q, const void* k_cache, const void* v_cache, float* out, float* lse, const int* cache_seqlens,
+                         void* workspace, int B, int H, int Hkv, int Nq, int Ncap, int d, int layout, float softmax_scale, int causal,
+                         int dtype, void* stream) {
+  const int rc = check_decode(q, k_cache, v_cache, out, workspace, B, H, Hkv, Nq, Ncap, d, layout, softmax_scale, dtype, true);
+  if (rc != FA_OK) return rc;
+  return run_decode(q, k_cache, v_cache, out, lse, cache_seqlens, workspace, B, H, Hkv, Nq, Ncap, d, layout, softmax_scale, causal, dtype,
+                    stream, true);
+}
+
+int fa_mi355x_extend_append(const void* k_new, const void* v_new, void* k_cache, void* v_cache, const int* cache_seqlens, int B, int Hkv,
+                            int Nq, int Ncap, int d_new, int d, int layout, int dtype, void* stream) {
+  const int rc = check_append(k_new, v_new, k_cache, v_cache, B, Hkv, Nq, Ncap, d_new, d, layout, dtype, true);
+  if (rc != FA_OK) return rc;
+  return run_append(k_new, v_new, k_cache, v_cache, cache_seqlens, B, Hkv, Nq, Ncap, d_new, d, layout, dtype, stream);
+}
+
+int fa_mi355x_fwd_extend_append(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
+                                const int* cache_seqlens, void* workspace, int B, int H, int Hkv, int Nq, int Ncap, int d_new, int d,
+                                int layout, float softmax_scale, int causal, int dtype, void* stream) {
+  int rc = check_decode(q, k_cache, v_cache, out, workspace, B, H, Hkv, Nq, Ncap, d, layout, softmax_scale, dtype, true);
+  if (rc == FA_OK) rc = check_append(k_new, v_new, k_cache, v_cache, B, Hkv, Nq, Ncap, d_new, d, layout, dtype, true);
+  if (rc != FA_OK) return rc;
+  rc = run_append(k_new, v_new, k_cache, v_cache, cache_seqlens, B, Hkv, Nq, Ncap, d_new, d, layout, dtype, stream);
+  if (rc != FA_OK) return rc;
+  return run_decode(q, k_cache, v_cache, out, lse, cache_seqlens, workspace, B, H, Hkv, Nq, Ncap, d, layout, softmax_scale, causal, dtype,
+                    stream, true);
 }
 
 // The ungrouped entry points: Hkv = H.

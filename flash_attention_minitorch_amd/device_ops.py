@@ -581,6 +581,17 @@ def decode_workspace(q, k_cache, layout="bnhd"):
     return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=q.device) if nbytes else None
 
 
+def _extend_workspace_bytes(B, H, Hkv, Nq, Ncap, dp):
+    return _lib.decode().fa_mi355x_extend_workspace_bytes(B, H, Hkv, Nq, Ncap, dp)
+
+
+def extend_workspace(q, k_cache, layout="bnhd"):
+    """decode_workspace for flash_attn_extend (fa_mi355x_extend_workspace_bytes: the extend call has a split policy of its own)."""
+    B, H, Hkv, Nq, Ncap, _, dp = _decode_dims(q, k_cache, layout)
+    nbytes = _extend_workspace_bytes(B, H, Hkv, Nq, Ncap, dp)
+    return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=q.device) if nbytes else None
+
+
 def _check_seqlens(cache_seqlens, B, device):
     if cache_seqlens is not None and (cache_seqlens.dtype != torch.int32 or tuple(cache_seqlens.shape) != (B,)
                                       or cache_seqlens.device != device or not cache_seqlens.is_contiguous()):
@@ -612,12 +623,8 @@ def _check_new(k_new, v_new, k_cache, layout, Nq=None):
     return n, d_new
 
 
-def decode_append(k_new, v_new, k_cache, v_cache, cache_seqlens=None, layout="bnhd"):
-    """Write the Nq <= 128 new tokens' k and v into the caches on the device (fa_mi355x_decode_append): k_new, v_new (B, Nq, Hkv,
-    d_new) for "bnhd" or (B, Hkv, Nq, d_new) for "bhnd", 1 <= d_new <= dp, into caches (B, Ncap, Hkv, dp) / (B, Hkv, Ncap, dp).
-    ``cache_seqlens`` COUNTS the new tokens, as flash_attn_decode reads it: token i goes to row clamp(len_b, 0, Ncap) - Nq + i when
-    that is >= 0 (None: the last Nq rows), with zeros in columns d_new .. dp-1; every other row keeps its contents.  k_new and v_new
-    must not alias the caches.  In place, no host synchronisation."""
+def _append(who, entry, k_new, v_new, k_cache, v_cache, cache_seqlens, layout):
+    """decode_append / extend_append: the checks, then the library's ``entry``."""
     if layout not in _DECODE_LAYOUTS:
         raise ValueError(f"layout must be one of {sorted(_DECODE_LAYOUTS)}")
     if k_cache.dim() != 4 or k_cache.shape != v_cache.shape:
@@ -632,24 +639,28 @@ def decode_append(k_new, v_new, k_cache, v_cache, cache_seqlens=None, layout="bn
     for t in (k_cache, v_cache):
         if t.device != k_cache.device or not t.is_contiguous():
             raise ValueError("k_cache and v_cache must be contiguous and live on one device")
-        _require_gpu(t, "decode_append")
-    _lib.decode_check(_lib.decode().fa_mi355x_decode_append(
+        _require_gpu(t, who)
+    _lib.decode_check(getattr(_lib.decode(), entry)(
         _ptr(k_new), _ptr(v_new), _ptr(k_cache), _ptr(v_cache), _ptr(cache_seqlens), B, Hkv, Nq, Ncap, d_new, dp,
         _DECODE_LAYOUTS[layout], dtype, _stream_ptr()))
 
 
-def flash_attn_decode(q, k_cache, v_cache, cache_seqlens=None, causal=True, softmax_scale=None, layout="bnhd", out=None, lse=None,
-                      workspace=None, k_new=None, v_new=None):
-    """Attention of Nq <= 128 new queries against a KV cache (fa_mi355x_fwd_decode / _gqa, include/flash_attn_mi355x_decode.h).
-    ``layout`` "bnhd": q (B, Nq, H, d), caches (B, Ncap, Hkv, dp); "bhnd": q (B, H, Nq, d), caches (B, Hkv, Ncap, dp).  Hkv is the
-    cache's own head count and must divide H: Hkv < H is a grouped-query (Hkv = 1: multi-query) cache, query head h reads cache head
-    h // (H // Hkv), and the group's heads share one pass over it (no expansion of the cache).  dp in {32, 64, 128};
-    a q with fewer columns (d < dp) is zero-padded to the cache's row length (the cache itself holds zero columns d .. dp-1) and the
-    default scale is then 1/sqrt(d).  ``cache_seqlens``: int32 (B,) on q's device, the valid cache rows per batch element counting the
-    new tokens (None: all Ncap); clamped to [0, Ncap] on the device, no host synchronisation.  ``causal``: the queries are the last Nq
-    positions.  ``k_new``, ``v_new`` (both or neither; shapes and placement as decode_append): the new tokens' k and v, written into
-    the caches on the device in front of the attention (fa_mi355x_fwd_decode_append: decode_append, then this call, one library call).
-    Returns (out fp32 in q's shape, lse fp32 (B, H, Nq)): rows with no admissible key give out = 0, lse = -inf."""
+def decode_append(k_new, v_new, k_cache, v_cache, cache_seqlens=None, layout="bnhd"):
+    """Write the Nq <= 128 new tokens' k and v into the caches on the device (fa_mi355x_decode_append): k_new, v_new (B, Nq, Hkv,
+    d_new) for "bnhd" or (B, Hkv, Nq, d_new) for "bhnd", 1 <= d_new <= dp, into caches (B, Ncap, Hkv, dp) / (B, Hkv, Ncap, dp).
+    ``cache_seqlens`` COUNTS the new tokens, as flash_attn_decode reads it: token i goes to row clamp(len_b, 0, Ncap) - Nq + i when
+    that is >= 0 (None: the last Nq rows), with zeros in columns d_new .. dp-1; every other row keeps its contents.  k_new and v_new
+    must not alias the caches.  In place, no host synchronisation."""
+    _append("decode_append", "fa_mi355x_decode_append", k_new, v_new, k_cache, v_cache, cache_seqlens, layout)
+
+
+def extend_append(k_new, v_new, k_cache, v_cache, cache_seqlens=None, layout="bnhd"):
+    """decode_append for any number of new tokens (fa_mi355x_extend_append: the same kernel, placement and checks, no bound on Nq)."""
+    _append("extend_append", "fa_mi355x_extend_append", k_new, v_new, k_cache, v_cache, cache_seqlens, layout)
+
+
+def _cache_attention(who, extend, q, k_cache, v_cache, cache_seqlens, causal, softmax_scale, layout, out, lse, workspace, k_new, v_new):
+    """flash_attn_decode / flash_attn_extend (``extend``): the checks, the head-dim padding, then the library's entry point."""
     if (k_new is None) != (v_new is None):
         raise ValueError("k_new and v_new go together: give both (fused append) or neither")
     if layout not in _DECODE_LAYOUTS:
@@ -666,7 +677,7 @@ def flash_attn_decode(q, k_cache, v_cache, cache_seqlens=None, causal=True, soft
     if k_new is not None:
         _, d_new = _check_new(k_new, v_new, k_cache, layout, Nq)
     for t in (q, k_cache, v_cache):
-        _require_gpu(t, "flash_attn_decode")
+        _require_gpu(t, who)
         if t.device != q.device:
             raise ValueError("q, k_cache and v_cache must live on one device")
         if not t.is_contiguous():
@@ -682,12 +693,20 @@ def flash_attn_decode(q, k_cache, v_cache, cache_seqlens=None, causal=True, soft
     elif tuple(lse.shape) != (B, H, Nq) or lse.dtype != torch.float32 or not lse.is_contiguous():
         raise ValueError("lse must be a contiguous float32 tensor of shape (B, H, Nq)")
     lib = _lib.decode()
+    new_ws, ws_bytes = (extend_workspace, _extend_workspace_bytes) if extend else (decode_workspace, _decode_workspace_bytes)
     if workspace is None:
-        workspace = decode_workspace(qp, k_cache, layout)
-    elif workspace.numel() * workspace.element_size() < _decode_workspace_bytes(B, H, Hkv, Nq, Ncap, dp):
-        raise ValueError("workspace too small: size it with decode_workspace()")
+        workspace = new_ws(qp, k_cache, layout)
+    elif workspace.numel() * workspace.element_size() < ws_bytes(B, H, Hkv, Nq, Ncap, dp):
+        raise ValueError(f"workspace too small: size it with {new_ws.__name__}()")
     tail = (_DECODE_LAYOUTS[layout], float(softmax_scale), int(bool(causal)), dtype, _stream_ptr())
-    if k_new is not None:
+    if extend:   # (one grouped form; always the extend kernels, whatever Nq)
+        if k_new is not None:
+            status = lib.fa_mi355x_fwd_extend_append(_ptr(qp), _ptr(k_new), _ptr(v_new), _ptr(k_cache), _ptr(v_cache), _ptr(outp),
+                                                     _ptr(lse), _ptr(cache_seqlens), _ptr(workspace), B, H, Hkv, Nq, Ncap, d_new, dp, *tail)
+        else:
+            status = lib.fa_mi355x_fwd_extend(_ptr(qp), _ptr(k_cache), _ptr(v_cache), _ptr(outp), _ptr(lse), _ptr(cache_seqlens),
+                                              _ptr(workspace), B, H, Hkv, Nq, Ncap, dp, *tail)
+    elif k_new is not None:
         status = lib.fa_mi355x_fwd_decode_append(_ptr(qp), _ptr(k_new), _ptr(v_new), _ptr(k_cache), _ptr(v_cache), _ptr(outp), _ptr(lse),
                                                  _ptr(cache_seqlens), _ptr(workspace), B, H, Hkv, Nq, Ncap, d_new, dp, *tail)
     else:
@@ -697,3 +716,32 @@ def flash_attn_decode(q, k_cache, v_cache, cache_seqlens=None, causal=True, soft
                      Nq, Ncap, dp, *tail)
     _lib.decode_check(status)
     return (_unpad(outp, d, out) if d < dp else outp), lse
+
+
+def flash_attn_decode(q, k_cache, v_cache, cache_seqlens=None, causal=True, softmax_scale=None, layout="bnhd", out=None, lse=None,
+                      workspace=None, k_new=None, v_new=None):
+    """Attention of Nq <= 128 new queries against a KV cache (fa_mi355x_fwd_decode / _gqa, include/flash_attn_mi355x_decode.h).
+    ``layout`` "bnhd": q (B, Nq, H, d), caches (B, Ncap, Hkv, dp); "bhnd": q (B, H, Nq, d), caches (B, Hkv, Ncap, dp).  Hkv is the
+    cache's own head count and must divide H: Hkv < H is a grouped-query (Hkv = 1: multi-query) cache, query head h reads cache head
+    h // (H // Hkv), and the group's heads share one pass over it (no expansion of the cache).  dp in {32, 64, 128};
+    a q with fewer columns (d < dp) is zero-padded to the cache's row length (the cache itself holds zero columns d .. dp-1) and the
+    default scale is then 1/sqrt(d).  ``cache_seqlens``: int32 (B,) on q's device, the valid cache rows per batch element counting the
+    new tokens (None: all Ncap); clamped to [0, Ncap] on the device, no host synchronisation.  ``causal``: the queries are the last Nq
+    positions.  ``k_new``, ``v_new`` (both or neither; shapes and placement as decode_append): the new tokens' k and v, written into
+    the caches on the device in front of the attention (fa_mi355x_fwd_decode_append: decode_append, then this call, one library call).
+    Returns (out fp32 in q's shape, lse fp32 (B, H, Nq)): rows with no admissible key give out = 0, lse = -inf."""
+    return _cache_attention("flash_attn_decode", False, q, k_cache, v_cache, cache_seqlens, causal, softmax_scale, layout, out, lse,
+                            workspace, k_new, v_new)
+
+
+def flash_attn_extend(q, k_cache, v_cache, cache_seqlens=None, causal=True, softmax_scale=None, layout="bnhd", out=None, lse=None,
+                      workspace=None, k_new=None, v_new=None):
+    """flash_attn_decode for ANY number Nq >= 1 of new queries (fa_mi355x_fwd_extend / fa_mi355x_fwd_extend_append): a long input that
+    follows a cached prefix, or one piece of a chunked prefill (the same call, from an empty cache on).  Every argument, check, the
+    head-dim padding (the default scale keeps the caller's 1/sqrt(d)) and the return value are flash_attn_decode's; ``workspace`` is
+    sized by extend_workspace (the extend call has its own split policy), ``k_new`` / ``v_new`` are appended as by extend_append.
+    Always the extend kernels, whatever Nq: a workgroup owns 128 rows of a kv head's G * Nq and shares each staged K / V tile among
+    them, and a causal call loads no tile above a block's last position.  For Nq <= 128 the result agrees with flash_attn_decode to
+    rounding, not bit for bit."""
+    return _cache_attention("flash_attn_extend", True, q, k_cache, v_cache, cache_seqlens, causal, softmax_scale, layout, out, lse,
+                            workspace, k_new, v_new)

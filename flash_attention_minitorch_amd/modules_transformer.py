@@ -78,8 +78,10 @@ def attention_stack(x, layers, n_head: int, causal: bool = True, fused_layout: b
 # token and keeps the last row.  With a KV cache, the prompt runs once through the fused causal forward (attention_stack_prefill), and
 # every further step projects only its new tokens, appends their k and v at each batch element's own length and attends to the cache
 # with the decode kernels (attention_stack_step): one pass over the cached K and V per layer instead of causal attention over N tokens.
+# More than 128 new tokens at once (a second turn, a long message after a cached prefix, a prompt fed in pieces) go through the
+# extend kernels (attention_stack_extend, attention_stack_prefill_chunked).
 
-MAX_STEP_TOKENS = 128   # fa_mi355x_fwd_decode's largest Nq; longer inputs are prefill
+MAX_STEP_TOKENS = 128   # fa_mi355x_fwd_decode's largest Nq; longer inputs are prefill, or attention_stack_extend after a prefix
 
 
 class KVCache:
@@ -105,6 +107,12 @@ class KVCache:
         key = tuple(q.shape)
         if key not in self._workspaces:
             self._workspaces[key] = device_ops.decode_workspace(q, self.k[0], "bnhd")
+        return self._workspaces[key]
+
+    def extend_workspace(self, q):
+        key = ("extend",) + tuple(q.shape)   # (the extend call has a split policy of its own: never the decode call's buffer)
+        if key not in self._workspaces:
+            self._workspaces[key] = device_ops.extend_workspace(q, self.k[0], "bnhd")
         return self._workspaces[key]
 
     def _pad(self, t):
@@ -199,6 +207,45 @@ def attention_stack_step_fused(x_new, layers, n_head: int, cache: KVCache):
     (flash_attn_decode(..., k_new=, v_new=)), which writes k and v into the cache and then attends.  No row indices, padded copies
     or index_copy_ on the caller's side; the same results and the same cache contents, bit for bit."""
     return _step(x_new, layers, n_head, cache, fused=True)
+
+
+def attention_stack_extend(x_new, layers, n_head: int, cache: KVCache):
+    """attention_stack_step_fused without its bound on T: x_new (B, T, E), any T >= 1 new tokens that follow each batch element's
+    cached prefix (a second turn, a long message after a cached system prompt; from an empty cache, a prompt or its first piece).
+    T <= 128 IS attention_stack_step_fused (the same bits).  Above that every layer projects the new tokens and hands q, k and v to
+    one device_ops.flash_attn_extend(..., k_new=, v_new=) call, which appends k and v at rows lengths[b] .. lengths[b] + T - 1 and
+    attends causally with the extend kernels (128 rows per workgroup sharing each staged tile of the cache).  Lengths grow by T on
+    the device; the capacity check is the host's, through ``cache.length_bound``.  Returns the stack's output for the new tokens
+    (B, T, E): the last T rows of attention_stack over the whole sequence."""
+    B, T, E = x_new.shape
+    if T <= MAX_STEP_TOKENS:
+        return attention_stack_step_fused(x_new, layers, n_head, cache)
+    if cache.length_bound + T > cache.capacity:
+        raise ValueError(f"cache capacity {cache.capacity} exceeded")
+    new_len = cache.lengths + T
+    x = x_new
+    for li, (wq, wk, wv, wo) in enumerate(layers):
+        q, k, v = _project(x, wq, wk, wv, n_head)
+        _check_kv_heads(k, cache)
+        o, _ = device_ops.flash_attn_extend(q, cache.k[li], cache.v[li], new_len, causal=True, layout="bnhd",
+                                            workspace=cache.extend_workspace(q), k_new=k, v_new=v)
+        x = x + (o.reshape(B * T, E).to(x.dtype) @ wo).view(B, T, E)
+    cache.lengths.copy_(new_len)
+    cache.length_bound += T
+    return x
+
+
+def attention_stack_prefill_chunked(x, layers, n_head: int, cache: KVCache, chunk: int):
+    """attention_stack_prefill in pieces of ``chunk`` tokens: the lengths are reset, then every piece of x (B, P, E) goes through
+    attention_stack_extend after the pieces before it, so the activations of a step are bounded by the piece, not the prompt.
+    Returns the stack's output (B, P, E); the cache ends as attention_stack_prefill leaves it (lengths = P), to rounding."""
+    if chunk < 1:
+        raise ValueError("chunk must be positive")
+    if x.shape[1] > cache.capacity:
+        raise ValueError(f"prompt of {x.shape[1]} tokens exceeds the cache capacity {cache.capacity}")
+    cache.lengths.zero_()
+    cache.length_bound = 0
+    return torch.cat([attention_stack_extend(piece.contiguous(), layers, n_head, cache) for piece in x.split(chunk, 1)], dim=1)
 
 
 class GraphedStep:

@@ -21,7 +21,8 @@
 extern "C" {
 #endif
 
-/* Largest number of new queries per call; more is prefill (fa_mi355x_fwd_layout / fa_mi355x_fwd_scaled). */
+/* Largest number of new queries per decode call; more is prefill (fa_mi355x_fwd_layout / fa_mi355x_fwd_scaled) or, against a
+ * cache, the extend entry points at the end of this header. */
 #define FA_DECODE_MAX_NQ 128
 
 /* Bytes of device workspace fa_mi355x_fwd_decode needs for these sizes: 0 when the call runs as one split, else
@@ -98,6 +99,42 @@ int fa_mi355x_decode_append(const void* k_new, const void* v_new, void* k_cache,
  * from fa_mi355x_decode_workspace_bytes_gqa, same bits).  q has d columns (padded by the caller when d_new < d, as above).  Every
  * argument either of the two rejects is rejected here, before any HIP call and before the caches are touched. */
 int fa_mi355x_fwd_decode_append(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
+                                const int* cache_seqlens, void* workspace, int B, int H, int Hkv, int Nq, int Ncap, int d_new, int d,
+                                int layout, float softmax_scale, int causal, int dtype, void* stream);
+
+/* Extend: ANY number Nq >= 1 of new queries against the cache -- a long input that follows a cached prefix (a second chat turn, a
+ * user message after a cached system prompt, re-scoring more than 128 tokens) and chunked prefill (the same call from an empty
+ * cache, piece by piece).  The semantics, arguments and their order are those of the _gqa decode entry points above (Hkv = H is the
+ * ungrouped call; there is one form only), with no upper bound on Nq:
+ *
+ *   out[b,h,i,:] = softmax_j(scale * q[b,h,i,:] . k[b,h/G,j,:]) . v[b,h/G,j,:],   j < len_b;   causal: query i sits at len_b - Nq + i
+ *
+ * Kernels of their own: a workgroup owns a 128-row block of a kv head's G*Nq rows (row i*G + g, as above) and a key chunk; its four
+ * waves take 32 rows each and share every staged 128-key tile of K and V, each wave keeps its own online softmax, and under `causal`
+ * a workgroup loads no tile above its block's last position.  Everything said of fa_mi355x_fwd_decode_gqa holds: len_b clamped to
+ * [0, Ncap] on the device, rows at or past len_b contribute nothing whatever they hold and nothing past row Ncap - 1 is read, a row
+ * with no admissible key returns out = 0 and lse = -inf, fp32 scaling of every score, no atomics (repeated calls are bitwise
+ * identical), asynchronous on `stream`, no allocation, no host synchronisation (capturable in a graph).  For Nq <= 128 the result
+ * agrees with fa_mi355x_fwd_decode_gqa to rounding, not bitwise (another summation order).
+ *   workspace   fa_mi355x_extend_workspace_bytes(B, H, Hkv, Nq, Ncap, d) bytes: B*H*nsplit*Nq*(d + 2) floats, 0 for one split
+ *   splits      the decode policy with 128-row blocks: B*Hkv*ceil(G*Nq/128) groups, aimed at 512 workgroups (two per CU of an
+ *               assumed 256-CU chip), chunks a multiple of 256 keys and at least 256; a pure function of the arguments (0 for sizes the size queries
+ *               cannot answer, as above)
+ * FA_ERR_BAD_ARG / FA_ERR_UNSUPPORTED_D before any HIP call for every argument fa_mi355x_fwd_decode_gqa rejects but Nq > 128, and
+ * for G*Nq >= 2^25 rows per kv head, a batch element of q or of the cache of 2 GiB or more, and launches whose workgroup counts
+ * (B*Hkv*nsplit*ceil(G*Nq/128) rounded up to 8 items, and B*H*Nq for the combine) do not fit an unsigned int. */
+int fa_mi355x_extend_splits(int B, int H, int Hkv, int Nq, int Ncap, int d, int dtype);
+size_t fa_mi355x_extend_workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int d);
+int fa_mi355x_fwd_extend(const void* q, const void* k_cache, const void* v_cache, float* out, float* lse, const int* cache_seqlens,
+                         void* workspace, int B, int H, int Hkv, int Nq, int Ncap, int d, int layout, float softmax_scale, int causal,
+                         int dtype, void* stream);
+
+/* fa_mi355x_decode_append without its bound on Nq (the same kernel, the same placement: new token i at row L_b - Nq + i), and that
+ * launch followed on the same stream by exactly fa_mi355x_fwd_extend, as fa_mi355x_fwd_decode_append is for the decode call: every
+ * argument either of the two rejects is rejected before any HIP call and before the caches are touched. */
+int fa_mi355x_extend_append(const void* k_new, const void* v_new, void* k_cache, void* v_cache, const int* cache_seqlens, int B, int Hkv,
+                            int Nq, int Ncap, int d_new, int d, int layout, int dtype, void* stream);
+int fa_mi355x_fwd_extend_append(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
                                 const int* cache_seqlens, void* workspace, int B, int H, int Hkv, int Nq, int Ncap, int d_new, int d,
                                 int layout, float softmax_scale, int causal, int dtype, void* stream);
 
