@@ -56,11 +56,11 @@ def _torch():
     return torch
 
 
-def _plans(B, H, Hkv, N, d, causal, dtype, opts):
+def _plans(B, H, Hkv, N, d, causal, dtype, opts, variant=2):
     from flash_attention_minitorch_amd import _lib
     o = (tuple(opts or ()) + (0,) * 8)[:8] + (3,)
     code = _lib.FA_DTYPE_BF16 if dtype == "bf16" else _lib.FA_DTYPE_F32
-    return tuple(";".join(_lib.plan_gqa(B, H, Hkv, N, d, causal, _lib.FA_VARIANT_FA2, code, st, o)) for st in (0, 7))
+    return tuple(";".join(_lib.plan_gqa(B, H, Hkv, N, d, causal, variant, code, st, o)) for st in (0, 7))
 
 
 def _same_kernel_opts(B, H, N, d, causal, dtype, opts):
@@ -71,6 +71,24 @@ def _same_kernel_opts(B, H, N, d, causal, dtype, opts):
     if "bwd_onepass_f32_kernel" in _lib.plan(B * H, N, d, causal, _lib.FA_VARIANT_FA2, code, 7, opts):
         return (tuple(opts or ()) + (0,) * 5)[:4] + (4,)
     return opts
+
+
+def _oracle(q, k, v, do, causal, kv_heads=None):
+    """The fp64 oracle of a grouped call, numpy q, do (B, H, N, d) and k, v (B, Hkv, N, d), on the whole groups ``kv_heads`` (indices
+    into the flattened (B, Hkv); None: all of them, in order).  Per group, in that order: o, dq (n, G, N, d) and L, m (n, G, N) per
+    query head, dk, dv (n, N, d) summed over the group's G heads in fp64."""
+    B, H, N, d = q.shape
+    Hkv = k.shape[1]
+    G = H // Hkv
+    qg, dog = q.reshape(B * Hkv, G, N, d), do.reshape(B * Hkv, G, N, d)
+    kf, vf = k.reshape(B * Hkv, 1, N, d), v.reshape(B * Hkv, 1, N, d)
+    per = {n: [] for n in ("o", "L", "m", "dq", "dk", "dv")}
+    for i in (range(B * Hkv) if kv_heads is None else kv_heads):
+        o, L, m, _ = oracle.dense_attention_fw(qg[i], kf[i], vf[i], causal)
+        dq, dk, dv = oracle.dense_attention_bw(qg[i], kf[i], vf[i], dog[i], causal)
+        for n, a in zip(("o", "L", "m", "dq", "dk", "dv"), (o, L, m, dq, dk.sum(axis=0), dv.sum(axis=0))):
+            per[n].append(np.asarray(a, dtype=np.float64))
+    return {n: np.stack(a) for n, a in per.items()}
 
 
 _INPUTS = {}
@@ -89,17 +107,9 @@ def _inputs(shape, grouping):
         k, v = rand_u(rng, (B, Hkv, N, d)), rand_u(rng, (B, Hkv, N, d))
         if dtype == "bf16":
             q, k, v, do = (oracle.bf16_round(t) for t in (q, k, v, do))
-        ke, ve = np.repeat(k, G, axis=1), np.repeat(v, G, axis=1)
-        per = {n: [] for n in ("o", "L", "dq", "dk", "dv")}
-        for b in range(B):
-            for h in range(H):
-                o, L, _, _ = oracle.dense_attention_fw(q[b, h], ke[b, h], ve[b, h], causal)
-                dq, dk, dv = oracle.dense_attention_bw(q[b, h], ke[b, h], ve[b, h], do[b, h], causal)
-                for n, a in zip(("o", "L", "dq", "dk", "dv"), (o, L, dq, dk, dv)):
-                    per[n].append(np.asarray(a, dtype=np.float64))
-        ref = {n: np.stack(a).reshape((B, H) + a[0].shape) for n, a in per.items()}
-        for n in ("dk", "dv"):
-            ref[n] = ref[n].reshape(B, Hkv, G, N, d).sum(axis=2)
+        per = _oracle(q, k, v, do, causal)
+        ref = {n: per[n].reshape((B, H) + per[n].shape[2:]) for n in ("o", "L", "dq")}
+        ref.update({n: per[n].reshape(B, Hkv, N, d) for n in ("dk", "dv")})
         _INPUTS[key] = (q, k, v, do, ref)
     return _INPUTS[key]
 
@@ -119,21 +129,31 @@ def _expand(t, G, layout):
     return t.repeat_interleave(G, dim=2 if layout == "bnhd" else 1).contiguous()
 
 
-def _grouped(tq, tk, tv, tdo, causal, layout, opts):
+def _grouped(tq, tk, tv, tdo, causal, layout, opts, variant=2, softmax_scale=None, guard="auto"):
+    """(out, l, dq, dk, dv) of the grouped forward and backward; with variant = FA-1 also m, behind them.  ``guard``: "auto", None, or a
+    tensor that both calls read."""
     from flash_attention_minitorch_amd import device_ops
-    out, l, _ = device_ops.flash_attn_fwd_gqa(tq, tk, tv, causal=causal, layout=layout, opts=opts)
-    dq, dk, dv = device_ops.flash_attn_bwd_gqa(tq, tk, tv, out, tdo, l, causal=causal, layout=layout, opts=opts)
-    return out, l, dq, dk, dv
+    out, l, m = device_ops.flash_attn_fwd_gqa(tq, tk, tv, causal=causal, variant=variant, softmax_scale=softmax_scale, layout=layout,
+                                              guard=guard, opts=opts)
+    dq, dk, dv = device_ops.flash_attn_bwd_gqa(tq, tk, tv, out, tdo, l, m, causal=causal, variant=variant, softmax_scale=softmax_scale,
+                                               layout=layout, guard=guard, opts=opts)
+    return (out, l, dq, dk, dv) + (() if m is None else (m,))
 
 
-def _ungrouped(tq, tk, tv, tdo, causal, layout, opts):
-    """The existing by-heads entry points (fa_mi355x_fwd_guarded / _bwd_guarded) on tensors of one shape."""
+def _ungrouped(tq, tk, tv, tdo, causal, layout, opts, variant=2, softmax_scale=None, guard="auto"):
+    """The existing by-heads entry points (fa_mi355x_fwd_guarded / _bwd_guarded) on tensors of one shape; results as _grouped."""
     from flash_attention_minitorch_amd import device_ops
     if layout == "bnhd":
-        out, l, _ = device_ops.flash_attn_fwd_bnhd(tq, tk, tv, causal, opts=opts)
-        return (out, l) + tuple(device_ops.flash_attn_bwd_bnhd(tq, tk, tv, out, tdo, l, causal=causal, opts=opts))
-    out, l, _ = device_ops.flash_attn_fwd(tq, tk, tv, causal, opts=opts)
-    return (out, l) + tuple(device_ops.flash_attn_bwd(tq, tk, tv, out, tdo, l, causal=causal, opts=opts))
+        out, l, m = device_ops.flash_attn_fwd_bnhd(tq, tk, tv, causal, variant, softmax_scale, guard=guard, opts=opts)
+        g = device_ops.flash_attn_bwd_bnhd(tq, tk, tv, out, tdo, l, m, causal=causal, variant=variant, softmax_scale=softmax_scale,
+                                           guard=guard, opts=opts)
+    elif softmax_scale is None:
+        out, l, m = device_ops.flash_attn_fwd(tq, tk, tv, causal, variant, opts=opts, guard=guard)
+        g = device_ops.flash_attn_bwd(tq, tk, tv, out, tdo, l, m, causal=causal, variant=variant, opts=opts, guard=guard)
+    else:   # (the public (B, H, N, d) calls take no scale: the call path they share with the (B, N, H, d) ones does)
+        out, l, m = device_ops._fwd(device_ops._BHND, tq, tk, tv, causal, variant, softmax_scale, opts, guard=guard)
+        g = device_ops._bwd(device_ops._BHND, tq, tk, tv, out, tdo, l, m, causal, variant, softmax_scale, opts, guard=guard)
+    return (out, l) + tuple(g) + (() if m is None else (m,))
 
 
 def _check_group_sum(got, per_head, G, layout, what):
@@ -153,14 +173,38 @@ def _check_group_sum(got, per_head, G, layout, what):
     assert got.shape == total.shape and worst <= 0.0, (what, worst)
 
 
-def _against_library(tq, tk, tv, tdo, got, G, causal, layout, opts_ungrouped):
+def _against_library(tq, tk, tv, tdo, got, G, causal, layout, opts_ungrouped, variant=2, softmax_scale=None, guard="auto"):
     torch = _torch()
-    ref = _ungrouped(tq, _expand(tk, G, layout), _expand(tv, G, layout), tdo, causal, layout, opts_ungrouped)
+    ref = _ungrouped(tq, _expand(tk, G, layout), _expand(tv, G, layout), tdo, causal, layout, opts_ungrouped, variant, softmax_scale,
+                     guard)
     torch.cuda.synchronize()
+    assert len(got) == len(ref)
     for name, a, b in zip(("out", "l", "dq"), (got[0], got[1], got[2]), (ref[0], ref[1], ref[2])):
         assert torch.equal(a, b), f"{name} differs from the ungrouped call on expanded k, v"
+    if len(got) > 5:   # FA-1: the row maxima
+        assert got[5].shape == ref[5].shape and torch.equal(got[5], ref[5]), "m differs from the ungrouped call on expanded k, v"
     _check_group_sum(got[3], ref[3], G, layout, "dk")
     _check_group_sum(got[4], ref[4], G, layout, "dv")
+
+
+def _check_oracle(got, ref, kv_heads, Hkv, layout, dtype, tag, bound=None):
+    """(out, l, dq, dk, dv) of a grouped call against _oracle's ``ref`` on the whole groups ``kv_heads`` (None: all): max-abs error below
+    the envelope on o, L and dq and G times it on dk and dv, or ``bound(name, reference)`` in its place.  Returns the errors."""
+    B = got[1].shape[0]
+    G = got[1].shape[1] // Hkv
+    N, d = got[1].shape[2], got[0].shape[-1]
+    sel = list(range(B * Hkv) if kv_heads is None else kv_heads)
+    have = {"o": _bhnd(got[0], layout).reshape(B * Hkv, G, N, d)[sel], "L": to_np(got[1]).reshape(B * Hkv, G, N)[sel],
+            "dq": _bhnd(got[2], layout).reshape(B * Hkv, G, N, d)[sel], "dk": _bhnd(got[3], layout).reshape(B * Hkv, N, d)[sel],
+            "dv": _bhnd(got[4], layout).reshape(B * Hkv, N, d)[sel]}
+    errs = {n: maxabs(a, ref[n]) for n, a in have.items()}
+    env = ENVELOPE[dtype]
+    lim = {n: (bound(n, ref[n]) if bound else env) * (G if n in ("dk", "dv") else 1) for n in have}
+    print(f"{tag} ({len(sel)} groups of {G}): " + ", ".join(f"{n} {e:.3e} (< {lim[n]:.1e})" for n, e in errs.items()))
+    for n, a in have.items():
+        assert np.all(np.isfinite(a)), (tag, n)
+        assert errs[n] < lim[n], (tag, n, errs[n], lim[n])
+    return errs
 
 
 @pytest.mark.parametrize("shape,grouping,layout", CASES, ids=[f"{s}-{g}-{lay}" for s, g, lay in CASES])

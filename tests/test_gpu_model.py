@@ -137,3 +137,63 @@ def test_folded_softmax_scale_keeps_the_slot_kernels_exact_on_large_activations(
         scale = max(1.0, float(np.max(np.abs(ref))))
         assert maxabs(got, ref) < (5e-3 if nm == "o" else 1e-2) * scale, (nm, maxabs(got, ref), scale)
     assert maxabs(to_np(l), rL) < 1e-3 * max(1.0, float(np.max(np.abs(rL))))
+
+
+_GROUPED_MODEL = {}
+
+
+def _grouped_model():
+    """A two-layer causal grouped-query stack (B = 2, N = 300, E = 256, H = 4 query heads, Hkv = 2 kv heads, d = 64: wk, wv of shape
+    (E, Hkv * d)) and, computed once, its fp64 oracle: _oracle_stack on weights whose k / v column blocks are repeated per group
+    (query head h reads kv head h // G), dwk and dwv folded back by summing each group's column blocks."""
+    if not _GROUPED_MODEL:
+        rng = np.random.default_rng(4400)
+        B, N, E, H, Hkv, LAYERS = 2, 300, 256, 4, 2, 2
+        d, G = E // H, H // Hkv
+        x, dout = rand_u(rng, (B, N, E)), rand_u(rng, (B, N, E))
+        w = lambda cols: (rand_u(rng, (E, cols)) * np.float32(1.5 / np.sqrt(E))).astype(np.float32)
+        layers = [(w(E), w(Hkv * d), w(Hkv * d), w(E)) for _ in range(LAYERS)]
+        expand = lambda t: np.repeat(t.reshape(E, Hkv, 1, d), G, axis=2).reshape(E, E)
+        fold = lambda t: t.reshape(E, Hkv, G, d).sum(axis=2).reshape(E, Hkv * d)
+        expanded = [(wq, expand(wk), expand(wv), wo) for wq, wk, wv, wo in layers]
+        ry, rdx, rg = _oracle_stack(x, expanded, H, True, dout)
+        rg = [(dwq, fold(dwk), fold(dwv), dwo) for dwq, dwk, dwv, dwo in rg]
+        _GROUPED_MODEL.update(x=x, dout=dout, layers=layers, expanded=expanded, fold=fold, H=H, ref=(ry, rdx, rg))
+    return _GROUPED_MODEL
+
+
+@pytest.mark.parametrize("fold_scale", [False, True])
+def test_grouped_query_attention_stack_fp32_matches_fp64_oracle_chain(fold_scale):
+    """multi_head_attention with (E, Hkv * d) key / value weights under autograd, end to end: the kernels read the Hkv heads of k and v in
+    place (device_ops.flash_attn_gqa) and the ordered group sum gives dk, dv in k's shape, from which wk.grad and wv.grad come out in
+    wk's shape.  Output, dx and every weight gradient against the fp64 oracle chain at this file's tolerance, with the scale folded
+    into the query projection (softmax_scale = ln 2) and without; and the same stack on the expanded weights through the ungrouped
+    path, its dwk / dwv folded per group, agrees within the same tolerance."""
+    import torch
+    from flash_attention_minitorch_amd import modules_transformer as mt
+    m = _grouped_model()
+    ry, rdx, rg = m["ref"]
+    tol = lambda ref: 2e-4 * max(1.0, float(np.max(np.abs(ref))))
+
+    def run(layers):
+        tx = torch.from_numpy(m["x"]).cuda().requires_grad_(True)
+        tl = [tuple(torch.from_numpy(w).cuda().requires_grad_(True) for w in lw) for lw in layers]
+        y = mt.attention_stack(tx, tl, m["H"], causal=True, fold_scale=fold_scale)
+        y.backward(torch.from_numpy(m["dout"]).cuda())
+        return y, tx, tl
+    y, tx, tl = run(m["layers"])
+    assert maxabs(to_np(y), ry) < tol(ry), (maxabs(to_np(y), ry), tol(ry))
+    assert maxabs(to_np(tx.grad), rdx) < tol(rdx), (maxabs(to_np(tx.grad), rdx), tol(rdx))
+    for li, (lw, lref) in enumerate(zip(tl, rg)):
+        for nm, got, ref in zip(("wq", "wk", "wv", "wo"), lw, lref):
+            assert got.grad.shape == got.shape, (li, nm)
+            print(f"grouped model fold_scale={fold_scale} layer {li} d{nm}: {maxabs(to_np(got.grad), ref):.3e} (< {tol(ref):.3e})")
+            assert maxabs(to_np(got.grad), ref) < tol(ref), (li, nm, maxabs(to_np(got.grad), ref), tol(ref))
+    # a second opinion: the ungrouped path on the expanded weights
+    y2, tx2, tl2 = run(m["expanded"])
+    assert maxabs(to_np(y2), to_np(y)) < tol(ry) and maxabs(to_np(tx2.grad), to_np(tx.grad)) < tol(rdx)
+    for li, (lw, lw2, lref) in enumerate(zip(tl, tl2, rg)):
+        for nm, got, other, ref in zip(("wq", "wk", "wv", "wo"), lw, lw2, lref):
+            og = to_np(other.grad)
+            og = m["fold"](og) if nm in ("wk", "wv") else og
+            assert maxabs(to_np(got.grad), og) < tol(ref), ("expanded", li, nm, maxabs(to_np(got.grad), og), tol(ref))

@@ -150,6 +150,38 @@ def test_plan_of_a_grouped_call_adds_one_group_sum_behind_the_dkdv_stage(built):
     assert built.plan_gqa(2, 8, 8, 256, 64, False, 2, 1, 7) == built.plan(16, 256, 64, False, 2, 1, 7)
 
 
+def test_every_plan_the_gpu_edge_tests_assert(built):
+    """tests/test_gpu_gqa_edges.py asserts the kernel plan of each of its cases, so that a policy change cannot move a case off its
+    kernel unnoticed; plan_pins() lists every one of them.  Held here against fa_mi355x_plan_gqa of the CPU build, which plans for the
+    256 CUs of an MI355X: the table is proved without a GPU.  Below that, the rows the table rests on, spelled out."""
+    import test_gpu_gqa_edges as edges
+    pins = edges.plan_pins()
+    assert len(pins) > 150
+    for (B, H, Hkv, N, d, causal, variant, dtype, stages, opts), want in pins:
+        got = ";".join(built.plan_gqa(B, H, Hkv, N, d, causal, variant, 1 if dtype == "bf16" else 0, stages, opts or None))
+        assert got == want, ((B, H, Hkv, N, d, causal, variant, dtype, stages, opts), got, want)
+    guarded = (0,) * 8 + (3,)
+    slot = ["bwd_dq_slot_kernel", "bwd_dkdv_slot_kernel", "group_sum_kernel"]
+    phased_causal = ["bwd_dq_kernel", "bwd_dq_kernel", "bwd_dkdv_kernel", "group_sum_kernel"]
+    # bf16, d = 64, N = 512, causal: batch * (N / 256) >= 128 takes the causal slot builds by default, 32 heads do not
+    assert built.plan_gqa(8, 16, 4, 512, 64, True, 2, 1, 7, guarded) == slot
+    assert built.plan_gqa(8, 16, 4, 512, 64, True, 2, 1, 0, guarded) == ["fwd_slot_kernel", "fwd_kernel"]
+    assert built.plan_gqa(2, 8, 2, 512, 64, True, 2, 1, 7, guarded) == phased_causal
+    assert built.plan_gqa(2, 12, 3, 768, 64, True, 2, 1, 7, guarded) == phased_causal
+    assert built.plan_gqa(2, 12, 3, 768, 64, False, 2, 1, 7, guarded) == slot
+    assert built.plan_gqa(3, 24, 8, 1024, 64, True, 2, 1, 7, (5, 3, 3, 0, 0, 0, 0, 2, 3)) == slot
+    # fp32, d = 64: the ungrouped call of these sizes takes the one-pass backward, the grouped one what option 4 = 4 selects
+    for B, H, Hkv, N in edges.ONEPASS_SHAPES:
+        for causal in (False, True):
+            assert built.plan(B * H, N, 64, causal, 2, 0, 7) == ["bwd_prep_kernel", "bwd_onepass_f32_kernel"]
+            assert built.plan_gqa(B, H, Hkv, N, 64, causal, 2, 0, 7) == ["bwd_prep_kernel", "bwd_dkdv_kernel", "group_sum_kernel",
+                                                                         "bwd_dq_kernel"]
+    # a stage mask runs the group sum behind the dK/dV stage alone
+    assert built.plan_gqa(2, 8, 2, 600, 64, False, 2, 1, 2) == ["bwd_dkdv_slot_kernel", "group_sum_kernel"]
+    assert built.plan_gqa(2, 8, 2, 600, 64, False, 2, 1, 4) == ["bwd_dq_slot_kernel"]
+    assert built.plan_gqa(2, 8, 2, 600, 64, False, 2, 1, 1) == ["bwd_prep_kernel"]
+
+
 # ---- the Python layer, against a recorder ----------------------------------------------------------------------------------------------
 
 from flash_attention_minitorch_amd import _lib, device_ops as dev, modules_transformer as mt   # noqa: E402
