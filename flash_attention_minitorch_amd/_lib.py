@@ -35,6 +35,7 @@ FA_DTYPE_BF16 = 1
 FA_OK = 0
 FA_LAYOUT_BHND = 0
 FA_LAYOUT_BNHD = 1
+FA_PAGE_ROWS = 128   # a paged cache's page_size is a multiple of this (include/flash_attn_mi355x_decode.h)
 
 _handles: dict = {}
 
@@ -125,6 +126,16 @@ DECODE_ABI = {
     "fa_mi355x_decode_last_error": (_s, []),
 }
 
+# the same for include/flash_attn_mi355x_decode_paged.h (the paged forms of the same library; tests/test_paged_cpu.py)
+PAGED_ABI = {
+    "fa_mi355x_fwd_decode_paged": (_i, [_vp] * 8 + [_i] * 9 + [_f, _i, _i, _vp]),
+    "fa_mi355x_decode_append_paged": (_i, [_vp] * 6 + [_i] * 10 + [_vp]),
+    "fa_mi355x_fwd_decode_append_paged": (_i, [_vp] * 10 + [_i] * 10 + [_f, _i, _i, _vp]),
+    "fa_mi355x_fwd_extend_paged": (_i, [_vp] * 8 + [_i] * 9 + [_f, _i, _i, _vp]),
+    "fa_mi355x_extend_append_paged": (_i, [_vp] * 6 + [_i] * 10 + [_vp]),
+    "fa_mi355x_fwd_extend_append_paged": (_i, [_vp] * 10 + [_i] * 10 + [_f, _i, _i, _vp]),
+}
+
 
 def _typed(name: str, abi: dict) -> ctypes.CDLL:
     """The library with restype / argtypes of every symbol in ``abi`` set (once, on first load)."""
@@ -193,8 +204,8 @@ DECODE_NAME = "libflash_attn_mi355x_decode.so"
 
 
 def decode() -> ctypes.CDLL:
-    """libflash_attn_mi355x_decode.so (include/flash_attn_mi355x_decode.h) with argtypes set."""
-    return _typed(DECODE_NAME, DECODE_ABI)
+    """libflash_attn_mi355x_decode.so (include/flash_attn_mi355x_decode.h and its _paged.h) with argtypes set."""
+    return _typed(DECODE_NAME, {**DECODE_ABI, **PAGED_ABI})
 
 
 def decode_check(status: int) -> None:

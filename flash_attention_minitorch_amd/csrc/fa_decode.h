@@ -26,6 +26,13 @@
 // [0, Ncap]), with the row offset in the per-lane voffset, so rows at or past len_b read as zero in hardware: whatever they hold (NaN
 // included) reaches neither a score nor the P.V product, and no load goes past row Ncap - 1.  Q goes through a resource of its batch
 // element with (head, query) in the voffset; rows rho >= G * Nq get the resource's size as their offset, read as zero and store nothing.
+//
+// Paged caches (the PAGED builds of the split, extend and append kernels; include/flash_attn_mi355x_decode_paged.h): the cache is a
+// pool of pages of page_size rows and a block table [B][max_pages] names each batch element's pages.  page_size is a multiple of the
+// 128-key super tile and every chunk starts on a multiple of it, so a staged tile never straddles two pages: paging costs one
+// wave-uniform table entry and one resource per super tile (PageWalk), and the tile loop, the LDS image and the MFMA work are those
+// of the contiguous builds, which is why a paged call returns the contiguous call's bits on the gathered cache.  The PAGED = false
+// builds are the code they were (same registers, LDS and instructions: DESIGN.md "Paged").
 #pragma once
 #include "fa_common.h"
 
@@ -48,6 +55,10 @@ struct DecodeArgs {
   long q_bstride, q_hstride, kv_bstride, kv_hstride;
   int causal;
   float tau;
+  // paged builds only (a pool of pages and a block table instead of one slab per batch element; Ncap = max_pages * page_size)
+  const int* table;    // [B][max_pages] page ids
+  int page_size, num_pages, max_pages;   // rows per page (a multiple of DEC_ROWS), pages in the pool, table entries per batch element
+  long page_stride;    // elements between consecutive pages: page_size * Hkv * D
 };
 
 FA_DEV int clamp_len(const int* seqlens, int Ncap, int b) {
@@ -78,9 +89,44 @@ template <typename S> FA_DEV void load_rows(S& st, rsrc_t rs, int row0) {
   }
 }
 
+// Paged cache: logical row j of batch element b is row j % page_size of page table[b][j / page_size].  page_size is a multiple of
+// DEC_ROWS and every chunk starts on a multiple of it, so a super tile lies inside one page: the tile at logical row t0 goes through
+// a resource of its page's (kv head) slice sized to the page's valid rows, min(page_size, len - page start), with the tile's row
+// inside the page in the voffset, exactly as load_rows does for the slab.  Rows at or past len_b read as zero as before, and a page
+// id is clamped to the pool, so no access leaves it whatever the table holds.  (slot, off) walk forward by additions; the id of the
+// tile after the one being loaded is fetched a tile ahead, so the table's latency sits under a tile's products.  Everything here is
+// wave-uniform: the table is read through a workgroup-uniform index and the id passes readfirstlane, so the resources stay in SGPRs.
+struct PageWalk {
+  const int* row;   // the table row of this batch element
+  int slot, off;    // of the next tile to load: its entry in the row and its first row inside that page
+  int next;         // that tile's page id (clamped)
+  FA_DEV int id(const DecodeArgs& a) const { return __builtin_amdgcn_readfirstlane(min(max(row[slot], 0), a.num_pages - 1)); }
+  // t0: the first tile of the workgroup's chunk
+  FA_DEV void init(const DecodeArgs& a, int b, int t0) {
+    row = a.table + (size_t)b * a.max_pages;
+    slot = t0 / a.page_size;
+    off = t0 - slot * a.page_size;
+    next = id(a);
+  }
+  // loads the tile at (slot, off) and steps to the one after it, fetching its id if there is one (more)
+  template <typename T, int D, typename S> FA_DEV void load(const DecodeArgs& a, S& sk, S& sv, size_t hoff, int len, bool more) {
+    const int rows = min(a.page_size, len - slot * a.page_size);
+    const uint32_t bytes = ((uint32_t)(rows - 1) * a.kv_ld + D) * (uint32_t)sizeof(T);
+    const size_t base = (size_t)next * a.page_stride + hoff;
+    load_rows(sk, make_rsrc(reinterpret_cast<const T*>(a.k) + base, bytes), off);
+    load_rows(sv, make_rsrc(reinterpret_cast<const T*>(a.v) + base, bytes), off);
+    off += DEC_ROWS;
+    if (off == a.page_size) {
+      off = 0;
+      ++slot;
+    }
+    if (more) next = id(a);
+  }
+};
+
 // GROUPED = false is the G = 1 build: rho = i with no row arithmetic in front of the workgroup's first loads (a workgroup lives for a
-// few super tiles, so its prologue is not free: DESIGN.md "Decode").
-template <typename T, int D, bool GROUPED>
+// few super tiles, so its prologue is not free: DESIGN.md "Decode").  PAGED: the cache is a pool read through a block table (PageWalk).
+template <typename T, int D, bool GROUPED, bool PAGED = false>
 __global__ void __launch_bounds__(256) decode_split_kernel(DecodeArgs a) {
   using A = Atom<T>;
   typedef typename A::frag frag;
@@ -116,13 +162,14 @@ __global__ void __launch_bounds__(256) decode_split_kernel(DecodeArgs a) {
   float m_run = -INFINITY, l_run = 0.f;
 
   if (c0 < c1) {   // (a chunk wholly past len_b loads nothing and leaves the empty partial m = -inf, l = 0)
-    const size_t kvoff = (size_t)b * a.kv_bstride + (size_t)hkv * a.kv_hstride;
+    const size_t kvoff = (PAGED ? 0 : (size_t)b * a.kv_bstride) + (size_t)hkv * a.kv_hstride;   // (paged: inside a page)
     const uint32_t esz = sizeof(T);
     const uint32_t q_bytes = (uint32_t)a.q_bstride * esz;
     const rsrc_t qrs = make_rsrc(reinterpret_cast<const T*>(a.q) + (size_t)b * a.q_bstride, q_bytes);
     const uint32_t kv_bytes = ((uint32_t)(len - 1) * a.kv_ld + D) * esz;
-    const rsrc_t krs = make_rsrc(reinterpret_cast<const T*>(a.k) + kvoff, kv_bytes);
+    const rsrc_t krs = make_rsrc(reinterpret_cast<const T*>(a.k) + kvoff, kv_bytes);   // (the slab's: unused by a paged build)
     const rsrc_t vrs = make_rsrc(reinterpret_cast<const T*>(a.v) + kvoff, kv_bytes);
+    PageWalk pw;
 
     frag qf[KC];
     const int qoff = live ? (hd * (int)a.q_hstride + qi * a.q_ld + 8 * h) * (int)esz : (int)q_bytes;
@@ -138,15 +185,24 @@ __global__ void __launch_bounds__(256) decode_split_kernel(DecodeArgs a) {
     // the positions pos_lo .. pos_hi (wave-uniform; pos_hi may count rows past G * Nq, which only keeps a tile that masks to nothing)
     const int qpos = len - a.Nq + qi;
     const int pos_lo = len - a.Nq + (GROUPED ? row_query(a, q0) : q0), pos_hi = len - a.Nq + (GROUPED ? row_query(a, q0 + 31) : q0 + 31);
-    load_rows(sk, krs, c0);
-    load_rows(sv, vrs, c0);
+    if constexpr (PAGED) {
+      pw.init(a, b, c0);
+      pw.template load<T, D>(a, sk, sv, kvoff, len, c0 + DEC_ROWS < c1);
+    } else {
+      load_rows(sk, krs, c0);
+      load_rows(sv, vrs, c0);
+    }
     for (int t0 = c0; t0 < c1; t0 += DEC_ROWS) {
       __syncthreads();   // (the previous super tile's reads are done)
       sk.store(tk);
       sv.store(tv);
       if (t0 + DEC_ROWS < c1) {
-        load_rows(sk, krs, t0 + DEC_ROWS);
-        load_rows(sv, vrs, t0 + DEC_ROWS);
+        if constexpr (PAGED) {
+          pw.template load<T, D>(a, sk, sv, kvoff, len, t0 + 2 * DEC_ROWS < c1);
+        } else {
+          load_rows(sk, krs, t0 + DEC_ROWS);
+          load_rows(sv, vrs, t0 + DEC_ROWS);
+        }
       }
       __syncthreads();
       const int kbase = t0 + 32 * w;
@@ -268,7 +324,7 @@ __global__ void __launch_bounds__(256) decode_split_kernel(DecodeArgs a) {
 // only those that straddle pos_lo .. pos_hi.  A wave whose rows are all >= G * Nq stages, meets the barriers and stores nothing.
 constexpr int EXT_BLOCK = 128;   // rows per workgroup: 32 per wave
 
-template <typename T, int D>
+template <typename T, int D, bool PAGED = false>
 __global__ void __launch_bounds__(256) extend_split_kernel(DecodeArgs a) {
   using A = Atom<T>;
   typedef typename A::frag frag;
@@ -304,13 +360,14 @@ __global__ void __launch_bounds__(256) extend_split_kernel(DecodeArgs a) {
   float m_run = -INFINITY, l_run = 0.f;
 
   if (c0 < cend) {   // (a chunk past len_b, or past every position of the block, loads nothing and leaves m = -inf, l = 0)
-    const size_t kvoff = (size_t)b * a.kv_bstride + (size_t)hkv * a.kv_hstride;
+    const size_t kvoff = (PAGED ? 0 : (size_t)b * a.kv_bstride) + (size_t)hkv * a.kv_hstride;   // (paged: inside a page)
     const uint32_t esz = sizeof(T);
     const uint32_t q_bytes = (uint32_t)a.q_bstride * esz;
     const rsrc_t qrs = make_rsrc(reinterpret_cast<const T*>(a.q) + (size_t)b * a.q_bstride, q_bytes);
     const uint32_t kv_bytes = ((uint32_t)(len - 1) * a.kv_ld + D) * esz;
-    const rsrc_t krs = make_rsrc(reinterpret_cast<const T*>(a.k) + kvoff, kv_bytes);
+    const rsrc_t krs = make_rsrc(reinterpret_cast<const T*>(a.k) + kvoff, kv_bytes);   // (the slab's: unused by a paged build)
     const rsrc_t vrs = make_rsrc(reinterpret_cast<const T*>(a.v) + kvoff, kv_bytes);
+    PageWalk pw;
 
     frag qf[KC];
     const int qoff = live ? (hd * (int)a.q_hstride + qi * a.q_ld + 8 * h) * (int)esz : (int)q_bytes;
@@ -326,15 +383,24 @@ __global__ void __launch_bounds__(256) extend_split_kernel(DecodeArgs a) {
     // sub-tile that masks to nothing for the real rows' lanes)
     const int qpos = len - a.Nq + qi;
     const int pos_lo = len - a.Nq + row_query(a, q0), pos_hi = len - a.Nq + row_query(a, q0 + 31);
-    load_rows(sk, krs, c0);
-    load_rows(sv, vrs, c0);
+    if constexpr (PAGED) {
+      pw.init(a, b, c0);
+      pw.template load<T, D>(a, sk, sv, kvoff, len, c0 + DEC_ROWS < cend);
+    } else {
+      load_rows(sk, krs, c0);
+      load_rows(sv, vrs, c0);
+    }
     for (int t0 = c0; t0 < cend; t0 += DEC_ROWS) {
       __syncthreads();   // (the previous super tile's reads are done)
       sk.store(tk);
       sv.store(tv);
       if (t0 + DEC_ROWS < cend) {
-        load_rows(sk, krs, t0 + DEC_ROWS);
-        load_rows(sv, vrs, t0 + DEC_ROWS);
+        if constexpr (PAGED) {
+          pw.template load<T, D>(a, sk, sv, kvoff, len, t0 + 2 * DEC_ROWS < cend);
+        } else {
+          load_rows(sk, krs, t0 + DEC_ROWS);
+          load_rows(sv, vrs, t0 + DEC_ROWS);
+        }
       }
       __syncthreads();
       if (!wave_live) continue;
@@ -475,12 +541,17 @@ struct AppendArgs {
   int ch_shift;         // log2(D / E): lanes per row
   int kv_ld;            // elements between consecutive rows of one head of the cache (D or Hkv*D)
   long kv_bstride, kv_hstride;
+  // paged builds only, as in DecodeArgs (Ncap = max_pages * page_size)
+  const int* table;
+  int page_size, num_pages, max_pages;
+  long page_stride;
 };
 
 // A lane = E consecutive elements of one new row, of K and of V: E = 16 bytes' worth (one vector load and store each; the host picks
 // it when d_new * sizeof(T) is a multiple of 16 and all four pointers are 16-byte aligned) or E = 1.  Consecutive lanes walk the
 // source in memory order.  The elements are copied as bits; the cache's row length D (a power of two) is a run-time argument.
-template <typename T, int E>
+// PAGED: row pos is row pos % page_size of page table[b][pos / page_size], the id clamped to the pool as the split kernels do.
+template <typename T, int E, bool PAGED = false>
 __global__ void __launch_bounds__(256) decode_append_kernel(AppendArgs a) {
   typedef typename std::conditional<sizeof(T) == 2, uint16_t, uint32_t>::type U;
   typedef __attribute__((ext_vector_type(E))) U vec;
@@ -498,7 +569,14 @@ __global__ void __launch_bounds__(256) decode_append_kernel(AppendArgs a) {
   const int pos = clamp_len(a.seqlens, a.Ncap, b) - a.Nq + i;
   if (pos < 0) return;
   const size_t src = (size_t)row * a.d_new + col;
-  const size_t dst = (size_t)b * a.kv_bstride + (size_t)hkv * a.kv_hstride + (size_t)pos * a.kv_ld + col;
+  size_t dst;
+  if constexpr (PAGED) {
+    const int slot = pos / a.page_size;
+    const int page = min(max(a.table[(size_t)b * a.max_pages + slot], 0), a.num_pages - 1);
+    dst = (size_t)page * a.page_stride + (size_t)hkv * a.kv_hstride + (size_t)(pos - slot * a.page_size) * a.kv_ld + col;
+  } else {
+    dst = (size_t)b * a.kv_bstride + (size_t)hkv * a.kv_hstride + (size_t)pos * a.kv_ld + col;
+  }
   vec kk = {}, vv = {};
   if (col < a.d_new) {   // (E > 1: d_new is a multiple of E, so the whole lane is inside the row)
     kk = *reinterpret_cast<const vec*>(reinterpret_cast<const U*>(a.k_new) + src);

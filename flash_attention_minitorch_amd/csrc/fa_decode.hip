@@ -1,5 +1,6 @@
-// C ABI of the MI355X KV-cache decode library (declared in include/flash_attn_mi355x_decode.h): argument checks, the split policies
-// (decode: 32-row blocks, at most 128 queries; extend: 128-row blocks, any number) and the launches of the kernels of fa_decode.h.
+// C ABI of the MI355X KV-cache decode library (declared in include/flash_attn_mi355x_decode.h and its _paged.h): argument checks,
+// the split policies (decode: 32-row blocks, at most 128 queries; extend: 128-row blocks, any number) and the launches of the kernels
+// of fa_decode.h.  A paged call (a pool and a block table) takes the contiguous call's policy at Ncap = max_pages * page_size.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -78,7 +79,10 @@ size_t ext_workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int d) {
 long split_grid(long items, int nqb) { return (items + 7) / 8 * 8 * nqb; }
 
 template <typename T, int D> int launch_extend(fa::DecodeArgs a, int BH, hipStream_t st) {
-  hipLaunchKernelGGL((fa::extend_split_kernel<T, D>), dim3((unsigned)split_grid(a.items, a.nqb)), dim3(256), 0, st, a);
+  if (a.table)
+    hipLaunchKernelGGL((fa::extend_split_kernel<T, D, true>), dim3((unsigned)split_grid(a.items, a.nqb)), dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL((fa::extend_split_kernel<T, D>), dim3((unsigned)split_grid(a.items, a.nqb)), dim3(256), 0, st, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return set_err(FA_ERR_HIP, "extend_split_kernel launch", e);
   if (a.nsplit > 1) {
@@ -99,7 +103,9 @@ template <typename T> int launch_extend_d(const fa::DecodeArgs& a, int BH, int d
 
 template <typename T, int D> int launch(fa::DecodeArgs a, int BH, hipStream_t st) {
   const int grid = ((a.items + 7) / 8) * 8 * a.nqb;
-  if (a.G > 1)
+  if (a.table)   // (one paged build, the grouped one: G = 1 computes the same rows, and a paged workgroup looks up its page anyway)
+    hipLaunchKernelGGL((fa::decode_split_kernel<T, D, true, true>), dim3(grid), dim3(256), 0, st, a);
+  else if (a.G > 1)
     hipLaunchKernelGGL((fa::decode_split_kernel<T, D, true>), dim3(grid), dim3(256), 0, st, a);
   else
     hipLaunchKernelGGL((fa::decode_split_kernel<T, D, false>), dim3(grid), dim3(256), 0, st, a);
@@ -121,9 +127,41 @@ template <typename T> int launch_d(const fa::DecodeArgs& a, int BH, int d, hipSt
   }
 }
 
+// A paged call's block table and pool geometry (null: the contiguous call).
+struct Paging {
+  const int* table;
+  int num_pages, page_size, max_pages;
+};
+
+// The checks a paged call makes first: FA_OK with the logical capacity max_pages * page_size in *Ncap, or the error.
+int check_pages(const Paging& p, int* Ncap) {
+  g_err[0] = 0;
+  if (!p.table) return set_err(FA_ERR_BAD_ARG, "null block_table");
+  if (p.num_pages <= 0) return set_err(FA_ERR_BAD_ARG, "num_pages must be positive");
+  if (p.page_size <= 0) return set_err(FA_ERR_BAD_ARG, "page_size must be positive");
+  if (p.max_pages <= 0) return set_err(FA_ERR_BAD_ARG, "max_pages must be positive");
+  if (p.page_size % FA_PAGE_ROWS != 0) {
+    snprintf(g_err, sizeof(g_err), "page_size = %d must be a multiple of %d rows", p.page_size, FA_PAGE_ROWS);
+    return FA_ERR_BAD_ARG;
+  }
+  // (the kernels count logical rows in an int, a super tile past the capacity included)
+  if ((long)p.max_pages * p.page_size + fa::DEC_ROWS > 0x7fffffffL)
+    return set_err(FA_ERR_BAD_ARG, "max_pages * page_size (the logical capacity) must fit an int");
+  *Ncap = p.max_pages * p.page_size;
+  return FA_OK;
+}
+
+// (a buffer load's row offset is a 32-bit byte count inside one page; page base addresses are 64-bit, so the pool may be any size)
+int check_page_bytes(int page_size, int Hkv, int d, int dtype) {
+  const long esz = dtype == FA_DTYPE_BF16 ? 2 : 4;
+  if ((long)page_size * Hkv * d * esz >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "one page of the pool must stay under 2 GiB");
+  return FA_OK;
+}
+
 // The argument checks of fa_mi355x_fwd_decode_gqa, or (extend) of fa_mi355x_fwd_extend: FA_OK, or the error with its message set.
+// page_size > 0: a paged call with Ncap = max_pages * page_size, where the bound on a batch element of the cache is one on a page.
 int check_decode(const void* q, const void* k_cache, const void* v_cache, const float* out, const void* workspace, int B, int H, int Hkv,
-                 int Nq, int Ncap, int d, int layout, float softmax_scale, int dtype, bool extend = false) {
+                 int Nq, int Ncap, int d, int layout, float softmax_scale, int dtype, bool extend = false, int page_size = 0) {
   g_err[0] = 0;
   if (B <= 0 || H <= 0 || Nq <= 0 || Ncap <= 0 || d <= 0) return set_err(FA_ERR_BAD_ARG, "B, H, Nq, Ncap and d must be positive");
   if (Hkv <= 0) return set_err(FA_ERR_BAD_ARG, "Hkv must be positive");
@@ -145,7 +183,11 @@ int check_decode(const void* q, const void* k_cache, const void* v_cache, const 
   const long esz = dtype == FA_DTYPE_BF16 ? 2 : 4;
   // (a buffer load's row offset is a 32-bit byte count: one batch element, plus a super tile of rows past its end, stays under 2 GiB;
   // q's (head, query) offset within its batch element likewise)
-  if (((long)Ncap + fa::DEC_ROWS) * Hkv * d * esz >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "one batch element of the cache must stay under 2 GiB");
+  if (page_size > 0) {
+    if (check_page_bytes(page_size, Hkv, d, dtype) != FA_OK) return FA_ERR_BAD_ARG;
+  } else if (((long)Ncap + fa::DEC_ROWS) * Hkv * d * esz >= (1L << 31)) {
+    return set_err(FA_ERR_BAD_ARG, "one batch element of the cache must stay under 2 GiB");
+  }
   if ((long)Nq * H * d * esz >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "one batch element of q must stay under 2 GiB");
   if (extend) {
     // (the workgroup counts of the split and the combine launch are unsigned ints, the items an int)
@@ -164,7 +206,7 @@ int check_decode(const void* q, const void* k_cache, const void* v_cache, const 
 // The split (and combine) launches of a checked call: the decode kernels, or (extend) the extend kernels under their own policy.
 int run_decode(const void* q, const void* k_cache, const void* v_cache, float* out, float* lse, const int* cache_seqlens, void* workspace,
                int B, int H, int Hkv, int Nq, int Ncap, int d, int layout, float softmax_scale, int causal, int dtype, void* stream,
-               bool extend = false) {
+               bool extend = false, const Paging* pg = nullptr) {
   const int ns = extend ? ext_splits(B, H, Hkv, Nq, Ncap) : splits(B, H, Hkv, Nq, Ncap);
   fa::DecodeArgs a;
   a.q = q;
@@ -194,6 +236,18 @@ int run_decode(const void* q, const void* k_cache, const void* v_cache, float* o
   a.kv_hstride = bnhd ? d : (long)Ncap * d;
   a.causal = causal ? 1 : 0;
   a.tau = softmax_scale > 0.f ? softmax_scale : sqrtf(1.0f / (float)d);
+  a.table = nullptr;
+  a.page_size = a.num_pages = a.max_pages = 0;
+  a.page_stride = 0;
+  if (pg) {   // the pools: pages of [page_size][Hkv][d] or [Hkv][page_size][d]
+    a.table = pg->table;
+    a.page_size = pg->page_size;
+    a.num_pages = pg->num_pages;
+    a.max_pages = pg->max_pages;
+    a.page_stride = (long)pg->page_size * Hkv * d;
+    a.kv_bstride = 0;
+    a.kv_hstride = bnhd ? d : (long)pg->page_size * d;
+  }
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (extend) return dtype == FA_DTYPE_BF16 ? launch_extend_d<fa::bf16_t>(a, B * H, d, st) : launch_extend_d<float>(a, B * H, d, st);
   return dtype == FA_DTYPE_BF16 ? launch_d<fa::bf16_t>(a, B * H, d, st) : launch_d<float>(a, B * H, d, st);
@@ -221,7 +275,10 @@ int check_append(const void* k_new, const void* v_new, const void* k_cache, cons
 template <typename T, int E> int launch_append(fa::AppendArgs a, int d, hipStream_t st) {
   a.ch_shift = __builtin_ctz(d / E);
   a.lanes <<= a.ch_shift;   // (rows on entry)
-  hipLaunchKernelGGL((fa::decode_append_kernel<T, E>), dim3((unsigned)((a.lanes + 255) / 256)), dim3(256), 0, st, a);
+  if (a.table)
+    hipLaunchKernelGGL((fa::decode_append_kernel<T, E, true>), dim3((unsigned)((a.lanes + 255) / 256)), dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL((fa::decode_append_kernel<T, E>), dim3((unsigned)((a.lanes + 255) / 256)), dim3(256), 0, st, a);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? FA_OK : set_err(FA_ERR_HIP, "decode_append_kernel launch", e);
 }
@@ -232,7 +289,7 @@ template <typename T> int launch_append_e(const fa::AppendArgs& a, int d, bool v
 
 // The append launch of a checked call.
 int run_append(const void* k_new, const void* v_new, void* k_cache, void* v_cache, const int* cache_seqlens, int B, int Hkv, int Nq,
-               int Ncap, int d_new, int d, int layout, int dtype, void* stream) {
+               int Ncap, int d_new, int d, int layout, int dtype, void* stream, const Paging* pg = nullptr) {
   fa::AppendArgs a;
   a.k_new = k_new;
   a.v_new = v_new;
@@ -248,6 +305,18 @@ int run_append(const void* k_new, const void* v_new, void* k_cache, void* v_cach
   a.kv_ld = a.bnhd ? Hkv * d : d;
   a.kv_bstride = (long)Ncap * Hkv * d;
   a.kv_hstride = a.bnhd ? d : (long)Ncap * d;
+  a.table = nullptr;
+  a.page_size = a.num_pages = a.max_pages = 0;
+  a.page_stride = 0;
+  if (pg) {
+    a.table = pg->table;
+    a.page_size = pg->page_size;
+    a.num_pages = pg->num_pages;
+    a.max_pages = pg->max_pages;
+    a.page_stride = (long)pg->page_size * Hkv * d;
+    a.kv_bstride = 0;
+    a.kv_hstride = a.bnhd ? d : (long)pg->page_size * d;
+  }
   const size_t esz = dtype == FA_DTYPE_BF16 ? 2 : 4;
   // 16-byte lanes where every row of the source starts on 16 bytes, as every row of the cache does once its base is
   const bool vec = (d_new * esz) % 16 == 0 &&
@@ -337,6 +406,85 @@ int fa_mi355x_fwd_extend_append(const void* q, const void* k_new, const void* v_
   if (rc != FA_OK) return rc;
   return run_decode(q, k_cache, v_cache, out, lse, cache_seqlens, workspace, B, H, Hkv, Nq, Ncap, d, layout, softmax_scale, causal, dtype,
                     stream, true);
+}
+
+// The paged entry points: the _gqa / extend forms above on a pool of pages read through a block table.
+namespace {
+
+int attend_paged(bool extend, bool fused, const void* q, const void* k_new, const void* v_new, void* k_pool, void* v_pool, float* out, float* lse,
+                 const int* cache_seqlens, const Paging& pg, void* workspace, int B, int H, int Hkv, int Nq, int d_new, int d, int layout,
+                 float softmax_scale, int causal, int dtype, void* stream) {
+  int Ncap = 0;
+  int rc = check_pages(pg, &Ncap);
+  if (rc == FA_OK) rc = check_decode(q, k_pool, v_pool, out, workspace, B, H, Hkv, Nq, Ncap, d, layout, softmax_scale, dtype, extend, pg.page_size);
+  if (rc == FA_OK && fused) rc = check_append(k_new, v_new, k_pool, v_pool, B, Hkv, Nq, Ncap, d_new, d, layout, dtype, extend);
+  if (rc != FA_OK) return rc;
+  if (fused) {
+    rc = run_append(k_new, v_new, k_pool, v_pool, cache_seqlens, B, Hkv, Nq, Ncap, d_new, d, layout, dtype, stream, &pg);
+    if (rc != FA_OK) return rc;
+  }
+  return run_decode(q, k_pool, v_pool, out, lse, cache_seqlens, workspace, B, H, Hkv, Nq, Ncap, d, layout, softmax_scale, causal, dtype,
+                    stream, extend, &pg);
+}
+
+int append_paged(bool extend, const void* k_new, const void* v_new, void* k_pool, void* v_pool, const int* cache_seqlens, const Paging& pg,
+                 int B, int Hkv, int Nq, int d_new, int d, int layout, int dtype, void* stream) {
+  int Ncap = 0;
+  int rc = check_pages(pg, &Ncap);
+  if (rc == FA_OK) rc = check_append(k_new, v_new, k_pool, v_pool, B, Hkv, Nq, Ncap, d_new, d, layout, dtype, extend);
+  if (rc == FA_OK) rc = check_page_bytes(pg.page_size, Hkv, d, dtype);
+  if (rc != FA_OK) return rc;
+  return run_append(k_new, v_new, k_pool, v_pool, cache_seqlens, B, Hkv, Nq, Ncap, d_new, d, layout, dtype, stream, &pg);
+}
+
+}  // namespace
+
+int fa_mi355x_fwd_decode_paged(const void* q, const void* k_pool, const void* v_pool, float* out, float* lse, const int* cache_seqlens,
+                               const int* block_table, void* workspace, int B, int H, int Hkv, int Nq, int num_pages, int page_size,
+                               int max_pages, int d, int layout, float softmax_scale, int causal, int dtype, void* stream) {
+  const Paging pg = {block_table, num_pages, page_size, max_pages};
+  return attend_paged(false, false, q, nullptr, nullptr, const_cast<void*>(k_pool), const_cast<void*>(v_pool), out, lse, cache_seqlens, pg,
+                      workspace, B, H, Hkv, Nq, d, d, layout, softmax_scale, causal, dtype, stream);
+}
+
+int fa_mi355x_fwd_extend_paged(const void* q, const void* k_pool, const void* v_pool, float* out, float* lse, const int* cache_seqlens,
+                               const int* block_table, void* workspace, int B, int H, int Hkv, int Nq, int num_pages, int page_size,
+                               int max_pages, int d, int layout, float softmax_scale, int causal, int dtype, void* stream) {
+  const Paging pg = {block_table, num_pages, page_size, max_pages};
+  return attend_paged(true, false, q, nullptr, nullptr, const_cast<void*>(k_pool), const_cast<void*>(v_pool), out, lse, cache_seqlens, pg,
+                      workspace, B, H, Hkv, Nq, d, d, layout, softmax_scale, causal, dtype, stream);
+}
+
+int fa_mi355x_decode_append_paged(const void* k_new, const void* v_new, void* k_pool, void* v_pool, const int* cache_seqlens,
+                                  const int* block_table, int B, int Hkv, int Nq, int num_pages, int page_size, int max_pages, int d_new,
+                                  int d, int layout, int dtype, void* stream) {
+  const Paging pg = {block_table, num_pages, page_size, max_pages};
+  return append_paged(false, k_new, v_new, k_pool, v_pool, cache_seqlens, pg, B, Hkv, Nq, d_new, d, layout, dtype, stream);
+}
+
+int fa_mi355x_extend_append_paged(const void* k_new, const void* v_new, void* k_pool, void* v_pool, const int* cache_seqlens,
+                                  const int* block_table, int B, int Hkv, int Nq, int num_pages, int page_size, int max_pages, int d_new,
+                                  int d, int layout, int dtype, void* stream) {
+  const Paging pg = {block_table, num_pages, page_size, max_pages};
+  return append_paged(true, k_new, v_new, k_pool, v_pool, cache_seqlens, pg, B, Hkv, Nq, d_new, d, layout, dtype, stream);
+}
+
+int fa_mi355x_fwd_decode_append_paged(const void* q, const void* k_new, const void* v_new, void* k_pool, void* v_pool, float* out,
+                                      float* lse, const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv,
+                                      int Nq, int num_pages, int page_size, int max_pages, int d_new, int d, int layout,
+                                      float softmax_scale, int causal, int dtype, void* stream) {
+  const Paging pg = {block_table, num_pages, page_size, max_pages};
+  return attend_paged(false, true, q, k_new, v_new, k_pool, v_pool, out, lse, cache_seqlens, pg, workspace, B, H, Hkv, Nq, d_new, d, layout,
+                      softmax_scale, causal, dtype, stream);
+}
+
+int fa_mi355x_fwd_extend_append_paged(const void* q, const void* k_new, const void* v_new, void* k_pool, void* v_pool, float* out,
+                                      float* lse, const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv,
+                                      int Nq, int num_pages, int page_size, int max_pages, int d_new, int d, int layout,
+                                      float softmax_scale, int causal, int dtype, void* stream) {
+  const Paging pg = {block_table, num_pages, page_size, max_pages};
+  return attend_paged(true, true, q, k_new, v_new, k_pool, v_pool, out, lse, cache_seqlens, pg, workspace, B, H, Hkv, Nq, d_new, d, layout,
+                      softmax_scale, causal, dtype, stream);
 }
 
 // The ungrouped entry points: Hkv = H.

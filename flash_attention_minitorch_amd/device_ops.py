@@ -552,9 +552,50 @@ def flash_attn_gqa(q, k, v, causal=False, softmax_scale=None, layout="bnhd"):
     return _FlashAttnGqaFn.apply(q, k, v, bool(causal), softmax_scale, layout)
 
 
-def _decode_dims(q, k_cache, layout):
+def _pool_dims(k_pool, layout):
+    """(num_pages, page_size, Hkv, dp) of a paged cache's pool: (num_pages, page_size, Hkv, dp) for "bnhd", (num_pages, Hkv, page_size,
+    dp) for "bhnd", page_size a positive multiple of 128 rows."""
+    if k_pool.dim() != 4:
+        raise ValueError('the pools of a paged cache are 4-d: (num_pages, page_size, Hkv, dp) for "bnhd", (num_pages, Hkv, page_size, dp) '
+                         'for "bhnd"')
+    num_pages, page_size, Hkv, dp = k_pool.shape
+    if layout != "bnhd":
+        page_size, Hkv = Hkv, page_size
+    if num_pages <= 0 or page_size <= 0 or page_size % _lib.FA_PAGE_ROWS:
+        raise ValueError(f"page_size = {page_size} must be a positive multiple of {_lib.FA_PAGE_ROWS} rows (and the pool hold a page)")
+    return num_pages, page_size, Hkv, dp
+
+
+def _check_table(block_table, B, device):
+    if (not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2
+            or block_table.shape[0] != B or block_table.shape[1] < 1 or block_table.device != device
+            or not block_table.is_contiguous()):
+        raise ValueError("block_table must be a contiguous int32 tensor of shape (B, max_pages) on q's device")
+
+
+def _max_pages(block_table, max_pages):
+    """The table's second dimension, or the caller's ``max_pages`` (None: a contiguous cache)."""
+    if block_table is not None:
+        if not isinstance(block_table, torch.Tensor) or block_table.dim() != 2:
+            raise ValueError("block_table must be a contiguous int32 tensor of shape (B, max_pages) on q's device")
+        return int(block_table.shape[1])
+    if max_pages is not None and max_pages < 1:
+        raise ValueError("max_pages must be positive")
+    return max_pages
+
+
+def _decode_dims(q, k_cache, layout, max_pages=None):
     """(B, H, Hkv, Nq, Ncap, dq, dp) of a decode call: q (B, Nq, H, dq) / cache (B, Ncap, Hkv, dp) for "bnhd", (B, H, Nq, dq) /
-    (B, Hkv, Ncap, dp) for "bhnd"; H a multiple of Hkv (grouped-query heads: query head h reads cache head h // (H // Hkv))."""
+    (B, Hkv, Ncap, dp) for "bhnd"; H a multiple of Hkv (grouped-query heads: query head h reads cache head h // (H // Hkv)).
+    ``max_pages``: k_cache is a paged cache's pool (_pool_dims) and Ncap = max_pages * page_size."""
+    if max_pages is not None:
+        if q.dim() != 4:
+            raise ValueError("decode expects a 4-d q")
+        _, page_size, Hkv, dp = _pool_dims(k_cache, layout)
+        (B, Nq, H, dq) = q.shape if layout == "bnhd" else (q.shape[0], q.shape[2], q.shape[1], q.shape[3])
+        if Hkv <= 0 or H % Hkv:
+            raise ValueError(f"q has {H} heads, the pool {Hkv}: the pool's heads must divide q's")
+        return B, H, Hkv, Nq, max_pages * page_size, dq, dp
     if q.dim() != 4 or k_cache.dim() != 4:
         raise ValueError("decode expects 4-d q and caches")
     if layout == "bnhd":
@@ -573,10 +614,12 @@ def _decode_workspace_bytes(B, H, Hkv, Nq, Ncap, dp):
     return lib.fa_mi355x_decode_workspace_bytes_gqa(B, H, Hkv, Nq, Ncap, dp)
 
 
-def decode_workspace(q, k_cache, layout="bnhd"):
+def decode_workspace(q, k_cache, layout="bnhd", block_table=None, max_pages=None):
     """Scratch for flash_attn_decode with these tensors (fa_mi355x_decode_workspace_bytes; one partial O, m, l per query row and key
-    chunk), or None when the call runs as one split and needs none.  A pure function of the shapes: allocate once, reuse every step."""
-    B, H, Hkv, Nq, Ncap, _, dp = _decode_dims(q, k_cache, layout)
+    chunk), or None when the call runs as one split and needs none.  A pure function of the shapes: allocate once, reuse every step.
+    A paged call (``k_cache`` the pool): give the block table or its ``max_pages``; the size is the contiguous call's for
+    Ncap = max_pages * page_size."""
+    B, H, Hkv, Nq, Ncap, _, dp = _decode_dims(q, k_cache, layout, _max_pages(block_table, max_pages))
     nbytes = _decode_workspace_bytes(B, H, Hkv, Nq, Ncap, dp)
     return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=q.device) if nbytes else None
 
@@ -585,9 +628,9 @@ def _extend_workspace_bytes(B, H, Hkv, Nq, Ncap, dp):
     return _lib.decode().fa_mi355x_extend_workspace_bytes(B, H, Hkv, Nq, Ncap, dp)
 
 
-def extend_workspace(q, k_cache, layout="bnhd"):
+def extend_workspace(q, k_cache, layout="bnhd", block_table=None, max_pages=None):
     """decode_workspace for flash_attn_extend (fa_mi355x_extend_workspace_bytes: the extend call has a split policy of its own)."""
-    B, H, Hkv, Nq, Ncap, _, dp = _decode_dims(q, k_cache, layout)
+    B, H, Hkv, Nq, Ncap, _, dp = _decode_dims(q, k_cache, layout, _max_pages(block_table, max_pages))
     nbytes = _extend_workspace_bytes(B, H, Hkv, Nq, Ncap, dp)
     return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=q.device) if nbytes else None
 
@@ -598,9 +641,10 @@ def _check_seqlens(cache_seqlens, B, device):
         raise ValueError("cache_seqlens must be a contiguous int32 tensor of shape (B,) on q's device")
 
 
-def _check_new(k_new, v_new, k_cache, layout, Nq=None):
+def _check_new(k_new, v_new, k_cache, layout, Nq=None, paged=False):
     """(Nq, d_new) of the new tokens' k_new / v_new, (B, Nq, Hkv, d_new) for "bnhd" or (B, Hkv, Nq, d_new) for "bhnd", checked
-    against the cache they are appended to (and against the caller's Nq, when given)."""
+    against the cache they are appended to (and against the caller's Nq, when given).  ``paged``: the cache is a pool, whose first
+    dimension counts pages (the block table is what B is held against)."""
     if k_new.dim() != 4 or k_new.shape != v_new.shape:
         raise ValueError("k_new and v_new must be 4-d tensors of one shape")
     if k_new.dtype != k_cache.dtype or v_new.dtype != k_cache.dtype:
@@ -609,6 +653,8 @@ def _check_new(k_new, v_new, k_cache, layout, Nq=None):
         (B, n, Hkv, d_new), (Bc, _, Hc, dp) = k_new.shape, k_cache.shape
     else:
         (B, Hkv, n, d_new), (Bc, Hc, _, dp) = k_new.shape, k_cache.shape
+    if paged:
+        Bc = B
     if (B, Hkv) != (Bc, Hc):
         raise ValueError(f"k_new and the cache disagree on (B, Hkv): {(B, Hkv)} vs {(Bc, Hc)}")
     if Nq is not None and n != Nq:
@@ -623,8 +669,8 @@ def _check_new(k_new, v_new, k_cache, layout, Nq=None):
     return n, d_new
 
 
-def _append(who, entry, k_new, v_new, k_cache, v_cache, cache_seqlens, layout):
-    """decode_append / extend_append: the checks, then the library's ``entry``."""
+def _append(who, entry, k_new, v_new, k_cache, v_cache, cache_seqlens, layout, block_table=None):
+    """decode_append / extend_append: the checks, then the library's ``entry`` (its _paged form when there is a block table)."""
     if layout not in _DECODE_LAYOUTS:
         raise ValueError(f"layout must be one of {sorted(_DECODE_LAYOUTS)}")
     if k_cache.dim() != 4 or k_cache.shape != v_cache.shape:
@@ -632,35 +678,45 @@ def _append(who, entry, k_new, v_new, k_cache, v_cache, cache_seqlens, layout):
     if v_cache.dtype != k_cache.dtype:
         raise TypeError("k_cache and v_cache must share one dtype")
     dtype = _dtype_code(k_cache)
-    Nq, d_new = _check_new(k_new, v_new, k_cache, layout)
-    B, dp = k_cache.shape[0], k_cache.shape[3]
+    paged = block_table is not None
+    if paged:
+        num_pages, page_size, _, _ = _pool_dims(k_cache, layout)
+    Nq, d_new = _check_new(k_new, v_new, k_cache, layout, paged=paged)
+    B, dp = k_new.shape[0], k_cache.shape[3]
     Ncap, Hkv = (k_cache.shape[1], k_cache.shape[2]) if layout == "bnhd" else (k_cache.shape[2], k_cache.shape[1])
     _check_seqlens(cache_seqlens, B, k_cache.device)
+    if paged:
+        _check_table(block_table, B, k_cache.device)
     for t in (k_cache, v_cache):
         if t.device != k_cache.device or not t.is_contiguous():
             raise ValueError("k_cache and v_cache must be contiguous and live on one device")
         _require_gpu(t, who)
-    _lib.decode_check(getattr(_lib.decode(), entry)(
-        _ptr(k_new), _ptr(v_new), _ptr(k_cache), _ptr(v_cache), _ptr(cache_seqlens), B, Hkv, Nq, Ncap, d_new, dp,
+    where = (_ptr(block_table), B, Hkv, Nq, num_pages, page_size, block_table.shape[1]) if paged else (B, Hkv, Nq, Ncap)
+    _lib.decode_check(getattr(_lib.decode(), entry + "_paged" * paged)(
+        _ptr(k_new), _ptr(v_new), _ptr(k_cache), _ptr(v_cache), _ptr(cache_seqlens), *where, d_new, dp,
         _DECODE_LAYOUTS[layout], dtype, _stream_ptr()))
 
 
-def decode_append(k_new, v_new, k_cache, v_cache, cache_seqlens=None, layout="bnhd"):
+def decode_append(k_new, v_new, k_cache, v_cache, cache_seqlens=None, layout="bnhd", block_table=None):
     """Write the Nq <= 128 new tokens' k and v into the caches on the device (fa_mi355x_decode_append): k_new, v_new (B, Nq, Hkv,
     d_new) for "bnhd" or (B, Hkv, Nq, d_new) for "bhnd", 1 <= d_new <= dp, into caches (B, Ncap, Hkv, dp) / (B, Hkv, Ncap, dp).
     ``cache_seqlens`` COUNTS the new tokens, as flash_attn_decode reads it: token i goes to row clamp(len_b, 0, Ncap) - Nq + i when
     that is >= 0 (None: the last Nq rows), with zeros in columns d_new .. dp-1; every other row keeps its contents.  k_new and v_new
-    must not alias the caches.  In place, no host synchronisation."""
-    _append("decode_append", "fa_mi355x_decode_append", k_new, v_new, k_cache, v_cache, cache_seqlens, layout)
+    must not alias the caches.  In place, no host synchronisation.  ``block_table`` (int32 (B, max_pages)): the caches are the pools
+    of a paged cache (flash_attn_decode), row r of batch element b is row r % page_size of page block_table[b, r // page_size], and
+    Ncap = max_pages * page_size; a page that two sequences share is written by both (the caller keeps appends off shared pages)."""
+    _append("decode_append", "fa_mi355x_decode_append", k_new, v_new, k_cache, v_cache, cache_seqlens, layout, block_table)
 
 
-def extend_append(k_new, v_new, k_cache, v_cache, cache_seqlens=None, layout="bnhd"):
+def extend_append(k_new, v_new, k_cache, v_cache, cache_seqlens=None, layout="bnhd", block_table=None):
     """decode_append for any number of new tokens (fa_mi355x_extend_append: the same kernel, placement and checks, no bound on Nq)."""
-    _append("extend_append", "fa_mi355x_extend_append", k_new, v_new, k_cache, v_cache, cache_seqlens, layout)
+    _append("extend_append", "fa_mi355x_extend_append", k_new, v_new, k_cache, v_cache, cache_seqlens, layout, block_table)
 
 
-def _cache_attention(who, extend, q, k_cache, v_cache, cache_seqlens, causal, softmax_scale, layout, out, lse, workspace, k_new, v_new):
-    """flash_attn_decode / flash_attn_extend (``extend``): the checks, the head-dim padding, then the library's entry point."""
+def _cache_attention(who, extend, q, k_cache, v_cache, cache_seqlens, causal, softmax_scale, layout, out, lse, workspace, k_new, v_new,
+                     block_table=None):
+    """flash_attn_decode / flash_attn_extend (``extend``): the checks, the head-dim padding, then the library's entry point (its
+    _paged form when there is a block table)."""
     if (k_new is None) != (v_new is None):
         raise ValueError("k_new and v_new go together: give both (fused append) or neither")
     if layout not in _DECODE_LAYOUTS:
@@ -670,12 +726,21 @@ def _cache_attention(who, extend, q, k_cache, v_cache, cache_seqlens, causal, so
         raise TypeError("q, k_cache and v_cache must share one dtype")
     if k_cache.shape != v_cache.shape:
         raise ValueError("k_cache and v_cache must have one shape")
-    B, H, Hkv, Nq, Ncap, d, dp = _decode_dims(q, k_cache, layout)
+    paged = block_table is not None
+    pages = {}
+    if paged:
+        pages = dict(max_pages=_max_pages(block_table, None))
+        num_pages, page_size, _, _ = _pool_dims(k_cache, layout)
+    B, H, Hkv, Nq, Ncap, d, dp = _decode_dims(q, k_cache, layout, **pages)
     if d > dp:
         raise ValueError(f"q's head dim {d} exceeds the cache's row length {dp}")
     _check_seqlens(cache_seqlens, B, q.device)
+    if paged:
+        _check_table(block_table, B, q.device)
     if k_new is not None:
-        _, d_new = _check_new(k_new, v_new, k_cache, layout, Nq)
+        _, d_new = _check_new(k_new, v_new, k_cache, layout, Nq, paged=paged)
+        if k_new.shape[0] != B:
+            raise ValueError(f"k_new holds {k_new.shape[0]} batch elements, q {B}")
     for t in (q, k_cache, v_cache):
         _require_gpu(t, who)
         if t.device != q.device:
@@ -695,11 +760,18 @@ def _cache_attention(who, extend, q, k_cache, v_cache, cache_seqlens, causal, so
     lib = _lib.decode()
     new_ws, ws_bytes = (extend_workspace, _extend_workspace_bytes) if extend else (decode_workspace, _decode_workspace_bytes)
     if workspace is None:
-        workspace = new_ws(qp, k_cache, layout)
+        workspace = new_ws(qp, k_cache, layout, **pages)
     elif workspace.numel() * workspace.element_size() < ws_bytes(B, H, Hkv, Nq, Ncap, dp):
         raise ValueError(f"workspace too small: size it with {new_ws.__name__}()")
     tail = (_DECODE_LAYOUTS[layout], float(softmax_scale), int(bool(causal)), dtype, _stream_ptr())
-    if extend:   # (one grouped form; always the extend kernels, whatever Nq)
+    if paged:   # (one grouped form of each: the contiguous calls' arguments with the table after the lengths and the pool's geometry for Ncap)
+        name = "fa_mi355x_fwd_" + ("extend" if extend else "decode") + ("_append" if k_new is not None else "") + "_paged"
+        new = (_ptr(k_new), _ptr(v_new)) if k_new is not None else ()
+        dims = (d_new, dp) if k_new is not None else (dp,)
+        status = getattr(lib, name)(_ptr(qp), *new, _ptr(k_cache), _ptr(v_cache), _ptr(outp), _ptr(lse), _ptr(cache_seqlens),
+                                    _ptr(block_table), _ptr(workspace), B, H, Hkv, Nq, num_pages, page_size, pages["max_pages"], *dims,
+                                    *tail)
+    elif extend:   # (one grouped form; always the extend kernels, whatever Nq)
         if k_new is not None:
             status = lib.fa_mi355x_fwd_extend_append(_ptr(qp), _ptr(k_new), _ptr(v_new), _ptr(k_cache), _ptr(v_cache), _ptr(outp),
                                                      _ptr(lse), _ptr(cache_seqlens), _ptr(workspace), B, H, Hkv, Nq, Ncap, d_new, dp, *tail)
@@ -719,7 +791,7 @@ def _cache_attention(who, extend, q, k_cache, v_cache, cache_seqlens, causal, so
 
 
 def flash_attn_decode(q, k_cache, v_cache, cache_seqlens=None, causal=True, softmax_scale=None, layout="bnhd", out=None, lse=None,
-                      workspace=None, k_new=None, v_new=None):
+                      workspace=None, k_new=None, v_new=None, block_table=None):
     """Attention of Nq <= 128 new queries against a KV cache (fa_mi355x_fwd_decode / _gqa, include/flash_attn_mi355x_decode.h).
     ``layout`` "bnhd": q (B, Nq, H, d), caches (B, Ncap, Hkv, dp); "bhnd": q (B, H, Nq, d), caches (B, Hkv, Ncap, dp).  Hkv is the
     cache's own head count and must divide H: Hkv < H is a grouped-query (Hkv = 1: multi-query) cache, query head h reads cache head
@@ -729,19 +801,24 @@ def flash_attn_decode(q, k_cache, v_cache, cache_seqlens=None, causal=True, soft
     new tokens (None: all Ncap); clamped to [0, Ncap] on the device, no host synchronisation.  ``causal``: the queries are the last Nq
     positions.  ``k_new``, ``v_new`` (both or neither; shapes and placement as decode_append): the new tokens' k and v, written into
     the caches on the device in front of the attention (fa_mi355x_fwd_decode_append: decode_append, then this call, one library call).
+    ``block_table`` (contiguous int32 (B, max_pages) on q's device): a PAGED cache.  k_cache and v_cache are then the pools,
+    (num_pages, page_size, Hkv, dp) for "bnhd" or (num_pages, Hkv, page_size, dp) for "bhnd" with page_size a multiple of 128, cache
+    row j of batch element b is row j % page_size of page block_table[b, j // page_size], Ncap = max_pages * page_size, and entries
+    past a sequence's last page are never read (fa_mi355x_fwd_decode_paged; ids are clamped to the pool on the device).  The result
+    is bit for bit the contiguous call's on the gathered cache; size a workspace with decode_workspace(..., block_table=).
     Returns (out fp32 in q's shape, lse fp32 (B, H, Nq)): rows with no admissible key give out = 0, lse = -inf."""
     return _cache_attention("flash_attn_decode", False, q, k_cache, v_cache, cache_seqlens, causal, softmax_scale, layout, out, lse,
-                            workspace, k_new, v_new)
+                            workspace, k_new, v_new, block_table)
 
 
 def flash_attn_extend(q, k_cache, v_cache, cache_seqlens=None, causal=True, softmax_scale=None, layout="bnhd", out=None, lse=None,
-                      workspace=None, k_new=None, v_new=None):
+                      workspace=None, k_new=None, v_new=None, block_table=None):
     """flash_attn_decode for ANY number Nq >= 1 of new queries (fa_mi355x_fwd_extend / fa_mi355x_fwd_extend_append): a long input that
     follows a cached prefix, or one piece of a chunked prefill (the same call, from an empty cache on).  Every argument, check, the
     head-dim padding (the default scale keeps the caller's 1/sqrt(d)) and the return value are flash_attn_decode's; ``workspace`` is
     sized by extend_workspace (the extend call has its own split policy), ``k_new`` / ``v_new`` are appended as by extend_append.
     Always the extend kernels, whatever Nq: a workgroup owns 128 rows of a kv head's G * Nq and shares each staged K / V tile among
     them, and a causal call loads no tile above a block's last position.  For Nq <= 128 the result agrees with flash_attn_decode to
-    rounding, not bit for bit."""
+    rounding, not bit for bit.  ``block_table``: a paged cache, as in flash_attn_decode (fa_mi355x_fwd_extend_paged)."""
     return _cache_attention("flash_attn_extend", True, q, k_cache, v_cache, cache_seqlens, causal, softmax_scale, layout, out, lse,
-                            workspace, k_new, v_new)
+                            workspace, k_new, v_new, block_table)

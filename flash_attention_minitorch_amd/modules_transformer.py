@@ -103,20 +103,93 @@ class KVCache:
         self.length_bound = 0   # host-side upper bound of every length: capacity checks without a device synchronisation
         self._workspaces = {}
 
+    block_table = None   # (a PagedKVCache has one)
+
+    def paging(self):
+        """The keyword that makes a device_ops call a paged one: none for this cache, block_table= for a PagedKVCache."""
+        return {} if self.block_table is None else dict(block_table=self.block_table)
+
+    def reserve(self, n_tokens, rows=None):
+        """Make sure the sequences own memory for ``n_tokens`` rows: a slab cache owns its ``capacity`` rows from the start."""
+
     def workspace(self, q):
         key = tuple(q.shape)
         if key not in self._workspaces:
-            self._workspaces[key] = device_ops.decode_workspace(q, self.k[0], "bnhd")
+            self._workspaces[key] = device_ops.decode_workspace(q, self.k[0], "bnhd", **self.paging())
         return self._workspaces[key]
 
     def extend_workspace(self, q):
         key = ("extend",) + tuple(q.shape)   # (the extend call has a split policy of its own: never the decode call's buffer)
         if key not in self._workspaces:
-            self._workspaces[key] = device_ops.extend_workspace(q, self.k[0], "bnhd")
+            self._workspaces[key] = device_ops.extend_workspace(q, self.k[0], "bnhd", **self.paging())
         return self._workspaces[key]
 
     def _pad(self, t):
         return t if self.dp == self.head_dim else device_ops.pad_head_dim(t, self.dp)
+
+
+class PagedKVCache(KVCache):
+    """A KVCache whose memory is handed out by the page: ``k[l]``, ``v[l]`` are per-layer POOLS (n_pages, page_size, n_kv_head, dp) and
+    one ``block_table`` (B, max_pages) int32 on the device, shared by the layers, names the pages of each sequence in order
+    (max_pages = ceil(capacity / page_size); cache row j of sequence b is row j % page_size of page block_table[b, j // page_size]).
+    ``page_size`` is a multiple of 128 rows.  ``n_pages`` defaults to B * max_pages (every sequence can reach ``capacity``) and may be
+    smaller: sequences of different lengths then share what a slab cache would reserve B times over.  The host keeps a free list and
+    each sequence's page list; ``lengths`` and ``length_bound`` are KVCache's.  The stack functions reserve what a call needs and pass
+    ``block_table`` to the same device_ops calls; results are bit for bit those of a KVCache of capacity max_pages * page_size."""
+
+    def __init__(self, n_layers, B, capacity, n_head, head_dim, dtype, device, n_kv_head=None, page_size=128, n_pages=None):
+        self.head_dim, self.dp = head_dim, device_ops.padded_head_dim(head_dim)
+        self.capacity, self.n_head = capacity, n_head
+        self.n_kv_head = n_head if n_kv_head is None else n_kv_head
+        if self.n_kv_head <= 0 or n_head % self.n_kv_head:
+            raise ValueError(f"n_kv_head = {n_kv_head} must divide n_head = {n_head}")
+        if page_size <= 0 or page_size % _lib.FA_PAGE_ROWS:
+            raise ValueError(f"page_size = {page_size} must be a positive multiple of {_lib.FA_PAGE_ROWS} rows")
+        if capacity <= 0:
+            raise ValueError("capacity must be positive")
+        self.page_size, self.max_pages = page_size, -(-capacity // page_size)
+        self.n_pages = B * self.max_pages if n_pages is None else n_pages
+        if self.n_pages <= 0:
+            raise ValueError("n_pages must be positive")
+        shape = (self.n_pages, page_size, self.n_kv_head, self.dp)
+        self.k = [torch.zeros(shape, dtype=dtype, device=device) for _ in range(n_layers)]
+        self.v = [torch.zeros(shape, dtype=dtype, device=device) for _ in range(n_layers)]
+        self.block_table = torch.zeros((B, self.max_pages), dtype=torch.int32, device=device)   # (entries past a sequence's pages: never read)
+        self.lengths = torch.zeros(B, dtype=torch.int32, device=device)
+        self.length_bound = 0
+        self._workspaces = {}
+        self.free = list(range(self.n_pages - 1, -1, -1))   # (handed out from the end: page 0 first)
+        self.pages = [[] for _ in range(B)]                 # the pages of each sequence, in order
+
+    def reserve(self, n_tokens, rows=None):
+        """Make sure the sequences ``rows`` (default all) own pages for ``n_tokens`` cache rows each.  New pages come from the free list
+        and only the table rows that changed are written to the device, in place (the table's address never changes: a captured
+        graph keeps reading it).  Nothing is launched when every sequence already owns enough.  RuntimeError, naming the shortfall and
+        with nothing handed out, when the pool runs out."""
+        if n_tokens > self.max_pages * self.page_size:
+            raise ValueError(f"{n_tokens} rows exceed the table's {self.max_pages} pages of {self.page_size}")
+        need = -(-n_tokens // self.page_size)
+        rows = range(len(self.pages)) if rows is None else list(rows)
+        missing = sum(max(0, need - len(self.pages[b])) for b in rows)
+        if missing > len(self.free):
+            raise RuntimeError(f"page pool exhausted: {missing} more pages needed for {n_tokens} rows per sequence, {len(self.free)} of "
+                               f"{self.n_pages} free ({missing - len(self.free)} short)")
+        for b in rows:
+            own = self.pages[b]
+            if len(own) >= need:
+                continue
+            while len(own) < need:
+                own.append(self.free.pop())
+            row = own + [0] * (self.max_pages - len(own))
+            self.block_table[b].copy_(torch.tensor(row, dtype=torch.int32))
+
+    def release(self, b):
+        """Sequence b is finished: its pages go back to the free list (the next reserve hands them out again) and its length to 0.
+        Its table row keeps its stale entries, which a sequence of length 0 never reads.  ``length_bound`` stays the bound of the
+        others."""
+        self.free.extend(reversed(self.pages[b]))
+        self.pages[b] = []
+        self.lengths[b] = 0
 
 
 def _project(x, wq, wk, wv, n_head):
@@ -143,12 +216,18 @@ def attention_stack_prefill(x, layers, n_head: int, cache: KVCache):
     if P > cache.capacity:
         raise ValueError(f"prompt of {P} tokens exceeds the cache capacity {cache.capacity}")
     d = E // n_head
+    if cache.block_table is not None:
+        cache.reserve(P)
+        cache.lengths.fill_(P)   # (the paged append places the prompt by the lengths)
     for li, (wq, wk, wv, wo) in enumerate(layers):
         q, k, v = _project(x, wq, wk, wv, n_head)
         _check_kv_heads(k, cache)
         kp, vp = cache._pad(k), cache._pad(v)
-        cache.k[li][:, :P] = kp
-        cache.v[li][:, :P] = vp
+        if cache.block_table is None:
+            cache.k[li][:, :P] = kp
+            cache.v[li][:, :P] = vp
+        else:   # rows lengths[b] - P .. lengths[b] - 1 = 0 .. P - 1 of every sequence's pages (zero columns past head_dim)
+            device_ops.extend_append(k, v, cache.k[li], cache.v[li], cache.lengths, "bnhd", **cache.paging())
         # (a grouped-query stack: the kernels read the Hkv heads in place)
         fwd = device_ops.flash_attn_fwd_bnhd if cache.n_kv_head == n_head else device_ops.flash_attn_fwd_gqa
         if cache.dp == d:
@@ -168,6 +247,10 @@ def _step(x_new, layers, n_head: int, cache: KVCache, fused: bool):
         raise ValueError(f"a step takes at most {MAX_STEP_TOKENS} tokens; use attention_stack_prefill for longer inputs")
     if cache.length_bound + T > cache.capacity:
         raise ValueError(f"cache capacity {cache.capacity} exceeded")
+    if not fused and cache.block_table is not None:
+        raise ValueError("attention_stack_step appends with torch indexing into a slab: a PagedKVCache steps through "
+                         "attention_stack_step_fused")
+    cache.reserve(cache.length_bound + T)
     dev = x_new.device
     if not fused:
         # rows b * capacity + lengths[b] + t of the (B * capacity, Hkv, dp) view of a layer's cache: the new tokens' k and v
@@ -186,7 +269,7 @@ def _step(x_new, layers, n_head: int, cache: KVCache, fused: bool):
             for dst, t in ((cache.k[li], k), (cache.v[li], v)):
                 dst.view(B * cache.capacity, hkv, cache.dp).index_copy_(0, rows, cache._pad(t).reshape(B * T, hkv, cache.dp))
         o, _ = device_ops.flash_attn_decode(q, cache.k[li], cache.v[li], new_len, causal=True, layout="bnhd",
-                                            workspace=cache.workspace(q), **new)
+                                            workspace=cache.workspace(q), **new, **cache.paging())
         x = x + (o.reshape(B * T, E).to(x.dtype) @ wo).view(B, T, E)
     cache.lengths.copy_(new_len)
     cache.length_bound += T
@@ -222,13 +305,14 @@ def attention_stack_extend(x_new, layers, n_head: int, cache: KVCache):
         return attention_stack_step_fused(x_new, layers, n_head, cache)
     if cache.length_bound + T > cache.capacity:
         raise ValueError(f"cache capacity {cache.capacity} exceeded")
+    cache.reserve(cache.length_bound + T)
     new_len = cache.lengths + T
     x = x_new
     for li, (wq, wk, wv, wo) in enumerate(layers):
         q, k, v = _project(x, wq, wk, wv, n_head)
         _check_kv_heads(k, cache)
         o, _ = device_ops.flash_attn_extend(q, cache.k[li], cache.v[li], new_len, causal=True, layout="bnhd",
-                                            workspace=cache.extend_workspace(q), k_new=k, v_new=v)
+                                            workspace=cache.extend_workspace(q), k_new=k, v_new=v, **cache.paging())
         x = x + (o.reshape(B * T, E).to(x.dtype) @ wo).view(B, T, E)
     cache.lengths.copy_(new_len)
     cache.length_bound += T
@@ -286,6 +370,8 @@ class GraphedStep:
             raise ValueError(f"this graph steps {self.T} tokens at a time, got {T}")
         if self.cache.length_bound + T > self.cache.capacity:
             raise ValueError(f"cache capacity {self.cache.capacity} exceeded")
+        # (a paged cache: the pages of this step, outside the graph; the table is edited in place, so the graph reads the new entries)
+        self.cache.reserve(self.cache.length_bound + T)
         if self.graph is None:
             self._capture(x_new)
         elif x_new.shape != self.x.shape or x_new.dtype != self.x.dtype:

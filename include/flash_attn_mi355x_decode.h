@@ -144,4 +144,9 @@ const char* fa_mi355x_decode_last_error(void);
 #ifdef __cplusplus
 }
 #endif
+
+/* Paged KV caches (a pool of pages and a block table instead of one slab per sequence): the six _paged forms of the entry points
+ * above, part of this library and of this header, kept in a file of their own. */
+#include "flash_attn_mi355x_decode_paged.h"
+
 #endif /* FLASH_ATTN_MI355X_DECODE_H */
