@@ -136,6 +136,18 @@ PAGED_ABI = {
     "fa_mi355x_fwd_extend_append_paged": (_i, [_vp] * 10 + [_i] * 10 + [_f, _i, _i, _vp]),
 }
 
+# the same for include/flash_attn_mi355x_decode_ragged.h (the ragged-batch forms of the same library; tests/test_ragged_cpu.py)
+RAGGED_ABI = {
+    "fa_mi355x_ragged_splits": (_i, [_i] * 7),
+    "fa_mi355x_ragged_workspace_bytes": (_sz, [_i] * 6),
+    "fa_mi355x_fwd_ragged": (_i, [_vp] * 8 + [_i] * 7 + [_f, _i, _i, _vp]),
+    "fa_mi355x_ragged_append": (_i, [_vp] * 6 + [_i] * 8 + [_vp]),
+    "fa_mi355x_fwd_ragged_append": (_i, [_vp] * 10 + [_i] * 8 + [_f, _i, _i, _vp]),
+    "fa_mi355x_fwd_ragged_paged": (_i, [_vp] * 9 + [_i] * 9 + [_f, _i, _i, _vp]),
+    "fa_mi355x_ragged_append_paged": (_i, [_vp] * 7 + [_i] * 10 + [_vp]),
+    "fa_mi355x_fwd_ragged_append_paged": (_i, [_vp] * 11 + [_i] * 10 + [_f, _i, _i, _vp]),
+}
+
 
 def _typed(name: str, abi: dict) -> ctypes.CDLL:
     """The library with restype / argtypes of every symbol in ``abi`` set (once, on first load)."""
@@ -204,8 +216,8 @@ DECODE_NAME = "libflash_attn_mi355x_decode.so"
 
 
 def decode() -> ctypes.CDLL:
-    """libflash_attn_mi355x_decode.so (include/flash_attn_mi355x_decode.h and its _paged.h) with argtypes set."""
-    return _typed(DECODE_NAME, {**DECODE_ABI, **PAGED_ABI})
+    """libflash_attn_mi355x_decode.so (include/flash_attn_mi355x_decode.h, its _paged.h and its _ragged.h) with argtypes set."""
+    return _typed(DECODE_NAME, {**DECODE_ABI, **PAGED_ABI, **RAGGED_ABI})
 
 
 def decode_check(status: int) -> None:

@@ -33,6 +33,14 @@
 // wave-uniform table entry and one resource per super tile (PageWalk), and the tile loop, the LDS image and the MFMA work are those
 // of the contiguous builds, which is why a paged call returns the contiguous call's bits on the gathered cache.  The PAGED = false
 // builds are the code they were (same registers, LDS and instructions: DESIGN.md "Paged").
+//
+// Ragged batches (the RAGGED builds of the extend, combine and append kernels; include/flash_attn_mi355x_decode_ragged.h): the new
+// tokens of all sequences are PACKED into buffers of T rows, [T][H][d], and cu[b] .. cu[b+1] - 1 are the rows of sequence b, so every
+// sequence brings its own number nq_b of new tokens.  ragged_schedule_kernel turns cu into a block map in front of the attention:
+// one entry (sequence, row block in it) per 128-row block of a sequence's G * nq_b rows, so a row block never straddles two sequences
+// and a workgroup of the extend kernel reads its entry, then its sequence's first packed row and nq_b, and is from there on the
+// uniform build with nq_b for Nq.  All of these are wave-uniform (readfirstlane): the resources stay in SGPRs.  Outputs, lse and the
+// partials are indexed by packed row.  The RAGGED = false builds are the code they were (DESIGN.md "Ragged").
 #pragma once
 #include "fa_common.h"
 
@@ -61,12 +69,29 @@ struct DecodeArgs {
   long page_stride;    // elements between consecutive pages: page_size * Hkv * D
 };
 
+// The argument of the ragged builds (a type of its own: the other builds keep the kernel argument they had).  Nq = ntok: the combine
+// kernel sees one batch element of ntok queries; nqb = entries of the block map; items = Hkv * nsplit; q is token-major: q_ld =
+// H * D, q_hstride = D.
+struct RaggedArgs : DecodeArgs {
+  const int* cu;       // [nseq + 1] boundaries of the sequences in the packed buffers
+  const int* map;      // [nqb][2] (sequence or -1: unused, row block within the sequence), written by ragged_schedule_kernel
+  int nseq, ntok;      // sequences; rows of the packed buffers
+};
+template <bool RAGGED> using DecodeArgsOf = typename std::conditional<RAGGED, RaggedArgs, DecodeArgs>::type;
+
 FA_DEV int clamp_len(const int* seqlens, int Ncap, int b) {
   const int len = seqlens ? seqlens[b] : Ncap;
   return min(max(len, 0), Ncap);
 }
 
 FA_DEV int clamp_len(const DecodeArgs& a, int b) { return clamp_len(a.seqlens, a.Ncap, b); }
+
+// Ragged: sequence b owns the packed rows s .. s + nq - 1, s = clamp(cu[b], 0, ntok) and s + nq = clamp(cu[b+1], s, ntok): whatever
+// the array holds, no row leaves the ntok-row buffers.  nq may be 0.
+FA_DEV void seq_rows(const int* cu, int ntok, int b, int& s, int& nq) {
+  s = min(max(cu[b], 0), ntok);
+  nq = min(max(cu[b + 1], s), ntok) - s;
+}
 
 // rho / G for a row index 0 <= rho < 2^25 without the integer division's long dependent chain in front of the workgroup's first
 // loads: the float quotient is off by at most one, which the remainder corrects.  (G = 1: exact at once.)
@@ -324,8 +349,10 @@ __global__ void __launch_bounds__(256) decode_split_kernel(DecodeArgs a) {
 // only those that straddle pos_lo .. pos_hi.  A wave whose rows are all >= G * Nq stages, meets the barriers and stores nothing.
 constexpr int EXT_BLOCK = 128;   // rows per workgroup: 32 per wave
 
-template <typename T, int D, bool PAGED = false>
-__global__ void __launch_bounds__(256) extend_split_kernel(DecodeArgs a) {
+// RAGGED: the row block is entry `slot % nqb` of the block map, which names its sequence b and its block qb within b's G * nq_b
+// rows; the items are (kv head, split) alone.  nq_ below is nq_b, row0 the sequence's first packed row.
+template <typename T, int D, bool PAGED = false, bool RAGGED = false>
+__global__ void __launch_bounds__(256) extend_split_kernel(DecodeArgsOf<RAGGED> a) {
   using A = Atom<T>;
   typedef typename A::frag frag;
   constexpr int KC = D / 16, DT = D / 32;
@@ -336,22 +363,36 @@ __global__ void __launch_bounds__(256) extend_split_kernel(DecodeArgs a) {
 
   // workgroup -> (item, row block) as in decode_split_kernel: the row blocks of one item share an XCD's L2
   const int id = blockIdx.x, slot = id >> 3;
-  const int qb = slot % a.nqb, item = (slot / a.nqb) * 8 + (id & 7);
+  const int entry = slot % a.nqb, item = (slot / a.nqb) * 8 + (id & 7);
   if (item >= a.items) return;
   const int bh = item / a.nsplit, split = item - bh * a.nsplit;
-  const int b = bh / a.Hkv, hkv = bh - b * a.Hkv;
+  int b_ = bh / a.Hkv, hkv_ = bh - b_ * a.Hkv, qb_ = entry, row0_ = 0, nq_ = 0;
+  if constexpr (RAGGED) {
+    b_ = __builtin_amdgcn_readfirstlane(a.map[2 * entry]);
+    if (b_ < 0) return;   // (an unused entry: the map is sized for the worst case)
+    qb_ = __builtin_amdgcn_readfirstlane(a.map[2 * entry + 1]);
+    hkv_ = bh;
+    seq_rows(a.cu, a.ntok, b_, row0_, nq_);
+    row0_ = __builtin_amdgcn_readfirstlane(row0_);
+    nq_ = __builtin_amdgcn_readfirstlane(nq_);
+  }
+  const int b = b_, hkv = hkv_, qb = qb_, row0 = row0_;
+  // The sequence's own count, or the call's.  A macro, not a local `const int Nq`: a local reads a.Nq once at the top of the uniform
+  // build, which moved two of its fp32 builds from 58 to 59 SGPRs; with a.Nq read where it always was, the uniform builds compile to
+  // the code they were (DESIGN.md "Ragged").  Do not fold it into a variable without comparing the resource report.
+#define FA_NQ (RAGGED ? nq_ : a.Nq)
   const int len = __builtin_amdgcn_readfirstlane(clamp_len(a, b));
   const int c0 = split * a.chunk, c1 = min(c0 + a.chunk, len);
 
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int rows = a.G * a.Nq;
+  const int rows = a.G * FA_NQ;
   const int q0 = qb * EXT_BLOCK + 32 * w, rho = q0 + r, qi = row_query(a, rho), hd = hkv * a.G + (rho - qi * a.G);
   const bool live = rho < rows;
   const bool wave_live = q0 < rows;   // (wave-uniform)
   const float c = a.tau * LOG2E;
   // causal: the last key any row of the block sees is the position of its last row (of its last REAL row: rows >= G * Nq see nothing)
-  const int blk_hi = len - a.Nq + row_query(a, min(qb * EXT_BLOCK + EXT_BLOCK, rows) - 1);
+  const int blk_hi = len - FA_NQ + row_query(a, min(qb * EXT_BLOCK + EXT_BLOCK, rows) - 1);
   const int cend = a.causal ? min(c1, blk_hi + 1) : c1;
 
   f32x16 acc_o[DT];
@@ -362,8 +403,9 @@ __global__ void __launch_bounds__(256) extend_split_kernel(DecodeArgs a) {
   if (c0 < cend) {   // (a chunk past len_b, or past every position of the block, loads nothing and leaves m = -inf, l = 0)
     const size_t kvoff = (PAGED ? 0 : (size_t)b * a.kv_bstride) + (size_t)hkv * a.kv_hstride;   // (paged: inside a page)
     const uint32_t esz = sizeof(T);
-    const uint32_t q_bytes = (uint32_t)a.q_bstride * esz;
-    const rsrc_t qrs = make_rsrc(reinterpret_cast<const T*>(a.q) + (size_t)b * a.q_bstride, q_bytes);
+    // (ragged: the resource of the sequence's own nq_b * H * D elements of the packed q)
+    const uint32_t q_bytes = RAGGED ? (uint32_t)nq_ * (uint32_t)a.q_ld * esz : (uint32_t)a.q_bstride * esz;
+    const rsrc_t qrs = make_rsrc(reinterpret_cast<const T*>(a.q) + (RAGGED ? (size_t)row0 * a.q_ld : (size_t)b * a.q_bstride), q_bytes);
     const uint32_t kv_bytes = ((uint32_t)(len - 1) * a.kv_ld + D) * esz;
     const rsrc_t krs = make_rsrc(reinterpret_cast<const T*>(a.k) + kvoff, kv_bytes);   // (the slab's: unused by a paged build)
     const rsrc_t vrs = make_rsrc(reinterpret_cast<const T*>(a.v) + kvoff, kv_bytes);
@@ -381,8 +423,8 @@ __global__ void __launch_bounds__(256) extend_split_kernel(DecodeArgs a) {
     sv.init(tid, a.kv_ld);
     // the wave's rows span the positions pos_lo .. pos_hi (wave-uniform; rows past G * Nq may push pos_hi up, which only keeps a
     // sub-tile that masks to nothing for the real rows' lanes)
-    const int qpos = len - a.Nq + qi;
-    const int pos_lo = len - a.Nq + row_query(a, q0), pos_hi = len - a.Nq + row_query(a, q0 + 31);
+    const int qpos = len - FA_NQ + qi;
+    const int pos_lo = len - FA_NQ + row_query(a, q0), pos_hi = len - FA_NQ + row_query(a, q0 + 31);
     if constexpr (PAGED) {
       pw.init(a, b, c0);
       pw.template load<T, D>(a, sk, sv, kvoff, len, c0 + DEC_ROWS < cend);
@@ -454,10 +496,11 @@ __global__ void __launch_bounds__(256) extend_split_kernel(DecodeArgs a) {
   }
   const float l_tot = xhalf_sum(l_run);
   if (!live) return;   // (no barrier follows)
-  const size_t bhq = (size_t)b * a.H + hd;
+  // (ragged: out, lse and the partials by packed row row0 + qi, as one batch element of a.Nq = ntok queries)
+  const size_t bhq = RAGGED ? (size_t)hd : (size_t)b * a.H + hd;
   if (a.nsplit == 1) {   // final: out = O / l, lse = m * tau + ln l; a row without an admissible key: out = 0, lse = -inf
     const float inv = (l_tot > 0.f) ? 1.0f / l_tot : 0.f;
-    float* orow = a.out + (size_t)b * a.q_bstride + (size_t)hd * a.q_hstride + (size_t)qi * a.q_ld;
+    float* orow = a.out + (RAGGED ? 0 : (size_t)b * a.q_bstride) + (size_t)hd * a.q_hstride + (size_t)(RAGGED ? row0 + qi : qi) * a.q_ld;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
@@ -465,9 +508,9 @@ __global__ void __launch_bounds__(256) extend_split_kernel(DecodeArgs a) {
         f32x4 val = {acc_o[dt][4 * g] * inv, acc_o[dt][4 * g + 1] * inv, acc_o[dt][4 * g + 2] * inv, acc_o[dt][4 * g + 3] * inv};
         *reinterpret_cast<f32x4*>(orow + 32 * dt + 8 * g + 4 * h) = val;
       }
-    if (h == 0 && a.lse) a.lse[bhq * a.Nq + qi] = (l_tot > 0.f) ? m_run * a.tau + __logf(l_tot) : -INFINITY;
+    if (h == 0 && a.lse) a.lse[bhq * a.Nq + (RAGGED ? row0 + qi : qi)] = (l_tot > 0.f) ? m_run * a.tau + __logf(l_tot) : -INFINITY;
   } else {
-    const size_t pr = (bhq * a.nsplit + split) * a.Nq + qi;
+    const size_t pr = (bhq * a.nsplit + split) * a.Nq + (RAGGED ? row0 + qi : qi);
     float* prow = a.part_o + pr * D;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt)
@@ -479,17 +522,27 @@ __global__ void __launch_bounds__(256) extend_split_kernel(DecodeArgs a) {
     if (h == 0) *reinterpret_cast<f32x2*>(a.part_ml + 2 * pr) = f32x2{m_run, l_tot};
   }
 }
+#undef FA_NQ
 
 // out[row] = sum_s O_s 2^(c (m_s - M)) / sum_s l_s 2^(c (m_s - M)), M = max_s m_s.  A workgroup = one (bh, row): thread (g, j) takes
 // columns 4g .. 4g+3 of the splits j, j + S, j + 2S, ... and the S partial sums of a column group are added in the order j = 0 .. S-1
 // (a fixed order: bitwise repeatable).
-template <int D>
-__global__ void __launch_bounds__(256) decode_combine_kernel(DecodeArgs a) {
+// RAGGED: one batch element of Nq = ntok packed rows; a row in front of the first sequence or behind the last one (the unused tail
+// of the packed buffers) has no partials and is neither read nor written.  (A cu that is not non-decreasing can make an earlier
+// sequence end past the last one's end: its rows there are then left as they were, where a one-split call writes them.)
+template <int D, bool RAGGED = false>
+__global__ void __launch_bounds__(256) decode_combine_kernel(DecodeArgsOf<RAGGED> a) {
   constexpr int G = D / 4, S = 256 / G;
   __shared__ f32x4 red_o[256];
   __shared__ float red_m[256], red_l[256];
   const int tid = threadIdx.x, g = tid % G, j = tid / G;
   const int row = blockIdx.x % a.Nq, bh = blockIdx.x / a.Nq;
+  if constexpr (RAGGED) {   // (workgroup-uniform: in front of the barriers)
+    int s0, n0, sl, nl;
+    seq_rows(a.cu, a.ntok, 0, s0, n0);
+    seq_rows(a.cu, a.ntok, a.nseq - 1, sl, nl);
+    if (row < s0 || row >= sl + nl) return;
+  }
   const int b = bh / a.H, hd = bh - b * a.H;
   const float c = a.tau * LOG2E;
   const size_t p0 = (size_t)bh * a.nsplit * a.Nq + row;   // partial row of split s: p0 + s * Nq
@@ -525,6 +578,41 @@ __global__ void __launch_bounds__(256) decode_combine_kernel(DecodeArgs a) {
   if (g == 0 && a.lse) a.lse[(size_t)bh * a.Nq + row] = (l > 0.f) ? m_all * a.tau + __logf(l) : -INFINITY;
 }
 
+// ---- ragged: the block map -------------------------------------------------------------------------------------------------------
+// One workgroup turns cu into the block map of the ragged extend kernel: for b = 0, 1, ... in order, one entry (b, qb) for each of
+// the ceil(G * nq_b / 128) row blocks of sequence b (none for nq_b = 0), then (-1, 0) up to the map's `cap` entries.  For a cu that
+// is non-decreasing the blocks number at most floor(G * ntok / 128) + min(nseq, ntok) = cap (every non-empty sequence rounds up at
+// most once); for any other cu the counts saturate at cap and the entries past it are dropped, so the map is never overrun.
+// Thread t takes the sequences t * per .. t * per + per - 1: its block count, an exclusive prefix over the 256 counts in LDS, then
+// its entries.  Integer work in a fixed order: the map is a function of cu alone.  The map is written as int pairs (8 bytes) at the
+// workspace's base and the partials behind it as 16-byte vectors: the workspace is 16-byte aligned (the header says so).
+__global__ void __launch_bounds__(256) ragged_schedule_kernel(const int* cu, int* map, int nseq, int ntok, int G, int cap) {
+  __shared__ int counts[256];
+  const int tid = threadIdx.x;
+  const int per = (int)(((long)nseq + 255) / 256);
+  const int b0 = (int)min((long)tid * per, (long)nseq), b1 = (int)min((long)b0 + per, (long)nseq);
+  int n = 0;
+  for (int b = b0; b < b1; ++b) {
+    int s, nq;
+    seq_rows(cu, ntok, b, s, nq);
+    n = min(n + (G * nq + EXT_BLOCK - 1) / EXT_BLOCK, cap);
+  }
+  counts[tid] = n;
+  __syncthreads();
+  int off = 0, total = 0;
+  for (int u = 0; u < 256; ++u) {
+    if (u == tid) off = total;
+    total = min(total + counts[u], cap);
+  }
+  for (int b = b0; b < b1; ++b) {
+    int s, nq;
+    seq_rows(cu, ntok, b, s, nq);
+    const int nb = (G * nq + EXT_BLOCK - 1) / EXT_BLOCK;
+    for (int qb = 0; qb < nb && off < cap; ++qb, ++off) *reinterpret_cast<int2*>(map + 2 * (size_t)off) = make_int2(b, qb);
+  }
+  for (int i = total + tid; i < cap; i += 256) *reinterpret_cast<int2*>(map + 2 * (size_t)i) = make_int2(-1, 0);
+}
+
 // ---- append: the new tokens' k and v into the caches ------------------------------------------------------------------------------
 // k_new / v_new hold rows of d_new <= D elements, [B][Nq][Hkv] (bnhd) or [B][Hkv][Nq] of them, contiguous.  With L_b = len_b clamped
 // to [0, Ncap] (the length COUNTS the new tokens, as the split kernel reads it), token i goes to cache row L_b - Nq + i: the position
@@ -547,12 +635,21 @@ struct AppendArgs {
   long page_stride;
 };
 
+// The argument of the ragged builds, as RaggedArgs: k_new / v_new are [ntok][Hkv][d_new] and lanes = ntok * Hkv * (D / E).
+struct RaggedAppendArgs : AppendArgs {
+  const int* cu;
+  int nseq, ntok;
+};
+
 // A lane = E consecutive elements of one new row, of K and of V: E = 16 bytes' worth (one vector load and store each; the host picks
 // it when d_new * sizeof(T) is a multiple of 16 and all four pointers are 16-byte aligned) or E = 1.  Consecutive lanes walk the
 // source in memory order.  The elements are copied as bits; the cache's row length D (a power of two) is a run-time argument.
 // PAGED: row pos is row pos % page_size of page table[b][pos / page_size], the id clamped to the pool as the split kernels do.
-template <typename T, int E, bool PAGED = false>
-__global__ void __launch_bounds__(256) decode_append_kernel(AppendArgs a) {
+// RAGGED: the source is packed, row (t, hkv); the lane finds the sequence that owns packed row t by a binary search of cu (the first
+// b whose clamped end is above t) and places token i = t - s_b of nq_b as above.  A row that no sequence owns (in front of the first
+// one, or the unused tail) is not copied.
+template <typename T, int E, bool PAGED = false, bool RAGGED = false>
+__global__ void __launch_bounds__(256) decode_append_kernel(typename std::conditional<RAGGED, RaggedAppendArgs, AppendArgs>::type a) {
   typedef typename std::conditional<sizeof(T) == 2, uint16_t, uint32_t>::type U;
   typedef __attribute__((ext_vector_type(E))) U vec;
   static_assert(E == 1 || E * sizeof(T) == 16, "a lane moves one element or 16 bytes");
@@ -560,13 +657,33 @@ __global__ void __launch_bounds__(256) decode_append_kernel(AppendArgs a) {
   if (lane >= a.lanes) return;
   const long row = lane >> a.ch_shift;           // source row (b, i, hkv) or (b, hkv, i)
   const int col = (int)(lane - (row << a.ch_shift)) * E;
-  const int inner = a.bnhd ? a.Hkv : a.Nq;
-  const long outer = row / inner;
-  const int in = (int)(row - outer * inner);
-  const int mid = a.bnhd ? a.Nq : a.Hkv;
-  const int b = (int)(outer / mid), md = (int)(outer - (long)b * mid);
-  const int i = a.bnhd ? md : in, hkv = a.bnhd ? in : md;
-  const int pos = clamp_len(a.seqlens, a.Ncap, b) - a.Nq + i;
+  int b_, i_, hkv_, nq_ = a.Nq;
+  if constexpr (RAGGED) {
+    const int t = (int)(row / a.Hkv);
+    hkv_ = (int)(row - (long)t * a.Hkv);
+    int lo = 0, hi = a.nseq;   // the first b in [0, nseq) with clamp(cu[b + 1]) > t, or nseq: none
+    while (lo < hi) {
+      const int mid = lo + ((hi - lo) >> 1);
+      if (min(max(a.cu[mid + 1], 0), a.ntok) > t) hi = mid; else lo = mid + 1;
+    }
+    if (lo == a.nseq) return;
+    int s;
+    seq_rows(a.cu, a.ntok, lo, s, nq_);
+    if (t < s || t >= s + nq_) return;
+    b_ = lo;
+    i_ = t - s;
+  } else {
+    const int inner = a.bnhd ? a.Hkv : a.Nq;
+    const long outer = row / inner;
+    const int in = (int)(row - outer * inner);
+    const int mid = a.bnhd ? a.Nq : a.Hkv;
+    b_ = (int)(outer / mid);
+    const int md = (int)(outer - (long)b_ * mid);
+    i_ = a.bnhd ? md : in;
+    hkv_ = a.bnhd ? in : md;
+  }
+  const int b = b_, i = i_, hkv = hkv_;
+  const int pos = clamp_len(a.seqlens, a.Ncap, b) - nq_ + i;
   if (pos < 0) return;
   const size_t src = (size_t)row * a.d_new + col;
   size_t dst;

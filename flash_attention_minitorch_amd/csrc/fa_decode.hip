@@ -1,6 +1,7 @@
-// C ABI of the MI355X KV-cache decode library (declared in include/flash_attn_mi355x_decode.h and its _paged.h): argument checks,
-// the split policies (decode: 32-row blocks, at most 128 queries; extend: 128-row blocks, any number) and the launches of the kernels
-// of fa_decode.h.  A paged call (a pool and a block table) takes the contiguous call's policy at Ncap = max_pages * page_size.
+// C ABI of the MI355X KV-cache decode library (declared in include/flash_attn_mi355x_decode.h, its _paged.h and its _ragged.h):
+// argument checks, the split policies (decode: 32-row blocks, at most 128 queries; extend: 128-row blocks, any number; ragged: the
+// extend policy on an upper bound of the row blocks) and the launches of the kernels of fa_decode.h.  A paged call (a pool and a
+// block table) takes the contiguous call's policy at Ncap = max_pages * page_size.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -58,12 +59,13 @@ size_t workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int d) {
 constexpr int EXT_WAVES = 2;
 int ext_row_blocks(int H, int Hkv, int Nq) { return (int)(((long)(H / Hkv) * Nq + fa::EXT_BLOCK - 1) / fa::EXT_BLOCK); }
 
-int ext_chunk_keys(int B, int H, int Hkv, int Nq, int Ncap) {
-  const long groups = (long)B * Hkv * ext_row_blocks(H, Hkv, Nq);
+int ext_chunk_for(long groups, int Ncap) {
   const long want = std::max(1L, (DEC_CUS * EXT_WAVES + groups - 1) / groups);
   const long per = (Ncap + want - 1) / want;
   return (int)std::max((long)DEC_MIN_CHUNK, (per + DEC_MIN_CHUNK - 1) / DEC_MIN_CHUNK * DEC_MIN_CHUNK);
 }
+
+int ext_chunk_keys(int B, int H, int Hkv, int Nq, int Ncap) { return ext_chunk_for((long)B * Hkv * ext_row_blocks(H, Hkv, Nq), Ncap); }
 
 int ext_splits(int B, int H, int Hkv, int Nq, int Ncap) {
   const int ch = ext_chunk_keys(B, H, Hkv, Nq, Ncap);
@@ -76,7 +78,26 @@ size_t ext_workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int d) {
 }
 
 // workgroups of the split launch: the items rounded up to 8, times the row blocks (the kernels' workgroup -> (item, row block) map)
-long split_grid(long items, int nqb) { return (items + 7) / 8 * 8 * nqb; }
+long split_grid(long items, long nqb) { return (items + 7) / 8 * 8 * nqb; }
+
+// Ragged policy: the extend policy on what the ARGUMENTS say about the row blocks, never the device arrays: a sequence's G * nq_b rows
+// round up to 128 at most once, so B sequences that share T packed rows have at most floor(G * T / 128) + min(B, T) row blocks.  That
+// bound sizes the block map and the grid and stands for the row blocks in the policy, so the split count, the workspace and a
+// captured graph do not depend on cu_seqlens_q.  (It under-splits a step whose tokens all sit in one of many sequences.)
+long rag_blocks(int B, int H, int Hkv, int T) { return (long)(H / Hkv) * T / fa::EXT_BLOCK + std::min(B, T); }
+int rag_chunk_keys(int B, int H, int Hkv, int T, int Ncap) { return ext_chunk_for((long)Hkv * rag_blocks(B, H, Hkv, T), Ncap); }
+
+int rag_splits(int B, int H, int Hkv, int T, int Ncap) {
+  const int ch = rag_chunk_keys(B, H, Hkv, T, Ncap);
+  return (int)(((long)Ncap + ch - 1) / ch);
+}
+
+// the workspace: the block map ((sequence, block) int pairs, rounded up to 16 bytes), then the partials of H * ns * T rows
+size_t rag_map_bytes(int B, int H, int Hkv, int T) { return ((size_t)rag_blocks(B, H, Hkv, T) * 2 * sizeof(int) + 15) / 16 * 16; }
+
+size_t rag_workspace_bytes(int B, int H, int Hkv, int T, int Ncap, int d) {
+  return rag_map_bytes(B, H, Hkv, T) + (size_t)H * rag_splits(B, H, Hkv, T, Ncap) * T * (size_t)(d + 2) * sizeof(float);
+}
 
 template <typename T, int D> int launch_extend(fa::DecodeArgs a, int BH, hipStream_t st) {
   if (a.table)
@@ -272,31 +293,39 @@ int check_append(const void* k_new, const void* v_new, const void* k_cache, cons
   return FA_OK;
 }
 
-template <typename T, int E> int launch_append(fa::AppendArgs a, int d, hipStream_t st) {
+template <typename T, int E> int launch_append(fa::RaggedAppendArgs a, int d, hipStream_t st) {
   a.ch_shift = __builtin_ctz(d / E);
   a.lanes <<= a.ch_shift;   // (rows on entry)
-  if (a.table)
-    hipLaunchKernelGGL((fa::decode_append_kernel<T, E, true>), dim3((unsigned)((a.lanes + 255) / 256)), dim3(256), 0, st, a);
+  const dim3 grid((unsigned)((a.lanes + 255) / 256));
+  if (a.cu && a.table)
+    hipLaunchKernelGGL((fa::decode_append_kernel<T, E, true, true>), grid, dim3(256), 0, st, a);
+  else if (a.cu)
+    hipLaunchKernelGGL((fa::decode_append_kernel<T, E, false, true>), grid, dim3(256), 0, st, a);
+  else if (a.table)
+    hipLaunchKernelGGL((fa::decode_append_kernel<T, E, true>), grid, dim3(256), 0, st, static_cast<const fa::AppendArgs&>(a));
   else
-    hipLaunchKernelGGL((fa::decode_append_kernel<T, E>), dim3((unsigned)((a.lanes + 255) / 256)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL((fa::decode_append_kernel<T, E>), grid, dim3(256), 0, st, static_cast<const fa::AppendArgs&>(a));
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? FA_OK : set_err(FA_ERR_HIP, "decode_append_kernel launch", e);
 }
 
-template <typename T> int launch_append_e(const fa::AppendArgs& a, int d, bool vec, hipStream_t st) {
+template <typename T> int launch_append_e(const fa::RaggedAppendArgs& a, int d, bool vec, hipStream_t st) {
   return vec ? launch_append<T, 16 / sizeof(T)>(a, d, st) : launch_append<T, 1>(a, d, st);
 }
 
-// The append launch of a checked call.
+// The append launch of a checked call.  cu: the ragged append of Nq = T packed rows shared by the B sequences.
 int run_append(const void* k_new, const void* v_new, void* k_cache, void* v_cache, const int* cache_seqlens, int B, int Hkv, int Nq,
-               int Ncap, int d_new, int d, int layout, int dtype, void* stream, const Paging* pg = nullptr) {
-  fa::AppendArgs a;
+               int Ncap, int d_new, int d, int layout, int dtype, void* stream, const Paging* pg = nullptr, const int* cu = nullptr) {
+  fa::RaggedAppendArgs a;
   a.k_new = k_new;
   a.v_new = v_new;
   a.k = k_cache;
   a.v = v_cache;
   a.seqlens = cache_seqlens;
-  a.lanes = (long)B * Nq * Hkv;
+  a.lanes = cu ? (long)Nq * Hkv : (long)B * Nq * Hkv;
+  a.cu = cu;
+  a.nseq = B;
+  a.ntok = Nq;
   a.Hkv = Hkv;
   a.Nq = Nq;
   a.Ncap = Ncap;
@@ -323,6 +352,161 @@ int run_append(const void* k_new, const void* v_new, void* k_cache, void* v_cach
                    (((uintptr_t)k_new | (uintptr_t)v_new | (uintptr_t)k_cache | (uintptr_t)v_cache) & 15) == 0;
   hipStream_t st = static_cast<hipStream_t>(stream);
   return dtype == FA_DTYPE_BF16 ? launch_append_e<fa::bf16_t>(a, d, vec, st) : launch_append_e<float>(a, d, vec, st);
+}
+
+// ---- ragged batches (include/flash_attn_mi355x_decode_ragged.h) ----
+// The argument checks of fa_mi355x_fwd_ragged: those of fa_mi355x_fwd_extend with T in the place of Nq, a null cu_seqlens_q, and
+// a null workspace (the block map lives there: every ragged call needs one).  page_size > 0: a paged call, as in check_decode.
+int check_ragged(const void* q, const void* k_cache, const void* v_cache, const float* out, const int* cu, const void* workspace, int B,
+                 int H, int Hkv, int T, int Ncap, int d, int layout, float softmax_scale, int dtype, int page_size = 0) {
+  g_err[0] = 0;
+  if (B <= 0 || H <= 0 || T <= 0 || Ncap <= 0 || d <= 0) return set_err(FA_ERR_BAD_ARG, "B, H, T, Ncap and d must be positive");
+  if (Hkv <= 0) return set_err(FA_ERR_BAD_ARG, "Hkv must be positive");
+  if (H % Hkv != 0) {
+    snprintf(g_err, sizeof(g_err), "H = %d query heads must be a multiple of Hkv = %d cache heads", H, Hkv);
+    return FA_ERR_BAD_ARG;
+  }
+  if (dtype != FA_DTYPE_F32 && dtype != FA_DTYPE_BF16) return set_err(FA_ERR_BAD_ARG, "unknown dtype");
+  if (layout != FA_LAYOUT_BHND && layout != FA_LAYOUT_BNHD) return set_err(FA_ERR_BAD_ARG, "unknown layout");
+  if (!q || !k_cache || !v_cache || !out) return set_err(FA_ERR_BAD_ARG, "null pointer argument");
+  if (!cu) return set_err(FA_ERR_BAD_ARG, "null cu_seqlens_q");
+  if (d != 32 && d != 64 && d != 128)
+    return set_err(FA_ERR_UNSUPPORTED_D, "decode supports d in {32, 64, 128}: pad the cache with zero columns for other d <= 128");
+  if (softmax_scale != 0.f && (!(softmax_scale > 0.f) || !std::isfinite(softmax_scale)))
+    return set_err(FA_ERR_BAD_ARG, "softmax_scale must be positive and finite (0: 1/sqrt(d))");
+  // (row_query is exact for rows below 2^25; a sequence has at most G * T of them)
+  if ((long)(H / Hkv) * T >= (1L << 25)) return set_err(FA_ERR_BAD_ARG, "G * T rows per kv head must stay under 2^25");
+  const long esz = dtype == FA_DTYPE_BF16 ? 2 : 4;
+  if (page_size > 0) {
+    if (check_page_bytes(page_size, Hkv, d, dtype) != FA_OK) return FA_ERR_BAD_ARG;
+  } else if (((long)Ncap + fa::DEC_ROWS) * Hkv * d * esz >= (1L << 31)) {
+    return set_err(FA_ERR_BAD_ARG, "one batch element of the cache must stay under 2 GiB");
+  }
+  // (a sequence may own every packed row: its q resource and the (head, query) offsets inside it are 32-bit byte counts)
+  if ((long)T * H * d * esz >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "q (T * H * d elements) must stay under 2 GiB");
+  const int ns = rag_splits(B, H, Hkv, T, Ncap);
+  if (split_grid((long)Hkv * ns, rag_blocks(B, H, Hkv, T)) >= (1L << 32) || (long)Hkv * ns >= (1L << 31) || (long)H * T >= (1L << 32))
+    return set_err(FA_ERR_BAD_ARG, "too many workgroups for one launch: Hkv * splits * row blocks and H * T must fit an unsigned int");
+  if (!workspace)
+    return set_err(FA_ERR_BAD_ARG, "null workspace: a ragged call always needs fa_mi355x_ragged_workspace_bytes() bytes (the block map)");
+  return FA_OK;
+}
+
+// ... of fa_mi355x_ragged_append: those of fa_mi355x_extend_append with T in the place of B * Nq, and a null cu_seqlens_q.
+int check_ragged_append(const void* k_new, const void* v_new, const void* k_cache, const void* v_cache, const int* cu, int B, int Hkv, int T,
+                        int Ncap, int d_new, int d, int layout, int dtype) {
+  g_err[0] = 0;
+  if (B <= 0 || Hkv <= 0 || T <= 0 || Ncap <= 0 || d <= 0) return set_err(FA_ERR_BAD_ARG, "B, Hkv, T, Ncap and d must be positive");
+  if (dtype != FA_DTYPE_F32 && dtype != FA_DTYPE_BF16) return set_err(FA_ERR_BAD_ARG, "unknown dtype");
+  if (layout != FA_LAYOUT_BHND && layout != FA_LAYOUT_BNHD) return set_err(FA_ERR_BAD_ARG, "unknown layout");
+  if (!k_new || !v_new || !k_cache || !v_cache) return set_err(FA_ERR_BAD_ARG, "null pointer argument (k_new, v_new and the caches)");
+  if (!cu) return set_err(FA_ERR_BAD_ARG, "null cu_seqlens_q");
+  if (d != 32 && d != 64 && d != 128) return set_err(FA_ERR_UNSUPPORTED_D, "decode supports cache rows of d in {32, 64, 128}");
+  if (d_new < 1 || d_new > d) {
+    snprintf(g_err, sizeof(g_err), "d_new = %d must be in 1 .. d = %d", d_new, d);
+    return FA_ERR_BAD_ARG;
+  }
+  // (the kernel counts packed rows in an int; one lane per element at the most, the workgroup count an int)
+  if ((long)T * Hkv * d / 256 >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "too many new elements for one append launch");
+  return FA_OK;
+}
+
+template <typename T, int D> int launch_ragged(fa::RaggedArgs a, hipStream_t st) {
+  hipLaunchKernelGGL(fa::ragged_schedule_kernel, dim3(1), dim3(256), 0, st, a.cu, const_cast<int*>(a.map), a.nseq, a.ntok, a.G, a.nqb);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return set_err(FA_ERR_HIP, "ragged_schedule_kernel launch", e);
+  const dim3 grid((unsigned)split_grid(a.items, a.nqb));
+  if (a.table)
+    hipLaunchKernelGGL((fa::extend_split_kernel<T, D, true, true>), grid, dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL((fa::extend_split_kernel<T, D, false, true>), grid, dim3(256), 0, st, a);
+  e = hipGetLastError();
+  if (e != hipSuccess) return set_err(FA_ERR_HIP, "extend_split_kernel (ragged) launch", e);
+  if (a.nsplit > 1) {
+    hipLaunchKernelGGL((fa::decode_combine_kernel<D, true>), dim3((unsigned)((long)a.H * a.ntok)), dim3(256), 0, st, a);
+    e = hipGetLastError();
+    if (e != hipSuccess) return set_err(FA_ERR_HIP, "decode_combine_kernel (ragged) launch", e);
+  }
+  return FA_OK;
+}
+
+template <typename T> int launch_ragged_d(const fa::RaggedArgs& a, int d, hipStream_t st) {
+  switch (d) {
+    case 32: return launch_ragged<T, 32>(a, st);
+    case 64: return launch_ragged<T, 64>(a, st);
+    default: return launch_ragged<T, 128>(a, st);
+  }
+}
+
+// The schedule, split (and combine) launches of a checked ragged call.
+int run_ragged(const void* q, const void* k_cache, const void* v_cache, float* out, float* lse, const int* cu, const int* cache_seqlens,
+               void* workspace, int B, int H, int Hkv, int T, int Ncap, int d, int layout, float softmax_scale, int causal, int dtype,
+               void* stream, const Paging* pg) {
+  const int ns = rag_splits(B, H, Hkv, T, Ncap);
+  fa::RaggedArgs a;
+  a.q = q;
+  a.k = k_cache;
+  a.v = v_cache;
+  a.out = out;
+  a.lse = lse;
+  a.map = static_cast<const int*>(workspace);
+  a.part_o = reinterpret_cast<float*>(static_cast<char*>(workspace) + rag_map_bytes(B, H, Hkv, T));
+  a.part_ml = a.part_o + (size_t)H * ns * T * d;
+  a.seqlens = cache_seqlens;
+  a.cu = cu;
+  a.nseq = B;
+  a.ntok = T;
+  a.H = H;
+  a.Hkv = Hkv;
+  a.G = H / Hkv;
+  a.inv_G = 1.0f / (float)a.G;
+  a.Nq = T;   // (the combine kernel's view: one batch element of T queries)
+  a.Ncap = Ncap;
+  a.nsplit = ns;
+  a.chunk = rag_chunk_keys(B, H, Hkv, T, Ncap);
+  a.nqb = (int)rag_blocks(B, H, Hkv, T);
+  a.items = Hkv * ns;
+  const bool bnhd = layout == FA_LAYOUT_BNHD;
+  a.q_ld = H * d;   // (the packed buffers are token-major whatever the caches' layout)
+  a.q_hstride = d;
+  a.q_bstride = (long)T * H * d;
+  a.kv_ld = bnhd ? Hkv * d : d;
+  a.kv_bstride = (long)Ncap * Hkv * d;
+  a.kv_hstride = bnhd ? d : (long)Ncap * d;
+  a.causal = causal ? 1 : 0;
+  a.tau = softmax_scale > 0.f ? softmax_scale : sqrtf(1.0f / (float)d);
+  a.table = nullptr;
+  a.page_size = a.num_pages = a.max_pages = 0;
+  a.page_stride = 0;
+  if (pg) {
+    a.table = pg->table;
+    a.page_size = pg->page_size;
+    a.num_pages = pg->num_pages;
+    a.max_pages = pg->max_pages;
+    a.page_stride = (long)pg->page_size * Hkv * d;
+    a.kv_bstride = 0;
+    a.kv_hstride = bnhd ? d : (long)pg->page_size * d;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  return dtype == FA_DTYPE_BF16 ? launch_ragged_d<fa::bf16_t>(a, d, st) : launch_ragged_d<float>(a, d, st);
+}
+
+// One ragged call: the attention (attend), the append (append), or the append then the attention; pg: the paged form.
+int ragged_call(bool attend, bool append, const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out,
+                float* lse, const int* cu, const int* cache_seqlens, const Paging* pg, void* workspace, int B, int H, int Hkv, int T, int Ncap,
+                int d_new, int d, int layout, float softmax_scale, int causal, int dtype, void* stream) {
+  int rc = pg ? check_pages(*pg, &Ncap) : FA_OK;
+  if (rc == FA_OK && attend)
+    rc = check_ragged(q, k_cache, v_cache, out, cu, workspace, B, H, Hkv, T, Ncap, d, layout, softmax_scale, dtype, pg ? pg->page_size : 0);
+  if (rc == FA_OK && append) rc = check_ragged_append(k_new, v_new, k_cache, v_cache, cu, B, Hkv, T, Ncap, d_new, d, layout, dtype);
+  if (rc == FA_OK && append && pg) rc = check_page_bytes(pg->page_size, Hkv, d, dtype);
+  if (rc != FA_OK) return rc;
+  if (append) {
+    rc = run_append(k_new, v_new, k_cache, v_cache, cache_seqlens, B, Hkv, T, Ncap, d_new, d, layout, dtype, stream, pg, cu);
+    if (rc != FA_OK || !attend) return rc;
+  }
+  return run_ragged(q, k_cache, v_cache, out, lse, cu, cache_seqlens, workspace, B, H, Hkv, T, Ncap, d, layout, softmax_scale, causal, dtype,
+                    stream, pg);
 }
 
 }  // namespace
@@ -485,6 +669,66 @@ int fa_mi355x_fwd_extend_append_paged(const void* q, const void* k_new, const vo
   const Paging pg = {block_table, num_pages, page_size, max_pages};
   return attend_paged(true, true, q, k_new, v_new, k_pool, v_pool, out, lse, cache_seqlens, pg, workspace, B, H, Hkv, Nq, d_new, d, layout,
                       softmax_scale, causal, dtype, stream);
+}
+
+// The ragged entry points (include/flash_attn_mi355x_decode_ragged.h): the new tokens of all sequences packed into T rows, the
+// sequences' boundaries in cu_seqlens_q on the device.
+int fa_mi355x_ragged_splits(int B, int H, int Hkv, int T, int Ncap, int d, int dtype) {
+  (void)dtype;
+  if (!sizes_ok(B, H, Hkv, T, Ncap, d)) return 0;
+  return rag_splits(B, H, Hkv, T, Ncap);
+}
+
+size_t fa_mi355x_ragged_workspace_bytes(int B, int H, int Hkv, int T, int Ncap, int d) {
+  if (!sizes_ok(B, H, Hkv, T, Ncap, d)) return 0;
+  return rag_workspace_bytes(B, H, Hkv, T, Ncap, d);
+}
+
+int fa_mi355x_fwd_ragged(const void* q, const void* k_cache, const void* v_cache, float* out, float* lse, const int* cu_seqlens_q,
+                         const int* cache_seqlens, void* workspace, int B, int H, int Hkv, int T, int Ncap, int d, int layout,
+                         float softmax_scale, int causal, int dtype, void* stream) {
+  return ragged_call(true, false, q, nullptr, nullptr, const_cast<void*>(k_cache), const_cast<void*>(v_cache), out, lse, cu_seqlens_q,
+                     cache_seqlens, nullptr, workspace, B, H, Hkv, T, Ncap, d, d, layout, softmax_scale, causal, dtype, stream);
+}
+
+int fa_mi355x_ragged_append(const void* k_new, const void* v_new, void* k_cache, void* v_cache, const int* cu_seqlens_q,
+                            const int* cache_seqlens, int B, int Hkv, int T, int Ncap, int d_new, int d, int layout, int dtype,
+                            void* stream) {
+  return ragged_call(false, true, nullptr, k_new, v_new, k_cache, v_cache, nullptr, nullptr, cu_seqlens_q, cache_seqlens, nullptr, nullptr, B,
+                     Hkv, Hkv, T, Ncap, d_new, d, layout, 0.f, 0, dtype, stream);
+}
+
+int fa_mi355x_fwd_ragged_append(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
+                                const int* cu_seqlens_q, const int* cache_seqlens, void* workspace, int B, int H, int Hkv, int T,
+                                int Ncap, int d_new, int d, int layout, float softmax_scale, int causal, int dtype, void* stream) {
+  return ragged_call(true, true, q, k_new, v_new, k_cache, v_cache, out, lse, cu_seqlens_q, cache_seqlens, nullptr, workspace, B, H, Hkv, T,
+                     Ncap, d_new, d, layout, softmax_scale, causal, dtype, stream);
+}
+
+int fa_mi355x_fwd_ragged_paged(const void* q, const void* k_pool, const void* v_pool, float* out, float* lse, const int* cu_seqlens_q,
+                               const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv, int T,
+                               int num_pages, int page_size, int max_pages, int d, int layout, float softmax_scale, int causal,
+                               int dtype, void* stream) {
+  const Paging pg = {block_table, num_pages, page_size, max_pages};
+  return ragged_call(true, false, q, nullptr, nullptr, const_cast<void*>(k_pool), const_cast<void*>(v_pool), out, lse, cu_seqlens_q,
+                     cache_seqlens, &pg, workspace, B, H, Hkv, T, 0, d, d, layout, softmax_scale, causal, dtype, stream);
+}
+
+int fa_mi355x_ragged_append_paged(const void* k_new, const void* v_new, void* k_pool, void* v_pool, const int* cu_seqlens_q,
+                                  const int* cache_seqlens, const int* block_table, int B, int Hkv, int T, int num_pages, int page_size,
+                                  int max_pages, int d_new, int d, int layout, int dtype, void* stream) {
+  const Paging pg = {block_table, num_pages, page_size, max_pages};
+  return ragged_call(false, true, nullptr, k_new, v_new, k_pool, v_pool, nullptr, nullptr, cu_seqlens_q, cache_seqlens, &pg, nullptr, B, Hkv,
+                     Hkv, T, 0, d_new, d, layout, 0.f, 0, dtype, stream);
+}
+
+int fa_mi355x_fwd_ragged_append_paged(const void* q, const void* k_new, const void* v_new, void* k_pool, void* v_pool, float* out,
+                                      float* lse, const int* cu_seqlens_q, const int* cache_seqlens, const int* block_table,
+                                      void* workspace, int B, int H, int Hkv, int T, int num_pages, int page_size, int max_pages,
+                                      int d_new, int d, int layout, float softmax_scale, int causal, int dtype, void* stream) {
+  const Paging pg = {block_table, num_pages, page_size, max_pages};
+  return ragged_call(true, true, q, k_new, v_new, k_pool, v_pool, out, lse, cu_seqlens_q, cache_seqlens, &pg, workspace, B, H, Hkv, T, 0,
+                     d_new, d, layout, softmax_scale, causal, dtype, stream);
 }
 
 // The ungrouped entry points: Hkv = H.

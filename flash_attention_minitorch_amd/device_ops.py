@@ -822,3 +822,183 @@ def flash_attn_extend(q, k_cache, v_cache, cache_seqlens=None, causal=True, soft
     rounding, not bit for bit.  ``block_table``: a paged cache, as in flash_attn_decode (fa_mi355x_fwd_extend_paged)."""
     return _cache_attention("flash_attn_extend", True, q, k_cache, v_cache, cache_seqlens, causal, softmax_scale, layout, out, lse,
                             workspace, k_new, v_new, block_table)
+
+
+# ---- ragged batches: every sequence brings its own number of new tokens (include/flash_attn_mi355x_decode_ragged.h) ----
+
+def _check_cu(cu_seqlens_q, B, device):
+    if (not isinstance(cu_seqlens_q, torch.Tensor) or cu_seqlens_q.dtype != torch.int32 or cu_seqlens_q.dim() != 1
+            or (B is not None and cu_seqlens_q.shape[0] != B + 1) or cu_seqlens_q.shape[0] < 2 or cu_seqlens_q.device != device
+            or not cu_seqlens_q.is_contiguous()):
+        raise ValueError("cu_seqlens_q must be a contiguous int32 tensor of shape (B + 1,) on q's device")
+
+
+def _ragged_dims(q, k_cache, cu_seqlens_q, layout, max_pages=None):
+    """(B, H, Hkv, T, Ncap, dq, dp) of a ragged call: q (T, H, dq) packed, caches (B, Ncap, Hkv, dp) for "bnhd" or (B, Hkv, Ncap, dp)
+    for "bhnd", cu_seqlens_q (B + 1,).  ``max_pages``: k_cache is a paged cache's pool (_pool_dims), B is cu_seqlens_q's, and
+    Ncap = max_pages * page_size."""
+    if q.dim() != 3:
+        raise ValueError("a ragged call expects a 3-d packed q (T, H, d)")
+    T, H, dq = q.shape
+    if max_pages is not None:
+        _, page_size, Hkv, dp = _pool_dims(k_cache, layout)
+        _check_cu(cu_seqlens_q, None, q.device)
+        B, Ncap = cu_seqlens_q.shape[0] - 1, max_pages * page_size
+    else:
+        if k_cache.dim() != 4:
+            raise ValueError("a ragged call expects 4-d caches")
+        B, dp = k_cache.shape[0], k_cache.shape[3]
+        Ncap, Hkv = (k_cache.shape[1], k_cache.shape[2]) if layout == "bnhd" else (k_cache.shape[2], k_cache.shape[1])
+        _check_cu(cu_seqlens_q, B, q.device)
+    if T < 1 or Hkv <= 0 or H % Hkv:
+        raise ValueError(f"q has {H} heads, the cache {Hkv}: the cache's heads must divide q's (and q hold a row)")
+    return B, H, Hkv, T, Ncap, dq, dp
+
+
+def ragged_workspace(q, k_cache, cu_seqlens_q, layout="bnhd", block_table=None, max_pages=None):
+    """Scratch for flash_attn_ragged with these tensors (fa_mi355x_ragged_workspace_bytes): the block map and one partial O, m, l per
+    packed row and key chunk.  Never None: the map lives there, so every ragged call needs one.  A pure function of the SHAPES
+    (cu_seqlens_q's contents are not read): allocate once, reuse every step.  A paged call (``k_cache`` the pool): give the block
+    table or its ``max_pages``; the size is the contiguous call's for Ncap = max_pages * page_size."""
+    if layout not in _DECODE_LAYOUTS:
+        raise ValueError(f"layout must be one of {sorted(_DECODE_LAYOUTS)}")
+    B, H, Hkv, T, Ncap, _, dp = _ragged_dims(q, k_cache, cu_seqlens_q, layout, _max_pages(block_table, max_pages))
+    nbytes = _lib.decode().fa_mi355x_ragged_workspace_bytes(B, H, Hkv, T, Ncap, dp)
+    return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=q.device)
+
+
+def _check_new_ragged(k_new, v_new, k_cache, T, Hkv, dp):
+    """d_new of the packed new tokens' k_new / v_new (T, Hkv, d_new), checked against the cache they are appended to."""
+    if k_new.dim() != 3 or k_new.shape != v_new.shape:
+        raise ValueError("k_new and v_new must be 3-d packed tensors (T, Hkv, d_new) of one shape")
+    if k_new.dtype != k_cache.dtype or v_new.dtype != k_cache.dtype:
+        raise TypeError("k_new and v_new must have the cache's dtype")
+    n, hkv, d_new = k_new.shape
+    if hkv != Hkv:
+        raise ValueError(f"k_new and the cache disagree on Hkv: {hkv} vs {Hkv}")
+    if T is not None and n != T:
+        raise ValueError(f"k_new holds {n} packed rows, q {T}")
+    if n < 1 or not 1 <= d_new <= dp:
+        raise ValueError(f"k_new's head dim {d_new} must be in 1 .. {dp}, the cache's row length (and k_new hold a row)")
+    for t in (k_new, v_new):
+        if t.device != k_cache.device:
+            raise ValueError("k_new and v_new must live on the cache's device")
+        if not t.is_contiguous():
+            raise ValueError("k_new and v_new must be contiguous")
+    return n, d_new
+
+
+def _cache_geometry(k_cache, v_cache, layout, block_table):
+    """The checks every ragged call makes on its caches, and ((num_pages, page_size) or None, Hkv, dp, Ncap or None)."""
+    if layout not in _DECODE_LAYOUTS:
+        raise ValueError(f"layout must be one of {sorted(_DECODE_LAYOUTS)}")
+    if k_cache.dim() != 4 or k_cache.shape != v_cache.shape:
+        raise ValueError("k_cache and v_cache must be 4-d tensors of one shape")
+    if v_cache.dtype != k_cache.dtype:
+        raise TypeError("k_cache and v_cache must share one dtype")
+    if block_table is not None:
+        num_pages, page_size, Hkv, dp = _pool_dims(k_cache, layout)
+        return (num_pages, page_size), Hkv, dp, None
+    Ncap, Hkv = (k_cache.shape[1], k_cache.shape[2]) if layout == "bnhd" else (k_cache.shape[2], k_cache.shape[1])
+    return None, Hkv, k_cache.shape[3], Ncap
+
+
+def ragged_append(k_new, v_new, k_cache, v_cache, cu_seqlens_q, cache_seqlens=None, layout="bnhd", block_table=None):
+    """Write the packed new tokens' k and v into the caches on the device (fa_mi355x_ragged_append): k_new, v_new (T, Hkv, d_new),
+    1 <= d_new <= dp, sequence b's rows cu_seqlens_q[b] .. cu_seqlens_q[b + 1] - 1 (clamped on the device so that no row leaves the
+    buffers; a sequence may own none), into caches (B, Ncap, Hkv, dp) / (B, Hkv, Ncap, dp) (``layout`` names the caches' layout only:
+    the packed buffers are token-major).  ``cache_seqlens`` COUNTS the new tokens: token i of sequence b goes to row
+    clamp(len_b, 0, Ncap) - nq_b + i when that is >= 0, with zeros in columns d_new .. dp-1; every other cache row, and every packed
+    row past the last sequence, is left alone.  In place, no host synchronisation.  ``block_table``: the caches are a paged cache's
+    pools, as in decode_append."""
+    pages, Hkv, dp, Ncap = _cache_geometry(k_cache, v_cache, layout, block_table)
+    dtype = _dtype_code(k_cache)
+    T, d_new = _check_new_ragged(k_new, v_new, k_cache, None, Hkv, dp)
+    _check_cu(cu_seqlens_q, None if pages else k_cache.shape[0], k_cache.device)
+    B = cu_seqlens_q.shape[0] - 1   # (a pool's first dimension counts pages: the table is what B is held against)
+    _check_seqlens(cache_seqlens, B, k_cache.device)
+    if pages:
+        _check_table(block_table, B, k_cache.device)
+    for t in (k_cache, v_cache):
+        if t.device != k_cache.device or not t.is_contiguous():
+            raise ValueError("k_cache and v_cache must be contiguous and live on one device")
+        _require_gpu(t, "ragged_append")
+    lib = _lib.decode()
+    head = (_ptr(k_new), _ptr(v_new), _ptr(k_cache), _ptr(v_cache), _ptr(cu_seqlens_q), _ptr(cache_seqlens))
+    tail = (d_new, dp, _DECODE_LAYOUTS[layout], dtype, _stream_ptr())
+    if pages:
+        status = lib.fa_mi355x_ragged_append_paged(*head, _ptr(block_table), B, Hkv, T, *pages, block_table.shape[1], *tail)
+    else:
+        status = lib.fa_mi355x_ragged_append(*head, B, Hkv, T, Ncap, *tail)
+    _lib.decode_check(status)
+
+
+def flash_attn_ragged(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens=None, causal=True, softmax_scale=None, layout="bnhd", out=None,
+                      lse=None, workspace=None, k_new=None, v_new=None, block_table=None, max_pages=None):
+    """One attention call over a RAGGED batch (fa_mi355x_fwd_ragged / _fwd_ragged_append and their _paged forms): every sequence
+    brings its own number of new tokens -- some decode one, one is part-way through a chunked prefill, some have none.  ``q`` is
+    PACKED, (T, H, d): sequence b owns rows cu_seqlens_q[b] .. cu_seqlens_q[b + 1] - 1 (``cu_seqlens_q`` contiguous int32 (B + 1,) on
+    q's device, read and clamped on the device: no host synchronisation, no access outside the T rows whatever it holds; T may exceed
+    cu_seqlens_q[B], the rows past it are the unused tail of a fixed-capacity buffer and are neither read nor written).  The caches,
+    ``cache_seqlens`` (counting the new tokens), ``causal`` (token i of sequence b sits at len_b - nq_b + i), the head-dim padding
+    and the default scale are flash_attn_extend's; ``layout`` names the caches' layout only.  ``k_new``, ``v_new`` (both or neither,
+    (T, Hkv, d_new) packed like q): appended as by ragged_append in front of the attention, one library call.  ``block_table``: a
+    paged cache, as in flash_attn_decode; ``max_pages``, when given, must be the table's second dimension (the figure a workspace
+    was sized with through ragged_workspace(..., max_pages=): a mismatch is an error here, not a workspace of the wrong size).  ``workspace``: from ragged_workspace (always needed: it
+    holds the block map).  Per sequence the result is flash_attn_extend's on that sequence alone (bit for bit where both run as one
+    split).  A step in which EVERY sequence decodes one token is faster through flash_attn_decode (measured, profiles/ragged_bench.txt:
+    1.10x in bf16, 2.4x in fp32 at B = 32, length 4096).
+    Returns (out fp32 (T, H, d), lse fp32 (H, T)): rows with no admissible key give out = 0, lse = -inf; rows of the unused tail
+    keep what they held."""
+    if (k_new is None) != (v_new is None):
+        raise ValueError("k_new and v_new go together: give both (fused append) or neither")
+    pages, Hkv, dp, _ = _cache_geometry(k_cache, v_cache, layout, block_table)
+    dtype = _dtype_code(q)
+    if k_cache.dtype != q.dtype:
+        raise TypeError("q, k_cache and v_cache must share one dtype")
+    mp = _max_pages(block_table, None)
+    if max_pages is not None and max_pages != mp:   # (the caller's own figure, e.g. the one a workspace was sized with: held against the table)
+        raise ValueError(f"max_pages = {max_pages} is not the block_table's second dimension ({mp}; a contiguous cache has none)")
+    B, H, Hkv, T, Ncap, d, dp = _ragged_dims(q, k_cache, cu_seqlens_q, layout, mp)
+    if d > dp:
+        raise ValueError(f"q's head dim {d} exceeds the cache's row length {dp}")
+    _check_seqlens(cache_seqlens, B, q.device)
+    if pages:
+        _check_table(block_table, B, q.device)
+    if k_new is not None:
+        _, d_new = _check_new_ragged(k_new, v_new, k_cache, T, Hkv, dp)
+    for t in (q, k_cache, v_cache):
+        if t.device != q.device:
+            raise ValueError("q, k_cache and v_cache must live on one device")
+        if not t.is_contiguous():
+            raise ValueError("q, k_cache and v_cache must be contiguous")
+    if out is not None and (out.shape != q.shape or out.dtype != torch.float32 or not out.is_contiguous()):
+        raise ValueError("out must be a contiguous float32 tensor of q's shape")
+    if lse is not None and (tuple(lse.shape) != (H, T) or lse.dtype != torch.float32 or not lse.is_contiguous()):
+        raise ValueError("lse must be a contiguous float32 tensor of shape (H, T)")
+    lib = _lib.decode()
+    if workspace is not None and workspace.numel() * workspace.element_size() < lib.fa_mi355x_ragged_workspace_bytes(B, H, Hkv, T, Ncap, dp):
+        raise ValueError("workspace too small: size it with ragged_workspace()")
+    for t in (q, k_cache, v_cache):
+        _require_gpu(t, "flash_attn_ragged")
+    if softmax_scale is None:
+        softmax_scale = 0.0 if d == dp else d ** -0.5
+    qp = pad_head_dim(q, dp) if d < dp else q
+    if out is not None and d == dp:
+        outp = out
+    elif out is not None:   # (padded: the rows of the unused tail must come back as the caller's out held them)
+        outp = pad_head_dim(out, dp)
+    else:
+        outp = torch.empty(qp.shape, dtype=torch.float32, device=q.device)
+    if lse is None:
+        lse = torch.empty((H, T), dtype=torch.float32, device=q.device)
+    if workspace is None:
+        workspace = ragged_workspace(qp, k_cache, cu_seqlens_q, layout, max_pages=mp)
+    new = (_ptr(k_new), _ptr(v_new)) if k_new is not None else ()
+    dims = (d_new, dp) if k_new is not None else (dp,)
+    name = "fa_mi355x_fwd_ragged" + ("_append" if k_new is not None else "") + ("_paged" if pages else "")
+    where = (_ptr(block_table), _ptr(workspace), B, H, Hkv, T, *pages, mp) if pages else (_ptr(workspace), B, H, Hkv, T, Ncap)
+    status = getattr(lib, name)(_ptr(qp), *new, _ptr(k_cache), _ptr(v_cache), _ptr(outp), _ptr(lse), _ptr(cu_seqlens_q), _ptr(cache_seqlens),
+                                *where, *dims, _DECODE_LAYOUTS[layout], float(softmax_scale), int(bool(causal)), dtype, _stream_ptr())
+    _lib.decode_check(status)
+    return (_unpad(outp, d, out) if d < dp else outp), lse

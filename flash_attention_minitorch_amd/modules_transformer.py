@@ -124,6 +124,12 @@ class KVCache:
             self._workspaces[key] = device_ops.extend_workspace(q, self.k[0], "bnhd", **self.paging())
         return self._workspaces[key]
 
+    def ragged_workspace(self, q, cu_seqlens_q):
+        key = ("ragged",) + tuple(q.shape)   # (the ragged call sizes its own: the block map lives there)
+        if key not in self._workspaces:
+            self._workspaces[key] = device_ops.ragged_workspace(q, self.k[0], cu_seqlens_q, "bnhd", **self.paging())
+        return self._workspaces[key]
+
     def _pad(self, t):
         return t if self.dp == self.head_dim else device_ops.pad_head_dim(t, self.dp)
 
@@ -316,6 +322,43 @@ def attention_stack_extend(x_new, layers, n_head: int, cache: KVCache):
         x = x + (o.reshape(B * T, E).to(x.dtype) @ wo).view(B, T, E)
     cache.lengths.copy_(new_len)
     cache.length_bound += T
+    return x
+
+
+def attention_stack_ragged(x_new, counts, layers, n_head: int, cache: KVCache):
+    """One step of a serving loop over a RAGGED batch: sequence b brings ``counts[b]`` new tokens (a host list of B non-negative ints:
+    1 for a sequence that decodes, hundreds for one in the middle of a chunked prefill, 0 for one with nothing to do), PACKED
+    sequence after sequence into x_new (T, E), sum(counts) <= T (the rows past the sum are the unused tail of a fixed-capacity buffer).
+    Builds cu_seqlens_q and lengths + counts on the device and makes ONE fused device_ops.flash_attn_ragged(..., k_new=, v_new=) call
+    per layer, which appends every sequence's k and v at rows lengths[b] .. lengths[b] + counts[b] - 1 and attends causally; then
+    lengths grow by counts.  The capacity check is the host's: length_bound + max(counts) <= capacity, and length_bound grows by
+    max(counts).  A PagedKVCache reserves pages up to that bound for the sequences with counts[b] > 0 -- more than a short sequence
+    needs (page-exact reservation wants the per-sequence lengths on the host, which this layer does not keep).  Returns (T, E): for
+    each sequence, attention_stack_extend's output on that sequence alone, to rounding; rows past sum(counts) are unspecified."""
+    if x_new.dim() != 2:
+        raise ValueError("x_new must be packed: (T, E)")
+    T, E = x_new.shape
+    B = cache.lengths.shape[0]
+    counts = [int(c) for c in counts]
+    if len(counts) != B or min(counts) < 0 or sum(counts) > T:
+        raise ValueError(f"counts must be {B} non-negative ints with sum <= T = {T}")
+    top = max(counts)
+    if cache.length_bound + top > cache.capacity:
+        raise ValueError(f"cache capacity {cache.capacity} exceeded")
+    cache.reserve(cache.length_bound + top, rows=[b for b, c in enumerate(counts) if c > 0])
+    cnt = torch.tensor(counts, dtype=torch.int32)
+    cu = torch.cat([torch.zeros(1, dtype=torch.int32), torch.cumsum(cnt, 0, dtype=torch.int32)]).to(x_new.device)
+    new_len = cache.lengths + cnt.to(x_new.device)
+    x = x_new
+    for li, (wq, wk, wv, wo) in enumerate(layers):
+        q, k, v = (t[0] for t in _project(x[None], wq, wk, wv, n_head))   # packed: (T, heads, d)
+        if k.shape[1] != cache.n_kv_head:
+            raise ValueError(f"the layers project {k.shape[1]} kv heads, the cache holds {cache.n_kv_head}")
+        o, _ = device_ops.flash_attn_ragged(q, cache.k[li], cache.v[li], cu, new_len, causal=True, layout="bnhd",
+                                            workspace=cache.ragged_workspace(q, cu), k_new=k, v_new=v, **cache.paging())
+        x = x + o.reshape(T, E).to(x.dtype) @ wo
+    cache.lengths.copy_(new_len)
+    cache.length_bound += top
     return x
 
 

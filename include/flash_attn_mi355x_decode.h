@@ -149,4 +149,8 @@ const char* fa_mi355x_decode_last_error(void);
  * above, part of this library and of this header, kept in a file of their own. */
 #include "flash_attn_mi355x_decode_paged.h"
 
+/* Ragged batches (packed new tokens, a per-sequence count of them in a device array, contiguous or paged caches): the eight
+ * ragged entry points, part of this library and of this header, kept in a file of their own. */
+#include "flash_attn_mi355x_decode_ragged.h"
+
 #endif /* FLASH_ATTN_MI355X_DECODE_H */
