@@ -148,6 +148,19 @@ RAGGED_ABI = {
     "fa_mi355x_fwd_ragged_append_paged": (_i, [_vp] * 11 + [_i] * 10 + [_f, _i, _i, _vp]),
 }
 
+# the same for include/flash_attn_mi355x_decode_window.h (the sliding-window forms of the same library; tests/test_window_cpu.py)
+WINDOW_ABI = {
+    "fa_mi355x_decode_window_splits": (_i, [_i] * 8),
+    "fa_mi355x_decode_window_workspace_bytes": (_sz, [_i] * 7),
+    "fa_mi355x_fwd_decode_window": (_i, [_vp] * 10 + [_i] * 11 + [_f, _i, _i, _i, _vp]),
+    "fa_mi355x_extend_window_splits": (_i, [_i] * 8),
+    "fa_mi355x_extend_window_workspace_bytes": (_sz, [_i] * 7),
+    "fa_mi355x_fwd_extend_window": (_i, [_vp] * 10 + [_i] * 11 + [_f, _i, _i, _i, _vp]),
+    "fa_mi355x_ragged_window_splits": (_i, [_i] * 8),
+    "fa_mi355x_ragged_window_workspace_bytes": (_sz, [_i] * 7),
+    "fa_mi355x_fwd_ragged_window": (_i, [_vp] * 11 + [_i] * 11 + [_f, _i, _i, _i, _vp]),
+}
+
 
 def _typed(name: str, abi: dict) -> ctypes.CDLL:
     """The library with restype / argtypes of every symbol in ``abi`` set (once, on first load)."""
@@ -216,8 +229,9 @@ DECODE_NAME = "libflash_attn_mi355x_decode.so"
 
 
 def decode() -> ctypes.CDLL:
-    """libflash_attn_mi355x_decode.so (include/flash_attn_mi355x_decode.h, its _paged.h and its _ragged.h) with argtypes set."""
-    return _typed(DECODE_NAME, {**DECODE_ABI, **PAGED_ABI, **RAGGED_ABI})
+    """libflash_attn_mi355x_decode.so (include/flash_attn_mi355x_decode.h, its _paged.h, its _ragged.h and its _window.h) with argtypes
+    set."""
+    return _typed(DECODE_NAME, {**DECODE_ABI, **PAGED_ABI, **RAGGED_ABI, **WINDOW_ABI})
 
 
 def decode_check(status: int) -> None:

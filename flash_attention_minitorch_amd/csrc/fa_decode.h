@@ -41,6 +41,17 @@
 // and a workgroup of the extend kernel reads its entry, then its sequence's first packed row and nq_b, and is from there on the
 // uniform build with nq_b for Nq.  All of these are wave-uniform (readfirstlane): the resources stay in SGPRs.  Outputs, lse and the
 // partials are indexed by packed row.  The RAGGED = false builds are the code they were (DESIGN.md "Ragged").
+//
+// Sliding window (the WINDOW builds of the split and extend kernels; include/flash_attn_mi355x_decode_window.h): a causal call in
+// which the query at position p admits the W keys p - W < j <= p.  A workgroup's key range starts at its row block's lowest window
+// EDGE (the lowest key its first row admits, clamped to 0) rounded down to a super tile, split s covers [lo + s * chunk,
+// lo + (s + 1) * chunk), and the host sizes the splits on the W + block + 127 keys a block can need instead of on Ncap: the work and
+// the HBM traffic follow the window, not the cache.  lo is a multiple of 128, so a super tile still lies inside one page and the
+// staging, the LDS image and the order of the products on the admitted keys are those of the other builds.  No tile wholly below
+// the edge is loaded; the rows below it in the first tile are zeroed in the staging registers (they may hold anything: a released
+// page); a wave skips a 32-key sub-tile wholly below its rows' lowest edge and masks per element only where a sub-tile straddles
+// an edge.  Everything is wave-uniform and derived from len on the device.  The WINDOW = false builds are the code they were
+// (DESIGN.md "Window").
 #pragma once
 #include "fa_common.h"
 
@@ -66,6 +77,7 @@ struct DecodeArgs {
   // paged builds only (a pool of pages and a block table instead of one slab per batch element; Ncap = max_pages * page_size)
   const int* table;    // [B][max_pages] page ids
   int page_size, num_pages, max_pages;   // rows per page (a multiple of DEC_ROWS), pages in the pool, table entries per batch element
+  int window;          // window builds only: W >= 1 (in the four bytes that padded page_stride: no other field moves)
   long page_stride;    // elements between consecutive pages: page_size * Hkv * D
 };
 
@@ -114,6 +126,17 @@ template <typename S> FA_DEV void load_rows(S& st, rsrc_t rs, int row0) {
   }
 }
 
+// Window builds: the first tile of a block's key range starts up to 127 rows below the block's window edge.  No row of the block
+// admits those keys, and they may hold anything (NaN included: P = 0 times a NaN of V is a NaN), so they become zeros in the staging
+// registers, as the hardware makes the rows at or past len.  n: the rows of the staged tile below the edge.  (A thread's first row
+// is voff / ldb: voff = row * ldb + a column offset below ldb.  Once per workgroup, in front of its tile loop.)
+template <typename S> FA_DEV void zero_below(S& st, int n) {
+  const int row = st.voff / st.ldb;
+#pragma unroll
+  for (int i = 0; i < S::PER; ++i)
+    if (row + i * S::RSTEP < n) st.regs[i] = u32x4{0u, 0u, 0u, 0u};
+}
+
 // Paged cache: logical row j of batch element b is row j % page_size of page table[b][j / page_size].  page_size is a multiple of
 // DEC_ROWS and every chunk starts on a multiple of it, so a super tile lies inside one page: the tile at logical row t0 goes through
 // a resource of its page's (kv head) slice sized to the page's valid rows, min(page_size, len - page start), with the tile's row
@@ -151,7 +174,9 @@ struct PageWalk {
 
 // GROUPED = false is the G = 1 build: rho = i with no row arithmetic in front of the workgroup's first loads (a workgroup lives for a
 // few super tiles, so its prologue is not free: DESIGN.md "Decode").  PAGED: the cache is a pool read through a block table (PageWalk).
-template <typename T, int D, bool GROUPED, bool PAGED = false>
+// WINDOW: a sliding window of a.window keys (causal).  The key range belongs to the 32-row BLOCK, not to the call: wedge is the
+// lowest key the block's first row admits, so every block walks about W + 32 + 127 keys whatever Nq.
+template <typename T, int D, bool GROUPED, bool PAGED = false, bool WINDOW = false>
 __global__ void __launch_bounds__(256) decode_split_kernel(DecodeArgs a) {
   using A = Atom<T>;
   typedef typename A::frag frag;
@@ -171,7 +196,9 @@ __global__ void __launch_bounds__(256) decode_split_kernel(DecodeArgs a) {
   const int bh = item / a.nsplit, split = item - bh * a.nsplit;
   const int b = bh / a.Hkv, hkv = bh - b * a.Hkv;
   const int len = __builtin_amdgcn_readfirstlane(clamp_len(a, b));
-  const int c0 = split * a.chunk, c1 = min(c0 + a.chunk, len);
+  int wedge = 0;   // (window builds) the block's window edge; the key range starts at the super tile that holds it
+  if constexpr (WINDOW) wedge = max(len - a.Nq + (GROUPED ? row_query(a, qb * 32) : qb * 32) - a.window + 1, 0);
+  const int c0 = (WINDOW ? wedge & ~(DEC_ROWS - 1) : 0) + split * a.chunk, c1 = min(c0 + a.chunk, len);
 
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -217,6 +244,12 @@ __global__ void __launch_bounds__(256) decode_split_kernel(DecodeArgs a) {
       load_rows(sk, krs, c0);
       load_rows(sv, vrs, c0);
     }
+    if constexpr (WINDOW) {
+      if (c0 < wedge) {   // (split 0 of a block whose edge is inside a super tile)
+        zero_below(sk, wedge - c0);
+        zero_below(sv, wedge - c0);
+      }
+    }
     for (int t0 = c0; t0 < c1; t0 += DEC_ROWS) {
       __syncthreads();   // (the previous super tile's reads are done)
       sk.store(tk);
@@ -232,14 +265,18 @@ __global__ void __launch_bounds__(256) decode_split_kernel(DecodeArgs a) {
       __syncthreads();
       const int kbase = t0 + 32 * w;
       if (kbase >= c1 || (a.causal && kbase > pos_hi)) continue;   // wave-uniform: no admissible key in the wave's 32
+      if constexpr (WINDOW) {
+        if (kbase + 31 <= pos_lo - a.window) continue;   // wave-uniform: the 32 keys are below every row's window
+      }
       f32x16 s = zero16();
 #pragma unroll
       for (int kc = 0; kc < KC; ++kc) A::mma(s, A::template row_frag<D>(tk, ra, 32 * w, kc), qf[kc]);
-      if (kbase + 32 > c1 || (a.causal && kbase + 31 > pos_lo)) {   // wave-uniform
+      // (window: only the sub-tiles that hold a key at or below the highest row's edge - 1 mask for it)
+      if (kbase + 32 > c1 || (a.causal && kbase + 31 > pos_lo) || (WINDOW && kbase <= pos_hi - a.window)) {   // wave-uniform
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
           const int key = kbase + acc_row(i, h);
-          if (key >= c1 || (a.causal && key > qpos)) s[i] = -INFINITY;
+          if (key >= c1 || (a.causal && key > qpos) || (WINDOW && key <= qpos - a.window)) s[i] = -INFINITY;
         }
       }
       float mx = s[0];
@@ -351,7 +388,10 @@ constexpr int EXT_BLOCK = 128;   // rows per workgroup: 32 per wave
 
 // RAGGED: the row block is entry `slot % nqb` of the block map, which names its sequence b and its block qb within b's G * nq_b
 // rows; the items are (kv head, split) alone.  nq_ below is nq_b, row0 the sequence's first packed row.
-template <typename T, int D, bool PAGED = false, bool RAGGED = false>
+// WINDOW: a sliding window of a.window keys (causal).  wedge, the lowest key the 128-row block's first row admits, is to the
+// start of the block's key range what blk_hi is to its end: a block walks about W + 128 + 127 keys wherever it sits in a long
+// input.  Each wave then skips and masks by its own 32 rows' edges.
+template <typename T, int D, bool PAGED = false, bool RAGGED = false, bool WINDOW = false>
 __global__ void __launch_bounds__(256) extend_split_kernel(DecodeArgsOf<RAGGED> a) {
   using A = Atom<T>;
   typedef typename A::frag frag;
@@ -382,7 +422,9 @@ __global__ void __launch_bounds__(256) extend_split_kernel(DecodeArgsOf<RAGGED> 
   // the code they were (DESIGN.md "Ragged").  Do not fold it into a variable without comparing the resource report.
 #define FA_NQ (RAGGED ? nq_ : a.Nq)
   const int len = __builtin_amdgcn_readfirstlane(clamp_len(a, b));
-  const int c0 = split * a.chunk, c1 = min(c0 + a.chunk, len);
+  int wedge = 0;   // (window builds) the block's window edge; the key range starts at the super tile that holds it
+  if constexpr (WINDOW) wedge = max(len - FA_NQ + row_query(a, qb * EXT_BLOCK) - a.window + 1, 0);
+  const int c0 = (WINDOW ? wedge & ~(DEC_ROWS - 1) : 0) + split * a.chunk, c1 = min(c0 + a.chunk, len);
 
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -432,6 +474,12 @@ __global__ void __launch_bounds__(256) extend_split_kernel(DecodeArgsOf<RAGGED> 
       load_rows(sk, krs, c0);
       load_rows(sv, vrs, c0);
     }
+    if constexpr (WINDOW) {
+      if (c0 < wedge) {   // (split 0 of a block whose edge is inside a super tile)
+        zero_below(sk, wedge - c0);
+        zero_below(sv, wedge - c0);
+      }
+    }
     for (int t0 = c0; t0 < cend; t0 += DEC_ROWS) {
       __syncthreads();   // (the previous super tile's reads are done)
       sk.store(tk);
@@ -450,14 +498,18 @@ __global__ void __launch_bounds__(256) extend_split_kernel(DecodeArgsOf<RAGGED> 
       for (int st = 0; st < DEC_ROWS / 32; ++st) {
         const int kbase = t0 + 32 * st;
         if (kbase >= cend || (a.causal && kbase > pos_hi)) break;   // wave-uniform: no admissible key here or further on
+        if constexpr (WINDOW) {
+          if (kbase + 31 <= pos_lo - a.window) continue;   // wave-uniform: the 32 keys are below every window of the wave's rows
+        }
         f32x16 s = zero16();
 #pragma unroll
         for (int kc = 0; kc < KC; ++kc) A::mma(s, A::template row_frag<D>(tk, ra, 32 * st, kc), qf[kc]);
-        if (kbase + 32 > c1 || (a.causal && kbase + 31 > pos_lo)) {   // wave-uniform
+        // (window: only the sub-tiles that hold a key at or below the wave's highest edge - 1 mask for it)
+        if (kbase + 32 > c1 || (a.causal && kbase + 31 > pos_lo) || (WINDOW && kbase <= pos_hi - a.window)) {   // wave-uniform
 #pragma unroll
           for (int i = 0; i < 16; ++i) {
             const int key = kbase + acc_row(i, h);
-            if (key >= c1 || (a.causal && key > qpos)) s[i] = -INFINITY;
+            if (key >= c1 || (a.causal && key > qpos) || (WINDOW && key <= qpos - a.window)) s[i] = -INFINITY;
           }
         }
         float mx = s[0];

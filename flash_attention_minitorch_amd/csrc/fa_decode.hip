@@ -1,7 +1,8 @@
 // C ABI of the MI355X KV-cache decode library (declared in include/flash_attn_mi355x_decode.h, its _paged.h and its _ragged.h):
 // argument checks, the split policies (decode: 32-row blocks, at most 128 queries; extend: 128-row blocks, any number; ragged: the
 // extend policy on an upper bound of the row blocks) and the launches of the kernels of fa_decode.h.  A paged call (a pool and a
-// block table) takes the contiguous call's policy at Ncap = max_pages * page_size.
+// block table) takes the contiguous call's policy at Ncap = max_pages * page_size.  A windowed call (_window.h) takes the three
+// policies on its window span (span_keys) instead of Ncap.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -77,6 +78,23 @@ size_t ext_workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int d) {
   return ns == 1 ? 0 : (size_t)B * H * ns * Nq * (size_t)(d + 2) * sizeof(float);
 }
 
+// Sliding window (include/flash_attn_mi355x_decode_window.h).  A window of W >= Ncap keys admits every key of every row (a row's
+// position is at most len - 1 <= Ncap - 1): such a call IS the unwindowed call, the same launches and the same bits, and so is
+// W = 0.  This also bounds what the device computes with: W < Ncap.
+int win_of(int window, int Ncap) { return window >= Ncap ? 0 : window; }
+
+// The window SPAN: the keys one row block can need, which is what the three policies split where they split Ncap.  A block's rows
+// sit at positions p_first .. p_last with p_last - p_first <= min(Nq, block_rows) - 1 (row i * G + g: block_rows rows span at most
+// block_rows positions, and no more than the call has).  Its key range starts at lo = (p_first - W + 1, clamped to 0) rounded DOWN
+// to a super tile, at most 127 keys below the edge, and ends at p_last:
+//   p_last - lo + 1 <= (p_last - p_first) + W + 127 <= W + min(Nq, block_rows) - 1 + 127
+// and never more than the cache holds.  nsplit * chunk >= span, so the splits of every block cover [lo, p_last].
+int span_keys(int window, int Ncap, int Nq, int block_rows) {
+  const int W = win_of(window, Ncap);
+  if (W == 0) return Ncap;
+  return (int)std::min((long)Ncap, (long)W + std::min(Nq, block_rows) - 1 + fa::DEC_ROWS - 1);
+}
+
 // workgroups of the split launch: the items rounded up to 8, times the row blocks (the kernels' workgroup -> (item, row block) map)
 long split_grid(long items, long nqb) { return (items + 7) / 8 * 8 * nqb; }
 
@@ -100,7 +118,11 @@ size_t rag_workspace_bytes(int B, int H, int Hkv, int T, int Ncap, int d) {
 }
 
 template <typename T, int D> int launch_extend(fa::DecodeArgs a, int BH, hipStream_t st) {
-  if (a.table)
+  if (a.window && a.table)
+    hipLaunchKernelGGL((fa::extend_split_kernel<T, D, true, false, true>), dim3((unsigned)split_grid(a.items, a.nqb)), dim3(256), 0, st, a);
+  else if (a.window)
+    hipLaunchKernelGGL((fa::extend_split_kernel<T, D, false, false, true>), dim3((unsigned)split_grid(a.items, a.nqb)), dim3(256), 0, st, a);
+  else if (a.table)
     hipLaunchKernelGGL((fa::extend_split_kernel<T, D, true>), dim3((unsigned)split_grid(a.items, a.nqb)), dim3(256), 0, st, a);
   else
     hipLaunchKernelGGL((fa::extend_split_kernel<T, D>), dim3((unsigned)split_grid(a.items, a.nqb)), dim3(256), 0, st, a);
@@ -124,7 +146,11 @@ template <typename T> int launch_extend_d(const fa::DecodeArgs& a, int BH, int d
 
 template <typename T, int D> int launch(fa::DecodeArgs a, int BH, hipStream_t st) {
   const int grid = ((a.items + 7) / 8) * 8 * a.nqb;
-  if (a.table)   // (one paged build, the grouped one: G = 1 computes the same rows, and a paged workgroup looks up its page anyway)
+  if (a.window && a.table)   // (the windowed builds: grouped, as the paged one is)
+    hipLaunchKernelGGL((fa::decode_split_kernel<T, D, true, true, true>), dim3(grid), dim3(256), 0, st, a);
+  else if (a.window)
+    hipLaunchKernelGGL((fa::decode_split_kernel<T, D, true, false, true>), dim3(grid), dim3(256), 0, st, a);
+  else if (a.table)   // (one paged build, the grouped one: G = 1 computes the same rows, and a paged workgroup looks up its page anyway)
     hipLaunchKernelGGL((fa::decode_split_kernel<T, D, true, true>), dim3(grid), dim3(256), 0, st, a);
   else if (a.G > 1)
     hipLaunchKernelGGL((fa::decode_split_kernel<T, D, true>), dim3(grid), dim3(256), 0, st, a);
@@ -181,8 +207,10 @@ int check_page_bytes(int page_size, int Hkv, int d, int dtype) {
 
 // The argument checks of fa_mi355x_fwd_decode_gqa, or (extend) of fa_mi355x_fwd_extend: FA_OK, or the error with its message set.
 // page_size > 0: a paged call with Ncap = max_pages * page_size, where the bound on a batch element of the cache is one on a page.
+// window: the splits are those of the window span.
 int check_decode(const void* q, const void* k_cache, const void* v_cache, const float* out, const void* workspace, int B, int H, int Hkv,
-                 int Nq, int Ncap, int d, int layout, float softmax_scale, int dtype, bool extend = false, int page_size = 0) {
+                 int Nq, int Ncap, int d, int layout, float softmax_scale, int dtype, bool extend = false, int page_size = 0,
+                 int window = 0) {
   g_err[0] = 0;
   if (B <= 0 || H <= 0 || Nq <= 0 || Ncap <= 0 || d <= 0) return set_err(FA_ERR_BAD_ARG, "B, H, Nq, Ncap and d must be positive");
   if (Hkv <= 0) return set_err(FA_ERR_BAD_ARG, "Hkv must be positive");
@@ -212,14 +240,14 @@ int check_decode(const void* q, const void* k_cache, const void* v_cache, const 
   if ((long)Nq * H * d * esz >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "one batch element of q must stay under 2 GiB");
   if (extend) {
     // (the workgroup counts of the split and the combine launch are unsigned ints, the items an int)
-    const int ens = ext_splits(B, H, Hkv, Nq, Ncap);
+    const int ens = ext_splits(B, H, Hkv, Nq, span_keys(window, Ncap, Nq, fa::EXT_BLOCK));
     if (split_grid((long)B * Hkv * ens, ext_row_blocks(H, Hkv, Nq)) >= (1L << 32) || (long)B * Hkv * ens >= (1L << 31) ||
         (long)B * H * Nq >= (1L << 32))
       return set_err(FA_ERR_BAD_ARG, "too many workgroups for one launch: B * Hkv * splits * row blocks and B * H * Nq must fit an unsigned int");
     if (ens > 1 && !workspace) return set_err(FA_ERR_BAD_ARG, "null workspace: this call needs fa_mi355x_extend_workspace_bytes() bytes");
     return FA_OK;
   }
-  const int ns = splits(B, H, Hkv, Nq, Ncap);
+  const int ns = splits(B, H, Hkv, Nq, span_keys(window, Ncap, Nq, 32));
   if (ns > 1 && !workspace) return set_err(FA_ERR_BAD_ARG, "null workspace: this call needs fa_mi355x_decode_workspace_bytes() bytes");
   return FA_OK;
 }
@@ -227,8 +255,9 @@ int check_decode(const void* q, const void* k_cache, const void* v_cache, const 
 // The split (and combine) launches of a checked call: the decode kernels, or (extend) the extend kernels under their own policy.
 int run_decode(const void* q, const void* k_cache, const void* v_cache, float* out, float* lse, const int* cache_seqlens, void* workspace,
                int B, int H, int Hkv, int Nq, int Ncap, int d, int layout, float softmax_scale, int causal, int dtype, void* stream,
-               bool extend = false, const Paging* pg = nullptr) {
-  const int ns = extend ? ext_splits(B, H, Hkv, Nq, Ncap) : splits(B, H, Hkv, Nq, Ncap);
+               bool extend = false, const Paging* pg = nullptr, int window = 0) {
+  const int span = span_keys(window, Ncap, Nq, extend ? fa::EXT_BLOCK : 32);   // (no window: Ncap)
+  const int ns = extend ? ext_splits(B, H, Hkv, Nq, span) : splits(B, H, Hkv, Nq, span);
   fa::DecodeArgs a;
   a.q = q;
   a.k = k_cache;
@@ -245,7 +274,8 @@ int run_decode(const void* q, const void* k_cache, const void* v_cache, float* o
   a.Nq = Nq;
   a.Ncap = Ncap;
   a.nsplit = ns;
-  a.chunk = extend ? ext_chunk_keys(B, H, Hkv, Nq, Ncap) : chunk_keys(B, H, Hkv, Nq, Ncap);
+  a.chunk = extend ? ext_chunk_keys(B, H, Hkv, Nq, span) : chunk_keys(B, H, Hkv, Nq, span);
+  a.window = win_of(window, Ncap);
   a.nqb = extend ? ext_row_blocks(H, Hkv, Nq) : row_blocks(H, Hkv, Nq);
   a.items = B * Hkv * ns;
   const bool bnhd = layout == FA_LAYOUT_BNHD;
@@ -358,7 +388,7 @@ int run_append(const void* k_new, const void* v_new, void* k_cache, void* v_cach
 // The argument checks of fa_mi355x_fwd_ragged: those of fa_mi355x_fwd_extend with T in the place of Nq, a null cu_seqlens_q, and
 // a null workspace (the block map lives there: every ragged call needs one).  page_size > 0: a paged call, as in check_decode.
 int check_ragged(const void* q, const void* k_cache, const void* v_cache, const float* out, const int* cu, const void* workspace, int B,
-                 int H, int Hkv, int T, int Ncap, int d, int layout, float softmax_scale, int dtype, int page_size = 0) {
+                 int H, int Hkv, int T, int Ncap, int d, int layout, float softmax_scale, int dtype, int page_size = 0, int window = 0) {
   g_err[0] = 0;
   if (B <= 0 || H <= 0 || T <= 0 || Ncap <= 0 || d <= 0) return set_err(FA_ERR_BAD_ARG, "B, H, T, Ncap and d must be positive");
   if (Hkv <= 0) return set_err(FA_ERR_BAD_ARG, "Hkv must be positive");
@@ -384,7 +414,7 @@ int check_ragged(const void* q, const void* k_cache, const void* v_cache, const 
   }
   // (a sequence may own every packed row: its q resource and the (head, query) offsets inside it are 32-bit byte counts)
   if ((long)T * H * d * esz >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "q (T * H * d elements) must stay under 2 GiB");
-  const int ns = rag_splits(B, H, Hkv, T, Ncap);
+  const int ns = rag_splits(B, H, Hkv, T, span_keys(window, Ncap, T, fa::EXT_BLOCK));
   if (split_grid((long)Hkv * ns, rag_blocks(B, H, Hkv, T)) >= (1L << 32) || (long)Hkv * ns >= (1L << 31) || (long)H * T >= (1L << 32))
     return set_err(FA_ERR_BAD_ARG, "too many workgroups for one launch: Hkv * splits * row blocks and H * T must fit an unsigned int");
   if (!workspace)
@@ -416,7 +446,11 @@ template <typename T, int D> int launch_ragged(fa::RaggedArgs a, hipStream_t st)
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return set_err(FA_ERR_HIP, "ragged_schedule_kernel launch", e);
   const dim3 grid((unsigned)split_grid(a.items, a.nqb));
-  if (a.table)
+  if (a.window && a.table)
+    hipLaunchKernelGGL((fa::extend_split_kernel<T, D, true, true, true>), grid, dim3(256), 0, st, a);
+  else if (a.window)
+    hipLaunchKernelGGL((fa::extend_split_kernel<T, D, false, true, true>), grid, dim3(256), 0, st, a);
+  else if (a.table)
     hipLaunchKernelGGL((fa::extend_split_kernel<T, D, true, true>), grid, dim3(256), 0, st, a);
   else
     hipLaunchKernelGGL((fa::extend_split_kernel<T, D, false, true>), grid, dim3(256), 0, st, a);
@@ -441,8 +475,9 @@ template <typename T> int launch_ragged_d(const fa::RaggedArgs& a, int d, hipStr
 // The schedule, split (and combine) launches of a checked ragged call.
 int run_ragged(const void* q, const void* k_cache, const void* v_cache, float* out, float* lse, const int* cu, const int* cache_seqlens,
                void* workspace, int B, int H, int Hkv, int T, int Ncap, int d, int layout, float softmax_scale, int causal, int dtype,
-               void* stream, const Paging* pg) {
-  const int ns = rag_splits(B, H, Hkv, T, Ncap);
+               void* stream, const Paging* pg, int window = 0) {
+  const int span = span_keys(window, Ncap, T, fa::EXT_BLOCK);   // (no window: Ncap; a sequence may own all T rows)
+  const int ns = rag_splits(B, H, Hkv, T, span);
   fa::RaggedArgs a;
   a.q = q;
   a.k = k_cache;
@@ -463,7 +498,8 @@ int run_ragged(const void* q, const void* k_cache, const void* v_cache, float* o
   a.Nq = T;   // (the combine kernel's view: one batch element of T queries)
   a.Ncap = Ncap;
   a.nsplit = ns;
-  a.chunk = rag_chunk_keys(B, H, Hkv, T, Ncap);
+  a.chunk = rag_chunk_keys(B, H, Hkv, T, span);
+  a.window = win_of(window, Ncap);
   a.nqb = (int)rag_blocks(B, H, Hkv, T);
   a.items = Hkv * ns;
   const bool bnhd = layout == FA_LAYOUT_BNHD;
@@ -494,10 +530,11 @@ int run_ragged(const void* q, const void* k_cache, const void* v_cache, float* o
 // One ragged call: the attention (attend), the append (append), or the append then the attention; pg: the paged form.
 int ragged_call(bool attend, bool append, const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out,
                 float* lse, const int* cu, const int* cache_seqlens, const Paging* pg, void* workspace, int B, int H, int Hkv, int T, int Ncap,
-                int d_new, int d, int layout, float softmax_scale, int causal, int dtype, void* stream) {
+                int d_new, int d, int layout, float softmax_scale, int causal, int dtype, void* stream, int window = 0) {
   int rc = pg ? check_pages(*pg, &Ncap) : FA_OK;
   if (rc == FA_OK && attend)
-    rc = check_ragged(q, k_cache, v_cache, out, cu, workspace, B, H, Hkv, T, Ncap, d, layout, softmax_scale, dtype, pg ? pg->page_size : 0);
+    rc = check_ragged(q, k_cache, v_cache, out, cu, workspace, B, H, Hkv, T, Ncap, d, layout, softmax_scale, dtype, pg ? pg->page_size : 0,
+                      window);
   if (rc == FA_OK && append) rc = check_ragged_append(k_new, v_new, k_cache, v_cache, cu, B, Hkv, T, Ncap, d_new, d, layout, dtype);
   if (rc == FA_OK && append && pg) rc = check_page_bytes(pg->page_size, Hkv, d, dtype);
   if (rc != FA_OK) return rc;
@@ -506,7 +543,7 @@ int ragged_call(bool attend, bool append, const void* q, const void* k_new, cons
     if (rc != FA_OK || !attend) return rc;
   }
   return run_ragged(q, k_cache, v_cache, out, lse, cu, cache_seqlens, workspace, B, H, Hkv, T, Ncap, d, layout, softmax_scale, causal, dtype,
-                    stream, pg);
+                    stream, pg, window);
 }
 
 }  // namespace
@@ -595,20 +632,32 @@ int fa_mi355x_fwd_extend_append(const void* q, const void* k_new, const void* v_
 // The paged entry points: the _gqa / extend forms above on a pool of pages read through a block table.
 namespace {
 
-int attend_paged(bool extend, bool fused, const void* q, const void* k_new, const void* v_new, void* k_pool, void* v_pool, float* out, float* lse,
-                 const int* cache_seqlens, const Paging& pg, void* workspace, int B, int H, int Hkv, int Nq, int d_new, int d, int layout,
-                 float softmax_scale, int causal, int dtype, void* stream) {
-  int Ncap = 0;
-  int rc = check_pages(pg, &Ncap);
-  if (rc == FA_OK) rc = check_decode(q, k_pool, v_pool, out, workspace, B, H, Hkv, Nq, Ncap, d, layout, softmax_scale, dtype, extend, pg.page_size);
-  if (rc == FA_OK && fused) rc = check_append(k_new, v_new, k_pool, v_pool, B, Hkv, Nq, Ncap, d_new, d, layout, dtype, extend);
+// One decode or extend call, fused with the append or not, on a pool (pg: Ncap comes from its geometry) or on slabs of Ncap rows
+// (pg null), windowed or not.
+int attend(bool extend, bool fused, const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
+           const int* cache_seqlens, const Paging* pg, void* workspace, int B, int H, int Hkv, int Nq, int Ncap, int d_new, int d, int layout,
+           float softmax_scale, int causal, int dtype, void* stream, int window = 0) {
+  int rc = pg ? check_pages(*pg, &Ncap) : FA_OK;
+  if (rc == FA_OK)
+    rc = check_decode(q, k_cache, v_cache, out, workspace, B, H, Hkv, Nq, Ncap, d, layout, softmax_scale, dtype, extend, pg ? pg->page_size : 0,
+                      window);
+  if (rc == FA_OK && fused) rc = check_append(k_new, v_new, k_cache, v_cache, B, Hkv, Nq, Ncap, d_new, d, layout, dtype, extend);
   if (rc != FA_OK) return rc;
   if (fused) {
-    rc = run_append(k_new, v_new, k_pool, v_pool, cache_seqlens, B, Hkv, Nq, Ncap, d_new, d, layout, dtype, stream, &pg);
+    rc = run_append(k_new, v_new, k_cache, v_cache, cache_seqlens, B, Hkv, Nq, Ncap, d_new, d, layout, dtype, stream, pg);
     if (rc != FA_OK) return rc;
   }
-  return run_decode(q, k_pool, v_pool, out, lse, cache_seqlens, workspace, B, H, Hkv, Nq, Ncap, d, layout, softmax_scale, causal, dtype,
-                    stream, extend, &pg);
+  return run_decode(q, k_cache, v_cache, out, lse, cache_seqlens, workspace, B, H, Hkv, Nq, Ncap, d, layout, softmax_scale, causal, dtype,
+                    stream, extend, pg, window);
+}
+
+// The checks a windowed call makes first.
+int check_window(int window, int causal) {
+  g_err[0] = 0;
+  if (window < 0) return set_err(FA_ERR_BAD_ARG, "window must not be negative (0: no window)");
+  if (window > 0 && !causal)
+    return set_err(FA_ERR_BAD_ARG, "a sliding window needs the causal mask: window > 0 with causal = 0 (the window ends at the query's position)");
+  return FA_OK;
 }
 
 int append_paged(bool extend, const void* k_new, const void* v_new, void* k_pool, void* v_pool, const int* cache_seqlens, const Paging& pg,
@@ -627,16 +676,16 @@ int fa_mi355x_fwd_decode_paged(const void* q, const void* k_pool, const void* v_
                                const int* block_table, void* workspace, int B, int H, int Hkv, int Nq, int num_pages, int page_size,
                                int max_pages, int d, int layout, float softmax_scale, int causal, int dtype, void* stream) {
   const Paging pg = {block_table, num_pages, page_size, max_pages};
-  return attend_paged(false, false, q, nullptr, nullptr, const_cast<void*>(k_pool), const_cast<void*>(v_pool), out, lse, cache_seqlens, pg,
-                      workspace, B, H, Hkv, Nq, d, d, layout, softmax_scale, causal, dtype, stream);
+  return attend(false, false, q, nullptr, nullptr, const_cast<void*>(k_pool), const_cast<void*>(v_pool), out, lse, cache_seqlens, &pg,
+                workspace, B, H, Hkv, Nq, 0, d, d, layout, softmax_scale, causal, dtype, stream);
 }
 
 int fa_mi355x_fwd_extend_paged(const void* q, const void* k_pool, const void* v_pool, float* out, float* lse, const int* cache_seqlens,
                                const int* block_table, void* workspace, int B, int H, int Hkv, int Nq, int num_pages, int page_size,
                                int max_pages, int d, int layout, float softmax_scale, int causal, int dtype, void* stream) {
   const Paging pg = {block_table, num_pages, page_size, max_pages};
-  return attend_paged(true, false, q, nullptr, nullptr, const_cast<void*>(k_pool), const_cast<void*>(v_pool), out, lse, cache_seqlens, pg,
-                      workspace, B, H, Hkv, Nq, d, d, layout, softmax_scale, causal, dtype, stream);
+  return attend(true, false, q, nullptr, nullptr, const_cast<void*>(k_pool), const_cast<void*>(v_pool), out, lse, cache_seqlens, &pg,
+                workspace, B, H, Hkv, Nq, 0, d, d, layout, softmax_scale, causal, dtype, stream);
 }
 
 int fa_mi355x_decode_append_paged(const void* k_new, const void* v_new, void* k_pool, void* v_pool, const int* cache_seqlens,
@@ -658,8 +707,8 @@ int fa_mi355x_fwd_decode_append_paged(const void* q, const void* k_new, const vo
                                       int Nq, int num_pages, int page_size, int max_pages, int d_new, int d, int layout,
                                       float softmax_scale, int causal, int dtype, void* stream) {
   const Paging pg = {block_table, num_pages, page_size, max_pages};
-  return attend_paged(false, true, q, k_new, v_new, k_pool, v_pool, out, lse, cache_seqlens, pg, workspace, B, H, Hkv, Nq, d_new, d, layout,
-                      softmax_scale, causal, dtype, stream);
+  return attend(false, true, q, k_new, v_new, k_pool, v_pool, out, lse, cache_seqlens, &pg, workspace, B, H, Hkv, Nq, 0, d_new, d, layout,
+                softmax_scale, causal, dtype, stream);
 }
 
 int fa_mi355x_fwd_extend_append_paged(const void* q, const void* k_new, const void* v_new, void* k_pool, void* v_pool, float* out,
@@ -667,8 +716,8 @@ int fa_mi355x_fwd_extend_append_paged(const void* q, const void* k_new, const vo
                                       int Nq, int num_pages, int page_size, int max_pages, int d_new, int d, int layout,
                                       float softmax_scale, int causal, int dtype, void* stream) {
   const Paging pg = {block_table, num_pages, page_size, max_pages};
-  return attend_paged(true, true, q, k_new, v_new, k_pool, v_pool, out, lse, cache_seqlens, pg, workspace, B, H, Hkv, Nq, d_new, d, layout,
-                      softmax_scale, causal, dtype, stream);
+  return attend(true, true, q, k_new, v_new, k_pool, v_pool, out, lse, cache_seqlens, &pg, workspace, B, H, Hkv, Nq, 0, d_new, d, layout,
+                softmax_scale, causal, dtype, stream);
 }
 
 // The ragged entry points (include/flash_attn_mi355x_decode_ragged.h): the new tokens of all sequences packed into T rows, the
@@ -729,6 +778,74 @@ int fa_mi355x_fwd_ragged_append_paged(const void* q, const void* k_new, const vo
   const Paging pg = {block_table, num_pages, page_size, max_pages};
   return ragged_call(true, true, q, k_new, v_new, k_pool, v_pool, out, lse, cu_seqlens_q, cache_seqlens, &pg, workspace, B, H, Hkv, T, 0,
                      d_new, d, layout, softmax_scale, causal, dtype, stream);
+}
+
+// The windowed entry points (include/flash_attn_mi355x_decode_window.h): one per call family.  k_new / v_new null: attend only;
+// block_table null: slabs of Ncap rows, otherwise the pool's geometry stands for Ncap.
+int fa_mi355x_decode_window_splits(int B, int H, int Hkv, int Nq, int Ncap, int d, int dtype, int window) {
+  (void)dtype;
+  if (!sizes_ok(B, H, Hkv, Nq, Ncap, d) || window < 0) return 0;
+  return splits(B, H, Hkv, Nq, span_keys(window, Ncap, Nq, 32));
+}
+
+size_t fa_mi355x_decode_window_workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int d, int window) {
+  if (!sizes_ok(B, H, Hkv, Nq, Ncap, d) || window < 0) return 0;
+  return workspace_bytes(B, H, Hkv, Nq, span_keys(window, Ncap, Nq, 32), d);
+}
+
+int fa_mi355x_extend_window_splits(int B, int H, int Hkv, int Nq, int Ncap, int d, int dtype, int window) {
+  (void)dtype;
+  if (!sizes_ok(B, H, Hkv, Nq, Ncap, d) || window < 0) return 0;
+  return ext_splits(B, H, Hkv, Nq, span_keys(window, Ncap, Nq, fa::EXT_BLOCK));
+}
+
+size_t fa_mi355x_extend_window_workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int d, int window) {
+  if (!sizes_ok(B, H, Hkv, Nq, Ncap, d) || window < 0) return 0;
+  return ext_workspace_bytes(B, H, Hkv, Nq, span_keys(window, Ncap, Nq, fa::EXT_BLOCK), d);
+}
+
+int fa_mi355x_ragged_window_splits(int B, int H, int Hkv, int T, int Ncap, int d, int dtype, int window) {
+  (void)dtype;
+  if (!sizes_ok(B, H, Hkv, T, Ncap, d) || window < 0) return 0;
+  return rag_splits(B, H, Hkv, T, span_keys(window, Ncap, T, fa::EXT_BLOCK));
+}
+
+size_t fa_mi355x_ragged_window_workspace_bytes(int B, int H, int Hkv, int T, int Ncap, int d, int window) {
+  if (!sizes_ok(B, H, Hkv, T, Ncap, d) || window < 0) return 0;
+  return rag_workspace_bytes(B, H, Hkv, T, span_keys(window, Ncap, T, fa::EXT_BLOCK), d);
+}
+
+int fa_mi355x_fwd_decode_window(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
+                                const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv, int Nq, int Ncap,
+                                int num_pages, int page_size, int max_pages, int d_new, int d, int layout, float softmax_scale, int causal,
+                                int window, int dtype, void* stream) {
+  const int rc = check_window(window, causal);
+  if (rc != FA_OK) return rc;
+  const Paging pg = {block_table, num_pages, page_size, max_pages};
+  return attend(false, k_new || v_new, q, k_new, v_new, k_cache, v_cache, out, lse, cache_seqlens, block_table ? &pg : nullptr, workspace, B, H,
+                Hkv, Nq, Ncap, d_new, d, layout, softmax_scale, causal, dtype, stream, window);
+}
+
+int fa_mi355x_fwd_extend_window(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
+                                const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv, int Nq, int Ncap,
+                                int num_pages, int page_size, int max_pages, int d_new, int d, int layout, float softmax_scale, int causal,
+                                int window, int dtype, void* stream) {
+  const int rc = check_window(window, causal);
+  if (rc != FA_OK) return rc;
+  const Paging pg = {block_table, num_pages, page_size, max_pages};
+  return attend(true, k_new || v_new, q, k_new, v_new, k_cache, v_cache, out, lse, cache_seqlens, block_table ? &pg : nullptr, workspace, B, H,
+                Hkv, Nq, Ncap, d_new, d, layout, softmax_scale, causal, dtype, stream, window);
+}
+
+int fa_mi355x_fwd_ragged_window(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
+                                const int* cu_seqlens_q, const int* cache_seqlens, const int* block_table, void* workspace, int B, int H,
+                                int Hkv, int T, int Ncap, int num_pages, int page_size, int max_pages, int d_new, int d, int layout,
+                                float softmax_scale, int causal, int window, int dtype, void* stream) {
+  const int rc = check_window(window, causal);
+  if (rc != FA_OK) return rc;
+  const Paging pg = {block_table, num_pages, page_size, max_pages};
+  return ragged_call(true, k_new || v_new, q, k_new, v_new, k_cache, v_cache, out, lse, cu_seqlens_q, cache_seqlens,
+                     block_table ? &pg : nullptr, workspace, B, H, Hkv, T, Ncap, d_new, d, layout, softmax_scale, causal, dtype, stream, window);
 }
 
 // The ungrouped entry points: Hkv = H.

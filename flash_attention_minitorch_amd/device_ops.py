@@ -14,6 +14,7 @@ supply, and exactly one C call.
 from __future__ import annotations
 
 import ctypes
+import operator
 
 import torch
 
@@ -607,31 +608,54 @@ def _decode_dims(q, k_cache, layout, max_pages=None):
     return B, H, Hkv, Nq, Ncap, dq, dp
 
 
-def _decode_workspace_bytes(B, H, Hkv, Nq, Ncap, dp):
+def _decode_workspace_bytes(B, H, Hkv, Nq, Ncap, dp, window=None):
     lib = _lib.decode()
+    if window is not None:
+        return lib.fa_mi355x_decode_window_workspace_bytes(B, H, Hkv, Nq, Ncap, dp, window)
     if Hkv == H:
         return lib.fa_mi355x_decode_workspace_bytes(B, H, Nq, Ncap, dp)
     return lib.fa_mi355x_decode_workspace_bytes_gqa(B, H, Hkv, Nq, Ncap, dp)
 
 
-def decode_workspace(q, k_cache, layout="bnhd", block_table=None, max_pages=None):
+def _check_window(window, causal=True):
+    """``window`` as the library takes it: None stays None (the unwindowed entry points), otherwise an int >= 0 under the causal mask."""
+    if window is None:
+        return None
+    try:
+        window = None if isinstance(window, bool) else operator.index(window)
+    except TypeError:
+        window = None
+    if window is None:
+        raise ValueError("window must be None or an int: the number of positions a token sees, its own included")
+    if window < 0:
+        raise ValueError("window must not be negative (None or 0: no window)")
+    if window > 0 and not causal:
+        raise ValueError("a sliding window needs the causal mask: window= with causal=False")
+    return window
+
+
+def decode_workspace(q, k_cache, layout="bnhd", block_table=None, max_pages=None, window=None):
     """Scratch for flash_attn_decode with these tensors (fa_mi355x_decode_workspace_bytes; one partial O, m, l per query row and key
     chunk), or None when the call runs as one split and needs none.  A pure function of the shapes: allocate once, reuse every step.
     A paged call (``k_cache`` the pool): give the block table or its ``max_pages``; the size is the contiguous call's for
-    Ncap = max_pages * page_size."""
+    Ncap = max_pages * page_size.  ``window``: for flash_attn_decode(..., window=) (fa_mi355x_decode_window_workspace_bytes: the
+    splits follow the window span, not the cache)."""
     B, H, Hkv, Nq, Ncap, _, dp = _decode_dims(q, k_cache, layout, _max_pages(block_table, max_pages))
-    nbytes = _decode_workspace_bytes(B, H, Hkv, Nq, Ncap, dp)
+    nbytes = _decode_workspace_bytes(B, H, Hkv, Nq, Ncap, dp, _check_window(window))
     return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=q.device) if nbytes else None
 
 
-def _extend_workspace_bytes(B, H, Hkv, Nq, Ncap, dp):
+def _extend_workspace_bytes(B, H, Hkv, Nq, Ncap, dp, window=None):
+    if window is not None:
+        return _lib.decode().fa_mi355x_extend_window_workspace_bytes(B, H, Hkv, Nq, Ncap, dp, window)
     return _lib.decode().fa_mi355x_extend_workspace_bytes(B, H, Hkv, Nq, Ncap, dp)
 
 
-def extend_workspace(q, k_cache, layout="bnhd", block_table=None, max_pages=None):
-    """decode_workspace for flash_attn_extend (fa_mi355x_extend_workspace_bytes: the extend call has a split policy of its own)."""
+def extend_workspace(q, k_cache, layout="bnhd", block_table=None, max_pages=None, window=None):
+    """decode_workspace for flash_attn_extend (fa_mi355x_extend_workspace_bytes: the extend call has a split policy of its own;
+    ``window``: fa_mi355x_extend_window_workspace_bytes)."""
     B, H, Hkv, Nq, Ncap, _, dp = _decode_dims(q, k_cache, layout, _max_pages(block_table, max_pages))
-    nbytes = _extend_workspace_bytes(B, H, Hkv, Nq, Ncap, dp)
+    nbytes = _extend_workspace_bytes(B, H, Hkv, Nq, Ncap, dp, _check_window(window))
     return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=q.device) if nbytes else None
 
 
@@ -714,9 +738,10 @@ def extend_append(k_new, v_new, k_cache, v_cache, cache_seqlens=None, layout="bn
 
 
 def _cache_attention(who, extend, q, k_cache, v_cache, cache_seqlens, causal, softmax_scale, layout, out, lse, workspace, k_new, v_new,
-                     block_table=None):
+                     block_table=None, window=None):
     """flash_attn_decode / flash_attn_extend (``extend``): the checks, the head-dim padding, then the library's entry point (its
-    _paged form when there is a block table)."""
+    _paged form when there is a block table; with a ``window``, the family's one _window entry point)."""
+    window = _check_window(window, causal)
     if (k_new is None) != (v_new is None):
         raise ValueError("k_new and v_new go together: give both (fused append) or neither")
     if layout not in _DECODE_LAYOUTS:
@@ -760,11 +785,18 @@ def _cache_attention(who, extend, q, k_cache, v_cache, cache_seqlens, causal, so
     lib = _lib.decode()
     new_ws, ws_bytes = (extend_workspace, _extend_workspace_bytes) if extend else (decode_workspace, _decode_workspace_bytes)
     if workspace is None:
-        workspace = new_ws(qp, k_cache, layout, **pages)
-    elif workspace.numel() * workspace.element_size() < ws_bytes(B, H, Hkv, Nq, Ncap, dp):
+        workspace = new_ws(qp, k_cache, layout, **pages, window=window)
+    elif workspace.numel() * workspace.element_size() < ws_bytes(B, H, Hkv, Nq, Ncap, dp, window):
         raise ValueError(f"workspace too small: size it with {new_ws.__name__}()")
     tail = (_DECODE_LAYOUTS[layout], float(softmax_scale), int(bool(causal)), dtype, _stream_ptr())
-    if paged:   # (one grouped form of each: the contiguous calls' arguments with the table after the lengths and the pool's geometry for Ncap)
+    if window is not None:   # (one entry point per family: null k_new / v_new attend only, a null table is a slab cache)
+        fwd = lib.fa_mi355x_fwd_extend_window if extend else lib.fa_mi355x_fwd_decode_window
+        geometry = (num_pages, page_size, pages["max_pages"]) if paged else (0, 0, 0)
+        status = fwd(_ptr(qp), _ptr(k_new), _ptr(v_new), _ptr(k_cache), _ptr(v_cache), _ptr(outp), _ptr(lse), _ptr(cache_seqlens),
+                     _ptr(block_table), _ptr(workspace), B, H, Hkv, Nq, 0 if paged else Ncap, *geometry,
+                     d_new if k_new is not None else dp, dp, _DECODE_LAYOUTS[layout], float(softmax_scale), int(bool(causal)), window,
+                     dtype, _stream_ptr())
+    elif paged:   # (one grouped form of each: the contiguous calls' arguments with the table after the lengths and the pool's geometry for Ncap)
         name = "fa_mi355x_fwd_" + ("extend" if extend else "decode") + ("_append" if k_new is not None else "") + "_paged"
         new = (_ptr(k_new), _ptr(v_new)) if k_new is not None else ()
         dims = (d_new, dp) if k_new is not None else (dp,)
@@ -791,7 +823,7 @@ def _cache_attention(who, extend, q, k_cache, v_cache, cache_seqlens, causal, so
 
 
 def flash_attn_decode(q, k_cache, v_cache, cache_seqlens=None, causal=True, softmax_scale=None, layout="bnhd", out=None, lse=None,
-                      workspace=None, k_new=None, v_new=None, block_table=None):
+                      workspace=None, k_new=None, v_new=None, block_table=None, window=None):
     """Attention of Nq <= 128 new queries against a KV cache (fa_mi355x_fwd_decode / _gqa, include/flash_attn_mi355x_decode.h).
     ``layout`` "bnhd": q (B, Nq, H, d), caches (B, Ncap, Hkv, dp); "bhnd": q (B, H, Nq, d), caches (B, Hkv, Ncap, dp).  Hkv is the
     cache's own head count and must divide H: Hkv < H is a grouped-query (Hkv = 1: multi-query) cache, query head h reads cache head
@@ -806,22 +838,30 @@ def flash_attn_decode(q, k_cache, v_cache, cache_seqlens=None, causal=True, soft
     row j of batch element b is row j % page_size of page block_table[b, j // page_size], Ncap = max_pages * page_size, and entries
     past a sequence's last page are never read (fa_mi355x_fwd_decode_paged; ids are clamped to the pool on the device).  The result
     is bit for bit the contiguous call's on the gathered cache; size a workspace with decode_workspace(..., block_table=).
+    ``window`` (None, or an int >= 0; causal only): SLIDING-WINDOW attention (fa_mi355x_fwd_decode_window,
+    include/flash_attn_mi355x_decode_window.h).  The query at position p admits the W keys p - W < j <= p, its own position
+    included (Mistral's ``sliding_window``); lse covers the admitted keys.  The kernels start each row block's key range at its
+    window, so the work and the bytes read follow W and not the cache's length, and cache rows (and the pages of a paged cache) wholly
+    below the window are never read.  None takes the unwindowed entry points above; 0, and any W >= Ncap, is the unwindowed call
+    through the windowed entry point (the same launches and bits).  Size a workspace with decode_workspace(..., window=).
     Returns (out fp32 in q's shape, lse fp32 (B, H, Nq)): rows with no admissible key give out = 0, lse = -inf."""
     return _cache_attention("flash_attn_decode", False, q, k_cache, v_cache, cache_seqlens, causal, softmax_scale, layout, out, lse,
-                            workspace, k_new, v_new, block_table)
+                            workspace, k_new, v_new, block_table, window)
 
 
 def flash_attn_extend(q, k_cache, v_cache, cache_seqlens=None, causal=True, softmax_scale=None, layout="bnhd", out=None, lse=None,
-                      workspace=None, k_new=None, v_new=None, block_table=None):
+                      workspace=None, k_new=None, v_new=None, block_table=None, window=None):
     """flash_attn_decode for ANY number Nq >= 1 of new queries (fa_mi355x_fwd_extend / fa_mi355x_fwd_extend_append): a long input that
     follows a cached prefix, or one piece of a chunked prefill (the same call, from an empty cache on).  Every argument, check, the
     head-dim padding (the default scale keeps the caller's 1/sqrt(d)) and the return value are flash_attn_decode's; ``workspace`` is
     sized by extend_workspace (the extend call has its own split policy), ``k_new`` / ``v_new`` are appended as by extend_append.
     Always the extend kernels, whatever Nq: a workgroup owns 128 rows of a kv head's G * Nq and shares each staged K / V tile among
     them, and a causal call loads no tile above a block's last position.  For Nq <= 128 the result agrees with flash_attn_decode to
-    rounding, not bit for bit.  ``block_table``: a paged cache, as in flash_attn_decode (fa_mi355x_fwd_extend_paged)."""
+    rounding, not bit for bit.  ``block_table``: a paged cache, as in flash_attn_decode (fa_mi355x_fwd_extend_paged).  ``window``:
+    sliding-window attention, as in flash_attn_decode (fa_mi355x_fwd_extend_window): every 128-row block walks its own W + 128
+    positions' worth of keys wherever it sits in a long input; size a workspace with extend_workspace(..., window=)."""
     return _cache_attention("flash_attn_extend", True, q, k_cache, v_cache, cache_seqlens, causal, softmax_scale, layout, out, lse,
-                            workspace, k_new, v_new, block_table)
+                            workspace, k_new, v_new, block_table, window)
 
 
 # ---- ragged batches: every sequence brings its own number of new tokens (include/flash_attn_mi355x_decode_ragged.h) ----
@@ -855,15 +895,22 @@ def _ragged_dims(q, k_cache, cu_seqlens_q, layout, max_pages=None):
     return B, H, Hkv, T, Ncap, dq, dp
 
 
-def ragged_workspace(q, k_cache, cu_seqlens_q, layout="bnhd", block_table=None, max_pages=None):
+def _ragged_workspace_bytes(B, H, Hkv, T, Ncap, dp, window=None):
+    if window is not None:
+        return _lib.decode().fa_mi355x_ragged_window_workspace_bytes(B, H, Hkv, T, Ncap, dp, window)
+    return _lib.decode().fa_mi355x_ragged_workspace_bytes(B, H, Hkv, T, Ncap, dp)
+
+
+def ragged_workspace(q, k_cache, cu_seqlens_q, layout="bnhd", block_table=None, max_pages=None, window=None):
     """Scratch for flash_attn_ragged with these tensors (fa_mi355x_ragged_workspace_bytes): the block map and one partial O, m, l per
     packed row and key chunk.  Never None: the map lives there, so every ragged call needs one.  A pure function of the SHAPES
     (cu_seqlens_q's contents are not read): allocate once, reuse every step.  A paged call (``k_cache`` the pool): give the block
-    table or its ``max_pages``; the size is the contiguous call's for Ncap = max_pages * page_size."""
+    table or its ``max_pages``; the size is the contiguous call's for Ncap = max_pages * page_size.  ``window``: for
+    flash_attn_ragged(..., window=) (fa_mi355x_ragged_window_workspace_bytes)."""
     if layout not in _DECODE_LAYOUTS:
         raise ValueError(f"layout must be one of {sorted(_DECODE_LAYOUTS)}")
     B, H, Hkv, T, Ncap, _, dp = _ragged_dims(q, k_cache, cu_seqlens_q, layout, _max_pages(block_table, max_pages))
-    nbytes = _lib.decode().fa_mi355x_ragged_workspace_bytes(B, H, Hkv, T, Ncap, dp)
+    nbytes = _ragged_workspace_bytes(B, H, Hkv, T, Ncap, dp, _check_window(window))
     return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=q.device)
 
 
@@ -934,7 +981,7 @@ def ragged_append(k_new, v_new, k_cache, v_cache, cu_seqlens_q, cache_seqlens=No
 
 
 def flash_attn_ragged(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens=None, causal=True, softmax_scale=None, layout="bnhd", out=None,
-                      lse=None, workspace=None, k_new=None, v_new=None, block_table=None, max_pages=None):
+                      lse=None, workspace=None, k_new=None, v_new=None, block_table=None, max_pages=None, window=None):
     """One attention call over a RAGGED batch (fa_mi355x_fwd_ragged / _fwd_ragged_append and their _paged forms): every sequence
     brings its own number of new tokens -- some decode one, one is part-way through a chunked prefill, some have none.  ``q`` is
     PACKED, (T, H, d): sequence b owns rows cu_seqlens_q[b] .. cu_seqlens_q[b + 1] - 1 (``cu_seqlens_q`` contiguous int32 (B + 1,) on
@@ -947,9 +994,12 @@ def flash_attn_ragged(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens=None, cau
     was sized with through ragged_workspace(..., max_pages=): a mismatch is an error here, not a workspace of the wrong size).  ``workspace``: from ragged_workspace (always needed: it
     holds the block map).  Per sequence the result is flash_attn_extend's on that sequence alone (bit for bit where both run as one
     split).  A step in which EVERY sequence decodes one token is faster through flash_attn_decode (measured, profiles/ragged_bench.txt:
-    1.10x in bf16, 2.4x in fp32 at B = 32, length 4096).
+    1.10x in bf16, 2.4x in fp32 at B = 32, length 4096).  ``window``: sliding-window attention, as in flash_attn_decode
+    (fa_mi355x_fwd_ragged_window; token i of sequence b sits at len_b - nq_b + i and admits the W keys up to its own position); size
+    a workspace with ragged_workspace(..., window=).
     Returns (out fp32 (T, H, d), lse fp32 (H, T)): rows with no admissible key give out = 0, lse = -inf; rows of the unused tail
     keep what they held."""
+    window = _check_window(window, causal)
     if (k_new is None) != (v_new is None):
         raise ValueError("k_new and v_new go together: give both (fused append) or neither")
     pages, Hkv, dp, _ = _cache_geometry(k_cache, v_cache, layout, block_table)
@@ -977,7 +1027,7 @@ def flash_attn_ragged(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens=None, cau
     if lse is not None and (tuple(lse.shape) != (H, T) or lse.dtype != torch.float32 or not lse.is_contiguous()):
         raise ValueError("lse must be a contiguous float32 tensor of shape (H, T)")
     lib = _lib.decode()
-    if workspace is not None and workspace.numel() * workspace.element_size() < lib.fa_mi355x_ragged_workspace_bytes(B, H, Hkv, T, Ncap, dp):
+    if workspace is not None and workspace.numel() * workspace.element_size() < _ragged_workspace_bytes(B, H, Hkv, T, Ncap, dp, window):
         raise ValueError("workspace too small: size it with ragged_workspace()")
     for t in (q, k_cache, v_cache):
         _require_gpu(t, "flash_attn_ragged")
@@ -993,7 +1043,15 @@ def flash_attn_ragged(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens=None, cau
     if lse is None:
         lse = torch.empty((H, T), dtype=torch.float32, device=q.device)
     if workspace is None:
-        workspace = ragged_workspace(qp, k_cache, cu_seqlens_q, layout, max_pages=mp)
+        workspace = ragged_workspace(qp, k_cache, cu_seqlens_q, layout, max_pages=mp, window=window)
+    if window is not None:   # (the family's one windowed entry point: null k_new / v_new attend only, a null table is a slab cache)
+        geometry = (0, *pages, mp) if pages else (Ncap, 0, 0, 0)
+        status = lib.fa_mi355x_fwd_ragged_window(
+            _ptr(qp), _ptr(k_new), _ptr(v_new), _ptr(k_cache), _ptr(v_cache), _ptr(outp), _ptr(lse), _ptr(cu_seqlens_q), _ptr(cache_seqlens),
+            _ptr(block_table), _ptr(workspace), B, H, Hkv, T, *geometry, d_new if k_new is not None else dp, dp, _DECODE_LAYOUTS[layout],
+            float(softmax_scale), int(bool(causal)), window, dtype, _stream_ptr())
+        _lib.decode_check(status)
+        return (_unpad(outp, d, out) if d < dp else outp), lse
     new = (_ptr(k_new), _ptr(v_new)) if k_new is not None else ()
     dims = (d_new, dp) if k_new is not None else (dp,)
     name = "fa_mi355x_fwd_ragged" + ("_append" if k_new is not None else "") + ("_paged" if pages else "")

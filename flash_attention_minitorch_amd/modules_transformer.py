@@ -80,17 +80,30 @@ def attention_stack(x, layers, n_head: int, causal: bool = True, fused_layout: b
 # with the decode kernels (attention_stack_step): one pass over the cached K and V per layer instead of causal attention over N tokens.
 # More than 128 new tokens at once (a second turn, a long message after a cached prefix, a prompt fed in pieces) go through the
 # extend kernels (attention_stack_extend, attention_stack_prefill_chunked).
+# A cache built with window=W makes every one of these calls a sliding-window one (each token sees the last W positions): the step,
+# fused step, extend, ragged and chunked-prefill functions and GraphedStep pass cache.window to device_ops, and a PagedKVCache gives
+# the pages behind the window back through release_behind_window.
 
 MAX_STEP_TOKENS = 128   # fa_mi355x_fwd_decode's largest Nq; longer inputs are prefill, or attention_stack_extend after a prefix
+
+
+def _check_cache_window(window):
+    if window is not None and (isinstance(window, bool) or not isinstance(window, int) or window < 1):
+        raise ValueError("window must be None or a positive int: the positions a token sees, its own included")
+    return window
 
 
 class KVCache:
     """Per-layer k and v caches of a causal attention stack: ``k[l]``, ``v[l]`` are (B, capacity, n_kv_head, dp) in the projection's
     own [B][N][H][d] layout (no permute), dp = head_dim rounded up to 32, 64 or 128 with zero columns past head_dim.  ``n_kv_head``
     (default n_head) is the number of key/value heads of a grouped-query stack: it must divide n_head, and the cache holds only those.
-    ``lengths``: device int32 (B,), the valid rows per batch element (read by the decode kernels, never by the host)."""
+    ``lengths``: device int32 (B,), the valid rows per batch element (read by the decode kernels, never by the host).
+    ``window`` (None, or an int >= 1): the stack's layers use SLIDING-WINDOW attention, every token sees the last ``window``
+    positions, its own included (Mistral's ``sliding_window``); the stack functions pass it to every device_ops call on this cache.
+    The cache still holds every row (no ring buffer): a PagedKVCache gives the memory back through release_behind_window."""
 
-    def __init__(self, n_layers, B, capacity, n_head, head_dim, dtype, device, n_kv_head=None):
+    def __init__(self, n_layers, B, capacity, n_head, head_dim, dtype, device, n_kv_head=None, window=None):
+        self.window = _check_cache_window(window)
         self.head_dim, self.dp = head_dim, device_ops.padded_head_dim(head_dim)
         self.capacity, self.n_head = capacity, n_head
         self.n_kv_head = n_head if n_kv_head is None else n_kv_head
@@ -109,25 +122,29 @@ class KVCache:
         """The keyword that makes a device_ops call a paged one: none for this cache, block_table= for a PagedKVCache."""
         return {} if self.block_table is None else dict(block_table=self.block_table)
 
+    def windowing(self):
+        """The keyword that makes a device_ops call a windowed one: none for a cache without a window (the unwindowed entry points)."""
+        return {} if self.window is None else dict(window=self.window)
+
     def reserve(self, n_tokens, rows=None):
         """Make sure the sequences own memory for ``n_tokens`` rows: a slab cache owns its ``capacity`` rows from the start."""
 
     def workspace(self, q):
-        key = tuple(q.shape)
+        key = (self.window,) + tuple(q.shape)   # (a windowed call splits on its window span: a buffer of its own size)
         if key not in self._workspaces:
-            self._workspaces[key] = device_ops.decode_workspace(q, self.k[0], "bnhd", **self.paging())
+            self._workspaces[key] = device_ops.decode_workspace(q, self.k[0], "bnhd", **self.paging(), **self.windowing())
         return self._workspaces[key]
 
     def extend_workspace(self, q):
-        key = ("extend",) + tuple(q.shape)   # (the extend call has a split policy of its own: never the decode call's buffer)
+        key = ("extend", self.window) + tuple(q.shape)   # (the extend call has a split policy of its own: never the decode call's buffer)
         if key not in self._workspaces:
-            self._workspaces[key] = device_ops.extend_workspace(q, self.k[0], "bnhd", **self.paging())
+            self._workspaces[key] = device_ops.extend_workspace(q, self.k[0], "bnhd", **self.paging(), **self.windowing())
         return self._workspaces[key]
 
     def ragged_workspace(self, q, cu_seqlens_q):
-        key = ("ragged",) + tuple(q.shape)   # (the ragged call sizes its own: the block map lives there)
+        key = ("ragged", self.window) + tuple(q.shape)   # (the ragged call sizes its own: the block map lives there)
         if key not in self._workspaces:
-            self._workspaces[key] = device_ops.ragged_workspace(q, self.k[0], cu_seqlens_q, "bnhd", **self.paging())
+            self._workspaces[key] = device_ops.ragged_workspace(q, self.k[0], cu_seqlens_q, "bnhd", **self.paging(), **self.windowing())
         return self._workspaces[key]
 
     def _pad(self, t):
@@ -141,9 +158,13 @@ class PagedKVCache(KVCache):
     ``page_size`` is a multiple of 128 rows.  ``n_pages`` defaults to B * max_pages (every sequence can reach ``capacity``) and may be
     smaller: sequences of different lengths then share what a slab cache would reserve B times over.  The host keeps a free list and
     each sequence's page list; ``lengths`` and ``length_bound`` are KVCache's.  The stack functions reserve what a call needs and pass
-    ``block_table`` to the same device_ops calls; results are bit for bit those of a KVCache of capacity max_pages * page_size."""
+    ``block_table`` to the same device_ops calls; results are bit for bit those of a KVCache of capacity max_pages * page_size.
+    ``window``: as in KVCache; release_behind_window then returns the pages that have fallen out of every future window to the pool,
+    so a long-running sequence holds O(window) pages.  ``released[b]`` counts the leading table slots sequence b no longer owns
+    (``pages[b]`` are the pages of the slots behind them)."""
 
-    def __init__(self, n_layers, B, capacity, n_head, head_dim, dtype, device, n_kv_head=None, page_size=128, n_pages=None):
+    def __init__(self, n_layers, B, capacity, n_head, head_dim, dtype, device, n_kv_head=None, page_size=128, n_pages=None, window=None):
+        self.window = _check_cache_window(window)
         self.head_dim, self.dp = head_dim, device_ops.padded_head_dim(head_dim)
         self.capacity, self.n_head = capacity, n_head
         self.n_kv_head = n_head if n_kv_head is None else n_kv_head
@@ -166,6 +187,7 @@ class PagedKVCache(KVCache):
         self._workspaces = {}
         self.free = list(range(self.n_pages - 1, -1, -1))   # (handed out from the end: page 0 first)
         self.pages = [[] for _ in range(B)]                 # the pages of each sequence, in order
+        self.released = [0] * B                             # leading table slots given back by release_behind_window
 
     def reserve(self, n_tokens, rows=None):
         """Make sure the sequences ``rows`` (default all) own pages for ``n_tokens`` cache rows each.  New pages come from the free list
@@ -176,17 +198,17 @@ class PagedKVCache(KVCache):
             raise ValueError(f"{n_tokens} rows exceed the table's {self.max_pages} pages of {self.page_size}")
         need = -(-n_tokens // self.page_size)
         rows = range(len(self.pages)) if rows is None else list(rows)
-        missing = sum(max(0, need - len(self.pages[b])) for b in rows)
+        missing = sum(max(0, need - self.released[b] - len(self.pages[b])) for b in rows)
         if missing > len(self.free):
             raise RuntimeError(f"page pool exhausted: {missing} more pages needed for {n_tokens} rows per sequence, {len(self.free)} of "
                                f"{self.n_pages} free ({missing - len(self.free)} short)")
         for b in rows:
-            own = self.pages[b]
-            if len(own) >= need:
+            own, gone = self.pages[b], self.released[b]   # (released leading slots stay unowned: the windowed kernels never read them)
+            if gone + len(own) >= need:
                 continue
-            while len(own) < need:
+            while gone + len(own) < need:
                 own.append(self.free.pop())
-            row = own + [0] * (self.max_pages - len(own))
+            row = [0] * gone + own + [0] * (self.max_pages - gone - len(own))
             self.block_table[b].copy_(torch.tensor(row, dtype=torch.int32))
 
     def release(self, b):
@@ -195,7 +217,32 @@ class PagedKVCache(KVCache):
         others."""
         self.free.extend(reversed(self.pages[b]))
         self.pages[b] = []
+        self.released[b] = 0
         self.lengths[b] = 0
+
+    def release_behind_window(self, lengths):
+        """Give back the pages no present or future query of a windowed cache can see.  ``lengths``: a host sequence of B ints, the rows
+        each sequence holds now (the caller's own bookkeeping: the cache keeps no lengths on the host, and none is read from the device
+        here).  Every later query of sequence b sits at a position >= lengths[b] and admits keys above its position - window, so a
+        page whose last row is <= lengths[b] - window is out of reach for good: it goes back to the free list (the next reserve may
+        hand it to anyone) and its table slot is counted in ``released[b]``.  Nothing is written to the device: the windowed kernels
+        start every key range at the window and never read those slots, whatever they hold.  Returns the number of pages freed."""
+        if self.window is None:
+            raise ValueError("release_behind_window needs a cache with a window: without one every row stays visible")
+        lengths = [int(n) for n in lengths]
+        if len(lengths) != len(self.pages):
+            raise ValueError(f"lengths must hold one int per sequence ({len(self.pages)})")
+        freed = 0
+        for b, n in enumerate(lengths):
+            # slot s holds rows s * page_size .. (s + 1) * page_size - 1: out of reach when (s + 1) * page_size - 1 <= n - window
+            behind = max(0, n - self.window + 1) // self.page_size
+            drop = min(behind - self.released[b], len(self.pages[b]))
+            if drop > 0:
+                self.free.extend(reversed(self.pages[b][:drop]))
+                del self.pages[b][:drop]
+                self.released[b] += drop
+                freed += drop
+        return freed
 
 
 def _project(x, wq, wk, wv, n_head):
@@ -217,10 +264,13 @@ def attention_stack_prefill(x, layers, n_head: int, cache: KVCache):
     """attention_stack(x, layers, n_head, causal=True) over a prompt x (B, P, E) that also (re)fills ``cache`` with every layer's k and
     v of the P tokens (lengths = P).  A grouped-query stack (wk, wv of shape (E, Hkv * d)) stores its Hkv heads, and the prompt's own
     attention reads those cache-shaped k and v in place (device_ops.flash_attn_fwd_gqa: no expanded copy).  Returns the stack's
-    output (B, P, E)."""
+    output (B, P, E).  A WINDOWED cache does not use that square forward, which has no window: its prompt goes through the extend
+    kernels as one piece (attention_stack_prefill_chunked with chunk = P), which append and attend through the window."""
     B, P, E = x.shape
     if P > cache.capacity:
         raise ValueError(f"prompt of {P} tokens exceeds the cache capacity {cache.capacity}")
+    if cache.window is not None:
+        return attention_stack_prefill_chunked(x, layers, n_head, cache, max(P, 1))
     d = E // n_head
     if cache.block_table is not None:
         cache.reserve(P)
@@ -275,7 +325,7 @@ def _step(x_new, layers, n_head: int, cache: KVCache, fused: bool):
             for dst, t in ((cache.k[li], k), (cache.v[li], v)):
                 dst.view(B * cache.capacity, hkv, cache.dp).index_copy_(0, rows, cache._pad(t).reshape(B * T, hkv, cache.dp))
         o, _ = device_ops.flash_attn_decode(q, cache.k[li], cache.v[li], new_len, causal=True, layout="bnhd",
-                                            workspace=cache.workspace(q), **new, **cache.paging())
+                                            workspace=cache.workspace(q), **new, **cache.paging(), **cache.windowing())
         x = x + (o.reshape(B * T, E).to(x.dtype) @ wo).view(B, T, E)
     cache.lengths.copy_(new_len)
     cache.length_bound += T
@@ -318,7 +368,7 @@ def attention_stack_extend(x_new, layers, n_head: int, cache: KVCache):
         q, k, v = _project(x, wq, wk, wv, n_head)
         _check_kv_heads(k, cache)
         o, _ = device_ops.flash_attn_extend(q, cache.k[li], cache.v[li], new_len, causal=True, layout="bnhd",
-                                            workspace=cache.extend_workspace(q), k_new=k, v_new=v, **cache.paging())
+                                            workspace=cache.extend_workspace(q), k_new=k, v_new=v, **cache.paging(), **cache.windowing())
         x = x + (o.reshape(B * T, E).to(x.dtype) @ wo).view(B, T, E)
     cache.lengths.copy_(new_len)
     cache.length_bound += T
@@ -355,7 +405,8 @@ def attention_stack_ragged(x_new, counts, layers, n_head: int, cache: KVCache):
         if k.shape[1] != cache.n_kv_head:
             raise ValueError(f"the layers project {k.shape[1]} kv heads, the cache holds {cache.n_kv_head}")
         o, _ = device_ops.flash_attn_ragged(q, cache.k[li], cache.v[li], cu, new_len, causal=True, layout="bnhd",
-                                            workspace=cache.ragged_workspace(q, cu), k_new=k, v_new=v, **cache.paging())
+                                            workspace=cache.ragged_workspace(q, cu), k_new=k, v_new=v, **cache.paging(),
+                                            **cache.windowing())
         x = x + o.reshape(T, E).to(x.dtype) @ wo
     cache.lengths.copy_(new_len)
     cache.length_bound += top
@@ -372,6 +423,9 @@ def attention_stack_prefill_chunked(x, layers, n_head: int, cache: KVCache, chun
         raise ValueError(f"prompt of {x.shape[1]} tokens exceeds the cache capacity {cache.capacity}")
     cache.lengths.zero_()
     cache.length_bound = 0
+    for b, gone in enumerate(getattr(cache, "released", ())):
+        if gone:   # (a windowed paged cache that gave its leading pages back: the sequence starts over and owns row 0 again)
+            cache.release(b)
     return torch.cat([attention_stack_extend(piece.contiguous(), layers, n_head, cache) for piece in x.split(chunk, 1)], dim=1)
 
 

@@ -153,4 +153,8 @@ const char* fa_mi355x_decode_last_error(void);
  * ragged entry points, part of this library and of this header, kept in a file of their own. */
 #include "flash_attn_mi355x_decode_ragged.h"
 
+/* Sliding-window attention (each token sees the last W positions only) for the decode, extend and ragged calls, slab or paged, fused
+ * with the append or not: nine entry points, part of this library and of this header, kept in a file of their own. */
+#include "flash_attn_mi355x_decode_window.h"
+
 #endif /* FLASH_ATTN_MI355X_DECODE_H */
