@@ -161,6 +161,13 @@ WINDOW_ABI = {
     "fa_mi355x_fwd_ragged_window": (_i, [_vp] * 11 + [_i] * 11 + [_f, _i, _i, _i, _vp]),
 }
 
+# the same for include/flash_attn_mi355x_decode_fp8.h (caches of e4m3 bytes with per-kv-head scales; tests/test_fp8_cpu.py)
+FP8_ABI = {
+    "fa_mi355x_fwd_decode_fp8": (_i, [_vp] * 12 + [_i] * 11 + [_f, _i, _i, _vp]),
+    "fa_mi355x_fwd_extend_fp8": (_i, [_vp] * 12 + [_i] * 11 + [_f, _i, _i, _vp]),
+    "fa_mi355x_append_fp8": (_i, [_vp] * 8 + [_i] * 11 + [_vp]),
+}
+
 
 def _typed(name: str, abi: dict) -> ctypes.CDLL:
     """The library with restype / argtypes of every symbol in ``abi`` set (once, on first load)."""
@@ -229,9 +236,9 @@ DECODE_NAME = "libflash_attn_mi355x_decode.so"
 
 
 def decode() -> ctypes.CDLL:
-    """libflash_attn_mi355x_decode.so (include/flash_attn_mi355x_decode.h, its _paged.h, its _ragged.h and its _window.h) with argtypes
-    set."""
-    return _typed(DECODE_NAME, {**DECODE_ABI, **PAGED_ABI, **RAGGED_ABI, **WINDOW_ABI})
+    """libflash_attn_mi355x_decode.so (include/flash_attn_mi355x_decode.h, its _paged.h, its _ragged.h, its _window.h and its _fp8.h)
+    with argtypes set."""
+    return _typed(DECODE_NAME, {**DECODE_ABI, **PAGED_ABI, **RAGGED_ABI, **WINDOW_ABI, **FP8_ABI})
 
 
 def decode_check(status: int) -> None:

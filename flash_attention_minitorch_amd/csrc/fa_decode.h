@@ -52,6 +52,16 @@
 // page); a wave skips a 32-key sub-tile wholly below its rows' lowest edge and masks per element only where a sub-tile straddles
 // an edge.  Everything is wave-uniform and derived from len on the device.  The WINDOW = false builds are the code they were
 // (DESIGN.md "Window").
+//
+// FP8 caches (the FP8 builds of the split, extend and combine kernels, and append_fp8_kernel; include/flash_attn_mi355x_decode_fp8.h):
+// the caches hold OCP e4m3fn bytes and the real value of an element of kv head h is scale[h] * e4m3 (k_scale / v_scale, fp32 arrays
+// of Hkv entries read on the device).  Every e4m3 value is a bf16 value, so a tile goes HBM -> registers as bytes and is widened to
+// the bf16 LDS image on its way from the staging registers to LDS (Fp8Stager): the image, the fragments, the MFMAs, the softmax and
+// the split / combine are those of the bf16 builds, which is why an fp8 call returns bit for bit what the bf16 call returns on the
+// cache cast to bf16.  The scales never touch an element: k_scale[hkv] multiplies tau once per workgroup (the exp2 constant, the
+// lse, the combine kernel's weights), v_scale[hkv] multiplies the final 1 / l (the one-split store and the combine kernel); the
+// partials in the workspace stay unscaled.  bf16 queries only, no window, no ragged form.  The FP8 = false builds are the code
+// they were (DESIGN.md "FP8 cache").
 #pragma once
 #include "fa_common.h"
 
@@ -89,7 +99,15 @@ struct RaggedArgs : DecodeArgs {
   const int* map;      // [nqb][2] (sequence or -1: unused, row block within the sequence), written by ragged_schedule_kernel
   int nseq, ntok;      // sequences; rows of the packed buffers
 };
-template <bool RAGGED> using DecodeArgsOf = typename std::conditional<RAGGED, RaggedArgs, DecodeArgs>::type;
+// The argument of the FP8 builds, as RaggedArgs: the two per-kv-head scales (null: all ones).
+struct Fp8Args : DecodeArgs {
+  const float* k_scale;   // [Hkv] or null
+  const float* v_scale;   // [Hkv] or null
+};
+template <bool RAGGED, bool FP8 = false>
+using DecodeArgsOf = typename std::conditional<FP8, Fp8Args, typename std::conditional<RAGGED, RaggedArgs, DecodeArgs>::type>::type;
+// (positive and finite is the caller's contract: the kernels do not check a scale)
+FA_DEV float scale_of(const float* scale, int hkv) { return scale ? scale[hkv] : 1.0f; }
 
 FA_DEV int clamp_len(const int* seqlens, int Ncap, int b) {
   const int len = seqlens ? seqlens[b] : Ncap;
@@ -137,6 +155,45 @@ template <typename S> FA_DEV void zero_below(S& st, int n) {
     if (row + i * S::RSTEP < n) st.regs[i] = u32x4{0u, 0u, 0u, 0u};
 }
 
+// FP8 builds: TileStager<bf16_t, D, DEC_ROWS, 256> for rows of one byte per element.  The thread -> (row, 16-byte bf16 chunk) map and
+// lds_off are that stager's own (init runs it and halves its byte offsets: row * ld + 8 * ch); a chunk is loaded as the 8 cache
+// bytes that become it, stays 8 bytes until store, and is widened there: v_cvt_scalef32_pk_bf16_fp8 with a scale of 1, one
+// instruction per pair of elements, exact for all 256 codes (every e4m3 value is a bf16 value; both NaN codes give a bf16 NaN).
+template <int D> struct Fp8Stager {
+  using B16 = TileStager<bf16_t, D, DEC_ROWS, 256>;
+  static constexpr int NCH = B16::NCH, PER = B16::PER, RSTEP = B16::RSTEP;
+  static_assert(NCH % 256 == 0, "every thread has a chunk");
+  typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
+  u32x2 regs[PER];
+  int voff, lds_off, ldb;   // as TileStager's, in cache bytes
+  static constexpr bool live = true;
+  FA_DEV void init(int tid, int ld) {
+    B16 b;
+    b.init(tid, ld);
+    voff = b.voff >> 1;
+    lds_off = b.lds_off;
+    ldb = ld;
+  }
+  FA_DEV void store(lds_char* tile) const {
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+      const u32x4 w = {__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(regs[i][0], 1.0f, false)),
+                       __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(regs[i][0], 1.0f, true)),
+                       __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(regs[i][1], 1.0f, false)),
+                       __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(regs[i][1], 1.0f, true))};
+      *FA_LDS(u32x4, tile + lds_off + Atom<bf16_t>::template off<D>(i * RSTEP, 0)) = w;
+    }
+  }
+};
+
+// load_rows for the byte rows of an fp8 cache: 8 bytes per chunk, the same row offsets under the resource's range check
+template <int D> FA_DEV void load_rows(Fp8Stager<D>& st, rsrc_t rs, int row0) {
+#pragma unroll
+  for (int i = 0; i < Fp8Stager<D>::PER; ++i)
+    st.regs[i] = __builtin_bit_cast(typename Fp8Stager<D>::u32x2,
+                                    __builtin_amdgcn_raw_buffer_load_b64(rs, st.voff + (row0 + i * Fp8Stager<D>::RSTEP) * st.ldb, 0, 0));
+}
+
 // Paged cache: logical row j of batch element b is row j % page_size of page table[b][j / page_size].  page_size is a multiple of
 // DEC_ROWS and every chunk starts on a multiple of it, so a super tile lies inside one page: the tile at logical row t0 goes through
 // a resource of its page's (kv head) slice sized to the page's valid rows, min(page_size, len - page start), with the tile's row
@@ -156,7 +213,7 @@ struct PageWalk {
     off = t0 - slot * a.page_size;
     next = id(a);
   }
-  // loads the tile at (slot, off) and steps to the one after it, fetching its id if there is one (more)
+  // loads the tile at (slot, off) and steps to the one after it, fetching its id if there is one (more); T: the CACHE's element
   template <typename T, int D, typename S> FA_DEV void load(const DecodeArgs& a, S& sk, S& sv, size_t hoff, int len, bool more) {
     const int rows = min(a.page_size, len - slot * a.page_size);
     const uint32_t bytes = ((uint32_t)(rows - 1) * a.kv_ld + D) * (uint32_t)sizeof(T);
@@ -176,9 +233,13 @@ struct PageWalk {
 // few super tiles, so its prologue is not free: DESIGN.md "Decode").  PAGED: the cache is a pool read through a block table (PageWalk).
 // WINDOW: a sliding window of a.window keys (causal).  The key range belongs to the 32-row BLOCK, not to the call: wedge is the
 // lowest key the block's first row admits, so every block walks about W + 32 + 127 keys whatever Nq.
-template <typename T, int D, bool GROUPED, bool PAGED = false, bool WINDOW = false>
-__global__ void __launch_bounds__(256) decode_split_kernel(DecodeArgs a) {
+// FP8: the caches hold e4m3 bytes (C, the cache's element type, is a byte) and a carries the two scales; T, the queries' type and
+// the type of the LDS image, is bf16.  tau8 = tau * k_scale[hkv] stands for tau wherever the kernel uses it.
+template <typename T, int D, bool GROUPED, bool PAGED = false, bool WINDOW = false, bool FP8 = false>
+__global__ void __launch_bounds__(256) decode_split_kernel(DecodeArgsOf<false, FP8> a) {
+  static_assert(!FP8 || (std::is_same<T, bf16_t>::value && GROUPED && !WINDOW), "fp8 caches: bf16 queries, the grouped form, no window");
   using A = Atom<T>;
+  typedef typename std::conditional<FP8, uint8_t, T>::type C;
   typedef typename A::frag frag;
   constexpr int KC = D / 16, DT = D / 32;
   constexpr int TB = A::template tile_bytes<D>(DEC_ROWS);
@@ -206,7 +267,11 @@ __global__ void __launch_bounds__(256) decode_split_kernel(DecodeArgs a) {
   const int G = GROUPED ? a.G : 1;
   const int q0 = qb * 32, rho = q0 + r, qi = GROUPED ? row_query(a, rho) : rho, hd = hkv * G + (rho - qi * G);
   const bool live = rho < G * a.Nq;
-  const float c = a.tau * LOG2E;
+  // (a macro, as FA_NQ below: the other builds read a.tau where they always did)
+  float tau8 = 0.f;
+  if constexpr (FP8) tau8 = a.tau * scale_of(a.k_scale, hkv);
+#define FA_TAU (FP8 ? tau8 : a.tau)
+  const float c = FA_TAU * LOG2E;
 
   f32x16 acc_o[DT];
 #pragma unroll
@@ -218,9 +283,9 @@ __global__ void __launch_bounds__(256) decode_split_kernel(DecodeArgs a) {
     const uint32_t esz = sizeof(T);
     const uint32_t q_bytes = (uint32_t)a.q_bstride * esz;
     const rsrc_t qrs = make_rsrc(reinterpret_cast<const T*>(a.q) + (size_t)b * a.q_bstride, q_bytes);
-    const uint32_t kv_bytes = ((uint32_t)(len - 1) * a.kv_ld + D) * esz;
-    const rsrc_t krs = make_rsrc(reinterpret_cast<const T*>(a.k) + kvoff, kv_bytes);   // (the slab's: unused by a paged build)
-    const rsrc_t vrs = make_rsrc(reinterpret_cast<const T*>(a.v) + kvoff, kv_bytes);
+    const uint32_t kv_bytes = ((uint32_t)(len - 1) * a.kv_ld + D) * (uint32_t)sizeof(C);
+    const rsrc_t krs = make_rsrc(reinterpret_cast<const C*>(a.k) + kvoff, kv_bytes);   // (the slab's: unused by a paged build)
+    const rsrc_t vrs = make_rsrc(reinterpret_cast<const C*>(a.v) + kvoff, kv_bytes);
     PageWalk pw;
 
     frag qf[KC];
@@ -230,7 +295,7 @@ __global__ void __launch_bounds__(256) decode_split_kernel(DecodeArgs a) {
 
     const LaneAddr ra = A::template row_addr<D>(lane);
     const LaneAddr ta = A::template tr_addr<D>(lane);
-    TileStager<T, D, DEC_ROWS, 256> sk, sv;
+    typename std::conditional<FP8, Fp8Stager<D>, TileStager<T, D, DEC_ROWS, 256>>::type sk, sv;
     sk.init(tid, a.kv_ld);
     sv.init(tid, a.kv_ld);
     // causal: query i sits at position len - Nq + i and sees keys j <= len - Nq + i (bottom-right aligned); the block's rows span
@@ -239,7 +304,7 @@ __global__ void __launch_bounds__(256) decode_split_kernel(DecodeArgs a) {
     const int pos_lo = len - a.Nq + (GROUPED ? row_query(a, q0) : q0), pos_hi = len - a.Nq + (GROUPED ? row_query(a, q0 + 31) : q0 + 31);
     if constexpr (PAGED) {
       pw.init(a, b, c0);
-      pw.template load<T, D>(a, sk, sv, kvoff, len, c0 + DEC_ROWS < c1);
+      pw.template load<C, D>(a, sk, sv, kvoff, len, c0 + DEC_ROWS < c1);
     } else {
       load_rows(sk, krs, c0);
       load_rows(sv, vrs, c0);
@@ -256,7 +321,7 @@ __global__ void __launch_bounds__(256) decode_split_kernel(DecodeArgs a) {
       sv.store(tv);
       if (t0 + DEC_ROWS < c1) {
         if constexpr (PAGED) {
-          pw.template load<T, D>(a, sk, sv, kvoff, len, t0 + 2 * DEC_ROWS < c1);
+          pw.template load<C, D>(a, sk, sv, kvoff, len, t0 + 2 * DEC_ROWS < c1);
         } else {
           load_rows(sk, krs, t0 + DEC_ROWS);
           load_rows(sv, vrs, t0 + DEC_ROWS);
@@ -351,7 +416,8 @@ __global__ void __launch_bounds__(256) decode_split_kernel(DecodeArgs a) {
   if (!live) return;
   const size_t bhq = (size_t)b * a.H + hd;
   if (a.nsplit == 1) {   // final: out = O / l, lse = m * tau + ln l; a row without an admissible key: out = 0, lse = -inf
-    const float inv = (l_tot > 0.f) ? 1.0f / l_tot : 0.f;
+    float inv = (l_tot > 0.f) ? 1.0f / l_tot : 0.f;
+    if constexpr (FP8) inv *= scale_of(a.v_scale, hkv);   // (the scale of V: once per row, on 1 / l)
     float* orow = a.out + (size_t)b * a.q_bstride + (size_t)hd * a.q_hstride + (size_t)qi * a.q_ld;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt)
@@ -360,7 +426,7 @@ __global__ void __launch_bounds__(256) decode_split_kernel(DecodeArgs a) {
         f32x4 val = {acc_o[dt][4 * g] * inv, acc_o[dt][4 * g + 1] * inv, acc_o[dt][4 * g + 2] * inv, acc_o[dt][4 * g + 3] * inv};
         *reinterpret_cast<f32x4*>(orow + 32 * dt + 8 * g + 4 * h) = val;
       }
-    if (h == 0 && a.lse) a.lse[bhq * a.Nq + qi] = (l_tot > 0.f) ? m_all * a.tau + __logf(l_tot) : -INFINITY;
+    if (h == 0 && a.lse) a.lse[bhq * a.Nq + qi] = (l_tot > 0.f) ? m_all * FA_TAU + __logf(l_tot) : -INFINITY;
   } else {
     const size_t pr = (bhq * a.nsplit + split) * a.Nq + qi;
     float* prow = a.part_o + pr * D;
@@ -374,6 +440,7 @@ __global__ void __launch_bounds__(256) decode_split_kernel(DecodeArgs a) {
     if (h == 0) *reinterpret_cast<f32x2*>(a.part_ml + 2 * pr) = f32x2{m_all, l_tot};
   }
 }
+#undef FA_TAU
 
 // ---- extend: any number of new queries against the cache ---------------------------------------------------------------------------
 // The split kernel's semantics for any Nq >= 1 with the roles of its waves swapped: a workgroup = one (batch*kv head, key chunk,
@@ -391,9 +458,12 @@ constexpr int EXT_BLOCK = 128;   // rows per workgroup: 32 per wave
 // WINDOW: a sliding window of a.window keys (causal).  wedge, the lowest key the 128-row block's first row admits, is to the
 // start of the block's key range what blk_hi is to its end: a block walks about W + 128 + 127 keys wherever it sits in a long
 // input.  Each wave then skips and masks by its own 32 rows' edges.
-template <typename T, int D, bool PAGED = false, bool RAGGED = false, bool WINDOW = false>
-__global__ void __launch_bounds__(256) extend_split_kernel(DecodeArgsOf<RAGGED> a) {
+// FP8: as in decode_split_kernel (C: a byte; tau8 for tau; v_scale on the final 1 / l).
+template <typename T, int D, bool PAGED = false, bool RAGGED = false, bool WINDOW = false, bool FP8 = false>
+__global__ void __launch_bounds__(256) extend_split_kernel(DecodeArgsOf<RAGGED, FP8> a) {
+  static_assert(!FP8 || (std::is_same<T, bf16_t>::value && !RAGGED && !WINDOW), "fp8 caches: bf16 queries, no ragged form, no window");
   using A = Atom<T>;
+  typedef typename std::conditional<FP8, uint8_t, T>::type C;
   typedef typename A::frag frag;
   constexpr int KC = D / 16, DT = D / 32;
   constexpr int TB = A::template tile_bytes<D>(DEC_ROWS);
@@ -432,7 +502,10 @@ __global__ void __launch_bounds__(256) extend_split_kernel(DecodeArgsOf<RAGGED> 
   const int q0 = qb * EXT_BLOCK + 32 * w, rho = q0 + r, qi = row_query(a, rho), hd = hkv * a.G + (rho - qi * a.G);
   const bool live = rho < rows;
   const bool wave_live = q0 < rows;   // (wave-uniform)
-  const float c = a.tau * LOG2E;
+  float tau8 = 0.f;
+  if constexpr (FP8) tau8 = a.tau * scale_of(a.k_scale, hkv);
+#define FA_TAU (FP8 ? tau8 : a.tau)
+  const float c = FA_TAU * LOG2E;
   // causal: the last key any row of the block sees is the position of its last row (of its last REAL row: rows >= G * Nq see nothing)
   const int blk_hi = len - FA_NQ + row_query(a, min(qb * EXT_BLOCK + EXT_BLOCK, rows) - 1);
   const int cend = a.causal ? min(c1, blk_hi + 1) : c1;
@@ -448,9 +521,9 @@ __global__ void __launch_bounds__(256) extend_split_kernel(DecodeArgsOf<RAGGED> 
     // (ragged: the resource of the sequence's own nq_b * H * D elements of the packed q)
     const uint32_t q_bytes = RAGGED ? (uint32_t)nq_ * (uint32_t)a.q_ld * esz : (uint32_t)a.q_bstride * esz;
     const rsrc_t qrs = make_rsrc(reinterpret_cast<const T*>(a.q) + (RAGGED ? (size_t)row0 * a.q_ld : (size_t)b * a.q_bstride), q_bytes);
-    const uint32_t kv_bytes = ((uint32_t)(len - 1) * a.kv_ld + D) * esz;
-    const rsrc_t krs = make_rsrc(reinterpret_cast<const T*>(a.k) + kvoff, kv_bytes);   // (the slab's: unused by a paged build)
-    const rsrc_t vrs = make_rsrc(reinterpret_cast<const T*>(a.v) + kvoff, kv_bytes);
+    const uint32_t kv_bytes = ((uint32_t)(len - 1) * a.kv_ld + D) * (uint32_t)sizeof(C);
+    const rsrc_t krs = make_rsrc(reinterpret_cast<const C*>(a.k) + kvoff, kv_bytes);   // (the slab's: unused by a paged build)
+    const rsrc_t vrs = make_rsrc(reinterpret_cast<const C*>(a.v) + kvoff, kv_bytes);
     PageWalk pw;
 
     frag qf[KC];
@@ -460,7 +533,7 @@ __global__ void __launch_bounds__(256) extend_split_kernel(DecodeArgsOf<RAGGED> 
 
     const LaneAddr ra = A::template row_addr<D>(lane);
     const LaneAddr ta = A::template tr_addr<D>(lane);
-    TileStager<T, D, DEC_ROWS, 256> sk, sv;
+    typename std::conditional<FP8, Fp8Stager<D>, TileStager<T, D, DEC_ROWS, 256>>::type sk, sv;
     sk.init(tid, a.kv_ld);
     sv.init(tid, a.kv_ld);
     // the wave's rows span the positions pos_lo .. pos_hi (wave-uniform; rows past G * Nq may push pos_hi up, which only keeps a
@@ -469,7 +542,7 @@ __global__ void __launch_bounds__(256) extend_split_kernel(DecodeArgsOf<RAGGED> 
     const int pos_lo = len - FA_NQ + row_query(a, q0), pos_hi = len - FA_NQ + row_query(a, q0 + 31);
     if constexpr (PAGED) {
       pw.init(a, b, c0);
-      pw.template load<T, D>(a, sk, sv, kvoff, len, c0 + DEC_ROWS < cend);
+      pw.template load<C, D>(a, sk, sv, kvoff, len, c0 + DEC_ROWS < cend);
     } else {
       load_rows(sk, krs, c0);
       load_rows(sv, vrs, c0);
@@ -486,7 +559,7 @@ __global__ void __launch_bounds__(256) extend_split_kernel(DecodeArgsOf<RAGGED> 
       sv.store(tv);
       if (t0 + DEC_ROWS < cend) {
         if constexpr (PAGED) {
-          pw.template load<T, D>(a, sk, sv, kvoff, len, t0 + 2 * DEC_ROWS < cend);
+          pw.template load<C, D>(a, sk, sv, kvoff, len, t0 + 2 * DEC_ROWS < cend);
         } else {
           load_rows(sk, krs, t0 + DEC_ROWS);
           load_rows(sv, vrs, t0 + DEC_ROWS);
@@ -551,7 +624,8 @@ __global__ void __launch_bounds__(256) extend_split_kernel(DecodeArgsOf<RAGGED> 
   // (ragged: out, lse and the partials by packed row row0 + qi, as one batch element of a.Nq = ntok queries)
   const size_t bhq = RAGGED ? (size_t)hd : (size_t)b * a.H + hd;
   if (a.nsplit == 1) {   // final: out = O / l, lse = m * tau + ln l; a row without an admissible key: out = 0, lse = -inf
-    const float inv = (l_tot > 0.f) ? 1.0f / l_tot : 0.f;
+    float inv = (l_tot > 0.f) ? 1.0f / l_tot : 0.f;
+    if constexpr (FP8) inv *= scale_of(a.v_scale, hkv);   // (the scale of V: once per row, on 1 / l)
     float* orow = a.out + (RAGGED ? 0 : (size_t)b * a.q_bstride) + (size_t)hd * a.q_hstride + (size_t)(RAGGED ? row0 + qi : qi) * a.q_ld;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt)
@@ -560,7 +634,7 @@ __global__ void __launch_bounds__(256) extend_split_kernel(DecodeArgsOf<RAGGED> 
         f32x4 val = {acc_o[dt][4 * g] * inv, acc_o[dt][4 * g + 1] * inv, acc_o[dt][4 * g + 2] * inv, acc_o[dt][4 * g + 3] * inv};
         *reinterpret_cast<f32x4*>(orow + 32 * dt + 8 * g + 4 * h) = val;
       }
-    if (h == 0 && a.lse) a.lse[bhq * a.Nq + (RAGGED ? row0 + qi : qi)] = (l_tot > 0.f) ? m_run * a.tau + __logf(l_tot) : -INFINITY;
+    if (h == 0 && a.lse) a.lse[bhq * a.Nq + (RAGGED ? row0 + qi : qi)] = (l_tot > 0.f) ? m_run * FA_TAU + __logf(l_tot) : -INFINITY;
   } else {
     const size_t pr = (bhq * a.nsplit + split) * a.Nq + (RAGGED ? row0 + qi : qi);
     float* prow = a.part_o + pr * D;
@@ -575,6 +649,7 @@ __global__ void __launch_bounds__(256) extend_split_kernel(DecodeArgsOf<RAGGED> 
   }
 }
 #undef FA_NQ
+#undef FA_TAU
 
 // out[row] = sum_s O_s 2^(c (m_s - M)) / sum_s l_s 2^(c (m_s - M)), M = max_s m_s.  A workgroup = one (bh, row): thread (g, j) takes
 // columns 4g .. 4g+3 of the splits j, j + S, j + 2S, ... and the S partial sums of a column group are added in the order j = 0 .. S-1
@@ -582,8 +657,9 @@ __global__ void __launch_bounds__(256) extend_split_kernel(DecodeArgsOf<RAGGED> 
 // RAGGED: one batch element of Nq = ntok packed rows; a row in front of the first sequence or behind the last one (the unused tail
 // of the packed buffers) has no partials and is neither read nor written.  (A cu that is not non-decreasing can make an earlier
 // sequence end past the last one's end: its rows there are then left as they were, where a one-split call writes them.)
-template <int D, bool RAGGED = false>
-__global__ void __launch_bounds__(256) decode_combine_kernel(DecodeArgsOf<RAGGED> a) {
+// FP8: the row's kv head is hd / a.G; its k_scale multiplies tau (the weights and the lse), its v_scale the final 1 / l.
+template <int D, bool RAGGED = false, bool FP8 = false>
+__global__ void __launch_bounds__(256) decode_combine_kernel(DecodeArgsOf<RAGGED, FP8> a) {
   constexpr int G = D / 4, S = 256 / G;
   __shared__ f32x4 red_o[256];
   __shared__ float red_m[256], red_l[256];
@@ -596,7 +672,10 @@ __global__ void __launch_bounds__(256) decode_combine_kernel(DecodeArgsOf<RAGGED
     if (row < s0 || row >= sl + nl) return;
   }
   const int b = bh / a.H, hd = bh - b * a.H;
-  const float c = a.tau * LOG2E;
+  float tau8 = 0.f;
+  if constexpr (FP8) tau8 = a.tau * scale_of(a.k_scale, hd / a.G);
+#define FA_TAU (FP8 ? tau8 : a.tau)
+  const float c = FA_TAU * LOG2E;
   const size_t p0 = (size_t)bh * a.nsplit * a.Nq + row;   // partial row of split s: p0 + s * Nq
   float m = -INFINITY;
   for (int s = j; s < a.nsplit; s += S) m = fmaxf(m, a.part_ml[2 * (p0 + (size_t)s * a.Nq)]);
@@ -624,11 +703,13 @@ __global__ void __launch_bounds__(256) decode_combine_kernel(DecodeArgsOf<RAGGED
     acc += red_o[u * G + g];
     l += red_l[u * G + g];
   }
-  const float inv = (l > 0.f) ? 1.0f / l : 0.f;
+  float inv = (l > 0.f) ? 1.0f / l : 0.f;
+  if constexpr (FP8) inv *= scale_of(a.v_scale, hd / a.G);
   float* orow = a.out + (size_t)b * a.q_bstride + (size_t)hd * a.q_hstride + (size_t)row * a.q_ld;
   *reinterpret_cast<f32x4*>(orow + 4 * g) = acc * inv;
-  if (g == 0 && a.lse) a.lse[(size_t)bh * a.Nq + row] = (l > 0.f) ? m_all * a.tau + __logf(l) : -INFINITY;
+  if (g == 0 && a.lse) a.lse[(size_t)bh * a.Nq + row] = (l > 0.f) ? m_all * FA_TAU + __logf(l) : -INFINITY;
 }
+#undef FA_TAU
 
 // ---- ragged: the block map -------------------------------------------------------------------------------------------------------
 // One workgroup turns cu into the block map of the ragged extend kernel: for b = 0, 1, ... in order, one entry (b, qb) for each of
@@ -753,6 +834,90 @@ __global__ void __launch_bounds__(256) decode_append_kernel(typename std::condit
   }
   *reinterpret_cast<vec*>(reinterpret_cast<U*>(a.k) + dst) = kk;
   *reinterpret_cast<vec*>(reinterpret_cast<U*>(a.v) + dst) = vv;
+}
+
+// ---- append into an fp8 cache: quantise on the way -----------------------------------------------------------------------------
+// The uniform append above for bf16 sources and caches of e4m3 bytes: the same placement (row L_b - Nq + i, nothing below row 0, the
+// paged lookup with clamped ids), zero BYTES in columns d_new .. D-1, and for an element x of kv head h
+//     code = rne_e4m3(clamp(fp32(x) * (1.0f / scale[h]), -448, 448))
+// with the reciprocal and the product each correctly rounded in fp32 (an IEEE division: the build has no fast-math).  The clamp
+// sits in front of the conversion, so overflow saturates to +-448 (0x7E / 0xFE) and never reaches the NaN code; a NaN input stores
+// 0x7F.  v_cvt_pk_fp8_f32 rounds to nearest even, denormals included.
+struct Fp8AppendArgs : AppendArgs {
+  const float* k_scale;   // [Hkv] or null (all ones)
+  const float* v_scale;
+};
+
+FA_DEV float fp8_prescale(float x, float rcp) {
+  return (x != x) ? x : __builtin_fminf(__builtin_fmaxf(x * rcp, -448.0f), 448.0f);   // (a NaN stays one: min / max would drop it)
+}
+// two elements -> two codes in the low (hi = false) or high half of `old`
+FA_DEV uint32_t fp8_pack2(float x0, float x1, float rcp, uint32_t old, bool hi) {
+  const float p0 = fp8_prescale(x0, rcp), p1 = fp8_prescale(x1, rcp);
+  uint32_t w = hi ? (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(p0, p1, (int)old, true)
+                  : (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(p0, p1, (int)old, false);
+  const int sh = hi ? 16 : 0;   // (the conversion gives a NaN the code 0xFF: the format's canonical NaN byte is stored instead)
+  if (p0 != p0) w = (w & ~(0xffu << sh)) | (0x7fu << sh);
+  if (p1 != p1) w = (w & ~(0xff00u << sh)) | (0x7f00u << sh);
+  return w;
+}
+
+// A lane = E consecutive elements of one new row, of K and of V: E = 8 (one 16-byte load and one 8-byte store each; the host picks it
+// when d_new is a multiple of 8, the sources are 16-byte aligned and the caches 8-byte aligned) or E = 1.
+template <int E, bool PAGED = false>
+__global__ void __launch_bounds__(256) append_fp8_kernel(Fp8AppendArgs a) {
+  static_assert(E == 1 || E == 8, "a lane moves one element or eight");
+  const long lane = (long)blockIdx.x * 256 + threadIdx.x;
+  if (lane >= a.lanes) return;
+  const long row = lane >> a.ch_shift;           // source row (b, i, hkv) or (b, hkv, i)
+  const int col = (int)(lane - (row << a.ch_shift)) * E;
+  const int inner = a.bnhd ? a.Hkv : a.Nq;
+  const long outer = row / inner;
+  const int in = (int)(row - outer * inner);
+  const int mid = a.bnhd ? a.Nq : a.Hkv;
+  const int b = (int)(outer / mid);
+  const int md = (int)(outer - (long)b * mid);
+  const int i = a.bnhd ? md : in, hkv = a.bnhd ? in : md;
+  const int pos = clamp_len(a.seqlens, a.Ncap, b) - a.Nq + i;
+  if (pos < 0) return;
+  const size_t src = (size_t)row * a.d_new + col;
+  size_t dst;
+  if constexpr (PAGED) {
+    const int slot = pos / a.page_size;
+    const int page = min(max(a.table[(size_t)b * a.max_pages + slot], 0), a.num_pages - 1);
+    dst = (size_t)page * a.page_stride + (size_t)hkv * a.kv_hstride + (size_t)(pos - slot * a.page_size) * a.kv_ld + col;
+  } else {
+    dst = (size_t)b * a.kv_bstride + (size_t)hkv * a.kv_hstride + (size_t)pos * a.kv_ld + col;
+  }
+  const float rk = 1.0f / scale_of(a.k_scale, hkv), rv = 1.0f / scale_of(a.v_scale, hkv);
+  uint8_t* kd = reinterpret_cast<uint8_t*>(a.k) + dst;
+  uint8_t* vd = reinterpret_cast<uint8_t*>(a.v) + dst;
+  if constexpr (E == 8) {
+    typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
+    u32x2 kk = {0u, 0u}, vv = {0u, 0u};
+    if (col < a.d_new) {   // (d_new is a multiple of 8, so the whole lane is inside the row)
+      const bf16x8 ks = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const bf16_t*>(a.k_new) + src);
+      const bf16x8 vs = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const bf16_t*>(a.v_new) + src);
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        kk[j] = fp8_pack2((float)ks[4 * j], (float)ks[4 * j + 1], rk, 0u, false);
+        kk[j] = fp8_pack2((float)ks[4 * j + 2], (float)ks[4 * j + 3], rk, kk[j], true);
+        vv[j] = fp8_pack2((float)vs[4 * j], (float)vs[4 * j + 1], rv, 0u, false);
+        vv[j] = fp8_pack2((float)vs[4 * j + 2], (float)vs[4 * j + 3], rv, vv[j], true);
+      }
+    }
+    *reinterpret_cast<u32x2*>(kd) = kk;
+    *reinterpret_cast<u32x2*>(vd) = vv;
+  } else {
+    uint8_t kk = 0, vv = 0;
+    if (col < a.d_new) {
+      const float xk = (float)reinterpret_cast<const bf16_t*>(a.k_new)[src], xv = (float)reinterpret_cast<const bf16_t*>(a.v_new)[src];
+      kk = (uint8_t)fp8_pack2(xk, xk, rk, 0u, false);
+      vv = (uint8_t)fp8_pack2(xv, xv, rv, 0u, false);
+    }
+    *kd = kk;
+    *vd = vv;
+  }
 }
 
 }  // namespace fa

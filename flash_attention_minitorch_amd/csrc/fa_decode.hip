@@ -2,7 +2,8 @@
 // argument checks, the split policies (decode: 32-row blocks, at most 128 queries; extend: 128-row blocks, any number; ragged: the
 // extend policy on an upper bound of the row blocks) and the launches of the kernels of fa_decode.h.  A paged call (a pool and a
 // block table) takes the contiguous call's policy at Ncap = max_pages * page_size.  A windowed call (_window.h) takes the three
-// policies on its window span (span_keys) instead of Ncap.
+// policies on its window span (span_keys) instead of Ncap.  An fp8 call (_fp8.h: caches of e4m3 bytes, per-kv-head scales) takes the
+// bf16 call's policy and workspace for the same arguments; its cache bounds count one byte per element.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -174,6 +175,42 @@ template <typename T> int launch_d(const fa::DecodeArgs& a, int BH, int d, hipSt
   }
 }
 
+// An fp8 call's scales (null: a bf16 or fp32 cache).
+struct Fp8 {
+  const float* k_scale;
+  const float* v_scale;
+};
+
+// The FP8 builds: bf16 queries, the grouped form of the split kernel (as the paged build takes it for G = 1), slab or paged.
+template <int D> int launch_fp8(fa::Fp8Args a, int BH, bool extend, hipStream_t st) {
+  using T = fa::bf16_t;
+  const dim3 grid((unsigned)split_grid(a.items, a.nqb));
+  if (extend && a.table)
+    hipLaunchKernelGGL((fa::extend_split_kernel<T, D, true, false, false, true>), grid, dim3(256), 0, st, a);
+  else if (extend)
+    hipLaunchKernelGGL((fa::extend_split_kernel<T, D, false, false, false, true>), grid, dim3(256), 0, st, a);
+  else if (a.table)
+    hipLaunchKernelGGL((fa::decode_split_kernel<T, D, true, true, false, true>), grid, dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL((fa::decode_split_kernel<T, D, true, false, false, true>), grid, dim3(256), 0, st, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return set_err(FA_ERR_HIP, extend ? "extend_split_kernel (fp8) launch" : "decode_split_kernel (fp8) launch", e);
+  if (a.nsplit > 1) {
+    hipLaunchKernelGGL((fa::decode_combine_kernel<D, false, true>), dim3((unsigned)((long)BH * a.Nq)), dim3(256), 0, st, a);
+    e = hipGetLastError();
+    if (e != hipSuccess) return set_err(FA_ERR_HIP, "decode_combine_kernel (fp8) launch", e);
+  }
+  return FA_OK;
+}
+
+int launch_fp8_d(const fa::Fp8Args& a, int BH, int d, bool extend, hipStream_t st) {
+  switch (d) {
+    case 32: return launch_fp8<32>(a, BH, extend, st);
+    case 64: return launch_fp8<64>(a, BH, extend, st);
+    default: return launch_fp8<128>(a, BH, extend, st);
+  }
+}
+
 // A paged call's block table and pool geometry (null: the contiguous call).
 struct Paging {
   const int* table;
@@ -199,18 +236,19 @@ int check_pages(const Paging& p, int* Ncap) {
 }
 
 // (a buffer load's row offset is a 32-bit byte count inside one page; page base addresses are 64-bit, so the pool may be any size)
-int check_page_bytes(int page_size, int Hkv, int d, int dtype) {
-  const long esz = dtype == FA_DTYPE_BF16 ? 2 : 4;
+// (fp8: the pool holds one byte per element whatever dtype, the queries' type, says)
+int check_page_bytes(int page_size, int Hkv, int d, int dtype, bool fp8 = false) {
+  const long esz = fp8 ? 1 : dtype == FA_DTYPE_BF16 ? 2 : 4;
   if ((long)page_size * Hkv * d * esz >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "one page of the pool must stay under 2 GiB");
   return FA_OK;
 }
 
 // The argument checks of fa_mi355x_fwd_decode_gqa, or (extend) of fa_mi355x_fwd_extend: FA_OK, or the error with its message set.
 // page_size > 0: a paged call with Ncap = max_pages * page_size, where the bound on a batch element of the cache is one on a page.
-// window: the splits are those of the window span.
+// window: the splits are those of the window span.  fp8: the caches hold one byte per element and the queries are bf16.
 int check_decode(const void* q, const void* k_cache, const void* v_cache, const float* out, const void* workspace, int B, int H, int Hkv,
                  int Nq, int Ncap, int d, int layout, float softmax_scale, int dtype, bool extend = false, int page_size = 0,
-                 int window = 0) {
+                 int window = 0, bool fp8 = false) {
   g_err[0] = 0;
   if (B <= 0 || H <= 0 || Nq <= 0 || Ncap <= 0 || d <= 0) return set_err(FA_ERR_BAD_ARG, "B, H, Nq, Ncap and d must be positive");
   if (Hkv <= 0) return set_err(FA_ERR_BAD_ARG, "Hkv must be positive");
@@ -233,8 +271,8 @@ int check_decode(const void* q, const void* k_cache, const void* v_cache, const 
   // (a buffer load's row offset is a 32-bit byte count: one batch element, plus a super tile of rows past its end, stays under 2 GiB;
   // q's (head, query) offset within its batch element likewise)
   if (page_size > 0) {
-    if (check_page_bytes(page_size, Hkv, d, dtype) != FA_OK) return FA_ERR_BAD_ARG;
-  } else if (((long)Ncap + fa::DEC_ROWS) * Hkv * d * esz >= (1L << 31)) {
+    if (check_page_bytes(page_size, Hkv, d, dtype, fp8) != FA_OK) return FA_ERR_BAD_ARG;
+  } else if (((long)Ncap + fa::DEC_ROWS) * Hkv * d * (fp8 ? 1 : esz) >= (1L << 31)) {
     return set_err(FA_ERR_BAD_ARG, "one batch element of the cache must stay under 2 GiB");
   }
   if ((long)Nq * H * d * esz >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "one batch element of q must stay under 2 GiB");
@@ -255,10 +293,12 @@ int check_decode(const void* q, const void* k_cache, const void* v_cache, const 
 // The split (and combine) launches of a checked call: the decode kernels, or (extend) the extend kernels under their own policy.
 int run_decode(const void* q, const void* k_cache, const void* v_cache, float* out, float* lse, const int* cache_seqlens, void* workspace,
                int B, int H, int Hkv, int Nq, int Ncap, int d, int layout, float softmax_scale, int causal, int dtype, void* stream,
-               bool extend = false, const Paging* pg = nullptr, int window = 0) {
+               bool extend = false, const Paging* pg = nullptr, int window = 0, const Fp8* f8 = nullptr) {
   const int span = span_keys(window, Ncap, Nq, extend ? fa::EXT_BLOCK : 32);   // (no window: Ncap)
   const int ns = extend ? ext_splits(B, H, Hkv, Nq, span) : splits(B, H, Hkv, Nq, span);
-  fa::DecodeArgs a;
+  fa::Fp8Args a;   // (the other builds take its DecodeArgs part)
+  a.k_scale = f8 ? f8->k_scale : nullptr;
+  a.v_scale = f8 ? f8->v_scale : nullptr;
   a.q = q;
   a.k = k_cache;
   a.v = v_cache;
@@ -300,6 +340,7 @@ int run_decode(const void* q, const void* k_cache, const void* v_cache, float* o
     a.kv_hstride = bnhd ? d : (long)pg->page_size * d;
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
+  if (f8) return launch_fp8_d(a, B * H, d, extend, st);
   if (extend) return dtype == FA_DTYPE_BF16 ? launch_extend_d<fa::bf16_t>(a, B * H, d, st) : launch_extend_d<float>(a, B * H, d, st);
   return dtype == FA_DTYPE_BF16 ? launch_d<fa::bf16_t>(a, B * H, d, st) : launch_d<float>(a, B * H, d, st);
 }
@@ -343,9 +384,22 @@ template <typename T> int launch_append_e(const fa::RaggedAppendArgs& a, int d, 
   return vec ? launch_append<T, 16 / sizeof(T)>(a, d, st) : launch_append<T, 1>(a, d, st);
 }
 
+template <int E> int launch_append_fp8(fa::Fp8AppendArgs a, int d, hipStream_t st) {
+  a.ch_shift = __builtin_ctz(d / E);
+  a.lanes <<= a.ch_shift;   // (rows on entry)
+  const dim3 grid((unsigned)((a.lanes + 255) / 256));
+  if (a.table)
+    hipLaunchKernelGGL((fa::append_fp8_kernel<E, true>), grid, dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL((fa::append_fp8_kernel<E>), grid, dim3(256), 0, st, a);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? FA_OK : set_err(FA_ERR_HIP, "append_fp8_kernel launch", e);
+}
+
 // The append launch of a checked call.  cu: the ragged append of Nq = T packed rows shared by the B sequences.
 int run_append(const void* k_new, const void* v_new, void* k_cache, void* v_cache, const int* cache_seqlens, int B, int Hkv, int Nq,
-               int Ncap, int d_new, int d, int layout, int dtype, void* stream, const Paging* pg = nullptr, const int* cu = nullptr) {
+               int Ncap, int d_new, int d, int layout, int dtype, void* stream, const Paging* pg = nullptr, const int* cu = nullptr,
+               const Fp8* f8 = nullptr) {
   fa::RaggedAppendArgs a;
   a.k_new = k_new;
   a.v_new = v_new;
@@ -381,6 +435,14 @@ int run_append(const void* k_new, const void* v_new, void* k_cache, void* v_cach
   const bool vec = (d_new * esz) % 16 == 0 &&
                    (((uintptr_t)k_new | (uintptr_t)v_new | (uintptr_t)k_cache | (uintptr_t)v_cache) & 15) == 0;
   hipStream_t st = static_cast<hipStream_t>(stream);
+  if (f8) {   // bf16 sources into byte caches: eight elements to a lane where every source row starts on 16 bytes and every cache row on 8
+    fa::Fp8AppendArgs fa8;
+    static_cast<fa::AppendArgs&>(fa8) = a;
+    fa8.k_scale = f8->k_scale;
+    fa8.v_scale = f8->v_scale;
+    const bool vec8 = d_new % 8 == 0 && (((uintptr_t)k_new | (uintptr_t)v_new) & 15) == 0 && (((uintptr_t)k_cache | (uintptr_t)v_cache) & 7) == 0;
+    return vec8 ? launch_append_fp8<8>(fa8, d, st) : launch_append_fp8<1>(fa8, d, st);
+  }
   return dtype == FA_DTYPE_BF16 ? launch_append_e<fa::bf16_t>(a, d, vec, st) : launch_append_e<float>(a, d, vec, st);
 }
 
@@ -636,19 +698,28 @@ namespace {
 // (pg null), windowed or not.
 int attend(bool extend, bool fused, const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
            const int* cache_seqlens, const Paging* pg, void* workspace, int B, int H, int Hkv, int Nq, int Ncap, int d_new, int d, int layout,
-           float softmax_scale, int causal, int dtype, void* stream, int window = 0) {
+           float softmax_scale, int causal, int dtype, void* stream, int window = 0, const Fp8* f8 = nullptr) {
   int rc = pg ? check_pages(*pg, &Ncap) : FA_OK;
   if (rc == FA_OK)
     rc = check_decode(q, k_cache, v_cache, out, workspace, B, H, Hkv, Nq, Ncap, d, layout, softmax_scale, dtype, extend, pg ? pg->page_size : 0,
-                      window);
+                      window, f8 != nullptr);
   if (rc == FA_OK && fused) rc = check_append(k_new, v_new, k_cache, v_cache, B, Hkv, Nq, Ncap, d_new, d, layout, dtype, extend);
   if (rc != FA_OK) return rc;
   if (fused) {
-    rc = run_append(k_new, v_new, k_cache, v_cache, cache_seqlens, B, Hkv, Nq, Ncap, d_new, d, layout, dtype, stream, pg);
+    rc = run_append(k_new, v_new, k_cache, v_cache, cache_seqlens, B, Hkv, Nq, Ncap, d_new, d, layout, dtype, stream, pg, nullptr, f8);
     if (rc != FA_OK) return rc;
   }
   return run_decode(q, k_cache, v_cache, out, lse, cache_seqlens, workspace, B, H, Hkv, Nq, Ncap, d, layout, softmax_scale, causal, dtype,
-                    stream, extend, pg, window);
+                    stream, extend, pg, window, f8);
+}
+
+// The check an fp8 call makes first: the queries and the new tokens are bf16.
+int check_fp8(int dtype) {
+  g_err[0] = 0;
+  if (dtype == FA_DTYPE_F32)
+    return set_err(FA_ERR_BAD_ARG, "an fp8 cache takes bf16 queries and new tokens: FA_DTYPE_F32 is not supported (dtype must be FA_DTYPE_BF16)");
+  if (dtype != FA_DTYPE_BF16) return set_err(FA_ERR_BAD_ARG, "unknown dtype");
+  return FA_OK;
 }
 
 // The checks a windowed call makes first.
@@ -846,6 +917,51 @@ int fa_mi355x_fwd_ragged_window(const void* q, const void* k_new, const void* v_
   const Paging pg = {block_table, num_pages, page_size, max_pages};
   return ragged_call(true, k_new || v_new, q, k_new, v_new, k_cache, v_cache, out, lse, cu_seqlens_q, cache_seqlens,
                      block_table ? &pg : nullptr, workspace, B, H, Hkv, T, Ncap, d_new, d, layout, softmax_scale, causal, dtype, stream, window);
+}
+
+// The fp8 entry points (include/flash_attn_mi355x_decode_fp8.h): caches of e4m3 bytes with per-kv-head scales.  k_new / v_new null:
+// attend only; block_table null: slabs of Ncap rows.
+int fa_mi355x_fwd_decode_fp8(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, const float* k_scale,
+                             const float* v_scale, float* out, float* lse, const int* cache_seqlens, const int* block_table, void* workspace,
+                             int B, int H, int Hkv, int Nq, int Ncap, int num_pages, int page_size, int max_pages, int d_new, int d,
+                             int layout, float softmax_scale, int causal, int dtype, void* stream) {
+  const int rc = check_fp8(dtype);
+  if (rc != FA_OK) return rc;
+  const Paging pg = {block_table, num_pages, page_size, max_pages};
+  const Fp8 f8 = {k_scale, v_scale};
+  return attend(false, k_new || v_new, q, k_new, v_new, k_cache, v_cache, out, lse, cache_seqlens, block_table ? &pg : nullptr, workspace, B, H,
+                Hkv, Nq, Ncap, d_new, d, layout, softmax_scale, causal, dtype, stream, 0, &f8);
+}
+
+int fa_mi355x_fwd_extend_fp8(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, const float* k_scale,
+                             const float* v_scale, float* out, float* lse, const int* cache_seqlens, const int* block_table, void* workspace,
+                             int B, int H, int Hkv, int Nq, int Ncap, int num_pages, int page_size, int max_pages, int d_new, int d,
+                             int layout, float softmax_scale, int causal, int dtype, void* stream) {
+  const int rc = check_fp8(dtype);
+  if (rc != FA_OK) return rc;
+  const Paging pg = {block_table, num_pages, page_size, max_pages};
+  const Fp8 f8 = {k_scale, v_scale};
+  return attend(true, k_new || v_new, q, k_new, v_new, k_cache, v_cache, out, lse, cache_seqlens, block_table ? &pg : nullptr, workspace, B, H,
+                Hkv, Nq, Ncap, d_new, d, layout, softmax_scale, causal, dtype, stream, 0, &f8);
+}
+
+int fa_mi355x_append_fp8(const void* k_new, const void* v_new, void* k_cache, void* v_cache, const float* k_scale, const float* v_scale,
+                         const int* cache_seqlens, const int* block_table, int B, int Hkv, int Nq, int Ncap, int num_pages, int page_size,
+                         int max_pages, int d_new, int d, int layout, int dtype, void* stream) {
+  int rc = check_fp8(dtype);
+  const Paging pg = {block_table, num_pages, page_size, max_pages};
+  if (rc == FA_OK && block_table) rc = check_pages(pg, &Ncap);
+  if (rc == FA_OK) rc = check_append(k_new, v_new, k_cache, v_cache, B, Hkv, Nq, Ncap, d_new, d, layout, dtype, true);
+  if (rc == FA_OK) {   // (a store's row offset is added to a 64-bit address: the bound is the attention's, whose loads read these rows)
+    if (block_table)
+      rc = check_page_bytes(page_size, Hkv, d, dtype, true);
+    else if (((long)Ncap + fa::DEC_ROWS) * Hkv * d >= (1L << 31))
+      rc = set_err(FA_ERR_BAD_ARG, "one batch element of the cache must stay under 2 GiB");
+  }
+  if (rc != FA_OK) return rc;
+  const Fp8 f8 = {k_scale, v_scale};
+  return run_append(k_new, v_new, k_cache, v_cache, cache_seqlens, B, Hkv, Nq, Ncap, d_new, d, layout, dtype, stream, block_table ? &pg : nullptr,
+                    nullptr, &f8);
 }
 
 // The ungrouped entry points: Hkv = H.

@@ -639,7 +639,7 @@ def decode_workspace(q, k_cache, layout="bnhd", block_table=None, max_pages=None
     chunk), or None when the call runs as one split and needs none.  A pure function of the shapes: allocate once, reuse every step.
     A paged call (``k_cache`` the pool): give the block table or its ``max_pages``; the size is the contiguous call's for
     Ncap = max_pages * page_size.  ``window``: for flash_attn_decode(..., window=) (fa_mi355x_decode_window_workspace_bytes: the
-    splits follow the window span, not the cache)."""
+    splits follow the window span, not the cache).  An fp8 cache is sized as the bf16 cache of its shape is (the same splits)."""
     B, H, Hkv, Nq, Ncap, _, dp = _decode_dims(q, k_cache, layout, _max_pages(block_table, max_pages))
     nbytes = _decode_workspace_bytes(B, H, Hkv, Nq, Ncap, dp, _check_window(window))
     return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=q.device) if nbytes else None
@@ -659,6 +659,29 @@ def extend_workspace(q, k_cache, layout="bnhd", block_table=None, max_pages=None
     return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=q.device) if nbytes else None
 
 
+_FP8 = getattr(torch, "float8_e4m3fn", None)   # the dtype of an fp8 KV cache (include/flash_attn_mi355x_decode_fp8.h)
+
+
+def _is_fp8(t):
+    return _FP8 is not None and t.dtype == _FP8
+
+
+def _check_scales(k_scale, v_scale, fp8, Hkv, device):
+    """``k_scale`` / ``v_scale`` of an fp8 cache: None (all ones) or contiguous float32 (Hkv,) tensors on the cache's device.  Given
+    with any other cache they are an error, not ignored."""
+    if not fp8:
+        if k_scale is not None or v_scale is not None:
+            raise ValueError("k_scale and v_scale belong to an fp8 (torch.float8_e4m3fn) cache: this cache is not one")
+        return
+    for name, t in (("k_scale", k_scale), ("v_scale", v_scale)):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise TypeError(f"{name} must be a float32 tensor of shape (Hkv,) = ({Hkv},)")
+        if tuple(t.shape) != (Hkv,) or not t.is_contiguous() or t.device != device:
+            raise ValueError(f"{name} must be a contiguous float32 tensor of shape (Hkv,) = ({Hkv},) on the cache's device")
+
+
 def _check_seqlens(cache_seqlens, B, device):
     if cache_seqlens is not None and (cache_seqlens.dtype != torch.int32 or tuple(cache_seqlens.shape) != (B,)
                                       or cache_seqlens.device != device or not cache_seqlens.is_contiguous()):
@@ -671,7 +694,10 @@ def _check_new(k_new, v_new, k_cache, layout, Nq=None, paged=False):
     dimension counts pages (the block table is what B is held against)."""
     if k_new.dim() != 4 or k_new.shape != v_new.shape:
         raise ValueError("k_new and v_new must be 4-d tensors of one shape")
-    if k_new.dtype != k_cache.dtype or v_new.dtype != k_cache.dtype:
+    if _is_fp8(k_cache):
+        if k_new.dtype != torch.bfloat16 or v_new.dtype != torch.bfloat16:
+            raise TypeError("an fp8 cache takes bfloat16 k_new and v_new (they are quantised on the device)")
+    elif k_new.dtype != k_cache.dtype or v_new.dtype != k_cache.dtype:
         raise TypeError("k_new and v_new must have the cache's dtype")
     if layout == "bnhd":
         (B, n, Hkv, d_new), (Bc, _, Hc, dp) = k_new.shape, k_cache.shape
@@ -693,21 +719,24 @@ def _check_new(k_new, v_new, k_cache, layout, Nq=None, paged=False):
     return n, d_new
 
 
-def _append(who, entry, k_new, v_new, k_cache, v_cache, cache_seqlens, layout, block_table=None):
-    """decode_append / extend_append: the checks, then the library's ``entry`` (its _paged form when there is a block table)."""
+def _append(who, entry, k_new, v_new, k_cache, v_cache, cache_seqlens, layout, block_table=None, k_scale=None, v_scale=None):
+    """decode_append / extend_append: the checks, then the library's ``entry`` (its _paged form when there is a block table; for an
+    fp8 cache fa_mi355x_append_fp8, which quantises)."""
     if layout not in _DECODE_LAYOUTS:
         raise ValueError(f"layout must be one of {sorted(_DECODE_LAYOUTS)}")
     if k_cache.dim() != 4 or k_cache.shape != v_cache.shape:
         raise ValueError("k_cache and v_cache must be 4-d tensors of one shape")
     if v_cache.dtype != k_cache.dtype:
         raise TypeError("k_cache and v_cache must share one dtype")
-    dtype = _dtype_code(k_cache)
+    fp8 = _is_fp8(k_cache)
+    dtype = _lib.FA_DTYPE_BF16 if fp8 else _dtype_code(k_cache)
     paged = block_table is not None
     if paged:
         num_pages, page_size, _, _ = _pool_dims(k_cache, layout)
     Nq, d_new = _check_new(k_new, v_new, k_cache, layout, paged=paged)
     B, dp = k_new.shape[0], k_cache.shape[3]
     Ncap, Hkv = (k_cache.shape[1], k_cache.shape[2]) if layout == "bnhd" else (k_cache.shape[2], k_cache.shape[1])
+    _check_scales(k_scale, v_scale, fp8, Hkv, k_cache.device)
     _check_seqlens(cache_seqlens, B, k_cache.device)
     if paged:
         _check_table(block_table, B, k_cache.device)
@@ -715,39 +744,60 @@ def _append(who, entry, k_new, v_new, k_cache, v_cache, cache_seqlens, layout, b
         if t.device != k_cache.device or not t.is_contiguous():
             raise ValueError("k_cache and v_cache must be contiguous and live on one device")
         _require_gpu(t, who)
+    if fp8:   # (one entry point for any Nq: a null table is a slab cache)
+        if who == "decode_append" and Nq > 128:
+            raise ValueError("decode_append takes at most 128 new tokens per call: use extend_append")
+        geometry = (0, num_pages, page_size, block_table.shape[1]) if paged else (Ncap, 0, 0, 0)
+        _lib.decode_check(_lib.decode().fa_mi355x_append_fp8(
+            _ptr(k_new), _ptr(v_new), _ptr(k_cache), _ptr(v_cache), _ptr(k_scale), _ptr(v_scale), _ptr(cache_seqlens), _ptr(block_table),
+            B, Hkv, Nq, *geometry, d_new, dp, _DECODE_LAYOUTS[layout], dtype, _stream_ptr()))
+        return
     where = (_ptr(block_table), B, Hkv, Nq, num_pages, page_size, block_table.shape[1]) if paged else (B, Hkv, Nq, Ncap)
     _lib.decode_check(getattr(_lib.decode(), entry + "_paged" * paged)(
         _ptr(k_new), _ptr(v_new), _ptr(k_cache), _ptr(v_cache), _ptr(cache_seqlens), *where, d_new, dp,
         _DECODE_LAYOUTS[layout], dtype, _stream_ptr()))
 
 
-def decode_append(k_new, v_new, k_cache, v_cache, cache_seqlens=None, layout="bnhd", block_table=None):
+def decode_append(k_new, v_new, k_cache, v_cache, cache_seqlens=None, layout="bnhd", block_table=None, k_scale=None, v_scale=None):
     """Write the Nq <= 128 new tokens' k and v into the caches on the device (fa_mi355x_decode_append): k_new, v_new (B, Nq, Hkv,
     d_new) for "bnhd" or (B, Hkv, Nq, d_new) for "bhnd", 1 <= d_new <= dp, into caches (B, Ncap, Hkv, dp) / (B, Hkv, Ncap, dp).
     ``cache_seqlens`` COUNTS the new tokens, as flash_attn_decode reads it: token i goes to row clamp(len_b, 0, Ncap) - Nq + i when
     that is >= 0 (None: the last Nq rows), with zeros in columns d_new .. dp-1; every other row keeps its contents.  k_new and v_new
     must not alias the caches.  In place, no host synchronisation.  ``block_table`` (int32 (B, max_pages)): the caches are the pools
     of a paged cache (flash_attn_decode), row r of batch element b is row r % page_size of page block_table[b, r // page_size], and
-    Ncap = max_pages * page_size; a page that two sequences share is written by both (the caller keeps appends off shared pages)."""
-    _append("decode_append", "fa_mi355x_decode_append", k_new, v_new, k_cache, v_cache, cache_seqlens, layout, block_table)
+    Ncap = max_pages * page_size; a page that two sequences share is written by both (the caller keeps appends off shared pages).
+    An FP8 cache (torch.float8_e4m3fn caches, bfloat16 k_new / v_new; fa_mi355x_append_fp8): every element x of kv head h is stored
+    as the e4m3 code of clamp(x * (1 / scale[h]), -448, 448), rounded to nearest even (overflow saturates to +-448, a NaN stores the
+    NaN code 0x7F), with ``k_scale`` / ``v_scale`` contiguous float32 (Hkv,) on the cache's device (None: ones); columns d_new .. dp-1
+    are zero bytes.  Scales with any other cache are an error."""
+    _append("decode_append", "fa_mi355x_decode_append", k_new, v_new, k_cache, v_cache, cache_seqlens, layout, block_table, k_scale, v_scale)
 
 
-def extend_append(k_new, v_new, k_cache, v_cache, cache_seqlens=None, layout="bnhd", block_table=None):
+def extend_append(k_new, v_new, k_cache, v_cache, cache_seqlens=None, layout="bnhd", block_table=None, k_scale=None, v_scale=None):
     """decode_append for any number of new tokens (fa_mi355x_extend_append: the same kernel, placement and checks, no bound on Nq)."""
-    _append("extend_append", "fa_mi355x_extend_append", k_new, v_new, k_cache, v_cache, cache_seqlens, layout, block_table)
+    _append("extend_append", "fa_mi355x_extend_append", k_new, v_new, k_cache, v_cache, cache_seqlens, layout, block_table, k_scale, v_scale)
 
 
 def _cache_attention(who, extend, q, k_cache, v_cache, cache_seqlens, causal, softmax_scale, layout, out, lse, workspace, k_new, v_new,
-                     block_table=None, window=None):
+                     block_table=None, window=None, k_scale=None, v_scale=None):
     """flash_attn_decode / flash_attn_extend (``extend``): the checks, the head-dim padding, then the library's entry point (its
-    _paged form when there is a block table; with a ``window``, the family's one _window entry point)."""
+    _paged form when there is a block table; with a ``window``, the family's one _window entry point; on an fp8 cache, the family's
+    one _fp8 entry point)."""
     window = _check_window(window, causal)
     if (k_new is None) != (v_new is None):
         raise ValueError("k_new and v_new go together: give both (fused append) or neither")
     if layout not in _DECODE_LAYOUTS:
         raise ValueError(f"layout must be one of {sorted(_DECODE_LAYOUTS)}")
     dtype = _dtype_code(q)
-    if k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
+    fp8 = _is_fp8(k_cache) or _is_fp8(v_cache)
+    if fp8:
+        if k_cache.dtype != v_cache.dtype:
+            raise TypeError("k_cache and v_cache must share one dtype")
+        if q.dtype != torch.bfloat16:
+            raise TypeError("an fp8 cache takes bfloat16 queries")
+        if window is not None:
+            raise ValueError("a sliding window on an fp8 cache is not built: window= with torch.float8_e4m3fn caches")
+    elif k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
         raise TypeError("q, k_cache and v_cache must share one dtype")
     if k_cache.shape != v_cache.shape:
         raise ValueError("k_cache and v_cache must have one shape")
@@ -759,6 +809,7 @@ def _cache_attention(who, extend, q, k_cache, v_cache, cache_seqlens, causal, so
     B, H, Hkv, Nq, Ncap, d, dp = _decode_dims(q, k_cache, layout, **pages)
     if d > dp:
         raise ValueError(f"q's head dim {d} exceeds the cache's row length {dp}")
+    _check_scales(k_scale, v_scale, fp8, Hkv, q.device)
     _check_seqlens(cache_seqlens, B, q.device)
     if paged:
         _check_table(block_table, B, q.device)
@@ -789,7 +840,13 @@ def _cache_attention(who, extend, q, k_cache, v_cache, cache_seqlens, causal, so
     elif workspace.numel() * workspace.element_size() < ws_bytes(B, H, Hkv, Nq, Ncap, dp, window):
         raise ValueError(f"workspace too small: size it with {new_ws.__name__}()")
     tail = (_DECODE_LAYOUTS[layout], float(softmax_scale), int(bool(causal)), dtype, _stream_ptr())
-    if window is not None:   # (one entry point per family: null k_new / v_new attend only, a null table is a slab cache)
+    if fp8:   # (one entry point per family, as the windowed calls: null k_new / v_new attend only, a null table is a slab cache)
+        fwd = lib.fa_mi355x_fwd_extend_fp8 if extend else lib.fa_mi355x_fwd_decode_fp8
+        geometry = (num_pages, page_size, pages["max_pages"]) if paged else (0, 0, 0)
+        status = fwd(_ptr(qp), _ptr(k_new), _ptr(v_new), _ptr(k_cache), _ptr(v_cache), _ptr(k_scale), _ptr(v_scale), _ptr(outp), _ptr(lse),
+                     _ptr(cache_seqlens), _ptr(block_table), _ptr(workspace), B, H, Hkv, Nq, 0 if paged else Ncap, *geometry,
+                     d_new if k_new is not None else dp, dp, *tail)
+    elif window is not None:   # (one entry point per family: null k_new / v_new attend only, a null table is a slab cache)
         fwd = lib.fa_mi355x_fwd_extend_window if extend else lib.fa_mi355x_fwd_decode_window
         geometry = (num_pages, page_size, pages["max_pages"]) if paged else (0, 0, 0)
         status = fwd(_ptr(qp), _ptr(k_new), _ptr(v_new), _ptr(k_cache), _ptr(v_cache), _ptr(outp), _ptr(lse), _ptr(cache_seqlens),
@@ -823,7 +880,7 @@ def _cache_attention(who, extend, q, k_cache, v_cache, cache_seqlens, causal, so
 
 
 def flash_attn_decode(q, k_cache, v_cache, cache_seqlens=None, causal=True, softmax_scale=None, layout="bnhd", out=None, lse=None,
-                      workspace=None, k_new=None, v_new=None, block_table=None, window=None):
+                      workspace=None, k_new=None, v_new=None, block_table=None, window=None, k_scale=None, v_scale=None):
     """Attention of Nq <= 128 new queries against a KV cache (fa_mi355x_fwd_decode / _gqa, include/flash_attn_mi355x_decode.h).
     ``layout`` "bnhd": q (B, Nq, H, d), caches (B, Ncap, Hkv, dp); "bhnd": q (B, H, Nq, d), caches (B, Hkv, Ncap, dp).  Hkv is the
     cache's own head count and must divide H: Hkv < H is a grouped-query (Hkv = 1: multi-query) cache, query head h reads cache head
@@ -844,13 +901,20 @@ def flash_attn_decode(q, k_cache, v_cache, cache_seqlens=None, causal=True, soft
     window, so the work and the bytes read follow W and not the cache's length, and cache rows (and the pages of a paged cache) wholly
     below the window are never read.  None takes the unwindowed entry points above; 0, and any W >= Ncap, is the unwindowed call
     through the windowed entry point (the same launches and bits).  Size a workspace with decode_workspace(..., window=).
+    FP8 caches (k_cache and v_cache of dtype torch.float8_e4m3fn, slab or paged; fa_mi355x_fwd_decode_fp8,
+    include/flash_attn_mi355x_decode_fp8.h): the caches hold e4m3 bytes and the value of an element of cache head h is
+    scale[h] * e4m3, with ``k_scale`` / ``v_scale`` contiguous float32 (Hkv,) tensors on q's device (None: ones; read on the device).
+    q, k_new and v_new are bfloat16; k_new / v_new are quantised as decode_append does.  Half the bytes per cached row; with
+    power-of-two scales the result is bit for bit the bf16 call's on the cache cast to bfloat16 with softmax_scale * k_scale,
+    times v_scale.  The workspace is the bf16 call's (decode_workspace takes the fp8 cache).  No ``window`` on an fp8 cache, and
+    scales with any other cache are an error.
     Returns (out fp32 in q's shape, lse fp32 (B, H, Nq)): rows with no admissible key give out = 0, lse = -inf."""
     return _cache_attention("flash_attn_decode", False, q, k_cache, v_cache, cache_seqlens, causal, softmax_scale, layout, out, lse,
-                            workspace, k_new, v_new, block_table, window)
+                            workspace, k_new, v_new, block_table, window, k_scale, v_scale)
 
 
 def flash_attn_extend(q, k_cache, v_cache, cache_seqlens=None, causal=True, softmax_scale=None, layout="bnhd", out=None, lse=None,
-                      workspace=None, k_new=None, v_new=None, block_table=None, window=None):
+                      workspace=None, k_new=None, v_new=None, block_table=None, window=None, k_scale=None, v_scale=None):
     """flash_attn_decode for ANY number Nq >= 1 of new queries (fa_mi355x_fwd_extend / fa_mi355x_fwd_extend_append): a long input that
     follows a cached prefix, or one piece of a chunked prefill (the same call, from an empty cache on).  Every argument, check, the
     head-dim padding (the default scale keeps the caller's 1/sqrt(d)) and the return value are flash_attn_decode's; ``workspace`` is
@@ -859,9 +923,10 @@ def flash_attn_extend(q, k_cache, v_cache, cache_seqlens=None, causal=True, soft
     them, and a causal call loads no tile above a block's last position.  For Nq <= 128 the result agrees with flash_attn_decode to
     rounding, not bit for bit.  ``block_table``: a paged cache, as in flash_attn_decode (fa_mi355x_fwd_extend_paged).  ``window``:
     sliding-window attention, as in flash_attn_decode (fa_mi355x_fwd_extend_window): every 128-row block walks its own W + 128
-    positions' worth of keys wherever it sits in a long input; size a workspace with extend_workspace(..., window=)."""
+    positions' worth of keys wherever it sits in a long input; size a workspace with extend_workspace(..., window=).  ``k_scale`` /
+    ``v_scale``: an fp8 cache, as in flash_attn_decode (fa_mi355x_fwd_extend_fp8)."""
     return _cache_attention("flash_attn_extend", True, q, k_cache, v_cache, cache_seqlens, causal, softmax_scale, layout, out, lse,
-                            workspace, k_new, v_new, block_table, window)
+                            workspace, k_new, v_new, block_table, window, k_scale, v_scale)
 
 
 # ---- ragged batches: every sequence brings its own number of new tokens (include/flash_attn_mi355x_decode_ragged.h) ----
@@ -943,6 +1008,9 @@ def _cache_geometry(k_cache, v_cache, layout, block_table):
         raise ValueError("k_cache and v_cache must be 4-d tensors of one shape")
     if v_cache.dtype != k_cache.dtype:
         raise TypeError("k_cache and v_cache must share one dtype")
+    if _is_fp8(k_cache):
+        raise TypeError("the ragged calls on an fp8 (torch.float8_e4m3fn) cache are not built: use flash_attn_decode / flash_attn_extend "
+                        "and decode_append / extend_append")
     if block_table is not None:
         num_pages, page_size, Hkv, dp = _pool_dims(k_cache, layout)
         return (num_pages, page_size), Hkv, dp, None

@@ -83,6 +83,9 @@ def attention_stack(x, layers, n_head: int, causal: bool = True, fused_layout: b
 # A cache built with window=W makes every one of these calls a sliding-window one (each token sees the last W positions): the step,
 # fused step, extend, ragged and chunked-prefill functions and GraphedStep pass cache.window to device_ops, and a PagedKVCache gives
 # the pages behind the window back through release_behind_window.
+# A cache built with kv_dtype=torch.float8_e4m3fn holds e4m3 bytes with one scale per (layer, kv head): the fused step, extend and
+# chunked-prefill functions and GraphedStep pass the layer's scales (cache.quant(li)) to the same device_ops calls, which quantise on
+# the append; a prompt fills the cache through extend_append while its own attention stays the square forward on the unquantised k, v.
 
 MAX_STEP_TOKENS = 128   # fa_mi355x_fwd_decode's largest Nq; longer inputs are prefill, or attention_stack_extend after a prefix
 
@@ -93,6 +96,28 @@ def _check_cache_window(window):
     return window
 
 
+def _check_cache_quant(kv_dtype, kv_scale, dtype, window, n_layers, n_kv_head, device):
+    """(the caches' dtype, the (k, v) scales or None) of a cache built with ``kv_dtype`` / ``kv_scale``."""
+    if kv_dtype is None or kv_dtype == dtype:
+        if kv_scale is not None:
+            raise ValueError("kv_scale belongs to an fp8 cache: give kv_dtype=torch.float8_e4m3fn")
+        return dtype, None
+    if kv_dtype != device_ops._FP8:
+        raise ValueError("kv_dtype must be None, the compute dtype or torch.float8_e4m3fn")
+    if dtype != torch.bfloat16:
+        raise TypeError("an fp8 cache takes a bfloat16 stack")
+    if window is not None:
+        raise ValueError("a sliding window on an fp8 cache is not built")
+    if kv_scale is not None:
+        if len(kv_scale) != 2:
+            raise ValueError("kv_scale must be a pair (k_scale, v_scale) of float32 (n_layers, n_kv_head) tensors")
+        for t in kv_scale:
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (n_layers, n_kv_head):
+                raise ValueError("kv_scale must be a pair (k_scale, v_scale) of float32 (n_layers, n_kv_head) tensors")
+        kv_scale = tuple(t.to(device).contiguous() for t in kv_scale)
+    return kv_dtype, kv_scale
+
+
 class KVCache:
     """Per-layer k and v caches of a causal attention stack: ``k[l]``, ``v[l]`` are (B, capacity, n_kv_head, dp) in the projection's
     own [B][N][H][d] layout (no permute), dp = head_dim rounded up to 32, 64 or 128 with zero columns past head_dim.  ``n_kv_head``
@@ -100,9 +125,14 @@ class KVCache:
     ``lengths``: device int32 (B,), the valid rows per batch element (read by the decode kernels, never by the host).
     ``window`` (None, or an int >= 1): the stack's layers use SLIDING-WINDOW attention, every token sees the last ``window``
     positions, its own included (Mistral's ``sliding_window``); the stack functions pass it to every device_ops call on this cache.
-    The cache still holds every row (no ring buffer): a PagedKVCache gives the memory back through release_behind_window."""
+    The cache still holds every row (no ring buffer): a PagedKVCache gives the memory back through release_behind_window.
+    ``kv_dtype`` (None: ``dtype``, or torch.float8_e4m3fn): an FP8 cache holds e4m3 bytes, half the memory and half the bytes a step
+    reads, and ``kv_scale`` (None: ones, or a pair (k_scale, v_scale) of float32 (n_layers, n_kv_head) tensors) gives every layer's
+    per-head scales: a cached element is scale * e4m3.  The stack must be bfloat16; the fused step, extend and chunked-prefill
+    functions and GraphedStep quantise on the append; attention_stack_step (torch indexing), attention_stack_ragged and a window
+    are not built for it."""
 
-    def __init__(self, n_layers, B, capacity, n_head, head_dim, dtype, device, n_kv_head=None, window=None):
+    def __init__(self, n_layers, B, capacity, n_head, head_dim, dtype, device, n_kv_head=None, window=None, kv_dtype=None, kv_scale=None):
         self.window = _check_cache_window(window)
         self.head_dim, self.dp = head_dim, device_ops.padded_head_dim(head_dim)
         self.capacity, self.n_head = capacity, n_head
@@ -110,6 +140,7 @@ class KVCache:
         if self.n_kv_head <= 0 or n_head % self.n_kv_head:
             raise ValueError(f"n_kv_head = {n_kv_head} must divide n_head = {n_head}")
         shape = (B, capacity, self.n_kv_head, self.dp)
+        dtype, self.kv_scale = _check_cache_quant(kv_dtype, kv_scale, dtype, self.window, n_layers, self.n_kv_head, device)
         self.k = [torch.zeros(shape, dtype=dtype, device=device) for _ in range(n_layers)]
         self.v = [torch.zeros(shape, dtype=dtype, device=device) for _ in range(n_layers)]
         self.lengths = torch.zeros(B, dtype=torch.int32, device=device)
@@ -125,6 +156,17 @@ class KVCache:
     def windowing(self):
         """The keyword that makes a device_ops call a windowed one: none for a cache without a window (the unwindowed entry points)."""
         return {} if self.window is None else dict(window=self.window)
+
+    @property
+    def fp8(self):
+        return device_ops._is_fp8(self.k[0])
+
+    def quant(self, li):
+        """The keywords that give a device_ops call on layer ``li`` of an fp8 cache its scales: none for any other cache, and none
+        for an fp8 cache whose scales are all ones."""
+        if not self.fp8 or self.kv_scale is None:
+            return {}
+        return dict(k_scale=self.kv_scale[0][li], v_scale=self.kv_scale[1][li])
 
     def reserve(self, n_tokens, rows=None):
         """Make sure the sequences own memory for ``n_tokens`` rows: a slab cache owns its ``capacity`` rows from the start."""
@@ -163,7 +205,8 @@ class PagedKVCache(KVCache):
     so a long-running sequence holds O(window) pages.  ``released[b]`` counts the leading table slots sequence b no longer owns
     (``pages[b]`` are the pages of the slots behind them)."""
 
-    def __init__(self, n_layers, B, capacity, n_head, head_dim, dtype, device, n_kv_head=None, page_size=128, n_pages=None, window=None):
+    def __init__(self, n_layers, B, capacity, n_head, head_dim, dtype, device, n_kv_head=None, page_size=128, n_pages=None, window=None,
+                 kv_dtype=None, kv_scale=None):
         self.window = _check_cache_window(window)
         self.head_dim, self.dp = head_dim, device_ops.padded_head_dim(head_dim)
         self.capacity, self.n_head = capacity, n_head
@@ -179,6 +222,7 @@ class PagedKVCache(KVCache):
         if self.n_pages <= 0:
             raise ValueError("n_pages must be positive")
         shape = (self.n_pages, page_size, self.n_kv_head, self.dp)
+        dtype, self.kv_scale = _check_cache_quant(kv_dtype, kv_scale, dtype, self.window, n_layers, self.n_kv_head, device)
         self.k = [torch.zeros(shape, dtype=dtype, device=device) for _ in range(n_layers)]
         self.v = [torch.zeros(shape, dtype=dtype, device=device) for _ in range(n_layers)]
         self.block_table = torch.zeros((B, self.max_pages), dtype=torch.int32, device=device)   # (entries past a sequence's pages: never read)
@@ -272,18 +316,19 @@ def attention_stack_prefill(x, layers, n_head: int, cache: KVCache):
     if cache.window is not None:
         return attention_stack_prefill_chunked(x, layers, n_head, cache, max(P, 1))
     d = E // n_head
-    if cache.block_table is not None:
+    if cache.block_table is not None or cache.fp8:
         cache.reserve(P)
-        cache.lengths.fill_(P)   # (the paged append places the prompt by the lengths)
+        cache.lengths.fill_(P)   # (the library's append places the prompt by the lengths)
     for li, (wq, wk, wv, wo) in enumerate(layers):
         q, k, v = _project(x, wq, wk, wv, n_head)
         _check_kv_heads(k, cache)
         kp, vp = cache._pad(k), cache._pad(v)
-        if cache.block_table is None:
+        if cache.block_table is None and not cache.fp8:
             cache.k[li][:, :P] = kp
             cache.v[li][:, :P] = vp
-        else:   # rows lengths[b] - P .. lengths[b] - 1 = 0 .. P - 1 of every sequence's pages (zero columns past head_dim)
-            device_ops.extend_append(k, v, cache.k[li], cache.v[li], cache.lengths, "bnhd", **cache.paging())
+        else:   # rows lengths[b] - P .. lengths[b] - 1 = 0 .. P - 1 of every sequence's pages (zero columns past head_dim); an fp8
+            # cache, slab or paged, is filled here too: the append quantises, and the attention below reads the unquantised k, v
+            device_ops.extend_append(k, v, cache.k[li], cache.v[li], cache.lengths, "bnhd", **cache.paging(), **cache.quant(li))
         # (a grouped-query stack: the kernels read the Hkv heads in place)
         fwd = device_ops.flash_attn_fwd_bnhd if cache.n_kv_head == n_head else device_ops.flash_attn_fwd_gqa
         if cache.dp == d:
@@ -306,6 +351,9 @@ def _step(x_new, layers, n_head: int, cache: KVCache, fused: bool):
     if not fused and cache.block_table is not None:
         raise ValueError("attention_stack_step appends with torch indexing into a slab: a PagedKVCache steps through "
                          "attention_stack_step_fused")
+    if not fused and cache.fp8:
+        raise ValueError("attention_stack_step appends with torch indexing, which does not quantise: an fp8 cache steps through "
+                         "attention_stack_step_fused")
     cache.reserve(cache.length_bound + T)
     dev = x_new.device
     if not fused:
@@ -325,7 +373,7 @@ def _step(x_new, layers, n_head: int, cache: KVCache, fused: bool):
             for dst, t in ((cache.k[li], k), (cache.v[li], v)):
                 dst.view(B * cache.capacity, hkv, cache.dp).index_copy_(0, rows, cache._pad(t).reshape(B * T, hkv, cache.dp))
         o, _ = device_ops.flash_attn_decode(q, cache.k[li], cache.v[li], new_len, causal=True, layout="bnhd",
-                                            workspace=cache.workspace(q), **new, **cache.paging(), **cache.windowing())
+                                            workspace=cache.workspace(q), **new, **cache.paging(), **cache.windowing(), **cache.quant(li))
         x = x + (o.reshape(B * T, E).to(x.dtype) @ wo).view(B, T, E)
     cache.lengths.copy_(new_len)
     cache.length_bound += T
@@ -368,7 +416,8 @@ def attention_stack_extend(x_new, layers, n_head: int, cache: KVCache):
         q, k, v = _project(x, wq, wk, wv, n_head)
         _check_kv_heads(k, cache)
         o, _ = device_ops.flash_attn_extend(q, cache.k[li], cache.v[li], new_len, causal=True, layout="bnhd",
-                                            workspace=cache.extend_workspace(q), k_new=k, v_new=v, **cache.paging(), **cache.windowing())
+                                            workspace=cache.extend_workspace(q), k_new=k, v_new=v, **cache.paging(), **cache.windowing(),
+                                            **cache.quant(li))
         x = x + (o.reshape(B * T, E).to(x.dtype) @ wo).view(B, T, E)
     cache.lengths.copy_(new_len)
     cache.length_bound += T
@@ -387,6 +436,8 @@ def attention_stack_ragged(x_new, counts, layers, n_head: int, cache: KVCache):
     each sequence, attention_stack_extend's output on that sequence alone, to rounding; rows past sum(counts) are unspecified."""
     if x_new.dim() != 2:
         raise ValueError("x_new must be packed: (T, E)")
+    if cache.fp8:
+        raise ValueError("the ragged calls on an fp8 cache are not built: step an fp8 cache through attention_stack_step_fused / _extend")
     T, E = x_new.shape
     B = cache.lengths.shape[0]
     counts = [int(c) for c in counts]

@@ -157,4 +157,8 @@ const char* fa_mi355x_decode_last_error(void);
  * with the append or not: nine entry points, part of this library and of this header, kept in a file of their own. */
 #include "flash_attn_mi355x_decode_window.h"
 
+/* FP8 (e4m3) KV caches with per-kv-head scales for the decode and extend calls, slab or paged, and the quantising append: three
+ * entry points, part of this library and of this header, kept in a file of their own. */
+#include "flash_attn_mi355x_decode_fp8.h"
+
 #endif /* FLASH_ATTN_MI355X_DECODE_H */
