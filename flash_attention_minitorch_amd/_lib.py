@@ -161,6 +161,19 @@ WINDOW_ABI = {
     "fa_mi355x_fwd_ragged_window": (_i, [_vp] * 11 + [_i] * 11 + [_f, _i, _i, _i, _vp]),
 }
 
+# the same for include/flash_attn_mi355x_decode_sink.h (the windowed forms with attention-sink tokens; tests/test_sink_cpu.py)
+SINK_ABI = {
+    "fa_mi355x_decode_sink_splits": (_i, [_i] * 9),
+    "fa_mi355x_decode_sink_workspace_bytes": (_sz, [_i] * 8),
+    "fa_mi355x_fwd_decode_sink": (_i, [_vp] * 10 + [_i] * 11 + [_f, _i, _i, _i, _i, _vp]),
+    "fa_mi355x_extend_sink_splits": (_i, [_i] * 9),
+    "fa_mi355x_extend_sink_workspace_bytes": (_sz, [_i] * 8),
+    "fa_mi355x_fwd_extend_sink": (_i, [_vp] * 10 + [_i] * 11 + [_f, _i, _i, _i, _i, _vp]),
+    "fa_mi355x_ragged_sink_splits": (_i, [_i] * 9),
+    "fa_mi355x_ragged_sink_workspace_bytes": (_sz, [_i] * 8),
+    "fa_mi355x_fwd_ragged_sink": (_i, [_vp] * 11 + [_i] * 11 + [_f, _i, _i, _i, _i, _vp]),
+}
+
 # the same for include/flash_attn_mi355x_decode_fp8.h (caches of e4m3 bytes with per-kv-head scales; tests/test_fp8_cpu.py)
 FP8_ABI = {
     "fa_mi355x_fwd_decode_fp8": (_i, [_vp] * 12 + [_i] * 11 + [_f, _i, _i, _vp]),
@@ -236,9 +249,9 @@ DECODE_NAME = "libflash_attn_mi355x_decode.so"
 
 
 def decode() -> ctypes.CDLL:
-    """libflash_attn_mi355x_decode.so (include/flash_attn_mi355x_decode.h, its _paged.h, its _ragged.h, its _window.h and its _fp8.h)
-    with argtypes set."""
-    return _typed(DECODE_NAME, {**DECODE_ABI, **PAGED_ABI, **RAGGED_ABI, **WINDOW_ABI, **FP8_ABI})
+    """libflash_attn_mi355x_decode.so (include/flash_attn_mi355x_decode.h, its _paged.h, its _ragged.h, its _window.h, its _fp8.h and its
+    _sink.h) with argtypes set."""
+    return _typed(DECODE_NAME, {**DECODE_ABI, **PAGED_ABI, **RAGGED_ABI, **WINDOW_ABI, **FP8_ABI, **SINK_ABI})
 
 
 def decode_check(status: int) -> None:

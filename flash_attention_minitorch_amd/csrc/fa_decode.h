@@ -53,6 +53,16 @@
 // an edge.  Everything is wave-uniform and derived from len on the device.  The WINDOW = false builds are the code they were
 // (DESIGN.md "Window").
 //
+// Attention sinks (decode_split_sink_kernel, extend_split_sink_kernel; include/flash_attn_mi355x_decode_sink.h): a windowed call in
+// which every query also admits the first S positions, j < S.  A row block's key range is two ranges walked as one loop in ascending
+// key order: the super tiles 0 .. vs - 128 that hold a sink key and lie wholly below lo (vs = min(S rounded up to a tile, lo)), then
+// the window's tiles from lo on; a tile at or above lo that holds keys below S admits them through the mask, so no key counts
+// twice.  The splits cut the virtual axis on which the two ranges are adjacent (sink_chunk), so they stay balanced wherever the
+// jump from vs to lo falls; a paged walk re-initialises at lo and reads no table entry in between.  The staged rows S <= j < wedge
+// become zeros (zero_rows: the tail of the last sink tile, the head of the first window tile).  The sink kernels share their body
+// with the other builds as TEXT (fa_decode_split_body.h, fa_decode_extend_body.h), so the other builds are the code they were
+// (DESIGN.md "Sinks").
+//
 // FP8 caches (the FP8 builds of the split, extend and combine kernels, and append_fp8_kernel; include/flash_attn_mi355x_decode_fp8.h):
 // the caches hold OCP e4m3fn bytes and the real value of an element of kv head h is scale[h] * e4m3 (k_scale / v_scale, fp32 arrays
 // of Hkv entries read on the device).  Every e4m3 value is a bf16 value, so a tile goes HBM -> registers as bytes and is widened to
@@ -104,6 +114,14 @@ struct Fp8Args : DecodeArgs {
   const float* k_scale;   // [Hkv] or null
   const float* v_scale;   // [Hkv] or null
 };
+// The arguments of the SINK builds, likewise: S, the number of leading positions every later query keeps (1 <= S < Ncap).
+struct SinkArgs : DecodeArgs {
+  int sink;
+};
+struct RaggedSinkArgs : RaggedArgs {
+  int sink;
+};
+template <bool RAGGED> using SinkArgsOf = typename std::conditional<RAGGED, RaggedSinkArgs, SinkArgs>::type;
 template <bool RAGGED, bool FP8 = false>
 using DecodeArgsOf = typename std::conditional<FP8, Fp8Args, typename std::conditional<RAGGED, RaggedArgs, DecodeArgs>::type>::type;
 // (positive and finite is the caller's contract: the kernels do not check a scale)
@@ -153,6 +171,15 @@ template <typename S> FA_DEV void zero_below(S& st, int n) {
 #pragma unroll
   for (int i = 0; i < S::PER; ++i)
     if (row + i * S::RSTEP < n) st.regs[i] = u32x4{0u, 0u, 0u, 0u};
+}
+
+// Sink builds: the range form.  The staged rows n0 <= row < n1 become zeros (n0 may be negative, n1 past the tile): the rows at or
+// past the last sink key and below the block's window edge, in the last sink tile and in the first tile of the window's range.
+template <typename S> FA_DEV void zero_rows(S& st, int n0, int n1) {
+  const int row = st.voff / st.ldb;
+#pragma unroll
+  for (int i = 0; i < S::PER; ++i)
+    if (row + i * S::RSTEP >= n0 && row + i * S::RSTEP < n1) st.regs[i] = u32x4{0u, 0u, 0u, 0u};
 }
 
 // FP8 builds: TileStager<bf16_t, D, DEC_ROWS, 256> for rows of one byte per element.  The thread -> (row, 16-byte bf16 chunk) map and
@@ -229,218 +256,49 @@ struct PageWalk {
   }
 };
 
+// Sink builds (include/flash_attn_mi355x_decode_sink.h): a row block walks the super tiles 0 .. vs - 128 that hold a sink key and
+// lie wholly below lo, the start of its window range, and then the tiles from lo on: one loop in ascending key order.
+// The tile behind the one at t on that walk (t + DEC_ROWS == vs is the jump; vs == lo: the two ranges are adjacent).
+FA_DEV int sink_next(int t, int vs, int lo) { return t + DEC_ROWS == vs ? lo : t + DEC_ROWS; }
+// The bounds of split `split` of that walk in logical keys.  The splits cut the VIRTUAL axis on which the two ranges are adjacent
+// (virtual key v is key v below vs and key v + lo - vs from there on), so they stay balanced, and a split past the end is empty.
+FA_DEV void sink_chunk(int split, int chunk, int len, int vs, int lo, int& c0, int& c1) {
+  const int jump = lo - vs, v0 = split * chunk, v1 = min(v0 + chunk, len - jump);
+  c0 = v0 + (v0 >= vs ? jump : 0);   // (a split that starts at the jump starts at lo)
+  c1 = v1 + (v1 > vs ? jump : 0);    // (one that ends at it ends at vs: c1 is never inside (vs, lo])
+}
+// PageWalk::load for the tile at t, which leaves the walk at sink_next(t) if that tile lies below `end`: at the jump by an init
+// at lo, so that the table entries between the last sink tile's page and lo's page are never read.
+template <typename C, int D, typename S>
+FA_DEV void sink_load(PageWalk& pw, const DecodeArgs& a, int b, S& sk, S& sv, size_t hoff, int len, int t, int vs, int lo, int end) {
+  const int t2 = sink_next(t, vs, lo);
+  const bool more = t2 < end, jump = t2 != t + DEC_ROWS;
+  pw.template load<C, D>(a, sk, sv, hoff, len, more && !jump);
+  if (more && jump) pw.init(a, b, t2);
+}
+
 // GROUPED = false is the G = 1 build: rho = i with no row arithmetic in front of the workgroup's first loads (a workgroup lives for a
 // few super tiles, so its prologue is not free: DESIGN.md "Decode").  PAGED: the cache is a pool read through a block table (PageWalk).
 // WINDOW: a sliding window of a.window keys (causal).  The key range belongs to the 32-row BLOCK, not to the call: wedge is the
 // lowest key the block's first row admits, so every block walks about W + 32 + 127 keys whatever Nq.
 // FP8: the caches hold e4m3 bytes (C, the cache's element type, is a byte) and a carries the two scales; T, the queries' type and
 // the type of the LDS image, is bf16.  tau8 = tau * k_scale[hkv] stands for tau wherever the kernel uses it.
+// SINK (with WINDOW; a.sink = S): the first S positions stay admitted beside the window; the key range becomes the sink tiles, then
+// the window's (above).  The sink builds are kernels of their own, decode_split_sink_kernel below, with the same body: it is
+// fa_decode_split_body.h, included as text in both (that file says why it is not a function).
 template <typename T, int D, bool GROUPED, bool PAGED = false, bool WINDOW = false, bool FP8 = false>
 __global__ void __launch_bounds__(256) decode_split_kernel(DecodeArgsOf<false, FP8> a) {
-  static_assert(!FP8 || (std::is_same<T, bf16_t>::value && GROUPED && !WINDOW), "fp8 caches: bf16 queries, the grouped form, no window");
-  using A = Atom<T>;
-  typedef typename std::conditional<FP8, uint8_t, T>::type C;
-  typedef typename A::frag frag;
-  constexpr int KC = D / 16, DT = D / 32;
-  constexpr int TB = A::template tile_bytes<D>(DEC_ROWS);
-  constexpr int PW = (16 * DT + 2) * 64 * 4;   // one wave's partial: [lane][16*DT accumulator registers, m, l]
-  static_assert(3 * PW <= 2 * TB, "the partials of waves 1-3 must fit the tile images");
-  __shared__ __attribute__((aligned(16))) char smem_raw[2 * TB];
-  lds_char* tk = (lds_char*)smem_raw;
-  lds_char* tv = tk + TB;
-
-  // workgroup -> (item = (b * Hkv + kv head) * nsplit + split, row block): the row blocks of one item are 8 workgroup ids apart, so
-  // they share an XCD's L2 under round-robin dispatch and the chunk is fetched from HBM once (speed only)
-  const int id = blockIdx.x, slot = id >> 3;
-  const int qb = slot % a.nqb, item = (slot / a.nqb) * 8 + (id & 7);
-  if (item >= a.items) return;
-  const int bh = item / a.nsplit, split = item - bh * a.nsplit;
-  const int b = bh / a.Hkv, hkv = bh - b * a.Hkv;
-  const int len = __builtin_amdgcn_readfirstlane(clamp_len(a, b));
-  int wedge = 0;   // (window builds) the block's window edge; the key range starts at the super tile that holds it
-  if constexpr (WINDOW) wedge = max(len - a.Nq + (GROUPED ? row_query(a, qb * 32) : qb * 32) - a.window + 1, 0);
-  const int c0 = (WINDOW ? wedge & ~(DEC_ROWS - 1) : 0) + split * a.chunk, c1 = min(c0 + a.chunk, len);
-
-  const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // the lane's row rho = qi * G + g: query qi of head hd = hkv * G + g
-  const int G = GROUPED ? a.G : 1;
-  const int q0 = qb * 32, rho = q0 + r, qi = GROUPED ? row_query(a, rho) : rho, hd = hkv * G + (rho - qi * G);
-  const bool live = rho < G * a.Nq;
-  // (a macro, as FA_NQ below: the other builds read a.tau where they always did)
-  float tau8 = 0.f;
-  if constexpr (FP8) tau8 = a.tau * scale_of(a.k_scale, hkv);
-#define FA_TAU (FP8 ? tau8 : a.tau)
-  const float c = FA_TAU * LOG2E;
-
-  f32x16 acc_o[DT];
-#pragma unroll
-  for (int dt = 0; dt < DT; ++dt) acc_o[dt] = zero16();
-  float m_run = -INFINITY, l_run = 0.f;
-
-  if (c0 < c1) {   // (a chunk wholly past len_b loads nothing and leaves the empty partial m = -inf, l = 0)
-    const size_t kvoff = (PAGED ? 0 : (size_t)b * a.kv_bstride) + (size_t)hkv * a.kv_hstride;   // (paged: inside a page)
-    const uint32_t esz = sizeof(T);
-    const uint32_t q_bytes = (uint32_t)a.q_bstride * esz;
-    const rsrc_t qrs = make_rsrc(reinterpret_cast<const T*>(a.q) + (size_t)b * a.q_bstride, q_bytes);
-    const uint32_t kv_bytes = ((uint32_t)(len - 1) * a.kv_ld + D) * (uint32_t)sizeof(C);
-    const rsrc_t krs = make_rsrc(reinterpret_cast<const C*>(a.k) + kvoff, kv_bytes);   // (the slab's: unused by a paged build)
-    const rsrc_t vrs = make_rsrc(reinterpret_cast<const C*>(a.v) + kvoff, kv_bytes);
-    PageWalk pw;
-
-    frag qf[KC];
-    const int qoff = live ? (hd * (int)a.q_hstride + qi * a.q_ld + 8 * h) * (int)esz : (int)q_bytes;
-#pragma unroll
-    for (int kc = 0; kc < KC; ++kc) qf[kc] = load_frag_buf<T>(qrs, qoff + 16 * kc * (int)esz);
-
-    const LaneAddr ra = A::template row_addr<D>(lane);
-    const LaneAddr ta = A::template tr_addr<D>(lane);
-    typename std::conditional<FP8, Fp8Stager<D>, TileStager<T, D, DEC_ROWS, 256>>::type sk, sv;
-    sk.init(tid, a.kv_ld);
-    sv.init(tid, a.kv_ld);
-    // causal: query i sits at position len - Nq + i and sees keys j <= len - Nq + i (bottom-right aligned); the block's rows span
-    // the positions pos_lo .. pos_hi (wave-uniform; pos_hi may count rows past G * Nq, which only keeps a tile that masks to nothing)
-    const int qpos = len - a.Nq + qi;
-    const int pos_lo = len - a.Nq + (GROUPED ? row_query(a, q0) : q0), pos_hi = len - a.Nq + (GROUPED ? row_query(a, q0 + 31) : q0 + 31);
-    if constexpr (PAGED) {
-      pw.init(a, b, c0);
-      pw.template load<C, D>(a, sk, sv, kvoff, len, c0 + DEC_ROWS < c1);
-    } else {
-      load_rows(sk, krs, c0);
-      load_rows(sv, vrs, c0);
-    }
-    if constexpr (WINDOW) {
-      if (c0 < wedge) {   // (split 0 of a block whose edge is inside a super tile)
-        zero_below(sk, wedge - c0);
-        zero_below(sv, wedge - c0);
-      }
-    }
-    for (int t0 = c0; t0 < c1; t0 += DEC_ROWS) {
-      __syncthreads();   // (the previous super tile's reads are done)
-      sk.store(tk);
-      sv.store(tv);
-      if (t0 + DEC_ROWS < c1) {
-        if constexpr (PAGED) {
-          pw.template load<C, D>(a, sk, sv, kvoff, len, t0 + 2 * DEC_ROWS < c1);
-        } else {
-          load_rows(sk, krs, t0 + DEC_ROWS);
-          load_rows(sv, vrs, t0 + DEC_ROWS);
-        }
-      }
-      __syncthreads();
-      const int kbase = t0 + 32 * w;
-      if (kbase >= c1 || (a.causal && kbase > pos_hi)) continue;   // wave-uniform: no admissible key in the wave's 32
-      if constexpr (WINDOW) {
-        if (kbase + 31 <= pos_lo - a.window) continue;   // wave-uniform: the 32 keys are below every row's window
-      }
-      f32x16 s = zero16();
-#pragma unroll
-      for (int kc = 0; kc < KC; ++kc) A::mma(s, A::template row_frag<D>(tk, ra, 32 * w, kc), qf[kc]);
-      // (window: only the sub-tiles that hold a key at or below the highest row's edge - 1 mask for it)
-      if (kbase + 32 > c1 || (a.causal && kbase + 31 > pos_lo) || (WINDOW && kbase <= pos_hi - a.window)) {   // wave-uniform
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const int key = kbase + acc_row(i, h);
-          if (key >= c1 || (a.causal && key > qpos) || (WINDOW && key <= qpos - a.window)) s[i] = -INFINITY;
-        }
-      }
-      float mx = s[0];
-#pragma unroll
-      for (int i = 1; i < 16; ++i) mx = fmaxf(mx, s[i]);
-      const float m_new = fmaxf(m_run, xhalf_max(mx));
-      const float nm = (m_new == -INFINITY) ? 0.f : -m_new * c;   // (every key so far masked: any finite reference, P = 0)
-      const float alpha = __builtin_amdgcn_exp2f(__builtin_fmaf(m_run, c, nm));
-      float rs = 0.f;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        s[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[i], c, nm));
-        rs += s[i];
-      }
-      if (__any(alpha != 1.0f)) {
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-          for (int i = 0; i < 16; ++i) acc_o[dt][i] *= alpha;
-      }
-      l_run = l_run * alpha + rs;
-      m_run = m_new;
-      // bf16: P goes in at 16 significant bits (pack + pack_lo): a row with few admissible keys holds P of order 1, whose 2^-9
-      // rounding would not average out (the decode step's first tokens, causal rows near position 0)
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        const frag p_hi = A::pack(s, s2);
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) {
-          const frag vt = A::template tr_frag<D>(tv, ta, 32 * w + 16 * s2, dt);
-          A::mma(acc_o[dt], vt, p_hi);
-          if constexpr (A::SPLITS) A::mma(acc_o[dt], vt, A::pack_lo(s, s2, p_hi));
-        }
-      }
-    }
-  }
-  const float l_w = xhalf_sum(l_run);
-
-  // the partials of waves 1-3 meet in LDS (over the tile images), wave 0 adds them in wave order
-  __syncthreads();
-  if (w != 0) {
-    lds_char* mine = tk + (w - 1) * PW + lane * (16 * DT + 2) * 4;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) *FA_LDS(float, mine + (16 * dt + i) * 4) = acc_o[dt][i];
-    *FA_LDS(float, mine + 16 * DT * 4) = m_run;
-    *FA_LDS(float, mine + (16 * DT + 1) * 4) = l_w;
-  }
-  __syncthreads();
-  if (w != 0) return;
-  float m_all = m_run;
-#pragma unroll
-  for (int u = 0; u < 3; ++u) m_all = fmaxf(m_all, *FA_LDS(float, tk + u * PW + (lane * (16 * DT + 2) + 16 * DT) * 4));
-  float wgt = (m_run == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f((m_run - m_all) * c);
-  float l_tot = l_w * wgt;
-#pragma unroll
-  for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc_o[dt][i] *= wgt;
-#pragma unroll
-  for (int u = 0; u < 3; ++u) {
-    lds_char* pu = tk + u * PW + lane * (16 * DT + 2) * 4;
-    const float mu = *FA_LDS(float, pu + 16 * DT * 4);
-    wgt = (mu == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f((mu - m_all) * c);
-    l_tot += *FA_LDS(float, pu + (16 * DT + 1) * 4) * wgt;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc_o[dt][i] += *FA_LDS(float, pu + (16 * dt + i) * 4) * wgt;
-  }
-  if (!live) return;
-  const size_t bhq = (size_t)b * a.H + hd;
-  if (a.nsplit == 1) {   // final: out = O / l, lse = m * tau + ln l; a row without an admissible key: out = 0, lse = -inf
-    float inv = (l_tot > 0.f) ? 1.0f / l_tot : 0.f;
-    if constexpr (FP8) inv *= scale_of(a.v_scale, hkv);   // (the scale of V: once per row, on 1 / l)
-    float* orow = a.out + (size_t)b * a.q_bstride + (size_t)hd * a.q_hstride + (size_t)qi * a.q_ld;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        f32x4 val = {acc_o[dt][4 * g] * inv, acc_o[dt][4 * g + 1] * inv, acc_o[dt][4 * g + 2] * inv, acc_o[dt][4 * g + 3] * inv};
-        *reinterpret_cast<f32x4*>(orow + 32 * dt + 8 * g + 4 * h) = val;
-      }
-    if (h == 0 && a.lse) a.lse[bhq * a.Nq + qi] = (l_tot > 0.f) ? m_all * FA_TAU + __logf(l_tot) : -INFINITY;
-  } else {
-    const size_t pr = (bhq * a.nsplit + split) * a.Nq + qi;
-    float* prow = a.part_o + pr * D;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        f32x4 val = {acc_o[dt][4 * g], acc_o[dt][4 * g + 1], acc_o[dt][4 * g + 2], acc_o[dt][4 * g + 3]};
-        *reinterpret_cast<f32x4*>(prow + 32 * dt + 8 * g + 4 * h) = val;
-      }
-    if (h == 0) *reinterpret_cast<f32x2*>(a.part_ml + 2 * pr) = f32x2{m_all, l_tot};
-  }
+  constexpr bool SINK = false;
+#include "fa_decode_split_body.h"
 }
-#undef FA_TAU
+
+// The SINK builds: grouped and windowed, slab or paged.  (The argument is SinkArgs, spelled as a type that depends on a template
+// parameter: the body's FP8 statements name fields it does not have, and are discarded unchecked only under a dependent type.)
+template <typename T, int D, bool PAGED>
+__global__ void __launch_bounds__(256) decode_split_sink_kernel(SinkArgsOf<PAGED && false> a) {
+  constexpr bool GROUPED = true, WINDOW = true, FP8 = false, SINK = true;
+#include "fa_decode_split_body.h"
+}
 
 // ---- extend: any number of new queries against the cache ---------------------------------------------------------------------------
 // The split kernel's semantics for any Nq >= 1 with the roles of its waves swapped: a workgroup = one (batch*kv head, key chunk,
@@ -459,197 +317,19 @@ constexpr int EXT_BLOCK = 128;   // rows per workgroup: 32 per wave
 // start of the block's key range what blk_hi is to its end: a block walks about W + 128 + 127 keys wherever it sits in a long
 // input.  Each wave then skips and masks by its own 32 rows' edges.
 // FP8: as in decode_split_kernel (C: a byte; tau8 for tau; v_scale on the final 1 / l).
+// SINK: as in decode_split_kernel, per 128-row block; the body is fa_decode_extend_body.h, included as text in both kernels.
 template <typename T, int D, bool PAGED = false, bool RAGGED = false, bool WINDOW = false, bool FP8 = false>
 __global__ void __launch_bounds__(256) extend_split_kernel(DecodeArgsOf<RAGGED, FP8> a) {
-  static_assert(!FP8 || (std::is_same<T, bf16_t>::value && !RAGGED && !WINDOW), "fp8 caches: bf16 queries, no ragged form, no window");
-  using A = Atom<T>;
-  typedef typename std::conditional<FP8, uint8_t, T>::type C;
-  typedef typename A::frag frag;
-  constexpr int KC = D / 16, DT = D / 32;
-  constexpr int TB = A::template tile_bytes<D>(DEC_ROWS);
-  __shared__ __attribute__((aligned(16))) char smem_raw[2 * TB];
-  lds_char* tk = (lds_char*)smem_raw;
-  lds_char* tv = tk + TB;
-
-  // workgroup -> (item, row block) as in decode_split_kernel: the row blocks of one item share an XCD's L2
-  const int id = blockIdx.x, slot = id >> 3;
-  const int entry = slot % a.nqb, item = (slot / a.nqb) * 8 + (id & 7);
-  if (item >= a.items) return;
-  const int bh = item / a.nsplit, split = item - bh * a.nsplit;
-  int b_ = bh / a.Hkv, hkv_ = bh - b_ * a.Hkv, qb_ = entry, row0_ = 0, nq_ = 0;
-  if constexpr (RAGGED) {
-    b_ = __builtin_amdgcn_readfirstlane(a.map[2 * entry]);
-    if (b_ < 0) return;   // (an unused entry: the map is sized for the worst case)
-    qb_ = __builtin_amdgcn_readfirstlane(a.map[2 * entry + 1]);
-    hkv_ = bh;
-    seq_rows(a.cu, a.ntok, b_, row0_, nq_);
-    row0_ = __builtin_amdgcn_readfirstlane(row0_);
-    nq_ = __builtin_amdgcn_readfirstlane(nq_);
-  }
-  const int b = b_, hkv = hkv_, qb = qb_, row0 = row0_;
-  // The sequence's own count, or the call's.  A macro, not a local `const int Nq`: a local reads a.Nq once at the top of the uniform
-  // build, which moved two of its fp32 builds from 58 to 59 SGPRs; with a.Nq read where it always was, the uniform builds compile to
-  // the code they were (DESIGN.md "Ragged").  Do not fold it into a variable without comparing the resource report.
-#define FA_NQ (RAGGED ? nq_ : a.Nq)
-  const int len = __builtin_amdgcn_readfirstlane(clamp_len(a, b));
-  int wedge = 0;   // (window builds) the block's window edge; the key range starts at the super tile that holds it
-  if constexpr (WINDOW) wedge = max(len - FA_NQ + row_query(a, qb * EXT_BLOCK) - a.window + 1, 0);
-  const int c0 = (WINDOW ? wedge & ~(DEC_ROWS - 1) : 0) + split * a.chunk, c1 = min(c0 + a.chunk, len);
-
-  const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int rows = a.G * FA_NQ;
-  const int q0 = qb * EXT_BLOCK + 32 * w, rho = q0 + r, qi = row_query(a, rho), hd = hkv * a.G + (rho - qi * a.G);
-  const bool live = rho < rows;
-  const bool wave_live = q0 < rows;   // (wave-uniform)
-  float tau8 = 0.f;
-  if constexpr (FP8) tau8 = a.tau * scale_of(a.k_scale, hkv);
-#define FA_TAU (FP8 ? tau8 : a.tau)
-  const float c = FA_TAU * LOG2E;
-  // causal: the last key any row of the block sees is the position of its last row (of its last REAL row: rows >= G * Nq see nothing)
-  const int blk_hi = len - FA_NQ + row_query(a, min(qb * EXT_BLOCK + EXT_BLOCK, rows) - 1);
-  const int cend = a.causal ? min(c1, blk_hi + 1) : c1;
-
-  f32x16 acc_o[DT];
-#pragma unroll
-  for (int dt = 0; dt < DT; ++dt) acc_o[dt] = zero16();
-  float m_run = -INFINITY, l_run = 0.f;
-
-  if (c0 < cend) {   // (a chunk past len_b, or past every position of the block, loads nothing and leaves m = -inf, l = 0)
-    const size_t kvoff = (PAGED ? 0 : (size_t)b * a.kv_bstride) + (size_t)hkv * a.kv_hstride;   // (paged: inside a page)
-    const uint32_t esz = sizeof(T);
-    // (ragged: the resource of the sequence's own nq_b * H * D elements of the packed q)
-    const uint32_t q_bytes = RAGGED ? (uint32_t)nq_ * (uint32_t)a.q_ld * esz : (uint32_t)a.q_bstride * esz;
-    const rsrc_t qrs = make_rsrc(reinterpret_cast<const T*>(a.q) + (RAGGED ? (size_t)row0 * a.q_ld : (size_t)b * a.q_bstride), q_bytes);
-    const uint32_t kv_bytes = ((uint32_t)(len - 1) * a.kv_ld + D) * (uint32_t)sizeof(C);
-    const rsrc_t krs = make_rsrc(reinterpret_cast<const C*>(a.k) + kvoff, kv_bytes);   // (the slab's: unused by a paged build)
-    const rsrc_t vrs = make_rsrc(reinterpret_cast<const C*>(a.v) + kvoff, kv_bytes);
-    PageWalk pw;
-
-    frag qf[KC];
-    const int qoff = live ? (hd * (int)a.q_hstride + qi * a.q_ld + 8 * h) * (int)esz : (int)q_bytes;
-#pragma unroll
-    for (int kc = 0; kc < KC; ++kc) qf[kc] = load_frag_buf<T>(qrs, qoff + 16 * kc * (int)esz);
-
-    const LaneAddr ra = A::template row_addr<D>(lane);
-    const LaneAddr ta = A::template tr_addr<D>(lane);
-    typename std::conditional<FP8, Fp8Stager<D>, TileStager<T, D, DEC_ROWS, 256>>::type sk, sv;
-    sk.init(tid, a.kv_ld);
-    sv.init(tid, a.kv_ld);
-    // the wave's rows span the positions pos_lo .. pos_hi (wave-uniform; rows past G * Nq may push pos_hi up, which only keeps a
-    // sub-tile that masks to nothing for the real rows' lanes)
-    const int qpos = len - FA_NQ + qi;
-    const int pos_lo = len - FA_NQ + row_query(a, q0), pos_hi = len - FA_NQ + row_query(a, q0 + 31);
-    if constexpr (PAGED) {
-      pw.init(a, b, c0);
-      pw.template load<C, D>(a, sk, sv, kvoff, len, c0 + DEC_ROWS < cend);
-    } else {
-      load_rows(sk, krs, c0);
-      load_rows(sv, vrs, c0);
-    }
-    if constexpr (WINDOW) {
-      if (c0 < wedge) {   // (split 0 of a block whose edge is inside a super tile)
-        zero_below(sk, wedge - c0);
-        zero_below(sv, wedge - c0);
-      }
-    }
-    for (int t0 = c0; t0 < cend; t0 += DEC_ROWS) {
-      __syncthreads();   // (the previous super tile's reads are done)
-      sk.store(tk);
-      sv.store(tv);
-      if (t0 + DEC_ROWS < cend) {
-        if constexpr (PAGED) {
-          pw.template load<C, D>(a, sk, sv, kvoff, len, t0 + 2 * DEC_ROWS < cend);
-        } else {
-          load_rows(sk, krs, t0 + DEC_ROWS);
-          load_rows(sv, vrs, t0 + DEC_ROWS);
-        }
-      }
-      __syncthreads();
-      if (!wave_live) continue;
-#pragma unroll
-      for (int st = 0; st < DEC_ROWS / 32; ++st) {
-        const int kbase = t0 + 32 * st;
-        if (kbase >= cend || (a.causal && kbase > pos_hi)) break;   // wave-uniform: no admissible key here or further on
-        if constexpr (WINDOW) {
-          if (kbase + 31 <= pos_lo - a.window) continue;   // wave-uniform: the 32 keys are below every window of the wave's rows
-        }
-        f32x16 s = zero16();
-#pragma unroll
-        for (int kc = 0; kc < KC; ++kc) A::mma(s, A::template row_frag<D>(tk, ra, 32 * st, kc), qf[kc]);
-        // (window: only the sub-tiles that hold a key at or below the wave's highest edge - 1 mask for it)
-        if (kbase + 32 > c1 || (a.causal && kbase + 31 > pos_lo) || (WINDOW && kbase <= pos_hi - a.window)) {   // wave-uniform
-#pragma unroll
-          for (int i = 0; i < 16; ++i) {
-            const int key = kbase + acc_row(i, h);
-            if (key >= c1 || (a.causal && key > qpos) || (WINDOW && key <= qpos - a.window)) s[i] = -INFINITY;
-          }
-        }
-        float mx = s[0];
-#pragma unroll
-        for (int i = 1; i < 16; ++i) mx = fmaxf(mx, s[i]);
-        const float m_new = fmaxf(m_run, xhalf_max(mx));
-        const float nm = (m_new == -INFINITY) ? 0.f : -m_new * c;   // (every key so far masked: any finite reference, P = 0)
-        const float alpha = __builtin_amdgcn_exp2f(__builtin_fmaf(m_run, c, nm));
-        float rs = 0.f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          s[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[i], c, nm));
-          rs += s[i];
-        }
-        if (__any(alpha != 1.0f)) {
-#pragma unroll
-          for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc_o[dt][i] *= alpha;
-        }
-        l_run = l_run * alpha + rs;
-        m_run = m_new;
-        // bf16: P at 16 significant bits (pack + pack_lo), as in decode_split_kernel
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          const frag p_hi = A::pack(s, s2);
-#pragma unroll
-          for (int dt = 0; dt < DT; ++dt) {
-            const frag vt = A::template tr_frag<D>(tv, ta, 32 * st + 16 * s2, dt);
-            A::mma(acc_o[dt], vt, p_hi);
-            if constexpr (A::SPLITS) A::mma(acc_o[dt], vt, A::pack_lo(s, s2, p_hi));
-          }
-        }
-      }
-    }
-  }
-  const float l_tot = xhalf_sum(l_run);
-  if (!live) return;   // (no barrier follows)
-  // (ragged: out, lse and the partials by packed row row0 + qi, as one batch element of a.Nq = ntok queries)
-  const size_t bhq = RAGGED ? (size_t)hd : (size_t)b * a.H + hd;
-  if (a.nsplit == 1) {   // final: out = O / l, lse = m * tau + ln l; a row without an admissible key: out = 0, lse = -inf
-    float inv = (l_tot > 0.f) ? 1.0f / l_tot : 0.f;
-    if constexpr (FP8) inv *= scale_of(a.v_scale, hkv);   // (the scale of V: once per row, on 1 / l)
-    float* orow = a.out + (RAGGED ? 0 : (size_t)b * a.q_bstride) + (size_t)hd * a.q_hstride + (size_t)(RAGGED ? row0 + qi : qi) * a.q_ld;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        f32x4 val = {acc_o[dt][4 * g] * inv, acc_o[dt][4 * g + 1] * inv, acc_o[dt][4 * g + 2] * inv, acc_o[dt][4 * g + 3] * inv};
-        *reinterpret_cast<f32x4*>(orow + 32 * dt + 8 * g + 4 * h) = val;
-      }
-    if (h == 0 && a.lse) a.lse[bhq * a.Nq + (RAGGED ? row0 + qi : qi)] = (l_tot > 0.f) ? m_run * FA_TAU + __logf(l_tot) : -INFINITY;
-  } else {
-    const size_t pr = (bhq * a.nsplit + split) * a.Nq + (RAGGED ? row0 + qi : qi);
-    float* prow = a.part_o + pr * D;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        f32x4 val = {acc_o[dt][4 * g], acc_o[dt][4 * g + 1], acc_o[dt][4 * g + 2], acc_o[dt][4 * g + 3]};
-        *reinterpret_cast<f32x4*>(prow + 32 * dt + 8 * g + 4 * h) = val;
-      }
-    if (h == 0) *reinterpret_cast<f32x2*>(a.part_ml + 2 * pr) = f32x2{m_run, l_tot};
-  }
+  constexpr bool SINK = false;
+#include "fa_decode_extend_body.h"
 }
-#undef FA_NQ
-#undef FA_TAU
+
+// The SINK builds: windowed, slab or paged, uniform or ragged.
+template <typename T, int D, bool PAGED, bool RAGGED>
+__global__ void __launch_bounds__(256) extend_split_sink_kernel(SinkArgsOf<RAGGED> a) {
+  constexpr bool WINDOW = true, FP8 = false, SINK = true;
+#include "fa_decode_extend_body.h"
+}
 
 // out[row] = sum_s O_s 2^(c (m_s - M)) / sum_s l_s 2^(c (m_s - M)), M = max_s m_s.  A workgroup = one (bh, row): thread (g, j) takes
 // columns 4g .. 4g+3 of the splits j, j + S, j + 2S, ... and the S partial sums of a column group are added in the order j = 0 .. S-1

@@ -2,7 +2,7 @@
 // argument checks, the split policies (decode: 32-row blocks, at most 128 queries; extend: 128-row blocks, any number; ragged: the
 // extend policy on an upper bound of the row blocks) and the launches of the kernels of fa_decode.h.  A paged call (a pool and a
 // block table) takes the contiguous call's policy at Ncap = max_pages * page_size.  A windowed call (_window.h) takes the three
-// policies on its window span (span_keys) instead of Ncap.  An fp8 call (_fp8.h: caches of e4m3 bytes, per-kv-head scales) takes the
+// policies on its window span (span_keys) instead of Ncap, a sink call (_sink.h) on that span plus its sink tiles.  An fp8 call (_fp8.h: caches of e4m3 bytes, per-kv-head scales) takes the
 // bf16 call's policy and workspace for the same arguments; its cache bounds count one byte per element.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -82,7 +82,10 @@ size_t ext_workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int d) {
 // Sliding window (include/flash_attn_mi355x_decode_window.h).  A window of W >= Ncap keys admits every key of every row (a row's
 // position is at most len - 1 <= Ncap - 1): such a call IS the unwindowed call, the same launches and the same bits, and so is
 // W = 0.  This also bounds what the device computes with: W < Ncap.
-int win_of(int window, int Ncap) { return window >= Ncap ? 0 : window; }
+// Sinks (include/flash_attn_mi355x_decode_sink.h): S >= Ncap first positions admit every key of every row as well, and S = 0 is
+// the windowed call; sinks without a window mean nothing.  The device computes with 1 <= W < Ncap and 0 <= S < Ncap.
+int win_of(int window, int Ncap, int sink = 0) { return window >= Ncap || sink >= Ncap ? 0 : window; }
+int sink_of(int window, int sink, int Ncap) { return win_of(window, Ncap, sink) == 0 ? 0 : sink; }
 
 // The window SPAN: the keys one row block can need, which is what the three policies split where they split Ncap.  A block's rows
 // sit at positions p_first .. p_last with p_last - p_first <= min(Nq, block_rows) - 1 (row i * G + g: block_rows rows span at most
@@ -90,10 +93,13 @@ int win_of(int window, int Ncap) { return window >= Ncap ? 0 : window; }
 // to a super tile, at most 127 keys below the edge, and ends at p_last:
 //   p_last - lo + 1 <= (p_last - p_first) + W + 127 <= W + min(Nq, block_rows) - 1 + 127
 // and never more than the cache holds.  nsplit * chunk >= span, so the splits of every block cover [lo, p_last].
-int span_keys(int window, int Ncap, int Nq, int block_rows) {
-  const int W = win_of(window, Ncap);
+// With S sinks a block walks, in front of that range, the super tiles that hold a sink key and lie wholly below lo: at most
+// ceil(S / 128) of them, which the span counts in full.
+int span_keys(int window, int Ncap, int Nq, int block_rows, int sink = 0) {
+  const int W = win_of(window, Ncap, sink);
   if (W == 0) return Ncap;
-  return (int)std::min((long)Ncap, (long)W + std::min(Nq, block_rows) - 1 + fa::DEC_ROWS - 1);
+  const long sink_keys = ((long)sink + fa::DEC_ROWS - 1) / fa::DEC_ROWS * fa::DEC_ROWS;
+  return (int)std::min((long)Ncap, sink_keys + W + std::min(Nq, block_rows) - 1 + fa::DEC_ROWS - 1);
 }
 
 // workgroups of the split launch: the items rounded up to 8, times the row blocks (the kernels' workgroup -> (item, row block) map)
@@ -118,8 +124,16 @@ size_t rag_workspace_bytes(int B, int H, int Hkv, int T, int Ncap, int d) {
   return rag_map_bytes(B, H, Hkv, T) + (size_t)H * rag_splits(B, H, Hkv, T, Ncap) * T * (size_t)(d + 2) * sizeof(float);
 }
 
-template <typename T, int D> int launch_extend(fa::DecodeArgs a, int BH, hipStream_t st) {
-  if (a.window && a.table)
+template <typename T, int D> int launch_extend(fa::DecodeArgs a, int BH, int sink, hipStream_t st) {
+  if (sink) {   // (the sink builds: their own kernels and argument; a.window >= 1)
+    fa::SinkArgs sa;
+    static_cast<fa::DecodeArgs&>(sa) = a;
+    sa.sink = sink;
+    if (a.table)
+      hipLaunchKernelGGL((fa::extend_split_sink_kernel<T, D, true, false>), dim3((unsigned)split_grid(a.items, a.nqb)), dim3(256), 0, st, sa);
+    else
+      hipLaunchKernelGGL((fa::extend_split_sink_kernel<T, D, false, false>), dim3((unsigned)split_grid(a.items, a.nqb)), dim3(256), 0, st, sa);
+  } else if (a.window && a.table)
     hipLaunchKernelGGL((fa::extend_split_kernel<T, D, true, false, true>), dim3((unsigned)split_grid(a.items, a.nqb)), dim3(256), 0, st, a);
   else if (a.window)
     hipLaunchKernelGGL((fa::extend_split_kernel<T, D, false, false, true>), dim3((unsigned)split_grid(a.items, a.nqb)), dim3(256), 0, st, a);
@@ -137,17 +151,25 @@ template <typename T, int D> int launch_extend(fa::DecodeArgs a, int BH, hipStre
   return FA_OK;
 }
 
-template <typename T> int launch_extend_d(const fa::DecodeArgs& a, int BH, int d, hipStream_t st) {
+template <typename T> int launch_extend_d(const fa::DecodeArgs& a, int BH, int d, int sink, hipStream_t st) {
   switch (d) {
-    case 32: return launch_extend<T, 32>(a, BH, st);
-    case 64: return launch_extend<T, 64>(a, BH, st);
-    default: return launch_extend<T, 128>(a, BH, st);
+    case 32: return launch_extend<T, 32>(a, BH, sink, st);
+    case 64: return launch_extend<T, 64>(a, BH, sink, st);
+    default: return launch_extend<T, 128>(a, BH, sink, st);
   }
 }
 
-template <typename T, int D> int launch(fa::DecodeArgs a, int BH, hipStream_t st) {
+template <typename T, int D> int launch(fa::DecodeArgs a, int BH, int sink, hipStream_t st) {
   const int grid = ((a.items + 7) / 8) * 8 * a.nqb;
-  if (a.window && a.table)   // (the windowed builds: grouped, as the paged one is)
+  if (sink) {   // (the sink builds: their own kernels and argument; grouped, as the windowed builds are; a.window >= 1)
+    fa::SinkArgs sa;
+    static_cast<fa::DecodeArgs&>(sa) = a;
+    sa.sink = sink;
+    if (a.table)
+      hipLaunchKernelGGL((fa::decode_split_sink_kernel<T, D, true>), dim3(grid), dim3(256), 0, st, sa);
+    else
+      hipLaunchKernelGGL((fa::decode_split_sink_kernel<T, D, false>), dim3(grid), dim3(256), 0, st, sa);
+  } else if (a.window && a.table)   // (the windowed builds: grouped, as the paged one is)
     hipLaunchKernelGGL((fa::decode_split_kernel<T, D, true, true, true>), dim3(grid), dim3(256), 0, st, a);
   else if (a.window)
     hipLaunchKernelGGL((fa::decode_split_kernel<T, D, true, false, true>), dim3(grid), dim3(256), 0, st, a);
@@ -167,11 +189,11 @@ template <typename T, int D> int launch(fa::DecodeArgs a, int BH, hipStream_t st
   return FA_OK;
 }
 
-template <typename T> int launch_d(const fa::DecodeArgs& a, int BH, int d, hipStream_t st) {
+template <typename T> int launch_d(const fa::DecodeArgs& a, int BH, int d, int sink, hipStream_t st) {
   switch (d) {
-    case 32: return launch<T, 32>(a, BH, st);
-    case 64: return launch<T, 64>(a, BH, st);
-    default: return launch<T, 128>(a, BH, st);
+    case 32: return launch<T, 32>(a, BH, sink, st);
+    case 64: return launch<T, 64>(a, BH, sink, st);
+    default: return launch<T, 128>(a, BH, sink, st);
   }
 }
 
@@ -245,10 +267,10 @@ int check_page_bytes(int page_size, int Hkv, int d, int dtype, bool fp8 = false)
 
 // The argument checks of fa_mi355x_fwd_decode_gqa, or (extend) of fa_mi355x_fwd_extend: FA_OK, or the error with its message set.
 // page_size > 0: a paged call with Ncap = max_pages * page_size, where the bound on a batch element of the cache is one on a page.
-// window: the splits are those of the window span.  fp8: the caches hold one byte per element and the queries are bf16.
+// window, sink: the splits are those of the window span.  fp8: the caches hold one byte per element and the queries are bf16.
 int check_decode(const void* q, const void* k_cache, const void* v_cache, const float* out, const void* workspace, int B, int H, int Hkv,
                  int Nq, int Ncap, int d, int layout, float softmax_scale, int dtype, bool extend = false, int page_size = 0,
-                 int window = 0, bool fp8 = false) {
+                 int window = 0, bool fp8 = false, int sink = 0) {
   g_err[0] = 0;
   if (B <= 0 || H <= 0 || Nq <= 0 || Ncap <= 0 || d <= 0) return set_err(FA_ERR_BAD_ARG, "B, H, Nq, Ncap and d must be positive");
   if (Hkv <= 0) return set_err(FA_ERR_BAD_ARG, "Hkv must be positive");
@@ -278,14 +300,14 @@ int check_decode(const void* q, const void* k_cache, const void* v_cache, const 
   if ((long)Nq * H * d * esz >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "one batch element of q must stay under 2 GiB");
   if (extend) {
     // (the workgroup counts of the split and the combine launch are unsigned ints, the items an int)
-    const int ens = ext_splits(B, H, Hkv, Nq, span_keys(window, Ncap, Nq, fa::EXT_BLOCK));
+    const int ens = ext_splits(B, H, Hkv, Nq, span_keys(window, Ncap, Nq, fa::EXT_BLOCK, sink));
     if (split_grid((long)B * Hkv * ens, ext_row_blocks(H, Hkv, Nq)) >= (1L << 32) || (long)B * Hkv * ens >= (1L << 31) ||
         (long)B * H * Nq >= (1L << 32))
       return set_err(FA_ERR_BAD_ARG, "too many workgroups for one launch: B * Hkv * splits * row blocks and B * H * Nq must fit an unsigned int");
     if (ens > 1 && !workspace) return set_err(FA_ERR_BAD_ARG, "null workspace: this call needs fa_mi355x_extend_workspace_bytes() bytes");
     return FA_OK;
   }
-  const int ns = splits(B, H, Hkv, Nq, span_keys(window, Ncap, Nq, 32));
+  const int ns = splits(B, H, Hkv, Nq, span_keys(window, Ncap, Nq, 32, sink));
   if (ns > 1 && !workspace) return set_err(FA_ERR_BAD_ARG, "null workspace: this call needs fa_mi355x_decode_workspace_bytes() bytes");
   return FA_OK;
 }
@@ -293,8 +315,8 @@ int check_decode(const void* q, const void* k_cache, const void* v_cache, const 
 // The split (and combine) launches of a checked call: the decode kernels, or (extend) the extend kernels under their own policy.
 int run_decode(const void* q, const void* k_cache, const void* v_cache, float* out, float* lse, const int* cache_seqlens, void* workspace,
                int B, int H, int Hkv, int Nq, int Ncap, int d, int layout, float softmax_scale, int causal, int dtype, void* stream,
-               bool extend = false, const Paging* pg = nullptr, int window = 0, const Fp8* f8 = nullptr) {
-  const int span = span_keys(window, Ncap, Nq, extend ? fa::EXT_BLOCK : 32);   // (no window: Ncap)
+               bool extend = false, const Paging* pg = nullptr, int window = 0, const Fp8* f8 = nullptr, int sink = 0) {
+  const int span = span_keys(window, Ncap, Nq, extend ? fa::EXT_BLOCK : 32, sink);   // (no window: Ncap)
   const int ns = extend ? ext_splits(B, H, Hkv, Nq, span) : splits(B, H, Hkv, Nq, span);
   fa::Fp8Args a;   // (the other builds take its DecodeArgs part)
   a.k_scale = f8 ? f8->k_scale : nullptr;
@@ -315,7 +337,8 @@ int run_decode(const void* q, const void* k_cache, const void* v_cache, float* o
   a.Ncap = Ncap;
   a.nsplit = ns;
   a.chunk = extend ? ext_chunk_keys(B, H, Hkv, Nq, span) : chunk_keys(B, H, Hkv, Nq, span);
-  a.window = win_of(window, Ncap);
+  a.window = win_of(window, Ncap, sink);
+  sink = sink_of(window, sink, Ncap);
   a.nqb = extend ? ext_row_blocks(H, Hkv, Nq) : row_blocks(H, Hkv, Nq);
   a.items = B * Hkv * ns;
   const bool bnhd = layout == FA_LAYOUT_BNHD;
@@ -341,8 +364,8 @@ int run_decode(const void* q, const void* k_cache, const void* v_cache, float* o
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (f8) return launch_fp8_d(a, B * H, d, extend, st);
-  if (extend) return dtype == FA_DTYPE_BF16 ? launch_extend_d<fa::bf16_t>(a, B * H, d, st) : launch_extend_d<float>(a, B * H, d, st);
-  return dtype == FA_DTYPE_BF16 ? launch_d<fa::bf16_t>(a, B * H, d, st) : launch_d<float>(a, B * H, d, st);
+  if (extend) return dtype == FA_DTYPE_BF16 ? launch_extend_d<fa::bf16_t>(a, B * H, d, sink, st) : launch_extend_d<float>(a, B * H, d, sink, st);
+  return dtype == FA_DTYPE_BF16 ? launch_d<fa::bf16_t>(a, B * H, d, sink, st) : launch_d<float>(a, B * H, d, sink, st);
 }
 
 // The argument checks of the append: FA_OK, or the error with its message set.
@@ -450,7 +473,8 @@ int run_append(const void* k_new, const void* v_new, void* k_cache, void* v_cach
 // The argument checks of fa_mi355x_fwd_ragged: those of fa_mi355x_fwd_extend with T in the place of Nq, a null cu_seqlens_q, and
 // a null workspace (the block map lives there: every ragged call needs one).  page_size > 0: a paged call, as in check_decode.
 int check_ragged(const void* q, const void* k_cache, const void* v_cache, const float* out, const int* cu, const void* workspace, int B,
-                 int H, int Hkv, int T, int Ncap, int d, int layout, float softmax_scale, int dtype, int page_size = 0, int window = 0) {
+                 int H, int Hkv, int T, int Ncap, int d, int layout, float softmax_scale, int dtype, int page_size = 0, int window = 0,
+                 int sink = 0) {
   g_err[0] = 0;
   if (B <= 0 || H <= 0 || T <= 0 || Ncap <= 0 || d <= 0) return set_err(FA_ERR_BAD_ARG, "B, H, T, Ncap and d must be positive");
   if (Hkv <= 0) return set_err(FA_ERR_BAD_ARG, "Hkv must be positive");
@@ -476,7 +500,7 @@ int check_ragged(const void* q, const void* k_cache, const void* v_cache, const 
   }
   // (a sequence may own every packed row: its q resource and the (head, query) offsets inside it are 32-bit byte counts)
   if ((long)T * H * d * esz >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "q (T * H * d elements) must stay under 2 GiB");
-  const int ns = rag_splits(B, H, Hkv, T, span_keys(window, Ncap, T, fa::EXT_BLOCK));
+  const int ns = rag_splits(B, H, Hkv, T, span_keys(window, Ncap, T, fa::EXT_BLOCK, sink));
   if (split_grid((long)Hkv * ns, rag_blocks(B, H, Hkv, T)) >= (1L << 32) || (long)Hkv * ns >= (1L << 31) || (long)H * T >= (1L << 32))
     return set_err(FA_ERR_BAD_ARG, "too many workgroups for one launch: Hkv * splits * row blocks and H * T must fit an unsigned int");
   if (!workspace)
@@ -503,12 +527,20 @@ int check_ragged_append(const void* k_new, const void* v_new, const void* k_cach
   return FA_OK;
 }
 
-template <typename T, int D> int launch_ragged(fa::RaggedArgs a, hipStream_t st) {
+template <typename T, int D> int launch_ragged(fa::RaggedArgs a, int sink, hipStream_t st) {
   hipLaunchKernelGGL(fa::ragged_schedule_kernel, dim3(1), dim3(256), 0, st, a.cu, const_cast<int*>(a.map), a.nseq, a.ntok, a.G, a.nqb);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return set_err(FA_ERR_HIP, "ragged_schedule_kernel launch", e);
   const dim3 grid((unsigned)split_grid(a.items, a.nqb));
-  if (a.window && a.table)
+  if (sink) {   // (the sink builds: their own kernels and argument; a.window >= 1)
+    fa::RaggedSinkArgs sa;
+    static_cast<fa::RaggedArgs&>(sa) = a;
+    sa.sink = sink;
+    if (a.table)
+      hipLaunchKernelGGL((fa::extend_split_sink_kernel<T, D, true, true>), grid, dim3(256), 0, st, sa);
+    else
+      hipLaunchKernelGGL((fa::extend_split_sink_kernel<T, D, false, true>), grid, dim3(256), 0, st, sa);
+  } else if (a.window && a.table)
     hipLaunchKernelGGL((fa::extend_split_kernel<T, D, true, true, true>), grid, dim3(256), 0, st, a);
   else if (a.window)
     hipLaunchKernelGGL((fa::extend_split_kernel<T, D, false, true, true>), grid, dim3(256), 0, st, a);
@@ -526,19 +558,19 @@ template <typename T, int D> int launch_ragged(fa::RaggedArgs a, hipStream_t st)
   return FA_OK;
 }
 
-template <typename T> int launch_ragged_d(const fa::RaggedArgs& a, int d, hipStream_t st) {
+template <typename T> int launch_ragged_d(const fa::RaggedArgs& a, int d, int sink, hipStream_t st) {
   switch (d) {
-    case 32: return launch_ragged<T, 32>(a, st);
-    case 64: return launch_ragged<T, 64>(a, st);
-    default: return launch_ragged<T, 128>(a, st);
+    case 32: return launch_ragged<T, 32>(a, sink, st);
+    case 64: return launch_ragged<T, 64>(a, sink, st);
+    default: return launch_ragged<T, 128>(a, sink, st);
   }
 }
 
 // The schedule, split (and combine) launches of a checked ragged call.
 int run_ragged(const void* q, const void* k_cache, const void* v_cache, float* out, float* lse, const int* cu, const int* cache_seqlens,
                void* workspace, int B, int H, int Hkv, int T, int Ncap, int d, int layout, float softmax_scale, int causal, int dtype,
-               void* stream, const Paging* pg, int window = 0) {
-  const int span = span_keys(window, Ncap, T, fa::EXT_BLOCK);   // (no window: Ncap; a sequence may own all T rows)
+               void* stream, const Paging* pg, int window = 0, int sink = 0) {
+  const int span = span_keys(window, Ncap, T, fa::EXT_BLOCK, sink);   // (no window: Ncap; a sequence may own all T rows)
   const int ns = rag_splits(B, H, Hkv, T, span);
   fa::RaggedArgs a;
   a.q = q;
@@ -561,7 +593,8 @@ int run_ragged(const void* q, const void* k_cache, const void* v_cache, float* o
   a.Ncap = Ncap;
   a.nsplit = ns;
   a.chunk = rag_chunk_keys(B, H, Hkv, T, span);
-  a.window = win_of(window, Ncap);
+  a.window = win_of(window, Ncap, sink);
+  sink = sink_of(window, sink, Ncap);
   a.nqb = (int)rag_blocks(B, H, Hkv, T);
   a.items = Hkv * ns;
   const bool bnhd = layout == FA_LAYOUT_BNHD;
@@ -586,17 +619,17 @@ int run_ragged(const void* q, const void* k_cache, const void* v_cache, float* o
     a.kv_hstride = bnhd ? d : (long)pg->page_size * d;
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
-  return dtype == FA_DTYPE_BF16 ? launch_ragged_d<fa::bf16_t>(a, d, st) : launch_ragged_d<float>(a, d, st);
+  return dtype == FA_DTYPE_BF16 ? launch_ragged_d<fa::bf16_t>(a, d, sink, st) : launch_ragged_d<float>(a, d, sink, st);
 }
 
 // One ragged call: the attention (attend), the append (append), or the append then the attention; pg: the paged form.
 int ragged_call(bool attend, bool append, const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out,
                 float* lse, const int* cu, const int* cache_seqlens, const Paging* pg, void* workspace, int B, int H, int Hkv, int T, int Ncap,
-                int d_new, int d, int layout, float softmax_scale, int causal, int dtype, void* stream, int window = 0) {
+                int d_new, int d, int layout, float softmax_scale, int causal, int dtype, void* stream, int window = 0, int sink = 0) {
   int rc = pg ? check_pages(*pg, &Ncap) : FA_OK;
   if (rc == FA_OK && attend)
     rc = check_ragged(q, k_cache, v_cache, out, cu, workspace, B, H, Hkv, T, Ncap, d, layout, softmax_scale, dtype, pg ? pg->page_size : 0,
-                      window);
+                      window, sink);
   if (rc == FA_OK && append) rc = check_ragged_append(k_new, v_new, k_cache, v_cache, cu, B, Hkv, T, Ncap, d_new, d, layout, dtype);
   if (rc == FA_OK && append && pg) rc = check_page_bytes(pg->page_size, Hkv, d, dtype);
   if (rc != FA_OK) return rc;
@@ -605,7 +638,7 @@ int ragged_call(bool attend, bool append, const void* q, const void* k_new, cons
     if (rc != FA_OK || !attend) return rc;
   }
   return run_ragged(q, k_cache, v_cache, out, lse, cu, cache_seqlens, workspace, B, H, Hkv, T, Ncap, d, layout, softmax_scale, causal, dtype,
-                    stream, pg, window);
+                    stream, pg, window, sink);
 }
 
 }  // namespace
@@ -698,11 +731,11 @@ namespace {
 // (pg null), windowed or not.
 int attend(bool extend, bool fused, const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
            const int* cache_seqlens, const Paging* pg, void* workspace, int B, int H, int Hkv, int Nq, int Ncap, int d_new, int d, int layout,
-           float softmax_scale, int causal, int dtype, void* stream, int window = 0, const Fp8* f8 = nullptr) {
+           float softmax_scale, int causal, int dtype, void* stream, int window = 0, const Fp8* f8 = nullptr, int sink = 0) {
   int rc = pg ? check_pages(*pg, &Ncap) : FA_OK;
   if (rc == FA_OK)
     rc = check_decode(q, k_cache, v_cache, out, workspace, B, H, Hkv, Nq, Ncap, d, layout, softmax_scale, dtype, extend, pg ? pg->page_size : 0,
-                      window, f8 != nullptr);
+                      window, f8 != nullptr, sink);
   if (rc == FA_OK && fused) rc = check_append(k_new, v_new, k_cache, v_cache, B, Hkv, Nq, Ncap, d_new, d, layout, dtype, extend);
   if (rc != FA_OK) return rc;
   if (fused) {
@@ -710,7 +743,7 @@ int attend(bool extend, bool fused, const void* q, const void* k_new, const void
     if (rc != FA_OK) return rc;
   }
   return run_decode(q, k_cache, v_cache, out, lse, cache_seqlens, workspace, B, H, Hkv, Nq, Ncap, d, layout, softmax_scale, causal, dtype,
-                    stream, extend, pg, window, f8);
+                    stream, extend, pg, window, f8, sink);
 }
 
 // The check an fp8 call makes first: the queries and the new tokens are bf16.
@@ -722,9 +755,10 @@ int check_fp8(int dtype) {
   return FA_OK;
 }
 
-// The checks a windowed call makes first.
-int check_window(int window, int causal) {
+// The checks a windowed call makes first (sink: 0 in the calls that have none).
+int check_window(int window, int causal, int sink = 0) {
   g_err[0] = 0;
+  if (sink < 0) return set_err(FA_ERR_BAD_ARG, "sink must not be negative (0: no sink tokens)");
   if (window < 0) return set_err(FA_ERR_BAD_ARG, "window must not be negative (0: no window)");
   if (window > 0 && !causal)
     return set_err(FA_ERR_BAD_ARG, "a sliding window needs the causal mask: window > 0 with causal = 0 (the window ends at the query's position)");
@@ -917,6 +951,74 @@ int fa_mi355x_fwd_ragged_window(const void* q, const void* k_new, const void* v_
   const Paging pg = {block_table, num_pages, page_size, max_pages};
   return ragged_call(true, k_new || v_new, q, k_new, v_new, k_cache, v_cache, out, lse, cu_seqlens_q, cache_seqlens,
                      block_table ? &pg : nullptr, workspace, B, H, Hkv, T, Ncap, d_new, d, layout, softmax_scale, causal, dtype, stream, window);
+}
+
+// The sink entry points (include/flash_attn_mi355x_decode_sink.h): the windowed ones with `sink` first positions kept beside the window.
+int fa_mi355x_decode_sink_splits(int B, int H, int Hkv, int Nq, int Ncap, int d, int dtype, int window, int sink) {
+  (void)dtype;
+  if (!sizes_ok(B, H, Hkv, Nq, Ncap, d) || window < 0 || sink < 0) return 0;
+  return splits(B, H, Hkv, Nq, span_keys(window, Ncap, Nq, 32, sink));
+}
+
+size_t fa_mi355x_decode_sink_workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int d, int window, int sink) {
+  if (!sizes_ok(B, H, Hkv, Nq, Ncap, d) || window < 0 || sink < 0) return 0;
+  return workspace_bytes(B, H, Hkv, Nq, span_keys(window, Ncap, Nq, 32, sink), d);
+}
+
+int fa_mi355x_extend_sink_splits(int B, int H, int Hkv, int Nq, int Ncap, int d, int dtype, int window, int sink) {
+  (void)dtype;
+  if (!sizes_ok(B, H, Hkv, Nq, Ncap, d) || window < 0 || sink < 0) return 0;
+  return ext_splits(B, H, Hkv, Nq, span_keys(window, Ncap, Nq, fa::EXT_BLOCK, sink));
+}
+
+size_t fa_mi355x_extend_sink_workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int d, int window, int sink) {
+  if (!sizes_ok(B, H, Hkv, Nq, Ncap, d) || window < 0 || sink < 0) return 0;
+  return ext_workspace_bytes(B, H, Hkv, Nq, span_keys(window, Ncap, Nq, fa::EXT_BLOCK, sink), d);
+}
+
+int fa_mi355x_ragged_sink_splits(int B, int H, int Hkv, int T, int Ncap, int d, int dtype, int window, int sink) {
+  (void)dtype;
+  if (!sizes_ok(B, H, Hkv, T, Ncap, d) || window < 0 || sink < 0) return 0;
+  return rag_splits(B, H, Hkv, T, span_keys(window, Ncap, T, fa::EXT_BLOCK, sink));
+}
+
+size_t fa_mi355x_ragged_sink_workspace_bytes(int B, int H, int Hkv, int T, int Ncap, int d, int window, int sink) {
+  if (!sizes_ok(B, H, Hkv, T, Ncap, d) || window < 0 || sink < 0) return 0;
+  return rag_workspace_bytes(B, H, Hkv, T, span_keys(window, Ncap, T, fa::EXT_BLOCK, sink), d);
+}
+
+int fa_mi355x_fwd_decode_sink(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
+                              const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv, int Nq, int Ncap,
+                              int num_pages, int page_size, int max_pages, int d_new, int d, int layout, float softmax_scale, int causal,
+                              int window, int sink, int dtype, void* stream) {
+  const int rc = check_window(window, causal, sink);
+  if (rc != FA_OK) return rc;
+  const Paging pg = {block_table, num_pages, page_size, max_pages};
+  return attend(false, k_new || v_new, q, k_new, v_new, k_cache, v_cache, out, lse, cache_seqlens, block_table ? &pg : nullptr, workspace, B, H,
+                Hkv, Nq, Ncap, d_new, d, layout, softmax_scale, causal, dtype, stream, window, nullptr, sink);
+}
+
+int fa_mi355x_fwd_extend_sink(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
+                              const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv, int Nq, int Ncap,
+                              int num_pages, int page_size, int max_pages, int d_new, int d, int layout, float softmax_scale, int causal,
+                              int window, int sink, int dtype, void* stream) {
+  const int rc = check_window(window, causal, sink);
+  if (rc != FA_OK) return rc;
+  const Paging pg = {block_table, num_pages, page_size, max_pages};
+  return attend(true, k_new || v_new, q, k_new, v_new, k_cache, v_cache, out, lse, cache_seqlens, block_table ? &pg : nullptr, workspace, B, H,
+                Hkv, Nq, Ncap, d_new, d, layout, softmax_scale, causal, dtype, stream, window, nullptr, sink);
+}
+
+int fa_mi355x_fwd_ragged_sink(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
+                              const int* cu_seqlens_q, const int* cache_seqlens, const int* block_table, void* workspace, int B, int H,
+                              int Hkv, int T, int Ncap, int num_pages, int page_size, int max_pages, int d_new, int d, int layout,
+                              float softmax_scale, int causal, int window, int sink, int dtype, void* stream) {
+  const int rc = check_window(window, causal, sink);
+  if (rc != FA_OK) return rc;
+  const Paging pg = {block_table, num_pages, page_size, max_pages};
+  return ragged_call(true, k_new || v_new, q, k_new, v_new, k_cache, v_cache, out, lse, cu_seqlens_q, cache_seqlens,
+                     block_table ? &pg : nullptr, workspace, B, H, Hkv, T, Ncap, d_new, d, layout, softmax_scale, causal, dtype, stream, window,
+                     sink);
 }
 
 // The fp8 entry points (include/flash_attn_mi355x_decode_fp8.h): caches of e4m3 bytes with per-kv-head scales.  k_new / v_new null:

@@ -608,8 +608,10 @@ def _decode_dims(q, k_cache, layout, max_pages=None):
     return B, H, Hkv, Nq, Ncap, dq, dp
 
 
-def _decode_workspace_bytes(B, H, Hkv, Nq, Ncap, dp, window=None):
+def _decode_workspace_bytes(B, H, Hkv, Nq, Ncap, dp, window=None, sink=None):
     lib = _lib.decode()
+    if sink is not None:
+        return lib.fa_mi355x_decode_sink_workspace_bytes(B, H, Hkv, Nq, Ncap, dp, window, sink)
     if window is not None:
         return lib.fa_mi355x_decode_window_workspace_bytes(B, H, Hkv, Nq, Ncap, dp, window)
     if Hkv == H:
@@ -634,28 +636,51 @@ def _check_window(window, causal=True):
     return window
 
 
-def decode_workspace(q, k_cache, layout="bnhd", block_table=None, max_pages=None, window=None):
+def _check_sink(sink, window):
+    """``sink`` as the library takes it beside a checked ``window``: None and 0 are None (today's entry points), otherwise an
+    int >= 1, which needs a window."""
+    if sink is None:
+        return None
+    try:
+        sink = None if isinstance(sink, bool) else operator.index(sink)
+    except TypeError:
+        sink = None
+    if sink is None:
+        raise ValueError("sink must be None or an int: the number of first positions every token keeps beside its window")
+    if sink < 0:
+        raise ValueError("sink must not be negative (None or 0: no sink tokens)")
+    if sink > 0 and window is None:
+        raise ValueError("sink tokens stand beside a sliding window: sink= needs window=")
+    return sink or None
+
+
+def decode_workspace(q, k_cache, layout="bnhd", block_table=None, max_pages=None, window=None, sink=None):
     """Scratch for flash_attn_decode with these tensors (fa_mi355x_decode_workspace_bytes; one partial O, m, l per query row and key
     chunk), or None when the call runs as one split and needs none.  A pure function of the shapes: allocate once, reuse every step.
     A paged call (``k_cache`` the pool): give the block table or its ``max_pages``; the size is the contiguous call's for
     Ncap = max_pages * page_size.  ``window``: for flash_attn_decode(..., window=) (fa_mi355x_decode_window_workspace_bytes: the
-    splits follow the window span, not the cache).  An fp8 cache is sized as the bf16 cache of its shape is (the same splits)."""
+    splits follow the window span, not the cache).  ``sink``: for flash_attn_decode(..., window=, sink=)
+    (fa_mi355x_decode_sink_workspace_bytes).  An fp8 cache is sized as the bf16 cache of its shape is (the same splits)."""
     B, H, Hkv, Nq, Ncap, _, dp = _decode_dims(q, k_cache, layout, _max_pages(block_table, max_pages))
-    nbytes = _decode_workspace_bytes(B, H, Hkv, Nq, Ncap, dp, _check_window(window))
+    window = _check_window(window)
+    nbytes = _decode_workspace_bytes(B, H, Hkv, Nq, Ncap, dp, window, _check_sink(sink, window))
     return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=q.device) if nbytes else None
 
 
-def _extend_workspace_bytes(B, H, Hkv, Nq, Ncap, dp, window=None):
+def _extend_workspace_bytes(B, H, Hkv, Nq, Ncap, dp, window=None, sink=None):
+    if sink is not None:
+        return _lib.decode().fa_mi355x_extend_sink_workspace_bytes(B, H, Hkv, Nq, Ncap, dp, window, sink)
     if window is not None:
         return _lib.decode().fa_mi355x_extend_window_workspace_bytes(B, H, Hkv, Nq, Ncap, dp, window)
     return _lib.decode().fa_mi355x_extend_workspace_bytes(B, H, Hkv, Nq, Ncap, dp)
 
 
-def extend_workspace(q, k_cache, layout="bnhd", block_table=None, max_pages=None, window=None):
+def extend_workspace(q, k_cache, layout="bnhd", block_table=None, max_pages=None, window=None, sink=None):
     """decode_workspace for flash_attn_extend (fa_mi355x_extend_workspace_bytes: the extend call has a split policy of its own;
-    ``window``: fa_mi355x_extend_window_workspace_bytes)."""
+    ``window``: fa_mi355x_extend_window_workspace_bytes; ``sink``: fa_mi355x_extend_sink_workspace_bytes)."""
     B, H, Hkv, Nq, Ncap, _, dp = _decode_dims(q, k_cache, layout, _max_pages(block_table, max_pages))
-    nbytes = _extend_workspace_bytes(B, H, Hkv, Nq, Ncap, dp, _check_window(window))
+    window = _check_window(window)
+    nbytes = _extend_workspace_bytes(B, H, Hkv, Nq, Ncap, dp, window, _check_sink(sink, window))
     return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=q.device) if nbytes else None
 
 
@@ -779,11 +804,12 @@ def extend_append(k_new, v_new, k_cache, v_cache, cache_seqlens=None, layout="bn
 
 
 def _cache_attention(who, extend, q, k_cache, v_cache, cache_seqlens, causal, softmax_scale, layout, out, lse, workspace, k_new, v_new,
-                     block_table=None, window=None, k_scale=None, v_scale=None):
+                     block_table=None, window=None, k_scale=None, v_scale=None, sink=None):
     """flash_attn_decode / flash_attn_extend (``extend``): the checks, the head-dim padding, then the library's entry point (its
-    _paged form when there is a block table; with a ``window``, the family's one _window entry point; on an fp8 cache, the family's
-    one _fp8 entry point)."""
+    _paged form when there is a block table; with a ``window``, the family's one _window entry point, with ``sink`` tokens beside it
+    the family's one _sink entry point; on an fp8 cache, the family's one _fp8 entry point)."""
     window = _check_window(window, causal)
+    sink = _check_sink(sink, window)
     if (k_new is None) != (v_new is None):
         raise ValueError("k_new and v_new go together: give both (fused append) or neither")
     if layout not in _DECODE_LAYOUTS:
@@ -797,6 +823,8 @@ def _cache_attention(who, extend, q, k_cache, v_cache, cache_seqlens, causal, so
             raise TypeError("an fp8 cache takes bfloat16 queries")
         if window is not None:
             raise ValueError("a sliding window on an fp8 cache is not built: window= with torch.float8_e4m3fn caches")
+        if sink is not None:
+            raise ValueError("sink tokens on an fp8 cache are not built: sink= with torch.float8_e4m3fn caches")
     elif k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
         raise TypeError("q, k_cache and v_cache must share one dtype")
     if k_cache.shape != v_cache.shape:
@@ -836,8 +864,8 @@ def _cache_attention(who, extend, q, k_cache, v_cache, cache_seqlens, causal, so
     lib = _lib.decode()
     new_ws, ws_bytes = (extend_workspace, _extend_workspace_bytes) if extend else (decode_workspace, _decode_workspace_bytes)
     if workspace is None:
-        workspace = new_ws(qp, k_cache, layout, **pages, window=window)
-    elif workspace.numel() * workspace.element_size() < ws_bytes(B, H, Hkv, Nq, Ncap, dp, window):
+        workspace = new_ws(qp, k_cache, layout, **pages, window=window, sink=sink)
+    elif workspace.numel() * workspace.element_size() < ws_bytes(B, H, Hkv, Nq, Ncap, dp, window, sink):
         raise ValueError(f"workspace too small: size it with {new_ws.__name__}()")
     tail = (_DECODE_LAYOUTS[layout], float(softmax_scale), int(bool(causal)), dtype, _stream_ptr())
     if fp8:   # (one entry point per family, as the windowed calls: null k_new / v_new attend only, a null table is a slab cache)
@@ -847,11 +875,14 @@ def _cache_attention(who, extend, q, k_cache, v_cache, cache_seqlens, causal, so
                      _ptr(cache_seqlens), _ptr(block_table), _ptr(workspace), B, H, Hkv, Nq, 0 if paged else Ncap, *geometry,
                      d_new if k_new is not None else dp, dp, *tail)
     elif window is not None:   # (one entry point per family: null k_new / v_new attend only, a null table is a slab cache)
-        fwd = lib.fa_mi355x_fwd_extend_window if extend else lib.fa_mi355x_fwd_decode_window
+        if sink is not None:   # (the same arguments with sink behind window)
+            fwd, win = (lib.fa_mi355x_fwd_extend_sink if extend else lib.fa_mi355x_fwd_decode_sink), (window, sink)
+        else:
+            fwd, win = (lib.fa_mi355x_fwd_extend_window if extend else lib.fa_mi355x_fwd_decode_window), (window,)
         geometry = (num_pages, page_size, pages["max_pages"]) if paged else (0, 0, 0)
         status = fwd(_ptr(qp), _ptr(k_new), _ptr(v_new), _ptr(k_cache), _ptr(v_cache), _ptr(outp), _ptr(lse), _ptr(cache_seqlens),
                      _ptr(block_table), _ptr(workspace), B, H, Hkv, Nq, 0 if paged else Ncap, *geometry,
-                     d_new if k_new is not None else dp, dp, _DECODE_LAYOUTS[layout], float(softmax_scale), int(bool(causal)), window,
+                     d_new if k_new is not None else dp, dp, _DECODE_LAYOUTS[layout], float(softmax_scale), int(bool(causal)), *win,
                      dtype, _stream_ptr())
     elif paged:   # (one grouped form of each: the contiguous calls' arguments with the table after the lengths and the pool's geometry for Ncap)
         name = "fa_mi355x_fwd_" + ("extend" if extend else "decode") + ("_append" if k_new is not None else "") + "_paged"
@@ -880,7 +911,7 @@ def _cache_attention(who, extend, q, k_cache, v_cache, cache_seqlens, causal, so
 
 
 def flash_attn_decode(q, k_cache, v_cache, cache_seqlens=None, causal=True, softmax_scale=None, layout="bnhd", out=None, lse=None,
-                      workspace=None, k_new=None, v_new=None, block_table=None, window=None, k_scale=None, v_scale=None):
+                      workspace=None, k_new=None, v_new=None, block_table=None, window=None, k_scale=None, v_scale=None, sink=None):
     """Attention of Nq <= 128 new queries against a KV cache (fa_mi355x_fwd_decode / _gqa, include/flash_attn_mi355x_decode.h).
     ``layout`` "bnhd": q (B, Nq, H, d), caches (B, Ncap, Hkv, dp); "bhnd": q (B, H, Nq, d), caches (B, Hkv, Ncap, dp).  Hkv is the
     cache's own head count and must divide H: Hkv < H is a grouped-query (Hkv = 1: multi-query) cache, query head h reads cache head
@@ -901,20 +932,25 @@ def flash_attn_decode(q, k_cache, v_cache, cache_seqlens=None, causal=True, soft
     window, so the work and the bytes read follow W and not the cache's length, and cache rows (and the pages of a paged cache) wholly
     below the window are never read.  None takes the unwindowed entry points above; 0, and any W >= Ncap, is the unwindowed call
     through the windowed entry point (the same launches and bits).  Size a workspace with decode_workspace(..., window=).
+    ``sink`` (None, or an int >= 0; needs ``window``): ATTENTION-SINK tokens (fa_mi355x_fwd_decode_sink,
+    include/flash_attn_mi355x_decode_sink.h).  The first S positions of every sequence stay admitted beside the window: the query at
+    p admits j <= p with j > p - W or j < S, a key in both counted once.  None and 0 take the paths above exactly; S >= Ncap, and
+    window 0 or >= Ncap, is the unwindowed call.  A block reads ceil(S / 128) sink tiles beside its window's; the pages of a paged
+    cache that hold the first S rows must stay.  Size a workspace with decode_workspace(..., window=, sink=).
     FP8 caches (k_cache and v_cache of dtype torch.float8_e4m3fn, slab or paged; fa_mi355x_fwd_decode_fp8,
     include/flash_attn_mi355x_decode_fp8.h): the caches hold e4m3 bytes and the value of an element of cache head h is
     scale[h] * e4m3, with ``k_scale`` / ``v_scale`` contiguous float32 (Hkv,) tensors on q's device (None: ones; read on the device).
     q, k_new and v_new are bfloat16; k_new / v_new are quantised as decode_append does.  Half the bytes per cached row; with
     power-of-two scales the result is bit for bit the bf16 call's on the cache cast to bfloat16 with softmax_scale * k_scale,
-    times v_scale.  The workspace is the bf16 call's (decode_workspace takes the fp8 cache).  No ``window`` on an fp8 cache, and
+    times v_scale.  The workspace is the bf16 call's (decode_workspace takes the fp8 cache).  No ``window`` or ``sink`` on an fp8 cache, and
     scales with any other cache are an error.
     Returns (out fp32 in q's shape, lse fp32 (B, H, Nq)): rows with no admissible key give out = 0, lse = -inf."""
     return _cache_attention("flash_attn_decode", False, q, k_cache, v_cache, cache_seqlens, causal, softmax_scale, layout, out, lse,
-                            workspace, k_new, v_new, block_table, window, k_scale, v_scale)
+                            workspace, k_new, v_new, block_table, window, k_scale, v_scale, sink)
 
 
 def flash_attn_extend(q, k_cache, v_cache, cache_seqlens=None, causal=True, softmax_scale=None, layout="bnhd", out=None, lse=None,
-                      workspace=None, k_new=None, v_new=None, block_table=None, window=None, k_scale=None, v_scale=None):
+                      workspace=None, k_new=None, v_new=None, block_table=None, window=None, k_scale=None, v_scale=None, sink=None):
     """flash_attn_decode for ANY number Nq >= 1 of new queries (fa_mi355x_fwd_extend / fa_mi355x_fwd_extend_append): a long input that
     follows a cached prefix, or one piece of a chunked prefill (the same call, from an empty cache on).  Every argument, check, the
     head-dim padding (the default scale keeps the caller's 1/sqrt(d)) and the return value are flash_attn_decode's; ``workspace`` is
@@ -924,9 +960,10 @@ def flash_attn_extend(q, k_cache, v_cache, cache_seqlens=None, causal=True, soft
     rounding, not bit for bit.  ``block_table``: a paged cache, as in flash_attn_decode (fa_mi355x_fwd_extend_paged).  ``window``:
     sliding-window attention, as in flash_attn_decode (fa_mi355x_fwd_extend_window): every 128-row block walks its own W + 128
     positions' worth of keys wherever it sits in a long input; size a workspace with extend_workspace(..., window=).  ``k_scale`` /
-    ``v_scale``: an fp8 cache, as in flash_attn_decode (fa_mi355x_fwd_extend_fp8)."""
+    ``v_scale``: an fp8 cache, as in flash_attn_decode (fa_mi355x_fwd_extend_fp8).  ``sink``: attention-sink tokens beside the
+    window, as in flash_attn_decode (fa_mi355x_fwd_extend_sink; extend_workspace(..., window=, sink=))."""
     return _cache_attention("flash_attn_extend", True, q, k_cache, v_cache, cache_seqlens, causal, softmax_scale, layout, out, lse,
-                            workspace, k_new, v_new, block_table, window, k_scale, v_scale)
+                            workspace, k_new, v_new, block_table, window, k_scale, v_scale, sink)
 
 
 # ---- ragged batches: every sequence brings its own number of new tokens (include/flash_attn_mi355x_decode_ragged.h) ----
@@ -960,22 +997,26 @@ def _ragged_dims(q, k_cache, cu_seqlens_q, layout, max_pages=None):
     return B, H, Hkv, T, Ncap, dq, dp
 
 
-def _ragged_workspace_bytes(B, H, Hkv, T, Ncap, dp, window=None):
+def _ragged_workspace_bytes(B, H, Hkv, T, Ncap, dp, window=None, sink=None):
+    if sink is not None:
+        return _lib.decode().fa_mi355x_ragged_sink_workspace_bytes(B, H, Hkv, T, Ncap, dp, window, sink)
     if window is not None:
         return _lib.decode().fa_mi355x_ragged_window_workspace_bytes(B, H, Hkv, T, Ncap, dp, window)
     return _lib.decode().fa_mi355x_ragged_workspace_bytes(B, H, Hkv, T, Ncap, dp)
 
 
-def ragged_workspace(q, k_cache, cu_seqlens_q, layout="bnhd", block_table=None, max_pages=None, window=None):
+def ragged_workspace(q, k_cache, cu_seqlens_q, layout="bnhd", block_table=None, max_pages=None, window=None, sink=None):
     """Scratch for flash_attn_ragged with these tensors (fa_mi355x_ragged_workspace_bytes): the block map and one partial O, m, l per
     packed row and key chunk.  Never None: the map lives there, so every ragged call needs one.  A pure function of the SHAPES
     (cu_seqlens_q's contents are not read): allocate once, reuse every step.  A paged call (``k_cache`` the pool): give the block
     table or its ``max_pages``; the size is the contiguous call's for Ncap = max_pages * page_size.  ``window``: for
-    flash_attn_ragged(..., window=) (fa_mi355x_ragged_window_workspace_bytes)."""
+    flash_attn_ragged(..., window=) (fa_mi355x_ragged_window_workspace_bytes); ``sink``: for flash_attn_ragged(..., window=, sink=)
+    (fa_mi355x_ragged_sink_workspace_bytes)."""
     if layout not in _DECODE_LAYOUTS:
         raise ValueError(f"layout must be one of {sorted(_DECODE_LAYOUTS)}")
     B, H, Hkv, T, Ncap, _, dp = _ragged_dims(q, k_cache, cu_seqlens_q, layout, _max_pages(block_table, max_pages))
-    nbytes = _ragged_workspace_bytes(B, H, Hkv, T, Ncap, dp, _check_window(window))
+    window = _check_window(window)
+    nbytes = _ragged_workspace_bytes(B, H, Hkv, T, Ncap, dp, window, _check_sink(sink, window))
     return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=q.device)
 
 
@@ -1049,7 +1090,7 @@ def ragged_append(k_new, v_new, k_cache, v_cache, cu_seqlens_q, cache_seqlens=No
 
 
 def flash_attn_ragged(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens=None, causal=True, softmax_scale=None, layout="bnhd", out=None,
-                      lse=None, workspace=None, k_new=None, v_new=None, block_table=None, max_pages=None, window=None):
+                      lse=None, workspace=None, k_new=None, v_new=None, block_table=None, max_pages=None, window=None, sink=None):
     """One attention call over a RAGGED batch (fa_mi355x_fwd_ragged / _fwd_ragged_append and their _paged forms): every sequence
     brings its own number of new tokens -- some decode one, one is part-way through a chunked prefill, some have none.  ``q`` is
     PACKED, (T, H, d): sequence b owns rows cu_seqlens_q[b] .. cu_seqlens_q[b + 1] - 1 (``cu_seqlens_q`` contiguous int32 (B + 1,) on
@@ -1064,10 +1105,12 @@ def flash_attn_ragged(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens=None, cau
     split).  A step in which EVERY sequence decodes one token is faster through flash_attn_decode (measured, profiles/ragged_bench.txt:
     1.10x in bf16, 2.4x in fp32 at B = 32, length 4096).  ``window``: sliding-window attention, as in flash_attn_decode
     (fa_mi355x_fwd_ragged_window; token i of sequence b sits at len_b - nq_b + i and admits the W keys up to its own position); size
-    a workspace with ragged_workspace(..., window=).
+    a workspace with ragged_workspace(..., window=).  ``sink``: attention-sink tokens beside the window, as in flash_attn_decode
+    (fa_mi355x_fwd_ragged_sink: the first S positions of each sequence; ragged_workspace(..., window=, sink=)).
     Returns (out fp32 (T, H, d), lse fp32 (H, T)): rows with no admissible key give out = 0, lse = -inf; rows of the unused tail
     keep what they held."""
     window = _check_window(window, causal)
+    sink = _check_sink(sink, window)
     if (k_new is None) != (v_new is None):
         raise ValueError("k_new and v_new go together: give both (fused append) or neither")
     pages, Hkv, dp, _ = _cache_geometry(k_cache, v_cache, layout, block_table)
@@ -1095,7 +1138,7 @@ def flash_attn_ragged(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens=None, cau
     if lse is not None and (tuple(lse.shape) != (H, T) or lse.dtype != torch.float32 or not lse.is_contiguous()):
         raise ValueError("lse must be a contiguous float32 tensor of shape (H, T)")
     lib = _lib.decode()
-    if workspace is not None and workspace.numel() * workspace.element_size() < _ragged_workspace_bytes(B, H, Hkv, T, Ncap, dp, window):
+    if workspace is not None and workspace.numel() * workspace.element_size() < _ragged_workspace_bytes(B, H, Hkv, T, Ncap, dp, window, sink):
         raise ValueError("workspace too small: size it with ragged_workspace()")
     for t in (q, k_cache, v_cache):
         _require_gpu(t, "flash_attn_ragged")
@@ -1111,13 +1154,14 @@ def flash_attn_ragged(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens=None, cau
     if lse is None:
         lse = torch.empty((H, T), dtype=torch.float32, device=q.device)
     if workspace is None:
-        workspace = ragged_workspace(qp, k_cache, cu_seqlens_q, layout, max_pages=mp, window=window)
+        workspace = ragged_workspace(qp, k_cache, cu_seqlens_q, layout, max_pages=mp, window=window, sink=sink)
     if window is not None:   # (the family's one windowed entry point: null k_new / v_new attend only, a null table is a slab cache)
         geometry = (0, *pages, mp) if pages else (Ncap, 0, 0, 0)
-        status = lib.fa_mi355x_fwd_ragged_window(
+        fwd, win = (lib.fa_mi355x_fwd_ragged_window, (window,)) if sink is None else (lib.fa_mi355x_fwd_ragged_sink, (window, sink))
+        status = fwd(
             _ptr(qp), _ptr(k_new), _ptr(v_new), _ptr(k_cache), _ptr(v_cache), _ptr(outp), _ptr(lse), _ptr(cu_seqlens_q), _ptr(cache_seqlens),
             _ptr(block_table), _ptr(workspace), B, H, Hkv, T, *geometry, d_new if k_new is not None else dp, dp, _DECODE_LAYOUTS[layout],
-            float(softmax_scale), int(bool(causal)), window, dtype, _stream_ptr())
+            float(softmax_scale), int(bool(causal)), *win, dtype, _stream_ptr())
         _lib.decode_check(status)
         return (_unpad(outp, d, out) if d < dp else outp), lse
     new = (_ptr(k_new), _ptr(v_new)) if k_new is not None else ()

@@ -82,7 +82,8 @@ def attention_stack(x, layers, n_head: int, causal: bool = True, fused_layout: b
 # extend kernels (attention_stack_extend, attention_stack_prefill_chunked).
 # A cache built with window=W makes every one of these calls a sliding-window one (each token sees the last W positions): the step,
 # fused step, extend, ragged and chunked-prefill functions and GraphedStep pass cache.window to device_ops, and a PagedKVCache gives
-# the pages behind the window back through release_behind_window.
+# the pages behind the window back through release_behind_window.  With sink=S beside the window every token also keeps the first S
+# positions (attention sinks): windowing() carries both, and the pages that hold those rows are never released.
 # A cache built with kv_dtype=torch.float8_e4m3fn holds e4m3 bytes with one scale per (layer, kv head): the fused step, extend and
 # chunked-prefill functions and GraphedStep pass the layer's scales (cache.quant(li)) to the same device_ops calls, which quantise on
 # the append; a prompt fills the cache through extend_append while its own attention stays the square forward on the unquantised k, v.
@@ -94,6 +95,14 @@ def _check_cache_window(window):
     if window is not None and (isinstance(window, bool) or not isinstance(window, int) or window < 1):
         raise ValueError("window must be None or a positive int: the positions a token sees, its own included")
     return window
+
+
+def _check_cache_sink(sink, window):
+    if sink is not None and (isinstance(sink, bool) or not isinstance(sink, int) or sink < 0):
+        raise ValueError("sink must be None or an int >= 0: the first positions every token keeps beside its window")
+    if sink and window is None:
+        raise ValueError("sink tokens stand beside a sliding window: sink= needs window=")
+    return sink or None
 
 
 def _check_cache_quant(kv_dtype, kv_scale, dtype, window, n_layers, n_kv_head, device):
@@ -126,14 +135,19 @@ class KVCache:
     ``window`` (None, or an int >= 1): the stack's layers use SLIDING-WINDOW attention, every token sees the last ``window``
     positions, its own included (Mistral's ``sliding_window``); the stack functions pass it to every device_ops call on this cache.
     The cache still holds every row (no ring buffer): a PagedKVCache gives the memory back through release_behind_window.
+    ``sink`` (None, or an int >= 0; needs ``window``): ATTENTION-SINK tokens, the first ``sink`` positions of every sequence stay
+    visible to every later token beside its window (a mask on the cache's logical rows: positions are not re-assigned, and there
+    are no learned sink logits).
     ``kv_dtype`` (None: ``dtype``, or torch.float8_e4m3fn): an FP8 cache holds e4m3 bytes, half the memory and half the bytes a step
     reads, and ``kv_scale`` (None: ones, or a pair (k_scale, v_scale) of float32 (n_layers, n_kv_head) tensors) gives every layer's
     per-head scales: a cached element is scale * e4m3.  The stack must be bfloat16; the fused step, extend and chunked-prefill
-    functions and GraphedStep quantise on the append; attention_stack_step (torch indexing), attention_stack_ragged and a window
-    are not built for it."""
+    functions and GraphedStep quantise on the append; attention_stack_step (torch indexing), attention_stack_ragged, a window
+    and sink tokens are not built for it."""
 
-    def __init__(self, n_layers, B, capacity, n_head, head_dim, dtype, device, n_kv_head=None, window=None, kv_dtype=None, kv_scale=None):
+    def __init__(self, n_layers, B, capacity, n_head, head_dim, dtype, device, n_kv_head=None, window=None, kv_dtype=None, kv_scale=None,
+                 sink=None):
         self.window = _check_cache_window(window)
+        self.sink = _check_cache_sink(sink, self.window)
         self.head_dim, self.dp = head_dim, device_ops.padded_head_dim(head_dim)
         self.capacity, self.n_head = capacity, n_head
         self.n_kv_head = n_head if n_kv_head is None else n_kv_head
@@ -154,8 +168,11 @@ class KVCache:
         return {} if self.block_table is None else dict(block_table=self.block_table)
 
     def windowing(self):
-        """The keyword that makes a device_ops call a windowed one: none for a cache without a window (the unwindowed entry points)."""
-        return {} if self.window is None else dict(window=self.window)
+        """The keywords that make a device_ops call a windowed one: none for a cache without a window (the unwindowed entry points),
+        window= for a windowed one, and sink= beside it for one that keeps sink tokens."""
+        if self.window is None:
+            return {}
+        return dict(window=self.window) if self.sink is None else dict(window=self.window, sink=self.sink)
 
     @property
     def fp8(self):
@@ -172,19 +189,19 @@ class KVCache:
         """Make sure the sequences own memory for ``n_tokens`` rows: a slab cache owns its ``capacity`` rows from the start."""
 
     def workspace(self, q):
-        key = (self.window,) + tuple(q.shape)   # (a windowed call splits on its window span: a buffer of its own size)
+        key = (self.window, self.sink) + tuple(q.shape)   # (a windowed call splits on its window span: a buffer of its own size)
         if key not in self._workspaces:
             self._workspaces[key] = device_ops.decode_workspace(q, self.k[0], "bnhd", **self.paging(), **self.windowing())
         return self._workspaces[key]
 
     def extend_workspace(self, q):
-        key = ("extend", self.window) + tuple(q.shape)   # (the extend call has a split policy of its own: never the decode call's buffer)
+        key = ("extend", self.window, self.sink) + tuple(q.shape)   # (the extend call has a split policy of its own: never the decode call's buffer)
         if key not in self._workspaces:
             self._workspaces[key] = device_ops.extend_workspace(q, self.k[0], "bnhd", **self.paging(), **self.windowing())
         return self._workspaces[key]
 
     def ragged_workspace(self, q, cu_seqlens_q):
-        key = ("ragged", self.window) + tuple(q.shape)   # (the ragged call sizes its own: the block map lives there)
+        key = ("ragged", self.window, self.sink) + tuple(q.shape)   # (the ragged call sizes its own: the block map lives there)
         if key not in self._workspaces:
             self._workspaces[key] = device_ops.ragged_workspace(q, self.k[0], cu_seqlens_q, "bnhd", **self.paging(), **self.windowing())
         return self._workspaces[key]
@@ -203,11 +220,17 @@ class PagedKVCache(KVCache):
     ``block_table`` to the same device_ops calls; results are bit for bit those of a KVCache of capacity max_pages * page_size.
     ``window``: as in KVCache; release_behind_window then returns the pages that have fallen out of every future window to the pool,
     so a long-running sequence holds O(window) pages.  ``released[b]`` counts the leading table slots sequence b no longer owns
-    (``pages[b]`` are the pages of the slots behind them)."""
+    (``pages[b]`` are the pages of the slots behind them).
+    ``sink``: as in KVCache.  The ``sink_pages`` = ceil(sink / page_size) leading table slots hold the sink rows and are NEVER
+    released.  The invariant: sequence b owns the slots 0 .. sink_pages - 1 (as many of them as it has grown into) and the slots from
+    sink_pages + released[b] on; ``released[b]`` counts the released slots directly behind the sink slots, and ``pages[b]`` lists the
+    owned pages in slot order, the sink pages first.  The slots in between keep stale or zero entries, which the kernels never
+    read.  Without sinks sink_pages = 0 and this is the rule above."""
 
     def __init__(self, n_layers, B, capacity, n_head, head_dim, dtype, device, n_kv_head=None, page_size=128, n_pages=None, window=None,
-                 kv_dtype=None, kv_scale=None):
+                 kv_dtype=None, kv_scale=None, sink=None):
         self.window = _check_cache_window(window)
+        self.sink = _check_cache_sink(sink, self.window)
         self.head_dim, self.dp = head_dim, device_ops.padded_head_dim(head_dim)
         self.capacity, self.n_head = capacity, n_head
         self.n_kv_head = n_head if n_kv_head is None else n_kv_head
@@ -218,6 +241,7 @@ class PagedKVCache(KVCache):
         if capacity <= 0:
             raise ValueError("capacity must be positive")
         self.page_size, self.max_pages = page_size, -(-capacity // page_size)
+        self.sink_pages = -(-(self.sink or 0) // page_size)   # leading table slots that release_behind_window keeps
         self.n_pages = B * self.max_pages if n_pages is None else n_pages
         if self.n_pages <= 0:
             raise ValueError("n_pages must be positive")
@@ -231,7 +255,7 @@ class PagedKVCache(KVCache):
         self._workspaces = {}
         self.free = list(range(self.n_pages - 1, -1, -1))   # (handed out from the end: page 0 first)
         self.pages = [[] for _ in range(B)]                 # the pages of each sequence, in order
-        self.released = [0] * B                             # leading table slots given back by release_behind_window
+        self.released = [0] * B                             # table slots behind the sink slots given back by release_behind_window
 
     def reserve(self, n_tokens, rows=None):
         """Make sure the sequences ``rows`` (default all) own pages for ``n_tokens`` cache rows each.  New pages come from the free list
@@ -247,12 +271,13 @@ class PagedKVCache(KVCache):
             raise RuntimeError(f"page pool exhausted: {missing} more pages needed for {n_tokens} rows per sequence, {len(self.free)} of "
                                f"{self.n_pages} free ({missing - len(self.free)} short)")
         for b in rows:
-            own, gone = self.pages[b], self.released[b]   # (released leading slots stay unowned: the windowed kernels never read them)
+            own, gone = self.pages[b], self.released[b]   # (released slots stay unowned: the windowed kernels never read them)
             if gone + len(own) >= need:
                 continue
             while gone + len(own) < need:
                 own.append(self.free.pop())
-            row = [0] * gone + own + [0] * (self.max_pages - gone - len(own))
+            keep = self.sink_pages   # (gone > 0 only once the sequence owns every sink slot; the released slots sit behind them)
+            row = own[:keep] + [0] * gone + own[keep:] + [0] * (self.max_pages - gone - len(own))
             self.block_table[b].copy_(torch.tensor(row, dtype=torch.int32))
 
     def release(self, b):
@@ -270,7 +295,9 @@ class PagedKVCache(KVCache):
         here).  Every later query of sequence b sits at a position >= lengths[b] and admits keys above its position - window, so a
         page whose last row is <= lengths[b] - window is out of reach for good: it goes back to the free list (the next reserve may
         hand it to anyone) and its table slot is counted in ``released[b]``.  Nothing is written to the device: the windowed kernels
-        start every key range at the window and never read those slots, whatever they hold.  Returns the number of pages freed."""
+        start every key range at the window and never read those slots, whatever they hold.  A cache with sink tokens keeps its
+        ``sink_pages`` leading slots, which every later query still reads, and releases from the slot behind them on.  Returns the
+        number of pages freed."""
         if self.window is None:
             raise ValueError("release_behind_window needs a cache with a window: without one every row stays visible")
         lengths = [int(n) for n in lengths]
@@ -280,10 +307,11 @@ class PagedKVCache(KVCache):
         for b, n in enumerate(lengths):
             # slot s holds rows s * page_size .. (s + 1) * page_size - 1: out of reach when (s + 1) * page_size - 1 <= n - window
             behind = max(0, n - self.window + 1) // self.page_size
-            drop = min(behind - self.released[b], len(self.pages[b]))
+            keep = self.sink_pages   # (the sink slots stay; the releasable slots are keep .. behind - 1)
+            drop = min(behind - keep - self.released[b], len(self.pages[b]) - keep)
             if drop > 0:
-                self.free.extend(reversed(self.pages[b][:drop]))
-                del self.pages[b][:drop]
+                self.free.extend(reversed(self.pages[b][keep:keep + drop]))
+                del self.pages[b][keep:keep + drop]
                 self.released[b] += drop
                 freed += drop
         return freed

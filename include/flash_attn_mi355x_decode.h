@@ -161,4 +161,8 @@ const char* fa_mi355x_decode_last_error(void);
  * entry points, part of this library and of this header, kept in a file of their own. */
 #include "flash_attn_mi355x_decode_fp8.h"
 
+/* Attention-sink tokens (the first S positions stay visible beside the sliding window) for the windowed decode, extend and ragged
+ * calls: nine entry points, part of this library and of this header, kept in a file of their own. */
+#include "flash_attn_mi355x_decode_sink.h"
+
 #endif /* FLASH_ATTN_MI355X_DECODE_H */
