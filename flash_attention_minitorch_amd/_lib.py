@@ -181,6 +181,13 @@ FP8_ABI = {
     "fa_mi355x_append_fp8": (_i, [_vp] * 8 + [_i] * 11 + [_vp]),
 }
 
+# the same for include/flash_attn_mi355x_decode_rope.h (rotary embeddings: a tensor rotated, and the roped append; tests/test_rope_cpu.py)
+ROPE_ABI = {
+    "fa_mi355x_rope": (_i, [_vp] * 5 + [_i] * 10 + [_vp]),
+    "fa_mi355x_rope_append": (_i, [_vp] * 12 + [_i] * 16 + [_vp]),
+    "fa_mi355x_rope_append_ragged": (_i, [_vp] * 11 + [_i] * 15 + [_vp]),
+}
+
 
 def _typed(name: str, abi: dict) -> ctypes.CDLL:
     """The library with restype / argtypes of every symbol in ``abi`` set (once, on first load)."""
@@ -249,9 +256,9 @@ DECODE_NAME = "libflash_attn_mi355x_decode.so"
 
 
 def decode() -> ctypes.CDLL:
-    """libflash_attn_mi355x_decode.so (include/flash_attn_mi355x_decode.h, its _paged.h, its _ragged.h, its _window.h, its _fp8.h and its
-    _sink.h) with argtypes set."""
-    return _typed(DECODE_NAME, {**DECODE_ABI, **PAGED_ABI, **RAGGED_ABI, **WINDOW_ABI, **FP8_ABI, **SINK_ABI})
+    """libflash_attn_mi355x_decode.so (include/flash_attn_mi355x_decode.h, its _paged.h, its _ragged.h, its _window.h, its _fp8.h, its
+    _sink.h and its _rope.h) with argtypes set."""
+    return _typed(DECODE_NAME, {**DECODE_ABI, **PAGED_ABI, **RAGGED_ABI, **WINDOW_ABI, **FP8_ABI, **SINK_ABI, **ROPE_ABI})
 
 
 def decode_check(status: int) -> None:

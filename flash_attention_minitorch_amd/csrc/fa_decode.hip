@@ -3,7 +3,8 @@
 // extend policy on an upper bound of the row blocks) and the launches of the kernels of fa_decode.h.  A paged call (a pool and a
 // block table) takes the contiguous call's policy at Ncap = max_pages * page_size.  A windowed call (_window.h) takes the three
 // policies on its window span (span_keys) instead of Ncap, a sink call (_sink.h) on that span plus its sink tiles.  An fp8 call (_fp8.h: caches of e4m3 bytes, per-kv-head scales) takes the
-// bf16 call's policy and workspace for the same arguments; its cache bounds count one byte per element.
+// bf16 call's policy and workspace for the same arguments; its cache bounds count one byte per element.  The rotary calls (_rope.h)
+// launch the kernels of fa_rope.h in front of the attend-only entry points.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -12,6 +13,7 @@
 
 #include "../../include/flash_attn_mi355x_decode.h"
 #include "fa_decode.h"
+#include "fa_rope.h"
 
 namespace {
 
@@ -1064,6 +1066,227 @@ int fa_mi355x_append_fp8(const void* k_new, const void* v_new, void* k_cache, vo
   const Fp8 f8 = {k_scale, v_scale};
   return run_append(k_new, v_new, k_cache, v_cache, cache_seqlens, B, Hkv, Nq, Ncap, d_new, d, layout, dtype, stream, block_table ? &pg : nullptr,
                     nullptr, &f8);
+}
+
+// The rotary entry points (include/flash_attn_mi355x_decode_rope.h): a tensor rotated by position, and the roped append that goes
+// in front of the EXISTING attend-only entry points (rope_kernel and rope_append_kernel of fa_rope.h; no attention kernel changes).
+}  // extern "C"  (the launchers below are templates)
+
+namespace {
+
+// The checks of the tables and the rotary dimension; row_len: the shortest row that is rotated.
+int check_rope(const void* cos, const void* sin, int rot, int row_len, int max_pos, int interleaved, int inverse) {
+  if (!cos || !sin) return set_err(FA_ERR_BAD_ARG, "null cos or sin (the rotary tables, fp32 [max_pos][rot / 2])");
+  if (interleaved != 0 && interleaved != 1) return set_err(FA_ERR_BAD_ARG, "interleaved must be 0 (NeoX pairs) or 1 (GPT-J pairs)");
+  if (inverse != 0 && inverse != 1) return set_err(FA_ERR_BAD_ARG, "inverse must be 0 or 1");
+  if (rot < 2 || rot % 2 != 0 || rot > row_len) {
+    snprintf(g_err, sizeof(g_err), "rot = %d must be even and in 2 .. %d (the rotated rows' length: min(d_new, d) with new tokens)", rot, row_len);
+    return FA_ERR_BAD_ARG;
+  }
+  if (max_pos <= 0) return set_err(FA_ERR_BAD_ARG, "max_pos must be positive");
+  return FA_OK;
+}
+
+// 16-byte lanes (E elements): the pairs' halves (NeoX) or the pairs (interleaved) fall on whole vectors, which also aligns the
+// E (E / 2) table entries a lane reads; every row and every pointer on 16 bytes (align: an fp8 cache's rows on 8).
+bool rope_vec(int E, int rot, int interleaved, int len_a, int len_b, uintptr_t ptrs, uintptr_t caches, uintptr_t cache_align) {
+  if ((interleaved ? rot : rot / 2) % E != 0 || len_a % E != 0 || len_b % E != 0) return false;
+  return (ptrs & 15) == 0 && (caches & (cache_align - 1)) == 0;
+}
+
+template <typename T, int E> int launch_rope(fa::RopeArgs a, bool il, hipStream_t st) {
+  a.cpr = a.d / E;
+  a.lanes *= a.cpr;   // (rows on entry)
+  const dim3 grid((unsigned)((a.lanes + 255) / 256));
+  if (il)
+    hipLaunchKernelGGL((fa::rope_kernel<T, E, true>), grid, dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL((fa::rope_kernel<T, E, false>), grid, dim3(256), 0, st, a);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? FA_OK : set_err(FA_ERR_HIP, "rope_kernel launch", e);
+}
+
+template <typename T, int E, bool IL, bool FP8> void launch_rope_append_il(const fa::RopeAppendArgs& a, dim3 grid, hipStream_t st) {
+  if constexpr (FP8) {
+    if (a.table)
+      hipLaunchKernelGGL((fa::rope_append_kernel<T, E, IL, true, false, true>), grid, dim3(256), 0, st, a);
+    else
+      hipLaunchKernelGGL((fa::rope_append_kernel<T, E, IL, false, false, true>), grid, dim3(256), 0, st, a);
+  } else if (a.cu && a.table)
+    hipLaunchKernelGGL((fa::rope_append_kernel<T, E, IL, true, true>), grid, dim3(256), 0, st, a);
+  else if (a.cu)
+    hipLaunchKernelGGL((fa::rope_append_kernel<T, E, IL, false, true>), grid, dim3(256), 0, st, a);
+  else if (a.table)
+    hipLaunchKernelGGL((fa::rope_append_kernel<T, E, IL, true>), grid, dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL((fa::rope_append_kernel<T, E, IL>), grid, dim3(256), 0, st, a);
+}
+
+template <typename T, int E, bool FP8 = false> int launch_rope_append(fa::RopeAppendArgs a, bool il, hipStream_t st) {
+  a.ch_shift = __builtin_ctz(a.d / E);
+  a.lanes <<= a.ch_shift;     // (rows on entry)
+  a.q_lanes <<= a.ch_shift;
+  const dim3 grid((unsigned)((a.q_lanes + a.lanes + 255) / 256));
+  if (il)
+    launch_rope_append_il<T, E, true, FP8>(a, grid, st);
+  else
+    launch_rope_append_il<T, E, false, FP8>(a, grid, st);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? FA_OK : set_err(FA_ERR_HIP, "rope_append_kernel launch", e);
+}
+
+// One roped append, uniform (cu null: Nq new tokens per batch element) or ragged (cu: Nq = T packed rows); q / q_rot or
+// k_new / v_new may be absent (both null).  Every check comes first; then the one launch.
+int rope_append_call(const void* q, void* q_rot, const void* k_new, const void* v_new, void* k_cache, void* v_cache, const Fp8* f8,
+                     const float* cos, const float* sin, const int* cu, bool ragged, const int* cache_seqlens, const Paging* pg, int B, int H,
+                     int Hkv, int Nq, int Ncap, int d_new, int d, int rot, int max_pos, int layout, int interleaved, int dtype,
+                     void* stream) {
+  g_err[0] = 0;
+  int rc = f8 ? check_fp8(dtype) : FA_OK;
+  if (rc != FA_OK) return rc;
+  if ((q == nullptr) != (q_rot == nullptr)) return set_err(FA_ERR_BAD_ARG, "q and q_rot go together: give both, or neither (append only)");
+  if ((k_new == nullptr) != (v_new == nullptr))
+    return set_err(FA_ERR_BAD_ARG, "k_new and v_new go together: give both, or neither (rotate q only)");
+  if (!q && !k_new) return set_err(FA_ERR_BAD_ARG, "nothing to do: q / q_rot and k_new / v_new are all null");
+  if (pg) rc = check_pages(*pg, &Ncap);
+  if (rc != FA_OK) return rc;
+  if (k_new) {
+    rc = ragged ? check_ragged_append(k_new, v_new, k_cache, v_cache, cu, B, Hkv, Nq, Ncap, d_new, d, layout, dtype)
+                : check_append(k_new, v_new, k_cache, v_cache, B, Hkv, Nq, Ncap, d_new, d, layout, dtype, true);
+    if (rc == FA_OK && pg) rc = check_page_bytes(pg->page_size, Hkv, d, dtype, f8 != nullptr);
+    if (rc == FA_OK && f8 && !pg && ((long)Ncap + fa::DEC_ROWS) * Hkv * d >= (1L << 31))
+      rc = set_err(FA_ERR_BAD_ARG, "one batch element of the cache must stay under 2 GiB");
+    if (rc != FA_OK) return rc;
+  } else {
+    if (B <= 0 || Nq <= 0 || Ncap <= 0 || d <= 0) return set_err(FA_ERR_BAD_ARG, "B, Nq (T), Ncap and d must be positive");
+    if (dtype != FA_DTYPE_F32 && dtype != FA_DTYPE_BF16) return set_err(FA_ERR_BAD_ARG, "unknown dtype");
+    if (layout != FA_LAYOUT_BHND && layout != FA_LAYOUT_BNHD) return set_err(FA_ERR_BAD_ARG, "unknown layout");
+    if (ragged && !cu) return set_err(FA_ERR_BAD_ARG, "null cu_seqlens_q");
+    if (d != 32 && d != 64 && d != 128) return set_err(FA_ERR_UNSUPPORTED_D, "decode supports rows of d in {32, 64, 128}");
+    d_new = d;
+  }
+  if (q) {
+    if (H <= 0) return set_err(FA_ERR_BAD_ARG, "H must be positive");
+    // (one lane per element at the most, the workgroup count of q's and the new rows' lanes together an unsigned int)
+    if ((long)(ragged ? 1 : B) * Nq * H * d / 256 >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "too many q elements for one rope_append launch");
+  }
+  rc = check_rope(cos, sin, rot, std::min(d_new, d), max_pos, interleaved, 0);
+  if (rc != FA_OK) return rc;
+  if (max_pos < Ncap) {
+    snprintf(g_err, sizeof(g_err), "max_pos = %d table rows do not cover the cache's capacity of %d rows: every row needs an angle", max_pos, Ncap);
+    return FA_ERR_BAD_ARG;
+  }
+  fa::RopeAppendArgs a;
+  a.k_new = k_new;
+  a.v_new = v_new;
+  a.k = k_cache;
+  a.v = v_cache;
+  a.seqlens = cache_seqlens;
+  const long seqs = ragged ? 1 : B;
+  a.lanes = k_new ? seqs * Nq * Hkv : 0;
+  a.q_lanes = q ? seqs * Nq * H : 0;
+  a.Hkv = Hkv;
+  a.Nq = Nq;
+  a.Ncap = Ncap;
+  a.d_new = d_new;
+  a.bnhd = layout == FA_LAYOUT_BNHD;
+  a.kv_ld = a.bnhd ? Hkv * d : d;
+  a.kv_bstride = (long)Ncap * Hkv * d;
+  a.kv_hstride = a.bnhd ? d : (long)Ncap * d;
+  a.table = nullptr;
+  a.page_size = a.num_pages = a.max_pages = 0;
+  a.page_stride = 0;
+  if (pg) {
+    a.table = pg->table;
+    a.page_size = pg->page_size;
+    a.num_pages = pg->num_pages;
+    a.max_pages = pg->max_pages;
+    a.page_stride = (long)pg->page_size * Hkv * d;
+    a.kv_bstride = 0;
+    a.kv_hstride = a.bnhd ? d : (long)pg->page_size * d;
+  }
+  a.q = q;
+  a.q_rot = q_rot;
+  a.cos = cos;
+  a.sin = sin;
+  a.k_scale = f8 ? f8->k_scale : nullptr;
+  a.v_scale = f8 ? f8->v_scale : nullptr;
+  a.H = H;
+  a.d = d;
+  a.rot = rot;
+  a.max_pos = max_pos;
+  a.cu = ragged ? cu : nullptr;
+  a.nseq = B;
+  a.ntok = Nq;
+  const int esz = dtype == FA_DTYPE_BF16 ? 2 : 4;
+  const uintptr_t ptrs = (uintptr_t)q | (uintptr_t)q_rot | (uintptr_t)k_new | (uintptr_t)v_new | (uintptr_t)cos | (uintptr_t)sin;
+  const uintptr_t caches = k_new ? (uintptr_t)k_cache | (uintptr_t)v_cache : 0;
+  const bool vec = rope_vec(16 / esz, rot, interleaved, d_new, d, ptrs, caches, f8 ? 8 : 16);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const bool il = interleaved != 0;
+  if (f8) return vec ? launch_rope_append<fa::bf16_t, 8, true>(a, il, st) : launch_rope_append<fa::bf16_t, 1, true>(a, il, st);
+  if (dtype == FA_DTYPE_BF16) return vec ? launch_rope_append<fa::bf16_t, 8>(a, il, st) : launch_rope_append<fa::bf16_t, 1>(a, il, st);
+  return vec ? launch_rope_append<float, 4>(a, il, st) : launch_rope_append<float, 1>(a, il, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+int fa_mi355x_rope(const void* x, void* y, const float* cos, const float* sin, const int* pos_offsets, int B, int N, int H, int d, int rot,
+                   int max_pos, int layout, int interleaved, int inverse, int dtype, void* stream) {
+  g_err[0] = 0;
+  if (B <= 0 || N <= 0 || H <= 0 || d <= 0) return set_err(FA_ERR_BAD_ARG, "B, N, H and d must be positive");
+  if (dtype != FA_DTYPE_F32 && dtype != FA_DTYPE_BF16) return set_err(FA_ERR_BAD_ARG, "unknown dtype");
+  if (layout != FA_LAYOUT_BHND && layout != FA_LAYOUT_BNHD) return set_err(FA_ERR_BAD_ARG, "unknown layout");
+  if (!x || !y) return set_err(FA_ERR_BAD_ARG, "null pointer argument (x and y)");
+  const int rc = check_rope(cos, sin, rot, d, max_pos, interleaved, inverse);
+  if (rc != FA_OK) return rc;
+  // (one lane per element at the most, 256 lanes to a workgroup, the workgroup count an int)
+  if ((long)B * N * H * d / 256 >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "too many elements for one rope launch");
+  fa::RopeArgs a;
+  a.x = x;
+  a.y = y;
+  a.cos = cos;
+  a.sin = sin;
+  a.offsets = pos_offsets;
+  a.lanes = (long)B * N * H;
+  a.N = N;
+  a.H = H;
+  a.d = d;
+  a.rot = rot;
+  a.max_pos = max_pos;
+  a.bnhd = layout == FA_LAYOUT_BNHD;
+  a.inverse = inverse;
+  const int esz = dtype == FA_DTYPE_BF16 ? 2 : 4;
+  const bool vec = rope_vec(16 / esz, rot, interleaved, d, d, (uintptr_t)x | (uintptr_t)y | (uintptr_t)cos | (uintptr_t)sin, 0, 16);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const bool il = interleaved != 0;
+  if (dtype == FA_DTYPE_BF16) return vec ? launch_rope<fa::bf16_t, 8>(a, il, st) : launch_rope<fa::bf16_t, 1>(a, il, st);
+  return vec ? launch_rope<float, 4>(a, il, st) : launch_rope<float, 1>(a, il, st);
+}
+
+int fa_mi355x_rope_append(const void* q, void* q_rot, const void* k_new, const void* v_new, void* k_cache, void* v_cache, const float* k_scale,
+                          const float* v_scale, const float* cos, const float* sin, const int* cache_seqlens, const int* block_table, int B,
+                          int H, int Hkv, int Nq, int Ncap, int num_pages, int page_size, int max_pages, int d_new, int d, int rot,
+                          int max_pos, int layout, int interleaved, int cache_fp8, int dtype, void* stream) {
+  if (cache_fp8 != 0 && cache_fp8 != 1) {
+    g_err[0] = 0;
+    return set_err(FA_ERR_BAD_ARG, "cache_fp8 must be 0 or 1");
+  }
+  const Paging pg = {block_table, num_pages, page_size, max_pages};
+  const Fp8 f8 = {k_scale, v_scale};
+  return rope_append_call(q, q_rot, k_new, v_new, k_cache, v_cache, cache_fp8 ? &f8 : nullptr, cos, sin, nullptr, false, cache_seqlens,
+                          block_table ? &pg : nullptr, B, H, Hkv, Nq, Ncap, d_new, d, rot, max_pos, layout, interleaved, dtype, stream);
+}
+
+int fa_mi355x_rope_append_ragged(const void* q, void* q_rot, const void* k_new, const void* v_new, void* k_cache, void* v_cache,
+                                 const float* cos, const float* sin, const int* cu_seqlens_q, const int* cache_seqlens,
+                                 const int* block_table, int B, int H, int Hkv, int T, int Ncap, int num_pages, int page_size, int max_pages,
+                                 int d_new, int d, int rot, int max_pos, int layout, int interleaved, int dtype, void* stream) {
+  const Paging pg = {block_table, num_pages, page_size, max_pages};
+  return rope_append_call(q, q_rot, k_new, v_new, k_cache, v_cache, nullptr, cos, sin, cu_seqlens_q, true, cache_seqlens,
+                          block_table ? &pg : nullptr, B, H, Hkv, T, Ncap, d_new, d, rot, max_pos, layout, interleaved, dtype, stream);
 }
 
 // The ungrouped entry points: Hkv = H.

@@ -744,9 +744,152 @@ def _check_new(k_new, v_new, k_cache, layout, Nq=None, paged=False):
     return n, d_new
 
 
-def _append(who, entry, k_new, v_new, k_cache, v_cache, cache_seqlens, layout, block_table=None, k_scale=None, v_scale=None):
+# ---- rotary position embeddings (include/flash_attn_mi355x_decode_rope.h) ----
+
+def rotary_table(max_pos, rot, base=10000.0, device=None):
+    """The (cos, sin) tables of a rotary embedding, float32 (max_pos, rot // 2) on ``device``: the angle of position p and pair j is
+    p * base ** (-2 j / rot), computed in float64 and rounded once.  Any other table (scaled, YaRN) can be built by the caller: the
+    kernels only read what they are given."""
+    rot, max_pos = operator.index(rot), operator.index(max_pos)
+    if rot < 2 or rot % 2:
+        raise ValueError("rot, the rotary dimension, must be even and at least 2")
+    if max_pos < 1:
+        raise ValueError("max_pos must be positive")
+    inv = float(base) ** (-torch.arange(0, rot, 2, dtype=torch.float64) / rot)
+    ang = torch.arange(max_pos, dtype=torch.float64)[:, None] * inv[None, :]
+    return (ang.cos().to(torch.float32).to(device).contiguous(), ang.sin().to(torch.float32).to(device).contiguous())
+
+
+def _check_rotary(cos, sin, device, interleaved=False):
+    """``rotary_cos`` / ``rotary_sin`` as the library takes them: both None is None (no rotary: the paths without it); otherwise contiguous
+    float32 (max_pos, rot / 2) tensors of one shape on ``device``, and the answer is (rot, max_pos, interleaved as 0 / 1)."""
+    if cos is None and sin is None:
+        return None
+    if cos is None or sin is None:
+        raise ValueError("rotary_cos and rotary_sin go together: give both tables or neither")
+    for name, t in (("rotary_cos", cos), ("rotary_sin", sin)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise TypeError(f"{name} must be a float32 tensor of shape (max_pos, rot / 2)")
+    if cos.dim() != 2 or cos.shape != sin.shape or cos.shape[0] < 1 or cos.shape[1] < 1:
+        raise ValueError("rotary_cos and rotary_sin must have one shape, (max_pos, rot / 2)")
+    if cos.device != device or sin.device != device:
+        raise ValueError("rotary_cos and rotary_sin must live on the device of the tensors they rotate")
+    if not cos.is_contiguous() or not sin.is_contiguous():
+        raise ValueError("rotary_cos and rotary_sin must be contiguous")
+    return 2 * cos.shape[1], cos.shape[0], int(bool(interleaved))
+
+
+def _rotary_call(x, y, cos, sin, seqlen_offsets, interleaved, inverse, layout):
+    B, N, H, d = x.shape if layout == "bnhd" else (x.shape[0], x.shape[2], x.shape[1], x.shape[3])
+    rot, max_pos, il = _check_rotary(cos, sin, x.device, interleaved)
+    _lib.decode_check(_lib.decode().fa_mi355x_rope(
+        _ptr(x), _ptr(y), _ptr(cos), _ptr(sin), _ptr(seqlen_offsets), B, N, H, d, rot, max_pos, _DECODE_LAYOUTS[layout], il,
+        int(bool(inverse)), _dtype_code(x), _stream_ptr()))
+    return y
+
+
+class _RotaryFn(torch.autograd.Function):
+    """apply_rotary under autograd: a rotation is orthogonal, so the gradient is the inverse rotation of the cotangent."""
+
+    @staticmethod
+    def forward(ctx, x, cos, sin, seqlen_offsets, interleaved, inverse, layout, out):
+        ctx.save_for_backward(cos, sin, seqlen_offsets)
+        ctx.how = (interleaved, inverse, layout)
+        if out is None:
+            out = torch.empty_like(x)
+        else:   # (an input that the call fills: x itself for the in-place rotation)
+            ctx.mark_dirty(out)
+        return _rotary_call(x, out, cos, sin, seqlen_offsets, interleaved, inverse, layout)
+
+    @staticmethod
+    def backward(ctx, g):
+        cos, sin, seqlen_offsets = ctx.saved_tensors
+        interleaved, inverse, layout = ctx.how
+        g = g.contiguous()
+        return _rotary_call(g, torch.empty_like(g), cos, sin, seqlen_offsets, interleaved, not inverse, layout), None, None, None, None, None, None, None
+
+
+def apply_rotary(x, cos, sin, seqlen_offsets=None, interleaved=False, inverse=False, layout="bnhd", out=None):
+    """Rotary position embedding of a tensor (fa_mi355x_rope, include/flash_attn_mi355x_decode_rope.h): x (B, N, H, d) for "bnhd" or
+    (B, H, N, d) for "bhnd", float32 or bfloat16, contiguous; ``cos`` / ``sin`` contiguous float32 (max_pos, rot / 2) on x's device
+    (rotary_table), rot even and <= d.  Row i of batch element b sits at position seqlen_offsets[b] + i (``seqlen_offsets``: a
+    contiguous int32 (B,) tensor on x's device, read on the device; None: zeros), clamped to the table on the device.  Pair j of a
+    row is (x[j], x[j + rot/2]) (NeoX / Llama) or, ``interleaved``, (x[2j], x[2j+1]) (GPT-J); with c, s the pair's table entries
+    y1 = x1 c - x2 s and y2 = x2 c + x1 s in float32, rounded once to x's dtype; ``inverse`` takes -s.  Columns rot .. d-1 are
+    copied.  ``out``: a contiguous tensor of x's shape and dtype, which may be x (in place).  Differentiable in x: the backward is
+    the inverse rotation of the gradient."""
+    if layout not in _DECODE_LAYOUTS:
+        raise ValueError(f"layout must be one of {sorted(_DECODE_LAYOUTS)}")
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise ValueError("apply_rotary expects a 4-d x")
+    _dtype_code(x)
+    rot = _check_rotary(cos, sin, x.device)
+    if rot is None:
+        raise ValueError("apply_rotary needs both tables, cos and sin")
+    if rot[0] > x.shape[3]:
+        raise ValueError(f"the tables' rotary dimension {rot[0]} exceeds x's head dim {x.shape[3]}")
+    if seqlen_offsets is not None and (not isinstance(seqlen_offsets, torch.Tensor) or seqlen_offsets.dtype != torch.int32
+                                       or tuple(seqlen_offsets.shape) != (x.shape[0],) or seqlen_offsets.device != x.device
+                                       or not seqlen_offsets.is_contiguous()):
+        raise ValueError("seqlen_offsets must be a contiguous int32 tensor of shape (B,) on x's device")
+    if not x.is_contiguous():
+        raise ValueError("x must be contiguous")
+    if out is not None and (out.shape != x.shape or out.dtype != x.dtype or out.device != x.device or not out.is_contiguous()):
+        raise ValueError("out must be a contiguous tensor of x's shape, dtype and device")
+    _require_gpu(x, "apply_rotary")
+    return _RotaryFn.apply(x, cos, sin, seqlen_offsets, bool(interleaved), bool(inverse), layout, out)
+
+
+def _rope_append(rotary, q, q_rot, k_new, v_new, k_cache, v_cache, k_scale, v_scale, cache_seqlens, cu_seqlens_q, block_table, B, H, Hkv,
+                 Nq, Ncap, pool, d_new, dp, layout, fp8, dtype):
+    """The roped append in front of an attend-only call (fa_mi355x_rope_append, or _ragged with ``cu_seqlens_q``): q -> q_rot,
+    k_new -> the K cache, both rotated at the positions the append gives the tokens, v_new -> the V cache; q / q_rot or k_new / v_new
+    may be None.  ``pool``: (num_pages, page_size, max_pages) of a paged cache, or None."""
+    cos, sin, (rot, max_pos, il) = rotary
+    geometry = (0, *pool) if pool else (Ncap, 0, 0, 0)
+    lib = _lib.decode()
+    if cu_seqlens_q is not None:
+        status = lib.fa_mi355x_rope_append_ragged(
+            _ptr(q), _ptr(q_rot), _ptr(k_new), _ptr(v_new), _ptr(k_cache), _ptr(v_cache), _ptr(cos), _ptr(sin), _ptr(cu_seqlens_q),
+            _ptr(cache_seqlens), _ptr(block_table), B, H, Hkv, Nq, *geometry, d_new, dp, rot, max_pos, _DECODE_LAYOUTS[layout], il, dtype,
+            _stream_ptr())
+    else:
+        status = lib.fa_mi355x_rope_append(
+            _ptr(q), _ptr(q_rot), _ptr(k_new), _ptr(v_new), _ptr(k_cache), _ptr(v_cache), _ptr(k_scale), _ptr(v_scale), _ptr(cos), _ptr(sin),
+            _ptr(cache_seqlens), _ptr(block_table), B, H, Hkv, Nq, *geometry, d_new, dp, rot, max_pos, _DECODE_LAYOUTS[layout], il,
+            int(bool(fp8)), dtype, _stream_ptr())
+    _lib.decode_check(status)
+
+
+def _rotary_of(rotary_cos, rotary_sin, rotary_interleaved, device):
+    """None (no rotary), or (cos, sin, (rot, max_pos, interleaved)) of checked tables."""
+    dims = _check_rotary(rotary_cos, rotary_sin, device, rotary_interleaved)
+    return None if dims is None else (rotary_cos, rotary_sin, dims)
+
+
+def _check_rot(rotary, d, d_new=None):
+    rot = rotary[2][0]
+    if rot > d or (d_new is not None and rot > d_new):
+        raise ValueError(f"the tables' rotary dimension {rot} exceeds the head dim of the rows it rotates ({d if d_new is None else min(d, d_new)})")
+
+
+def _q_rot_buffer(q_rot, q, qp):
+    """The tensor the rotated (padded) q goes into: the caller's ``q_rot`` where it fits as it is, otherwise a new one."""
+    if q_rot is not None and (not isinstance(q_rot, torch.Tensor) or q_rot.shape != q.shape or q_rot.dtype != q.dtype
+                              or q_rot.device != q.device or not q_rot.is_contiguous()):
+        raise ValueError("q_rot must be a contiguous tensor of q's shape, dtype and device")
+    if q_rot is None:
+        return torch.empty_like(qp)
+    return q_rot if qp is q else pad_head_dim(q_rot, qp.shape[-1])   # (padded: rows a ragged call does not own come back as they were)
+
+
+def _append(who, entry, k_new, v_new, k_cache, v_cache, cache_seqlens, layout, block_table=None, k_scale=None, v_scale=None,
+            rotary_cos=None, rotary_sin=None, rotary_interleaved=False, q_rot=None):
     """decode_append / extend_append: the checks, then the library's ``entry`` (its _paged form when there is a block table; for an
-    fp8 cache fa_mi355x_append_fp8, which quantises)."""
+    fp8 cache fa_mi355x_append_fp8, which quantises; with rotary tables fa_mi355x_rope_append without a q)."""
+    rotary = _rotary_of(rotary_cos, rotary_sin, rotary_interleaved, k_cache.device)
+    if q_rot is not None:
+        raise ValueError("q_rot belongs to a call that has a q: an append rotates k_new only")
     if layout not in _DECODE_LAYOUTS:
         raise ValueError(f"layout must be one of {sorted(_DECODE_LAYOUTS)}")
     if k_cache.dim() != 4 or k_cache.shape != v_cache.shape:
@@ -769,9 +912,14 @@ def _append(who, entry, k_new, v_new, k_cache, v_cache, cache_seqlens, layout, b
         if t.device != k_cache.device or not t.is_contiguous():
             raise ValueError("k_cache and v_cache must be contiguous and live on one device")
         _require_gpu(t, who)
+    if (fp8 or rotary) and who == "decode_append" and Nq > 128:
+        raise ValueError("decode_append takes at most 128 new tokens per call: use extend_append")
+    if rotary:   # (one entry point for any Nq, slab or paged, fp8 or not: no q, so k_new alone is rotated)
+        _check_rot(rotary, dp, d_new)
+        _rope_append(rotary, None, None, k_new, v_new, k_cache, v_cache, k_scale, v_scale, cache_seqlens, None, block_table, B, Hkv, Hkv,
+                     Nq, Ncap, (num_pages, page_size, block_table.shape[1]) if paged else None, d_new, dp, layout, fp8, dtype)
+        return
     if fp8:   # (one entry point for any Nq: a null table is a slab cache)
-        if who == "decode_append" and Nq > 128:
-            raise ValueError("decode_append takes at most 128 new tokens per call: use extend_append")
         geometry = (0, num_pages, page_size, block_table.shape[1]) if paged else (Ncap, 0, 0, 0)
         _lib.decode_check(_lib.decode().fa_mi355x_append_fp8(
             _ptr(k_new), _ptr(v_new), _ptr(k_cache), _ptr(v_cache), _ptr(k_scale), _ptr(v_scale), _ptr(cache_seqlens), _ptr(block_table),
@@ -783,7 +931,8 @@ def _append(who, entry, k_new, v_new, k_cache, v_cache, cache_seqlens, layout, b
         _DECODE_LAYOUTS[layout], dtype, _stream_ptr()))
 
 
-def decode_append(k_new, v_new, k_cache, v_cache, cache_seqlens=None, layout="bnhd", block_table=None, k_scale=None, v_scale=None):
+def decode_append(k_new, v_new, k_cache, v_cache, cache_seqlens=None, layout="bnhd", block_table=None, k_scale=None, v_scale=None,
+                  rotary_cos=None, rotary_sin=None, rotary_interleaved=False, q_rot=None):
     """Write the Nq <= 128 new tokens' k and v into the caches on the device (fa_mi355x_decode_append): k_new, v_new (B, Nq, Hkv,
     d_new) for "bnhd" or (B, Hkv, Nq, d_new) for "bhnd", 1 <= d_new <= dp, into caches (B, Ncap, Hkv, dp) / (B, Hkv, Ncap, dp).
     ``cache_seqlens`` COUNTS the new tokens, as flash_attn_decode reads it: token i goes to row clamp(len_b, 0, Ncap) - Nq + i when
@@ -794,22 +943,35 @@ def decode_append(k_new, v_new, k_cache, v_cache, cache_seqlens=None, layout="bn
     An FP8 cache (torch.float8_e4m3fn caches, bfloat16 k_new / v_new; fa_mi355x_append_fp8): every element x of kv head h is stored
     as the e4m3 code of clamp(x * (1 / scale[h]), -448, 448), rounded to nearest even (overflow saturates to +-448, a NaN stores the
     NaN code 0x7F), with ``k_scale`` / ``v_scale`` contiguous float32 (Hkv,) on the cache's device (None: ones); columns d_new .. dp-1
-    are zero bytes.  Scales with any other cache are an error."""
-    _append("decode_append", "fa_mi355x_decode_append", k_new, v_new, k_cache, v_cache, cache_seqlens, layout, block_table, k_scale, v_scale)
+    are zero bytes.  Scales with any other cache are an error.
+    ``rotary_cos`` / ``rotary_sin`` (both or neither; rotary_table): k_new is ROTATED on its way into the K cache
+    (fa_mi355x_rope_append without a q): token i of batch element b at position clamp(len_b, 0, Ncap) - Nq + i, the row it is
+    written to; ``rotary_interleaved`` picks GPT-J pairs.  The tables must cover the cache (max_pos >= Ncap).  v_new is never
+    rotated.  ``q_rot`` must stay None here (an append has no q)."""
+    _append("decode_append", "fa_mi355x_decode_append", k_new, v_new, k_cache, v_cache, cache_seqlens, layout, block_table, k_scale, v_scale,
+            rotary_cos, rotary_sin, rotary_interleaved, q_rot)
 
 
-def extend_append(k_new, v_new, k_cache, v_cache, cache_seqlens=None, layout="bnhd", block_table=None, k_scale=None, v_scale=None):
+def extend_append(k_new, v_new, k_cache, v_cache, cache_seqlens=None, layout="bnhd", block_table=None, k_scale=None, v_scale=None,
+                  rotary_cos=None, rotary_sin=None, rotary_interleaved=False, q_rot=None):
     """decode_append for any number of new tokens (fa_mi355x_extend_append: the same kernel, placement and checks, no bound on Nq)."""
-    _append("extend_append", "fa_mi355x_extend_append", k_new, v_new, k_cache, v_cache, cache_seqlens, layout, block_table, k_scale, v_scale)
+    _append("extend_append", "fa_mi355x_extend_append", k_new, v_new, k_cache, v_cache, cache_seqlens, layout, block_table, k_scale, v_scale,
+            rotary_cos, rotary_sin, rotary_interleaved, q_rot)
 
 
 def _cache_attention(who, extend, q, k_cache, v_cache, cache_seqlens, causal, softmax_scale, layout, out, lse, workspace, k_new, v_new,
-                     block_table=None, window=None, k_scale=None, v_scale=None, sink=None):
+                     block_table=None, window=None, k_scale=None, v_scale=None, sink=None, rotary_cos=None, rotary_sin=None,
+                     rotary_interleaved=False, q_rot=None):
     """flash_attn_decode / flash_attn_extend (``extend``): the checks, the head-dim padding, then the library's entry point (its
     _paged form when there is a block table; with a ``window``, the family's one _window entry point, with ``sink`` tokens beside it
-    the family's one _sink entry point; on an fp8 cache, the family's one _fp8 entry point)."""
+    the family's one _sink entry point; on an fp8 cache, the family's one _fp8 entry point).  With rotary tables:
+    fa_mi355x_rope_append (q -> q_rot, the rotated k_new and v_new into the caches), then the ATTEND-ONLY form of the same choice
+    on q_rot."""
     window = _check_window(window, causal)
     sink = _check_sink(sink, window)
+    rotary = _rotary_of(rotary_cos, rotary_sin, rotary_interleaved, q.device)
+    if rotary is None and q_rot is not None:
+        raise ValueError("q_rot is where a roped call leaves the rotated q: it needs rotary_cos and rotary_sin")
     if (k_new is None) != (v_new is None):
         raise ValueError("k_new and v_new go together: give both (fused append) or neither")
     if layout not in _DECODE_LAYOUTS:
@@ -867,6 +1029,15 @@ def _cache_attention(who, extend, q, k_cache, v_cache, cache_seqlens, causal, so
         workspace = new_ws(qp, k_cache, layout, **pages, window=window, sink=sink)
     elif workspace.numel() * workspace.element_size() < ws_bytes(B, H, Hkv, Nq, Ncap, dp, window, sink):
         raise ValueError(f"workspace too small: size it with {new_ws.__name__}()")
+    if rotary:   # (the roped append, then the attend-only form of whatever follows, on the rotated q)
+        _check_rot(rotary, d, d_new if k_new is not None else None)
+        qr = _q_rot_buffer(q_rot, q, qp)
+        _rope_append(rotary, qp, qr, k_new, v_new, k_cache, v_cache, k_scale, v_scale, cache_seqlens, None, block_table, B, H, Hkv, Nq,
+                     Ncap, (num_pages, page_size, pages["max_pages"]) if paged else None, d_new if k_new is not None else dp, dp, layout,
+                     fp8, dtype)
+        if q_rot is not None and qr is not q_rot:
+            q_rot.copy_(qr[..., :d])
+        qp, k_new, v_new = qr, None, None
     tail = (_DECODE_LAYOUTS[layout], float(softmax_scale), int(bool(causal)), dtype, _stream_ptr())
     if fp8:   # (one entry point per family, as the windowed calls: null k_new / v_new attend only, a null table is a slab cache)
         fwd = lib.fa_mi355x_fwd_extend_fp8 if extend else lib.fa_mi355x_fwd_decode_fp8
@@ -911,7 +1082,8 @@ def _cache_attention(who, extend, q, k_cache, v_cache, cache_seqlens, causal, so
 
 
 def flash_attn_decode(q, k_cache, v_cache, cache_seqlens=None, causal=True, softmax_scale=None, layout="bnhd", out=None, lse=None,
-                      workspace=None, k_new=None, v_new=None, block_table=None, window=None, k_scale=None, v_scale=None, sink=None):
+                      workspace=None, k_new=None, v_new=None, block_table=None, window=None, k_scale=None, v_scale=None, sink=None,
+                      rotary_cos=None, rotary_sin=None, rotary_interleaved=False, q_rot=None):
     """Attention of Nq <= 128 new queries against a KV cache (fa_mi355x_fwd_decode / _gqa, include/flash_attn_mi355x_decode.h).
     ``layout`` "bnhd": q (B, Nq, H, d), caches (B, Ncap, Hkv, dp); "bhnd": q (B, H, Nq, d), caches (B, Hkv, Ncap, dp).  Hkv is the
     cache's own head count and must divide H: Hkv < H is a grouped-query (Hkv = 1: multi-query) cache, query head h reads cache head
@@ -944,13 +1116,23 @@ def flash_attn_decode(q, k_cache, v_cache, cache_seqlens=None, causal=True, soft
     power-of-two scales the result is bit for bit the bf16 call's on the cache cast to bfloat16 with softmax_scale * k_scale,
     times v_scale.  The workspace is the bf16 call's (decode_workspace takes the fp8 cache).  No ``window`` or ``sink`` on an fp8 cache, and
     scales with any other cache are an error.
+    ``rotary_cos`` / ``rotary_sin`` (both or neither: contiguous float32 (max_pos, rot / 2) on q's device, rotary_table; rot even,
+    <= d and <= d_new, max_pos >= Ncap): ROTARY position embeddings (include/flash_attn_mi355x_decode_rope.h).  One launch
+    (fa_mi355x_rope_append) rotates q into ``q_rot`` (a contiguous tensor of q's shape and dtype, which may be q; None: allocated),
+    rotates k_new on its way into the K cache and copies v_new into the V cache; the attention is then the ATTEND-ONLY form of
+    whichever entry point the other arguments select, on q_rot.  New token i of batch element b, and its query, sit at position
+    clamp(len_b, 0, Ncap) - Nq + i; ``rotary_interleaved`` picks GPT-J pairs (x[2j], x[2j+1]) instead of NeoX ones
+    (x[j], x[j + rot/2]).  Bit for bit the call without the tables on apply_rotary(q) and apply_rotary(k_new) at those positions.
+    Works with every cache feature above (paged, window, sink, fp8).  Without k_new / v_new only q is rotated.
     Returns (out fp32 in q's shape, lse fp32 (B, H, Nq)): rows with no admissible key give out = 0, lse = -inf."""
     return _cache_attention("flash_attn_decode", False, q, k_cache, v_cache, cache_seqlens, causal, softmax_scale, layout, out, lse,
-                            workspace, k_new, v_new, block_table, window, k_scale, v_scale, sink)
+                            workspace, k_new, v_new, block_table, window, k_scale, v_scale, sink, rotary_cos, rotary_sin, rotary_interleaved,
+                            q_rot)
 
 
 def flash_attn_extend(q, k_cache, v_cache, cache_seqlens=None, causal=True, softmax_scale=None, layout="bnhd", out=None, lse=None,
-                      workspace=None, k_new=None, v_new=None, block_table=None, window=None, k_scale=None, v_scale=None, sink=None):
+                      workspace=None, k_new=None, v_new=None, block_table=None, window=None, k_scale=None, v_scale=None, sink=None,
+                      rotary_cos=None, rotary_sin=None, rotary_interleaved=False, q_rot=None):
     """flash_attn_decode for ANY number Nq >= 1 of new queries (fa_mi355x_fwd_extend / fa_mi355x_fwd_extend_append): a long input that
     follows a cached prefix, or one piece of a chunked prefill (the same call, from an empty cache on).  Every argument, check, the
     head-dim padding (the default scale keeps the caller's 1/sqrt(d)) and the return value are flash_attn_decode's; ``workspace`` is
@@ -961,9 +1143,12 @@ def flash_attn_extend(q, k_cache, v_cache, cache_seqlens=None, causal=True, soft
     sliding-window attention, as in flash_attn_decode (fa_mi355x_fwd_extend_window): every 128-row block walks its own W + 128
     positions' worth of keys wherever it sits in a long input; size a workspace with extend_workspace(..., window=).  ``k_scale`` /
     ``v_scale``: an fp8 cache, as in flash_attn_decode (fa_mi355x_fwd_extend_fp8).  ``sink``: attention-sink tokens beside the
-    window, as in flash_attn_decode (fa_mi355x_fwd_extend_sink; extend_workspace(..., window=, sink=))."""
+    window, as in flash_attn_decode (fa_mi355x_fwd_extend_sink; extend_workspace(..., window=, sink=)).  ``rotary_cos`` /
+    ``rotary_sin`` / ``rotary_interleaved`` / ``q_rot``: rotary embeddings, as in flash_attn_decode (fa_mi355x_rope_append, then the
+    attend-only extend call on q_rot)."""
     return _cache_attention("flash_attn_extend", True, q, k_cache, v_cache, cache_seqlens, causal, softmax_scale, layout, out, lse,
-                            workspace, k_new, v_new, block_table, window, k_scale, v_scale, sink)
+                            workspace, k_new, v_new, block_table, window, k_scale, v_scale, sink, rotary_cos, rotary_sin, rotary_interleaved,
+                            q_rot)
 
 
 # ---- ragged batches: every sequence brings its own number of new tokens (include/flash_attn_mi355x_decode_ragged.h) ----
@@ -1059,14 +1244,20 @@ def _cache_geometry(k_cache, v_cache, layout, block_table):
     return None, Hkv, k_cache.shape[3], Ncap
 
 
-def ragged_append(k_new, v_new, k_cache, v_cache, cu_seqlens_q, cache_seqlens=None, layout="bnhd", block_table=None):
+def ragged_append(k_new, v_new, k_cache, v_cache, cu_seqlens_q, cache_seqlens=None, layout="bnhd", block_table=None, rotary_cos=None,
+                  rotary_sin=None, rotary_interleaved=False, q_rot=None):
     """Write the packed new tokens' k and v into the caches on the device (fa_mi355x_ragged_append): k_new, v_new (T, Hkv, d_new),
     1 <= d_new <= dp, sequence b's rows cu_seqlens_q[b] .. cu_seqlens_q[b + 1] - 1 (clamped on the device so that no row leaves the
     buffers; a sequence may own none), into caches (B, Ncap, Hkv, dp) / (B, Hkv, Ncap, dp) (``layout`` names the caches' layout only:
     the packed buffers are token-major).  ``cache_seqlens`` COUNTS the new tokens: token i of sequence b goes to row
     clamp(len_b, 0, Ncap) - nq_b + i when that is >= 0, with zeros in columns d_new .. dp-1; every other cache row, and every packed
     row past the last sequence, is left alone.  In place, no host synchronisation.  ``block_table``: the caches are a paged cache's
-    pools, as in decode_append."""
+    pools, as in decode_append.  ``rotary_cos`` / ``rotary_sin`` / ``rotary_interleaved``: k_new is rotated on its way into the K
+    cache, as in decode_append (fa_mi355x_rope_append_ragged without a q; token i of sequence b at position
+    clamp(len_b, 0, Ncap) - nq_b + i); ``q_rot`` must stay None."""
+    rotary = _rotary_of(rotary_cos, rotary_sin, rotary_interleaved, k_cache.device)
+    if q_rot is not None:
+        raise ValueError("q_rot belongs to a call that has a q: an append rotates k_new only")
     pages, Hkv, dp, Ncap = _cache_geometry(k_cache, v_cache, layout, block_table)
     dtype = _dtype_code(k_cache)
     T, d_new = _check_new_ragged(k_new, v_new, k_cache, None, Hkv, dp)
@@ -1079,6 +1270,11 @@ def ragged_append(k_new, v_new, k_cache, v_cache, cu_seqlens_q, cache_seqlens=No
         if t.device != k_cache.device or not t.is_contiguous():
             raise ValueError("k_cache and v_cache must be contiguous and live on one device")
         _require_gpu(t, "ragged_append")
+    if rotary:
+        _check_rot(rotary, dp, d_new)
+        _rope_append(rotary, None, None, k_new, v_new, k_cache, v_cache, None, None, cache_seqlens, cu_seqlens_q, block_table, B, Hkv, Hkv,
+                     T, Ncap, (*pages, block_table.shape[1]) if pages else None, d_new, dp, layout, False, dtype)
+        return
     lib = _lib.decode()
     head = (_ptr(k_new), _ptr(v_new), _ptr(k_cache), _ptr(v_cache), _ptr(cu_seqlens_q), _ptr(cache_seqlens))
     tail = (d_new, dp, _DECODE_LAYOUTS[layout], dtype, _stream_ptr())
@@ -1090,7 +1286,8 @@ def ragged_append(k_new, v_new, k_cache, v_cache, cu_seqlens_q, cache_seqlens=No
 
 
 def flash_attn_ragged(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens=None, causal=True, softmax_scale=None, layout="bnhd", out=None,
-                      lse=None, workspace=None, k_new=None, v_new=None, block_table=None, max_pages=None, window=None, sink=None):
+                      lse=None, workspace=None, k_new=None, v_new=None, block_table=None, max_pages=None, window=None, sink=None,
+                      rotary_cos=None, rotary_sin=None, rotary_interleaved=False, q_rot=None):
     """One attention call over a RAGGED batch (fa_mi355x_fwd_ragged / _fwd_ragged_append and their _paged forms): every sequence
     brings its own number of new tokens -- some decode one, one is part-way through a chunked prefill, some have none.  ``q`` is
     PACKED, (T, H, d): sequence b owns rows cu_seqlens_q[b] .. cu_seqlens_q[b + 1] - 1 (``cu_seqlens_q`` contiguous int32 (B + 1,) on
@@ -1107,10 +1304,16 @@ def flash_attn_ragged(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens=None, cau
     (fa_mi355x_fwd_ragged_window; token i of sequence b sits at len_b - nq_b + i and admits the W keys up to its own position); size
     a workspace with ragged_workspace(..., window=).  ``sink``: attention-sink tokens beside the window, as in flash_attn_decode
     (fa_mi355x_fwd_ragged_sink: the first S positions of each sequence; ragged_workspace(..., window=, sink=)).
+    ``rotary_cos`` / ``rotary_sin`` / ``rotary_interleaved`` / ``q_rot``: rotary embeddings, as in flash_attn_decode
+    (fa_mi355x_rope_append_ragged, then the attend-only ragged call on q_rot; token i of sequence b sits at
+    clamp(len_b, 0, Ncap) - nq_b + i; the rows of q_rot that no sequence owns keep what they held).
     Returns (out fp32 (T, H, d), lse fp32 (H, T)): rows with no admissible key give out = 0, lse = -inf; rows of the unused tail
     keep what they held."""
     window = _check_window(window, causal)
     sink = _check_sink(sink, window)
+    rotary = _rotary_of(rotary_cos, rotary_sin, rotary_interleaved, q.device)
+    if rotary is None and q_rot is not None:
+        raise ValueError("q_rot is where a roped call leaves the rotated q: it needs rotary_cos and rotary_sin")
     if (k_new is None) != (v_new is None):
         raise ValueError("k_new and v_new go together: give both (fused append) or neither")
     pages, Hkv, dp, _ = _cache_geometry(k_cache, v_cache, layout, block_table)
@@ -1155,6 +1358,14 @@ def flash_attn_ragged(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens=None, cau
         lse = torch.empty((H, T), dtype=torch.float32, device=q.device)
     if workspace is None:
         workspace = ragged_workspace(qp, k_cache, cu_seqlens_q, layout, max_pages=mp, window=window, sink=sink)
+    if rotary:   # (the roped append, then the attend-only form of whatever follows, on the rotated q)
+        _check_rot(rotary, d, d_new if k_new is not None else None)
+        qr = _q_rot_buffer(q_rot, q, qp)
+        _rope_append(rotary, qp, qr, k_new, v_new, k_cache, v_cache, None, None, cache_seqlens, cu_seqlens_q, block_table, B, H, Hkv, T, Ncap,
+                     (*pages, mp) if pages else None, d_new if k_new is not None else dp, dp, layout, False, dtype)
+        if q_rot is not None and qr is not q_rot:
+            q_rot.copy_(qr[..., :d])
+        qp, k_new, v_new = qr, None, None
     if window is not None:   # (the family's one windowed entry point: null k_new / v_new attend only, a null table is a slab cache)
         geometry = (0, *pages, mp) if pages else (Ncap, 0, 0, 0)
         fwd, win = (lib.fa_mi355x_fwd_ragged_window, (window,)) if sink is None else (lib.fa_mi355x_fwd_ragged_sink, (window, sink))

@@ -39,7 +39,32 @@ def _expand_kv(t, n_head):
     return t[:, :, :, None, :].expand(B, N, Hkv, n_head // Hkv, d).reshape(B, N, n_head, d)
 
 
-def multi_head_attention(x, wq, wk, wv, wo, n_head: int, causal: bool = True, fused_layout: bool = True, fold_scale: bool = False):
+class Rotary:
+    """The rotary position embedding of a stack: the (cos, sin) tables (contiguous float32 (max_pos, rot / 2) on the stack's device,
+    device_ops.rotary_table or the caller's own), ``interleaved`` (GPT-J pairs (x[2j], x[2j+1]) instead of NeoX / Llama pairs
+    (x[j], x[j + rot/2])) and ``rot`` = the rotary dimension, which may be smaller than the head dim (the other columns pass)."""
+
+    def __init__(self, cos, sin, interleaved: bool = False):
+        if cos is None or sin is None:
+            raise ValueError("Rotary needs both tables, cos and sin")
+        self.rot, self.max_pos, _ = device_ops._check_rotary(cos, sin, getattr(cos, "device", None), interleaved)
+        self.cos, self.sin, self.interleaved = cos, sin, bool(interleaved)
+
+    @classmethod
+    def table(cls, max_pos, rot, base=10000.0, device=None, interleaved: bool = False):
+        return cls(*device_ops.rotary_table(max_pos, rot, base, device), interleaved)
+
+    def keywords(self):
+        """The keywords that make a device_ops KV-cache call a roped one."""
+        return dict(rotary_cos=self.cos, rotary_sin=self.sin, rotary_interleaved=self.interleaved)
+
+    def apply(self, t, seqlen_offsets=None):
+        """t (B, N, heads, d) rotated at positions seqlen_offsets[b] + i (None: i); differentiable."""
+        return device_ops.apply_rotary(t, self.cos, self.sin, seqlen_offsets, self.interleaved)
+
+
+def multi_head_attention(x, wq, wk, wv, wo, n_head: int, causal: bool = True, fused_layout: bool = True, fold_scale: bool = False,
+                         rope=None):
     """MultiHeadAttention.forward (modules_transfomer.py:141-157).  x: (B, N, E); wq, wo: (E, E); wk, wv: (E, E), or (E, Hkv * d) for
     grouped-query heads (Hkv divides n_head, d = E // n_head; query head h reads kv head h // (n_head // Hkv)).  With ``fused_layout``
     the kernels read the Hkv heads of k and v in place, forward and backward (device_ops.flash_attn_gqa: no expanded copy, and the
@@ -48,10 +73,14 @@ def multi_head_attention(x, wq, wk, wv, wo, n_head: int, causal: bool = True, fu
     Bias-free, as the reference's ``Linear(..., bias=False)`` projections (:40-52).
     ``fold_scale`` (with ``fused_layout``): log2(e)/sqrt(d) is folded into the query projection's weights and the operator is called
     with softmax_scale = ln 2 -- the same function of x, but the bf16 MFMA-slot kernels' folded scale is then exactly 1: no extra
-    operand rounding whatever the magnitude of the activations (DESIGN.md section 3 "Scaling")."""
+    operand rounding whatever the magnitude of the activations (DESIGN.md section 3 "Scaling").
+    ``rope`` (a Rotary): q and k are rotated by position (token i at position i) between the projection and the operator
+    (device_ops.apply_rotary, whose backward is the inverse rotation: the path is trainable)."""
     B, N, E = x.shape
     if fused_layout:
         q, k, v = _project(x, wq * (LOG2E / (E // n_head) ** 0.5) if fold_scale else wq, wk, wv, n_head)
+        if rope is not None:
+            q, k = rope.apply(q), rope.apply(k)
         if k.shape[2] == n_head:
             o = _attention(q, k, v, causal, _lib.FA_LAYOUT_BNHD, LN2 if fold_scale else None)   # (B, N, H, d) fp32: already merged
         else:   # grouped-query heads: k and v stay (B, N, Hkv, d)
@@ -59,17 +88,20 @@ def multi_head_attention(x, wq, wk, wv, wo, n_head: int, causal: bool = True, fu
         merged = o.reshape(B * N, E)
     else:
         q, k, v = _project(x, wq, wk, wv, n_head)
+        if rope is not None:
+            q, k = rope.apply(q), rope.apply(k)
         q, k, v = (t.permute(0, 2, 1, 3).contiguous() for t in (q, _expand_kv(k, n_head), _expand_kv(v, n_head)))
         o = _attention(q, k, v, causal, _lib.FA_LAYOUT_BHND)                                  # (B, H, N, d)
         merged = o.permute(0, 2, 1, 3).contiguous().view(B * N, E)
     return (merged.to(x.dtype) @ wo).view(B, N, E)
 
 
-def attention_stack(x, layers, n_head: int, causal: bool = True, fused_layout: bool = True, fold_scale: bool = False):
+def attention_stack(x, layers, n_head: int, causal: bool = True, fused_layout: bool = True, fold_scale: bool = False, rope=None):
     """x <- x + MultiHeadAttention_l(x) for every (wq, wk, wv, wo) in ``layers``: the attention data flow of the reference's
-    4-layer causal DecoderLM (modules_transfomer.py:255-351) without its out-of-scope LayerNorm / FFN blocks."""
+    4-layer causal DecoderLM (modules_transfomer.py:255-351) without its out-of-scope LayerNorm / FFN blocks.  ``rope``: every
+    layer rotates its q and k (multi_head_attention)."""
     for (wq, wk, wv, wo) in layers:
-        x = x + multi_head_attention(x, wq, wk, wv, wo, n_head, causal, fused_layout, fold_scale)
+        x = x + multi_head_attention(x, wq, wk, wv, wo, n_head, causal, fused_layout, fold_scale, rope)
     return x
 
 
@@ -87,6 +119,10 @@ def attention_stack(x, layers, n_head: int, causal: bool = True, fused_layout: b
 # A cache built with kv_dtype=torch.float8_e4m3fn holds e4m3 bytes with one scale per (layer, kv head): the fused step, extend and
 # chunked-prefill functions and GraphedStep pass the layer's scales (cache.quant(li)) to the same device_ops calls, which quantise on
 # the append; a prompt fills the cache through extend_append while its own attention stays the square forward on the unquantised k, v.
+# A cache built with rope=Rotary(...) encodes positions with rotary embeddings: rotary() carries the tables to every fused step,
+# extend, ragged and chunked-prefill call and to GraphedStep (one fa_mi355x_rope_append launch per layer rotates q and the new k on
+# their way in, then the attend-only call runs); the square prefill and the unfused step rotate q and k with apply_rotary.  The
+# cache holds ROTATED keys.
 
 MAX_STEP_TOKENS = 128   # fa_mi355x_fwd_decode's largest Nq; longer inputs are prefill, or attention_stack_extend after a prefix
 
@@ -103,6 +139,19 @@ def _check_cache_sink(sink, window):
     if sink and window is None:
         raise ValueError("sink tokens stand beside a sliding window: sink= needs window=")
     return sink or None
+
+
+def _check_cache_rope(rope, rows, head_dim):
+    """``rope`` of a cache that can hold ``rows`` rows per sequence: every row needs an angle."""
+    if rope is None:
+        return None
+    if not isinstance(rope, Rotary):
+        raise TypeError("rope must be None or a Rotary")
+    if rope.max_pos < rows:
+        raise ValueError(f"the rotary tables hold max_pos = {rope.max_pos} positions, the cache {rows} rows: max_pos must cover the capacity")
+    if rope.rot > head_dim:
+        raise ValueError(f"the rotary dimension {rope.rot} exceeds the head dim {head_dim}")
+    return rope
 
 
 def _check_cache_quant(kv_dtype, kv_scale, dtype, window, n_layers, n_kv_head, device):
@@ -142,10 +191,13 @@ class KVCache:
     reads, and ``kv_scale`` (None: ones, or a pair (k_scale, v_scale) of float32 (n_layers, n_kv_head) tensors) gives every layer's
     per-head scales: a cached element is scale * e4m3.  The stack must be bfloat16; the fused step, extend and chunked-prefill
     functions and GraphedStep quantise on the append; attention_stack_step (torch indexing), attention_stack_ragged, a window
-    and sink tokens are not built for it."""
+    and sink tokens are not built for it.
+    ``rope`` (None, or a Rotary whose tables cover the capacity): the stack encodes positions with ROTARY embeddings; the stack
+    functions rotate every q and every new k by its position (the row it is appended to), and the cache holds rotated keys."""
 
     def __init__(self, n_layers, B, capacity, n_head, head_dim, dtype, device, n_kv_head=None, window=None, kv_dtype=None, kv_scale=None,
-                 sink=None):
+                 sink=None, rope=None):
+        self.rope = _check_cache_rope(rope, capacity, head_dim)
         self.window = _check_cache_window(window)
         self.sink = _check_cache_sink(sink, self.window)
         self.head_dim, self.dp = head_dim, device_ops.padded_head_dim(head_dim)
@@ -162,6 +214,11 @@ class KVCache:
         self._workspaces = {}
 
     block_table = None   # (a PagedKVCache has one)
+    rope = None
+
+    def rotary(self):
+        """The keywords that make a device_ops call a roped one: none for a cache without rotary embeddings."""
+        return {} if self.rope is None else self.rope.keywords()
 
     def paging(self):
         """The keyword that makes a device_ops call a paged one: none for this cache, block_table= for a PagedKVCache."""
@@ -228,7 +285,7 @@ class PagedKVCache(KVCache):
     read.  Without sinks sink_pages = 0 and this is the rule above."""
 
     def __init__(self, n_layers, B, capacity, n_head, head_dim, dtype, device, n_kv_head=None, page_size=128, n_pages=None, window=None,
-                 kv_dtype=None, kv_scale=None, sink=None):
+                 kv_dtype=None, kv_scale=None, sink=None, rope=None):
         self.window = _check_cache_window(window)
         self.sink = _check_cache_sink(sink, self.window)
         self.head_dim, self.dp = head_dim, device_ops.padded_head_dim(head_dim)
@@ -241,6 +298,7 @@ class PagedKVCache(KVCache):
         if capacity <= 0:
             raise ValueError("capacity must be positive")
         self.page_size, self.max_pages = page_size, -(-capacity // page_size)
+        self.rope = _check_cache_rope(rope, self.max_pages * page_size, head_dim)   # (the library holds max_pos against the table's rows)
         self.sink_pages = -(-(self.sink or 0) // page_size)   # leading table slots that release_behind_window keeps
         self.n_pages = B * self.max_pages if n_pages is None else n_pages
         if self.n_pages <= 0:
@@ -350,6 +408,8 @@ def attention_stack_prefill(x, layers, n_head: int, cache: KVCache):
     for li, (wq, wk, wv, wo) in enumerate(layers):
         q, k, v = _project(x, wq, wk, wv, n_head)
         _check_kv_heads(k, cache)
+        if cache.rope is not None:   # (token i of the prompt sits at position i; the cache is filled with the rotated k)
+            q, k = cache.rope.apply(q), cache.rope.apply(k)
         kp, vp = cache._pad(k), cache._pad(v)
         if cache.block_table is None and not cache.fp8:
             cache.k[li][:, :P] = kp
@@ -395,8 +455,10 @@ def _step(x_new, layers, n_head: int, cache: KVCache, fused: bool):
         _check_kv_heads(k, cache)
         new = {}
         if fused:   # the library writes k and v at rows new_len[b] - T .. new_len[b] - 1 (zero columns past head_dim), then attends
-            new = dict(k_new=k, v_new=v)
+            new = dict(k_new=k, v_new=v, **cache.rotary())   # (a roped cache: q and k rotated on their way in, at those rows' positions)
         else:
+            if cache.rope is not None:   # (token t of batch element b sits at position lengths[b] + t)
+                q, k = cache.rope.apply(q, cache.lengths), cache.rope.apply(k, cache.lengths)
             hkv = cache.n_kv_head
             for dst, t in ((cache.k[li], k), (cache.v[li], v)):
                 dst.view(B * cache.capacity, hkv, cache.dp).index_copy_(0, rows, cache._pad(t).reshape(B * T, hkv, cache.dp))
@@ -445,7 +507,7 @@ def attention_stack_extend(x_new, layers, n_head: int, cache: KVCache):
         _check_kv_heads(k, cache)
         o, _ = device_ops.flash_attn_extend(q, cache.k[li], cache.v[li], new_len, causal=True, layout="bnhd",
                                             workspace=cache.extend_workspace(q), k_new=k, v_new=v, **cache.paging(), **cache.windowing(),
-                                            **cache.quant(li))
+                                            **cache.quant(li), **cache.rotary())
         x = x + (o.reshape(B * T, E).to(x.dtype) @ wo).view(B, T, E)
     cache.lengths.copy_(new_len)
     cache.length_bound += T
@@ -485,7 +547,7 @@ def attention_stack_ragged(x_new, counts, layers, n_head: int, cache: KVCache):
             raise ValueError(f"the layers project {k.shape[1]} kv heads, the cache holds {cache.n_kv_head}")
         o, _ = device_ops.flash_attn_ragged(q, cache.k[li], cache.v[li], cu, new_len, causal=True, layout="bnhd",
                                             workspace=cache.ragged_workspace(q, cu), k_new=k, v_new=v, **cache.paging(),
-                                            **cache.windowing())
+                                            **cache.windowing(), **cache.rotary())
         x = x + o.reshape(T, E).to(x.dtype) @ wo
     cache.lengths.copy_(new_len)
     cache.length_bound += top

@@ -165,4 +165,8 @@ const char* fa_mi355x_decode_last_error(void);
  * calls: nine entry points, part of this library and of this header, kept in a file of their own. */
 #include "flash_attn_mi355x_decode_sink.h"
 
+/* Rotary position embeddings: a tensor rotated by position, and the fused rotate-and-append that goes in front of the attend-only
+ * entry points above, uniform and ragged: three entry points, part of this library and of this header, kept in a file of their own. */
+#include "flash_attn_mi355x_decode_rope.h"
+
 #endif /* FLASH_ATTN_MI355X_DECODE_H */

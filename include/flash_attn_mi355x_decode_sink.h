@@ -28,7 +28,7 @@ extern "C" {
  *                workspace and bits.  The device therefore only ever computes with 1 <= W < Ncap and 1 <= S < Ncap.
  *   causal only  window > 0 with causal = 0 is FA_ERR_BAD_ARG, the window's own check.
  *   Sinks are a mask on the logical rows of the cache.  NOT built: sinks on an fp8 cache; learned sink logits (gpt-oss); a
- *   re-assignment of positions inside the cache (StreamingLLM's other half: this stack has no rotary embedding); a ring-buffer cache;
+ *   re-assignment of positions inside the cache (StreamingLLM's other half: the rotary calls of _rope.h keep a token's position); a ring-buffer cache;
  *   a window or sinks in the training forward and backward.
  *
  * One entry point per call family, each with the arguments of its windowed form and `sink` directly after `window`; k_new / v_new
