@@ -31,6 +31,15 @@ else
   echo "[compile_cuda.sh] $DECODE is up to date"
 fi
 
+# Sliding-window / attention-sink forward and backward (include/flash_attn_mi355x_window.h): a third library, for the same reason
+WINDOW="$OUT_DIR/libflash_attn_mi355x_window.so"
+if stale "$WINDOW"; then
+  echo "[compile_cuda.sh] hipcc --offload-arch=$ARCH  fa_window.hip -> $WINDOW"
+  "$HIPCC" "${FLAGS[@]}" "$SRC/fa_window.hip" -o "$WINDOW"
+else
+  echo "[compile_cuda.sh] $WINDOW is up to date"
+fi
+
 shim() {  # name variant FW|BW
   "$HIPCC" -O2 -fPIC -shared -x c++ "$SRC/fa_shim.cpp" -DFA_SHIM_VARIANT="$2" -DFA_SHIM_"$3" \
       -L"$OUT_DIR" -lflash_attn_mi355x -Wl,-rpath,'$ORIGIN' -o "$OUT_DIR/$1.so"

@@ -188,6 +188,15 @@ ROPE_ABI = {
     "fa_mi355x_rope_append_ragged": (_i, [_vp] * 11 + [_i] * 15 + [_vp]),
 }
 
+# the same for include/flash_attn_mi355x_window.h: libflash_attn_mi355x_window.so, the sliding-window / attention-sink forward and
+# backward of the training side (tests/test_window_train_cpu.py).  WINDOW_ABI above is the decode library's windowed family.
+WINDOW_TRAIN_ABI = {
+    "fa_mi355x_fwd_window": (_i, [_vp] * 5 + [_i] * 6 + [_f, _i, _i, _i, _vp]),
+    "fa_mi355x_bwd_window_workspace_bytes": (_sz, [_i] * 5),
+    "fa_mi355x_bwd_window": (_i, [_vp] * 10 + [_i] * 6 + [_f, _i, _i, _i, _vp]),
+    "fa_mi355x_window_last_error": (_s, []),
+}
+
 
 def _typed(name: str, abi: dict) -> ctypes.CDLL:
     """The library with restype / argtypes of every symbol in ``abi`` set (once, on first load)."""
@@ -264,3 +273,16 @@ def decode() -> ctypes.CDLL:
 def decode_check(status: int) -> None:
     if status != FA_OK:
         _raise(status, decode(), "fa_mi355x_decode_last_error", "flash_attn_mi355x_decode")
+
+
+WINDOW_NAME = "libflash_attn_mi355x_window.so"
+
+
+def window() -> ctypes.CDLL:
+    """libflash_attn_mi355x_window.so (include/flash_attn_mi355x_window.h) with argtypes set."""
+    return _typed(WINDOW_NAME, WINDOW_TRAIN_ABI)
+
+
+def window_check(status: int) -> None:
+    if status != FA_OK:
+        _raise(status, window(), "fa_mi355x_window_last_error", "flash_attn_mi355x_window")

@@ -547,9 +547,13 @@ class _FlashAttnGqaFn(torch.autograd.Function):
         return dq.to(q.dtype), dk.to(q.dtype), dv.to(q.dtype), None, None, None
 
 
-def flash_attn_gqa(q, k, v, causal=False, softmax_scale=None, layout="bnhd"):
+def flash_attn_gqa(q, k, v, causal=False, softmax_scale=None, layout="bnhd", window=None, sink=None):
     """Attention with grouped-query heads under autograd (FA-2): out fp32 in q's shape; q.grad in q's shape and dtype, k.grad and
-    v.grad in k's."""
+    v.grad in k's.  ``window`` = W (with ``sink`` = S): row i admits key j iff j <= i and (j > i - W or j < S), the mask of the
+    KV-cache calls, through the kernels of libflash_attn_mi355x_window.so; None or 0, W >= N or S >= N is this call without them."""
+    ws = _training_window(window, sink, causal, q.shape[1 if layout == "bnhd" else 2] if q.dim() == 4 else 0)
+    if ws is not None:
+        return _FlashAttnWindowFn.apply(q, k, v, softmax_scale, layout, *ws)
     return _FlashAttnGqaFn.apply(q, k, v, bool(causal), softmax_scale, layout)
 
 
@@ -652,6 +656,96 @@ def _check_sink(sink, window):
     if sink > 0 and window is None:
         raise ValueError("sink tokens stand beside a sliding window: sink= needs window=")
     return sink or None
+
+
+# ---- sliding window and attention sinks in the training forward and backward: fa_mi355x_fwd_window / _bwd_window ------------------
+# The mask of the KV-cache calls below with the query of row i at position i: row i admits key j iff j <= i and (j > i - W or j < S).
+# Kernels of their own in a library of their own (libflash_attn_mi355x_window.so); they scale in fp32: no guard, no opts.  FA-2 side
+# output (lse) only; no key mask, no dropout.
+
+def _training_window(window, sink, causal, N):
+    """(W, S) when a call over N positions is a windowed one, None when it is the unwindowed call: window None or 0, W >= N or
+    S >= N."""
+    window = _check_window(window, causal)
+    sink = _check_sink(sink, window)
+    if not window or window >= N or (sink or 0) >= N:
+        return None
+    return window, sink or 0
+
+
+def _check_window_call(window, sink):
+    """``window`` and ``sink`` of the windowed entry points themselves: W >= 1, S >= 0 (larger than N: clamped by the library)."""
+    window = _check_window(window)
+    sink = _check_sink(sink, window)
+    if not window:
+        raise ValueError("the windowed call needs window >= 1 (flash_attn_fwd_gqa is the call without a window)")
+    return window, sink or 0
+
+
+def bwd_workspace_window(q, k, layout="bnhd"):
+    """Scratch for flash_attn_bwd_window with these tensors (fa_mi355x_bwd_window_workspace_bytes): as bwd_workspace_gqa."""
+    B, H, Hkv, N, d, _ = _check_gqa(layout, q, k, k)
+    nbytes = _lib.window().fa_mi355x_bwd_window_workspace_bytes(B, H, Hkv, N, d)
+    return torch.empty((nbytes + 3) // 4, dtype=_F32, device=q.device)
+
+
+def flash_attn_fwd_window(q, k, v, window, sink=None, softmax_scale=None, layout="bnhd", out=None):
+    """Causal forward under a sliding window of ``window`` positions and ``sink`` first positions, grouped-query heads as
+    flash_attn_fwd_gqa.  Returns (out fp32 in q's shape, lse (B, H, N))."""
+    window, sink = _check_window_call(window, sink)
+    B, H, Hkv, N, d, dtype = _check_gqa(layout, q, k, v)
+    if out is not None and (out.dtype is not _F32 or out.shape != q.shape or not out.is_contiguous() or out.get_device() != q.get_device()):
+        raise ValueError("out must be a contiguous float32 tensor of q's shape")
+    lse = torch.empty((B, H, N), dtype=_F32, device=q.device)
+    if out is None:
+        out = torch.empty(q.shape, dtype=_F32, device=q.device)
+    _lib.window_check(_lib.window().fa_mi355x_fwd_window(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), B, H, Hkv, N, d,
+                                                         _DECODE_LAYOUTS[layout], float(softmax_scale or 0.0), window, sink, dtype,
+                                                         _stream_ptr()))
+    return out, lse
+
+
+def flash_attn_bwd_window(q, k, v, out, out_grad, lse, window, sink=None, softmax_scale=None, layout="bnhd", workspace=None, grads=None):
+    """Backward of flash_attn_fwd_window.  Returns (dq in q's shape, dk, dv in k's shape), fp32; no atomics, the same bits on every
+    run.  ``workspace``: bwd_workspace_window(q, k, layout); ``grads``: (dq, dk, dv) buffers to write into."""
+    window, sink = _check_window_call(window, sink)
+    B, H, Hkv, N, d, dtype = _check_gqa(layout, q, k, v, out, out_grad)
+    lib, dev = _lib.window(), q.get_device()
+    _check_buffer(lse, dev, "lse", B * H * N)
+    if workspace is not None:
+        if workspace.numel() * workspace.element_size() < lib.fa_mi355x_bwd_window_workspace_bytes(B, H, Hkv, N, d):
+            raise ValueError("workspace too small: size it with bwd_workspace_window(q, k, layout)")
+        if not workspace.is_contiguous() or workspace.get_device() != dev or workspace.data_ptr() % 256:
+            raise ValueError("workspace must be a contiguous, 256-byte aligned tensor on q's device")
+    if grads is not None:
+        for g, like in zip(grads, (q, k, v)):
+            _check_buffer(g, dev, "each of grads", like.numel())
+    if workspace is None:
+        workspace = bwd_workspace_window(q, k, layout)
+    dq, dk, dv = grads or (torch.empty(t.shape, dtype=_F32, device=q.device) for t in (q, k, v))
+    _lib.window_check(lib.fa_mi355x_bwd_window(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(out_grad), _ptr(dq), _ptr(dk), _ptr(dv),
+                                               _ptr(lse), _ptr(workspace), B, H, Hkv, N, d, _DECODE_LAYOUTS[layout],
+                                               float(softmax_scale or 0.0), window, sink, dtype, _stream_ptr()))
+    return dq, dk, dv
+
+
+class _FlashAttnWindowFn(torch.autograd.Function):
+    """flash_attn_gqa under a sliding window (and sink tokens): the forward saves q, the unexpanded k and v, o and lse; gradients are
+    cast to the input dtype."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, softmax_scale, layout, window, sink):
+        o, lse = flash_attn_fwd_window(q, k, v, window, sink, softmax_scale, layout)
+        ctx.save_for_backward(q, k, v, o, lse)
+        ctx.args = softmax_scale, layout, window, sink
+        return o
+
+    @staticmethod
+    def backward(ctx, out_grad):
+        q, k, v, o, lse = ctx.saved_tensors
+        softmax_scale, layout, window, sink = ctx.args
+        dq, dk, dv = flash_attn_bwd_window(q, k, v, o, out_grad.to(q.dtype).contiguous(), lse, window, sink, softmax_scale, layout)
+        return dq.to(q.dtype), dk.to(q.dtype), dv.to(q.dtype), None, None, None, None
 
 
 def decode_workspace(q, k_cache, layout="bnhd", block_table=None, max_pages=None, window=None, sink=None):

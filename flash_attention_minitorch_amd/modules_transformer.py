@@ -64,7 +64,7 @@ class Rotary:
 
 
 def multi_head_attention(x, wq, wk, wv, wo, n_head: int, causal: bool = True, fused_layout: bool = True, fold_scale: bool = False,
-                         rope=None):
+                         rope=None, window=None, sink=None):
     """MultiHeadAttention.forward (modules_transfomer.py:141-157).  x: (B, N, E); wq, wo: (E, E); wk, wv: (E, E), or (E, Hkv * d) for
     grouped-query heads (Hkv divides n_head, d = E // n_head; query head h reads kv head h // (n_head // Hkv)).  With ``fused_layout``
     the kernels read the Hkv heads of k and v in place, forward and backward (device_ops.flash_attn_gqa: no expanded copy, and the
@@ -75,13 +75,19 @@ def multi_head_attention(x, wq, wk, wv, wo, n_head: int, causal: bool = True, fu
     with softmax_scale = ln 2 -- the same function of x, but the bf16 MFMA-slot kernels' folded scale is then exactly 1: no extra
     operand rounding whatever the magnitude of the activations (DESIGN.md section 3 "Scaling").
     ``rope`` (a Rotary): q and k are rotated by position (token i at position i) between the projection and the operator
-    (device_ops.apply_rotary, whose backward is the inverse rotation: the path is trainable)."""
+    (device_ops.apply_rotary, whose backward is the inverse rotation: the path is trainable).
+    ``window`` = W, ``sink`` = S: the sliding-window mask a KVCache(window=W, sink=S) generates under (token i sees the last W
+    positions and the first S), forward and backward (device_ops.flash_attn_gqa(window=, sink=)); the rotation comes first, as
+    without a window.  None or 0, W >= N or S >= N: the layer without them."""
     B, N, E = x.shape
+    windowed = device_ops._training_window(window, sink, causal, N) is not None
     if fused_layout:
         q, k, v = _project(x, wq * (LOG2E / (E // n_head) ** 0.5) if fold_scale else wq, wk, wv, n_head)
         if rope is not None:
             q, k = rope.apply(q), rope.apply(k)
-        if k.shape[2] == n_head:
+        if windowed:   # grouped or not: k and v stay (B, N, Hkv, d)
+            o = device_ops.flash_attn_gqa(q, k, v, causal, LN2 if fold_scale else None, "bnhd", window, sink)
+        elif k.shape[2] == n_head:
             o = _attention(q, k, v, causal, _lib.FA_LAYOUT_BNHD, LN2 if fold_scale else None)   # (B, N, H, d) fp32: already merged
         else:   # grouped-query heads: k and v stay (B, N, Hkv, d)
             o = device_ops.flash_attn_gqa(q, k, v, causal, LN2 if fold_scale else None, "bnhd")
@@ -91,17 +97,22 @@ def multi_head_attention(x, wq, wk, wv, wo, n_head: int, causal: bool = True, fu
         if rope is not None:
             q, k = rope.apply(q), rope.apply(k)
         q, k, v = (t.permute(0, 2, 1, 3).contiguous() for t in (q, _expand_kv(k, n_head), _expand_kv(v, n_head)))
-        o = _attention(q, k, v, causal, _lib.FA_LAYOUT_BHND)                                  # (B, H, N, d)
+        if windowed:
+            o = device_ops.flash_attn_gqa(q, k, v, causal, None, "bhnd", window, sink)
+        else:
+            o = _attention(q, k, v, causal, _lib.FA_LAYOUT_BHND)                              # (B, H, N, d)
         merged = o.permute(0, 2, 1, 3).contiguous().view(B * N, E)
     return (merged.to(x.dtype) @ wo).view(B, N, E)
 
 
-def attention_stack(x, layers, n_head: int, causal: bool = True, fused_layout: bool = True, fold_scale: bool = False, rope=None):
+def attention_stack(x, layers, n_head: int, causal: bool = True, fused_layout: bool = True, fold_scale: bool = False, rope=None,
+                    window=None, sink=None):
     """x <- x + MultiHeadAttention_l(x) for every (wq, wk, wv, wo) in ``layers``: the attention data flow of the reference's
     4-layer causal DecoderLM (modules_transfomer.py:255-351) without its out-of-scope LayerNorm / FFN blocks.  ``rope``: every
-    layer rotates its q and k (multi_head_attention)."""
+    layer rotates its q and k (multi_head_attention).  ``window``, ``sink``: every layer attends under the sliding-window mask of a
+    KVCache(window=, sink=), so a model that generates through such a cache trains under the mask it runs with."""
     for (wq, wk, wv, wo) in layers:
-        x = x + multi_head_attention(x, wq, wk, wv, wo, n_head, causal, fused_layout, fold_scale, rope)
+        x = x + multi_head_attention(x, wq, wk, wv, wo, n_head, causal, fused_layout, fold_scale, rope, window, sink)
     return x
 
 

@@ -29,7 +29,7 @@ extern "C" {
  *   causal only  window > 0 with causal = 0 is FA_ERR_BAD_ARG, the window's own check.
  *   Sinks are a mask on the logical rows of the cache.  NOT built: sinks on an fp8 cache; learned sink logits (gpt-oss); a
  *   re-assignment of positions inside the cache (StreamingLLM's other half: the rotary calls of _rope.h keep a token's position); a ring-buffer cache;
- *   a window or sinks in the training forward and backward.
+ *   (The training forward and backward under this mask are flash_attn_mi355x_window.h, a library of its own.)
  *
  * One entry point per call family, each with the arguments of its windowed form and `sink` directly after `window`; k_new / v_new
  * (both NULL: attend only) and block_table (NULL: slab caches) are optional as there.  Every argument check of the windowed forms

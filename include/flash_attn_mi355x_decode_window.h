@@ -30,7 +30,7 @@ extern "C" {
  *   append       is untouched: new token i goes to row L_b - Nq + i.  A fused call appends first, then attends through the window.
  *   A ring-buffer cache of W rows is NOT what this is: the cache keeps logical rows 0 .. L_b - 1; memory is saved by releasing pages
  *   (below).  Attention-sink tokens beside the window are flash_attn_mi355x_decode_sink.h.  A window on an fp8 cache is out of
- *   scope, and the training forward and backward have none.
+ *   scope.  The training forward and backward under this mask: flash_attn_mi355x_window.h (a library of its own).
  *
  * One entry point per call family.  Each takes, beyond the arguments of its family (flash_attn_mi355x_decode.h, _ragged.h):
  *   k_new, v_new   both NULL: attend only.  Both given: the family's append in front of the attention, one call (d_new as there;
