@@ -1,15 +1,19 @@
-// C ABI of the MI355X KV-cache decode library (declared in include/flash_attn_mi355x_decode.h, its _paged.h and its _ragged.h):
-// argument checks, the split policies (decode: 32-row blocks, at most 128 queries; extend: 128-row blocks, any number; ragged: the
-// extend policy on an upper bound of the row blocks) and the launches of the kernels of fa_decode.h.  A paged call (a pool and a
-// block table) takes the contiguous call's policy at Ncap = max_pages * page_size.  A windowed call (_window.h) takes the three
-// policies on its window span (span_keys) instead of Ncap, a sink call (_sink.h) on that span plus its sink tiles.  An fp8 call (_fp8.h: caches of e4m3 bytes, per-kv-head scales) takes the
-// bf16 call's policy and workspace for the same arguments; its cache bounds count one byte per element.  The rotary calls (_rope.h)
-// launch the kernels of fa_rope.h in front of the attend-only entry points.
+// C ABI of the MI355X KV-cache decode library (declared in include/flash_attn_mi355x_decode.h and its _paged.h, _ragged.h,
+// _window.h, _sink.h, _fp8.h and _rope.h).  Every entry point fills one KvCall (the call as it was received) and hands it to run():
+// the entry point's prelude (check_fp8 or check_window), the page geometry (check_pages), the attention's checks (check_attend, which
+// also returns the call's Policy), the append's (check_append), then the append launch (run_append) and the attention's launches
+// (run_attend -> launch_split).  policy() is the one split policy: the three families (decode: 32-row blocks, at most 128 queries;
+// extend: 128-row blocks, any number; ragged: the extend policy on an upper bound of the row blocks) differ by the data of FAMILIES.
+// A paged call (a pool and a block table) takes the contiguous call's policy at Ncap = max_pages * page_size.  A windowed call takes
+// the policy on its window span (span_keys) instead of Ncap, a sink call on that span plus its sink tiles.  An fp8 call (caches of
+// e4m3 bytes, per-kv-head scales) takes the bf16 call's policy and workspace for the same arguments; its cache bounds count one byte
+// per element.  The rotary calls launch the kernels of fa_rope.h in front of the attend-only entry points.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 #include <algorithm>
 #include <stdio.h>
+#include <type_traits>
 
 #include "../../include/flash_attn_mi355x_decode.h"
 #include "fa_decode.h"
@@ -19,77 +23,125 @@ namespace {
 
 thread_local char g_err[512] = "";
 
-int set_err(int code, const char* what, hipError_t e = hipSuccess) {
-  if (e != hipSuccess)
-    snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
-  else
-    snprintf(g_err, sizeof(g_err), "%s", what);
+int set_err(int code, const char* what) {
+  snprintf(g_err, sizeof(g_err), "%s", what);
   return code;
 }
 
-// Split policy (DESIGN.md "Decode"): enough (batch*kv head, chunk, row block) workgroups to cover a 256-CU chip four times, chunks a
-// multiple of 256 keys (two super tiles) and at least 256 keys.  A kv head has G*Nq rows (G = H / Hkv query heads per kv head), 32 to
-// a block.  Launches that already have 1024 workgroups without splitting run as one split.  The chip size is assumed, not queried,
-// so the split count is a function of the arguments alone.
-constexpr int DEC_CUS = 256, DEC_WAVES = 4, DEC_MIN_CHUNK = 256;
-
-// (positive sizes and H a multiple of Hkv: what the two size queries need to answer at all)
-bool sizes_ok(int B, int H, int Hkv, int Nq, int Ncap, int d) {
-  return B > 0 && H > 0 && Hkv > 0 && Nq > 0 && Ncap > 0 && d > 0 && H % Hkv == 0;
+int hip_err(const char* what, hipError_t e) {
+  snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
+  return FA_ERR_HIP;
 }
 
-int row_blocks(int H, int Hkv, int Nq) { return (int)(((long)(H / Hkv) * Nq + 31) / 32); }
+// What the three call families do differently, as data: the split policy's two figures, and the messages that name a family's
+// arguments or its size query (null: the family has no such check).
+enum Family { DECODE, EXTEND, RAGGED };
 
-int chunk_keys(int B, int H, int Hkv, int Nq, int Ncap) {
-  const long groups = (long)B * Hkv * row_blocks(H, Hkv, Nq);
-  const long want = std::max(1L, (DEC_CUS * DEC_WAVES + groups - 1) / groups);
-  const long per = (Ncap + want - 1) / want;
-  return (int)std::max((long)DEC_MIN_CHUNK, (per + DEC_MIN_CHUNK - 1) / DEC_MIN_CHUNK * DEC_MIN_CHUNK);
-}
+struct FamilyRule {
+  int block_rows, waves;   // rows of a workgroup's row block; workgroups per CU the split aims at
+  const char *sizes, *append_sizes, *rows, *q_bytes, *grid, *workspace, *split_launch, *combine_launch;
+};
 
-int splits(int B, int H, int Hkv, int Nq, int Ncap) {
-  const int ch = chunk_keys(B, H, Hkv, Nq, Ncap);
-  return (int)(((long)Ncap + ch - 1) / ch);
-}
+// Extend: a workgroup of extend_split_kernel owns 128 rows, and TWO workgroups per CU are the target: a workgroup there lives for a
+// long key loop, so a second round of workgroups buys nothing, while every split costs a partial per row and the combine launch
+// over B*H*Nq rows (measured: profiles/extend_bench.txt).
+constexpr FamilyRule FAMILIES[3] = {
+    {32, 4, "B, H, Nq, Ncap and d must be positive", "B, Hkv, Nq, Ncap and d must be positive", nullptr,
+     "one batch element of q must stay under 2 GiB", nullptr, "null workspace: this call needs fa_mi355x_decode_workspace_bytes() bytes",
+     "decode_split_kernel launch", "decode_combine_kernel launch"},
+    {fa::EXT_BLOCK, 2, "B, H, Nq, Ncap and d must be positive", "B, Hkv, Nq, Ncap and d must be positive",
+     "G * Nq rows per kv head must stay under 2^25", "one batch element of q must stay under 2 GiB",
+     "too many workgroups for one launch: B * Hkv * splits * row blocks and B * H * Nq must fit an unsigned int",
+     "null workspace: this call needs fa_mi355x_extend_workspace_bytes() bytes", "extend_split_kernel launch",
+     "decode_combine_kernel launch"},
+    {fa::EXT_BLOCK, 2, "B, H, T, Ncap and d must be positive", "B, Hkv, T, Ncap and d must be positive",
+     "G * T rows per kv head must stay under 2^25", "q (T * H * d elements) must stay under 2 GiB",
+     "too many workgroups for one launch: Hkv * splits * row blocks and H * T must fit an unsigned int",
+     "null workspace: a ragged call always needs fa_mi355x_ragged_workspace_bytes() bytes (the block map)",
+     "extend_split_kernel (ragged) launch", "decode_combine_kernel (ragged) launch"},
+};
 
-size_t workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int d) {
-  const int ns = splits(B, H, Hkv, Nq, Ncap);
-  return ns == 1 ? 0 : (size_t)B * H * ns * Nq * (size_t)(d + 2) * sizeof(float);
-}
+// A paged call's block table and pool geometry (all zero in the contiguous call).
+struct Paging {
+  const int* table;
+  int num_pages, page_size, max_pages;
+};
 
-// Extend policy: the same with 128-row blocks (a workgroup of extend_split_kernel owns 128 rows): groups = B * Hkv * ceil(G*Nq / 128),
-// and TWO workgroups per CU as the target: a workgroup here lives for a long key loop, so a second round of workgroups buys nothing,
-// while every split costs a partial per row and the combine launch over B*H*Nq rows (measured: profiles/extend_bench.txt).
-constexpr int EXT_WAVES = 2;
-int ext_row_blocks(int H, int Hkv, int Nq) { return (int)(((long)(H / Hkv) * Nq + fa::EXT_BLOCK - 1) / fa::EXT_BLOCK); }
+// An fp8 call's scales (either may be null: all ones); on false: a bf16 or fp32 cache.
+struct Fp8 {
+  bool on;
+  const float* k_scale;
+  const float* v_scale;
+};
 
-int ext_chunk_for(long groups, int Ncap) {
-  const long want = std::max(1L, (DEC_CUS * EXT_WAVES + groups - 1) / groups);
-  const long per = (Ncap + want - 1) / want;
-  return (int)std::max((long)DEC_MIN_CHUNK, (per + DEC_MIN_CHUNK - 1) / DEC_MIN_CHUNK * DEC_MIN_CHUNK);
-}
+// One KV-cache call as its entry point received it.  The setters group the arguments the prototypes group; what an entry point does
+// not set keeps the value here.  Nq is T, the packed rows, in the ragged family; Ncap is overwritten by the pool's capacity in a
+// paged call.
+struct KvCall {
+  Family family;
+  bool attend = false, append = false;   // what to do: the attention, the append, or the append then the attention
+  const void *q = nullptr, *k_new = nullptr, *v_new = nullptr;
+  void *k_cache = nullptr, *v_cache = nullptr;
+  float *out = nullptr, *lse = nullptr;
+  const int *cu = nullptr, *seqlens = nullptr;
+  void* workspace = nullptr;
+  // a pool and a block table (pg) in the place of slabs of Ncap rows.  (A flag beside pg.table: the _paged entry points answer a null
+  // table with an error, the later forms take it for slabs.)
+  bool paged = false;
+  Paging pg = {nullptr, 0, 0, 0};
+  Fp8 f8 = {false, nullptr, nullptr};
+  int B = 0, H = 0, Hkv = 0, Nq = 0, Ncap = 0, d_new = 0, d = 0;
+  int layout = 0, causal = 0, window = 0, sink = 0, dtype = 0;
+  float softmax_scale = 0.f;
+  hipStream_t stream = nullptr;
 
-int ext_chunk_keys(int B, int H, int Hkv, int Nq, int Ncap) { return ext_chunk_for((long)B * Hkv * ext_row_blocks(H, Hkv, Nq), Ncap); }
-
-int ext_splits(int B, int H, int Hkv, int Nq, int Ncap) {
-  const int ch = ext_chunk_keys(B, H, Hkv, Nq, Ncap);
-  return (int)(((long)Ncap + ch - 1) / ch);
-}
-
-size_t ext_workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int d) {
-  const int ns = ext_splits(B, H, Hkv, Nq, Ncap);
-  return ns == 1 ? 0 : (size_t)B * H * ns * Nq * (size_t)(d + 2) * sizeof(float);
-}
+  explicit KvCall(Family f) : family(f) {}
+  KvCall& attention(const void* q_, float* out_, float* lse_, void* workspace_, float softmax_scale_, int causal_) {
+    attend = true;
+    q = q_, out = out_, lse = lse_, workspace = workspace_, softmax_scale = softmax_scale_, causal = causal_;
+    return *this;
+  }
+  KvCall& new_tokens(const void* k_new_, const void* v_new_, int d_new_) {
+    append = true;
+    k_new = k_new_, v_new = v_new_, d_new = d_new_;
+    return *this;
+  }
+  // (the attend-only prototypes take the caches const: only an append writes them)
+  KvCall& cache(const void* k_, const void* v_, const int* seqlens_, int Ncap_) {
+    k_cache = const_cast<void*>(k_), v_cache = const_cast<void*>(v_), seqlens = seqlens_, Ncap = Ncap_;
+    return *this;
+  }
+  KvCall& pool(const int* table, int num_pages, int page_size, int max_pages) {
+    paged = true;
+    pg = {table, num_pages, page_size, max_pages};
+    return *this;
+  }
+  // (the forms that take both kinds of cache: a null block_table means slabs of Ncap rows)
+  KvCall& pool_or_slabs(const int* table, int num_pages, int page_size, int max_pages) {
+    return table ? pool(table, num_pages, page_size, max_pages) : *this;
+  }
+  KvCall& heads(int B_, int H_, int Hkv_, int Nq_, int d_) {
+    B = B_, H = H_, Hkv = Hkv_, Nq = Nq_, d = d_;
+    return *this;
+  }
+  KvCall& format(int layout_, int dtype_, void* stream_) {
+    layout = layout_, dtype = dtype_, stream = static_cast<hipStream_t>(stream_);
+    return *this;
+  }
+  bool bnhd() const { return layout == FA_LAYOUT_BNHD; }
+  long seqs() const { return family == RAGGED ? 1 : B; }   // batch elements that own Nq rows each: the ragged ones share T
+  long esz() const { return dtype == FA_DTYPE_BF16 ? 2 : 4; }
+};
 
 // Sliding window (include/flash_attn_mi355x_decode_window.h).  A window of W >= Ncap keys admits every key of every row (a row's
 // position is at most len - 1 <= Ncap - 1): such a call IS the unwindowed call, the same launches and the same bits, and so is
 // W = 0.  This also bounds what the device computes with: W < Ncap.
 // Sinks (include/flash_attn_mi355x_decode_sink.h): S >= Ncap first positions admit every key of every row as well, and S = 0 is
 // the windowed call; sinks without a window mean nothing.  The device computes with 1 <= W < Ncap and 0 <= S < Ncap.
-int win_of(int window, int Ncap, int sink = 0) { return window >= Ncap || sink >= Ncap ? 0 : window; }
-int sink_of(int window, int sink, int Ncap) { return win_of(window, Ncap, sink) == 0 ? 0 : sink; }
+int win_of(int window, int sink, int Ncap) { return window >= Ncap || sink >= Ncap ? 0 : window; }
+int sink_of(int window, int sink, int Ncap) { return win_of(window, sink, Ncap) == 0 ? 0 : sink; }
 
-// The window SPAN: the keys one row block can need, which is what the three policies split where they split Ncap.  A block's rows
+// The window SPAN: the keys one row block can need, which is what the policy splits where it splits Ncap.  A block's rows
 // sit at positions p_first .. p_last with p_last - p_first <= min(Nq, block_rows) - 1 (row i * G + g: block_rows rows span at most
 // block_rows positions, and no more than the call has).  Its key range starts at lo = (p_first - W + 1, clamped to 0) rounded DOWN
 // to a super tile, at most 127 keys below the edge, and ends at p_last:
@@ -97,8 +149,8 @@ int sink_of(int window, int sink, int Ncap) { return win_of(window, Ncap, sink) 
 // and never more than the cache holds.  nsplit * chunk >= span, so the splits of every block cover [lo, p_last].
 // With S sinks a block walks, in front of that range, the super tiles that hold a sink key and lie wholly below lo: at most
 // ceil(S / 128) of them, which the span counts in full.
-int span_keys(int window, int Ncap, int Nq, int block_rows, int sink = 0) {
-  const int W = win_of(window, Ncap, sink);
+int span_keys(int window, int sink, int Ncap, int Nq, int block_rows) {
+  const int W = win_of(window, sink, Ncap);
   if (W == 0) return Ncap;
   const long sink_keys = ((long)sink + fa::DEC_ROWS - 1) / fa::DEC_ROWS * fa::DEC_ROWS;
   return (int)std::min((long)Ncap, sink_keys + W + std::min(Nq, block_rows) - 1 + fa::DEC_ROWS - 1);
@@ -107,141 +159,75 @@ int span_keys(int window, int Ncap, int Nq, int block_rows, int sink = 0) {
 // workgroups of the split launch: the items rounded up to 8, times the row blocks (the kernels' workgroup -> (item, row block) map)
 long split_grid(long items, long nqb) { return (items + 7) / 8 * 8 * nqb; }
 
-// Ragged policy: the extend policy on what the ARGUMENTS say about the row blocks, never the device arrays: a sequence's G * nq_b rows
-// round up to 128 at most once, so B sequences that share T packed rows have at most floor(G * T / 128) + min(B, T) row blocks.  That
-// bound sizes the block map and the grid and stands for the row blocks in the policy, so the split count, the workspace and a
-// captured graph do not depend on cu_seqlens_q.  (It under-splits a step whose tokens all sit in one of many sequences.)
-long rag_blocks(int B, int H, int Hkv, int T) { return (long)(H / Hkv) * T / fa::EXT_BLOCK + std::min(B, T); }
-int rag_chunk_keys(int B, int H, int Hkv, int T, int Ncap) { return ext_chunk_for((long)Hkv * rag_blocks(B, H, Hkv, T), Ncap); }
+// Split policy (DESIGN.md "Decode"): enough (batch*kv head, chunk, row block) workgroups to cover a 256-CU chip `waves` times, chunks
+// a multiple of 256 keys (two super tiles) and at least 256 keys.  A kv head has G*Nq rows (G = H / Hkv query heads per kv head),
+// block_rows to a block.  Launches that already have that many workgroups without splitting run as one split.  The chip size is
+// assumed, not queried, so the split count is a function of the arguments alone.
+// Ragged: the policy on what the ARGUMENTS say about the row blocks, never the device arrays: a sequence's G * nq_b rows round up to
+// 128 at most once, so B sequences that share T packed rows have at most floor(G * T / 128) + min(B, T) row blocks.  That bound
+// sizes the block map and the grid and stands for the row blocks in the policy, so the split count, the workspace and a captured
+// graph do not depend on cu_seqlens_q.  (It under-splits a step whose tokens all sit in one of many sequences.)  Its figures are per
+// call, not per batch element.
+constexpr int DEC_CUS = 256, DEC_MIN_CHUNK = 256;
 
-int rag_splits(int B, int H, int Hkv, int T, int Ncap) {
-  const int ch = rag_chunk_keys(B, H, Hkv, T, Ncap);
-  return (int)(((long)Ncap + ch - 1) / ch);
-}
-
-// the workspace: the block map ((sequence, block) int pairs, rounded up to 16 bytes), then the partials of H * ns * T rows
-size_t rag_map_bytes(int B, int H, int Hkv, int T) { return ((size_t)rag_blocks(B, H, Hkv, T) * 2 * sizeof(int) + 15) / 16 * 16; }
-
-size_t rag_workspace_bytes(int B, int H, int Hkv, int T, int Ncap, int d) {
-  return rag_map_bytes(B, H, Hkv, T) + (size_t)H * rag_splits(B, H, Hkv, T, Ncap) * T * (size_t)(d + 2) * sizeof(float);
-}
-
-template <typename T, int D> int launch_extend(fa::DecodeArgs a, int BH, int sink, hipStream_t st) {
-  if (sink) {   // (the sink builds: their own kernels and argument; a.window >= 1)
-    fa::SinkArgs sa;
-    static_cast<fa::DecodeArgs&>(sa) = a;
-    sa.sink = sink;
-    if (a.table)
-      hipLaunchKernelGGL((fa::extend_split_sink_kernel<T, D, true, false>), dim3((unsigned)split_grid(a.items, a.nqb)), dim3(256), 0, st, sa);
-    else
-      hipLaunchKernelGGL((fa::extend_split_sink_kernel<T, D, false, false>), dim3((unsigned)split_grid(a.items, a.nqb)), dim3(256), 0, st, sa);
-  } else if (a.window && a.table)
-    hipLaunchKernelGGL((fa::extend_split_kernel<T, D, true, false, true>), dim3((unsigned)split_grid(a.items, a.nqb)), dim3(256), 0, st, a);
-  else if (a.window)
-    hipLaunchKernelGGL((fa::extend_split_kernel<T, D, false, false, true>), dim3((unsigned)split_grid(a.items, a.nqb)), dim3(256), 0, st, a);
-  else if (a.table)
-    hipLaunchKernelGGL((fa::extend_split_kernel<T, D, true>), dim3((unsigned)split_grid(a.items, a.nqb)), dim3(256), 0, st, a);
-  else
-    hipLaunchKernelGGL((fa::extend_split_kernel<T, D>), dim3((unsigned)split_grid(a.items, a.nqb)), dim3(256), 0, st, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_err(FA_ERR_HIP, "extend_split_kernel launch", e);
-  if (a.nsplit > 1) {
-    hipLaunchKernelGGL((fa::decode_combine_kernel<D>), dim3((unsigned)((long)BH * a.Nq)), dim3(256), 0, st, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return set_err(FA_ERR_HIP, "decode_combine_kernel launch", e);
-  }
-  return FA_OK;
-}
-
-template <typename T> int launch_extend_d(const fa::DecodeArgs& a, int BH, int d, int sink, hipStream_t st) {
-  switch (d) {
-    case 32: return launch_extend<T, 32>(a, BH, sink, st);
-    case 64: return launch_extend<T, 64>(a, BH, sink, st);
-    default: return launch_extend<T, 128>(a, BH, sink, st);
-  }
-}
-
-template <typename T, int D> int launch(fa::DecodeArgs a, int BH, int sink, hipStream_t st) {
-  const int grid = ((a.items + 7) / 8) * 8 * a.nqb;
-  if (sink) {   // (the sink builds: their own kernels and argument; grouped, as the windowed builds are; a.window >= 1)
-    fa::SinkArgs sa;
-    static_cast<fa::DecodeArgs&>(sa) = a;
-    sa.sink = sink;
-    if (a.table)
-      hipLaunchKernelGGL((fa::decode_split_sink_kernel<T, D, true>), dim3(grid), dim3(256), 0, st, sa);
-    else
-      hipLaunchKernelGGL((fa::decode_split_sink_kernel<T, D, false>), dim3(grid), dim3(256), 0, st, sa);
-  } else if (a.window && a.table)   // (the windowed builds: grouped, as the paged one is)
-    hipLaunchKernelGGL((fa::decode_split_kernel<T, D, true, true, true>), dim3(grid), dim3(256), 0, st, a);
-  else if (a.window)
-    hipLaunchKernelGGL((fa::decode_split_kernel<T, D, true, false, true>), dim3(grid), dim3(256), 0, st, a);
-  else if (a.table)   // (one paged build, the grouped one: G = 1 computes the same rows, and a paged workgroup looks up its page anyway)
-    hipLaunchKernelGGL((fa::decode_split_kernel<T, D, true, true>), dim3(grid), dim3(256), 0, st, a);
-  else if (a.G > 1)
-    hipLaunchKernelGGL((fa::decode_split_kernel<T, D, true>), dim3(grid), dim3(256), 0, st, a);
-  else
-    hipLaunchKernelGGL((fa::decode_split_kernel<T, D, false>), dim3(grid), dim3(256), 0, st, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_err(FA_ERR_HIP, "decode_split_kernel launch", e);
-  if (a.nsplit > 1) {
-    hipLaunchKernelGGL((fa::decode_combine_kernel<D>), dim3((unsigned)(BH * a.Nq)), dim3(256), 0, st, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return set_err(FA_ERR_HIP, "decode_combine_kernel launch", e);
-  }
-  return FA_OK;
-}
-
-template <typename T> int launch_d(const fa::DecodeArgs& a, int BH, int d, int sink, hipStream_t st) {
-  switch (d) {
-    case 32: return launch<T, 32>(a, BH, sink, st);
-    case 64: return launch<T, 64>(a, BH, sink, st);
-    default: return launch<T, 128>(a, BH, sink, st);
-  }
-}
-
-// An fp8 call's scales (null: a bf16 or fp32 cache).
-struct Fp8 {
-  const float* k_scale;
-  const float* v_scale;
+struct Policy {
+  int span;      // the keys that are split: Ncap, or the window span
+  long nqb;      // row blocks per kv head (ragged: entries of the block map)
+  int chunk, nsplit;
+  long items;    // (batch element, kv head, split) triples; ragged: (kv head, split) pairs
+  // the workspace: (ragged) the block map, (sequence, block) int pairs rounded up to 16 bytes, then the partials of all rows and
+  // splits; a decode or extend call of one split needs none
+  size_t map_bytes, workspace_bytes;
 };
 
-// The FP8 builds: bf16 queries, the grouped form of the split kernel (as the paged build takes it for G = 1), slab or paged.
-template <int D> int launch_fp8(fa::Fp8Args a, int BH, bool extend, hipStream_t st) {
-  using T = fa::bf16_t;
-  const dim3 grid((unsigned)split_grid(a.items, a.nqb));
-  if (extend && a.table)
-    hipLaunchKernelGGL((fa::extend_split_kernel<T, D, true, false, false, true>), grid, dim3(256), 0, st, a);
-  else if (extend)
-    hipLaunchKernelGGL((fa::extend_split_kernel<T, D, false, false, false, true>), grid, dim3(256), 0, st, a);
-  else if (a.table)
-    hipLaunchKernelGGL((fa::decode_split_kernel<T, D, true, true, false, true>), grid, dim3(256), 0, st, a);
-  else
-    hipLaunchKernelGGL((fa::decode_split_kernel<T, D, true, false, false, true>), grid, dim3(256), 0, st, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_err(FA_ERR_HIP, extend ? "extend_split_kernel (fp8) launch" : "decode_split_kernel (fp8) launch", e);
-  if (a.nsplit > 1) {
-    hipLaunchKernelGGL((fa::decode_combine_kernel<D, false, true>), dim3((unsigned)((long)BH * a.Nq)), dim3(256), 0, st, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return set_err(FA_ERR_HIP, "decode_combine_kernel (fp8) launch", e);
-  }
+Policy policy(Family f, int B, int H, int Hkv, int Nq, int Ncap, int d, int window, int sink) {
+  const FamilyRule& r = FAMILIES[f];
+  const long G = H / Hkv, seqs = f == RAGGED ? 1 : B;
+  Policy p;
+  p.span = span_keys(window, sink, Ncap, Nq, r.block_rows);
+  p.nqb = f == RAGGED ? G * Nq / r.block_rows + std::min(B, Nq) : (G * Nq + r.block_rows - 1) / r.block_rows;
+  const long groups = seqs * Hkv * p.nqb;
+  const long want = std::max(1L, (DEC_CUS * r.waves + groups - 1) / groups);
+  const long per = (p.span + want - 1) / want;
+  p.chunk = (int)std::max((long)DEC_MIN_CHUNK, (per + DEC_MIN_CHUNK - 1) / DEC_MIN_CHUNK * DEC_MIN_CHUNK);
+  p.nsplit = (int)(((long)p.span + p.chunk - 1) / p.chunk);
+  p.items = seqs * Hkv * p.nsplit;
+  p.map_bytes = f == RAGGED ? ((size_t)p.nqb * 2 * sizeof(int) + 15) / 16 * 16 : 0;
+  const size_t partials = (size_t)seqs * H * p.nsplit * Nq * (size_t)(d + 2) * sizeof(float);
+  p.workspace_bytes = f == RAGGED ? p.map_bytes + partials : p.nsplit == 1 ? 0 : partials;
+  return p;
+}
+
+Policy policy(const KvCall& c) { return policy(c.family, c.B, c.H, c.Hkv, c.Nq, c.Ncap, c.d, c.window, c.sink); }
+
+// The size queries: all zero unless the sizes are positive, H is a multiple of Hkv and window and sink are not negative (what the
+// policy needs to answer at all).
+Policy query(Family f, int B, int H, int Hkv, int Nq, int Ncap, int d, int window, int sink) {
+  const bool ok = B > 0 && H > 0 && Hkv > 0 && Nq > 0 && Ncap > 0 && d > 0 && H % Hkv == 0 && window >= 0 && sink >= 0;
+  return ok ? policy(f, B, H, Hkv, Nq, Ncap, d, window, sink) : Policy{};
+}
+
+// ---- the checks ----
+// The check an fp8 call makes first: the queries and the new tokens are bf16.
+int check_fp8(int dtype) {
+  g_err[0] = 0;
+  if (dtype == FA_DTYPE_F32)
+    return set_err(FA_ERR_BAD_ARG, "an fp8 cache takes bf16 queries and new tokens: FA_DTYPE_F32 is not supported (dtype must be FA_DTYPE_BF16)");
+  if (dtype != FA_DTYPE_BF16) return set_err(FA_ERR_BAD_ARG, "unknown dtype");
   return FA_OK;
 }
 
-int launch_fp8_d(const fa::Fp8Args& a, int BH, int d, bool extend, hipStream_t st) {
-  switch (d) {
-    case 32: return launch_fp8<32>(a, BH, extend, st);
-    case 64: return launch_fp8<64>(a, BH, extend, st);
-    default: return launch_fp8<128>(a, BH, extend, st);
-  }
+// The checks a windowed call makes first (sink: 0 in the calls that have none; a call without a window passes).
+int check_window(int window, int causal, int sink) {
+  g_err[0] = 0;
+  if (sink < 0) return set_err(FA_ERR_BAD_ARG, "sink must not be negative (0: no sink tokens)");
+  if (window < 0) return set_err(FA_ERR_BAD_ARG, "window must not be negative (0: no window)");
+  if (window > 0 && !causal)
+    return set_err(FA_ERR_BAD_ARG, "a sliding window needs the causal mask: window > 0 with causal = 0 (the window ends at the query's position)");
+  return FA_OK;
 }
 
-// A paged call's block table and pool geometry (null: the contiguous call).
-struct Paging {
-  const int* table;
-  int num_pages, page_size, max_pages;
-};
-
-// The checks a paged call makes first: FA_OK with the logical capacity max_pages * page_size in *Ncap, or the error.
+// The checks a paged call makes next: FA_OK with the logical capacity max_pages * page_size in *Ncap, or the error.
 int check_pages(const Paging& p, int* Ncap) {
   g_err[0] = 0;
   if (!p.table) return set_err(FA_ERR_BAD_ARG, "null block_table");
@@ -259,821 +245,314 @@ int check_pages(const Paging& p, int* Ncap) {
   return FA_OK;
 }
 
-// (a buffer load's row offset is a 32-bit byte count inside one page; page base addresses are 64-bit, so the pool may be any size)
-// (fp8: the pool holds one byte per element whatever dtype, the queries' type, says)
-int check_page_bytes(int page_size, int Hkv, int d, int dtype, bool fp8 = false) {
-  const long esz = fp8 ? 1 : dtype == FA_DTYPE_BF16 ? 2 : 4;
-  if ((long)page_size * Hkv * d * esz >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "one page of the pool must stay under 2 GiB");
-  return FA_OK;
-}
-
-// The argument checks of fa_mi355x_fwd_decode_gqa, or (extend) of fa_mi355x_fwd_extend: FA_OK, or the error with its message set.
-// page_size > 0: a paged call with Ncap = max_pages * page_size, where the bound on a batch element of the cache is one on a page.
-// window, sink: the splits are those of the window span.  fp8: the caches hold one byte per element and the queries are bf16.
-int check_decode(const void* q, const void* k_cache, const void* v_cache, const float* out, const void* workspace, int B, int H, int Hkv,
-                 int Nq, int Ncap, int d, int layout, float softmax_scale, int dtype, bool extend = false, int page_size = 0,
-                 int window = 0, bool fp8 = false, int sink = 0) {
-  g_err[0] = 0;
-  if (B <= 0 || H <= 0 || Nq <= 0 || Ncap <= 0 || d <= 0) return set_err(FA_ERR_BAD_ARG, "B, H, Nq, Ncap and d must be positive");
-  if (Hkv <= 0) return set_err(FA_ERR_BAD_ARG, "Hkv must be positive");
-  if (H % Hkv != 0) {
-    snprintf(g_err, sizeof(g_err), "H = %d query heads must be a multiple of Hkv = %d cache heads", H, Hkv);
-    return FA_ERR_BAD_ARG;
-  }
-  if (!extend && Nq > FA_DECODE_MAX_NQ)
-    return set_err(FA_ERR_BAD_ARG, "Nq > 128 is prefill: use fa_mi355x_fwd_layout or fa_mi355x_fwd_scaled (the forward entry points)");
-  if (dtype != FA_DTYPE_F32 && dtype != FA_DTYPE_BF16) return set_err(FA_ERR_BAD_ARG, "unknown dtype");
-  if (layout != FA_LAYOUT_BHND && layout != FA_LAYOUT_BNHD) return set_err(FA_ERR_BAD_ARG, "unknown layout");
-  if (!q || !k_cache || !v_cache || !out) return set_err(FA_ERR_BAD_ARG, "null pointer argument");
-  if (d != 32 && d != 64 && d != 128)
-    return set_err(FA_ERR_UNSUPPORTED_D, "decode supports d in {32, 64, 128}: pad the cache with zero columns for other d <= 128");
-  if (softmax_scale != 0.f && (!(softmax_scale > 0.f) || !std::isfinite(softmax_scale)))
-    return set_err(FA_ERR_BAD_ARG, "softmax_scale must be positive and finite (0: 1/sqrt(d))");
-  // (row_query is exact for rows below 2^25)
-  if (extend && (long)(H / Hkv) * Nq >= (1L << 25)) return set_err(FA_ERR_BAD_ARG, "G * Nq rows per kv head must stay under 2^25");
-  const long esz = dtype == FA_DTYPE_BF16 ? 2 : 4;
-  // (a buffer load's row offset is a 32-bit byte count: one batch element, plus a super tile of rows past its end, stays under 2 GiB;
-  // q's (head, query) offset within its batch element likewise)
-  if (page_size > 0) {
-    if (check_page_bytes(page_size, Hkv, d, dtype, fp8) != FA_OK) return FA_ERR_BAD_ARG;
-  } else if (((long)Ncap + fa::DEC_ROWS) * Hkv * d * (fp8 ? 1 : esz) >= (1L << 31)) {
+// A buffer load's row offset is a 32-bit byte count: one batch element of a slab, plus a super tile of rows past its end, stays
+// under 2 GiB; in a pool the bound is on one page (page base addresses are 64-bit, so the pool may be any size).  An fp8 cache
+// holds one byte per element whatever dtype, the queries' type, says.
+int check_cache_bytes(const KvCall& c) {
+  const long esz = c.f8.on ? 1 : c.esz();
+  if (c.paged) {
+    if ((long)c.pg.page_size * c.Hkv * c.d * esz >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "one page of the pool must stay under 2 GiB");
+  } else if (((long)c.Ncap + fa::DEC_ROWS) * c.Hkv * c.d * esz >= (1L << 31)) {
     return set_err(FA_ERR_BAD_ARG, "one batch element of the cache must stay under 2 GiB");
   }
-  if ((long)Nq * H * d * esz >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "one batch element of q must stay under 2 GiB");
-  if (extend) {
-    // (the workgroup counts of the split and the combine launch are unsigned ints, the items an int)
-    const int ens = ext_splits(B, H, Hkv, Nq, span_keys(window, Ncap, Nq, fa::EXT_BLOCK, sink));
-    if (split_grid((long)B * Hkv * ens, ext_row_blocks(H, Hkv, Nq)) >= (1L << 32) || (long)B * Hkv * ens >= (1L << 31) ||
-        (long)B * H * Nq >= (1L << 32))
-      return set_err(FA_ERR_BAD_ARG, "too many workgroups for one launch: B * Hkv * splits * row blocks and B * H * Nq must fit an unsigned int");
-    if (ens > 1 && !workspace) return set_err(FA_ERR_BAD_ARG, "null workspace: this call needs fa_mi355x_extend_workspace_bytes() bytes");
-    return FA_OK;
-  }
-  const int ns = splits(B, H, Hkv, Nq, span_keys(window, Ncap, Nq, 32, sink));
-  if (ns > 1 && !workspace) return set_err(FA_ERR_BAD_ARG, "null workspace: this call needs fa_mi355x_decode_workspace_bytes() bytes");
   return FA_OK;
 }
 
-// The split (and combine) launches of a checked call: the decode kernels, or (extend) the extend kernels under their own policy.
-int run_decode(const void* q, const void* k_cache, const void* v_cache, float* out, float* lse, const int* cache_seqlens, void* workspace,
-               int B, int H, int Hkv, int Nq, int Ncap, int d, int layout, float softmax_scale, int causal, int dtype, void* stream,
-               bool extend = false, const Paging* pg = nullptr, int window = 0, const Fp8* f8 = nullptr, int sink = 0) {
-  const int span = span_keys(window, Ncap, Nq, extend ? fa::EXT_BLOCK : 32, sink);   // (no window: Ncap)
-  const int ns = extend ? ext_splits(B, H, Hkv, Nq, span) : splits(B, H, Hkv, Nq, span);
-  fa::Fp8Args a;   // (the other builds take its DecodeArgs part)
-  a.k_scale = f8 ? f8->k_scale : nullptr;
-  a.v_scale = f8 ? f8->v_scale : nullptr;
-  a.q = q;
-  a.k = k_cache;
-  a.v = v_cache;
-  a.out = out;
-  a.lse = lse;
-  a.part_o = static_cast<float*>(workspace);
-  a.part_ml = ns > 1 ? a.part_o + (size_t)B * H * ns * Nq * d : nullptr;
-  a.seqlens = cache_seqlens;
-  a.H = H;
-  a.Hkv = Hkv;
-  a.G = H / Hkv;
-  a.inv_G = 1.0f / (float)a.G;
-  a.Nq = Nq;
-  a.Ncap = Ncap;
-  a.nsplit = ns;
-  a.chunk = extend ? ext_chunk_keys(B, H, Hkv, Nq, span) : chunk_keys(B, H, Hkv, Nq, span);
-  a.window = win_of(window, Ncap, sink);
-  sink = sink_of(window, sink, Ncap);
-  a.nqb = extend ? ext_row_blocks(H, Hkv, Nq) : row_blocks(H, Hkv, Nq);
-  a.items = B * Hkv * ns;
-  const bool bnhd = layout == FA_LAYOUT_BNHD;
-  a.q_ld = bnhd ? H * d : d;
-  a.kv_ld = bnhd ? Hkv * d : d;
-  a.q_bstride = (long)Nq * H * d;
-  a.kv_bstride = (long)Ncap * Hkv * d;
-  a.q_hstride = bnhd ? d : (long)Nq * d;
-  a.kv_hstride = bnhd ? d : (long)Ncap * d;
-  a.causal = causal ? 1 : 0;
-  a.tau = softmax_scale > 0.f ? softmax_scale : sqrtf(1.0f / (float)d);
-  a.table = nullptr;
-  a.page_size = a.num_pages = a.max_pages = 0;
-  a.page_stride = 0;
-  if (pg) {   // the pools: pages of [page_size][Hkv][d] or [Hkv][page_size][d]
-    a.table = pg->table;
-    a.page_size = pg->page_size;
-    a.num_pages = pg->num_pages;
-    a.max_pages = pg->max_pages;
-    a.page_stride = (long)pg->page_size * Hkv * d;
-    a.kv_bstride = 0;
-    a.kv_hstride = bnhd ? d : (long)pg->page_size * d;
-  }
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (f8) return launch_fp8_d(a, B * H, d, extend, st);
-  if (extend) return dtype == FA_DTYPE_BF16 ? launch_extend_d<fa::bf16_t>(a, B * H, d, sink, st) : launch_extend_d<float>(a, B * H, d, sink, st);
-  return dtype == FA_DTYPE_BF16 ? launch_d<fa::bf16_t>(a, B * H, d, sink, st) : launch_d<float>(a, B * H, d, sink, st);
-}
-
-// The argument checks of the append: FA_OK, or the error with its message set.
-int check_append(const void* k_new, const void* v_new, const void* k_cache, const void* v_cache, int B, int Hkv, int Nq, int Ncap,
-                 int d_new, int d, int layout, int dtype, bool extend = false) {
+// The argument checks of the attention: FA_OK with the call's policy in *out, or the error with its message set.  The families
+// differ in the Nq <= 128 of decode, the null cu_seqlens_q of ragged, the names in the messages and the bounds of FAMILIES.
+int check_attend(const KvCall& c, Policy* out) {
+  const FamilyRule& r = FAMILIES[c.family];
   g_err[0] = 0;
-  if (B <= 0 || Hkv <= 0 || Nq <= 0 || Ncap <= 0 || d <= 0) return set_err(FA_ERR_BAD_ARG, "B, Hkv, Nq, Ncap and d must be positive");
-  if (!extend && Nq > FA_DECODE_MAX_NQ) return set_err(FA_ERR_BAD_ARG, "Nq > 128 new tokens per call: fill the cache of a prompt directly");
-  if (dtype != FA_DTYPE_F32 && dtype != FA_DTYPE_BF16) return set_err(FA_ERR_BAD_ARG, "unknown dtype");
-  if (layout != FA_LAYOUT_BHND && layout != FA_LAYOUT_BNHD) return set_err(FA_ERR_BAD_ARG, "unknown layout");
-  if (!k_new || !v_new || !k_cache || !v_cache) return set_err(FA_ERR_BAD_ARG, "null pointer argument (k_new, v_new and the caches)");
-  if (d != 32 && d != 64 && d != 128) return set_err(FA_ERR_UNSUPPORTED_D, "decode supports cache rows of d in {32, 64, 128}");
-  if (d_new < 1 || d_new > d) {
-    snprintf(g_err, sizeof(g_err), "d_new = %d must be in 1 .. d = %d", d_new, d);
+  if (c.B <= 0 || c.H <= 0 || c.Nq <= 0 || c.Ncap <= 0 || c.d <= 0) return set_err(FA_ERR_BAD_ARG, r.sizes);
+  if (c.Hkv <= 0) return set_err(FA_ERR_BAD_ARG, "Hkv must be positive");
+  if (c.H % c.Hkv != 0) {
+    snprintf(g_err, sizeof(g_err), "H = %d query heads must be a multiple of Hkv = %d cache heads", c.H, c.Hkv);
     return FA_ERR_BAD_ARG;
   }
-  // (one lane per element at the most, 256 lanes to a workgroup, the workgroup count an int)
-  if ((long)B * Nq * Hkv * d / 256 >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "too many new elements for one append launch");
+  if (c.family == DECODE && c.Nq > FA_DECODE_MAX_NQ)
+    return set_err(FA_ERR_BAD_ARG, "Nq > 128 is prefill: use fa_mi355x_fwd_layout or fa_mi355x_fwd_scaled (the forward entry points)");
+  if (c.dtype != FA_DTYPE_F32 && c.dtype != FA_DTYPE_BF16) return set_err(FA_ERR_BAD_ARG, "unknown dtype");
+  if (c.layout != FA_LAYOUT_BHND && c.layout != FA_LAYOUT_BNHD) return set_err(FA_ERR_BAD_ARG, "unknown layout");
+  if (!c.q || !c.k_cache || !c.v_cache || !c.out) return set_err(FA_ERR_BAD_ARG, "null pointer argument");
+  if (c.family == RAGGED && !c.cu) return set_err(FA_ERR_BAD_ARG, "null cu_seqlens_q");
+  if (c.d != 32 && c.d != 64 && c.d != 128)
+    return set_err(FA_ERR_UNSUPPORTED_D, "decode supports d in {32, 64, 128}: pad the cache with zero columns for other d <= 128");
+  if (c.softmax_scale != 0.f && (!(c.softmax_scale > 0.f) || !std::isfinite(c.softmax_scale)))
+    return set_err(FA_ERR_BAD_ARG, "softmax_scale must be positive and finite (0: 1/sqrt(d))");
+  // (row_query is exact for rows below 2^25; a ragged sequence has at most G * T of them)
+  if (r.rows && (long)(c.H / c.Hkv) * c.Nq >= (1L << 25)) return set_err(FA_ERR_BAD_ARG, r.rows);
+  if (check_cache_bytes(c) != FA_OK) return FA_ERR_BAD_ARG;
+  // (q's (head, query) offset within its batch element is a 32-bit byte count as well; a ragged sequence may own every packed row)
+  if ((long)c.Nq * c.H * c.d * c.esz() >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, r.q_bytes);
+  const Policy p = policy(c);
+  // (the workgroup counts of the split and the combine launch are unsigned ints, the items an int)
+  if (r.grid && (split_grid(p.items, p.nqb) >= (1L << 32) || p.items >= (1L << 31) || c.seqs() * c.H * c.Nq >= (1L << 32)))
+    return set_err(FA_ERR_BAD_ARG, r.grid);
+  // (the ragged block map lives in the workspace: every ragged call needs one)
+  if ((p.nsplit > 1 || c.family == RAGGED) && !c.workspace) return set_err(FA_ERR_BAD_ARG, r.workspace);
+  *out = p;
   return FA_OK;
+}
+
+// The argument checks of the append: FA_OK, or the error with its message set.  Ragged: T packed rows in the place of B * Nq, and
+// a null cu_seqlens_q.  An append without the attention also makes the attention's check of the cache's size.
+int check_append(const KvCall& c) {
+  g_err[0] = 0;
+  if (c.B <= 0 || c.Hkv <= 0 || c.Nq <= 0 || c.Ncap <= 0 || c.d <= 0) return set_err(FA_ERR_BAD_ARG, FAMILIES[c.family].append_sizes);
+  if (c.family == DECODE && c.Nq > FA_DECODE_MAX_NQ)
+    return set_err(FA_ERR_BAD_ARG, "Nq > 128 new tokens per call: fill the cache of a prompt directly");
+  if (c.dtype != FA_DTYPE_F32 && c.dtype != FA_DTYPE_BF16) return set_err(FA_ERR_BAD_ARG, "unknown dtype");
+  if (c.layout != FA_LAYOUT_BHND && c.layout != FA_LAYOUT_BNHD) return set_err(FA_ERR_BAD_ARG, "unknown layout");
+  if (!c.k_new || !c.v_new || !c.k_cache || !c.v_cache)
+    return set_err(FA_ERR_BAD_ARG, "null pointer argument (k_new, v_new and the caches)");
+  if (c.family == RAGGED && !c.cu) return set_err(FA_ERR_BAD_ARG, "null cu_seqlens_q");
+  if (c.d != 32 && c.d != 64 && c.d != 128) return set_err(FA_ERR_UNSUPPORTED_D, "decode supports cache rows of d in {32, 64, 128}");
+  if (c.d_new < 1 || c.d_new > c.d) {
+    snprintf(g_err, sizeof(g_err), "d_new = %d must be in 1 .. d = %d", c.d_new, c.d);
+    return FA_ERR_BAD_ARG;
+  }
+  // (one lane per element at the most, 256 lanes to a workgroup, the workgroup count an int; the ragged kernel counts packed rows in
+  // an int)
+  if (c.seqs() * c.Nq * c.Hkv * c.d / 256 >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "too many new elements for one append launch");
+  // (a store's row offset is added to a 64-bit address: the bound is the attention's, whose loads read these rows.  A page of any
+  // pool, and the slabs an fp8 append fills; a fused call's attention has checked it already)
+  if (!c.attend && (c.paged || c.f8.on)) return check_cache_bytes(c);
+  return FA_OK;
+}
+
+// ---- the kernel arguments ----
+// The one place that writes cache geometry, into a DecodeArgs, RaggedArgs, AppendArgs or RopeAppendArgs: slabs of Ncap rows per batch
+// element, or (a block table) pool pages of [page_size][Hkv][d] or [Hkv][page_size][d] rows.
+template <typename A> void set_cache_geometry(A& a, const KvCall& c) {
+  const long rows = c.paged ? c.pg.page_size : c.Ncap;   // rows of one slab or page
+  a.kv_ld = c.bnhd() ? c.Hkv * c.d : c.d;
+  a.kv_hstride = c.bnhd() ? c.d : rows * c.d;
+  a.kv_bstride = c.paged ? 0 : (long)c.Ncap * c.Hkv * c.d;
+  a.table = c.pg.table;
+  a.page_size = c.pg.page_size;
+  a.num_pages = c.pg.num_pages;
+  a.max_pages = c.pg.max_pages;
+  a.page_stride = (long)c.pg.page_size * c.Hkv * c.d;
+}
+
+// The AppendArgs part of every append's argument (lanes: rows on entry, which the launchers turn into lanes).
+void set_append(fa::AppendArgs& a, const KvCall& c) {
+  a.k_new = c.k_new;
+  a.v_new = c.v_new;
+  a.k = c.k_cache;
+  a.v = c.v_cache;
+  a.seqlens = c.seqlens;
+  a.lanes = c.k_new ? c.seqs() * c.Nq * c.Hkv : 0;
+  a.Hkv = c.Hkv;
+  a.Nq = c.Nq;
+  a.Ncap = c.Ncap;
+  a.d_new = c.d_new;
+  a.bnhd = c.bnhd();
+  set_cache_geometry(a, c);
+}
+
+// The host's view of a split launch: every build's argument is a part of it (DecodeArgs, RaggedArgs) or a copy of such a part with
+// the scales or the sink count behind it (Fp8Args, SinkArgs, RaggedSinkArgs), which the leg that launches such a build makes.
+struct SplitArgs : fa::RaggedArgs {
+  Fp8 f8;
+  int sink;   // S >= 1: a sink reaches the device
+};
+
+template <typename S, typename Base> S with_sink(const SplitArgs& a) {
+  S s;
+  static_cast<Base&>(s) = a;
+  s.sink = a.sink;
+  return s;
+}
+
+fa::Fp8Args with_scales(const SplitArgs& a) {
+  fa::Fp8Args f;
+  static_cast<fa::DecodeArgs&>(f) = a;
+  f.k_scale = a.f8.k_scale;
+  f.v_scale = a.f8.v_scale;
+  return f;
+}
+
+// ---- the launches ----
+template <typename A, typename B> void launch256(void (*kernel)(A), long grid, hipStream_t st, const B& a) {
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), 0, st, static_cast<const A&>(a));
+}
+
+// The launches of a checked attention: (ragged) the schedule, the split build of the table below, and the combine if nsplit > 1.
+// Which instance serves which call:
+//   decode  the ungrouped build for exactly the slab, unwindowed, non-fp8, G == 1 call; the grouped build for every other (one paged
+//           build: G = 1 computes the same rows, and a paged workgroup looks up its page anyway; the windowed, sink and fp8 builds
+//           likewise)
+//   extend, ragged  PAGED x WINDOW as the call has them; ragged is the RAGGED flag of the extend kernels
+//   sink    kernels and an argument of their own, only when a sink reaches the device (a.sink >= 1, which implies a.window >= 1)
+//   fp8     bf16 queries, slab or paged, no window (the Python layer refuses the combination by name)
+template <typename T, int D> int launch_split(const SplitArgs& a, Family f, hipStream_t st) {
+  constexpr bool BF16 = std::is_same<T, fa::bf16_t>::value;
+  const bool paged = a.table != nullptr, window = a.window != 0;
+  const long grid = split_grid(a.items, a.nqb);
+  if (f == RAGGED) {
+    hipLaunchKernelGGL(fa::ragged_schedule_kernel, dim3(1), dim3(256), 0, st, a.cu, const_cast<int*>(a.map), a.nseq, a.ntok, a.G, a.nqb);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_err("ragged_schedule_kernel launch", e);
+  }
+  const char* what = FAMILIES[f].split_launch;
+  if (a.f8.on) {
+    what = f == EXTEND ? "extend_split_kernel (fp8) launch" : "decode_split_kernel (fp8) launch";
+    if constexpr (BF16) {   // (check_fp8: never fp32 queries)
+      const fa::Fp8Args fa8 = with_scales(a);
+      if (f == EXTEND && paged) launch256(fa::extend_split_kernel<T, D, true, false, false, true>, grid, st, fa8);
+      else if (f == EXTEND) launch256(fa::extend_split_kernel<T, D, false, false, false, true>, grid, st, fa8);
+      else if (paged) launch256(fa::decode_split_kernel<T, D, true, true, false, true>, grid, st, fa8);
+      else launch256(fa::decode_split_kernel<T, D, true, false, false, true>, grid, st, fa8);
+    }
+  } else if (f == DECODE) {
+    if (a.sink) {
+      const fa::SinkArgs sa = with_sink<fa::SinkArgs, fa::DecodeArgs>(a);
+      if (paged) launch256(fa::decode_split_sink_kernel<T, D, true>, grid, st, sa);
+      else launch256(fa::decode_split_sink_kernel<T, D, false>, grid, st, sa);
+    } else if (window && paged) launch256(fa::decode_split_kernel<T, D, true, true, true>, grid, st, a);
+    else if (window) launch256(fa::decode_split_kernel<T, D, true, false, true>, grid, st, a);
+    else if (paged) launch256(fa::decode_split_kernel<T, D, true, true>, grid, st, a);
+    else if (a.G > 1) launch256(fa::decode_split_kernel<T, D, true>, grid, st, a);
+    else launch256(fa::decode_split_kernel<T, D, false>, grid, st, a);
+  } else if (f == EXTEND) {
+    if (a.sink) {
+      const fa::SinkArgs sa = with_sink<fa::SinkArgs, fa::DecodeArgs>(a);
+      if (paged) launch256(fa::extend_split_sink_kernel<T, D, true, false>, grid, st, sa);
+      else launch256(fa::extend_split_sink_kernel<T, D, false, false>, grid, st, sa);
+    } else if (window && paged) launch256(fa::extend_split_kernel<T, D, true, false, true>, grid, st, a);
+    else if (window) launch256(fa::extend_split_kernel<T, D, false, false, true>, grid, st, a);
+    else if (paged) launch256(fa::extend_split_kernel<T, D, true>, grid, st, a);
+    else launch256(fa::extend_split_kernel<T, D>, grid, st, a);
+  } else {
+    if (a.sink) {
+      const fa::RaggedSinkArgs sa = with_sink<fa::RaggedSinkArgs, fa::RaggedArgs>(a);
+      if (paged) launch256(fa::extend_split_sink_kernel<T, D, true, true>, grid, st, sa);
+      else launch256(fa::extend_split_sink_kernel<T, D, false, true>, grid, st, sa);
+    } else if (window && paged) launch256(fa::extend_split_kernel<T, D, true, true, true>, grid, st, a);
+    else if (window) launch256(fa::extend_split_kernel<T, D, false, true, true>, grid, st, a);
+    else if (paged) launch256(fa::extend_split_kernel<T, D, true, true>, grid, st, a);
+    else launch256(fa::extend_split_kernel<T, D, false, true>, grid, st, a);
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_err(what, e);
+  if (a.nsplit > 1) {
+    const long rows = (f == RAGGED ? 1L : a.nseq) * a.H * a.Nq;   // one workgroup per output row
+    if (a.f8.on) launch256(fa::decode_combine_kernel<D, false, true>, rows, st, with_scales(a));
+    else if (f == RAGGED) launch256(fa::decode_combine_kernel<D, true>, rows, st, a);
+    else launch256(fa::decode_combine_kernel<D>, rows, st, a);
+    e = hipGetLastError();
+    if (e != hipSuccess) return hip_err(a.f8.on ? "decode_combine_kernel (fp8) launch" : FAMILIES[f].combine_launch, e);
+  }
+  return FA_OK;
+}
+
+template <typename T> int launch_split_d(const SplitArgs& a, Family f, int d, hipStream_t st) {
+  switch (d) {
+    case 32: return launch_split<T, 32>(a, f, st);
+    case 64: return launch_split<T, 64>(a, f, st);
+    default: return launch_split<T, 128>(a, f, st);
+  }
+}
+
+// The launches of a checked attention under the policy its check returned.
+int run_attend(const KvCall& c, const Policy& p) {
+  const bool ragged = c.family == RAGGED;
+  SplitArgs a;
+  a.q = c.q;
+  a.k = c.k_cache;
+  a.v = c.v_cache;
+  a.out = c.out;
+  a.lse = c.lse;
+  a.map = static_cast<const int*>(c.workspace);   // (ragged: the block map, then the partials)
+  a.part_o = reinterpret_cast<float*>(static_cast<char*>(c.workspace) + p.map_bytes);
+  a.part_ml = p.nsplit > 1 || ragged ? a.part_o + (size_t)c.seqs() * c.H * p.nsplit * c.Nq * c.d : nullptr;
+  a.seqlens = c.seqlens;
+  a.cu = c.cu;
+  a.nseq = c.B;
+  a.ntok = c.Nq;
+  a.H = c.H;
+  a.Hkv = c.Hkv;
+  a.G = c.H / c.Hkv;
+  a.inv_G = 1.0f / (float)a.G;
+  a.Nq = c.Nq;   // (ragged: the combine kernel's view, one batch element of T queries)
+  a.Ncap = c.Ncap;
+  a.nsplit = p.nsplit;
+  a.chunk = p.chunk;
+  a.window = win_of(c.window, c.sink, c.Ncap);
+  a.sink = sink_of(c.window, c.sink, c.Ncap);
+  a.nqb = (int)p.nqb;
+  a.items = (int)p.items;
+  const bool q_bnhd = c.bnhd() || ragged;   // (the packed buffers are token-major whatever the caches' layout)
+  a.q_ld = q_bnhd ? c.H * c.d : c.d;
+  a.q_bstride = (long)c.Nq * c.H * c.d;
+  a.q_hstride = q_bnhd ? c.d : (long)c.Nq * c.d;
+  set_cache_geometry(a, c);
+  a.causal = c.causal ? 1 : 0;
+  a.tau = c.softmax_scale > 0.f ? c.softmax_scale : sqrtf(1.0f / (float)c.d);
+  a.f8 = c.f8;
+  return c.dtype == FA_DTYPE_BF16 ? launch_split_d<fa::bf16_t>(a, c.family, c.d, c.stream) : launch_split_d<float>(a, c.family, c.d, c.stream);
 }
 
 template <typename T, int E> int launch_append(fa::RaggedAppendArgs a, int d, hipStream_t st) {
   a.ch_shift = __builtin_ctz(d / E);
   a.lanes <<= a.ch_shift;   // (rows on entry)
-  const dim3 grid((unsigned)((a.lanes + 255) / 256));
-  if (a.cu && a.table)
-    hipLaunchKernelGGL((fa::decode_append_kernel<T, E, true, true>), grid, dim3(256), 0, st, a);
-  else if (a.cu)
-    hipLaunchKernelGGL((fa::decode_append_kernel<T, E, false, true>), grid, dim3(256), 0, st, a);
-  else if (a.table)
-    hipLaunchKernelGGL((fa::decode_append_kernel<T, E, true>), grid, dim3(256), 0, st, static_cast<const fa::AppendArgs&>(a));
-  else
-    hipLaunchKernelGGL((fa::decode_append_kernel<T, E>), grid, dim3(256), 0, st, static_cast<const fa::AppendArgs&>(a));
+  const long grid = (a.lanes + 255) / 256;
+  if (a.cu && a.table) launch256(fa::decode_append_kernel<T, E, true, true>, grid, st, a);
+  else if (a.cu) launch256(fa::decode_append_kernel<T, E, false, true>, grid, st, a);
+  else if (a.table) launch256(fa::decode_append_kernel<T, E, true>, grid, st, a);
+  else launch256(fa::decode_append_kernel<T, E>, grid, st, a);
   const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? FA_OK : set_err(FA_ERR_HIP, "decode_append_kernel launch", e);
-}
-
-template <typename T> int launch_append_e(const fa::RaggedAppendArgs& a, int d, bool vec, hipStream_t st) {
-  return vec ? launch_append<T, 16 / sizeof(T)>(a, d, st) : launch_append<T, 1>(a, d, st);
+  return e == hipSuccess ? FA_OK : hip_err("decode_append_kernel launch", e);
 }
 
 template <int E> int launch_append_fp8(fa::Fp8AppendArgs a, int d, hipStream_t st) {
   a.ch_shift = __builtin_ctz(d / E);
   a.lanes <<= a.ch_shift;   // (rows on entry)
-  const dim3 grid((unsigned)((a.lanes + 255) / 256));
-  if (a.table)
-    hipLaunchKernelGGL((fa::append_fp8_kernel<E, true>), grid, dim3(256), 0, st, a);
-  else
-    hipLaunchKernelGGL((fa::append_fp8_kernel<E>), grid, dim3(256), 0, st, a);
+  const long grid = (a.lanes + 255) / 256;
+  if (a.table) launch256(fa::append_fp8_kernel<E, true>, grid, st, a);
+  else launch256(fa::append_fp8_kernel<E>, grid, st, a);
   const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? FA_OK : set_err(FA_ERR_HIP, "append_fp8_kernel launch", e);
+  return e == hipSuccess ? FA_OK : hip_err("append_fp8_kernel launch", e);
 }
 
-// The append launch of a checked call.  cu: the ragged append of Nq = T packed rows shared by the B sequences.
-int run_append(const void* k_new, const void* v_new, void* k_cache, void* v_cache, const int* cache_seqlens, int B, int Hkv, int Nq,
-               int Ncap, int d_new, int d, int layout, int dtype, void* stream, const Paging* pg = nullptr, const int* cu = nullptr,
-               const Fp8* f8 = nullptr) {
+// The append launch of a checked call.  Ragged: the append of T packed rows shared by the B sequences.
+int run_append(const KvCall& c) {
+  const uintptr_t news = (uintptr_t)c.k_new | (uintptr_t)c.v_new, caches = (uintptr_t)c.k_cache | (uintptr_t)c.v_cache;
+  if (c.f8.on) {   // bf16 sources into byte caches: eight elements to a lane where every source row starts on 16 bytes and every cache row on 8
+    fa::Fp8AppendArgs a;
+    set_append(a, c);
+    a.k_scale = c.f8.k_scale;
+    a.v_scale = c.f8.v_scale;
+    const bool vec8 = c.d_new % 8 == 0 && (news & 15) == 0 && (caches & 7) == 0;
+    return vec8 ? launch_append_fp8<8>(a, c.d, c.stream) : launch_append_fp8<1>(a, c.d, c.stream);
+  }
   fa::RaggedAppendArgs a;
-  a.k_new = k_new;
-  a.v_new = v_new;
-  a.k = k_cache;
-  a.v = v_cache;
-  a.seqlens = cache_seqlens;
-  a.lanes = cu ? (long)Nq * Hkv : (long)B * Nq * Hkv;
-  a.cu = cu;
-  a.nseq = B;
-  a.ntok = Nq;
-  a.Hkv = Hkv;
-  a.Nq = Nq;
-  a.Ncap = Ncap;
-  a.d_new = d_new;
-  a.bnhd = layout == FA_LAYOUT_BNHD;
-  a.kv_ld = a.bnhd ? Hkv * d : d;
-  a.kv_bstride = (long)Ncap * Hkv * d;
-  a.kv_hstride = a.bnhd ? d : (long)Ncap * d;
-  a.table = nullptr;
-  a.page_size = a.num_pages = a.max_pages = 0;
-  a.page_stride = 0;
-  if (pg) {
-    a.table = pg->table;
-    a.page_size = pg->page_size;
-    a.num_pages = pg->num_pages;
-    a.max_pages = pg->max_pages;
-    a.page_stride = (long)pg->page_size * Hkv * d;
-    a.kv_bstride = 0;
-    a.kv_hstride = a.bnhd ? d : (long)pg->page_size * d;
-  }
-  const size_t esz = dtype == FA_DTYPE_BF16 ? 2 : 4;
+  set_append(a, c);
+  a.cu = c.cu;
+  a.nseq = c.B;
+  a.ntok = c.Nq;
   // 16-byte lanes where every row of the source starts on 16 bytes, as every row of the cache does once its base is
-  const bool vec = (d_new * esz) % 16 == 0 &&
-                   (((uintptr_t)k_new | (uintptr_t)v_new | (uintptr_t)k_cache | (uintptr_t)v_cache) & 15) == 0;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (f8) {   // bf16 sources into byte caches: eight elements to a lane where every source row starts on 16 bytes and every cache row on 8
-    fa::Fp8AppendArgs fa8;
-    static_cast<fa::AppendArgs&>(fa8) = a;
-    fa8.k_scale = f8->k_scale;
-    fa8.v_scale = f8->v_scale;
-    const bool vec8 = d_new % 8 == 0 && (((uintptr_t)k_new | (uintptr_t)v_new) & 15) == 0 && (((uintptr_t)k_cache | (uintptr_t)v_cache) & 7) == 0;
-    return vec8 ? launch_append_fp8<8>(fa8, d, st) : launch_append_fp8<1>(fa8, d, st);
-  }
-  return dtype == FA_DTYPE_BF16 ? launch_append_e<fa::bf16_t>(a, d, vec, st) : launch_append_e<float>(a, d, vec, st);
+  const bool vec = (c.d_new * c.esz()) % 16 == 0 && ((news | caches) & 15) == 0;
+  if (c.dtype == FA_DTYPE_BF16) return vec ? launch_append<fa::bf16_t, 8>(a, c.d, c.stream) : launch_append<fa::bf16_t, 1>(a, c.d, c.stream);
+  return vec ? launch_append<float, 4>(a, c.d, c.stream) : launch_append<float, 1>(a, c.d, c.stream);
 }
 
-// ---- ragged batches (include/flash_attn_mi355x_decode_ragged.h) ----
-// The argument checks of fa_mi355x_fwd_ragged: those of fa_mi355x_fwd_extend with T in the place of Nq, a null cu_seqlens_q, and
-// a null workspace (the block map lives there: every ragged call needs one).  page_size > 0: a paged call, as in check_decode.
-int check_ragged(const void* q, const void* k_cache, const void* v_cache, const float* out, const int* cu, const void* workspace, int B,
-                 int H, int Hkv, int T, int Ncap, int d, int layout, float softmax_scale, int dtype, int page_size = 0, int window = 0,
-                 int sink = 0) {
-  g_err[0] = 0;
-  if (B <= 0 || H <= 0 || T <= 0 || Ncap <= 0 || d <= 0) return set_err(FA_ERR_BAD_ARG, "B, H, T, Ncap and d must be positive");
-  if (Hkv <= 0) return set_err(FA_ERR_BAD_ARG, "Hkv must be positive");
-  if (H % Hkv != 0) {
-    snprintf(g_err, sizeof(g_err), "H = %d query heads must be a multiple of Hkv = %d cache heads", H, Hkv);
-    return FA_ERR_BAD_ARG;
-  }
-  if (dtype != FA_DTYPE_F32 && dtype != FA_DTYPE_BF16) return set_err(FA_ERR_BAD_ARG, "unknown dtype");
-  if (layout != FA_LAYOUT_BHND && layout != FA_LAYOUT_BNHD) return set_err(FA_ERR_BAD_ARG, "unknown layout");
-  if (!q || !k_cache || !v_cache || !out) return set_err(FA_ERR_BAD_ARG, "null pointer argument");
-  if (!cu) return set_err(FA_ERR_BAD_ARG, "null cu_seqlens_q");
-  if (d != 32 && d != 64 && d != 128)
-    return set_err(FA_ERR_UNSUPPORTED_D, "decode supports d in {32, 64, 128}: pad the cache with zero columns for other d <= 128");
-  if (softmax_scale != 0.f && (!(softmax_scale > 0.f) || !std::isfinite(softmax_scale)))
-    return set_err(FA_ERR_BAD_ARG, "softmax_scale must be positive and finite (0: 1/sqrt(d))");
-  // (row_query is exact for rows below 2^25; a sequence has at most G * T of them)
-  if ((long)(H / Hkv) * T >= (1L << 25)) return set_err(FA_ERR_BAD_ARG, "G * T rows per kv head must stay under 2^25");
-  const long esz = dtype == FA_DTYPE_BF16 ? 2 : 4;
-  if (page_size > 0) {
-    if (check_page_bytes(page_size, Hkv, d, dtype) != FA_OK) return FA_ERR_BAD_ARG;
-  } else if (((long)Ncap + fa::DEC_ROWS) * Hkv * d * esz >= (1L << 31)) {
-    return set_err(FA_ERR_BAD_ARG, "one batch element of the cache must stay under 2 GiB");
-  }
-  // (a sequence may own every packed row: its q resource and the (head, query) offsets inside it are 32-bit byte counts)
-  if ((long)T * H * d * esz >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "q (T * H * d elements) must stay under 2 GiB");
-  const int ns = rag_splits(B, H, Hkv, T, span_keys(window, Ncap, T, fa::EXT_BLOCK, sink));
-  if (split_grid((long)Hkv * ns, rag_blocks(B, H, Hkv, T)) >= (1L << 32) || (long)Hkv * ns >= (1L << 31) || (long)H * T >= (1L << 32))
-    return set_err(FA_ERR_BAD_ARG, "too many workgroups for one launch: Hkv * splits * row blocks and H * T must fit an unsigned int");
-  if (!workspace)
-    return set_err(FA_ERR_BAD_ARG, "null workspace: a ragged call always needs fa_mi355x_ragged_workspace_bytes() bytes (the block map)");
-  return FA_OK;
+// The one path of every attention and append entry point: every check, in the order in which errors win, then the launches.
+int run(KvCall c) {
+  int rc = c.f8.on ? check_fp8(c.dtype) : check_window(c.window, c.causal, c.sink);
+  if (rc == FA_OK && c.paged) rc = check_pages(c.pg, &c.Ncap);
+  Policy p{};
+  if (rc == FA_OK && c.attend) rc = check_attend(c, &p);
+  if (rc == FA_OK && c.append) rc = check_append(c);
+  if (rc == FA_OK && c.append) rc = run_append(c);
+  if (rc == FA_OK && c.attend) rc = run_attend(c, p);
+  return rc;
 }
 
-// ... of fa_mi355x_ragged_append: those of fa_mi355x_extend_append with T in the place of B * Nq, and a null cu_seqlens_q.
-int check_ragged_append(const void* k_new, const void* v_new, const void* k_cache, const void* v_cache, const int* cu, int B, int Hkv, int T,
-                        int Ncap, int d_new, int d, int layout, int dtype) {
-  g_err[0] = 0;
-  if (B <= 0 || Hkv <= 0 || T <= 0 || Ncap <= 0 || d <= 0) return set_err(FA_ERR_BAD_ARG, "B, Hkv, T, Ncap and d must be positive");
-  if (dtype != FA_DTYPE_F32 && dtype != FA_DTYPE_BF16) return set_err(FA_ERR_BAD_ARG, "unknown dtype");
-  if (layout != FA_LAYOUT_BHND && layout != FA_LAYOUT_BNHD) return set_err(FA_ERR_BAD_ARG, "unknown layout");
-  if (!k_new || !v_new || !k_cache || !v_cache) return set_err(FA_ERR_BAD_ARG, "null pointer argument (k_new, v_new and the caches)");
-  if (!cu) return set_err(FA_ERR_BAD_ARG, "null cu_seqlens_q");
-  if (d != 32 && d != 64 && d != 128) return set_err(FA_ERR_UNSUPPORTED_D, "decode supports cache rows of d in {32, 64, 128}");
-  if (d_new < 1 || d_new > d) {
-    snprintf(g_err, sizeof(g_err), "d_new = %d must be in 1 .. d = %d", d_new, d);
-    return FA_ERR_BAD_ARG;
-  }
-  // (the kernel counts packed rows in an int; one lane per element at the most, the workgroup count an int)
-  if ((long)T * Hkv * d / 256 >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "too many new elements for one append launch");
-  return FA_OK;
-}
-
-template <typename T, int D> int launch_ragged(fa::RaggedArgs a, int sink, hipStream_t st) {
-  hipLaunchKernelGGL(fa::ragged_schedule_kernel, dim3(1), dim3(256), 0, st, a.cu, const_cast<int*>(a.map), a.nseq, a.ntok, a.G, a.nqb);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_err(FA_ERR_HIP, "ragged_schedule_kernel launch", e);
-  const dim3 grid((unsigned)split_grid(a.items, a.nqb));
-  if (sink) {   // (the sink builds: their own kernels and argument; a.window >= 1)
-    fa::RaggedSinkArgs sa;
-    static_cast<fa::RaggedArgs&>(sa) = a;
-    sa.sink = sink;
-    if (a.table)
-      hipLaunchKernelGGL((fa::extend_split_sink_kernel<T, D, true, true>), grid, dim3(256), 0, st, sa);
-    else
-      hipLaunchKernelGGL((fa::extend_split_sink_kernel<T, D, false, true>), grid, dim3(256), 0, st, sa);
-  } else if (a.window && a.table)
-    hipLaunchKernelGGL((fa::extend_split_kernel<T, D, true, true, true>), grid, dim3(256), 0, st, a);
-  else if (a.window)
-    hipLaunchKernelGGL((fa::extend_split_kernel<T, D, false, true, true>), grid, dim3(256), 0, st, a);
-  else if (a.table)
-    hipLaunchKernelGGL((fa::extend_split_kernel<T, D, true, true>), grid, dim3(256), 0, st, a);
-  else
-    hipLaunchKernelGGL((fa::extend_split_kernel<T, D, false, true>), grid, dim3(256), 0, st, a);
-  e = hipGetLastError();
-  if (e != hipSuccess) return set_err(FA_ERR_HIP, "extend_split_kernel (ragged) launch", e);
-  if (a.nsplit > 1) {
-    hipLaunchKernelGGL((fa::decode_combine_kernel<D, true>), dim3((unsigned)((long)a.H * a.ntok)), dim3(256), 0, st, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return set_err(FA_ERR_HIP, "decode_combine_kernel (ragged) launch", e);
-  }
-  return FA_OK;
-}
-
-template <typename T> int launch_ragged_d(const fa::RaggedArgs& a, int d, int sink, hipStream_t st) {
-  switch (d) {
-    case 32: return launch_ragged<T, 32>(a, sink, st);
-    case 64: return launch_ragged<T, 64>(a, sink, st);
-    default: return launch_ragged<T, 128>(a, sink, st);
-  }
-}
-
-// The schedule, split (and combine) launches of a checked ragged call.
-int run_ragged(const void* q, const void* k_cache, const void* v_cache, float* out, float* lse, const int* cu, const int* cache_seqlens,
-               void* workspace, int B, int H, int Hkv, int T, int Ncap, int d, int layout, float softmax_scale, int causal, int dtype,
-               void* stream, const Paging* pg, int window = 0, int sink = 0) {
-  const int span = span_keys(window, Ncap, T, fa::EXT_BLOCK, sink);   // (no window: Ncap; a sequence may own all T rows)
-  const int ns = rag_splits(B, H, Hkv, T, span);
-  fa::RaggedArgs a;
-  a.q = q;
-  a.k = k_cache;
-  a.v = v_cache;
-  a.out = out;
-  a.lse = lse;
-  a.map = static_cast<const int*>(workspace);
-  a.part_o = reinterpret_cast<float*>(static_cast<char*>(workspace) + rag_map_bytes(B, H, Hkv, T));
-  a.part_ml = a.part_o + (size_t)H * ns * T * d;
-  a.seqlens = cache_seqlens;
-  a.cu = cu;
-  a.nseq = B;
-  a.ntok = T;
-  a.H = H;
-  a.Hkv = Hkv;
-  a.G = H / Hkv;
-  a.inv_G = 1.0f / (float)a.G;
-  a.Nq = T;   // (the combine kernel's view: one batch element of T queries)
-  a.Ncap = Ncap;
-  a.nsplit = ns;
-  a.chunk = rag_chunk_keys(B, H, Hkv, T, span);
-  a.window = win_of(window, Ncap, sink);
-  sink = sink_of(window, sink, Ncap);
-  a.nqb = (int)rag_blocks(B, H, Hkv, T);
-  a.items = Hkv * ns;
-  const bool bnhd = layout == FA_LAYOUT_BNHD;
-  a.q_ld = H * d;   // (the packed buffers are token-major whatever the caches' layout)
-  a.q_hstride = d;
-  a.q_bstride = (long)T * H * d;
-  a.kv_ld = bnhd ? Hkv * d : d;
-  a.kv_bstride = (long)Ncap * Hkv * d;
-  a.kv_hstride = bnhd ? d : (long)Ncap * d;
-  a.causal = causal ? 1 : 0;
-  a.tau = softmax_scale > 0.f ? softmax_scale : sqrtf(1.0f / (float)d);
-  a.table = nullptr;
-  a.page_size = a.num_pages = a.max_pages = 0;
-  a.page_stride = 0;
-  if (pg) {
-    a.table = pg->table;
-    a.page_size = pg->page_size;
-    a.num_pages = pg->num_pages;
-    a.max_pages = pg->max_pages;
-    a.page_stride = (long)pg->page_size * Hkv * d;
-    a.kv_bstride = 0;
-    a.kv_hstride = bnhd ? d : (long)pg->page_size * d;
-  }
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  return dtype == FA_DTYPE_BF16 ? launch_ragged_d<fa::bf16_t>(a, d, sink, st) : launch_ragged_d<float>(a, d, sink, st);
-}
-
-// One ragged call: the attention (attend), the append (append), or the append then the attention; pg: the paged form.
-int ragged_call(bool attend, bool append, const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out,
-                float* lse, const int* cu, const int* cache_seqlens, const Paging* pg, void* workspace, int B, int H, int Hkv, int T, int Ncap,
-                int d_new, int d, int layout, float softmax_scale, int causal, int dtype, void* stream, int window = 0, int sink = 0) {
-  int rc = pg ? check_pages(*pg, &Ncap) : FA_OK;
-  if (rc == FA_OK && attend)
-    rc = check_ragged(q, k_cache, v_cache, out, cu, workspace, B, H, Hkv, T, Ncap, d, layout, softmax_scale, dtype, pg ? pg->page_size : 0,
-                      window, sink);
-  if (rc == FA_OK && append) rc = check_ragged_append(k_new, v_new, k_cache, v_cache, cu, B, Hkv, T, Ncap, d_new, d, layout, dtype);
-  if (rc == FA_OK && append && pg) rc = check_page_bytes(pg->page_size, Hkv, d, dtype);
-  if (rc != FA_OK) return rc;
-  if (append) {
-    rc = run_append(k_new, v_new, k_cache, v_cache, cache_seqlens, B, Hkv, T, Ncap, d_new, d, layout, dtype, stream, pg, cu);
-    if (rc != FA_OK || !attend) return rc;
-  }
-  return run_ragged(q, k_cache, v_cache, out, lse, cu, cache_seqlens, workspace, B, H, Hkv, T, Ncap, d, layout, softmax_scale, causal, dtype,
-                    stream, pg, window, sink);
-}
-
-}  // namespace
-
-extern "C" {
-
-size_t fa_mi355x_decode_workspace_bytes_gqa(int B, int H, int Hkv, int Nq, int Ncap, int d) {
-  if (!sizes_ok(B, H, Hkv, Nq, Ncap, d)) return 0;
-  return workspace_bytes(B, H, Hkv, Nq, Ncap, d);
-}
-
-int fa_mi355x_decode_splits_gqa(int B, int H, int Hkv, int Nq, int Ncap, int d, int dtype) {
-  (void)dtype;
-  if (!sizes_ok(B, H, Hkv, Nq, Ncap, d)) return 0;
-  return splits(B, H, Hkv, Nq, Ncap);
-}
-
-int fa_mi355x_fwd_decode_gqa(const void* q, const void* k_cache, const void* v_cache, float* out, float* lse, const int* cache_seqlens,
-                             void* workspace, int B, int H, int Hkv, int Nq, int Ncap, int d, int layout, float softmax_scale,
-                             int causal, int dtype, void* stream) {
-  const int rc = check_decode(q, k_cache, v_cache, out, workspace, B, H, Hkv, Nq, Ncap, d, layout, softmax_scale, dtype);
-  if (rc != FA_OK) return rc;
-  return run_decode(q, k_cache, v_cache, out, lse, cache_seqlens, workspace, B, H, Hkv, Nq, Ncap, d, layout, softmax_scale, causal, dtype,
-                    stream);
-}
-
-int fa_mi355x_decode_append(const void* k_new, const void* v_new, void* k_cache, void* v_cache, const int* cache_seqlens, int B, int Hkv,
-                            int Nq, int Ncap, int d_new, int d, int layout, int dtype, void* stream) {
-  const int rc = check_append(k_new, v_new, k_cache, v_cache, B, Hkv, Nq, Ncap, d_new, d, layout, dtype);
-  if (rc != FA_OK) return rc;
-  return run_append(k_new, v_new, k_cache, v_cache, cache_seqlens, B, Hkv, Nq, Ncap, d_new, d, layout, dtype, stream);
-}
-
-int fa_mi355x_fwd_decode_append(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
-                                const int* cache_seqlens, void* workspace, int B, int H, int Hkv, int Nq, int Ncap, int d_new, int d,
-                                int layout, float softmax_scale, int causal, int dtype, void* stream) {
-  int rc = check_decode(q, k_cache, v_cache, out, workspace, B, H, Hkv, Nq, Ncap, d, layout, softmax_scale, dtype);
-  if (rc == FA_OK) rc = check_append(k_new, v_new, k_cache, v_cache, B, Hkv, Nq, Ncap, d_new, d, layout, dtype);
-  if (rc != FA_OK) return rc;
-  rc = run_append(k_new, v_new, k_cache, v_cache, cache_seqlens, B, Hkv, Nq, Ncap, d_new, d, layout, dtype, stream);
-  if (rc != FA_OK) return rc;
-  return run_decode(q, k_cache, v_cache, out, lse, cache_seqlens, workspace, B, H, Hkv, Nq, Ncap, d, layout, softmax_scale, causal, dtype,
-                    stream);
-}
-
-// The extend entry points: any Nq, the extend kernels and their policy; the append is the decode library's own.
-size_t fa_mi355x_extend_workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int d) {
-  if (!sizes_ok(B, H, Hkv, Nq, Ncap, d)) return 0;
-  return ext_workspace_bytes(B, H, Hkv, Nq, Ncap, d);
-}
-
-int fa_mi355x_extend_splits(int B, int H, int Hkv, int Nq, int Ncap, int d, int dtype) {
-  (void)dtype;
-  if (!sizes_ok(B, H, Hkv, Nq, Ncap, d)) return 0;
-  return ext_splits(B, H, Hkv, Nq, Ncap);
-}
-
-int fa_mi355x_fwd_extend(const void* q, const void* k_cache, const void* v_cache, float* out, float* lse, const int* cache_seqlens,
-                         void* workspace, int B, int H, int Hkv, int Nq, int Ncap, int d, int layout, float softmax_scale, int causal,
-                         int dtype, void* stream) {
-  const int rc = check_decode(q, k_cache, v_cache, out, workspace, B, H, Hkv, Nq, Ncap, d, layout, softmax_scale, dtype, true);
-  if (rc != FA_OK) return rc;
-  return run_decode(q, k_cache, v_cache, out, lse, cache_seqlens, workspace, B, H, Hkv, Nq, Ncap, d, layout, softmax_scale, causal, dtype,
-                    stream, true);
-}
-
-int fa_mi355x_extend_append(const void* k_new, const void* v_new, void* k_cache, void* v_cache, const int* cache_seqlens, int B, int Hkv,
-                            int Nq, int Ncap, int d_new, int d, int layout, int dtype, void* stream) {
-  const int rc = check_append(k_new, v_new, k_cache, v_cache, B, Hkv, Nq, Ncap, d_new, d, layout, dtype, true);
-  if (rc != FA_OK) return rc;
-  return run_append(k_new, v_new, k_cache, v_cache, cache_seqlens, B, Hkv, Nq, Ncap, d_new, d, layout, dtype, stream);
-}
-
-int fa_mi355x_fwd_extend_append(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
-                                const int* cache_seqlens, void* workspace, int B, int H, int Hkv, int Nq, int Ncap, int d_new, int d,
-                                int layout, float softmax_scale, int causal, int dtype, void* stream) {
-  int rc = check_decode(q, k_cache, v_cache, out, workspace, B, H, Hkv, Nq, Ncap, d, layout, softmax_scale, dtype, true);
-  if (rc == FA_OK) rc = check_append(k_new, v_new, k_cache, v_cache, B, Hkv, Nq, Ncap, d_new, d, layout, dtype, true);
-  if (rc != FA_OK) return rc;
-  rc = run_append(k_new, v_new, k_cache, v_cache, cache_seqlens, B, Hkv, Nq, Ncap, d_new, d, layout, dtype, stream);
-  if (rc != FA_OK) return rc;
-  return run_decode(q, k_cache, v_cache, out, lse, cache_seqlens, workspace, B, H, Hkv, Nq, Ncap, d, layout, softmax_scale, causal, dtype,
-                    stream, true);
-}
-
-// The paged entry points: the _gqa / extend forms above on a pool of pages read through a block table.
-namespace {
-
-// One decode or extend call, fused with the append or not, on a pool (pg: Ncap comes from its geometry) or on slabs of Ncap rows
-// (pg null), windowed or not.
-int attend(bool extend, bool fused, const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
-           const int* cache_seqlens, const Paging* pg, void* workspace, int B, int H, int Hkv, int Nq, int Ncap, int d_new, int d, int layout,
-           float softmax_scale, int causal, int dtype, void* stream, int window = 0, const Fp8* f8 = nullptr, int sink = 0) {
-  int rc = pg ? check_pages(*pg, &Ncap) : FA_OK;
-  if (rc == FA_OK)
-    rc = check_decode(q, k_cache, v_cache, out, workspace, B, H, Hkv, Nq, Ncap, d, layout, softmax_scale, dtype, extend, pg ? pg->page_size : 0,
-                      window, f8 != nullptr, sink);
-  if (rc == FA_OK && fused) rc = check_append(k_new, v_new, k_cache, v_cache, B, Hkv, Nq, Ncap, d_new, d, layout, dtype, extend);
-  if (rc != FA_OK) return rc;
-  if (fused) {
-    rc = run_append(k_new, v_new, k_cache, v_cache, cache_seqlens, B, Hkv, Nq, Ncap, d_new, d, layout, dtype, stream, pg, nullptr, f8);
-    if (rc != FA_OK) return rc;
-  }
-  return run_decode(q, k_cache, v_cache, out, lse, cache_seqlens, workspace, B, H, Hkv, Nq, Ncap, d, layout, softmax_scale, causal, dtype,
-                    stream, extend, pg, window, f8, sink);
-}
-
-// The check an fp8 call makes first: the queries and the new tokens are bf16.
-int check_fp8(int dtype) {
-  g_err[0] = 0;
-  if (dtype == FA_DTYPE_F32)
-    return set_err(FA_ERR_BAD_ARG, "an fp8 cache takes bf16 queries and new tokens: FA_DTYPE_F32 is not supported (dtype must be FA_DTYPE_BF16)");
-  if (dtype != FA_DTYPE_BF16) return set_err(FA_ERR_BAD_ARG, "unknown dtype");
-  return FA_OK;
-}
-
-// The checks a windowed call makes first (sink: 0 in the calls that have none).
-int check_window(int window, int causal, int sink = 0) {
-  g_err[0] = 0;
-  if (sink < 0) return set_err(FA_ERR_BAD_ARG, "sink must not be negative (0: no sink tokens)");
-  if (window < 0) return set_err(FA_ERR_BAD_ARG, "window must not be negative (0: no window)");
-  if (window > 0 && !causal)
-    return set_err(FA_ERR_BAD_ARG, "a sliding window needs the causal mask: window > 0 with causal = 0 (the window ends at the query's position)");
-  return FA_OK;
-}
-
-int append_paged(bool extend, const void* k_new, const void* v_new, void* k_pool, void* v_pool, const int* cache_seqlens, const Paging& pg,
-                 int B, int Hkv, int Nq, int d_new, int d, int layout, int dtype, void* stream) {
-  int Ncap = 0;
-  int rc = check_pages(pg, &Ncap);
-  if (rc == FA_OK) rc = check_append(k_new, v_new, k_pool, v_pool, B, Hkv, Nq, Ncap, d_new, d, layout, dtype, extend);
-  if (rc == FA_OK) rc = check_page_bytes(pg.page_size, Hkv, d, dtype);
-  if (rc != FA_OK) return rc;
-  return run_append(k_new, v_new, k_pool, v_pool, cache_seqlens, B, Hkv, Nq, Ncap, d_new, d, layout, dtype, stream, &pg);
-}
-
-}  // namespace
-
-int fa_mi355x_fwd_decode_paged(const void* q, const void* k_pool, const void* v_pool, float* out, float* lse, const int* cache_seqlens,
-                               const int* block_table, void* workspace, int B, int H, int Hkv, int Nq, int num_pages, int page_size,
-                               int max_pages, int d, int layout, float softmax_scale, int causal, int dtype, void* stream) {
-  const Paging pg = {block_table, num_pages, page_size, max_pages};
-  return attend(false, false, q, nullptr, nullptr, const_cast<void*>(k_pool), const_cast<void*>(v_pool), out, lse, cache_seqlens, &pg,
-                workspace, B, H, Hkv, Nq, 0, d, d, layout, softmax_scale, causal, dtype, stream);
-}
-
-int fa_mi355x_fwd_extend_paged(const void* q, const void* k_pool, const void* v_pool, float* out, float* lse, const int* cache_seqlens,
-                               const int* block_table, void* workspace, int B, int H, int Hkv, int Nq, int num_pages, int page_size,
-                               int max_pages, int d, int layout, float softmax_scale, int causal, int dtype, void* stream) {
-  const Paging pg = {block_table, num_pages, page_size, max_pages};
-  return attend(true, false, q, nullptr, nullptr, const_cast<void*>(k_pool), const_cast<void*>(v_pool), out, lse, cache_seqlens, &pg,
-                workspace, B, H, Hkv, Nq, 0, d, d, layout, softmax_scale, causal, dtype, stream);
-}
-
-int fa_mi355x_decode_append_paged(const void* k_new, const void* v_new, void* k_pool, void* v_pool, const int* cache_seqlens,
-                                  const int* block_table, int B, int Hkv, int Nq, int num_pages, int page_size, int max_pages, int d_new,
-                                  int d, int layout, int dtype, void* stream) {
-  const Paging pg = {block_table, num_pages, page_size, max_pages};
-  return append_paged(false, k_new, v_new, k_pool, v_pool, cache_seqlens, pg, B, Hkv, Nq, d_new, d, layout, dtype, stream);
-}
-
-int fa_mi355x_extend_append_paged(const void* k_new, const void* v_new, void* k_pool, void* v_pool, const int* cache_seqlens,
-                                  const int* block_table, int B, int Hkv, int Nq, int num_pages, int page_size, int max_pages, int d_new,
-                                  int d, int layout, int dtype, void* stream) {
-  const Paging pg = {block_table, num_pages, page_size, max_pages};
-  return append_paged(true, k_new, v_new, k_pool, v_pool, cache_seqlens, pg, B, Hkv, Nq, d_new, d, layout, dtype, stream);
-}
-
-int fa_mi355x_fwd_decode_append_paged(const void* q, const void* k_new, const void* v_new, void* k_pool, void* v_pool, float* out,
-                                      float* lse, const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv,
-                                      int Nq, int num_pages, int page_size, int max_pages, int d_new, int d, int layout,
-                                      float softmax_scale, int causal, int dtype, void* stream) {
-  const Paging pg = {block_table, num_pages, page_size, max_pages};
-  return attend(false, true, q, k_new, v_new, k_pool, v_pool, out, lse, cache_seqlens, &pg, workspace, B, H, Hkv, Nq, 0, d_new, d, layout,
-                softmax_scale, causal, dtype, stream);
-}
-
-int fa_mi355x_fwd_extend_append_paged(const void* q, const void* k_new, const void* v_new, void* k_pool, void* v_pool, float* out,
-                                      float* lse, const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv,
-                                      int Nq, int num_pages, int page_size, int max_pages, int d_new, int d, int layout,
-                                      float softmax_scale, int causal, int dtype, void* stream) {
-  const Paging pg = {block_table, num_pages, page_size, max_pages};
-  return attend(true, true, q, k_new, v_new, k_pool, v_pool, out, lse, cache_seqlens, &pg, workspace, B, H, Hkv, Nq, 0, d_new, d, layout,
-                softmax_scale, causal, dtype, stream);
-}
-
-// The ragged entry points (include/flash_attn_mi355x_decode_ragged.h): the new tokens of all sequences packed into T rows, the
-// sequences' boundaries in cu_seqlens_q on the device.
-int fa_mi355x_ragged_splits(int B, int H, int Hkv, int T, int Ncap, int d, int dtype) {
-  (void)dtype;
-  if (!sizes_ok(B, H, Hkv, T, Ncap, d)) return 0;
-  return rag_splits(B, H, Hkv, T, Ncap);
-}
-
-size_t fa_mi355x_ragged_workspace_bytes(int B, int H, int Hkv, int T, int Ncap, int d) {
-  if (!sizes_ok(B, H, Hkv, T, Ncap, d)) return 0;
-  return rag_workspace_bytes(B, H, Hkv, T, Ncap, d);
-}
-
-int fa_mi355x_fwd_ragged(const void* q, const void* k_cache, const void* v_cache, float* out, float* lse, const int* cu_seqlens_q,
-                         const int* cache_seqlens, void* workspace, int B, int H, int Hkv, int T, int Ncap, int d, int layout,
-                         float softmax_scale, int causal, int dtype, void* stream) {
-  return ragged_call(true, false, q, nullptr, nullptr, const_cast<void*>(k_cache), const_cast<void*>(v_cache), out, lse, cu_seqlens_q,
-                     cache_seqlens, nullptr, workspace, B, H, Hkv, T, Ncap, d, d, layout, softmax_scale, causal, dtype, stream);
-}
-
-int fa_mi355x_ragged_append(const void* k_new, const void* v_new, void* k_cache, void* v_cache, const int* cu_seqlens_q,
-                            const int* cache_seqlens, int B, int Hkv, int T, int Ncap, int d_new, int d, int layout, int dtype,
-                            void* stream) {
-  return ragged_call(false, true, nullptr, k_new, v_new, k_cache, v_cache, nullptr, nullptr, cu_seqlens_q, cache_seqlens, nullptr, nullptr, B,
-                     Hkv, Hkv, T, Ncap, d_new, d, layout, 0.f, 0, dtype, stream);
-}
-
-int fa_mi355x_fwd_ragged_append(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
-                                const int* cu_seqlens_q, const int* cache_seqlens, void* workspace, int B, int H, int Hkv, int T,
-                                int Ncap, int d_new, int d, int layout, float softmax_scale, int causal, int dtype, void* stream) {
-  return ragged_call(true, true, q, k_new, v_new, k_cache, v_cache, out, lse, cu_seqlens_q, cache_seqlens, nullptr, workspace, B, H, Hkv, T,
-                     Ncap, d_new, d, layout, softmax_scale, causal, dtype, stream);
-}
-
-int fa_mi355x_fwd_ragged_paged(const void* q, const void* k_pool, const void* v_pool, float* out, float* lse, const int* cu_seqlens_q,
-                               const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv, int T,
-                               int num_pages, int page_size, int max_pages, int d, int layout, float softmax_scale, int causal,
-                               int dtype, void* stream) {
-  const Paging pg = {block_table, num_pages, page_size, max_pages};
-  return ragged_call(true, false, q, nullptr, nullptr, const_cast<void*>(k_pool), const_cast<void*>(v_pool), out, lse, cu_seqlens_q,
-                     cache_seqlens, &pg, workspace, B, H, Hkv, T, 0, d, d, layout, softmax_scale, causal, dtype, stream);
-}
-
-int fa_mi355x_ragged_append_paged(const void* k_new, const void* v_new, void* k_pool, void* v_pool, const int* cu_seqlens_q,
-                                  const int* cache_seqlens, const int* block_table, int B, int Hkv, int T, int num_pages, int page_size,
-                                  int max_pages, int d_new, int d, int layout, int dtype, void* stream) {
-  const Paging pg = {block_table, num_pages, page_size, max_pages};
-  return ragged_call(false, true, nullptr, k_new, v_new, k_pool, v_pool, nullptr, nullptr, cu_seqlens_q, cache_seqlens, &pg, nullptr, B, Hkv,
-                     Hkv, T, 0, d_new, d, layout, 0.f, 0, dtype, stream);
-}
-
-int fa_mi355x_fwd_ragged_append_paged(const void* q, const void* k_new, const void* v_new, void* k_pool, void* v_pool, float* out,
-                                      float* lse, const int* cu_seqlens_q, const int* cache_seqlens, const int* block_table,
-                                      void* workspace, int B, int H, int Hkv, int T, int num_pages, int page_size, int max_pages,
-                                      int d_new, int d, int layout, float softmax_scale, int causal, int dtype, void* stream) {
-  const Paging pg = {block_table, num_pages, page_size, max_pages};
-  return ragged_call(true, true, q, k_new, v_new, k_pool, v_pool, out, lse, cu_seqlens_q, cache_seqlens, &pg, workspace, B, H, Hkv, T, 0,
-                     d_new, d, layout, softmax_scale, causal, dtype, stream);
-}
-
-// The windowed entry points (include/flash_attn_mi355x_decode_window.h): one per call family.  k_new / v_new null: attend only;
-// block_table null: slabs of Ncap rows, otherwise the pool's geometry stands for Ncap.
-int fa_mi355x_decode_window_splits(int B, int H, int Hkv, int Nq, int Ncap, int d, int dtype, int window) {
-  (void)dtype;
-  if (!sizes_ok(B, H, Hkv, Nq, Ncap, d) || window < 0) return 0;
-  return splits(B, H, Hkv, Nq, span_keys(window, Ncap, Nq, 32));
-}
-
-size_t fa_mi355x_decode_window_workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int d, int window) {
-  if (!sizes_ok(B, H, Hkv, Nq, Ncap, d) || window < 0) return 0;
-  return workspace_bytes(B, H, Hkv, Nq, span_keys(window, Ncap, Nq, 32), d);
-}
-
-int fa_mi355x_extend_window_splits(int B, int H, int Hkv, int Nq, int Ncap, int d, int dtype, int window) {
-  (void)dtype;
-  if (!sizes_ok(B, H, Hkv, Nq, Ncap, d) || window < 0) return 0;
-  return ext_splits(B, H, Hkv, Nq, span_keys(window, Ncap, Nq, fa::EXT_BLOCK));
-}
-
-size_t fa_mi355x_extend_window_workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int d, int window) {
-  if (!sizes_ok(B, H, Hkv, Nq, Ncap, d) || window < 0) return 0;
-  return ext_workspace_bytes(B, H, Hkv, Nq, span_keys(window, Ncap, Nq, fa::EXT_BLOCK), d);
-}
-
-int fa_mi355x_ragged_window_splits(int B, int H, int Hkv, int T, int Ncap, int d, int dtype, int window) {
-  (void)dtype;
-  if (!sizes_ok(B, H, Hkv, T, Ncap, d) || window < 0) return 0;
-  return rag_splits(B, H, Hkv, T, span_keys(window, Ncap, T, fa::EXT_BLOCK));
-}
-
-size_t fa_mi355x_ragged_window_workspace_bytes(int B, int H, int Hkv, int T, int Ncap, int d, int window) {
-  if (!sizes_ok(B, H, Hkv, T, Ncap, d) || window < 0) return 0;
-  return rag_workspace_bytes(B, H, Hkv, T, span_keys(window, Ncap, T, fa::EXT_BLOCK), d);
-}
-
-int fa_mi355x_fwd_decode_window(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
-                                const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv, int Nq, int Ncap,
-                                int num_pages, int page_size, int max_pages, int d_new, int d, int layout, float softmax_scale, int causal,
-                                int window, int dtype, void* stream) {
-  const int rc = check_window(window, causal);
-  if (rc != FA_OK) return rc;
-  const Paging pg = {block_table, num_pages, page_size, max_pages};
-  return attend(false, k_new || v_new, q, k_new, v_new, k_cache, v_cache, out, lse, cache_seqlens, block_table ? &pg : nullptr, workspace, B, H,
-                Hkv, Nq, Ncap, d_new, d, layout, softmax_scale, causal, dtype, stream, window);
-}
-
-int fa_mi355x_fwd_extend_window(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
-                                const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv, int Nq, int Ncap,
-                                int num_pages, int page_size, int max_pages, int d_new, int d, int layout, float softmax_scale, int causal,
-                                int window, int dtype, void* stream) {
-  const int rc = check_window(window, causal);
-  if (rc != FA_OK) return rc;
-  const Paging pg = {block_table, num_pages, page_size, max_pages};
-  return attend(true, k_new || v_new, q, k_new, v_new, k_cache, v_cache, out, lse, cache_seqlens, block_table ? &pg : nullptr, workspace, B, H,
-                Hkv, Nq, Ncap, d_new, d, layout, softmax_scale, causal, dtype, stream, window);
-}
-
-int fa_mi355x_fwd_ragged_window(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
-                                const int* cu_seqlens_q, const int* cache_seqlens, const int* block_table, void* workspace, int B, int H,
-                                int Hkv, int T, int Ncap, int num_pages, int page_size, int max_pages, int d_new, int d, int layout,
-                                float softmax_scale, int causal, int window, int dtype, void* stream) {
-  const int rc = check_window(window, causal);
-  if (rc != FA_OK) return rc;
-  const Paging pg = {block_table, num_pages, page_size, max_pages};
-  return ragged_call(true, k_new || v_new, q, k_new, v_new, k_cache, v_cache, out, lse, cu_seqlens_q, cache_seqlens,
-                     block_table ? &pg : nullptr, workspace, B, H, Hkv, T, Ncap, d_new, d, layout, softmax_scale, causal, dtype, stream, window);
-}
-
-// The sink entry points (include/flash_attn_mi355x_decode_sink.h): the windowed ones with `sink` first positions kept beside the window.
-int fa_mi355x_decode_sink_splits(int B, int H, int Hkv, int Nq, int Ncap, int d, int dtype, int window, int sink) {
-  (void)dtype;
-  if (!sizes_ok(B, H, Hkv, Nq, Ncap, d) || window < 0 || sink < 0) return 0;
-  return splits(B, H, Hkv, Nq, span_keys(window, Ncap, Nq, 32, sink));
-}
-
-size_t fa_mi355x_decode_sink_workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int d, int window, int sink) {
-  if (!sizes_ok(B, H, Hkv, Nq, Ncap, d) || window < 0 || sink < 0) return 0;
-  return workspace_bytes(B, H, Hkv, Nq, span_keys(window, Ncap, Nq, 32, sink), d);
-}
-
-int fa_mi355x_extend_sink_splits(int B, int H, int Hkv, int Nq, int Ncap, int d, int dtype, int window, int sink) {
-  (void)dtype;
-  if (!sizes_ok(B, H, Hkv, Nq, Ncap, d) || window < 0 || sink < 0) return 0;
-  return ext_splits(B, H, Hkv, Nq, span_keys(window, Ncap, Nq, fa::EXT_BLOCK, sink));
-}
-
-size_t fa_mi355x_extend_sink_workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int d, int window, int sink) {
-  if (!sizes_ok(B, H, Hkv, Nq, Ncap, d) || window < 0 || sink < 0) return 0;
-  return ext_workspace_bytes(B, H, Hkv, Nq, span_keys(window, Ncap, Nq, fa::EXT_BLOCK, sink), d);
-}
-
-int fa_mi355x_ragged_sink_splits(int B, int H, int Hkv, int T, int Ncap, int d, int dtype, int window, int sink) {
-  (void)dtype;
-  if (!sizes_ok(B, H, Hkv, T, Ncap, d) || window < 0 || sink < 0) return 0;
-  return rag_splits(B, H, Hkv, T, span_keys(window, Ncap, T, fa::EXT_BLOCK, sink));
-}
-
-size_t fa_mi355x_ragged_sink_workspace_bytes(int B, int H, int Hkv, int T, int Ncap, int d, int window, int sink) {
-  if (!sizes_ok(B, H, Hkv, T, Ncap, d) || window < 0 || sink < 0) return 0;
-  return rag_workspace_bytes(B, H, Hkv, T, span_keys(window, Ncap, T, fa::EXT_BLOCK, sink), d);
-}
-
-int fa_mi355x_fwd_decode_sink(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
-                              const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv, int Nq, int Ncap,
-                              int num_pages, int page_size, int max_pages, int d_new, int d, int layout, float softmax_scale, int causal,
-                              int window, int sink, int dtype, void* stream) {
-  const int rc = check_window(window, causal, sink);
-  if (rc != FA_OK) return rc;
-  const Paging pg = {block_table, num_pages, page_size, max_pages};
-  return attend(false, k_new || v_new, q, k_new, v_new, k_cache, v_cache, out, lse, cache_seqlens, block_table ? &pg : nullptr, workspace, B, H,
-                Hkv, Nq, Ncap, d_new, d, layout, softmax_scale, causal, dtype, stream, window, nullptr, sink);
-}
-
-int fa_mi355x_fwd_extend_sink(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
-                              const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv, int Nq, int Ncap,
-                              int num_pages, int page_size, int max_pages, int d_new, int d, int layout, float softmax_scale, int causal,
-                              int window, int sink, int dtype, void* stream) {
-  const int rc = check_window(window, causal, sink);
-  if (rc != FA_OK) return rc;
-  const Paging pg = {block_table, num_pages, page_size, max_pages};
-  return attend(true, k_new || v_new, q, k_new, v_new, k_cache, v_cache, out, lse, cache_seqlens, block_table ? &pg : nullptr, workspace, B, H,
-                Hkv, Nq, Ncap, d_new, d, layout, softmax_scale, causal, dtype, stream, window, nullptr, sink);
-}
-
-int fa_mi355x_fwd_ragged_sink(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
-                              const int* cu_seqlens_q, const int* cache_seqlens, const int* block_table, void* workspace, int B, int H,
-                              int Hkv, int T, int Ncap, int num_pages, int page_size, int max_pages, int d_new, int d, int layout,
-                              float softmax_scale, int causal, int window, int sink, int dtype, void* stream) {
-  const int rc = check_window(window, causal, sink);
-  if (rc != FA_OK) return rc;
-  const Paging pg = {block_table, num_pages, page_size, max_pages};
-  return ragged_call(true, k_new || v_new, q, k_new, v_new, k_cache, v_cache, out, lse, cu_seqlens_q, cache_seqlens,
-                     block_table ? &pg : nullptr, workspace, B, H, Hkv, T, Ncap, d_new, d, layout, softmax_scale, causal, dtype, stream, window,
-                     sink);
-}
-
-// The fp8 entry points (include/flash_attn_mi355x_decode_fp8.h): caches of e4m3 bytes with per-kv-head scales.  k_new / v_new null:
-// attend only; block_table null: slabs of Ncap rows.
-int fa_mi355x_fwd_decode_fp8(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, const float* k_scale,
-                             const float* v_scale, float* out, float* lse, const int* cache_seqlens, const int* block_table, void* workspace,
-                             int B, int H, int Hkv, int Nq, int Ncap, int num_pages, int page_size, int max_pages, int d_new, int d,
-                             int layout, float softmax_scale, int causal, int dtype, void* stream) {
-  const int rc = check_fp8(dtype);
-  if (rc != FA_OK) return rc;
-  const Paging pg = {block_table, num_pages, page_size, max_pages};
-  const Fp8 f8 = {k_scale, v_scale};
-  return attend(false, k_new || v_new, q, k_new, v_new, k_cache, v_cache, out, lse, cache_seqlens, block_table ? &pg : nullptr, workspace, B, H,
-                Hkv, Nq, Ncap, d_new, d, layout, softmax_scale, causal, dtype, stream, 0, &f8);
-}
-
-int fa_mi355x_fwd_extend_fp8(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, const float* k_scale,
-                             const float* v_scale, float* out, float* lse, const int* cache_seqlens, const int* block_table, void* workspace,
-                             int B, int H, int Hkv, int Nq, int Ncap, int num_pages, int page_size, int max_pages, int d_new, int d,
-                             int layout, float softmax_scale, int causal, int dtype, void* stream) {
-  const int rc = check_fp8(dtype);
-  if (rc != FA_OK) return rc;
-  const Paging pg = {block_table, num_pages, page_size, max_pages};
-  const Fp8 f8 = {k_scale, v_scale};
-  return attend(true, k_new || v_new, q, k_new, v_new, k_cache, v_cache, out, lse, cache_seqlens, block_table ? &pg : nullptr, workspace, B, H,
-                Hkv, Nq, Ncap, d_new, d, layout, softmax_scale, causal, dtype, stream, 0, &f8);
-}
-
-int fa_mi355x_append_fp8(const void* k_new, const void* v_new, void* k_cache, void* v_cache, const float* k_scale, const float* v_scale,
-                         const int* cache_seqlens, const int* block_table, int B, int Hkv, int Nq, int Ncap, int num_pages, int page_size,
-                         int max_pages, int d_new, int d, int layout, int dtype, void* stream) {
-  int rc = check_fp8(dtype);
-  const Paging pg = {block_table, num_pages, page_size, max_pages};
-  if (rc == FA_OK && block_table) rc = check_pages(pg, &Ncap);
-  if (rc == FA_OK) rc = check_append(k_new, v_new, k_cache, v_cache, B, Hkv, Nq, Ncap, d_new, d, layout, dtype, true);
-  if (rc == FA_OK) {   // (a store's row offset is added to a 64-bit address: the bound is the attention's, whose loads read these rows)
-    if (block_table)
-      rc = check_page_bytes(page_size, Hkv, d, dtype, true);
-    else if (((long)Ncap + fa::DEC_ROWS) * Hkv * d >= (1L << 31))
-      rc = set_err(FA_ERR_BAD_ARG, "one batch element of the cache must stay under 2 GiB");
-  }
-  if (rc != FA_OK) return rc;
-  const Fp8 f8 = {k_scale, v_scale};
-  return run_append(k_new, v_new, k_cache, v_cache, cache_seqlens, B, Hkv, Nq, Ncap, d_new, d, layout, dtype, stream, block_table ? &pg : nullptr,
-                    nullptr, &f8);
-}
-
-// The rotary entry points (include/flash_attn_mi355x_decode_rope.h): a tensor rotated by position, and the roped append that goes
-// in front of the EXISTING attend-only entry points (rope_kernel and rope_append_kernel of fa_rope.h; no attention kernel changes).
-}  // extern "C"  (the launchers below are templates)
-
-namespace {
-
+// ---- rotary embeddings (include/flash_attn_mi355x_decode_rope.h) ----
+// A tensor rotated by position, and the roped append that goes in front of the EXISTING attend-only entry points (rope_kernel and
+// rope_append_kernel of fa_rope.h; no attention kernel changes).
 // The checks of the tables and the rotary dimension; row_len: the shortest row that is rotated.
 int check_rope(const void* cos, const void* sin, int rot, int row_len, int max_pos, int interleaved, int inverse) {
   if (!cos || !sin) return set_err(FA_ERR_BAD_ARG, "null cos or sin (the rotary tables, fp32 [max_pos][rot / 2])");
@@ -1097,142 +576,458 @@ bool rope_vec(int E, int rot, int interleaved, int len_a, int len_b, uintptr_t p
 template <typename T, int E> int launch_rope(fa::RopeArgs a, bool il, hipStream_t st) {
   a.cpr = a.d / E;
   a.lanes *= a.cpr;   // (rows on entry)
-  const dim3 grid((unsigned)((a.lanes + 255) / 256));
-  if (il)
-    hipLaunchKernelGGL((fa::rope_kernel<T, E, true>), grid, dim3(256), 0, st, a);
-  else
-    hipLaunchKernelGGL((fa::rope_kernel<T, E, false>), grid, dim3(256), 0, st, a);
+  const long grid = (a.lanes + 255) / 256;
+  if (il) launch256(fa::rope_kernel<T, E, true>, grid, st, a);
+  else launch256(fa::rope_kernel<T, E, false>, grid, st, a);
   const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? FA_OK : set_err(FA_ERR_HIP, "rope_kernel launch", e);
+  return e == hipSuccess ? FA_OK : hip_err("rope_kernel launch", e);
 }
 
-template <typename T, int E, bool IL, bool FP8> void launch_rope_append_il(const fa::RopeAppendArgs& a, dim3 grid, hipStream_t st) {
+template <typename T, int E, bool IL, bool FP8> void launch_rope_append_il(const fa::RopeAppendArgs& a, long grid, hipStream_t st) {
   if constexpr (FP8) {
-    if (a.table)
-      hipLaunchKernelGGL((fa::rope_append_kernel<T, E, IL, true, false, true>), grid, dim3(256), 0, st, a);
-    else
-      hipLaunchKernelGGL((fa::rope_append_kernel<T, E, IL, false, false, true>), grid, dim3(256), 0, st, a);
-  } else if (a.cu && a.table)
-    hipLaunchKernelGGL((fa::rope_append_kernel<T, E, IL, true, true>), grid, dim3(256), 0, st, a);
-  else if (a.cu)
-    hipLaunchKernelGGL((fa::rope_append_kernel<T, E, IL, false, true>), grid, dim3(256), 0, st, a);
-  else if (a.table)
-    hipLaunchKernelGGL((fa::rope_append_kernel<T, E, IL, true>), grid, dim3(256), 0, st, a);
-  else
-    hipLaunchKernelGGL((fa::rope_append_kernel<T, E, IL>), grid, dim3(256), 0, st, a);
+    if (a.table) launch256(fa::rope_append_kernel<T, E, IL, true, false, true>, grid, st, a);
+    else launch256(fa::rope_append_kernel<T, E, IL, false, false, true>, grid, st, a);
+  } else if (a.cu && a.table) launch256(fa::rope_append_kernel<T, E, IL, true, true>, grid, st, a);
+  else if (a.cu) launch256(fa::rope_append_kernel<T, E, IL, false, true>, grid, st, a);
+  else if (a.table) launch256(fa::rope_append_kernel<T, E, IL, true>, grid, st, a);
+  else launch256(fa::rope_append_kernel<T, E, IL>, grid, st, a);
 }
 
-template <typename T, int E, bool FP8 = false> int launch_rope_append(fa::RopeAppendArgs a, bool il, hipStream_t st) {
+template <typename T, int E, bool FP8> int launch_rope_append(fa::RopeAppendArgs a, bool il, hipStream_t st) {
   a.ch_shift = __builtin_ctz(a.d / E);
   a.lanes <<= a.ch_shift;     // (rows on entry)
   a.q_lanes <<= a.ch_shift;
-  const dim3 grid((unsigned)((a.q_lanes + a.lanes + 255) / 256));
+  const long grid = (a.q_lanes + a.lanes + 255) / 256;
   if (il)
     launch_rope_append_il<T, E, true, FP8>(a, grid, st);
   else
     launch_rope_append_il<T, E, false, FP8>(a, grid, st);
   const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? FA_OK : set_err(FA_ERR_HIP, "rope_append_kernel launch", e);
+  return e == hipSuccess ? FA_OK : hip_err("rope_append_kernel launch", e);
 }
 
-// One roped append, uniform (cu null: Nq new tokens per batch element) or ragged (cu: Nq = T packed rows); q / q_rot or
-// k_new / v_new may be absent (both null).  Every check comes first; then the one launch.
-int rope_append_call(const void* q, void* q_rot, const void* k_new, const void* v_new, void* k_cache, void* v_cache, const Fp8* f8,
-                     const float* cos, const float* sin, const int* cu, bool ragged, const int* cache_seqlens, const Paging* pg, int B, int H,
-                     int Hkv, int Nq, int Ncap, int d_new, int d, int rot, int max_pos, int layout, int interleaved, int dtype,
-                     void* stream) {
+// What a roped append takes beside the cache call: where the rotated q goes, the tables and the rotary dimension.
+struct Rope {
+  void* q_rot;
+  const float *cos, *sin;
+  int rot, max_pos, interleaved;
+};
+
+// One roped append, uniform (the extend family: Nq new tokens per batch element, any number) or ragged (Nq = T packed rows); q / q_rot
+// or k_new / v_new may be absent (both null).  Every check comes first; then the one launch.
+int rope_append_call(KvCall c, const Rope& r) {
+  const bool ragged = c.family == RAGGED;
   g_err[0] = 0;
-  int rc = f8 ? check_fp8(dtype) : FA_OK;
+  int rc = c.f8.on ? check_fp8(c.dtype) : FA_OK;
   if (rc != FA_OK) return rc;
-  if ((q == nullptr) != (q_rot == nullptr)) return set_err(FA_ERR_BAD_ARG, "q and q_rot go together: give both, or neither (append only)");
-  if ((k_new == nullptr) != (v_new == nullptr))
+  if ((c.q == nullptr) != (r.q_rot == nullptr)) return set_err(FA_ERR_BAD_ARG, "q and q_rot go together: give both, or neither (append only)");
+  if ((c.k_new == nullptr) != (c.v_new == nullptr))
     return set_err(FA_ERR_BAD_ARG, "k_new and v_new go together: give both, or neither (rotate q only)");
-  if (!q && !k_new) return set_err(FA_ERR_BAD_ARG, "nothing to do: q / q_rot and k_new / v_new are all null");
-  if (pg) rc = check_pages(*pg, &Ncap);
+  if (!c.q && !c.k_new) return set_err(FA_ERR_BAD_ARG, "nothing to do: q / q_rot and k_new / v_new are all null");
+  if (c.paged) rc = check_pages(c.pg, &c.Ncap);
   if (rc != FA_OK) return rc;
-  if (k_new) {
-    rc = ragged ? check_ragged_append(k_new, v_new, k_cache, v_cache, cu, B, Hkv, Nq, Ncap, d_new, d, layout, dtype)
-                : check_append(k_new, v_new, k_cache, v_cache, B, Hkv, Nq, Ncap, d_new, d, layout, dtype, true);
-    if (rc == FA_OK && pg) rc = check_page_bytes(pg->page_size, Hkv, d, dtype, f8 != nullptr);
-    if (rc == FA_OK && f8 && !pg && ((long)Ncap + fa::DEC_ROWS) * Hkv * d >= (1L << 31))
-      rc = set_err(FA_ERR_BAD_ARG, "one batch element of the cache must stay under 2 GiB");
+  if (c.k_new) {
+    rc = check_append(c);
     if (rc != FA_OK) return rc;
   } else {
-    if (B <= 0 || Nq <= 0 || Ncap <= 0 || d <= 0) return set_err(FA_ERR_BAD_ARG, "B, Nq (T), Ncap and d must be positive");
-    if (dtype != FA_DTYPE_F32 && dtype != FA_DTYPE_BF16) return set_err(FA_ERR_BAD_ARG, "unknown dtype");
-    if (layout != FA_LAYOUT_BHND && layout != FA_LAYOUT_BNHD) return set_err(FA_ERR_BAD_ARG, "unknown layout");
-    if (ragged && !cu) return set_err(FA_ERR_BAD_ARG, "null cu_seqlens_q");
-    if (d != 32 && d != 64 && d != 128) return set_err(FA_ERR_UNSUPPORTED_D, "decode supports rows of d in {32, 64, 128}");
-    d_new = d;
+    if (c.B <= 0 || c.Nq <= 0 || c.Ncap <= 0 || c.d <= 0) return set_err(FA_ERR_BAD_ARG, "B, Nq (T), Ncap and d must be positive");
+    if (c.dtype != FA_DTYPE_F32 && c.dtype != FA_DTYPE_BF16) return set_err(FA_ERR_BAD_ARG, "unknown dtype");
+    if (c.layout != FA_LAYOUT_BHND && c.layout != FA_LAYOUT_BNHD) return set_err(FA_ERR_BAD_ARG, "unknown layout");
+    if (ragged && !c.cu) return set_err(FA_ERR_BAD_ARG, "null cu_seqlens_q");
+    if (c.d != 32 && c.d != 64 && c.d != 128) return set_err(FA_ERR_UNSUPPORTED_D, "decode supports rows of d in {32, 64, 128}");
+    c.d_new = c.d;
   }
-  if (q) {
-    if (H <= 0) return set_err(FA_ERR_BAD_ARG, "H must be positive");
+  if (c.q) {
+    if (c.H <= 0) return set_err(FA_ERR_BAD_ARG, "H must be positive");
     // (one lane per element at the most, the workgroup count of q's and the new rows' lanes together an unsigned int)
-    if ((long)(ragged ? 1 : B) * Nq * H * d / 256 >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "too many q elements for one rope_append launch");
+    if (c.seqs() * c.Nq * c.H * c.d / 256 >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "too many q elements for one rope_append launch");
   }
-  rc = check_rope(cos, sin, rot, std::min(d_new, d), max_pos, interleaved, 0);
+  rc = check_rope(r.cos, r.sin, r.rot, std::min(c.d_new, c.d), r.max_pos, r.interleaved, 0);
   if (rc != FA_OK) return rc;
-  if (max_pos < Ncap) {
-    snprintf(g_err, sizeof(g_err), "max_pos = %d table rows do not cover the cache's capacity of %d rows: every row needs an angle", max_pos, Ncap);
+  if (r.max_pos < c.Ncap) {
+    snprintf(g_err, sizeof(g_err), "max_pos = %d table rows do not cover the cache's capacity of %d rows: every row needs an angle", r.max_pos,
+             c.Ncap);
     return FA_ERR_BAD_ARG;
   }
   fa::RopeAppendArgs a;
-  a.k_new = k_new;
-  a.v_new = v_new;
-  a.k = k_cache;
-  a.v = v_cache;
-  a.seqlens = cache_seqlens;
-  const long seqs = ragged ? 1 : B;
-  a.lanes = k_new ? seqs * Nq * Hkv : 0;
-  a.q_lanes = q ? seqs * Nq * H : 0;
-  a.Hkv = Hkv;
-  a.Nq = Nq;
-  a.Ncap = Ncap;
-  a.d_new = d_new;
-  a.bnhd = layout == FA_LAYOUT_BNHD;
-  a.kv_ld = a.bnhd ? Hkv * d : d;
-  a.kv_bstride = (long)Ncap * Hkv * d;
-  a.kv_hstride = a.bnhd ? d : (long)Ncap * d;
-  a.table = nullptr;
-  a.page_size = a.num_pages = a.max_pages = 0;
-  a.page_stride = 0;
-  if (pg) {
-    a.table = pg->table;
-    a.page_size = pg->page_size;
-    a.num_pages = pg->num_pages;
-    a.max_pages = pg->max_pages;
-    a.page_stride = (long)pg->page_size * Hkv * d;
-    a.kv_bstride = 0;
-    a.kv_hstride = a.bnhd ? d : (long)pg->page_size * d;
-  }
-  a.q = q;
-  a.q_rot = q_rot;
-  a.cos = cos;
-  a.sin = sin;
-  a.k_scale = f8 ? f8->k_scale : nullptr;
-  a.v_scale = f8 ? f8->v_scale : nullptr;
-  a.H = H;
-  a.d = d;
-  a.rot = rot;
-  a.max_pos = max_pos;
-  a.cu = ragged ? cu : nullptr;
-  a.nseq = B;
-  a.ntok = Nq;
-  const int esz = dtype == FA_DTYPE_BF16 ? 2 : 4;
-  const uintptr_t ptrs = (uintptr_t)q | (uintptr_t)q_rot | (uintptr_t)k_new | (uintptr_t)v_new | (uintptr_t)cos | (uintptr_t)sin;
-  const uintptr_t caches = k_new ? (uintptr_t)k_cache | (uintptr_t)v_cache : 0;
-  const bool vec = rope_vec(16 / esz, rot, interleaved, d_new, d, ptrs, caches, f8 ? 8 : 16);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const bool il = interleaved != 0;
-  if (f8) return vec ? launch_rope_append<fa::bf16_t, 8, true>(a, il, st) : launch_rope_append<fa::bf16_t, 1, true>(a, il, st);
-  if (dtype == FA_DTYPE_BF16) return vec ? launch_rope_append<fa::bf16_t, 8>(a, il, st) : launch_rope_append<fa::bf16_t, 1>(a, il, st);
-  return vec ? launch_rope_append<float, 4>(a, il, st) : launch_rope_append<float, 1>(a, il, st);
+  set_append(a, c);
+  a.q = c.q;
+  a.q_rot = r.q_rot;
+  a.cos = r.cos;
+  a.sin = r.sin;
+  a.k_scale = c.f8.k_scale;
+  a.v_scale = c.f8.v_scale;
+  a.q_lanes = c.q ? c.seqs() * c.Nq * c.H : 0;
+  a.H = c.H;
+  a.d = c.d;
+  a.rot = r.rot;
+  a.max_pos = r.max_pos;
+  a.cu = c.cu;
+  a.nseq = c.B;
+  a.ntok = c.Nq;
+  const uintptr_t ptrs = (uintptr_t)c.q | (uintptr_t)r.q_rot | (uintptr_t)c.k_new | (uintptr_t)c.v_new | (uintptr_t)r.cos | (uintptr_t)r.sin;
+  const uintptr_t caches = c.k_new ? (uintptr_t)c.k_cache | (uintptr_t)c.v_cache : 0;
+  const bool vec = rope_vec(16 / (int)c.esz(), r.rot, r.interleaved, c.d_new, c.d, ptrs, caches, c.f8.on ? 8 : 16);
+  const bool il = r.interleaved != 0;
+  if (c.f8.on)
+    return vec ? launch_rope_append<fa::bf16_t, 8, true>(a, il, c.stream) : launch_rope_append<fa::bf16_t, 1, true>(a, il, c.stream);
+  if (c.dtype == FA_DTYPE_BF16)
+    return vec ? launch_rope_append<fa::bf16_t, 8, false>(a, il, c.stream) : launch_rope_append<fa::bf16_t, 1, false>(a, il, c.stream);
+  return vec ? launch_rope_append<float, 4, false>(a, il, c.stream) : launch_rope_append<float, 1, false>(a, il, c.stream);
 }
 
 }  // namespace
 
 extern "C" {
 
+// ---- the size queries: the policy's split count and workspace on (window, sink), 0 and 0 in the forms that have none ----
+int fa_mi355x_decode_splits_gqa(int B, int H, int Hkv, int Nq, int Ncap, int d, int dtype) {
+  (void)dtype;
+  return query(DECODE, B, H, Hkv, Nq, Ncap, d, 0, 0).nsplit;
+}
+
+size_t fa_mi355x_decode_workspace_bytes_gqa(int B, int H, int Hkv, int Nq, int Ncap, int d) {
+  return query(DECODE, B, H, Hkv, Nq, Ncap, d, 0, 0).workspace_bytes;
+}
+
+int fa_mi355x_extend_splits(int B, int H, int Hkv, int Nq, int Ncap, int d, int dtype) {
+  (void)dtype;
+  return query(EXTEND, B, H, Hkv, Nq, Ncap, d, 0, 0).nsplit;
+}
+
+size_t fa_mi355x_extend_workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int d) {
+  return query(EXTEND, B, H, Hkv, Nq, Ncap, d, 0, 0).workspace_bytes;
+}
+
+int fa_mi355x_ragged_splits(int B, int H, int Hkv, int T, int Ncap, int d, int dtype) {
+  (void)dtype;
+  return query(RAGGED, B, H, Hkv, T, Ncap, d, 0, 0).nsplit;
+}
+
+size_t fa_mi355x_ragged_workspace_bytes(int B, int H, int Hkv, int T, int Ncap, int d) {
+  return query(RAGGED, B, H, Hkv, T, Ncap, d, 0, 0).workspace_bytes;
+}
+
+int fa_mi355x_decode_window_splits(int B, int H, int Hkv, int Nq, int Ncap, int d, int dtype, int window) {
+  (void)dtype;
+  return query(DECODE, B, H, Hkv, Nq, Ncap, d, window, 0).nsplit;
+}
+
+size_t fa_mi355x_decode_window_workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int d, int window) {
+  return query(DECODE, B, H, Hkv, Nq, Ncap, d, window, 0).workspace_bytes;
+}
+
+int fa_mi355x_extend_window_splits(int B, int H, int Hkv, int Nq, int Ncap, int d, int dtype, int window) {
+  (void)dtype;
+  return query(EXTEND, B, H, Hkv, Nq, Ncap, d, window, 0).nsplit;
+}
+
+size_t fa_mi355x_extend_window_workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int d, int window) {
+  return query(EXTEND, B, H, Hkv, Nq, Ncap, d, window, 0).workspace_bytes;
+}
+
+int fa_mi355x_ragged_window_splits(int B, int H, int Hkv, int T, int Ncap, int d, int dtype, int window) {
+  (void)dtype;
+  return query(RAGGED, B, H, Hkv, T, Ncap, d, window, 0).nsplit;
+}
+
+size_t fa_mi355x_ragged_window_workspace_bytes(int B, int H, int Hkv, int T, int Ncap, int d, int window) {
+  return query(RAGGED, B, H, Hkv, T, Ncap, d, window, 0).workspace_bytes;
+}
+
+int fa_mi355x_decode_sink_splits(int B, int H, int Hkv, int Nq, int Ncap, int d, int dtype, int window, int sink) {
+  (void)dtype;
+  return query(DECODE, B, H, Hkv, Nq, Ncap, d, window, sink).nsplit;
+}
+
+size_t fa_mi355x_decode_sink_workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int d, int window, int sink) {
+  return query(DECODE, B, H, Hkv, Nq, Ncap, d, window, sink).workspace_bytes;
+}
+
+int fa_mi355x_extend_sink_splits(int B, int H, int Hkv, int Nq, int Ncap, int d, int dtype, int window, int sink) {
+  (void)dtype;
+  return query(EXTEND, B, H, Hkv, Nq, Ncap, d, window, sink).nsplit;
+}
+
+size_t fa_mi355x_extend_sink_workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int d, int window, int sink) {
+  return query(EXTEND, B, H, Hkv, Nq, Ncap, d, window, sink).workspace_bytes;
+}
+
+int fa_mi355x_ragged_sink_splits(int B, int H, int Hkv, int T, int Ncap, int d, int dtype, int window, int sink) {
+  (void)dtype;
+  return query(RAGGED, B, H, Hkv, T, Ncap, d, window, sink).nsplit;
+}
+
+size_t fa_mi355x_ragged_sink_workspace_bytes(int B, int H, int Hkv, int T, int Ncap, int d, int window, int sink) {
+  return query(RAGGED, B, H, Hkv, T, Ncap, d, window, sink).workspace_bytes;
+}
+
+// ---- decode and extend on slabs of Ncap rows: the attention, the append, and the append then the attention ----
+int fa_mi355x_fwd_decode_gqa(const void* q, const void* k_cache, const void* v_cache, float* out, float* lse, const int* cache_seqlens,
+                             void* workspace, int B, int H, int Hkv, int Nq, int Ncap, int d, int layout, float softmax_scale,
+                             int causal, int dtype, void* stream) {
+  KvCall c(DECODE);
+  c.attention(q, out, lse, workspace, softmax_scale, causal).cache(k_cache, v_cache, cache_seqlens, Ncap);
+  return run(c.heads(B, H, Hkv, Nq, d).format(layout, dtype, stream));
+}
+
+int fa_mi355x_decode_append(const void* k_new, const void* v_new, void* k_cache, void* v_cache, const int* cache_seqlens, int B, int Hkv,
+                            int Nq, int Ncap, int d_new, int d, int layout, int dtype, void* stream) {
+  KvCall c(DECODE);
+  c.new_tokens(k_new, v_new, d_new).cache(k_cache, v_cache, cache_seqlens, Ncap);
+  return run(c.heads(B, Hkv, Hkv, Nq, d).format(layout, dtype, stream));
+}
+
+int fa_mi355x_fwd_decode_append(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
+                                const int* cache_seqlens, void* workspace, int B, int H, int Hkv, int Nq, int Ncap, int d_new, int d,
+                                int layout, float softmax_scale, int causal, int dtype, void* stream) {
+  KvCall c(DECODE);
+  c.attention(q, out, lse, workspace, softmax_scale, causal).new_tokens(k_new, v_new, d_new).cache(k_cache, v_cache, cache_seqlens, Ncap);
+  return run(c.heads(B, H, Hkv, Nq, d).format(layout, dtype, stream));
+}
+
+int fa_mi355x_fwd_extend(const void* q, const void* k_cache, const void* v_cache, float* out, float* lse, const int* cache_seqlens,
+                         void* workspace, int B, int H, int Hkv, int Nq, int Ncap, int d, int layout, float softmax_scale, int causal,
+                         int dtype, void* stream) {
+  KvCall c(EXTEND);
+  c.attention(q, out, lse, workspace, softmax_scale, causal).cache(k_cache, v_cache, cache_seqlens, Ncap);
+  return run(c.heads(B, H, Hkv, Nq, d).format(layout, dtype, stream));
+}
+
+int fa_mi355x_extend_append(const void* k_new, const void* v_new, void* k_cache, void* v_cache, const int* cache_seqlens, int B, int Hkv,
+                            int Nq, int Ncap, int d_new, int d, int layout, int dtype, void* stream) {
+  KvCall c(EXTEND);
+  c.new_tokens(k_new, v_new, d_new).cache(k_cache, v_cache, cache_seqlens, Ncap);
+  return run(c.heads(B, Hkv, Hkv, Nq, d).format(layout, dtype, stream));
+}
+
+int fa_mi355x_fwd_extend_append(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
+                                const int* cache_seqlens, void* workspace, int B, int H, int Hkv, int Nq, int Ncap, int d_new, int d,
+                                int layout, float softmax_scale, int causal, int dtype, void* stream) {
+  KvCall c(EXTEND);
+  c.attention(q, out, lse, workspace, softmax_scale, causal).new_tokens(k_new, v_new, d_new).cache(k_cache, v_cache, cache_seqlens, Ncap);
+  return run(c.heads(B, H, Hkv, Nq, d).format(layout, dtype, stream));
+}
+
+// ---- the paged entry points: the forms above on a pool of pages read through a block table, whose geometry stands for Ncap ----
+int fa_mi355x_fwd_decode_paged(const void* q, const void* k_pool, const void* v_pool, float* out, float* lse, const int* cache_seqlens,
+                               const int* block_table, void* workspace, int B, int H, int Hkv, int Nq, int num_pages, int page_size,
+                               int max_pages, int d, int layout, float softmax_scale, int causal, int dtype, void* stream) {
+  KvCall c(DECODE);
+  c.attention(q, out, lse, workspace, softmax_scale, causal).cache(k_pool, v_pool, cache_seqlens, 0);
+  c.pool(block_table, num_pages, page_size, max_pages);
+  return run(c.heads(B, H, Hkv, Nq, d).format(layout, dtype, stream));
+}
+
+int fa_mi355x_fwd_extend_paged(const void* q, const void* k_pool, const void* v_pool, float* out, float* lse, const int* cache_seqlens,
+                               const int* block_table, void* workspace, int B, int H, int Hkv, int Nq, int num_pages, int page_size,
+                               int max_pages, int d, int layout, float softmax_scale, int causal, int dtype, void* stream) {
+  KvCall c(EXTEND);
+  c.attention(q, out, lse, workspace, softmax_scale, causal).cache(k_pool, v_pool, cache_seqlens, 0);
+  c.pool(block_table, num_pages, page_size, max_pages);
+  return run(c.heads(B, H, Hkv, Nq, d).format(layout, dtype, stream));
+}
+
+int fa_mi355x_decode_append_paged(const void* k_new, const void* v_new, void* k_pool, void* v_pool, const int* cache_seqlens,
+                                  const int* block_table, int B, int Hkv, int Nq, int num_pages, int page_size, int max_pages, int d_new,
+                                  int d, int layout, int dtype, void* stream) {
+  KvCall c(DECODE);
+  c.new_tokens(k_new, v_new, d_new).cache(k_pool, v_pool, cache_seqlens, 0);
+  c.pool(block_table, num_pages, page_size, max_pages);
+  return run(c.heads(B, Hkv, Hkv, Nq, d).format(layout, dtype, stream));
+}
+
+int fa_mi355x_extend_append_paged(const void* k_new, const void* v_new, void* k_pool, void* v_pool, const int* cache_seqlens,
+                                  const int* block_table, int B, int Hkv, int Nq, int num_pages, int page_size, int max_pages, int d_new,
+                                  int d, int layout, int dtype, void* stream) {
+  KvCall c(EXTEND);
+  c.new_tokens(k_new, v_new, d_new).cache(k_pool, v_pool, cache_seqlens, 0);
+  c.pool(block_table, num_pages, page_size, max_pages);
+  return run(c.heads(B, Hkv, Hkv, Nq, d).format(layout, dtype, stream));
+}
+
+int fa_mi355x_fwd_decode_append_paged(const void* q, const void* k_new, const void* v_new, void* k_pool, void* v_pool, float* out,
+                                      float* lse, const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv,
+                                      int Nq, int num_pages, int page_size, int max_pages, int d_new, int d, int layout,
+                                      float softmax_scale, int causal, int dtype, void* stream) {
+  KvCall c(DECODE);
+  c.attention(q, out, lse, workspace, softmax_scale, causal).new_tokens(k_new, v_new, d_new).cache(k_pool, v_pool, cache_seqlens, 0);
+  c.pool(block_table, num_pages, page_size, max_pages);
+  return run(c.heads(B, H, Hkv, Nq, d).format(layout, dtype, stream));
+}
+
+int fa_mi355x_fwd_extend_append_paged(const void* q, const void* k_new, const void* v_new, void* k_pool, void* v_pool, float* out,
+                                      float* lse, const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv,
+                                      int Nq, int num_pages, int page_size, int max_pages, int d_new, int d, int layout,
+                                      float softmax_scale, int causal, int dtype, void* stream) {
+  KvCall c(EXTEND);
+  c.attention(q, out, lse, workspace, softmax_scale, causal).new_tokens(k_new, v_new, d_new).cache(k_pool, v_pool, cache_seqlens, 0);
+  c.pool(block_table, num_pages, page_size, max_pages);
+  return run(c.heads(B, H, Hkv, Nq, d).format(layout, dtype, stream));
+}
+
+// ---- the ragged entry points (include/flash_attn_mi355x_decode_ragged.h): the new tokens of all sequences packed into T rows, the
+// sequences' boundaries in cu_seqlens_q on the device ----
+int fa_mi355x_fwd_ragged(const void* q, const void* k_cache, const void* v_cache, float* out, float* lse, const int* cu_seqlens_q,
+                         const int* cache_seqlens, void* workspace, int B, int H, int Hkv, int T, int Ncap, int d, int layout,
+                         float softmax_scale, int causal, int dtype, void* stream) {
+  KvCall c(RAGGED);
+  c.attention(q, out, lse, workspace, softmax_scale, causal).cache(k_cache, v_cache, cache_seqlens, Ncap);
+  c.cu = cu_seqlens_q;
+  return run(c.heads(B, H, Hkv, T, d).format(layout, dtype, stream));
+}
+
+int fa_mi355x_ragged_append(const void* k_new, const void* v_new, void* k_cache, void* v_cache, const int* cu_seqlens_q,
+                            const int* cache_seqlens, int B, int Hkv, int T, int Ncap, int d_new, int d, int layout, int dtype,
+                            void* stream) {
+  KvCall c(RAGGED);
+  c.new_tokens(k_new, v_new, d_new).cache(k_cache, v_cache, cache_seqlens, Ncap);
+  c.cu = cu_seqlens_q;
+  return run(c.heads(B, Hkv, Hkv, T, d).format(layout, dtype, stream));
+}
+
+int fa_mi355x_fwd_ragged_append(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
+                                const int* cu_seqlens_q, const int* cache_seqlens, void* workspace, int B, int H, int Hkv, int T,
+                                int Ncap, int d_new, int d, int layout, float softmax_scale, int causal, int dtype, void* stream) {
+  KvCall c(RAGGED);
+  c.attention(q, out, lse, workspace, softmax_scale, causal).new_tokens(k_new, v_new, d_new).cache(k_cache, v_cache, cache_seqlens, Ncap);
+  c.cu = cu_seqlens_q;
+  return run(c.heads(B, H, Hkv, T, d).format(layout, dtype, stream));
+}
+
+int fa_mi355x_fwd_ragged_paged(const void* q, const void* k_pool, const void* v_pool, float* out, float* lse, const int* cu_seqlens_q,
+                               const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv, int T,
+                               int num_pages, int page_size, int max_pages, int d, int layout, float softmax_scale, int causal,
+                               int dtype, void* stream) {
+  KvCall c(RAGGED);
+  c.attention(q, out, lse, workspace, softmax_scale, causal).cache(k_pool, v_pool, cache_seqlens, 0);
+  c.cu = cu_seqlens_q;
+  c.pool(block_table, num_pages, page_size, max_pages);
+  return run(c.heads(B, H, Hkv, T, d).format(layout, dtype, stream));
+}
+
+int fa_mi355x_ragged_append_paged(const void* k_new, const void* v_new, void* k_pool, void* v_pool, const int* cu_seqlens_q,
+                                  const int* cache_seqlens, const int* block_table, int B, int Hkv, int T, int num_pages, int page_size,
+                                  int max_pages, int d_new, int d, int layout, int dtype, void* stream) {
+  KvCall c(RAGGED);
+  c.new_tokens(k_new, v_new, d_new).cache(k_pool, v_pool, cache_seqlens, 0);
+  c.cu = cu_seqlens_q;
+  c.pool(block_table, num_pages, page_size, max_pages);
+  return run(c.heads(B, Hkv, Hkv, T, d).format(layout, dtype, stream));
+}
+
+int fa_mi355x_fwd_ragged_append_paged(const void* q, const void* k_new, const void* v_new, void* k_pool, void* v_pool, float* out,
+                                      float* lse, const int* cu_seqlens_q, const int* cache_seqlens, const int* block_table,
+                                      void* workspace, int B, int H, int Hkv, int T, int num_pages, int page_size, int max_pages,
+                                      int d_new, int d, int layout, float softmax_scale, int causal, int dtype, void* stream) {
+  KvCall c(RAGGED);
+  c.attention(q, out, lse, workspace, softmax_scale, causal).new_tokens(k_new, v_new, d_new).cache(k_pool, v_pool, cache_seqlens, 0);
+  c.cu = cu_seqlens_q;
+  c.pool(block_table, num_pages, page_size, max_pages);
+  return run(c.heads(B, H, Hkv, T, d).format(layout, dtype, stream));
+}
+
+// ---- the windowed, sink and fp8 entry points (_window.h, _sink.h, _fp8.h): one per call family.  k_new / v_new both null: attend
+// only; block_table null: slabs of Ncap rows, otherwise the pool's geometry stands for Ncap ----
+int fa_mi355x_fwd_decode_window(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
+                                const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv, int Nq, int Ncap,
+                                int num_pages, int page_size, int max_pages, int d_new, int d, int layout, float softmax_scale, int causal,
+                                int window, int dtype, void* stream) {
+  return fa_mi355x_fwd_decode_sink(q, k_new, v_new, k_cache, v_cache, out, lse, cache_seqlens, block_table, workspace, B, H, Hkv, Nq, Ncap,
+                                   num_pages, page_size, max_pages, d_new, d, layout, softmax_scale, causal, window, 0, dtype, stream);
+}
+
+int fa_mi355x_fwd_extend_window(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
+                                const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv, int Nq, int Ncap,
+                                int num_pages, int page_size, int max_pages, int d_new, int d, int layout, float softmax_scale, int causal,
+                                int window, int dtype, void* stream) {
+  return fa_mi355x_fwd_extend_sink(q, k_new, v_new, k_cache, v_cache, out, lse, cache_seqlens, block_table, workspace, B, H, Hkv, Nq, Ncap,
+                                   num_pages, page_size, max_pages, d_new, d, layout, softmax_scale, causal, window, 0, dtype, stream);
+}
+
+int fa_mi355x_fwd_ragged_window(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
+                                const int* cu_seqlens_q, const int* cache_seqlens, const int* block_table, void* workspace, int B, int H,
+                                int Hkv, int T, int Ncap, int num_pages, int page_size, int max_pages, int d_new, int d, int layout,
+                                float softmax_scale, int causal, int window, int dtype, void* stream) {
+  return fa_mi355x_fwd_ragged_sink(q, k_new, v_new, k_cache, v_cache, out, lse, cu_seqlens_q, cache_seqlens, block_table, workspace, B, H,
+                                   Hkv, T, Ncap, num_pages, page_size, max_pages, d_new, d, layout, softmax_scale, causal, window, 0, dtype,
+                                   stream);
+}
+
+int fa_mi355x_fwd_decode_sink(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
+                              const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv, int Nq, int Ncap,
+                              int num_pages, int page_size, int max_pages, int d_new, int d, int layout, float softmax_scale, int causal,
+                              int window, int sink, int dtype, void* stream) {
+  KvCall c(DECODE);
+  c.attention(q, out, lse, workspace, softmax_scale, causal).cache(k_cache, v_cache, cache_seqlens, Ncap);
+  c.pool_or_slabs(block_table, num_pages, page_size, max_pages).heads(B, H, Hkv, Nq, d).format(layout, dtype, stream);
+  if (k_new || v_new) c.new_tokens(k_new, v_new, d_new);
+  c.window = window, c.sink = sink;
+  return run(c);
+}
+
+int fa_mi355x_fwd_extend_sink(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
+                              const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv, int Nq, int Ncap,
+                              int num_pages, int page_size, int max_pages, int d_new, int d, int layout, float softmax_scale, int causal,
+                              int window, int sink, int dtype, void* stream) {
+  KvCall c(EXTEND);
+  c.attention(q, out, lse, workspace, softmax_scale, causal).cache(k_cache, v_cache, cache_seqlens, Ncap);
+  c.pool_or_slabs(block_table, num_pages, page_size, max_pages).heads(B, H, Hkv, Nq, d).format(layout, dtype, stream);
+  if (k_new || v_new) c.new_tokens(k_new, v_new, d_new);
+  c.window = window, c.sink = sink;
+  return run(c);
+}
+
+int fa_mi355x_fwd_ragged_sink(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
+                              const int* cu_seqlens_q, const int* cache_seqlens, const int* block_table, void* workspace, int B, int H,
+                              int Hkv, int T, int Ncap, int num_pages, int page_size, int max_pages, int d_new, int d, int layout,
+                              float softmax_scale, int causal, int window, int sink, int dtype, void* stream) {
+  KvCall c(RAGGED);
+  c.attention(q, out, lse, workspace, softmax_scale, causal).cache(k_cache, v_cache, cache_seqlens, Ncap);
+  c.pool_or_slabs(block_table, num_pages, page_size, max_pages).heads(B, H, Hkv, T, d).format(layout, dtype, stream);
+  if (k_new || v_new) c.new_tokens(k_new, v_new, d_new);
+  c.cu = cu_seqlens_q;
+  c.window = window, c.sink = sink;
+  return run(c);
+}
+
+int fa_mi355x_fwd_decode_fp8(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, const float* k_scale,
+                             const float* v_scale, float* out, float* lse, const int* cache_seqlens, const int* block_table, void* workspace,
+                             int B, int H, int Hkv, int Nq, int Ncap, int num_pages, int page_size, int max_pages, int d_new, int d,
+                             int layout, float softmax_scale, int causal, int dtype, void* stream) {
+  KvCall c(DECODE);
+  c.attention(q, out, lse, workspace, softmax_scale, causal).cache(k_cache, v_cache, cache_seqlens, Ncap);
+  c.pool_or_slabs(block_table, num_pages, page_size, max_pages).heads(B, H, Hkv, Nq, d).format(layout, dtype, stream);
+  if (k_new || v_new) c.new_tokens(k_new, v_new, d_new);
+  c.f8 = {true, k_scale, v_scale};
+  return run(c);
+}
+
+int fa_mi355x_fwd_extend_fp8(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, const float* k_scale,
+                             const float* v_scale, float* out, float* lse, const int* cache_seqlens, const int* block_table, void* workspace,
+                             int B, int H, int Hkv, int Nq, int Ncap, int num_pages, int page_size, int max_pages, int d_new, int d,
+                             int layout, float softmax_scale, int causal, int dtype, void* stream) {
+  KvCall c(EXTEND);
+  c.attention(q, out, lse, workspace, softmax_scale, causal).cache(k_cache, v_cache, cache_seqlens, Ncap);
+  c.pool_or_slabs(block_table, num_pages, page_size, max_pages).heads(B, H, Hkv, Nq, d).format(layout, dtype, stream);
+  if (k_new || v_new) c.new_tokens(k_new, v_new, d_new);
+  c.f8 = {true, k_scale, v_scale};
+  return run(c);
+}
+
+// (the append's checks are the extend family's: any Nq >= 1)
+int fa_mi355x_append_fp8(const void* k_new, const void* v_new, void* k_cache, void* v_cache, const float* k_scale, const float* v_scale,
+                         const int* cache_seqlens, const int* block_table, int B, int Hkv, int Nq, int Ncap, int num_pages, int page_size,
+                         int max_pages, int d_new, int d, int layout, int dtype, void* stream) {
+  KvCall c(EXTEND);
+  c.new_tokens(k_new, v_new, d_new).cache(k_cache, v_cache, cache_seqlens, Ncap);
+  c.pool_or_slabs(block_table, num_pages, page_size, max_pages).heads(B, Hkv, Hkv, Nq, d).format(layout, dtype, stream);
+  c.f8 = {true, k_scale, v_scale};
+  return run(c);
+}
+
+// ---- the rotary entry points (include/flash_attn_mi355x_decode_rope.h) ----
+// (no cache call: its own few checks, then the one launch)
 int fa_mi355x_rope(const void* x, void* y, const float* cos, const float* sin, const int* pos_offsets, int B, int N, int H, int d, int rot,
                    int max_pos, int layout, int interleaved, int inverse, int dtype, void* stream) {
   g_err[0] = 0;
@@ -1274,22 +1069,27 @@ int fa_mi355x_rope_append(const void* q, void* q_rot, const void* k_new, const v
     g_err[0] = 0;
     return set_err(FA_ERR_BAD_ARG, "cache_fp8 must be 0 or 1");
   }
-  const Paging pg = {block_table, num_pages, page_size, max_pages};
-  const Fp8 f8 = {k_scale, v_scale};
-  return rope_append_call(q, q_rot, k_new, v_new, k_cache, v_cache, cache_fp8 ? &f8 : nullptr, cos, sin, nullptr, false, cache_seqlens,
-                          block_table ? &pg : nullptr, B, H, Hkv, Nq, Ncap, d_new, d, rot, max_pos, layout, interleaved, dtype, stream);
+  KvCall c(EXTEND);   // (the append's checks are the extend family's: any Nq >= 1)
+  c.new_tokens(k_new, v_new, d_new).cache(k_cache, v_cache, cache_seqlens, Ncap);
+  c.pool_or_slabs(block_table, num_pages, page_size, max_pages).heads(B, H, Hkv, Nq, d).format(layout, dtype, stream);
+  c.q = q;
+  c.f8 = {cache_fp8 != 0, k_scale, v_scale};
+  return rope_append_call(c, {q_rot, cos, sin, rot, max_pos, interleaved});
 }
 
 int fa_mi355x_rope_append_ragged(const void* q, void* q_rot, const void* k_new, const void* v_new, void* k_cache, void* v_cache,
                                  const float* cos, const float* sin, const int* cu_seqlens_q, const int* cache_seqlens,
                                  const int* block_table, int B, int H, int Hkv, int T, int Ncap, int num_pages, int page_size, int max_pages,
                                  int d_new, int d, int rot, int max_pos, int layout, int interleaved, int dtype, void* stream) {
-  const Paging pg = {block_table, num_pages, page_size, max_pages};
-  return rope_append_call(q, q_rot, k_new, v_new, k_cache, v_cache, nullptr, cos, sin, cu_seqlens_q, true, cache_seqlens,
-                          block_table ? &pg : nullptr, B, H, Hkv, T, Ncap, d_new, d, rot, max_pos, layout, interleaved, dtype, stream);
+  KvCall c(RAGGED);
+  c.new_tokens(k_new, v_new, d_new).cache(k_cache, v_cache, cache_seqlens, Ncap);
+  c.pool_or_slabs(block_table, num_pages, page_size, max_pages).heads(B, H, Hkv, T, d).format(layout, dtype, stream);
+  c.q = q;
+  c.cu = cu_seqlens_q;
+  return rope_append_call(c, {q_rot, cos, sin, rot, max_pos, interleaved});
 }
 
-// The ungrouped entry points: Hkv = H.
+// ---- the ungrouped entry points: Hkv = H ----
 size_t fa_mi355x_decode_workspace_bytes(int B, int H, int Nq, int Ncap, int d) {
   return fa_mi355x_decode_workspace_bytes_gqa(B, H, H, Nq, Ncap, d);
 }

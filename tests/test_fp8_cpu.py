@@ -218,10 +218,21 @@ _BAD_APPEND = [
     (dict(Ncap=1 << 24, **_SLAB), BAD_ARG, "2 GiB"), (dict(page_size=1 << 24), BAD_ARG, "2 GiB"),
     (dict(Nq=129, d_new=65), BAD_ARG, "d_new = 65"),   # (any Nq >= 1: 129 new tokens are not what is wrong with this call)
 ]
+_TWO_FAULTS = [   # which error wins: the dtype prelude, the page geometry, then the family's checks (all three entry points)
+    (dict(dtype=0, kn=0), BAD_ARG, "FA_DTYPE_F32"), (dict(dtype=0, page_size=64), BAD_ARG, "FA_DTYPE_F32"), (dict(dtype=0, B=0), BAD_ARG, "FA_DTYPE_F32"),
+    (dict(dtype=5, num_pages=0), BAD_ARG, "unknown dtype"), (dict(dtype=5, d=48, d_new=48, **_SLAB), BAD_ARG, "unknown dtype"),
+    (dict(page_size=192, kn=0), BAD_ARG, "page_size = 192"), (dict(max_pages=0, layout=2), BAD_ARG, "max_pages"),
+    (dict(layout=2, k=0), BAD_ARG, "unknown layout"),
+]
 
 
 def _cases():
     out = [(e, o, c, m) for e in ("decode", "extend") for o, c, m in _BAD_ATTEND] + [("append", o, c, m) for o, c, m in _BAD_APPEND]
+    out += [(e, o, c, m) for e in ("decode", "extend", "append") for o, c, m in _TWO_FAULTS]
+    out += [(e, dict(q=0, d_new=65), BAD_ARG, "null pointer argument") for e in ("decode", "extend")]   # (the attention's before the append's)
+    # the cache bound: the attention's own check in the fused calls, after the append's checks in the append alone
+    out += [(e, dict(d_new=65, Ncap=1 << 24, **_SLAB), BAD_ARG, "2 GiB") for e in ("decode", "extend")]
+    out.append(("append", dict(d_new=65, Ncap=1 << 24, **_SLAB), BAD_ARG, "d_new = 65"))
     out += [("decode", dict(Nq=129), BAD_ARG, "Nq > 128"), ("decode", dict(Nq=129, **_SLAB, **_ATTEND_ONLY), BAD_ARG, "Nq > 128"),
             ("extend", dict(Nq=129, d_new=65), BAD_ARG, "d_new = 65"),
             ("extend", dict(H=1 << 12, Hkv=1, Nq=1 << 13, d=32, d_new=32), BAD_ARG, "2^25")]

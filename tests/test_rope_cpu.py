@@ -204,9 +204,28 @@ _BAD_ROPE = [
 ]
 
 
+_TWO_FAULTS_BOTH = [   # which error wins: the pairs, the page geometry, the append's checks, q's, the tables', max_pos against the cache
+    (dict(qr=0, rot=63), BAD_ARG, "q and q_rot"), (dict(qr=0, kn=0), BAD_ARG, "q and q_rot"), (dict(kn=0, page_size=192), BAD_ARG, "k_new and v_new"),
+    (dict(page_size=192, d_new=65), BAD_ARG, "page_size = 192"), (dict(d_new=65, rot=63), BAD_ARG, "d_new = 65"),
+    (dict(H=0, cos=0), BAD_ARG, "H must"), (dict(cos=0, il=2), BAD_ARG, "cos"), (dict(il=2, rot=63), BAD_ARG, "interleaved"),
+    (dict(rot=63, max_pos=5), BAD_ARG, "rot = 63"), (dict(dtype=5, layout=2, **_NO_KV), BAD_ARG, "unknown dtype"),
+]
+_TWO_FAULTS_APPEND = [   # cache_fp8, then the fp8 cache's dtype, in front of everything else
+    (dict(fp8=2, dtype=0), BAD_ARG, "cache_fp8"), (dict(fp8=2, qr=0), BAD_ARG, "cache_fp8"), (dict(fp8=2, page_size=192), BAD_ARG, "cache_fp8"),
+    (dict(fp8=1, dtype=0, qr=0), BAD_ARG, "FA_DTYPE_F32"), (dict(fp8=1, dtype=5, rot=63), BAD_ARG, "unknown dtype"),
+    (dict(fp8=1, d_new=65, Ncap=1 << 24, max_pos=1 << 24, **_SLAB), BAD_ARG, "d_new = 65"),
+]
+_TWO_FAULTS_RAGGED = [
+    (dict(cu=0, rot=63), BAD_ARG, "cu_seqlens_q"), (dict(cu=0, d=48, d_new=48, rot=48), BAD_ARG, "null cu_seqlens_q"),
+    (dict(cu=0, k=0), BAD_ARG, "null pointer argument"), (dict(cu=0, d=48, rot=48, **_NO_KV), BAD_ARG, "null cu_seqlens_q"),
+    (dict(cu=0, layout=2, **_NO_KV), BAD_ARG, "unknown layout"),
+]
+
+
 def _cases():
-    out = [(e, o, c, m) for e in ("append", "ragged") for o, c, m in _BAD_BOTH]
-    out += [("append", o, c, m) for o, c, m in _BAD_APPEND] + [("ragged", o, c, m) for o, c, m in _BAD_RAGGED]
+    out = [(e, o, c, m) for e in ("append", "ragged") for o, c, m in _BAD_BOTH + _TWO_FAULTS_BOTH]
+    out += [("append", o, c, m) for o, c, m in _BAD_APPEND + _TWO_FAULTS_APPEND]
+    out += [("ragged", o, c, m) for o, c, m in _BAD_RAGGED + _TWO_FAULTS_RAGGED]
     return out + [("rope", o, c, m) for o, c, m in _BAD_ROPE]
 
 

@@ -195,12 +195,25 @@ _BAD_FAMILY = [   # the existing checks, through the new entry points: attend-on
     (dict(ws=0, Ncap=65536, window=30000, **_SLAB), BAD_ARG, "workspace"),
     (dict(ws=0, Ncap=65536, window=100, sink=30000, **_SLAB), BAD_ARG, "workspace"),   # (the sink tiles alone make it several splits)
 ]
+_TWO_FAULTS = [   # which error wins: the prelude (sink, window, causal), the page geometry, the attention's checks in order, the append's
+    (dict(window=-1, q=0), BAD_ARG, "window must not be negative"), (dict(sink=-1, window=-1), BAD_ARG, "sink must not be negative"),
+    (dict(causal=0, page_size=64), BAD_ARG, "causal"), (dict(page_size=64, q=0), BAD_ARG, "page_size = 64"),
+    (dict(num_pages=0, B=0), BAD_ARG, "num_pages"), (dict(max_pages=1 << 24, q=0), BAD_ARG, "max_pages * page_size"),
+    (dict(H=8, Hkv=3, B=0), BAD_ARG, "must be positive"), (dict(layout=2, dtype=5), BAD_ARG, "unknown dtype"),
+    (dict(q=0, d_new=65), BAD_ARG, "null pointer argument"), (dict(d=48, d_new=48, kn=0), BAD_D, "32, 64, 128"),
+    (dict(scale=-1.0, d=48, d_new=48), BAD_D, "32, 64, 128"),
+]
 
 
 def _cases():
     out = []
     for family in FAMILIES:
-        out += [(family, o, c, m) for o, c, m in _BAD_SINK + _BAD_FAMILY]
+        out += [(family, o, c, m) for o, c, m in _BAD_SINK + _BAD_FAMILY + _TWO_FAULTS]
+        # (the attention's last check in front of the append's first)
+        out.append((family, dict(ws=0, Ncap=65536, window=30000, table=0, d_new=65), BAD_ARG, f"fa_mi355x_{family}_workspace_bytes"))
+    out += [("decode", dict(Nq=129, layout=2), BAD_ARG, "Nq > 128"), ("ragged", dict(cu=0, q=0), BAD_ARG, "null pointer argument"),
+            ("ragged", dict(cu=0, d=48, d_new=48), BAD_ARG, "null cu_seqlens_q"),
+            ("ragged", dict(ws=0, d_new=65), BAD_ARG, "fa_mi355x_ragged_workspace_bytes")]
     out += [("decode", dict(Nq=129), BAD_ARG, "Nq > 128"), ("decode", dict(Nq=129, **_SLAB, **_ATTEND_ONLY), BAD_ARG, "Nq > 128"),
             ("ragged", dict(cu=0), BAD_ARG, "cu_seqlens_q"), ("ragged", dict(cu=0, **_SLAB, **_ATTEND_ONLY), BAD_ARG, "cu_seqlens_q"),
             ("ragged", dict(ws=0, window=1, sink=1), BAD_ARG, "fa_mi355x_ragged_workspace_bytes"),   # (the block map: even as one split)
