@@ -188,6 +188,71 @@ ROPE_ABI = {
     "fa_mi355x_rope_append_ragged": (_i, [_vp] * 11 + [_i] * 15 + [_vp]),
 }
 
+# The positional order of every KV-cache symbol that device_ops calls, by the parameter names of the prototypes (k_pool / v_pool of
+# the _paged ones read k_cache / v_cache, T of the ragged ones Nq: one field each).  device_ops fills one dict of fields per public
+# call and every C call takes its arguments from it in this order; tests/test_kv_ops_cpu.py holds the table against the headers' text
+# and against the argtypes above.
+_PROLOGUE = "q k_new v_new k_cache v_cache"
+_PAGED = "B H Hkv Nq num_pages page_size max_pages"
+_EITHER = "B H Hkv Nq Ncap num_pages page_size max_pages"
+_TAIL = "layout softmax_scale causal dtype stream"
+_APPEND = "k_new v_new k_cache v_cache"
+KV_PARAMS = {
+    "fa_mi355x_fwd_decode": f"q k_cache v_cache out lse cache_seqlens workspace B H Nq Ncap d {_TAIL}",
+    "fa_mi355x_fwd_decode_gqa": f"q k_cache v_cache out lse cache_seqlens workspace B H Hkv Nq Ncap d {_TAIL}",
+    "fa_mi355x_fwd_extend": f"q k_cache v_cache out lse cache_seqlens workspace B H Hkv Nq Ncap d {_TAIL}",
+    "fa_mi355x_fwd_ragged": f"q k_cache v_cache out lse cu_seqlens_q cache_seqlens workspace B H Hkv Nq Ncap d {_TAIL}",
+    "fa_mi355x_fwd_decode_append": f"{_PROLOGUE} out lse cache_seqlens workspace B H Hkv Nq Ncap d_new d {_TAIL}",
+    "fa_mi355x_fwd_extend_append": f"{_PROLOGUE} out lse cache_seqlens workspace B H Hkv Nq Ncap d_new d {_TAIL}",
+    "fa_mi355x_fwd_ragged_append": f"{_PROLOGUE} out lse cu_seqlens_q cache_seqlens workspace B H Hkv Nq Ncap d_new d {_TAIL}",
+    "fa_mi355x_fwd_decode_paged": f"q k_cache v_cache out lse cache_seqlens block_table workspace {_PAGED} d {_TAIL}",
+    "fa_mi355x_fwd_extend_paged": f"q k_cache v_cache out lse cache_seqlens block_table workspace {_PAGED} d {_TAIL}",
+    "fa_mi355x_fwd_ragged_paged": f"q k_cache v_cache out lse cu_seqlens_q cache_seqlens block_table workspace {_PAGED} d {_TAIL}",
+    "fa_mi355x_fwd_decode_append_paged": f"{_PROLOGUE} out lse cache_seqlens block_table workspace {_PAGED} d_new d {_TAIL}",
+    "fa_mi355x_fwd_extend_append_paged": f"{_PROLOGUE} out lse cache_seqlens block_table workspace {_PAGED} d_new d {_TAIL}",
+    "fa_mi355x_fwd_ragged_append_paged": f"{_PROLOGUE} out lse cu_seqlens_q cache_seqlens block_table workspace {_PAGED} d_new d {_TAIL}",
+    "fa_mi355x_fwd_decode_window": f"{_PROLOGUE} out lse cache_seqlens block_table workspace {_EITHER} d_new d "
+                                   "layout softmax_scale causal window dtype stream",
+    "fa_mi355x_fwd_extend_window": f"{_PROLOGUE} out lse cache_seqlens block_table workspace {_EITHER} d_new d "
+                                   "layout softmax_scale causal window dtype stream",
+    "fa_mi355x_fwd_ragged_window": f"{_PROLOGUE} out lse cu_seqlens_q cache_seqlens block_table workspace {_EITHER} d_new d "
+                                   "layout softmax_scale causal window dtype stream",
+    "fa_mi355x_fwd_decode_sink": f"{_PROLOGUE} out lse cache_seqlens block_table workspace {_EITHER} d_new d "
+                                 "layout softmax_scale causal window sink dtype stream",
+    "fa_mi355x_fwd_extend_sink": f"{_PROLOGUE} out lse cache_seqlens block_table workspace {_EITHER} d_new d "
+                                 "layout softmax_scale causal window sink dtype stream",
+    "fa_mi355x_fwd_ragged_sink": f"{_PROLOGUE} out lse cu_seqlens_q cache_seqlens block_table workspace {_EITHER} d_new d "
+                                 "layout softmax_scale causal window sink dtype stream",
+    "fa_mi355x_fwd_decode_fp8": f"{_PROLOGUE} k_scale v_scale out lse cache_seqlens block_table workspace {_EITHER} d_new d {_TAIL}",
+    "fa_mi355x_fwd_extend_fp8": f"{_PROLOGUE} k_scale v_scale out lse cache_seqlens block_table workspace {_EITHER} d_new d {_TAIL}",
+    "fa_mi355x_decode_append": f"{_APPEND} cache_seqlens B Hkv Nq Ncap d_new d layout dtype stream",
+    "fa_mi355x_extend_append": f"{_APPEND} cache_seqlens B Hkv Nq Ncap d_new d layout dtype stream",
+    "fa_mi355x_ragged_append": f"{_APPEND} cu_seqlens_q cache_seqlens B Hkv Nq Ncap d_new d layout dtype stream",
+    "fa_mi355x_decode_append_paged": f"{_APPEND} cache_seqlens block_table B Hkv Nq num_pages page_size max_pages d_new d layout dtype stream",
+    "fa_mi355x_extend_append_paged": f"{_APPEND} cache_seqlens block_table B Hkv Nq num_pages page_size max_pages d_new d layout dtype stream",
+    "fa_mi355x_ragged_append_paged": f"{_APPEND} cu_seqlens_q cache_seqlens block_table B Hkv Nq num_pages page_size max_pages d_new d "
+                                     "layout dtype stream",
+    "fa_mi355x_append_fp8": f"{_APPEND} k_scale v_scale cache_seqlens block_table B Hkv Nq Ncap num_pages page_size max_pages d_new d "
+                            "layout dtype stream",
+    "fa_mi355x_rope_append": f"q q_rot {_APPEND} k_scale v_scale cos sin cache_seqlens block_table {_EITHER} d_new d rot max_pos "
+                             "layout interleaved cache_fp8 dtype stream",
+    "fa_mi355x_rope_append_ragged": f"q q_rot {_APPEND} cos sin cu_seqlens_q cache_seqlens block_table {_EITHER} d_new d rot max_pos "
+                                    "layout interleaved dtype stream",
+    "fa_mi355x_decode_workspace_bytes": "B H Nq Ncap d",
+    "fa_mi355x_decode_workspace_bytes_gqa": "B H Hkv Nq Ncap d",
+    "fa_mi355x_extend_workspace_bytes": "B H Hkv Nq Ncap d",
+    "fa_mi355x_ragged_workspace_bytes": "B H Hkv Nq Ncap d",
+    "fa_mi355x_decode_window_workspace_bytes": "B H Hkv Nq Ncap d window",
+    "fa_mi355x_extend_window_workspace_bytes": "B H Hkv Nq Ncap d window",
+    "fa_mi355x_ragged_window_workspace_bytes": "B H Hkv Nq Ncap d window",
+    "fa_mi355x_decode_sink_workspace_bytes": "B H Hkv Nq Ncap d window sink",
+    "fa_mi355x_extend_sink_workspace_bytes": "B H Hkv Nq Ncap d window sink",
+    "fa_mi355x_ragged_sink_workspace_bytes": "B H Hkv Nq Ncap d window sink",
+}
+KV_PARAMS = {sym: tuple(names.split()) for sym, names in KV_PARAMS.items()}   # (split once, here)
+KV_POINTERS = frozenset("q q_rot k_new v_new k_cache v_cache k_scale v_scale cos sin out lse cu_seqlens_q cache_seqlens block_table "
+                        "workspace stream".split())
+
 # the same for include/flash_attn_mi355x_window.h: libflash_attn_mi355x_window.so, the sliding-window / attention-sink forward and
 # backward of the training side (tests/test_window_train_cpu.py).  WINDOW_ABI above is the decode library's windowed family.
 WINDOW_TRAIN_ABI = {
@@ -262,12 +327,13 @@ def check(status: int) -> None:
 
 
 DECODE_NAME = "libflash_attn_mi355x_decode.so"
+_DECODE_LIB_ABI = {**DECODE_ABI, **PAGED_ABI, **RAGGED_ABI, **WINDOW_ABI, **FP8_ABI, **SINK_ABI, **ROPE_ABI}
 
 
 def decode() -> ctypes.CDLL:
     """libflash_attn_mi355x_decode.so (include/flash_attn_mi355x_decode.h, its _paged.h, its _ragged.h, its _window.h, its _fp8.h, its
-    _sink.h and its _rope.h) with argtypes set."""
-    return _typed(DECODE_NAME, {**DECODE_ABI, **PAGED_ABI, **RAGGED_ABI, **WINDOW_ABI, **FP8_ABI, **SINK_ABI, **ROPE_ABI})
+    _sink.h and its _rope.h) with argtypes set.  (Every KV-cache call comes through here: the tables are merged once, above.)"""
+    return _typed(DECODE_NAME, _DECODE_LIB_ABI)
 
 
 def decode_check(status: int) -> None:

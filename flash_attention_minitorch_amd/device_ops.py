@@ -589,53 +589,161 @@ def _max_pages(block_table, max_pages):
     return max_pages
 
 
-def _decode_dims(q, k_cache, layout, max_pages=None):
-    """(B, H, Hkv, Nq, Ncap, dq, dp) of a decode call: q (B, Nq, H, dq) / cache (B, Ncap, Hkv, dp) for "bnhd", (B, H, Nq, dq) /
-    (B, Hkv, Ncap, dp) for "bhnd"; H a multiple of Hkv (grouped-query heads: query head h reads cache head h // (H // Hkv)).
-    ``max_pages``: k_cache is a paged cache's pool (_pool_dims) and Ncap = max_pages * page_size."""
-    if max_pages is not None:
-        if q.dim() != 4:
-            raise ValueError("decode expects a 4-d q")
-        _, page_size, Hkv, dp = _pool_dims(k_cache, layout)
-        (B, Nq, H, dq) = q.shape if layout == "bnhd" else (q.shape[0], q.shape[2], q.shape[1], q.shape[3])
-        if Hkv <= 0 or H % Hkv:
-            raise ValueError(f"q has {H} heads, the pool {Hkv}: the pool's heads must divide q's")
-        return B, H, Hkv, Nq, max_pages * page_size, dq, dp
-    if q.dim() != 4 or k_cache.dim() != 4:
-        raise ValueError("decode expects 4-d q and caches")
-    if layout == "bnhd":
-        (B, Nq, H, dq), (Bc, Ncap, Hkv, dp) = q.shape, k_cache.shape
-    else:
-        (B, H, Nq, dq), (Bc, Hkv, Ncap, dp) = q.shape, k_cache.shape
-    if B != Bc or Hkv <= 0 or H % Hkv:
-        raise ValueError(f"q and the cache disagree on (B, H): {(B, H)} vs {(Bc, Hkv)} (the cache's heads must divide q's)")
-    return B, H, Hkv, Nq, Ncap, dq, dp
+# ---- the KV-cache calls (include/flash_attn_mi355x_decode*.h): one path for the three families ----------------------------------
+# What "decode" (Nq <= 128 new tokens per sequence), "extend" (any Nq) and "ragged" (packed rows under cu_seqlens_q) do differently,
+# as data; everything else is _kv_attention, _kv_append and _kv_workspace below.  ``attend`` / ``append`` / ``workspace``: the public
+# names, for the messages; ``packed``: q and the new tokens are (T, H, d) with cu_seqlens_q, not (B, Nq, H, d) -- their rank and the
+# messages about them follow it; ``lse``: its shape, in words; ``workspace_none``: a zero-byte workspace is None (the ragged one holds
+# the block map: never); ``append_bound``: the most new tokens the append takes on the fp8 and rotary paths; ``fp8``: built for fp8
+# caches; ``caches`` / ``cache_rank`` / ``kv_dtype``: the words of three messages; ``symbols``: the entry points and size queries by
+# variant (_kv_symbol picks one, _lib.KV_PARAMS has its arguments).
+_KV_FAMILIES = {
+    "decode": dict(
+        attend="flash_attn_decode", append="decode_append", workspace="decode_workspace", packed=False, lse="(B, H, Nq)",
+        workspace_none=True, append_bound=128, fp8=True, caches="k_cache and v_cache must have one shape",
+        cache_rank="decode expects 4-d q and caches", kv_dtype="q, k_cache and v_cache must share one dtype",
+        symbols=dict(
+            ungrouped="fa_mi355x_fwd_decode", attend="fa_mi355x_fwd_decode_gqa", fused="fa_mi355x_fwd_decode_append",
+            paged="fa_mi355x_fwd_decode_paged", fused_paged="fa_mi355x_fwd_decode_append_paged", window="fa_mi355x_fwd_decode_window",
+            sink="fa_mi355x_fwd_decode_sink", fp8="fa_mi355x_fwd_decode_fp8", append="fa_mi355x_decode_append",
+            append_paged="fa_mi355x_decode_append_paged", append_fp8="fa_mi355x_append_fp8", rope="fa_mi355x_rope_append",
+            size_ungrouped="fa_mi355x_decode_workspace_bytes", size="fa_mi355x_decode_workspace_bytes_gqa",
+            size_window="fa_mi355x_decode_window_workspace_bytes", size_sink="fa_mi355x_decode_sink_workspace_bytes")),
+    "extend": dict(
+        attend="flash_attn_extend", append="extend_append", workspace="extend_workspace", packed=False, lse="(B, H, Nq)",
+        workspace_none=True, append_bound=None, fp8=True, caches="k_cache and v_cache must have one shape",
+        cache_rank="decode expects 4-d q and caches", kv_dtype="q, k_cache and v_cache must share one dtype",
+        symbols=dict(
+            attend="fa_mi355x_fwd_extend", fused="fa_mi355x_fwd_extend_append", paged="fa_mi355x_fwd_extend_paged",
+            fused_paged="fa_mi355x_fwd_extend_append_paged", window="fa_mi355x_fwd_extend_window", sink="fa_mi355x_fwd_extend_sink",
+            fp8="fa_mi355x_fwd_extend_fp8", append="fa_mi355x_extend_append", append_paged="fa_mi355x_extend_append_paged",
+            append_fp8="fa_mi355x_append_fp8", rope="fa_mi355x_rope_append", size="fa_mi355x_extend_workspace_bytes",
+            size_window="fa_mi355x_extend_window_workspace_bytes", size_sink="fa_mi355x_extend_sink_workspace_bytes")),
+    "ragged": dict(
+        attend="flash_attn_ragged", append="ragged_append", workspace="ragged_workspace", packed=True, lse="(H, T)",
+        workspace_none=False, append_bound=None, fp8=False, caches="k_cache and v_cache must be 4-d tensors of one shape",
+        cache_rank="a ragged call expects 4-d caches", kv_dtype="k_cache and v_cache must share one dtype",
+        symbols=dict(
+            attend="fa_mi355x_fwd_ragged", fused="fa_mi355x_fwd_ragged_append", paged="fa_mi355x_fwd_ragged_paged",
+            fused_paged="fa_mi355x_fwd_ragged_append_paged", window="fa_mi355x_fwd_ragged_window", sink="fa_mi355x_fwd_ragged_sink",
+            append="fa_mi355x_ragged_append", append_paged="fa_mi355x_ragged_append_paged", rope="fa_mi355x_rope_append_ragged",
+            size="fa_mi355x_ragged_workspace_bytes", size_window="fa_mi355x_ragged_window_workspace_bytes",
+            size_sink="fa_mi355x_ragged_sink_workspace_bytes")),
+}
 
 
-def _decode_workspace_bytes(B, H, Hkv, Nq, Ncap, dp, window=None, sink=None):
-    lib = _lib.decode()
+def _kv_symbol(fam, op, paged=False, fused=False, window=None, sink=None, fp8=False, ungrouped=False):
+    """The C symbol of a call.  ``op`` "append": the append (fa_mi355x_append_fp8 takes slab and paged caches alike); "size": the size
+    query; "attend": the attention -- one entry point per family on an fp8 cache, with sink tokens and with a window (null k_new /
+    v_new attend only, a null table is a slab cache), otherwise the _paged and the fused _append forms.  ``window`` None takes the
+    unwindowed symbols; ``ungrouped`` (Hkv = H) the ones without an Hkv, where the family has them."""
+    symbols = fam["symbols"]
+    if op == "append":
+        return symbols["append_fp8" if fp8 else "append_paged" if paged else "append"]
+    if op == "size":
+        if sink is not None:
+            return symbols["size_sink"]
+        if window is not None:
+            return symbols["size_window"]
+        return symbols["size_ungrouped"] if ungrouped and "size_ungrouped" in symbols else symbols["size"]
+    if fp8:
+        return symbols["fp8"]
     if sink is not None:
-        return lib.fa_mi355x_decode_sink_workspace_bytes(B, H, Hkv, Nq, Ncap, dp, window, sink)
+        return symbols["sink"]
     if window is not None:
-        return lib.fa_mi355x_decode_window_workspace_bytes(B, H, Hkv, Nq, Ncap, dp, window)
-    if Hkv == H:
-        return lib.fa_mi355x_decode_workspace_bytes(B, H, Nq, Ncap, dp)
-    return lib.fa_mi355x_decode_workspace_bytes_gqa(B, H, Hkv, Nq, Ncap, dp)
+        return symbols["window"]
+    if paged:
+        return symbols["fused_paged" if fused else "paged"]
+    if fused:
+        return symbols["fused"]
+    return symbols["ungrouped"] if ungrouped and "ungrouped" in symbols else symbols["attend"]
+
+
+_KV_ARGS = {symbol: operator.itemgetter(*names) for symbol, names in _lib.KV_PARAMS.items()}   # fields -> the symbol's argument tuple
+
+
+def _kv_call(symbol, fields):
+    """The one place a KV-cache symbol is called: its arguments are ``fields`` in the order of the header's prototype
+    (_lib.KV_PARAMS; one itemgetter per symbol, made at import, does what [fields[n] for n in names] would)."""
+    return getattr(_lib.decode(), symbol)(*_KV_ARGS[symbol](fields))
+
+
+def _kv_geometry(fam, k_cache, layout, max_pages, q=None, cu_seqlens_q=None):
+    """(Hkv, dp, Ncap, pool, B, H, Nq, d) of a call.  The cache: (B, Ncap, Hkv, dp) for "bnhd" or (B, Hkv, Ncap, dp) for "bhnd" and
+    pool None, or, with ``max_pages`` (_max_pages), a paged cache's pool (_pool_dims), Ncap = max_pages * page_size and pool =
+    (num_pages, page_size, max_pages).  q (None, as the appends have none: B, H, Nq, d are None): packed (T, H, d) under cu_seqlens_q
+    (B + 1,), or (B, Nq, H, d) for "bnhd" / (B, H, Nq, d) for "bhnd"; H is a multiple of Hkv (grouped-query heads: query head h reads
+    cache head h // (H // Hkv)) and B the slab cache's (a pool's first dimension counts pages: the table is what B is held against)."""
+    if max_pages is not None:
+        num_pages, page_size, Hkv, dp = _pool_dims(k_cache, layout)
+        Ncap, pool = max_pages * page_size, (num_pages, page_size, max_pages)
+    else:
+        if k_cache.dim() != 4:
+            raise ValueError(fam["cache_rank"])
+        _, Ncap, Hkv, dp = k_cache.shape
+        if layout != "bnhd":
+            Ncap, Hkv = Hkv, Ncap
+        pool = None
+    if q is None:
+        return Hkv, dp, Ncap, pool, None, None, None, None
+    if fam["packed"]:
+        if q.dim() != 3:
+            raise ValueError("a ragged call expects a 3-d packed q (T, H, d)")
+        Nq, H, d = q.shape
+        _check_cu(cu_seqlens_q, None if pool else k_cache.shape[0], q.device)
+        B = cu_seqlens_q.shape[0] - 1
+        if Nq < 1 or Hkv <= 0 or H % Hkv:
+            raise ValueError(f"q has {H} heads, the cache {Hkv}: the cache's heads must divide q's (and q hold a row)")
+    else:
+        if q.dim() != 4:
+            raise ValueError("decode expects a 4-d q" if pool else fam["cache_rank"])
+        B, Nq, H, d = q.shape
+        if layout != "bnhd":
+            Nq, H = H, Nq
+        if pool:
+            if Hkv <= 0 or H % Hkv:
+                raise ValueError(f"q has {H} heads, the pool {Hkv}: the pool's heads must divide q's")
+        elif B != k_cache.shape[0] or Hkv <= 0 or H % Hkv:
+            raise ValueError(f"q and the cache disagree on (B, H): {(B, H)} vs {(k_cache.shape[0], Hkv)} (the cache's heads must divide q's)")
+    return Hkv, dp, Ncap, pool, B, H, Nq, d
+
+
+def _kv_workspace_bytes(fam, B, H, Hkv, Nq, Ncap, dp, window, sink):
+    """The family's size query for a call of these sizes."""
+    return _kv_call(_kv_symbol(fam, "size", False, False, window, sink, False, Hkv == H),
+                    {"B": B, "H": H, "Hkv": Hkv, "Nq": Nq, "Ncap": Ncap, "d": dp, "window": window, "sink": sink})
+
+
+def _kv_workspace(family, q, k_cache, cu_seqlens_q, layout, block_table, max_pages, window, sink):
+    """decode_workspace / extend_workspace / ragged_workspace."""
+    fam = _KV_FAMILIES[family]
+    if layout not in _DECODE_LAYOUTS:
+        raise ValueError(f"layout must be one of {sorted(_DECODE_LAYOUTS)}")
+    Hkv, dp, Ncap, _, B, H, Nq, _ = _kv_geometry(fam, k_cache, layout, _max_pages(block_table, max_pages), q, cu_seqlens_q)
+    window = _check_window(window)
+    nbytes = _kv_workspace_bytes(fam, B, H, Hkv, Nq, Ncap, dp, window, _check_sink(sink, window))
+    return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=q.device) if nbytes or not fam["workspace_none"] else None
+
+
+def _check_int_option(value, name, counts, unset):
+    """An option that counts positions (not None), as the library takes it: an int >= 0 (no bool, no float)."""
+    try:
+        value = None if isinstance(value, bool) else operator.index(value)
+    except TypeError:
+        value = None
+    if value is None:
+        raise ValueError(f"{name} must be None or an int: the number of {counts}")
+    if value < 0:
+        raise ValueError(f"{name} must not be negative (None or 0: {unset})")
+    return value
 
 
 def _check_window(window, causal=True):
     """``window`` as the library takes it: None stays None (the unwindowed entry points), otherwise an int >= 0 under the causal mask."""
     if window is None:
         return None
-    try:
-        window = None if isinstance(window, bool) else operator.index(window)
-    except TypeError:
-        window = None
-    if window is None:
-        raise ValueError("window must be None or an int: the number of positions a token sees, its own included")
-    if window < 0:
-        raise ValueError("window must not be negative (None or 0: no window)")
-    if window > 0 and not causal:
+    window = _check_int_option(window, "window", "positions a token sees, its own included", "no window")
+    if window and not causal:
         raise ValueError("a sliding window needs the causal mask: window= with causal=False")
     return window
 
@@ -645,15 +753,8 @@ def _check_sink(sink, window):
     int >= 1, which needs a window."""
     if sink is None:
         return None
-    try:
-        sink = None if isinstance(sink, bool) else operator.index(sink)
-    except TypeError:
-        sink = None
-    if sink is None:
-        raise ValueError("sink must be None or an int: the number of first positions every token keeps beside its window")
-    if sink < 0:
-        raise ValueError("sink must not be negative (None or 0: no sink tokens)")
-    if sink > 0 and window is None:
+    sink = _check_int_option(sink, "sink", "first positions every token keeps beside its window", "no sink tokens")
+    if sink and window is None:
         raise ValueError("sink tokens stand beside a sliding window: sink= needs window=")
     return sink or None
 
@@ -755,30 +856,18 @@ def decode_workspace(q, k_cache, layout="bnhd", block_table=None, max_pages=None
     Ncap = max_pages * page_size.  ``window``: for flash_attn_decode(..., window=) (fa_mi355x_decode_window_workspace_bytes: the
     splits follow the window span, not the cache).  ``sink``: for flash_attn_decode(..., window=, sink=)
     (fa_mi355x_decode_sink_workspace_bytes).  An fp8 cache is sized as the bf16 cache of its shape is (the same splits)."""
-    B, H, Hkv, Nq, Ncap, _, dp = _decode_dims(q, k_cache, layout, _max_pages(block_table, max_pages))
-    window = _check_window(window)
-    nbytes = _decode_workspace_bytes(B, H, Hkv, Nq, Ncap, dp, window, _check_sink(sink, window))
-    return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=q.device) if nbytes else None
-
-
-def _extend_workspace_bytes(B, H, Hkv, Nq, Ncap, dp, window=None, sink=None):
-    if sink is not None:
-        return _lib.decode().fa_mi355x_extend_sink_workspace_bytes(B, H, Hkv, Nq, Ncap, dp, window, sink)
-    if window is not None:
-        return _lib.decode().fa_mi355x_extend_window_workspace_bytes(B, H, Hkv, Nq, Ncap, dp, window)
-    return _lib.decode().fa_mi355x_extend_workspace_bytes(B, H, Hkv, Nq, Ncap, dp)
+    return _kv_workspace("decode", q, k_cache, None, layout, block_table, max_pages, window, sink)
 
 
 def extend_workspace(q, k_cache, layout="bnhd", block_table=None, max_pages=None, window=None, sink=None):
     """decode_workspace for flash_attn_extend (fa_mi355x_extend_workspace_bytes: the extend call has a split policy of its own;
     ``window``: fa_mi355x_extend_window_workspace_bytes; ``sink``: fa_mi355x_extend_sink_workspace_bytes)."""
-    B, H, Hkv, Nq, Ncap, _, dp = _decode_dims(q, k_cache, layout, _max_pages(block_table, max_pages))
-    window = _check_window(window)
-    nbytes = _extend_workspace_bytes(B, H, Hkv, Nq, Ncap, dp, window, _check_sink(sink, window))
-    return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=q.device) if nbytes else None
+    return _kv_workspace("extend", q, k_cache, None, layout, block_table, max_pages, window, sink)
 
 
 _FP8 = getattr(torch, "float8_e4m3fn", None)   # the dtype of an fp8 KV cache (include/flash_attn_mi355x_decode_fp8.h)
+_RAGGED_FP8 = ("the ragged calls on an fp8 (torch.float8_e4m3fn) cache are not built: use flash_attn_decode / flash_attn_extend "
+               "and decode_append / extend_append")
 
 
 def _is_fp8(t):
@@ -807,29 +896,31 @@ def _check_seqlens(cache_seqlens, B, device):
         raise ValueError("cache_seqlens must be a contiguous int32 tensor of shape (B,) on q's device")
 
 
-def _check_new(k_new, v_new, k_cache, layout, Nq=None, paged=False):
-    """(Nq, d_new) of the new tokens' k_new / v_new, (B, Nq, Hkv, d_new) for "bnhd" or (B, Hkv, Nq, d_new) for "bhnd", checked
-    against the cache they are appended to (and against the caller's Nq, when given).  ``paged``: the cache is a pool, whose first
-    dimension counts pages (the block table is what B is held against)."""
-    if k_new.dim() != 4 or k_new.shape != v_new.shape:
-        raise ValueError("k_new and v_new must be 4-d tensors of one shape")
+def _check_new(fam, k_new, v_new, k_cache, layout, Nq, Hkv, dp, Bc):
+    """(n, d_new) of the new tokens' k_new / v_new -- packed (T, Hkv, d_new), or (B, n, Hkv, d_new) for "bnhd" / (B, Hkv, n, d_new) for
+    "bhnd" -- checked against the cache they are appended to (Hkv heads of dp columns, and ``Bc`` batch elements; None: a pool, whose
+    first dimension counts pages) and against the caller's Nq, when given."""
+    packed = fam["packed"]
+    if k_new.dim() != (3 if packed else 4) or k_new.shape != v_new.shape:
+        raise ValueError("k_new and v_new must be 3-d packed tensors (T, Hkv, d_new) of one shape" if packed else
+                         "k_new and v_new must be 4-d tensors of one shape")
     if _is_fp8(k_cache):
         if k_new.dtype != torch.bfloat16 or v_new.dtype != torch.bfloat16:
             raise TypeError("an fp8 cache takes bfloat16 k_new and v_new (they are quantised on the device)")
     elif k_new.dtype != k_cache.dtype or v_new.dtype != k_cache.dtype:
         raise TypeError("k_new and v_new must have the cache's dtype")
-    if layout == "bnhd":
-        (B, n, Hkv, d_new), (Bc, _, Hc, dp) = k_new.shape, k_cache.shape
+    if packed:
+        n, hkv, d_new = k_new.shape
+        if hkv != Hkv:
+            raise ValueError(f"k_new and the cache disagree on Hkv: {hkv} vs {Hkv}")
     else:
-        (B, Hkv, n, d_new), (Bc, Hc, _, dp) = k_new.shape, k_cache.shape
-    if paged:
-        Bc = B
-    if (B, Hkv) != (Bc, Hc):
-        raise ValueError(f"k_new and the cache disagree on (B, Hkv): {(B, Hkv)} vs {(Bc, Hc)}")
+        B, n, hkv, d_new = k_new.shape if layout == "bnhd" else (k_new.shape[0], k_new.shape[2], k_new.shape[1], k_new.shape[3])
+        if (B, hkv) != (B if Bc is None else Bc, Hkv):
+            raise ValueError(f"k_new and the cache disagree on (B, Hkv): {(B, hkv)} vs {(B if Bc is None else Bc, Hkv)}")
     if Nq is not None and n != Nq:
-        raise ValueError(f"k_new holds {n} new tokens, q {Nq}")
-    if not 1 <= d_new <= dp:
-        raise ValueError(f"k_new's head dim {d_new} must be in 1 .. {dp}, the cache's row length")
+        raise ValueError(f"k_new holds {n} {'packed rows' if packed else 'new tokens'}, q {Nq}")
+    if (packed and n < 1) or not 1 <= d_new <= dp:
+        raise ValueError(f"k_new's head dim {d_new} must be in 1 .. {dp}, the cache's row length" + " (and k_new hold a row)" * packed)
     for t in (k_new, v_new):
         if t.device != k_cache.device:
             raise ValueError("k_new and v_new must live on the cache's device")
@@ -934,29 +1025,19 @@ def apply_rotary(x, cos, sin, seqlen_offsets=None, interleaved=False, inverse=Fa
     return _RotaryFn.apply(x, cos, sin, seqlen_offsets, bool(interleaved), bool(inverse), layout, out)
 
 
-def _rope_append(rotary, q, q_rot, k_new, v_new, k_cache, v_cache, k_scale, v_scale, cache_seqlens, cu_seqlens_q, block_table, B, H, Hkv,
-                 Nq, Ncap, pool, d_new, dp, layout, fp8, dtype):
-    """The roped append in front of an attend-only call (fa_mi355x_rope_append, or _ragged with ``cu_seqlens_q``): q -> q_rot,
+def _rope_append(fam, fields, rotary, fp8=False):
+    """The roped append in front of an attend-only call (the family's ``rope`` symbol): the q of ``fields`` -> its q_rot,
     k_new -> the K cache, both rotated at the positions the append gives the tokens, v_new -> the V cache; q / q_rot or k_new / v_new
-    may be None.  ``pool``: (num_pages, page_size, max_pages) of a paged cache, or None."""
-    cos, sin, (rot, max_pos, il) = rotary
-    geometry = (0, *pool) if pool else (Ncap, 0, 0, 0)
-    lib = _lib.decode()
-    if cu_seqlens_q is not None:
-        status = lib.fa_mi355x_rope_append_ragged(
-            _ptr(q), _ptr(q_rot), _ptr(k_new), _ptr(v_new), _ptr(k_cache), _ptr(v_cache), _ptr(cos), _ptr(sin), _ptr(cu_seqlens_q),
-            _ptr(cache_seqlens), _ptr(block_table), B, H, Hkv, Nq, *geometry, d_new, dp, rot, max_pos, _DECODE_LAYOUTS[layout], il, dtype,
-            _stream_ptr())
-    else:
-        status = lib.fa_mi355x_rope_append(
-            _ptr(q), _ptr(q_rot), _ptr(k_new), _ptr(v_new), _ptr(k_cache), _ptr(v_cache), _ptr(k_scale), _ptr(v_scale), _ptr(cos), _ptr(sin),
-            _ptr(cache_seqlens), _ptr(block_table), B, H, Hkv, Nq, *geometry, d_new, dp, rot, max_pos, _DECODE_LAYOUTS[layout], il,
-            int(bool(fp8)), dtype, _stream_ptr())
-    _lib.decode_check(status)
+    may be null."""
+    cos, sin, (rot, max_pos, interleaved) = rotary
+    _lib.decode_check(_kv_call(fam["symbols"]["rope"], dict(fields, cos=_ptr(cos), sin=_ptr(sin), rot=rot, max_pos=max_pos,
+                                                            interleaved=interleaved, cache_fp8=int(bool(fp8)))))
 
 
 def _rotary_of(rotary_cos, rotary_sin, rotary_interleaved, device):
     """None (no rotary), or (cos, sin, (rot, max_pos, interleaved)) of checked tables."""
+    if rotary_cos is None and rotary_sin is None:
+        return None
     dims = _check_rotary(rotary_cos, rotary_sin, device, rotary_interleaved)
     return None if dims is None else (rotary_cos, rotary_sin, dims)
 
@@ -977,10 +1058,12 @@ def _q_rot_buffer(q_rot, q, qp):
     return q_rot if qp is q else pad_head_dim(q_rot, qp.shape[-1])   # (padded: rows a ragged call does not own come back as they were)
 
 
-def _append(who, entry, k_new, v_new, k_cache, v_cache, cache_seqlens, layout, block_table=None, k_scale=None, v_scale=None,
-            rotary_cos=None, rotary_sin=None, rotary_interleaved=False, q_rot=None):
-    """decode_append / extend_append: the checks, then the library's ``entry`` (its _paged form when there is a block table; for an
-    fp8 cache fa_mi355x_append_fp8, which quantises; with rotary tables fa_mi355x_rope_append without a q)."""
+def _kv_append(family, k_new, v_new, k_cache, v_cache, cu_seqlens_q, cache_seqlens, layout, block_table, k_scale, v_scale, rotary_cos,
+               rotary_sin, rotary_interleaved, q_rot):
+    """decode_append / extend_append / ragged_append: the checks, then the family's append (its _paged form when there is a block
+    table; for an fp8 cache fa_mi355x_append_fp8, which quantises; with rotary tables the roped append without a q, one entry point
+    for any Nq, slab or paged, fp8 or not)."""
+    fam = _KV_FAMILIES[family]
     rotary = _rotary_of(rotary_cos, rotary_sin, rotary_interleaved, k_cache.device)
     if q_rot is not None:
         raise ValueError("q_rot belongs to a call that has a q: an append rotates k_new only")
@@ -991,38 +1074,37 @@ def _append(who, entry, k_new, v_new, k_cache, v_cache, cache_seqlens, layout, b
     if v_cache.dtype != k_cache.dtype:
         raise TypeError("k_cache and v_cache must share one dtype")
     fp8 = _is_fp8(k_cache)
+    if fp8 and not fam["fp8"]:
+        raise TypeError(_RAGGED_FP8)
     dtype = _lib.FA_DTYPE_BF16 if fp8 else _dtype_code(k_cache)
-    paged = block_table is not None
-    if paged:
-        num_pages, page_size, _, _ = _pool_dims(k_cache, layout)
-    Nq, d_new = _check_new(k_new, v_new, k_cache, layout, paged=paged)
-    B, dp = k_new.shape[0], k_cache.shape[3]
-    Ncap, Hkv = (k_cache.shape[1], k_cache.shape[2]) if layout == "bnhd" else (k_cache.shape[2], k_cache.shape[1])
+    Hkv, dp, Ncap, pool, *_ = _kv_geometry(fam, k_cache, layout, None if block_table is None else _max_pages(block_table, None))
+    Bc = None if pool else k_cache.shape[0]
+    Nq, d_new = _check_new(fam, k_new, v_new, k_cache, layout, None, Hkv, dp, Bc)
+    if fam["packed"]:
+        _check_cu(cu_seqlens_q, Bc, k_cache.device)
+    B = cu_seqlens_q.shape[0] - 1 if fam["packed"] else k_new.shape[0]
     _check_scales(k_scale, v_scale, fp8, Hkv, k_cache.device)
     _check_seqlens(cache_seqlens, B, k_cache.device)
-    if paged:
+    if pool:
         _check_table(block_table, B, k_cache.device)
     for t in (k_cache, v_cache):
         if t.device != k_cache.device or not t.is_contiguous():
             raise ValueError("k_cache and v_cache must be contiguous and live on one device")
-        _require_gpu(t, who)
-    if (fp8 or rotary) and who == "decode_append" and Nq > 128:
-        raise ValueError("decode_append takes at most 128 new tokens per call: use extend_append")
-    if rotary:   # (one entry point for any Nq, slab or paged, fp8 or not: no q, so k_new alone is rotated)
+        _require_gpu(t, fam["append"])
+    if (fp8 or rotary) and fam["append_bound"] and Nq > fam["append_bound"]:
+        raise ValueError(f"{fam['append']} takes at most {fam['append_bound']} new tokens per call: use extend_append")
+    num_pages, page_size, max_pages = pool or (0, 0, 0)
+    fields = {   # what the family's appends take, by the names of the prototypes (a paged cache goes without an Ncap)
+        "q": None, "q_rot": None, "k_new": k_new.data_ptr(), "v_new": v_new.data_ptr(), "k_cache": k_cache.data_ptr(),
+        "v_cache": v_cache.data_ptr(), "k_scale": _ptr(k_scale), "v_scale": _ptr(v_scale), "cu_seqlens_q": _ptr(cu_seqlens_q),
+        "cache_seqlens": _ptr(cache_seqlens), "block_table": _ptr(block_table), "B": B, "H": Hkv, "Hkv": Hkv, "Nq": Nq,
+        "Ncap": 0 if pool else Ncap, "num_pages": num_pages, "page_size": page_size, "max_pages": max_pages, "d_new": d_new, "d": dp,
+        "layout": _DECODE_LAYOUTS[layout], "dtype": dtype, "stream": _stream_ptr()}
+    if rotary:   # (no q, so k_new alone is rotated)
         _check_rot(rotary, dp, d_new)
-        _rope_append(rotary, None, None, k_new, v_new, k_cache, v_cache, k_scale, v_scale, cache_seqlens, None, block_table, B, Hkv, Hkv,
-                     Nq, Ncap, (num_pages, page_size, block_table.shape[1]) if paged else None, d_new, dp, layout, fp8, dtype)
-        return
-    if fp8:   # (one entry point for any Nq: a null table is a slab cache)
-        geometry = (0, num_pages, page_size, block_table.shape[1]) if paged else (Ncap, 0, 0, 0)
-        _lib.decode_check(_lib.decode().fa_mi355x_append_fp8(
-            _ptr(k_new), _ptr(v_new), _ptr(k_cache), _ptr(v_cache), _ptr(k_scale), _ptr(v_scale), _ptr(cache_seqlens), _ptr(block_table),
-            B, Hkv, Nq, *geometry, d_new, dp, _DECODE_LAYOUTS[layout], dtype, _stream_ptr()))
-        return
-    where = (_ptr(block_table), B, Hkv, Nq, num_pages, page_size, block_table.shape[1]) if paged else (B, Hkv, Nq, Ncap)
-    _lib.decode_check(getattr(_lib.decode(), entry + "_paged" * paged)(
-        _ptr(k_new), _ptr(v_new), _ptr(k_cache), _ptr(v_cache), _ptr(cache_seqlens), *where, d_new, dp,
-        _DECODE_LAYOUTS[layout], dtype, _stream_ptr()))
+        _rope_append(fam, fields, rotary, fp8)
+    else:
+        _lib.decode_check(_kv_call(_kv_symbol(fam, "append", paged=pool is not None, fp8=fp8), fields))
 
 
 def decode_append(k_new, v_new, k_cache, v_cache, cache_seqlens=None, layout="bnhd", block_table=None, k_scale=None, v_scale=None,
@@ -1042,25 +1124,26 @@ def decode_append(k_new, v_new, k_cache, v_cache, cache_seqlens=None, layout="bn
     (fa_mi355x_rope_append without a q): token i of batch element b at position clamp(len_b, 0, Ncap) - Nq + i, the row it is
     written to; ``rotary_interleaved`` picks GPT-J pairs.  The tables must cover the cache (max_pos >= Ncap).  v_new is never
     rotated.  ``q_rot`` must stay None here (an append has no q)."""
-    _append("decode_append", "fa_mi355x_decode_append", k_new, v_new, k_cache, v_cache, cache_seqlens, layout, block_table, k_scale, v_scale,
-            rotary_cos, rotary_sin, rotary_interleaved, q_rot)
+    _kv_append("decode", k_new, v_new, k_cache, v_cache, None, cache_seqlens, layout, block_table, k_scale, v_scale, rotary_cos, rotary_sin,
+               rotary_interleaved, q_rot)
 
 
 def extend_append(k_new, v_new, k_cache, v_cache, cache_seqlens=None, layout="bnhd", block_table=None, k_scale=None, v_scale=None,
                   rotary_cos=None, rotary_sin=None, rotary_interleaved=False, q_rot=None):
     """decode_append for any number of new tokens (fa_mi355x_extend_append: the same kernel, placement and checks, no bound on Nq)."""
-    _append("extend_append", "fa_mi355x_extend_append", k_new, v_new, k_cache, v_cache, cache_seqlens, layout, block_table, k_scale, v_scale,
-            rotary_cos, rotary_sin, rotary_interleaved, q_rot)
+    _kv_append("extend", k_new, v_new, k_cache, v_cache, None, cache_seqlens, layout, block_table, k_scale, v_scale, rotary_cos, rotary_sin,
+               rotary_interleaved, q_rot)
 
 
-def _cache_attention(who, extend, q, k_cache, v_cache, cache_seqlens, causal, softmax_scale, layout, out, lse, workspace, k_new, v_new,
-                     block_table=None, window=None, k_scale=None, v_scale=None, sink=None, rotary_cos=None, rotary_sin=None,
-                     rotary_interleaved=False, q_rot=None):
-    """flash_attn_decode / flash_attn_extend (``extend``): the checks, the head-dim padding, then the library's entry point (its
-    _paged form when there is a block table; with a ``window``, the family's one _window entry point, with ``sink`` tokens beside it
-    the family's one _sink entry point; on an fp8 cache, the family's one _fp8 entry point).  With rotary tables:
-    fa_mi355x_rope_append (q -> q_rot, the rotated k_new and v_new into the caches), then the ATTEND-ONLY form of the same choice
-    on q_rot."""
+def _kv_attention(family, q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, causal, softmax_scale, layout, out, lse, workspace, k_new, v_new,
+                  block_table, max_pages, window, k_scale, v_scale, sink, rotary_cos, rotary_sin, rotary_interleaved, q_rot):
+    """flash_attn_decode / flash_attn_extend / flash_attn_ragged: the checks in one order (the options; the caches and their dtypes; the
+    geometry; q, the lengths, the table, the new tokens; devices and strides; out, lse, the workspace's size; the GPU; the tables' rotary
+    dimension and q_rot), the head-dim padding, the buffers the caller did not supply, then the entry point _kv_symbol picks.  With
+    rotary tables: the roped append (q -> q_rot, the rotated k_new and v_new into the caches), then the ATTEND-ONLY form of the same
+    choice on q_rot."""
+    fam = _KV_FAMILIES[family]
+    packed = fam["packed"]
     window = _check_window(window, causal)
     sink = _check_sink(sink, window)
     rotary = _rotary_of(rotary_cos, rotary_sin, rotary_interleaved, q.device)
@@ -1070,108 +1153,88 @@ def _cache_attention(who, extend, q, k_cache, v_cache, cache_seqlens, causal, so
         raise ValueError("k_new and v_new go together: give both (fused append) or neither")
     if layout not in _DECODE_LAYOUTS:
         raise ValueError(f"layout must be one of {sorted(_DECODE_LAYOUTS)}")
+    if (packed and k_cache.dim() != 4) or k_cache.shape != v_cache.shape:
+        raise ValueError(fam["caches"])
     dtype = _dtype_code(q)
     fp8 = _is_fp8(k_cache) or _is_fp8(v_cache)
+    if k_cache.dtype != v_cache.dtype:
+        raise TypeError("k_cache and v_cache must share one dtype" if fp8 else fam["kv_dtype"])
     if fp8:
-        if k_cache.dtype != v_cache.dtype:
-            raise TypeError("k_cache and v_cache must share one dtype")
+        if not fam["fp8"]:
+            raise TypeError(_RAGGED_FP8)
         if q.dtype != torch.bfloat16:
             raise TypeError("an fp8 cache takes bfloat16 queries")
-        if window is not None:
+        if window is not None:   # (sink tokens need a window, so this refuses them on an fp8 cache as well)
             raise ValueError("a sliding window on an fp8 cache is not built: window= with torch.float8_e4m3fn caches")
-        if sink is not None:
-            raise ValueError("sink tokens on an fp8 cache are not built: sink= with torch.float8_e4m3fn caches")
-    elif k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
+    elif k_cache.dtype != q.dtype:
         raise TypeError("q, k_cache and v_cache must share one dtype")
-    if k_cache.shape != v_cache.shape:
-        raise ValueError("k_cache and v_cache must have one shape")
-    paged = block_table is not None
-    pages = {}
-    if paged:
-        pages = dict(max_pages=_max_pages(block_table, None))
-        num_pages, page_size, _, _ = _pool_dims(k_cache, layout)
-    B, H, Hkv, Nq, Ncap, d, dp = _decode_dims(q, k_cache, layout, **pages)
+    mp = None if block_table is None else _max_pages(block_table, None)
+    if max_pages is not None and max_pages != mp:   # (the caller's own figure, e.g. the one a workspace was sized with: held against the table)
+        raise ValueError(f"max_pages = {max_pages} is not the block_table's second dimension ({mp}; a contiguous cache has none)")
+    Hkv, dp, Ncap, pool, B, H, Nq, d = _kv_geometry(fam, k_cache, layout, mp, q, cu_seqlens_q)
     if d > dp:
         raise ValueError(f"q's head dim {d} exceeds the cache's row length {dp}")
     _check_scales(k_scale, v_scale, fp8, Hkv, q.device)
     _check_seqlens(cache_seqlens, B, q.device)
-    if paged:
+    if pool:
         _check_table(block_table, B, q.device)
+    d_new = dp
     if k_new is not None:
-        _, d_new = _check_new(k_new, v_new, k_cache, layout, Nq, paged=paged)
-        if k_new.shape[0] != B:
+        _, d_new = _check_new(fam, k_new, v_new, k_cache, layout, Nq, Hkv, dp, None if pool else B)
+        if not packed and k_new.shape[0] != B:
             raise ValueError(f"k_new holds {k_new.shape[0]} batch elements, q {B}")
     for t in (q, k_cache, v_cache):
-        _require_gpu(t, who)
         if t.device != q.device:
             raise ValueError("q, k_cache and v_cache must live on one device")
         if not t.is_contiguous():
             raise ValueError("q, k_cache and v_cache must be contiguous")
+    if out is not None and (out.shape != q.shape or out.dtype != torch.float32 or not out.is_contiguous()):
+        raise ValueError("out must be a contiguous float32 tensor of q's shape")
+    lse_shape = (H, Nq) if packed else (B, H, Nq)
+    if lse is not None and (tuple(lse.shape) != lse_shape or lse.dtype != torch.float32 or not lse.is_contiguous()):
+        raise ValueError(f"lse must be a contiguous float32 tensor of shape {fam['lse']}")
+    if workspace is not None and workspace.numel() * workspace.element_size() < _kv_workspace_bytes(fam, B, H, Hkv, Nq, Ncap, dp, window, sink):
+        raise ValueError(f"workspace too small: size it with {fam['workspace']}()")
+    _require_gpu(q, fam["attend"])   # (the caches live on q's device)
+    if rotary:
+        _check_rot(rotary, d, d_new if k_new is not None else None)
     if softmax_scale is None:
         softmax_scale = 0.0 if d == dp else d ** -0.5
     qp = pad_head_dim(q, dp) if d < dp else q
-    if out is not None and (out.shape != q.shape or out.dtype != torch.float32 or not out.is_contiguous()):
-        raise ValueError("out must be a contiguous float32 tensor of q's shape")
-    outp = out if out is not None and d == dp else torch.empty(qp.shape, dtype=torch.float32, device=q.device)
+    qr = _q_rot_buffer(q_rot, q, qp) if rotary else None
+    if out is not None and d == dp:
+        outp = out
+    elif out is not None and packed:   # (padded: the rows of the unused tail must come back as the caller's out held them)
+        outp = pad_head_dim(out, dp)
+    else:
+        outp = torch.empty(qp.shape, dtype=torch.float32, device=q.device)
     if lse is None:
-        lse = torch.empty((B, H, Nq), dtype=torch.float32, device=q.device)
-    elif tuple(lse.shape) != (B, H, Nq) or lse.dtype != torch.float32 or not lse.is_contiguous():
-        raise ValueError("lse must be a contiguous float32 tensor of shape (B, H, Nq)")
-    lib = _lib.decode()
-    new_ws, ws_bytes = (extend_workspace, _extend_workspace_bytes) if extend else (decode_workspace, _decode_workspace_bytes)
+        lse = torch.empty(lse_shape, dtype=torch.float32, device=q.device)
     if workspace is None:
-        workspace = new_ws(qp, k_cache, layout, **pages, window=window, sink=sink)
-    elif workspace.numel() * workspace.element_size() < ws_bytes(B, H, Hkv, Nq, Ncap, dp, window, sink):
-        raise ValueError(f"workspace too small: size it with {new_ws.__name__}()")
+        nbytes = _kv_workspace_bytes(fam, B, H, Hkv, Nq, Ncap, dp, window, sink)
+        if nbytes or not fam["workspace_none"]:
+            workspace = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=q.device)
+    num_pages, page_size, table_pages = pool or (0, 0, 0)
+    fields = {   # what the family's entry points take, by the names of the prototypes (a paged cache goes without an Ncap).  Written
+                 # out and not gathered in a loop: this is on the path of every launch-bound decode step.
+        "q": qp.data_ptr(), "q_rot": None if qr is None else qr.data_ptr(), "k_new": None if k_new is None else k_new.data_ptr(),
+        "v_new": None if v_new is None else v_new.data_ptr(), "k_cache": k_cache.data_ptr(), "v_cache": v_cache.data_ptr(),
+        "k_scale": None if k_scale is None else k_scale.data_ptr(), "v_scale": None if v_scale is None else v_scale.data_ptr(),
+        "out": outp.data_ptr(), "lse": lse.data_ptr(), "cu_seqlens_q": None if cu_seqlens_q is None else cu_seqlens_q.data_ptr(),
+        "cache_seqlens": None if cache_seqlens is None else cache_seqlens.data_ptr(),
+        "block_table": None if block_table is None else block_table.data_ptr(),
+        "workspace": None if workspace is None else workspace.data_ptr(), "B": B, "H": H, "Hkv": Hkv, "Nq": Nq,
+        "Ncap": 0 if pool else Ncap, "num_pages": num_pages, "page_size": page_size, "max_pages": table_pages, "d_new": d_new, "d": dp,
+        "layout": _DECODE_LAYOUTS[layout], "softmax_scale": float(softmax_scale), "causal": int(bool(causal)), "window": window,
+        "sink": sink, "dtype": dtype, "stream": _stream_ptr()}
     if rotary:   # (the roped append, then the attend-only form of whatever follows, on the rotated q)
-        _check_rot(rotary, d, d_new if k_new is not None else None)
-        qr = _q_rot_buffer(q_rot, q, qp)
-        _rope_append(rotary, qp, qr, k_new, v_new, k_cache, v_cache, k_scale, v_scale, cache_seqlens, None, block_table, B, H, Hkv, Nq,
-                     Ncap, (num_pages, page_size, pages["max_pages"]) if paged else None, d_new if k_new is not None else dp, dp, layout,
-                     fp8, dtype)
+        _rope_append(fam, fields, rotary, fp8)
         if q_rot is not None and qr is not q_rot:
             q_rot.copy_(qr[..., :d])
-        qp, k_new, v_new = qr, None, None
-    tail = (_DECODE_LAYOUTS[layout], float(softmax_scale), int(bool(causal)), dtype, _stream_ptr())
-    if fp8:   # (one entry point per family, as the windowed calls: null k_new / v_new attend only, a null table is a slab cache)
-        fwd = lib.fa_mi355x_fwd_extend_fp8 if extend else lib.fa_mi355x_fwd_decode_fp8
-        geometry = (num_pages, page_size, pages["max_pages"]) if paged else (0, 0, 0)
-        status = fwd(_ptr(qp), _ptr(k_new), _ptr(v_new), _ptr(k_cache), _ptr(v_cache), _ptr(k_scale), _ptr(v_scale), _ptr(outp), _ptr(lse),
-                     _ptr(cache_seqlens), _ptr(block_table), _ptr(workspace), B, H, Hkv, Nq, 0 if paged else Ncap, *geometry,
-                     d_new if k_new is not None else dp, dp, *tail)
-    elif window is not None:   # (one entry point per family: null k_new / v_new attend only, a null table is a slab cache)
-        if sink is not None:   # (the same arguments with sink behind window)
-            fwd, win = (lib.fa_mi355x_fwd_extend_sink if extend else lib.fa_mi355x_fwd_decode_sink), (window, sink)
-        else:
-            fwd, win = (lib.fa_mi355x_fwd_extend_window if extend else lib.fa_mi355x_fwd_decode_window), (window,)
-        geometry = (num_pages, page_size, pages["max_pages"]) if paged else (0, 0, 0)
-        status = fwd(_ptr(qp), _ptr(k_new), _ptr(v_new), _ptr(k_cache), _ptr(v_cache), _ptr(outp), _ptr(lse), _ptr(cache_seqlens),
-                     _ptr(block_table), _ptr(workspace), B, H, Hkv, Nq, 0 if paged else Ncap, *geometry,
-                     d_new if k_new is not None else dp, dp, _DECODE_LAYOUTS[layout], float(softmax_scale), int(bool(causal)), *win,
-                     dtype, _stream_ptr())
-    elif paged:   # (one grouped form of each: the contiguous calls' arguments with the table after the lengths and the pool's geometry for Ncap)
-        name = "fa_mi355x_fwd_" + ("extend" if extend else "decode") + ("_append" if k_new is not None else "") + "_paged"
-        new = (_ptr(k_new), _ptr(v_new)) if k_new is not None else ()
-        dims = (d_new, dp) if k_new is not None else (dp,)
-        status = getattr(lib, name)(_ptr(qp), *new, _ptr(k_cache), _ptr(v_cache), _ptr(outp), _ptr(lse), _ptr(cache_seqlens),
-                                    _ptr(block_table), _ptr(workspace), B, H, Hkv, Nq, num_pages, page_size, pages["max_pages"], *dims,
-                                    *tail)
-    elif extend:   # (one grouped form; always the extend kernels, whatever Nq)
-        if k_new is not None:
-            status = lib.fa_mi355x_fwd_extend_append(_ptr(qp), _ptr(k_new), _ptr(v_new), _ptr(k_cache), _ptr(v_cache), _ptr(outp),
-                                                     _ptr(lse), _ptr(cache_seqlens), _ptr(workspace), B, H, Hkv, Nq, Ncap, d_new, dp, *tail)
-        else:
-            status = lib.fa_mi355x_fwd_extend(_ptr(qp), _ptr(k_cache), _ptr(v_cache), _ptr(outp), _ptr(lse), _ptr(cache_seqlens),
-                                              _ptr(workspace), B, H, Hkv, Nq, Ncap, dp, *tail)
-    elif k_new is not None:
-        status = lib.fa_mi355x_fwd_decode_append(_ptr(qp), _ptr(k_new), _ptr(v_new), _ptr(k_cache), _ptr(v_cache), _ptr(outp), _ptr(lse),
-                                                 _ptr(cache_seqlens), _ptr(workspace), B, H, Hkv, Nq, Ncap, d_new, dp, *tail)
-    else:
-        # (Hkv == H goes through the ungrouped entry points, which are the Hkv = H case of the _gqa ones inside the library)
-        fwd, heads = (lib.fa_mi355x_fwd_decode, (H,)) if Hkv == H else (lib.fa_mi355x_fwd_decode_gqa, (H, Hkv))
-        status = fwd(_ptr(qp), _ptr(k_cache), _ptr(v_cache), _ptr(outp), _ptr(lse), _ptr(cache_seqlens), _ptr(workspace), B, *heads,
-                     Nq, Ncap, dp, *tail)
-    _lib.decode_check(status)
+        fields.update(q=_ptr(qr), k_new=None, v_new=None, d_new=dp)
+        k_new = None
+    symbol = _kv_symbol(fam, "attend", pool is not None, k_new is not None, window, sink, fp8, Hkv == H)
+    _lib.decode_check(_kv_call(symbol, fields))
     return (_unpad(outp, d, out) if d < dp else outp), lse
 
 
@@ -1219,9 +1282,8 @@ def flash_attn_decode(q, k_cache, v_cache, cache_seqlens=None, causal=True, soft
     (x[j], x[j + rot/2]).  Bit for bit the call without the tables on apply_rotary(q) and apply_rotary(k_new) at those positions.
     Works with every cache feature above (paged, window, sink, fp8).  Without k_new / v_new only q is rotated.
     Returns (out fp32 in q's shape, lse fp32 (B, H, Nq)): rows with no admissible key give out = 0, lse = -inf."""
-    return _cache_attention("flash_attn_decode", False, q, k_cache, v_cache, cache_seqlens, causal, softmax_scale, layout, out, lse,
-                            workspace, k_new, v_new, block_table, window, k_scale, v_scale, sink, rotary_cos, rotary_sin, rotary_interleaved,
-                            q_rot)
+    return _kv_attention("decode", q, k_cache, v_cache, None, cache_seqlens, causal, softmax_scale, layout, out, lse, workspace, k_new, v_new,
+                         block_table, None, window, k_scale, v_scale, sink, rotary_cos, rotary_sin, rotary_interleaved, q_rot)
 
 
 def flash_attn_extend(q, k_cache, v_cache, cache_seqlens=None, causal=True, softmax_scale=None, layout="bnhd", out=None, lse=None,
@@ -1240,9 +1302,8 @@ def flash_attn_extend(q, k_cache, v_cache, cache_seqlens=None, causal=True, soft
     window, as in flash_attn_decode (fa_mi355x_fwd_extend_sink; extend_workspace(..., window=, sink=)).  ``rotary_cos`` /
     ``rotary_sin`` / ``rotary_interleaved`` / ``q_rot``: rotary embeddings, as in flash_attn_decode (fa_mi355x_rope_append, then the
     attend-only extend call on q_rot)."""
-    return _cache_attention("flash_attn_extend", True, q, k_cache, v_cache, cache_seqlens, causal, softmax_scale, layout, out, lse,
-                            workspace, k_new, v_new, block_table, window, k_scale, v_scale, sink, rotary_cos, rotary_sin, rotary_interleaved,
-                            q_rot)
+    return _kv_attention("extend", q, k_cache, v_cache, None, cache_seqlens, causal, softmax_scale, layout, out, lse, workspace, k_new, v_new,
+                         block_table, None, window, k_scale, v_scale, sink, rotary_cos, rotary_sin, rotary_interleaved, q_rot)
 
 
 # ---- ragged batches: every sequence brings its own number of new tokens (include/flash_attn_mi355x_decode_ragged.h) ----
@@ -1254,36 +1315,6 @@ def _check_cu(cu_seqlens_q, B, device):
         raise ValueError("cu_seqlens_q must be a contiguous int32 tensor of shape (B + 1,) on q's device")
 
 
-def _ragged_dims(q, k_cache, cu_seqlens_q, layout, max_pages=None):
-    """(B, H, Hkv, T, Ncap, dq, dp) of a ragged call: q (T, H, dq) packed, caches (B, Ncap, Hkv, dp) for "bnhd" or (B, Hkv, Ncap, dp)
-    for "bhnd", cu_seqlens_q (B + 1,).  ``max_pages``: k_cache is a paged cache's pool (_pool_dims), B is cu_seqlens_q's, and
-    Ncap = max_pages * page_size."""
-    if q.dim() != 3:
-        raise ValueError("a ragged call expects a 3-d packed q (T, H, d)")
-    T, H, dq = q.shape
-    if max_pages is not None:
-        _, page_size, Hkv, dp = _pool_dims(k_cache, layout)
-        _check_cu(cu_seqlens_q, None, q.device)
-        B, Ncap = cu_seqlens_q.shape[0] - 1, max_pages * page_size
-    else:
-        if k_cache.dim() != 4:
-            raise ValueError("a ragged call expects 4-d caches")
-        B, dp = k_cache.shape[0], k_cache.shape[3]
-        Ncap, Hkv = (k_cache.shape[1], k_cache.shape[2]) if layout == "bnhd" else (k_cache.shape[2], k_cache.shape[1])
-        _check_cu(cu_seqlens_q, B, q.device)
-    if T < 1 or Hkv <= 0 or H % Hkv:
-        raise ValueError(f"q has {H} heads, the cache {Hkv}: the cache's heads must divide q's (and q hold a row)")
-    return B, H, Hkv, T, Ncap, dq, dp
-
-
-def _ragged_workspace_bytes(B, H, Hkv, T, Ncap, dp, window=None, sink=None):
-    if sink is not None:
-        return _lib.decode().fa_mi355x_ragged_sink_workspace_bytes(B, H, Hkv, T, Ncap, dp, window, sink)
-    if window is not None:
-        return _lib.decode().fa_mi355x_ragged_window_workspace_bytes(B, H, Hkv, T, Ncap, dp, window)
-    return _lib.decode().fa_mi355x_ragged_workspace_bytes(B, H, Hkv, T, Ncap, dp)
-
-
 def ragged_workspace(q, k_cache, cu_seqlens_q, layout="bnhd", block_table=None, max_pages=None, window=None, sink=None):
     """Scratch for flash_attn_ragged with these tensors (fa_mi355x_ragged_workspace_bytes): the block map and one partial O, m, l per
     packed row and key chunk.  Never None: the map lives there, so every ragged call needs one.  A pure function of the SHAPES
@@ -1291,51 +1322,7 @@ def ragged_workspace(q, k_cache, cu_seqlens_q, layout="bnhd", block_table=None, 
     table or its ``max_pages``; the size is the contiguous call's for Ncap = max_pages * page_size.  ``window``: for
     flash_attn_ragged(..., window=) (fa_mi355x_ragged_window_workspace_bytes); ``sink``: for flash_attn_ragged(..., window=, sink=)
     (fa_mi355x_ragged_sink_workspace_bytes)."""
-    if layout not in _DECODE_LAYOUTS:
-        raise ValueError(f"layout must be one of {sorted(_DECODE_LAYOUTS)}")
-    B, H, Hkv, T, Ncap, _, dp = _ragged_dims(q, k_cache, cu_seqlens_q, layout, _max_pages(block_table, max_pages))
-    window = _check_window(window)
-    nbytes = _ragged_workspace_bytes(B, H, Hkv, T, Ncap, dp, window, _check_sink(sink, window))
-    return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=q.device)
-
-
-def _check_new_ragged(k_new, v_new, k_cache, T, Hkv, dp):
-    """d_new of the packed new tokens' k_new / v_new (T, Hkv, d_new), checked against the cache they are appended to."""
-    if k_new.dim() != 3 or k_new.shape != v_new.shape:
-        raise ValueError("k_new and v_new must be 3-d packed tensors (T, Hkv, d_new) of one shape")
-    if k_new.dtype != k_cache.dtype or v_new.dtype != k_cache.dtype:
-        raise TypeError("k_new and v_new must have the cache's dtype")
-    n, hkv, d_new = k_new.shape
-    if hkv != Hkv:
-        raise ValueError(f"k_new and the cache disagree on Hkv: {hkv} vs {Hkv}")
-    if T is not None and n != T:
-        raise ValueError(f"k_new holds {n} packed rows, q {T}")
-    if n < 1 or not 1 <= d_new <= dp:
-        raise ValueError(f"k_new's head dim {d_new} must be in 1 .. {dp}, the cache's row length (and k_new hold a row)")
-    for t in (k_new, v_new):
-        if t.device != k_cache.device:
-            raise ValueError("k_new and v_new must live on the cache's device")
-        if not t.is_contiguous():
-            raise ValueError("k_new and v_new must be contiguous")
-    return n, d_new
-
-
-def _cache_geometry(k_cache, v_cache, layout, block_table):
-    """The checks every ragged call makes on its caches, and ((num_pages, page_size) or None, Hkv, dp, Ncap or None)."""
-    if layout not in _DECODE_LAYOUTS:
-        raise ValueError(f"layout must be one of {sorted(_DECODE_LAYOUTS)}")
-    if k_cache.dim() != 4 or k_cache.shape != v_cache.shape:
-        raise ValueError("k_cache and v_cache must be 4-d tensors of one shape")
-    if v_cache.dtype != k_cache.dtype:
-        raise TypeError("k_cache and v_cache must share one dtype")
-    if _is_fp8(k_cache):
-        raise TypeError("the ragged calls on an fp8 (torch.float8_e4m3fn) cache are not built: use flash_attn_decode / flash_attn_extend "
-                        "and decode_append / extend_append")
-    if block_table is not None:
-        num_pages, page_size, Hkv, dp = _pool_dims(k_cache, layout)
-        return (num_pages, page_size), Hkv, dp, None
-    Ncap, Hkv = (k_cache.shape[1], k_cache.shape[2]) if layout == "bnhd" else (k_cache.shape[2], k_cache.shape[1])
-    return None, Hkv, k_cache.shape[3], Ncap
+    return _kv_workspace("ragged", q, k_cache, cu_seqlens_q, layout, block_table, max_pages, window, sink)
 
 
 def ragged_append(k_new, v_new, k_cache, v_cache, cu_seqlens_q, cache_seqlens=None, layout="bnhd", block_table=None, rotary_cos=None,
@@ -1349,34 +1336,8 @@ def ragged_append(k_new, v_new, k_cache, v_cache, cu_seqlens_q, cache_seqlens=No
     pools, as in decode_append.  ``rotary_cos`` / ``rotary_sin`` / ``rotary_interleaved``: k_new is rotated on its way into the K
     cache, as in decode_append (fa_mi355x_rope_append_ragged without a q; token i of sequence b at position
     clamp(len_b, 0, Ncap) - nq_b + i); ``q_rot`` must stay None."""
-    rotary = _rotary_of(rotary_cos, rotary_sin, rotary_interleaved, k_cache.device)
-    if q_rot is not None:
-        raise ValueError("q_rot belongs to a call that has a q: an append rotates k_new only")
-    pages, Hkv, dp, Ncap = _cache_geometry(k_cache, v_cache, layout, block_table)
-    dtype = _dtype_code(k_cache)
-    T, d_new = _check_new_ragged(k_new, v_new, k_cache, None, Hkv, dp)
-    _check_cu(cu_seqlens_q, None if pages else k_cache.shape[0], k_cache.device)
-    B = cu_seqlens_q.shape[0] - 1   # (a pool's first dimension counts pages: the table is what B is held against)
-    _check_seqlens(cache_seqlens, B, k_cache.device)
-    if pages:
-        _check_table(block_table, B, k_cache.device)
-    for t in (k_cache, v_cache):
-        if t.device != k_cache.device or not t.is_contiguous():
-            raise ValueError("k_cache and v_cache must be contiguous and live on one device")
-        _require_gpu(t, "ragged_append")
-    if rotary:
-        _check_rot(rotary, dp, d_new)
-        _rope_append(rotary, None, None, k_new, v_new, k_cache, v_cache, None, None, cache_seqlens, cu_seqlens_q, block_table, B, Hkv, Hkv,
-                     T, Ncap, (*pages, block_table.shape[1]) if pages else None, d_new, dp, layout, False, dtype)
-        return
-    lib = _lib.decode()
-    head = (_ptr(k_new), _ptr(v_new), _ptr(k_cache), _ptr(v_cache), _ptr(cu_seqlens_q), _ptr(cache_seqlens))
-    tail = (d_new, dp, _DECODE_LAYOUTS[layout], dtype, _stream_ptr())
-    if pages:
-        status = lib.fa_mi355x_ragged_append_paged(*head, _ptr(block_table), B, Hkv, T, *pages, block_table.shape[1], *tail)
-    else:
-        status = lib.fa_mi355x_ragged_append(*head, B, Hkv, T, Ncap, *tail)
-    _lib.decode_check(status)
+    _kv_append("ragged", k_new, v_new, k_cache, v_cache, cu_seqlens_q, cache_seqlens, layout, block_table, None, None, rotary_cos, rotary_sin,
+               rotary_interleaved, q_rot)
 
 
 def flash_attn_ragged(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens=None, causal=True, softmax_scale=None, layout="bnhd", out=None,
@@ -1391,89 +1352,18 @@ def flash_attn_ragged(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens=None, cau
     and the default scale are flash_attn_extend's; ``layout`` names the caches' layout only.  ``k_new``, ``v_new`` (both or neither,
     (T, Hkv, d_new) packed like q): appended as by ragged_append in front of the attention, one library call.  ``block_table``: a
     paged cache, as in flash_attn_decode; ``max_pages``, when given, must be the table's second dimension (the figure a workspace
-    was sized with through ragged_workspace(..., max_pages=): a mismatch is an error here, not a workspace of the wrong size).  ``workspace``: from ragged_workspace (always needed: it
-    holds the block map).  Per sequence the result is flash_attn_extend's on that sequence alone (bit for bit where both run as one
-    split).  A step in which EVERY sequence decodes one token is faster through flash_attn_decode (measured, profiles/ragged_bench.txt:
-    1.10x in bf16, 2.4x in fp32 at B = 32, length 4096).  ``window``: sliding-window attention, as in flash_attn_decode
-    (fa_mi355x_fwd_ragged_window; token i of sequence b sits at len_b - nq_b + i and admits the W keys up to its own position); size
-    a workspace with ragged_workspace(..., window=).  ``sink``: attention-sink tokens beside the window, as in flash_attn_decode
-    (fa_mi355x_fwd_ragged_sink: the first S positions of each sequence; ragged_workspace(..., window=, sink=)).
+    was sized with through ragged_workspace(..., max_pages=): a mismatch is an error here, not a workspace of the wrong size).
+    ``workspace``: from ragged_workspace (always needed: it holds the block map).  Per sequence the result is flash_attn_extend's
+    on that sequence alone (bit for bit where both run as one split).  A step in which EVERY sequence decodes one token is faster
+    through flash_attn_decode (measured, profiles/ragged_bench.txt: 1.10x in bf16, 2.4x in fp32 at B = 32, length 4096).
+    ``window``: sliding-window attention, as in flash_attn_decode (fa_mi355x_fwd_ragged_window; token i of sequence b sits at
+    len_b - nq_b + i and admits the W keys up to its own position); size a workspace with ragged_workspace(..., window=).
+    ``sink``: attention-sink tokens beside the window, as in flash_attn_decode (fa_mi355x_fwd_ragged_sink: the first S positions of
+    each sequence; ragged_workspace(..., window=, sink=)).
     ``rotary_cos`` / ``rotary_sin`` / ``rotary_interleaved`` / ``q_rot``: rotary embeddings, as in flash_attn_decode
     (fa_mi355x_rope_append_ragged, then the attend-only ragged call on q_rot; token i of sequence b sits at
     clamp(len_b, 0, Ncap) - nq_b + i; the rows of q_rot that no sequence owns keep what they held).
     Returns (out fp32 (T, H, d), lse fp32 (H, T)): rows with no admissible key give out = 0, lse = -inf; rows of the unused tail
     keep what they held."""
-    window = _check_window(window, causal)
-    sink = _check_sink(sink, window)
-    rotary = _rotary_of(rotary_cos, rotary_sin, rotary_interleaved, q.device)
-    if rotary is None and q_rot is not None:
-        raise ValueError("q_rot is where a roped call leaves the rotated q: it needs rotary_cos and rotary_sin")
-    if (k_new is None) != (v_new is None):
-        raise ValueError("k_new and v_new go together: give both (fused append) or neither")
-    pages, Hkv, dp, _ = _cache_geometry(k_cache, v_cache, layout, block_table)
-    dtype = _dtype_code(q)
-    if k_cache.dtype != q.dtype:
-        raise TypeError("q, k_cache and v_cache must share one dtype")
-    mp = _max_pages(block_table, None)
-    if max_pages is not None and max_pages != mp:   # (the caller's own figure, e.g. the one a workspace was sized with: held against the table)
-        raise ValueError(f"max_pages = {max_pages} is not the block_table's second dimension ({mp}; a contiguous cache has none)")
-    B, H, Hkv, T, Ncap, d, dp = _ragged_dims(q, k_cache, cu_seqlens_q, layout, mp)
-    if d > dp:
-        raise ValueError(f"q's head dim {d} exceeds the cache's row length {dp}")
-    _check_seqlens(cache_seqlens, B, q.device)
-    if pages:
-        _check_table(block_table, B, q.device)
-    if k_new is not None:
-        _, d_new = _check_new_ragged(k_new, v_new, k_cache, T, Hkv, dp)
-    for t in (q, k_cache, v_cache):
-        if t.device != q.device:
-            raise ValueError("q, k_cache and v_cache must live on one device")
-        if not t.is_contiguous():
-            raise ValueError("q, k_cache and v_cache must be contiguous")
-    if out is not None and (out.shape != q.shape or out.dtype != torch.float32 or not out.is_contiguous()):
-        raise ValueError("out must be a contiguous float32 tensor of q's shape")
-    if lse is not None and (tuple(lse.shape) != (H, T) or lse.dtype != torch.float32 or not lse.is_contiguous()):
-        raise ValueError("lse must be a contiguous float32 tensor of shape (H, T)")
-    lib = _lib.decode()
-    if workspace is not None and workspace.numel() * workspace.element_size() < _ragged_workspace_bytes(B, H, Hkv, T, Ncap, dp, window, sink):
-        raise ValueError("workspace too small: size it with ragged_workspace()")
-    for t in (q, k_cache, v_cache):
-        _require_gpu(t, "flash_attn_ragged")
-    if softmax_scale is None:
-        softmax_scale = 0.0 if d == dp else d ** -0.5
-    qp = pad_head_dim(q, dp) if d < dp else q
-    if out is not None and d == dp:
-        outp = out
-    elif out is not None:   # (padded: the rows of the unused tail must come back as the caller's out held them)
-        outp = pad_head_dim(out, dp)
-    else:
-        outp = torch.empty(qp.shape, dtype=torch.float32, device=q.device)
-    if lse is None:
-        lse = torch.empty((H, T), dtype=torch.float32, device=q.device)
-    if workspace is None:
-        workspace = ragged_workspace(qp, k_cache, cu_seqlens_q, layout, max_pages=mp, window=window, sink=sink)
-    if rotary:   # (the roped append, then the attend-only form of whatever follows, on the rotated q)
-        _check_rot(rotary, d, d_new if k_new is not None else None)
-        qr = _q_rot_buffer(q_rot, q, qp)
-        _rope_append(rotary, qp, qr, k_new, v_new, k_cache, v_cache, None, None, cache_seqlens, cu_seqlens_q, block_table, B, H, Hkv, T, Ncap,
-                     (*pages, mp) if pages else None, d_new if k_new is not None else dp, dp, layout, False, dtype)
-        if q_rot is not None and qr is not q_rot:
-            q_rot.copy_(qr[..., :d])
-        qp, k_new, v_new = qr, None, None
-    if window is not None:   # (the family's one windowed entry point: null k_new / v_new attend only, a null table is a slab cache)
-        geometry = (0, *pages, mp) if pages else (Ncap, 0, 0, 0)
-        fwd, win = (lib.fa_mi355x_fwd_ragged_window, (window,)) if sink is None else (lib.fa_mi355x_fwd_ragged_sink, (window, sink))
-        status = fwd(
-            _ptr(qp), _ptr(k_new), _ptr(v_new), _ptr(k_cache), _ptr(v_cache), _ptr(outp), _ptr(lse), _ptr(cu_seqlens_q), _ptr(cache_seqlens),
-            _ptr(block_table), _ptr(workspace), B, H, Hkv, T, *geometry, d_new if k_new is not None else dp, dp, _DECODE_LAYOUTS[layout],
-            float(softmax_scale), int(bool(causal)), *win, dtype, _stream_ptr())
-        _lib.decode_check(status)
-        return (_unpad(outp, d, out) if d < dp else outp), lse
-    new = (_ptr(k_new), _ptr(v_new)) if k_new is not None else ()
-    dims = (d_new, dp) if k_new is not None else (dp,)
-    name = "fa_mi355x_fwd_ragged" + ("_append" if k_new is not None else "") + ("_paged" if pages else "")
-    where = (_ptr(block_table), _ptr(workspace), B, H, Hkv, T, *pages, mp) if pages else (_ptr(workspace), B, H, Hkv, T, Ncap)
-    status = getattr(lib, name)(_ptr(qp), *new, _ptr(k_cache), _ptr(v_cache), _ptr(outp), _ptr(lse), _ptr(cu_seqlens_q), _ptr(cache_seqlens),
-                                *where, *dims, _DECODE_LAYOUTS[layout], float(softmax_scale), int(bool(causal)), dtype, _stream_ptr())
-    _lib.decode_check(status)
-    return (_unpad(outp, d, out) if d < dp else outp), lse
+    return _kv_attention("ragged", q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, causal, softmax_scale, layout, out, lse, workspace, k_new,
+                         v_new, block_table, max_pages, window, None, None, sink, rotary_cos, rotary_sin, rotary_interleaved, q_rot)

@@ -27,7 +27,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from flash_attention_minitorch_amd import device_ops, modules_transformer as mt  # noqa: E402
+from flash_attention_minitorch_amd import _lib, device_ops, modules_transformer as mt  # noqa: E402
 from bench_window import B, D, H, HKV, rnd, run  # noqa: E402
 
 PAGE, ROT = 256, 128
@@ -69,10 +69,16 @@ class Case:
         device_ops.extend_append(self.kn, self.vn, self.kc, self.vc, self.lens, **self.where)
 
     def rope_append(self):
+        """fa_mi355x_rope_append alone, its arguments by the names of the prototype (include/flash_attn_mi355x_decode_rope.h)."""
         table = self.where.get("block_table")
-        pool = (self.kc.shape[0], PAGE, table.shape[1]) if table is not None else None
-        device_ops._rope_append((self.cos, self.sin, (ROT, self.N, 0)), self.q, self.q_rot, self.kn, self.vn, self.kc, self.vc, None, None,
-                                self.lens, None, table, B, H, HKV, self.T, self.N, pool, D, D, "bnhd", False, 1)
+        num_pages, page_size, max_pages = (self.kc.shape[0], PAGE, table.shape[1]) if table is not None else (0, 0, 0)
+        ptr = device_ops._ptr
+        _lib.decode_check(device_ops._kv_call("fa_mi355x_rope_append", dict(
+            q=ptr(self.q), q_rot=ptr(self.q_rot), k_new=ptr(self.kn), v_new=ptr(self.vn), k_cache=ptr(self.kc), v_cache=ptr(self.vc),
+            k_scale=None, v_scale=None, cos=ptr(self.cos), sin=ptr(self.sin), cache_seqlens=ptr(self.lens), block_table=ptr(table), B=B, H=H,
+            Hkv=HKV, Nq=self.T, Ncap=0 if table is not None else self.N, num_pages=num_pages, page_size=page_size, max_pages=max_pages,
+            d_new=D, d=D, rot=ROT, max_pos=self.N, layout=_lib.FA_LAYOUT_BNHD, interleaved=0, cache_fp8=0, dtype=_lib.FA_DTYPE_BF16,
+            stream=device_ops._stream_ptr())))
 
     # (b), (c) the fused calls
     def fused(self):
