@@ -16,6 +16,8 @@ LayerNorm, the feed-forward block and the embedding of ``DecoderLM`` (:255-351) 
 """
 from __future__ import annotations
 
+import collections
+
 import torch
 
 from . import _lib, device_ops
@@ -123,17 +125,14 @@ def attention_stack(x, layers, n_head: int, causal: bool = True, fused_layout: b
 # with the decode kernels (attention_stack_step): one pass over the cached K and V per layer instead of causal attention over N tokens.
 # More than 128 new tokens at once (a second turn, a long message after a cached prefix, a prompt fed in pieces) go through the
 # extend kernels (attention_stack_extend, attention_stack_prefill_chunked).
-# A cache built with window=W makes every one of these calls a sliding-window one (each token sees the last W positions): the step,
-# fused step, extend, ragged and chunked-prefill functions and GraphedStep pass cache.window to device_ops, and a PagedKVCache gives
-# the pages behind the window back through release_behind_window.  With sink=S beside the window every token also keeps the first S
-# positions (attention sinks): windowing() carries both, and the pages that hold those rows are never released.
-# A cache built with kv_dtype=torch.float8_e4m3fn holds e4m3 bytes with one scale per (layer, kv head): the fused step, extend and
-# chunked-prefill functions and GraphedStep pass the layer's scales (cache.quant(li)) to the same device_ops calls, which quantise on
-# the append; a prompt fills the cache through extend_append while its own attention stays the square forward on the unquantised k, v.
-# A cache built with rope=Rotary(...) encodes positions with rotary embeddings: rotary() carries the tables to every fused step,
-# extend, ragged and chunked-prefill call and to GraphedStep (one fa_mi355x_rope_append launch per layer rotates q and the new k on
-# their way in, then the attend-only call runs); the square prefill and the unfused step rotate q and k with apply_rotary.  The
-# cache holds ROTATED keys.
+# The step, fused step, extend and ragged functions (and through them chunked prefill and GraphedStep) are ONE loop, _advance, and
+# every attend call in it takes the cache's features from ONE place, cache.keywords(li):
+# window=W makes every call a sliding-window one (each token sees the last W positions), and a PagedKVCache gives the pages behind
+# the window back through release_behind_window; with sink=S every token also keeps the first S positions (attention sinks), whose
+# pages are never released.  kv_dtype=torch.float8_e4m3fn: the cache holds e4m3 bytes with one scale per (layer, kv head), the calls
+# quantise on the append, and a prompt fills the cache through extend_append while its own attention stays the square forward on the
+# unquantised k, v.  rope=Rotary(...): one fa_mi355x_rope_append launch per layer rotates q and the new k on their way in, then the
+# attend-only call runs; the square prefill and the unfused step rotate q and k with apply_rotary.  The cache holds ROTATED keys.
 
 MAX_STEP_TOKENS = 128   # fa_mi355x_fwd_decode's largest Nq; longer inputs are prefill, or attention_stack_extend after a prefix
 
@@ -204,11 +203,15 @@ class KVCache:
     functions and GraphedStep quantise on the append; attention_stack_step (torch indexing), attention_stack_ragged, a window
     and sink tokens are not built for it.
     ``rope`` (None, or a Rotary whose tables cover the capacity): the stack encodes positions with ROTARY embeddings; the stack
-    functions rotate every q and every new k by its position (the row it is appended to), and the cache holds rotated keys."""
+    functions rotate every q and every new k by its position (the row it is appended to), and the cache holds rotated keys.
+    The constructor, which is PagedKVCache's too, checks in this order and reports the first fault: ``window``, ``sink``,
+    ``n_kv_head``, what the memory layout adds (_pool: nothing here; ``page_size``, ``capacity``, ``n_pages`` of a PagedKVCache),
+    ``rope``, then ``kv_dtype`` / ``kv_scale``."""
+
+    block_table = None   # (a PagedKVCache has one)
 
     def __init__(self, n_layers, B, capacity, n_head, head_dim, dtype, device, n_kv_head=None, window=None, kv_dtype=None, kv_scale=None,
                  sink=None, rope=None):
-        self.rope = _check_cache_rope(rope, capacity, head_dim)
         self.window = _check_cache_window(window)
         self.sink = _check_cache_sink(sink, self.window)
         self.head_dim, self.dp = head_dim, device_ops.padded_head_dim(head_dim)
@@ -216,7 +219,8 @@ class KVCache:
         self.n_kv_head = n_head if n_kv_head is None else n_kv_head
         if self.n_kv_head <= 0 or n_head % self.n_kv_head:
             raise ValueError(f"n_kv_head = {n_kv_head} must divide n_head = {n_head}")
-        shape = (B, capacity, self.n_kv_head, self.dp)
+        shape, rows = self._pool(B)
+        self.rope = _check_cache_rope(rope, rows, head_dim)
         dtype, self.kv_scale = _check_cache_quant(kv_dtype, kv_scale, dtype, self.window, n_layers, self.n_kv_head, device)
         self.k = [torch.zeros(shape, dtype=dtype, device=device) for _ in range(n_layers)]
         self.v = [torch.zeros(shape, dtype=dtype, device=device) for _ in range(n_layers)]
@@ -224,8 +228,15 @@ class KVCache:
         self.length_bound = 0   # host-side upper bound of every length: capacity checks without a device synchronisation
         self._workspaces = {}
 
-    block_table = None   # (a PagedKVCache has one)
-    rope = None
+    def _pool(self, B):
+        """(the shape of every layer's k and v, the rows a sequence can reach: the positions the rope tables must cover)."""
+        return (B, self.capacity, self.n_kv_head, self.dp), self.capacity
+
+    def keywords(self, li, rotary=True, **new):
+        """Every keyword an attend call on layer ``li`` of this cache takes beside its tensors: paging, windowing, quant and rotary,
+        and the caller's own (``new``: k_new=, v_new=).  A new cache feature adds its provider here, and every stack function passes
+        it.  ``rotary=False``: the caller has rotated q and k itself (the unfused step)."""
+        return {**new, **self.paging(), **self.windowing(), **self.quant(li), **(self.rotary() if rotary else {})}
 
     def rotary(self):
         """The keywords that make a device_ops call a roped one: none for a cache without rotary embeddings."""
@@ -256,23 +267,28 @@ class KVCache:
     def reserve(self, n_tokens, rows=None):
         """Make sure the sequences own memory for ``n_tokens`` rows: a slab cache owns its ``capacity`` rows from the start."""
 
-    def workspace(self, q):
-        key = (self.window, self.sink) + tuple(q.shape)   # (a windowed call splits on its window span: a buffer of its own size)
+    def restart(self):
+        """Forget every sequence, for a new prompt: all lengths and their bound to 0 (the rows stay: the next append overwrites them)."""
+        self.lengths.zero_()
+        self.length_bound = 0
+
+    def _workspace(self, family, q, *cu_seqlens_q):
+        """The scratch of the ``family`` ("decode", "extend", "ragged") call with this q, sized once per key: every family splits by a
+        policy of its own (and the ragged call's block map lives there), and a windowed call on its window and sink spans."""
+        key = (() if family == "decode" else (family,)) + (self.window, self.sink) + tuple(q.shape)
         if key not in self._workspaces:
-            self._workspaces[key] = device_ops.decode_workspace(q, self.k[0], "bnhd", **self.paging(), **self.windowing())
+            size = getattr(device_ops, family + "_workspace")
+            self._workspaces[key] = size(q, self.k[0], *cu_seqlens_q, "bnhd", **self.paging(), **self.windowing())
         return self._workspaces[key]
+
+    def workspace(self, q):
+        return self._workspace("decode", q)
 
     def extend_workspace(self, q):
-        key = ("extend", self.window, self.sink) + tuple(q.shape)   # (the extend call has a split policy of its own: never the decode call's buffer)
-        if key not in self._workspaces:
-            self._workspaces[key] = device_ops.extend_workspace(q, self.k[0], "bnhd", **self.paging(), **self.windowing())
-        return self._workspaces[key]
+        return self._workspace("extend", q)
 
     def ragged_workspace(self, q, cu_seqlens_q):
-        key = ("ragged", self.window, self.sink) + tuple(q.shape)   # (the ragged call sizes its own: the block map lives there)
-        if key not in self._workspaces:
-            self._workspaces[key] = device_ops.ragged_workspace(q, self.k[0], cu_seqlens_q, "bnhd", **self.paging(), **self.windowing())
-        return self._workspaces[key]
+        return self._workspace("ragged", q, cu_seqlens_q)
 
     def _pad(self, t):
         return t if self.dp == self.head_dim else device_ops.pad_head_dim(t, self.dp)
@@ -297,34 +313,34 @@ class PagedKVCache(KVCache):
 
     def __init__(self, n_layers, B, capacity, n_head, head_dim, dtype, device, n_kv_head=None, page_size=128, n_pages=None, window=None,
                  kv_dtype=None, kv_scale=None, sink=None, rope=None):
-        self.window = _check_cache_window(window)
-        self.sink = _check_cache_sink(sink, self.window)
-        self.head_dim, self.dp = head_dim, device_ops.padded_head_dim(head_dim)
-        self.capacity, self.n_head = capacity, n_head
-        self.n_kv_head = n_head if n_kv_head is None else n_kv_head
-        if self.n_kv_head <= 0 or n_head % self.n_kv_head:
-            raise ValueError(f"n_kv_head = {n_kv_head} must divide n_head = {n_head}")
-        if page_size <= 0 or page_size % _lib.FA_PAGE_ROWS:
-            raise ValueError(f"page_size = {page_size} must be a positive multiple of {_lib.FA_PAGE_ROWS} rows")
-        if capacity <= 0:
-            raise ValueError("capacity must be positive")
-        self.page_size, self.max_pages = page_size, -(-capacity // page_size)
-        self.rope = _check_cache_rope(rope, self.max_pages * page_size, head_dim)   # (the library holds max_pos against the table's rows)
-        self.sink_pages = -(-(self.sink or 0) // page_size)   # leading table slots that release_behind_window keeps
-        self.n_pages = B * self.max_pages if n_pages is None else n_pages
-        if self.n_pages <= 0:
-            raise ValueError("n_pages must be positive")
-        shape = (self.n_pages, page_size, self.n_kv_head, self.dp)
-        dtype, self.kv_scale = _check_cache_quant(kv_dtype, kv_scale, dtype, self.window, n_layers, self.n_kv_head, device)
-        self.k = [torch.zeros(shape, dtype=dtype, device=device) for _ in range(n_layers)]
-        self.v = [torch.zeros(shape, dtype=dtype, device=device) for _ in range(n_layers)]
+        self.page_size, self.n_pages = page_size, n_pages   # (as given: _pool checks them at their place in KVCache's order)
+        super().__init__(n_layers, B, capacity, n_head, head_dim, dtype, device, n_kv_head, window, kv_dtype, kv_scale, sink, rope)
         self.block_table = torch.zeros((B, self.max_pages), dtype=torch.int32, device=device)   # (entries past a sequence's pages: never read)
-        self.lengths = torch.zeros(B, dtype=torch.int32, device=device)
-        self.length_bound = 0
-        self._workspaces = {}
         self.free = list(range(self.n_pages - 1, -1, -1))   # (handed out from the end: page 0 first)
         self.pages = [[] for _ in range(B)]                 # the pages of each sequence, in order
         self.released = [0] * B                             # table slots behind the sink slots given back by release_behind_window
+
+    def _pool(self, B):
+        if self.page_size <= 0 or self.page_size % _lib.FA_PAGE_ROWS:
+            raise ValueError(f"page_size = {self.page_size} must be a positive multiple of {_lib.FA_PAGE_ROWS} rows")
+        if self.capacity <= 0:
+            raise ValueError("capacity must be positive")
+        self.max_pages = -(-self.capacity // self.page_size)
+        self.sink_pages = -(-(self.sink or 0) // self.page_size)   # leading table slots that release_behind_window keeps
+        if self.n_pages is None:
+            self.n_pages = B * self.max_pages
+        if self.n_pages <= 0:
+            raise ValueError("n_pages must be positive")
+        # (the library holds the rope tables' max_pos against the table's rows, not the capacity)
+        return (self.n_pages, self.page_size, self.n_kv_head, self.dp), self.max_pages * self.page_size
+
+    def restart(self):
+        """KVCache.restart; the sequences that gave leading pages back (release_behind_window) are released whole, so that each
+        starts over owning row 0 again.  The others keep their pages."""
+        super().restart()
+        for b, gone in enumerate(self.released):
+            if gone:
+                self.release(b)
 
     def reserve(self, n_tokens, rows=None):
         """Make sure the sequences ``rows`` (default all) own pages for ``n_tokens`` cache rows each.  New pages come from the free list
@@ -397,8 +413,14 @@ def _project(x, wq, wk, wv, n_head):
 
 
 def _check_kv_heads(k, cache):
-    if k.shape[2] != cache.n_kv_head:
-        raise ValueError(f"the layers project {k.shape[2]} kv heads, the cache holds {cache.n_kv_head}")
+    """k (B, T, Hkv, d), or packed (T, Hkv, d): the head axis is the last but one."""
+    if k.shape[-2] != cache.n_kv_head:
+        raise ValueError(f"the layers project {k.shape[-2]} kv heads, the cache holds {cache.n_kv_head}")
+
+
+def _check_room(cache, n_tokens):
+    if cache.length_bound + n_tokens > cache.capacity:
+        raise ValueError(f"cache capacity {cache.capacity} exceeded")
 
 
 def attention_stack_prefill(x, layers, n_head: int, cache: KVCache):
@@ -413,71 +435,100 @@ def attention_stack_prefill(x, layers, n_head: int, cache: KVCache):
     if cache.window is not None:
         return attention_stack_prefill_chunked(x, layers, n_head, cache, max(P, 1))
     d = E // n_head
-    if cache.block_table is not None or cache.fp8:
-        cache.reserve(P)
-        cache.lengths.fill_(P)   # (the library's append places the prompt by the lengths)
+    # an fp8 cache, slab or paged, and every paged one take the prompt through the library's append (it quantises, and it knows the
+    # pages), at rows lengths[b] - P .. lengths[b] - 1 = 0 .. P - 1 of every sequence; a plain slab is filled by torch indexing
+    library_append = cache.block_table is not None or cache.fp8
+    cache.reserve(P)
+    cache.lengths.fill_(P)
+    cache.length_bound = P
+    # (a grouped-query stack: the kernels read the Hkv heads in place)
+    fwd = device_ops.flash_attn_fwd_bnhd if cache.n_kv_head == n_head else device_ops.flash_attn_fwd_gqa
     for li, (wq, wk, wv, wo) in enumerate(layers):
         q, k, v = _project(x, wq, wk, wv, n_head)
         _check_kv_heads(k, cache)
         if cache.rope is not None:   # (token i of the prompt sits at position i; the cache is filled with the rotated k)
             q, k = cache.rope.apply(q), cache.rope.apply(k)
         kp, vp = cache._pad(k), cache._pad(v)
-        if cache.block_table is None and not cache.fp8:
+        if library_append:   # (k is rotated already and an append has no window: paging and quant only; zero columns past head_dim)
+            device_ops.extend_append(k, v, cache.k[li], cache.v[li], cache.lengths, "bnhd", **cache.paging(), **cache.quant(li))
+        else:
             cache.k[li][:, :P] = kp
             cache.v[li][:, :P] = vp
-        else:   # rows lengths[b] - P .. lengths[b] - 1 = 0 .. P - 1 of every sequence's pages (zero columns past head_dim); an fp8
-            # cache, slab or paged, is filled here too: the append quantises, and the attention below reads the unquantised k, v
-            device_ops.extend_append(k, v, cache.k[li], cache.v[li], cache.lengths, "bnhd", **cache.paging(), **cache.quant(li))
-        # (a grouped-query stack: the kernels read the Hkv heads in place)
-        fwd = device_ops.flash_attn_fwd_bnhd if cache.n_kv_head == n_head else device_ops.flash_attn_fwd_gqa
-        if cache.dp == d:
+        if cache.dp == d:   # (the prompt's own attention reads the unquantised k, v)
             o, _, _ = fwd(q, kp, vp, True, _lib.FA_VARIANT_FA2)
         else:   # zero columns add nothing to the scores; the scale keeps the caller's d
             o, _, _ = fwd(cache._pad(q), kp, vp, True, _lib.FA_VARIANT_FA2, softmax_scale=d ** -0.5)
             o = o[..., :d]
         x = x + (o.reshape(B * P, E).to(x.dtype) @ wo).view(B, P, E)
-    cache.lengths.fill_(P)
-    cache.length_bound = P
     return x
 
 
-def _step(x_new, layers, n_head: int, cache: KVCache, fused: bool):
-    B, T, E = x_new.shape
-    if T > MAX_STEP_TOKENS:
-        raise ValueError(f"a step takes at most {MAX_STEP_TOKENS} tokens; use attention_stack_prefill for longer inputs")
-    if cache.length_bound + T > cache.capacity:
-        raise ValueError(f"cache capacity {cache.capacity} exceeded")
-    if not fused and cache.block_table is not None:
+def _indexed_append(cache, x_new):
+    """attention_stack_step's append, torch indexing into a slab: checks, and returns place(li, q, k, v) -> the q to attend with."""
+    if cache.block_table is not None:
         raise ValueError("attention_stack_step appends with torch indexing into a slab: a PagedKVCache steps through "
                          "attention_stack_step_fused")
-    if not fused and cache.fp8:
+    if cache.fp8:
         raise ValueError("attention_stack_step appends with torch indexing, which does not quantise: an fp8 cache steps through "
                          "attention_stack_step_fused")
-    cache.reserve(cache.length_bound + T)
-    dev = x_new.device
-    if not fused:
-        # rows b * capacity + lengths[b] + t of the (B * capacity, Hkv, dp) view of a layer's cache: the new tokens' k and v
-        rows = (cache.lengths.long() + torch.arange(B, device=dev) * cache.capacity)[:, None] + torch.arange(T, device=dev)
-        rows = rows.reshape(B * T)
-    new_len = cache.lengths + T
+    (B, T, _), dev, hkv = x_new.shape, x_new.device, cache.n_kv_head
+    # rows b * capacity + lengths[b] + t of the (B * capacity, Hkv, dp) view of a layer's cache: the new tokens' k and v
+    rows = (cache.lengths.long() + torch.arange(B, device=dev) * cache.capacity)[:, None] + torch.arange(T, device=dev)
+    rows = rows.reshape(B * T)
+
+    def place(li, q, k, v):
+        if cache.rope is not None:   # (token t of batch element b sits at position lengths[b] + t)
+            q, k = cache.rope.apply(q, cache.lengths), cache.rope.apply(k, cache.lengths)
+        for dst, t in ((cache.k[li], k), (cache.v[li], v)):
+            dst.view(B * cache.capacity, hkv, cache.dp).index_copy_(0, rows, cache._pad(t).reshape(B * T, hkv, cache.dp))
+        return q
+    return place
+
+
+# What tells the calls that advance a cache apart: the device_ops function that attends, the family whose workspace it takes, x_new
+# packed (T, E) with per-sequence counts or batched (B, T, E), the bound on T, and the append of the one call that does its own.
+_Family = collections.namedtuple("_Family", "attend workspace packed max_tokens append", defaults=(False, None, None))
+_STEP = _Family(device_ops.flash_attn_decode, "decode", max_tokens=MAX_STEP_TOKENS, append=_indexed_append)
+_STEP_FUSED = _Family(device_ops.flash_attn_decode, "decode", max_tokens=MAX_STEP_TOKENS)
+_EXTEND = _Family(device_ops.flash_attn_extend, "extend")
+_RAGGED = _Family(device_ops.flash_attn_ragged, "ragged", packed=True)
+
+
+def _advance(family, x_new, layers, n_head: int, cache: KVCache, counts=None):
+    """The one loop behind the step, the fused step, extend and ragged: make room for the new tokens (``counts[b]`` of sequence b in a
+    packed x_new, T of every sequence otherwise), then per layer project, hand q and the new k, v to the family's attend call (it
+    writes them at rows new_len[b] - n .. new_len[b] - 1, zero columns past head_dim, rotated on a roped cache, then attends) and add
+    the out-projection to the residual.  Lengths grow on the device, their bound on the host.  Only the ragged family builds
+    tensors on the host (counts, cu) and copies them over: GraphedStep captures the fused step, which must never."""
+    packed, shape = family.packed, tuple(x_new.shape)
+    T, E = shape[-2:]
+    if family.max_tokens is not None and T > family.max_tokens:
+        raise ValueError(f"a step takes at most {family.max_tokens} tokens; use attention_stack_prefill for longer inputs")
+    grow = max(counts) if packed else T
+    _check_room(cache, grow)
+    place = family.append and family.append(cache, x_new)
+    cache.reserve(cache.length_bound + grow, [b for b, c in enumerate(counts) if c > 0] if packed else None)
+    if packed:
+        cnt = torch.tensor(counts, dtype=torch.int32)
+        cu = torch.cat([torch.zeros(1, dtype=torch.int32), torch.cumsum(cnt, 0, dtype=torch.int32)]).to(x_new.device)
+        cu, new_len = (cu,), cache.lengths + cnt.to(x_new.device)   # (cu_seqlens_q: the ragged calls' one argument more)
+    else:
+        cu, new_len = (), cache.lengths + T
     x = x_new
     for li, (wq, wk, wv, wo) in enumerate(layers):
-        q, k, v = _project(x, wq, wk, wv, n_head)
+        q, k, v = _project(x[None] if packed else x, wq, wk, wv, n_head)
+        if packed:
+            q, k, v = q[0], k[0], v[0]   # (T, heads, d)
         _check_kv_heads(k, cache)
-        new = {}
-        if fused:   # the library writes k and v at rows new_len[b] - T .. new_len[b] - 1 (zero columns past head_dim), then attends
-            new = dict(k_new=k, v_new=v, **cache.rotary())   # (a roped cache: q and k rotated on their way in, at those rows' positions)
+        if place:
+            q, kw = place(li, q, k, v), cache.keywords(li, rotary=False)
         else:
-            if cache.rope is not None:   # (token t of batch element b sits at position lengths[b] + t)
-                q, k = cache.rope.apply(q, cache.lengths), cache.rope.apply(k, cache.lengths)
-            hkv = cache.n_kv_head
-            for dst, t in ((cache.k[li], k), (cache.v[li], v)):
-                dst.view(B * cache.capacity, hkv, cache.dp).index_copy_(0, rows, cache._pad(t).reshape(B * T, hkv, cache.dp))
-        o, _ = device_ops.flash_attn_decode(q, cache.k[li], cache.v[li], new_len, causal=True, layout="bnhd",
-                                            workspace=cache.workspace(q), **new, **cache.paging(), **cache.windowing(), **cache.quant(li))
-        x = x + (o.reshape(B * T, E).to(x.dtype) @ wo).view(B, T, E)
+            kw = cache.keywords(li, k_new=k, v_new=v)
+        o, _ = family.attend(q, cache.k[li], cache.v[li], *cu, new_len, causal=True, layout="bnhd",
+                             workspace=cache._workspace(family.workspace, q, *cu), **kw)
+        x = x + (o.reshape(-1, E).to(x.dtype) @ wo).view(shape)
     cache.lengths.copy_(new_len)
-    cache.length_bound += T
+    cache.length_bound += grow
     return x
 
 
@@ -487,14 +538,14 @@ def attention_stack_step(x_new, layers, n_head: int, cache: KVCache):
     attends causally to the cache with the decode kernels (a grouped-query stack appends its Hkv heads and its n_head query heads
     read them in place); lengths grow by T.  Returns the stack's output for the new tokens (B, T, E),
     the last T rows of attention_stack over the whole sequence."""
-    return _step(x_new, layers, n_head, cache, fused=False)
+    return _advance(_STEP, x_new, layers, n_head, cache)
 
 
 def attention_stack_step_fused(x_new, layers, n_head: int, cache: KVCache):
     """attention_stack_step with the append inside the library: every layer hands q, k and v to one fused call
     (flash_attn_decode(..., k_new=, v_new=)), which writes k and v into the cache and then attends.  No row indices, padded copies
     or index_copy_ on the caller's side; the same results and the same cache contents, bit for bit."""
-    return _step(x_new, layers, n_head, cache, fused=True)
+    return _advance(_STEP_FUSED, x_new, layers, n_head, cache)
 
 
 def attention_stack_extend(x_new, layers, n_head: int, cache: KVCache):
@@ -505,24 +556,9 @@ def attention_stack_extend(x_new, layers, n_head: int, cache: KVCache):
     attends causally with the extend kernels (128 rows per workgroup sharing each staged tile of the cache).  Lengths grow by T on
     the device; the capacity check is the host's, through ``cache.length_bound``.  Returns the stack's output for the new tokens
     (B, T, E): the last T rows of attention_stack over the whole sequence."""
-    B, T, E = x_new.shape
-    if T <= MAX_STEP_TOKENS:
+    if x_new.shape[1] <= MAX_STEP_TOKENS:
         return attention_stack_step_fused(x_new, layers, n_head, cache)
-    if cache.length_bound + T > cache.capacity:
-        raise ValueError(f"cache capacity {cache.capacity} exceeded")
-    cache.reserve(cache.length_bound + T)
-    new_len = cache.lengths + T
-    x = x_new
-    for li, (wq, wk, wv, wo) in enumerate(layers):
-        q, k, v = _project(x, wq, wk, wv, n_head)
-        _check_kv_heads(k, cache)
-        o, _ = device_ops.flash_attn_extend(q, cache.k[li], cache.v[li], new_len, causal=True, layout="bnhd",
-                                            workspace=cache.extend_workspace(q), k_new=k, v_new=v, **cache.paging(), **cache.windowing(),
-                                            **cache.quant(li), **cache.rotary())
-        x = x + (o.reshape(B * T, E).to(x.dtype) @ wo).view(B, T, E)
-    cache.lengths.copy_(new_len)
-    cache.length_bound += T
-    return x
+    return _advance(_EXTEND, x_new, layers, n_head, cache)
 
 
 def attention_stack_ragged(x_new, counts, layers, n_head: int, cache: KVCache):
@@ -539,30 +575,11 @@ def attention_stack_ragged(x_new, counts, layers, n_head: int, cache: KVCache):
         raise ValueError("x_new must be packed: (T, E)")
     if cache.fp8:
         raise ValueError("the ragged calls on an fp8 cache are not built: step an fp8 cache through attention_stack_step_fused / _extend")
-    T, E = x_new.shape
-    B = cache.lengths.shape[0]
+    T, B = x_new.shape[0], cache.lengths.shape[0]
     counts = [int(c) for c in counts]
     if len(counts) != B or min(counts) < 0 or sum(counts) > T:
         raise ValueError(f"counts must be {B} non-negative ints with sum <= T = {T}")
-    top = max(counts)
-    if cache.length_bound + top > cache.capacity:
-        raise ValueError(f"cache capacity {cache.capacity} exceeded")
-    cache.reserve(cache.length_bound + top, rows=[b for b, c in enumerate(counts) if c > 0])
-    cnt = torch.tensor(counts, dtype=torch.int32)
-    cu = torch.cat([torch.zeros(1, dtype=torch.int32), torch.cumsum(cnt, 0, dtype=torch.int32)]).to(x_new.device)
-    new_len = cache.lengths + cnt.to(x_new.device)
-    x = x_new
-    for li, (wq, wk, wv, wo) in enumerate(layers):
-        q, k, v = (t[0] for t in _project(x[None], wq, wk, wv, n_head))   # packed: (T, heads, d)
-        if k.shape[1] != cache.n_kv_head:
-            raise ValueError(f"the layers project {k.shape[1]} kv heads, the cache holds {cache.n_kv_head}")
-        o, _ = device_ops.flash_attn_ragged(q, cache.k[li], cache.v[li], cu, new_len, causal=True, layout="bnhd",
-                                            workspace=cache.ragged_workspace(q, cu), k_new=k, v_new=v, **cache.paging(),
-                                            **cache.windowing(), **cache.rotary())
-        x = x + o.reshape(T, E).to(x.dtype) @ wo
-    cache.lengths.copy_(new_len)
-    cache.length_bound += top
-    return x
+    return _advance(_RAGGED, x_new, layers, n_head, cache, counts)
 
 
 def attention_stack_prefill_chunked(x, layers, n_head: int, cache: KVCache, chunk: int):
@@ -573,11 +590,7 @@ def attention_stack_prefill_chunked(x, layers, n_head: int, cache: KVCache, chun
         raise ValueError("chunk must be positive")
     if x.shape[1] > cache.capacity:
         raise ValueError(f"prompt of {x.shape[1]} tokens exceeds the cache capacity {cache.capacity}")
-    cache.lengths.zero_()
-    cache.length_bound = 0
-    for b, gone in enumerate(getattr(cache, "released", ())):
-        if gone:   # (a windowed paged cache that gave its leading pages back: the sequence starts over and owns row 0 again)
-            cache.release(b)
+    cache.restart()
     return torch.cat([attention_stack_extend(piece.contiguous(), layers, n_head, cache) for piece in x.split(chunk, 1)], dim=1)
 
 
@@ -607,25 +620,24 @@ class GraphedStep:
             attention_stack_step_fused(self.x, self.layers, self.n_head, cache)
             cache.lengths.copy_(lengths)
         torch.cuda.current_stream().wait_stream(side)
-        cache.length_bound = bound
+        cache.length_bound = bound   # (for the capture's own capacity check and reserve; step() sets the bound after the replay)
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
+        with torch.cuda.graph(self.graph):   # (runs nothing on the device)
             self.y = attention_stack_step_fused(self.x, self.layers, self.n_head, cache)
-        cache.length_bound = bound   # (capturing runs nothing on the device; step() counts the replays)
 
     def step(self, x_new):
         B, T, E = x_new.shape
         if T != self.T:
             raise ValueError(f"this graph steps {self.T} tokens at a time, got {T}")
-        if self.cache.length_bound + T > self.cache.capacity:
-            raise ValueError(f"cache capacity {self.cache.capacity} exceeded")
+        cache, bound = self.cache, self.cache.length_bound
+        _check_room(cache, T)
         # (a paged cache: the pages of this step, outside the graph; the table is edited in place, so the graph reads the new entries)
-        self.cache.reserve(self.cache.length_bound + T)
+        cache.reserve(bound + T)
         if self.graph is None:
             self._capture(x_new)
         elif x_new.shape != self.x.shape or x_new.dtype != self.x.dtype:
             raise ValueError("x_new must keep the shape and dtype of the captured step")
         self.x.copy_(x_new)
         self.graph.replay()
-        self.cache.length_bound += T
+        cache.length_bound = bound + T
         return self.y
