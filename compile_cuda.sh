@@ -40,6 +40,15 @@ else
   echo "[compile_cuda.sh] $WINDOW is up to date"
 fi
 
+# Packed variable-length (cu_seqlens) forward and backward (include/flash_attn_mi355x_varlen.h): a fourth library, for the same reason
+VARLEN="$OUT_DIR/libflash_attn_mi355x_varlen.so"
+if stale "$VARLEN"; then
+  echo "[compile_cuda.sh] hipcc --offload-arch=$ARCH  fa_varlen.hip -> $VARLEN"
+  "$HIPCC" "${FLAGS[@]}" "$SRC/fa_varlen.hip" -o "$VARLEN"
+else
+  echo "[compile_cuda.sh] $VARLEN is up to date"
+fi
+
 shim() {  # name variant FW|BW
   "$HIPCC" -O2 -fPIC -shared -x c++ "$SRC/fa_shim.cpp" -DFA_SHIM_VARIANT="$2" -DFA_SHIM_"$3" \
       -L"$OUT_DIR" -lflash_attn_mi355x -Wl,-rpath,'$ORIGIN' -o "$OUT_DIR/$1.so"

@@ -352,3 +352,26 @@ def window() -> ctypes.CDLL:
 def window_check(status: int) -> None:
     if status != FA_OK:
         _raise(status, window(), "fa_mi355x_window_last_error", "flash_attn_mi355x_window")
+
+
+# the same for include/flash_attn_mi355x_varlen.h: libflash_attn_mi355x_varlen.so, the packed variable-length (cu_seqlens) forward and
+# backward of the training side and the rotary embedding that restarts at every sequence (tests/test_varlen_cpu.py)
+VARLEN_ABI = {
+    "fa_mi355x_fwd_varlen_workspace_bytes": (_sz, [_i] * 5),
+    "fa_mi355x_bwd_varlen_workspace_bytes": (_sz, [_i] * 5),
+    "fa_mi355x_fwd_varlen": (_i, [_vp] * 7 + [_i] * 5 + [_f, _i, _i, _i, _vp]),
+    "fa_mi355x_bwd_varlen": (_i, [_vp] * 11 + [_i] * 5 + [_f, _i, _i, _i, _vp]),
+    "fa_mi355x_rope_varlen": (_i, [_vp] * 5 + [_i] * 9 + [_vp]),
+    "fa_mi355x_varlen_last_error": (_s, []),
+}
+VARLEN_NAME = "libflash_attn_mi355x_varlen.so"
+
+
+def varlen() -> ctypes.CDLL:
+    """libflash_attn_mi355x_varlen.so (include/flash_attn_mi355x_varlen.h) with argtypes set."""
+    return _typed(VARLEN_NAME, VARLEN_ABI)
+
+
+def varlen_check(status: int) -> None:
+    if status != FA_OK:
+        _raise(status, varlen(), "fa_mi355x_varlen_last_error", "flash_attn_mi355x_varlen")

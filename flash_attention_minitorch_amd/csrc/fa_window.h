@@ -16,6 +16,26 @@
 #pragma once
 #include "fa_common.h"
 
+// The packed variable-length library (fa_varlen.h) builds the three kernels of this file under names of its own, with the block
+// taken from a device-side map instead of blockIdx alone: it defines the hooks below and includes this file as text, the way the
+// sink builds of fa_decode.h share their bodies.  Left undefined, the hooks spell the window library's kernels, token for token.
+//   FA_WIN_KERNEL(stem)       the kernel's name
+//   FA_WIN_GEOM_PARAMS        the parameters that say where the blocks are;  FA_WIN_MASK_PARAMS: the window and the sink
+//   FA_WIN_LOCATE(blk, nb)    sets bh and blk (query blocks);  FA_WIN_LOCATE_KEYS: the same for the key blocks of dK/dV
+//   FA_WIN_ROW0               the first row of the block's matrix within the buffers (a sequence's offset), as size_t
+//   FA_WIN_ROWCONST0          where the row constants (lse, nlc, ndelta) of the block's matrix begin
+#ifndef FA_WIN_KERNEL
+#define FA_WIN_KERNEL(stem) win_##stem##_kernel
+#define FA_WIN_GEOM_PARAMS int N, int nblk, int BH
+#define FA_WIN_MASK_PARAMS int W, int S
+#define FA_WIN_LOCATE(blk, nb) map_block(blockIdx.x, BH, nb, bh, blk);
+#define FA_WIN_LOCATE_KEYS(blk, nb)                                       \
+  if (S > 0) map_block_ranked(blockIdx.x, BH, nb, max(BH >> 3, 1), bh, blk); \
+  else map_block(blockIdx.x, BH, nb, bh, blk);
+#define FA_WIN_ROW0 (size_t)0
+#define FA_WIN_ROWCONST0 (size_t)bh * N
+#endif
+
 namespace fa {
 
 constexpr float WIN_DEFER_SUM = 64.0f;   // as fa_fwd.h's MAX_DEFER_SUM: bound on a lane's partial row sum while the reference stands
@@ -45,8 +65,8 @@ struct WinWalk {
 // ---------------------------------------------------------------------------------------------
 template <typename T, int D, int BN>
 __global__ void __launch_bounds__(256)
-win_fwd_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, float* __restrict__ o,
-               float* __restrict__ lse, int N, int nqb, int BH, Layout lay, float tau, int W, int S) {
+FA_WIN_KERNEL(fwd)(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, float* __restrict__ o,
+                   float* __restrict__ lse, FA_WIN_GEOM_PARAMS, Layout lay, float tau, FA_WIN_MASK_PARAMS) {
   using A = Atom<T>;
   typedef typename A::frag frag;
   constexpr int KC = D / 16, KT = BN / 32, DT = D / 32;
@@ -57,16 +77,16 @@ win_fwd_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __rest
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   int bh, qb;
-  map_block(blockIdx.x, BH, nqb, bh, qb);
+  FA_WIN_LOCATE(qb, nblk)
   const int q0 = qb * 128 + w * 32, qrow = q0 + r;
   const bool qvalid = qrow < N;
   const bool careful = A::SPLITS && (W + S < 64 || q0 < 64);   // wave-uniform: the wave's rows may admit fewer than 64 keys
-  const size_t base = head_base(lay, bh);
   const int ld = lay.ld;
+  const size_t base = head_base(lay, bh) + FA_WIN_ROW0 * ld;
   const uint32_t mat_bytes = ((uint32_t)(N - 1) * ld + D) * (uint32_t)sizeof(T);
   const rsrc_t qrs = make_rsrc(q + base, mat_bytes);
-  const size_t kvb = kv_base<D>(lay, bh, N);
   const int ldk = lay.ldk;
+  const size_t kvb = kv_base<D>(lay, bh, N) + FA_WIN_ROW0 * ldk;
   const uint32_t kv_bytes = ((uint32_t)(N - 1) * ldk + D) * (uint32_t)sizeof(T);
   const rsrc_t krs = make_rsrc(k + kvb, kv_bytes);
   const rsrc_t vrs = make_rsrc(v + kvb, kv_bytes);
@@ -225,7 +245,7 @@ win_fwd_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __rest
         f32x4 val = {acc_o[dt][4 * g] * inv, acc_o[dt][4 * g + 1] * inv, acc_o[dt][4 * g + 2] * inv, acc_o[dt][4 * g + 3] * inv};
         *reinterpret_cast<f32x4*>(orow + 32 * dt + 8 * g + 4 * h) = val;
       }
-    if (h == 0) lse[(size_t)bh * N + qrow] = m_ref * tau + __logf(l_tot);
+    if (h == 0) lse[FA_WIN_ROWCONST0 + qrow] = m_ref * tau + __logf(l_tot);
   }
 }
 
@@ -235,9 +255,9 @@ win_fwd_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __rest
 // ---------------------------------------------------------------------------------------------
 template <typename T, int D, int NWQ>
 __global__ void __launch_bounds__(64 * NWQ)
-win_dq_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, const T* __restrict__ dout,
-              const float* __restrict__ nlc, const float* __restrict__ ndelta, float* __restrict__ dq, int N, int nqb, int BH,
-              Layout lay, float tau, int W, int S) {
+FA_WIN_KERNEL(dq)(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, const T* __restrict__ dout,
+                  const float* __restrict__ nlc, const float* __restrict__ ndelta, float* __restrict__ dq, FA_WIN_GEOM_PARAMS,
+                  Layout lay, float tau, FA_WIN_MASK_PARAMS) {
   using A = Atom<T>;
   typedef typename A::frag frag;
   constexpr int BN = 32, KC = D / 16, DT = D / 32, QB = 32 * NWQ;
@@ -248,17 +268,17 @@ win_dq_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restr
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   int bh, qb;
-  map_block(blockIdx.x, BH, nqb, bh, qb);
+  FA_WIN_LOCATE(qb, nblk)
   const int q0 = qb * QB + w * 32, qrow = q0 + r;
   const bool qvalid = qrow < N;
   const bool careful = A::SPLITS && (W + S < 64 || q0 < 64);   // wave-uniform: see win_fwd_kernel
-  const size_t base = head_base(lay, bh);
   const int ld = lay.ld;
+  const size_t base = head_base(lay, bh) + FA_WIN_ROW0 * ld;
   const uint32_t mat_bytes = ((uint32_t)(N - 1) * ld + D) * (uint32_t)sizeof(T);
   const rsrc_t qrs = make_rsrc(q + base, mat_bytes);
   const rsrc_t dors = make_rsrc(dout + base, mat_bytes);
-  const size_t kvb = kv_base<D>(lay, bh, N);
   const int ldk = lay.ldk;
+  const size_t kvb = kv_base<D>(lay, bh, N) + FA_WIN_ROW0 * ldk;
   const uint32_t kv_bytes = ((uint32_t)(N - 1) * ldk + D) * (uint32_t)sizeof(T);
   const rsrc_t krs = make_rsrc(k + kvb, kv_bytes);
   const rsrc_t vrs = make_rsrc(v + kvb, kv_bytes);
@@ -272,8 +292,8 @@ win_dq_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restr
     dof[kc] = load_frag_buf<T>(dors, off);
   }
   // this lane's row constants; -delta, in every register, is the accumulator input of the dP^T tiles
-  const float nlq = qvalid ? nlc[(size_t)bh * N + qrow] * c : 0.f;   // -L * log2(e)
-  const float ndq = qvalid ? ndelta[(size_t)bh * N + qrow] : 0.f;
+  const float nlq = qvalid ? nlc[FA_WIN_ROWCONST0 + qrow] * c : 0.f;   // -L * log2(e)
+  const float ndq = qvalid ? ndelta[FA_WIN_ROWCONST0 + qrow] : 0.f;
   f32x16 nd16;
 #pragma unroll
   for (int i = 0; i < 16; ++i) nd16[i] = ndq;
@@ -381,9 +401,9 @@ win_dq_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restr
 // ---------------------------------------------------------------------------------------------
 template <typename T, int D, int NW, int QS>
 __global__ void __launch_bounds__(NW * 64)
-win_dkdv_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, const T* __restrict__ dout,
-                const float* __restrict__ nlc, const float* __restrict__ ndelta, float* __restrict__ dk, float* __restrict__ dv,
-                int N, int nkb, int BH, Layout lay, float tau, int W, int S) {
+FA_WIN_KERNEL(dkdv)(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, const T* __restrict__ dout,
+                    const float* __restrict__ nlc, const float* __restrict__ ndelta, float* __restrict__ dk, float* __restrict__ dv,
+                    FA_WIN_GEOM_PARAMS, Layout lay, float tau, FA_WIN_MASK_PARAMS) {
   using A = Atom<T>;
   typedef typename A::frag frag;
   constexpr int KC = D / 16, DT = D / 32, BK = NW * 32, NT = NW * 64, NSUB = QS / 32;
@@ -395,24 +415,23 @@ win_dkdv_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   int bh, kb;
-  // With sinks, key block 0 of every head sweeps all N queries where the others sweep about BK + W: those blocks are dispatched first,
+  // (FA_WIN_LOCATE_KEYS of the window library:) With sinks, key block 0 of every head sweeps all N queries where the others sweep about BK + W: those blocks are dispatched first,
   // across all heads of an XCD, so the long sweeps run beside the short ones instead of behind them (measured, profiles/
   // window_train_bench.txt: dispatched head by head they were a tail of 0.8 ms on 2.5 at N = 8192, W = 1024, S = 4).
-  if (S > 0) map_block_ranked(blockIdx.x, BH, nkb, max(BH >> 3, 1), bh, kb);
-  else map_block(blockIdx.x, BH, nkb, bh, kb);
+  FA_WIN_LOCATE_KEYS(kb, nblk)
   const int kb0 = kb * BK, kw0 = kb0 + w * 32, key = kw0 + r;
-  const size_t base = head_base(lay, bh);
   const int ld = lay.ld;
+  const size_t base = head_base(lay, bh) + FA_WIN_ROW0 * ld;
   const uint32_t mat_bytes = ((uint32_t)(N - 1) * ld + D) * (uint32_t)sizeof(T);
   const rsrc_t qrs = make_rsrc(q + base, mat_bytes);
   const rsrc_t dors = make_rsrc(dout + base, mat_bytes);
-  const size_t kvb = kv_base<D>(lay, bh, N);
   const int ldk = lay.ldk;
+  const size_t kvb = kv_base<D>(lay, bh, N) + FA_WIN_ROW0 * ldk;
   const uint32_t kv_bytes = ((uint32_t)(N - 1) * ldk + D) * (uint32_t)sizeof(T);
   const rsrc_t krs = make_rsrc(k + kvb, kv_bytes);
   const rsrc_t vrs = make_rsrc(v + kvb, kv_bytes);
-  const float* nlg = nlc + (size_t)bh * N;
-  const float* deg = ndelta + (size_t)bh * N;
+  const float* nlg = nlc + FA_WIN_ROWCONST0;
+  const float* deg = ndelta + FA_WIN_ROWCONST0;
   const float c = tau * LOG2E;
 
   frag kf[KC], vf[KC];

@@ -1367,3 +1367,205 @@ def flash_attn_ragged(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens=None, cau
     keep what they held."""
     return _kv_attention("ragged", q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, causal, softmax_scale, layout, out, lse, workspace, k_new,
                          v_new, block_table, max_pages, window, None, None, sink, rotary_cos, rotary_sin, rotary_interleaved, q_rot)
+
+
+# ---- packed variable-length batches in the training forward and backward (include/flash_attn_mi355x_varlen.h) ----------------------
+# q (T, H, d), k and v (T, Hkv, d), token-major as in the ragged calls above; sequence b owns the packed rows cu_seqlens[b] ..
+# cu_seqlens[b + 1] - 1 (clamped on the device; never read on the host).  Row i of a sequence sits at position i and admits key j of
+# the same sequence iff j <= i and (j > i - W or j < S).  Causal only.  The kernels are the window library's, run per (sequence,
+# block) off a device-side block map (libflash_attn_mi355x_varlen.so): per sequence the result is, bit for bit,
+# flash_attn_fwd_window / flash_attn_bwd_window on that sequence alone.  Rows no sequence owns come back as zeros.
+
+def _check_varlen(q, k, v, cu_seqlens, o=None, do=None):
+    """What _check_gqa checks, for packed 3-d tensors.  Returns (nseq, T, H, Hkv, d, dtype code) as the C entry points take them."""
+    _require_gpu(q, "device_ops")
+    dtype = _dtype_code(q)
+    if q.dim() != 3 or k.dim() != 3:
+        raise ValueError("expected packed 3-d tensors: q (T, H, d) and k, v (T, Hkv, d)")
+    dev = q.get_device()
+    if v.shape != k.shape:
+        raise ValueError("k and v must have one shape")
+    for t in (k, v):
+        if not t.is_cuda or t.dtype != q.dtype or t.get_device() != dev:
+            raise ValueError("q, k, v must be GPU tensors of one dtype on one device")
+    (T, H, d), (Tk, Hkv, dk) = q.shape, k.shape
+    if (T, d) != (Tk, dk):
+        raise ValueError(f"q and k disagree on (T, d): {(T, d)} vs {(Tk, dk)} (one cu_seqlens serves queries and keys)")
+    if T < 1:
+        raise ValueError("the packed batch is empty: T must be at least 1")
+    if Hkv <= 0 or H % Hkv:
+        raise ValueError(f"q's {H} heads must be a multiple of k's {Hkv}")
+    if d not in _NATIVE_D:
+        raise ValueError("the packed calls need a native head dim (32, 64, 128): flash_attn_varlen pads, or pad q, k and v "
+                         "(pad_head_dim) and pass softmax_scale")
+    _check_cu(cu_seqlens, None, q.device)
+    if do is not None and (do.shape != q.shape or do.dtype != q.dtype or do.get_device() != dev):
+        raise ValueError("out_grad must share q's shape, dtype and device")
+    for t in (q, k, v) + ((do,) if do is not None else ()):
+        if not t.is_contiguous():
+            raise ValueError("tensors must be contiguous")
+    if o is not None and (o.dtype is not _F32 or o.shape != q.shape or not o.is_contiguous() or o.get_device() != dev):
+        raise ValueError("out must be the forward's contiguous float32 output")
+    return cu_seqlens.shape[0] - 1, T, H, Hkv, d, dtype
+
+
+def _check_varlen_mask(window, sink):
+    """(W, S) as the packed entry points take them: 0 for None (no window: every j <= i); a sink needs a window."""
+    window = _check_window(window)
+    sink = _check_sink(sink, window)
+    if sink and not window:
+        raise ValueError("sink tokens stand beside a sliding window: sink= needs window >= 1")
+    return window or 0, sink or 0
+
+
+def _check_varlen_workspace(workspace, nbytes, dev):
+    if workspace.numel() * workspace.element_size() < nbytes:
+        raise ValueError("workspace too small: size it with varlen_workspace(q, k, cu_seqlens)")
+    if not workspace.is_contiguous() or workspace.get_device() != dev or workspace.data_ptr() % 256:
+        raise ValueError("workspace must be a contiguous, 256-byte aligned tensor on q's device")
+
+
+def varlen_workspace(q, k, cu_seqlens, backward=True):
+    """Scratch for flash_attn_varlen_bwd (``backward=False``: for flash_attn_varlen_fwd alone) with these tensors
+    (fa_mi355x_bwd_varlen_workspace_bytes / _fwd_): the block maps, the row constants and, when k has fewer heads than q, the dK and
+    dV of every query head.  Never empty: the maps live there.  A pure function of the SHAPES (cu_seqlens's contents are not read):
+    allocate once, reuse every step.  A backward workspace also serves the forward."""
+    nseq, T, H, Hkv, d, _ = _check_varlen(q, k, k, cu_seqlens)
+    lib = _lib.varlen()
+    nbytes = (lib.fa_mi355x_bwd_varlen_workspace_bytes if backward else lib.fa_mi355x_fwd_varlen_workspace_bytes)(nseq, T, H, Hkv, d)
+    return torch.empty((nbytes + 3) // 4, dtype=_F32, device=q.device)
+
+
+def flash_attn_varlen_fwd(q, k, v, cu_seqlens, window=None, sink=None, softmax_scale=None, out=None, workspace=None, lse=None):
+    """Causal forward over a packed batch (fa_mi355x_fwd_varlen): q (T, H, d), k and v (T, Hkv, d), ``cu_seqlens`` contiguous int32
+    (nseq + 1,) on q's device.  ``window`` = W, ``sink`` = S: the sliding-window mask within every sequence (None or 0: none).
+    Returns (out fp32 (T, H, d), lse (H, T)); rows no sequence owns are zero in both.  ``out``, ``lse``: buffers to write into;
+    ``workspace``: varlen_workspace(q, k, cu_seqlens) (with all three given the call allocates nothing: it can be captured in a graph)."""
+    window, sink = _check_varlen_mask(window, sink)
+    nseq, T, H, Hkv, d, dtype = _check_varlen(q, k, v, cu_seqlens)
+    lib, dev = _lib.varlen(), q.get_device()
+    if out is not None and (out.dtype is not _F32 or out.shape != q.shape or not out.is_contiguous() or out.get_device() != dev):
+        raise ValueError("out must be a contiguous float32 tensor of q's shape")
+    if workspace is not None:
+        _check_varlen_workspace(workspace, lib.fa_mi355x_fwd_varlen_workspace_bytes(nseq, T, H, Hkv, d), dev)
+    else:
+        workspace = varlen_workspace(q, k, cu_seqlens, backward=False)
+    if lse is not None:
+        _check_buffer(lse, dev, "lse", H * T)
+    else:
+        lse = torch.empty((H, T), dtype=_F32, device=q.device)
+    if out is None:
+        out = torch.empty(q.shape, dtype=_F32, device=q.device)
+    _lib.varlen_check(lib.fa_mi355x_fwd_varlen(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(cu_seqlens), _ptr(workspace), nseq, T,
+                                               H, Hkv, d, float(softmax_scale or 0.0), window, sink, dtype, _stream_ptr()))
+    return out, lse
+
+
+def flash_attn_varlen_bwd(q, k, v, out, out_grad, lse, cu_seqlens, window=None, sink=None, softmax_scale=None, workspace=None, grads=None):
+    """Backward of flash_attn_varlen_fwd (fa_mi355x_bwd_varlen).  Returns (dq in q's shape, dk, dv in k's shape), fp32, zero in the
+    rows no sequence owns; no atomics, the same bits on every run.  ``workspace``: varlen_workspace(q, k, cu_seqlens); ``grads``:
+    (dq, dk, dv) buffers to write into."""
+    window, sink = _check_varlen_mask(window, sink)
+    nseq, T, H, Hkv, d, dtype = _check_varlen(q, k, v, cu_seqlens, out, out_grad)
+    lib, dev = _lib.varlen(), q.get_device()
+    _check_buffer(lse, dev, "lse", H * T)
+    if workspace is not None:
+        _check_varlen_workspace(workspace, lib.fa_mi355x_bwd_varlen_workspace_bytes(nseq, T, H, Hkv, d), dev)
+    if grads is not None:
+        for g, like in zip(grads, (q, k, v)):
+            _check_buffer(g, dev, "each of grads", like.numel())
+    if workspace is None:
+        workspace = varlen_workspace(q, k, cu_seqlens)
+    dq, dk, dv = grads or (torch.empty(t.shape, dtype=_F32, device=q.device) for t in (q, k, v))
+    _lib.varlen_check(lib.fa_mi355x_bwd_varlen(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(out_grad), _ptr(dq), _ptr(dk), _ptr(dv),
+                                               _ptr(lse), _ptr(cu_seqlens), _ptr(workspace), nseq, T, H, Hkv, d,
+                                               float(softmax_scale or 0.0), window, sink, dtype, _stream_ptr()))
+    return dq, dk, dv
+
+
+class _FlashAttnVarlenFn(torch.autograd.Function):
+    """flash_attn_varlen under autograd: the forward saves q, the unexpanded k and v, o, lse and cu_seqlens; gradients are cast to
+    the input dtype."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, cu_seqlens, softmax_scale, window, sink):
+        o, lse = flash_attn_varlen_fwd(q, k, v, cu_seqlens, window, sink, softmax_scale)
+        ctx.save_for_backward(q, k, v, o, lse, cu_seqlens)
+        ctx.args = softmax_scale, window, sink
+        return o
+
+    @staticmethod
+    def backward(ctx, out_grad):
+        q, k, v, o, lse, cu_seqlens = ctx.saved_tensors
+        softmax_scale, window, sink = ctx.args
+        dq, dk, dv = flash_attn_varlen_bwd(q, k, v, o, out_grad.to(q.dtype).contiguous(), lse, cu_seqlens, window, sink, softmax_scale)
+        return dq.to(q.dtype), dk.to(q.dtype), dv.to(q.dtype), None, None, None, None
+
+
+def flash_attn_varlen(q, k, v, cu_seqlens, causal=True, softmax_scale=None, window=None, sink=None):
+    """Causal attention over a packed batch of sequences of different lengths, under autograd: q (T, H, d), k and v (T, Hkv, d),
+    ``cu_seqlens`` int32 (nseq + 1,) on q's device.  out fp32 (T, H, d); q.grad in q's shape and dtype, k.grad and v.grad in k's.
+    ``window``, ``sink``: as flash_attn_gqa, within every sequence.  A head dim other than 32, 64, 128 runs through zero-padded
+    columns with softmax_scale = 1 / sqrt(d).  Rows no sequence owns give zeros and take a zero gradient."""
+    if not causal:
+        raise ValueError("non-causal packed attention is not built: flash_attn_varlen is causal only (causal=False)")
+    window, sink = _check_varlen_mask(window, sink)
+    d = q.shape[-1] if isinstance(q, torch.Tensor) and q.dim() == 3 else 0
+    if d and d not in _NATIVE_D:
+        dp = padded_head_dim(d)
+        scale = softmax_scale if softmax_scale is not None else d ** -0.5
+        o = _FlashAttnVarlenFn.apply(pad_head_dim(q, dp), pad_head_dim(k, dp), pad_head_dim(v, dp), cu_seqlens, scale, window, sink)
+        return o[..., :d]
+    return _FlashAttnVarlenFn.apply(q, k, v, cu_seqlens, softmax_scale, window, sink)
+
+
+def _rotary_varlen_call(x, y, cos, sin, cu_seqlens, interleaved, inverse):
+    T, H, d = x.shape
+    rot, max_pos, il = _check_rotary(cos, sin, x.device, interleaved)
+    _lib.varlen_check(_lib.varlen().fa_mi355x_rope_varlen(
+        _ptr(x), _ptr(y), _ptr(cos), _ptr(sin), _ptr(cu_seqlens), cu_seqlens.shape[0] - 1, T, H, d, rot, max_pos, il, int(bool(inverse)),
+        _dtype_code(x), _stream_ptr()))
+    return y
+
+
+class _RotaryVarlenFn(torch.autograd.Function):
+    """apply_rotary_varlen under autograd: as _RotaryFn, the gradient is the inverse rotation of the cotangent."""
+
+    @staticmethod
+    def forward(ctx, x, cos, sin, cu_seqlens, interleaved, inverse, out):
+        ctx.save_for_backward(cos, sin, cu_seqlens)
+        ctx.how = (interleaved, inverse)
+        if out is None:
+            out = torch.empty_like(x)
+        else:
+            ctx.mark_dirty(out)
+        return _rotary_varlen_call(x, out, cos, sin, cu_seqlens, interleaved, inverse)
+
+    @staticmethod
+    def backward(ctx, g):
+        cos, sin, cu_seqlens = ctx.saved_tensors
+        interleaved, inverse = ctx.how
+        g = g.contiguous()
+        return _rotary_varlen_call(g, torch.empty_like(g), cos, sin, cu_seqlens, interleaved, not inverse), None, None, None, None, None, None
+
+
+def apply_rotary_varlen(x, cos, sin, cu_seqlens, interleaved=False, inverse=False, out=None):
+    """Rotary position embedding of a packed tensor (fa_mi355x_rope_varlen): x (T, H, d), float32 or bfloat16, contiguous; packed
+    row t of sequence b sits at position t - cu_seqlens[b], so positions restart at every sequence (clamped to the table on the
+    device); a row no sequence owns is copied.  Tables, pairs, arithmetic, ``inverse`` and ``out`` as apply_rotary: per sequence the
+    result is apply_rotary's on that sequence alone, bit for bit.  Differentiable in x by the inverse rotation."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 3:
+        raise ValueError("apply_rotary_varlen expects a packed 3-d x, (T, H, d)")
+    _dtype_code(x)
+    rot = _check_rotary(cos, sin, x.device)
+    if rot is None:
+        raise ValueError("apply_rotary_varlen needs both tables, cos and sin")
+    if rot[0] > x.shape[2]:
+        raise ValueError(f"the tables' rotary dimension {rot[0]} exceeds x's head dim {x.shape[2]}")
+    _check_cu(cu_seqlens, None, x.device)
+    if not x.is_contiguous():
+        raise ValueError("x must be contiguous")
+    if out is not None and (out.shape != x.shape or out.dtype != x.dtype or out.device != x.device or not out.is_contiguous()):
+        raise ValueError("out must be a contiguous tensor of x's shape, dtype and device")
+    _require_gpu(x, "apply_rotary_varlen")
+    return _RotaryVarlenFn.apply(x, cos, sin, cu_seqlens, bool(interleaved), bool(inverse), out)

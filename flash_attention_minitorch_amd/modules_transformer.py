@@ -118,6 +118,31 @@ def attention_stack(x, layers, n_head: int, causal: bool = True, fused_layout: b
     return x
 
 
+def multi_head_attention_packed(x, cu_seqlens, wq, wk, wv, wo, n_head: int, fold_scale: bool = False, rope=None, window=None,
+                                sink=None):
+    """multi_head_attention over a PACKED batch of sequences of different lengths: x (T, E), sequence b owns the rows
+    cu_seqlens[b] .. cu_seqlens[b + 1] - 1 (contiguous int32 (nseq + 1,) on x's device, handed to the kernels and never read on the
+    host), and every token attends causally within its own sequence (device_ops.flash_attn_varlen: no padding, no key mask).
+    Weights, grouped-query heads, ``fold_scale``, ``window`` and ``sink`` as multi_head_attention (the fused layout; causal only).
+    ``rope`` (a Rotary): positions restart at every sequence (device_ops.apply_rotary_varlen).  Rows no sequence owns give zero
+    attention output, hence zero rows of the result."""
+    T, E = x.shape
+    q, k, v = _project(x[None], wq * (LOG2E / (E // n_head) ** 0.5) if fold_scale else wq, wk, wv, n_head)
+    q, k, v = q[0], k[0], v[0]   # (T, heads, d)
+    if rope is not None:
+        q, k = (device_ops.apply_rotary_varlen(t, rope.cos, rope.sin, cu_seqlens, rope.interleaved) for t in (q, k))
+    o = device_ops.flash_attn_varlen(q, k, v, cu_seqlens, True, LN2 if fold_scale else None, window, sink)
+    return o.reshape(T, E).to(x.dtype) @ wo
+
+
+def attention_stack_packed(x, cu_seqlens, layers, n_head: int, fold_scale: bool = False, rope=None, window=None, sink=None):
+    """attention_stack over a packed batch: x <- x + multi_head_attention_packed_l(x) for every (wq, wk, wv, wo) in ``layers``.  Per
+    sequence it is attention_stack on that sequence alone; ``cu_seqlens`` goes to every layer's kernels as it is."""
+    for (wq, wk, wv, wo) in layers:
+        x = x + multi_head_attention_packed(x, cu_seqlens, wq, wk, wv, wo, n_head, fold_scale, rope, window, sink)
+    return x
+
+
 # ---- incremental generation: the inference half of the chain above ----------------------------------------------------------------
 # The reference's generate() (project/run_machine_translation.py:276-292) re-runs the whole model over the full prefix for every new
 # token and keeps the last row.  With a KV cache, the prompt runs once through the fused causal forward (attention_stack_prefill), and
