@@ -49,6 +49,15 @@ else
   echo "[compile_cuda.sh] $VARLEN is up to date"
 fi
 
+# Bidirectional packed attention with separate cu_seqlens for q and k (include/flash_attn_mi355x_bidir.h): a fifth library, for the same reason
+BIDIR="$OUT_DIR/libflash_attn_mi355x_bidir.so"
+if stale "$BIDIR"; then
+  echo "[compile_cuda.sh] hipcc --offload-arch=$ARCH  fa_bidir.hip -> $BIDIR"
+  "$HIPCC" "${FLAGS[@]}" "$SRC/fa_bidir.hip" -o "$BIDIR"
+else
+  echo "[compile_cuda.sh] $BIDIR is up to date"
+fi
+
 shim() {  # name variant FW|BW
   "$HIPCC" -O2 -fPIC -shared -x c++ "$SRC/fa_shim.cpp" -DFA_SHIM_VARIANT="$2" -DFA_SHIM_"$3" \
       -L"$OUT_DIR" -lflash_attn_mi355x -Wl,-rpath,'$ORIGIN' -o "$OUT_DIR/$1.so"

@@ -375,3 +375,25 @@ def varlen() -> ctypes.CDLL:
 def varlen_check(status: int) -> None:
     if status != FA_OK:
         _raise(status, varlen(), "fa_mi355x_varlen_last_error", "flash_attn_mi355x_varlen")
+
+
+# the same for include/flash_attn_mi355x_bidir.h: libflash_attn_mi355x_bidir.so, the bidirectional packed forward and backward with one
+# cu_seqlens for the queries and one for the keys (tests/test_bidir_cpu.py)
+BIDIR_ABI = {
+    "fa_mi355x_fwd_bidir_workspace_bytes": (_sz, [_i] * 6),
+    "fa_mi355x_bwd_bidir_workspace_bytes": (_sz, [_i] * 6),
+    "fa_mi355x_fwd_bidir": (_i, [_vp] * 8 + [_i] * 6 + [_f, _i, _vp]),
+    "fa_mi355x_bwd_bidir": (_i, [_vp] * 12 + [_i] * 6 + [_f, _i, _vp]),
+    "fa_mi355x_bidir_last_error": (_s, []),
+}
+BIDIR_NAME = "libflash_attn_mi355x_bidir.so"
+
+
+def bidir() -> ctypes.CDLL:
+    """libflash_attn_mi355x_bidir.so (include/flash_attn_mi355x_bidir.h) with argtypes set."""
+    return _typed(BIDIR_NAME, BIDIR_ABI)
+
+
+def bidir_check(status: int) -> None:
+    if status != FA_OK:
+        _raise(status, bidir(), "fa_mi355x_bidir_last_error", "flash_attn_mi355x_bidir")

@@ -1508,7 +1508,8 @@ def flash_attn_varlen(q, k, v, cu_seqlens, causal=True, softmax_scale=None, wind
     ``window``, ``sink``: as flash_attn_gqa, within every sequence.  A head dim other than 32, 64, 128 runs through zero-padded
     columns with softmax_scale = 1 / sqrt(d).  Rows no sequence owns give zeros and take a zero gradient."""
     if not causal:
-        raise ValueError("non-causal packed attention is not built: flash_attn_varlen is causal only (causal=False)")
+        raise ValueError("non-causal packed attention is not built: flash_attn_varlen is causal only (causal=False); "
+                         "flash_attn_varlen_bidir is the bidirectional packed call")
     window, sink = _check_varlen_mask(window, sink)
     d = q.shape[-1] if isinstance(q, torch.Tensor) and q.dim() == 3 else 0
     if d and d not in _NATIVE_D:
@@ -1569,3 +1570,176 @@ def apply_rotary_varlen(x, cos, sin, cu_seqlens, interleaved=False, inverse=Fals
         raise ValueError("out must be a contiguous tensor of x's shape, dtype and device")
     _require_gpu(x, "apply_rotary_varlen")
     return _RotaryVarlenFn.apply(x, cos, sin, cu_seqlens, bool(interleaved), bool(inverse), out)
+
+
+# ---- bidirectional packed attention with one cu_seqlens for q and one for k (include/flash_attn_mi355x_bidir.h) ---------------------
+# q (Tq, H, d), k and v (Tk, Hkv, d); sequence b owns the rows cu_seqlens_q[b] .. cu_seqlens_q[b + 1] - 1 of q and the rows
+# cu_seqlens_k[b] .. cu_seqlens_k[b + 1] - 1 of k and v (each clamped on the device against its own T; never read on the host), and
+# every query of a sequence admits every key of it: encoders on packed documents (one array for both) and cross-attention.  Kernels
+# of their own (libflash_attn_mi355x_bidir.so).  Query rows of a keyless sequence and rows no sequence owns come back as zeros.
+
+def _check_bidir(q, k, v, cu_seqlens_q, cu_seqlens_k, o=None, do=None):
+    """What _check_varlen checks, for two row counts.  Returns (nseq, Tq, Tk, H, Hkv, d, dtype code) as the C entry points take them."""
+    _require_gpu(q, "device_ops")
+    dtype = _dtype_code(q)
+    if q.dim() != 3 or k.dim() != 3:
+        raise ValueError("expected packed 3-d tensors: q (Tq, H, d) and k, v (Tk, Hkv, d)")
+    dev = q.get_device()
+    if v.shape != k.shape:
+        raise ValueError("k and v must have one shape")
+    for t in (k, v):
+        if not t.is_cuda or t.dtype != q.dtype or t.get_device() != dev:
+            raise ValueError("q, k, v must be GPU tensors of one dtype on one device")
+    (Tq, H, d), (Tk, Hkv, dk) = q.shape, k.shape
+    if d != dk:
+        raise ValueError(f"q and k disagree on the head dim: {d} vs {dk}")
+    if Tq < 1 or Tk < 1:
+        raise ValueError("the packed batch is empty: Tq and Tk must be at least 1")
+    if Hkv <= 0 or H % Hkv:
+        raise ValueError(f"q's {H} heads must be a multiple of k's {Hkv}")
+    if d not in _NATIVE_D:
+        raise ValueError("the packed calls need a native head dim (32, 64, 128): flash_attn_varlen_bidir pads, or pad q, k and v "
+                         "(pad_head_dim) and pass softmax_scale")
+    _check_cu(cu_seqlens_q, None, q.device)
+    if cu_seqlens_k is not cu_seqlens_q:
+        _check_cu(cu_seqlens_k, None, q.device)
+        if cu_seqlens_k.shape != cu_seqlens_q.shape:
+            raise ValueError("cu_seqlens_q and cu_seqlens_k must have one length: the same sequences, counted in q and in k")
+    if do is not None and (do.shape != q.shape or do.dtype != q.dtype or do.get_device() != dev):
+        raise ValueError("out_grad must share q's shape, dtype and device")
+    for t in (q, k, v) + ((do,) if do is not None else ()):
+        if not t.is_contiguous():
+            raise ValueError("tensors must be contiguous")
+    if o is not None and (o.dtype is not _F32 or o.shape != q.shape or not o.is_contiguous() or o.get_device() != dev):
+        raise ValueError("out must be the forward's contiguous float32 output")
+    return cu_seqlens_q.shape[0] - 1, Tq, Tk, H, Hkv, d, dtype
+
+
+def _check_bidir_workspace(workspace, nbytes, dev):
+    if workspace.numel() * workspace.element_size() < nbytes:
+        raise ValueError("workspace too small: size it with bidir_workspace(q, k, cu_seqlens_q, cu_seqlens_k)")
+    if not workspace.is_contiguous() or workspace.get_device() != dev or workspace.data_ptr() % 256:
+        raise ValueError("workspace must be a contiguous, 256-byte aligned tensor on q's device")
+
+
+def _self_cu(q, k, cu_seqlens_q, cu_seqlens_k):
+    """cu_seqlens_k=None: self-attention, one array for both buffers, and k has q's rows."""
+    if cu_seqlens_k is not None:
+        return cu_seqlens_k
+    if isinstance(q, torch.Tensor) and isinstance(k, torch.Tensor) and q.dim() == 3 and k.dim() == 3 and q.shape[0] != k.shape[0]:
+        raise ValueError(f"cu_seqlens_k=None means self-attention: k must have q's {q.shape[0]} rows, not {k.shape[0]}")
+    return cu_seqlens_q
+
+
+def bidir_workspace(q, k, cu_seqlens_q, cu_seqlens_k=None, backward=True):
+    """Scratch for flash_attn_varlen_bidir_bwd (``backward=False``: for flash_attn_varlen_bidir_fwd alone) with these tensors
+    (fa_mi355x_bwd_bidir_workspace_bytes / _fwd_): the two block maps, the row constants and, when k has fewer heads than q, the dK
+    and dV of every query head.  Never empty: the maps live there.  A pure function of the SHAPES (the arrays' contents are not
+    read): allocate once, reuse every step.  A backward workspace also serves the forward."""
+    cu_seqlens_k = _self_cu(q, k, cu_seqlens_q, cu_seqlens_k)
+    nseq, Tq, Tk, H, Hkv, d, _ = _check_bidir(q, k, k, cu_seqlens_q, cu_seqlens_k)
+    lib = _lib.bidir()
+    nbytes = (lib.fa_mi355x_bwd_bidir_workspace_bytes if backward else lib.fa_mi355x_fwd_bidir_workspace_bytes)(nseq, Tq, Tk, H, Hkv, d)
+    return torch.empty((nbytes + 3) // 4, dtype=_F32, device=q.device)
+
+
+def flash_attn_varlen_bidir_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k=None, softmax_scale=None, out=None, workspace=None, lse=None):
+    """Bidirectional forward over a packed batch (fa_mi355x_fwd_bidir): q (Tq, H, d), k and v (Tk, Hkv, d), the two arrays contiguous
+    int32 (nseq + 1,) on q's device (``cu_seqlens_k=None``: self-attention, the same array).  Returns (out fp32 (Tq, H, d), lse
+    (H, Tq)); query rows of a keyless sequence and rows no sequence owns are zero in both.  ``out``, ``lse``: buffers to write into;
+    ``workspace``: bidir_workspace(...) (with all three given the call allocates nothing: it can be captured in a graph)."""
+    cu_seqlens_k = _self_cu(q, k, cu_seqlens_q, cu_seqlens_k)
+    nseq, Tq, Tk, H, Hkv, d, dtype = _check_bidir(q, k, v, cu_seqlens_q, cu_seqlens_k)
+    lib, dev = _lib.bidir(), q.get_device()
+    if out is not None and (out.dtype is not _F32 or out.shape != q.shape or not out.is_contiguous() or out.get_device() != dev):
+        raise ValueError("out must be a contiguous float32 tensor of q's shape")
+    if workspace is not None:
+        _check_bidir_workspace(workspace, lib.fa_mi355x_fwd_bidir_workspace_bytes(nseq, Tq, Tk, H, Hkv, d), dev)
+    else:
+        workspace = bidir_workspace(q, k, cu_seqlens_q, cu_seqlens_k, backward=False)
+    if lse is not None:
+        _check_buffer(lse, dev, "lse", H * Tq)
+    else:
+        lse = torch.empty((H, Tq), dtype=_F32, device=q.device)
+    if out is None:
+        out = torch.empty(q.shape, dtype=_F32, device=q.device)
+    _lib.bidir_check(lib.fa_mi355x_fwd_bidir(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(cu_seqlens_q), _ptr(cu_seqlens_k),
+                                             _ptr(workspace), nseq, Tq, Tk, H, Hkv, d, float(softmax_scale or 0.0), dtype, _stream_ptr()))
+    return out, lse
+
+
+def flash_attn_varlen_bidir_bwd(q, k, v, out, out_grad, lse, cu_seqlens_q, cu_seqlens_k=None, softmax_scale=None, workspace=None,
+                                grads=None):
+    """Backward of flash_attn_varlen_bidir_fwd (fa_mi355x_bwd_bidir).  Returns (dq in q's shape, dk, dv in k's shape), fp32; zero in
+    the query rows of a keyless sequence, the key rows of a sequence without queries and the rows no sequence owns; no atomics, the
+    same bits on every run.  ``workspace``: bidir_workspace(...); ``grads``: (dq, dk, dv) buffers to write into."""
+    cu_seqlens_k = _self_cu(q, k, cu_seqlens_q, cu_seqlens_k)
+    nseq, Tq, Tk, H, Hkv, d, dtype = _check_bidir(q, k, v, cu_seqlens_q, cu_seqlens_k, out, out_grad)
+    lib, dev = _lib.bidir(), q.get_device()
+    _check_buffer(lse, dev, "lse", H * Tq)
+    if workspace is not None:
+        _check_bidir_workspace(workspace, lib.fa_mi355x_bwd_bidir_workspace_bytes(nseq, Tq, Tk, H, Hkv, d), dev)
+    if grads is not None:
+        for g, like in zip(grads, (q, k, v)):
+            _check_buffer(g, dev, "each of grads", like.numel())
+    if workspace is None:
+        workspace = bidir_workspace(q, k, cu_seqlens_q, cu_seqlens_k)
+    dq, dk, dv = grads or (torch.empty(t.shape, dtype=_F32, device=q.device) for t in (q, k, v))
+    _lib.bidir_check(lib.fa_mi355x_bwd_bidir(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(out_grad), _ptr(dq), _ptr(dk), _ptr(dv),
+                                             _ptr(lse), _ptr(cu_seqlens_q), _ptr(cu_seqlens_k), _ptr(workspace), nseq, Tq, Tk, H, Hkv, d,
+                                             float(softmax_scale or 0.0), dtype, _stream_ptr()))
+    return dq, dk, dv
+
+
+class _FlashAttnBidirFn(torch.autograd.Function):
+    """flash_attn_varlen_bidir under autograd: the forward saves q, the unexpanded k and v, o, lse and both cu arrays; gradients are
+    cast to the input dtypes."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, cu_seqlens_q, cu_seqlens_k, softmax_scale):
+        o, lse = flash_attn_varlen_bidir_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, softmax_scale)
+        ctx.save_for_backward(q, k, v, o, lse, cu_seqlens_q, cu_seqlens_k)
+        ctx.softmax_scale = softmax_scale
+        return o
+
+    @staticmethod
+    def backward(ctx, out_grad):
+        q, k, v, o, lse, cu_seqlens_q, cu_seqlens_k = ctx.saved_tensors
+        dq, dk, dv = flash_attn_varlen_bidir_bwd(q, k, v, o, out_grad.to(q.dtype).contiguous(), lse, cu_seqlens_q, cu_seqlens_k,
+                                                 ctx.softmax_scale)
+        return dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype), None, None, None
+
+
+def flash_attn_varlen_bidir(q, k, v, cu_seqlens_q, cu_seqlens_k=None, softmax_scale=None):
+    """Bidirectional attention over a packed batch, under autograd: q (Tq, H, d), k and v (Tk, Hkv, d); sequence b's queries
+    (``cu_seqlens_q``) admit every key of sequence b (``cu_seqlens_k``; None: self-attention, the same array, and k has Tq rows).
+    out fp32 (Tq, H, d); q.grad in q's shape and dtype, k.grad and v.grad in k's.  A head dim other than 32, 64, 128 runs through
+    zero-padded columns with softmax_scale = 1 / sqrt(d).  Query rows of a keyless sequence and rows no sequence owns give zeros and
+    take a zero gradient."""
+    cu_seqlens_k = _self_cu(q, k, cu_seqlens_q, cu_seqlens_k)
+    d = q.shape[-1] if isinstance(q, torch.Tensor) and q.dim() == 3 else 0
+    if d and d not in _NATIVE_D:
+        dp = padded_head_dim(d)
+        scale = softmax_scale if softmax_scale is not None else d ** -0.5
+        o = _FlashAttnBidirFn.apply(pad_head_dim(q, dp), pad_head_dim(k, dp), pad_head_dim(v, dp), cu_seqlens_q, cu_seqlens_k, scale)
+        return o[..., :d]
+    return _FlashAttnBidirFn.apply(q, k, v, cu_seqlens_q, cu_seqlens_k, softmax_scale)
+
+
+def flash_attn_cross(q, k, v, softmax_scale=None):
+    """Batched cross-attention under autograd: q (B, Nq, H, d), k and v (B, Nk, Hkv, d), contiguous; every query of batch element b
+    admits every key of it, Nq and Nk independent.  The tensors are viewed as packed ((B * Nq, H, d), (B * Nk, Hkv, d)) and the two
+    cu_seqlens are built on the device: flash_attn_varlen_bidir does the rest.  out fp32 (B, Nq, H, d)."""
+    if not isinstance(q, torch.Tensor) or not isinstance(k, torch.Tensor) or not isinstance(v, torch.Tensor) or q.dim() != 4 or k.dim() != 4:
+        raise ValueError("flash_attn_cross expects 4-d tensors: q (B, Nq, H, d) and k, v (B, Nk, Hkv, d)")
+    if v.shape != k.shape:
+        raise ValueError("k and v must have one shape")
+    (B, Nq, H, d), (Bk, Nk, Hkv, _) = q.shape, k.shape
+    if B != Bk:
+        raise ValueError(f"q and k disagree on the batch: {B} vs {Bk}")
+    if not (q.is_contiguous() and k.is_contiguous() and v.is_contiguous()):
+        raise ValueError("tensors must be contiguous")
+    steps = torch.arange(B + 1, dtype=torch.int32, device=q.device)
+    cu_q, cu_k = steps * Nq, steps * Nk
+    o = flash_attn_varlen_bidir(q.view(B * Nq, H, d), k.view(B * Nk, Hkv, d), v.view(B * Nk, Hkv, d), cu_q, cu_k, softmax_scale)
+    return o.view(B, Nq, H, o.shape[-1])

@@ -143,6 +143,42 @@ def attention_stack_packed(x, cu_seqlens, layers, n_head: int, fold_scale: bool 
     return x
 
 
+def multi_head_attention_packed_bidir(x, cu_seqlens, wq, wk, wv, wo, n_head: int, rope=None):
+    """Encoder self-attention over a packed batch: multi_head_attention_packed's data flow and weights, but every token attends to
+    EVERY token of its own sequence (device_ops.flash_attn_varlen_bidir with one array for queries and keys: no padding, no key
+    mask).  ``rope`` (a Rotary): positions restart at every sequence.  Rows no sequence owns give zero rows of the result."""
+    T, E = x.shape
+    q, k, v = _project(x[None], wq, wk, wv, n_head)
+    q, k, v = q[0], k[0], v[0]   # (T, heads, d)
+    if rope is not None:
+        q, k = (device_ops.apply_rotary_varlen(t, rope.cos, rope.sin, cu_seqlens, rope.interleaved) for t in (q, k))
+    o = device_ops.flash_attn_varlen_bidir(q, k, v, cu_seqlens)
+    return o.reshape(T, E).to(x.dtype) @ wo
+
+
+def encoder_stack_packed(x, cu_seqlens, layers, n_head: int, rope=None):
+    """The encoder layer stack over a packed batch: x <- x + multi_head_attention_packed_bidir_l(x) for every (wq, wk, wv, wo) in
+    ``layers``.  Per sequence it is attention_stack(causal=False) on that sequence alone."""
+    for (wq, wk, wv, wo) in layers:
+        x = x + multi_head_attention_packed_bidir(x, cu_seqlens, wq, wk, wv, wo, n_head, rope)
+    return x
+
+
+def cross_attention_packed(x, cu_seqlens_q, memory, cu_seqlens_k, wq, wk, wv, wo, n_head: int):
+    """Cross-attention over packed batches: the queries come from x (Tq, E) through wq (E, E), the keys and values from memory
+    (Tk, E_mem) through wk, wv (E_mem, E), or (E_mem, Hkv * d) for grouped-query heads (d = E // n_head), read grouped.  The tokens
+    of sequence b (``cu_seqlens_q``) attend all of sequence b's memory rows (``cu_seqlens_k``); a sequence without memory gives zero
+    attention output.  Returns (Tq, E)."""
+    Tq, E = x.shape
+    d = E // n_head
+    if wk.shape != wv.shape or wk.shape[1] % d or n_head % max(wk.shape[1] // d, 1):
+        raise ValueError(f"wk and wv must both be (E_mem, Hkv * {d}) with Hkv a divisor of n_head = {n_head}")
+    q = (x @ wq).view(Tq, n_head, d)
+    k, v = ((memory @ w).view(memory.shape[0], w.shape[1] // d, d) for w in (wk, wv))
+    o = device_ops.flash_attn_varlen_bidir(q, k, v, cu_seqlens_q, cu_seqlens_k)
+    return o.reshape(Tq, E).to(x.dtype) @ wo
+
+
 # ---- incremental generation: the inference half of the chain above ----------------------------------------------------------------
 # The reference's generate() (project/run_machine_translation.py:276-292) re-runs the whole model over the full prefix for every new
 # token and keeps the last row.  With a KV cache, the prompt runs once through the fused causal forward (attention_stack_prefill), and
