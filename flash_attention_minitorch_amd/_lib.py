@@ -188,6 +188,14 @@ ROPE_ABI = {
     "fa_mi355x_rope_append_ragged": (_i, [_vp] * 11 + [_i] * 15 + [_vp]),
 }
 
+# the same for include/flash_attn_mi355x_decode_softcap.h (logit soft-capping: the _window forms with `float softcap` behind the
+# window; tests/test_softcap_cpu.py)
+SOFTCAP_ABI = {
+    "fa_mi355x_fwd_decode_softcap": (_i, [_vp] * 10 + [_i] * 11 + [_f, _i, _i, _f, _i, _vp]),
+    "fa_mi355x_fwd_extend_softcap": (_i, [_vp] * 10 + [_i] * 11 + [_f, _i, _i, _f, _i, _vp]),
+    "fa_mi355x_fwd_ragged_softcap": (_i, [_vp] * 11 + [_i] * 11 + [_f, _i, _i, _f, _i, _vp]),
+}
+
 # The positional order of every KV-cache symbol that device_ops calls, by the parameter names of the prototypes (k_pool / v_pool of
 # the _paged ones read k_cache / v_cache, T of the ragged ones Nq: one field each).  device_ops fills one dict of fields per public
 # call and every C call takes its arguments from it in this order; tests/test_kv_ops_cpu.py holds the table against the headers' text
@@ -250,6 +258,19 @@ KV_PARAMS = {
     "fa_mi355x_ragged_sink_workspace_bytes": "B H Hkv Nq Ncap d window sink",
 }
 KV_PARAMS = {sym: tuple(names.split()) for sym, names in KV_PARAMS.items()}   # (split once, here)
+# The soft-capping symbols, likewise (tests/test_softcap_cpu.py holds them against their header and SOFTCAP_ABI).  A table of their
+# own: `softcap` is the one float beside softmax_scale, and KV_PARAMS above is held by tests/test_kv_ops_cpu.py to "every argument
+# that is no pointer and not softmax_scale is an int".  device_ops reads the two tables as one, KV_CALL_PARAMS.
+KV_SOFTCAP_PARAMS = {
+    "fa_mi355x_fwd_decode_softcap": f"{_PROLOGUE} out lse cache_seqlens block_table workspace {_EITHER} d_new d "
+                                    "layout softmax_scale causal window softcap dtype stream",
+    "fa_mi355x_fwd_extend_softcap": f"{_PROLOGUE} out lse cache_seqlens block_table workspace {_EITHER} d_new d "
+                                    "layout softmax_scale causal window softcap dtype stream",
+    "fa_mi355x_fwd_ragged_softcap": f"{_PROLOGUE} out lse cu_seqlens_q cache_seqlens block_table workspace {_EITHER} d_new d "
+                                    "layout softmax_scale causal window softcap dtype stream",
+}
+KV_SOFTCAP_PARAMS = {sym: tuple(names.split()) for sym, names in KV_SOFTCAP_PARAMS.items()}
+KV_CALL_PARAMS = {**KV_PARAMS, **KV_SOFTCAP_PARAMS}
 KV_POINTERS = frozenset("q q_rot k_new v_new k_cache v_cache k_scale v_scale cos sin out lse cu_seqlens_q cache_seqlens block_table "
                         "workspace stream".split())
 
@@ -327,12 +348,12 @@ def check(status: int) -> None:
 
 
 DECODE_NAME = "libflash_attn_mi355x_decode.so"
-_DECODE_LIB_ABI = {**DECODE_ABI, **PAGED_ABI, **RAGGED_ABI, **WINDOW_ABI, **FP8_ABI, **SINK_ABI, **ROPE_ABI}
+_DECODE_LIB_ABI = {**DECODE_ABI, **PAGED_ABI, **RAGGED_ABI, **WINDOW_ABI, **FP8_ABI, **SINK_ABI, **ROPE_ABI, **SOFTCAP_ABI}
 
 
 def decode() -> ctypes.CDLL:
     """libflash_attn_mi355x_decode.so (include/flash_attn_mi355x_decode.h, its _paged.h, its _ragged.h, its _window.h, its _fp8.h, its
-    _sink.h and its _rope.h) with argtypes set.  (Every KV-cache call comes through here: the tables are merged once, above.)"""
+    _sink.h, its _rope.h and its _softcap.h) with argtypes set.  (Every KV-cache call comes through here: the tables are merged once, above.)"""
     return _typed(DECODE_NAME, _DECODE_LIB_ABI)
 
 

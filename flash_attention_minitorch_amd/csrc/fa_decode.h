@@ -72,6 +72,14 @@
 // lse, the combine kernel's weights), v_scale[hkv] multiplies the final 1 / l (the one-split store and the combine kernel); the
 // partials in the workspace stay unscaled.  bf16 queries only, no window, no ragged form.  The FP8 = false builds are the code
 // they were (DESIGN.md "FP8 cache").
+//
+// Logit soft-capping (decode_split_softcap_kernel, extend_split_softcap_kernel; include/flash_attn_mi355x_decode_softcap.h): every
+// score becomes z = softcap * tanh(tau * s / softcap) right after the QK products and BEFORE the -inf masks (cap_score below; a mask
+// applied first would come out of the cap as -softcap, an admitted key).  From there on the scores are the logits: the softmax runs
+// with tau = 1, m_run and the partial m are in capped-logit units, lse = m + ln l, and the host hands the EXISTING combine kernels
+// tau = 1.  Key ranges, staging, page walk, window edges and the P.V products are the body's as they are.  No sinks and no fp8
+// cache beside a cap.  The softcap kernels share their body with the other builds as text, as the sink kernels do, so the other
+// builds are the code they were (DESIGN.md "Softcap").
 #pragma once
 #include "fa_common.h"
 
@@ -122,10 +130,28 @@ struct RaggedSinkArgs : RaggedArgs {
   int sink;
 };
 template <bool RAGGED> using SinkArgsOf = typename std::conditional<RAGGED, RaggedSinkArgs, SinkArgs>::type;
+// The arguments of the SOFTCAP builds, likewise: the cap, positive and finite (the host checks it).
+struct SoftcapArgs : DecodeArgs {
+  float softcap;
+};
+struct RaggedSoftcapArgs : RaggedArgs {
+  float softcap;
+};
+template <bool RAGGED> using SoftcapArgsOf = typename std::conditional<RAGGED, RaggedSoftcapArgs, SoftcapArgs>::type;
 template <bool RAGGED, bool FP8 = false>
 using DecodeArgsOf = typename std::conditional<FP8, Fp8Args, typename std::conditional<RAGGED, RaggedArgs, DecodeArgs>::type>::type;
 // (positive and finite is the caller's contract: the kernels do not check a scale)
 FA_DEV float scale_of(const float* scale, int hkv) { return scale ? scale[hkv] : 1.0f; }
+
+// Soft-capping: z = softcap * tanh(tau * s / softcap) for a raw score s, as softcap - 2 softcap / (t + 1) with t = e^(2 tau s /
+// softcap) = exp2(s * k2), k2 = 2 log2(e) tau / softcap (once per workgroup).  One v_exp_f32 and one v_rcp_f32 per score (gfx950
+// has no tanh).  It saturates without a special case: t = inf gives rcp = 0 and z = +softcap, t = 0 gives z = -softcap, and no
+// finite s gives a NaN (the (t - 1) / (t + 1) form gives inf / inf).  The absolute error is a few ulp of softcap, whatever s.
+FA_DEV float cap_score(float s, float k2, float softcap) {
+  const float t = __builtin_amdgcn_exp2f(s * k2);
+  return __builtin_fmaf(-2.0f * softcap, __builtin_amdgcn_rcpf(t + 1.0f), softcap);
+}
+FA_DEV float cap_k2(float tau, float softcap) { return 2.0f * LOG2E * tau / softcap; }
 
 FA_DEV int clamp_len(const int* seqlens, int Ncap, int b) {
   const int len = seqlens ? seqlens[b] : Ncap;
@@ -289,6 +315,7 @@ FA_DEV void sink_load(PageWalk& pw, const DecodeArgs& a, int b, S& sk, S& sv, si
 template <typename T, int D, bool GROUPED, bool PAGED = false, bool WINDOW = false, bool FP8 = false>
 __global__ void __launch_bounds__(256) decode_split_kernel(DecodeArgsOf<false, FP8> a) {
   constexpr bool SINK = false;
+  constexpr bool SOFTCAP = false;
 #include "fa_decode_split_body.h"
 }
 
@@ -297,6 +324,15 @@ __global__ void __launch_bounds__(256) decode_split_kernel(DecodeArgsOf<false, F
 template <typename T, int D, bool PAGED>
 __global__ void __launch_bounds__(256) decode_split_sink_kernel(SinkArgsOf<PAGED && false> a) {
   constexpr bool GROUPED = true, WINDOW = true, FP8 = false, SINK = true;
+  constexpr bool SOFTCAP = false;
+#include "fa_decode_split_body.h"
+}
+
+// The SOFTCAP builds (a.softcap: the cap): grouped, slab or paged, windowed or not.  (The argument's type depends on a template
+// parameter for the reason above.)
+template <typename T, int D, bool PAGED, bool WINDOW>
+__global__ void __launch_bounds__(256) decode_split_softcap_kernel(SoftcapArgsOf<PAGED && false> a) {
+  constexpr bool GROUPED = true, FP8 = false, SINK = false, SOFTCAP = true;
 #include "fa_decode_split_body.h"
 }
 
@@ -321,6 +357,7 @@ constexpr int EXT_BLOCK = 128;   // rows per workgroup: 32 per wave
 template <typename T, int D, bool PAGED = false, bool RAGGED = false, bool WINDOW = false, bool FP8 = false>
 __global__ void __launch_bounds__(256) extend_split_kernel(DecodeArgsOf<RAGGED, FP8> a) {
   constexpr bool SINK = false;
+  constexpr bool SOFTCAP = false;
 #include "fa_decode_extend_body.h"
 }
 
@@ -328,6 +365,14 @@ __global__ void __launch_bounds__(256) extend_split_kernel(DecodeArgsOf<RAGGED, 
 template <typename T, int D, bool PAGED, bool RAGGED>
 __global__ void __launch_bounds__(256) extend_split_sink_kernel(SinkArgsOf<RAGGED> a) {
   constexpr bool WINDOW = true, FP8 = false, SINK = true;
+  constexpr bool SOFTCAP = false;
+#include "fa_decode_extend_body.h"
+}
+
+// The SOFTCAP builds: slab or paged, uniform or ragged, windowed or not.
+template <typename T, int D, bool PAGED, bool RAGGED, bool WINDOW>
+__global__ void __launch_bounds__(256) extend_split_softcap_kernel(SoftcapArgsOf<RAGGED> a) {
+  constexpr bool FP8 = false, SINK = false, SOFTCAP = true;
 #include "fa_decode_extend_body.h"
 }
 

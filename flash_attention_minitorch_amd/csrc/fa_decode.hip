@@ -1,5 +1,5 @@
 // C ABI of the MI355X KV-cache decode library (declared in include/flash_attn_mi355x_decode.h and its _paged.h, _ragged.h,
-// _window.h, _sink.h, _fp8.h and _rope.h).  Every entry point fills one KvCall (the call as it was received) and hands it to run():
+// _window.h, _sink.h, _fp8.h, _softcap.h and _rope.h).  Every entry point fills one KvCall (the call as it was received) and hands it to run():
 // the entry point's prelude (check_fp8 or check_window), the page geometry (check_pages), the attention's checks (check_attend, which
 // also returns the call's Policy), the append's (check_append), then the append launch (run_append) and the attention's launches
 // (run_attend -> launch_split).  policy() is the one split policy: the three families (decode: 32-row blocks, at most 128 queries;
@@ -7,7 +7,8 @@
 // A paged call (a pool and a block table) takes the contiguous call's policy at Ncap = max_pages * page_size.  A windowed call takes
 // the policy on its window span (span_keys) instead of Ncap, a sink call on that span plus its sink tiles.  An fp8 call (caches of
 // e4m3 bytes, per-kv-head scales) takes the bf16 call's policy and workspace for the same arguments; its cache bounds count one byte
-// per element.  The rotary calls launch the kernels of fa_rope.h in front of the attend-only entry points.
+// per element.  A soft-capped call (softcap > 0) takes the policy and workspace of the same call without the cap, the softcap builds
+// of the split kernels and the existing combine kernels with tau = 1.  The rotary calls launch the kernels of fa_rope.h in front of the attend-only entry points.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -93,6 +94,7 @@ struct KvCall {
   int B = 0, H = 0, Hkv = 0, Nq = 0, Ncap = 0, d_new = 0, d = 0;
   int layout = 0, causal = 0, window = 0, sink = 0, dtype = 0;
   float softmax_scale = 0.f;
+  float softcap = 0.f;   // logit soft-capping (_softcap.h); 0: none
   hipStream_t stream = nullptr;
 
   explicit KvCall(Family f) : family(f) {}
@@ -217,9 +219,12 @@ int check_fp8(int dtype) {
   return FA_OK;
 }
 
-// The checks a windowed call makes first (sink: 0 in the calls that have none; a call without a window passes).
-int check_window(int window, int causal, int sink) {
+// The checks a windowed call makes first (sink and softcap: 0 in the calls that have none; a call without a window passes).  A cap
+// does not need the causal mask; a window still does.
+int check_window(int window, int causal, int sink, float softcap) {
   g_err[0] = 0;
+  if (!(softcap >= 0.f) || !std::isfinite(softcap))
+    return set_err(FA_ERR_BAD_ARG, "softcap must be finite and not negative (0: no soft-capping)");
   if (sink < 0) return set_err(FA_ERR_BAD_ARG, "sink must not be negative (0: no sink tokens)");
   if (window < 0) return set_err(FA_ERR_BAD_ARG, "window must not be negative (0: no window)");
   if (window > 0 && !causal)
@@ -355,8 +360,16 @@ void set_append(fa::AppendArgs& a, const KvCall& c) {
 // the scales or the sink count behind it (Fp8Args, SinkArgs, RaggedSinkArgs), which the leg that launches such a build makes.
 struct SplitArgs : fa::RaggedArgs {
   Fp8 f8;
-  int sink;   // S >= 1: a sink reaches the device
+  int sink;        // S >= 1: a sink reaches the device
+  float softcap;   // > 0: the softcap builds (SoftcapArgs, RaggedSoftcapArgs), and tau = 1 for the combine kernel
 };
+
+template <typename S, typename Base> S with_softcap(const SplitArgs& a) {
+  S s;
+  static_cast<Base&>(s) = a;
+  s.softcap = a.softcap;
+  return s;
+}
 
 template <typename S, typename Base> S with_sink(const SplitArgs& a) {
   S s;
@@ -386,6 +399,8 @@ template <typename A, typename B> void launch256(void (*kernel)(A), long grid, h
 //   extend, ragged  PAGED x WINDOW as the call has them; ragged is the RAGGED flag of the extend kernels
 //   sink    kernels and an argument of their own, only when a sink reaches the device (a.sink >= 1, which implies a.window >= 1)
 //   fp8     bf16 queries, slab or paged, no window (the Python layer refuses the combination by name)
+//   softcap kernels and an argument of their own, only when a cap reaches the device (a.softcap > 0): PAGED x WINDOW as the call has
+//           them, the grouped build in the decode family; the combine launch is the existing instance with tau = 1
 template <typename T, int D> int launch_split(const SplitArgs& a, Family f, hipStream_t st) {
   constexpr bool BF16 = std::is_same<T, fa::bf16_t>::value;
   const bool paged = a.table != nullptr, window = a.window != 0;
@@ -404,6 +419,26 @@ template <typename T, int D> int launch_split(const SplitArgs& a, Family f, hipS
       else if (f == EXTEND) launch256(fa::extend_split_kernel<T, D, false, false, false, true>, grid, st, fa8);
       else if (paged) launch256(fa::decode_split_kernel<T, D, true, true, false, true>, grid, st, fa8);
       else launch256(fa::decode_split_kernel<T, D, true, false, false, true>, grid, st, fa8);
+    }
+  } else if (a.softcap > 0.f) {   // (no sinks and no fp8 cache beside a cap: the softcap entry points have neither argument)
+    if (f == RAGGED) {
+      what = "extend_split_softcap_kernel (ragged) launch";
+      const fa::RaggedSoftcapArgs ca = with_softcap<fa::RaggedSoftcapArgs, fa::RaggedArgs>(a);
+      if (window && paged) launch256(fa::extend_split_softcap_kernel<T, D, true, true, true>, grid, st, ca);
+      else if (window) launch256(fa::extend_split_softcap_kernel<T, D, false, true, true>, grid, st, ca);
+      else if (paged) launch256(fa::extend_split_softcap_kernel<T, D, true, true, false>, grid, st, ca);
+      else launch256(fa::extend_split_softcap_kernel<T, D, false, true, false>, grid, st, ca);
+    } else {
+      what = f == EXTEND ? "extend_split_softcap_kernel launch" : "decode_split_softcap_kernel launch";
+      const fa::SoftcapArgs ca = with_softcap<fa::SoftcapArgs, fa::DecodeArgs>(a);
+      if (f == EXTEND && window && paged) launch256(fa::extend_split_softcap_kernel<T, D, true, false, true>, grid, st, ca);
+      else if (f == EXTEND && window) launch256(fa::extend_split_softcap_kernel<T, D, false, false, true>, grid, st, ca);
+      else if (f == EXTEND && paged) launch256(fa::extend_split_softcap_kernel<T, D, true, false, false>, grid, st, ca);
+      else if (f == EXTEND) launch256(fa::extend_split_softcap_kernel<T, D, false, false, false>, grid, st, ca);
+      else if (window && paged) launch256(fa::decode_split_softcap_kernel<T, D, true, true>, grid, st, ca);
+      else if (window) launch256(fa::decode_split_softcap_kernel<T, D, false, true>, grid, st, ca);
+      else if (paged) launch256(fa::decode_split_softcap_kernel<T, D, true, false>, grid, st, ca);
+      else launch256(fa::decode_split_softcap_kernel<T, D, false, false>, grid, st, ca);
     }
   } else if (f == DECODE) {
     if (a.sink) {
@@ -438,9 +473,14 @@ template <typename T, int D> int launch_split(const SplitArgs& a, Family f, hipS
   if (e != hipSuccess) return hip_err(what, e);
   if (a.nsplit > 1) {
     const long rows = (f == RAGGED ? 1L : a.nseq) * a.H * a.Nq;   // one workgroup per output row
+    // (softcap: the partials' m are capped logits already, so the EXISTING combine instances run with tau = 1; the softmax scale
+    // left there would weigh the splits wrongly)
+    SplitArgs one = a;
+    one.tau = 1.0f;
+    const SplitArgs& ca = a.softcap > 0.f ? one : a;
     if (a.f8.on) launch256(fa::decode_combine_kernel<D, false, true>, rows, st, with_scales(a));
-    else if (f == RAGGED) launch256(fa::decode_combine_kernel<D, true>, rows, st, a);
-    else launch256(fa::decode_combine_kernel<D>, rows, st, a);
+    else if (f == RAGGED) launch256(fa::decode_combine_kernel<D, true>, rows, st, ca);
+    else launch256(fa::decode_combine_kernel<D>, rows, st, ca);
     e = hipGetLastError();
     if (e != hipSuccess) return hip_err(a.f8.on ? "decode_combine_kernel (fp8) launch" : FAMILIES[f].combine_launch, e);
   }
@@ -491,6 +531,7 @@ int run_attend(const KvCall& c, const Policy& p) {
   a.causal = c.causal ? 1 : 0;
   a.tau = c.softmax_scale > 0.f ? c.softmax_scale : sqrtf(1.0f / (float)c.d);
   a.f8 = c.f8;
+  a.softcap = c.softcap;
   return c.dtype == FA_DTYPE_BF16 ? launch_split_d<fa::bf16_t>(a, c.family, c.d, c.stream) : launch_split_d<float>(a, c.family, c.d, c.stream);
 }
 
@@ -540,7 +581,7 @@ int run_append(const KvCall& c) {
 
 // The one path of every attention and append entry point: every check, in the order in which errors win, then the launches.
 int run(KvCall c) {
-  int rc = c.f8.on ? check_fp8(c.dtype) : check_window(c.window, c.causal, c.sink);
+  int rc = c.f8.on ? check_fp8(c.dtype) : check_window(c.window, c.causal, c.sink, c.softcap);
   if (rc == FA_OK && c.paged) rc = check_pages(c.pg, &c.Ncap);
   Policy p{};
   if (rc == FA_OK && c.attend) rc = check_attend(c, &p);
@@ -988,6 +1029,44 @@ int fa_mi355x_fwd_ragged_sink(const void* q, const void* k_new, const void* v_ne
   if (k_new || v_new) c.new_tokens(k_new, v_new, d_new);
   c.cu = cu_seqlens_q;
   c.window = window, c.sink = sink;
+  return run(c);
+}
+
+// ---- logit soft-capping (_softcap.h): the windowed forms with the cap behind the window; softcap = 0 is the _window call ----
+int fa_mi355x_fwd_decode_softcap(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
+                                 const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv, int Nq, int Ncap,
+                                 int num_pages, int page_size, int max_pages, int d_new, int d, int layout, float softmax_scale, int causal,
+                                 int window, float softcap, int dtype, void* stream) {
+  KvCall c(DECODE);
+  c.attention(q, out, lse, workspace, softmax_scale, causal).cache(k_cache, v_cache, cache_seqlens, Ncap);
+  c.pool_or_slabs(block_table, num_pages, page_size, max_pages).heads(B, H, Hkv, Nq, d).format(layout, dtype, stream);
+  if (k_new || v_new) c.new_tokens(k_new, v_new, d_new);
+  c.window = window, c.softcap = softcap;
+  return run(c);
+}
+
+int fa_mi355x_fwd_extend_softcap(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
+                                 const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv, int Nq, int Ncap,
+                                 int num_pages, int page_size, int max_pages, int d_new, int d, int layout, float softmax_scale, int causal,
+                                 int window, float softcap, int dtype, void* stream) {
+  KvCall c(EXTEND);
+  c.attention(q, out, lse, workspace, softmax_scale, causal).cache(k_cache, v_cache, cache_seqlens, Ncap);
+  c.pool_or_slabs(block_table, num_pages, page_size, max_pages).heads(B, H, Hkv, Nq, d).format(layout, dtype, stream);
+  if (k_new || v_new) c.new_tokens(k_new, v_new, d_new);
+  c.window = window, c.softcap = softcap;
+  return run(c);
+}
+
+int fa_mi355x_fwd_ragged_softcap(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
+                                 const int* cu_seqlens_q, const int* cache_seqlens, const int* block_table, void* workspace, int B, int H,
+                                 int Hkv, int T, int Ncap, int num_pages, int page_size, int max_pages, int d_new, int d, int layout,
+                                 float softmax_scale, int causal, int window, float softcap, int dtype, void* stream) {
+  KvCall c(RAGGED);
+  c.attention(q, out, lse, workspace, softmax_scale, causal).cache(k_cache, v_cache, cache_seqlens, Ncap);
+  c.pool_or_slabs(block_table, num_pages, page_size, max_pages).heads(B, H, Hkv, T, d).format(layout, dtype, stream);
+  if (k_new || v_new) c.new_tokens(k_new, v_new, d_new);
+  c.cu = cu_seqlens_q;
+  c.window = window, c.softcap = softcap;
   return run(c);
 }
 

@@ -1,9 +1,10 @@
-// The body of extend_split_kernel and extend_split_sink_kernel (fa_decode.h), included INSIDE each of the two: plain text, not a
+// The body of extend_split_kernel, extend_split_sink_kernel and extend_split_softcap_kernel (fa_decode.h), included INSIDE each: plain text, not a
 // function.  A function template that both kernels call is inlined only after it has been simplified on its own, and every existing
 // build of the kernel then comes out with other code than it had (compared per kernel: profiles/sink_isa_identity.txt); as text the
-// existing kernel is the function it was.  In scope: T, D, PAGED, RAGGED, WINDOW, FP8, SINK and the kernel's argument a.
+// existing kernel is the function it was.  In scope: T, D, PAGED, RAGGED, WINDOW, FP8, SINK, SOFTCAP and the kernel's argument a.
   static_assert(!FP8 || (std::is_same<T, bf16_t>::value && !RAGGED && !WINDOW), "fp8 caches: bf16 queries, no ragged form, no window");
   static_assert(!SINK || (WINDOW && !FP8), "sinks: beside a window, no fp8 cache");
+  static_assert(!SOFTCAP || (!FP8 && !SINK), "soft-capping: no fp8 cache, no sinks");
   using A = Atom<T>;
   typedef typename std::conditional<FP8, uint8_t, T>::type C;
   typedef typename A::frag frag;
@@ -53,7 +54,10 @@
   const bool wave_live = q0 < rows;   // (wave-uniform)
   float tau8 = 0.f;
   if constexpr (FP8) tau8 = a.tau * scale_of(a.k_scale, hkv);
-#define FA_TAU (FP8 ? tau8 : a.tau)
+  // (softcap builds: the capped scores ARE the logits, so the softmax's tau is 1; k2 is cap_score's exp2 constant)
+  float k2 = 0.f;
+  if constexpr (SOFTCAP) k2 = cap_k2(a.tau, a.softcap);
+#define FA_TAU (SOFTCAP ? 1.0f : FP8 ? tau8 : a.tau)
   const float c = FA_TAU * LOG2E;
   // causal: the last key any row of the block sees is the position of its last row (of its last REAL row: rows >= G * Nq see nothing)
   // (sink builds: blk_hi >= lo or the block has no sink tiles, so cend is never inside (vs, lo] either)
@@ -141,6 +145,10 @@
         f32x16 s = zero16();
 #pragma unroll
         for (int kc = 0; kc < KC; ++kc) A::mma(s, A::template row_frag<D>(tk, ra, 32 * st, kc), qf[kc]);
+        if constexpr (SOFTCAP) {   // the cap, in front of the masks: a masked score must stay -inf, not become -softcap
+#pragma unroll
+          for (int i = 0; i < 16; ++i) s[i] = cap_score(s[i], k2, a.softcap);
+        }
         // (window: only the sub-tiles that hold a key at or below the wave's highest edge - 1 mask for it; sink builds: and a key >= S)
         if (kbase + 32 > c1 || (a.causal && kbase + 31 > pos_lo) ||
             (WINDOW && kbase <= pos_hi - a.window && (!SINK || kbase + 31 >= S))) {   // wave-uniform

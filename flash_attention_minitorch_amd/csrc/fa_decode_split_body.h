@@ -1,9 +1,10 @@
-// The body of decode_split_kernel and decode_split_sink_kernel (fa_decode.h), included INSIDE each of the two: plain text, not a
+// The body of decode_split_kernel, decode_split_sink_kernel and decode_split_softcap_kernel (fa_decode.h), included INSIDE each: plain text, not a
 // function.  A function template that both kernels call is inlined only after it has been simplified on its own, and every existing
 // build of the kernel then comes out with other code than it had (compared per kernel: profiles/sink_isa_identity.txt); as text the
-// existing kernel is the function it was.  In scope: T, D, GROUPED, PAGED, WINDOW, FP8, SINK and the kernel's argument a.
+// existing kernel is the function it was.  In scope: T, D, GROUPED, PAGED, WINDOW, FP8, SINK, SOFTCAP and the kernel's argument a.
   static_assert(!FP8 || (std::is_same<T, bf16_t>::value && GROUPED && !WINDOW), "fp8 caches: bf16 queries, the grouped form, no window");
   static_assert(!SINK || (WINDOW && GROUPED && !FP8), "sinks: beside a window, the grouped form, no fp8 cache");
+  static_assert(!SOFTCAP || (GROUPED && !FP8 && !SINK), "soft-capping: the grouped form, no fp8 cache, no sinks");
   using A = Atom<T>;
   typedef typename std::conditional<FP8, uint8_t, T>::type C;
   typedef typename A::frag frag;
@@ -44,7 +45,10 @@
   // (a macro, as FA_NQ below: the other builds read a.tau where they always did)
   float tau8 = 0.f;
   if constexpr (FP8) tau8 = a.tau * scale_of(a.k_scale, hkv);
-#define FA_TAU (FP8 ? tau8 : a.tau)
+  // (softcap builds: the capped scores ARE the logits, so the softmax's tau is 1; k2 is cap_score's exp2 constant)
+  float k2 = 0.f;
+  if constexpr (SOFTCAP) k2 = cap_k2(a.tau, a.softcap);
+#define FA_TAU (SOFTCAP ? 1.0f : FP8 ? tau8 : a.tau)
   const float c = FA_TAU * LOG2E;
 
   f32x16 acc_o[DT];
@@ -126,6 +130,10 @@
       f32x16 s = zero16();
 #pragma unroll
       for (int kc = 0; kc < KC; ++kc) A::mma(s, A::template row_frag<D>(tk, ra, 32 * w, kc), qf[kc]);
+      if constexpr (SOFTCAP) {   // the cap, in front of the masks: a masked score must stay -inf, not become -softcap
+#pragma unroll
+        for (int i = 0; i < 16; ++i) s[i] = cap_score(s[i], k2, a.softcap);
+      }
       // (window: only the sub-tiles that hold a key at or below the highest row's edge - 1 mask for it; sink builds: and a key >= S)
       if (kbase + 32 > c1 || (a.causal && kbase + 31 > pos_lo) ||
           (WINDOW && kbase <= pos_hi - a.window && (!SINK || kbase + 31 >= S))) {   // wave-uniform

@@ -14,6 +14,8 @@ supply, and exactly one C call.
 from __future__ import annotations
 
 import ctypes
+import math
+import numbers
 import operator
 
 import torch
@@ -605,7 +607,8 @@ _KV_FAMILIES = {
         symbols=dict(
             ungrouped="fa_mi355x_fwd_decode", attend="fa_mi355x_fwd_decode_gqa", fused="fa_mi355x_fwd_decode_append",
             paged="fa_mi355x_fwd_decode_paged", fused_paged="fa_mi355x_fwd_decode_append_paged", window="fa_mi355x_fwd_decode_window",
-            sink="fa_mi355x_fwd_decode_sink", fp8="fa_mi355x_fwd_decode_fp8", append="fa_mi355x_decode_append",
+            sink="fa_mi355x_fwd_decode_sink", softcap="fa_mi355x_fwd_decode_softcap", fp8="fa_mi355x_fwd_decode_fp8",
+            append="fa_mi355x_decode_append",
             append_paged="fa_mi355x_decode_append_paged", append_fp8="fa_mi355x_append_fp8", rope="fa_mi355x_rope_append",
             size_ungrouped="fa_mi355x_decode_workspace_bytes", size="fa_mi355x_decode_workspace_bytes_gqa",
             size_window="fa_mi355x_decode_window_workspace_bytes", size_sink="fa_mi355x_decode_sink_workspace_bytes")),
@@ -616,7 +619,8 @@ _KV_FAMILIES = {
         symbols=dict(
             attend="fa_mi355x_fwd_extend", fused="fa_mi355x_fwd_extend_append", paged="fa_mi355x_fwd_extend_paged",
             fused_paged="fa_mi355x_fwd_extend_append_paged", window="fa_mi355x_fwd_extend_window", sink="fa_mi355x_fwd_extend_sink",
-            fp8="fa_mi355x_fwd_extend_fp8", append="fa_mi355x_extend_append", append_paged="fa_mi355x_extend_append_paged",
+            softcap="fa_mi355x_fwd_extend_softcap", fp8="fa_mi355x_fwd_extend_fp8", append="fa_mi355x_extend_append",
+            append_paged="fa_mi355x_extend_append_paged",
             append_fp8="fa_mi355x_append_fp8", rope="fa_mi355x_rope_append", size="fa_mi355x_extend_workspace_bytes",
             size_window="fa_mi355x_extend_window_workspace_bytes", size_sink="fa_mi355x_extend_sink_workspace_bytes")),
     "ragged": dict(
@@ -626,17 +630,20 @@ _KV_FAMILIES = {
         symbols=dict(
             attend="fa_mi355x_fwd_ragged", fused="fa_mi355x_fwd_ragged_append", paged="fa_mi355x_fwd_ragged_paged",
             fused_paged="fa_mi355x_fwd_ragged_append_paged", window="fa_mi355x_fwd_ragged_window", sink="fa_mi355x_fwd_ragged_sink",
-            append="fa_mi355x_ragged_append", append_paged="fa_mi355x_ragged_append_paged", rope="fa_mi355x_rope_append_ragged",
+            softcap="fa_mi355x_fwd_ragged_softcap", append="fa_mi355x_ragged_append", append_paged="fa_mi355x_ragged_append_paged",
+            rope="fa_mi355x_rope_append_ragged",
             size="fa_mi355x_ragged_workspace_bytes", size_window="fa_mi355x_ragged_window_workspace_bytes",
             size_sink="fa_mi355x_ragged_sink_workspace_bytes")),
 }
 
 
-def _kv_symbol(fam, op, paged=False, fused=False, window=None, sink=None, fp8=False, ungrouped=False):
+def _kv_symbol(fam, op, paged=False, fused=False, window=None, sink=None, fp8=False, ungrouped=False, softcap=None):
     """The C symbol of a call.  ``op`` "append": the append (fa_mi355x_append_fp8 takes slab and paged caches alike); "size": the size
     query; "attend": the attention -- one entry point per family on an fp8 cache, with sink tokens and with a window (null k_new /
     v_new attend only, a null table is a slab cache), otherwise the _paged and the fused _append forms.  ``window`` None takes the
-    unwindowed symbols; ``ungrouped`` (Hkv = H) the ones without an Hkv, where the family has them."""
+    unwindowed symbols; ``ungrouped`` (Hkv = H) the ones without an Hkv, where the family has them.  ``softcap`` (not None: a cap
+    above 0, never beside sink tokens or an fp8 cache) takes the family's one soft-capping entry point, windowed or not; the size
+    queries do not depend on it."""
     symbols = fam["symbols"]
     if op == "append":
         return symbols["append_fp8" if fp8 else "append_paged" if paged else "append"]
@@ -646,6 +653,8 @@ def _kv_symbol(fam, op, paged=False, fused=False, window=None, sink=None, fp8=Fa
         if window is not None:
             return symbols["size_window"]
         return symbols["size_ungrouped"] if ungrouped and "size_ungrouped" in symbols else symbols["size"]
+    if softcap is not None:
+        return symbols["softcap"]
     if fp8:
         return symbols["fp8"]
     if sink is not None:
@@ -659,7 +668,7 @@ def _kv_symbol(fam, op, paged=False, fused=False, window=None, sink=None, fp8=Fa
     return symbols["ungrouped"] if ungrouped and "ungrouped" in symbols else symbols["attend"]
 
 
-_KV_ARGS = {symbol: operator.itemgetter(*names) for symbol, names in _lib.KV_PARAMS.items()}   # fields -> the symbol's argument tuple
+_KV_ARGS = {symbol: operator.itemgetter(*names) for symbol, names in _lib.KV_CALL_PARAMS.items()}   # fields -> the symbol's argument tuple
 
 
 def _kv_call(symbol, fields):
@@ -757,6 +766,15 @@ def _check_sink(sink, window):
     if sink and window is None:
         raise ValueError("sink tokens stand beside a sliding window: sink= needs window=")
     return sink or None
+
+
+def _check_softcap(softcap):
+    """``softcap`` as the library takes it: None and 0 are None (today's entry points), otherwise a finite number above 0."""
+    if softcap is None:
+        return None
+    if isinstance(softcap, (bool, str)) or not isinstance(softcap, numbers.Real) or not math.isfinite(softcap) or softcap < 0:
+        raise ValueError("softcap must be None or a finite number >= 0: the logit cap, softcap * tanh(score / softcap) (None or 0: none)")
+    return float(softcap) or None
 
 
 # ---- sliding window and attention sinks in the training forward and backward: fa_mi355x_fwd_window / _bwd_window ------------------
@@ -1136,16 +1154,20 @@ def extend_append(k_new, v_new, k_cache, v_cache, cache_seqlens=None, layout="bn
 
 
 def _kv_attention(family, q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, causal, softmax_scale, layout, out, lse, workspace, k_new, v_new,
-                  block_table, max_pages, window, k_scale, v_scale, sink, rotary_cos, rotary_sin, rotary_interleaved, q_rot):
+                  block_table, max_pages, window, k_scale, v_scale, sink, rotary_cos, rotary_sin, rotary_interleaved, q_rot, softcap=None):
     """flash_attn_decode / flash_attn_extend / flash_attn_ragged: the checks in one order (the options; the caches and their dtypes; the
     geometry; q, the lengths, the table, the new tokens; devices and strides; out, lse, the workspace's size; the GPU; the tables' rotary
     dimension and q_rot), the head-dim padding, the buffers the caller did not supply, then the entry point _kv_symbol picks.  With
     rotary tables: the roped append (q -> q_rot, the rotated k_new and v_new into the caches), then the ATTEND-ONLY form of the same
-    choice on q_rot."""
+    choice on q_rot.  ``softcap``: the family's soft-capping entry point (a window rides along, 0 without one); refused beside sink
+    tokens and on an fp8 cache before any library call."""
     fam = _KV_FAMILIES[family]
     packed = fam["packed"]
     window = _check_window(window, causal)
     sink = _check_sink(sink, window)
+    softcap = _check_softcap(softcap)
+    if softcap is not None and sink is not None:
+        raise ValueError("softcap beside sink tokens is not built: softcap= with sink=")
     rotary = _rotary_of(rotary_cos, rotary_sin, rotary_interleaved, q.device)
     if rotary is None and q_rot is not None:
         raise ValueError("q_rot is where a roped call leaves the rotated q: it needs rotary_cos and rotary_sin")
@@ -1166,6 +1188,8 @@ def _kv_attention(family, q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, caus
             raise TypeError("an fp8 cache takes bfloat16 queries")
         if window is not None:   # (sink tokens need a window, so this refuses them on an fp8 cache as well)
             raise ValueError("a sliding window on an fp8 cache is not built: window= with torch.float8_e4m3fn caches")
+        if softcap is not None:
+            raise ValueError("softcap on an fp8 cache is not built: softcap= with torch.float8_e4m3fn caches")
     elif k_cache.dtype != q.dtype:
         raise TypeError("q, k_cache and v_cache must share one dtype")
     mp = None if block_table is None else _max_pages(block_table, None)
@@ -1225,22 +1249,23 @@ def _kv_attention(family, q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, caus
         "block_table": None if block_table is None else block_table.data_ptr(),
         "workspace": None if workspace is None else workspace.data_ptr(), "B": B, "H": H, "Hkv": Hkv, "Nq": Nq,
         "Ncap": 0 if pool else Ncap, "num_pages": num_pages, "page_size": page_size, "max_pages": table_pages, "d_new": d_new, "d": dp,
-        "layout": _DECODE_LAYOUTS[layout], "softmax_scale": float(softmax_scale), "causal": int(bool(causal)), "window": window,
-        "sink": sink, "dtype": dtype, "stream": _stream_ptr()}
+        "layout": _DECODE_LAYOUTS[layout], "softmax_scale": float(softmax_scale), "causal": int(bool(causal)),
+        "window": 0 if window is None and softcap is not None else window,   # (the softcap entry points take a window: 0 is none)
+        "sink": sink, "softcap": softcap, "dtype": dtype, "stream": _stream_ptr()}
     if rotary:   # (the roped append, then the attend-only form of whatever follows, on the rotated q)
         _rope_append(fam, fields, rotary, fp8)
         if q_rot is not None and qr is not q_rot:
             q_rot.copy_(qr[..., :d])
         fields.update(q=_ptr(qr), k_new=None, v_new=None, d_new=dp)
         k_new = None
-    symbol = _kv_symbol(fam, "attend", pool is not None, k_new is not None, window, sink, fp8, Hkv == H)
+    symbol = _kv_symbol(fam, "attend", pool is not None, k_new is not None, window, sink, fp8, Hkv == H, softcap)
     _lib.decode_check(_kv_call(symbol, fields))
     return (_unpad(outp, d, out) if d < dp else outp), lse
 
 
 def flash_attn_decode(q, k_cache, v_cache, cache_seqlens=None, causal=True, softmax_scale=None, layout="bnhd", out=None, lse=None,
                       workspace=None, k_new=None, v_new=None, block_table=None, window=None, k_scale=None, v_scale=None, sink=None,
-                      rotary_cos=None, rotary_sin=None, rotary_interleaved=False, q_rot=None):
+                      rotary_cos=None, rotary_sin=None, rotary_interleaved=False, q_rot=None, softcap=None):
     """Attention of Nq <= 128 new queries against a KV cache (fa_mi355x_fwd_decode / _gqa, include/flash_attn_mi355x_decode.h).
     ``layout`` "bnhd": q (B, Nq, H, d), caches (B, Ncap, Hkv, dp); "bhnd": q (B, H, Nq, d), caches (B, Hkv, Ncap, dp).  Hkv is the
     cache's own head count and must divide H: Hkv < H is a grouped-query (Hkv = 1: multi-query) cache, query head h reads cache head
@@ -1281,14 +1306,20 @@ def flash_attn_decode(q, k_cache, v_cache, cache_seqlens=None, causal=True, soft
     clamp(len_b, 0, Ncap) - Nq + i; ``rotary_interleaved`` picks GPT-J pairs (x[2j], x[2j+1]) instead of NeoX ones
     (x[j], x[j + rot/2]).  Bit for bit the call without the tables on apply_rotary(q) and apply_rotary(k_new) at those positions.
     Works with every cache feature above (paged, window, sink, fp8).  Without k_new / v_new only q is rotated.
+    ``softcap`` (None, or a finite number >= 0): LOGIT SOFT-CAPPING (fa_mi355x_fwd_decode_softcap,
+    include/flash_attn_mi355x_decode_softcap.h; Gemma-2's attn_logit_softcapping, Grok-1).  Every score becomes
+    softcap * tanh(softmax_scale * q.k / softcap) before the masks and the softmax; lse is taken over the capped logits.  None and 0
+    take the paths above exactly.  Works with a paged cache, a window (the one entry point takes both), the fused append, rotary
+    tables and causal=False; beside ``sink`` and on an fp8 cache it is a ValueError (not built).  The workspace does not depend on
+    the cap: decode_workspace(..., window=) sizes it.
     Returns (out fp32 in q's shape, lse fp32 (B, H, Nq)): rows with no admissible key give out = 0, lse = -inf."""
     return _kv_attention("decode", q, k_cache, v_cache, None, cache_seqlens, causal, softmax_scale, layout, out, lse, workspace, k_new, v_new,
-                         block_table, None, window, k_scale, v_scale, sink, rotary_cos, rotary_sin, rotary_interleaved, q_rot)
+                         block_table, None, window, k_scale, v_scale, sink, rotary_cos, rotary_sin, rotary_interleaved, q_rot, softcap)
 
 
 def flash_attn_extend(q, k_cache, v_cache, cache_seqlens=None, causal=True, softmax_scale=None, layout="bnhd", out=None, lse=None,
                       workspace=None, k_new=None, v_new=None, block_table=None, window=None, k_scale=None, v_scale=None, sink=None,
-                      rotary_cos=None, rotary_sin=None, rotary_interleaved=False, q_rot=None):
+                      rotary_cos=None, rotary_sin=None, rotary_interleaved=False, q_rot=None, softcap=None):
     """flash_attn_decode for ANY number Nq >= 1 of new queries (fa_mi355x_fwd_extend / fa_mi355x_fwd_extend_append): a long input that
     follows a cached prefix, or one piece of a chunked prefill (the same call, from an empty cache on).  Every argument, check, the
     head-dim padding (the default scale keeps the caller's 1/sqrt(d)) and the return value are flash_attn_decode's; ``workspace`` is
@@ -1301,9 +1332,9 @@ def flash_attn_extend(q, k_cache, v_cache, cache_seqlens=None, causal=True, soft
     ``v_scale``: an fp8 cache, as in flash_attn_decode (fa_mi355x_fwd_extend_fp8).  ``sink``: attention-sink tokens beside the
     window, as in flash_attn_decode (fa_mi355x_fwd_extend_sink; extend_workspace(..., window=, sink=)).  ``rotary_cos`` /
     ``rotary_sin`` / ``rotary_interleaved`` / ``q_rot``: rotary embeddings, as in flash_attn_decode (fa_mi355x_rope_append, then the
-    attend-only extend call on q_rot)."""
+    attend-only extend call on q_rot).  ``softcap``: logit soft-capping, as in flash_attn_decode (fa_mi355x_fwd_extend_softcap)."""
     return _kv_attention("extend", q, k_cache, v_cache, None, cache_seqlens, causal, softmax_scale, layout, out, lse, workspace, k_new, v_new,
-                         block_table, None, window, k_scale, v_scale, sink, rotary_cos, rotary_sin, rotary_interleaved, q_rot)
+                         block_table, None, window, k_scale, v_scale, sink, rotary_cos, rotary_sin, rotary_interleaved, q_rot, softcap)
 
 
 # ---- ragged batches: every sequence brings its own number of new tokens (include/flash_attn_mi355x_decode_ragged.h) ----
@@ -1342,7 +1373,7 @@ def ragged_append(k_new, v_new, k_cache, v_cache, cu_seqlens_q, cache_seqlens=No
 
 def flash_attn_ragged(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens=None, causal=True, softmax_scale=None, layout="bnhd", out=None,
                       lse=None, workspace=None, k_new=None, v_new=None, block_table=None, max_pages=None, window=None, sink=None,
-                      rotary_cos=None, rotary_sin=None, rotary_interleaved=False, q_rot=None):
+                      rotary_cos=None, rotary_sin=None, rotary_interleaved=False, q_rot=None, softcap=None):
     """One attention call over a RAGGED batch (fa_mi355x_fwd_ragged / _fwd_ragged_append and their _paged forms): every sequence
     brings its own number of new tokens -- some decode one, one is part-way through a chunked prefill, some have none.  ``q`` is
     PACKED, (T, H, d): sequence b owns rows cu_seqlens_q[b] .. cu_seqlens_q[b + 1] - 1 (``cu_seqlens_q`` contiguous int32 (B + 1,) on
@@ -1363,10 +1394,11 @@ def flash_attn_ragged(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens=None, cau
     ``rotary_cos`` / ``rotary_sin`` / ``rotary_interleaved`` / ``q_rot``: rotary embeddings, as in flash_attn_decode
     (fa_mi355x_rope_append_ragged, then the attend-only ragged call on q_rot; token i of sequence b sits at
     clamp(len_b, 0, Ncap) - nq_b + i; the rows of q_rot that no sequence owns keep what they held).
+    ``softcap``: logit soft-capping, as in flash_attn_decode (fa_mi355x_fwd_ragged_softcap).
     Returns (out fp32 (T, H, d), lse fp32 (H, T)): rows with no admissible key give out = 0, lse = -inf; rows of the unused tail
     keep what they held."""
     return _kv_attention("ragged", q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, causal, softmax_scale, layout, out, lse, workspace, k_new,
-                         v_new, block_table, max_pages, window, None, None, sink, rotary_cos, rotary_sin, rotary_interleaved, q_rot)
+                         v_new, block_table, max_pages, window, None, None, sink, rotary_cos, rotary_sin, rotary_interleaved, q_rot, softcap)
 
 
 # ---- packed variable-length batches in the training forward and backward (include/flash_attn_mi355x_varlen.h) ----------------------

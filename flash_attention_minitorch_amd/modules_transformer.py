@@ -17,6 +17,8 @@ LayerNorm, the feed-forward block and the embedding of ``DecoderLM`` (:255-351) 
 from __future__ import annotations
 
 import collections
+import math
+import numbers
 
 import torch
 
@@ -194,6 +196,8 @@ def cross_attention_packed(x, cu_seqlens_q, memory, cu_seqlens_k, wq, wk, wv, wo
 # quantise on the append, and a prompt fills the cache through extend_append while its own attention stays the square forward on the
 # unquantised k, v.  rope=Rotary(...): one fa_mi355x_rope_append launch per layer rotates q and the new k on their way in, then the
 # attend-only call runs; the square prefill and the unfused step rotate q and k with apply_rotary.  The cache holds ROTATED keys.
+# softcap=C: every call soft-caps its logits, C * tanh(score / C) (Gemma-2, Grok-1), through the family's softcap entry point; the
+# prompt takes the extend route, as on a windowed cache (the square forward has no cap).
 
 MAX_STEP_TOKENS = 128   # fa_mi355x_fwd_decode's largest Nq; longer inputs are prefill, or attention_stack_extend after a prefix
 
@@ -247,6 +251,19 @@ def _check_cache_quant(kv_dtype, kv_scale, dtype, window, n_layers, n_kv_head, d
     return kv_dtype, kv_scale
 
 
+def _check_cache_softcap(softcap, sink, fp8):
+    """``softcap`` of a cache: None, or a finite number above 0; not beside sink tokens, not on an fp8 cache (neither is built)."""
+    if softcap is None:
+        return None
+    if isinstance(softcap, (bool, str)) or not isinstance(softcap, numbers.Real) or not math.isfinite(softcap) or softcap <= 0:
+        raise ValueError("softcap must be None or a finite number above 0: the logit cap, softcap * tanh(score / softcap)")
+    if sink is not None:
+        raise ValueError("softcap beside sink tokens is not built: softcap= with sink=")
+    if fp8:
+        raise ValueError("softcap on an fp8 cache is not built: softcap= with kv_dtype=torch.float8_e4m3fn")
+    return float(softcap)
+
+
 class KVCache:
     """Per-layer k and v caches of a causal attention stack: ``k[l]``, ``v[l]`` are (B, capacity, n_kv_head, dp) in the projection's
     own [B][N][H][d] layout (no permute), dp = head_dim rounded up to 32, 64 or 128 with zero columns past head_dim.  ``n_kv_head``
@@ -265,14 +282,19 @@ class KVCache:
     and sink tokens are not built for it.
     ``rope`` (None, or a Rotary whose tables cover the capacity): the stack encodes positions with ROTARY embeddings; the stack
     functions rotate every q and every new k by its position (the row it is appended to), and the cache holds rotated keys.
+    ``softcap`` (None, or a finite number above 0): the stack's layers SOFT-CAP their attention logits, every score becomes
+    softcap * tanh(score / softcap) before the softmax (Gemma-2's ``attn_logit_softcapping``, Grok-1); the stack functions pass it
+    to every device_ops call on this cache, and a prompt goes through the extend kernels (the square forward has no cap).  Works
+    with a window, a paged cache and rotary embeddings; not built beside sink tokens or on an fp8 cache, and a cache has ONE window
+    (Gemma-2's alternating local and global layers are not covered).  The training forward and backward have no cap.
     The constructor, which is PagedKVCache's too, checks in this order and reports the first fault: ``window``, ``sink``,
     ``n_kv_head``, what the memory layout adds (_pool: nothing here; ``page_size``, ``capacity``, ``n_pages`` of a PagedKVCache),
-    ``rope``, then ``kv_dtype`` / ``kv_scale``."""
+    ``rope``, then ``kv_dtype`` / ``kv_scale``, then ``softcap``."""
 
     block_table = None   # (a PagedKVCache has one)
 
     def __init__(self, n_layers, B, capacity, n_head, head_dim, dtype, device, n_kv_head=None, window=None, kv_dtype=None, kv_scale=None,
-                 sink=None, rope=None):
+                 sink=None, rope=None, softcap=None):
         self.window = _check_cache_window(window)
         self.sink = _check_cache_sink(sink, self.window)
         self.head_dim, self.dp = head_dim, device_ops.padded_head_dim(head_dim)
@@ -283,6 +305,7 @@ class KVCache:
         shape, rows = self._pool(B)
         self.rope = _check_cache_rope(rope, rows, head_dim)
         dtype, self.kv_scale = _check_cache_quant(kv_dtype, kv_scale, dtype, self.window, n_layers, self.n_kv_head, device)
+        self.softcap = _check_cache_softcap(softcap, self.sink, dtype == device_ops._FP8)
         self.k = [torch.zeros(shape, dtype=dtype, device=device) for _ in range(n_layers)]
         self.v = [torch.zeros(shape, dtype=dtype, device=device) for _ in range(n_layers)]
         self.lengths = torch.zeros(B, dtype=torch.int32, device=device)
@@ -294,10 +317,14 @@ class KVCache:
         return (B, self.capacity, self.n_kv_head, self.dp), self.capacity
 
     def keywords(self, li, rotary=True, **new):
-        """Every keyword an attend call on layer ``li`` of this cache takes beside its tensors: paging, windowing, quant and rotary,
-        and the caller's own (``new``: k_new=, v_new=).  A new cache feature adds its provider here, and every stack function passes
-        it.  ``rotary=False``: the caller has rotated q and k itself (the unfused step)."""
-        return {**new, **self.paging(), **self.windowing(), **self.quant(li), **(self.rotary() if rotary else {})}
+        """Every keyword an attend call on layer ``li`` of this cache takes beside its tensors: paging, windowing, quant, rotary and
+        capping, and the caller's own (``new``: k_new=, v_new=).  A new cache feature adds its provider here, and every stack function
+        passes it.  ``rotary=False``: the caller has rotated q and k itself (the unfused step)."""
+        return {**new, **self.paging(), **self.windowing(), **self.quant(li), **(self.rotary() if rotary else {}), **self.capping()}
+
+    def capping(self):
+        """The keyword that makes a device_ops call a soft-capped one: none for a cache without a cap."""
+        return {} if self.softcap is None else dict(softcap=self.softcap)
 
     def rotary(self):
         """The keywords that make a device_ops call a roped one: none for a cache without rotary embeddings."""
@@ -373,9 +400,9 @@ class PagedKVCache(KVCache):
     read.  Without sinks sink_pages = 0 and this is the rule above."""
 
     def __init__(self, n_layers, B, capacity, n_head, head_dim, dtype, device, n_kv_head=None, page_size=128, n_pages=None, window=None,
-                 kv_dtype=None, kv_scale=None, sink=None, rope=None):
+                 kv_dtype=None, kv_scale=None, sink=None, rope=None, softcap=None):
         self.page_size, self.n_pages = page_size, n_pages   # (as given: _pool checks them at their place in KVCache's order)
-        super().__init__(n_layers, B, capacity, n_head, head_dim, dtype, device, n_kv_head, window, kv_dtype, kv_scale, sink, rope)
+        super().__init__(n_layers, B, capacity, n_head, head_dim, dtype, device, n_kv_head, window, kv_dtype, kv_scale, sink, rope, softcap)
         self.block_table = torch.zeros((B, self.max_pages), dtype=torch.int32, device=device)   # (entries past a sequence's pages: never read)
         self.free = list(range(self.n_pages - 1, -1, -1))   # (handed out from the end: page 0 first)
         self.pages = [[] for _ in range(B)]                 # the pages of each sequence, in order
@@ -489,11 +516,12 @@ def attention_stack_prefill(x, layers, n_head: int, cache: KVCache):
     v of the P tokens (lengths = P).  A grouped-query stack (wk, wv of shape (E, Hkv * d)) stores its Hkv heads, and the prompt's own
     attention reads those cache-shaped k and v in place (device_ops.flash_attn_fwd_gqa: no expanded copy).  Returns the stack's
     output (B, P, E).  A WINDOWED cache does not use that square forward, which has no window: its prompt goes through the extend
-    kernels as one piece (attention_stack_prefill_chunked with chunk = P), which append and attend through the window."""
+    kernels as one piece (attention_stack_prefill_chunked with chunk = P), which append and attend through the window.  A cache with
+    a SOFTCAP takes the same route: the square forward has no cap."""
     B, P, E = x.shape
     if P > cache.capacity:
         raise ValueError(f"prompt of {P} tokens exceeds the cache capacity {cache.capacity}")
-    if cache.window is not None:
+    if cache.window is not None or cache.softcap is not None:
         return attention_stack_prefill_chunked(x, layers, n_head, cache, max(P, 1))
     d = E // n_head
     # an fp8 cache, slab or paged, and every paged one take the prompt through the library's append (it quantises, and it knows the

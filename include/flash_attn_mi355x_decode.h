@@ -169,4 +169,9 @@ const char* fa_mi355x_decode_last_error(void);
  * entry points above, uniform and ragged: three entry points, part of this library and of this header, kept in a file of their own. */
 #include "flash_attn_mi355x_decode_rope.h"
 
+/* Logit soft-capping (every score becomes softcap * tanh(score / softcap) between the two products) for the decode, extend and
+ * ragged calls, slab or paged, windowed or not: three entry points, part of this library and of this header, kept in a file of
+ * their own. */
+#include "flash_attn_mi355x_decode_softcap.h"
+
 #endif /* FLASH_ATTN_MI355X_DECODE_H */
