@@ -282,6 +282,13 @@ WINDOW_TRAIN_ABI = {
     "fa_mi355x_bwd_window": (_i, [_vp] * 10 + [_i] * 6 + [_f, _i, _i, _i, _vp]),
     "fa_mi355x_window_last_error": (_s, []),
 }
+# the same for include/flash_attn_mi355x_window_softcap.h, which the same library exports: the two calls under logit soft-capping,
+# `float softcap` behind `int window` (tests/test_softcap_train_cpu.py).  A table of its own: tests/test_window_train_cpu.py holds
+# the one above to the window header's symbols.
+WINDOW_TRAIN_SOFTCAP_ABI = {
+    "fa_mi355x_fwd_window_softcap": (_i, [_vp] * 5 + [_i] * 6 + [_f, _i, _f, _i, _i, _vp]),
+    "fa_mi355x_bwd_window_softcap": (_i, [_vp] * 10 + [_i] * 6 + [_f, _i, _f, _i, _i, _vp]),
+}
 
 
 def _typed(name: str, abi: dict) -> ctypes.CDLL:
@@ -363,11 +370,12 @@ def decode_check(status: int) -> None:
 
 
 WINDOW_NAME = "libflash_attn_mi355x_window.so"
+_WINDOW_LIB_ABI = {**WINDOW_TRAIN_ABI, **WINDOW_TRAIN_SOFTCAP_ABI}
 
 
 def window() -> ctypes.CDLL:
-    """libflash_attn_mi355x_window.so (include/flash_attn_mi355x_window.h) with argtypes set."""
-    return _typed(WINDOW_NAME, WINDOW_TRAIN_ABI)
+    """libflash_attn_mi355x_window.so (include/flash_attn_mi355x_window.h and its _softcap.h) with argtypes set."""
+    return _typed(WINDOW_NAME, _WINDOW_LIB_ABI)
 
 
 def window_check(status: int) -> None:

@@ -22,6 +22,18 @@ FA_DEV int lane_fresh() {
   return l;
 }
 
+// Soft-capping (the KV-cache kernels of fa_decode.h and the cap builds of fa_window.h): z = softcap * tanh(tau * s / softcap) for a
+// raw score s, as softcap - 2 softcap / (t + 1) with t = e^(2 tau s / softcap) = exp2(s * k2), k2 = 2 log2(e) tau / softcap (once
+// per workgroup).  One v_exp_f32 and one v_rcp_f32 per score (gfx950 has no tanh).  It saturates without a special case: t = inf
+// gives rcp = 0 and z = +softcap, t = 0 gives z = -softcap, and no finite s gives a NaN (the (t - 1) / (t + 1) form gives
+// inf / inf).  The absolute error is a few ulp of softcap, whatever s.  The backward takes the cap's derivative from the same
+// r = 1 / (t + 1): 1 - tanh^2 = 4 r (1 - r), 0 at both saturations (4 t / (t + 1)^2 gives inf * 0 there).
+FA_DEV float cap_k2(float tau, float softcap) { return 2.0f * LOG2E * tau / softcap; }
+FA_DEV float cap_rcp(float s, float k2) { return __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(s * k2) + 1.0f); }
+FA_DEV float cap_z(float r, float softcap) { return __builtin_fmaf(-2.0f * softcap, r, softcap); }
+FA_DEV float cap_slope(float r) { return 4.0f * r * (1.0f - r); }
+FA_DEV float cap_score(float s, float k2, float softcap) { return cap_z(cap_rcp(s, k2), softcap); }
+
 template <typename T> FA_DEV typename Atom<T>::frag load_frag_buf(rsrc_t rs, int byte_off);
 template <> FA_DEV bf16x8 load_frag_buf<bf16_t>(rsrc_t rs, int byte_off) {
   return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, byte_off, 0, 0));

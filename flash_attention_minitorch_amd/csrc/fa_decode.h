@@ -143,15 +143,7 @@ using DecodeArgsOf = typename std::conditional<FP8, Fp8Args, typename std::condi
 // (positive and finite is the caller's contract: the kernels do not check a scale)
 FA_DEV float scale_of(const float* scale, int hkv) { return scale ? scale[hkv] : 1.0f; }
 
-// Soft-capping: z = softcap * tanh(tau * s / softcap) for a raw score s, as softcap - 2 softcap / (t + 1) with t = e^(2 tau s /
-// softcap) = exp2(s * k2), k2 = 2 log2(e) tau / softcap (once per workgroup).  One v_exp_f32 and one v_rcp_f32 per score (gfx950
-// has no tanh).  It saturates without a special case: t = inf gives rcp = 0 and z = +softcap, t = 0 gives z = -softcap, and no
-// finite s gives a NaN (the (t - 1) / (t + 1) form gives inf / inf).  The absolute error is a few ulp of softcap, whatever s.
-FA_DEV float cap_score(float s, float k2, float softcap) {
-  const float t = __builtin_amdgcn_exp2f(s * k2);
-  return __builtin_fmaf(-2.0f * softcap, __builtin_amdgcn_rcpf(t + 1.0f), softcap);
-}
-FA_DEV float cap_k2(float tau, float softcap) { return 2.0f * LOG2E * tau / softcap; }
+// (Soft-capping: cap_score and cap_k2 are in fa_common.h, which the training kernels of fa_window.h share.)
 
 FA_DEV int clamp_len(const int* seqlens, int Ncap, int b) {
   const int len = seqlens ? seqlens[b] : Ncap;

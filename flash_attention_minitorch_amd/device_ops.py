@@ -549,13 +549,22 @@ class _FlashAttnGqaFn(torch.autograd.Function):
         return dq.to(q.dtype), dk.to(q.dtype), dv.to(q.dtype), None, None, None
 
 
-def flash_attn_gqa(q, k, v, causal=False, softmax_scale=None, layout="bnhd", window=None, sink=None):
+def flash_attn_gqa(q, k, v, causal=False, softmax_scale=None, layout="bnhd", window=None, sink=None, softcap=None):
     """Attention with grouped-query heads under autograd (FA-2): out fp32 in q's shape; q.grad in q's shape and dtype, k.grad and
     v.grad in k's.  ``window`` = W (with ``sink`` = S): row i admits key j iff j <= i and (j > i - W or j < S), the mask of the
-    KV-cache calls, through the kernels of libflash_attn_mi355x_window.so; None or 0, W >= N or S >= N is this call without them."""
-    ws = _training_window(window, sink, causal, q.shape[1 if layout == "bnhd" else 2] if q.dim() == 4 else 0)
+    KV-cache calls, through the kernels of libflash_attn_mi355x_window.so; None or 0, W >= N or S >= N is this call without them.
+    ``softcap`` = C (causal only): LOGIT SOFT-CAPPING, every score becomes C * tanh(softmax_scale * q.k / C) before the mask, the
+    function of flash_attn_decode(..., softcap=), differentiated through the cap (fa_mi355x_fwd_window_softcap / _bwd_window_softcap;
+    without a window the call passes W = N).  None or 0 is this call without a cap."""
+    N = q.shape[1 if layout == "bnhd" else 2] if q.dim() == 4 else 0
+    softcap = _check_softcap(softcap)
+    if softcap is not None and not causal:
+        raise ValueError("softcap without the causal mask is not built: softcap= with causal=False")
+    ws = _training_window(window, sink, causal, N)
+    if softcap is not None:   # (the capped kernels are the window library's: a call without a window is the one with W = N)
+        return _FlashAttnWindowFn.apply(q, k, v, softmax_scale, layout, window or N, sink or 0, softcap)
     if ws is not None:
-        return _FlashAttnWindowFn.apply(q, k, v, softmax_scale, layout, *ws)
+        return _FlashAttnWindowFn.apply(q, k, v, softmax_scale, layout, *ws, None)
     return _FlashAttnGqaFn.apply(q, k, v, bool(causal), softmax_scale, layout)
 
 
@@ -808,26 +817,40 @@ def bwd_workspace_window(q, k, layout="bnhd"):
     return torch.empty((nbytes + 3) // 4, dtype=_F32, device=q.device)
 
 
-def flash_attn_fwd_window(q, k, v, window, sink=None, softmax_scale=None, layout="bnhd", out=None):
+def _window_call(lib, stem, softcap, front, B, H, Hkv, N, d, layout, softmax_scale, window, sink, dtype):
+    """The library's call ``stem`` (fa_mi355x_fwd_window, fa_mi355x_bwd_window) or, under a cap, its _softcap form: the same
+    arguments with the cap behind the window."""
+    head = (*front, B, H, Hkv, N, d, _DECODE_LAYOUTS[layout], float(softmax_scale or 0.0), window)
+    tail = (sink, dtype, _stream_ptr())
+    if softcap is None:
+        return getattr(lib, stem)(*head, *tail)
+    return getattr(lib, stem + "_softcap")(*head, softcap, *tail)
+
+
+def flash_attn_fwd_window(q, k, v, window, sink=None, softmax_scale=None, layout="bnhd", out=None, softcap=None):
     """Causal forward under a sliding window of ``window`` positions and ``sink`` first positions, grouped-query heads as
-    flash_attn_fwd_gqa.  Returns (out fp32 in q's shape, lse (B, H, N))."""
+    flash_attn_fwd_gqa.  Returns (out fp32 in q's shape, lse (B, H, N)).  ``softcap``: logit soft-capping, as in flash_attn_gqa
+    (fa_mi355x_fwd_window_softcap; lse is taken over the capped logits); None or 0: none, today's call."""
     window, sink = _check_window_call(window, sink)
+    softcap = _check_softcap(softcap)
     B, H, Hkv, N, d, dtype = _check_gqa(layout, q, k, v)
     if out is not None and (out.dtype is not _F32 or out.shape != q.shape or not out.is_contiguous() or out.get_device() != q.get_device()):
         raise ValueError("out must be a contiguous float32 tensor of q's shape")
     lse = torch.empty((B, H, N), dtype=_F32, device=q.device)
     if out is None:
         out = torch.empty(q.shape, dtype=_F32, device=q.device)
-    _lib.window_check(_lib.window().fa_mi355x_fwd_window(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), B, H, Hkv, N, d,
-                                                         _DECODE_LAYOUTS[layout], float(softmax_scale or 0.0), window, sink, dtype,
-                                                         _stream_ptr()))
+    _lib.window_check(_window_call(_lib.window(), "fa_mi355x_fwd_window", softcap, (_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse)),
+                                   B, H, Hkv, N, d, layout, softmax_scale, window, sink, dtype))
     return out, lse
 
 
-def flash_attn_bwd_window(q, k, v, out, out_grad, lse, window, sink=None, softmax_scale=None, layout="bnhd", workspace=None, grads=None):
+def flash_attn_bwd_window(q, k, v, out, out_grad, lse, window, sink=None, softmax_scale=None, layout="bnhd", workspace=None, grads=None,
+                          softcap=None):
     """Backward of flash_attn_fwd_window.  Returns (dq in q's shape, dk, dv in k's shape), fp32; no atomics, the same bits on every
-    run.  ``workspace``: bwd_workspace_window(q, k, layout); ``grads``: (dq, dk, dv) buffers to write into."""
+    run.  ``workspace``: bwd_workspace_window(q, k, layout); ``grads``: (dq, dk, dv) buffers to write into.  ``softcap``: the cap of
+    the forward that made out and lse (fa_mi355x_bwd_window_softcap; the workspace does not depend on it)."""
     window, sink = _check_window_call(window, sink)
+    softcap = _check_softcap(softcap)
     B, H, Hkv, N, d, dtype = _check_gqa(layout, q, k, v, out, out_grad)
     lib, dev = _lib.window(), q.get_device()
     _check_buffer(lse, dev, "lse", B * H * N)
@@ -842,29 +865,30 @@ def flash_attn_bwd_window(q, k, v, out, out_grad, lse, window, sink=None, softma
     if workspace is None:
         workspace = bwd_workspace_window(q, k, layout)
     dq, dk, dv = grads or (torch.empty(t.shape, dtype=_F32, device=q.device) for t in (q, k, v))
-    _lib.window_check(lib.fa_mi355x_bwd_window(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(out_grad), _ptr(dq), _ptr(dk), _ptr(dv),
-                                               _ptr(lse), _ptr(workspace), B, H, Hkv, N, d, _DECODE_LAYOUTS[layout],
-                                               float(softmax_scale or 0.0), window, sink, dtype, _stream_ptr()))
+    front = (_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(out_grad), _ptr(dq), _ptr(dk), _ptr(dv), _ptr(lse), _ptr(workspace))
+    _lib.window_check(_window_call(lib, "fa_mi355x_bwd_window", softcap, front, B, H, Hkv, N, d, layout, softmax_scale, window, sink,
+                                   dtype))
     return dq, dk, dv
 
 
 class _FlashAttnWindowFn(torch.autograd.Function):
-    """flash_attn_gqa under a sliding window (and sink tokens): the forward saves q, the unexpanded k and v, o and lse; gradients are
-    cast to the input dtype."""
+    """flash_attn_gqa under a sliding window (and sink tokens), with or without a logit cap: the forward saves q, the unexpanded k
+    and v, o and lse; gradients are cast to the input dtype."""
 
     @staticmethod
-    def forward(ctx, q, k, v, softmax_scale, layout, window, sink):
-        o, lse = flash_attn_fwd_window(q, k, v, window, sink, softmax_scale, layout)
+    def forward(ctx, q, k, v, softmax_scale, layout, window, sink, softcap):
+        o, lse = flash_attn_fwd_window(q, k, v, window, sink, softmax_scale, layout, softcap=softcap)
         ctx.save_for_backward(q, k, v, o, lse)
-        ctx.args = softmax_scale, layout, window, sink
+        ctx.args = softmax_scale, layout, window, sink, softcap
         return o
 
     @staticmethod
     def backward(ctx, out_grad):
         q, k, v, o, lse = ctx.saved_tensors
-        softmax_scale, layout, window, sink = ctx.args
-        dq, dk, dv = flash_attn_bwd_window(q, k, v, o, out_grad.to(q.dtype).contiguous(), lse, window, sink, softmax_scale, layout)
-        return dq.to(q.dtype), dk.to(q.dtype), dv.to(q.dtype), None, None, None, None
+        softmax_scale, layout, window, sink, softcap = ctx.args
+        dq, dk, dv = flash_attn_bwd_window(q, k, v, o, out_grad.to(q.dtype).contiguous(), lse, window, sink, softmax_scale, layout,
+                                           softcap=softcap)
+        return dq.to(q.dtype), dk.to(q.dtype), dv.to(q.dtype), None, None, None, None, None
 
 
 def decode_workspace(q, k_cache, layout="bnhd", block_table=None, max_pages=None, window=None, sink=None):

@@ -68,7 +68,7 @@ class Rotary:
 
 
 def multi_head_attention(x, wq, wk, wv, wo, n_head: int, causal: bool = True, fused_layout: bool = True, fold_scale: bool = False,
-                         rope=None, window=None, sink=None):
+                         rope=None, window=None, sink=None, softcap=None):
     """MultiHeadAttention.forward (modules_transfomer.py:141-157).  x: (B, N, E); wq, wo: (E, E); wk, wv: (E, E), or (E, Hkv * d) for
     grouped-query heads (Hkv divides n_head, d = E // n_head; query head h reads kv head h // (n_head // Hkv)).  With ``fused_layout``
     the kernels read the Hkv heads of k and v in place, forward and backward (device_ops.flash_attn_gqa: no expanded copy, and the
@@ -82,15 +82,19 @@ def multi_head_attention(x, wq, wk, wv, wo, n_head: int, causal: bool = True, fu
     (device_ops.apply_rotary, whose backward is the inverse rotation: the path is trainable).
     ``window`` = W, ``sink`` = S: the sliding-window mask a KVCache(window=W, sink=S) generates under (token i sees the last W
     positions and the first S), forward and backward (device_ops.flash_attn_gqa(window=, sink=)); the rotation comes first, as
-    without a window.  None or 0, W >= N or S >= N: the layer without them."""
+    without a window.  None or 0, W >= N or S >= N: the layer without them.
+    ``softcap`` = C (causal only): the logit cap a KVCache(softcap=C) generates under, C * tanh(score / C) on the scaled score before
+    the mask, forward and backward (device_ops.flash_attn_gqa(softcap=)); it composes with ``rope``, ``window``, ``sink`` and
+    ``fold_scale`` (the cap acts on softmax_scale * q.k, which folding leaves the same).  None or 0: the layer without a cap."""
     B, N, E = x.shape
-    windowed = device_ops._training_window(window, sink, causal, N) is not None
+    capped = device_ops._check_softcap(softcap) is not None
+    windowed = capped or device_ops._training_window(window, sink, causal, N) is not None   # (a cap: the window library's kernels)
     if fused_layout:
         q, k, v = _project(x, wq * (LOG2E / (E // n_head) ** 0.5) if fold_scale else wq, wk, wv, n_head)
         if rope is not None:
             q, k = rope.apply(q), rope.apply(k)
         if windowed:   # grouped or not: k and v stay (B, N, Hkv, d)
-            o = device_ops.flash_attn_gqa(q, k, v, causal, LN2 if fold_scale else None, "bnhd", window, sink)
+            o = device_ops.flash_attn_gqa(q, k, v, causal, LN2 if fold_scale else None, "bnhd", window, sink, softcap)
         elif k.shape[2] == n_head:
             o = _attention(q, k, v, causal, _lib.FA_LAYOUT_BNHD, LN2 if fold_scale else None)   # (B, N, H, d) fp32: already merged
         else:   # grouped-query heads: k and v stay (B, N, Hkv, d)
@@ -102,7 +106,7 @@ def multi_head_attention(x, wq, wk, wv, wo, n_head: int, causal: bool = True, fu
             q, k = rope.apply(q), rope.apply(k)
         q, k, v = (t.permute(0, 2, 1, 3).contiguous() for t in (q, _expand_kv(k, n_head), _expand_kv(v, n_head)))
         if windowed:
-            o = device_ops.flash_attn_gqa(q, k, v, causal, None, "bhnd", window, sink)
+            o = device_ops.flash_attn_gqa(q, k, v, causal, None, "bhnd", window, sink, softcap)
         else:
             o = _attention(q, k, v, causal, _lib.FA_LAYOUT_BHND)                              # (B, H, N, d)
         merged = o.permute(0, 2, 1, 3).contiguous().view(B * N, E)
@@ -110,13 +114,14 @@ def multi_head_attention(x, wq, wk, wv, wo, n_head: int, causal: bool = True, fu
 
 
 def attention_stack(x, layers, n_head: int, causal: bool = True, fused_layout: bool = True, fold_scale: bool = False, rope=None,
-                    window=None, sink=None):
+                    window=None, sink=None, softcap=None):
     """x <- x + MultiHeadAttention_l(x) for every (wq, wk, wv, wo) in ``layers``: the attention data flow of the reference's
     4-layer causal DecoderLM (modules_transfomer.py:255-351) without its out-of-scope LayerNorm / FFN blocks.  ``rope``: every
     layer rotates its q and k (multi_head_attention).  ``window``, ``sink``: every layer attends under the sliding-window mask of a
-    KVCache(window=, sink=), so a model that generates through such a cache trains under the mask it runs with."""
+    KVCache(window=, sink=), so a model that generates through such a cache trains under the mask it runs with.  ``softcap``: every
+    layer soft-caps its logits as a KVCache(softcap=) does (multi_head_attention), likewise."""
     for (wq, wk, wv, wo) in layers:
-        x = x + multi_head_attention(x, wq, wk, wv, wo, n_head, causal, fused_layout, fold_scale, rope, window, sink)
+        x = x + multi_head_attention(x, wq, wk, wv, wo, n_head, causal, fused_layout, fold_scale, rope, window, sink, softcap)
     return x
 
 
@@ -197,7 +202,7 @@ def cross_attention_packed(x, cu_seqlens_q, memory, cu_seqlens_k, wq, wk, wv, wo
 # unquantised k, v.  rope=Rotary(...): one fa_mi355x_rope_append launch per layer rotates q and the new k on their way in, then the
 # attend-only call runs; the square prefill and the unfused step rotate q and k with apply_rotary.  The cache holds ROTATED keys.
 # softcap=C: every call soft-caps its logits, C * tanh(score / C) (Gemma-2, Grok-1), through the family's softcap entry point; the
-# prompt takes the extend route, as on a windowed cache (the square forward has no cap).
+# prompt takes the extend route, as on a windowed cache (attention_stack(softcap=) trains under the same function).
 
 MAX_STEP_TOKENS = 128   # fa_mi355x_fwd_decode's largest Nq; longer inputs are prefill, or attention_stack_extend after a prefix
 

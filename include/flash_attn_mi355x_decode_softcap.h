@@ -29,8 +29,8 @@ extern "C" {
  *   causal           a cap does not need the causal mask (window = 0 with causal = 0 is a valid capped call); a window still does.
  *   empty rows       a row with no admissible key gives out = 0 and lse = -inf, as everywhere.
  *   append           is untouched.  A fused call appends first, then attends.
- *   Not built: a cap beside attention-sink tokens, a cap on an fp8 cache (there is no such entry point), and the training forward
- *   and backward under a cap.  Rotary embeddings need nothing new: fa_mi355x_rope_append in front, then the attend-only form of these
+ *   Not built: a cap beside attention-sink tokens and a cap on an fp8 cache (there is no such entry point).  The training forward
+ *   and backward under a cap are flash_attn_mi355x_window_softcap.h, in another library.  Rotary embeddings need nothing new: fa_mi355x_rope_append in front, then the attend-only form of these
  *   calls on q_rot.
  *
  * One entry point per call family.  Each is its family's _window prototype (flash_attn_mi355x_decode_window.h: k_new / v_new both
