@@ -12,51 +12,22 @@ HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 ARCH="${FA_ARCH:-gfx950}"
 mkdir -p "$OUT_DIR"
 
-CORE="$OUT_DIR/libflash_attn_mi355x.so"
 FLAGS=(--offload-arch="$ARCH" -O3 -std=c++17 -fPIC -shared -Wno-unused-value -mllvm -amdgpu-mfma-vgpr-form=1 -fno-slp-vectorize ${FA_EXTRA_FLAGS:-})
 stale() { [ ! -f "$1" ] || [ -n "$(find "$SRC" "$HERE/include" -newer "$1" \( -name '*.h' -o -name '*.hip' \) -print -quit)" ]; }
-if stale "$CORE"; then
-  echo "[compile_cuda.sh] hipcc --offload-arch=$ARCH  fa_api.hip -> $CORE"
-  "$HIPCC" "${FLAGS[@]}" "$SRC/fa_api.hip" -o "$CORE"
-else
-  echo "[compile_cuda.sh] $CORE is up to date"
-fi
-
-# KV-cache decode (include/flash_attn_mi355x_decode.h): its own library, so the training library's code object stays as it is
-DECODE="$OUT_DIR/libflash_attn_mi355x_decode.so"
-if [ ! -f "$DECODE" ] || [ -n "$(find "$SRC" "$HERE/include" -newer "$DECODE" \( -name '*.h' -o -name '*.hip' \) -print -quit)" ]; then
-  echo "[compile_cuda.sh] hipcc --offload-arch=$ARCH  fa_decode.hip -> $DECODE"
-  "$HIPCC" "${FLAGS[@]}" "$SRC/fa_decode.hip" -o "$DECODE"
-else
-  echo "[compile_cuda.sh] $DECODE is up to date"
-fi
-
-# Sliding-window / attention-sink forward and backward (include/flash_attn_mi355x_window.h): a third library, for the same reason
-WINDOW="$OUT_DIR/libflash_attn_mi355x_window.so"
-if stale "$WINDOW"; then
-  echo "[compile_cuda.sh] hipcc --offload-arch=$ARCH  fa_window.hip -> $WINDOW"
-  "$HIPCC" "${FLAGS[@]}" "$SRC/fa_window.hip" -o "$WINDOW"
-else
-  echo "[compile_cuda.sh] $WINDOW is up to date"
-fi
-
-# Packed variable-length (cu_seqlens) forward and backward (include/flash_attn_mi355x_varlen.h): a fourth library, for the same reason
-VARLEN="$OUT_DIR/libflash_attn_mi355x_varlen.so"
-if stale "$VARLEN"; then
-  echo "[compile_cuda.sh] hipcc --offload-arch=$ARCH  fa_varlen.hip -> $VARLEN"
-  "$HIPCC" "${FLAGS[@]}" "$SRC/fa_varlen.hip" -o "$VARLEN"
-else
-  echo "[compile_cuda.sh] $VARLEN is up to date"
-fi
-
-# Bidirectional packed attention with separate cu_seqlens for q and k (include/flash_attn_mi355x_bidir.h): a fifth library, for the same reason
-BIDIR="$OUT_DIR/libflash_attn_mi355x_bidir.so"
-if stale "$BIDIR"; then
-  echo "[compile_cuda.sh] hipcc --offload-arch=$ARCH  fa_bidir.hip -> $BIDIR"
-  "$HIPCC" "${FLAGS[@]}" "$SRC/fa_bidir.hip" -o "$BIDIR"
-else
-  echo "[compile_cuda.sh] $BIDIR is up to date"
-fi
+kernel_lib() {  # source stem, library suffix: one code object per library, so that a new library leaves the others' as they are
+  local lib="$OUT_DIR/libflash_attn_mi355x$2.so"
+  if stale "$lib"; then
+    echo "[compile_cuda.sh] hipcc --offload-arch=$ARCH  $1.hip -> $lib"
+    "$HIPCC" "${FLAGS[@]}" "$SRC/$1.hip" -o "$lib"
+  else
+    echo "[compile_cuda.sh] $lib is up to date"
+  fi
+}
+kernel_lib fa_api    ""          # the core library: training forward and backward (include/flash_attn_mi355x.h)
+kernel_lib fa_decode _decode     # KV-cache decode (include/flash_attn_mi355x_decode.h)
+kernel_lib fa_window _window     # sliding-window / attention-sink forward and backward (include/flash_attn_mi355x_window.h)
+kernel_lib fa_varlen _varlen     # packed variable-length (cu_seqlens) forward and backward (include/flash_attn_mi355x_varlen.h)
+kernel_lib fa_bidir  _bidir      # bidirectional packed attention, cu_seqlens for q and for k (include/flash_attn_mi355x_bidir.h)
 
 shim() {  # name variant FW|BW
   "$HIPCC" -O2 -fPIC -shared -x c++ "$SRC/fa_shim.cpp" -DFA_SHIM_VARIANT="$2" -DFA_SHIM_"$3" \

@@ -31,12 +31,6 @@ constexpr float BIDIR_DEFER_SUM = 64.0f;   // as fa_fwd.h's MAX_DEFER_SUM: bound
 // block -1: unused, the workgroup returns before its first barrier.
 constexpr int BIDIR_ENTRY_BYTES = 32;
 
-// fa_decode.h's seq_rows: sequence b owns rows s .. s + n - 1, s = clamp(cu[b], 0, T) and s + n = clamp(max(cu[b + 1], s), 0, T)
-FA_DEV void bidir_seq_rows(const int* cu, int T, int b, int& s, int& n) {
-  s = min(max(cu[b], 0), T);
-  n = min(max(cu[b + 1], s), T) - s;
-}
-
 // bytes of a buffer resource over n rows of ld elements whose last row ends after D of them (n = 0: no byte, every load reads zero)
 template <typename T, int D> FA_DEV uint32_t bidir_bytes(int n, int ld) {
   return n > 0 ? ((uint32_t)(n - 1) * (uint32_t)ld + D) * (uint32_t)sizeof(T) : 0u;
@@ -619,7 +613,7 @@ FA_DEV void bidir_build_map(const int* cu, int T, const int* cu_q, int Tq, const
   int n = 0;
   for (int b = b0; b < b1; ++b) {
     int s, nb;
-    bidir_seq_rows(cu, T, b, s, nb);
+    seq_rows(cu, T, b, s, nb);
     n = min(n + (nb + bs - 1) / bs, cap);
   }
   counts[tid] = n;
@@ -631,9 +625,9 @@ FA_DEV void bidir_build_map(const int* cu, int T, const int* cu_q, int Tq, const
   }
   for (int b = b0; b < b1; ++b) {
     int s, nb, sq, nq, sk, nk;
-    bidir_seq_rows(cu, T, b, s, nb);
-    bidir_seq_rows(cu_q, Tq, b, sq, nq);
-    bidir_seq_rows(cu_k, Tk, b, sk, nk);
+    seq_rows(cu, T, b, s, nb);
+    seq_rows(cu_q, Tq, b, sq, nq);
+    seq_rows(cu_k, Tk, b, sk, nk);
     const int blocks = (nb + bs - 1) / bs;
     for (int blk = 0; blk < blocks && off < cap; ++blk, ++off) {
       map[2 * off] = make_int4(sq, nq, sk, nk);
@@ -660,8 +654,8 @@ struct BidirFill {
 // leave no gap: each begins at or before the end of the one before it).  u counts them: 0 .. lead - 1, then the tail.
 FA_DEV void bidir_fill_unowned(const int* cu, int nseq, int T, float* m0, float* m1, int ld, float* rowc, int H, long start, long step) {
   int lead, n0, sl, nl;
-  bidir_seq_rows(cu, T, 0, lead, n0);
-  bidir_seq_rows(cu, T, nseq - 1, sl, nl);
+  seq_rows(cu, T, 0, lead, n0);
+  seq_rows(cu, T, nseq - 1, sl, nl);
   const int tail0 = sl + nl;
   const long count = (long)lead + (T - tail0);
   if (count <= 0) return;

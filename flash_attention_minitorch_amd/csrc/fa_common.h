@@ -135,4 +135,11 @@ FA_DEV f32x16 zero16() {
   return z;
 }
 
+// Packed rows (the ragged KV-cache calls, the varlen and the bidir library): sequence b owns the rows s .. s + n - 1,
+// s = clamp(cu[b], 0, T) and s + n = clamp(cu[b+1], s, T): whatever the array holds, no row leaves the T-row buffers.  n may be 0.
+FA_DEV void seq_rows(const int* cu, int T, int b, int& s, int& n) {
+  s = min(max(cu[b], 0), T);
+  n = min(max(cu[b + 1], s), T) - s;
+}
+
 }  // namespace fa

@@ -152,12 +152,7 @@ FA_DEV int clamp_len(const int* seqlens, int Ncap, int b) {
 
 FA_DEV int clamp_len(const DecodeArgs& a, int b) { return clamp_len(a.seqlens, a.Ncap, b); }
 
-// Ragged: sequence b owns the packed rows s .. s + nq - 1, s = clamp(cu[b], 0, ntok) and s + nq = clamp(cu[b+1], s, ntok): whatever
-// the array holds, no row leaves the ntok-row buffers.  nq may be 0.
-FA_DEV void seq_rows(const int* cu, int ntok, int b, int& s, int& nq) {
-  s = min(max(cu[b], 0), ntok);
-  nq = min(max(cu[b + 1], s), ntok) - s;
-}
+// (Ragged: seq_rows, which packed rows a sequence owns, is in fa_common.h, which the packed training libraries share.)
 
 // rho / G for a row index 0 <= rho < 2^25 without the integer division's long dependent chain in front of the workgroup's first
 // loads: the float quotient is off by at most one, which the remainder corrects.  (G = 1: exact at once.)

@@ -1,6 +1,6 @@
 // Packed variable-length batches for the training forward and backward on MI355X (gfx950): the kernels of
 // libflash_attn_mi355x_varlen.so (include/flash_attn_mi355x_varlen.h).  q / out / dO / dq are [T][H][d], k / v / dk / dv [T][Hkv][d];
-// cu_seqlens (int32, nseq + 1 entries, on the device) says which packed rows a sequence owns (seq_rows of fa_decode.h).
+// cu_seqlens (int32, nseq + 1 entries, on the device) says which packed rows a sequence owns (seq_rows of fa_common.h).
 //
 // The attention kernels are the three of fa_window.h, built here under names of their own (varlen_fwd_kernel, varlen_dq_kernel,
 // varlen_dkdv_kernel) through that file's hooks.  A workgroup takes (head, map entry) where a window workgroup takes (head, block);

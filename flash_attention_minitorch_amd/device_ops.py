@@ -172,6 +172,31 @@ def _check_buffer(t, dev, name, numel):
         raise ValueError(f"{name} must be a contiguous float32 tensor on q's device with at least {numel} elements")
 
 
+def _check_workspace(workspace, nbytes, dev, sizer):
+    """A caller's workspace for a call that needs ``nbytes``; ``sizer``: the call that makes one, for the message."""
+    if workspace.numel() * workspace.element_size() < nbytes:
+        raise ValueError(f"workspace too small: size it with {sizer}")
+    if not workspace.is_contiguous() or workspace.get_device() != dev or workspace.data_ptr() % 256:
+        raise ValueError("workspace must be a contiguous, 256-byte aligned tensor on q's device")
+
+
+def _check_out(out, q):
+    """A caller's ``out`` (None: the call allocates it): fp32 in q's shape."""
+    if out is not None and (out.dtype is not _F32 or out.shape != q.shape or not out.is_contiguous() or out.get_device() != q.get_device()):
+        raise ValueError("out must be a contiguous float32 tensor of q's shape")
+
+
+def _check_grads(grads, q, k, v):
+    """A caller's ``grads`` (dq, dk, dv; None: the call allocates them): fp32 buffers for the shapes of q, k and v."""
+    for g, like in zip(grads or (), (q, k, v)):
+        _check_buffer(g, q.get_device(), "each of grads", like.numel())
+
+
+def _new_f32(*like):
+    """New fp32 tensors in the shapes of ``like``, on their device."""
+    return tuple(torch.empty(t.shape, dtype=_F32, device=t.device) for t in like)
+
+
 def _check_inputs(layout, ts, o, key_mask, rank4):
     """The checks every call starts with, in the order the entry points have always run them: the tensors (GPU, dtype, shared shape /
     dtype / device, contiguity, rank), the key mask, the forward's O.  ``rank4``: the message for a BHND call that needs 4-d tensors
@@ -508,10 +533,7 @@ def flash_attn_bwd_gqa(q, k, v, out, out_grad, l, m=None, causal=False, variant=
     B, H, Hkv, N, d, dtype = _check_gqa(layout, q, k, v, out, out_grad)
     lib, dev = _lib.core(), q.device
     if workspace is not None:
-        if workspace.numel() * workspace.element_size() < lib.fa_mi355x_bwd_workspace_bytes_gqa(B, H, Hkv, N, d):
-            raise ValueError("workspace too small: size it with bwd_workspace_gqa(q, k, layout)")
-        if not workspace.is_contiguous() or workspace.get_device() != q.get_device() or workspace.data_ptr() % 256:
-            raise ValueError("workspace must be a contiguous, 256-byte aligned tensor on q's device")
+        _check_workspace(workspace, lib.fa_mi355x_bwd_workspace_bytes_gqa(B, H, Hkv, N, d), q.get_device(), "bwd_workspace_gqa(q, k, layout)")
     _check_caller(q.get_device(), B * H * N, l, m, guard)
     if grads is not None:
         for g, like in zip(grads, (q, k, v)):
@@ -562,9 +584,9 @@ def flash_attn_gqa(q, k, v, causal=False, softmax_scale=None, layout="bnhd", win
         raise ValueError("softcap without the causal mask is not built: softcap= with causal=False")
     ws = _training_window(window, sink, causal, N)
     if softcap is not None:   # (the capped kernels are the window library's: a call without a window is the one with W = N)
-        return _FlashAttnWindowFn.apply(q, k, v, softmax_scale, layout, window or N, sink or 0, softcap)
+        return _window_fn(q, k, v, softmax_scale, layout, window or N, sink or 0, softcap)
     if ws is not None:
-        return _FlashAttnWindowFn.apply(q, k, v, softmax_scale, layout, *ws, None)
+        return _window_fn(q, k, v, softmax_scale, layout, *ws, None)
     return _FlashAttnGqaFn.apply(q, k, v, bool(causal), softmax_scale, layout)
 
 
@@ -810,38 +832,141 @@ def _check_window_call(window, sink):
     return window, sink or 0
 
 
+# ---- the training-side libraries (window / softcap, varlen, bidir): one path for the three families -------------------------------
+# The NAMES by which the windowed calls here, the packed calls (flash_attn_varlen_*) and the bidirectional ones
+# (flash_attn_varlen_bidir_*, both below) differ; _side_fwd, _side_bwd and _side_workspace do the work.  What else a family has of its
+# own is code, not this table: its geometry (_side_geometry, over _check_gqa or _check_packed) and its mask scalars (the public
+# wrappers).  ``lib`` / ``check``: _lib's getter and status checker, looked up at call time; ``fwd`` / ``bwd``: the entry points
+# (under a logit cap: their _softcap forms, the cap behind the window); ``fwd_size`` / ``bwd_size``: the workspace sizes (None: the
+# call takes no workspace); ``sizer``: the public call that makes a workspace, for the message.  A call's arguments: the tensors, the
+# geometry, softmax_scale, the mask scalars, dtype, stream.
+_SIDE_FAMILIES = {
+    "window": dict(lib="window", check="window_check", fwd="fa_mi355x_fwd_window", bwd="fa_mi355x_bwd_window", fwd_size=None,
+                   bwd_size="fa_mi355x_bwd_window_workspace_bytes", sizer="bwd_workspace_window(q, k, layout)"),
+    "varlen": dict(lib="varlen", check="varlen_check", fwd="fa_mi355x_fwd_varlen", bwd="fa_mi355x_bwd_varlen",
+                   fwd_size="fa_mi355x_fwd_varlen_workspace_bytes", bwd_size="fa_mi355x_bwd_varlen_workspace_bytes",
+                   sizer="varlen_workspace(q, k, cu_seqlens)"),
+    "bidir": dict(lib="bidir", check="bidir_check", fwd="fa_mi355x_fwd_bidir", bwd="fa_mi355x_bwd_bidir",
+                  fwd_size="fa_mi355x_fwd_bidir_workspace_bytes", bwd_size="fa_mi355x_bwd_bidir_workspace_bytes",
+                  sizer="bidir_workspace(q, k, cu_seqlens_q, cu_seqlens_k)"),
+}
+
+
+def _side_geometry(family, q, k, v, index, layout, o=None, do=None):
+    """The family's checks of its tensors (``index``: the cu_seqlens arrays of a packed call).  Returns (the geometry arguments of
+    its entry points, those of its workspace sizes, lse's shape, dtype code)."""
+    if family == "window":
+        B, H, Hkv, N, d, dtype = _check_gqa(layout, q, k, v, o, do)
+        return (B, H, Hkv, N, d, _DECODE_LAYOUTS[layout]), (B, H, Hkv, N, d), (B, H, N), dtype
+    nseq, Tq, Tk, H, Hkv, d, dtype = _check_packed(q, k, v, index[0], index[-1], o, do, one_array=family == "varlen")
+    geom = (nseq, Tq, H, Hkv, d) if family == "varlen" else (nseq, Tq, Tk, H, Hkv, d)
+    return geom, geom, (H, Tq), dtype
+
+
+def _side_buffer(fam, size, sizes, workspace, q):
+    """A caller's ``workspace``, checked against the family's size query ``size``, or a new one."""
+    nbytes = getattr(getattr(_lib, fam["lib"])(), fam[size])(*sizes)
+    if workspace is None:
+        return torch.empty((nbytes + 3) // 4, dtype=_F32, device=q.device)
+    _check_workspace(workspace, nbytes, q.get_device(), fam["sizer"])
+    return workspace
+
+
+def _side_workspace(family, q, k, index=(), layout="bnhd", backward=True):
+    _, sizes, _, _ = _side_geometry(family, q, k, k, index, layout)
+    return _side_buffer(_SIDE_FAMILIES[family], "bwd_size" if backward else "fwd_size", sizes, None, q)
+
+
+def _side_call(fam, op, tensors, geom, softmax_scale, mask, softcap, dtype):
+    """The one place a training-side symbol is called."""
+    symbol = fam[op]
+    if softcap is not None:
+        symbol, mask = symbol + "_softcap", (mask[0], softcap, *mask[1:])
+    status = getattr(getattr(_lib, fam["lib"])(), symbol)(*map(_ptr, tensors), *geom, float(softmax_scale or 0.0), *mask, dtype, _stream_ptr())
+    getattr(_lib, fam["check"])(status)
+
+
+def _side_fwd(family, q, k, v, index, mask, softmax_scale, layout="bnhd", out=None, lse=None, workspace=None, softcap=None):
+    """The forward of a family: the checks (out, workspace, lse), what the caller did not supply (workspace, lse, out), one C call.
+    Returns (out, lse)."""
+    fam = _SIDE_FAMILIES[family]
+    geom, sizes, lse_shape, dtype = _side_geometry(family, q, k, v, index, layout)
+    _check_out(out, q)
+    workspace = () if fam["fwd_size"] is None else (_side_buffer(fam, "fwd_size", sizes, workspace, q),)
+    if lse is None:
+        lse = torch.empty(lse_shape, dtype=_F32, device=q.device)
+    else:
+        _check_buffer(lse, q.get_device(), "lse", math.prod(lse_shape))
+    if out is None:
+        out, = _new_f32(q)
+    _side_call(fam, "fwd", (q, k, v, out, lse, *index, *workspace), geom, softmax_scale, mask, softcap, dtype)
+    return out, lse
+
+
+def _side_bwd(family, q, k, v, out, out_grad, lse, index, mask, softmax_scale, layout="bnhd", workspace=None, grads=None, softcap=None):
+    """The backward of a family, likewise: every buffer of the caller is checked (lse, workspace, grads) before one is allocated
+    (workspace, grads).  Returns (dq, dk, dv)."""
+    fam = _SIDE_FAMILIES[family]
+    geom, sizes, lse_shape, dtype = _side_geometry(family, q, k, v, index, layout, out, out_grad)
+    _check_buffer(lse, q.get_device(), "lse", math.prod(lse_shape))
+    if workspace is not None:
+        _side_buffer(fam, "bwd_size", sizes, workspace, q)
+    _check_grads(grads, q, k, v)
+    if workspace is None:
+        workspace = _side_buffer(fam, "bwd_size", sizes, None, q)
+    dq, dk, dv = grads or _new_f32(q, k, v)
+    _side_call(fam, "bwd", (q, k, v, out, out_grad, dq, dk, dv, lse, *index, workspace), geom, softmax_scale, mask, softcap, dtype)
+    return dq, dk, dv
+
+
+class _FlashAttnSideFn(torch.autograd.Function):
+    """A family's public forward and backward (``fwd``, ``bwd``: flash_attn_fwd_window / _bwd_window, flash_attn_varlen_fwd / _bwd,
+    flash_attn_varlen_bidir_fwd / _bwd) under autograd.  ``index``: the tensors both take behind the operands (the cu_seqlens arrays);
+    ``options``: the keywords both take.  The forward saves q, the unexpanded k and v, o, lse and the index tensors; gradients are cast
+    to the input dtype (k and v have q's, by the checks)."""
+
+    @staticmethod
+    def forward(ctx, fwd, bwd, q, k, v, index, options):
+        o, lse = fwd(q, k, v, *index, **options)
+        ctx.save_for_backward(q, k, v, o, lse, *index)
+        ctx.bwd, ctx.options = bwd, options
+        return o
+
+    @staticmethod
+    def backward(ctx, out_grad):
+        q, k, v, o, lse, *index = ctx.saved_tensors
+        dq, dk, dv = ctx.bwd(q, k, v, o, out_grad.to(q.dtype).contiguous(), lse, *index, **ctx.options)
+        return None, None, dq.to(q.dtype), dk.to(q.dtype), dv.to(q.dtype), None, None
+
+
+def _native_head_dim(q, k, v, softmax_scale, attend):
+    """attend(q, k, v, softmax_scale) for packed tensors of any head dim: one other than 32, 64, 128 runs through zero-padded columns
+    with softmax_scale = 1 / sqrt(d), and the result loses them again."""
+    d = q.shape[-1] if isinstance(q, torch.Tensor) and q.dim() == 3 else 0
+    if not d or d in _NATIVE_D:
+        return attend(q, k, v, softmax_scale)
+    dp = padded_head_dim(d)
+    scale = softmax_scale if softmax_scale is not None else d ** -0.5
+    return attend(pad_head_dim(q, dp), pad_head_dim(k, dp), pad_head_dim(v, dp), scale)[..., :d]
+
+
+def _window_fn(q, k, v, softmax_scale, layout, window, sink, softcap):
+    """flash_attn_gqa under a sliding window (and sink tokens), with or without a logit cap."""
+    return _FlashAttnSideFn.apply(flash_attn_fwd_window, flash_attn_bwd_window, q, k, v, (),
+                                  dict(window=window, sink=sink, softmax_scale=softmax_scale, layout=layout, softcap=softcap))
+
+
 def bwd_workspace_window(q, k, layout="bnhd"):
     """Scratch for flash_attn_bwd_window with these tensors (fa_mi355x_bwd_window_workspace_bytes): as bwd_workspace_gqa."""
-    B, H, Hkv, N, d, _ = _check_gqa(layout, q, k, k)
-    nbytes = _lib.window().fa_mi355x_bwd_window_workspace_bytes(B, H, Hkv, N, d)
-    return torch.empty((nbytes + 3) // 4, dtype=_F32, device=q.device)
-
-
-def _window_call(lib, stem, softcap, front, B, H, Hkv, N, d, layout, softmax_scale, window, sink, dtype):
-    """The library's call ``stem`` (fa_mi355x_fwd_window, fa_mi355x_bwd_window) or, under a cap, its _softcap form: the same
-    arguments with the cap behind the window."""
-    head = (*front, B, H, Hkv, N, d, _DECODE_LAYOUTS[layout], float(softmax_scale or 0.0), window)
-    tail = (sink, dtype, _stream_ptr())
-    if softcap is None:
-        return getattr(lib, stem)(*head, *tail)
-    return getattr(lib, stem + "_softcap")(*head, softcap, *tail)
+    return _side_workspace("window", q, k, (), layout)
 
 
 def flash_attn_fwd_window(q, k, v, window, sink=None, softmax_scale=None, layout="bnhd", out=None, softcap=None):
     """Causal forward under a sliding window of ``window`` positions and ``sink`` first positions, grouped-query heads as
     flash_attn_fwd_gqa.  Returns (out fp32 in q's shape, lse (B, H, N)).  ``softcap``: logit soft-capping, as in flash_attn_gqa
     (fa_mi355x_fwd_window_softcap; lse is taken over the capped logits); None or 0: none, today's call."""
-    window, sink = _check_window_call(window, sink)
-    softcap = _check_softcap(softcap)
-    B, H, Hkv, N, d, dtype = _check_gqa(layout, q, k, v)
-    if out is not None and (out.dtype is not _F32 or out.shape != q.shape or not out.is_contiguous() or out.get_device() != q.get_device()):
-        raise ValueError("out must be a contiguous float32 tensor of q's shape")
-    lse = torch.empty((B, H, N), dtype=_F32, device=q.device)
-    if out is None:
-        out = torch.empty(q.shape, dtype=_F32, device=q.device)
-    _lib.window_check(_window_call(_lib.window(), "fa_mi355x_fwd_window", softcap, (_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse)),
-                                   B, H, Hkv, N, d, layout, softmax_scale, window, sink, dtype))
-    return out, lse
+    mask = _check_window_call(window, sink)
+    return _side_fwd("window", q, k, v, (), mask, softmax_scale, layout, out, softcap=_check_softcap(softcap))
 
 
 def flash_attn_bwd_window(q, k, v, out, out_grad, lse, window, sink=None, softmax_scale=None, layout="bnhd", workspace=None, grads=None,
@@ -849,46 +974,8 @@ def flash_attn_bwd_window(q, k, v, out, out_grad, lse, window, sink=None, softma
     """Backward of flash_attn_fwd_window.  Returns (dq in q's shape, dk, dv in k's shape), fp32; no atomics, the same bits on every
     run.  ``workspace``: bwd_workspace_window(q, k, layout); ``grads``: (dq, dk, dv) buffers to write into.  ``softcap``: the cap of
     the forward that made out and lse (fa_mi355x_bwd_window_softcap; the workspace does not depend on it)."""
-    window, sink = _check_window_call(window, sink)
-    softcap = _check_softcap(softcap)
-    B, H, Hkv, N, d, dtype = _check_gqa(layout, q, k, v, out, out_grad)
-    lib, dev = _lib.window(), q.get_device()
-    _check_buffer(lse, dev, "lse", B * H * N)
-    if workspace is not None:
-        if workspace.numel() * workspace.element_size() < lib.fa_mi355x_bwd_window_workspace_bytes(B, H, Hkv, N, d):
-            raise ValueError("workspace too small: size it with bwd_workspace_window(q, k, layout)")
-        if not workspace.is_contiguous() or workspace.get_device() != dev or workspace.data_ptr() % 256:
-            raise ValueError("workspace must be a contiguous, 256-byte aligned tensor on q's device")
-    if grads is not None:
-        for g, like in zip(grads, (q, k, v)):
-            _check_buffer(g, dev, "each of grads", like.numel())
-    if workspace is None:
-        workspace = bwd_workspace_window(q, k, layout)
-    dq, dk, dv = grads or (torch.empty(t.shape, dtype=_F32, device=q.device) for t in (q, k, v))
-    front = (_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(out_grad), _ptr(dq), _ptr(dk), _ptr(dv), _ptr(lse), _ptr(workspace))
-    _lib.window_check(_window_call(lib, "fa_mi355x_bwd_window", softcap, front, B, H, Hkv, N, d, layout, softmax_scale, window, sink,
-                                   dtype))
-    return dq, dk, dv
-
-
-class _FlashAttnWindowFn(torch.autograd.Function):
-    """flash_attn_gqa under a sliding window (and sink tokens), with or without a logit cap: the forward saves q, the unexpanded k
-    and v, o and lse; gradients are cast to the input dtype."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, softmax_scale, layout, window, sink, softcap):
-        o, lse = flash_attn_fwd_window(q, k, v, window, sink, softmax_scale, layout, softcap=softcap)
-        ctx.save_for_backward(q, k, v, o, lse)
-        ctx.args = softmax_scale, layout, window, sink, softcap
-        return o
-
-    @staticmethod
-    def backward(ctx, out_grad):
-        q, k, v, o, lse = ctx.saved_tensors
-        softmax_scale, layout, window, sink, softcap = ctx.args
-        dq, dk, dv = flash_attn_bwd_window(q, k, v, o, out_grad.to(q.dtype).contiguous(), lse, window, sink, softmax_scale, layout,
-                                           softcap=softcap)
-        return dq.to(q.dtype), dk.to(q.dtype), dv.to(q.dtype), None, None, None, None, None
+    mask = _check_window_call(window, sink)
+    return _side_bwd("window", q, k, v, out, out_grad, lse, (), mask, softmax_scale, layout, workspace, grads, _check_softcap(softcap))
 
 
 def decode_workspace(q, k_cache, layout="bnhd", block_table=None, max_pages=None, window=None, sink=None):
@@ -1432,29 +1519,42 @@ def flash_attn_ragged(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens=None, cau
 # block) off a device-side block map (libflash_attn_mi355x_varlen.so): per sequence the result is, bit for bit,
 # flash_attn_fwd_window / flash_attn_bwd_window on that sequence alone.  Rows no sequence owns come back as zeros.
 
-def _check_varlen(q, k, v, cu_seqlens, o=None, do=None):
-    """What _check_gqa checks, for packed 3-d tensors.  Returns (nseq, T, H, Hkv, d, dtype code) as the C entry points take them."""
+def _check_packed(q, k, v, cu_q, cu_k, o=None, do=None, *, one_array):
+    """What _check_gqa checks, for packed 3-d tensors.  ``one_array``: the causal packed calls, where one cu_seqlens serves queries
+    and keys and q and k agree on (T, d); otherwise the bidirectional ones, with a row count and an array for either side.  Returns
+    (nseq, Tq, Tk, H, Hkv, d, dtype code)."""
+    tq, tk, wrapper = ("T", "T", "flash_attn_varlen") if one_array else ("Tq", "Tk", "flash_attn_varlen_bidir")
     _require_gpu(q, "device_ops")
     dtype = _dtype_code(q)
     if q.dim() != 3 or k.dim() != 3:
-        raise ValueError("expected packed 3-d tensors: q (T, H, d) and k, v (T, Hkv, d)")
+        raise ValueError(f"expected packed 3-d tensors: q ({tq}, H, d) and k, v ({tk}, Hkv, d)")
     dev = q.get_device()
     if v.shape != k.shape:
         raise ValueError("k and v must have one shape")
     for t in (k, v):
         if not t.is_cuda or t.dtype != q.dtype or t.get_device() != dev:
             raise ValueError("q, k, v must be GPU tensors of one dtype on one device")
-    (T, H, d), (Tk, Hkv, dk) = q.shape, k.shape
-    if (T, d) != (Tk, dk):
-        raise ValueError(f"q and k disagree on (T, d): {(T, d)} vs {(Tk, dk)} (one cu_seqlens serves queries and keys)")
-    if T < 1:
-        raise ValueError("the packed batch is empty: T must be at least 1")
+    (Tq, H, d), (Tk, Hkv, dk) = q.shape, k.shape
+    if one_array:
+        if (Tq, d) != (Tk, dk):
+            raise ValueError(f"q and k disagree on (T, d): {(Tq, d)} vs {(Tk, dk)} (one cu_seqlens serves queries and keys)")
+        if Tq < 1:
+            raise ValueError("the packed batch is empty: T must be at least 1")
+    else:
+        if d != dk:
+            raise ValueError(f"q and k disagree on the head dim: {d} vs {dk}")
+        if Tq < 1 or Tk < 1:
+            raise ValueError("the packed batch is empty: Tq and Tk must be at least 1")
     if Hkv <= 0 or H % Hkv:
         raise ValueError(f"q's {H} heads must be a multiple of k's {Hkv}")
     if d not in _NATIVE_D:
-        raise ValueError("the packed calls need a native head dim (32, 64, 128): flash_attn_varlen pads, or pad q, k and v "
+        raise ValueError(f"the packed calls need a native head dim (32, 64, 128): {wrapper} pads, or pad q, k and v "
                          "(pad_head_dim) and pass softmax_scale")
-    _check_cu(cu_seqlens, None, q.device)
+    _check_cu(cu_q, None, q.device)
+    if cu_k is not cu_q:
+        _check_cu(cu_k, None, q.device)
+        if cu_k.shape != cu_q.shape:
+            raise ValueError("cu_seqlens_q and cu_seqlens_k must have one length: the same sequences, counted in q and in k")
     if do is not None and (do.shape != q.shape or do.dtype != q.dtype or do.get_device() != dev):
         raise ValueError("out_grad must share q's shape, dtype and device")
     for t in (q, k, v) + ((do,) if do is not None else ()):
@@ -1462,7 +1562,7 @@ def _check_varlen(q, k, v, cu_seqlens, o=None, do=None):
             raise ValueError("tensors must be contiguous")
     if o is not None and (o.dtype is not _F32 or o.shape != q.shape or not o.is_contiguous() or o.get_device() != dev):
         raise ValueError("out must be the forward's contiguous float32 output")
-    return cu_seqlens.shape[0] - 1, T, H, Hkv, d, dtype
+    return cu_q.shape[0] - 1, Tq, Tk, H, Hkv, d, dtype
 
 
 def _check_varlen_mask(window, sink):
@@ -1474,22 +1574,12 @@ def _check_varlen_mask(window, sink):
     return window or 0, sink or 0
 
 
-def _check_varlen_workspace(workspace, nbytes, dev):
-    if workspace.numel() * workspace.element_size() < nbytes:
-        raise ValueError("workspace too small: size it with varlen_workspace(q, k, cu_seqlens)")
-    if not workspace.is_contiguous() or workspace.get_device() != dev or workspace.data_ptr() % 256:
-        raise ValueError("workspace must be a contiguous, 256-byte aligned tensor on q's device")
-
-
 def varlen_workspace(q, k, cu_seqlens, backward=True):
     """Scratch for flash_attn_varlen_bwd (``backward=False``: for flash_attn_varlen_fwd alone) with these tensors
     (fa_mi355x_bwd_varlen_workspace_bytes / _fwd_): the block maps, the row constants and, when k has fewer heads than q, the dK and
     dV of every query head.  Never empty: the maps live there.  A pure function of the SHAPES (cu_seqlens's contents are not read):
     allocate once, reuse every step.  A backward workspace also serves the forward."""
-    nseq, T, H, Hkv, d, _ = _check_varlen(q, k, k, cu_seqlens)
-    lib = _lib.varlen()
-    nbytes = (lib.fa_mi355x_bwd_varlen_workspace_bytes if backward else lib.fa_mi355x_fwd_varlen_workspace_bytes)(nseq, T, H, Hkv, d)
-    return torch.empty((nbytes + 3) // 4, dtype=_F32, device=q.device)
+    return _side_workspace("varlen", q, k, (cu_seqlens,), backward=backward)
 
 
 def flash_attn_varlen_fwd(q, k, v, cu_seqlens, window=None, sink=None, softmax_scale=None, out=None, workspace=None, lse=None):
@@ -1497,65 +1587,16 @@ def flash_attn_varlen_fwd(q, k, v, cu_seqlens, window=None, sink=None, softmax_s
     (nseq + 1,) on q's device.  ``window`` = W, ``sink`` = S: the sliding-window mask within every sequence (None or 0: none).
     Returns (out fp32 (T, H, d), lse (H, T)); rows no sequence owns are zero in both.  ``out``, ``lse``: buffers to write into;
     ``workspace``: varlen_workspace(q, k, cu_seqlens) (with all three given the call allocates nothing: it can be captured in a graph)."""
-    window, sink = _check_varlen_mask(window, sink)
-    nseq, T, H, Hkv, d, dtype = _check_varlen(q, k, v, cu_seqlens)
-    lib, dev = _lib.varlen(), q.get_device()
-    if out is not None and (out.dtype is not _F32 or out.shape != q.shape or not out.is_contiguous() or out.get_device() != dev):
-        raise ValueError("out must be a contiguous float32 tensor of q's shape")
-    if workspace is not None:
-        _check_varlen_workspace(workspace, lib.fa_mi355x_fwd_varlen_workspace_bytes(nseq, T, H, Hkv, d), dev)
-    else:
-        workspace = varlen_workspace(q, k, cu_seqlens, backward=False)
-    if lse is not None:
-        _check_buffer(lse, dev, "lse", H * T)
-    else:
-        lse = torch.empty((H, T), dtype=_F32, device=q.device)
-    if out is None:
-        out = torch.empty(q.shape, dtype=_F32, device=q.device)
-    _lib.varlen_check(lib.fa_mi355x_fwd_varlen(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(cu_seqlens), _ptr(workspace), nseq, T,
-                                               H, Hkv, d, float(softmax_scale or 0.0), window, sink, dtype, _stream_ptr()))
-    return out, lse
+    mask = _check_varlen_mask(window, sink)
+    return _side_fwd("varlen", q, k, v, (cu_seqlens,), mask, softmax_scale, out=out, lse=lse, workspace=workspace)
 
 
 def flash_attn_varlen_bwd(q, k, v, out, out_grad, lse, cu_seqlens, window=None, sink=None, softmax_scale=None, workspace=None, grads=None):
     """Backward of flash_attn_varlen_fwd (fa_mi355x_bwd_varlen).  Returns (dq in q's shape, dk, dv in k's shape), fp32, zero in the
     rows no sequence owns; no atomics, the same bits on every run.  ``workspace``: varlen_workspace(q, k, cu_seqlens); ``grads``:
     (dq, dk, dv) buffers to write into."""
-    window, sink = _check_varlen_mask(window, sink)
-    nseq, T, H, Hkv, d, dtype = _check_varlen(q, k, v, cu_seqlens, out, out_grad)
-    lib, dev = _lib.varlen(), q.get_device()
-    _check_buffer(lse, dev, "lse", H * T)
-    if workspace is not None:
-        _check_varlen_workspace(workspace, lib.fa_mi355x_bwd_varlen_workspace_bytes(nseq, T, H, Hkv, d), dev)
-    if grads is not None:
-        for g, like in zip(grads, (q, k, v)):
-            _check_buffer(g, dev, "each of grads", like.numel())
-    if workspace is None:
-        workspace = varlen_workspace(q, k, cu_seqlens)
-    dq, dk, dv = grads or (torch.empty(t.shape, dtype=_F32, device=q.device) for t in (q, k, v))
-    _lib.varlen_check(lib.fa_mi355x_bwd_varlen(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(out_grad), _ptr(dq), _ptr(dk), _ptr(dv),
-                                               _ptr(lse), _ptr(cu_seqlens), _ptr(workspace), nseq, T, H, Hkv, d,
-                                               float(softmax_scale or 0.0), window, sink, dtype, _stream_ptr()))
-    return dq, dk, dv
-
-
-class _FlashAttnVarlenFn(torch.autograd.Function):
-    """flash_attn_varlen under autograd: the forward saves q, the unexpanded k and v, o, lse and cu_seqlens; gradients are cast to
-    the input dtype."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, cu_seqlens, softmax_scale, window, sink):
-        o, lse = flash_attn_varlen_fwd(q, k, v, cu_seqlens, window, sink, softmax_scale)
-        ctx.save_for_backward(q, k, v, o, lse, cu_seqlens)
-        ctx.args = softmax_scale, window, sink
-        return o
-
-    @staticmethod
-    def backward(ctx, out_grad):
-        q, k, v, o, lse, cu_seqlens = ctx.saved_tensors
-        softmax_scale, window, sink = ctx.args
-        dq, dk, dv = flash_attn_varlen_bwd(q, k, v, o, out_grad.to(q.dtype).contiguous(), lse, cu_seqlens, window, sink, softmax_scale)
-        return dq.to(q.dtype), dk.to(q.dtype), dv.to(q.dtype), None, None, None, None
+    mask = _check_varlen_mask(window, sink)
+    return _side_bwd("varlen", q, k, v, out, out_grad, lse, (cu_seqlens,), mask, softmax_scale, workspace=workspace, grads=grads)
 
 
 def flash_attn_varlen(q, k, v, cu_seqlens, causal=True, softmax_scale=None, window=None, sink=None):
@@ -1567,13 +1608,8 @@ def flash_attn_varlen(q, k, v, cu_seqlens, causal=True, softmax_scale=None, wind
         raise ValueError("non-causal packed attention is not built: flash_attn_varlen is causal only (causal=False); "
                          "flash_attn_varlen_bidir is the bidirectional packed call")
     window, sink = _check_varlen_mask(window, sink)
-    d = q.shape[-1] if isinstance(q, torch.Tensor) and q.dim() == 3 else 0
-    if d and d not in _NATIVE_D:
-        dp = padded_head_dim(d)
-        scale = softmax_scale if softmax_scale is not None else d ** -0.5
-        o = _FlashAttnVarlenFn.apply(pad_head_dim(q, dp), pad_head_dim(k, dp), pad_head_dim(v, dp), cu_seqlens, scale, window, sink)
-        return o[..., :d]
-    return _FlashAttnVarlenFn.apply(q, k, v, cu_seqlens, softmax_scale, window, sink)
+    return _native_head_dim(q, k, v, softmax_scale, lambda q, k, v, scale: _FlashAttnSideFn.apply(
+        flash_attn_varlen_fwd, flash_attn_varlen_bwd, q, k, v, (cu_seqlens,), dict(window=window, sink=sink, softmax_scale=scale)))
 
 
 def _rotary_varlen_call(x, y, cos, sin, cu_seqlens, interleaved, inverse):
@@ -1634,50 +1670,6 @@ def apply_rotary_varlen(x, cos, sin, cu_seqlens, interleaved=False, inverse=Fals
 # every query of a sequence admits every key of it: encoders on packed documents (one array for both) and cross-attention.  Kernels
 # of their own (libflash_attn_mi355x_bidir.so).  Query rows of a keyless sequence and rows no sequence owns come back as zeros.
 
-def _check_bidir(q, k, v, cu_seqlens_q, cu_seqlens_k, o=None, do=None):
-    """What _check_varlen checks, for two row counts.  Returns (nseq, Tq, Tk, H, Hkv, d, dtype code) as the C entry points take them."""
-    _require_gpu(q, "device_ops")
-    dtype = _dtype_code(q)
-    if q.dim() != 3 or k.dim() != 3:
-        raise ValueError("expected packed 3-d tensors: q (Tq, H, d) and k, v (Tk, Hkv, d)")
-    dev = q.get_device()
-    if v.shape != k.shape:
-        raise ValueError("k and v must have one shape")
-    for t in (k, v):
-        if not t.is_cuda or t.dtype != q.dtype or t.get_device() != dev:
-            raise ValueError("q, k, v must be GPU tensors of one dtype on one device")
-    (Tq, H, d), (Tk, Hkv, dk) = q.shape, k.shape
-    if d != dk:
-        raise ValueError(f"q and k disagree on the head dim: {d} vs {dk}")
-    if Tq < 1 or Tk < 1:
-        raise ValueError("the packed batch is empty: Tq and Tk must be at least 1")
-    if Hkv <= 0 or H % Hkv:
-        raise ValueError(f"q's {H} heads must be a multiple of k's {Hkv}")
-    if d not in _NATIVE_D:
-        raise ValueError("the packed calls need a native head dim (32, 64, 128): flash_attn_varlen_bidir pads, or pad q, k and v "
-                         "(pad_head_dim) and pass softmax_scale")
-    _check_cu(cu_seqlens_q, None, q.device)
-    if cu_seqlens_k is not cu_seqlens_q:
-        _check_cu(cu_seqlens_k, None, q.device)
-        if cu_seqlens_k.shape != cu_seqlens_q.shape:
-            raise ValueError("cu_seqlens_q and cu_seqlens_k must have one length: the same sequences, counted in q and in k")
-    if do is not None and (do.shape != q.shape or do.dtype != q.dtype or do.get_device() != dev):
-        raise ValueError("out_grad must share q's shape, dtype and device")
-    for t in (q, k, v) + ((do,) if do is not None else ()):
-        if not t.is_contiguous():
-            raise ValueError("tensors must be contiguous")
-    if o is not None and (o.dtype is not _F32 or o.shape != q.shape or not o.is_contiguous() or o.get_device() != dev):
-        raise ValueError("out must be the forward's contiguous float32 output")
-    return cu_seqlens_q.shape[0] - 1, Tq, Tk, H, Hkv, d, dtype
-
-
-def _check_bidir_workspace(workspace, nbytes, dev):
-    if workspace.numel() * workspace.element_size() < nbytes:
-        raise ValueError("workspace too small: size it with bidir_workspace(q, k, cu_seqlens_q, cu_seqlens_k)")
-    if not workspace.is_contiguous() or workspace.get_device() != dev or workspace.data_ptr() % 256:
-        raise ValueError("workspace must be a contiguous, 256-byte aligned tensor on q's device")
-
-
 def _self_cu(q, k, cu_seqlens_q, cu_seqlens_k):
     """cu_seqlens_k=None: self-attention, one array for both buffers, and k has q's rows."""
     if cu_seqlens_k is not None:
@@ -1692,11 +1684,7 @@ def bidir_workspace(q, k, cu_seqlens_q, cu_seqlens_k=None, backward=True):
     (fa_mi355x_bwd_bidir_workspace_bytes / _fwd_): the two block maps, the row constants and, when k has fewer heads than q, the dK
     and dV of every query head.  Never empty: the maps live there.  A pure function of the SHAPES (the arrays' contents are not
     read): allocate once, reuse every step.  A backward workspace also serves the forward."""
-    cu_seqlens_k = _self_cu(q, k, cu_seqlens_q, cu_seqlens_k)
-    nseq, Tq, Tk, H, Hkv, d, _ = _check_bidir(q, k, k, cu_seqlens_q, cu_seqlens_k)
-    lib = _lib.bidir()
-    nbytes = (lib.fa_mi355x_bwd_bidir_workspace_bytes if backward else lib.fa_mi355x_fwd_bidir_workspace_bytes)(nseq, Tq, Tk, H, Hkv, d)
-    return torch.empty((nbytes + 3) // 4, dtype=_F32, device=q.device)
+    return _side_workspace("bidir", q, k, (cu_seqlens_q, _self_cu(q, k, cu_seqlens_q, cu_seqlens_k)), backward=backward)
 
 
 def flash_attn_varlen_bidir_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k=None, softmax_scale=None, out=None, workspace=None, lse=None):
@@ -1704,24 +1692,8 @@ def flash_attn_varlen_bidir_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k=None, softma
     int32 (nseq + 1,) on q's device (``cu_seqlens_k=None``: self-attention, the same array).  Returns (out fp32 (Tq, H, d), lse
     (H, Tq)); query rows of a keyless sequence and rows no sequence owns are zero in both.  ``out``, ``lse``: buffers to write into;
     ``workspace``: bidir_workspace(...) (with all three given the call allocates nothing: it can be captured in a graph)."""
-    cu_seqlens_k = _self_cu(q, k, cu_seqlens_q, cu_seqlens_k)
-    nseq, Tq, Tk, H, Hkv, d, dtype = _check_bidir(q, k, v, cu_seqlens_q, cu_seqlens_k)
-    lib, dev = _lib.bidir(), q.get_device()
-    if out is not None and (out.dtype is not _F32 or out.shape != q.shape or not out.is_contiguous() or out.get_device() != dev):
-        raise ValueError("out must be a contiguous float32 tensor of q's shape")
-    if workspace is not None:
-        _check_bidir_workspace(workspace, lib.fa_mi355x_fwd_bidir_workspace_bytes(nseq, Tq, Tk, H, Hkv, d), dev)
-    else:
-        workspace = bidir_workspace(q, k, cu_seqlens_q, cu_seqlens_k, backward=False)
-    if lse is not None:
-        _check_buffer(lse, dev, "lse", H * Tq)
-    else:
-        lse = torch.empty((H, Tq), dtype=_F32, device=q.device)
-    if out is None:
-        out = torch.empty(q.shape, dtype=_F32, device=q.device)
-    _lib.bidir_check(lib.fa_mi355x_fwd_bidir(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(cu_seqlens_q), _ptr(cu_seqlens_k),
-                                             _ptr(workspace), nseq, Tq, Tk, H, Hkv, d, float(softmax_scale or 0.0), dtype, _stream_ptr()))
-    return out, lse
+    index = (cu_seqlens_q, _self_cu(q, k, cu_seqlens_q, cu_seqlens_k))
+    return _side_fwd("bidir", q, k, v, index, (), softmax_scale, out=out, lse=lse, workspace=workspace)
 
 
 def flash_attn_varlen_bidir_bwd(q, k, v, out, out_grad, lse, cu_seqlens_q, cu_seqlens_k=None, softmax_scale=None, workspace=None,
@@ -1729,41 +1701,8 @@ def flash_attn_varlen_bidir_bwd(q, k, v, out, out_grad, lse, cu_seqlens_q, cu_se
     """Backward of flash_attn_varlen_bidir_fwd (fa_mi355x_bwd_bidir).  Returns (dq in q's shape, dk, dv in k's shape), fp32; zero in
     the query rows of a keyless sequence, the key rows of a sequence without queries and the rows no sequence owns; no atomics, the
     same bits on every run.  ``workspace``: bidir_workspace(...); ``grads``: (dq, dk, dv) buffers to write into."""
-    cu_seqlens_k = _self_cu(q, k, cu_seqlens_q, cu_seqlens_k)
-    nseq, Tq, Tk, H, Hkv, d, dtype = _check_bidir(q, k, v, cu_seqlens_q, cu_seqlens_k, out, out_grad)
-    lib, dev = _lib.bidir(), q.get_device()
-    _check_buffer(lse, dev, "lse", H * Tq)
-    if workspace is not None:
-        _check_bidir_workspace(workspace, lib.fa_mi355x_bwd_bidir_workspace_bytes(nseq, Tq, Tk, H, Hkv, d), dev)
-    if grads is not None:
-        for g, like in zip(grads, (q, k, v)):
-            _check_buffer(g, dev, "each of grads", like.numel())
-    if workspace is None:
-        workspace = bidir_workspace(q, k, cu_seqlens_q, cu_seqlens_k)
-    dq, dk, dv = grads or (torch.empty(t.shape, dtype=_F32, device=q.device) for t in (q, k, v))
-    _lib.bidir_check(lib.fa_mi355x_bwd_bidir(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(out_grad), _ptr(dq), _ptr(dk), _ptr(dv),
-                                             _ptr(lse), _ptr(cu_seqlens_q), _ptr(cu_seqlens_k), _ptr(workspace), nseq, Tq, Tk, H, Hkv, d,
-                                             float(softmax_scale or 0.0), dtype, _stream_ptr()))
-    return dq, dk, dv
-
-
-class _FlashAttnBidirFn(torch.autograd.Function):
-    """flash_attn_varlen_bidir under autograd: the forward saves q, the unexpanded k and v, o, lse and both cu arrays; gradients are
-    cast to the input dtypes."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, cu_seqlens_q, cu_seqlens_k, softmax_scale):
-        o, lse = flash_attn_varlen_bidir_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, softmax_scale)
-        ctx.save_for_backward(q, k, v, o, lse, cu_seqlens_q, cu_seqlens_k)
-        ctx.softmax_scale = softmax_scale
-        return o
-
-    @staticmethod
-    def backward(ctx, out_grad):
-        q, k, v, o, lse, cu_seqlens_q, cu_seqlens_k = ctx.saved_tensors
-        dq, dk, dv = flash_attn_varlen_bidir_bwd(q, k, v, o, out_grad.to(q.dtype).contiguous(), lse, cu_seqlens_q, cu_seqlens_k,
-                                                 ctx.softmax_scale)
-        return dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype), None, None, None
+    index = (cu_seqlens_q, _self_cu(q, k, cu_seqlens_q, cu_seqlens_k))
+    return _side_bwd("bidir", q, k, v, out, out_grad, lse, index, (), softmax_scale, workspace=workspace, grads=grads)
 
 
 def flash_attn_varlen_bidir(q, k, v, cu_seqlens_q, cu_seqlens_k=None, softmax_scale=None):
@@ -1772,14 +1711,9 @@ def flash_attn_varlen_bidir(q, k, v, cu_seqlens_q, cu_seqlens_k=None, softmax_sc
     out fp32 (Tq, H, d); q.grad in q's shape and dtype, k.grad and v.grad in k's.  A head dim other than 32, 64, 128 runs through
     zero-padded columns with softmax_scale = 1 / sqrt(d).  Query rows of a keyless sequence and rows no sequence owns give zeros and
     take a zero gradient."""
-    cu_seqlens_k = _self_cu(q, k, cu_seqlens_q, cu_seqlens_k)
-    d = q.shape[-1] if isinstance(q, torch.Tensor) and q.dim() == 3 else 0
-    if d and d not in _NATIVE_D:
-        dp = padded_head_dim(d)
-        scale = softmax_scale if softmax_scale is not None else d ** -0.5
-        o = _FlashAttnBidirFn.apply(pad_head_dim(q, dp), pad_head_dim(k, dp), pad_head_dim(v, dp), cu_seqlens_q, cu_seqlens_k, scale)
-        return o[..., :d]
-    return _FlashAttnBidirFn.apply(q, k, v, cu_seqlens_q, cu_seqlens_k, softmax_scale)
+    index = (cu_seqlens_q, _self_cu(q, k, cu_seqlens_q, cu_seqlens_k))
+    return _native_head_dim(q, k, v, softmax_scale, lambda q, k, v, scale: _FlashAttnSideFn.apply(
+        flash_attn_varlen_bidir_fwd, flash_attn_varlen_bidir_bwd, q, k, v, index, dict(softmax_scale=scale)))
 
 
 def flash_attn_cross(q, k, v, softmax_scale=None):

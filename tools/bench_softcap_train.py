@@ -36,8 +36,8 @@ def sides_of(g, N, W):
     dof = do.float()
     Wc = W or N
 
-    def attend(tq, tk, tv, cap):   # (the autograd Function flash_attn_gqa routes a windowed or capped call to)
-        return device_ops._FlashAttnWindowFn.apply(tq, tk, tv, None, "bnhd", Wc, 0, cap)
+    def attend(tq, tk, tv, cap):   # (the autograd path flash_attn_gqa routes a windowed or capped call to)
+        return device_ops._window_fn(tq, tk, tv, None, "bnhd", Wc, 0, cap)
 
     def fwd(op):
         def call():
