@@ -96,6 +96,7 @@ CORE_ABI = {
     "fa_mi355x_fwd_padded": (_i, [_vp] * 6 + [_i] * 7 + [_vp]),
     "fa_mi355x_bwd_padded": (_i, [_vp] * 11 + [_i] * 7 + [_vp]),
     "fa_mi355x_plan": (_i, [_i] * 7 + [_ip, _i, _s, _sz]),
+    "fa_mi355x_plan_builds": (_i, [_i] * 7 + [_ip, _i, _s, _sz]),
     "fa_mi355x_fwd_layout": (_i, [_vp] * 6 + [_i] * 8 + [_vp]),
     "fa_mi355x_bwd_layout": (_i, [_vp] * 11 + [_i] * 8 + [_vp]),
     "fa_mi355x_fwd_masked": (_i, [_vp] * 7 + [_i] * 8 + [_vp]),
@@ -337,6 +338,11 @@ def plan(batch, n, d, causal, variant, dtype, stages, opts=None):
     """Kernel names, in launch order, of the call with these arguments (fa_mi355x_plan: the library's own dispatch code with the
     launches skipped).  stages = 0: the forward; otherwise the backward stage mask."""
     return _plan(core().fa_mi355x_plan, (batch, n, d), causal, variant, dtype, stages, opts)
+
+
+def plan_builds(batch, n, d, causal, variant, dtype, stages, opts=None):
+    """``plan`` with one name per build instead of one per kernel family (fa_mi355x_plan_builds), e.g. DKDV_SLOT64_TILED."""
+    return _plan(core().fa_mi355x_plan_builds, (batch, n, d), causal, variant, dtype, stages, opts)
 
 
 def plan_gqa(B, H, Hkv, n, d, causal, variant, dtype, stages, opts=None):

@@ -43,7 +43,8 @@ constexpr double FWD_SPLITK_MAX_WGS_PER_CU = 0.5, FWD_SPLITK_MAX_WGS_PER_CU_CAUS
 inline bool d_supported(int d) { return d == 32 || d == 64 || d == 128; }
 inline int d_padded(int d) { return d <= 32 ? 32 : (d <= 64 ? 64 : 128); }
 
-// Per-call kernel selection (fa_mi355x_fwd_ex / fa_mi355x_bwd_ex; every other entry point runs the defaults): [0] dK/dV geometry,
+// Per-call kernel selection (fa_mi355x_fwd_ex / fa_mi355x_bwd_ex; every other entry point runs the defaults): [0] dK/dV geometry
+// (6 = the 8-wave slot builds wherever the 64-keys-per-wave build would run, 7 = that build wherever it is valid: select_dkdv),
 // [1] forward kernel, [2] dQ kernel, [3] reserved, [4] preprocess / fp32 one-pass backward, [5] 1 = one head per workgroup in the
 // tiled slot builds, [6] reserved, [7] causal block order.  Only values whose kernels give correct results are accepted (parse_opts).
 // [8] where tau*log2(e) is applied (see select_call): 0 = by the call's scale guard when it has one, else fp32 scaling; 1 = the caller
@@ -57,7 +58,7 @@ int parse_opts(const int* opts, int nopts, Tun& t) {
   if (nopts < 0 || nopts > NTUN || (nopts > 0 && !opts)) return set_err(FA_ERR_BAD_ARG, "bad options array");
   for (int i = 0; i < nopts; ++i) t.v[i] = opts[i];
   // (the values that lost their A/B were retired with their kernels: DESIGN.md section 3, "Retired experiments")
-  static const int allowed[NTUN][7] = {{0, 3, 4, 5, -1}, {0, 2, 3, 4, -1}, {0, 2, 3, -1}, {0, -1}, {0, 1, 4, 5, -1}, {0, 1, -1}, {0, -1}, {0, 1, 2, -1},
+  static const int allowed[NTUN][7] = {{0, 3, 4, 5, 6, 7, -1}, {0, 2, 3, 4, -1}, {0, 2, 3, -1}, {0, -1}, {0, 1, 4, 5, -1}, {0, 1, -1}, {0, -1}, {0, 1, 2, -1},
                                        {0, 1, 2, 3, -1}, {0, 1, -1}};
   for (int i = 0; i < NTUN; ++i) {
     bool ok = false;
@@ -192,7 +193,8 @@ int launch_scale_guard(const void* q, const void* k, long rows, long krows, int 
   X(DQ_WAVE8, "bwd_dq_kernel")                                                                                                       \
   X(DQ_SLOT_CAUSAL, "bwd_dq_slot_kernel") X(DQ_SLOT_TILED, "bwd_dq_slot_kernel") X(DQ_SLOT_WHOLE, "bwd_dq_slot_kernel")              \
   X(DQ_SLOT_MASKED, "bwd_dq_slot_kernel")                                                                                            \
-  X(DKDV_SLOT_TILED, "bwd_dkdv_slot_kernel") X(DKDV_SLOT, "bwd_dkdv_slot_kernel") X(DKDV_SLOT_CAUSAL, "bwd_dkdv_slot_kernel")        \
+  X(DKDV_SLOT, "bwd_dkdv_slot_kernel") X(DKDV_SLOT_CAUSAL, "bwd_dkdv_slot_kernel")                                                   \
+  X(DKDV_SLOT64_TILED, "bwd_dkdv_slot_kernel")   /* fa::bwd_dkdv_slot64_kernel: the family's 4-wave, 64-keys-per-wave build */         \
   X(DKDV_CARE_DROP, "bwd_dkdv_kernel") X(DKDV_CARE, "bwd_dkdv_kernel") X(DKDV_DROP_F32, "bwd_dkdv_kernel")                           \
   X(DKDV_CARE_MAIN, "bwd_dkdv_kernel") X(DKDV_PAIRED, "bwd_dkdv_kernel") X(DKDV_PAIRED_M3, "bwd_dkdv_kernel")                        \
   X(DKDV_PLAIN, "bwd_dkdv_kernel") X(DKDV_F32_64, "bwd_dkdv_kernel")                                                                 \
@@ -207,6 +209,9 @@ enum Kern : int { FA_KERNS(X) };
 #undef X
 #define X(id, name) name,
 constexpr const char* KERN_NAME[] = {FA_KERNS(X)};
+#undef X
+#define X(id, name) #id,
+constexpr const char* BUILD_NAME[] = {FA_KERNS(X)};   // fa_mi355x_plan_builds: one name per build, where KERN_NAME has one per family
 #undef X
 
 struct Step {
@@ -470,12 +475,21 @@ Selection select_dkdv(const Call& c) {
     // The continuous slot pipeline (no drain at stage boundaries, three-slot LDS-DMA ring) carries both scalings and picks one per
     // launch (Layout::scale_sel): no twin launch.  Option 0 = 4: the compiler-interleaved phased kernel below.
     const bool plain = !c.lay.drop_thr && !c.lay.kmask;
-    if (!causal && tun.v[0] == 0 && plain && N >= 64) {
+    if (!causal && (tun.v[0] == 0 || tun.v[0] == 6 || tun.v[0] == 7) && plain && N >= 64) {
       // d = 64, non-causal default: the continuous slot pipeline; rows thinned by a key mask or N < 64 go to the kernel below, whose
       // per-sub-slice path splits P and dS.  Key block kb of several consecutive heads per workgroup: head_tiles
       const int nkb = (N + 255) / 256, tiles = head_tiles(c, nkb);
-      if (tiles > 1) s.add(DKDV_SLOT_TILED, (batch / tiles) * nkb, 512, nkb).tiles = tiles;
-      else s.add(DKDV_SLOT, batch * nkb, 512, nkb);
+      // The 64-keys-per-wave build (fa_bwd_dkdv64.h: four waves, one per SIMD, half the LDS reads per MFMA, bitwise the same dK, dV)
+      // takes every launch the tiled 8-wave build would take: those give every CU a workgroup, and with one 256-thread workgroup
+      // per CU nothing else fills a CU that has none.  It replaced the 8-wave several-heads build (1.8 % of the step at the metric
+      // shape, bitwise the same).  Option 0 = 6 runs the 8-wave one-head build there instead (for A/B runs and tests in one process);
+      // 7 runs the 64-key build wherever it is valid (N a multiple of 256, ungrouped heads), in head groups of 4 where head_tiles
+      // forms none, the last one partial.
+      const bool can64 = N % 256 == 0 && c.lay.G == 1;
+      if (can64 && (tun.v[0] == 7 || (tun.v[0] == 0 && tiles > 1))) {
+        const int t64 = tiles > 1 ? tiles : (c.tun.v[5] ? 1 : 4);
+        s.add(DKDV_SLOT64_TILED, ((batch + t64 - 1) / t64) * nkb, 256, nkb).tiles = t64;
+      } else s.add(DKDV_SLOT, batch * nkb, 512, nkb);
       return s;
     }
     if (causal && plain && N % 256 == 0 && (tun.v[0] == 5 || (tun.v[0] == 0 && batch * (N / 256) >= 128))) {   // (tuning key 0 = 5 forces it)
@@ -629,8 +643,9 @@ int execute(const Call& c, const Selection& sel) {
       case DQ_SLOT_MASKED:
         if constexpr (BF && D == 64) FA_DQ_SLOT();
         break;
-      case DKDV_SLOT_TILED:
-        if constexpr (BF && D == 64) FA_DKDV_SLOT(false, true);
+      case DKDV_SLOT64_TILED:
+        if constexpr (BF && D == 64)
+          FA_GO((fa::bwd_dkdv_slot64_kernel<T, 64>), FA_QKV, (const T*)c.dout, c.nl2(), c.delta(), c.dk, c.dv, N, s.nb, batch, lay, c.tau);
         break;
       case DKDV_SLOT:
         if constexpr (BF && D == 64) FA_DKDV_SLOT();
@@ -1090,13 +1105,14 @@ Call plan_call(int B, int N, int d, int causal, int variant, int dtype, int stag
   c.nopts = nopts;
   return c;
 }
-int plan(Call c, char* out, size_t n) {
+int plan(Call c, char* out, size_t n, bool builds = false) {
   if (int rc = validate(c)) return rc;
   if (!out || n == 0) return set_err(FA_ERR_BAD_ARG, "null output buffer");
   const Selection sel = select_any(c, true);   // built exactly as a real call builds it
   std::string joined;
   for (int i = 0; i < sel.n; ++i)
-    if (const char* name = KERN_NAME[sel.steps[i].kern]) joined += (joined.empty() ? "" : ";") + std::string(name);
+    if (const char* name = KERN_NAME[sel.steps[i].kern])
+      joined += (joined.empty() ? "" : ";") + std::string(builds ? BUILD_NAME[sel.steps[i].kern] : name);
   if (joined.size() + 1 > n) return set_err(FA_ERR_BAD_ARG, "plan buffer too small");
   memcpy(out, joined.c_str(), joined.size() + 1);
   return FA_OK;
@@ -1166,6 +1182,11 @@ int fa_mi355x_measure_mfma_peak(double min_ms, double* tflops, double* clock_ghz
 int fa_mi355x_plan(int batch, int N, int d, int causal, int variant, int dtype, int stages, const int* opts, int nopts, char* out,
                    size_t n) {
   return plan(plan_call(batch, N, d, causal, variant, dtype, stages, opts, nopts), out, n);
+}
+
+int fa_mi355x_plan_builds(int batch, int N, int d, int causal, int variant, int dtype, int stages, const int* opts, int nopts,
+                          char* out, size_t n) {
+  return plan(plan_call(batch, N, d, causal, variant, dtype, stages, opts, nopts), out, n, true);
 }
 
 int fa_mi355x_plan_gqa(int B, int H, int Hkv, int N, int d, int causal, int variant, int dtype, int stages, const int* opts,

@@ -140,6 +140,51 @@ template <> struct Atom<bf16_t> {
 };
 
 // ---------------------------------------------------------------------------------------------
+// The same MFMA with EXPLICIT REGISTER CLASSES (inline asm), for kernels that run one wave per SIMD on the whole 512-entry file: the
+// lane-stationary operands and the long-lived accumulators live in AGPRs for a whole sweep, the streamed operand and every tile the
+// VALU touches in arch VGPRs.  With the builtin hipcc decides the class itself and either copies AGPR-resident fragments back in
+// front of every MFMA or gives up the split; with the constraint spelled out it has nothing to decide.  Used by
+// bwd_dkdv_slot64_kernel only: every other kernel keeps the builtin.
+// hipcc pads no hazard of an asm statement, so the CALLER keeps these distances (in the slot schedules they hold by construction):
+//   * a VGPR operand written by VALU is not read by the MFMA that follows it directly (two wait states: one full slot in between);
+//   * a tile written by vs / vs_c is read by VALU at least 12 wait states later (a later period); ag's accumulators are read by
+//     anything but the next ag on the same tile only behind mma_drain.
+// ---------------------------------------------------------------------------------------------
+struct MfmaRC {
+  typedef bf16x8 frag;
+  // AGPR accumulator += VGPR streamed x VGPR packed (dV^T += dO^T P, dK^T += Q^T dS)
+  static FA_DEV void ag(f32x16& acc, const frag& a, const frag& b) {
+    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
+  }
+  // AGPR accumulator = a x b + 0: the zero accumulator input (with zero fragments: how a sweep clears its tiles, a definition in
+  // AGPRs).  Off the hot path, so it carries its own two wait states behind whatever wrote a and b.
+  static FA_DEV void ag_z(f32x16& acc, const frag& a, const frag& b) {
+    asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=a"(acc) : "v"(a), "v"(b));
+  }
+  // VGPR tile += VGPR streamed x AGPR lane-stationary (S' and dP' chains against the K / V fragments)
+  static FA_DEV void vs(f32x16& d, const frag& a, const frag& b_agpr) {
+    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "a"(b_agpr));
+  }
+  // VGPR tile = a x b + c0, c0 (a VGPR tile: the row constants) left intact
+  static FA_DEV void vs_c(f32x16& d, const frag& a, const frag& b_agpr, const f32x16& c0) {
+    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %3" : "=&v"(d) : "v"(a), "a"(b_agpr), "v"(c0));
+  }
+  // a fragment moved into AGPRs (compiler copies in front of the statement; then two wait states before an MFMA may read it)
+  static FA_DEV frag to_agpr(const frag& x) {
+    frag y;
+    asm volatile("s_nop 1" : "=a"(y) : "0"(x));
+    return y;
+  }
+  // The accumulators of a finished sweep become readable: the longest pass count plus margin in wait states.  The tiles are operands
+  // of the statement, so every read of them depends on it and none can be placed above it (a sched_barrier holds inside one basic
+  // block only, and hipcc does move the AGPR -> VGPR copies of a later block up to the sweep's exit).
+  static FA_DEV void mma_drain(f32x16 (&x)[2][2], f32x16 (&y)[2][2]) {
+    asm volatile("s_nop 15\n\ts_nop 15"
+                 : "+a"(x[0][0]), "+a"(x[0][1]), "+a"(x[1][0]), "+a"(x[1][1]), "+a"(y[0][0]), "+a"(y[0][1]), "+a"(y[1][0]), "+a"(y[1][1]));
+  }
+};
+
+// ---------------------------------------------------------------------------------------------
 // fp32 (exact, v_mfma_f32_32x32x2_f32): row-major LDS tile padded by 16 B per row -- ds_read_b128 row
 // reads and ds_read_b32 column reads are both conflict free.
 // ---------------------------------------------------------------------------------------------

@@ -566,7 +566,9 @@ bwd_dkdv_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __res
 // follow in the ring (requested by the last iteration) and are taken wave by wave in plain per-sub-slice form: wave w multiplies
 // sub-slices w..7 of the block and masks the first one; queries 0..63 split P and dS into two bf16 fragments there
 // (Atom::pack_lo).  Workgroups are ranked longest-first across all heads (map_block_ranked), so the grid ends level.
-// TILED = true (non-causal, N a multiple of 256): a workgroup takes key block kb of lay.tiles CONSECUTIVE HEADS, one after the
+// TILED = true (the library no longer builds it: those launches run bwd_dkdv_slot64_kernel, fa_bwd_dkdv64.h, which took this form over;
+// taking the parameter out changes the register allocation of the one-head build, 222 -> 215 VGPRs, and waits for a change that
+// measures that kernel): non-causal, N a multiple of 256: a workgroup takes key block kb of lay.tiles CONSECUTIVE HEADS, one after the
 // other, without leaving the pipeline's ring (the workgroups of all key blocks of a head group move from head to head together, so
 // a head's Q / dO stream is still shared through the XCD's L2; consecutive key blocks of ONE head per workgroup lost that sharing
 // and measured 9 % slower at B = 32): the last stage iteration of a head requests stage 0 of the next head into the next ring slot,

@@ -28,12 +28,13 @@
 // whose tile offset is a scalar operand (out-of-range rows read as zero) -- no address VALU inside the loops.
 //
 // Files: fa_atoms.h (MFMA / LDS / LDS-DMA primitives), fa_common.h (constants, small helpers), fa_fwd.h (forward),
-// fa_bwd_dkdv.h (preprocess, dK / dV), fa_bwd_dq.h (dQ), fa_aux.h (sustained-peak loop, layout probes).
+// fa_bwd_dkdv.h (preprocess, dK / dV), fa_bwd_dkdv64.h (dK / dV, 64 keys per wave), fa_bwd_dq.h (dQ), fa_aux.h (sustained-peak loop, layout probes).
 #pragma once
 #include "fa_common.h"
 #include "fa_fwd.h"
 #include "fa_fwd_splitk_f32.h"
 #include "fa_bwd_dkdv.h"
+#include "fa_bwd_dkdv64.h"
 #include "fa_bwd_dq.h"
 #include "fa_bwd_onepass_f32.h"
 #include "fa_aux.h"

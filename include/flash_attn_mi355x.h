@@ -142,6 +142,10 @@ int fa_mi355x_bwd_stages(const void* q, const void* k, const void* v, const floa
  *            are cut into 4 or 8 parts); 4 restores
  *            the bitwise repeatable two-kernel path (FA_MI355X_DETERMINISTIC=1 in the environment does the same for every call
  *            that does not ask for 5: the reference's launch_flash_attn_bw has no options argument);
+ *   opts[0]  6 / 7 (bf16, d = 64, non-causal, no key mask / dropout): the non-causal dK/dV slot kernel has a four-wave build with 64
+ *            keys per wave (half the LDS reads per MFMA, bitwise the same dk, dv), selected by default for the launches that take
+ *            several heads per workgroup (opts[5]).  6 = always the eight-wave build; 7 = the four-wave build wherever it is valid
+ *            (N a multiple of 256, ungrouped heads), in groups of 4 heads where the default forms none
  *   opts[5]  1 = the non-causal d = 64 dK/dV kernel takes one head per workgroup (default: key block kb of several consecutive heads
  *            per workgroup when the launch still covers every CU), and so does the non-causal d = 64 dQ kernel (default: query block
  *            qb of several consecutive heads, same condition); bitwise the same results
@@ -260,6 +264,11 @@ int fa_mi355x_bwd_padded(const void* q, const void* k, const void* v, const floa
  * preprocess (and therefore runs first).  bench.py labels its per-kernel timings and its roofline from this. */
 int fa_mi355x_plan(int batch, int N, int d, int causal, int variant, int dtype, int stages, const int* opts, int nopts, char* out,
                    size_t n);
+/* The same plan with one name per BUILD instead of one per kernel family (the selection's own build ids), e.g.
+ * "DQ_SLOT_TILED;DKDV_SLOT64_TILED": DKDV_SLOT64_TILED is bwd_dkdv_slot_kernel's four-wave build with 64 keys per wave,
+ * DKDV_SLOT its eight-wave build (one head per workgroup). */
+int fa_mi355x_plan_builds(int batch, int N, int d, int causal, int variant, int dtype, int stages, const int* opts, int nopts,
+                          char* out, size_t n);
 
 /* The same two operations on the layout the projection writes: SURVEY.md row f1.  minitorch's MultiHeadAttention
  * produces q, k, v as (B, N, H, d) views and then pays permute(0,2,1,3).contiguous() for each of them, and the
