@@ -432,3 +432,25 @@ def bidir() -> ctypes.CDLL:
 def bidir_check(status: int) -> None:
     if status != FA_OK:
         _raise(status, bidir(), "fa_mi355x_bidir_last_error", "flash_attn_mi355x_bidir")
+
+
+# the same for include/flash_attn_mi355x_prefix.h: libflash_attn_mi355x_prefix.so, the causal packed forward and backward under the
+# same two arrays, the queries being the last positions of the keys (tests/test_prefix_cpu.py)
+PREFIX_ABI = {
+    "fa_mi355x_fwd_prefix_workspace_bytes": (_sz, [_i] * 6),
+    "fa_mi355x_bwd_prefix_workspace_bytes": (_sz, [_i] * 6),
+    "fa_mi355x_fwd_prefix": (_i, [_vp] * 8 + [_i] * 6 + [_f, _i, _vp]),
+    "fa_mi355x_bwd_prefix": (_i, [_vp] * 12 + [_i] * 6 + [_f, _i, _vp]),
+    "fa_mi355x_prefix_last_error": (_s, []),
+}
+PREFIX_NAME = "libflash_attn_mi355x_prefix.so"
+
+
+def prefix() -> ctypes.CDLL:
+    """libflash_attn_mi355x_prefix.so (include/flash_attn_mi355x_prefix.h) with argtypes set."""
+    return _typed(PREFIX_NAME, PREFIX_ABI)
+
+
+def prefix_check(status: int) -> None:
+    if status != FA_OK:
+        _raise(status, prefix(), "fa_mi355x_prefix_last_error", "flash_attn_mi355x_prefix")

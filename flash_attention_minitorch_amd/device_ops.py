@@ -832,23 +832,27 @@ def _check_window_call(window, sink):
     return window, sink or 0
 
 
-# ---- the training-side libraries (window / softcap, varlen, bidir): one path for the three families -------------------------------
-# The NAMES by which the windowed calls here, the packed calls (flash_attn_varlen_*) and the bidirectional ones
-# (flash_attn_varlen_bidir_*, both below) differ; _side_fwd, _side_bwd and _side_workspace do the work.  What else a family has of its
+# ---- the training-side libraries (window / softcap, varlen, bidir, prefix): one path for the families -------------------------------
+# The NAMES by which the windowed calls here, the packed calls (flash_attn_varlen_*), the bidirectional ones
+# (flash_attn_varlen_bidir_*) and the causal two-array ones (flash_attn_varlen_prefix_*, all below) differ; _side_fwd, _side_bwd and _side_workspace do the work.  What else a family has of its
 # own is code, not this table: its geometry (_side_geometry, over _check_gqa or _check_packed) and its mask scalars (the public
 # wrappers).  ``lib`` / ``check``: _lib's getter and status checker, looked up at call time; ``fwd`` / ``bwd``: the entry points
 # (under a logit cap: their _softcap forms, the cap behind the window); ``fwd_size`` / ``bwd_size``: the workspace sizes (None: the
-# call takes no workspace); ``sizer``: the public call that makes a workspace, for the message.  A call's arguments: the tensors, the
-# geometry, softmax_scale, the mask scalars, dtype, stream.
+# call takes no workspace); ``sizer``: the public call that makes a workspace, for the message; ``wrapper`` (packed families): the
+# public call that pads the head dim, likewise.  A call's arguments: the tensors, the geometry, softmax_scale, the mask scalars,
+# dtype, stream.
 _SIDE_FAMILIES = {
     "window": dict(lib="window", check="window_check", fwd="fa_mi355x_fwd_window", bwd="fa_mi355x_bwd_window", fwd_size=None,
                    bwd_size="fa_mi355x_bwd_window_workspace_bytes", sizer="bwd_workspace_window(q, k, layout)"),
     "varlen": dict(lib="varlen", check="varlen_check", fwd="fa_mi355x_fwd_varlen", bwd="fa_mi355x_bwd_varlen",
                    fwd_size="fa_mi355x_fwd_varlen_workspace_bytes", bwd_size="fa_mi355x_bwd_varlen_workspace_bytes",
-                   sizer="varlen_workspace(q, k, cu_seqlens)"),
+                   sizer="varlen_workspace(q, k, cu_seqlens)", wrapper="flash_attn_varlen"),
     "bidir": dict(lib="bidir", check="bidir_check", fwd="fa_mi355x_fwd_bidir", bwd="fa_mi355x_bwd_bidir",
                   fwd_size="fa_mi355x_fwd_bidir_workspace_bytes", bwd_size="fa_mi355x_bwd_bidir_workspace_bytes",
-                  sizer="bidir_workspace(q, k, cu_seqlens_q, cu_seqlens_k)"),
+                  sizer="bidir_workspace(q, k, cu_seqlens_q, cu_seqlens_k)", wrapper="flash_attn_varlen_bidir"),
+    "prefix": dict(lib="prefix", check="prefix_check", fwd="fa_mi355x_fwd_prefix", bwd="fa_mi355x_bwd_prefix",
+                   fwd_size="fa_mi355x_fwd_prefix_workspace_bytes", bwd_size="fa_mi355x_bwd_prefix_workspace_bytes",
+                   sizer="prefix_workspace(q, k, cu_seqlens_q, cu_seqlens_k)", wrapper="flash_attn_varlen_prefix"),
 }
 
 
@@ -858,7 +862,8 @@ def _side_geometry(family, q, k, v, index, layout, o=None, do=None):
     if family == "window":
         B, H, Hkv, N, d, dtype = _check_gqa(layout, q, k, v, o, do)
         return (B, H, Hkv, N, d, _DECODE_LAYOUTS[layout]), (B, H, Hkv, N, d), (B, H, N), dtype
-    nseq, Tq, Tk, H, Hkv, d, dtype = _check_packed(q, k, v, index[0], index[-1], o, do, one_array=family == "varlen")
+    nseq, Tq, Tk, H, Hkv, d, dtype = _check_packed(q, k, v, index[0], index[-1], o, do, one_array=family == "varlen",
+                                                   wrapper=_SIDE_FAMILIES[family]["wrapper"])
     geom = (nseq, Tq, H, Hkv, d) if family == "varlen" else (nseq, Tq, Tk, H, Hkv, d)
     return geom, geom, (H, Tq), dtype
 
@@ -1519,11 +1524,12 @@ def flash_attn_ragged(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens=None, cau
 # block) off a device-side block map (libflash_attn_mi355x_varlen.so): per sequence the result is, bit for bit,
 # flash_attn_fwd_window / flash_attn_bwd_window on that sequence alone.  Rows no sequence owns come back as zeros.
 
-def _check_packed(q, k, v, cu_q, cu_k, o=None, do=None, *, one_array):
+def _check_packed(q, k, v, cu_q, cu_k, o=None, do=None, *, one_array, wrapper):
     """What _check_gqa checks, for packed 3-d tensors.  ``one_array``: the causal packed calls, where one cu_seqlens serves queries
-    and keys and q and k agree on (T, d); otherwise the bidirectional ones, with a row count and an array for either side.  Returns
-    (nseq, Tq, Tk, H, Hkv, d, dtype code)."""
-    tq, tk, wrapper = ("T", "T", "flash_attn_varlen") if one_array else ("Tq", "Tk", "flash_attn_varlen_bidir")
+    and keys and q and k agree on (T, d); otherwise the two-array ones (bidirectional, or causal behind a prefix), with a row count and
+    an array for either side.  ``wrapper``: the public call that pads the head dim, for the message.  Returns (nseq, Tq, Tk, H, Hkv,
+    d, dtype code)."""
+    tq, tk = ("T", "T") if one_array else ("Tq", "Tk")
     _require_gpu(q, "device_ops")
     dtype = _dtype_code(q)
     if q.dim() != 3 or k.dim() != 3:
@@ -1716,12 +1722,11 @@ def flash_attn_varlen_bidir(q, k, v, cu_seqlens_q, cu_seqlens_k=None, softmax_sc
         flash_attn_varlen_bidir_fwd, flash_attn_varlen_bidir_bwd, q, k, v, index, dict(softmax_scale=scale)))
 
 
-def flash_attn_cross(q, k, v, softmax_scale=None):
-    """Batched cross-attention under autograd: q (B, Nq, H, d), k and v (B, Nk, Hkv, d), contiguous; every query of batch element b
-    admits every key of it, Nq and Nk independent.  The tensors are viewed as packed ((B * Nq, H, d), (B * Nk, Hkv, d)) and the two
-    cu_seqlens are built on the device: flash_attn_varlen_bidir does the rest.  out fp32 (B, Nq, H, d)."""
+def _batched_two_array(name, attend, q, k, v, softmax_scale):
+    """``attend`` (a packed two-array call under autograd) on batched tensors: q (B, Nq, H, d), k and v (B, Nk, Hkv, d) are viewed as
+    packed ((B * Nq, H, d), (B * Nk, Hkv, d)) and the two cu_seqlens are built on the device.  out fp32 (B, Nq, H, d)."""
     if not isinstance(q, torch.Tensor) or not isinstance(k, torch.Tensor) or not isinstance(v, torch.Tensor) or q.dim() != 4 or k.dim() != 4:
-        raise ValueError("flash_attn_cross expects 4-d tensors: q (B, Nq, H, d) and k, v (B, Nk, Hkv, d)")
+        raise ValueError(f"{name} expects 4-d tensors: q (B, Nq, H, d) and k, v (B, Nk, Hkv, d)")
     if v.shape != k.shape:
         raise ValueError("k and v must have one shape")
     (B, Nq, H, d), (Bk, Nk, Hkv, _) = q.shape, k.shape
@@ -1731,5 +1736,61 @@ def flash_attn_cross(q, k, v, softmax_scale=None):
         raise ValueError("tensors must be contiguous")
     steps = torch.arange(B + 1, dtype=torch.int32, device=q.device)
     cu_q, cu_k = steps * Nq, steps * Nk
-    o = flash_attn_varlen_bidir(q.view(B * Nq, H, d), k.view(B * Nk, Hkv, d), v.view(B * Nk, Hkv, d), cu_q, cu_k, softmax_scale)
+    o = attend(q.view(B * Nq, H, d), k.view(B * Nk, Hkv, d), v.view(B * Nk, Hkv, d), cu_q, cu_k, softmax_scale)
     return o.view(B, Nq, H, o.shape[-1])
+
+
+def flash_attn_cross(q, k, v, softmax_scale=None):
+    """Batched cross-attention under autograd: q (B, Nq, H, d), k and v (B, Nk, Hkv, d), contiguous; every query of batch element b
+    admits every key of it, Nq and Nk independent.  The tensors are viewed as packed ((B * Nq, H, d), (B * Nk, Hkv, d)) and the two
+    cu_seqlens are built on the device: flash_attn_varlen_bidir does the rest.  out fp32 (B, Nq, H, d)."""
+    return _batched_two_array("flash_attn_cross", flash_attn_varlen_bidir, q, k, v, softmax_scale)
+
+
+# ---- causal packed attention with one cu_seqlens for q and one for k: a cached prefix (include/flash_attn_mi355x_prefix.h) ----------
+# The tensors and the two arrays of the bidirectional calls above; the queries of sequence b are the LAST n_q positions of its n_k
+# keys, so with D = n_k - n_q row i admits the keys 0 .. i + D (the bottom-right alignment of flash-attn >= 2.1, the mask
+# flash_attn_extend generates with).  Kernels of their own (libflash_attn_mi355x_prefix.so).  Rows that admit no key (i + D < 0, a
+# keyless sequence) and rows no sequence owns come back as zeros.
+
+def prefix_workspace(q, k, cu_seqlens_q, cu_seqlens_k=None, backward=True):
+    """Scratch for flash_attn_varlen_prefix_bwd (``backward=False``: for flash_attn_varlen_prefix_fwd alone) with these tensors
+    (fa_mi355x_bwd_prefix_workspace_bytes / _fwd_): as bidir_workspace, a pure function of the SHAPES."""
+    return _side_workspace("prefix", q, k, (cu_seqlens_q, _self_cu(q, k, cu_seqlens_q, cu_seqlens_k)), backward=backward)
+
+
+def flash_attn_varlen_prefix_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k=None, softmax_scale=None, out=None, workspace=None, lse=None):
+    """Causal forward over a packed batch whose sequences have n_q queries behind n_k - n_q earlier keys (fa_mi355x_fwd_prefix): q
+    (Tq, H, d), k and v (Tk, Hkv, d), the two arrays contiguous int32 (nseq + 1,) on q's device (``cu_seqlens_k=None``: causal
+    self-attention, the same array).  Returns (out fp32 (Tq, H, d), lse (H, Tq)); rows that admit no key and rows no sequence owns
+    are zero in both.  ``out``, ``lse``: buffers to write into; ``workspace``: prefix_workspace(...) (with all three given the call
+    allocates nothing: it can be captured in a graph)."""
+    index = (cu_seqlens_q, _self_cu(q, k, cu_seqlens_q, cu_seqlens_k))
+    return _side_fwd("prefix", q, k, v, index, (), softmax_scale, out=out, lse=lse, workspace=workspace)
+
+
+def flash_attn_varlen_prefix_bwd(q, k, v, out, out_grad, lse, cu_seqlens_q, cu_seqlens_k=None, softmax_scale=None, workspace=None,
+                                 grads=None):
+    """Backward of flash_attn_varlen_prefix_fwd (fa_mi355x_bwd_prefix).  Returns (dq in q's shape, dk, dv in k's shape), fp32; zero in
+    the query rows that admit no key, the key rows of a sequence without queries and the rows no sequence owns; no atomics, the same
+    bits on every run.  ``workspace``: prefix_workspace(...); ``grads``: (dq, dk, dv) buffers to write into."""
+    index = (cu_seqlens_q, _self_cu(q, k, cu_seqlens_q, cu_seqlens_k))
+    return _side_bwd("prefix", q, k, v, out, out_grad, lse, index, (), softmax_scale, workspace=workspace, grads=grads)
+
+
+def flash_attn_varlen_prefix(q, k, v, cu_seqlens_q, cu_seqlens_k=None, softmax_scale=None):
+    """Causal attention over a packed batch with a cached prefix, under autograd: q (Tq, H, d), k and v (Tk, Hkv, d); sequence b's
+    queries (``cu_seqlens_q``) are the last positions of sequence b's keys (``cu_seqlens_k``; None: causal self-attention, the same
+    array, and k has Tq rows), and row i admits the keys 0 .. i + n_k - n_q.  out fp32 (Tq, H, d); q.grad in q's shape and dtype,
+    k.grad and v.grad in k's, the prefix rows included.  A head dim other than 32, 64, 128 runs through zero-padded columns with
+    softmax_scale = 1 / sqrt(d).  Rows that admit no key and rows no sequence owns give zeros and take a zero gradient."""
+    index = (cu_seqlens_q, _self_cu(q, k, cu_seqlens_q, cu_seqlens_k))
+    return _native_head_dim(q, k, v, softmax_scale, lambda q, k, v, scale: _FlashAttnSideFn.apply(
+        flash_attn_varlen_prefix_fwd, flash_attn_varlen_prefix_bwd, q, k, v, index, dict(softmax_scale=scale)))
+
+
+def flash_attn_prefix(q, k, v, softmax_scale=None):
+    """Batched causal attention behind a prefix, under autograd: q (B, Nq, H, d) are the last Nq positions of k and v (B, Nk, Hkv, d),
+    contiguous: the differentiable counterpart of flash_attn_extend on a slab cache that holds the same keys.  Built as
+    flash_attn_cross, over flash_attn_varlen_prefix.  out fp32 (B, Nq, H, d)."""
+    return _batched_two_array("flash_attn_prefix", flash_attn_varlen_prefix, q, k, v, softmax_scale)

@@ -150,6 +150,52 @@ def attention_stack_packed(x, cu_seqlens, layers, n_head: int, fold_scale: bool 
     return x
 
 
+def prefix_gather_index(cu_seqlens, cu_seqlens_prefix, T: int, Tp: int):
+    """int64 (Tp + T,): for every row of the packed keys under cu_seqlens_k = cu_seqlens + cu_seqlens_prefix, its source row in
+    cat(prefix rows, token rows): sequence b's keys are its prefix rows followed by its own tokens.  Built on the arrays' device
+    from the arrays alone (searchsorted; nothing is read on the host).  A row no sequence owns under cu_seqlens_k takes some row
+    inside the buffer: the kernels neither read it nor give it a gradient."""
+    cu, cup = cu_seqlens.long(), cu_seqlens_prefix.long()
+    cuk = cu + cup
+    t = torch.arange(Tp + T, device=cu.device)
+    b = (torch.searchsorted(cuk[1:].contiguous(), t, right=True)).clamp_(max=cu.shape[0] - 2)   # cuk[b] <= t < cuk[b + 1]
+    j = t - cuk[b]
+    n_prefix = cup[b + 1] - cup[b]
+    src = torch.where(j < n_prefix, cup[b] + j, Tp + cu[b] + j - n_prefix)
+    return src.clamp_(0, Tp + T - 1)
+
+
+def multi_head_attention_packed_prefix(x, cu_seqlens, prefix_k, prefix_v, cu_seqlens_prefix, wq, wk, wv, wo, n_head: int):
+    """multi_head_attention_packed behind a PREFIX of keys and values that are given, not projected: x (T, E) as there, prefix_k and
+    prefix_v (Tp, Hkv, d) with sequence b owning the rows cu_seqlens_prefix[b] .. cu_seqlens_prefix[b + 1] - 1 (prefix tuning, where
+    they are the trained parameters; a cached prompt; the earlier chunks of a long sequence).  Every token attends its sequence's
+    prefix rows and, causally, its sequence's own tokens: the keys of a sequence are its prefix rows followed by its tokens' keys
+    (prefix_gather_index, differentiable through torch's indexing: prefix_k.grad and prefix_v.grad flow), cu_seqlens_k =
+    cu_seqlens + cu_seqlens_prefix, and device_ops.flash_attn_varlen_prefix does the rest.  Neither array is read on the host.
+    No ``rope``: apply_rotary_varlen restarts positions at every sequence and has no offset for the tokens behind a prefix."""
+    T, E = x.shape
+    q, k, v = _project(x[None], wq, wk, wv, n_head)
+    q, k, v = q[0], k[0], v[0]   # (T, heads, d)
+    if prefix_k.shape != prefix_v.shape or prefix_k.dim() != 3 or prefix_k.shape[1:] != k.shape[1:]:
+        raise ValueError(f"prefix_k and prefix_v must both be (Tp, Hkv, d) = (Tp, {k.shape[1]}, {k.shape[2]}), the projected keys' heads")
+    if cu_seqlens_prefix.shape != cu_seqlens.shape:
+        raise ValueError("cu_seqlens and cu_seqlens_prefix must have one length: the same sequences, counted in tokens and in prefix rows")
+    src = prefix_gather_index(cu_seqlens, cu_seqlens_prefix, T, prefix_k.shape[0])
+    k_all, v_all = (torch.cat((p.to(t.dtype), t))[src] for p, t in ((prefix_k, k), (prefix_v, v)))
+    o = device_ops.flash_attn_varlen_prefix(q, k_all, v_all, cu_seqlens, cu_seqlens + cu_seqlens_prefix)
+    return o.reshape(T, E).to(x.dtype) @ wo
+
+
+def attention_stack_packed_prefix(x, cu_seqlens, prefixes, cu_seqlens_prefix, layers, n_head: int):
+    """attention_stack_packed behind per-layer prefixes: x <- x + multi_head_attention_packed_prefix_l(x) for every (wq, wk, wv, wo)
+    in ``layers`` with its (prefix_k, prefix_v) of ``prefixes``; one cu_seqlens_prefix for all layers."""
+    if len(prefixes) != len(layers):
+        raise ValueError(f"one (prefix_k, prefix_v) per layer: {len(prefixes)} prefixes for {len(layers)} layers")
+    for (prefix_k, prefix_v), (wq, wk, wv, wo) in zip(prefixes, layers):
+        x = x + multi_head_attention_packed_prefix(x, cu_seqlens, prefix_k, prefix_v, cu_seqlens_prefix, wq, wk, wv, wo, n_head)
+    return x
+
+
 def multi_head_attention_packed_bidir(x, cu_seqlens, wq, wk, wv, wo, n_head: int, rope=None):
     """Encoder self-attention over a packed batch: multi_head_attention_packed's data flow and weights, but every token attends to
     EVERY token of its own sequence (device_ops.flash_attn_varlen_bidir with one array for queries and keys: no padding, no key
