@@ -454,3 +454,25 @@ def prefix() -> ctypes.CDLL:
 def prefix_check(status: int) -> None:
     if status != FA_OK:
         _raise(status, prefix(), "fa_mi355x_prefix_last_error", "flash_attn_mi355x_prefix")
+
+
+# the same for include/flash_attn_mi355x_local.h: libflash_attn_mi355x_local.so, the packed forward and backward under a two-sided
+# sliding window, `int window_left, int window_right` behind softmax_scale, under the same two arrays (tests/test_local_cpu.py)
+LOCAL_ABI = {
+    "fa_mi355x_fwd_local_workspace_bytes": (_sz, [_i] * 6),
+    "fa_mi355x_bwd_local_workspace_bytes": (_sz, [_i] * 6),
+    "fa_mi355x_fwd_local": (_i, [_vp] * 8 + [_i] * 6 + [_f, _i, _i, _i, _vp]),
+    "fa_mi355x_bwd_local": (_i, [_vp] * 12 + [_i] * 6 + [_f, _i, _i, _i, _vp]),
+    "fa_mi355x_local_last_error": (_s, []),
+}
+LOCAL_NAME = "libflash_attn_mi355x_local.so"
+
+
+def local() -> ctypes.CDLL:
+    """libflash_attn_mi355x_local.so (include/flash_attn_mi355x_local.h) with argtypes set."""
+    return _typed(LOCAL_NAME, LOCAL_ABI)
+
+
+def local_check(status: int) -> None:
+    if status != FA_OK:
+        _raise(status, local(), "fa_mi355x_local_last_error", "flash_attn_mi355x_local")

@@ -832,9 +832,9 @@ def _check_window_call(window, sink):
     return window, sink or 0
 
 
-# ---- the training-side libraries (window / softcap, varlen, bidir, prefix): one path for the families -------------------------------
+# ---- the training-side libraries (window / softcap, varlen, bidir, prefix, local): one path for the families ------------------------
 # The NAMES by which the windowed calls here, the packed calls (flash_attn_varlen_*), the bidirectional ones
-# (flash_attn_varlen_bidir_*) and the causal two-array ones (flash_attn_varlen_prefix_*, all below) differ; _side_fwd, _side_bwd and _side_workspace do the work.  What else a family has of its
+# (flash_attn_varlen_bidir_*), the causal two-array ones (flash_attn_varlen_prefix_*) and the banded ones (flash_attn_varlen_local_*, all below) differ; _side_fwd, _side_bwd and _side_workspace do the work.  What else a family has of its
 # own is code, not this table: its geometry (_side_geometry, over _check_gqa or _check_packed) and its mask scalars (the public
 # wrappers).  ``lib`` / ``check``: _lib's getter and status checker, looked up at call time; ``fwd`` / ``bwd``: the entry points
 # (under a logit cap: their _softcap forms, the cap behind the window); ``fwd_size`` / ``bwd_size``: the workspace sizes (None: the
@@ -853,6 +853,9 @@ _SIDE_FAMILIES = {
     "prefix": dict(lib="prefix", check="prefix_check", fwd="fa_mi355x_fwd_prefix", bwd="fa_mi355x_bwd_prefix",
                    fwd_size="fa_mi355x_fwd_prefix_workspace_bytes", bwd_size="fa_mi355x_bwd_prefix_workspace_bytes",
                    sizer="prefix_workspace(q, k, cu_seqlens_q, cu_seqlens_k)", wrapper="flash_attn_varlen_prefix"),
+    "local": dict(lib="local", check="local_check", fwd="fa_mi355x_fwd_local", bwd="fa_mi355x_bwd_local",
+                  fwd_size="fa_mi355x_fwd_local_workspace_bytes", bwd_size="fa_mi355x_bwd_local_workspace_bytes",
+                  sizer="local_workspace(q, k, cu_seqlens_q, cu_seqlens_k)", wrapper="flash_attn_varlen_local"),
 }
 
 
@@ -1794,3 +1797,97 @@ def flash_attn_prefix(q, k, v, softmax_scale=None):
     contiguous: the differentiable counterpart of flash_attn_extend on a slab cache that holds the same keys.  Built as
     flash_attn_cross, over flash_attn_varlen_prefix.  out fp32 (B, Nq, H, d)."""
     return _batched_two_array("flash_attn_prefix", flash_attn_varlen_prefix, q, k, v, softmax_scale)
+
+
+# ---- packed attention under a two-sided sliding window, a band (include/flash_attn_mi355x_local.h) ---------------------------------
+# The tensors, the two arrays and the bottom-right alignment of the causal calls above: row i of a sequence sits at key position
+# p = i + n_k - n_q and, under window = (L, R), admits the keys max(0, p - L) .. min(n_k - 1, p + R); a side of -1 (or None) is
+# unbounded.  Kernels of their own (libflash_attn_mi355x_local.so), which walk only the tiles that meet the band.  (-1, -1) IS the
+# bidirectional call and (-1, 0) the causal one: those two windows go to the functions above, launches and bits unchanged.  Rows that
+# admit no key, keys no row admits and rows no sequence owns come back as zeros.
+
+def _check_band(window):
+    """``window`` of the banded calls as the library takes it: (left, right), each an int >= -1 (None, for a side or for the pair:
+    -1, unbounded)."""
+    if window is None:
+        return -1, -1
+    sides = None
+    if not isinstance(window, (str, bytes, torch.Tensor)):
+        try:
+            sides = tuple(window)
+        except TypeError:
+            sides = None
+    if sides is None or len(sides) != 2:
+        raise ValueError("window must be a pair (left, right): the positions a token sees before and behind its own, each an int >= -1 "
+                         "(-1 or None: unbounded)")
+    pair = []
+    for side in sides:
+        if side is None:
+            side = -1
+        try:
+            side = None if isinstance(side, bool) else operator.index(side)
+        except TypeError:
+            side = None
+        if side is None or side < -1:
+            raise ValueError("window must be a pair (left, right) of ints >= -1 (-1 or None: unbounded on that side)")
+        pair.append(side)
+    return tuple(pair)
+
+
+_BAND_ROUTES = {(-1, -1): "bidir", (-1, 0): "prefix"}   # the windows that are an existing call
+
+
+def local_workspace(q, k, cu_seqlens_q, cu_seqlens_k=None, backward=True):
+    """Scratch for flash_attn_varlen_local_bwd (``backward=False``: for flash_attn_varlen_local_fwd alone) with these tensors
+    (fa_mi355x_bwd_local_workspace_bytes / _fwd_): as bidir_workspace, a pure function of the SHAPES, the same for every window (the
+    sizes are those of bidir_workspace and prefix_workspace, so it also serves the two windows that run as those calls)."""
+    return _side_workspace("local", q, k, (cu_seqlens_q, _self_cu(q, k, cu_seqlens_q, cu_seqlens_k)), backward=backward)
+
+
+def flash_attn_varlen_local_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k=None, window=(-1, -1), softmax_scale=None, out=None, workspace=None,
+                                lse=None):
+    """Forward under a two-sided sliding window over a packed batch (fa_mi355x_fwd_local): q (Tq, H, d), k and v (Tk, Hkv, d), the two
+    arrays contiguous int32 (nseq + 1,) on q's device (``cu_seqlens_k=None``: self-attention, the same array); ``window`` = (left,
+    right), ints >= -1.  Returns (out fp32 (Tq, H, d), lse (H, Tq)); rows that admit no key and rows no sequence owns are zero in
+    both.  (-1, -1) is flash_attn_varlen_bidir_fwd and (-1, 0) flash_attn_varlen_prefix_fwd, and runs as them.  ``out``, ``lse``:
+    buffers to write into; ``workspace``: local_workspace(...) (with all three given the call allocates nothing: it can be captured
+    in a graph)."""
+    window = _check_band(window)
+    index = (cu_seqlens_q, _self_cu(q, k, cu_seqlens_q, cu_seqlens_k))
+    family = _BAND_ROUTES.get(window, "local")
+    return _side_fwd(family, q, k, v, index, window if family == "local" else (), softmax_scale, out=out, lse=lse, workspace=workspace)
+
+
+def flash_attn_varlen_local_bwd(q, k, v, out, out_grad, lse, cu_seqlens_q, cu_seqlens_k=None, window=(-1, -1), softmax_scale=None,
+                                workspace=None, grads=None):
+    """Backward of flash_attn_varlen_local_fwd (fa_mi355x_bwd_local) under the same ``window``.  Returns (dq in q's shape, dk, dv in
+    k's shape), fp32; zero in the query rows that admit no key, the key rows no query admits and the rows no sequence owns; no
+    atomics, the same bits on every run.  ``workspace``: local_workspace(...); ``grads``: (dq, dk, dv) buffers to write into."""
+    window = _check_band(window)
+    index = (cu_seqlens_q, _self_cu(q, k, cu_seqlens_q, cu_seqlens_k))
+    family = _BAND_ROUTES.get(window, "local")
+    return _side_bwd(family, q, k, v, out, out_grad, lse, index, window if family == "local" else (), softmax_scale,
+                     workspace=workspace, grads=grads)
+
+
+def flash_attn_varlen_local(q, k, v, cu_seqlens_q, cu_seqlens_k=None, window=(-1, -1), softmax_scale=None):
+    """Attention under a two-sided sliding window over a packed batch, under autograd: q (Tq, H, d), k and v (Tk, Hkv, d); sequence
+    b's queries (``cu_seqlens_q``) are the last positions of sequence b's keys (``cu_seqlens_k``; None: self-attention, the same
+    array, and k has Tq rows), and the row at position p admits the keys p - left .. p + right of its sequence (``window`` = (left,
+    right), ints >= -1; -1 or None: unbounded on that side).  out fp32 (Tq, H, d); q.grad in q's shape and dtype, k.grad and v.grad
+    in k's.  A head dim other than 32, 64, 128 runs through zero-padded columns with softmax_scale = 1 / sqrt(d).  Rows that admit no
+    key and rows no sequence owns give zeros and take a zero gradient.  (-1, -1) is flash_attn_varlen_bidir and (-1, 0)
+    flash_attn_varlen_prefix: the same launches and bits."""
+    window = _check_band(window)
+    index = (cu_seqlens_q, _self_cu(q, k, cu_seqlens_q, cu_seqlens_k))
+    return _native_head_dim(q, k, v, softmax_scale, lambda q, k, v, scale: _FlashAttnSideFn.apply(
+        flash_attn_varlen_local_fwd, flash_attn_varlen_local_bwd, q, k, v, index, dict(window=window, softmax_scale=scale)))
+
+
+def flash_attn_local(q, k, v, window, softmax_scale=None):
+    """Batched attention under a two-sided sliding window, under autograd: q (B, Nq, H, d) are the last Nq positions of k and v
+    (B, Nk, Hkv, d), contiguous; ``window`` = (left, right) as flash_attn_varlen_local.  Built as flash_attn_cross, over
+    flash_attn_varlen_local.  out fp32 (B, Nq, H, d)."""
+    window = _check_band(window)
+    return _batched_two_array("flash_attn_local", lambda q, k, v, cu_q, cu_k, scale: flash_attn_varlen_local(
+        q, k, v, cu_q, cu_k, window, scale), q, k, v, softmax_scale)

@@ -196,24 +196,44 @@ def attention_stack_packed_prefix(x, cu_seqlens, prefixes, cu_seqlens_prefix, la
     return x
 
 
-def multi_head_attention_packed_bidir(x, cu_seqlens, wq, wk, wv, wo, n_head: int, rope=None):
+def multi_head_attention_packed_bidir(x, cu_seqlens, wq, wk, wv, wo, n_head: int, rope=None, window=None):
     """Encoder self-attention over a packed batch: multi_head_attention_packed's data flow and weights, but every token attends to
     EVERY token of its own sequence (device_ops.flash_attn_varlen_bidir with one array for queries and keys: no padding, no key
-    mask).  ``rope`` (a Rotary): positions restart at every sequence.  Rows no sequence owns give zero rows of the result."""
+    mask).  ``rope`` (a Rotary): positions restart at every sequence.  Rows no sequence owns give zero rows of the result.
+    ``window`` = (left, right): local attention, every token attends the ``left`` tokens before and the ``right`` tokens behind it
+    in its own sequence (device_ops.flash_attn_varlen_local; -1 or None: unbounded on that side); None: no window, the call above."""
     T, E = x.shape
     q, k, v = _project(x[None], wq, wk, wv, n_head)
     q, k, v = q[0], k[0], v[0]   # (T, heads, d)
     if rope is not None:
         q, k = (device_ops.apply_rotary_varlen(t, rope.cos, rope.sin, cu_seqlens, rope.interleaved) for t in (q, k))
-    o = device_ops.flash_attn_varlen_bidir(q, k, v, cu_seqlens)
+    if window is None:
+        o = device_ops.flash_attn_varlen_bidir(q, k, v, cu_seqlens)
+    else:
+        o = device_ops.flash_attn_varlen_local(q, k, v, cu_seqlens, window=window)
     return o.reshape(T, E).to(x.dtype) @ wo
 
 
-def encoder_stack_packed(x, cu_seqlens, layers, n_head: int, rope=None):
+def _layer_windows(window, n_layers):
+    """``window`` of a stack as one entry per layer: None (no layer has one), one pair (every layer has it), or a sequence of
+    ``n_layers`` entries, each a pair or None."""
+    if window is None:
+        return [None] * n_layers
+    window = list(window)
+    if len(window) == 2 and all(w is None or isinstance(w, int) for w in window):   # one (left, right)
+        return [tuple(window)] * n_layers
+    if len(window) != n_layers:
+        raise ValueError(f"window must be None, one (left, right) pair or one entry per layer: {len(window)} entries for {n_layers} layers")
+    return window
+
+
+def encoder_stack_packed(x, cu_seqlens, layers, n_head: int, rope=None, window=None):
     """The encoder layer stack over a packed batch: x <- x + multi_head_attention_packed_bidir_l(x) for every (wq, wk, wv, wo) in
-    ``layers``.  Per sequence it is attention_stack(causal=False) on that sequence alone."""
-    for (wq, wk, wv, wo) in layers:
-        x = x + multi_head_attention_packed_bidir(x, cu_seqlens, wq, wk, wv, wo, n_head, rope)
+    ``layers``.  Per sequence it is attention_stack(causal=False) on that sequence alone.  ``window``: None, one (left, right) pair
+    for every layer, or a sequence with one entry per layer, each a pair or None (global and local layers in alternation)."""
+    layers = list(layers)
+    for (wq, wk, wv, wo), w in zip(layers, _layer_windows(window, len(layers))):
+        x = x + multi_head_attention_packed_bidir(x, cu_seqlens, wq, wk, wv, wo, n_head, rope, w)
     return x
 
 

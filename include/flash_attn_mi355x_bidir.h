@@ -47,8 +47,9 @@
  * HIP call.  Asynchronous on `stream`, no allocation, nothing read back: every call can be captured in a graph and replayed on other
  * lengths.  No atomics and a fixed summation order: a call repeats bit for bit.
  *
- * Not in this library: a causal mask under two different arrays (bottom-right alignment), one- or two-sided windows and sinks, key
- * mask, dropout and FA-1 outputs, fp8, a host-pointer reference ABI, the MFMA-slot pipelines.
+ * Not in this library: a causal mask under two different arrays (bottom-right alignment) and one- or two-sided windows (both are
+ * calls of their own: flash_attn_mi355x_local.h has the windows, and the causal mask as its window (-1, 0)); not built anywhere:
+ * windows and sinks together, key mask, dropout and FA-1 outputs, fp8, a host-pointer reference ABI, the MFMA-slot pipelines.
  */
 #ifndef FLASH_ATTN_MI355X_BIDIR_H
 #define FLASH_ATTN_MI355X_BIDIR_H

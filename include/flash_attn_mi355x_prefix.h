@@ -54,8 +54,9 @@
  * HIP call.  Asynchronous on `stream`, no allocation, nothing read back: every call can be captured in a graph and replayed on other
  * lengths in both arrays.  No atomics and a fixed summation order: a call repeats bit for bit.
  *
- * Not in this library: windows, sinks or a logit cap under two arrays, rotary offsets, key mask, dropout and FA-1 outputs, fp8, a
- * host-pointer reference ABI, the MFMA-slot pipelines.
+ * Not in this library: windows, sinks or a logit cap under two arrays (a one- or two-sided window under the same two arrays is a call
+ * of its own, flash_attn_mi355x_local.h; sinks and a cap beside it are not built), rotary offsets, key mask, dropout and FA-1
+ * outputs, fp8, a host-pointer reference ABI, the MFMA-slot pipelines.
  */
 #ifndef FLASH_ATTN_MI355X_PREFIX_H
 #define FLASH_ATTN_MI355X_PREFIX_H
