@@ -30,6 +30,7 @@ kernel_lib fa_varlen _varlen     # packed variable-length (cu_seqlens) forward a
 kernel_lib fa_bidir  _bidir      # bidirectional packed attention, cu_seqlens for q and for k (include/flash_attn_mi355x_bidir.h)
 kernel_lib fa_prefix _prefix     # causal packed attention under the same two arrays, a cached prefix (include/flash_attn_mi355x_prefix.h)
 kernel_lib fa_local  _local      # two-sided sliding window (a band) under the same two arrays (include/flash_attn_mi355x_local.h)
+kernel_lib fa_lsink  _lsink      # learned sink logits in training: the forward and the logit gradient (include/flash_attn_mi355x_lsink.h)
 
 shim() {  # name variant FW|BW
   "$HIPCC" -O2 -fPIC -shared -x c++ "$SRC/fa_shim.cpp" -DFA_SHIM_VARIANT="$2" -DFA_SHIM_"$3" \

@@ -197,6 +197,14 @@ SOFTCAP_ABI = {
     "fa_mi355x_fwd_ragged_softcap": (_i, [_vp] * 11 + [_i] * 11 + [_f, _i, _i, _f, _i, _vp]),
 }
 
+# the same for include/flash_attn_mi355x_decode_lsink.h (learned sink logits: the _window forms with `const float* sink_logits`
+# behind the window; tests/test_lsink_cpu.py)
+LSINK_ABI = {
+    "fa_mi355x_fwd_decode_lsink": (_i, [_vp] * 10 + [_i] * 11 + [_f, _i, _i, _vp, _i, _vp]),
+    "fa_mi355x_fwd_extend_lsink": (_i, [_vp] * 10 + [_i] * 11 + [_f, _i, _i, _vp, _i, _vp]),
+    "fa_mi355x_fwd_ragged_lsink": (_i, [_vp] * 11 + [_i] * 11 + [_f, _i, _i, _vp, _i, _vp]),
+}
+
 # The positional order of every KV-cache symbol that device_ops calls, by the parameter names of the prototypes (k_pool / v_pool of
 # the _paged ones read k_cache / v_cache, T of the ragged ones Nq: one field each).  device_ops fills one dict of fields per public
 # call and every C call takes its arguments from it in this order; tests/test_kv_ops_cpu.py holds the table against the headers' text
@@ -271,9 +279,20 @@ KV_SOFTCAP_PARAMS = {
                                     "layout softmax_scale causal window softcap dtype stream",
 }
 KV_SOFTCAP_PARAMS = {sym: tuple(names.split()) for sym, names in KV_SOFTCAP_PARAMS.items()}
-KV_CALL_PARAMS = {**KV_PARAMS, **KV_SOFTCAP_PARAMS}
+# The learned-sink-logit symbols, likewise (tests/test_lsink_cpu.py holds them against their header and LSINK_ABI): a table of their
+# own, since tests/test_kv_ops_cpu.py holds KV_PARAMS against a fixed list of ABI tables.
+KV_LSINK_PARAMS = {
+    "fa_mi355x_fwd_decode_lsink": f"{_PROLOGUE} out lse cache_seqlens block_table workspace {_EITHER} d_new d "
+                                  "layout softmax_scale causal window sink_logits dtype stream",
+    "fa_mi355x_fwd_extend_lsink": f"{_PROLOGUE} out lse cache_seqlens block_table workspace {_EITHER} d_new d "
+                                  "layout softmax_scale causal window sink_logits dtype stream",
+    "fa_mi355x_fwd_ragged_lsink": f"{_PROLOGUE} out lse cu_seqlens_q cache_seqlens block_table workspace {_EITHER} d_new d "
+                                  "layout softmax_scale causal window sink_logits dtype stream",
+}
+KV_LSINK_PARAMS = {sym: tuple(names.split()) for sym, names in KV_LSINK_PARAMS.items()}
+KV_CALL_PARAMS = {**KV_PARAMS, **KV_SOFTCAP_PARAMS, **KV_LSINK_PARAMS}
 KV_POINTERS = frozenset("q q_rot k_new v_new k_cache v_cache k_scale v_scale cos sin out lse cu_seqlens_q cache_seqlens block_table "
-                        "workspace stream".split())
+                        "workspace sink_logits stream".split())
 
 # the same for include/flash_attn_mi355x_window.h: libflash_attn_mi355x_window.so, the sliding-window / attention-sink forward and
 # backward of the training side (tests/test_window_train_cpu.py).  WINDOW_ABI above is the decode library's windowed family.
@@ -361,12 +380,12 @@ def check(status: int) -> None:
 
 
 DECODE_NAME = "libflash_attn_mi355x_decode.so"
-_DECODE_LIB_ABI = {**DECODE_ABI, **PAGED_ABI, **RAGGED_ABI, **WINDOW_ABI, **FP8_ABI, **SINK_ABI, **ROPE_ABI, **SOFTCAP_ABI}
+_DECODE_LIB_ABI = {**DECODE_ABI, **PAGED_ABI, **RAGGED_ABI, **WINDOW_ABI, **FP8_ABI, **SINK_ABI, **ROPE_ABI, **SOFTCAP_ABI, **LSINK_ABI}
 
 
 def decode() -> ctypes.CDLL:
     """libflash_attn_mi355x_decode.so (include/flash_attn_mi355x_decode.h, its _paged.h, its _ragged.h, its _window.h, its _fp8.h, its
-    _sink.h, its _rope.h and its _softcap.h) with argtypes set.  (Every KV-cache call comes through here: the tables are merged once, above.)"""
+    _sink.h, its _rope.h, its _softcap.h and its _lsink.h) with argtypes set.  (Every KV-cache call comes through here: the tables are merged once, above.)"""
     return _typed(DECODE_NAME, _DECODE_LIB_ABI)
 
 
@@ -387,6 +406,28 @@ def window() -> ctypes.CDLL:
 def window_check(status: int) -> None:
     if status != FA_OK:
         _raise(status, window(), "fa_mi355x_window_last_error", "flash_attn_mi355x_window")
+
+
+# the same for include/flash_attn_mi355x_lsink.h: libflash_attn_mi355x_lsink.so, the training side of learned sink logits: the windowed
+# forward with one logit per query head in every softmax, and the gradient of the logits (tests/test_lsink_cpu.py).  (LSINK_ABI above
+# is the decode library's family.)
+LSINK_TRAIN_ABI = {
+    "fa_mi355x_fwd_window_lsink": (_i, [_vp] * 6 + [_i] * 6 + [_f, _i, _i, _vp]),
+    "fa_mi355x_sink_logits_grad_workspace_bytes": (_sz, [_i] * 4),
+    "fa_mi355x_sink_logits_grad": (_i, [_vp] * 6 + [_i] * 6 + [_vp]),
+    "fa_mi355x_lsink_last_error": (_s, []),
+}
+LSINK_NAME = "libflash_attn_mi355x_lsink.so"
+
+
+def lsink() -> ctypes.CDLL:
+    """libflash_attn_mi355x_lsink.so (include/flash_attn_mi355x_lsink.h) with argtypes set."""
+    return _typed(LSINK_NAME, LSINK_TRAIN_ABI)
+
+
+def lsink_check(status: int) -> None:
+    if status != FA_OK:
+        _raise(status, lsink(), "fa_mi355x_lsink_last_error", "flash_attn_mi355x_lsink")
 
 
 # the same for include/flash_attn_mi355x_varlen.h: libflash_attn_mi355x_varlen.so, the packed variable-length (cu_seqlens) forward and

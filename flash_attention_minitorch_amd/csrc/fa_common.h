@@ -34,6 +34,19 @@ FA_DEV float cap_z(float r, float softcap) { return __builtin_fmaf(-2.0f * softc
 FA_DEV float cap_slope(float r) { return 4.0f * r * (1.0f - r); }
 FA_DEV float cap_score(float s, float k2, float softcap) { return cap_z(cap_rcp(s, k2), softcap); }
 
+// Learned sink logits: the end of a row of the LSINK builds.  m (raw score units, -inf: no admitted key) and l are the row's reduced
+// maximum and sum, tau the softmax scale, a the head's logit.  In log2 units mm = m c, zs = a log2(e), M = max(mm, zs): one of wa, ws
+// is 1 and the other at most 1, so denom >= 1 and nothing overflows for any finite a and m.  inv = wa / denom stands where 1 / l stood;
+// lse = ln(e^a + sum_j e^z_j).  A row without a key: inv = 0 and lse = a, the logit itself and not its round trip through log2.
+constexpr float LN2 = 0.6931471805599453f;
+FA_DEV void lsink_finish(float m, float l, float tau, float a, float& inv, float& lse) {
+  const float mm = m * (tau * LOG2E), zs = a * LOG2E, M = fmaxf(mm, zs);
+  const float wa = (m == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(mm - M), ws = __builtin_amdgcn_exp2f(zs - M);
+  const float denom = l * wa + ws;
+  inv = wa / denom;
+  lse = (m == -INFINITY) ? a : M * LN2 + __logf(denom);
+}
+
 template <typename T> FA_DEV typename Atom<T>::frag load_frag_buf(rsrc_t rs, int byte_off);
 template <> FA_DEV bf16x8 load_frag_buf<bf16_t>(rsrc_t rs, int byte_off) {
   return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, byte_off, 0, 0));

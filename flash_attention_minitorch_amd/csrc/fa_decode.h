@@ -80,6 +80,14 @@
 // tau = 1.  Key ranges, staging, page walk, window edges and the P.V products are the body's as they are.  No sinks and no fp8
 // cache beside a cap.  The softcap kernels share their body with the other builds as text, as the sink kernels do, so the other
 // builds are the code they were (DESIGN.md "Softcap").
+//
+// Learned sink logits (decode_split_lsink_kernel, extend_split_lsink_kernel, decode_combine_lsink_kernel;
+// include/flash_attn_mi355x_decode_lsink.h): gpt-oss's one fp32 logit per QUERY head, a column of every row's softmax that has no
+// value vector: lse = ln(e^a + sum_j e^z_j), P_j = e^(z_j - lse), out = P . V.  The logit is not scaled by tau and no mask touches
+// it.  Key ranges, staging, the online softmax and the partials are the body's as they are; the logit enters where a row is
+// FINISHED (lsink_finish): the one-split store of the split kernels, or the combine kernel behind its reduction, so it counts once
+// however many splits a row has, and the workspace holds what it held.  The array is read on the device at that point, one load
+// per row.  No sink tokens, no cap and no fp8 cache beside it.  Body shared as text, as above (DESIGN.md "Learned sinks").
 #pragma once
 #include "fa_common.h"
 
@@ -138,12 +146,23 @@ struct RaggedSoftcapArgs : RaggedArgs {
   float softcap;
 };
 template <bool RAGGED> using SoftcapArgsOf = typename std::conditional<RAGGED, RaggedSoftcapArgs, SoftcapArgs>::type;
+// The arguments of the LSINK builds, likewise: one learned logit per QUERY head, fp32 [H], read on the device (never null here: the
+// host sends a call without them to the other builds).
+struct LsinkArgs : DecodeArgs {
+  const float* sink_logits;
+};
+struct RaggedLsinkArgs : RaggedArgs {
+  const float* sink_logits;
+};
+template <bool RAGGED> using LsinkArgsOf = typename std::conditional<RAGGED, RaggedLsinkArgs, LsinkArgs>::type;
 template <bool RAGGED, bool FP8 = false>
 using DecodeArgsOf = typename std::conditional<FP8, Fp8Args, typename std::conditional<RAGGED, RaggedArgs, DecodeArgs>::type>::type;
 // (positive and finite is the caller's contract: the kernels do not check a scale)
 FA_DEV float scale_of(const float* scale, int hkv) { return scale ? scale[hkv] : 1.0f; }
 
 // (Soft-capping: cap_score and cap_k2 are in fa_common.h, which the training kernels of fa_window.h share.)
+
+// (Learned sink logits: lsink_finish, the end of a row, is in fa_common.h, which the training forward of fa_window.h shares.)
 
 FA_DEV int clamp_len(const int* seqlens, int Ncap, int b) {
   const int len = seqlens ? seqlens[b] : Ncap;
@@ -303,6 +322,7 @@ template <typename T, int D, bool GROUPED, bool PAGED = false, bool WINDOW = fal
 __global__ void __launch_bounds__(256) decode_split_kernel(DecodeArgsOf<false, FP8> a) {
   constexpr bool SINK = false;
   constexpr bool SOFTCAP = false;
+  constexpr bool LSINK = false;
 #include "fa_decode_split_body.h"
 }
 
@@ -312,6 +332,7 @@ template <typename T, int D, bool PAGED>
 __global__ void __launch_bounds__(256) decode_split_sink_kernel(SinkArgsOf<PAGED && false> a) {
   constexpr bool GROUPED = true, WINDOW = true, FP8 = false, SINK = true;
   constexpr bool SOFTCAP = false;
+  constexpr bool LSINK = false;
 #include "fa_decode_split_body.h"
 }
 
@@ -320,6 +341,15 @@ __global__ void __launch_bounds__(256) decode_split_sink_kernel(SinkArgsOf<PAGED
 template <typename T, int D, bool PAGED, bool WINDOW>
 __global__ void __launch_bounds__(256) decode_split_softcap_kernel(SoftcapArgsOf<PAGED && false> a) {
   constexpr bool GROUPED = true, FP8 = false, SINK = false, SOFTCAP = true;
+  constexpr bool LSINK = false;
+#include "fa_decode_split_body.h"
+}
+
+// The LSINK builds (a.sink_logits: one learned logit per query head): grouped, slab or paged, windowed or not.  They differ from
+// the other builds in the one-split store alone (lsink_finish); a partial in the workspace is the other builds' partial.
+template <typename T, int D, bool PAGED, bool WINDOW>
+__global__ void __launch_bounds__(256) decode_split_lsink_kernel(LsinkArgsOf<PAGED && false> a) {
+  constexpr bool GROUPED = true, FP8 = false, SINK = false, SOFTCAP = false, LSINK = true;
 #include "fa_decode_split_body.h"
 }
 
@@ -345,6 +375,7 @@ template <typename T, int D, bool PAGED = false, bool RAGGED = false, bool WINDO
 __global__ void __launch_bounds__(256) extend_split_kernel(DecodeArgsOf<RAGGED, FP8> a) {
   constexpr bool SINK = false;
   constexpr bool SOFTCAP = false;
+  constexpr bool LSINK = false;
 #include "fa_decode_extend_body.h"
 }
 
@@ -353,6 +384,7 @@ template <typename T, int D, bool PAGED, bool RAGGED>
 __global__ void __launch_bounds__(256) extend_split_sink_kernel(SinkArgsOf<RAGGED> a) {
   constexpr bool WINDOW = true, FP8 = false, SINK = true;
   constexpr bool SOFTCAP = false;
+  constexpr bool LSINK = false;
 #include "fa_decode_extend_body.h"
 }
 
@@ -360,6 +392,14 @@ __global__ void __launch_bounds__(256) extend_split_sink_kernel(SinkArgsOf<RAGGE
 template <typename T, int D, bool PAGED, bool RAGGED, bool WINDOW>
 __global__ void __launch_bounds__(256) extend_split_softcap_kernel(SoftcapArgsOf<RAGGED> a) {
   constexpr bool FP8 = false, SINK = false, SOFTCAP = true;
+  constexpr bool LSINK = false;
+#include "fa_decode_extend_body.h"
+}
+
+// The LSINK builds: slab or paged, uniform or ragged, windowed or not (as in decode_split_lsink_kernel: the one-split store).
+template <typename T, int D, bool PAGED, bool RAGGED, bool WINDOW>
+__global__ void __launch_bounds__(256) extend_split_lsink_kernel(LsinkArgsOf<RAGGED> a) {
+  constexpr bool FP8 = false, SINK = false, SOFTCAP = false, LSINK = true;
 #include "fa_decode_extend_body.h"
 }
 
@@ -372,56 +412,18 @@ __global__ void __launch_bounds__(256) extend_split_softcap_kernel(SoftcapArgsOf
 // FP8: the row's kv head is hd / a.G; its k_scale multiplies tau (the weights and the lse), its v_scale the final 1 / l.
 template <int D, bool RAGGED = false, bool FP8 = false>
 __global__ void __launch_bounds__(256) decode_combine_kernel(DecodeArgsOf<RAGGED, FP8> a) {
-  constexpr int G = D / 4, S = 256 / G;
-  __shared__ f32x4 red_o[256];
-  __shared__ float red_m[256], red_l[256];
-  const int tid = threadIdx.x, g = tid % G, j = tid / G;
-  const int row = blockIdx.x % a.Nq, bh = blockIdx.x / a.Nq;
-  if constexpr (RAGGED) {   // (workgroup-uniform: in front of the barriers)
-    int s0, n0, sl, nl;
-    seq_rows(a.cu, a.ntok, 0, s0, n0);
-    seq_rows(a.cu, a.ntok, a.nseq - 1, sl, nl);
-    if (row < s0 || row >= sl + nl) return;
-  }
-  const int b = bh / a.H, hd = bh - b * a.H;
-  float tau8 = 0.f;
-  if constexpr (FP8) tau8 = a.tau * scale_of(a.k_scale, hd / a.G);
-#define FA_TAU (FP8 ? tau8 : a.tau)
-  const float c = FA_TAU * LOG2E;
-  const size_t p0 = (size_t)bh * a.nsplit * a.Nq + row;   // partial row of split s: p0 + s * Nq
-  float m = -INFINITY;
-  for (int s = j; s < a.nsplit; s += S) m = fmaxf(m, a.part_ml[2 * (p0 + (size_t)s * a.Nq)]);
-  red_m[tid] = m;
-  __syncthreads();
-  float m_all = -INFINITY;
-  for (int u = 0; u < S; ++u) m_all = fmaxf(m_all, red_m[u * G + g]);
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  float l = 0.f;
-  if (m_all != -INFINITY) {
-    for (int s = j; s < a.nsplit; s += S) {
-      const size_t p = p0 + (size_t)s * a.Nq;
-      const f32x2 ml = *reinterpret_cast<const f32x2*>(a.part_ml + 2 * p);
-      if (ml[0] == -INFINITY) continue;
-      const float wgt = __builtin_amdgcn_exp2f((ml[0] - m_all) * c);
-      l += ml[1] * wgt;
-      acc += *reinterpret_cast<const f32x4*>(a.part_o + p * D + 4 * g) * wgt;
-    }
-  }
-  red_o[tid] = acc;
-  red_l[tid] = l;
-  __syncthreads();
-  if (j != 0) return;
-  for (int u = 1; u < S; ++u) {
-    acc += red_o[u * G + g];
-    l += red_l[u * G + g];
-  }
-  float inv = (l > 0.f) ? 1.0f / l : 0.f;
-  if constexpr (FP8) inv *= scale_of(a.v_scale, hd / a.G);
-  float* orow = a.out + (size_t)b * a.q_bstride + (size_t)hd * a.q_hstride + (size_t)row * a.q_ld;
-  *reinterpret_cast<f32x4*>(orow + 4 * g) = acc * inv;
-  if (g == 0 && a.lse) a.lse[(size_t)bh * a.Nq + row] = (l > 0.f) ? m_all * FA_TAU + __logf(l) : -INFINITY;
+  constexpr bool LSINK = false;
+#include "fa_decode_combine_body.h"
 }
-#undef FA_TAU
+
+// The LSINK build of the combine kernel (uniform and ragged): the partials are the other builds' (unnormalised, without the logit),
+// and the row's sink column joins once, behind the reduction (lsink_finish).  The body is fa_decode_combine_body.h, included as
+// text in both kernels.
+template <int D, bool RAGGED>
+__global__ void __launch_bounds__(256) decode_combine_lsink_kernel(LsinkArgsOf<RAGGED> a) {
+  constexpr bool FP8 = false, LSINK = true;
+#include "fa_decode_combine_body.h"
+}
 
 // ---- ragged: the block map -------------------------------------------------------------------------------------------------------
 // One workgroup turns cu into the block map of the ragged extend kernel: for b = 0, 1, ... in order, one entry (b, qb) for each of

@@ -1,5 +1,5 @@
 // C ABI of the MI355X KV-cache decode library (declared in include/flash_attn_mi355x_decode.h and its _paged.h, _ragged.h,
-// _window.h, _sink.h, _fp8.h, _softcap.h and _rope.h).  Every entry point fills one KvCall (the call as it was received) and hands it to run():
+// _window.h, _sink.h, _fp8.h, _softcap.h, _lsink.h and _rope.h).  Every entry point fills one KvCall (the call as it was received) and hands it to run():
 // the entry point's prelude (check_fp8 or check_window), the page geometry (check_pages), the attention's checks (check_attend, which
 // also returns the call's Policy), the append's (check_append), then the append launch (run_append) and the attention's launches
 // (run_attend -> launch_split).  policy() is the one split policy: the three families (decode: 32-row blocks, at most 128 queries;
@@ -8,7 +8,8 @@
 // the policy on its window span (span_keys) instead of Ncap, a sink call on that span plus its sink tiles.  An fp8 call (caches of
 // e4m3 bytes, per-kv-head scales) takes the bf16 call's policy and workspace for the same arguments; its cache bounds count one byte
 // per element.  A soft-capped call (softcap > 0) takes the policy and workspace of the same call without the cap, the softcap builds
-// of the split kernels and the existing combine kernels with tau = 1.  The rotary calls launch the kernels of fa_rope.h in front of the attend-only entry points.
+// of the split kernels and the existing combine kernels with tau = 1.  A call with learned sink logits (sink_logits not null) takes
+// the policy and workspace of the same call without them, the lsink builds of the split kernels and of the combine kernel.  The rotary calls launch the kernels of fa_rope.h in front of the attend-only entry points.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -95,6 +96,7 @@ struct KvCall {
   int layout = 0, causal = 0, window = 0, sink = 0, dtype = 0;
   float softmax_scale = 0.f;
   float softcap = 0.f;   // logit soft-capping (_softcap.h); 0: none
+  const float* sink_logits = nullptr;   // learned sink logits (_lsink.h), fp32 [H] on the device; null: none
   hipStream_t stream = nullptr;
 
   explicit KvCall(Family f) : family(f) {}
@@ -362,7 +364,15 @@ struct SplitArgs : fa::RaggedArgs {
   Fp8 f8;
   int sink;        // S >= 1: a sink reaches the device
   float softcap;   // > 0: the softcap builds (SoftcapArgs, RaggedSoftcapArgs), and tau = 1 for the combine kernel
+  const float* sink_logits;   // not null: the lsink builds (LsinkArgs, RaggedLsinkArgs) and the lsink build of the combine kernel
 };
+
+template <typename S, typename Base> S with_lsink(const SplitArgs& a) {
+  S s;
+  static_cast<Base&>(s) = a;
+  s.sink_logits = a.sink_logits;
+  return s;
+}
 
 template <typename S, typename Base> S with_softcap(const SplitArgs& a) {
   S s;
@@ -401,6 +411,8 @@ template <typename A, typename B> void launch256(void (*kernel)(A), long grid, h
 //   fp8     bf16 queries, slab or paged, no window (the Python layer refuses the combination by name)
 //   softcap kernels and an argument of their own, only when a cap reaches the device (a.softcap > 0): PAGED x WINDOW as the call has
 //           them, the grouped build in the decode family; the combine launch is the existing instance with tau = 1
+//   lsink   kernels and an argument of their own, only when the logits reach the device (a.sink_logits not null): the softcap
+//           legs' choice of builds, and the lsink build of the combine kernel; as many launches as the call without the logits
 template <typename T, int D> int launch_split(const SplitArgs& a, Family f, hipStream_t st) {
   constexpr bool BF16 = std::is_same<T, fa::bf16_t>::value;
   const bool paged = a.table != nullptr, window = a.window != 0;
@@ -439,6 +451,26 @@ template <typename T, int D> int launch_split(const SplitArgs& a, Family f, hipS
       else if (window) launch256(fa::decode_split_softcap_kernel<T, D, false, true>, grid, st, ca);
       else if (paged) launch256(fa::decode_split_softcap_kernel<T, D, true, false>, grid, st, ca);
       else launch256(fa::decode_split_softcap_kernel<T, D, false, false>, grid, st, ca);
+    }
+  } else if (a.sink_logits) {   // (no sink tokens, no cap and no fp8 cache beside the logits: the lsink entry points have none of them)
+    if (f == RAGGED) {
+      what = "extend_split_lsink_kernel (ragged) launch";
+      const fa::RaggedLsinkArgs la = with_lsink<fa::RaggedLsinkArgs, fa::RaggedArgs>(a);
+      if (window && paged) launch256(fa::extend_split_lsink_kernel<T, D, true, true, true>, grid, st, la);
+      else if (window) launch256(fa::extend_split_lsink_kernel<T, D, false, true, true>, grid, st, la);
+      else if (paged) launch256(fa::extend_split_lsink_kernel<T, D, true, true, false>, grid, st, la);
+      else launch256(fa::extend_split_lsink_kernel<T, D, false, true, false>, grid, st, la);
+    } else {
+      what = f == EXTEND ? "extend_split_lsink_kernel launch" : "decode_split_lsink_kernel launch";
+      const fa::LsinkArgs la = with_lsink<fa::LsinkArgs, fa::DecodeArgs>(a);
+      if (f == EXTEND && window && paged) launch256(fa::extend_split_lsink_kernel<T, D, true, false, true>, grid, st, la);
+      else if (f == EXTEND && window) launch256(fa::extend_split_lsink_kernel<T, D, false, false, true>, grid, st, la);
+      else if (f == EXTEND && paged) launch256(fa::extend_split_lsink_kernel<T, D, true, false, false>, grid, st, la);
+      else if (f == EXTEND) launch256(fa::extend_split_lsink_kernel<T, D, false, false, false>, grid, st, la);
+      else if (window && paged) launch256(fa::decode_split_lsink_kernel<T, D, true, true>, grid, st, la);
+      else if (window) launch256(fa::decode_split_lsink_kernel<T, D, false, true>, grid, st, la);
+      else if (paged) launch256(fa::decode_split_lsink_kernel<T, D, true, false>, grid, st, la);
+      else launch256(fa::decode_split_lsink_kernel<T, D, false, false>, grid, st, la);
     }
   } else if (f == DECODE) {
     if (a.sink) {
@@ -479,6 +511,9 @@ template <typename T, int D> int launch_split(const SplitArgs& a, Family f, hipS
     one.tau = 1.0f;
     const SplitArgs& ca = a.softcap > 0.f ? one : a;
     if (a.f8.on) launch256(fa::decode_combine_kernel<D, false, true>, rows, st, with_scales(a));
+    else if (a.sink_logits && f == RAGGED)   // (the logits: the lsink build, which adds the sink column behind its reduction)
+      launch256(fa::decode_combine_lsink_kernel<D, true>, rows, st, with_lsink<fa::RaggedLsinkArgs, fa::RaggedArgs>(a));
+    else if (a.sink_logits) launch256(fa::decode_combine_lsink_kernel<D, false>, rows, st, with_lsink<fa::LsinkArgs, fa::DecodeArgs>(a));
     else if (f == RAGGED) launch256(fa::decode_combine_kernel<D, true>, rows, st, ca);
     else launch256(fa::decode_combine_kernel<D>, rows, st, ca);
     e = hipGetLastError();
@@ -532,6 +567,7 @@ int run_attend(const KvCall& c, const Policy& p) {
   a.tau = c.softmax_scale > 0.f ? c.softmax_scale : sqrtf(1.0f / (float)c.d);
   a.f8 = c.f8;
   a.softcap = c.softcap;
+  a.sink_logits = c.sink_logits;
   return c.dtype == FA_DTYPE_BF16 ? launch_split_d<fa::bf16_t>(a, c.family, c.d, c.stream) : launch_split_d<float>(a, c.family, c.d, c.stream);
 }
 
@@ -1067,6 +1103,44 @@ int fa_mi355x_fwd_ragged_softcap(const void* q, const void* k_new, const void* v
   if (k_new || v_new) c.new_tokens(k_new, v_new, d_new);
   c.cu = cu_seqlens_q;
   c.window = window, c.softcap = softcap;
+  return run(c);
+}
+
+// ---- learned sink logits (_lsink.h): the windowed forms with the logits behind the window; null sink_logits is the _window call ----
+int fa_mi355x_fwd_decode_lsink(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
+                               const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv, int Nq, int Ncap,
+                               int num_pages, int page_size, int max_pages, int d_new, int d, int layout, float softmax_scale, int causal,
+                               int window, const float* sink_logits, int dtype, void* stream) {
+  KvCall c(DECODE);
+  c.attention(q, out, lse, workspace, softmax_scale, causal).cache(k_cache, v_cache, cache_seqlens, Ncap);
+  c.pool_or_slabs(block_table, num_pages, page_size, max_pages).heads(B, H, Hkv, Nq, d).format(layout, dtype, stream);
+  if (k_new || v_new) c.new_tokens(k_new, v_new, d_new);
+  c.window = window, c.sink_logits = sink_logits;
+  return run(c);
+}
+
+int fa_mi355x_fwd_extend_lsink(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
+                               const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv, int Nq, int Ncap,
+                               int num_pages, int page_size, int max_pages, int d_new, int d, int layout, float softmax_scale, int causal,
+                               int window, const float* sink_logits, int dtype, void* stream) {
+  KvCall c(EXTEND);
+  c.attention(q, out, lse, workspace, softmax_scale, causal).cache(k_cache, v_cache, cache_seqlens, Ncap);
+  c.pool_or_slabs(block_table, num_pages, page_size, max_pages).heads(B, H, Hkv, Nq, d).format(layout, dtype, stream);
+  if (k_new || v_new) c.new_tokens(k_new, v_new, d_new);
+  c.window = window, c.sink_logits = sink_logits;
+  return run(c);
+}
+
+int fa_mi355x_fwd_ragged_lsink(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
+                               const int* cu_seqlens_q, const int* cache_seqlens, const int* block_table, void* workspace, int B, int H,
+                               int Hkv, int T, int Ncap, int num_pages, int page_size, int max_pages, int d_new, int d, int layout,
+                               float softmax_scale, int causal, int window, const float* sink_logits, int dtype, void* stream) {
+  KvCall c(RAGGED);
+  c.attention(q, out, lse, workspace, softmax_scale, causal).cache(k_cache, v_cache, cache_seqlens, Ncap);
+  c.pool_or_slabs(block_table, num_pages, page_size, max_pages).heads(B, H, Hkv, T, d).format(layout, dtype, stream);
+  if (k_new || v_new) c.new_tokens(k_new, v_new, d_new);
+  c.cu = cu_seqlens_q;
+  c.window = window, c.sink_logits = sink_logits;
   return run(c);
 }
 

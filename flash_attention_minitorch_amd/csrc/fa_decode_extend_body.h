@@ -1,10 +1,11 @@
-// The body of extend_split_kernel, extend_split_sink_kernel and extend_split_softcap_kernel (fa_decode.h), included INSIDE each: plain text, not a
+// The body of extend_split_kernel and its _sink, _softcap and _lsink kernels (fa_decode.h), included INSIDE each: plain text, not a
 // function.  A function template that both kernels call is inlined only after it has been simplified on its own, and every existing
 // build of the kernel then comes out with other code than it had (compared per kernel: profiles/sink_isa_identity.txt); as text the
-// existing kernel is the function it was.  In scope: T, D, PAGED, RAGGED, WINDOW, FP8, SINK, SOFTCAP and the kernel's argument a.
+// existing kernel is the function it was.  In scope: T, D, PAGED, RAGGED, WINDOW, FP8, SINK, SOFTCAP, LSINK and the kernel's argument a.
   static_assert(!FP8 || (std::is_same<T, bf16_t>::value && !RAGGED && !WINDOW), "fp8 caches: bf16 queries, no ragged form, no window");
   static_assert(!SINK || (WINDOW && !FP8), "sinks: beside a window, no fp8 cache");
   static_assert(!SOFTCAP || (!FP8 && !SINK), "soft-capping: no fp8 cache, no sinks");
+  static_assert(!LSINK || (!FP8 && !SINK && !SOFTCAP), "learned sink logits: no fp8 cache, no sink tokens, no cap");
   using A = Atom<T>;
   typedef typename std::conditional<FP8, uint8_t, T>::type C;
   typedef typename A::frag frag;
@@ -199,6 +200,8 @@
   if (a.nsplit == 1) {   // final: out = O / l, lse = m * tau + ln l; a row without an admissible key: out = 0, lse = -inf
     float inv = (l_tot > 0.f) ? 1.0f / l_tot : 0.f;
     if constexpr (FP8) inv *= scale_of(a.v_scale, hkv);   // (the scale of V: once per row, on 1 / l)
+    float lse_s = 0.f;   // (lsink builds: the head's logit joins the row as one more column; a row without a key: out = 0, lse = a)
+    if constexpr (LSINK) lsink_finish(m_run, l_tot, FA_TAU, a.sink_logits[hd], inv, lse_s);
     float* orow = a.out + (RAGGED ? 0 : (size_t)b * a.q_bstride) + (size_t)hd * a.q_hstride + (size_t)(RAGGED ? row0 + qi : qi) * a.q_ld;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt)
@@ -207,7 +210,11 @@
         f32x4 val = {acc_o[dt][4 * g] * inv, acc_o[dt][4 * g + 1] * inv, acc_o[dt][4 * g + 2] * inv, acc_o[dt][4 * g + 3] * inv};
         *reinterpret_cast<f32x4*>(orow + 32 * dt + 8 * g + 4 * h) = val;
       }
-    if (h == 0 && a.lse) a.lse[bhq * a.Nq + (RAGGED ? row0 + qi : qi)] = (l_tot > 0.f) ? m_run * FA_TAU + __logf(l_tot) : -INFINITY;
+    if constexpr (LSINK) {
+      if (h == 0 && a.lse) a.lse[bhq * a.Nq + (RAGGED ? row0 + qi : qi)] = lse_s;
+    } else {
+      if (h == 0 && a.lse) a.lse[bhq * a.Nq + (RAGGED ? row0 + qi : qi)] = (l_tot > 0.f) ? m_run * FA_TAU + __logf(l_tot) : -INFINITY;
+    }
   } else {
     const size_t pr = (bhq * a.nsplit + split) * a.Nq + (RAGGED ? row0 + qi : qi);
     float* prow = a.part_o + pr * D;

@@ -67,6 +67,9 @@ struct WinWalk {
 #define FA_WIN_NAME(stem) FA_WIN_KERNEL(stem)
 #define FA_WIN_CAP_PARAM
 #define FA_WIN_CAP_VALUE 0.f
+#define FA_WIN_LSINK 0
+#define FA_WIN_LSINK_PARAM
+#define FA_WIN_LSINK_LOGIT 0.f
 #include "fa_window_body.h"
 #undef FA_WIN_CAP
 #undef FA_WIN_NAME
@@ -82,6 +85,34 @@ struct WinWalk {
 #undef FA_WIN_NAME
 #undef FA_WIN_CAP_PARAM
 #undef FA_WIN_CAP_VALUE
+#endif
+#undef FA_WIN_LSINK
+#undef FA_WIN_LSINK_PARAM
+#undef FA_WIN_LSINK_LOGIT
+// Once more, where the includer asks for it, with learned sink logits in the FORWARD's epilogue (include/flash_attn_mi355x_lsink.h):
+// the head's logit a = sink_logits[bh % sink_heads] joins the row's softmax as a column without a value vector where the row's
+// 1 / l is formed (lsink_finish of fa_common.h, the KV-cache calls' arithmetic): out = O wa / denom, lse = ln(e^a + sum_j e^z_j).
+// Every difference sits under `if constexpr (LSINK)`, so the other builds are the code they were.  The backward needs no build: P =
+// exp2(s c - lse log2 e) and delta = rowsum(dO o out) are what the dQ and dK/dV kernels form from the lse and out they are given, and
+// with this forward's lse and out those are the sink softmax's (the dq and dkdv templates of this inclusion are never instantiated).
+// Only fa_lsink.hip defines FA_WIN_LSINK_KERNEL: neither the window library nor the packed one gains a kernel.
+//   FA_WIN_LSINK_KERNEL(stem)   the name of the kernel's lsink build; undefined: no lsink builds
+#ifdef FA_WIN_LSINK_KERNEL
+#define FA_WIN_CAP 0
+#define FA_WIN_NAME(stem) FA_WIN_LSINK_KERNEL(stem)
+#define FA_WIN_CAP_PARAM
+#define FA_WIN_CAP_VALUE 0.f
+#define FA_WIN_LSINK 1
+#define FA_WIN_LSINK_PARAM , const float* __restrict__ sink_logits, int sink_heads
+#define FA_WIN_LSINK_LOGIT sink_logits[bh % sink_heads]
+#include "fa_window_body.h"
+#undef FA_WIN_CAP
+#undef FA_WIN_NAME
+#undef FA_WIN_CAP_PARAM
+#undef FA_WIN_CAP_VALUE
+#undef FA_WIN_LSINK
+#undef FA_WIN_LSINK_PARAM
+#undef FA_WIN_LSINK_LOGIT
 #endif
 
 }  // namespace fa

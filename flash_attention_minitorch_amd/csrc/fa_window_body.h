@@ -1,6 +1,8 @@
 // The three kernels of fa_window.h, included by that file INSIDE namespace fa: plain text, not a header (no #pragma once), read
 // once per build.  In scope: the FA_WIN_* hooks of fa_window.h, FA_WIN_NAME (the kernel's name in this build), FA_WIN_CAP (1: the
-// soft-capping build), FA_WIN_CAP_PARAM (its extra argument) and FA_WIN_CAP_VALUE (the cap, 0.f in the other build).
+// soft-capping build), FA_WIN_CAP_PARAM (its extra argument) and FA_WIN_CAP_VALUE (the cap, 0.f in the other build); FA_WIN_LSINK
+// (1: the forward ends its rows with a learned sink logit), FA_WIN_LSINK_PARAM (the forward's extra arguments) and
+// FA_WIN_LSINK_LOGIT (the row's logit, 0.f in the other builds).
 //
 // The cap builds (CAP): k2 = cap_k2(tau, softcap) once per workgroup, r = cap_rcp(s, k2) and z = cap_z(r, softcap) per score, in
 // front of the masks (a mask applied first would come out of the cap as -softcap, an admitted key).  From there the scores are the
@@ -17,7 +19,8 @@
 template <typename T, int D, int BN>
 __global__ void __launch_bounds__(256)
 FA_WIN_NAME(fwd)(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, float* __restrict__ o,
-                   float* __restrict__ lse, FA_WIN_GEOM_PARAMS, Layout lay, float tau, FA_WIN_MASK_PARAMS FA_WIN_CAP_PARAM) {
+                   float* __restrict__ lse, FA_WIN_GEOM_PARAMS, Layout lay, float tau, FA_WIN_MASK_PARAMS FA_WIN_CAP_PARAM
+                   FA_WIN_LSINK_PARAM) {
   using A = Atom<T>;
   typedef typename A::frag frag;
   constexpr int KC = D / 16, KT = BN / 32, DT = D / 32;
@@ -193,7 +196,10 @@ FA_WIN_NAME(fwd)(const T* __restrict__ q, const T* __restrict__ k, const T* __re
 
   const float l_tot = xhalf_sum(l_run);   // > 0 for every real row: it admits its own position
   if (qvalid) {
-    const float inv = 1.0f / l_tot;
+    constexpr bool LSINK = FA_WIN_LSINK;   // (lsink build: the head's logit joins the row where its 1 / l is formed)
+    float inv_s = 0.f, lse_s = 0.f;
+    if constexpr (LSINK) lsink_finish(m_ref, l_tot, tau, FA_WIN_LSINK_LOGIT, inv_s, lse_s);
+    const float inv = LSINK ? inv_s : 1.0f / l_tot;
     float* orow = o + base + (size_t)qrow * ld;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt)
@@ -202,7 +208,7 @@ FA_WIN_NAME(fwd)(const T* __restrict__ q, const T* __restrict__ k, const T* __re
         f32x4 val = {acc_o[dt][4 * g] * inv, acc_o[dt][4 * g + 1] * inv, acc_o[dt][4 * g + 2] * inv, acc_o[dt][4 * g + 3] * inv};
         *reinterpret_cast<f32x4*>(orow + 32 * dt + 8 * g + 4 * h) = val;
       }
-    if (h == 0) lse[FA_WIN_ROWCONST0 + qrow] = (CAP ? m_ref : m_ref * tau) + __logf(l_tot);
+    if (h == 0) lse[FA_WIN_ROWCONST0 + qrow] = LSINK ? lse_s : (CAP ? m_ref : m_ref * tau) + __logf(l_tot);
   }
 }
 

@@ -571,14 +571,28 @@ class _FlashAttnGqaFn(torch.autograd.Function):
         return dq.to(q.dtype), dk.to(q.dtype), dv.to(q.dtype), None, None, None
 
 
-def flash_attn_gqa(q, k, v, causal=False, softmax_scale=None, layout="bnhd", window=None, sink=None, softcap=None):
+def flash_attn_gqa(q, k, v, causal=False, softmax_scale=None, layout="bnhd", window=None, sink=None, softcap=None, sink_logits=None):
     """Attention with grouped-query heads under autograd (FA-2): out fp32 in q's shape; q.grad in q's shape and dtype, k.grad and
     v.grad in k's.  ``window`` = W (with ``sink`` = S): row i admits key j iff j <= i and (j > i - W or j < S), the mask of the
     KV-cache calls, through the kernels of libflash_attn_mi355x_window.so; None or 0, W >= N or S >= N is this call without them.
     ``softcap`` = C (causal only): LOGIT SOFT-CAPPING, every score becomes C * tanh(softmax_scale * q.k / C) before the mask, the
     function of flash_attn_decode(..., softcap=), differentiated through the cap (fa_mi355x_fwd_window_softcap / _bwd_window_softcap;
-    without a window the call passes W = N).  None or 0 is this call without a cap."""
+    without a window the call passes W = N).  None or 0 is this call without a cap.
+    ``sink_logits`` (causal only; a contiguous float32 (H,) tensor on q's device, which may require grad): LEARNED SINK LOGITS, one
+    per query head, a column of every softmax without a value vector, the function of flash_attn_decode(..., sink_logits=)
+    (fa_mi355x_fwd_window_lsink; dq, dk, dv through fa_mi355x_bwd_window on this forward's out and lse; ``sink_logits.grad`` float32
+    (H,) through fa_mi355x_sink_logits_grad, launched only when the logits require grad).  Works with ``window``; beside
+    ``causal=False``, ``softcap`` or ``sink`` it is a ValueError (not built).  None is this call without them."""
     N = q.shape[1 if layout == "bnhd" else 2] if q.dim() == 4 else 0
+    if sink_logits is not None:
+        if not causal:
+            raise ValueError("sink_logits without the causal mask is not built: sink_logits= with causal=False")
+        if _check_softcap(softcap) is not None:
+            raise ValueError("sink_logits beside a logit cap is not built: sink_logits= with softcap=")
+        window = _check_window(window, causal)
+        if _check_sink(sink, window) is not None:
+            raise ValueError("sink_logits beside sink tokens is not built: sink_logits= with sink=")
+        return _lsink_fn(q, k, v, sink_logits, softmax_scale, layout, min(window or N, N) or 1)
     softcap = _check_softcap(softcap)
     if softcap is not None and not causal:
         raise ValueError("softcap without the causal mask is not built: softcap= with causal=False")
@@ -638,7 +652,8 @@ _KV_FAMILIES = {
         symbols=dict(
             ungrouped="fa_mi355x_fwd_decode", attend="fa_mi355x_fwd_decode_gqa", fused="fa_mi355x_fwd_decode_append",
             paged="fa_mi355x_fwd_decode_paged", fused_paged="fa_mi355x_fwd_decode_append_paged", window="fa_mi355x_fwd_decode_window",
-            sink="fa_mi355x_fwd_decode_sink", softcap="fa_mi355x_fwd_decode_softcap", fp8="fa_mi355x_fwd_decode_fp8",
+            sink="fa_mi355x_fwd_decode_sink", softcap="fa_mi355x_fwd_decode_softcap", lsink="fa_mi355x_fwd_decode_lsink",
+            fp8="fa_mi355x_fwd_decode_fp8",
             append="fa_mi355x_decode_append",
             append_paged="fa_mi355x_decode_append_paged", append_fp8="fa_mi355x_append_fp8", rope="fa_mi355x_rope_append",
             size_ungrouped="fa_mi355x_decode_workspace_bytes", size="fa_mi355x_decode_workspace_bytes_gqa",
@@ -650,7 +665,8 @@ _KV_FAMILIES = {
         symbols=dict(
             attend="fa_mi355x_fwd_extend", fused="fa_mi355x_fwd_extend_append", paged="fa_mi355x_fwd_extend_paged",
             fused_paged="fa_mi355x_fwd_extend_append_paged", window="fa_mi355x_fwd_extend_window", sink="fa_mi355x_fwd_extend_sink",
-            softcap="fa_mi355x_fwd_extend_softcap", fp8="fa_mi355x_fwd_extend_fp8", append="fa_mi355x_extend_append",
+            softcap="fa_mi355x_fwd_extend_softcap", lsink="fa_mi355x_fwd_extend_lsink", fp8="fa_mi355x_fwd_extend_fp8",
+            append="fa_mi355x_extend_append",
             append_paged="fa_mi355x_extend_append_paged",
             append_fp8="fa_mi355x_append_fp8", rope="fa_mi355x_rope_append", size="fa_mi355x_extend_workspace_bytes",
             size_window="fa_mi355x_extend_window_workspace_bytes", size_sink="fa_mi355x_extend_sink_workspace_bytes")),
@@ -661,20 +677,22 @@ _KV_FAMILIES = {
         symbols=dict(
             attend="fa_mi355x_fwd_ragged", fused="fa_mi355x_fwd_ragged_append", paged="fa_mi355x_fwd_ragged_paged",
             fused_paged="fa_mi355x_fwd_ragged_append_paged", window="fa_mi355x_fwd_ragged_window", sink="fa_mi355x_fwd_ragged_sink",
-            softcap="fa_mi355x_fwd_ragged_softcap", append="fa_mi355x_ragged_append", append_paged="fa_mi355x_ragged_append_paged",
+            softcap="fa_mi355x_fwd_ragged_softcap", lsink="fa_mi355x_fwd_ragged_lsink", append="fa_mi355x_ragged_append",
+            append_paged="fa_mi355x_ragged_append_paged",
             rope="fa_mi355x_rope_append_ragged",
             size="fa_mi355x_ragged_workspace_bytes", size_window="fa_mi355x_ragged_window_workspace_bytes",
             size_sink="fa_mi355x_ragged_sink_workspace_bytes")),
 }
 
 
-def _kv_symbol(fam, op, paged=False, fused=False, window=None, sink=None, fp8=False, ungrouped=False, softcap=None):
+def _kv_symbol(fam, op, paged=False, fused=False, window=None, sink=None, fp8=False, ungrouped=False, softcap=None, lsink=False):
     """The C symbol of a call.  ``op`` "append": the append (fa_mi355x_append_fp8 takes slab and paged caches alike); "size": the size
     query; "attend": the attention -- one entry point per family on an fp8 cache, with sink tokens and with a window (null k_new /
     v_new attend only, a null table is a slab cache), otherwise the _paged and the fused _append forms.  ``window`` None takes the
     unwindowed symbols; ``ungrouped`` (Hkv = H) the ones without an Hkv, where the family has them.  ``softcap`` (not None: a cap
     above 0, never beside sink tokens or an fp8 cache) takes the family's one soft-capping entry point, windowed or not; the size
-    queries do not depend on it."""
+    queries do not depend on it.  ``lsink`` (learned sink logits: never beside a cap, sink tokens or an fp8 cache) takes the family's
+    one _lsink entry point, likewise."""
     symbols = fam["symbols"]
     if op == "append":
         return symbols["append_fp8" if fp8 else "append_paged" if paged else "append"]
@@ -686,6 +704,8 @@ def _kv_symbol(fam, op, paged=False, fused=False, window=None, sink=None, fp8=Fa
         return symbols["size_ungrouped"] if ungrouped and "size_ungrouped" in symbols else symbols["size"]
     if softcap is not None:
         return symbols["softcap"]
+    if lsink:
+        return symbols["lsink"]
     if fp8:
         return symbols["fp8"]
     if sink is not None:
@@ -806,6 +826,17 @@ def _check_softcap(softcap):
     if isinstance(softcap, (bool, str)) or not isinstance(softcap, numbers.Real) or not math.isfinite(softcap) or softcap < 0:
         raise ValueError("softcap must be None or a finite number >= 0: the logit cap, softcap * tanh(score / softcap) (None or 0: none)")
     return float(softcap) or None
+
+
+def _check_sink_logits(sink_logits, H, device):
+    """``sink_logits`` of a call with H query heads whose q lives on ``device``: None, or a contiguous float32 (H,) tensor there (one
+    learned logit per QUERY head, read on the device)."""
+    if sink_logits is None:
+        return None
+    if (not isinstance(sink_logits, torch.Tensor) or sink_logits.dtype != torch.float32 or tuple(sink_logits.shape) != (H,)
+            or sink_logits.device != device or not sink_logits.is_contiguous()):
+        raise ValueError(f"sink_logits must be a contiguous float32 tensor of shape (H,) = ({H},) on q's device: one logit per query head")
+    return sink_logits
 
 
 # ---- sliding window and attention sinks in the training forward and backward: fa_mi355x_fwd_window / _bwd_window ------------------
@@ -931,20 +962,23 @@ class _FlashAttnSideFn(torch.autograd.Function):
     """A family's public forward and backward (``fwd``, ``bwd``: flash_attn_fwd_window / _bwd_window, flash_attn_varlen_fwd / _bwd,
     flash_attn_varlen_bidir_fwd / _bwd) under autograd.  ``index``: the tensors both take behind the operands (the cu_seqlens arrays);
     ``options``: the keywords both take.  The forward saves q, the unexpanded k and v, o, lse and the index tensors; gradients are cast
-    to the input dtype (k and v have q's, by the checks)."""
+    to the input dtype (k and v have q's, by the checks).  ``learned``: further DIFFERENTIABLE tensors both take behind the index (the
+    learned sink logits); ``bwd`` then also takes ``wanted``, which of them need a gradient, and returns theirs (None where not
+    wanted) behind dq, dk, dv."""
 
     @staticmethod
-    def forward(ctx, fwd, bwd, q, k, v, index, options):
-        o, lse = fwd(q, k, v, *index, **options)
-        ctx.save_for_backward(q, k, v, o, lse, *index)
-        ctx.bwd, ctx.options = bwd, options
+    def forward(ctx, fwd, bwd, q, k, v, index, options, *learned):
+        o, lse = fwd(q, k, v, *index, *learned, **options)
+        ctx.save_for_backward(q, k, v, o, lse, *index, *learned)
+        ctx.bwd, ctx.options, ctx.n_learned = bwd, options, len(learned)
         return o
 
     @staticmethod
     def backward(ctx, out_grad):
-        q, k, v, o, lse, *index = ctx.saved_tensors
-        dq, dk, dv = ctx.bwd(q, k, v, o, out_grad.to(q.dtype).contiguous(), lse, *index, **ctx.options)
-        return None, None, dq.to(q.dtype), dk.to(q.dtype), dv.to(q.dtype), None, None
+        q, k, v, o, lse, *rest = ctx.saved_tensors
+        more = {"wanted": tuple(ctx.needs_input_grad[7:])} if ctx.n_learned else {}
+        dq, dk, dv, *dlearned = ctx.bwd(q, k, v, o, out_grad.to(q.dtype).contiguous(), lse, *rest, **ctx.options, **more)
+        return (None, None, dq.to(q.dtype), dk.to(q.dtype), dv.to(q.dtype), None, None, *dlearned)
 
 
 def _native_head_dim(q, k, v, softmax_scale, attend):
@@ -962,6 +996,75 @@ def _window_fn(q, k, v, softmax_scale, layout, window, sink, softcap):
     """flash_attn_gqa under a sliding window (and sink tokens), with or without a logit cap."""
     return _FlashAttnSideFn.apply(flash_attn_fwd_window, flash_attn_bwd_window, q, k, v, (),
                                   dict(window=window, sink=sink, softmax_scale=softmax_scale, layout=layout, softcap=softcap))
+
+
+# ---- learned sink logits in training (include/flash_attn_mi355x_lsink.h; libflash_attn_mi355x_lsink.so) ------------------------------
+# gpt-oss's one fp32 logit per query head, a column of every row's softmax without a value vector, under the causal (windowed) mask:
+# the function flash_attn_decode(..., sink_logits=) generates with.  The forward is a kernel of its own; dq, dk and dv are
+# flash_attn_bwd_window on this forward's out and lse (P = exp2(s c - lse log2 e) and delta = rowsum(dO o out) are what it computes
+# from what it is given); the gradient of the logits, d a_h = -sum_{b,i} e^(a_h - lse_bhi) delta_bhi, is sink_logits_grad.
+
+def flash_attn_fwd_window_lsink(q, k, v, window, sink_logits, softmax_scale=None, layout="bnhd", out=None):
+    """Causal forward under a sliding window of ``window`` positions (>= 1; N and above: no window) with learned sink logits
+    (fa_mi355x_fwd_window_lsink): ``sink_logits`` a contiguous float32 (H,) tensor on q's device, read there.  Grouped-query heads as
+    flash_attn_fwd_gqa.  Returns (out fp32 in q's shape, lse (B, H, N) = ln(e^a + sum_j e^z_j))."""
+    window, _ = _check_window_call(window, None)
+    B, H, Hkv, N, d, dtype = _check_gqa(layout, q, k, v)
+    _check_sink_logits(sink_logits, H, q.device)
+    if sink_logits is None:
+        raise ValueError("sink_logits must be a contiguous float32 (H,) tensor: flash_attn_fwd_window is the call without the logits")
+    _check_out(out, q)
+    lse = torch.empty((B, H, N), dtype=_F32, device=q.device)
+    if out is None:
+        out, = _new_f32(q)
+    _lib.lsink_check(_lib.lsink().fa_mi355x_fwd_window_lsink(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), _ptr(sink_logits), B, H, Hkv, N,
+                                                            d, _DECODE_LAYOUTS[layout], float(softmax_scale or 0.0), window, dtype,
+                                                            _stream_ptr()))
+    return out, lse
+
+
+def lsink_workspace(q, layout="bnhd"):
+    """Scratch for sink_logits_grad with an out of q's shape (fa_mi355x_sink_logits_grad_workspace_bytes: one partial per head and
+    slice of 512 rows)."""
+    B, H, _, N, d, _ = _check_gqa(layout, q, q, q)
+    nbytes = _lib.lsink().fa_mi355x_sink_logits_grad_workspace_bytes(B, H, N, d)
+    return torch.empty((nbytes + 3) // 4, dtype=_F32, device=q.device)
+
+
+def sink_logits_grad(out, out_grad, lse, sink_logits, layout="bnhd", workspace=None):
+    """The gradient of the learned sink logits (fa_mi355x_sink_logits_grad): float32 (H,), -sum over every row of the head of
+    e^(a - lse) * rowsum(out_grad o out).  ``out`` (fp32) and ``lse`` are flash_attn_fwd_window_lsink's, ``out_grad`` has out's shape
+    and the forward's input dtype.  Two launches, no atomics: the same bits on every run.  ``workspace``: lsink_workspace(q, layout)."""
+    B, H, _, N, d, dtype = _check_gqa(layout, out_grad, out_grad, out_grad, out)
+    _check_sink_logits(sink_logits, H, out.device)
+    _check_buffer(lse, out.get_device(), "lse", B * H * N)
+    nbytes = _lib.lsink().fa_mi355x_sink_logits_grad_workspace_bytes(B, H, N, d)
+    if workspace is None:
+        workspace = torch.empty((nbytes + 3) // 4, dtype=_F32, device=out.device)
+    else:
+        _check_workspace(workspace, nbytes, out.get_device(), "lsink_workspace(q, layout)")
+    grad = torch.empty(H, dtype=_F32, device=out.device)
+    _lib.lsink_check(_lib.lsink().fa_mi355x_sink_logits_grad(_ptr(out), _ptr(out_grad), _ptr(lse), _ptr(sink_logits), _ptr(grad),
+                                                            _ptr(workspace), B, H, N, d, _DECODE_LAYOUTS[layout], dtype, _stream_ptr()))
+    return grad
+
+
+def _lsink_fwd(q, k, v, sink_logits, window, softmax_scale, layout):
+    """flash_attn_fwd_window_lsink with the learned tensor behind the operands, as _FlashAttnSideFn passes it."""
+    return flash_attn_fwd_window_lsink(q, k, v, window, sink_logits, softmax_scale, layout)
+
+
+def _lsink_bwd(q, k, v, out, out_grad, lse, sink_logits, window, softmax_scale, layout, wanted):
+    """The backward of flash_attn_fwd_window_lsink under autograd: the EXISTING windowed backward on this forward's out and lse, and
+    the logits' gradient only where it is wanted (no launch otherwise)."""
+    dq, dk, dv = flash_attn_bwd_window(q, k, v, out, out_grad, lse, window, None, softmax_scale, layout)
+    return dq, dk, dv, (sink_logits_grad(out, out_grad, lse, sink_logits, layout) if wanted[0] else None)
+
+
+def _lsink_fn(q, k, v, sink_logits, softmax_scale, layout, window):
+    """flash_attn_gqa with learned sink logits: the project's one training-side Function, the logits its one learned tensor."""
+    return _FlashAttnSideFn.apply(_lsink_fwd, _lsink_bwd, q, k, v, (),
+                                  dict(window=window, softmax_scale=softmax_scale, layout=layout), sink_logits)
 
 
 def bwd_workspace_window(q, k, layout="bnhd"):
@@ -1273,13 +1376,15 @@ def extend_append(k_new, v_new, k_cache, v_cache, cache_seqlens=None, layout="bn
 
 
 def _kv_attention(family, q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, causal, softmax_scale, layout, out, lse, workspace, k_new, v_new,
-                  block_table, max_pages, window, k_scale, v_scale, sink, rotary_cos, rotary_sin, rotary_interleaved, q_rot, softcap=None):
+                  block_table, max_pages, window, k_scale, v_scale, sink, rotary_cos, rotary_sin, rotary_interleaved, q_rot, softcap=None,
+                  sink_logits=None):
     """flash_attn_decode / flash_attn_extend / flash_attn_ragged: the checks in one order (the options; the caches and their dtypes; the
     geometry; q, the lengths, the table, the new tokens; devices and strides; out, lse, the workspace's size; the GPU; the tables' rotary
     dimension and q_rot), the head-dim padding, the buffers the caller did not supply, then the entry point _kv_symbol picks.  With
     rotary tables: the roped append (q -> q_rot, the rotated k_new and v_new into the caches), then the ATTEND-ONLY form of the same
     choice on q_rot.  ``softcap``: the family's soft-capping entry point (a window rides along, 0 without one); refused beside sink
-    tokens and on an fp8 cache before any library call."""
+    tokens and on an fp8 cache before any library call.  ``sink_logits``: the family's _lsink entry point (a window rides along
+    likewise); refused beside sink tokens, beside a cap and on an fp8 cache before any library call."""
     fam = _KV_FAMILIES[family]
     packed = fam["packed"]
     window = _check_window(window, causal)
@@ -1287,6 +1392,10 @@ def _kv_attention(family, q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, caus
     softcap = _check_softcap(softcap)
     if softcap is not None and sink is not None:
         raise ValueError("softcap beside sink tokens is not built: softcap= with sink=")
+    if sink_logits is not None and sink is not None:
+        raise ValueError("sink_logits beside sink tokens is not built: sink_logits= with sink=")
+    if sink_logits is not None and softcap is not None:
+        raise ValueError("sink_logits beside a logit cap is not built: sink_logits= with softcap=")
     rotary = _rotary_of(rotary_cos, rotary_sin, rotary_interleaved, q.device)
     if rotary is None and q_rot is not None:
         raise ValueError("q_rot is where a roped call leaves the rotated q: it needs rotary_cos and rotary_sin")
@@ -1309,6 +1418,8 @@ def _kv_attention(family, q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, caus
             raise ValueError("a sliding window on an fp8 cache is not built: window= with torch.float8_e4m3fn caches")
         if softcap is not None:
             raise ValueError("softcap on an fp8 cache is not built: softcap= with torch.float8_e4m3fn caches")
+        if sink_logits is not None:
+            raise ValueError("sink_logits on an fp8 cache is not built: sink_logits= with torch.float8_e4m3fn caches")
     elif k_cache.dtype != q.dtype:
         raise TypeError("q, k_cache and v_cache must share one dtype")
     mp = None if block_table is None else _max_pages(block_table, None)
@@ -1318,6 +1429,7 @@ def _kv_attention(family, q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, caus
     if d > dp:
         raise ValueError(f"q's head dim {d} exceeds the cache's row length {dp}")
     _check_scales(k_scale, v_scale, fp8, Hkv, q.device)
+    _check_sink_logits(sink_logits, H, q.device)
     _check_seqlens(cache_seqlens, B, q.device)
     if pool:
         _check_table(block_table, B, q.device)
@@ -1369,22 +1481,24 @@ def _kv_attention(family, q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, caus
         "workspace": None if workspace is None else workspace.data_ptr(), "B": B, "H": H, "Hkv": Hkv, "Nq": Nq,
         "Ncap": 0 if pool else Ncap, "num_pages": num_pages, "page_size": page_size, "max_pages": table_pages, "d_new": d_new, "d": dp,
         "layout": _DECODE_LAYOUTS[layout], "softmax_scale": float(softmax_scale), "causal": int(bool(causal)),
-        "window": 0 if window is None and softcap is not None else window,   # (the softcap entry points take a window: 0 is none)
-        "sink": sink, "softcap": softcap, "dtype": dtype, "stream": _stream_ptr()}
+        # (the softcap and lsink entry points take a window: 0 is none)
+        "window": 0 if window is None and (softcap is not None or sink_logits is not None) else window,
+        "sink": sink, "softcap": softcap, "sink_logits": None if sink_logits is None else sink_logits.data_ptr(), "dtype": dtype,
+        "stream": _stream_ptr()}
     if rotary:   # (the roped append, then the attend-only form of whatever follows, on the rotated q)
         _rope_append(fam, fields, rotary, fp8)
         if q_rot is not None and qr is not q_rot:
             q_rot.copy_(qr[..., :d])
         fields.update(q=_ptr(qr), k_new=None, v_new=None, d_new=dp)
         k_new = None
-    symbol = _kv_symbol(fam, "attend", pool is not None, k_new is not None, window, sink, fp8, Hkv == H, softcap)
+    symbol = _kv_symbol(fam, "attend", pool is not None, k_new is not None, window, sink, fp8, Hkv == H, softcap, sink_logits is not None)
     _lib.decode_check(_kv_call(symbol, fields))
     return (_unpad(outp, d, out) if d < dp else outp), lse
 
 
 def flash_attn_decode(q, k_cache, v_cache, cache_seqlens=None, causal=True, softmax_scale=None, layout="bnhd", out=None, lse=None,
                       workspace=None, k_new=None, v_new=None, block_table=None, window=None, k_scale=None, v_scale=None, sink=None,
-                      rotary_cos=None, rotary_sin=None, rotary_interleaved=False, q_rot=None, softcap=None):
+                      rotary_cos=None, rotary_sin=None, rotary_interleaved=False, q_rot=None, softcap=None, sink_logits=None):
     """Attention of Nq <= 128 new queries against a KV cache (fa_mi355x_fwd_decode / _gqa, include/flash_attn_mi355x_decode.h).
     ``layout`` "bnhd": q (B, Nq, H, d), caches (B, Ncap, Hkv, dp); "bhnd": q (B, H, Nq, d), caches (B, Hkv, Ncap, dp).  Hkv is the
     cache's own head count and must divide H: Hkv < H is a grouped-query (Hkv = 1: multi-query) cache, query head h reads cache head
@@ -1431,14 +1545,23 @@ def flash_attn_decode(q, k_cache, v_cache, cache_seqlens=None, causal=True, soft
     take the paths above exactly.  Works with a paged cache, a window (the one entry point takes both), the fused append, rotary
     tables and causal=False; beside ``sink`` and on an fp8 cache it is a ValueError (not built).  The workspace does not depend on
     the cap: decode_workspace(..., window=) sizes it.
+    ``sink_logits`` (None, or a contiguous float32 (H,) tensor of FINITE values on q's device): LEARNED ATTENTION-SINK LOGITS
+    (fa_mi355x_fwd_decode_lsink, include/flash_attn_mi355x_decode_lsink.h; gpt-oss's ``sinks``).  The logit a of a query head joins
+    every row's softmax as one more column that has no value vector: lse = ln(e^a + sum_j e^z_j) over the admitted keys j,
+    P_j = e^(z_j - lse), out = P . V, which is out0 * sigmoid(lse0 - a) and lse0 + softplus(a - lse0) of the call without it.  The
+    logit is not scaled, not rotated and not masked.  The kernels read the tensor on the device, so a captured call replays with the
+    values it holds then.  A row with no admissible key gives out = 0 and lse = a.  None takes the paths above exactly.  Works with
+    a paged cache, a window, the fused append, rotary tables and causal=False, in as many launches as the call without it; beside
+    ``sink``, beside ``softcap`` and on an fp8 cache it is a ValueError (not built).  The workspace does not depend on it.
     Returns (out fp32 in q's shape, lse fp32 (B, H, Nq)): rows with no admissible key give out = 0, lse = -inf."""
     return _kv_attention("decode", q, k_cache, v_cache, None, cache_seqlens, causal, softmax_scale, layout, out, lse, workspace, k_new, v_new,
-                         block_table, None, window, k_scale, v_scale, sink, rotary_cos, rotary_sin, rotary_interleaved, q_rot, softcap)
+                         block_table, None, window, k_scale, v_scale, sink, rotary_cos, rotary_sin, rotary_interleaved, q_rot, softcap,
+                         sink_logits)
 
 
 def flash_attn_extend(q, k_cache, v_cache, cache_seqlens=None, causal=True, softmax_scale=None, layout="bnhd", out=None, lse=None,
                       workspace=None, k_new=None, v_new=None, block_table=None, window=None, k_scale=None, v_scale=None, sink=None,
-                      rotary_cos=None, rotary_sin=None, rotary_interleaved=False, q_rot=None, softcap=None):
+                      rotary_cos=None, rotary_sin=None, rotary_interleaved=False, q_rot=None, softcap=None, sink_logits=None):
     """flash_attn_decode for ANY number Nq >= 1 of new queries (fa_mi355x_fwd_extend / fa_mi355x_fwd_extend_append): a long input that
     follows a cached prefix, or one piece of a chunked prefill (the same call, from an empty cache on).  Every argument, check, the
     head-dim padding (the default scale keeps the caller's 1/sqrt(d)) and the return value are flash_attn_decode's; ``workspace`` is
@@ -1451,9 +1574,11 @@ def flash_attn_extend(q, k_cache, v_cache, cache_seqlens=None, causal=True, soft
     ``v_scale``: an fp8 cache, as in flash_attn_decode (fa_mi355x_fwd_extend_fp8).  ``sink``: attention-sink tokens beside the
     window, as in flash_attn_decode (fa_mi355x_fwd_extend_sink; extend_workspace(..., window=, sink=)).  ``rotary_cos`` /
     ``rotary_sin`` / ``rotary_interleaved`` / ``q_rot``: rotary embeddings, as in flash_attn_decode (fa_mi355x_rope_append, then the
-    attend-only extend call on q_rot).  ``softcap``: logit soft-capping, as in flash_attn_decode (fa_mi355x_fwd_extend_softcap)."""
+    attend-only extend call on q_rot).  ``softcap``: logit soft-capping, as in flash_attn_decode (fa_mi355x_fwd_extend_softcap).
+    ``sink_logits``: learned sink logits, as in flash_attn_decode (fa_mi355x_fwd_extend_lsink)."""
     return _kv_attention("extend", q, k_cache, v_cache, None, cache_seqlens, causal, softmax_scale, layout, out, lse, workspace, k_new, v_new,
-                         block_table, None, window, k_scale, v_scale, sink, rotary_cos, rotary_sin, rotary_interleaved, q_rot, softcap)
+                         block_table, None, window, k_scale, v_scale, sink, rotary_cos, rotary_sin, rotary_interleaved, q_rot, softcap,
+                         sink_logits)
 
 
 # ---- ragged batches: every sequence brings its own number of new tokens (include/flash_attn_mi355x_decode_ragged.h) ----
@@ -1492,7 +1617,7 @@ def ragged_append(k_new, v_new, k_cache, v_cache, cu_seqlens_q, cache_seqlens=No
 
 def flash_attn_ragged(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens=None, causal=True, softmax_scale=None, layout="bnhd", out=None,
                       lse=None, workspace=None, k_new=None, v_new=None, block_table=None, max_pages=None, window=None, sink=None,
-                      rotary_cos=None, rotary_sin=None, rotary_interleaved=False, q_rot=None, softcap=None):
+                      rotary_cos=None, rotary_sin=None, rotary_interleaved=False, q_rot=None, softcap=None, sink_logits=None):
     """One attention call over a RAGGED batch (fa_mi355x_fwd_ragged / _fwd_ragged_append and their _paged forms): every sequence
     brings its own number of new tokens -- some decode one, one is part-way through a chunked prefill, some have none.  ``q`` is
     PACKED, (T, H, d): sequence b owns rows cu_seqlens_q[b] .. cu_seqlens_q[b + 1] - 1 (``cu_seqlens_q`` contiguous int32 (B + 1,) on
@@ -1514,10 +1639,13 @@ def flash_attn_ragged(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens=None, cau
     (fa_mi355x_rope_append_ragged, then the attend-only ragged call on q_rot; token i of sequence b sits at
     clamp(len_b, 0, Ncap) - nq_b + i; the rows of q_rot that no sequence owns keep what they held).
     ``softcap``: logit soft-capping, as in flash_attn_decode (fa_mi355x_fwd_ragged_softcap).
+    ``sink_logits``: learned sink logits, as in flash_attn_decode (fa_mi355x_fwd_ragged_lsink); a sequence's row with no admissible
+    key gives out = 0 and lse = its head's logit.
     Returns (out fp32 (T, H, d), lse fp32 (H, T)): rows with no admissible key give out = 0, lse = -inf; rows of the unused tail
     keep what they held."""
     return _kv_attention("ragged", q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, causal, softmax_scale, layout, out, lse, workspace, k_new,
-                         v_new, block_table, max_pages, window, None, None, sink, rotary_cos, rotary_sin, rotary_interleaved, q_rot, softcap)
+                         v_new, block_table, max_pages, window, None, None, sink, rotary_cos, rotary_sin, rotary_interleaved, q_rot, softcap,
+                         sink_logits)
 
 
 # ---- packed variable-length batches in the training forward and backward (include/flash_attn_mi355x_varlen.h) ----------------------

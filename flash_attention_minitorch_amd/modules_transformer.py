@@ -68,7 +68,7 @@ class Rotary:
 
 
 def multi_head_attention(x, wq, wk, wv, wo, n_head: int, causal: bool = True, fused_layout: bool = True, fold_scale: bool = False,
-                         rope=None, window=None, sink=None, softcap=None):
+                         rope=None, window=None, sink=None, softcap=None, sink_logits=None):
     """MultiHeadAttention.forward (modules_transfomer.py:141-157).  x: (B, N, E); wq, wo: (E, E); wk, wv: (E, E), or (E, Hkv * d) for
     grouped-query heads (Hkv divides n_head, d = E // n_head; query head h reads kv head h // (n_head // Hkv)).  With ``fused_layout``
     the kernels read the Hkv heads of k and v in place, forward and backward (device_ops.flash_attn_gqa: no expanded copy, and the
@@ -85,16 +85,20 @@ def multi_head_attention(x, wq, wk, wv, wo, n_head: int, causal: bool = True, fu
     without a window.  None or 0, W >= N or S >= N: the layer without them.
     ``softcap`` = C (causal only): the logit cap a KVCache(softcap=C) generates under, C * tanh(score / C) on the scaled score before
     the mask, forward and backward (device_ops.flash_attn_gqa(softcap=)); it composes with ``rope``, ``window``, ``sink`` and
-    ``fold_scale`` (the cap acts on softmax_scale * q.k, which folding leaves the same).  None or 0: the layer without a cap."""
+    ``fold_scale`` (the cap acts on softmax_scale * q.k, which folding leaves the same).  None or 0: the layer without a cap.
+    ``sink_logits`` (causal only; float32 (n_head,), which may require grad): the learned sink logits a KVCache(sink_logits=) generates
+    under, one column more in every softmax of a head (device_ops.flash_attn_gqa(sink_logits=)); composes with ``rope``, ``window``
+    and ``fold_scale`` (the logit is in logit units: no scale touches it); not beside ``sink`` or ``softcap``."""
     B, N, E = x.shape
     capped = device_ops._check_softcap(softcap) is not None
-    windowed = capped or device_ops._training_window(window, sink, causal, N) is not None   # (a cap: the window library's kernels)
+    # (a cap, and learned sink logits: kernels of the window family, whatever the window)
+    windowed = capped or sink_logits is not None or device_ops._training_window(window, sink, causal, N) is not None
     if fused_layout:
         q, k, v = _project(x, wq * (LOG2E / (E // n_head) ** 0.5) if fold_scale else wq, wk, wv, n_head)
         if rope is not None:
             q, k = rope.apply(q), rope.apply(k)
         if windowed:   # grouped or not: k and v stay (B, N, Hkv, d)
-            o = device_ops.flash_attn_gqa(q, k, v, causal, LN2 if fold_scale else None, "bnhd", window, sink, softcap)
+            o = device_ops.flash_attn_gqa(q, k, v, causal, LN2 if fold_scale else None, "bnhd", window, sink, softcap, sink_logits)
         elif k.shape[2] == n_head:
             o = _attention(q, k, v, causal, _lib.FA_LAYOUT_BNHD, LN2 if fold_scale else None)   # (B, N, H, d) fp32: already merged
         else:   # grouped-query heads: k and v stay (B, N, Hkv, d)
@@ -106,7 +110,7 @@ def multi_head_attention(x, wq, wk, wv, wo, n_head: int, causal: bool = True, fu
             q, k = rope.apply(q), rope.apply(k)
         q, k, v = (t.permute(0, 2, 1, 3).contiguous() for t in (q, _expand_kv(k, n_head), _expand_kv(v, n_head)))
         if windowed:
-            o = device_ops.flash_attn_gqa(q, k, v, causal, None, "bhnd", window, sink, softcap)
+            o = device_ops.flash_attn_gqa(q, k, v, causal, None, "bhnd", window, sink, softcap, sink_logits)
         else:
             o = _attention(q, k, v, causal, _lib.FA_LAYOUT_BHND)                              # (B, H, N, d)
         merged = o.permute(0, 2, 1, 3).contiguous().view(B * N, E)
@@ -114,14 +118,18 @@ def multi_head_attention(x, wq, wk, wv, wo, n_head: int, causal: bool = True, fu
 
 
 def attention_stack(x, layers, n_head: int, causal: bool = True, fused_layout: bool = True, fold_scale: bool = False, rope=None,
-                    window=None, sink=None, softcap=None):
+                    window=None, sink=None, softcap=None, sink_logits=None):
     """x <- x + MultiHeadAttention_l(x) for every (wq, wk, wv, wo) in ``layers``: the attention data flow of the reference's
     4-layer causal DecoderLM (modules_transfomer.py:255-351) without its out-of-scope LayerNorm / FFN blocks.  ``rope``: every
     layer rotates its q and k (multi_head_attention).  ``window``, ``sink``: every layer attends under the sliding-window mask of a
     KVCache(window=, sink=), so a model that generates through such a cache trains under the mask it runs with.  ``softcap``: every
-    layer soft-caps its logits as a KVCache(softcap=) does (multi_head_attention), likewise."""
-    for (wq, wk, wv, wo) in layers:
-        x = x + multi_head_attention(x, wq, wk, wv, wo, n_head, causal, fused_layout, fold_scale, rope, window, sink, softcap)
+    layer soft-caps its logits as a KVCache(softcap=) does (multi_head_attention), likewise.  ``sink_logits``: float32
+    (n_layers, n_head), layer l attends with row l as its learned sink logits, as a KVCache(sink_logits=) does."""
+    if sink_logits is not None and (not isinstance(sink_logits, torch.Tensor) or sink_logits.dim() != 2 or sink_logits.shape[0] != len(layers)):
+        raise ValueError("sink_logits must be a float32 (n_layers, n_head) tensor: one row of learned logits per layer")
+    for li, (wq, wk, wv, wo) in enumerate(layers):
+        x = x + multi_head_attention(x, wq, wk, wv, wo, n_head, causal, fused_layout, fold_scale, rope, window, sink, softcap,
+                                     None if sink_logits is None else sink_logits[li])
     return x
 
 
@@ -269,6 +277,8 @@ def cross_attention_packed(x, cu_seqlens_q, memory, cu_seqlens_k, wq, wk, wv, wo
 # attend-only call runs; the square prefill and the unfused step rotate q and k with apply_rotary.  The cache holds ROTATED keys.
 # softcap=C: every call soft-caps its logits, C * tanh(score / C) (Gemma-2, Grok-1), through the family's softcap entry point; the
 # prompt takes the extend route, as on a windowed cache (attention_stack(softcap=) trains under the same function).
+# sink_logits=(n_layers, H) fp32: every call of layer li adds that layer's learned sink logits to its softmax (gpt-oss), through the
+# family's _lsink entry point; the prompt takes the extend route likewise.
 
 MAX_STEP_TOKENS = 128   # fa_mi355x_fwd_decode's largest Nq; longer inputs are prefill, or attention_stack_extend after a prefix
 
@@ -335,6 +345,24 @@ def _check_cache_softcap(softcap, sink, fp8):
     return float(softcap)
 
 
+def _check_cache_sink_logits(sink_logits, sink, softcap, fp8, n_layers, n_head, device):
+    """``sink_logits`` of a cache: None, or a float32 (n_layers, n_head) tensor, one learned logit per layer and QUERY head; not
+    beside sink tokens, a cap or an fp8 cache (none is built).  Kept as the caller's tensor where it already lives on the cache's
+    device, contiguous: a parameter updated in place is what the next call reads."""
+    if sink_logits is None:
+        return None
+    if not isinstance(sink_logits, torch.Tensor) or sink_logits.dtype != torch.float32 or tuple(sink_logits.shape) != (n_layers, n_head):
+        raise ValueError(f"sink_logits must be None or a float32 (n_layers, n_head) = ({n_layers}, {n_head}) tensor: one learned logit "
+                         "per layer and query head")
+    if sink is not None:
+        raise ValueError("sink_logits beside sink tokens is not built: sink_logits= with sink=")
+    if softcap is not None:
+        raise ValueError("sink_logits beside a logit cap is not built: sink_logits= with softcap=")
+    if fp8:
+        raise ValueError("sink_logits on an fp8 cache is not built: sink_logits= with kv_dtype=torch.float8_e4m3fn")
+    return sink_logits.detach().to(device).contiguous()
+
+
 class KVCache:
     """Per-layer k and v caches of a causal attention stack: ``k[l]``, ``v[l]`` are (B, capacity, n_kv_head, dp) in the projection's
     own [B][N][H][d] layout (no permute), dp = head_dim rounded up to 32, 64 or 128 with zero columns past head_dim.  ``n_kv_head``
@@ -344,8 +372,8 @@ class KVCache:
     positions, its own included (Mistral's ``sliding_window``); the stack functions pass it to every device_ops call on this cache.
     The cache still holds every row (no ring buffer): a PagedKVCache gives the memory back through release_behind_window.
     ``sink`` (None, or an int >= 0; needs ``window``): ATTENTION-SINK tokens, the first ``sink`` positions of every sequence stay
-    visible to every later token beside its window (a mask on the cache's logical rows: positions are not re-assigned, and there
-    are no learned sink logits).
+    visible to every later token beside its window (a mask on the cache's logical rows: positions are not re-assigned; learned
+    sink LOGITS are ``sink_logits`` below, another thing).
     ``kv_dtype`` (None: ``dtype``, or torch.float8_e4m3fn): an FP8 cache holds e4m3 bytes, half the memory and half the bytes a step
     reads, and ``kv_scale`` (None: ones, or a pair (k_scale, v_scale) of float32 (n_layers, n_kv_head) tensors) gives every layer's
     per-head scales: a cached element is scale * e4m3.  The stack must be bfloat16; the fused step, extend and chunked-prefill
@@ -358,14 +386,19 @@ class KVCache:
     to every device_ops call on this cache, and a prompt goes through the extend kernels (the square forward has no cap).  Works
     with a window, a paged cache and rotary embeddings; not built beside sink tokens or on an fp8 cache, and a cache has ONE window
     (Gemma-2's alternating local and global layers are not covered).  The training forward and backward have no cap.
+    ``sink_logits`` (None, or a float32 (n_layers, n_head) tensor): LEARNED ATTENTION-SINK LOGITS (gpt-oss), one per layer and query
+    head; layer li's row joins every softmax of that layer as a column without a value vector (device_ops.flash_attn_decode's
+    ``sink_logits``).  The stack functions pass the row to every device_ops call on this cache, the kernels read it on the device
+    (a GraphedStep replays with the values it holds then), and a prompt goes through the extend kernels (the square forward has no
+    logit).  Works with a window, a paged cache and rotary embeddings; not built beside sink tokens, a cap or on an fp8 cache.
     The constructor, which is PagedKVCache's too, checks in this order and reports the first fault: ``window``, ``sink``,
     ``n_kv_head``, what the memory layout adds (_pool: nothing here; ``page_size``, ``capacity``, ``n_pages`` of a PagedKVCache),
-    ``rope``, then ``kv_dtype`` / ``kv_scale``, then ``softcap``."""
+    ``rope``, then ``kv_dtype`` / ``kv_scale``, then ``softcap``, then ``sink_logits``."""
 
     block_table = None   # (a PagedKVCache has one)
 
     def __init__(self, n_layers, B, capacity, n_head, head_dim, dtype, device, n_kv_head=None, window=None, kv_dtype=None, kv_scale=None,
-                 sink=None, rope=None, softcap=None):
+                 sink=None, rope=None, softcap=None, sink_logits=None):
         self.window = _check_cache_window(window)
         self.sink = _check_cache_sink(sink, self.window)
         self.head_dim, self.dp = head_dim, device_ops.padded_head_dim(head_dim)
@@ -377,6 +410,7 @@ class KVCache:
         self.rope = _check_cache_rope(rope, rows, head_dim)
         dtype, self.kv_scale = _check_cache_quant(kv_dtype, kv_scale, dtype, self.window, n_layers, self.n_kv_head, device)
         self.softcap = _check_cache_softcap(softcap, self.sink, dtype == device_ops._FP8)
+        self.sink_logits = _check_cache_sink_logits(sink_logits, self.sink, self.softcap, dtype == device_ops._FP8, n_layers, n_head, device)
         self.k = [torch.zeros(shape, dtype=dtype, device=device) for _ in range(n_layers)]
         self.v = [torch.zeros(shape, dtype=dtype, device=device) for _ in range(n_layers)]
         self.lengths = torch.zeros(B, dtype=torch.int32, device=device)
@@ -388,10 +422,16 @@ class KVCache:
         return (B, self.capacity, self.n_kv_head, self.dp), self.capacity
 
     def keywords(self, li, rotary=True, **new):
-        """Every keyword an attend call on layer ``li`` of this cache takes beside its tensors: paging, windowing, quant, rotary and
-        capping, and the caller's own (``new``: k_new=, v_new=).  A new cache feature adds its provider here, and every stack function
+        """Every keyword an attend call on layer ``li`` of this cache takes beside its tensors: paging, windowing, quant, rotary,
+        capping and learned sink logits, and the caller's own (``new``: k_new=, v_new=).  A new cache feature adds its provider here, and every stack function
         passes it.  ``rotary=False``: the caller has rotated q and k itself (the unfused step)."""
-        return {**new, **self.paging(), **self.windowing(), **self.quant(li), **(self.rotary() if rotary else {}), **self.capping()}
+        return {**new, **self.paging(), **self.windowing(), **self.quant(li), **(self.rotary() if rotary else {}), **self.capping(),
+                **self.learned_sinks(li)}
+
+    def learned_sinks(self, li):
+        """The keyword that gives a device_ops call on layer ``li`` its learned sink logits (row li, a view: the kernels read the
+        cache's own tensor): none for a cache without them."""
+        return {} if self.sink_logits is None else dict(sink_logits=self.sink_logits[li])
 
     def capping(self):
         """The keyword that makes a device_ops call a soft-capped one: none for a cache without a cap."""
@@ -471,9 +511,10 @@ class PagedKVCache(KVCache):
     read.  Without sinks sink_pages = 0 and this is the rule above."""
 
     def __init__(self, n_layers, B, capacity, n_head, head_dim, dtype, device, n_kv_head=None, page_size=128, n_pages=None, window=None,
-                 kv_dtype=None, kv_scale=None, sink=None, rope=None, softcap=None):
+                 kv_dtype=None, kv_scale=None, sink=None, rope=None, softcap=None, sink_logits=None):
         self.page_size, self.n_pages = page_size, n_pages   # (as given: _pool checks them at their place in KVCache's order)
-        super().__init__(n_layers, B, capacity, n_head, head_dim, dtype, device, n_kv_head, window, kv_dtype, kv_scale, sink, rope, softcap)
+        super().__init__(n_layers, B, capacity, n_head, head_dim, dtype, device, n_kv_head, window, kv_dtype, kv_scale, sink, rope, softcap,
+                         sink_logits)
         self.block_table = torch.zeros((B, self.max_pages), dtype=torch.int32, device=device)   # (entries past a sequence's pages: never read)
         self.free = list(range(self.n_pages - 1, -1, -1))   # (handed out from the end: page 0 first)
         self.pages = [[] for _ in range(B)]                 # the pages of each sequence, in order
@@ -588,11 +629,11 @@ def attention_stack_prefill(x, layers, n_head: int, cache: KVCache):
     attention reads those cache-shaped k and v in place (device_ops.flash_attn_fwd_gqa: no expanded copy).  Returns the stack's
     output (B, P, E).  A WINDOWED cache does not use that square forward, which has no window: its prompt goes through the extend
     kernels as one piece (attention_stack_prefill_chunked with chunk = P), which append and attend through the window.  A cache with
-    a SOFTCAP takes the same route: the square forward has no cap."""
+    a SOFTCAP takes the same route: the square forward has no cap.  So does a cache with learned SINK LOGITS."""
     B, P, E = x.shape
     if P > cache.capacity:
         raise ValueError(f"prompt of {P} tokens exceeds the cache capacity {cache.capacity}")
-    if cache.window is not None or cache.softcap is not None:
+    if cache.window is not None or cache.softcap is not None or cache.sink_logits is not None:
         return attention_stack_prefill_chunked(x, layers, n_head, cache, max(P, 1))
     d = E // n_head
     # an fp8 cache, slab or paged, and every paged one take the prompt through the library's append (it quantises, and it knows the

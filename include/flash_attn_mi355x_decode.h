@@ -174,4 +174,9 @@ const char* fa_mi355x_decode_last_error(void);
  * their own. */
 #include "flash_attn_mi355x_decode_softcap.h"
 
+/* Learned attention-sink logits (gpt-oss: one fp32 logit per query head joins every softmax as a column without a value vector) for
+ * the decode, extend and ragged calls, slab or paged, windowed or not: three entry points, part of this library and of this header,
+ * kept in a file of their own. */
+#include "flash_attn_mi355x_decode_lsink.h"
+
 #endif /* FLASH_ATTN_MI355X_DECODE_H */

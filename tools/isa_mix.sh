@@ -1,5 +1,5 @@
 #!/usr/bin/env bash
-# Device assembly of the kernel libraries (csrc/fa_api.hip, csrc/fa_decode.hip, csrc/fa_window.hip, csrc/fa_varlen.hip, csrc/fa_bidir.hip, csrc/fa_prefix.hip, csrc/fa_local.hip), built with compile_cuda.sh's flags + -save-temps.
+# Device assembly of the kernel libraries (csrc/fa_api.hip, csrc/fa_decode.hip, csrc/fa_window.hip, csrc/fa_varlen.hip, csrc/fa_bidir.hip, csrc/fa_prefix.hip, csrc/fa_local.hip, csrc/fa_lsink.hip), built with compile_cuda.sh's flags + -save-temps.
 #   tools/isa_mix.sh mix   <tree> <out-dir> <mangled-kernel-substring>...   resource usage + per-basic-block instruction mix (fa_api)
 #   tools/isa_mix.sh split <tree> <out-dir>                                 one normalised .s per kernel: <out-dir>/kernels/<lib>/<kernel>.s
 # <tree> is a checkout of this repository, <out-dir> receives the temporaries (FA_ISA_NOBUILD=1: reuse what is there).
@@ -44,8 +44,8 @@ mix)
   done
   ;;
 split)
-  for lib in fa_api fa_decode fa_window fa_varlen fa_bidir fa_prefix fa_local; do
-    [ -f "$SRC/$lib.hip" ] || continue   # (a tree from before the window, the varlen, the bidir, the prefix or the local library has no such .hip)
+  for lib in fa_api fa_decode fa_window fa_varlen fa_bidir fa_prefix fa_local fa_lsink; do
+    [ -f "$SRC/$lib.hip" ] || continue   # (a tree from before the window, the varlen, the bidir, the prefix, the local or the lsink library has no such .hip)
     build "$lib"
     rm -rf "kernels/$lib"
     mkdir -p "kernels/$lib"
