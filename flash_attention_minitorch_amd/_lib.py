@@ -205,6 +205,18 @@ LSINK_ABI = {
     "fa_mi355x_fwd_ragged_lsink": (_i, [_vp] * 11 + [_i] * 11 + [_f, _i, _i, _vp, _i, _vp]),
 }
 
+# the same for include/flash_attn_mi355x_decode_d256.h (head dim 256: the _softcap prototypes, the _window size queries and an append
+# for slab or paged caches; tests/test_d256_cpu.py)
+D256_ABI = {
+    "fa_mi355x_fwd_decode_d256": (_i, [_vp] * 10 + [_i] * 11 + [_f, _i, _i, _f, _i, _vp]),
+    "fa_mi355x_fwd_extend_d256": (_i, [_vp] * 10 + [_i] * 11 + [_f, _i, _i, _f, _i, _vp]),
+    "fa_mi355x_append_d256": (_i, [_vp] * 6 + [_i] * 11 + [_vp]),
+    "fa_mi355x_decode_d256_splits": (_i, [_i] * 8),
+    "fa_mi355x_decode_d256_workspace_bytes": (_sz, [_i] * 7),
+    "fa_mi355x_extend_d256_splits": (_i, [_i] * 8),
+    "fa_mi355x_extend_d256_workspace_bytes": (_sz, [_i] * 7),
+}
+
 # The positional order of every KV-cache symbol that device_ops calls, by the parameter names of the prototypes (k_pool / v_pool of
 # the _paged ones read k_cache / v_cache, T of the ragged ones Nq: one field each).  device_ops fills one dict of fields per public
 # call and every C call takes its arguments from it in this order; tests/test_kv_ops_cpu.py holds the table against the headers' text
@@ -290,7 +302,18 @@ KV_LSINK_PARAMS = {
                                   "layout softmax_scale causal window sink_logits dtype stream",
 }
 KV_LSINK_PARAMS = {sym: tuple(names.split()) for sym, names in KV_LSINK_PARAMS.items()}
-KV_CALL_PARAMS = {**KV_PARAMS, **KV_SOFTCAP_PARAMS, **KV_LSINK_PARAMS}
+# The head-dim-256 symbols, likewise (tests/test_d256_cpu.py holds them against their header and D256_ABI).
+KV_D256_PARAMS = {
+    "fa_mi355x_fwd_decode_d256": f"{_PROLOGUE} out lse cache_seqlens block_table workspace {_EITHER} d_new d "
+                                 "layout softmax_scale causal window softcap dtype stream",
+    "fa_mi355x_fwd_extend_d256": f"{_PROLOGUE} out lse cache_seqlens block_table workspace {_EITHER} d_new d "
+                                 "layout softmax_scale causal window softcap dtype stream",
+    "fa_mi355x_append_d256": f"{_APPEND} cache_seqlens block_table B Hkv Nq Ncap num_pages page_size max_pages d_new d layout dtype stream",
+    "fa_mi355x_decode_d256_workspace_bytes": "B H Hkv Nq Ncap d window",
+    "fa_mi355x_extend_d256_workspace_bytes": "B H Hkv Nq Ncap d window",
+}
+KV_D256_PARAMS = {sym: tuple(names.split()) for sym, names in KV_D256_PARAMS.items()}
+KV_CALL_PARAMS = {**KV_PARAMS, **KV_SOFTCAP_PARAMS, **KV_LSINK_PARAMS, **KV_D256_PARAMS}
 KV_POINTERS = frozenset("q q_rot k_new v_new k_cache v_cache k_scale v_scale cos sin out lse cu_seqlens_q cache_seqlens block_table "
                         "workspace sink_logits stream".split())
 
@@ -380,12 +403,13 @@ def check(status: int) -> None:
 
 
 DECODE_NAME = "libflash_attn_mi355x_decode.so"
-_DECODE_LIB_ABI = {**DECODE_ABI, **PAGED_ABI, **RAGGED_ABI, **WINDOW_ABI, **FP8_ABI, **SINK_ABI, **ROPE_ABI, **SOFTCAP_ABI, **LSINK_ABI}
+_DECODE_LIB_ABI = {**DECODE_ABI, **PAGED_ABI, **RAGGED_ABI, **WINDOW_ABI, **FP8_ABI, **SINK_ABI, **ROPE_ABI, **SOFTCAP_ABI, **LSINK_ABI,
+                   **D256_ABI}
 
 
 def decode() -> ctypes.CDLL:
     """libflash_attn_mi355x_decode.so (include/flash_attn_mi355x_decode.h, its _paged.h, its _ragged.h, its _window.h, its _fp8.h, its
-    _sink.h, its _rope.h, its _softcap.h and its _lsink.h) with argtypes set.  (Every KV-cache call comes through here: the tables are merged once, above.)"""
+    _sink.h, its _rope.h, its _softcap.h, its _lsink.h and its _d256.h) with argtypes set.  (Every KV-cache call comes through here: the tables are merged once, above.)"""
     return _typed(DECODE_NAME, _DECODE_LIB_ABI)
 
 

@@ -1,5 +1,5 @@
 // C ABI of the MI355X KV-cache decode library (declared in include/flash_attn_mi355x_decode.h and its _paged.h, _ragged.h,
-// _window.h, _sink.h, _fp8.h, _softcap.h, _lsink.h and _rope.h).  Every entry point fills one KvCall (the call as it was received) and hands it to run():
+// _window.h, _sink.h, _fp8.h, _softcap.h, _lsink.h, _rope.h and _d256.h).  Every entry point fills one KvCall (the call as it was received) and hands it to run():
 // the entry point's prelude (check_fp8 or check_window), the page geometry (check_pages), the attention's checks (check_attend, which
 // also returns the call's Policy), the append's (check_append), then the append launch (run_append) and the attention's launches
 // (run_attend -> launch_split).  policy() is the one split policy: the three families (decode: 32-row blocks, at most 128 queries;
@@ -19,6 +19,7 @@
 
 #include "../../include/flash_attn_mi355x_decode.h"
 #include "fa_decode.h"
+#include "fa_decode_d256.h"
 #include "fa_rope.h"
 
 namespace {
@@ -97,6 +98,7 @@ struct KvCall {
   float softmax_scale = 0.f;
   float softcap = 0.f;   // logit soft-capping (_softcap.h); 0: none
   const float* sink_logits = nullptr;   // learned sink logits (_lsink.h), fp32 [H] on the device; null: none
+  bool d256 = false;   // the head-dim-256 entry points (_d256.h): d = 256 exactly, bf16, the kernels of fa_decode_d256.h
   hipStream_t stream = nullptr;
 
   explicit KvCall(Family f) : family(f) {}
@@ -265,6 +267,15 @@ int check_cache_bytes(const KvCall& c) {
   return FA_OK;
 }
 
+// What the head-dim-256 entry points (_d256.h) ask in the place of d in {32, 64, 128}.
+int check_d256(const KvCall& c) {
+  if (c.d != fa::D256)
+    return set_err(FA_ERR_UNSUPPORTED_D, "the _d256 entry points take d = 256 exactly: d in {32, 64, 128} runs through the other entry points");
+  if (c.dtype != FA_DTYPE_BF16)
+    return set_err(FA_ERR_BAD_ARG, "the d = 256 kernels are built for bf16 alone: FA_DTYPE_F32 is not supported (dtype must be FA_DTYPE_BF16)");
+  return FA_OK;
+}
+
 // The argument checks of the attention: FA_OK with the call's policy in *out, or the error with its message set.  The families
 // differ in the Nq <= 128 of decode, the null cu_seqlens_q of ragged, the names in the messages and the bounds of FAMILIES.
 int check_attend(const KvCall& c, Policy* out) {
@@ -282,7 +293,10 @@ int check_attend(const KvCall& c, Policy* out) {
   if (c.layout != FA_LAYOUT_BHND && c.layout != FA_LAYOUT_BNHD) return set_err(FA_ERR_BAD_ARG, "unknown layout");
   if (!c.q || !c.k_cache || !c.v_cache || !c.out) return set_err(FA_ERR_BAD_ARG, "null pointer argument");
   if (c.family == RAGGED && !c.cu) return set_err(FA_ERR_BAD_ARG, "null cu_seqlens_q");
-  if (c.d != 32 && c.d != 64 && c.d != 128)
+  if (c.d256) {
+    const int rc = check_d256(c);
+    if (rc != FA_OK) return rc;
+  } else if (c.d != 32 && c.d != 64 && c.d != 128)
     return set_err(FA_ERR_UNSUPPORTED_D, "decode supports d in {32, 64, 128}: pad the cache with zero columns for other d <= 128");
   if (c.softmax_scale != 0.f && (!(c.softmax_scale > 0.f) || !std::isfinite(c.softmax_scale)))
     return set_err(FA_ERR_BAD_ARG, "softmax_scale must be positive and finite (0: 1/sqrt(d))");
@@ -313,7 +327,11 @@ int check_append(const KvCall& c) {
   if (!c.k_new || !c.v_new || !c.k_cache || !c.v_cache)
     return set_err(FA_ERR_BAD_ARG, "null pointer argument (k_new, v_new and the caches)");
   if (c.family == RAGGED && !c.cu) return set_err(FA_ERR_BAD_ARG, "null cu_seqlens_q");
-  if (c.d != 32 && c.d != 64 && c.d != 128) return set_err(FA_ERR_UNSUPPORTED_D, "decode supports cache rows of d in {32, 64, 128}");
+  if (c.d256) {
+    const int rc = check_d256(c);
+    if (rc != FA_OK) return rc;
+  } else if (c.d != 32 && c.d != 64 && c.d != 128)
+    return set_err(FA_ERR_UNSUPPORTED_D, "decode supports cache rows of d in {32, 64, 128}");
   if (c.d_new < 1 || c.d_new > c.d) {
     snprintf(g_err, sizeof(g_err), "d_new = %d must be in 1 .. d = %d", c.d_new, c.d);
     return FA_ERR_BAD_ARG;
@@ -522,6 +540,38 @@ template <typename T, int D> int launch_split(const SplitArgs& a, Family f, hipS
   return FA_OK;
 }
 
+// The launches of a checked head-dim-256 attention (decode or extend, bf16): the build of fa_decode_d256.h that the call's cache
+// (slab / paged), window and cap select, and decode_combine_d256_kernel if nsplit > 1, with tau = 1 behind a cap as above.
+template <bool PAGED, bool WINDOW, bool SOFTCAP> void launch_d256_build(const fa::D256Args& a, Family f, long grid, hipStream_t st) {
+  if (f == EXTEND) hipLaunchKernelGGL((fa::extend_split_d256_kernel<PAGED, WINDOW, SOFTCAP>), dim3((unsigned)grid), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((fa::decode_split_d256_kernel<PAGED, WINDOW, SOFTCAP>), dim3((unsigned)grid), dim3(512), 0, st, a);
+}
+
+int launch_d256(const SplitArgs& a, Family f, hipStream_t st) {
+  const fa::D256Args da = with_softcap<fa::SoftcapArgs, fa::DecodeArgs>(a);
+  const long grid = split_grid(a.items, a.nqb);
+  switch ((a.table != nullptr) * 4 + (a.window != 0) * 2 + (a.softcap > 0.f)) {
+    case 0: launch_d256_build<false, false, false>(da, f, grid, st); break;
+    case 1: launch_d256_build<false, false, true>(da, f, grid, st); break;
+    case 2: launch_d256_build<false, true, false>(da, f, grid, st); break;
+    case 3: launch_d256_build<false, true, true>(da, f, grid, st); break;
+    case 4: launch_d256_build<true, false, false>(da, f, grid, st); break;
+    case 5: launch_d256_build<true, false, true>(da, f, grid, st); break;
+    case 6: launch_d256_build<true, true, false>(da, f, grid, st); break;
+    default: launch_d256_build<true, true, true>(da, f, grid, st); break;
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_err(f == EXTEND ? "extend_split_d256_kernel launch" : "decode_split_d256_kernel launch", e);
+  if (a.nsplit > 1) {
+    fa::DecodeArgs ca = a;
+    if (a.softcap > 0.f) ca.tau = 1.0f;
+    launch256(fa::decode_combine_d256_kernel<false>, (long)a.nseq * a.H * a.Nq, st, ca);
+    e = hipGetLastError();
+    if (e != hipSuccess) return hip_err("decode_combine_d256_kernel launch", e);
+  }
+  return FA_OK;
+}
+
 template <typename T> int launch_split_d(const SplitArgs& a, Family f, int d, hipStream_t st) {
   switch (d) {
     case 32: return launch_split<T, 32>(a, f, st);
@@ -568,6 +618,7 @@ int run_attend(const KvCall& c, const Policy& p) {
   a.f8 = c.f8;
   a.softcap = c.softcap;
   a.sink_logits = c.sink_logits;
+  if (c.d256) return launch_d256(a, c.family, c.stream);
   return c.dtype == FA_DTYPE_BF16 ? launch_split_d<fa::bf16_t>(a, c.family, c.d, c.stream) : launch_split_d<float>(a, c.family, c.d, c.stream);
 }
 
@@ -1177,6 +1228,60 @@ int fa_mi355x_append_fp8(const void* k_new, const void* v_new, void* k_cache, vo
   c.pool_or_slabs(block_table, num_pages, page_size, max_pages).heads(B, Hkv, Hkv, Nq, d).format(layout, dtype, stream);
   c.f8 = {true, k_scale, v_scale};
   return run(c);
+}
+
+// ---- head dim 256 (_d256.h): the _softcap prototypes and the _window size queries on d = 256, and the append ----
+int fa_mi355x_fwd_decode_d256(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
+                              const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv, int Nq, int Ncap,
+                              int num_pages, int page_size, int max_pages, int d_new, int d, int layout, float softmax_scale, int causal,
+                              int window, float softcap, int dtype, void* stream) {
+  KvCall c(DECODE);
+  c.attention(q, out, lse, workspace, softmax_scale, causal).cache(k_cache, v_cache, cache_seqlens, Ncap);
+  c.pool_or_slabs(block_table, num_pages, page_size, max_pages).heads(B, H, Hkv, Nq, d).format(layout, dtype, stream);
+  if (k_new || v_new) c.new_tokens(k_new, v_new, d_new);
+  c.window = window, c.softcap = softcap, c.d256 = true;
+  return run(c);
+}
+
+int fa_mi355x_fwd_extend_d256(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
+                              const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv, int Nq, int Ncap,
+                              int num_pages, int page_size, int max_pages, int d_new, int d, int layout, float softmax_scale, int causal,
+                              int window, float softcap, int dtype, void* stream) {
+  KvCall c(EXTEND);
+  c.attention(q, out, lse, workspace, softmax_scale, causal).cache(k_cache, v_cache, cache_seqlens, Ncap);
+  c.pool_or_slabs(block_table, num_pages, page_size, max_pages).heads(B, H, Hkv, Nq, d).format(layout, dtype, stream);
+  if (k_new || v_new) c.new_tokens(k_new, v_new, d_new);
+  c.window = window, c.softcap = softcap, c.d256 = true;
+  return run(c);
+}
+
+// (the append's checks are the extend family's: any Nq >= 1; the kernel is decode_append_kernel at a 256-element row)
+int fa_mi355x_append_d256(const void* k_new, const void* v_new, void* k_cache, void* v_cache, const int* cache_seqlens,
+                          const int* block_table, int B, int Hkv, int Nq, int Ncap, int num_pages, int page_size, int max_pages,
+                          int d_new, int d, int layout, int dtype, void* stream) {
+  KvCall c(EXTEND);
+  c.new_tokens(k_new, v_new, d_new).cache(k_cache, v_cache, cache_seqlens, Ncap);
+  c.pool_or_slabs(block_table, num_pages, page_size, max_pages).heads(B, Hkv, Hkv, Nq, d).format(layout, dtype, stream);
+  c.d256 = true;
+  return run(c);
+}
+
+int fa_mi355x_decode_d256_splits(int B, int H, int Hkv, int Nq, int Ncap, int d, int dtype, int window) {
+  (void)dtype;
+  return d == fa::D256 ? query(DECODE, B, H, Hkv, Nq, Ncap, d, window, 0).nsplit : 0;
+}
+
+size_t fa_mi355x_decode_d256_workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int d, int window) {
+  return d == fa::D256 ? query(DECODE, B, H, Hkv, Nq, Ncap, d, window, 0).workspace_bytes : 0;
+}
+
+int fa_mi355x_extend_d256_splits(int B, int H, int Hkv, int Nq, int Ncap, int d, int dtype, int window) {
+  (void)dtype;
+  return d == fa::D256 ? query(EXTEND, B, H, Hkv, Nq, Ncap, d, window, 0).nsplit : 0;
+}
+
+size_t fa_mi355x_extend_d256_workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int d, int window) {
+  return d == fa::D256 ? query(EXTEND, B, H, Hkv, Nq, Ncap, d, window, 0).workspace_bytes : 0;
 }
 
 // ---- the rotary entry points (include/flash_attn_mi355x_decode_rope.h) ----

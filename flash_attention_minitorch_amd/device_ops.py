@@ -653,7 +653,8 @@ _KV_FAMILIES = {
             ungrouped="fa_mi355x_fwd_decode", attend="fa_mi355x_fwd_decode_gqa", fused="fa_mi355x_fwd_decode_append",
             paged="fa_mi355x_fwd_decode_paged", fused_paged="fa_mi355x_fwd_decode_append_paged", window="fa_mi355x_fwd_decode_window",
             sink="fa_mi355x_fwd_decode_sink", softcap="fa_mi355x_fwd_decode_softcap", lsink="fa_mi355x_fwd_decode_lsink",
-            fp8="fa_mi355x_fwd_decode_fp8",
+            fp8="fa_mi355x_fwd_decode_fp8", d256="fa_mi355x_fwd_decode_d256", append_d256="fa_mi355x_append_d256",
+            size_d256="fa_mi355x_decode_d256_workspace_bytes",
             append="fa_mi355x_decode_append",
             append_paged="fa_mi355x_decode_append_paged", append_fp8="fa_mi355x_append_fp8", rope="fa_mi355x_rope_append",
             size_ungrouped="fa_mi355x_decode_workspace_bytes", size="fa_mi355x_decode_workspace_bytes_gqa",
@@ -666,6 +667,7 @@ _KV_FAMILIES = {
             attend="fa_mi355x_fwd_extend", fused="fa_mi355x_fwd_extend_append", paged="fa_mi355x_fwd_extend_paged",
             fused_paged="fa_mi355x_fwd_extend_append_paged", window="fa_mi355x_fwd_extend_window", sink="fa_mi355x_fwd_extend_sink",
             softcap="fa_mi355x_fwd_extend_softcap", lsink="fa_mi355x_fwd_extend_lsink", fp8="fa_mi355x_fwd_extend_fp8",
+            d256="fa_mi355x_fwd_extend_d256", append_d256="fa_mi355x_append_d256", size_d256="fa_mi355x_extend_d256_workspace_bytes",
             append="fa_mi355x_extend_append",
             append_paged="fa_mi355x_extend_append_paged",
             append_fp8="fa_mi355x_append_fp8", rope="fa_mi355x_rope_append", size="fa_mi355x_extend_workspace_bytes",
@@ -685,15 +687,18 @@ _KV_FAMILIES = {
 }
 
 
-def _kv_symbol(fam, op, paged=False, fused=False, window=None, sink=None, fp8=False, ungrouped=False, softcap=None, lsink=False):
+def _kv_symbol(fam, op, paged=False, fused=False, window=None, sink=None, fp8=False, ungrouped=False, softcap=None, lsink=False, d256=False):
     """The C symbol of a call.  ``op`` "append": the append (fa_mi355x_append_fp8 takes slab and paged caches alike); "size": the size
     query; "attend": the attention -- one entry point per family on an fp8 cache, with sink tokens and with a window (null k_new /
     v_new attend only, a null table is a slab cache), otherwise the _paged and the fused _append forms.  ``window`` None takes the
     unwindowed symbols; ``ungrouped`` (Hkv = H) the ones without an Hkv, where the family has them.  ``softcap`` (not None: a cap
     above 0, never beside sink tokens or an fp8 cache) takes the family's one soft-capping entry point, windowed or not; the size
     queries do not depend on it.  ``lsink`` (learned sink logits: never beside a cap, sink tokens or an fp8 cache) takes the family's
-    one _lsink entry point, likewise."""
+    one _lsink entry point, likewise.  ``d256`` (a cache of 256-wide rows, checked by _check_d256: none of the options that have no
+    such build) takes the family's one _d256 entry point per op, which has a window, a cap, the new tokens and a table as arguments."""
     symbols = fam["symbols"]
+    if d256:
+        return symbols[{"append": "append_d256", "size": "size_d256"}.get(op, "d256")]
     if op == "append":
         return symbols["append_fp8" if fp8 else "append_paged" if paged else "append"]
     if op == "size":
@@ -768,8 +773,31 @@ def _kv_geometry(fam, k_cache, layout, max_pages, q=None, cu_seqlens_q=None):
     return Hkv, dp, Ncap, pool, B, H, Nq, d
 
 
+_D256 = 256   # the one head dim above 128 the KV-cache calls run at, through kernels of its own (include/flash_attn_mi355x_decode_d256.h)
+
+
+def _check_d256(fam, cache, sink=None, sink_logits=None, rotary=None):
+    """A call on caches of 256-wide rows: what is not built at that head dim is refused here by name, before any library call."""
+    if "d256" not in fam["symbols"]:
+        raise ValueError(f"{fam['attend']} and {fam['append']} at head dim 256 are not built: use flash_attn_decode / flash_attn_extend "
+                         "and decode_append / extend_append")
+    if _is_fp8(cache):
+        raise ValueError("an fp8 (torch.float8_e4m3fn) cache at head dim 256 is not built: the d = 256 kernels take bfloat16 caches")
+    if cache.dtype != torch.bfloat16:
+        raise ValueError("a float32 cache at head dim 256 is not built: the d = 256 kernels take bfloat16 caches")
+    if sink is not None:
+        raise ValueError("sink tokens at head dim 256 are not built: sink= on a cache of 256-wide rows")
+    if sink_logits is not None:
+        raise ValueError("sink_logits at head dim 256 is not built: sink_logits= on a cache of 256-wide rows")
+    if rotary:
+        raise ValueError("the fused rotary keywords at head dim 256 are not built: rotary_cos= / rotary_sin= on a cache of 256-wide "
+                         "rows (rotate q and k_new with apply_rotary in front of the call)")
+
+
 def _kv_workspace_bytes(fam, B, H, Hkv, Nq, Ncap, dp, window, sink):
     """The family's size query for a call of these sizes."""
+    if dp == _D256:   # (checked by _check_d256: no sink; the one query takes a window, 0 for none)
+        return _kv_call(_kv_symbol(fam, "size", d256=True), {"B": B, "H": H, "Hkv": Hkv, "Nq": Nq, "Ncap": Ncap, "d": dp, "window": window or 0})
     return _kv_call(_kv_symbol(fam, "size", False, False, window, sink, False, Hkv == H),
                     {"B": B, "H": H, "Hkv": Hkv, "Nq": Nq, "Ncap": Ncap, "d": dp, "window": window, "sink": sink})
 
@@ -781,6 +809,8 @@ def _kv_workspace(family, q, k_cache, cu_seqlens_q, layout, block_table, max_pag
         raise ValueError(f"layout must be one of {sorted(_DECODE_LAYOUTS)}")
     Hkv, dp, Ncap, _, B, H, Nq, _ = _kv_geometry(fam, k_cache, layout, _max_pages(block_table, max_pages), q, cu_seqlens_q)
     window = _check_window(window)
+    if dp == _D256:
+        _check_d256(fam, k_cache, _check_sink(sink, window))
     nbytes = _kv_workspace_bytes(fam, B, H, Hkv, Nq, Ncap, dp, window, _check_sink(sink, window))
     return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=q.device) if nbytes or not fam["workspace_none"] else None
 
@@ -1318,6 +1348,8 @@ def _kv_append(family, k_new, v_new, k_cache, v_cache, cu_seqlens_q, cache_seqle
         raise TypeError(_RAGGED_FP8)
     dtype = _lib.FA_DTYPE_BF16 if fp8 else _dtype_code(k_cache)
     Hkv, dp, Ncap, pool, *_ = _kv_geometry(fam, k_cache, layout, None if block_table is None else _max_pages(block_table, None))
+    if dp == _D256:
+        _check_d256(fam, k_cache, rotary=rotary)
     Bc = None if pool else k_cache.shape[0]
     Nq, d_new = _check_new(fam, k_new, v_new, k_cache, layout, None, Hkv, dp, Bc)
     if fam["packed"]:
@@ -1344,7 +1376,7 @@ def _kv_append(family, k_new, v_new, k_cache, v_cache, cu_seqlens_q, cache_seqle
         _check_rot(rotary, dp, d_new)
         _rope_append(fam, fields, rotary, fp8)
     else:
-        _lib.decode_check(_kv_call(_kv_symbol(fam, "append", paged=pool is not None, fp8=fp8), fields))
+        _lib.decode_check(_kv_call(_kv_symbol(fam, "append", paged=pool is not None, fp8=fp8, d256=dp == _D256), fields))
 
 
 def decode_append(k_new, v_new, k_cache, v_cache, cache_seqlens=None, layout="bnhd", block_table=None, k_scale=None, v_scale=None,
@@ -1426,6 +1458,8 @@ def _kv_attention(family, q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, caus
     if max_pages is not None and max_pages != mp:   # (the caller's own figure, e.g. the one a workspace was sized with: held against the table)
         raise ValueError(f"max_pages = {max_pages} is not the block_table's second dimension ({mp}; a contiguous cache has none)")
     Hkv, dp, Ncap, pool, B, H, Nq, d = _kv_geometry(fam, k_cache, layout, mp, q, cu_seqlens_q)
+    if dp == _D256:
+        _check_d256(fam, k_cache, sink, sink_logits, rotary)
     if d > dp:
         raise ValueError(f"q's head dim {d} exceeds the cache's row length {dp}")
     _check_scales(k_scale, v_scale, fp8, Hkv, q.device)
@@ -1491,7 +1525,10 @@ def _kv_attention(family, q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, caus
             q_rot.copy_(qr[..., :d])
         fields.update(q=_ptr(qr), k_new=None, v_new=None, d_new=dp)
         k_new = None
-    symbol = _kv_symbol(fam, "attend", pool is not None, k_new is not None, window, sink, fp8, Hkv == H, softcap, sink_logits is not None)
+    if dp == _D256:   # (the one entry point takes a window and a cap: 0 is none)
+        fields.update(window=window or 0, softcap=softcap or 0.0)
+    symbol = _kv_symbol(fam, "attend", pool is not None, k_new is not None, window, sink, fp8, Hkv == H, softcap, sink_logits is not None,
+                        dp == _D256)
     _lib.decode_check(_kv_call(symbol, fields))
     return (_unpad(outp, d, out) if d < dp else outp), lse
 
@@ -1502,7 +1539,10 @@ def flash_attn_decode(q, k_cache, v_cache, cache_seqlens=None, causal=True, soft
     """Attention of Nq <= 128 new queries against a KV cache (fa_mi355x_fwd_decode / _gqa, include/flash_attn_mi355x_decode.h).
     ``layout`` "bnhd": q (B, Nq, H, d), caches (B, Ncap, Hkv, dp); "bhnd": q (B, H, Nq, d), caches (B, Hkv, Ncap, dp).  Hkv is the
     cache's own head count and must divide H: Hkv < H is a grouped-query (Hkv = 1: multi-query) cache, query head h reads cache head
-    h // (H // Hkv), and the group's heads share one pass over it (no expansion of the cache).  dp in {32, 64, 128};
+    h // (H // Hkv), and the group's heads share one pass over it (no expansion of the cache).  dp in {32, 64, 128}, or 256
+    (bfloat16 only, kernels of their own behind fa_mi355x_fwd_decode_d256, include/flash_attn_mi355x_decode_d256.h: slab or paged,
+    ``window``, ``softcap``, the fused append and causal=False work as below; ``sink``, ``sink_logits``, an fp8 or float32 cache and
+    the rotary keywords are a ValueError there, and so is flash_attn_ragged);
     a q with fewer columns (d < dp) is zero-padded to the cache's row length (the cache itself holds zero columns d .. dp-1) and the
     default scale is then 1/sqrt(d).  ``cache_seqlens``: int32 (B,) on q's device, the valid cache rows per batch element counting the
     new tokens (None: all Ncap); clamped to [0, Ncap] on the device, no host synchronisation.  ``causal``: the queries are the last Nq

@@ -401,7 +401,8 @@ class KVCache:
                  sink=None, rope=None, softcap=None, sink_logits=None):
         self.window = _check_cache_window(window)
         self.sink = _check_cache_sink(sink, self.window)
-        self.head_dim, self.dp = head_dim, device_ops.padded_head_dim(head_dim)
+        # (256-wide heads have KV-cache kernels of their own; every other head dim runs at the next of 32, 64, 128)
+        self.head_dim, self.dp = head_dim, head_dim if head_dim == device_ops._D256 else device_ops.padded_head_dim(head_dim)
         self.capacity, self.n_head = capacity, n_head
         self.n_kv_head = n_head if n_kv_head is None else n_kv_head
         if self.n_kv_head <= 0 or n_head % self.n_kv_head:
@@ -629,11 +630,12 @@ def attention_stack_prefill(x, layers, n_head: int, cache: KVCache):
     attention reads those cache-shaped k and v in place (device_ops.flash_attn_fwd_gqa: no expanded copy).  Returns the stack's
     output (B, P, E).  A WINDOWED cache does not use that square forward, which has no window: its prompt goes through the extend
     kernels as one piece (attention_stack_prefill_chunked with chunk = P), which append and attend through the window.  A cache with
-    a SOFTCAP takes the same route: the square forward has no cap.  So does a cache with learned SINK LOGITS."""
+    a SOFTCAP takes the same route: the square forward has no cap.  So does a cache with learned SINK LOGITS, and one of 256-wide
+    heads (the training forward stops at d = 128)."""
     B, P, E = x.shape
     if P > cache.capacity:
         raise ValueError(f"prompt of {P} tokens exceeds the cache capacity {cache.capacity}")
-    if cache.window is not None or cache.softcap is not None or cache.sink_logits is not None:
+    if cache.window is not None or cache.softcap is not None or cache.sink_logits is not None or cache.dp == device_ops._D256:
         return attention_stack_prefill_chunked(x, layers, n_head, cache, max(P, 1))
     d = E // n_head
     # an fp8 cache, slab or paged, and every paged one take the prompt through the library's append (it quantises, and it knows the

@@ -179,4 +179,9 @@ const char* fa_mi355x_decode_last_error(void);
  * kept in a file of their own. */
 #include "flash_attn_mi355x_decode_lsink.h"
 
+/* Head dim 256 (Gemma-2 2B / 9B, most of Gemma-3): the decode and extend calls and the append on caches whose rows hold 256 bf16
+ * elements, through kernels of their own: seven entry points, part of this library and of this header, kept in a file of their
+ * own.  (The entry points above keep answering d = 256 with FA_ERR_UNSUPPORTED_D.) */
+#include "flash_attn_mi355x_decode_d256.h"
+
 #endif /* FLASH_ATTN_MI355X_DECODE_H */
