@@ -2,14 +2,17 @@
 // _window.h, _sink.h, _fp8.h, _softcap.h, _lsink.h, _rope.h and _d256.h).  Every entry point fills one KvCall (the call as it was received) and hands it to run():
 // the entry point's prelude (check_fp8 or check_window), the page geometry (check_pages), the attention's checks (check_attend, which
 // also returns the call's Policy), the append's (check_append), then the append launch (run_append) and the attention's launches
-// (run_attend -> launch_split).  policy() is the one split policy: the three families (decode: 32-row blocks, at most 128 queries;
-// extend: 128-row blocks, any number; ragged: the extend policy on an upper bound of the row blocks) differ by the data of FAMILIES.
+// (run_attend): select() reads them off the one launch table, a row per kernel instance with the call it serves, as plain data (the
+// ragged schedule, the split build, the combine build), and launch() walks that value.  policy() is the one split policy: the three
+// families (decode: 32-row blocks, at most 128 queries; extend: 128-row blocks, any number; ragged: the extend policy on an upper
+// bound of the row blocks) differ by the data of FAMILIES.
 // A paged call (a pool and a block table) takes the contiguous call's policy at Ncap = max_pages * page_size.  A windowed call takes
 // the policy on its window span (span_keys) instead of Ncap, a sink call on that span plus its sink tiles.  An fp8 call (caches of
 // e4m3 bytes, per-kv-head scales) takes the bf16 call's policy and workspace for the same arguments; its cache bounds count one byte
-// per element.  A soft-capped call (softcap > 0) takes the policy and workspace of the same call without the cap, the softcap builds
-// of the split kernels and the existing combine kernels with tau = 1.  A call with learned sink logits (sink_logits not null) takes
-// the policy and workspace of the same call without them, the lsink builds of the split kernels and of the combine kernel.  The rotary calls launch the kernels of fa_rope.h in front of the attend-only entry points.
+// per element.  A soft-capped call (softcap > 0) takes the policy and workspace of the same call without the cap, the softcap rows of
+// the table and the existing combine kernels with tau = 1.  A call with learned sink logits (sink_logits not null) takes the policy
+// and workspace of the same call without them and the lsink rows, split and combine.  d = 256 (_d256.h) is a table of the same rows
+// over the kernels of fa_decode_d256.h.  The rotary calls launch the kernels of fa_rope.h in front of the attend-only entry points.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -42,7 +45,7 @@ enum Family { DECODE, EXTEND, RAGGED };
 
 struct FamilyRule {
   int block_rows, waves;   // rows of a workgroup's row block; workgroups per CU the split aims at
-  const char *sizes, *append_sizes, *rows, *q_bytes, *grid, *workspace, *split_launch, *combine_launch;
+  const char *sizes, *append_sizes, *rows, *q_bytes, *grid, *workspace;
 };
 
 // Extend: a workgroup of extend_split_kernel owns 128 rows, and TWO workgroups per CU are the target: a workgroup there lives for a
@@ -50,18 +53,15 @@ struct FamilyRule {
 // over B*H*Nq rows (measured: profiles/extend_bench.txt).
 constexpr FamilyRule FAMILIES[3] = {
     {32, 4, "B, H, Nq, Ncap and d must be positive", "B, Hkv, Nq, Ncap and d must be positive", nullptr,
-     "one batch element of q must stay under 2 GiB", nullptr, "null workspace: this call needs fa_mi355x_decode_workspace_bytes() bytes",
-     "decode_split_kernel launch", "decode_combine_kernel launch"},
+     "one batch element of q must stay under 2 GiB", nullptr, "null workspace: this call needs fa_mi355x_decode_workspace_bytes() bytes"},
     {fa::EXT_BLOCK, 2, "B, H, Nq, Ncap and d must be positive", "B, Hkv, Nq, Ncap and d must be positive",
      "G * Nq rows per kv head must stay under 2^25", "one batch element of q must stay under 2 GiB",
      "too many workgroups for one launch: B * Hkv * splits * row blocks and B * H * Nq must fit an unsigned int",
-     "null workspace: this call needs fa_mi355x_extend_workspace_bytes() bytes", "extend_split_kernel launch",
-     "decode_combine_kernel launch"},
+     "null workspace: this call needs fa_mi355x_extend_workspace_bytes() bytes"},
     {fa::EXT_BLOCK, 2, "B, H, T, Ncap and d must be positive", "B, Hkv, T, Ncap and d must be positive",
      "G * T rows per kv head must stay under 2^25", "q (T * H * d elements) must stay under 2 GiB",
      "too many workgroups for one launch: Hkv * splits * row blocks and H * T must fit an unsigned int",
-     "null workspace: a ragged call always needs fa_mi355x_ragged_workspace_bytes() bytes (the block map)",
-     "extend_split_kernel (ragged) launch", "decode_combine_kernel (ragged) launch"},
+     "null workspace: a ragged call always needs fa_mi355x_ragged_workspace_bytes() bytes (the block map)"},
 };
 
 // A paged call's block table and pool geometry (all zero in the contiguous call).
@@ -267,8 +267,10 @@ int check_cache_bytes(const KvCall& c) {
   return FA_OK;
 }
 
-// What the head-dim-256 entry points (_d256.h) ask in the place of d in {32, 64, 128}.
-int check_d256(const KvCall& c) {
+// Which d an entry point accepts: d in {32, 64, 128}, answered with the caller's message (the attention's and the append's differ);
+// the head-dim-256 entry points (_d256.h) ask for d = 256 exactly and bf16 in its place.
+int check_d(const KvCall& c, const char* unsupported) {
+  if (!c.d256) return c.d == 32 || c.d == 64 || c.d == 128 ? FA_OK : set_err(FA_ERR_UNSUPPORTED_D, unsupported);
   if (c.d != fa::D256)
     return set_err(FA_ERR_UNSUPPORTED_D, "the _d256 entry points take d = 256 exactly: d in {32, 64, 128} runs through the other entry points");
   if (c.dtype != FA_DTYPE_BF16)
@@ -293,11 +295,8 @@ int check_attend(const KvCall& c, Policy* out) {
   if (c.layout != FA_LAYOUT_BHND && c.layout != FA_LAYOUT_BNHD) return set_err(FA_ERR_BAD_ARG, "unknown layout");
   if (!c.q || !c.k_cache || !c.v_cache || !c.out) return set_err(FA_ERR_BAD_ARG, "null pointer argument");
   if (c.family == RAGGED && !c.cu) return set_err(FA_ERR_BAD_ARG, "null cu_seqlens_q");
-  if (c.d256) {
-    const int rc = check_d256(c);
-    if (rc != FA_OK) return rc;
-  } else if (c.d != 32 && c.d != 64 && c.d != 128)
-    return set_err(FA_ERR_UNSUPPORTED_D, "decode supports d in {32, 64, 128}: pad the cache with zero columns for other d <= 128");
+  const int rc = check_d(c, "decode supports d in {32, 64, 128}: pad the cache with zero columns for other d <= 128");
+  if (rc != FA_OK) return rc;
   if (c.softmax_scale != 0.f && (!(c.softmax_scale > 0.f) || !std::isfinite(c.softmax_scale)))
     return set_err(FA_ERR_BAD_ARG, "softmax_scale must be positive and finite (0: 1/sqrt(d))");
   // (row_query is exact for rows below 2^25; a ragged sequence has at most G * T of them)
@@ -327,11 +326,8 @@ int check_append(const KvCall& c) {
   if (!c.k_new || !c.v_new || !c.k_cache || !c.v_cache)
     return set_err(FA_ERR_BAD_ARG, "null pointer argument (k_new, v_new and the caches)");
   if (c.family == RAGGED && !c.cu) return set_err(FA_ERR_BAD_ARG, "null cu_seqlens_q");
-  if (c.d256) {
-    const int rc = check_d256(c);
-    if (rc != FA_OK) return rc;
-  } else if (c.d != 32 && c.d != 64 && c.d != 128)
-    return set_err(FA_ERR_UNSUPPORTED_D, "decode supports cache rows of d in {32, 64, 128}");
+  const int rc = check_d(c, "decode supports cache rows of d in {32, 64, 128}");
+  if (rc != FA_OK) return rc;
   if (c.d_new < 1 || c.d_new > c.d) {
     snprintf(g_err, sizeof(g_err), "d_new = %d must be in 1 .. d = %d", c.d_new, c.d);
     return FA_ERR_BAD_ARG;
@@ -376,42 +372,25 @@ void set_append(fa::AppendArgs& a, const KvCall& c) {
   set_cache_geometry(a, c);
 }
 
-// The host's view of a split launch: every build's argument is a part of it (DecodeArgs, RaggedArgs) or a copy of such a part with
-// the scales or the sink count behind it (Fp8Args, SinkArgs, RaggedSinkArgs), which the leg that launches such a build makes.
+// The host's view of an attention's launches: every build's argument is a part of it (DecodeArgs, RaggedArgs) or such a part with the
+// scales, the sink count, the cap or the logits behind it (Fp8Args and the Sink, Softcap and Lsink pairs), which kernel_arg makes.
 struct SplitArgs : fa::RaggedArgs {
   Fp8 f8;
   int sink;        // S >= 1: a sink reaches the device
-  float softcap;   // > 0: the softcap builds (SoftcapArgs, RaggedSoftcapArgs), and tau = 1 for the combine kernel
-  const float* sink_logits;   // not null: the lsink builds (LsinkArgs, RaggedLsinkArgs) and the lsink build of the combine kernel
+  float softcap;   // > 0: a cap reaches the device
+  const float* sink_logits;   // not null: the logits reach the device
 };
 
-template <typename S, typename Base> S with_lsink(const SplitArgs& a) {
-  S s;
-  static_cast<Base&>(s) = a;
-  s.sink_logits = a.sink_logits;
-  return s;
-}
-
-template <typename S, typename Base> S with_softcap(const SplitArgs& a) {
-  S s;
-  static_cast<Base&>(s) = a;
-  s.softcap = a.softcap;
-  return s;
-}
-
-template <typename S, typename Base> S with_sink(const SplitArgs& a) {
-  S s;
-  static_cast<Base&>(s) = a;
-  s.sink = a.sink;
-  return s;
-}
-
-fa::Fp8Args with_scales(const SplitArgs& a) {
-  fa::Fp8Args f;
-  static_cast<fa::DecodeArgs&>(f) = a;
-  f.k_scale = a.f8.k_scale;
-  f.v_scale = a.f8.v_scale;
-  return f;
+// The one converter: a build's argument type A out of the host's view.
+template <typename A> A kernel_arg(const SplitArgs& a) {
+  constexpr bool R = std::is_base_of<fa::RaggedArgs, A>::value;
+  A k;
+  static_cast<typename std::conditional<R, fa::RaggedArgs, fa::DecodeArgs>::type&>(k) = a;
+  if constexpr (std::is_same<A, fa::Fp8Args>::value) k.k_scale = a.f8.k_scale, k.v_scale = a.f8.v_scale;
+  if constexpr (std::is_same<A, fa::SinkArgsOf<R>>::value) k.sink = a.sink;
+  if constexpr (std::is_same<A, fa::SoftcapArgsOf<R>>::value) k.softcap = a.softcap;
+  if constexpr (std::is_same<A, fa::LsinkArgsOf<R>>::value) k.sink_logits = a.sink_logits;
+  return k;
 }
 
 // ---- the launches ----
@@ -419,165 +398,170 @@ template <typename A, typename B> void launch256(void (*kernel)(A), long grid, h
   hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), 0, st, static_cast<const A&>(a));
 }
 
-// The launches of a checked attention: (ragged) the schedule, the split build of the table below, and the combine if nsplit > 1.
-// Which instance serves which call:
-//   decode  the ungrouped build for exactly the slab, unwindowed, non-fp8, G == 1 call; the grouped build for every other (one paged
-//           build: G = 1 computes the same rows, and a paged workgroup looks up its page anyway; the windowed, sink and fp8 builds
-//           likewise)
-//   extend, ragged  PAGED x WINDOW as the call has them; ragged is the RAGGED flag of the extend kernels
-//   sink    kernels and an argument of their own, only when a sink reaches the device (a.sink >= 1, which implies a.window >= 1)
-//   fp8     bf16 queries, slab or paged, no window (the Python layer refuses the combination by name)
-//   softcap kernels and an argument of their own, only when a cap reaches the device (a.softcap > 0): PAGED x WINDOW as the call has
-//           them, the grouped build in the decode family; the combine launch is the existing instance with tau = 1
-//   lsink   kernels and an argument of their own, only when the logits reach the device (a.sink_logits not null): the softcap
-//           legs' choice of builds, and the lsink build of the combine kernel; as many launches as the call without the logits
-template <typename T, int D> int launch_split(const SplitArgs& a, Family f, hipStream_t st) {
-  constexpr bool BF16 = std::is_same<T, fa::bf16_t>::value;
-  const bool paged = a.table != nullptr, window = a.window != 0;
-  const long grid = split_grid(a.items, a.nqb);
-  if (f == RAGGED) {
-    hipLaunchKernelGGL(fa::ragged_schedule_kernel, dim3(1), dim3(256), 0, st, a.cu, const_cast<int*>(a.map), a.nseq, a.ntok, a.G, a.nqb);
+// One launch of an attention as data: go<kernel>, which makes the kernel's own argument and launches it with its workgroup size (256
+// lanes, or the 512 of decode_split_d256_kernel), and the name that goes into the hip_err message.
+using LaunchFn = void (*)(const SplitArgs&, long grid, hipStream_t);
+struct Launch {
+  LaunchFn fn;
+  const char* what;
+};
+
+template <typename A> A arg_of(void (*)(A));
+template <auto K, int BLOCK = 256> void go(const SplitArgs& a, long grid, hipStream_t st) {
+  hipLaunchKernelGGL(K, dim3((unsigned)grid), dim3(BLOCK), 0, st, kernel_arg<decltype(arg_of(K))>(a));
+}
+void go_schedule(const SplitArgs& a, long grid, hipStream_t st) {
+  hipLaunchKernelGGL(fa::ragged_schedule_kernel, dim3((unsigned)grid), dim3(256), 0, st, a.cu, const_cast<int*>(a.map), a.nseq, a.ntok, a.G, a.nqb);
+}
+
+// The launch table: every kernel instance an attention launches, once, with the call it serves.  A split build serves the calls of
+// its family whose cache (slab or PAGED), mask (WINDOW or none) and feature are the row's.  The feature is what reaches the device:
+// the fp8 scales, else a cap (softcap > 0), else the logits (sink_logits not null), else sink tokens (S >= 1, which implies a
+// window), else nothing; the entry points take one of them each.  G1: the ungrouped decode_split_kernel<T, D, false> serves only the
+// slab, unwindowed, featureless call of G = 1; the grouped build behind it serves every other such call, and G = 1 on every other row
+// as well (it computes the same rows, and a paged workgroup looks up its page anyway).  ragged is the RAGGED flag of the extend
+// kernels.  fp8: bf16 queries (check_fp8), no window (the Python layer refuses the combination by name).  d = 256 (bf16, decode and
+// extend, PAGED x WINDOW x cap) is the table of its own kernels (fa_decode_d256.h) below.  The SCHEDULE row goes in front of every
+// ragged split, a COMBINE row behind a split of nsplit > 1: one for decode and extend (the row says DECODE) and one for ragged, with
+// builds of their own only where the combine has a state of its own (the fp8 scales, the logits: every other feature takes PLAIN).
+enum Feature { PLAIN, SINK, LSINK, SOFTCAP, FP8 };
+enum { PAGED = 1, WINDOW = 2, G1 = 4, COMBINE = 8, SCHEDULE = 16 };
+
+struct Row {
+  Family family;
+  Feature feature;
+  int flags;
+  Launch launch;
+};
+struct Table {
+  const Row* rows;
+  size_t n;
+};
+
+template <typename T, int D> Table table() {
+  static const Row rows[] = {
+      {DECODE, PLAIN, G1, go<fa::decode_split_kernel<T, D, false>>, "decode_split_kernel launch"},
+      {DECODE, PLAIN, 0, go<fa::decode_split_kernel<T, D, true>>, "decode_split_kernel launch"},
+      {DECODE, PLAIN, PAGED, go<fa::decode_split_kernel<T, D, true, true>>, "decode_split_kernel launch"},
+      {DECODE, PLAIN, WINDOW, go<fa::decode_split_kernel<T, D, true, false, true>>, "decode_split_kernel launch"},
+      {DECODE, PLAIN, PAGED | WINDOW, go<fa::decode_split_kernel<T, D, true, true, true>>, "decode_split_kernel launch"},
+      {DECODE, SINK, WINDOW, go<fa::decode_split_sink_kernel<T, D, false>>, "decode_split_kernel launch"},
+      {DECODE, SINK, PAGED | WINDOW, go<fa::decode_split_sink_kernel<T, D, true>>, "decode_split_kernel launch"},
+      {DECODE, LSINK, 0, go<fa::decode_split_lsink_kernel<T, D, false, false>>, "decode_split_lsink_kernel launch"},
+      {DECODE, LSINK, PAGED, go<fa::decode_split_lsink_kernel<T, D, true, false>>, "decode_split_lsink_kernel launch"},
+      {DECODE, LSINK, WINDOW, go<fa::decode_split_lsink_kernel<T, D, false, true>>, "decode_split_lsink_kernel launch"},
+      {DECODE, LSINK, PAGED | WINDOW, go<fa::decode_split_lsink_kernel<T, D, true, true>>, "decode_split_lsink_kernel launch"},
+      {DECODE, SOFTCAP, 0, go<fa::decode_split_softcap_kernel<T, D, false, false>>, "decode_split_softcap_kernel launch"},
+      {DECODE, SOFTCAP, PAGED, go<fa::decode_split_softcap_kernel<T, D, true, false>>, "decode_split_softcap_kernel launch"},
+      {DECODE, SOFTCAP, WINDOW, go<fa::decode_split_softcap_kernel<T, D, false, true>>, "decode_split_softcap_kernel launch"},
+      {DECODE, SOFTCAP, PAGED | WINDOW, go<fa::decode_split_softcap_kernel<T, D, true, true>>, "decode_split_softcap_kernel launch"},
+      {DECODE, FP8, 0, go<fa::decode_split_kernel<fa::bf16_t, D, true, false, false, true>>, "decode_split_kernel (fp8) launch"},
+      {DECODE, FP8, PAGED, go<fa::decode_split_kernel<fa::bf16_t, D, true, true, false, true>>, "decode_split_kernel (fp8) launch"},
+      {EXTEND, PLAIN, 0, go<fa::extend_split_kernel<T, D>>, "extend_split_kernel launch"},
+      {EXTEND, PLAIN, PAGED, go<fa::extend_split_kernel<T, D, true>>, "extend_split_kernel launch"},
+      {EXTEND, PLAIN, WINDOW, go<fa::extend_split_kernel<T, D, false, false, true>>, "extend_split_kernel launch"},
+      {EXTEND, PLAIN, PAGED | WINDOW, go<fa::extend_split_kernel<T, D, true, false, true>>, "extend_split_kernel launch"},
+      {EXTEND, SINK, WINDOW, go<fa::extend_split_sink_kernel<T, D, false, false>>, "extend_split_kernel launch"},
+      {EXTEND, SINK, PAGED | WINDOW, go<fa::extend_split_sink_kernel<T, D, true, false>>, "extend_split_kernel launch"},
+      {EXTEND, LSINK, 0, go<fa::extend_split_lsink_kernel<T, D, false, false, false>>, "extend_split_lsink_kernel launch"},
+      {EXTEND, LSINK, PAGED, go<fa::extend_split_lsink_kernel<T, D, true, false, false>>, "extend_split_lsink_kernel launch"},
+      {EXTEND, LSINK, WINDOW, go<fa::extend_split_lsink_kernel<T, D, false, false, true>>, "extend_split_lsink_kernel launch"},
+      {EXTEND, LSINK, PAGED | WINDOW, go<fa::extend_split_lsink_kernel<T, D, true, false, true>>, "extend_split_lsink_kernel launch"},
+      {EXTEND, SOFTCAP, 0, go<fa::extend_split_softcap_kernel<T, D, false, false, false>>, "extend_split_softcap_kernel launch"},
+      {EXTEND, SOFTCAP, PAGED, go<fa::extend_split_softcap_kernel<T, D, true, false, false>>, "extend_split_softcap_kernel launch"},
+      {EXTEND, SOFTCAP, WINDOW, go<fa::extend_split_softcap_kernel<T, D, false, false, true>>, "extend_split_softcap_kernel launch"},
+      {EXTEND, SOFTCAP, PAGED | WINDOW, go<fa::extend_split_softcap_kernel<T, D, true, false, true>>, "extend_split_softcap_kernel launch"},
+      {EXTEND, FP8, 0, go<fa::extend_split_kernel<fa::bf16_t, D, false, false, false, true>>, "extend_split_kernel (fp8) launch"},
+      {EXTEND, FP8, PAGED, go<fa::extend_split_kernel<fa::bf16_t, D, true, false, false, true>>, "extend_split_kernel (fp8) launch"},
+      {RAGGED, PLAIN, SCHEDULE, go_schedule, "ragged_schedule_kernel launch"},
+      {RAGGED, PLAIN, 0, go<fa::extend_split_kernel<T, D, false, true>>, "extend_split_kernel (ragged) launch"},
+      {RAGGED, PLAIN, PAGED, go<fa::extend_split_kernel<T, D, true, true>>, "extend_split_kernel (ragged) launch"},
+      {RAGGED, PLAIN, WINDOW, go<fa::extend_split_kernel<T, D, false, true, true>>, "extend_split_kernel (ragged) launch"},
+      {RAGGED, PLAIN, PAGED | WINDOW, go<fa::extend_split_kernel<T, D, true, true, true>>, "extend_split_kernel (ragged) launch"},
+      {RAGGED, SINK, WINDOW, go<fa::extend_split_sink_kernel<T, D, false, true>>, "extend_split_kernel (ragged) launch"},
+      {RAGGED, SINK, PAGED | WINDOW, go<fa::extend_split_sink_kernel<T, D, true, true>>, "extend_split_kernel (ragged) launch"},
+      {RAGGED, LSINK, 0, go<fa::extend_split_lsink_kernel<T, D, false, true, false>>, "extend_split_lsink_kernel (ragged) launch"},
+      {RAGGED, LSINK, PAGED, go<fa::extend_split_lsink_kernel<T, D, true, true, false>>, "extend_split_lsink_kernel (ragged) launch"},
+      {RAGGED, LSINK, WINDOW, go<fa::extend_split_lsink_kernel<T, D, false, true, true>>, "extend_split_lsink_kernel (ragged) launch"},
+      {RAGGED, LSINK, PAGED | WINDOW, go<fa::extend_split_lsink_kernel<T, D, true, true, true>>, "extend_split_lsink_kernel (ragged) launch"},
+      {RAGGED, SOFTCAP, 0, go<fa::extend_split_softcap_kernel<T, D, false, true, false>>, "extend_split_softcap_kernel (ragged) launch"},
+      {RAGGED, SOFTCAP, PAGED, go<fa::extend_split_softcap_kernel<T, D, true, true, false>>, "extend_split_softcap_kernel (ragged) launch"},
+      {RAGGED, SOFTCAP, WINDOW, go<fa::extend_split_softcap_kernel<T, D, false, true, true>>, "extend_split_softcap_kernel (ragged) launch"},
+      {RAGGED, SOFTCAP, PAGED | WINDOW, go<fa::extend_split_softcap_kernel<T, D, true, true, true>>, "extend_split_softcap_kernel (ragged) launch"},
+      {DECODE, PLAIN, COMBINE, go<fa::decode_combine_kernel<D>>, "decode_combine_kernel launch"},
+      {DECODE, LSINK, COMBINE, go<fa::decode_combine_lsink_kernel<D, false>>, "decode_combine_kernel launch"},
+      {DECODE, FP8, COMBINE, go<fa::decode_combine_kernel<D, false, true>>, "decode_combine_kernel (fp8) launch"},
+      {RAGGED, PLAIN, COMBINE, go<fa::decode_combine_kernel<D, true>>, "decode_combine_kernel (ragged) launch"},
+      {RAGGED, LSINK, COMBINE, go<fa::decode_combine_lsink_kernel<D, true>>, "decode_combine_kernel (ragged) launch"},
+  };
+  return {rows, sizeof(rows) / sizeof(rows[0])};
+}
+
+template <> Table table<fa::bf16_t, fa::D256>() {
+  static const Row rows[] = {
+      {DECODE, PLAIN, 0, go<fa::decode_split_d256_kernel<false, false, false>, 512>, "decode_split_d256_kernel launch"},
+      {DECODE, PLAIN, PAGED, go<fa::decode_split_d256_kernel<true, false, false>, 512>, "decode_split_d256_kernel launch"},
+      {DECODE, PLAIN, WINDOW, go<fa::decode_split_d256_kernel<false, true, false>, 512>, "decode_split_d256_kernel launch"},
+      {DECODE, PLAIN, PAGED | WINDOW, go<fa::decode_split_d256_kernel<true, true, false>, 512>, "decode_split_d256_kernel launch"},
+      {DECODE, SOFTCAP, 0, go<fa::decode_split_d256_kernel<false, false, true>, 512>, "decode_split_d256_kernel launch"},
+      {DECODE, SOFTCAP, PAGED, go<fa::decode_split_d256_kernel<true, false, true>, 512>, "decode_split_d256_kernel launch"},
+      {DECODE, SOFTCAP, WINDOW, go<fa::decode_split_d256_kernel<false, true, true>, 512>, "decode_split_d256_kernel launch"},
+      {DECODE, SOFTCAP, PAGED | WINDOW, go<fa::decode_split_d256_kernel<true, true, true>, 512>, "decode_split_d256_kernel launch"},
+      {EXTEND, PLAIN, 0, go<fa::extend_split_d256_kernel<false, false, false>>, "extend_split_d256_kernel launch"},
+      {EXTEND, PLAIN, PAGED, go<fa::extend_split_d256_kernel<true, false, false>>, "extend_split_d256_kernel launch"},
+      {EXTEND, PLAIN, WINDOW, go<fa::extend_split_d256_kernel<false, true, false>>, "extend_split_d256_kernel launch"},
+      {EXTEND, PLAIN, PAGED | WINDOW, go<fa::extend_split_d256_kernel<true, true, false>>, "extend_split_d256_kernel launch"},
+      {EXTEND, SOFTCAP, 0, go<fa::extend_split_d256_kernel<false, false, true>>, "extend_split_d256_kernel launch"},
+      {EXTEND, SOFTCAP, PAGED, go<fa::extend_split_d256_kernel<true, false, true>>, "extend_split_d256_kernel launch"},
+      {EXTEND, SOFTCAP, WINDOW, go<fa::extend_split_d256_kernel<false, true, true>>, "extend_split_d256_kernel launch"},
+      {EXTEND, SOFTCAP, PAGED | WINDOW, go<fa::extend_split_d256_kernel<true, true, true>>, "extend_split_d256_kernel launch"},
+      {DECODE, PLAIN, COMBINE, go<fa::decode_combine_d256_kernel<false>>, "decode_combine_d256_kernel launch"},
+  };
+  return {rows, sizeof(rows) / sizeof(rows[0])};
+}
+
+Launch find(Table t, Family f, Feature x, int flags, bool grouped) {
+  for (const Row* r = t.rows; r != t.rows + t.n; ++r)
+    if (r->family == f && r->feature == x && (r->flags & ~G1) == flags && !(grouped && (r->flags & G1))) return r->launch;
+  return {nullptr, nullptr};
+}
+
+// A checked call's launches, in order: the ragged schedule if any, the split build, the combine build if any (a null fn: none).
+struct Launches {
+  Launch schedule, split, combine;
+};
+
+Launches select(Family f, int dtype, int d, bool paged, bool window, Feature x, bool grouped, bool split) {
+  const bool bf16 = dtype == FA_DTYPE_BF16;
+  const Table t = d == 32   ? (bf16 ? table<fa::bf16_t, 32>() : table<float, 32>())
+                  : d == 64 ? (bf16 ? table<fa::bf16_t, 64>() : table<float, 64>())
+                  : d == 128 ? (bf16 ? table<fa::bf16_t, 128>() : table<float, 128>())
+                             : table<fa::bf16_t, fa::D256>();
+  Launches l = {};
+  if (f == RAGGED) l.schedule = find(t, RAGGED, PLAIN, SCHEDULE, grouped);
+  l.split = find(t, f, x, paged * PAGED | window * WINDOW, grouped);
+  if (split) l.combine = find(t, f == RAGGED ? RAGGED : DECODE, x == FP8 || x == LSINK ? x : PLAIN, COMBINE, grouped);
+  return l;
+}
+
+// The one launcher: a ragged schedule is one workgroup, a split build split_grid workgroups, a combine build one per output row.  A
+// combine launch behind a cap runs with tau = 1: the partials' m are capped logits already, and the softmax scale left there would
+// weigh the splits wrongly.
+int launch(const Launches& l, const SplitArgs& a, hipStream_t st) {
+  SplitArgs capped = a;
+  if (a.softcap > 0.f) capped.tau = 1.0f;
+  const struct {
+    const Launch& launch;
+    const SplitArgs& args;
+    long grid;
+  } steps[] = {{l.schedule, a, 1}, {l.split, a, split_grid(a.items, a.nqb)}, {l.combine, capped, (a.cu ? 1L : a.nseq) * a.H * a.Nq}};
+  for (const auto& s : steps) {
+    if (!s.launch.fn) continue;
+    s.launch.fn(s.args, s.grid, st);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_err("ragged_schedule_kernel launch", e);
-  }
-  const char* what = FAMILIES[f].split_launch;
-  if (a.f8.on) {
-    what = f == EXTEND ? "extend_split_kernel (fp8) launch" : "decode_split_kernel (fp8) launch";
-    if constexpr (BF16) {   // (check_fp8: never fp32 queries)
-      const fa::Fp8Args fa8 = with_scales(a);
-      if (f == EXTEND && paged) launch256(fa::extend_split_kernel<T, D, true, false, false, true>, grid, st, fa8);
-      else if (f == EXTEND) launch256(fa::extend_split_kernel<T, D, false, false, false, true>, grid, st, fa8);
-      else if (paged) launch256(fa::decode_split_kernel<T, D, true, true, false, true>, grid, st, fa8);
-      else launch256(fa::decode_split_kernel<T, D, true, false, false, true>, grid, st, fa8);
-    }
-  } else if (a.softcap > 0.f) {   // (no sinks and no fp8 cache beside a cap: the softcap entry points have neither argument)
-    if (f == RAGGED) {
-      what = "extend_split_softcap_kernel (ragged) launch";
-      const fa::RaggedSoftcapArgs ca = with_softcap<fa::RaggedSoftcapArgs, fa::RaggedArgs>(a);
-      if (window && paged) launch256(fa::extend_split_softcap_kernel<T, D, true, true, true>, grid, st, ca);
-      else if (window) launch256(fa::extend_split_softcap_kernel<T, D, false, true, true>, grid, st, ca);
-      else if (paged) launch256(fa::extend_split_softcap_kernel<T, D, true, true, false>, grid, st, ca);
-      else launch256(fa::extend_split_softcap_kernel<T, D, false, true, false>, grid, st, ca);
-    } else {
-      what = f == EXTEND ? "extend_split_softcap_kernel launch" : "decode_split_softcap_kernel launch";
-      const fa::SoftcapArgs ca = with_softcap<fa::SoftcapArgs, fa::DecodeArgs>(a);
-      if (f == EXTEND && window && paged) launch256(fa::extend_split_softcap_kernel<T, D, true, false, true>, grid, st, ca);
-      else if (f == EXTEND && window) launch256(fa::extend_split_softcap_kernel<T, D, false, false, true>, grid, st, ca);
-      else if (f == EXTEND && paged) launch256(fa::extend_split_softcap_kernel<T, D, true, false, false>, grid, st, ca);
-      else if (f == EXTEND) launch256(fa::extend_split_softcap_kernel<T, D, false, false, false>, grid, st, ca);
-      else if (window && paged) launch256(fa::decode_split_softcap_kernel<T, D, true, true>, grid, st, ca);
-      else if (window) launch256(fa::decode_split_softcap_kernel<T, D, false, true>, grid, st, ca);
-      else if (paged) launch256(fa::decode_split_softcap_kernel<T, D, true, false>, grid, st, ca);
-      else launch256(fa::decode_split_softcap_kernel<T, D, false, false>, grid, st, ca);
-    }
-  } else if (a.sink_logits) {   // (no sink tokens, no cap and no fp8 cache beside the logits: the lsink entry points have none of them)
-    if (f == RAGGED) {
-      what = "extend_split_lsink_kernel (ragged) launch";
-      const fa::RaggedLsinkArgs la = with_lsink<fa::RaggedLsinkArgs, fa::RaggedArgs>(a);
-      if (window && paged) launch256(fa::extend_split_lsink_kernel<T, D, true, true, true>, grid, st, la);
-      else if (window) launch256(fa::extend_split_lsink_kernel<T, D, false, true, true>, grid, st, la);
-      else if (paged) launch256(fa::extend_split_lsink_kernel<T, D, true, true, false>, grid, st, la);
-      else launch256(fa::extend_split_lsink_kernel<T, D, false, true, false>, grid, st, la);
-    } else {
-      what = f == EXTEND ? "extend_split_lsink_kernel launch" : "decode_split_lsink_kernel launch";
-      const fa::LsinkArgs la = with_lsink<fa::LsinkArgs, fa::DecodeArgs>(a);
-      if (f == EXTEND && window && paged) launch256(fa::extend_split_lsink_kernel<T, D, true, false, true>, grid, st, la);
-      else if (f == EXTEND && window) launch256(fa::extend_split_lsink_kernel<T, D, false, false, true>, grid, st, la);
-      else if (f == EXTEND && paged) launch256(fa::extend_split_lsink_kernel<T, D, true, false, false>, grid, st, la);
-      else if (f == EXTEND) launch256(fa::extend_split_lsink_kernel<T, D, false, false, false>, grid, st, la);
-      else if (window && paged) launch256(fa::decode_split_lsink_kernel<T, D, true, true>, grid, st, la);
-      else if (window) launch256(fa::decode_split_lsink_kernel<T, D, false, true>, grid, st, la);
-      else if (paged) launch256(fa::decode_split_lsink_kernel<T, D, true, false>, grid, st, la);
-      else launch256(fa::decode_split_lsink_kernel<T, D, false, false>, grid, st, la);
-    }
-  } else if (f == DECODE) {
-    if (a.sink) {
-      const fa::SinkArgs sa = with_sink<fa::SinkArgs, fa::DecodeArgs>(a);
-      if (paged) launch256(fa::decode_split_sink_kernel<T, D, true>, grid, st, sa);
-      else launch256(fa::decode_split_sink_kernel<T, D, false>, grid, st, sa);
-    } else if (window && paged) launch256(fa::decode_split_kernel<T, D, true, true, true>, grid, st, a);
-    else if (window) launch256(fa::decode_split_kernel<T, D, true, false, true>, grid, st, a);
-    else if (paged) launch256(fa::decode_split_kernel<T, D, true, true>, grid, st, a);
-    else if (a.G > 1) launch256(fa::decode_split_kernel<T, D, true>, grid, st, a);
-    else launch256(fa::decode_split_kernel<T, D, false>, grid, st, a);
-  } else if (f == EXTEND) {
-    if (a.sink) {
-      const fa::SinkArgs sa = with_sink<fa::SinkArgs, fa::DecodeArgs>(a);
-      if (paged) launch256(fa::extend_split_sink_kernel<T, D, true, false>, grid, st, sa);
-      else launch256(fa::extend_split_sink_kernel<T, D, false, false>, grid, st, sa);
-    } else if (window && paged) launch256(fa::extend_split_kernel<T, D, true, false, true>, grid, st, a);
-    else if (window) launch256(fa::extend_split_kernel<T, D, false, false, true>, grid, st, a);
-    else if (paged) launch256(fa::extend_split_kernel<T, D, true>, grid, st, a);
-    else launch256(fa::extend_split_kernel<T, D>, grid, st, a);
-  } else {
-    if (a.sink) {
-      const fa::RaggedSinkArgs sa = with_sink<fa::RaggedSinkArgs, fa::RaggedArgs>(a);
-      if (paged) launch256(fa::extend_split_sink_kernel<T, D, true, true>, grid, st, sa);
-      else launch256(fa::extend_split_sink_kernel<T, D, false, true>, grid, st, sa);
-    } else if (window && paged) launch256(fa::extend_split_kernel<T, D, true, true, true>, grid, st, a);
-    else if (window) launch256(fa::extend_split_kernel<T, D, false, true, true>, grid, st, a);
-    else if (paged) launch256(fa::extend_split_kernel<T, D, true, true>, grid, st, a);
-    else launch256(fa::extend_split_kernel<T, D, false, true>, grid, st, a);
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_err(what, e);
-  if (a.nsplit > 1) {
-    const long rows = (f == RAGGED ? 1L : a.nseq) * a.H * a.Nq;   // one workgroup per output row
-    // (softcap: the partials' m are capped logits already, so the EXISTING combine instances run with tau = 1; the softmax scale
-    // left there would weigh the splits wrongly)
-    SplitArgs one = a;
-    one.tau = 1.0f;
-    const SplitArgs& ca = a.softcap > 0.f ? one : a;
-    if (a.f8.on) launch256(fa::decode_combine_kernel<D, false, true>, rows, st, with_scales(a));
-    else if (a.sink_logits && f == RAGGED)   // (the logits: the lsink build, which adds the sink column behind its reduction)
-      launch256(fa::decode_combine_lsink_kernel<D, true>, rows, st, with_lsink<fa::RaggedLsinkArgs, fa::RaggedArgs>(a));
-    else if (a.sink_logits) launch256(fa::decode_combine_lsink_kernel<D, false>, rows, st, with_lsink<fa::LsinkArgs, fa::DecodeArgs>(a));
-    else if (f == RAGGED) launch256(fa::decode_combine_kernel<D, true>, rows, st, ca);
-    else launch256(fa::decode_combine_kernel<D>, rows, st, ca);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_err(a.f8.on ? "decode_combine_kernel (fp8) launch" : FAMILIES[f].combine_launch, e);
+    if (e != hipSuccess) return hip_err(s.launch.what, e);
   }
   return FA_OK;
-}
-
-// The launches of a checked head-dim-256 attention (decode or extend, bf16): the build of fa_decode_d256.h that the call's cache
-// (slab / paged), window and cap select, and decode_combine_d256_kernel if nsplit > 1, with tau = 1 behind a cap as above.
-template <bool PAGED, bool WINDOW, bool SOFTCAP> void launch_d256_build(const fa::D256Args& a, Family f, long grid, hipStream_t st) {
-  if (f == EXTEND) hipLaunchKernelGGL((fa::extend_split_d256_kernel<PAGED, WINDOW, SOFTCAP>), dim3((unsigned)grid), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((fa::decode_split_d256_kernel<PAGED, WINDOW, SOFTCAP>), dim3((unsigned)grid), dim3(512), 0, st, a);
-}
-
-int launch_d256(const SplitArgs& a, Family f, hipStream_t st) {
-  const fa::D256Args da = with_softcap<fa::SoftcapArgs, fa::DecodeArgs>(a);
-  const long grid = split_grid(a.items, a.nqb);
-  switch ((a.table != nullptr) * 4 + (a.window != 0) * 2 + (a.softcap > 0.f)) {
-    case 0: launch_d256_build<false, false, false>(da, f, grid, st); break;
-    case 1: launch_d256_build<false, false, true>(da, f, grid, st); break;
-    case 2: launch_d256_build<false, true, false>(da, f, grid, st); break;
-    case 3: launch_d256_build<false, true, true>(da, f, grid, st); break;
-    case 4: launch_d256_build<true, false, false>(da, f, grid, st); break;
-    case 5: launch_d256_build<true, false, true>(da, f, grid, st); break;
-    case 6: launch_d256_build<true, true, false>(da, f, grid, st); break;
-    default: launch_d256_build<true, true, true>(da, f, grid, st); break;
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_err(f == EXTEND ? "extend_split_d256_kernel launch" : "decode_split_d256_kernel launch", e);
-  if (a.nsplit > 1) {
-    fa::DecodeArgs ca = a;
-    if (a.softcap > 0.f) ca.tau = 1.0f;
-    launch256(fa::decode_combine_d256_kernel<false>, (long)a.nseq * a.H * a.Nq, st, ca);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_err("decode_combine_d256_kernel launch", e);
-  }
-  return FA_OK;
-}
-
-template <typename T> int launch_split_d(const SplitArgs& a, Family f, int d, hipStream_t st) {
-  switch (d) {
-    case 32: return launch_split<T, 32>(a, f, st);
-    case 64: return launch_split<T, 64>(a, f, st);
-    default: return launch_split<T, 128>(a, f, st);
-  }
 }
 
 // The launches of a checked attention under the policy its check returned.
@@ -618,8 +602,10 @@ int run_attend(const KvCall& c, const Policy& p) {
   a.f8 = c.f8;
   a.softcap = c.softcap;
   a.sink_logits = c.sink_logits;
-  if (c.d256) return launch_d256(a, c.family, c.stream);
-  return c.dtype == FA_DTYPE_BF16 ? launch_split_d<fa::bf16_t>(a, c.family, c.d, c.stream) : launch_split_d<float>(a, c.family, c.d, c.stream);
+  const Feature x = c.f8.on ? FP8 : c.softcap > 0.f ? SOFTCAP : c.sink_logits ? LSINK : a.sink ? SINK : PLAIN;   // (the order of precedence)
+  const Launches l = select(c.family, c.dtype, c.d, a.table != nullptr, a.window != 0, x, a.G > 1, p.nsplit > 1);
+  if (!l.split.fn) return set_err(FA_ERR_BAD_ARG, "no build of the split kernels serves this call");
+  return launch(l, a, c.stream);
 }
 
 template <typename T, int E> int launch_append(fa::RaggedAppendArgs a, int d, hipStream_t st) {
@@ -802,6 +788,21 @@ int rope_append_call(KvCall c, const Rope& r) {
   if (c.dtype == FA_DTYPE_BF16)
     return vec ? launch_rope_append<fa::bf16_t, 8, false>(a, il, c.stream) : launch_rope_append<fa::bf16_t, 1, false>(a, il, c.stream);
   return vec ? launch_rope_append<float, 4, false>(a, il, c.stream) : launch_rope_append<float, 1, false>(a, il, c.stream);
+}
+
+// The general form of the later entry points (_window.h, _sink.h, _softcap.h, _lsink.h, _fp8.h, _d256.h), as a call: k_new / v_new both
+// null: attend only; block_table null: slabs of Ncap rows, otherwise the pool's geometry stands for Ncap; cu: the ragged family's
+// cu_seqlens_q.  Each entry point adds the one argument it has beside these.
+KvCall general(Family f, const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
+               const int* cu, const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv, int Nq, int Ncap,
+               int num_pages, int page_size, int max_pages, int d_new, int d, int layout, float softmax_scale, int causal, int dtype,
+               void* stream) {
+  KvCall c(f);
+  c.attention(q, out, lse, workspace, softmax_scale, causal).cache(k_cache, v_cache, cache_seqlens, Ncap);
+  c.pool_or_slabs(block_table, num_pages, page_size, max_pages).heads(B, H, Hkv, Nq, d).format(layout, dtype, stream);
+  if (k_new || v_new) c.new_tokens(k_new, v_new, d_new);
+  c.cu = cu;
+  return c;
 }
 
 }  // namespace
@@ -1061,35 +1062,38 @@ int fa_mi355x_fwd_decode_window(const void* q, const void* k_new, const void* v_
                                 const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv, int Nq, int Ncap,
                                 int num_pages, int page_size, int max_pages, int d_new, int d, int layout, float softmax_scale, int causal,
                                 int window, int dtype, void* stream) {
-  return fa_mi355x_fwd_decode_sink(q, k_new, v_new, k_cache, v_cache, out, lse, cache_seqlens, block_table, workspace, B, H, Hkv, Nq, Ncap,
-                                   num_pages, page_size, max_pages, d_new, d, layout, softmax_scale, causal, window, 0, dtype, stream);
+  KvCall c = general(DECODE, q, k_new, v_new, k_cache, v_cache, out, lse, nullptr, cache_seqlens, block_table, workspace, B, H, Hkv, Nq, Ncap,
+                     num_pages, page_size, max_pages, d_new, d, layout, softmax_scale, causal, dtype, stream);
+  c.window = window;
+  return run(c);
 }
 
 int fa_mi355x_fwd_extend_window(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
                                 const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv, int Nq, int Ncap,
                                 int num_pages, int page_size, int max_pages, int d_new, int d, int layout, float softmax_scale, int causal,
                                 int window, int dtype, void* stream) {
-  return fa_mi355x_fwd_extend_sink(q, k_new, v_new, k_cache, v_cache, out, lse, cache_seqlens, block_table, workspace, B, H, Hkv, Nq, Ncap,
-                                   num_pages, page_size, max_pages, d_new, d, layout, softmax_scale, causal, window, 0, dtype, stream);
+  KvCall c = general(EXTEND, q, k_new, v_new, k_cache, v_cache, out, lse, nullptr, cache_seqlens, block_table, workspace, B, H, Hkv, Nq, Ncap,
+                     num_pages, page_size, max_pages, d_new, d, layout, softmax_scale, causal, dtype, stream);
+  c.window = window;
+  return run(c);
 }
 
 int fa_mi355x_fwd_ragged_window(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
                                 const int* cu_seqlens_q, const int* cache_seqlens, const int* block_table, void* workspace, int B, int H,
                                 int Hkv, int T, int Ncap, int num_pages, int page_size, int max_pages, int d_new, int d, int layout,
                                 float softmax_scale, int causal, int window, int dtype, void* stream) {
-  return fa_mi355x_fwd_ragged_sink(q, k_new, v_new, k_cache, v_cache, out, lse, cu_seqlens_q, cache_seqlens, block_table, workspace, B, H,
-                                   Hkv, T, Ncap, num_pages, page_size, max_pages, d_new, d, layout, softmax_scale, causal, window, 0, dtype,
-                                   stream);
+  KvCall c = general(RAGGED, q, k_new, v_new, k_cache, v_cache, out, lse, cu_seqlens_q, cache_seqlens, block_table, workspace, B, H, Hkv, T, Ncap,
+                     num_pages, page_size, max_pages, d_new, d, layout, softmax_scale, causal, dtype, stream);
+  c.window = window;
+  return run(c);
 }
 
 int fa_mi355x_fwd_decode_sink(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, float* out, float* lse,
                               const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv, int Nq, int Ncap,
                               int num_pages, int page_size, int max_pages, int d_new, int d, int layout, float softmax_scale, int causal,
                               int window, int sink, int dtype, void* stream) {
-  KvCall c(DECODE);
-  c.attention(q, out, lse, workspace, softmax_scale, causal).cache(k_cache, v_cache, cache_seqlens, Ncap);
-  c.pool_or_slabs(block_table, num_pages, page_size, max_pages).heads(B, H, Hkv, Nq, d).format(layout, dtype, stream);
-  if (k_new || v_new) c.new_tokens(k_new, v_new, d_new);
+  KvCall c = general(DECODE, q, k_new, v_new, k_cache, v_cache, out, lse, nullptr, cache_seqlens, block_table, workspace, B, H, Hkv, Nq, Ncap,
+                     num_pages, page_size, max_pages, d_new, d, layout, softmax_scale, causal, dtype, stream);
   c.window = window, c.sink = sink;
   return run(c);
 }
@@ -1098,10 +1102,8 @@ int fa_mi355x_fwd_extend_sink(const void* q, const void* k_new, const void* v_ne
                               const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv, int Nq, int Ncap,
                               int num_pages, int page_size, int max_pages, int d_new, int d, int layout, float softmax_scale, int causal,
                               int window, int sink, int dtype, void* stream) {
-  KvCall c(EXTEND);
-  c.attention(q, out, lse, workspace, softmax_scale, causal).cache(k_cache, v_cache, cache_seqlens, Ncap);
-  c.pool_or_slabs(block_table, num_pages, page_size, max_pages).heads(B, H, Hkv, Nq, d).format(layout, dtype, stream);
-  if (k_new || v_new) c.new_tokens(k_new, v_new, d_new);
+  KvCall c = general(EXTEND, q, k_new, v_new, k_cache, v_cache, out, lse, nullptr, cache_seqlens, block_table, workspace, B, H, Hkv, Nq, Ncap,
+                     num_pages, page_size, max_pages, d_new, d, layout, softmax_scale, causal, dtype, stream);
   c.window = window, c.sink = sink;
   return run(c);
 }
@@ -1110,11 +1112,8 @@ int fa_mi355x_fwd_ragged_sink(const void* q, const void* k_new, const void* v_ne
                               const int* cu_seqlens_q, const int* cache_seqlens, const int* block_table, void* workspace, int B, int H,
                               int Hkv, int T, int Ncap, int num_pages, int page_size, int max_pages, int d_new, int d, int layout,
                               float softmax_scale, int causal, int window, int sink, int dtype, void* stream) {
-  KvCall c(RAGGED);
-  c.attention(q, out, lse, workspace, softmax_scale, causal).cache(k_cache, v_cache, cache_seqlens, Ncap);
-  c.pool_or_slabs(block_table, num_pages, page_size, max_pages).heads(B, H, Hkv, T, d).format(layout, dtype, stream);
-  if (k_new || v_new) c.new_tokens(k_new, v_new, d_new);
-  c.cu = cu_seqlens_q;
+  KvCall c = general(RAGGED, q, k_new, v_new, k_cache, v_cache, out, lse, cu_seqlens_q, cache_seqlens, block_table, workspace, B, H, Hkv, T, Ncap,
+                     num_pages, page_size, max_pages, d_new, d, layout, softmax_scale, causal, dtype, stream);
   c.window = window, c.sink = sink;
   return run(c);
 }
@@ -1124,10 +1123,8 @@ int fa_mi355x_fwd_decode_softcap(const void* q, const void* k_new, const void* v
                                  const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv, int Nq, int Ncap,
                                  int num_pages, int page_size, int max_pages, int d_new, int d, int layout, float softmax_scale, int causal,
                                  int window, float softcap, int dtype, void* stream) {
-  KvCall c(DECODE);
-  c.attention(q, out, lse, workspace, softmax_scale, causal).cache(k_cache, v_cache, cache_seqlens, Ncap);
-  c.pool_or_slabs(block_table, num_pages, page_size, max_pages).heads(B, H, Hkv, Nq, d).format(layout, dtype, stream);
-  if (k_new || v_new) c.new_tokens(k_new, v_new, d_new);
+  KvCall c = general(DECODE, q, k_new, v_new, k_cache, v_cache, out, lse, nullptr, cache_seqlens, block_table, workspace, B, H, Hkv, Nq, Ncap,
+                     num_pages, page_size, max_pages, d_new, d, layout, softmax_scale, causal, dtype, stream);
   c.window = window, c.softcap = softcap;
   return run(c);
 }
@@ -1136,10 +1133,8 @@ int fa_mi355x_fwd_extend_softcap(const void* q, const void* k_new, const void* v
                                  const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv, int Nq, int Ncap,
                                  int num_pages, int page_size, int max_pages, int d_new, int d, int layout, float softmax_scale, int causal,
                                  int window, float softcap, int dtype, void* stream) {
-  KvCall c(EXTEND);
-  c.attention(q, out, lse, workspace, softmax_scale, causal).cache(k_cache, v_cache, cache_seqlens, Ncap);
-  c.pool_or_slabs(block_table, num_pages, page_size, max_pages).heads(B, H, Hkv, Nq, d).format(layout, dtype, stream);
-  if (k_new || v_new) c.new_tokens(k_new, v_new, d_new);
+  KvCall c = general(EXTEND, q, k_new, v_new, k_cache, v_cache, out, lse, nullptr, cache_seqlens, block_table, workspace, B, H, Hkv, Nq, Ncap,
+                     num_pages, page_size, max_pages, d_new, d, layout, softmax_scale, causal, dtype, stream);
   c.window = window, c.softcap = softcap;
   return run(c);
 }
@@ -1148,11 +1143,8 @@ int fa_mi355x_fwd_ragged_softcap(const void* q, const void* k_new, const void* v
                                  const int* cu_seqlens_q, const int* cache_seqlens, const int* block_table, void* workspace, int B, int H,
                                  int Hkv, int T, int Ncap, int num_pages, int page_size, int max_pages, int d_new, int d, int layout,
                                  float softmax_scale, int causal, int window, float softcap, int dtype, void* stream) {
-  KvCall c(RAGGED);
-  c.attention(q, out, lse, workspace, softmax_scale, causal).cache(k_cache, v_cache, cache_seqlens, Ncap);
-  c.pool_or_slabs(block_table, num_pages, page_size, max_pages).heads(B, H, Hkv, T, d).format(layout, dtype, stream);
-  if (k_new || v_new) c.new_tokens(k_new, v_new, d_new);
-  c.cu = cu_seqlens_q;
+  KvCall c = general(RAGGED, q, k_new, v_new, k_cache, v_cache, out, lse, cu_seqlens_q, cache_seqlens, block_table, workspace, B, H, Hkv, T, Ncap,
+                     num_pages, page_size, max_pages, d_new, d, layout, softmax_scale, causal, dtype, stream);
   c.window = window, c.softcap = softcap;
   return run(c);
 }
@@ -1162,10 +1154,8 @@ int fa_mi355x_fwd_decode_lsink(const void* q, const void* k_new, const void* v_n
                                const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv, int Nq, int Ncap,
                                int num_pages, int page_size, int max_pages, int d_new, int d, int layout, float softmax_scale, int causal,
                                int window, const float* sink_logits, int dtype, void* stream) {
-  KvCall c(DECODE);
-  c.attention(q, out, lse, workspace, softmax_scale, causal).cache(k_cache, v_cache, cache_seqlens, Ncap);
-  c.pool_or_slabs(block_table, num_pages, page_size, max_pages).heads(B, H, Hkv, Nq, d).format(layout, dtype, stream);
-  if (k_new || v_new) c.new_tokens(k_new, v_new, d_new);
+  KvCall c = general(DECODE, q, k_new, v_new, k_cache, v_cache, out, lse, nullptr, cache_seqlens, block_table, workspace, B, H, Hkv, Nq, Ncap,
+                     num_pages, page_size, max_pages, d_new, d, layout, softmax_scale, causal, dtype, stream);
   c.window = window, c.sink_logits = sink_logits;
   return run(c);
 }
@@ -1174,10 +1164,8 @@ int fa_mi355x_fwd_extend_lsink(const void* q, const void* k_new, const void* v_n
                                const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv, int Nq, int Ncap,
                                int num_pages, int page_size, int max_pages, int d_new, int d, int layout, float softmax_scale, int causal,
                                int window, const float* sink_logits, int dtype, void* stream) {
-  KvCall c(EXTEND);
-  c.attention(q, out, lse, workspace, softmax_scale, causal).cache(k_cache, v_cache, cache_seqlens, Ncap);
-  c.pool_or_slabs(block_table, num_pages, page_size, max_pages).heads(B, H, Hkv, Nq, d).format(layout, dtype, stream);
-  if (k_new || v_new) c.new_tokens(k_new, v_new, d_new);
+  KvCall c = general(EXTEND, q, k_new, v_new, k_cache, v_cache, out, lse, nullptr, cache_seqlens, block_table, workspace, B, H, Hkv, Nq, Ncap,
+                     num_pages, page_size, max_pages, d_new, d, layout, softmax_scale, causal, dtype, stream);
   c.window = window, c.sink_logits = sink_logits;
   return run(c);
 }
@@ -1186,11 +1174,8 @@ int fa_mi355x_fwd_ragged_lsink(const void* q, const void* k_new, const void* v_n
                                const int* cu_seqlens_q, const int* cache_seqlens, const int* block_table, void* workspace, int B, int H,
                                int Hkv, int T, int Ncap, int num_pages, int page_size, int max_pages, int d_new, int d, int layout,
                                float softmax_scale, int causal, int window, const float* sink_logits, int dtype, void* stream) {
-  KvCall c(RAGGED);
-  c.attention(q, out, lse, workspace, softmax_scale, causal).cache(k_cache, v_cache, cache_seqlens, Ncap);
-  c.pool_or_slabs(block_table, num_pages, page_size, max_pages).heads(B, H, Hkv, T, d).format(layout, dtype, stream);
-  if (k_new || v_new) c.new_tokens(k_new, v_new, d_new);
-  c.cu = cu_seqlens_q;
+  KvCall c = general(RAGGED, q, k_new, v_new, k_cache, v_cache, out, lse, cu_seqlens_q, cache_seqlens, block_table, workspace, B, H, Hkv, T, Ncap,
+                     num_pages, page_size, max_pages, d_new, d, layout, softmax_scale, causal, dtype, stream);
   c.window = window, c.sink_logits = sink_logits;
   return run(c);
 }
@@ -1199,10 +1184,8 @@ int fa_mi355x_fwd_decode_fp8(const void* q, const void* k_new, const void* v_new
                              const float* v_scale, float* out, float* lse, const int* cache_seqlens, const int* block_table, void* workspace,
                              int B, int H, int Hkv, int Nq, int Ncap, int num_pages, int page_size, int max_pages, int d_new, int d,
                              int layout, float softmax_scale, int causal, int dtype, void* stream) {
-  KvCall c(DECODE);
-  c.attention(q, out, lse, workspace, softmax_scale, causal).cache(k_cache, v_cache, cache_seqlens, Ncap);
-  c.pool_or_slabs(block_table, num_pages, page_size, max_pages).heads(B, H, Hkv, Nq, d).format(layout, dtype, stream);
-  if (k_new || v_new) c.new_tokens(k_new, v_new, d_new);
+  KvCall c = general(DECODE, q, k_new, v_new, k_cache, v_cache, out, lse, nullptr, cache_seqlens, block_table, workspace, B, H, Hkv, Nq, Ncap,
+                     num_pages, page_size, max_pages, d_new, d, layout, softmax_scale, causal, dtype, stream);
   c.f8 = {true, k_scale, v_scale};
   return run(c);
 }
@@ -1211,10 +1194,8 @@ int fa_mi355x_fwd_extend_fp8(const void* q, const void* k_new, const void* v_new
                              const float* v_scale, float* out, float* lse, const int* cache_seqlens, const int* block_table, void* workspace,
                              int B, int H, int Hkv, int Nq, int Ncap, int num_pages, int page_size, int max_pages, int d_new, int d,
                              int layout, float softmax_scale, int causal, int dtype, void* stream) {
-  KvCall c(EXTEND);
-  c.attention(q, out, lse, workspace, softmax_scale, causal).cache(k_cache, v_cache, cache_seqlens, Ncap);
-  c.pool_or_slabs(block_table, num_pages, page_size, max_pages).heads(B, H, Hkv, Nq, d).format(layout, dtype, stream);
-  if (k_new || v_new) c.new_tokens(k_new, v_new, d_new);
+  KvCall c = general(EXTEND, q, k_new, v_new, k_cache, v_cache, out, lse, nullptr, cache_seqlens, block_table, workspace, B, H, Hkv, Nq, Ncap,
+                     num_pages, page_size, max_pages, d_new, d, layout, softmax_scale, causal, dtype, stream);
   c.f8 = {true, k_scale, v_scale};
   return run(c);
 }
@@ -1235,10 +1216,8 @@ int fa_mi355x_fwd_decode_d256(const void* q, const void* k_new, const void* v_ne
                               const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv, int Nq, int Ncap,
                               int num_pages, int page_size, int max_pages, int d_new, int d, int layout, float softmax_scale, int causal,
                               int window, float softcap, int dtype, void* stream) {
-  KvCall c(DECODE);
-  c.attention(q, out, lse, workspace, softmax_scale, causal).cache(k_cache, v_cache, cache_seqlens, Ncap);
-  c.pool_or_slabs(block_table, num_pages, page_size, max_pages).heads(B, H, Hkv, Nq, d).format(layout, dtype, stream);
-  if (k_new || v_new) c.new_tokens(k_new, v_new, d_new);
+  KvCall c = general(DECODE, q, k_new, v_new, k_cache, v_cache, out, lse, nullptr, cache_seqlens, block_table, workspace, B, H, Hkv, Nq, Ncap,
+                     num_pages, page_size, max_pages, d_new, d, layout, softmax_scale, causal, dtype, stream);
   c.window = window, c.softcap = softcap, c.d256 = true;
   return run(c);
 }
@@ -1247,10 +1226,8 @@ int fa_mi355x_fwd_extend_d256(const void* q, const void* k_new, const void* v_ne
                               const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Hkv, int Nq, int Ncap,
                               int num_pages, int page_size, int max_pages, int d_new, int d, int layout, float softmax_scale, int causal,
                               int window, float softcap, int dtype, void* stream) {
-  KvCall c(EXTEND);
-  c.attention(q, out, lse, workspace, softmax_scale, causal).cache(k_cache, v_cache, cache_seqlens, Ncap);
-  c.pool_or_slabs(block_table, num_pages, page_size, max_pages).heads(B, H, Hkv, Nq, d).format(layout, dtype, stream);
-  if (k_new || v_new) c.new_tokens(k_new, v_new, d_new);
+  KvCall c = general(EXTEND, q, k_new, v_new, k_cache, v_cache, out, lse, nullptr, cache_seqlens, block_table, workspace, B, H, Hkv, Nq, Ncap,
+                     num_pages, page_size, max_pages, d_new, d, layout, softmax_scale, causal, dtype, stream);
   c.window = window, c.softcap = softcap, c.d256 = true;
   return run(c);
 }
