@@ -31,6 +31,9 @@ kernel_lib fa_bidir  _bidir      # bidirectional packed attention, cu_seqlens fo
 kernel_lib fa_prefix _prefix     # causal packed attention under the same two arrays, a cached prefix (include/flash_attn_mi355x_prefix.h)
 kernel_lib fa_local  _local      # two-sided sliding window (a band) under the same two arrays (include/flash_attn_mi355x_local.h)
 kernel_lib fa_lsink  _lsink      # learned sink logits in training: the forward and the logit gradient (include/flash_attn_mi355x_lsink.h)
+# multi-head latent attention decode on a latent KV cache (include/flash_attn_mi355x_mla.h).  The whole library is built without packed
+# fp32 instructions, a target feature (the host pass does not know it and says that it ignores it).
+( FLAGS+=(-Xclang -target-feature -Xclang -packed-fp32-ops); kernel_lib fa_mla _mla )
 
 shim() {  # name variant FW|BW
   "$HIPCC" -O2 -fPIC -shared -x c++ "$SRC/fa_shim.cpp" -DFA_SHIM_VARIANT="$2" -DFA_SHIM_"$3" \

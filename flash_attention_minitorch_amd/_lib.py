@@ -541,3 +541,26 @@ def local() -> ctypes.CDLL:
 def local_check(status: int) -> None:
     if status != FA_OK:
         _raise(status, local(), "fa_mi355x_local_last_error", "flash_attn_mi355x_local")
+
+
+# the same for include/flash_attn_mi355x_mla.h: libflash_attn_mi355x_mla.so, multi-head latent attention (DeepSeek MLA) decode on a
+# latent KV cache of 576-wide rows: the fused append-and-attend call, the append, the two size queries (tests/test_mla_cpu.py)
+MLA_ABI = {
+    "fa_mi355x_fwd_decode_mla": (_i, [_vp] * 8 + [_i] * 7 + [_f, _i, _vp]),
+    "fa_mi355x_mla_append": (_i, [_vp] * 4 + [_i] * 6 + [_vp]),
+    "fa_mi355x_decode_mla_splits": (_i, [_i] * 4),
+    "fa_mi355x_decode_mla_workspace_bytes": (_sz, [_i] * 4),
+    "fa_mi355x_mla_last_error": (_s, []),
+}
+MLA_NAME = "libflash_attn_mi355x_mla.so"
+MLA_D_QK, MLA_D_V = 576, 512   # columns of a cache row (and of q); the leading columns that are the value (and out's columns)
+
+
+def mla() -> ctypes.CDLL:
+    """libflash_attn_mi355x_mla.so (include/flash_attn_mi355x_mla.h) with argtypes set."""
+    return _typed(MLA_NAME, MLA_ABI)
+
+
+def mla_check(status: int) -> None:
+    if status != FA_OK:
+        _raise(status, mla(), "fa_mi355x_mla_last_error", "flash_attn_mi355x_mla")

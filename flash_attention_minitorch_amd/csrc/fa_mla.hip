@@ -1,0 +1,200 @@
+// C ABI of libflash_attn_mi355x_mla.so (include/flash_attn_mi355x_mla.h): multi-head latent attention decode on a latent KV cache.
+// The kernels are fa_mla.h's.  Every entry point fills one MlaCall, check() answers every bad argument before any HIP call, and the
+// split policy is stated once (policy()): the two size queries and the launch answer from it.
+#include "../../include/flash_attn_mi355x_mla.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+
+#include "fa_mla.h"
+
+namespace {
+
+thread_local char g_err[512] = "";
+
+int set_err(int code, const char* what) {
+  snprintf(g_err, sizeof(g_err), "%s", what);
+  return code;
+}
+
+int hip_err(const char* what, hipError_t e) {
+  snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
+  return FA_ERR_HIP;
+}
+
+struct MlaCall {
+  const void* q = nullptr;
+  const void* kv_new = nullptr;
+  void* kv_cache = nullptr;
+  float *out = nullptr, *lse = nullptr;
+  const int *seqlens = nullptr, *table = nullptr;
+  void* workspace = nullptr;
+  int B = 0, H = 1, Nq = 0, Ncap = 0, num_pages = 0, page_size = 0, max_pages = 0;
+  float softmax_scale = 0.f;
+  int causal = 0;
+  bool attend = false, append = false;
+  hipStream_t stream = nullptr;
+};
+
+// Split policy: the decode library's rule (fa_decode.hip: policy) with one cache head and the 64-row block.  A workgroup holds a
+// CU alone (88 KB of LDS, the whole register file), so the aim is two rounds of (batch, chunk, row block) workgroups on the 256 CUs:
+// the second round levels sequences of unequal length.  Chunks are whole 128-key super tiles (a page is a whole number of them) and
+// at least 256 keys.  The chip size is assumed, not queried: the split count is a function of the arguments alone.
+constexpr int MLA_CUS = 256, MLA_ROUNDS = 2, MLA_SUPER = 128, MLA_MIN_CHUNK = 256;
+static_assert(FA_PAGE_ROWS % MLA_SUPER == 0 && MLA_SUPER % fa::MLA_TILE == 0, "a page is whole super tiles, a super tile whole tiles");
+
+struct Policy {
+  long nqb;     // 64-row blocks of the H * Nq rows
+  int chunk, nsplit;
+  long items;   // (batch element, split) pairs
+  size_t workspace_bytes;
+};
+
+Policy policy(int B, int H, int Nq, int Ncap) {
+  Policy p;
+  p.nqb = ((long)H * Nq + fa::MLA_BLOCK - 1) / fa::MLA_BLOCK;
+  const long groups = (long)B * p.nqb;
+  const long want = std::max(1L, (MLA_CUS * MLA_ROUNDS + groups - 1) / groups);
+  const long per = (Ncap + want - 1) / want;
+  p.chunk = (int)std::max((long)MLA_MIN_CHUNK, (per + MLA_SUPER - 1) / MLA_SUPER * MLA_SUPER);
+  p.nsplit = (int)(((long)Ncap + p.chunk - 1) / p.chunk);
+  p.items = (long)B * p.nsplit;
+  p.workspace_bytes = p.nsplit == 1 ? 0 : (size_t)B * H * p.nsplit * Nq * (size_t)(fa::MLA_DV + 2) * sizeof(float);
+  return p;
+}
+
+Policy query(int B, int H, int Nq, int Ncap) { return B > 0 && H > 0 && Nq > 0 && Ncap > 0 ? policy(B, H, Nq, Ncap) : Policy{}; }
+
+long split_grid(long items, long nqb) { return (items + 7) / 8 * 8 * nqb; }
+
+bool misaligned(const void* p) { return (uintptr_t)p % 16 != 0; }
+
+// Every check of a call, in one order, before any HIP call.  A paged call's Ncap becomes max_pages * page_size.
+int check(MlaCall& c, Policy* out) {
+  g_err[0] = 0;
+  if (c.B <= 0 || c.H <= 0 || c.Nq <= 0) return set_err(FA_ERR_BAD_ARG, "B, H and Nq must be positive");
+  if (c.Nq > FA_DECODE_MAX_NQ)
+    return set_err(FA_ERR_BAD_ARG, "Nq > 128 is prefill: a prompt is prefilled un-absorbed, through the forward entry points");
+  if (c.table) {
+    if (c.num_pages <= 0 || c.page_size <= 0 || c.max_pages <= 0)
+      return set_err(FA_ERR_BAD_ARG, "num_pages, page_size and max_pages must be positive");
+    if (c.page_size % FA_PAGE_ROWS != 0) {
+      snprintf(g_err, sizeof(g_err), "page_size = %d must be a multiple of %d rows", c.page_size, FA_PAGE_ROWS);
+      return FA_ERR_BAD_ARG;
+    }
+    if ((long)c.max_pages * c.page_size + MLA_SUPER > 0x7fffffffL)
+      return set_err(FA_ERR_BAD_ARG, "max_pages * page_size (the logical capacity) must fit an int");
+    if ((long)c.page_size * fa::MLA_ROW_BYTES >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "one page of the pool must stay under 2 GiB");
+    c.Ncap = c.max_pages * c.page_size;
+  } else {
+    if (c.Ncap <= 0) return set_err(FA_ERR_BAD_ARG, "Ncap must be positive");
+    // (a buffer load's row offset is a 32-bit byte count: a slab, plus a tile of rows past its end)
+    if (((long)c.Ncap + fa::MLA_TILE) * fa::MLA_ROW_BYTES >= (1L << 31))
+      return set_err(FA_ERR_BAD_ARG, "one batch element of the cache must stay under 2 GiB");
+  }
+  if (!c.kv_cache) return set_err(FA_ERR_BAD_ARG, "null pointer argument: kv_cache");
+  if (c.append && !c.kv_new) return set_err(FA_ERR_BAD_ARG, "null pointer argument: kv_new");
+  if (misaligned(c.kv_cache) || misaligned(c.kv_new)) return set_err(FA_ERR_BAD_ARG, "kv_cache and kv_new must be 16-byte aligned");
+  if ((long)c.B * c.Nq * fa::MlaStager::CPR / 256 >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "too many new rows for one append launch");
+  if (!c.attend) return FA_OK;
+  if (!c.q || !c.out) return set_err(FA_ERR_BAD_ARG, "null pointer argument: q and out");
+  if (misaligned(c.q) || misaligned(c.out) || misaligned(c.workspace))
+    return set_err(FA_ERR_BAD_ARG, "q, out and the workspace must be 16-byte aligned");
+  if (!(c.softmax_scale > 0.f) || !std::isfinite(c.softmax_scale))
+    return set_err(FA_ERR_BAD_ARG, "softmax_scale must be positive and finite: it is required (576 is not the model's head dim)");
+  if ((long)c.H * c.Nq >= (1L << 25)) return set_err(FA_ERR_BAD_ARG, "H * Nq rows must stay under 2^25");
+  if ((long)c.Nq * c.H * fa::MLA_ROW_BYTES >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "one batch element of q must stay under 2 GiB");
+  const Policy p = policy(c.B, c.H, c.Nq, c.Ncap);
+  if (split_grid(p.items, p.nqb) >= (1L << 32) || p.items >= (1L << 31) || (long)c.B * c.H * c.Nq >= (1L << 32))
+    return set_err(FA_ERR_BAD_ARG, "too many workgroups for one launch: B * splits * row blocks and B * H * Nq must fit an unsigned int");
+  if (p.nsplit > 1 && !c.workspace)
+    return set_err(FA_ERR_BAD_ARG, "null workspace: this call needs fa_mi355x_decode_mla_workspace_bytes() bytes");
+  *out = p;
+  return FA_OK;
+}
+
+int launch_append(const MlaCall& c) {
+  fa::MlaAppendArgs a;
+  a.kv_new = c.kv_new;
+  a.kv = c.kv_cache;
+  a.seqlens = c.seqlens;
+  a.table = c.table;
+  a.lanes = (long)c.B * c.Nq * fa::MlaStager::CPR;
+  a.Nq = c.Nq, a.Ncap = c.Ncap, a.page_size = c.page_size, a.num_pages = c.num_pages, a.max_pages = c.max_pages;
+  hipLaunchKernelGGL(fa::mla_append_kernel, dim3((unsigned)((a.lanes + 255) / 256)), dim3(256), 0, c.stream, a);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? FA_OK : hip_err("mla_append_kernel launch", e);
+}
+
+int launch_attend(const MlaCall& c, const Policy& p) {
+  constexpr int D = fa::MLA_DQK, DV = fa::MLA_DV;
+  fa::DecodeArgs a{};
+  a.q = c.q, a.k = c.kv_cache, a.v = c.kv_cache;
+  a.out = c.out, a.lse = c.lse;
+  a.part_o = (float*)c.workspace;
+  a.part_ml = a.part_o ? a.part_o + (size_t)c.B * c.H * p.nsplit * c.Nq * DV : nullptr;
+  a.seqlens = c.seqlens;
+  a.H = c.H, a.Hkv = 1, a.G = c.H, a.Nq = c.Nq, a.Ncap = c.Ncap;
+  a.nsplit = p.nsplit, a.chunk = p.chunk, a.nqb = (int)p.nqb, a.items = (int)p.items;
+  a.inv_G = 1.0f / (float)c.H;
+  a.q_ld = c.H * D, a.q_hstride = D, a.q_bstride = (long)c.Nq * c.H * D;
+  a.kv_ld = D, a.kv_hstride = 0, a.kv_bstride = (long)c.Ncap * D;
+  a.causal = c.causal ? 1 : 0;
+  a.tau = c.softmax_scale;
+  a.table = c.table;
+  a.page_size = c.page_size, a.num_pages = c.num_pages, a.max_pages = c.max_pages;
+  a.page_stride = (long)c.page_size * D;
+  const unsigned grid = (unsigned)split_grid(p.items, p.nqb);
+  if (c.table) hipLaunchKernelGGL(fa::mla_decode_split_kernel<true>, dim3(grid), dim3(256), 0, c.stream, a);
+  else hipLaunchKernelGGL(fa::mla_decode_split_kernel<false>, dim3(grid), dim3(256), 0, c.stream, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_err("mla_decode_split_kernel launch", e);
+  if (p.nsplit == 1) return FA_OK;
+  // (the combine body addresses out through q's strides: out's stand in their place)
+  a.q_ld = c.H * DV, a.q_hstride = DV, a.q_bstride = (long)c.Nq * c.H * DV;
+  hipLaunchKernelGGL(fa::mla_decode_combine_kernel<false>, dim3((unsigned)((long)c.B * c.H * c.Nq)), dim3(256), 0, c.stream, a);
+  e = hipGetLastError();
+  return e == hipSuccess ? FA_OK : hip_err("mla_decode_combine_kernel launch", e);
+}
+
+int run(MlaCall& c) {
+  Policy p{};
+  if (int rc = check(c, &p)) return rc;
+  if (c.append)
+    if (int rc = launch_append(c)) return rc;
+  return c.attend ? launch_attend(c, p) : FA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* fa_mi355x_mla_last_error(void) { return g_err; }
+
+int fa_mi355x_fwd_decode_mla(const void* q, const void* kv_new, void* kv_cache, float* out, float* lse, const int* cache_seqlens,
+                             const int* block_table, void* workspace, int B, int H, int Nq, int Ncap, int num_pages, int page_size,
+                             int max_pages, float softmax_scale, int causal, void* stream) {
+  MlaCall c;
+  c.q = q, c.kv_new = kv_new, c.kv_cache = kv_cache, c.out = out, c.lse = lse, c.seqlens = cache_seqlens, c.table = block_table;
+  c.workspace = workspace, c.B = B, c.H = H, c.Nq = Nq, c.Ncap = Ncap, c.num_pages = num_pages, c.page_size = page_size;
+  c.max_pages = max_pages, c.softmax_scale = softmax_scale, c.causal = causal, c.stream = static_cast<hipStream_t>(stream);
+  c.attend = true, c.append = kv_new != nullptr;
+  return run(c);
+}
+
+int fa_mi355x_mla_append(const void* kv_new, void* kv_cache, const int* cache_seqlens, const int* block_table, int B, int Nq, int Ncap,
+                         int num_pages, int page_size, int max_pages, void* stream) {
+  MlaCall c;
+  c.kv_new = kv_new, c.kv_cache = kv_cache, c.seqlens = cache_seqlens, c.table = block_table, c.B = B, c.Nq = Nq, c.Ncap = Ncap;
+  c.num_pages = num_pages, c.page_size = page_size, c.max_pages = max_pages, c.stream = static_cast<hipStream_t>(stream);
+  c.append = true;
+  return run(c);
+}
+
+int fa_mi355x_decode_mla_splits(int B, int H, int Nq, int Ncap) { return query(B, H, Nq, Ncap).nsplit; }
+
+size_t fa_mi355x_decode_mla_workspace_bytes(int B, int H, int Nq, int Ncap) { return query(B, H, Nq, Ncap).workspace_bytes; }
+
+}  // extern "C"

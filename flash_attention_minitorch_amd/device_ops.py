@@ -2059,3 +2059,122 @@ def flash_attn_local(q, k, v, window, softmax_scale=None):
     window = _check_band(window)
     return _batched_two_array("flash_attn_local", lambda q, k, v, cu_q, cu_k, scale: flash_attn_varlen_local(
         q, k, v, cu_q, cu_k, window, scale), q, k, v, softmax_scale)
+
+
+# ---- multi-head latent attention (DeepSeek MLA) decode on a latent KV cache (include/flash_attn_mi355x_mla.h) --------------------
+# One cache row of 576 bf16 columns per token, shared by all heads: c_kv (512) then the rotated k_pe (64).  q carries the absorbed
+# q_nope . W_UK in columns 0..511 and the rotated q_pe in 512..575; out has the 512 latent columns.  Shapes and dtypes are checked by
+# name first, then devices and contiguity, then the library is called.
+_MLA_QK, _MLA_V = _lib.MLA_D_QK, _lib.MLA_D_V
+
+
+def _mla_tensor(t, name, shape_words, rank):
+    """A bf16 operand of rank ``rank`` whose rows are 576 wide."""
+    if not isinstance(t, torch.Tensor) or t.dim() != rank or t.shape[-1] != _MLA_QK:
+        raise ValueError(f"{name} must be {shape_words}: rows of {_MLA_QK} columns (c_kv 512 | k_pe 64); other latent widths are not built")
+    if t.dtype != torch.bfloat16:
+        raise TypeError(f"{name} must be bfloat16 (got {t.dtype}): the MLA kernels are built for bf16 alone")
+
+
+def _mla_resident(t, name, device):
+    _require_gpu(t, "flash_attn_decode_mla / mla_append")
+    if t.device != device or not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous and on the cache's device")
+
+
+def _mla_cache(kv_cache, block_table, B, max_pages=None):
+    """(Ncap, num_pages, page_size, max_pages) of a latent cache: a slab (B, Ncap, 576), or with ``block_table`` (or ``max_pages``, for
+    the size query) a pool (num_pages, page_size, 576) of logical capacity max_pages * page_size."""
+    _mla_tensor(kv_cache, "kv_cache", f"(B, Ncap, {_MLA_QK}), or a pool (num_pages, page_size, {_MLA_QK}) under a block_table", 3)
+    max_pages = _max_pages(block_table, max_pages)
+    if max_pages is None:
+        if kv_cache.shape[0] != B or kv_cache.shape[1] < 1:
+            raise ValueError(f"kv_cache must be (B, Ncap, {_MLA_QK}) with B = {B} and Ncap >= 1")
+        return int(kv_cache.shape[1]), 0, 0, 0
+    num_pages, page_size = int(kv_cache.shape[0]), int(kv_cache.shape[1])
+    if num_pages < 1 or page_size < 1 or page_size % _lib.FA_PAGE_ROWS:
+        raise ValueError(f"page_size = {page_size} must be a positive multiple of {_lib.FA_PAGE_ROWS} rows (and the pool hold a page)")
+    if block_table is not None:
+        _check_table(block_table, B, kv_cache.device)
+    return max_pages * page_size, num_pages, page_size, max_pages
+
+
+def _mla_new(kv_new, B, Nq=None):
+    """Nq of the new tokens' rows (B, Nq, 576), against the call's B (and its Nq, in the fused call)."""
+    _mla_tensor(kv_new, "kv_new", f"(B, Nq, {_MLA_QK})", 3)
+    if kv_new.shape[0] != B or (Nq is not None and kv_new.shape[1] != Nq):
+        raise ValueError(f"kv_new must be (B, Nq, {_MLA_QK}) with q's B and Nq")
+    if not 1 <= kv_new.shape[1] <= 128:
+        raise ValueError("Nq must be in 1 .. 128: a prompt is prefilled un-absorbed (flash_attn_gqa)")
+    return int(kv_new.shape[1])
+
+
+def _mla_q(q):
+    _mla_tensor(q, "q", f"(B, Nq, H, {_MLA_QK})", 4)
+    B, Nq, H = (int(x) for x in q.shape[:3])
+    if B < 1 or H < 1 or not 1 <= Nq <= 128:
+        raise ValueError("B and H must be positive and Nq in 1 .. 128: a prompt is prefilled un-absorbed (flash_attn_gqa)")
+    return B, Nq, H
+
+
+def mla_workspace(q, kv_cache, block_table=None, max_pages=None):
+    """Scratch for flash_attn_decode_mla on these shapes (fa_mi355x_decode_mla_workspace_bytes), or None when the call runs one split.
+    A pool without its table: pass ``max_pages``."""
+    B, Nq, H = _mla_q(q)
+    Ncap = _mla_cache(kv_cache, block_table, B, max_pages)[0]
+    nbytes = _lib.mla().fa_mi355x_decode_mla_workspace_bytes(B, H, Nq, Ncap)
+    return torch.empty(nbytes // 4, dtype=_F32, device=q.device) if nbytes else None
+
+
+def mla_append(kv_new, kv_cache, cache_seqlens, block_table=None):
+    """Append the new tokens' latent rows (fa_mi355x_mla_append): ``kv_new`` bf16 (B, Nq, 576); token i of sequence b goes to row
+    cache_seqlens[b] - Nq + i (the lengths COUNT the new tokens), slab or paged.  In place; returns kv_cache."""
+    if not isinstance(kv_new, torch.Tensor) or kv_new.dim() != 3:
+        raise ValueError(f"kv_new must be (B, Nq, {_MLA_QK})")
+    B = int(kv_new.shape[0])
+    Nq = _mla_new(kv_new, B)
+    Ncap, num_pages, page_size, max_pages = _mla_cache(kv_cache, block_table, B)
+    _mla_resident(kv_cache, "kv_cache", kv_cache.device)
+    _mla_resident(kv_new, "kv_new", kv_cache.device)
+    _check_seqlens(cache_seqlens, B, kv_cache.device)
+    _lib.mla_check(_lib.mla().fa_mi355x_mla_append(_ptr(kv_new), _ptr(kv_cache), _ptr(cache_seqlens), _ptr(block_table), B, Nq, Ncap,
+                                                   num_pages, page_size, max_pages, _stream_ptr()))
+    return kv_cache
+
+
+def flash_attn_decode_mla(q, kv_cache, cache_seqlens, softmax_scale, causal=True, kv_new=None, block_table=None, out=None, lse=None,
+                          workspace=None):
+    """One MLA decode step on a latent KV cache (fa_mi355x_fwd_decode_mla).  ``q`` bf16 (B, Nq, H, 576): the absorbed q_nope . W_UK in
+    columns 0..511, the rotated q_pe in 512..575.  ``kv_cache`` bf16 (B, Ncap, 576), or with ``block_table`` (B, max_pages) int32 a
+    pool (num_pages, page_size, 576).  ``cache_seqlens`` int32 (B,) on the device; under ``causal`` the queries are the last Nq
+    positions of each sequence.  ``kv_new`` bf16 (B, Nq, 576): appended first, in the same call (the lengths count it).
+    ``softmax_scale`` is REQUIRED: 576 is not the model's head dim (DeepSeek: (128 + 64) ** -0.5 times its YaRN factor).
+    Returns (out fp32 (B, Nq, H, 512), lse fp32 (B, H, Nq)); a sequence of length 0 gives out = 0 and lse = -inf.  No host
+    synchronisation: the call can be captured in a graph (``workspace``: mla_workspace(...), allocated per call when None)."""
+    B, Nq, H = _mla_q(q)
+    if not isinstance(softmax_scale, numbers.Real) or not softmax_scale > 0 or not math.isfinite(softmax_scale):
+        raise ValueError("softmax_scale is required, positive and finite: the absorbed width 576 is not the model's head dim")
+    Ncap, num_pages, page_size, max_pages = _mla_cache(kv_cache, block_table, B)
+    if kv_new is not None:
+        _mla_new(kv_new, B, Nq)
+    dev = kv_cache.device
+    for t, name in ((kv_cache, "kv_cache"), (q, "q")) + (((kv_new, "kv_new"),) if kv_new is not None else ()):
+        _mla_resident(t, name, dev)
+    _check_seqlens(cache_seqlens, B, dev)
+    if out is None:
+        out = torch.empty((B, Nq, H, _MLA_V), dtype=_F32, device=dev)
+    elif out.dtype is not _F32 or tuple(out.shape) != (B, Nq, H, _MLA_V) or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"out must be a contiguous float32 tensor of shape (B, Nq, H, {_MLA_V}) on q's device")
+    if lse is None:
+        lse = torch.empty((B, H, Nq), dtype=_F32, device=dev)
+    else:
+        _check_buffer(lse, q.get_device(), "lse", B * H * Nq)
+    nbytes = _lib.mla().fa_mi355x_decode_mla_workspace_bytes(B, H, Nq, Ncap)
+    if workspace is None:
+        workspace = torch.empty(nbytes // 4, dtype=_F32, device=dev) if nbytes else None
+    elif nbytes:
+        _check_workspace(workspace, nbytes, q.get_device(), "mla_workspace(q, kv_cache, block_table)")
+    _lib.mla_check(_lib.mla().fa_mi355x_fwd_decode_mla(_ptr(q), _ptr(kv_new), _ptr(kv_cache), _ptr(out), _ptr(lse), _ptr(cache_seqlens),
+                                                       _ptr(block_table), _ptr(workspace) if nbytes else None, B, H, Nq, Ncap, num_pages,
+                                                       page_size, max_pages, float(softmax_scale), int(bool(causal)), _stream_ptr()))
+    return out, lse

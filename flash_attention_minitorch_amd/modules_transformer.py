@@ -844,3 +844,69 @@ class GraphedStep:
         self.graph.replay()
         cache.length_bound = bound + T
         return self.y
+
+
+# ---- multi-head latent attention (DeepSeek MLA): the absorbed decode step on a latent cache ----------------------------------------
+MLA_LATENT, MLA_ROPE = 512, 64   # c_kv columns and k_pe columns of a cache row (device_ops.flash_attn_decode_mla: 576 = 512 + 64)
+
+# One layer's weights, all in x's dtype: wq (E, H * (dn + 64)) gives each head q_nope (dn) | q_pe (64); w_dkv (E, 576) gives the token's
+# c_kv (512) | k_pe (64, shared by the heads, before its rotation); w_uk (H, dn, 512): k_nope of head h is c_kv . w_uk[h]^T; w_uv
+# (H, 512, dv): v of head h is c_kv . w_uv[h]; wo (H * dv, E).
+MLAWeights = collections.namedtuple("MLAWeights", "wq w_dkv w_uk w_uv wo")
+
+
+class LatentKVCache:
+    """The cache of an MLA stack: per layer ONE row of 576 bf16 columns per token (c_kv | rotated k_pe), shared by all heads.
+    ``kv[l]`` is a slab (B, capacity, 576), or with ``page_size`` (a multiple of 128 rows) a pool (n_pages, page_size, 576) read
+    through ``block_table`` (B, max_pages) int32, which starts as sequence b owning pages b * max_pages .. and may be rewritten in
+    place.  ``lengths`` int32 (B,) lives on the device; ``advance(n)`` counts n new tokens per sequence without a host round trip."""
+
+    def __init__(self, n_layers, B, capacity, device, page_size=None, n_pages=None):
+        if n_layers < 1 or B < 1 or capacity < 1:
+            raise ValueError("n_layers, B and capacity must be positive")
+        self.capacity, self.block_table = capacity, None
+        shape = (B, capacity, MLA_LATENT + MLA_ROPE)
+        if page_size is not None:
+            if page_size <= 0 or page_size % _lib.FA_PAGE_ROWS:
+                raise ValueError(f"page_size = {page_size} must be a positive multiple of {_lib.FA_PAGE_ROWS} rows")
+            max_pages = -(-capacity // page_size)
+            n_pages = B * max_pages if n_pages is None else n_pages
+            if n_pages < B * max_pages:
+                raise ValueError("n_pages must hold max_pages pages for every sequence")
+            self.block_table = torch.arange(B * max_pages, dtype=torch.int32, device=device).view(B, max_pages)
+            shape = (n_pages, page_size, MLA_LATENT + MLA_ROPE)
+        self.kv = [torch.zeros(shape, dtype=torch.bfloat16, device=device) for _ in range(n_layers)]
+        self.lengths = torch.zeros(B, dtype=torch.int32, device=device)
+        self._workspaces = {}
+
+    def advance(self, n_tokens):
+        self.lengths += n_tokens
+
+    def workspace(self, q):
+        key = tuple(q.shape)
+        if key not in self._workspaces:
+            self._workspaces[key] = device_ops.mla_workspace(q, self.kv[0], self.block_table)
+        return self._workspaces[key]
+
+
+def mla_attention_step(x, cache: LatentKVCache, li: int, weights: MLAWeights, n_head: int, rope: Rotary, softmax_scale=None):
+    """One absorbed MLA step of layer ``li``: x (B, T, E) are the T <= 128 newest tokens of each sequence and ``cache.lengths``
+    already COUNTS them (cache.advance(T) once per step, in front of the layers).  (1) down-project: q = x wq, c_kv | k_pe = x w_dkv;
+    (2) rotate q_pe and k_pe at the positions lengths - T + i (``rope``: 64 rotary columns); (3) q_lat = q_nope . w_uk per head;
+    (4) ONE fused call appends c_kv | k_pe to the latent cache and attends over it (device_ops.flash_attn_decode_mla);
+    (5) out . w_uv per head, then wo.  ``softmax_scale``: (dn + 64) ** -0.5 unless given (a YaRN model passes its own).
+    Equal, up to rounding, to un-absorbed attention on k_h = [c_kv . w_uk[h]^T | k_pe], v_h = c_kv . w_uv[h]."""
+    B, T, _ = x.shape
+    wq, w_dkv, w_uk, w_uv, wo = weights
+    dn = w_uk.shape[1]
+    q = (x @ wq).view(B, T, n_head, dn + MLA_ROPE)
+    kv = x @ w_dkv
+    offsets = cache.lengths - T
+    q_pe = rope.apply(q[..., dn:].contiguous(), offsets)
+    k_pe = rope.apply(kv[..., MLA_LATENT:].reshape(B, T, 1, MLA_ROPE).contiguous(), offsets)
+    q_abs = torch.cat([torch.einsum("bthn,hnc->bthc", q[..., :dn], w_uk), q_pe], -1).contiguous()
+    kv_new = torch.cat([kv[..., :MLA_LATENT], k_pe.view(B, T, MLA_ROPE)], -1).contiguous()
+    scale = (dn + MLA_ROPE) ** -0.5 if softmax_scale is None else softmax_scale
+    out, _ = device_ops.flash_attn_decode_mla(q_abs, cache.kv[li], cache.lengths, scale, True, kv_new, cache.block_table,
+                                              workspace=cache.workspace(q_abs))
+    return torch.einsum("bthc,hcv->bthv", out.to(x.dtype), w_uv).reshape(B, T, -1) @ wo
