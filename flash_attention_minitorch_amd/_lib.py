@@ -554,11 +554,19 @@ MLA_ABI = {
 }
 MLA_NAME = "libflash_attn_mi355x_mla.so"
 MLA_D_QK, MLA_D_V = 576, 512   # columns of a cache row (and of q); the leading columns that are the value (and out's columns)
+# include/flash_attn_mi355x_mla_sparse.h, in the same library: sparse MLA decode (DeepSeek-V3.2 DSA) over per-query index lists, with
+# `indices` behind kv_cache and `topk` behind Nq (tests/test_mla_sparse_cpu.py).  A table of its own: MLA_ABI is its header's symbols.
+MLA_SPARSE_ABI = {
+    "fa_mi355x_fwd_decode_mla_sparse": (_i, [_vp] * 9 + [_i] * 8 + [_f, _i, _vp]),
+    "fa_mi355x_decode_mla_sparse_splits": (_i, [_i] * 4),
+    "fa_mi355x_decode_mla_sparse_workspace_bytes": (_sz, [_i] * 4),
+}
+MLA_TOPK_STEP = 64   # an index list is a whole number of 64-entry tiles
 
 
 def mla() -> ctypes.CDLL:
-    """libflash_attn_mi355x_mla.so (include/flash_attn_mi355x_mla.h) with argtypes set."""
-    return _typed(MLA_NAME, MLA_ABI)
+    """libflash_attn_mi355x_mla.so (include/flash_attn_mi355x_mla.h, include/flash_attn_mi355x_mla_sparse.h) with argtypes set."""
+    return _typed(MLA_NAME, {**MLA_ABI, **MLA_SPARSE_ABI})
 
 
 def mla_check(status: int) -> None:

@@ -28,7 +28,8 @@
 // mla_append_kernel: token i of batch element b goes to row len_b - Nq + i, slab or paged, in 16-byte moves.
 //
 // Not built: window, sink tokens, soft cap, learned sink logits, fp8 latents, the ragged family, an extend kernel for long prefills,
-// other latent widths, the training backward.
+// other latent widths, the training backward.  (Attention over per-query index lists, DeepSeek-V3.2's sparse attention, is a kernel
+// of its own on this image and these products: fa_mla_sparse.h.)
 #pragma once
 #include "fa_atoms.h"
 #include "fa_common.h"

@@ -1,7 +1,9 @@
 // C ABI of libflash_attn_mi355x_mla.so (include/flash_attn_mi355x_mla.h): multi-head latent attention decode on a latent KV cache.
 // The kernels are fa_mla.h's.  Every entry point fills one MlaCall, check() answers every bad argument before any HIP call, and the
-// split policy is stated once (policy()): the two size queries and the launch answer from it.
+// split policy is stated once (split_rule(), under policy() and sparse_policy()): the size queries and the launches answer from it.
+// The sparse call (include/flash_attn_mi355x_mla_sparse.h, kernel in fa_mla_sparse.h) is an MlaCall with an index list.
 #include "../../include/flash_attn_mi355x_mla.h"
+#include "../../include/flash_attn_mi355x_mla_sparse.h"
 
 #include <algorithm>
 #include <cmath>
@@ -9,6 +11,7 @@
 #include <cstdio>
 
 #include "fa_mla.h"
+#include "fa_mla_sparse.h"
 
 namespace {
 
@@ -30,11 +33,12 @@ struct MlaCall {
   void* kv_cache = nullptr;
   float *out = nullptr, *lse = nullptr;
   const int *seqlens = nullptr, *table = nullptr;
+  const int* indices = nullptr;   // the sparse call: [B][Nq][topk]
   void* workspace = nullptr;
-  int B = 0, H = 1, Nq = 0, Ncap = 0, num_pages = 0, page_size = 0, max_pages = 0;
+  int B = 0, H = 1, Nq = 0, topk = 0, Ncap = 0, num_pages = 0, page_size = 0, max_pages = 0;
   float softmax_scale = 0.f;
   int causal = 0;
-  bool attend = false, append = false;
+  bool attend = false, append = false, sparse = false;
   hipStream_t stream = nullptr;
 };
 
@@ -52,20 +56,35 @@ struct Policy {
   size_t workspace_bytes;
 };
 
+// The rule itself: `groups` sets of workgroups walk `n` keys (dense: the cache's capacity; sparse: the entries of an index list).
+void split_rule(Policy& p, long groups, int n, int B, int H, int Nq) {
+  const long want = std::max(1L, (MLA_CUS * MLA_ROUNDS + groups - 1) / groups);
+  const long per = (n + want - 1) / want;
+  p.chunk = (int)std::max((long)MLA_MIN_CHUNK, (per + MLA_SUPER - 1) / MLA_SUPER * MLA_SUPER);
+  p.nsplit = (int)(((long)n + p.chunk - 1) / p.chunk);
+  p.workspace_bytes = p.nsplit == 1 ? 0 : (size_t)B * H * p.nsplit * Nq * (size_t)(fa::MLA_DV + 2) * sizeof(float);
+}
+
 Policy policy(int B, int H, int Nq, int Ncap) {
   Policy p;
   p.nqb = ((long)H * Nq + fa::MLA_BLOCK - 1) / fa::MLA_BLOCK;
-  const long groups = (long)B * p.nqb;
-  const long want = std::max(1L, (MLA_CUS * MLA_ROUNDS + groups - 1) / groups);
-  const long per = (Ncap + want - 1) / want;
-  p.chunk = (int)std::max((long)MLA_MIN_CHUNK, (per + MLA_SUPER - 1) / MLA_SUPER * MLA_SUPER);
-  p.nsplit = (int)(((long)Ncap + p.chunk - 1) / p.chunk);
+  split_rule(p, (long)B * p.nqb, Ncap, B, H, Nq);
   p.items = (long)B * p.nsplit;
-  p.workspace_bytes = p.nsplit == 1 ? 0 : (size_t)B * H * p.nsplit * Nq * (size_t)(fa::MLA_DV + 2) * sizeof(float);
   return p;
 }
 
-Policy query(int B, int H, int Nq, int Ncap) { return B > 0 && H > 0 && Nq > 0 && Ncap > 0 ? policy(B, H, Nq, Ncap) : Policy{}; }
+// The sparse call: a block holds 64 heads of ONE query token, and the chunks cut that token's list.
+Policy sparse_policy(int B, int H, int Nq, int topk) {
+  Policy p;
+  p.nqb = ((long)H + fa::MLA_BLOCK - 1) / fa::MLA_BLOCK;
+  split_rule(p, (long)B * Nq * p.nqb, topk, B, H, Nq);
+  p.items = (long)B * Nq * p.nsplit;
+  return p;
+}
+
+Policy query(int B, int H, int Nq, int n, bool sparse = false) {
+  return B > 0 && H > 0 && Nq > 0 && n > 0 ? (sparse ? sparse_policy(B, H, Nq, n) : policy(B, H, Nq, n)) : Policy{};
+}
 
 long split_grid(long items, long nqb) { return (items + 7) / 8 * 8 * nqb; }
 
@@ -87,6 +106,8 @@ int check(MlaCall& c, Policy* out) {
     if ((long)c.max_pages * c.page_size + MLA_SUPER > 0x7fffffffL)
       return set_err(FA_ERR_BAD_ARG, "max_pages * page_size (the logical capacity) must fit an int");
     if ((long)c.page_size * fa::MLA_ROW_BYTES >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "one page of the pool must stay under 2 GiB");
+    if (c.sparse && (long)c.num_pages * c.page_size >= (1L << 31))
+      return set_err(FA_ERR_BAD_ARG, "num_pages * page_size (the pool's rows) must stay under 2^31 for the sparse call");
     c.Ncap = c.max_pages * c.page_size;
   } else {
     if (c.Ncap <= 0) return set_err(FA_ERR_BAD_ARG, "Ncap must be positive");
@@ -106,7 +127,16 @@ int check(MlaCall& c, Policy* out) {
     return set_err(FA_ERR_BAD_ARG, "softmax_scale must be positive and finite: it is required (576 is not the model's head dim)");
   if ((long)c.H * c.Nq >= (1L << 25)) return set_err(FA_ERR_BAD_ARG, "H * Nq rows must stay under 2^25");
   if ((long)c.Nq * c.H * fa::MLA_ROW_BYTES >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "one batch element of q must stay under 2 GiB");
-  const Policy p = policy(c.B, c.H, c.Nq, c.Ncap);
+  if (c.sparse) {
+    if (!c.indices) return set_err(FA_ERR_BAD_ARG, "null pointer argument: indices");
+    if ((uintptr_t)c.indices % 4 != 0) return set_err(FA_ERR_BAD_ARG, "indices must be 4-byte aligned");
+    if (c.topk <= 0 || c.topk % fa::MLA_TILE != 0) {
+      snprintf(g_err, sizeof(g_err), "topk = %d must be a positive multiple of %d entries", c.topk, fa::MLA_TILE);
+      return FA_ERR_BAD_ARG;
+    }
+    if ((long)c.B * c.Nq * c.topk >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "B * Nq * topk index entries must stay under 2^31");
+  }
+  const Policy p = c.sparse ? sparse_policy(c.B, c.H, c.Nq, c.topk) : policy(c.B, c.H, c.Nq, c.Ncap);
   if (split_grid(p.items, p.nqb) >= (1L << 32) || p.items >= (1L << 31) || (long)c.B * c.H * c.Nq >= (1L << 32))
     return set_err(FA_ERR_BAD_ARG, "too many workgroups for one launch: B * splits * row blocks and B * H * Nq must fit an unsigned int");
   if (p.nsplit > 1 && !c.workspace)
@@ -147,10 +177,21 @@ int launch_attend(const MlaCall& c, const Policy& p) {
   a.page_size = c.page_size, a.num_pages = c.num_pages, a.max_pages = c.max_pages;
   a.page_stride = (long)c.page_size * D;
   const unsigned grid = (unsigned)split_grid(p.items, p.nqb);
-  if (c.table) hipLaunchKernelGGL(fa::mla_decode_split_kernel<true>, dim3(grid), dim3(256), 0, c.stream, a);
-  else hipLaunchKernelGGL(fa::mla_decode_split_kernel<false>, dim3(grid), dim3(256), 0, c.stream, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_err("mla_decode_split_kernel launch", e);
+  hipError_t e;
+  if (c.sparse) {   // (the same argument and the list; G = H is not read: a block's rows are heads of one token)
+    fa::MlaSparseArgs sa{};
+    static_cast<fa::DecodeArgs&>(sa) = a;
+    sa.indices = c.indices, sa.topk = c.topk;
+    if (c.table) hipLaunchKernelGGL(fa::mla_sparse_split_kernel<true>, dim3(grid), dim3(256), 0, c.stream, sa);
+    else hipLaunchKernelGGL(fa::mla_sparse_split_kernel<false>, dim3(grid), dim3(256), 0, c.stream, sa);
+    e = hipGetLastError();
+    if (e != hipSuccess) return hip_err("mla_sparse_split_kernel launch", e);
+  } else {
+    if (c.table) hipLaunchKernelGGL(fa::mla_decode_split_kernel<true>, dim3(grid), dim3(256), 0, c.stream, a);
+    else hipLaunchKernelGGL(fa::mla_decode_split_kernel<false>, dim3(grid), dim3(256), 0, c.stream, a);
+    e = hipGetLastError();
+    if (e != hipSuccess) return hip_err("mla_decode_split_kernel launch", e);
+  }
   if (p.nsplit == 1) return FA_OK;
   // (the combine body addresses out through q's strides: out's stand in their place)
   a.q_ld = c.H * DV, a.q_hstride = DV, a.q_bstride = (long)c.Nq * c.H * DV;
@@ -184,6 +225,19 @@ int fa_mi355x_fwd_decode_mla(const void* q, const void* kv_new, void* kv_cache, 
   return run(c);
 }
 
+int fa_mi355x_fwd_decode_mla_sparse(const void* q, const void* kv_new, void* kv_cache, const int* indices, float* out, float* lse,
+                                    const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Nq, int topk,
+                                    int Ncap, int num_pages, int page_size, int max_pages, float softmax_scale, int causal,
+                                    void* stream) {
+  MlaCall c;
+  c.q = q, c.kv_new = kv_new, c.kv_cache = kv_cache, c.out = out, c.lse = lse, c.seqlens = cache_seqlens, c.table = block_table;
+  c.workspace = workspace, c.B = B, c.H = H, c.Nq = Nq, c.Ncap = Ncap, c.num_pages = num_pages, c.page_size = page_size;
+  c.max_pages = max_pages, c.softmax_scale = softmax_scale, c.causal = causal, c.stream = static_cast<hipStream_t>(stream);
+  c.indices = indices, c.topk = topk;
+  c.attend = true, c.append = kv_new != nullptr, c.sparse = true;
+  return run(c);
+}
+
 int fa_mi355x_mla_append(const void* kv_new, void* kv_cache, const int* cache_seqlens, const int* block_table, int B, int Nq, int Ncap,
                          int num_pages, int page_size, int max_pages, void* stream) {
   MlaCall c;
@@ -196,5 +250,11 @@ int fa_mi355x_mla_append(const void* kv_new, void* kv_cache, const int* cache_se
 int fa_mi355x_decode_mla_splits(int B, int H, int Nq, int Ncap) { return query(B, H, Nq, Ncap).nsplit; }
 
 size_t fa_mi355x_decode_mla_workspace_bytes(int B, int H, int Nq, int Ncap) { return query(B, H, Nq, Ncap).workspace_bytes; }
+
+int fa_mi355x_decode_mla_sparse_splits(int B, int H, int Nq, int topk) { return query(B, H, Nq, topk, true).nsplit; }
+
+size_t fa_mi355x_decode_mla_sparse_workspace_bytes(int B, int H, int Nq, int topk) {
+  return query(B, H, Nq, topk, true).workspace_bytes;
+}
 
 }  // extern "C"

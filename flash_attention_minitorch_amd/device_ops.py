@@ -2117,12 +2117,38 @@ def _mla_q(q):
     return B, Nq, H
 
 
-def mla_workspace(q, kv_cache, block_table=None, max_pages=None):
+def _mla_indices(indices, B, Nq, device):
+    """topk of a sparse call's index lists: int32 (B, Nq, topk), topk a positive multiple of 64, contiguous, on the cache's device."""
+    step = _lib.MLA_TOPK_STEP
+    if not isinstance(indices, torch.Tensor) or indices.dtype != torch.int32:
+        raise TypeError(f"indices must be an int32 tensor (got {getattr(indices, 'dtype', type(indices).__name__)})")
+    if indices.dim() != 3 or indices.shape[0] != B or indices.shape[1] != Nq:
+        raise ValueError(f"indices must be (B, Nq, topk) with q's B = {B} and Nq = {Nq} (got {tuple(indices.shape)}): a list per query token")
+    return _mla_topk(int(indices.shape[2]), indices, device)
+
+
+def _mla_topk(topk, indices=None, device=None):
+    if not isinstance(topk, int) or topk < _lib.MLA_TOPK_STEP or topk % _lib.MLA_TOPK_STEP:
+        raise ValueError(f"topk = {topk} must be a positive multiple of {_lib.MLA_TOPK_STEP}: pad the index lists with -1")
+    if indices is not None and (not indices.is_contiguous() or indices.device != device):
+        raise ValueError("indices must be contiguous and on the cache's device")
+    return topk
+
+
+def _mla_workspace_bytes(B, H, Nq, Ncap, topk):
+    """The dense call's workspace, or with ``topk`` the sparse call's (whose splits cut the index list, not the cache)."""
+    if topk is None:
+        return _lib.mla().fa_mi355x_decode_mla_workspace_bytes(B, H, Nq, Ncap)
+    return _lib.mla().fa_mi355x_decode_mla_sparse_workspace_bytes(B, H, Nq, topk)
+
+
+def mla_workspace(q, kv_cache, block_table=None, max_pages=None, topk=None):
     """Scratch for flash_attn_decode_mla on these shapes (fa_mi355x_decode_mla_workspace_bytes), or None when the call runs one split.
-    A pool without its table: pass ``max_pages``."""
+    A pool without its table: pass ``max_pages``.  ``topk``: for the sparse call with index lists of that many entries
+    (fa_mi355x_decode_mla_sparse_workspace_bytes)."""
     B, Nq, H = _mla_q(q)
     Ncap = _mla_cache(kv_cache, block_table, B, max_pages)[0]
-    nbytes = _lib.mla().fa_mi355x_decode_mla_workspace_bytes(B, H, Nq, Ncap)
+    nbytes = _mla_workspace_bytes(B, H, Nq, Ncap, None if topk is None else _mla_topk(topk))
     return torch.empty(nbytes // 4, dtype=_F32, device=q.device) if nbytes else None
 
 
@@ -2143,14 +2169,18 @@ def mla_append(kv_new, kv_cache, cache_seqlens, block_table=None):
 
 
 def flash_attn_decode_mla(q, kv_cache, cache_seqlens, softmax_scale, causal=True, kv_new=None, block_table=None, out=None, lse=None,
-                          workspace=None):
+                          workspace=None, indices=None):
     """One MLA decode step on a latent KV cache (fa_mi355x_fwd_decode_mla).  ``q`` bf16 (B, Nq, H, 576): the absorbed q_nope . W_UK in
     columns 0..511, the rotated q_pe in 512..575.  ``kv_cache`` bf16 (B, Ncap, 576), or with ``block_table`` (B, max_pages) int32 a
     pool (num_pages, page_size, 576).  ``cache_seqlens`` int32 (B,) on the device; under ``causal`` the queries are the last Nq
     positions of each sequence.  ``kv_new`` bf16 (B, Nq, 576): appended first, in the same call (the lengths count it).
     ``softmax_scale`` is REQUIRED: 576 is not the model's head dim (DeepSeek: (128 + 64) ** -0.5 times its YaRN factor).
     Returns (out fp32 (B, Nq, H, 512), lse fp32 (B, H, Nq)); a sequence of length 0 gives out = 0 and lse = -inf.  No host
-    synchronisation: the call can be captured in a graph (``workspace``: mla_workspace(...), allocated per call when None)."""
+    synchronisation: the call can be captured in a graph (``workspace``: mla_workspace(...), allocated per call when None).
+    ``indices`` int32 (B, Nq, topk), topk a multiple of 64: the sparse call (fa_mi355x_fwd_decode_mla_sparse; DeepSeek-V3.2 DSA).
+    Query token (b, i) attends, in all its heads, only the positions its list names; an entry j counts iff 0 <= j < len_b (and
+    j <= len_b - Nq + i under ``causal``), any other value (-1 padding) is an entry that is not there, and a position named twice
+    counts twice.  A query without an admitted entry gives out = 0 and lse = -inf.  (``workspace``: mla_workspace(..., topk=topk).)"""
     B, Nq, H = _mla_q(q)
     if not isinstance(softmax_scale, numbers.Real) or not softmax_scale > 0 or not math.isfinite(softmax_scale):
         raise ValueError("softmax_scale is required, positive and finite: the absorbed width 576 is not the model's head dim")
@@ -2158,6 +2188,7 @@ def flash_attn_decode_mla(q, kv_cache, cache_seqlens, softmax_scale, causal=True
     if kv_new is not None:
         _mla_new(kv_new, B, Nq)
     dev = kv_cache.device
+    topk = None if indices is None else _mla_indices(indices, B, Nq, dev)
     for t, name in ((kv_cache, "kv_cache"), (q, "q")) + (((kv_new, "kv_new"),) if kv_new is not None else ()):
         _mla_resident(t, name, dev)
     _check_seqlens(cache_seqlens, B, dev)
@@ -2169,11 +2200,17 @@ def flash_attn_decode_mla(q, kv_cache, cache_seqlens, softmax_scale, causal=True
         lse = torch.empty((B, H, Nq), dtype=_F32, device=dev)
     else:
         _check_buffer(lse, q.get_device(), "lse", B * H * Nq)
-    nbytes = _lib.mla().fa_mi355x_decode_mla_workspace_bytes(B, H, Nq, Ncap)
+    nbytes = _mla_workspace_bytes(B, H, Nq, Ncap, topk)
     if workspace is None:
         workspace = torch.empty(nbytes // 4, dtype=_F32, device=dev) if nbytes else None
     elif nbytes:
         _check_workspace(workspace, nbytes, q.get_device(), "mla_workspace(q, kv_cache, block_table)")
+    if indices is not None:
+        _lib.mla_check(_lib.mla().fa_mi355x_fwd_decode_mla_sparse(
+            _ptr(q), _ptr(kv_new), _ptr(kv_cache), _ptr(indices), _ptr(out), _ptr(lse), _ptr(cache_seqlens), _ptr(block_table),
+            _ptr(workspace) if nbytes else None, B, H, Nq, topk, Ncap, num_pages, page_size, max_pages, float(softmax_scale),
+            int(bool(causal)), _stream_ptr()))
+        return out, lse
     _lib.mla_check(_lib.mla().fa_mi355x_fwd_decode_mla(_ptr(q), _ptr(kv_new), _ptr(kv_cache), _ptr(out), _ptr(lse), _ptr(cache_seqlens),
                                                        _ptr(block_table), _ptr(workspace) if nbytes else None, B, H, Nq, Ncap, num_pages,
                                                        page_size, max_pages, float(softmax_scale), int(bool(causal)), _stream_ptr()))

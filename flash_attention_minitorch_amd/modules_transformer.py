@@ -882,20 +882,23 @@ class LatentKVCache:
     def advance(self, n_tokens):
         self.lengths += n_tokens
 
-    def workspace(self, q):
-        key = tuple(q.shape)
+    def workspace(self, q, topk=None):
+        key = tuple(q.shape) + (topk,)
         if key not in self._workspaces:
-            self._workspaces[key] = device_ops.mla_workspace(q, self.kv[0], self.block_table)
+            self._workspaces[key] = device_ops.mla_workspace(q, self.kv[0], self.block_table, topk=topk)
         return self._workspaces[key]
 
 
-def mla_attention_step(x, cache: LatentKVCache, li: int, weights: MLAWeights, n_head: int, rope: Rotary, softmax_scale=None):
+def mla_attention_step(x, cache: LatentKVCache, li: int, weights: MLAWeights, n_head: int, rope: Rotary, softmax_scale=None,
+                       indices=None):
     """One absorbed MLA step of layer ``li``: x (B, T, E) are the T <= 128 newest tokens of each sequence and ``cache.lengths``
     already COUNTS them (cache.advance(T) once per step, in front of the layers).  (1) down-project: q = x wq, c_kv | k_pe = x w_dkv;
     (2) rotate q_pe and k_pe at the positions lengths - T + i (``rope``: 64 rotary columns); (3) q_lat = q_nope . w_uk per head;
     (4) ONE fused call appends c_kv | k_pe to the latent cache and attends over it (device_ops.flash_attn_decode_mla);
     (5) out . w_uv per head, then wo.  ``softmax_scale``: (dn + 64) ** -0.5 unless given (a YaRN model passes its own).
-    Equal, up to rounding, to un-absorbed attention on k_h = [c_kv . w_uk[h]^T | k_pe], v_h = c_kv . w_uv[h]."""
+    Equal, up to rounding, to un-absorbed attention on k_h = [c_kv . w_uk[h]^T | k_pe], v_h = c_kv . w_uv[h].
+    ``indices`` int32 (B, T, topk): DeepSeek-V3.2 sparse attention, token (b, t) attends only the cache positions its list names
+    (device_ops.flash_attn_decode_mla's ``indices``).  The indexer that scores the cache and picks them is the caller's."""
     B, T, _ = x.shape
     wq, w_dkv, w_uk, w_uv, wo = weights
     dn = w_uk.shape[1]
@@ -907,6 +910,8 @@ def mla_attention_step(x, cache: LatentKVCache, li: int, weights: MLAWeights, n_
     q_abs = torch.cat([torch.einsum("bthn,hnc->bthc", q[..., :dn], w_uk), q_pe], -1).contiguous()
     kv_new = torch.cat([kv[..., :MLA_LATENT], k_pe.view(B, T, MLA_ROPE)], -1).contiguous()
     scale = (dn + MLA_ROPE) ** -0.5 if softmax_scale is None else softmax_scale
+    sparse = {} if indices is None else {"indices": indices}   # (the dense step is the call it was)
     out, _ = device_ops.flash_attn_decode_mla(q_abs, cache.kv[li], cache.lengths, scale, True, kv_new, cache.block_table,
-                                              workspace=cache.workspace(q_abs))
+                                              workspace=cache.workspace(q_abs, None if indices is None else int(indices.shape[-1])),
+                                              **sparse)
     return torch.einsum("bthc,hcv->bthv", out.to(x.dtype), w_uv).reshape(B, T, -1) @ wo

@@ -25,6 +25,8 @@
  *
  * Not built: a sliding window, sink tokens, a soft cap, learned sink logits, fp8 latents, the ragged family, an extend kernel for
  * long prefills (a prompt is prefilled un-absorbed, as ordinary attention), other latent widths, the training backward.
+ * (Sparse attention over per-query index lists, DeepSeek-V3.2 DSA, is in this library under a header of its own:
+ * flash_attn_mi355x_mla_sparse.h.)
  */
 #ifndef FLASH_ATTN_MI355X_MLA_H
 #define FLASH_ATTN_MI355X_MLA_H
