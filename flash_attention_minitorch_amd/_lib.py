@@ -562,11 +562,22 @@ MLA_SPARSE_ABI = {
     "fa_mi355x_decode_mla_sparse_workspace_bytes": (_sz, [_i] * 4),
 }
 MLA_TOPK_STEP = 64   # an index list is a whole number of 64-entry tiles
+# include/flash_attn_mi355x_mla_indexer.h, in the same library: the lightning indexer that produces those lists (index scores, top-k
+# selection, the index-key append, the three in one call, the two size queries; tests/test_mla_indexer_cpu.py).  A table of its own.
+MLA_INDEXER_ABI = {
+    "fa_mi355x_mla_index_scores": (_i, [_vp] * 7 + [_i] * 8 + [_vp]),
+    "fa_mi355x_mla_index_topk": (_i, [_vp] * 3 + [_i] * 4 + [_vp]),
+    "fa_mi355x_mla_index_append": (_i, [_vp] * 4 + [_i] * 6 + [_vp]),
+    "fa_mi355x_mla_indexer": (_i, [_vp] * 8 + [_i] * 9 + [_vp]),
+    "fa_mi355x_mla_indexer_scores_bytes": (_sz, [_i] * 3),
+    "fa_mi355x_mla_index_chunks": (_i, [_i] * 4),
+}
+MLA_INDEX_D, MLA_INDEX_MAX_HEADS = 128, 128   # columns of an index key (and of an index query); index heads at the most
 
 
 def mla() -> ctypes.CDLL:
-    """libflash_attn_mi355x_mla.so (include/flash_attn_mi355x_mla.h, include/flash_attn_mi355x_mla_sparse.h) with argtypes set."""
-    return _typed(MLA_NAME, {**MLA_ABI, **MLA_SPARSE_ABI})
+    """libflash_attn_mi355x_mla.so (include/flash_attn_mi355x_mla.h, ..._mla_sparse.h, ..._mla_indexer.h) with argtypes set."""
+    return _typed(MLA_NAME, {**MLA_ABI, **MLA_SPARSE_ABI, **MLA_INDEXER_ABI})
 
 
 def mla_check(status: int) -> None:

@@ -2,7 +2,10 @@
 // The kernels are fa_mla.h's.  Every entry point fills one MlaCall, check() answers every bad argument before any HIP call, and the
 // split policy is stated once (split_rule(), under policy() and sparse_policy()): the size queries and the launches answer from it.
 // The sparse call (include/flash_attn_mi355x_mla_sparse.h, kernel in fa_mla_sparse.h) is an MlaCall with an index list.
+// The indexer that produces such lists (include/flash_attn_mi355x_mla_indexer.h, kernels in fa_mla_indexer.h) fills one IndexCall,
+// which check_index() answers the same way; its chunking is index_policy(), under the split policies.
 #include "../../include/flash_attn_mi355x_mla.h"
+#include "../../include/flash_attn_mi355x_mla_indexer.h"
 #include "../../include/flash_attn_mi355x_mla_sparse.h"
 
 #include <algorithm>
@@ -11,6 +14,7 @@
 #include <cstdio>
 
 #include "fa_mla.h"
+#include "fa_mla_indexer.h"
 #include "fa_mla_sparse.h"
 
 namespace {
@@ -87,6 +91,31 @@ Policy query(int B, int H, int Nq, int n, bool sparse = false) {
 }
 
 long split_grid(long items, long nqb) { return (items + 7) / 8 * 8 * nqb; }
+
+// The indexer's score launch: a workgroup = (batch element, group of tokens, chunk of keys) streams its chunk once for the group's
+// tokens.  A group is as many tokens as the 64 KB of Q in LDS hold (8 blocks of 32 heads), 4 at the most.  Two workgroups share a
+// CU (66 KB of LDS each), so the aim is two rounds of two workgroups on each of the 256 CUs; chunks are whole 128-key steps (a page
+// is a whole number of them) and at least 512 keys, which keeps the 16 KB of Q per token a small part of what a workgroup reads.
+constexpr int IDX_WGS_PER_CU = 2, IDX_MIN_CHUNK = 512;
+static_assert(FA_PAGE_ROWS % fa::MLA_IDX_STEP == 0 && IDX_MIN_CHUNK % fa::MLA_IDX_STEP == 0, "a page and a chunk are whole steps");
+
+struct IndexPolicy {
+  int group = 0, ngroups = 0, chunk = 0, nchunk = 0;
+};
+
+IndexPolicy index_policy(int B, int HI, int Nq, int Ncap) {
+  IndexPolicy p;
+  if (B <= 0 || HI <= 0 || Nq <= 0 || Ncap <= 0) return p;
+  const int tiles = (HI + 31) / 32;
+  p.group = std::min(Nq, std::min(fa::MLA_IDX_MAX_GROUP, std::max(1, fa::MLA_IDX_QBLOCKS / tiles)));
+  p.ngroups = (Nq + p.group - 1) / p.group;
+  const long groups = (long)B * p.ngroups;
+  const long want = std::max(1L, ((long)MLA_CUS * IDX_WGS_PER_CU * MLA_ROUNDS + groups - 1) / groups);
+  const long per = (Ncap + want - 1) / want;
+  p.chunk = (int)std::max((long)IDX_MIN_CHUNK, (per + fa::MLA_IDX_STEP - 1) / fa::MLA_IDX_STEP * fa::MLA_IDX_STEP);
+  p.nchunk = (int)(((long)Ncap + p.chunk - 1) / p.chunk);
+  return p;
+}
 
 bool misaligned(const void* p) { return (uintptr_t)p % 16 != 0; }
 
@@ -208,6 +237,107 @@ int run(MlaCall& c) {
   return c.attend ? launch_attend(c, p) : FA_OK;
 }
 
+// ---- the indexer ----
+struct IndexCall {
+  const void* q_idx = nullptr;
+  const float* weights = nullptr;
+  const void* kidx_new = nullptr;
+  void* kidx_cache = nullptr;
+  float* scores = nullptr;
+  int* indices = nullptr;
+  const int *seqlens = nullptr, *table = nullptr;
+  int B = 0, HI = 1, Nq = 0, topk = 0, Ncap = 0, num_pages = 0, page_size = 0, max_pages = 0, causal = 0;
+  bool append = false, score = false, select = false;
+  hipStream_t stream = nullptr;
+};
+
+bool misaligned4(const void* p) { return (uintptr_t)p % 4 != 0; }
+
+// Every check of an indexer call, in one order, before any HIP call.  A paged call's Ncap becomes max_pages * page_size.
+int check_index(IndexCall& c, IndexPolicy* out) {
+  g_err[0] = 0;
+  if (c.B <= 0 || c.HI <= 0 || c.Nq <= 0) return set_err(FA_ERR_BAD_ARG, "B, HI and Nq must be positive");
+  if (c.Nq > FA_DECODE_MAX_NQ) return set_err(FA_ERR_BAD_ARG, "Nq > 128 is prefill: an indexer for prefill is not built");
+  if (c.HI > fa::MLA_IDX_MAX_HI) return set_err(FA_ERR_BAD_ARG, "HI must be in 1 .. 128 index heads");
+  if (c.table) {
+    if (c.num_pages <= 0 || c.page_size <= 0 || c.max_pages <= 0)
+      return set_err(FA_ERR_BAD_ARG, "num_pages, page_size and max_pages must be positive");
+    if (c.page_size % FA_PAGE_ROWS != 0) {
+      snprintf(g_err, sizeof(g_err), "page_size = %d must be a multiple of %d rows", c.page_size, FA_PAGE_ROWS);
+      return FA_ERR_BAD_ARG;
+    }
+    if ((long)c.max_pages * c.page_size + fa::MLA_IDX_STEP > 0x7fffffffL)
+      return set_err(FA_ERR_BAD_ARG, "max_pages * page_size (the logical capacity) must fit an int");
+    c.Ncap = c.max_pages * c.page_size;
+  } else {
+    if (c.Ncap <= 0) return set_err(FA_ERR_BAD_ARG, "Ncap must be positive");
+    // (a buffer load's row offset is a 32-bit byte count: a slab, plus a step of rows past its end)
+    if (!c.select || c.score || c.append)
+      if (((long)c.Ncap + fa::MLA_IDX_STEP) * fa::MLA_IDX_ROW_BYTES >= (1L << 31))
+        return set_err(FA_ERR_BAD_ARG, "one batch element of the index-key cache must stay under 2 GiB");
+  }
+  if (misaligned4(c.seqlens) || misaligned4(c.table)) return set_err(FA_ERR_BAD_ARG, "cache_seqlens and block_table must be 4-byte aligned");
+  if (c.append || c.score) {
+    if (!c.kidx_cache) return set_err(FA_ERR_BAD_ARG, "null pointer argument: kidx_cache");
+    if (c.append && !c.kidx_new) return set_err(FA_ERR_BAD_ARG, "null pointer argument: kidx_new");
+    if (misaligned(c.kidx_cache) || misaligned(c.kidx_new)) return set_err(FA_ERR_BAD_ARG, "kidx_cache and kidx_new must be 16-byte aligned");
+  }
+  if (c.score) {
+    if (!c.q_idx || !c.weights) return set_err(FA_ERR_BAD_ARG, "null pointer argument: q_idx and weights");
+    if (misaligned(c.q_idx) || misaligned(c.weights)) return set_err(FA_ERR_BAD_ARG, "q_idx and weights must be 16-byte aligned");
+  }
+  if (c.score || c.select) {
+    if (!c.scores) return set_err(FA_ERR_BAD_ARG, "null pointer argument: scores");
+    if (misaligned(c.scores)) return set_err(FA_ERR_BAD_ARG, "scores must be 16-byte aligned");
+  }
+  if (c.select) {
+    if (!c.indices) return set_err(FA_ERR_BAD_ARG, "null pointer argument: indices");
+    if (misaligned4(c.indices)) return set_err(FA_ERR_BAD_ARG, "indices must be 4-byte aligned");
+    if (c.topk <= 0 || c.topk % fa::MLA_TILE != 0) {
+      snprintf(g_err, sizeof(g_err), "topk = %d must be a positive multiple of %d entries", c.topk, fa::MLA_TILE);
+      return FA_ERR_BAD_ARG;
+    }
+    if ((long)c.B * c.Nq * c.topk >= (1L << 30)) return set_err(FA_ERR_BAD_ARG, "B * Nq * topk index entries must stay under 2^30");
+    if (c.Ncap >= (1 << 30)) return set_err(FA_ERR_BAD_ARG, "a row of scores (Ncap) must stay under 2^30 entries");
+  }
+  const IndexPolicy p = index_policy(c.B, c.HI, c.Nq, c.Ncap);
+  if ((long)c.B * p.ngroups * p.nchunk >= (1L << 31) || (long)c.B * c.Nq * (fa::MLA_IDX_D / 8) / 256 >= (1L << 31))
+    return set_err(FA_ERR_BAD_ARG, "too many workgroups for one launch");
+  *out = p;
+  return FA_OK;
+}
+
+int run_index(IndexCall& c) {
+  IndexPolicy p;
+  if (int rc = check_index(c, &p)) return rc;
+  hipError_t e;
+  if (c.append) {
+    fa::MlaAppendArgs a;
+    a.kv_new = c.kidx_new, a.kv = c.kidx_cache, a.seqlens = c.seqlens, a.table = c.table;
+    a.lanes = (long)c.B * c.Nq * (fa::MLA_IDX_D / 8);
+    a.Nq = c.Nq, a.Ncap = c.Ncap, a.page_size = c.page_size, a.num_pages = c.num_pages, a.max_pages = c.max_pages;
+    hipLaunchKernelGGL(fa::mla_index_append_kernel, dim3((unsigned)((a.lanes + 255) / 256)), dim3(256), 0, c.stream, a);
+    if ((e = hipGetLastError()) != hipSuccess) return hip_err("mla_index_append_kernel launch", e);
+  }
+  if (c.score) {
+    fa::MlaIndexArgs a;
+    a.q = c.q_idx, a.w = c.weights, a.k = c.kidx_cache, a.scores = c.scores, a.seqlens = c.seqlens, a.table = c.table;
+    a.HI = c.HI, a.Nq = c.Nq, a.Ncap = c.Ncap, a.chunk = p.chunk, a.nchunk = p.nchunk, a.group = p.group, a.ngroups = p.ngroups;
+    a.page_size = c.page_size, a.num_pages = c.num_pages, a.max_pages = c.max_pages, a.causal = c.causal ? 1 : 0;
+    const dim3 grid((unsigned)((long)c.B * p.ngroups * p.nchunk));
+    if (c.table) hipLaunchKernelGGL(fa::mla_index_scores_kernel<true>, grid, dim3(256), 0, c.stream, a);
+    else hipLaunchKernelGGL(fa::mla_index_scores_kernel<false>, grid, dim3(256), 0, c.stream, a);
+    if ((e = hipGetLastError()) != hipSuccess) return hip_err("mla_index_scores_kernel launch", e);
+  }
+  if (c.select) {
+    fa::MlaTopkArgs a;
+    a.scores = c.scores, a.indices = c.indices, a.seqlens = c.seqlens, a.Nq = c.Nq, a.Ncap = c.Ncap, a.topk = c.topk;
+    hipLaunchKernelGGL(fa::mla_index_topk_kernel, dim3((unsigned)(c.B * c.Nq)), dim3(fa::MLA_TOPK_THREADS), 0, c.stream, a);
+    if ((e = hipGetLastError()) != hipSuccess) return hip_err("mla_index_topk_kernel launch", e);
+  }
+  return FA_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -256,5 +386,51 @@ int fa_mi355x_decode_mla_sparse_splits(int B, int H, int Nq, int topk) { return 
 size_t fa_mi355x_decode_mla_sparse_workspace_bytes(int B, int H, int Nq, int topk) {
   return query(B, H, Nq, topk, true).workspace_bytes;
 }
+
+int fa_mi355x_mla_index_scores(const void* q_idx, const float* weights, const void* kidx_new, void* kidx_cache, float* scores,
+                               const int* cache_seqlens, const int* block_table, int B, int HI, int Nq, int Ncap, int num_pages,
+                               int page_size, int max_pages, int causal, void* stream) {
+  IndexCall c;
+  c.q_idx = q_idx, c.weights = weights, c.kidx_new = kidx_new, c.kidx_cache = kidx_cache, c.scores = scores, c.seqlens = cache_seqlens;
+  c.table = block_table, c.B = B, c.HI = HI, c.Nq = Nq, c.Ncap = Ncap, c.num_pages = num_pages, c.page_size = page_size;
+  c.max_pages = max_pages, c.causal = causal, c.stream = static_cast<hipStream_t>(stream);
+  c.append = kidx_new != nullptr, c.score = true;
+  return run_index(c);
+}
+
+int fa_mi355x_mla_index_topk(const float* scores, int* indices, const int* cache_seqlens, int B, int Nq, int Ncap, int topk,
+                             void* stream) {
+  IndexCall c;
+  c.scores = const_cast<float*>(scores), c.indices = indices, c.seqlens = cache_seqlens, c.B = B, c.Nq = Nq, c.Ncap = Ncap, c.topk = topk;
+  c.stream = static_cast<hipStream_t>(stream);
+  c.select = true;
+  return run_index(c);
+}
+
+int fa_mi355x_mla_index_append(const void* kidx_new, void* kidx_cache, const int* cache_seqlens, const int* block_table, int B, int Nq,
+                               int Ncap, int num_pages, int page_size, int max_pages, void* stream) {
+  IndexCall c;
+  c.kidx_new = kidx_new, c.kidx_cache = kidx_cache, c.seqlens = cache_seqlens, c.table = block_table, c.B = B, c.Nq = Nq, c.Ncap = Ncap;
+  c.num_pages = num_pages, c.page_size = page_size, c.max_pages = max_pages, c.stream = static_cast<hipStream_t>(stream);
+  c.append = true;
+  return run_index(c);
+}
+
+int fa_mi355x_mla_indexer(const void* q_idx, const float* weights, const void* kidx_new, void* kidx_cache, float* scores, int* indices,
+                          const int* cache_seqlens, const int* block_table, int B, int HI, int Nq, int topk, int Ncap, int num_pages,
+                          int page_size, int max_pages, int causal, void* stream) {
+  IndexCall c;
+  c.q_idx = q_idx, c.weights = weights, c.kidx_new = kidx_new, c.kidx_cache = kidx_cache, c.scores = scores, c.indices = indices;
+  c.seqlens = cache_seqlens, c.table = block_table, c.B = B, c.HI = HI, c.Nq = Nq, c.topk = topk, c.Ncap = Ncap, c.num_pages = num_pages;
+  c.page_size = page_size, c.max_pages = max_pages, c.causal = causal, c.stream = static_cast<hipStream_t>(stream);
+  c.append = kidx_new != nullptr, c.score = true, c.select = true;
+  return run_index(c);
+}
+
+size_t fa_mi355x_mla_indexer_scores_bytes(int B, int Nq, int Ncap) {
+  return B > 0 && Nq > 0 && Ncap > 0 ? (size_t)B * Nq * Ncap * sizeof(float) : 0;
+}
+
+int fa_mi355x_mla_index_chunks(int B, int HI, int Nq, int Ncap) { return index_policy(B, HI, Nq, Ncap).nchunk; }
 
 }  // extern "C"

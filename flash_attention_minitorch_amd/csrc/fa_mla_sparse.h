@@ -1,5 +1,5 @@
 // Sparse MLA decode (DeepSeek-V3.2 sparse attention, DSA) on the latent KV cache of fa_mla.h, for MI355X (gfx950): every query token
-// brings a list of topk cache positions (an indexer's top-k; the indexer is the caller's) and all heads of that token attend those
+// brings a list of topk cache positions (an indexer's top-k: fa_mla_indexer.h's, or the caller's) and all heads of that token attend those
 // rows alone.  Declared in include/flash_attn_mi355x_mla_sparse.h, dispatched by fa_mla.hip into the same library.  The tile image,
 // its swizzle, MlaStager's lane-to-chunk map, the two fragment readers, the P buffer, the row constants, the partial layout and
 // mla_decode_combine_kernel are fa_mla.h's, used as they are: this header changes no definition of it.
@@ -30,8 +30,8 @@
 //     the key halves' maximum exchange, P as the bf16 hi + lo pair, each wave's 128 output columns for all 64 rows, alpha through
 //     LDS, the final or the partial store.  topk is a multiple of 64: there is no partial tile.
 //
-// Not built: the indexer, a sparse prefill / extend kernel, fp8 latents, other topk granularities than 64, a window, cap or sink
-// beside the indices.
+// Not built: a sparse prefill / extend kernel, fp8 latents, other topk granularities than 64, a window, cap or sink beside the
+// indices.  (The indexer is fa_mla_indexer.h.)
 #pragma once
 #include "fa_mla.h"
 

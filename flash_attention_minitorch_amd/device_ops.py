@@ -2215,3 +2215,145 @@ def flash_attn_decode_mla(q, kv_cache, cache_seqlens, softmax_scale, causal=True
                                                        _ptr(block_table), _ptr(workspace) if nbytes else None, B, H, Nq, Ncap, num_pages,
                                                        page_size, max_pages, float(softmax_scale), int(bool(causal)), _stream_ptr()))
     return out, lse
+
+
+# ---- the lightning indexer of sparse MLA decode (include/flash_attn_mi355x_mla_indexer.h) ---------------------------------------
+# It produces flash_attn_decode_mla's ``indices``: index queries bf16 (B, Nq, HI, 128) and per-head weights fp32 (B, Nq, HI) score every
+# cached index key (bf16 rows of 128 columns, a slab or a pool under the latent cache's block table), and a top-k selection turns a
+# row of scores into an ascending index list.  Checked as the MLA calls are: shapes and dtypes by name, then devices and contiguity.
+_IDX_D = _lib.MLA_INDEX_D
+
+
+def _idx_tensor(t, name, shape_words, rank, dtype=torch.bfloat16, last=_IDX_D):
+    if not isinstance(t, torch.Tensor) or t.dim() != rank or (last is not None and t.shape[-1] != last):
+        raise ValueError(f"{name} must be {shape_words}" + (f": rows of {_IDX_D} columns; other index dims are not built" if last else ""))
+    if t.dtype != dtype:
+        raise TypeError(f"{name} must be {str(dtype).replace('torch.', '')} (got {t.dtype})")
+
+
+def _idx_resident(device, **operands):
+    """Every operand contiguous and on the cache's device, named when it is not; then the device a GPU."""
+    for name, t in operands.items():
+        if t is not None and (t.device != device or not t.is_contiguous()):
+            raise ValueError(f"{name} must be contiguous and on the cache's device")
+    for t in operands.values():
+        if t is not None:
+            _require_gpu(t, "mla_indexer")
+
+
+def _idx_cache(kidx_cache, block_table, B):
+    """(Ncap, num_pages, page_size, max_pages) of an index-key cache: a slab (B, Ncap, 128), or under ``block_table`` a pool."""
+    _idx_tensor(kidx_cache, "kidx_cache", f"(B, Ncap, {_IDX_D}), or a pool (num_pages, page_size, {_IDX_D}) under a block_table", 3)
+    max_pages = _max_pages(block_table, None)
+    if max_pages is None:
+        if kidx_cache.shape[0] != B or kidx_cache.shape[1] < 1:
+            raise ValueError(f"kidx_cache must be (B, Ncap, {_IDX_D}) with B = {B} and Ncap >= 1")
+        return int(kidx_cache.shape[1]), 0, 0, 0
+    num_pages, page_size = int(kidx_cache.shape[0]), int(kidx_cache.shape[1])
+    if num_pages < 1 or page_size < 1 or page_size % _lib.FA_PAGE_ROWS:
+        raise ValueError(f"page_size = {page_size} must be a positive multiple of {_lib.FA_PAGE_ROWS} rows (and the pool hold a page)")
+    _check_table(block_table, B, kidx_cache.device)
+    return max_pages * page_size, num_pages, page_size, max_pages
+
+
+def _idx_new(kidx_new, B, Nq=None):
+    _idx_tensor(kidx_new, "kidx_new", f"(B, Nq, {_IDX_D})", 3)
+    if kidx_new.shape[0] != B or (Nq is not None and kidx_new.shape[1] != Nq):
+        raise ValueError(f"kidx_new must be (B, Nq, {_IDX_D}) with q_idx's B and Nq")
+    if not 1 <= kidx_new.shape[1] <= 128:
+        raise ValueError("Nq must be in 1 .. 128: an indexer for prefill is not built")
+    return int(kidx_new.shape[1])
+
+
+def _idx_queries(q_idx, weights):
+    _idx_tensor(q_idx, "q_idx", f"(B, Nq, HI, {_IDX_D})", 4)
+    B, Nq, HI = (int(x) for x in q_idx.shape[:3])
+    if B < 1 or not 1 <= Nq <= 128 or not 1 <= HI <= _lib.MLA_INDEX_MAX_HEADS:
+        raise ValueError(f"B must be positive, Nq in 1 .. 128 and HI in 1 .. {_lib.MLA_INDEX_MAX_HEADS}")
+    _idx_tensor(weights, "weights", "(B, Nq, HI)", 3, _F32, None)
+    if tuple(weights.shape) != (B, Nq, HI):
+        raise ValueError(f"weights must be (B, Nq, HI) = {(B, Nq, HI)} (got {tuple(weights.shape)}): one weight per index head")
+    return B, Nq, HI
+
+
+def _idx_buffer(t, name, shape, dtype, device):
+    """The caller's output buffer, or a fresh one."""
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != device:
+        raise ValueError(f"{name} must be a contiguous {str(dtype).replace('torch.', '')} tensor of shape {shape} on the cache's device")
+    return t
+
+
+def _idx_score_operands(q_idx, weights, kidx_cache, cache_seqlens, kidx_new, block_table, scores):
+    B, Nq, HI = _idx_queries(q_idx, weights)
+    geom = _idx_cache(kidx_cache, block_table, B)
+    if kidx_new is not None:
+        _idx_new(kidx_new, B, Nq)
+    dev = kidx_cache.device
+    scores = _idx_buffer(scores, "scores", (B, Nq, geom[0]), _F32, dev)
+    _idx_resident(dev, kidx_cache=kidx_cache, q_idx=q_idx, weights=weights, kidx_new=kidx_new)
+    _check_seqlens(cache_seqlens, B, dev)
+    return B, Nq, HI, geom, scores
+
+
+def mla_index_scores(q_idx, weights, kidx_cache, cache_seqlens, causal=True, kidx_new=None, block_table=None, scores=None):
+    """Index scores of the new tokens against every cached index key (fa_mi355x_mla_index_scores): scores[b, i, s] = sum_h
+    weights[b, i, h] * relu(q_idx[b, i, h] . kidx[b, s]) for s < len_b, -inf where s is not admitted (under ``causal``:
+    s > len_b - Nq + i); entries at or past len_b are left as they are.  ``q_idx`` bf16 (B, Nq, HI, 128), ``weights`` fp32 (B, Nq, HI)
+    with HI^-1/2 and the softmax scale folded in, ``kidx_cache`` bf16 (B, Ncap, 128) or with ``block_table`` a pool (num_pages,
+    page_size, 128), ``cache_seqlens`` int32 (B,) on the device.  ``kidx_new`` bf16 (B, Nq, 128): appended first, in the same call
+    (mla_index_append's rule).  Returns ``scores`` fp32 (B, Nq, Ncap) (the caller's buffer, or a fresh one).  No host synchronisation."""
+    B, Nq, HI, (Ncap, num_pages, page_size, max_pages), scores = _idx_score_operands(q_idx, weights, kidx_cache, cache_seqlens, kidx_new,
+                                                                                     block_table, scores)
+    _lib.mla_check(_lib.mla().fa_mi355x_mla_index_scores(
+        _ptr(q_idx), _ptr(weights), _ptr(kidx_new), _ptr(kidx_cache), _ptr(scores), _ptr(cache_seqlens), _ptr(block_table), B, HI, Nq, Ncap,
+        num_pages, page_size, max_pages, int(bool(causal)), _stream_ptr()))
+    return scores
+
+
+def mla_index_topk(scores, cache_seqlens, topk, indices=None):
+    """The index lists of rows of scores (fa_mi355x_mla_index_topk): of scores[b, i, :len_b] fp32 (B, Nq, Ncap) the min(topk, admitted)
+    largest (whatever is not -inf or NaN is admitted; equal scores by position ascending), written to ``indices`` int32 (B, Nq, topk) in
+    ascending position order, the rest -1.  ``topk`` a positive multiple of 64.  A pure function of the score bits."""
+    _idx_tensor(scores, "scores", "(B, Nq, Ncap)", 3, _F32, None)
+    B, Nq, Ncap = (int(x) for x in scores.shape)
+    if B < 1 or not 1 <= Nq <= 128 or Ncap < 1:
+        raise ValueError("scores must be (B, Nq, Ncap) with B and Ncap positive and Nq in 1 .. 128")
+    _mla_topk(topk)
+    indices = _idx_buffer(indices, "indices", (B, Nq, topk), torch.int32, scores.device)
+    _idx_resident(scores.device, scores=scores)
+    _check_seqlens(cache_seqlens, B, scores.device)
+    _lib.mla_check(_lib.mla().fa_mi355x_mla_index_topk(_ptr(scores), _ptr(indices), _ptr(cache_seqlens), B, Nq, Ncap, topk, _stream_ptr()))
+    return indices
+
+
+def mla_index_append(kidx_new, kidx_cache, cache_seqlens, block_table=None):
+    """Append the new tokens' index keys (fa_mi355x_mla_index_append): ``kidx_new`` bf16 (B, Nq, 128); token i of sequence b goes to row
+    cache_seqlens[b] - Nq + i (the lengths COUNT the new tokens), slab or paged.  In place; returns kidx_cache."""
+    if not isinstance(kidx_new, torch.Tensor) or kidx_new.dim() != 3:
+        raise ValueError(f"kidx_new must be (B, Nq, {_IDX_D})")
+    B = int(kidx_new.shape[0])
+    Nq = _idx_new(kidx_new, B)
+    Ncap, num_pages, page_size, max_pages = _idx_cache(kidx_cache, block_table, B)
+    _idx_resident(kidx_cache.device, kidx_cache=kidx_cache, kidx_new=kidx_new)
+    _check_seqlens(cache_seqlens, B, kidx_cache.device)
+    _lib.mla_check(_lib.mla().fa_mi355x_mla_index_append(_ptr(kidx_new), _ptr(kidx_cache), _ptr(cache_seqlens), _ptr(block_table), B, Nq,
+                                                         Ncap, num_pages, page_size, max_pages, _stream_ptr()))
+    return kidx_cache
+
+
+def mla_indexer(q_idx, weights, kidx_cache, cache_seqlens, topk, causal=True, kidx_new=None, block_table=None, scores=None, indices=None):
+    """The whole indexer in one call (fa_mi355x_mla_indexer): mla_index_append (``kidx_new`` given), mla_index_scores and mla_index_topk,
+    bit for bit.  Returns ``indices`` int32 (B, Nq, topk), which flash_attn_decode_mla(indices=) attends; ``scores`` (B, Nq, Ncap) fp32 is
+    the buffer the scores go through (a fresh one when None).  No host synchronisation: the call can be captured in a graph."""
+    _mla_topk(topk)
+    if indices is not None:
+        indices = _idx_buffer(indices, "indices", tuple(q_idx.shape[:2]) + (topk,), torch.int32, getattr(kidx_cache, "device", None))
+    B, Nq, HI, (Ncap, num_pages, page_size, max_pages), scores = _idx_score_operands(q_idx, weights, kidx_cache, cache_seqlens, kidx_new,
+                                                                                     block_table, scores)
+    indices = _idx_buffer(indices, "indices", (B, Nq, topk), torch.int32, kidx_cache.device)
+    _lib.mla_check(_lib.mla().fa_mi355x_mla_indexer(
+        _ptr(q_idx), _ptr(weights), _ptr(kidx_new), _ptr(kidx_cache), _ptr(scores), _ptr(indices), _ptr(cache_seqlens), _ptr(block_table),
+        B, HI, Nq, topk, Ncap, num_pages, page_size, max_pages, int(bool(causal)), _stream_ptr()))
+    return indices

@@ -853,15 +853,21 @@ MLA_LATENT, MLA_ROPE = 512, 64   # c_kv columns and k_pe columns of a cache row 
 # c_kv (512) | k_pe (64, shared by the heads, before its rotation); w_uk (H, dn, 512): k_nope of head h is c_kv . w_uk[h]^T; w_uv
 # (H, 512, dv): v of head h is c_kv . w_uv[h]; wo (H * dv, E).
 MLAWeights = collections.namedtuple("MLAWeights", "wq w_dkv w_uk w_uv wo")
+# The lightning indexer of a DeepSeek-V3.2 sparse layer, in x's dtype: wq_idx (E, HI * 128) gives each of the HI index heads its query,
+# wk_idx (E, 128) the token's one index key, w_head (E, HI) the per-token head weights.
+MLA_INDEX = 128
+IndexerWeights = collections.namedtuple("IndexerWeights", "wq_idx wk_idx w_head")
 
 
 class LatentKVCache:
     """The cache of an MLA stack: per layer ONE row of 576 bf16 columns per token (c_kv | rotated k_pe), shared by all heads.
     ``kv[l]`` is a slab (B, capacity, 576), or with ``page_size`` (a multiple of 128 rows) a pool (n_pages, page_size, 576) read
     through ``block_table`` (B, max_pages) int32, which starts as sequence b owning pages b * max_pages .. and may be rewritten in
-    place.  ``lengths`` int32 (B,) lives on the device; ``advance(n)`` counts n new tokens per sequence without a host round trip."""
+    place.  ``lengths`` int32 (B,) lives on the device; ``advance(n)`` counts n new tokens per sequence without a host round trip.
+    ``index_keys``: the cache also holds the indexer's keys, ``kidx[l]`` bf16 rows of 128 columns in a slab or a pool of the same
+    geometry under the same block table, and the buffers the indexer's scores go through (``index_scores(Nq)``)."""
 
-    def __init__(self, n_layers, B, capacity, device, page_size=None, n_pages=None):
+    def __init__(self, n_layers, B, capacity, device, page_size=None, n_pages=None, index_keys=False):
         if n_layers < 1 or B < 1 or capacity < 1:
             raise ValueError("n_layers, B and capacity must be positive")
         self.capacity, self.block_table = capacity, None
@@ -876,8 +882,9 @@ class LatentKVCache:
             self.block_table = torch.arange(B * max_pages, dtype=torch.int32, device=device).view(B, max_pages)
             shape = (n_pages, page_size, MLA_LATENT + MLA_ROPE)
         self.kv = [torch.zeros(shape, dtype=torch.bfloat16, device=device) for _ in range(n_layers)]
+        self.kidx = [torch.zeros(shape[:2] + (MLA_INDEX,), dtype=torch.bfloat16, device=device) for _ in range(n_layers)] if index_keys else None
         self.lengths = torch.zeros(B, dtype=torch.int32, device=device)
-        self._workspaces = {}
+        self._workspaces, self._scores = {}, {}
 
     def advance(self, n_tokens):
         self.lengths += n_tokens
@@ -888,9 +895,16 @@ class LatentKVCache:
             self._workspaces[key] = device_ops.mla_workspace(q, self.kv[0], self.block_table, topk=topk)
         return self._workspaces[key]
 
+    def index_scores(self, Nq):
+        """The fp32 (B, Nq, logical capacity) buffer of device_ops.mla_indexer's scores, one per Nq, shared by the layers."""
+        if Nq not in self._scores:
+            rows = self.kv[0].shape[1] * (1 if self.block_table is None else self.block_table.shape[1])
+            self._scores[Nq] = torch.empty((self.lengths.shape[0], Nq, rows), dtype=torch.float32, device=self.lengths.device)
+        return self._scores[Nq]
+
 
 def mla_attention_step(x, cache: LatentKVCache, li: int, weights: MLAWeights, n_head: int, rope: Rotary, softmax_scale=None,
-                       indices=None):
+                       indices=None, indexer=None, topk=None):
     """One absorbed MLA step of layer ``li``: x (B, T, E) are the T <= 128 newest tokens of each sequence and ``cache.lengths``
     already COUNTS them (cache.advance(T) once per step, in front of the layers).  (1) down-project: q = x wq, c_kv | k_pe = x w_dkv;
     (2) rotate q_pe and k_pe at the positions lengths - T + i (``rope``: 64 rotary columns); (3) q_lat = q_nope . w_uk per head;
@@ -898,7 +912,17 @@ def mla_attention_step(x, cache: LatentKVCache, li: int, weights: MLAWeights, n_
     (5) out . w_uv per head, then wo.  ``softmax_scale``: (dn + 64) ** -0.5 unless given (a YaRN model passes its own).
     Equal, up to rounding, to un-absorbed attention on k_h = [c_kv . w_uk[h]^T | k_pe], v_h = c_kv . w_uv[h].
     ``indices`` int32 (B, T, topk): DeepSeek-V3.2 sparse attention, token (b, t) attends only the cache positions its list names
-    (device_ops.flash_attn_decode_mla's ``indices``).  The indexer that scores the cache and picks them is the caller's."""
+    (device_ops.flash_attn_decode_mla's ``indices``).  The lists are the caller's, or with ``indexer`` (an IndexerWeights; the cache built
+    with index_keys=True) and ``topk`` (a multiple of 64) the step's own: q_idx = x wq_idx per index head and k_idx = x wk_idx, their
+    first 64 columns rotated at the tokens' positions like q_pe and k_pe, weights = (x w_head) * HI^-1/2 * 128^-1/2 in fp32, and ONE
+    device_ops.mla_indexer call appends k_idx to cache.kidx[li], scores the cache and selects each token's top-k, which the sparse
+    call then attends.  ``indexer`` and ``indices`` together raise.  DeepSeek's LayerNorm on k_idx and its fp8 quantisation of the
+    index keys are not part of this step."""
+    if indexer is not None:
+        if indices is not None:
+            raise ValueError("indexer and indices exclude each other: the step selects the lists, or the caller supplies them")
+        if cache.kidx is None or topk is None:
+            raise ValueError("indexer needs a LatentKVCache built with index_keys=True and topk")
     B, T, _ = x.shape
     wq, w_dkv, w_uk, w_uv, wo = weights
     dn = w_uk.shape[1]
@@ -910,6 +934,13 @@ def mla_attention_step(x, cache: LatentKVCache, li: int, weights: MLAWeights, n_
     q_abs = torch.cat([torch.einsum("bthn,hnc->bthc", q[..., :dn], w_uk), q_pe], -1).contiguous()
     kv_new = torch.cat([kv[..., :MLA_LATENT], k_pe.view(B, T, MLA_ROPE)], -1).contiguous()
     scale = (dn + MLA_ROPE) ** -0.5 if softmax_scale is None else softmax_scale
+    if indexer is not None:
+        HI = indexer.w_head.shape[1]
+        q_idx = rope.apply((x @ indexer.wq_idx).view(B, T, HI, MLA_INDEX), offsets)
+        k_idx = rope.apply((x @ indexer.wk_idx).view(B, T, 1, MLA_INDEX), offsets).view(B, T, MLA_INDEX)
+        w_idx = ((x @ indexer.w_head).float() * (HI ** -0.5 * MLA_INDEX ** -0.5)).contiguous()
+        indices = device_ops.mla_indexer(q_idx, w_idx, cache.kidx[li], cache.lengths, topk, True, k_idx, cache.block_table,
+                                         scores=cache.index_scores(T))
     sparse = {} if indices is None else {"indices": indices}   # (the dense step is the call it was)
     out, _ = device_ops.flash_attn_decode_mla(q_abs, cache.kv[li], cache.lengths, scale, True, kv_new, cache.block_table,
                                               workspace=cache.workspace(q_abs, None if indices is None else int(indices.shape[-1])),

@@ -24,8 +24,8 @@
  * paged: 64-bit global loads, such a row zeroed in registers), with the chain index -> page id -> row -> LDS pipelined in registers
  * over three tiles.  The products, the partial layout and mla_decode_combine_kernel are flash_attn_mi355x_mla.h's.
  *
- * Not built: the indexer (the scorer that produces the top-k: the caller supplies the indices, as it supplies rotary tables), a
- * sparse prefill / extend kernel, fp8 latents, other topk granularities than 64, a window, cap or sink beside the indices.
+ * The indices are the caller's, or the indexer's of flash_attn_mi355x_mla_indexer.h.  Not built: a sparse prefill / extend kernel,
+ * fp8 latents, other topk granularities than 64, a window, cap or sink beside the indices.
  */
 #ifndef FLASH_ATTN_MI355X_MLA_SPARSE_H
 #define FLASH_ATTN_MI355X_MLA_SPARSE_H
