@@ -573,11 +573,19 @@ MLA_INDEXER_ABI = {
     "fa_mi355x_mla_index_chunks": (_i, [_i] * 4),
 }
 MLA_INDEX_D, MLA_INDEX_MAX_HEADS = 128, 128   # columns of an index key (and of an index query); index heads at the most
+# include/flash_attn_mi355x_mla_fp8.h, in the same library: the dense call, the sparse call and the append on an fp8 latent cache of
+# 656-byte rows, each with its bf16 twin's parameter list (tests/test_mla_fp8_cpu.py).  A table of its own.
+MLA_FP8_ABI = {
+    "fa_mi355x_fwd_decode_mla_fp8": MLA_ABI["fa_mi355x_fwd_decode_mla"],
+    "fa_mi355x_fwd_decode_mla_sparse_fp8": MLA_SPARSE_ABI["fa_mi355x_fwd_decode_mla_sparse"],
+    "fa_mi355x_mla_append_fp8": MLA_ABI["fa_mi355x_mla_append"],
+}
+MLA_FP8_ROW_BYTES = 656   # 512 e4m3 codes, four fp32 tile scales, 64 bf16 k_pe columns
 
 
 def mla() -> ctypes.CDLL:
-    """libflash_attn_mi355x_mla.so (include/flash_attn_mi355x_mla.h, ..._mla_sparse.h, ..._mla_indexer.h) with argtypes set."""
-    return _typed(MLA_NAME, {**MLA_ABI, **MLA_SPARSE_ABI, **MLA_INDEXER_ABI})
+    """libflash_attn_mi355x_mla.so (include/flash_attn_mi355x_mla.h, ..._mla_sparse.h, ..._mla_indexer.h, ..._mla_fp8.h) with argtypes set."""
+    return _typed(MLA_NAME, {**MLA_ABI, **MLA_SPARSE_ABI, **MLA_INDEXER_ABI, **MLA_FP8_ABI})
 
 
 def mla_check(status: int) -> None:

@@ -4,7 +4,10 @@
 // The sparse call (include/flash_attn_mi355x_mla_sparse.h, kernel in fa_mla_sparse.h) is an MlaCall with an index list.
 // The indexer that produces such lists (include/flash_attn_mi355x_mla_indexer.h, kernels in fa_mla_indexer.h) fills one IndexCall,
 // which check_index() answers the same way; its chunking is index_policy(), under the split policies.
+// The fp8 latent cache (include/flash_attn_mi355x_mla_fp8.h, kernels in fa_mla_fp8.h) is an MlaCall with the fp8 flag: rows of 656
+// bytes in the bounds and the strides, the fp8 builds in the launches, the same policies.
 #include "../../include/flash_attn_mi355x_mla.h"
+#include "../../include/flash_attn_mi355x_mla_fp8.h"
 #include "../../include/flash_attn_mi355x_mla_indexer.h"
 #include "../../include/flash_attn_mi355x_mla_sparse.h"
 
@@ -14,6 +17,7 @@
 #include <cstdio>
 
 #include "fa_mla.h"
+#include "fa_mla_fp8.h"
 #include "fa_mla_indexer.h"
 #include "fa_mla_sparse.h"
 
@@ -43,6 +47,8 @@ struct MlaCall {
   float softmax_scale = 0.f;
   int causal = 0;
   bool attend = false, append = false, sparse = false;
+  bool fp8 = false;   // the cache holds 656-byte rows (e4m3 codes, tile scales, bf16 k_pe)
+  long row_bytes() const { return fp8 ? fa::MLA_FP8_ROW_BYTES : fa::MLA_ROW_BYTES; }
   hipStream_t stream = nullptr;
 };
 
@@ -134,14 +140,14 @@ int check(MlaCall& c, Policy* out) {
     }
     if ((long)c.max_pages * c.page_size + MLA_SUPER > 0x7fffffffL)
       return set_err(FA_ERR_BAD_ARG, "max_pages * page_size (the logical capacity) must fit an int");
-    if ((long)c.page_size * fa::MLA_ROW_BYTES >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "one page of the pool must stay under 2 GiB");
+    if ((long)c.page_size * c.row_bytes() >= (1L << 31)) return set_err(FA_ERR_BAD_ARG, "one page of the pool must stay under 2 GiB");
     if (c.sparse && (long)c.num_pages * c.page_size >= (1L << 31))
       return set_err(FA_ERR_BAD_ARG, "num_pages * page_size (the pool's rows) must stay under 2^31 for the sparse call");
     c.Ncap = c.max_pages * c.page_size;
   } else {
     if (c.Ncap <= 0) return set_err(FA_ERR_BAD_ARG, "Ncap must be positive");
     // (a buffer load's row offset is a 32-bit byte count: a slab, plus a tile of rows past its end)
-    if (((long)c.Ncap + fa::MLA_TILE) * fa::MLA_ROW_BYTES >= (1L << 31))
+    if (((long)c.Ncap + fa::MLA_TILE) * c.row_bytes() >= (1L << 31))
       return set_err(FA_ERR_BAD_ARG, "one batch element of the cache must stay under 2 GiB");
   }
   if (!c.kv_cache) return set_err(FA_ERR_BAD_ARG, "null pointer argument: kv_cache");
@@ -182,9 +188,14 @@ int launch_append(const MlaCall& c) {
   a.table = c.table;
   a.lanes = (long)c.B * c.Nq * fa::MlaStager::CPR;
   a.Nq = c.Nq, a.Ncap = c.Ncap, a.page_size = c.page_size, a.num_pages = c.num_pages, a.max_pages = c.max_pages;
-  hipLaunchKernelGGL(fa::mla_append_kernel, dim3((unsigned)((a.lanes + 255) / 256)), dim3(256), 0, c.stream, a);
+  if (c.fp8) {   // (a wave per new row, four to a workgroup: `lanes` counts rows)
+    a.lanes = (long)c.B * c.Nq;
+    hipLaunchKernelGGL(fa::mla_fp8_append_kernel, dim3((unsigned)((a.lanes + 3) / 4)), dim3(256), 0, c.stream, a);
+  } else {
+    hipLaunchKernelGGL(fa::mla_append_kernel, dim3((unsigned)((a.lanes + 255) / 256)), dim3(256), 0, c.stream, a);
+  }
   const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? FA_OK : hip_err("mla_append_kernel launch", e);
+  return e == hipSuccess ? FA_OK : hip_err(c.fp8 ? "mla_fp8_append_kernel launch" : "mla_append_kernel launch", e);
 }
 
 int launch_attend(const MlaCall& c, const Policy& p) {
@@ -199,24 +210,29 @@ int launch_attend(const MlaCall& c, const Policy& p) {
   a.nsplit = p.nsplit, a.chunk = p.chunk, a.nqb = (int)p.nqb, a.items = (int)p.items;
   a.inv_G = 1.0f / (float)c.H;
   a.q_ld = c.H * D, a.q_hstride = D, a.q_bstride = (long)c.Nq * c.H * D;
-  a.kv_ld = D, a.kv_hstride = 0, a.kv_bstride = (long)c.Ncap * D;
+  const int KD = (int)(c.row_bytes() / 2);   // a cache row in the 2-byte units of the argument's strides: 576, or 328 for fp8
+  a.kv_ld = KD, a.kv_hstride = 0, a.kv_bstride = (long)c.Ncap * KD;
   a.causal = c.causal ? 1 : 0;
   a.tau = c.softmax_scale;
   a.table = c.table;
   a.page_size = c.page_size, a.num_pages = c.num_pages, a.max_pages = c.max_pages;
-  a.page_stride = (long)c.page_size * D;
+  a.page_stride = (long)c.page_size * KD;
   const unsigned grid = (unsigned)split_grid(p.items, p.nqb);
   hipError_t e;
   if (c.sparse) {   // (the same argument and the list; G = H is not read: a block's rows are heads of one token)
     fa::MlaSparseArgs sa{};
     static_cast<fa::DecodeArgs&>(sa) = a;
     sa.indices = c.indices, sa.topk = c.topk;
-    if (c.table) hipLaunchKernelGGL(fa::mla_sparse_split_kernel<true>, dim3(grid), dim3(256), 0, c.stream, sa);
+    if (c.fp8 && c.table) hipLaunchKernelGGL(fa::mla_fp8_sparse_split_kernel<true>, dim3(grid), dim3(256), 0, c.stream, sa);
+    else if (c.fp8) hipLaunchKernelGGL(fa::mla_fp8_sparse_split_kernel<false>, dim3(grid), dim3(256), 0, c.stream, sa);
+    else if (c.table) hipLaunchKernelGGL(fa::mla_sparse_split_kernel<true>, dim3(grid), dim3(256), 0, c.stream, sa);
     else hipLaunchKernelGGL(fa::mla_sparse_split_kernel<false>, dim3(grid), dim3(256), 0, c.stream, sa);
     e = hipGetLastError();
     if (e != hipSuccess) return hip_err("mla_sparse_split_kernel launch", e);
   } else {
-    if (c.table) hipLaunchKernelGGL(fa::mla_decode_split_kernel<true>, dim3(grid), dim3(256), 0, c.stream, a);
+    if (c.fp8 && c.table) hipLaunchKernelGGL(fa::mla_fp8_split_kernel<true>, dim3(grid), dim3(256), 0, c.stream, a);
+    else if (c.fp8) hipLaunchKernelGGL(fa::mla_fp8_split_kernel<false>, dim3(grid), dim3(256), 0, c.stream, a);
+    else if (c.table) hipLaunchKernelGGL(fa::mla_decode_split_kernel<true>, dim3(grid), dim3(256), 0, c.stream, a);
     else hipLaunchKernelGGL(fa::mla_decode_split_kernel<false>, dim3(grid), dim3(256), 0, c.stream, a);
     e = hipGetLastError();
     if (e != hipSuccess) return hip_err("mla_decode_split_kernel launch", e);
@@ -344,10 +360,11 @@ extern "C" {
 
 const char* fa_mi355x_mla_last_error(void) { return g_err; }
 
-int fa_mi355x_fwd_decode_mla(const void* q, const void* kv_new, void* kv_cache, float* out, float* lse, const int* cache_seqlens,
-                             const int* block_table, void* workspace, int B, int H, int Nq, int Ncap, int num_pages, int page_size,
-                             int max_pages, float softmax_scale, int causal, void* stream) {
+static int decode_mla(bool fp8, const void* q, const void* kv_new, void* kv_cache, float* out, float* lse, const int* cache_seqlens,
+                      const int* block_table, void* workspace, int B, int H, int Nq, int Ncap, int num_pages, int page_size,
+                      int max_pages, float softmax_scale, int causal, void* stream) {
   MlaCall c;
+  c.fp8 = fp8;
   c.q = q, c.kv_new = kv_new, c.kv_cache = kv_cache, c.out = out, c.lse = lse, c.seqlens = cache_seqlens, c.table = block_table;
   c.workspace = workspace, c.B = B, c.H = H, c.Nq = Nq, c.Ncap = Ncap, c.num_pages = num_pages, c.page_size = page_size;
   c.max_pages = max_pages, c.softmax_scale = softmax_scale, c.causal = causal, c.stream = static_cast<hipStream_t>(stream);
@@ -355,11 +372,25 @@ int fa_mi355x_fwd_decode_mla(const void* q, const void* kv_new, void* kv_cache, 
   return run(c);
 }
 
-int fa_mi355x_fwd_decode_mla_sparse(const void* q, const void* kv_new, void* kv_cache, const int* indices, float* out, float* lse,
-                                    const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Nq, int topk,
-                                    int Ncap, int num_pages, int page_size, int max_pages, float softmax_scale, int causal,
-                                    void* stream) {
+int fa_mi355x_fwd_decode_mla(const void* q, const void* kv_new, void* kv_cache, float* out, float* lse, const int* cache_seqlens,
+                             const int* block_table, void* workspace, int B, int H, int Nq, int Ncap, int num_pages, int page_size,
+                             int max_pages, float softmax_scale, int causal, void* stream) {
+  return decode_mla(false, q, kv_new, kv_cache, out, lse, cache_seqlens, block_table, workspace, B, H, Nq, Ncap, num_pages, page_size,
+                    max_pages, softmax_scale, causal, stream);
+}
+
+int fa_mi355x_fwd_decode_mla_fp8(const void* q, const void* kv_new, void* kv_cache, float* out, float* lse, const int* cache_seqlens,
+                                 const int* block_table, void* workspace, int B, int H, int Nq, int Ncap, int num_pages, int page_size,
+                                 int max_pages, float softmax_scale, int causal, void* stream) {
+  return decode_mla(true, q, kv_new, kv_cache, out, lse, cache_seqlens, block_table, workspace, B, H, Nq, Ncap, num_pages, page_size,
+                    max_pages, softmax_scale, causal, stream);
+}
+
+static int decode_mla_sparse(bool fp8, const void* q, const void* kv_new, void* kv_cache, const int* indices, float* out, float* lse,
+                             const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Nq, int topk,
+                             int Ncap, int num_pages, int page_size, int max_pages, float softmax_scale, int causal, void* stream) {
   MlaCall c;
+  c.fp8 = fp8;
   c.q = q, c.kv_new = kv_new, c.kv_cache = kv_cache, c.out = out, c.lse = lse, c.seqlens = cache_seqlens, c.table = block_table;
   c.workspace = workspace, c.B = B, c.H = H, c.Nq = Nq, c.Ncap = Ncap, c.num_pages = num_pages, c.page_size = page_size;
   c.max_pages = max_pages, c.softmax_scale = softmax_scale, c.causal = causal, c.stream = static_cast<hipStream_t>(stream);
@@ -368,13 +399,40 @@ int fa_mi355x_fwd_decode_mla_sparse(const void* q, const void* kv_new, void* kv_
   return run(c);
 }
 
-int fa_mi355x_mla_append(const void* kv_new, void* kv_cache, const int* cache_seqlens, const int* block_table, int B, int Nq, int Ncap,
-                         int num_pages, int page_size, int max_pages, void* stream) {
+int fa_mi355x_fwd_decode_mla_sparse(const void* q, const void* kv_new, void* kv_cache, const int* indices, float* out, float* lse,
+                                    const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Nq, int topk,
+                                    int Ncap, int num_pages, int page_size, int max_pages, float softmax_scale, int causal,
+                                    void* stream) {
+  return decode_mla_sparse(false, q, kv_new, kv_cache, indices, out, lse, cache_seqlens, block_table, workspace, B, H, Nq, topk, Ncap,
+                           num_pages, page_size, max_pages, softmax_scale, causal, stream);
+}
+
+int fa_mi355x_fwd_decode_mla_sparse_fp8(const void* q, const void* kv_new, void* kv_cache, const int* indices, float* out, float* lse,
+                                        const int* cache_seqlens, const int* block_table, void* workspace, int B, int H, int Nq,
+                                        int topk, int Ncap, int num_pages, int page_size, int max_pages, float softmax_scale,
+                                        int causal, void* stream) {
+  return decode_mla_sparse(true, q, kv_new, kv_cache, indices, out, lse, cache_seqlens, block_table, workspace, B, H, Nq, topk, Ncap,
+                           num_pages, page_size, max_pages, softmax_scale, causal, stream);
+}
+
+static int mla_append(bool fp8, const void* kv_new, void* kv_cache, const int* cache_seqlens, const int* block_table, int B, int Nq,
+                      int Ncap, int num_pages, int page_size, int max_pages, void* stream) {
   MlaCall c;
+  c.fp8 = fp8;
   c.kv_new = kv_new, c.kv_cache = kv_cache, c.seqlens = cache_seqlens, c.table = block_table, c.B = B, c.Nq = Nq, c.Ncap = Ncap;
   c.num_pages = num_pages, c.page_size = page_size, c.max_pages = max_pages, c.stream = static_cast<hipStream_t>(stream);
   c.append = true;
   return run(c);
+}
+
+int fa_mi355x_mla_append(const void* kv_new, void* kv_cache, const int* cache_seqlens, const int* block_table, int B, int Nq, int Ncap,
+                         int num_pages, int page_size, int max_pages, void* stream) {
+  return mla_append(false, kv_new, kv_cache, cache_seqlens, block_table, B, Nq, Ncap, num_pages, page_size, max_pages, stream);
+}
+
+int fa_mi355x_mla_append_fp8(const void* kv_new, void* kv_cache, const int* cache_seqlens, const int* block_table, int B, int Nq,
+                             int Ncap, int num_pages, int page_size, int max_pages, void* stream) {
+  return mla_append(true, kv_new, kv_cache, cache_seqlens, block_table, B, Nq, Ncap, num_pages, page_size, max_pages, stream);
 }
 
 int fa_mi355x_decode_mla_splits(int B, int H, int Nq, int Ncap) { return query(B, H, Nq, Ncap).nsplit; }

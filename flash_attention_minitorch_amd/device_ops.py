@@ -2066,6 +2066,10 @@ def flash_attn_local(q, k, v, window, softmax_scale=None):
 # q_nope . W_UK in columns 0..511 and the rotated q_pe in 512..575; out has the 512 latent columns.  Shapes and dtypes are checked by
 # name first, then devices and contiguity, then the library is called.
 _MLA_QK, _MLA_V = _lib.MLA_D_QK, _lib.MLA_D_V
+# An fp8 latent cache (include/flash_attn_mi355x_mla_fp8.h) is a torch.uint8 tensor with rows of 656 bytes: 512 e4m3fn codes, four fp32
+# power-of-two scales (one per 128 columns), the 64 k_pe columns as bf16.  The three calls below take their fp8 path on such a cache;
+# q and kv_new stay bf16.
+_MLA_FP8_ROW = _lib.MLA_FP8_ROW_BYTES
 
 
 def _mla_tensor(t, name, shape_words, rank):
@@ -2074,6 +2078,19 @@ def _mla_tensor(t, name, shape_words, rank):
         raise ValueError(f"{name} must be {shape_words}: rows of {_MLA_QK} columns (c_kv 512 | k_pe 64); other latent widths are not built")
     if t.dtype != torch.bfloat16:
         raise TypeError(f"{name} must be bfloat16 (got {t.dtype}): the MLA kernels are built for bf16 alone")
+
+
+def _mla_fp8(kv_cache):
+    """True for an fp8 latent cache, a uint8 tensor, whose shape and contiguity are checked by name here."""
+    if not isinstance(kv_cache, torch.Tensor) or kv_cache.dtype != torch.uint8:
+        return False
+    if kv_cache.dim() != 3 or kv_cache.shape[-1] != _MLA_FP8_ROW:
+        raise ValueError(f"a uint8 kv_cache is an fp8 latent cache and must be (B, Ncap, {_MLA_FP8_ROW}), or a pool (num_pages, page_size, "
+                         f"{_MLA_FP8_ROW}) under a block_table: rows of {_MLA_FP8_ROW} bytes (512 e4m3 codes | 4 fp32 scales | k_pe 64 bf16); "
+                         f"got {tuple(kv_cache.shape)}")
+    if not kv_cache.is_contiguous():
+        raise ValueError(f"kv_cache must be contiguous: an fp8 latent cache is a byte array of {_MLA_FP8_ROW}-byte rows")
+    return True
 
 
 def _mla_resident(t, name, device):
@@ -2085,11 +2102,12 @@ def _mla_resident(t, name, device):
 def _mla_cache(kv_cache, block_table, B, max_pages=None):
     """(Ncap, num_pages, page_size, max_pages) of a latent cache: a slab (B, Ncap, 576), or with ``block_table`` (or ``max_pages``, for
     the size query) a pool (num_pages, page_size, 576) of logical capacity max_pages * page_size."""
-    _mla_tensor(kv_cache, "kv_cache", f"(B, Ncap, {_MLA_QK}), or a pool (num_pages, page_size, {_MLA_QK}) under a block_table", 3)
+    if not _mla_fp8(kv_cache):
+        _mla_tensor(kv_cache, "kv_cache", f"(B, Ncap, {_MLA_QK}), or a pool (num_pages, page_size, {_MLA_QK}) under a block_table", 3)
     max_pages = _max_pages(block_table, max_pages)
     if max_pages is None:
         if kv_cache.shape[0] != B or kv_cache.shape[1] < 1:
-            raise ValueError(f"kv_cache must be (B, Ncap, {_MLA_QK}) with B = {B} and Ncap >= 1")
+            raise ValueError(f"kv_cache must be (B, Ncap, {kv_cache.shape[2]}) with B = {B} and Ncap >= 1")
         return int(kv_cache.shape[1]), 0, 0, 0
     num_pages, page_size = int(kv_cache.shape[0]), int(kv_cache.shape[1])
     if num_pages < 1 or page_size < 1 or page_size % _lib.FA_PAGE_ROWS:
@@ -2154,7 +2172,9 @@ def mla_workspace(q, kv_cache, block_table=None, max_pages=None, topk=None):
 
 def mla_append(kv_new, kv_cache, cache_seqlens, block_table=None):
     """Append the new tokens' latent rows (fa_mi355x_mla_append): ``kv_new`` bf16 (B, Nq, 576); token i of sequence b goes to row
-    cache_seqlens[b] - Nq + i (the lengths COUNT the new tokens), slab or paged.  In place; returns kv_cache."""
+    cache_seqlens[b] - Nq + i (the lengths COUNT the new tokens), slab or paged.  In place; returns kv_cache.  Into an fp8 latent cache
+    (torch.uint8, rows of 656 bytes) the rows are quantised on the way (fa_mi355x_mla_append_fp8): per 128-column tile the smallest
+    power-of-two scale that holds the tile's maximum in e4m3's range, k_pe copied."""
     if not isinstance(kv_new, torch.Tensor) or kv_new.dim() != 3:
         raise ValueError(f"kv_new must be (B, Nq, {_MLA_QK})")
     B = int(kv_new.shape[0])
@@ -2163,8 +2183,9 @@ def mla_append(kv_new, kv_cache, cache_seqlens, block_table=None):
     _mla_resident(kv_cache, "kv_cache", kv_cache.device)
     _mla_resident(kv_new, "kv_new", kv_cache.device)
     _check_seqlens(cache_seqlens, B, kv_cache.device)
-    _lib.mla_check(_lib.mla().fa_mi355x_mla_append(_ptr(kv_new), _ptr(kv_cache), _ptr(cache_seqlens), _ptr(block_table), B, Nq, Ncap,
-                                                   num_pages, page_size, max_pages, _stream_ptr()))
+    append = _lib.mla().fa_mi355x_mla_append_fp8 if kv_cache.dtype is torch.uint8 else _lib.mla().fa_mi355x_mla_append
+    _lib.mla_check(append(_ptr(kv_new), _ptr(kv_cache), _ptr(cache_seqlens), _ptr(block_table), B, Nq, Ncap,
+                          num_pages, page_size, max_pages, _stream_ptr()))
     return kv_cache
 
 
@@ -2180,7 +2201,10 @@ def flash_attn_decode_mla(q, kv_cache, cache_seqlens, softmax_scale, causal=True
     ``indices`` int32 (B, Nq, topk), topk a multiple of 64: the sparse call (fa_mi355x_fwd_decode_mla_sparse; DeepSeek-V3.2 DSA).
     Query token (b, i) attends, in all its heads, only the positions its list names; an entry j counts iff 0 <= j < len_b (and
     j <= len_b - Nq + i under ``causal``), any other value (-1 padding) is an entry that is not there, and a position named twice
-    counts twice.  A query without an admitted entry gives out = 0 and lse = -inf.  (``workspace``: mla_workspace(..., topk=topk).)"""
+    counts twice.  A query without an admitted entry gives out = 0 and lse = -inf.  (``workspace``: mla_workspace(..., topk=topk).)
+    ``kv_cache`` torch.uint8 with rows of 656 bytes: an fp8 latent cache (fa_mi355x_fwd_decode_mla_fp8, ..._sparse_fp8; the format is
+    include/flash_attn_mi355x_mla_fp8.h's).  The result is bit for bit the bf16 call's on the dequantised cache; ``kv_new`` stays bf16
+    and is quantised on its way in."""
     B, Nq, H = _mla_q(q)
     if not isinstance(softmax_scale, numbers.Real) or not softmax_scale > 0 or not math.isfinite(softmax_scale):
         raise ValueError("softmax_scale is required, positive and finite: the absorbed width 576 is not the model's head dim")
@@ -2205,15 +2229,17 @@ def flash_attn_decode_mla(q, kv_cache, cache_seqlens, softmax_scale, causal=True
         workspace = torch.empty(nbytes // 4, dtype=_F32, device=dev) if nbytes else None
     elif nbytes:
         _check_workspace(workspace, nbytes, q.get_device(), "mla_workspace(q, kv_cache, block_table)")
+    fp8 = "_fp8" if kv_cache.dtype is torch.uint8 else ""
     if indices is not None:
-        _lib.mla_check(_lib.mla().fa_mi355x_fwd_decode_mla_sparse(
+        _lib.mla_check(getattr(_lib.mla(), "fa_mi355x_fwd_decode_mla_sparse" + fp8)(
             _ptr(q), _ptr(kv_new), _ptr(kv_cache), _ptr(indices), _ptr(out), _ptr(lse), _ptr(cache_seqlens), _ptr(block_table),
             _ptr(workspace) if nbytes else None, B, H, Nq, topk, Ncap, num_pages, page_size, max_pages, float(softmax_scale),
             int(bool(causal)), _stream_ptr()))
         return out, lse
-    _lib.mla_check(_lib.mla().fa_mi355x_fwd_decode_mla(_ptr(q), _ptr(kv_new), _ptr(kv_cache), _ptr(out), _ptr(lse), _ptr(cache_seqlens),
-                                                       _ptr(block_table), _ptr(workspace) if nbytes else None, B, H, Nq, Ncap, num_pages,
-                                                       page_size, max_pages, float(softmax_scale), int(bool(causal)), _stream_ptr()))
+    _lib.mla_check(getattr(_lib.mla(), "fa_mi355x_fwd_decode_mla" + fp8)(
+        _ptr(q), _ptr(kv_new), _ptr(kv_cache), _ptr(out), _ptr(lse), _ptr(cache_seqlens), _ptr(block_table),
+        _ptr(workspace) if nbytes else None, B, H, Nq, Ncap, num_pages, page_size, max_pages, float(softmax_scale), int(bool(causal)),
+        _stream_ptr()))
     return out, lse
 
 

@@ -865,9 +865,11 @@ class LatentKVCache:
     through ``block_table`` (B, max_pages) int32, which starts as sequence b owning pages b * max_pages .. and may be rewritten in
     place.  ``lengths`` int32 (B,) lives on the device; ``advance(n)`` counts n new tokens per sequence without a host round trip.
     ``index_keys``: the cache also holds the indexer's keys, ``kidx[l]`` bf16 rows of 128 columns in a slab or a pool of the same
-    geometry under the same block table, and the buffers the indexer's scores go through (``index_scores(Nq)``)."""
+    geometry under the same block table, and the buffers the indexer's scores go through (``index_scores(Nq)``).
+    ``fp8``: the rows are the 656 bytes of an fp8 latent cache (torch.uint8: 512 e4m3 codes, four fp32 tile scales, k_pe as bf16;
+    include/flash_attn_mi355x_mla_fp8.h), which the same device_ops calls quantise into and read; the index keys stay bf16."""
 
-    def __init__(self, n_layers, B, capacity, device, page_size=None, n_pages=None, index_keys=False):
+    def __init__(self, n_layers, B, capacity, device, page_size=None, n_pages=None, index_keys=False, fp8=False):
         if n_layers < 1 or B < 1 or capacity < 1:
             raise ValueError("n_layers, B and capacity must be positive")
         self.capacity, self.block_table = capacity, None
@@ -881,7 +883,10 @@ class LatentKVCache:
                 raise ValueError("n_pages must hold max_pages pages for every sequence")
             self.block_table = torch.arange(B * max_pages, dtype=torch.int32, device=device).view(B, max_pages)
             shape = (n_pages, page_size, MLA_LATENT + MLA_ROPE)
-        self.kv = [torch.zeros(shape, dtype=torch.bfloat16, device=device) for _ in range(n_layers)]
+        if fp8:
+            self.kv = [torch.zeros(shape[:2] + (_lib.MLA_FP8_ROW_BYTES,), dtype=torch.uint8, device=device) for _ in range(n_layers)]
+        else:
+            self.kv = [torch.zeros(shape, dtype=torch.bfloat16, device=device) for _ in range(n_layers)]
         self.kidx = [torch.zeros(shape[:2] + (MLA_INDEX,), dtype=torch.bfloat16, device=device) for _ in range(n_layers)] if index_keys else None
         self.lengths = torch.zeros(B, dtype=torch.int32, device=device)
         self._workspaces, self._scores = {}, {}

@@ -23,10 +23,10 @@
  * and every wave multiplies it into its own 128 of the 512 output columns for all 64 rows (64 MFMAs): no MFMA is issued twice.
  * Several key chunks leave (o[512], m, l) partials that mla_decode_combine_kernel merges in split order.
  *
- * Not built: a sliding window, sink tokens, a soft cap, learned sink logits, fp8 latents, the ragged family, an extend kernel for
+ * Not built: a sliding window, sink tokens, a soft cap, learned sink logits, the ragged family, an extend kernel for
  * long prefills (a prompt is prefilled un-absorbed, as ordinary attention), other latent widths, the training backward.
  * (Sparse attention over per-query index lists, DeepSeek-V3.2 DSA, is in this library under a header of its own:
- * flash_attn_mi355x_mla_sparse.h.)
+ * flash_attn_mi355x_mla_sparse.h; an fp8 latent cache under flash_attn_mi355x_mla_fp8.h.)
  */
 #ifndef FLASH_ATTN_MI355X_MLA_H
 #define FLASH_ATTN_MI355X_MLA_H

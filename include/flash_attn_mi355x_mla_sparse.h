@@ -25,7 +25,7 @@
  * over three tiles.  The products, the partial layout and mla_decode_combine_kernel are flash_attn_mi355x_mla.h's.
  *
  * The indices are the caller's, or the indexer's of flash_attn_mi355x_mla_indexer.h.  Not built: a sparse prefill / extend kernel,
- * fp8 latents, other topk granularities than 64, a window, cap or sink beside the indices.
+ * other topk granularities than 64, a window, cap or sink beside the indices.
  */
 #ifndef FLASH_ATTN_MI355X_MLA_SPARSE_H
 #define FLASH_ATTN_MI355X_MLA_SPARSE_H
