@@ -34,6 +34,9 @@ kernel_lib fa_lsink  _lsink      # learned sink logits in training: the forward 
 # multi-head latent attention decode on a latent KV cache (include/flash_attn_mi355x_mla.h).  The whole library is built without packed
 # fp32 instructions, a target feature (the host pass does not know it and says that it ignores it).
 ( FLAGS+=(-Xclang -target-feature -Xclang -packed-fp32-ops); kernel_lib fa_mla _mla )
+# ... and its prompt half, causal packed attention at 192 score and 128 value columns (include/flash_attn_mi355x_mla_prefill.h): a
+# library of its own, under the common flags, so that the decode library's code object and flags stay what they are.
+( kernel_lib fa_mla_prefill _mla_prefill )
 
 shim() {  # name variant FW|BW
   "$HIPCC" -O2 -fPIC -shared -x c++ "$SRC/fa_shim.cpp" -DFA_SHIM_VARIANT="$2" -DFA_SHIM_"$3" \

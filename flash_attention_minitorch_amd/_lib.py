@@ -591,3 +591,25 @@ def mla() -> ctypes.CDLL:
 def mla_check(status: int) -> None:
     if status != FA_OK:
         _raise(status, mla(), "fa_mi355x_mla_last_error", "flash_attn_mi355x_mla")
+
+
+# the same for include/flash_attn_mi355x_mla_prefill.h: libflash_attn_mi355x_mla_prefill.so, the prompt half of MLA: causal packed
+# attention at 192 score columns (k_nope 128 per head | k_pe 64 per token) and 128 value columns under the two arrays of PREFIX_ABI,
+# k_nope and v with a row stride and a head stride each (tests/test_mla_prefill_cpu.py)
+MLA_PREFILL_ABI = {
+    "fa_mi355x_fwd_mla_prefill_workspace_bytes": (_sz, [_i] * 4),
+    "fa_mi355x_fwd_mla_prefill": (_i, [_vp] * 9 + [_i] * 8 + [_f, _vp]),
+    "fa_mi355x_mla_prefill_last_error": (_s, []),
+}
+MLA_PREFILL_NAME = "libflash_attn_mi355x_mla_prefill.so"
+MLA_PREFILL_D_NOPE, MLA_PREFILL_D_ROPE, MLA_PREFILL_D_V = 128, 64, 128   # columns of k_nope, of k_pe (q has both) and of v (and out)
+
+
+def mla_prefill() -> ctypes.CDLL:
+    """libflash_attn_mi355x_mla_prefill.so (include/flash_attn_mi355x_mla_prefill.h) with argtypes set."""
+    return _typed(MLA_PREFILL_NAME, MLA_PREFILL_ABI)
+
+
+def mla_prefill_check(status: int) -> None:
+    if status != FA_OK:
+        _raise(status, mla_prefill(), "fa_mi355x_mla_prefill_last_error", "flash_attn_mi355x_mla_prefill")

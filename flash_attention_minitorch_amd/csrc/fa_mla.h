@@ -27,8 +27,8 @@
 //     and a paged call returns the slab call's bits on the gathered cache.  Resources end at len_b or at the page.
 // mla_append_kernel: token i of batch element b goes to row len_b - Nq + i, slab or paged, in 16-byte moves.
 //
-// Not built: window, sink tokens, soft cap, learned sink logits, the ragged family, an extend kernel for long prefills,
-// other latent widths, the training backward.  (Attention over per-query index lists, DeepSeek-V3.2's sparse attention, is a kernel
+// Not built: window, sink tokens, soft cap, learned sink logits, the ragged family, other latent widths, the training backward.
+// (A prompt is prefilled before absorption by a kernel of its own: fa_mla_prefill.h.  Attention over per-query index lists, DeepSeek-V3.2's sparse attention, is a kernel
 // of its own on this image and these products: fa_mla_sparse.h.  An fp8 latent cache: fa_mla_fp8.h.)
 #pragma once
 #include "fa_atoms.h"

@@ -2383,3 +2383,101 @@ def mla_indexer(q_idx, weights, kidx_cache, cache_seqlens, topk, causal=True, ki
         _ptr(q_idx), _ptr(weights), _ptr(kidx_new), _ptr(kidx_cache), _ptr(scores), _ptr(indices), _ptr(cache_seqlens), _ptr(block_table),
         B, HI, Nq, topk, Ncap, num_pages, page_size, max_pages, int(bool(causal)), _stream_ptr()))
     return indices
+
+
+# ---- MLA prefill: the prompt half, before absorption (include/flash_attn_mi355x_mla_prefill.h) --------------------------------------
+# Causal packed attention whose head has 192 score columns and 128 value columns, on the tensors an MLA layer has: q bf16 (Tq, H, 192)
+# = q_nope | rotated q_pe, k_nope and v bf16 (Tk, H, 128), k_pe bf16 (Tk, 64), one rotated vector per token that every head reads.
+# The two arrays are flash_attn_varlen_prefix_fwd's: the queries of a sequence are the last positions of its keys.  A kernel of its
+# own (libflash_attn_mi355x_mla_prefill.so); checked as the MLA calls are, by name, before the library is called.
+_MLAP_N, _MLAP_R, _MLAP_V = _lib.MLA_PREFILL_D_NOPE, _lib.MLA_PREFILL_D_ROPE, _lib.MLA_PREFILL_D_V
+
+
+def _mlap_tensor(t, name, shape, words):
+    """A bf16 operand of the prefill call: its rank and last dimension, then its dtype."""
+    if not isinstance(t, torch.Tensor) or t.dim() != len(shape) or t.shape[-1] != shape[-1]:
+        raise ValueError(f"{name} must be {words}; other head shapes are not built")
+    if t.dtype != torch.bfloat16:
+        raise TypeError(f"{name} must be bfloat16 (got {t.dtype}): the MLA prefill kernel is built for bf16 alone")
+
+
+def _mlap_strided(t, name, Tk, H):
+    """(row stride, head stride) of k_nope or v, which may be a view (of the up-projection's output, say)."""
+    if tuple(t.shape[:2]) != (Tk, H):
+        raise ValueError(f"{name} must be (Tk, H, {t.shape[-1]}) with k_pe's Tk = {Tk} and q's H = {H}")
+    ld, hs, inner = (int(s) for s in t.stride())
+    hs = hs if H > 1 else max(hs, int(t.shape[-1]))   # (a dimension of one element may carry any stride)
+    if inner != 1 or ld % 8 or hs % 8 or hs < t.shape[-1] or ld < (H - 1) * hs + t.shape[-1] or t.data_ptr() % 16:
+        raise ValueError(f"{name} may be a view, but its last dimension must be contiguous, its row and head strides multiples of 8 "
+                         f"elements that keep heads and rows apart, and its first element 16-byte aligned (strides {tuple(t.stride())})")
+    return ld, hs
+
+
+def _mlap_operands(q, k_nope, k_pe=None, v=None):
+    """(Tq, Tk, H) of the call's operands; the size query passes q and k_nope alone."""
+    _mlap_tensor(q, "q", (0, 0, _MLAP_N + _MLAP_R), f"(Tq, H, {_MLAP_N + _MLAP_R}): q_nope {_MLAP_N} | rotated q_pe {_MLAP_R}")
+    _mlap_tensor(k_nope, "k_nope", (0, 0, _MLAP_N), f"(Tk, H, {_MLAP_N})")
+    Tq, H, Tk = int(q.shape[0]), int(q.shape[1]), int(k_nope.shape[0])
+    if Tq < 1 or Tk < 1 or H < 1:
+        raise ValueError("the packed batch is empty: Tq, Tk and H must be at least 1")
+    if k_pe is not None:
+        _mlap_tensor(k_pe, "k_pe", (0, _MLAP_R), f"(Tk, {_MLAP_R}): one rotated vector per token, shared by the heads")
+        _mlap_tensor(v, "v", (0, 0, _MLAP_V), f"(Tk, H, {_MLAP_V})")
+        if k_pe.shape[0] != Tk:
+            raise ValueError(f"k_pe must have k_nope's {Tk} rows, not {k_pe.shape[0]}")
+    return Tq, Tk, H
+
+
+def mla_prefill_workspace(q, k_nope, cu_seqlens_q, cu_seqlens_k=None):
+    """Scratch for flash_attn_mla_prefill on these shapes (fa_mi355x_fwd_mla_prefill_workspace_bytes): the query-block map.  A pure
+    function of the SHAPES (the arrays' contents are not read): allocate once, reuse every call."""
+    Tq, Tk, H = _mlap_operands(q, k_nope)
+    _check_cu(cu_seqlens_q, None, q.device)
+    nbytes = _lib.mla_prefill().fa_mi355x_fwd_mla_prefill_workspace_bytes(cu_seqlens_q.shape[0] - 1, Tq, Tk, H)
+    return torch.empty(nbytes // 4, dtype=_F32, device=q.device)
+
+
+def flash_attn_mla_prefill(q, k_nope, k_pe, v, cu_seqlens_q, cu_seqlens_k=None, softmax_scale=None, out=None, lse=None, workspace=None):
+    """MLA prefill on a packed batch (fa_mi355x_fwd_mla_prefill): ``q`` bf16 (Tq, H, 192) = q_nope | rotated q_pe, ``k_nope`` and ``v``
+    bf16 (Tk, H, 128), ``k_pe`` bf16 (Tk, 64) rotated, one vector per token.  k_nope and v may be non-contiguous views whose last
+    dimension is contiguous (the two halves of an up-projection's (Tk, H, 256) output): their strides are passed through.
+    ``cu_seqlens_q`` / ``cu_seqlens_k`` int32 (nseq + 1,) on the device, as in flash_attn_varlen_prefix_fwd: sequence b's queries are
+    the LAST positions of its keys, row i admits key j iff j <= i + n_k - n_q.  ``cu_seqlens_k=None``: the same array, plain causal
+    self-attention.  ``softmax_scale=None``: 192 ** -0.5.  Returns (out fp32 (Tq, H, 128), lse fp32 (H, Tq)); rows that admit no key
+    and rows no sequence owns are zeros.  No host synchronisation: the call can be captured in a graph."""
+    Tq, Tk, H = _mlap_operands(q, k_nope, k_pe, v)
+    if cu_seqlens_k is None and Tq != Tk:
+        raise ValueError(f"cu_seqlens_k=None means self-attention: k_nope must have q's {Tq} rows, not {Tk}")
+    if softmax_scale is not None and (not isinstance(softmax_scale, numbers.Real) or not softmax_scale > 0 or not math.isfinite(softmax_scale)):
+        raise ValueError("softmax_scale must be positive and finite (None: 192 ** -0.5)")
+    (k_ld, k_hs), (v_ld, v_hs) = _mlap_strided(k_nope, "k_nope", Tk, H), _mlap_strided(v, "v", Tk, H)
+    if not q.is_contiguous() or not k_pe.is_contiguous():
+        raise ValueError("q and k_pe must be contiguous")
+    _require_gpu(q, "flash_attn_mla_prefill")
+    dev = q.device
+    if any(t.device != dev for t in (k_nope, k_pe, v)):
+        raise ValueError("q, k_nope, k_pe and v must be on one device")
+    _check_cu(cu_seqlens_q, None, dev)
+    cu_k = cu_seqlens_q if cu_seqlens_k is None else cu_seqlens_k
+    if cu_k is not cu_seqlens_q:
+        _check_cu(cu_k, None, dev)
+        if cu_k.shape != cu_seqlens_q.shape:
+            raise ValueError("cu_seqlens_q and cu_seqlens_k must have one length: the same sequences, counted in q and in k")
+    nseq = cu_seqlens_q.shape[0] - 1
+    if out is None:
+        out = torch.empty((Tq, H, _MLAP_V), dtype=_F32, device=dev)
+    elif out.dtype is not _F32 or tuple(out.shape) != (Tq, H, _MLAP_V) or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"out must be a contiguous float32 tensor of shape (Tq, H, {_MLAP_V}) on q's device")
+    if lse is None:
+        lse = torch.empty((H, Tq), dtype=_F32, device=dev)
+    else:
+        _check_buffer(lse, q.get_device(), "lse", H * Tq)
+    nbytes = _lib.mla_prefill().fa_mi355x_fwd_mla_prefill_workspace_bytes(nseq, Tq, Tk, H)
+    if workspace is None:
+        workspace = torch.empty(nbytes // 4, dtype=_F32, device=dev)
+    else:
+        _check_workspace(workspace, nbytes, q.get_device(), "mla_prefill_workspace(q, k_nope, cu_seqlens_q)")
+    _lib.mla_prefill_check(_lib.mla_prefill().fa_mi355x_fwd_mla_prefill(
+        _ptr(q), _ptr(k_nope), _ptr(k_pe), _ptr(v), _ptr(out), _ptr(lse), _ptr(cu_seqlens_q), _ptr(cu_k), _ptr(workspace), nseq, Tq, Tk, H,
+        k_ld, k_hs, v_ld, v_hs, float(softmax_scale or 0.0), _stream_ptr()))
+    return out, lse

@@ -951,3 +951,38 @@ def mla_attention_step(x, cache: LatentKVCache, li: int, weights: MLAWeights, n_
                                               workspace=cache.workspace(q_abs, None if indices is None else int(indices.shape[-1])),
                                               **sparse)
     return torch.einsum("bthc,hcv->bthv", out.to(x.dtype), w_uv).reshape(B, T, -1) @ wo
+
+
+MLA_PREFILL_PIECE = 128   # tokens per device_ops.mla_append call (its Nq bound)
+
+
+def mla_attention_prefill(x, cache: LatentKVCache, li: int, weights: MLAWeights, n_head: int, rope: Rotary, softmax_scale=None):
+    """The prompt of layer ``li``, before absorption: x (B, P, E) are the P tokens of each sequence's prompt, which starts at
+    position 0 (the tokens attend each other and nothing already in the cache).  ``cache.lengths`` already COUNTS them
+    (cache.advance(P) once, in front of the layers): token i sits at position lengths - P + i.  (1) project: q = x wq, c_kv | k_pe = x w_dkv; (2) rotate q_pe and k_pe at those positions;
+    (3) write c_kv | k_pe into the latent cache (device_ops.mla_append in pieces of at most 128 tokens, each under lengths formed on
+    the device: slab, paged or fp8, whatever the cache is); (4) ONE GEMM up-projects the prompt's latents to (B * P, H, 256) =
+    k_nope | v per head; (5) device_ops.flash_attn_mla_prefill attends on the two views of that buffer and k_pe, one sequence per
+    batch element; (6) wo.  mla_attention_step continues on the same cache.  No host synchronisation.  Needs dn = dv = 128 (the
+    kernel's head shape).  ``softmax_scale``: 192 ** -0.5 unless given (a YaRN model passes its own)."""
+    B, P, _ = x.shape
+    wq, w_dkv, w_uk, w_uv, wo = weights
+    dn, dv = w_uk.shape[1], w_uv.shape[2]
+    if dn != _lib.MLA_PREFILL_D_NOPE or dv != _lib.MLA_PREFILL_D_V:
+        raise ValueError(f"mla_attention_prefill needs dn = {_lib.MLA_PREFILL_D_NOPE} and dv = {_lib.MLA_PREFILL_D_V} (the prefill "
+                         f"kernel's head shape), not dn = {dn} and dv = {dv}")
+    q = (x @ wq).view(B, P, n_head, dn + MLA_ROPE)
+    kv = x @ w_dkv
+    offsets = cache.lengths - P
+    q_pe = rope.apply(q[..., dn:].contiguous(), offsets)
+    k_pe = rope.apply(kv[..., MLA_LATENT:].reshape(B, P, 1, MLA_ROPE).contiguous(), offsets).view(B, P, MLA_ROPE)
+    rows = torch.cat([kv[..., :MLA_LATENT], k_pe], -1)
+    for s in range(0, P, MLA_PREFILL_PIECE):
+        e = min(s + MLA_PREFILL_PIECE, P)
+        device_ops.mla_append(rows[:, s:e].contiguous(), cache.kv[li], offsets + e, cache.block_table)
+    w_up = torch.cat([w_uk.transpose(1, 2), w_uv], -1).permute(1, 0, 2).reshape(MLA_LATENT, n_head * (dn + dv))   # (512, H * 256)
+    kv_up = (kv[..., :MLA_LATENT].reshape(B * P, MLA_LATENT) @ w_up).view(B * P, n_head, dn + dv)
+    cu = torch.arange(B + 1, dtype=torch.int32, device=x.device) * P
+    out, _ = device_ops.flash_attn_mla_prefill(torch.cat([q[..., :dn], q_pe], -1).view(B * P, n_head, dn + MLA_ROPE), kv_up[..., :dn],
+                                               k_pe.reshape(B * P, MLA_ROPE), kv_up[..., dn:], cu, softmax_scale=softmax_scale)
+    return out.to(x.dtype).view(B, P, n_head * dv) @ wo
