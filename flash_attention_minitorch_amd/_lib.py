@@ -599,10 +599,17 @@ def mla_check(status: int) -> None:
 MLA_PREFILL_ABI = {
     "fa_mi355x_fwd_mla_prefill_workspace_bytes": (_sz, [_i] * 4),
     "fa_mi355x_fwd_mla_prefill": (_i, [_vp] * 9 + [_i] * 8 + [_f, _vp]),
+    "fa_mi355x_bwd_mla_prefill_workspace_bytes": (_sz, [_i] * 4),
+    "fa_mi355x_bwd_mla_prefill": (_i, [_vp] * 14 + [_i] * 12 + [_f, _vp]),
     "fa_mi355x_mla_prefill_last_error": (_s, []),
 }
 MLA_PREFILL_NAME = "libflash_attn_mi355x_mla_prefill.so"
 MLA_PREFILL_D_NOPE, MLA_PREFILL_D_ROPE, MLA_PREFILL_D_V = 128, 64, 128   # columns of k_nope, of k_pe (q has both) and of v (and out)
+
+
+def mla_prefill_heads_per_group(H: int) -> int:
+    """Heads whose dk_pe one workgroup of the backward adds up (csrc/fa_mla_prefill_bwd.h: clamp(H / 16, 2, 8)); ceil(H / this) groups."""
+    return min(8, max(2, H // 16))
 
 
 def mla_prefill() -> ctypes.CDLL:

@@ -2428,13 +2428,114 @@ def _mlap_operands(q, k_nope, k_pe=None, v=None):
     return Tq, Tk, H
 
 
-def mla_prefill_workspace(q, k_nope, cu_seqlens_q, cu_seqlens_k=None):
-    """Scratch for flash_attn_mla_prefill on these shapes (fa_mi355x_fwd_mla_prefill_workspace_bytes): the query-block map.  A pure
-    function of the SHAPES (the arrays' contents are not read): allocate once, reuse every call."""
+def mla_prefill_workspace(q, k_nope, cu_seqlens_q, cu_seqlens_k=None, backward=False):
+    """Scratch for flash_attn_mla_prefill on these shapes (fa_mi355x_fwd_mla_prefill_workspace_bytes): the query-block map;
+    ``backward=True``: for flash_attn_mla_prefill_bwd (fa_mi355x_bwd_mla_prefill_workspace_bytes: both maps, the row constants, the
+    dk_pe partials).  A pure function of the SHAPES (the arrays' contents are not read): allocate once, reuse every call."""
     Tq, Tk, H = _mlap_operands(q, k_nope)
     _check_cu(cu_seqlens_q, None, q.device)
-    nbytes = _lib.mla_prefill().fa_mi355x_fwd_mla_prefill_workspace_bytes(cu_seqlens_q.shape[0] - 1, Tq, Tk, H)
-    return torch.empty(nbytes // 4, dtype=_F32, device=q.device)
+    lib = _lib.mla_prefill()
+    size = lib.fa_mi355x_bwd_mla_prefill_workspace_bytes if backward else lib.fa_mi355x_fwd_mla_prefill_workspace_bytes
+    return torch.empty(size(cu_seqlens_q.shape[0] - 1, Tq, Tk, H) // 4, dtype=_F32, device=q.device)
+
+
+def _mlap_call(q, k_nope, k_pe, v, cu_seqlens_q, cu_seqlens_k, softmax_scale, who):
+    """The checks both prefill calls make on the forward's operands; (Tq, Tk, H, strides of k_nope and of v, cu_k, nseq)."""
+    Tq, Tk, H = _mlap_operands(q, k_nope, k_pe, v)
+    if cu_seqlens_k is None and Tq != Tk:
+        raise ValueError(f"cu_seqlens_k=None means self-attention: k_nope must have q's {Tq} rows, not {Tk}")
+    if softmax_scale is not None and (not isinstance(softmax_scale, numbers.Real) or not softmax_scale > 0 or not math.isfinite(softmax_scale)):
+        raise ValueError("softmax_scale must be positive and finite (None: 192 ** -0.5)")
+    k_st, v_st = _mlap_strided(k_nope, "k_nope", Tk, H), _mlap_strided(v, "v", Tk, H)
+    if not q.is_contiguous() or not k_pe.is_contiguous():
+        raise ValueError("q and k_pe must be contiguous")
+    _require_gpu(q, who)
+    dev = q.device
+    if any(t.device != dev for t in (k_nope, k_pe, v)):
+        raise ValueError("q, k_nope, k_pe and v must be on one device")
+    _check_cu(cu_seqlens_q, None, dev)
+    cu_k = cu_seqlens_q if cu_seqlens_k is None else cu_seqlens_k
+    if cu_k is not cu_seqlens_q:
+        _check_cu(cu_k, None, dev)
+        if cu_k.shape != cu_seqlens_q.shape:
+            raise ValueError("cu_seqlens_q and cu_seqlens_k must have one length: the same sequences, counted in q and in k")
+    return Tq, Tk, H, k_st, v_st, cu_k, cu_seqlens_q.shape[0] - 1
+
+
+def _mlap_grad(t, name, Tk, H, dev):
+    """(row stride, head stride) of dk_nope or dv: fp32 (Tk, H, 128), maybe a view under _mlap_strided's rules at 4-element steps."""
+    if not isinstance(t, torch.Tensor) or t.dtype is not _F32 or tuple(t.shape) != (Tk, H, _MLAP_N) or t.device != dev:
+        raise ValueError(f"grads: {name} must be a float32 tensor of shape (Tk, H, {_MLAP_N}) on q's device")
+    ld, hs, inner = (int(s) for s in t.stride())
+    hs = hs if H > 1 else max(hs, _MLAP_N)
+    if inner != 1 or ld % 4 or hs % 4 or hs < _MLAP_N or ld < (H - 1) * hs + _MLAP_N or t.data_ptr() % 16:
+        raise ValueError(f"grads: {name} may be a view, but its last dimension must be contiguous, its row and head strides multiples of 4 "
+                         f"elements that keep heads and rows apart, and its first element 16-byte aligned (strides {tuple(t.stride())})")
+    return ld, hs
+
+
+def flash_attn_mla_prefill_bwd(q, k_nope, k_pe, v, out, out_grad, lse, cu_seqlens_q, cu_seqlens_k=None, softmax_scale=None, workspace=None,
+                               grads=None):
+    """The backward of flash_attn_mla_prefill (fa_mi355x_bwd_mla_prefill) from its operands, its ``out`` (fp32 (Tq, H, 128)) and
+    ``lse`` (fp32 (H, Tq)), and ``out_grad`` of out's shape, which is converted to bf16.  Returns fp32 (dq (Tq, H, 192), dk_nope
+    (Tk, H, 128), dk_pe (Tk, 64), dv (Tk, H, 128)); dk_pe is the sum over the heads.  ``grads``: these four as the caller's buffers;
+    dk_nope and dv may be the two views of one (Tk, H, 256) buffer.  Keys no query admits, rows that admit no key and rows no sequence
+    owns get exact zeros.  ``workspace``: mla_prefill_workspace(..., backward=True).  No host synchronisation."""
+    Tq, Tk, H, (k_ld, k_hs), (v_ld, v_hs), cu_k, nseq = _mlap_call(q, k_nope, k_pe, v, cu_seqlens_q, cu_seqlens_k, softmax_scale,
+                                                                   "flash_attn_mla_prefill_bwd")
+    dev = q.device
+    for t, name in ((out, "out"), (out_grad, "out_grad")):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != (Tq, H, _MLAP_V) or t.device != dev:
+            raise ValueError(f"{name} must have the forward's shape (Tq, H, {_MLAP_V}) on q's device")
+    if out.dtype is not _F32 or not out.is_contiguous():
+        raise ValueError("out must be the forward's contiguous float32 result")
+    _check_buffer(lse, q.get_device(), "lse", H * Tq)
+    nbytes = _lib.mla_prefill().fa_mi355x_bwd_mla_prefill_workspace_bytes(nseq, Tq, Tk, H)
+    if workspace is not None:
+        _check_workspace(workspace, nbytes, q.get_device(), "mla_prefill_workspace(q, k_nope, cu_seqlens_q, backward=True)")
+    if grads is not None:
+        if len(grads) != 4:
+            raise ValueError("grads must be (dq, dk_nope, dk_pe, dv)")
+        dq, dk_nope, dk_pe, dv = grads
+        for t, name, shape in ((dq, "dq", (Tq, H, _MLAP_N + _MLAP_R)), (dk_pe, "dk_pe", (Tk, _MLAP_R))):
+            if not isinstance(t, torch.Tensor) or t.dtype is not _F32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"grads: {name} must be a contiguous float32 tensor of shape {shape} on q's device")
+    else:
+        dq = torch.empty((Tq, H, _MLAP_N + _MLAP_R), dtype=_F32, device=dev)
+        dk_nope, dv = (torch.empty((Tk, H, _MLAP_N), dtype=_F32, device=dev) for _ in range(2))
+        dk_pe = torch.empty((Tk, _MLAP_R), dtype=_F32, device=dev)
+    (dk_ld, dk_hs), (dv_ld, dv_hs) = _mlap_grad(dk_nope, "dk_nope", Tk, H, dev), _mlap_grad(dv, "dv", Tk, H, dev)
+    if workspace is None:
+        workspace = torch.empty(nbytes // 4, dtype=_F32, device=dev)
+    dout = out_grad.to(torch.bfloat16).contiguous()
+    _lib.mla_prefill_check(_lib.mla_prefill().fa_mi355x_bwd_mla_prefill(
+        _ptr(q), _ptr(k_nope), _ptr(k_pe), _ptr(v), _ptr(out), _ptr(dout), _ptr(lse), _ptr(dq), _ptr(dk_nope), _ptr(dk_pe), _ptr(dv),
+        _ptr(cu_seqlens_q), _ptr(cu_k), _ptr(workspace), nseq, Tq, Tk, H, k_ld, k_hs, v_ld, v_hs, dk_ld, dk_hs, dv_ld, dv_hs,
+        float(softmax_scale or 0.0), _stream_ptr()))
+    return dq, dk_nope, dk_pe, dv
+
+
+class _MlaPrefillFn(torch.autograd.Function):
+    """flash_attn_mla_prefill and flash_attn_mla_prefill_bwd under autograd; gradients in the inputs' dtype and shape."""
+
+    @staticmethod
+    def forward(ctx, q, k_nope, k_pe, v, cu_seqlens_q, cu_seqlens_k, softmax_scale):
+        out, lse = flash_attn_mla_prefill(q, k_nope, k_pe, v, cu_seqlens_q, cu_seqlens_k, softmax_scale)
+        ctx.save_for_backward(q, k_nope, k_pe, v, out, lse, cu_seqlens_q, *(() if cu_seqlens_k is None else (cu_seqlens_k,)))
+        ctx.softmax_scale = softmax_scale
+        return out
+
+    @staticmethod
+    def backward(ctx, out_grad):
+        q, k_nope, k_pe, v, out, lse, cu_q, *cu_k = ctx.saved_tensors
+        grads = flash_attn_mla_prefill_bwd(q, k_nope, k_pe, v, out, out_grad, lse, cu_q, *(cu_k or (None,)), ctx.softmax_scale)
+        return (*(g.to(t.dtype) for g, t in zip(grads, (q, k_nope, k_pe, v))), None, None, None)
+
+
+def flash_attn_mla_prefill_train(q, k_nope, k_pe, v, cu_seqlens_q, cu_seqlens_k=None, softmax_scale=None):
+    """flash_attn_mla_prefill under autograd: returns out fp32 (Tq, H, 128), and backward() leaves gradients in the dtype and shape of
+    q, k_nope, k_pe and v (k_nope and v as views of one leaf (Tk, H, 256) buffer: that leaf's .grad holds both halves)."""
+    return _MlaPrefillFn.apply(q, k_nope, k_pe, v, cu_seqlens_q, cu_seqlens_k, softmax_scale)
 
 
 def flash_attn_mla_prefill(q, k_nope, k_pe, v, cu_seqlens_q, cu_seqlens_k=None, softmax_scale=None, out=None, lse=None, workspace=None):
@@ -2445,25 +2546,9 @@ def flash_attn_mla_prefill(q, k_nope, k_pe, v, cu_seqlens_q, cu_seqlens_k=None, 
     the LAST positions of its keys, row i admits key j iff j <= i + n_k - n_q.  ``cu_seqlens_k=None``: the same array, plain causal
     self-attention.  ``softmax_scale=None``: 192 ** -0.5.  Returns (out fp32 (Tq, H, 128), lse fp32 (H, Tq)); rows that admit no key
     and rows no sequence owns are zeros.  No host synchronisation: the call can be captured in a graph."""
-    Tq, Tk, H = _mlap_operands(q, k_nope, k_pe, v)
-    if cu_seqlens_k is None and Tq != Tk:
-        raise ValueError(f"cu_seqlens_k=None means self-attention: k_nope must have q's {Tq} rows, not {Tk}")
-    if softmax_scale is not None and (not isinstance(softmax_scale, numbers.Real) or not softmax_scale > 0 or not math.isfinite(softmax_scale)):
-        raise ValueError("softmax_scale must be positive and finite (None: 192 ** -0.5)")
-    (k_ld, k_hs), (v_ld, v_hs) = _mlap_strided(k_nope, "k_nope", Tk, H), _mlap_strided(v, "v", Tk, H)
-    if not q.is_contiguous() or not k_pe.is_contiguous():
-        raise ValueError("q and k_pe must be contiguous")
-    _require_gpu(q, "flash_attn_mla_prefill")
+    Tq, Tk, H, (k_ld, k_hs), (v_ld, v_hs), cu_k, nseq = _mlap_call(q, k_nope, k_pe, v, cu_seqlens_q, cu_seqlens_k, softmax_scale,
+                                                                   "flash_attn_mla_prefill")
     dev = q.device
-    if any(t.device != dev for t in (k_nope, k_pe, v)):
-        raise ValueError("q, k_nope, k_pe and v must be on one device")
-    _check_cu(cu_seqlens_q, None, dev)
-    cu_k = cu_seqlens_q if cu_seqlens_k is None else cu_seqlens_k
-    if cu_k is not cu_seqlens_q:
-        _check_cu(cu_k, None, dev)
-        if cu_k.shape != cu_seqlens_q.shape:
-            raise ValueError("cu_seqlens_q and cu_seqlens_k must have one length: the same sequences, counted in q and in k")
-    nseq = cu_seqlens_q.shape[0] - 1
     if out is None:
         out = torch.empty((Tq, H, _MLAP_V), dtype=_F32, device=dev)
     elif out.dtype is not _F32 or tuple(out.shape) != (Tq, H, _MLAP_V) or not out.is_contiguous() or out.device != dev:

@@ -23,8 +23,9 @@
  * and every wave multiplies it into its own 128 of the 512 output columns for all 64 rows (64 MFMAs): no MFMA is issued twice.
  * Several key chunks leave (o[512], m, l) partials that mla_decode_combine_kernel merges in split order.
  *
- * Not built: a sliding window, sink tokens, a soft cap, learned sink logits, the ragged family, other latent widths, the training
- * backward.  (A prompt is prefilled before absorption by a library of its own: flash_attn_mi355x_mla_prefill.h.)
+ * Not built: a sliding window, sink tokens, a soft cap, learned sink logits, the ragged family, other latent widths, a backward
+ * of the absorbed form.  (A prompt is prefilled before absorption by a library of its own, flash_attn_mi355x_mla_prefill.h, which
+ * also has the training backward at that head shape.)
  * (Sparse attention over per-query index lists, DeepSeek-V3.2 DSA, is in this library under a header of its own:
  * flash_attn_mi355x_mla_sparse.h; an fp8 latent cache under flash_attn_mi355x_mla_fp8.h.)
  */
