@@ -581,11 +581,20 @@ MLA_FP8_ABI = {
     "fa_mi355x_mla_append_fp8": MLA_ABI["fa_mi355x_mla_append"],
 }
 MLA_FP8_ROW_BYTES = 656   # 512 e4m3 codes, four fp32 tile scales, 64 bf16 k_pe columns
+# include/flash_attn_mi355x_mla_indexer_fp8.h, in the same library: the indexer on fp8 index keys of 144-byte rows (the score call, the
+# quantising append, the fused call), each with its bf16 twin's parameter list (tests/test_mla_indexer_fp8_cpu.py).  A table of its own.
+MLA_INDEXER_FP8_ABI = {
+    "fa_mi355x_mla_index_scores_fp8": MLA_INDEXER_ABI["fa_mi355x_mla_index_scores"],
+    "fa_mi355x_mla_index_append_fp8": MLA_INDEXER_ABI["fa_mi355x_mla_index_append"],
+    "fa_mi355x_mla_indexer_fp8": MLA_INDEXER_ABI["fa_mi355x_mla_indexer"],
+}
+MLA_INDEX_FP8_ROW_BYTES = 144   # 128 e4m3 codes, one fp32 scale, 12 reserved bytes
 
 
 def mla() -> ctypes.CDLL:
-    """libflash_attn_mi355x_mla.so (include/flash_attn_mi355x_mla.h, ..._mla_sparse.h, ..._mla_indexer.h, ..._mla_fp8.h) with argtypes set."""
-    return _typed(MLA_NAME, {**MLA_ABI, **MLA_SPARSE_ABI, **MLA_INDEXER_ABI, **MLA_FP8_ABI})
+    """libflash_attn_mi355x_mla.so (include/flash_attn_mi355x_mla.h, ..._mla_sparse.h, ..._mla_indexer.h, ..._mla_fp8.h,
+    ..._mla_indexer_fp8.h) with argtypes set."""
+    return _typed(MLA_NAME, {**MLA_ABI, **MLA_SPARSE_ABI, **MLA_INDEXER_ABI, **MLA_FP8_ABI, **MLA_INDEXER_FP8_ABI})
 
 
 def mla_check(status: int) -> None:

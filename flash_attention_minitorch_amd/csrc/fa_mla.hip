@@ -6,9 +6,12 @@
 // which check_index() answers the same way; its chunking is index_policy(), under the split policies.
 // The fp8 latent cache (include/flash_attn_mi355x_mla_fp8.h, kernels in fa_mla_fp8.h) is an MlaCall with the fp8 flag: rows of 656
 // bytes in the bounds and the strides, the fp8 builds in the launches, the same policies.
+// FP8 index keys (include/flash_attn_mi355x_mla_indexer_fp8.h, kernels in fa_mla_indexer_fp8.h) are an IndexCall with the fp8 flag:
+// rows of 144 bytes in the slab bound, the fp8 append and score kernels in the launches, the same chunks, the same top-k.
 #include "../../include/flash_attn_mi355x_mla.h"
 #include "../../include/flash_attn_mi355x_mla_fp8.h"
 #include "../../include/flash_attn_mi355x_mla_indexer.h"
+#include "../../include/flash_attn_mi355x_mla_indexer_fp8.h"
 #include "../../include/flash_attn_mi355x_mla_sparse.h"
 
 #include <algorithm>
@@ -19,6 +22,7 @@
 #include "fa_mla.h"
 #include "fa_mla_fp8.h"
 #include "fa_mla_indexer.h"
+#include "fa_mla_indexer_fp8.h"
 #include "fa_mla_sparse.h"
 
 namespace {
@@ -264,6 +268,8 @@ struct IndexCall {
   const int *seqlens = nullptr, *table = nullptr;
   int B = 0, HI = 1, Nq = 0, topk = 0, Ncap = 0, num_pages = 0, page_size = 0, max_pages = 0, causal = 0;
   bool append = false, score = false, select = false;
+  bool fp8 = false;   // the index-key cache holds 144-byte rows (e4m3 codes, one scale)
+  long row_bytes() const { return fp8 ? fa::MLA_IDX8_ROW_BYTES : fa::MLA_IDX_ROW_BYTES; }
   hipStream_t stream = nullptr;
 };
 
@@ -289,7 +295,7 @@ int check_index(IndexCall& c, IndexPolicy* out) {
     if (c.Ncap <= 0) return set_err(FA_ERR_BAD_ARG, "Ncap must be positive");
     // (a buffer load's row offset is a 32-bit byte count: a slab, plus a step of rows past its end)
     if (!c.select || c.score || c.append)
-      if (((long)c.Ncap + fa::MLA_IDX_STEP) * fa::MLA_IDX_ROW_BYTES >= (1L << 31))
+      if (((long)c.Ncap + fa::MLA_IDX_STEP) * c.row_bytes() >= (1L << 31))
         return set_err(FA_ERR_BAD_ARG, "one batch element of the index-key cache must stay under 2 GiB");
   }
   if (misaligned4(c.seqlens) || misaligned4(c.table)) return set_err(FA_ERR_BAD_ARG, "cache_seqlens and block_table must be 4-byte aligned");
@@ -332,8 +338,10 @@ int run_index(IndexCall& c) {
     a.kv_new = c.kidx_new, a.kv = c.kidx_cache, a.seqlens = c.seqlens, a.table = c.table;
     a.lanes = (long)c.B * c.Nq * (fa::MLA_IDX_D / 8);
     a.Nq = c.Nq, a.Ncap = c.Ncap, a.page_size = c.page_size, a.num_pages = c.num_pages, a.max_pages = c.max_pages;
-    hipLaunchKernelGGL(fa::mla_index_append_kernel, dim3((unsigned)((a.lanes + 255) / 256)), dim3(256), 0, c.stream, a);
-    if ((e = hipGetLastError()) != hipSuccess) return hip_err("mla_index_append_kernel launch", e);
+    const dim3 grid((unsigned)((a.lanes + 255) / 256));
+    if (c.fp8) hipLaunchKernelGGL(fa::mla_index_append_fp8_kernel, grid, dim3(256), 0, c.stream, a);
+    else hipLaunchKernelGGL(fa::mla_index_append_kernel, grid, dim3(256), 0, c.stream, a);
+    if ((e = hipGetLastError()) != hipSuccess) return hip_err(c.fp8 ? "mla_index_append_fp8_kernel launch" : "mla_index_append_kernel launch", e);
   }
   if (c.score) {
     fa::MlaIndexArgs a;
@@ -341,9 +349,11 @@ int run_index(IndexCall& c) {
     a.HI = c.HI, a.Nq = c.Nq, a.Ncap = c.Ncap, a.chunk = p.chunk, a.nchunk = p.nchunk, a.group = p.group, a.ngroups = p.ngroups;
     a.page_size = c.page_size, a.num_pages = c.num_pages, a.max_pages = c.max_pages, a.causal = c.causal ? 1 : 0;
     const dim3 grid((unsigned)((long)c.B * p.ngroups * p.nchunk));
-    if (c.table) hipLaunchKernelGGL(fa::mla_index_scores_kernel<true>, grid, dim3(256), 0, c.stream, a);
+    if (c.fp8 && c.table) hipLaunchKernelGGL(fa::mla_index_scores_fp8_kernel<true>, grid, dim3(256), 0, c.stream, a);
+    else if (c.fp8) hipLaunchKernelGGL(fa::mla_index_scores_fp8_kernel<false>, grid, dim3(256), 0, c.stream, a);
+    else if (c.table) hipLaunchKernelGGL(fa::mla_index_scores_kernel<true>, grid, dim3(256), 0, c.stream, a);
     else hipLaunchKernelGGL(fa::mla_index_scores_kernel<false>, grid, dim3(256), 0, c.stream, a);
-    if ((e = hipGetLastError()) != hipSuccess) return hip_err("mla_index_scores_kernel launch", e);
+    if ((e = hipGetLastError()) != hipSuccess) return hip_err(c.fp8 ? "mla_index_scores_fp8_kernel launch" : "mla_index_scores_kernel launch", e);
   }
   if (c.select) {
     fa::MlaTopkArgs a;
@@ -445,15 +455,30 @@ size_t fa_mi355x_decode_mla_sparse_workspace_bytes(int B, int H, int Nq, int top
   return query(B, H, Nq, topk, true).workspace_bytes;
 }
 
-int fa_mi355x_mla_index_scores(const void* q_idx, const float* weights, const void* kidx_new, void* kidx_cache, float* scores,
-                               const int* cache_seqlens, const int* block_table, int B, int HI, int Nq, int Ncap, int num_pages,
-                               int page_size, int max_pages, int causal, void* stream) {
+static int index_scores(bool fp8, const void* q_idx, const float* weights, const void* kidx_new, void* kidx_cache, float* scores,
+                        const int* cache_seqlens, const int* block_table, int B, int HI, int Nq, int Ncap, int num_pages, int page_size,
+                        int max_pages, int causal, void* stream) {
   IndexCall c;
+  c.fp8 = fp8;
   c.q_idx = q_idx, c.weights = weights, c.kidx_new = kidx_new, c.kidx_cache = kidx_cache, c.scores = scores, c.seqlens = cache_seqlens;
   c.table = block_table, c.B = B, c.HI = HI, c.Nq = Nq, c.Ncap = Ncap, c.num_pages = num_pages, c.page_size = page_size;
   c.max_pages = max_pages, c.causal = causal, c.stream = static_cast<hipStream_t>(stream);
   c.append = kidx_new != nullptr, c.score = true;
   return run_index(c);
+}
+
+int fa_mi355x_mla_index_scores(const void* q_idx, const float* weights, const void* kidx_new, void* kidx_cache, float* scores,
+                               const int* cache_seqlens, const int* block_table, int B, int HI, int Nq, int Ncap, int num_pages,
+                               int page_size, int max_pages, int causal, void* stream) {
+  return index_scores(false, q_idx, weights, kidx_new, kidx_cache, scores, cache_seqlens, block_table, B, HI, Nq, Ncap, num_pages,
+                      page_size, max_pages, causal, stream);
+}
+
+int fa_mi355x_mla_index_scores_fp8(const void* q_idx, const float* weights, const void* kidx_new, void* kidx_cache, float* scores,
+                                   const int* cache_seqlens, const int* block_table, int B, int HI, int Nq, int Ncap, int num_pages,
+                                   int page_size, int max_pages, int causal, void* stream) {
+  return index_scores(true, q_idx, weights, kidx_new, kidx_cache, scores, cache_seqlens, block_table, B, HI, Nq, Ncap, num_pages,
+                      page_size, max_pages, causal, stream);
 }
 
 int fa_mi355x_mla_index_topk(const float* scores, int* indices, const int* cache_seqlens, int B, int Nq, int Ncap, int topk,
@@ -465,24 +490,50 @@ int fa_mi355x_mla_index_topk(const float* scores, int* indices, const int* cache
   return run_index(c);
 }
 
-int fa_mi355x_mla_index_append(const void* kidx_new, void* kidx_cache, const int* cache_seqlens, const int* block_table, int B, int Nq,
-                               int Ncap, int num_pages, int page_size, int max_pages, void* stream) {
+static int index_append(bool fp8, const void* kidx_new, void* kidx_cache, const int* cache_seqlens, const int* block_table, int B, int Nq,
+                        int Ncap, int num_pages, int page_size, int max_pages, void* stream) {
   IndexCall c;
+  c.fp8 = fp8;
   c.kidx_new = kidx_new, c.kidx_cache = kidx_cache, c.seqlens = cache_seqlens, c.table = block_table, c.B = B, c.Nq = Nq, c.Ncap = Ncap;
   c.num_pages = num_pages, c.page_size = page_size, c.max_pages = max_pages, c.stream = static_cast<hipStream_t>(stream);
   c.append = true;
   return run_index(c);
 }
 
-int fa_mi355x_mla_indexer(const void* q_idx, const float* weights, const void* kidx_new, void* kidx_cache, float* scores, int* indices,
-                          const int* cache_seqlens, const int* block_table, int B, int HI, int Nq, int topk, int Ncap, int num_pages,
-                          int page_size, int max_pages, int causal, void* stream) {
+int fa_mi355x_mla_index_append(const void* kidx_new, void* kidx_cache, const int* cache_seqlens, const int* block_table, int B, int Nq,
+                               int Ncap, int num_pages, int page_size, int max_pages, void* stream) {
+  return index_append(false, kidx_new, kidx_cache, cache_seqlens, block_table, B, Nq, Ncap, num_pages, page_size, max_pages, stream);
+}
+
+int fa_mi355x_mla_index_append_fp8(const void* kidx_new, void* kidx_cache, const int* cache_seqlens, const int* block_table, int B,
+                                   int Nq, int Ncap, int num_pages, int page_size, int max_pages, void* stream) {
+  return index_append(true, kidx_new, kidx_cache, cache_seqlens, block_table, B, Nq, Ncap, num_pages, page_size, max_pages, stream);
+}
+
+static int indexer(bool fp8, const void* q_idx, const float* weights, const void* kidx_new, void* kidx_cache, float* scores, int* indices,
+                   const int* cache_seqlens, const int* block_table, int B, int HI, int Nq, int topk, int Ncap, int num_pages,
+                   int page_size, int max_pages, int causal, void* stream) {
   IndexCall c;
+  c.fp8 = fp8;
   c.q_idx = q_idx, c.weights = weights, c.kidx_new = kidx_new, c.kidx_cache = kidx_cache, c.scores = scores, c.indices = indices;
   c.seqlens = cache_seqlens, c.table = block_table, c.B = B, c.HI = HI, c.Nq = Nq, c.topk = topk, c.Ncap = Ncap, c.num_pages = num_pages;
   c.page_size = page_size, c.max_pages = max_pages, c.causal = causal, c.stream = static_cast<hipStream_t>(stream);
   c.append = kidx_new != nullptr, c.score = true, c.select = true;
   return run_index(c);
+}
+
+int fa_mi355x_mla_indexer(const void* q_idx, const float* weights, const void* kidx_new, void* kidx_cache, float* scores, int* indices,
+                          const int* cache_seqlens, const int* block_table, int B, int HI, int Nq, int topk, int Ncap, int num_pages,
+                          int page_size, int max_pages, int causal, void* stream) {
+  return indexer(false, q_idx, weights, kidx_new, kidx_cache, scores, indices, cache_seqlens, block_table, B, HI, Nq, topk, Ncap,
+                 num_pages, page_size, max_pages, causal, stream);
+}
+
+int fa_mi355x_mla_indexer_fp8(const void* q_idx, const float* weights, const void* kidx_new, void* kidx_cache, float* scores,
+                              int* indices, const int* cache_seqlens, const int* block_table, int B, int HI, int Nq, int topk, int Ncap,
+                              int num_pages, int page_size, int max_pages, int causal, void* stream) {
+  return indexer(true, q_idx, weights, kidx_new, kidx_cache, scores, indices, cache_seqlens, block_table, B, HI, Nq, topk, Ncap,
+                 num_pages, page_size, max_pages, causal, stream);
 }
 
 size_t fa_mi355x_mla_indexer_scores_bytes(int B, int Nq, int Ncap) {

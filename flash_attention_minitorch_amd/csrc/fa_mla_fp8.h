@@ -23,7 +23,8 @@
 // 448), the codes are fa_decode.h's fp8_prescale / fp8_pack2 (clamp in front of the conversion, NaN -> 0x7F); one 8-byte store per
 // lane, one lane stores the 16 bytes of scales, eight lanes copy k_pe.  Placement is mla_append_kernel's.
 //
-// Not built: fp8 index keys for the indexer, fp8 queries or fp8 MFMAs, e5m2, scales that are not powers of two, other tile widths
+// (FP8 index keys for the indexer, with fp8 MFMAs, are fa_mla_indexer_fp8.h's.)
+// Not built: fp8 queries or fp8 MFMAs for the attention itself, e5m2, scales that are not powers of two, other tile widths
 // than 128, window / sink / cap, an extend kernel.
 #pragma once
 #include "fa_mla_sparse.h"

@@ -33,7 +33,8 @@
 // the score bits.  The row (128 KB at 32768 entries) is read five times, from L2.
 // mla_index_append_kernel: mla_append_kernel's rule on 128-wide rows (token i of batch element b goes to row len_b - Nq + i).
 //
-// Not built: fp8 index keys, a fused score + select launch, index dims other than 128, an indexer for prefill / extend, training.
+// FP8 index keys (144-byte rows, fp8 matrix instructions) are fa_mla_indexer_fp8.h's kernels, under this header's policy and top-k.
+// Not built: a fused score + select launch, index dims other than 128, an indexer for prefill / extend, training.
 #pragma once
 #include "fa_mla.h"
 

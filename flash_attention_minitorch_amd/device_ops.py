@@ -2248,6 +2248,21 @@ def flash_attn_decode_mla(q, kv_cache, cache_seqlens, softmax_scale, causal=True
 # cached index key (bf16 rows of 128 columns, a slab or a pool under the latent cache's block table), and a top-k selection turns a
 # row of scores into an ascending index list.  Checked as the MLA calls are: shapes and dtypes by name, then devices and contiguity.
 _IDX_D = _lib.MLA_INDEX_D
+# An fp8 index-key cache (include/flash_attn_mi355x_mla_indexer_fp8.h) is a torch.uint8 or torch.float8_e4m3fn tensor with rows of 144
+# bytes: 128 e4m3fn codes, one fp32 power-of-two scale, 12 reserved bytes.  The three calls that take a cache route to the fp8 entry
+# points on such a cache; q_idx and kidx_new stay bf16.
+_IDX_FP8_ROW = _lib.MLA_INDEX_FP8_ROW_BYTES
+
+
+def _idx_fp8(kidx_cache):
+    """"_fp8" for an fp8 index-key cache (a byte tensor, whose shape is checked by name here), "" for any other operand."""
+    if not isinstance(kidx_cache, torch.Tensor) or kidx_cache.dtype not in (torch.uint8, torch.float8_e4m3fn):
+        return ""
+    if kidx_cache.dim() != 3 or kidx_cache.shape[-1] != _IDX_FP8_ROW:
+        raise ValueError(f"kidx_cache must be (B, Ncap, {_IDX_FP8_ROW}) when it holds bytes, or a pool (num_pages, page_size, {_IDX_FP8_ROW}) "
+                         f"under a block_table: fp8 index keys are rows of {_IDX_FP8_ROW} bytes (128 e4m3 codes | fp32 scale | 12 reserved); "
+                         f"got {tuple(kidx_cache.shape)}")
+    return "_fp8"
 
 
 def _idx_tensor(t, name, shape_words, rank, dtype=torch.bfloat16, last=_IDX_D):
@@ -2269,11 +2284,12 @@ def _idx_resident(device, **operands):
 
 def _idx_cache(kidx_cache, block_table, B):
     """(Ncap, num_pages, page_size, max_pages) of an index-key cache: a slab (B, Ncap, 128), or under ``block_table`` a pool."""
-    _idx_tensor(kidx_cache, "kidx_cache", f"(B, Ncap, {_IDX_D}), or a pool (num_pages, page_size, {_IDX_D}) under a block_table", 3)
+    if not _idx_fp8(kidx_cache):
+        _idx_tensor(kidx_cache, "kidx_cache", f"(B, Ncap, {_IDX_D}), or a pool (num_pages, page_size, {_IDX_D}) under a block_table", 3)
     max_pages = _max_pages(block_table, None)
     if max_pages is None:
         if kidx_cache.shape[0] != B or kidx_cache.shape[1] < 1:
-            raise ValueError(f"kidx_cache must be (B, Ncap, {_IDX_D}) with B = {B} and Ncap >= 1")
+            raise ValueError(f"kidx_cache must be (B, Ncap, {kidx_cache.shape[2]}) with B = {B} and Ncap >= 1")
         return int(kidx_cache.shape[1]), 0, 0, 0
     num_pages, page_size = int(kidx_cache.shape[0]), int(kidx_cache.shape[1])
     if num_pages < 1 or page_size < 1 or page_size % _lib.FA_PAGE_ROWS:
@@ -2329,10 +2345,13 @@ def mla_index_scores(q_idx, weights, kidx_cache, cache_seqlens, causal=True, kid
     s > len_b - Nq + i); entries at or past len_b are left as they are.  ``q_idx`` bf16 (B, Nq, HI, 128), ``weights`` fp32 (B, Nq, HI)
     with HI^-1/2 and the softmax scale folded in, ``kidx_cache`` bf16 (B, Ncap, 128) or with ``block_table`` a pool (num_pages,
     page_size, 128), ``cache_seqlens`` int32 (B,) on the device.  ``kidx_new`` bf16 (B, Nq, 128): appended first, in the same call
-    (mla_index_append's rule).  Returns ``scores`` fp32 (B, Nq, Ncap) (the caller's buffer, or a fresh one).  No host synchronisation."""
+    (mla_index_append's rule).  Returns ``scores`` fp32 (B, Nq, Ncap) (the caller's buffer, or a fresh one).  No host synchronisation.
+    ``kidx_cache`` torch.uint8 or torch.float8_e4m3fn with rows of 144 bytes: fp8 index keys (fa_mi355x_mla_index_scores_fp8; the format
+    is include/flash_attn_mi355x_mla_indexer_fp8.h's).  ``q_idx`` stays bf16 and is quantised per (token, head) row inside the kernel:
+    the scores are the definition's on the dequantised queries and keys."""
     B, Nq, HI, (Ncap, num_pages, page_size, max_pages), scores = _idx_score_operands(q_idx, weights, kidx_cache, cache_seqlens, kidx_new,
                                                                                      block_table, scores)
-    _lib.mla_check(_lib.mla().fa_mi355x_mla_index_scores(
+    _lib.mla_check(getattr(_lib.mla(), "fa_mi355x_mla_index_scores" + _idx_fp8(kidx_cache))(
         _ptr(q_idx), _ptr(weights), _ptr(kidx_new), _ptr(kidx_cache), _ptr(scores), _ptr(cache_seqlens), _ptr(block_table), B, HI, Nq, Ncap,
         num_pages, page_size, max_pages, int(bool(causal)), _stream_ptr()))
     return scores
@@ -2356,7 +2375,9 @@ def mla_index_topk(scores, cache_seqlens, topk, indices=None):
 
 def mla_index_append(kidx_new, kidx_cache, cache_seqlens, block_table=None):
     """Append the new tokens' index keys (fa_mi355x_mla_index_append): ``kidx_new`` bf16 (B, Nq, 128); token i of sequence b goes to row
-    cache_seqlens[b] - Nq + i (the lengths COUNT the new tokens), slab or paged.  In place; returns kidx_cache."""
+    cache_seqlens[b] - Nq + i (the lengths COUNT the new tokens), slab or paged.  In place; returns kidx_cache.  Into an fp8 index-key
+    cache (bytes, rows of 144) the rows are quantised on the way (fa_mi355x_mla_index_append_fp8): the smallest power-of-two scale that
+    holds the row's maximum in e4m3's range."""
     if not isinstance(kidx_new, torch.Tensor) or kidx_new.dim() != 3:
         raise ValueError(f"kidx_new must be (B, Nq, {_IDX_D})")
     B = int(kidx_new.shape[0])
@@ -2364,22 +2385,23 @@ def mla_index_append(kidx_new, kidx_cache, cache_seqlens, block_table=None):
     Ncap, num_pages, page_size, max_pages = _idx_cache(kidx_cache, block_table, B)
     _idx_resident(kidx_cache.device, kidx_cache=kidx_cache, kidx_new=kidx_new)
     _check_seqlens(cache_seqlens, B, kidx_cache.device)
-    _lib.mla_check(_lib.mla().fa_mi355x_mla_index_append(_ptr(kidx_new), _ptr(kidx_cache), _ptr(cache_seqlens), _ptr(block_table), B, Nq,
-                                                         Ncap, num_pages, page_size, max_pages, _stream_ptr()))
+    _lib.mla_check(getattr(_lib.mla(), "fa_mi355x_mla_index_append" + _idx_fp8(kidx_cache))(
+        _ptr(kidx_new), _ptr(kidx_cache), _ptr(cache_seqlens), _ptr(block_table), B, Nq, Ncap, num_pages, page_size, max_pages, _stream_ptr()))
     return kidx_cache
 
 
 def mla_indexer(q_idx, weights, kidx_cache, cache_seqlens, topk, causal=True, kidx_new=None, block_table=None, scores=None, indices=None):
     """The whole indexer in one call (fa_mi355x_mla_indexer): mla_index_append (``kidx_new`` given), mla_index_scores and mla_index_topk,
     bit for bit.  Returns ``indices`` int32 (B, Nq, topk), which flash_attn_decode_mla(indices=) attends; ``scores`` (B, Nq, Ncap) fp32 is
-    the buffer the scores go through (a fresh one when None).  No host synchronisation: the call can be captured in a graph."""
+    the buffer the scores go through (a fresh one when None).  No host synchronisation: the call can be captured in a graph.  An fp8
+    index-key cache (bytes, rows of 144) takes fa_mi355x_mla_indexer_fp8: the fp8 append and scores, the same selection."""
     _mla_topk(topk)
     if indices is not None:
         indices = _idx_buffer(indices, "indices", tuple(q_idx.shape[:2]) + (topk,), torch.int32, getattr(kidx_cache, "device", None))
     B, Nq, HI, (Ncap, num_pages, page_size, max_pages), scores = _idx_score_operands(q_idx, weights, kidx_cache, cache_seqlens, kidx_new,
                                                                                      block_table, scores)
     indices = _idx_buffer(indices, "indices", (B, Nq, topk), torch.int32, kidx_cache.device)
-    _lib.mla_check(_lib.mla().fa_mi355x_mla_indexer(
+    _lib.mla_check(getattr(_lib.mla(), "fa_mi355x_mla_indexer" + _idx_fp8(kidx_cache))(
         _ptr(q_idx), _ptr(weights), _ptr(kidx_new), _ptr(kidx_cache), _ptr(scores), _ptr(indices), _ptr(cache_seqlens), _ptr(block_table),
         B, HI, Nq, topk, Ncap, num_pages, page_size, max_pages, int(bool(causal)), _stream_ptr()))
     return indices

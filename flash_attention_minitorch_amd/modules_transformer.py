@@ -865,9 +865,11 @@ class LatentKVCache:
     through ``block_table`` (B, max_pages) int32, which starts as sequence b owning pages b * max_pages .. and may be rewritten in
     place.  ``lengths`` int32 (B,) lives on the device; ``advance(n)`` counts n new tokens per sequence without a host round trip.
     ``index_keys``: the cache also holds the indexer's keys, ``kidx[l]`` bf16 rows of 128 columns in a slab or a pool of the same
-    geometry under the same block table, and the buffers the indexer's scores go through (``index_scores(Nq)``).
+    geometry under the same block table, and the buffers the indexer's scores go through (``index_scores(Nq)``).  ``index_keys="fp8"``:
+    the keys are the 144-byte rows of an fp8 index-key cache (torch.uint8: 128 e4m3 codes, an fp32 scale, 12 reserved bytes;
+    include/flash_attn_mi355x_mla_indexer_fp8.h), which device_ops.mla_indexer quantises into and scores on fp8 matrix instructions.
     ``fp8``: the rows are the 656 bytes of an fp8 latent cache (torch.uint8: 512 e4m3 codes, four fp32 tile scales, k_pe as bf16;
-    include/flash_attn_mi355x_mla_fp8.h), which the same device_ops calls quantise into and read; the index keys stay bf16."""
+    include/flash_attn_mi355x_mla_fp8.h), which the same device_ops calls quantise into and read; the index keys are ``index_keys``'s."""
 
     def __init__(self, n_layers, B, capacity, device, page_size=None, n_pages=None, index_keys=False, fp8=False):
         if n_layers < 1 or B < 1 or capacity < 1:
@@ -887,7 +889,10 @@ class LatentKVCache:
             self.kv = [torch.zeros(shape[:2] + (_lib.MLA_FP8_ROW_BYTES,), dtype=torch.uint8, device=device) for _ in range(n_layers)]
         else:
             self.kv = [torch.zeros(shape, dtype=torch.bfloat16, device=device) for _ in range(n_layers)]
-        self.kidx = [torch.zeros(shape[:2] + (MLA_INDEX,), dtype=torch.bfloat16, device=device) for _ in range(n_layers)] if index_keys else None
+        if isinstance(index_keys, str) and index_keys != "fp8":
+            raise ValueError(f"index_keys must be False, True (bf16 rows) or 'fp8' (144-byte rows), not {index_keys!r}")
+        kidx = (_lib.MLA_INDEX_FP8_ROW_BYTES, torch.uint8) if isinstance(index_keys, str) else (MLA_INDEX, torch.bfloat16)
+        self.kidx = [torch.zeros(shape[:2] + kidx[:1], dtype=kidx[1], device=device) for _ in range(n_layers)] if index_keys else None
         self.lengths = torch.zeros(B, dtype=torch.int32, device=device)
         self._workspaces, self._scores = {}, {}
 
@@ -921,8 +926,8 @@ def mla_attention_step(x, cache: LatentKVCache, li: int, weights: MLAWeights, n_
     with index_keys=True) and ``topk`` (a multiple of 64) the step's own: q_idx = x wq_idx per index head and k_idx = x wk_idx, their
     first 64 columns rotated at the tokens' positions like q_pe and k_pe, weights = (x w_head) * HI^-1/2 * 128^-1/2 in fp32, and ONE
     device_ops.mla_indexer call appends k_idx to cache.kidx[li], scores the cache and selects each token's top-k, which the sparse
-    call then attends.  ``indexer`` and ``indices`` together raise.  DeepSeek's LayerNorm on k_idx and its fp8 quantisation of the
-    index keys are not part of this step."""
+    call then attends.  ``indexer`` and ``indices`` together raise.  A cache built with index_keys="fp8" keeps the index keys
+    in fp8 (the same call quantises them); DeepSeek's LayerNorm on k_idx is not part of this step."""
     if indexer is not None:
         if indices is not None:
             raise ValueError("indexer and indices exclude each other: the step selects the lists, or the caller supplies them")

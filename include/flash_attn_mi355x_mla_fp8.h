@@ -29,7 +29,8 @@
  *
  * The split policy, fa_mi355x_decode_mla_splits / _workspace_bytes and their sparse forms answer for these calls too.
  *
- * Not built: fp8 index keys for the indexer, fp8 queries or fp8 MFMAs, e5m2, scales that are not powers of two, other tile widths
+ * (FP8 index keys for the indexer: flash_attn_mi355x_mla_indexer_fp8.h.)
+ * Not built: fp8 queries or fp8 MFMAs for the attention itself, e5m2, scales that are not powers of two, other tile widths
  * than 128, a window, sink or cap, an extend kernel.
  */
 #ifndef FLASH_ATTN_MI355X_MLA_FP8_H

@@ -27,7 +27,8 @@
  * (b, i) row, a radix select over the order-preserving image of the score in three histogram passes (LDS bins), then a compaction by
  * prefix sums in two more.  mla_index_append_kernel: 16-byte moves.
  *
- * Not built: fp8 index keys, a fused score + select launch, index dims other than 128, an indexer for prefill / extend, training.
+ * FP8 index keys: flash_attn_mi355x_mla_indexer_fp8.h, the same calls on 144-byte rows.
+ * Not built: a fused score + select launch, index dims other than 128, an indexer for prefill / extend, training.
  */
 #ifndef FLASH_ATTN_MI355X_MLA_INDEXER_H
 #define FLASH_ATTN_MI355X_MLA_INDEXER_H
